@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """bench.py - MPC control steps/sec of the SVGD-MPC inner loop on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]   (N>1: launched by torch.distributed.run, one rank per GPU)
+
+A plain run times the headline workload and nothing else: set-up, warm-up, the K timed steps, the outputs (--dump-outputs) and the
+JSON line.  --full adds every other leg described below (the cfg4 point of the scaling curve, the roofline legs, the CPU baseline,
+the closed loops; for N > 1 the all-gather probe, the one-GPU and the weak-scaled figures); without it their fields are null.
+
+--dump-outputs DIR: after the timed steps, what the last timed step computed goes to DIR/<name>.npy (float32): the chosen action
+sequence `a_seq` [H, da] and the particle weights `p_weights` [N] a caller of the tick receives (the last timed step fetches them,
+the others do not), and the particle set `theta` [N, H, da] the step left.  The timed context runs exactly max(W, 2000) warm-up
+ticks and the K timed ones from seeded inputs, so two runs with the same arguments compute the same ticks, build against build.
 
 N = 1 (the contract's workload): BASELINE.json configs[1] - Pendulum, 1024 Stein particles, S=128 action samples, M=1, H=30,
 5 SVGD iterations per tick, gpytorch-RBF ("K1") kernel, SGD lr 2, fp32, synthetic seeded inputs resident in HBM.  One "step" =
@@ -18,17 +27,19 @@ iteration per tick - sharded over the N ranks by particle index (strong scaling:
 RCCL all-gathers of DESIGN.md section 6; `value` = joint ticks/s.  `weak_cfg2` carries the round-1 weak-scaled figure
 (1024 Pendulum particles per GPU) as a secondary field when --weak is given.
 
-Warm-up: the W warm-up ticks are run, and then more of them until 1 s has passed (`warmup_ticks_run` says how many): the
-chip's clock needs load to settle - after the idle seconds of process start-up, 20 timed ticks take 137 us each behind 0.1 s of
-ticks and 126 us behind 0.3 s or more, whatever the kernel (tools/coldstart.py, tools/bench_timing_probe.py) - and the driver's
-W = 5 ticks are 0.6 ms.  The K timed ticks are exactly K (garbage collection off between the two clock readings).  torch's HIP context is created before the warm-up (its lazy creation
+Warm-up: the chip's clock needs load to settle - after the idle seconds of process start-up, 20 timed ticks take 137 us each behind
+0.1 s of ticks and 126 us behind 0.3 s or more, whatever the kernel (tools/coldstart.py, tools/bench_timing_probe.py) - and the
+driver's W = 5 ticks are 0.6 ms.  So a twin context of the same workload ticks for at least W ticks and 1 s first and is closed; the
+timed context then runs max(W, 2000) warm-up ticks and the K timed ones (20 timed ticks behind only 5 ticks of their own context
+read 2.7 us per tick above those behind 2000; 10 000 read no better).  A tick's outputs depend on every tick its context ran
+before it, which is why the time-bounded part of the warm-up runs on the twin (`warmup_ticks_run` counts both).  The K timed ticks are exactly K (garbage collection off between the two clock readings).  torch's HIP context is created before the warm-up (its lazy creation
 inside the first torch.cuda.synchronize() stalled the 20 ticks behind it for 37 ms).
 
-`scale_workload` (every line, N = 1 included): BASELINE.json configs[3] (Particle N=16384, S=64, M=4, H=40, 1 iteration) on the
+`scale_workload` (every N > 1 line; N = 1: with --full): BASELINE.json configs[3] (Particle N=16384, S=64, M=4, H=40, 1 iteration) on the
 N GPUs of the run - ticks/s, ms per tick and, for N > 1, the tick's all-gathers timed alone (comm_us_per_tick) - so that
 value(N) / value(1) can be formed on ONE workload from the driver's lines: scale_workload.ticks_per_s.
 
-Extra objects in the JSON line (tier contract):
+Extra objects in the JSON line (tier contract; --full only):
   roofline      top level: the TIMED kernel (svmpc_tick2_kernel, one launch = one control tick): SURVEY 8d algorithmic bytes over the
                 measured tick (`achieved` GB/s, `hbm_frac`) and what actually bounds it - VALU issue and hand-off latency (`frac` =
                 issue floor / measured, from the committed SQ_INSTS_VALU pass).  `rollout_kernel`: the rollout kernel in its HBM-BOUND
@@ -129,6 +140,13 @@ def profile_json(name, family=None):
             return j, rel
         return None, "%s was measured on other kernel sources (stamp %s, now %s): traffic not reported" % (rel, j.get("source_stamp"), srcstamp.stamp(family))
     return None, "no committed summary"
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: one float32 DIR/<name>.npy per array."""
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, np.float32))
 
 
 def cpu_model():
@@ -324,7 +342,16 @@ def main():
                     help="N=1: the timed open-loop leg and nothing else on the GPU (no cfg4 leg, no roofline legs, no closed loops, no CPU baseline): "
                          "under rocprofv3 the svmpc_tick2_kernel row is then the timed kernel alone (VERDICT r5 item 3)")
     ap.add_argument("--weak", action="store_true", help="N>1: also time the weak-scaled cfg2 form (1024 Pendulum particles per GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg besides the timed one (cfg4 point, roofline, CPU baseline, closed loops; N>1: all-gather probe, "
+                         "one-GPU and weak-scaled figures); a plain run times the headline workload alone")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:  # a plain run: the timed leg alone
+        args.open_loop_only = True
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -385,16 +412,22 @@ def main():
             sync()
         return n
 
-    def timed(tick, sync):
-        n_w = warm(tick, sync, args.warmup)
+    last_out = {}
+
+    def timed(tick, sync, n_warm=None, warm_s=None, last=None):
+        """(seconds of the K timed ticks, warm-up ticks run).  `last`: the call that makes the last timed tick (one that fetches its
+        outputs); its result lands in last_out["result"]."""
+        n_w = warm(tick, sync, args.warmup if n_warm is None else n_warm, warm_s)
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
         gc_was = gc.isenabled()
         gc.disable()  # (a collection inside a 2 ms region is a 5-10 % error; timeit does the same)
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(args.steps - (last is not None)):
             tick()
+        if last is not None:
+            last_out["result"] = last()
         t_enq = time.perf_counter()
         torch.cuda.synchronize()  # (a device-wide wait: it covers the context's own stream - no separate stream synchronisation in front of it)
         if dist is not None:
@@ -411,6 +444,8 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
         return el, n_w
+
+    TIMED_CONTEXT_WARM = 2000  # warm-up ticks of the timed context itself (module docstring: Warm-up)
 
     w = WORKLOAD
     state = np.array([3.0, 0.0], np.float32)
@@ -471,21 +506,42 @@ def main():
         if rank == 0 and not args.no_cpu_baseline:
             cpu = cpu_baseline()
         mu, theta = synth(w["N"], w["H"], 1)
-        ctx = Context(model=w["model"], N=w["N"], S=w["S"], M=1, H=w["H"], kernel=w["kernel"], lr=w["lr"], alpha=w["alpha"],
-                      sigma_a=w["sigma_a"], sigma_p=w["sigma_p"], device=local, seed=1234)
-        ctx.set_theta(theta)
-        ctx.set_prior(mu)
-        ctx.set_a_mat(theta)
+
+        def seeded_context():
+            c = Context(model=w["model"], N=w["N"], S=w["S"], M=1, H=w["H"], kernel=w["kernel"], lr=w["lr"], alpha=w["alpha"],
+                        sigma_a=w["sigma_a"], sigma_p=w["sigma_p"], device=local, seed=1234)
+            c.set_theta(theta)
+            c.set_prior(mu)
+            c.set_a_mat(theta)
+            return c
+
+        def tick_of(c):
+            return lambda: c.svmpc_tick(state, w["n_iters"], want_outputs=False)
+
+        ctx = None
         for attempt in range(3):
+            if ctx is not None:
+                ctx.close()
+            # the timed context is made first, so that closing the twin is the only pause between the clock warm-up and its ticks; the
+            # twin is closed before those: with two contexts alive the library chains their launches across streams
+            ctx = seeded_context()
+            twin = seeded_context()
+            n_clock = warm(tick_of(twin), twin.sync, args.warmup)
+            twin.close()
             rep0 = ctx.tick_stats()["replayed"]
-            el, n_warm = timed(lambda: ctx.svmpc_tick(state, w["n_iters"], want_outputs=False), ctx.sync)
+            el, n_warm = timed(tick_of(ctx), ctx.sync, n_warm=max(args.warmup, TIMED_CONTEXT_WARM), warm_s=0.0,
+                               last=(lambda: ctx.svmpc_tick(state, w["n_iters"])) if args.dump_outputs else None)
             replayed_in_region = ctx.tick_stats()["replayed"] - rep0
             if replayed_in_region == 0:  # (a replay is executed by sync(), outside the clock: such a run is not a measurement)
                 break
+        if args.dump_outputs:
+            a_seq, p_weights = last_out["result"]
+            dump_outputs(args.dump_outputs, dict(a_seq=a_seq, p_weights=p_weights, theta=ctx.get_theta()))
         extra["replayed_in_timed_region"] = replayed_in_region
         if replayed_in_region:
             extra["invalid"] = "ticks of the timed region were replayed outside it in all 3 attempts (device shared?): value is not a measurement"
-        extra["warmup_ticks_run"] = n_warm
+        extra["warmup_ticks_run"] = n_clock + n_warm
+        extra["warmup_ticks_on_timed_context"] = n_warm
         extra["tick_paths"] = ctx.tick_stats()  # which kernel served the ticks (tick2 = owner-computes one-launch tick)
         # closed loop (simulations.py:104-123): optimize + forward -> chosen sequence -> its first action steps the plant -> next tick
         def closed_loop(serve):
@@ -535,9 +591,16 @@ def main():
         st4 = np.array([-9.0, -9.0, 0.0, 0.0], np.float32)
         sh = ShardedSVMPC(common, rank, n_gpus, dist)
         sh.set_state(theta, mu)
-        el, n_warm = timed(lambda: sh.tick(st4, c4["n_iters"], params=params), sh.sync)
+        el, n_warm = timed(lambda: sh.tick(st4, c4["n_iters"], params=params), sh.sync,
+                           last=(lambda: sh.tick(st4, c4["n_iters"], params=params, want_outputs=True)) if args.dump_outputs else None)
         extra["warmup_ticks_run"] = n_warm
-        comm_us = sh.ctx.comm_probe(c4["n_iters"], 50) if sh.c_side else None  # the tick's all-gathers alone (collective: every rank)
+        if args.dump_outputs:  # (the library-form run: the peer-form trial below runs on the same contexts, and only when it sets up)
+            a_seq, p_weights = last_out["result"]
+            th_all = sh.ctx.get_theta()
+            if rank == 0:
+                dump_outputs(args.dump_outputs, dict(a_seq=a_seq, p_weights=p_weights, theta=th_all))
+        # the tick's all-gathers alone (collective: every rank)
+        comm_us = sh.ctx.comm_probe(c4["n_iters"], 50) if sh.c_side and args.full else None
         extra["scale_workload"] = dict(workload="Particle N=16384, S=64, M=4, H=40, 1 SVGD iter, K1, SGD, device Philox noise (BASELINE configs[3])",
                                        n_gpus=n_gpus, ticks_per_s=args.steps / el, ms_per_tick=1e3 * el / args.steps, comm_us_per_tick=comm_us,
                                        ticks=args.steps, warmup_ticks_run=n_warm, pairwise_units_left_out=far_shares(sh.ctx))
@@ -595,7 +658,7 @@ def main():
             extra["scale_workload"]["peer_gather"] = peer
         # the SAME joint problem on ONE GPU (unsharded context, rank 0, outside the timed region; the other ranks wait): the figure a
         # strong-scaling efficiency of this line has to be computed against - `python bench.py --gpus 1` runs cfg2, not this
-        if rank == 0 and (n_gpus > 1 or os.environ.get("DUST_BENCH_FORCE_DIST")):
+        if rank == 0 and args.full and (n_gpus > 1 or os.environ.get("DUST_BENCH_FORCE_DIST")):
             one = Context(**dict(common))
             one.set_theta(theta); one.set_prior(mu); one.set_a_mat(theta)
             # (the same number of warm-up and timed ticks as the sharded run: the particle set - and with it the share of exactly-zero
@@ -615,37 +678,38 @@ def main():
         # WEAK scaling in the particle count (north_star: "particle scaling"): 2048 particles PER GPU of the same Particle workload - at 8
         # GPUs this is configs[3] itself - against 2048 particles on one GPU (rank 0, unsharded, outside the timed region).  The pairwise
         # work per rank grows with the joint set (n_local x N pairs), so this is not free scaling either.
-        try:
-            n_w = 2048 * n_gpus
-            if n_w != c4["N"] or n_gpus == 1:
-                muw, thw = synth(n_w, c4["H"], 2, spread=1.0)
-                shw = ShardedSVMPC(dict(common, N=n_w), rank, n_gpus, dist)
-                shw.set_state(thw, muw)
-                elw, _ = timed(lambda: shw.tick(st4, c4["n_iters"], params=params), shw.sync)
-                tps_w = args.steps / elw
-                shw.ctx.close()
-            else:
-                tps_w = args.steps / el
-            one_w = None
-            if rank == 0:
-                mu1, th1 = synth(2048, c4["H"], 2, spread=1.0)
-                o1 = Context(**dict(common, N=2048))
-                o1.set_theta(th1); o1.set_prior(mu1); o1.set_a_mat(th1)
-                for _ in range(40):
-                    o1.svmpc_tick(st4, c4["n_iters"], params=params, want_outputs=False)
-                o1.sync()
-                t1 = time.perf_counter()
-                for _ in range(args.steps):
-                    o1.svmpc_tick(st4, c4["n_iters"], params=params, want_outputs=False)
-                o1.sync()
-                one_w = args.steps / (time.perf_counter() - t1)
-                o1.close()
-            dist.barrier()
-            extra["weak_workload"] = dict(workload="Particle, 2048 particles per GPU (N = %d), S=64, M=4, H=40, 1 SVGD iter, K1" % n_w, n_particles_total=n_w,
-                                          ticks_per_s=tps_w, one_gpu_2048_particles_ticks_per_s=one_w,
-                                          particle_throughput_vs_one_gpu=(tps_w * n_w / (one_w * 2048.0)) if one_w else None)
-        except Exception as e:  # noqa: BLE001
-            extra["weak_workload"] = dict(error=str(e)[:300])
+        if args.full:
+            try:
+                n_w = 2048 * n_gpus
+                if n_w != c4["N"] or n_gpus == 1:
+                    muw, thw = synth(n_w, c4["H"], 2, spread=1.0)
+                    shw = ShardedSVMPC(dict(common, N=n_w), rank, n_gpus, dist)
+                    shw.set_state(thw, muw)
+                    elw, _ = timed(lambda: shw.tick(st4, c4["n_iters"], params=params), shw.sync)
+                    tps_w = args.steps / elw
+                    shw.ctx.close()
+                else:
+                    tps_w = args.steps / el
+                one_w = None
+                if rank == 0:
+                    mu1, th1 = synth(2048, c4["H"], 2, spread=1.0)
+                    o1 = Context(**dict(common, N=2048))
+                    o1.set_theta(th1); o1.set_prior(mu1); o1.set_a_mat(th1)
+                    for _ in range(40):
+                        o1.svmpc_tick(st4, c4["n_iters"], params=params, want_outputs=False)
+                    o1.sync()
+                    t1 = time.perf_counter()
+                    for _ in range(args.steps):
+                        o1.svmpc_tick(st4, c4["n_iters"], params=params, want_outputs=False)
+                    o1.sync()
+                    one_w = args.steps / (time.perf_counter() - t1)
+                    o1.close()
+                dist.barrier()
+                extra["weak_workload"] = dict(workload="Particle, 2048 particles per GPU (N = %d), S=64, M=4, H=40, 1 SVGD iter, K1" % n_w, n_particles_total=n_w,
+                                              ticks_per_s=tps_w, one_gpu_2048_particles_ticks_per_s=one_w,
+                                              particle_throughput_vs_one_gpu=(tps_w * n_w / (one_w * 2048.0)) if one_w else None)
+            except Exception as e:  # noqa: BLE001
+                extra["weak_workload"] = dict(error=str(e)[:300])
         if args.weak:
             n_tot = w["N"] * n_gpus
             mu2, th2 = synth(n_tot, w["H"], 1)

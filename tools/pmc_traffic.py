@@ -1,8 +1,8 @@
 """Per-launch HBM traffic of one kernel from two rocprofv3 PMC passes (FETCH_SIZE and WRITE_SIZE cannot share a pass).
 
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_fetch -- python3 bench.py --no-cpu-baseline
-  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_write -- python3 bench.py --no-cpu-baseline
-  python tools/pmc_traffic.py gpurun_out/pmc_fetch gpurun_out/pmc_write rollout_stream_kernel profiles/round1_rollout_traffic.json
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d out/pmc_fetch -- python3 bench.py --full --no-cpu-baseline
+  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d out/pmc_write -- python3 bench.py --full --no-cpu-baseline
+  python tools/pmc_traffic.py out/pmc_fetch out/pmc_write rollout_stream_kernel profiles/round1_rollout_traffic.json
 
 Units and corrections (MI355X_MICROARCH.md, HBM section): both counters are in KiB; on gfx950 FETCH_SIZE tallies 128-byte
 requests at 64 bytes, so it is doubled (checked against this repo's own kernels: the Stein pass reads theta + score once per
