@@ -16,7 +16,8 @@ MODEL_PENDULUM, MODEL_PARTICLE, MODEL_SKID_STEER = 0, 1, 2
 COST_PENDULUM_QUADCOS, COST_PARTICLE_DEFAULT, COST_QUADRATIC = 0, 1, 2
 KERNEL_K1_RBF, KERNEL_K2_IIDMP, KERNEL_K2_SHARED, KERNEL_IMQ = 0, 1, 2, 3
 LIK_EXP_UTILITY, LIK_EXPECTED_COST = 0, 1
-OPT_SGD, OPT_ADAM = 0, 1
+OPT_SGD, OPT_ADAM, OPT_RMSPROP, OPT_ADAGRAD = 0, 1, 2, 3
+OPTF_MAXIMIZE, OPTF_NESTEROV, OPTF_AMSGRAD, OPTF_DECOUPLED_WD, OPTF_CENTERED = 1, 2, 4, 8, 16
 ROLL_REPEAT, ROLL_MEAN, ROLL_RESAMPLE = 0, 1, 2
 STEP_ARGMAX, STEP_AVERAGE, STEP_EXTERNAL = 0, 1, 2
 PARAM_PYFLOAT, PARAM_SAMPLED, PARAM_TENSOR0D = 0, 1, 2
@@ -76,6 +77,11 @@ class MpfConfig(C.Structure):
         ("obs_std", C.c_float), ("lr", C.c_float), ("bw_scale", C.c_float), ("init_bw", C.c_float),
         ("model_cfg", Config),
     ]
+
+
+class OptimConfig(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("flags", C.c_int32)] + [(n, C.c_double) for n in (
+        "lr", "beta1", "beta2", "eps", "weight_decay", "momentum", "dampening", "alpha", "lr_decay", "initial_accumulator_value")]
 
 
 FP = C.POINTER(C.c_float)
@@ -156,6 +162,9 @@ SYMBOLS = {
     "dust_mpf_clone": (C.c_int, [VP, C.POINTER(VP)]),
     "dust_set_k2_bandwidth": (C.c_int, [VP, C.c_float, C.c_float]),
     "dust_mpf_set_optimizer": (C.c_int, [VP, C.c_int, C.c_float, C.c_float, C.c_float]),
+    "dust_mpf_set_optimizer_ex": (C.c_int, [VP, C.POINTER(OptimConfig)]),
+    "dust_set_optimizer": (C.c_int, [VP, C.POINTER(OptimConfig)]),
+    "dust_get_optimizer": (C.c_int, [VP, C.POINTER(OptimConfig)]),
     "dust_mpf_destroy": (None, [VP]),
     "dust_mpf_optimize": (C.c_int, [VP, FP, FP, C.c_float, C.c_int, FP]),
     "dust_mpf_phi": (C.c_int, [VP, C.c_float, FP]),

@@ -140,6 +140,7 @@ class Context:
         self._h = None
         lib = L.load()
         k2_bw, k2_min = kw.pop("k2_bandwidth", None), kw.pop("k2_minimum_bw", 1e-5)
+        optim = kw.pop("optim", None)  # dust_amd.optim.optimizer_config(...): an optimiser beyond dust_config's plain SGD / Adam
         skid_kw = {k: kw.pop(k) for k in ("x_icr", "wheel_radius", "axial_distance", "goal", "w_quad_state", "w_quad_term", "w_quad_ctrl")
                    if k in kw}
         if _handle is not None:
@@ -169,6 +170,25 @@ class Context:
         # iid_mp(RBF(bandwidth >= 0)): fixed bandwidth instead of the median trick; RBF(minimum_bw=): the clamp of either (base_kernels.py:44-92)
         if (k2_bw is not None and float(k2_bw) >= 0) or (_handle is None and float(k2_min) != 1e-5 and got.kernel in (L.KERNEL_K2_IIDMP, L.KERNEL_K2_SHARED)):
             L.check(lib.dust_set_k2_bandwidth(self._h, float(-1.0 if k2_bw is None else k2_bw), float(k2_min)))
+        if _handle is None and optim is not None:
+            from . import optim as _optim
+
+            if not _optim.is_plain(optim):
+                self.set_optimizer(optim)
+
+    def set_optimizer(self, optim):
+        """dust_set_optimizer: the optimiser of a dict from dust_amd.optim.optimizer_config replaces the context's; its state restarts."""
+        from . import optim as _optim
+
+        L.check(L.load().dust_set_optimizer(self._h, C.byref(_optim.to_struct(optim))))
+
+    def get_optimizer(self):
+        """The context's optimiser as a dict of dust_amd.optim.optimizer_config (dust_get_optimizer)."""
+        from . import optim as _optim
+
+        o = L.OptimConfig()
+        L.check(L.load().dust_get_optimizer(self._h, C.byref(o)))
+        return _optim.from_struct(o)
 
     # ---- lifecycle
     # ---- C-side multi-GPU tick (include/dust_amd.h dust_comm_*): one RCCL communicator per sharded context
@@ -529,7 +549,7 @@ class Context:
 class MpfContext:
     def __init__(self, init_particles, initial_obs, model="pendulum", uncertain_params=("length", "mass"), log_space=False,
                  obs_std=0.1, lr=1e-3, bw_scale=1.0, init_bw=0.1, device=0, grid=None, _handle=None, optimizer="SGD", betas=(0.9, 0.999),
-                 eps=1e-8, **model_kw):
+                 eps=1e-8, optim=None, **model_kw):
         lib = L.load()
         x = _f(init_particles)
         self.Mp, self.P = x.shape
@@ -548,6 +568,11 @@ class MpfContext:
         if grid is not None:
             g = _f(grid)
             L.check(lib.dust_mpf_set_grid(self._h, _p(g), g.shape[0], g.shape[1], float(int(g.shape[0] / 2)), float(int(g.shape[1] / 2))))
+        from . import optim as _optim
+
+        if optim is not None and not _optim.is_plain(optim):  # dust_amd.optim.optimizer_config(...): its state persists as Adam's does
+            L.check(lib.dust_mpf_set_optimizer_ex(self._h, C.byref(_optim.to_struct(optim))))
+            return
         if optimizer not in ("SGD", "Adam"):
             raise NotImplementedError("MPF optimiser %r: the device filter implements SGD and Adam" % (optimizer,))
         if optimizer == "Adam":  # the reference's class default (svgd.py:115); its state persists across optimize() calls

@@ -36,8 +36,8 @@ struct K2Args {
   // optimiser step folded into k2_phi_kernel (apply != 0): what update_from_phi_kernel does in a launch of its own otherwise.  The phi
   // kernel reads the particles through the TRANSPOSED copy only, so the row-major theta may be updated in place while other
   // workgroups are still summing.
-  int apply, optimizer;
-  float lr, beta1, beta2, eps;
+  int apply;
+  OptArgs opt;
   float *theta_rw;      // [N][D] row-major particles (updated in place)
   float *thetaT_out;    // [D][N] or nullptr: the updated particles, transposed, for the NEXT iteration's bandwidth and phi kernels (a second
                         // buffer: this launch's other workgroups still read the current transposed copy) - no transpose launch between iterations
@@ -46,7 +46,7 @@ struct K2Args {
   // other workgroups still read x_rows); theta_out == nullptr: theta_rw is updated in place as described above
   const float *x_rows;
   float *theta_out;
-  float *adam_m, *adam_v;
+  float *opt_s0, *opt_s1, *opt_s2;  // optimiser state slots (handoff.hpp opt_step) or nullptr
   uint32_t *ctr;        // {tick, iter, adam_step}
   unsigned int *fused_cnt;
   int fused_tiles;
@@ -827,14 +827,7 @@ __global__ __launch_bounds__(256) void k2_phi_kernel(const K2Args a) {
         if (a.apply) {  // (update_from_phi_kernel's element)
           float th = a.theta_rw[o];
           const float gr = -phi;
-          if (a.optimizer == DUST_OPT_SGD) {
-            th = fmaf(-a.lr, gr, th);
-          } else {
-            float m = a.adam_m[o], v = a.adam_v[o];
-            th = adam_step(th, gr, m, v, a.lr, a.beta1, a.beta2, a.eps, (float)a.ctr[2]);
-            a.adam_m[o] = m;
-            a.adam_v[o] = v;
-          }
+          th = opt_apply(a.opt, a.opt_s0, a.opt_s1, a.opt_s2, o, th, gr, (float)a.ctr[2]);
           a.theta_rw[o] = th;
           if (a.thetaT_out) a.thetaT_out[(size_t)(c0 + q) * N + i] = th;
         }
@@ -904,14 +897,7 @@ __global__ __launch_bounds__(256) void k2_phi2_kernel(const K2Args a) {
       if (a.apply) {  // (update_from_phi_kernel's element)
         float th = a.theta_rw[o];
         const float gr = -phi;
-        if (a.optimizer == DUST_OPT_SGD) {
-          th = fmaf(-a.lr, gr, th);
-        } else {
-          float m = a.adam_m[o], v = a.adam_v[o];
-          th = adam_step(th, gr, m, v, a.lr, a.beta1, a.beta2, a.eps, (float)a.ctr[2]);
-          a.adam_m[o] = m;
-          a.adam_v[o] = v;
-        }
+        th = opt_apply(a.opt, a.opt_s0, a.opt_s1, a.opt_s2, o, th, gr, (float)a.ctr[2]);
         (a.theta_out ? a.theta_out : a.theta_rw)[o] = th;
         if (a.thetaT_out) a.thetaT_out[(size_t)g * N + i] = th;
       }
@@ -979,14 +965,7 @@ __global__ __launch_bounds__(1024) void k2_phi3_kernel(const K2Args a) {
       if (a.apply) {  // (update_from_phi_kernel's element)
         float th = a.theta_rw[o];
         const float gr = -phi;
-        if (a.optimizer == DUST_OPT_SGD) {
-          th = fmaf(-a.lr, gr, th);
-        } else {
-          float m = a.adam_m[o], v = a.adam_v[o];
-          th = adam_step(th, gr, m, v, a.lr, a.beta1, a.beta2, a.eps, (float)a.ctr[2]);
-          a.adam_m[o] = m;
-          a.adam_v[o] = v;
-        }
+        th = opt_apply(a.opt, a.opt_s0, a.opt_s1, a.opt_s2, o, th, gr, (float)a.ctr[2]);
         (a.theta_out ? a.theta_out : a.theta_rw)[o] = th;
         if (a.thetaT_out) a.thetaT_out[(size_t)g * N + i] = th;
       }

@@ -109,7 +109,8 @@ struct dust_ctx {
   // per-iteration products
   float *costsT, *omegaT, *grad_lik, *grad_pri, *score, *phi, *logl, *logp, *lw, *pw, *a_seq_out, *bw;
   int *istar;
-  float *adam_m, *adam_v;
+  dust_optim_config opt;             // the optimiser (dust_config's plain SGD / Adam until dust_set_optimizer)
+  float *opt_s0, *opt_s1, *opt_s2;   // its state slots [N][D] (handoff.hpp opt_step) or nullptr
   float *pA, *pB, *pM, *pL;  // slice partials of the tiled pairwise passes
   size_t pA_cap, pB_cap, pM_cap, pL_cap;
   float *pS;                 // Gram x score partials of the one-launch iteration (pA still holds the prior's while its Stein tiles run)
@@ -357,6 +358,73 @@ static int ensure(float **p, size_t *cap, size_t n) {
   return DUST_OK;
 }
 
+// ---- optimiser (dust_set_optimizer, dust_mpf_set_optimizer_ex): the checks torch's constructors make, the state slots in use, restart
+static dust_optim_config optim_plain(int kind, float lr, float beta1, float beta2, float eps) {
+  dust_optim_config o;
+  memset(&o, 0, sizeof o);
+  o.kind = kind;
+  o.lr = lr;
+  o.beta1 = beta1;
+  o.beta2 = beta2;
+  o.eps = eps;
+  return o;
+}
+static int validate_optim(const dust_optim_config *o) {
+  if (!o) return fail(DUST_ERR_INVALID, "null optimiser config");
+  static const int allowed[4] = {DUST_OPTF_MAXIMIZE | DUST_OPTF_NESTEROV, DUST_OPTF_MAXIMIZE | DUST_OPTF_AMSGRAD | DUST_OPTF_DECOUPLED_WD,
+                                 DUST_OPTF_MAXIMIZE | DUST_OPTF_CENTERED, DUST_OPTF_MAXIMIZE};
+  if (o->kind < DUST_OPT_SGD || o->kind > DUST_OPT_ADAGRAD)
+    return fail(DUST_ERR_UNSUPPORTED, "optimiser kind %d: the device implements SGD, Adam / AdamW, RMSprop and Adagrad", o->kind);
+  if (o->flags & ~allowed[o->kind]) return fail(DUST_ERR_UNSUPPORTED, "optimiser flags 0x%x do not belong to optimiser kind %d", o->flags, o->kind);
+  const double v[] = {o->lr, o->beta1, o->beta2, o->eps, o->weight_decay, o->momentum, o->dampening, o->alpha, o->lr_decay, o->initial_accumulator_value};
+  for (double x : v)
+    if (!std::isfinite(x)) return fail(DUST_ERR_INVALID, "optimiser options must be finite");
+  if (o->lr < 0.0) return fail(DUST_ERR_INVALID, "Invalid learning rate: %g", o->lr);
+  if (o->weight_decay < 0.0) return fail(DUST_ERR_INVALID, "Invalid weight_decay value: %g", o->weight_decay);
+  if (o->eps < 0.0) return fail(DUST_ERR_INVALID, "Invalid epsilon value: %g", o->eps);
+  if (o->momentum < 0.0) return fail(DUST_ERR_INVALID, "Invalid momentum value: %g", o->momentum);
+  if (o->kind == DUST_OPT_SGD && (o->flags & DUST_OPTF_NESTEROV) && (o->momentum <= 0.0 || o->dampening != 0.0))
+    return fail(DUST_ERR_INVALID, "Nesterov momentum requires a momentum and zero dampening");
+  if (o->kind == DUST_OPT_ADAM && !(o->beta1 >= 0.0 && o->beta1 < 1.0 && o->beta2 >= 0.0 && o->beta2 < 1.0))
+    return fail(DUST_ERR_INVALID, "Invalid beta parameters: (%g, %g)", o->beta1, o->beta2);
+  if (o->kind == DUST_OPT_RMSPROP && o->alpha < 0.0) return fail(DUST_ERR_INVALID, "Invalid alpha value: %g", o->alpha);
+  if (o->kind == DUST_OPT_ADAGRAD && (o->lr_decay < 0.0 || o->initial_accumulator_value < 0.0))
+    return fail(DUST_ERR_INVALID, "Invalid lr_decay / initial_accumulator_value: %g / %g", o->lr_decay, o->initial_accumulator_value);
+  return DUST_OK;
+}
+// bit k: state slot k is in use (handoff.hpp opt_step)
+static unsigned optim_slots(const dust_optim_config &o) {
+  switch (o.kind) {
+    case DUST_OPT_SGD: return o.momentum != 0.0 ? 1u : 0u;
+    case DUST_OPT_ADAM: return 3u | ((o.flags & DUST_OPTF_AMSGRAD) ? 4u : 0u);
+    case DUST_OPT_RMSPROP: return 1u | (o.momentum > 0.0 ? 2u : 0u) | ((o.flags & DUST_OPTF_CENTERED) ? 4u : 0u);
+    default: return 1u;
+  }
+}
+// (re)allocates exactly the slots `o` uses (n floats each; an unused slot is null, which the kernels read as "not in use")
+static int optim_slots_alloc(const dust_optim_config &o, float *s[3], size_t n) {
+  const unsigned m = optim_slots(o);
+  for (int k = 0; k < 3; ++k) {
+    if ((m >> k) & 1u) {
+      if (!s[k]) TRY(dalloc(&s[k], n));
+    } else if (s[k]) {
+      HIP_TRY(hipFree(s[k]));
+      s[k] = nullptr;
+    }
+  }
+  return DUST_OK;
+}
+// the state a fresh torch optimiser starts with: slot 0 at opt_restart_s0 (Adagrad's initial_accumulator_value), the others at zero
+static int optim_restart(const dust_optim_config &o, float *const s[3], size_t n, hipStream_t st) {
+  const float v0 = opt_restart_s0(o);
+  uint32_t bits;
+  memcpy(&bits, &v0, 4);
+  if (s[0]) HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s[0]), (int)bits, n, st));
+  for (int k = 1; k < 3; ++k)
+    if (s[k]) HIP_TRY(hipMemsetAsync(s[k], 0, n * sizeof(float), st));
+  return DUST_OK;
+}
+
 struct Prof {
   dust_ctx *c;
   int id;
@@ -422,7 +490,7 @@ static void free_all(dust_ctx *c) {
   // {theta, theta_alt} are always the two particle buffers, whichever is current
   float **fp[] = {&c->theta, &c->theta_alt, &c->thetaT, &c->thetaT_alt, &c->mu, &c->muT, &c->logmix, &c->mixw, &c->a_mat, &c->a_seq, &c->a_mix, &c->eta,
                   &c->costsT, &c->omegaT, &c->grad_lik, &c->grad_pri, &c->score, &c->phi, &c->logl, &c->logp, &c->lw,
-                  &c->outblk, &c->bw, &c->adam_m, &c->adam_v, &c->noise_stage, &c->actions, &c->states, &c->params_dev,
+                  &c->outblk, &c->bw, &c->opt_s0, &c->opt_s1, &c->opt_s2, &c->noise_stage, &c->actions, &c->states, &c->params_dev,
                   &c->state_dev, &c->tmp, &c->costs_stage, &c->tile_scratch, &c->wg_flags, &c->pA, &c->pB, &c->pM, &c->pL, &c->pS, &c->xpad, &c->kmat, &c->pk_idx, &c->pk_uoff, &c->pk_uq, &c->pk_soff, &c->pk_goff, &c->pk_nzu, &c->pk_perm, &c->pk_lead, &c->lp_idx, &c->lp_uoff, &c->lp_uq, &c->lp_soff, &c->lp_goff, &c->far_z, &c->far_n, &c->far_f, &c->far_g, &c->far_q, &c->far_cnt, &c->mw_dev, &c->cz_dev, &c->theta_w, &c->mu_w};
   for (auto p : fp)
     if (*p) (void)hipFree(*p);
@@ -711,11 +779,14 @@ static int create_impl(const dust_config *cfg, dust_ctx **out) {
   TRY(dalloc(&c->istar, (size_t)1));
   TRY(dalloc(&c->ctr_dev, (size_t)4));
   HIP_TRY(hipMemsetAsync(c->ctr_dev, 0, 4 * sizeof(uint32_t), c->stream));
-  if (cfg->optimizer == DUST_OPT_ADAM) {
-    TRY(dalloc(&c->adam_m, ND));
-    TRY(dalloc(&c->adam_v, ND));
-    HIP_TRY(hipMemsetAsync(c->adam_m, 0, ND * sizeof(float), c->stream));
-    HIP_TRY(hipMemsetAsync(c->adam_v, 0, ND * sizeof(float), c->stream));
+  c->opt = optim_plain(cfg->optimizer, cfg->lr, cfg->adam_beta1, cfg->adam_beta2, cfg->adam_eps);
+  {
+    float *slots[3] = {nullptr, nullptr, nullptr};
+    TRY(optim_slots_alloc(c->opt, slots, ND));
+    c->opt_s0 = slots[0];
+    c->opt_s1 = slots[1];
+    c->opt_s2 = slots[2];
+    TRY(optim_restart(c->opt, slots, ND, c->stream));
   }
   // a_mix starts as ones (disco.py:110); uniform prior weights until set_prior
   std::vector<float> ones((size_t)c->N, 1.0f);
@@ -893,9 +964,12 @@ extern "C" int dust_clone(const dust_ctx *src, dust_ctx **out) {
             {c->logmix, src->logmix, Nb}, {c->mixw, src->mixw, Nb}, {c->a_mix, src->a_mix, Nb}, {c->eta, src->eta, Nb},
             {c->logl, src->logl, Nb}, {c->a_seq, src->a_seq, c->D * sizeof(float)}, {c->costsT, src->costsT, SN}};
   for (auto &e : cp) TRY(d2d(c, e.dst, e.s, e.b));
-  if (src->adam_m) {
-    TRY(d2d(c, c->adam_m, src->adam_m, ND));
-    TRY(d2d(c, c->adam_v, src->adam_v, ND));
+  if (memcmp(&src->opt, &c->opt, sizeof c->opt) != 0) TRY(dust_set_optimizer(c, &src->opt));
+  {
+    float *const ds[3] = {c->opt_s0, c->opt_s1, c->opt_s2};
+    const float *const ss[3] = {src->opt_s0, src->opt_s1, src->opt_s2};
+    for (int k = 0; k < 3; ++k)
+      if (ss[k]) TRY(d2d(c, ds[k], ss[k], ND));
   }
   TRY(d2d(c, c->ctr_dev, src->ctr_dev, 4 * sizeof(uint32_t)));
   c->mu_aliased = src->mu_aliased;
@@ -1020,11 +1094,37 @@ extern "C" int dust_set_theta(dust_ctx *c, const float *theta) {
   HIP_TRY(hipSetDevice(c->cfg.device));
   TRY(h2d(c, c->theta, theta, (size_t)c->N * c->D * sizeof(float)));
   c->kmat_valid = false;
-  if (c->adam_m) {
-    HIP_TRY(hipMemsetAsync(c->adam_m, 0, (size_t)c->N * c->D * sizeof(float), c->stream));
-    HIP_TRY(hipMemsetAsync(c->adam_v, 0, (size_t)c->N * c->D * sizeof(float), c->stream));
+  if (c->opt_s0 || c->opt_s1 || c->opt_s2) {  // (a new parameter tensor: the optimiser's state and step count restart)
+    float *const slots[3] = {c->opt_s0, c->opt_s1, c->opt_s2};
+    TRY(optim_restart(c->opt, slots, (size_t)c->N * c->D, c->stream));
     HIP_TRY(hipMemsetAsync(c->ctr_dev + 2, 0, sizeof(uint32_t), c->stream));
   }
+  return DUST_OK;
+}
+
+extern "C" int dust_set_optimizer(dust_ctx *c, const dust_optim_config *opt) {
+  if (!c) return fail(DUST_ERR_INVALID, "null ctx");
+  TRY(validate_optim(opt));
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  TRY(settle_pending(c));
+  const size_t ND = (size_t)c->N * c->D;
+  float *slots[3] = {c->opt_s0, c->opt_s1, c->opt_s2};
+  HIP_TRY(hipStreamSynchronize(c->stream));  // (slots about to be freed may still be read by queued work)
+  TRY(optim_slots_alloc(*opt, slots, ND));
+  c->opt_s0 = slots[0];
+  c->opt_s1 = slots[1];
+  c->opt_s2 = slots[2];
+  c->opt = *opt;
+  TRY(optim_restart(c->opt, slots, ND, c->stream));
+  HIP_TRY(hipMemsetAsync(c->ctr_dev + 2, 0, sizeof(uint32_t), c->stream));
+  if (c->graph_exec || c->graph_exec_alt) graph_drop(c);  // (captured launches carry the optimiser and its slots by value)
+  c->persist_declined = 0;
+  return DUST_OK;
+}
+
+extern "C" int dust_get_optimizer(const dust_ctx *c, dust_optim_config *out) {
+  if (!c || !out) return fail(DUST_ERR_INVALID, "null argument");
+  *out = c->opt;
   return DUST_OK;
 }
 // RBF(bandwidth=, minimum_bw=) base_kernels.py:44-92 for the K2 kernels: bandwidth < 0 = the median trick (default); otherwise
@@ -2670,12 +2770,8 @@ static UpdateArgs update_args(dust_ctx *c, int apply) {
   u.D = c->D;
   u.i0 = c->n0;
   u.n_local = c->nloc;
-  u.optimizer = c->cfg.optimizer;
   u.apply = apply;
-  u.lr = c->cfg.lr;
-  u.beta1 = c->cfg.adam_beta1;
-  u.beta2 = c->cfg.adam_beta2;
-  u.eps = c->cfg.adam_eps;
+  u.opt = c->opt;
   const float ell = c->cfg.kernel == DUST_KERNEL_IMQ ? c->cfg.imq_ell : 0.69314718055994531f;  // softplus(0) = ln 2 (svmpc.py:78 typo keeps it)
   u.inv_l2 = 1.0f / (ell * ell);
   u.inv_n = 1.0f / c->N;
@@ -2685,8 +2781,9 @@ static UpdateArgs update_args(dust_ctx *c, int apply) {
   u.phi = c->phi;
   u.theta = c->theta;
   u.theta_out = c->theta;
-  u.adam_m = c->adam_m;
-  u.adam_v = c->adam_v;
+  u.opt_s0 = c->opt_s0;
+  u.opt_s1 = c->opt_s1;
+  u.opt_s2 = c->opt_s2;
   u.ctr = c->ctr_dev;
   u.fused_cnt = c->fused_cnt;
   u.fused_tiles = c->fused_cnt ? c->fused_tiles : 0;
@@ -2739,14 +2836,11 @@ static int launch_stein_update(dust_ctx *c, int apply, bool in_loop = false /* K
       if (apply) {  // the optimiser step rides in the phi kernel (no update_from_phi launch)
         const UpdateArgs u = update_args(c, 1);
         kp.apply = 1;
-        kp.optimizer = u.optimizer;
-        kp.lr = u.lr;
-        kp.beta1 = u.beta1;
-        kp.beta2 = u.beta2;
-        kp.eps = u.eps;
+        kp.opt = u.opt;
         kp.theta_rw = u.theta;
-        kp.adam_m = u.adam_m;
-        kp.adam_v = u.adam_v;
+        kp.opt_s0 = u.opt_s0;
+        kp.opt_s1 = u.opt_s1;
+        kp.opt_s2 = u.opt_s2;
         kp.ctr = u.ctr;
         kp.fused_cnt = u.fused_cnt;
         kp.fused_tiles = u.fused_tiles;
@@ -3214,8 +3308,10 @@ static RollArgs roll_args(dust_ctx *c, int steps, int strategy, const float *las
   r.i0 = c->n0;
   r.n_local = c->nloc;
   r.ctr = c->ctr_dev;
-  r.adam_m = c->adam_m;
-  r.adam_v = c->adam_v;
+  r.opt_s0 = c->opt_s0;
+  r.opt_s1 = c->opt_s1;
+  r.opt_s2 = c->opt_s2;
+  r.s0_restart = opt_restart_s0(c->opt);
   if (c->iter_cnt) {
     r.rearm = c->iter_cnt;
     r.rearm_lines = 2 * (2 * c->iter_tiles + c->iter_js);
@@ -3428,7 +3524,6 @@ static int launch_tick2(dust_ctx *c, const float *state, int n_steps, const floa
   f.lik = ra.lik;
   f.update_a_mat = 1;
   f.eps_base_mode = ra.eps_base_mode;
-  f.optimizer = c->cfg.optimizer;
   f.roll_strategy = c->cfg.roll_strategy;
   f.weighted_prior = c->cfg.weighted_prior;
   f.coef_given = ra.coef_given;
@@ -3490,10 +3585,7 @@ static int launch_tick2(dust_ctx *c, const float *state, int n_steps, const floa
     const UpdateArgs ua = update_args(c, 1);
     f.inv_l2 = ua.inv_l2;
     f.inv_n = ua.inv_n;
-    f.lr = ua.lr;
-    f.beta1 = ua.beta1;
-    f.beta2 = ua.beta2;
-    f.adam_eps = ua.eps;
+    f.opt = ua.opt;
     const PriorMerge pm = prior_merge_args(c);
     f.log_norm = pm.log_norm;
   }
@@ -3511,8 +3603,9 @@ static int launch_tick2(dust_ctx *c, const float *state, int n_steps, const floa
   f.logmix = c->logmix;
   f.mixw = c->mixw;
   f.a_mat = c->a_mat;
-  f.adam_m = c->adam_m;
-  f.adam_v = c->adam_v;
+  f.opt_s0 = c->opt_s0;
+  f.opt_s1 = c->opt_s1;
+  f.opt_s2 = c->opt_s2;
   f.costsT = c->costsT;
   f.grad_lik = c->grad_lik;
   f.grad_pri = c->grad_pri;

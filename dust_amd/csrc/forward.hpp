@@ -186,7 +186,8 @@ struct RollArgs {
   int hs_n;             // filled with the sentinel again
   // SVMPC.roll builds a NEW parameter tensor (theta.roll(...), svmpc.py:142-158) and stores it into the optimiser's param group:
   // torch keys optimiser state by tensor object, so Adam's exp_avg / exp_avg_sq / step restart at zero after every forward()
-  float *adam_m, *adam_v;  // [N][D] or nullptr (SGD)
+  float *opt_s0, *opt_s1, *opt_s2;  // optimiser state slots [N][D] or nullptr (plain SGD: none)
+  float s0_restart;                  // the value slot 0 restarts at (handoff.hpp opt_restart_s0)
   int steps;               // theta.roll(steps, dims=-2): circular shift along the horizon (svmpc.py:144); -1 in SVMPC.forward's default
   const float *last_row;   // [N][da] strategy "resample": the last action of a fresh prior sample per particle (svmpc.py:148-150)
 };
@@ -224,10 +225,9 @@ __global__ __launch_bounds__(128) void roll_kernel(const RollArgs a) {
   wg_sync();
   if (j < D) {
     a.theta_dst[(size_t)i * D + j] = out;
-    if (a.adam_m) {
-      a.adam_m[(size_t)i * D + j] = 0.f;
-      a.adam_v[(size_t)i * D + j] = 0.f;
-    }
+    if (a.opt_s0) a.opt_s0[(size_t)i * D + j] = a.s0_restart;
+    if (a.opt_s1) a.opt_s1[(size_t)i * D + j] = 0.f;
+    if (a.opt_s2) a.opt_s2[(size_t)i * D + j] = 0.f;
   }
 }
 
@@ -253,10 +253,9 @@ __global__ __launch_bounds__(1024) void finalize_roll_kernel(const FinalizeArgs 
   const float *th = a.theta + (size_t)i * D;
   if (j < D) {
     a.theta_dst[(size_t)i * D + j] = (j + a.da < D) ? th[j + a.da] : th[j];
-    if (a.adam_m) {
-      a.adam_m[(size_t)i * D + j] = 0.f;
-      a.adam_v[(size_t)i * D + j] = 0.f;
-    }
+    if (a.opt_s0) a.opt_s0[(size_t)i * D + j] = a.s0_restart;
+    if (a.opt_s1) a.opt_s1[(size_t)i * D + j] = 0.f;
+    if (a.opt_s2) a.opt_s2[(size_t)i * D + j] = 0.f;
   }
 }
 

@@ -44,21 +44,85 @@ __device__ __forceinline__ bool spin_until(const unsigned int *p, const unsigned
   return true;
 }
 
-// torch.optim.Adam, single-tensor CPU path (svgd.py:115 is the reference's class default), on grad = -phi: lerp_ for exp_avg
-// (vectorised form: fmadd(w, grad - m, m)), mul_ + addcmul_ for exp_avg_sq ((value * g) * g), bias corrections / step size /
-// sqrt(bias_correction2) as Python floats (double), addcdiv_ as self + (value * m) / denom.  `t` is the 1-based step count
-// since the last roll (the optimiser state restarts at every forward(): forward.hpp RollArgs).
-__device__ __forceinline__ float adam_step(float th, const float g, float &m, float &v, const float lr, const float beta1, const float beta2,
-                                           const float eps, const float t) {
-  const float w1 = (float)(1.0 - (double)beta1), w2 = (float)(1.0 - (double)beta2);
-  const double bc1 = 1.0 - pow((double)beta1, (double)t), bc2 = 1.0 - pow((double)beta2, (double)t);
-  const float value = (float)(-((double)lr / bc1)), bc2s = (float)sqrt(bc2);
-  m = fmaf(w1, g - m, m);
-  v = v * beta2;
-  v = v + (w2 * g) * g;
-  const float denom = sqrtf(v) / bc2s + eps;
-  return th + (value * m) / denom;
+// Any optimiser of dust_set_optimizer (include/dust_amd.h dust_optim_config), one element, on grad `g` = -phi.  Each branch follows
+// the torch function named in it operation by operation, with the vectorised CPU kernels' forms: add(x, alpha=a) = fmadd(a, x, self),
+// addcmul = self + (value * t1) * t2, addcdiv = self + (value * t1) / t2, lerp (weight < 0.5) = fmadd(w, end - self, self).  Python-float
+// scalars are formed in double, then rounded.  State slots (restart values in opt_restart_s0): SGD s0 = momentum_buffer; Adam s0 / s1 /
+// s2 = exp_avg / exp_avg_sq / max_exp_avg_sq; RMSprop s0 / s1 / s2 = square_avg / momentum_buffer / grad_avg; Adagrad s0 = sum.  `t` is
+// the 1-based step count since the state last restarted (the device counter).  With no option set, SGD is `fmaf(-lr, g, th)` and Adam
+// is what the plain kinds of dust_config have always computed.  Limit: Adam's exp_avg.lerp_(grad, 1 - beta1) takes the weight < 0.5 form
+// only (beta1 > 0.5, which covers torch's default 0.9); for beta1 <= 0.5 torch switches to fmadd(w - 1, grad - m, grad), which differs in
+// the last ulp.  (The plain Adam of dust_config has always used this form; keeping it keeps those contexts' bits.)
+using OptArgs = dust_optim_config;
+
+__device__ __forceinline__ float opt_step(const OptArgs &o, float th, float g, float &s0, float &s1, float &s2, const float t) {
+  if (o.flags & DUST_OPTF_MAXIMIZE) g = -g;
+  if (o.kind == DUST_OPT_ADAM) {  // _single_tensor_adam
+    if (o.weight_decay != 0.0) {
+      if (o.flags & DUST_OPTF_DECOUPLED_WD) th = th * (float)(1.0 - o.lr * o.weight_decay);
+      else g = fmaf((float)o.weight_decay, th, g);
+    }
+    // torch.optim.Adam on the single-tensor CPU path: lerp_ for exp_avg, mul_ + addcmul_ for exp_avg_sq, bias corrections / step size /
+    // sqrt(bias_correction2) as Python floats (double), addcdiv_ as self + (value * m) / denom.  A plain Adam of dust_config carries fp32
+    // scalars, which widen exactly: the same bits as before this function served every optimiser.
+    const float w1 = (float)(1.0 - o.beta1), w2 = (float)(1.0 - o.beta2);
+    const double bc1 = 1.0 - pow(o.beta1, (double)t), bc2 = 1.0 - pow(o.beta2, (double)t);
+    const float value = (float)(-(o.lr / bc1)), bc2s = (float)sqrt(bc2);
+    s0 = fmaf(w1, g - s0, s0);
+    s1 = s1 * (float)o.beta2;
+    s1 = s1 + (w2 * g) * g;
+    float vh = s1;
+    if (o.flags & DUST_OPTF_AMSGRAD) vh = s2 = (s1 > s2 || s1 != s1) ? s1 : s2;  // torch.maximum (NaN propagates, unlike fmaxf)
+    const float denom = sqrtf(vh) / bc2s + (float)o.eps;
+    return th + (value * s0) / denom;
+  }
+  if (o.weight_decay != 0.0) g = fmaf((float)o.weight_decay, th, g);  // grad.add(param, alpha=weight_decay)
+  if (o.kind == DUST_OPT_SGD) {  // _single_tensor_sgd
+    if (o.momentum != 0.0) {
+      s0 = t == 1.f ? g : fmaf((float)(1.0 - o.dampening), g, s0 * (float)o.momentum);  // clone(grad) / mul_(momentum).add_(grad, alpha=1 - dampening)
+      g = (o.flags & DUST_OPTF_NESTEROV) ? fmaf((float)o.momentum, s0, g) : s0;
+    }
+    return fmaf(-(float)o.lr, g, th);  // param.add_(grad, alpha=-lr)
+  }
+  if (o.kind == DUST_OPT_RMSPROP) {  // _single_tensor_rmsprop
+    const float wa = (float)(1.0 - o.alpha);
+    s0 = s0 * (float)o.alpha;
+    s0 = s0 + (wa * g) * g;
+    float avg;
+    if (o.flags & DUST_OPTF_CENTERED) {
+      s2 = fabsf(wa) < 0.5f ? fmaf(wa, g - s2, s2) : fmaf(wa - 1.f, g - s2, g);  // grad_avg.lerp_(grad, 1 - alpha), both of torch's forms
+      avg = sqrtf(s0 + (-1.f * s2) * s2);
+    } else {
+      avg = sqrtf(s0);
+    }
+    avg = avg + (float)o.eps;
+    if (o.momentum > 0.0) {
+      s1 = s1 * (float)o.momentum;
+      s1 = s1 + (1.f * g) / avg;
+      return fmaf(-(float)o.lr, s1, th);
+    }
+    return th + (-(float)o.lr * g) / avg;
+  }
+  // DUST_OPT_ADAGRAD: _single_tensor_adagrad
+  const float clr = (float)(o.lr / (1.0 + ((double)t - 1.0) * o.lr_decay));
+  s0 = s0 + (1.f * g) * g;
+  const float std = sqrtf(s0) + (float)o.eps;
+  return th + (-clr * g) / std;
 }
+
+// One element's step with its state in HBM (slots that the optimiser does not use are null and neither read nor written)
+__device__ __forceinline__ float opt_apply(const OptArgs &o, float *s0p, float *s1p, float *s2p, const size_t e, const float th, const float g,
+                                           const float t) {
+  float s0 = s0p ? s0p[e] : 0.f, s1 = s1p ? s1p[e] : 0.f, s2 = s2p ? s2p[e] : 0.f;
+  const float r = opt_step(o, th, g, s0, s1, s2, t);
+  if (s0p) s0p[e] = s0;
+  if (s1p) s1p[e] = s1;
+  if (s2p) s2p[e] = s2;
+  return r;
+}
+
+// the value slot 0 restarts at (Adagrad's initial_accumulator_value; every other slot restarts at zero)
+__host__ __device__ inline float opt_restart_s0(const OptArgs &o) { return o.kind == DUST_OPT_ADAGRAD ? (float)o.initial_accumulator_value : 0.f; }
 
 
 // sin(fl(theta + pi_f)) and cos(theta) from ONE Cody-Waite reduction of theta.  fl(theta + pi_f) = theta + pi + e with

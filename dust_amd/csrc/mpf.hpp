@@ -20,7 +20,7 @@ struct MpfArgs {
   DevModel dm;
   int Mp, P, ds, da, n_steps, log_space, have_past;
   float prior_bwv[4];  // prior bandwidth per parameter dimension (equal after the first update_prior; MPF(bw=None) starts per-dimension)
-  float bw, lr, obs_std;
+  float bw, obs_std;
   float past_obs[4], past_action[2], obs[4];
   // control-channel noise of the one-step prediction (Particle(deterministic=False), particle.py:145-148 reached through
   // likelihoods.py:30-46): `acts` there is the bare action vector, so ONE d_a-vector is drawn per phi() call - i.e. per SVGD step -
@@ -30,10 +30,10 @@ struct MpfArgs {
   float *grad_norms;  // [n_steps] or nullptr
   float *phi_out;     // [Mp][P] or nullptr (phi of the first step, when n_steps == 0 semantics are wanted use n_steps=1, lr=0)
   // optimiser (SVGD.__init__ svgd.py:115: the class default is torch.optim.Adam; built once in MPF.__init__ mpf.py:24, so its
-  // state persists across optimize() calls): DUST_OPT_SGD, or DUST_OPT_ADAM with moments [Mp][P] in / out and t0 steps taken so far
-  int optimizer, t0;
-  float beta1, beta2, eps;
-  float *adam_m, *adam_v;
+  // state persists across optimize() calls): any optimiser of dust_set_optimizer, its state slots [Mp][P] in / out and t0 steps taken so far
+  OptArgs opt;  // handoff.hpp opt_step (the bare phi evaluation: plain SGD, no state)
+  int t0;
+  float *opt_s0, *opt_s1, *opt_s2;  // state slots [Mp][P] or nullptr
 };
 
 // d(next state)/d(params) of one model step, as autograd returns it through model.step (incl. clamp masks).
@@ -128,12 +128,12 @@ __global__ __launch_bounds__(1024) void mpf_optimize_kernel(const MpfArgs a) {
     inv_pbw2[p] = inv_pbw[p] * inv_pbw[p];
   }
   const double inv_bw2 = 1.0 / ((double)a.bw * (double)a.bw), inv_obs2 = 1.0 / ((double)a.obs_std * (double)a.obs_std);
-  float am[4] = {0.f, 0.f, 0.f, 0.f}, av[4] = {0.f, 0.f, 0.f, 0.f};  // Adam moments of this lane's particle (registers for the whole launch)
-  const bool adam = a.optimizer == DUST_OPT_ADAM;
-  if (adam && on && r == 0)
+  float am[4] = {0.f, 0.f, 0.f, 0.f}, av[4] = {0.f, 0.f, 0.f, 0.f}, a2[4] = {0.f, 0.f, 0.f, 0.f};  // optimiser state of this lane's particle (registers for the whole launch)
+  if (on && r == 0)
     _Pragma("unroll") for (int p = 0; p < P; ++p) {
-      am[p] = a.adam_m[i * P + p];
-      av[p] = a.adam_v[i * P + p];
+      if (a.opt_s0) am[p] = a.opt_s0[i * P + p];
+      if (a.opt_s1) av[p] = a.opt_s1[i * P + p];
+      if (a.opt_s2) a2[p] = a.opt_s2[i * P + p];
     }
   for (int it = 0; it < a.n_steps; ++it) {
     float xi[4] = {0.f, 0.f, 0.f, 0.f};
@@ -229,22 +229,18 @@ __global__ __launch_bounds__(1024) void mpf_optimize_kernel(const MpfArgs a) {
     if (on && r == 0 && it == 0 && a.phi_out)
       _Pragma("unroll") for (int p = 0; p < P; ++p) a.phi_out[i * P + p] = ph[p];
     if (on && r == 0) {
-      if (adam) {  // x.grad = -phi; optimizer.step() (mpf.py:59-62), the single-tensor Adam of stein.hpp adam_step
-        _Pragma("unroll") for (int p = 0; p < P; ++p)
-            xs[i * P + p] = adam_step(xi[p], -ph[p], am[p], av[p], a.lr, a.beta1, a.beta2, a.eps, (float)(a.t0 + it + 1));
-      } else {
-        _Pragma("unroll") for (int p = 0; p < P; ++p) xs[i * P + p] = fmaf(a.lr, ph[p], xi[p]);
-      }
+      // x.grad = -phi; optimizer.step() (mpf.py:59-62)
+      _Pragma("unroll") for (int p = 0; p < P; ++p) xs[i * P + p] = opt_step(a.opt, xi[p], -ph[p], am[p], av[p], a2[p], (float)(a.t0 + it + 1));
     }
     wg_sync();
   }
   if (on && r == 0) {
     _Pragma("unroll") for (int p = 0; p < P; ++p) a.x[i * P + p] = xs[i * P + p];
-    if (adam)
-      _Pragma("unroll") for (int p = 0; p < P; ++p) {
-        a.adam_m[i * P + p] = am[p];
-        a.adam_v[i * P + p] = av[p];
-      }
+    _Pragma("unroll") for (int p = 0; p < P; ++p) {
+      if (a.opt_s0) a.opt_s0[i * P + p] = am[p];
+      if (a.opt_s1) a.opt_s1[i * P + p] = av[p];
+      if (a.opt_s2) a.opt_s2[i * P + p] = a2[p];
+    }
   }
 }
 
@@ -345,12 +341,12 @@ __global__ __launch_bounds__(MPF_G_NT) void mpf_optimize_grid_kernel(const MpfGr
     inv_pbw2[p] = inv_pbw[p] * inv_pbw[p];
   }
   const double inv_bw2 = 1.0 / ((double)a.bw * (double)a.bw), inv_obs2 = 1.0 / ((double)a.obs_std * (double)a.obs_std);
-  float am[4] = {0.f, 0.f, 0.f, 0.f}, av[4] = {0.f, 0.f, 0.f, 0.f}, xn[4] = {0.f, 0.f, 0.f, 0.f};
-  const bool adam = a.optimizer == DUST_OPT_ADAM;
-  if (adam && lead)
+  float am[4] = {0.f, 0.f, 0.f, 0.f}, av[4] = {0.f, 0.f, 0.f, 0.f}, a2[4] = {0.f, 0.f, 0.f, 0.f}, xn[4] = {0.f, 0.f, 0.f, 0.f};
+  if (lead)
     _Pragma("unroll") for (int p = 0; p < P; ++p) {
-      am[p] = a.adam_m[i * P + p];
-      av[p] = a.adam_v[i * P + p];
+      if (a.opt_s0) am[p] = a.opt_s0[i * P + p];
+      if (a.opt_s1) av[p] = a.opt_s1[i * P + p];
+      if (a.opt_s2) a2[p] = a.opt_s2[i * P + p];
     }
   // lanes [0, 16) of wave 0 wait for the arrivals of every particle's wave on their shard line
   auto poll = [&](unsigned int *lines, const unsigned int phase) {
@@ -445,7 +441,7 @@ __global__ __launch_bounds__(MPF_G_NT) void mpf_optimize_grid_kernel(const MpfGr
         if (it == 0 && a.phi_out)
           _Pragma("unroll") for (int p = 0; p < P; ++p) a.phi_out[i * P + p] = ph[p];
         _Pragma("unroll") for (int p = 0; p < P; ++p) {
-          xn[p] = adam ? adam_step(xi[p], -ph[p], am[p], av[p], a.lr, a.beta1, a.beta2, a.eps, (float)(a.t0 + it + 1)) : fmaf(a.lr, ph[p], xi[p]);
+          xn[p] = opt_step(a.opt, xi[p], -ph[p], am[p], av[p], a2[p], (float)(a.t0 + it + 1));
           st_sc1(g.xg + ((size_t)((it + 1) & 1) * Mp + i) * P + p, xn[p]);
         }
       }
@@ -476,11 +472,11 @@ __global__ __launch_bounds__(MPF_G_NT) void mpf_optimize_grid_kernel(const MpfGr
   }
   if (lead) {
     _Pragma("unroll") for (int p = 0; p < P; ++p) a.x[i * P + p] = xn[p];
-    if (adam)
-      _Pragma("unroll") for (int p = 0; p < P; ++p) {
-        a.adam_m[i * P + p] = am[p];
-        a.adam_v[i * P + p] = av[p];
-      }
+    _Pragma("unroll") for (int p = 0; p < P; ++p) {
+      if (a.opt_s0) a.opt_s0[i * P + p] = am[p];
+      if (a.opt_s1) a.opt_s1[i * P + p] = av[p];
+      if (a.opt_s2) a.opt_s2[i * P + p] = a2[p];
+    }
   }
   if (b == 0 && a.grad_norms)  // ||phi|| of every step: the per-particle squares in particle order
     for (int it = tid; it < a.n_steps; it += MPF_G_NT) {
@@ -668,12 +664,12 @@ __global__ __launch_bounds__(MPF_G_NT) void mpf_optimize_poll_kernel(const MpfPo
     inv_pbw2[p] = inv_pbw[p] * inv_pbw[p];
   }
   const double inv_bw2 = 1.0 / ((double)a.bw * (double)a.bw);
-  float am[4] = {0.f, 0.f, 0.f, 0.f}, av[4] = {0.f, 0.f, 0.f, 0.f};
-  const bool adam = a.optimizer == DUST_OPT_ADAM;
-  if (adam && on)
+  float am[4] = {0.f, 0.f, 0.f, 0.f}, av[4] = {0.f, 0.f, 0.f, 0.f}, a2[4] = {0.f, 0.f, 0.f, 0.f};
+  if (on)
     _Pragma("unroll") for (int p = 0; p < P; ++p) {
-      am[p] = a.adam_m[io * P + p];
-      av[p] = a.adam_v[io * P + p];
+      if (a.opt_s0) am[p] = a.opt_s0[io * P + p];
+      if (a.opt_s1) av[p] = a.opt_s1[io * P + p];
+      if (a.opt_s2) a2[p] = a.opt_s2[io * P + p];
     }
   lik(xi, 0);
 
@@ -730,7 +726,7 @@ __global__ __launch_bounds__(MPF_G_NT) void mpf_optimize_poll_kernel(const MpfPo
         n2 += ph[p] * ph[p];
       }
       _Pragma("unroll") for (int p = 0; p < P; ++p)
-        xn[p] = adam ? adam_step(xi[p], -ph[p], am[p], av[p], a.lr, a.beta1, a.beta2, a.eps, (float)(a.t0 + it + 1)) : fmaf(a.lr, ph[p], xi[p]);
+        xn[p] = opt_step(a.opt, xi[p], -ph[p], am[p], av[p], a2[p], (float)(a.t0 + it + 1));
       if (on && lane == 0) {
         const int row = (((it + 1) & 1) * Mp + i) * NX;
 #pragma unroll
@@ -763,11 +759,11 @@ __global__ __launch_bounds__(MPF_G_NT) void mpf_optimize_poll_kernel(const MpfPo
     return;
   }
   _Pragma("unroll") for (int p = 0; p < P; ++p) a.x[i * P + p] = xi[p];
-  if (adam)
-    _Pragma("unroll") for (int p = 0; p < P; ++p) {
-      a.adam_m[i * P + p] = am[p];
-      a.adam_v[i * P + p] = av[p];
-    }
+  _Pragma("unroll") for (int p = 0; p < P; ++p) {
+    if (a.opt_s0) a.opt_s0[i * P + p] = am[p];
+    if (a.opt_s1) a.opt_s1[i * P + p] = av[p];
+    if (a.opt_s2) a.opt_s2[i * P + p] = a2[p];
+  }
 }
 
 struct MpfBw {
@@ -882,9 +878,9 @@ struct dust_mpf {
   hipStream_t stream;
   float *x, *gn, *phi, *tmp;
   size_t tmp_cap;
-  int optimizer, adam_t;       // dust_mpf_set_optimizer; steps taken so far
-  float beta1, beta2, adam_eps;
-  float *adam_m, *adam_v;      // [Mp][P] or nullptr (SGD)
+  dust_optim_config opt;       // dust_mpf_set_optimizer(_ex); plain SGD at cfg.lr until then
+  int opt_t;                   // steps taken so far
+  float *opt_s0, *opt_s1, *opt_s2;  // state slots [Mp][P] or nullptr
   uint32_t *grid_bits;
   int nx, ny;
   float off_x, off_y;
@@ -927,7 +923,7 @@ extern "C" void dust_mpf_destroy(dust_mpf *m) {
   if (!m) return;
   (void)hipSetDevice(m->cfg.device);
   if (m->stream) (void)hipStreamSynchronize(m->stream);
-  float *fp[] = {m->x, m->gn, m->phi, m->tmp, m->adam_m, m->adam_v, m->gbuf, reinterpret_cast<float *>(m->gcnt), m->pbuf, reinterpret_cast<float *>(m->pcnt)};
+  float *fp[] = {m->x, m->gn, m->phi, m->tmp, m->opt_s0, m->opt_s1, m->opt_s2, m->gbuf, reinterpret_cast<float *>(m->gcnt), m->pbuf, reinterpret_cast<float *>(m->pcnt)};
   for (float *p : fp)
     if (p) (void)hipFree(p);
   if (m->grid_bits) (void)hipFree(m->grid_bits);
@@ -961,6 +957,7 @@ extern "C" int dust_mpf_create(const dust_mpf_config *cfg, const float *init_par
   if (!m) return fail(DUST_ERR_HIP, "out of host memory");
   memset((void *)m, 0, sizeof *m);
   m->cfg = *cfg;
+  m->opt = optim_plain(DUST_OPT_SGD, cfg->lr, 0.f, 0.f, 0.f);
   m->Mp = cfg->n_particles;
   m->P = cfg->dim_p;
   *out = m;
@@ -1000,20 +997,27 @@ extern "C" int dust_mpf_set_grid(dust_mpf *m, const float *grid, int nx, int ny,
 // MPF(optimizer_class=..., **opt_args) (svgd.py:108-122): SGD (the demos' choice) or Adam (the class default).  (Re)starts the state.
 extern "C" int dust_mpf_set_optimizer(dust_mpf *m, int optimizer, float beta1, float beta2, float eps) {
   if (!m) return fail(DUST_ERR_INVALID, "null mpf");
-  if (optimizer != DUST_OPT_SGD && optimizer != DUST_OPT_ADAM) return fail(DUST_ERR_UNSUPPORTED, "MPF optimiser: SGD or Adam");
+  if (optimizer != DUST_OPT_SGD && optimizer != DUST_OPT_ADAM) return fail(DUST_ERR_UNSUPPORTED, "MPF optimiser: SGD or Adam (dust_mpf_set_optimizer_ex: the others)");
+  const dust_optim_config o = optim_plain(optimizer, m->cfg.lr, beta1, beta2, eps);
+  return dust_mpf_set_optimizer_ex(m, &o);
+}
+
+// any optimiser of dust_set_optimizer; its state starts fresh and persists across optimize() calls (built once in MPF.__init__, mpf.py:24)
+extern "C" int dust_mpf_set_optimizer_ex(dust_mpf *m, const dust_optim_config *opt) {
+  if (!m) return fail(DUST_ERR_INVALID, "null mpf");
+  TRY(validate_optim(opt));
   HIP_TRY(hipSetDevice(m->cfg.device));
-  m->optimizer = optimizer;
-  m->adam_t = 0;
-  m->beta1 = beta1;
-  m->beta2 = beta2;
-  m->adam_eps = eps;
-  if (optimizer == DUST_OPT_ADAM) {
-    const size_t n = (size_t)m->Mp * m->P;
-    if (!m->adam_m) TRY(dalloc(&m->adam_m, n));
-    if (!m->adam_v) TRY(dalloc(&m->adam_v, n));
-    HIP_TRY(hipMemsetAsync(m->adam_m, 0, n * sizeof(float), m->stream));
-    HIP_TRY(hipMemsetAsync(m->adam_v, 0, n * sizeof(float), m->stream));
-  }
+  const size_t n = (size_t)m->Mp * m->P;
+  float *slots[3] = {m->opt_s0, m->opt_s1, m->opt_s2};
+  HIP_TRY(hipStreamSynchronize(m->stream));  // (slots about to be freed may still be read by queued work)
+  TRY(optim_slots_alloc(*opt, slots, n));
+  m->opt_s0 = slots[0];
+  m->opt_s1 = slots[1];
+  m->opt_s2 = slots[2];
+  m->opt = *opt;
+  m->cfg.lr = (float)opt->lr;
+  m->opt_t = 0;
+  TRY(optim_restart(m->opt, slots, n, m->stream));
   return DUST_OK;
 }
 
@@ -1029,12 +1033,15 @@ extern "C" int dust_mpf_clone(const dust_mpf *src, dust_mpf **out) {
   memcpy(m->past_obs, src->past_obs, sizeof m->past_obs);
   memcpy(m->past_action, src->past_action, sizeof m->past_action);
   m->have_past = src->have_past;
-  if (src->optimizer == DUST_OPT_ADAM) {
-    TRY(dust_mpf_set_optimizer(m, DUST_OPT_ADAM, src->beta1, src->beta2, src->adam_eps));
+  if (memcmp(&src->opt, &m->opt, sizeof m->opt) != 0) {
+    TRY(dust_mpf_set_optimizer_ex(m, &src->opt));
     const size_t nb = (size_t)src->Mp * src->P * sizeof(float);
-    HIP_TRY(hipMemcpy(m->adam_m, src->adam_m, nb, hipMemcpyDeviceToDevice));
-    HIP_TRY(hipMemcpy(m->adam_v, src->adam_v, nb, hipMemcpyDeviceToDevice));
-    m->adam_t = src->adam_t;
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    float *const ds[3] = {m->opt_s0, m->opt_s1, m->opt_s2};
+    const float *const ss[3] = {src->opt_s0, src->opt_s1, src->opt_s2};
+    for (int k = 0; k < 3; ++k)
+      if (ss[k]) HIP_TRY(hipMemcpy(ds[k], ss[k], nb, hipMemcpyDeviceToDevice));
+    m->opt_t = src->opt_t;
   }
   if (src->grid_bits) {
     const size_t words = ((size_t)src->nx * src->ny + 31) / 32;
@@ -1119,7 +1126,6 @@ static int mpf_launch(dust_mpf *m, float bw, float lr, int n_steps, float *gn_de
   a.log_space = m->cfg.log_space;
   for (int p = 0; p < 4; ++p) a.prior_bwv[p] = m->prior_bwv[p];
   a.bw = bw;
-  a.lr = lr;
   a.obs_std = m->cfg.obs_std;
   for (int k = 0; k < 4; ++k) {
     a.past_obs[k] = m->past_obs[k];
@@ -1131,13 +1137,15 @@ static int mpf_launch(dust_mpf *m, float bw, float lr, int n_steps, float *gn_de
   a.x = m->x;
   a.grad_norms = gn_dev;
   a.phi_out = phi_dev;
-  a.optimizer = (optimise && m->optimizer == DUST_OPT_ADAM) ? DUST_OPT_ADAM : DUST_OPT_SGD;  // (the bare phi evaluation takes no step)
-  a.t0 = m->adam_t;
-  a.beta1 = m->beta1;
-  a.beta2 = m->beta2;
-  a.eps = m->adam_eps;
-  a.adam_m = m->adam_m;
-  a.adam_v = m->adam_v;
+  if (optimise) {
+    a.opt = m->opt;  // (its lr is the lr passed, m->cfg.lr, kept in double)
+    a.opt_s0 = m->opt_s0;
+    a.opt_s1 = m->opt_s1;
+    a.opt_s2 = m->opt_s2;
+  } else {  // the bare phi evaluation takes no step
+    a.opt = optim_plain(DUST_OPT_SGD, lr, 0.f, 0.f, 0.f);
+  }
+  a.t0 = m->opt_t;
   // the data-polled form (keys in registers) unless DUST_MPF_POLL=0, which selects the counter form
   if (grid && m->Mp <= MPF_POLL_MAX && !(getenv("DUST_MPF_POLL") && atoi(getenv("DUST_MPF_POLL")) == 0)) {
     const int NP = (m->P + 1) / 2, NX = NP + 1;
@@ -1268,7 +1276,7 @@ extern "C" int dust_mpf_optimize(dust_mpf *m, const float *action, const float *
       }
     }
   }
-  if (m->optimizer == DUST_OPT_ADAM) m->adam_t += n_steps;
+  m->opt_t += n_steps;
   for (int p = 0; p < 4; ++p) m->prior_bwv[p] = bw;  // update_prior(bw) mpf.py:85
   if (!gn_read) {
     if (want_gn) HIP_TRY(hipMemcpyAsync(m->hpin, m->gn, n_steps * sizeof(float), hipMemcpyDeviceToHost, m->stream));

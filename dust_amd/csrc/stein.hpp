@@ -624,8 +624,8 @@ struct UpdateArgs {
   int N, D, i0, n_local, JS;
   int JSA;               // slices of pA when they differ from pB's (pass 2 of pairwise_fused.hpp has its own grid); 0 = JS
   int ldp;               // row stride of pA / pB (D padded to 8*CPT)
-  int optimizer, apply;  // apply = 0: only materialise phi (stage-wise SVMPC.phi)
-  float lr, beta1, beta2, eps;
+  int apply;             // apply = 0: only materialise phi (stage-wise SVMPC.phi)
+  OptArgs opt;
   float inv_l2, inv_n;
   uint32_t *ctr;  // device counters {tick, iter, adam_step}; this kernel advances iter after use
   unsigned int *fused_cnt;  // [fused_tiles] hand-off counters of the fused prior+rollout launch: re-armed (zeroed) here
@@ -634,7 +634,7 @@ struct UpdateArgs {
   float *phi;     // [N][D]
   float *theta;   // [N][D] current particles
   float *theta_out;  // [N][D] where the updated particles go (== theta, or the other buffer of the ping-pong)
-  float *adam_m, *adam_v;
+  float *opt_s0, *opt_s1, *opt_s2;  // optimiser state slots [N][D] (handoff.hpp opt_step) or nullptr
 };
 
 // `sc1`: the partials were published inside the SAME launch (fused.hpp stein_update_kernel) with write-through stores and
@@ -676,16 +676,7 @@ __device__ __forceinline__ void update_body(const UpdateArgs &a, const int idx) 
   const float phi = sb * a.inv_l2 + sa * a.inv_n;
   a.phi[o] = phi;
   if (!a.apply) return;
-  const float g = -phi;
-  if (a.optimizer == DUST_OPT_SGD) {
-    th = fmaf(-a.lr, g, th);  // torch SGD: p.add_(grad, alpha=-lr), a vectorised fmadd
-  } else {  // torch.optim.Adam (no weight decay, no amsgrad)
-    float m = a.adam_m[o], v = a.adam_v[o];
-    th = adam_step(th, g, m, v, a.lr, a.beta1, a.beta2, a.eps, adam_t);
-    a.adam_m[o] = m;
-    a.adam_v[o] = v;
-  }
-  a.theta_out[o] = th;
+  a.theta_out[o] = opt_apply(a.opt, a.opt_s0, a.opt_s1, a.opt_s2, o, th, -phi, adam_t);  // theta.grad = -phi; optimizer.step()
 }
 
 __global__ void update_kernel(const UpdateArgs a) { update_body<false>(a, blockIdx.x * blockDim.x + threadIdx.x); }
@@ -700,16 +691,7 @@ __global__ void update_from_phi_kernel(const UpdateArgs a) {
   const int il = idx / a.D, d = idx - il * a.D;
   const size_t o = (size_t)(a.i0 + il) * a.D + d;
   float th = a.theta[o];
-  const float g = -a.phi[o];
-  if (a.optimizer == DUST_OPT_SGD) {
-    th = fmaf(-a.lr, g, th);
-  } else {
-    float m = a.adam_m[o], v = a.adam_v[o];
-    th = adam_step(th, g, m, v, a.lr, a.beta1, a.beta2, a.eps, adam_t);
-    a.adam_m[o] = m;
-    a.adam_v[o] = v;
-  }
-  a.theta[o] = th;
+  a.theta[o] = opt_apply(a.opt, a.opt_s0, a.opt_s1, a.opt_s2, o, th, -a.phi[o], adam_t);
 }
 
 // row-major [N][D] -> transposed [D][N] (K2's per-dimension kernels read the transposed copy)

@@ -545,15 +545,13 @@ __global__ __launch_bounds__(T2_NT, 4) void svmpc_tick2_kernel(const Tick2Args f
   const int ol = tid0 - 512, op = (ol >> 5) & 3, od = ol & 31;
   const bool ownv = isown && od < D;
   const size_t no = (size_t)(n_first + op) * D + (ownv ? od : 0);
-  const bool adam = f->optimizer == DUST_OPT_ADAM;
-  float thv = 0.f, amv = 0.f, adm = 0.f, adv = 0.f;
+  float thv = 0.f, amv = 0.f, adm = 0.f, adv = 0.f, ad2 = 0.f;  // (the optimiser's state slots: adm, adv, ad2)
   if (ownv) {
     thv = f->theta[no];
     if (f->update_a_mat) amv = f->a_mat[no];
-    if (adam) {
-      adm = f->adam_m[no];
-      adv = f->adam_v[no];
-    }
+    if (f->opt_s0) adm = f->opt_s0[no];
+    if (f->opt_s1) adv = f->opt_s1[no];
+    if (f->opt_s2) ad2 = f->opt_s2[no];
   }
   const uint32_t ctr_tick = f->ctr[0], ctr_iter0 = f->ctr[1], adam0 = f->ctr[2];
   float x0[DS];
@@ -1235,8 +1233,7 @@ __global__ __launch_bounds__(T2_NT, 4) void svmpc_tick2_kernel(const Tick2Args f
       for (int w = 0; w < 4; ++w) sb += rpart[(((op >> 1) * 4 + w) * 16 + (op & 1) * 8 + (od & 7)) * 4 + (od >> 3)];
       const float phi = sb * f->inv_l2 + sa * f->inv_n;
       const float gr = -phi;
-      if (!adam) thv = fmaf(-f->lr, gr, thv);
-      else thv = adam_step(thv, gr, adm, adv, f->lr, f->beta1, f->beta2, f->adam_eps, (float)(adam0 + (uint32_t)k + 1u));
+      thv = opt_step(f->opt, thv, gr, adm, adv, ad2, (float)(adam0 + (uint32_t)k + 1u));
       if (!ownv) thv = 0.f;
       th[op * T2_ROW + od] = thv;
       const unsigned long long badm = __ballot(ownv && !(fabsf(thv) <= 3.0e38f));
@@ -1273,10 +1270,9 @@ __global__ __launch_bounds__(T2_NT, 4) void svmpc_tick2_kernel(const Tick2Args f
     if (ownv) {
       f->theta[no] = thv;
       if (f->update_a_mat) f->a_mat[no] = amv;
-      if (adam) {
-        f->adam_m[no] = adm;
-        f->adam_v[no] = adv;
-      }
+      if (f->opt_s0) f->opt_s0[no] = adm;
+      if (f->opt_s1) f->opt_s1[no] = adv;
+      if (f->opt_s2) f->opt_s2[no] = ad2;
     }
     if (b == 0 && tid0 == 0) {
       f->ctr[1] = ctr_iter0 + (uint32_t)kf;
@@ -1423,10 +1419,10 @@ __global__ __launch_bounds__(T2_NT, 4) void svmpc_tick2_kernel(const Tick2Args f
       if (f->roll_strategy == DUST_ROLL_MEAN && od + DA >= D) out = outv;
       f->theta[no] = out;
       if (f->update_a_mat) f->a_mat[no] = amv;
-      if (adam) {  // SVMPC.roll makes a NEW parameter tensor: torch's optimiser state restarts
-        f->adam_m[no] = 0.f;
-        f->adam_v[no] = 0.f;
-      }
+      // SVMPC.roll makes a NEW parameter tensor: torch's optimiser state restarts
+      if (f->opt_s0) f->opt_s0[no] = opt_restart_s0(f->opt);
+      if (f->opt_s1) f->opt_s1[no] = 0.f;
+      if (f->opt_s2) f->opt_s2[no] = 0.f;
     }
   }
   if (b == 0 && tid0 == 0) {

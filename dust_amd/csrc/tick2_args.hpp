@@ -29,7 +29,7 @@ struct Tick2Args {
   int N, S, M, H, D;
   int n_iters, do_forward;
   int steps;             // ceil(N / 64) rounded up to a multiple of 16: 16-key steps of a pair wave in the theta-only pass (4 waves share the keys)
-  int lik, update_a_mat, eps_base_mode, optimizer, roll_strategy, weighted_prior;
+  int lik, update_a_mat, eps_base_mode, roll_strategy, weighted_prior;
   int coef_given;
   int test_abort;        // test hooks, every k-th launch.  1 (DUST_TICK2_TEST_ABORT=k): workgroup 0 publishes "abort" as if a peer were missing;
                          // 2 (DUST_TICK2_TEST_TIMEOUT=k): the last workgroup behaves as if its last wait had given up (no COMMIT)
@@ -44,7 +44,7 @@ struct Tick2Args {
   float cP;              // -0.5 log2(e) / sigma_p^2: exponent scale of the prior weights on the raw squared distance
   float cS;              // K1: -0.5 log2(e) / ell^2 (exponent scale); IMQ: 1 / ell^2
   float inv_l2, inv_n, log_norm;
-  float lr, beta1, beta2, adam_eps;
+  OptArgs opt;           // the optimiser (handoff.hpp opt_step)
   float x0[4];           // plant state (by value)
   uint64_t seed;
   uint32_t *ctr;         // device counters {tick, iter, adam_step}
@@ -55,7 +55,7 @@ struct Tick2Args {
   float *theta;          // [N][D] particles: read at the start of the tick, rolled (forward) / updated (optimize) at its end
   float *xq, *sq, *lwq;  // exchange buffers written through inside the launch: particles [N][32], score rows [N][32], log-weights [N]
   float *logmix, *mixw;  // [N] prior mixture (the means alias the particles: host check)
-  float *a_mat, *adam_m, *adam_v;
+  float *a_mat, *opt_s0, *opt_s1, *opt_s2;  // a_mat; optimiser state slots [N][D] or nullptr
   float *costsT, *grad_lik, *grad_pri, *score, *phi, *logl, *eta, *logp, *lw, *pw, *a_seq_out;
   int *istar;
   unsigned int *cnt;        // this tick's counter set (T2_SETS lines)

@@ -3,6 +3,7 @@ import numpy as np
 import torch
 
 from ..kernels import kernel_config
+from ..optim import check_optimizer, group_options, optimizer_config
 
 
 class SVMPC:
@@ -16,13 +17,12 @@ class SVMPC:
         self.w_prior, self.roll_strategy = weighted_prior, roll_strategy
         if roll_strategy not in ("repeat", "mean", "resample"):
             raise ValueError("{} is an invalid roll strategy.".format(roll_strategy))
-        if optimizer_class is torch.optim.SGD:
-            opt = dict(optimizer="SGD", lr=float(opt_args.get("lr", 1e-3)))
-        elif optimizer_class is torch.optim.Adam:
-            b = opt_args.get("betas", (0.9, 0.999))
-            opt = dict(optimizer="Adam", lr=float(opt_args.get("lr", 1e-3)), adam=(b[0], b[1], opt_args.get("eps", 1e-8)))
-        else:
-            raise NotImplementedError("optimizer %r has no HIP kernel (SGD and Adam do)" % (optimizer_class,))
+        # every option reaches the device or raises (dust_amd/optim.py); plain SGD / Adam keep dust_config's own fields
+        self._optim = optimizer_config(optimizer_class, opt_args)
+        oc = self._optim
+        opt = dict(optimizer="Adam" if oc["kind"] == "Adam" else "SGD", lr=oc["lr"], optim=oc)
+        if oc["kind"] == "Adam":
+            opt["adam"] = (oc["beta1"], oc["beta2"], oc["eps"])
         comp = prior.component_distribution.base_dist
         cov = comp.covariance_matrix
         cov = cov.reshape(-1, cov.shape[-2], cov.shape[-1])[0]
@@ -40,6 +40,7 @@ class SVMPC:
         # attribute compatibility (simulations.py never touches it): torch's optimiser object over a placeholder - the optimiser
         # STATE lives on the device and restarts at every roll, as torch's does when roll() swaps the parameter tensor
         self.optimizer = optimizer_class(params=[torch.zeros(1, requires_grad=True)], **opt_args)
+        self._opt_group = group_options(self.optimizer)  # (what the device runs: check_optimizer refuses later edits of the group)
 
     # -- device plumbing
     def _ctx(self, params_dist=None):
@@ -109,6 +110,7 @@ class SVMPC:
 
     def optimize(self, state, params_dist, bw=None, n_steps=None, debug=False, eps=None):
         """`bw` is accepted and ignored, as in the reference (dead value on both kernel branches)."""
+        check_optimizer(self.optimizer, self._opt_group)  # (an LR scheduler / a second param group on `self.optimizer` would not reach the device)
         ctx = self._ctx(params_dist)
         ctrl = self.likelihood.controller
         n_steps = self.n_steps if n_steps is None else n_steps
@@ -157,6 +159,7 @@ class SVMPC:
 
     def tick(self, state, params_dist, n_steps=None, eps=None):
         """optimize + forward enqueued back to back (dust_svmpc_tick)."""
+        check_optimizer(self.optimizer, self._opt_group)
         ctx = self._ctx(params_dist)
         n_steps = self.n_steps if n_steps is None else n_steps
         params, _ = self.likelihood.controller._sample_params(params_dist, n_steps)

@@ -45,7 +45,16 @@ enum dust_cost { DUST_COST_PENDULUM_QUADCOS = 0, DUST_COST_PARTICLE_DEFAULT = 1,
  * (svmpc.py:64-74, composite_kernels.py:33-64); K2_SHARED: indep_controls=False; IMQ: new, no reference. */
 enum dust_kernel { DUST_KERNEL_K1_RBF = 0, DUST_KERNEL_K2_IIDMP = 1, DUST_KERNEL_K2_SHARED = 2, DUST_KERNEL_IMQ = 3 };
 enum dust_likelihood { DUST_LIK_EXP_UTILITY = 0, DUST_LIK_EXPECTED_COST = 1 }; /* likelihoods.py:122-135 / 106-119 */
-enum dust_optimizer { DUST_OPT_SGD = 0, DUST_OPT_ADAM = 1 };                   /* svgd.py:115, demos use SGD */
+/* svgd.py:115, demos use SGD.  dust_config.optimizer takes SGD / Adam only; RMSprop / Adagrad (and AdamW: Adam with
+ * DUST_OPTF_DECOUPLED_WD) are chosen through dust_set_optimizer / dust_mpf_set_optimizer_ex. */
+enum dust_optimizer { DUST_OPT_SGD = 0, DUST_OPT_ADAM = 1, DUST_OPT_RMSPROP = 2, DUST_OPT_ADAGRAD = 3 };
+enum dust_optim_flags {
+  DUST_OPTF_MAXIMIZE = 1,        /* maximize=True (every class) */
+  DUST_OPTF_NESTEROV = 2,        /* SGD(nesterov=True) */
+  DUST_OPTF_AMSGRAD = 4,         /* Adam / AdamW(amsgrad=True) */
+  DUST_OPTF_DECOUPLED_WD = 8,    /* Adam(decoupled_weight_decay=True), i.e. AdamW: param *= 1 - lr * weight_decay */
+  DUST_OPTF_CENTERED = 16        /* RMSprop(centered=True) */
+};
 enum dust_roll { DUST_ROLL_REPEAT = 0, DUST_ROLL_MEAN = 1, DUST_ROLL_RESAMPLE = 2 }; /* svmpc.py:142-158 */
 enum dust_step_strategy { DUST_STEP_ARGMAX = 0, DUST_STEP_AVERAGE = 1, DUST_STEP_EXTERNAL = 2 }; /* disco.py:396-417 */
 /* how a model parameter enters the arithmetic: a Python float (double), a 0-dim fp32 tensor, or a sampled column */
@@ -137,6 +146,26 @@ typedef struct dust_skid_config {
   float goal[5], w_state[5], w_term[5], w_ctrl[2];
 } dust_skid_config;
 
+/* A torch.optim optimiser with its options (dust_set_optimizer, dust_mpf_set_optimizer_ex).  Each step follows the installed torch's
+ * single-tensor CPU function operation by operation - torch/optim/sgd.py _single_tensor_sgd, adam.py _single_tensor_adam (AdamW
+ * included), rmsprop.py _single_tensor_rmsprop, adagrad.py _single_tensor_adagrad - on grad = -phi: Python-float scalars are formed
+ * in double from these fields, as Python forms them, then rounded to fp32 where the tensor op takes them.  Fields a class does not
+ * have are ignored.  The step count (Adam's bias corrections, Adagrad's lr_decay, SGD's first momentum step) is the device's own
+ * step counter, which restarts with the state. */
+typedef struct dust_optim_config {
+  int32_t kind;  /* dust_optimizer */
+  int32_t flags; /* dust_optim_flags */
+  double lr;
+  double beta1, beta2;  /* Adam betas */
+  double eps;           /* Adam / RMSprop / Adagrad */
+  double weight_decay;  /* every class */
+  double momentum;      /* SGD / RMSprop */
+  double dampening;     /* SGD */
+  double alpha;         /* RMSprop smoothing constant */
+  double lr_decay;      /* Adagrad */
+  double initial_accumulator_value; /* Adagrad: the value its sum starts (and restarts) at */
+} dust_optim_config;
+
 typedef struct dust_ctx dust_ctx;
 typedef struct dust_mpf dust_mpf;
 
@@ -175,6 +204,15 @@ int dust_set_grid(dust_ctx *ctx, const float *grid, int nx, int ny, float off_x,
 
 /* particle / prior / controller state (all [N][H][da] or [N]) */
 int dust_set_theta(dust_ctx *ctx, const float *theta);                                /* SVMPC.theta svmpc.py:25 */
+/* SVMPC(optimizer_class=, **opt_args) svgd.py:109-125, svmpc.py:87-95: replaces the context's optimiser (dust_config.optimizer / lr /
+ * adam_* give plain SGD or Adam until then) and restarts its state.  The state - up to three [N][D] slots: SGD's momentum buffer;
+ * Adam's exp_avg, exp_avg_sq and AMSGrad max; RMSprop's square_avg, momentum buffer and grad_avg; Adagrad's sum - restarts at every
+ * roll (SVMPC.roll builds a new parameter tensor), at dust_set_theta and here; dust_clone copies it.  Every device path that takes
+ * an SVGD step applies it.  Adagrad differs from the reference here: torch's Adagrad creates its `sum` in __init__ only, so the
+ * reference's SVMPC raises KeyError('sum') at the first step after a roll; the device restarts `sum` at initial_accumulator_value as a
+ * fresh Adagrad on the rolled tensor would.  DUST_ERR_UNSUPPORTED names an option outside the table (e.g. SGD(nesterov=True) with dampening != 0). */
+int dust_set_optimizer(dust_ctx *ctx, const dust_optim_config *opt);
+int dust_get_optimizer(const dust_ctx *ctx, dust_optim_config *out);
 /* RBF(bandwidth=, minimum_bw=) of the K2 kernels (base_kernels.py:44-92): bandwidth < 0 = median trick (default), every
  * per-dimension h = max(bw_scale * median / log(N + 1), minimum_bw); otherwise the fixed h = clip(bw_scale * bandwidth^2 / log(N + 1),
  * minimum_bw) replaces the medians.  minimum_bw > 0 (the reference's default is 1e-5). */
@@ -349,6 +387,9 @@ int dust_mpf_clone(const dust_mpf *src, dust_mpf **out);
  * reference's class default; betas / eps as torch.optim.Adam).  The optimiser state starts at zero and persists across
  * dust_mpf_optimize calls, as the reference's does (the optimiser is built once in MPF.__init__). */
 int dust_mpf_set_optimizer(dust_mpf *mpf, int optimizer, float beta1, float beta2, float eps);
+/* Any optimiser of dust_set_optimizer for the filter; opt->lr replaces the config's lr.  The state (and the step count) starts at
+ * its initial value and persists across dust_mpf_optimize calls; dust_mpf_clone copies it. */
+int dust_mpf_set_optimizer_ex(dust_mpf *mpf, const dust_optim_config *opt);
 void dust_mpf_destroy(dust_mpf *mpf);
 /* MPF.optimize(action, new_obs, bw, n_steps) mpf.py:64-86 -> grad_norms [n_steps] */
 int dust_mpf_optimize(dust_mpf *mpf, const float *action, const float *new_obs, float bw, int n_steps, float *grad_norms);
