@@ -645,8 +645,8 @@ __device__ __forceinline__ void k2_bandwidth256(const K2Args &a, const int c, fl
   (void)nrounds;
 }
 
-// (the role as a launch of its own - DUST_K2_FORM=3, a measuring aid: its duration in a kernel trace is the role's time without the
-//  rollout waves around it)
+// (the role as a launch of its own - a measuring aid, tools/k2_bw_probe.hip: its duration in a kernel trace is the role's time without
+//  the rollout waves around it)
 __global__ __launch_bounds__(256) void k2_bandwidth256_kernel(const K2Args a) {
   extern __shared__ __attribute__((aligned(16))) float lds256[];
   k2_bandwidth256(a, (int)blockIdx.x, lds256);
@@ -757,7 +757,7 @@ __global__ __launch_bounds__(1024) void k2_bandwidth_pairs_kernel(const K2Args a
 // exp(-d2/h): exact fp32 division as the reference, then the bare v_exp_f32 (error ~|x| 2^-24, as in the K1 Gram value);
 // the 2/h factor of the repulsive term is applied once to the sum.
 enum { K2_JT = 2048 };
-template <int GD /* dimensions per kernel group: 1, or d_a (<= 2) when shared */>
+template <int GD /* dimensions per kernel group: d_a = 2 (shared K2) */>
 __global__ __launch_bounds__(256) void k2_phi_kernel(const K2Args a) {
   __shared__ float xcol[GD][K2_JT], scol[GD][K2_JT];
   __shared__ float part[4][64][4];
@@ -839,10 +839,11 @@ __global__ __launch_bounds__(256) void k2_phi_kernel(const K2Args a) {
   }
 }
 
-// The same for one dimension per kernel group (indep_controls = True: every demo) with TWO queries per lane (i and i + 64 of a 128-query
-// tile) in packed fp32: per key one packed subtract, two packed multiplies, two exponentials and two packed FMAs serve both queries
-// (19 instead of 25 issue cycles per pair, tools/valu_rate_probe.hip) and the broadcast reads of the key and its score are shared.
-// Element for element the operations of k2_phi_kernel<1>, in its order: the same bits.
+// One dimension per kernel group (indep_controls = True: every demo) with TWO queries per lane (i and i + 64 of a 128-query tile) in
+// packed fp32: per key one packed subtract, two packed multiplies, two exponentials and two packed FMAs serve both queries (19 instead
+// of 25 issue cycles per pair against one query per lane, tools/valu_rate_probe.hip) and the broadcast reads of the key and its score
+// are shared.  Per query and key: df = x_i - x_j, k = exp2((df * df) * ce), g1 += k s_j, g2 += k df, keys in index order within each
+// of the 4 slices; then phi = sum(g1) / N + ((sum(g2) * 2) / h) / N, slices summed in slice order.
 __global__ __launch_bounds__(256) void k2_phi2_kernel(const K2Args a) {
   __shared__ float xcol[K2_JT], scol[K2_JT];
   __shared__ float part[4][128][2];
@@ -995,9 +996,7 @@ static inline int launch_k2_bandwidth(hipStream_t stream, const K2Args &a) {
   } else {
     int np = 1;
     while (np < a.N) np <<= 1;
-    static const bool alone256 = getenv("DUST_K2_FORM") && atoi(getenv("DUST_K2_FORM")) == 3;
-    if (a.N <= 1024 && alone256) k2_bandwidth256_kernel<<<G, 256, (size_t)K2_BW256_LDS * sizeof(float), stream>>>(a);
-    else if (a.N <= 1024) k2_bandwidth_sorted_kernel<<<G, 1024, (size_t)2 * np * sizeof(float), stream>>>(a, np);  // (two buffers: the sort's LDS stages alternate)
+    if (a.N <= 1024) k2_bandwidth_sorted_kernel<<<G, 1024, (size_t)2 * np * sizeof(float), stream>>>(a, np);  // (two buffers: the sort's LDS stages alternate)
     else k2_bandwidth_sorted_big_kernel<<<G, 1024, (size_t)np * sizeof(float), stream>>>(a, np);
   }
   return hipGetLastError() != hipSuccess ? DUST_ERR_HIP : DUST_OK;
@@ -1005,14 +1004,10 @@ static inline int launch_k2_bandwidth(hipStream_t stream, const K2Args &a) {
 static inline int launch_k2_phi(hipStream_t stream, const K2Args &a) {
   const int G = a.shared ? a.H : a.D;
   if (a.da > 2) return DUST_ERR_UNSUPPORTED;
-  dim3 grid((a.n_local + 63) / 64, G);
   if (a.shared && a.da == 2) {
-    k2_phi_kernel<2><<<grid, 256, 0, stream>>>(a);
+    k2_phi_kernel<2><<<dim3((a.n_local + 63) / 64, G), 256, 0, stream>>>(a);
   } else {
-    static const bool one_q = getenv("DUST_K2_PHI1") != nullptr;  // development switch: one query per lane (k2_phi_kernel<1>)
-    static const bool two_q = getenv("DUST_K2_PHI2") != nullptr;  // development switch: the 256-lane launch at every size
-    if (one_q && !a.x_rows) k2_phi_kernel<1><<<grid, 256, 0, stream>>>(a);
-    else if (a.N <= K2_P3_N && !two_q) k2_phi3_kernel<<<dim3((a.n_local + K2_P3_Q - 1) / K2_P3_Q, G), 1024, 0, stream>>>(a);
+    if (a.N <= K2_P3_N) k2_phi3_kernel<<<dim3((a.n_local + K2_P3_Q - 1) / K2_P3_Q, G), 1024, 0, stream>>>(a);
     else k2_phi2_kernel<<<dim3((a.n_local + 127) / 128, G), 256, 0, stream>>>(a);
   }
   return hipGetLastError() != hipSuccess ? DUST_ERR_HIP : DUST_OK;

@@ -26,15 +26,7 @@
   do {                                                                                                                      \
     if ((p) && threadIdx.x == 0) (p)[4 * blockIdx.x + (k)] = (unsigned long long)__builtin_amdgcn_s_memrealtime();          \
   } while (0)
-// persistent tick (persist.hpp): wall-clock stamp into slot k of the workgroup's current iteration block
-#define DUST_TLP(p, k)                                                                                     \
-  do {                                                                                                      \
-    if ((p) && threadIdx.x == 0) (p)[k] = (unsigned long long)__builtin_amdgcn_s_memrealtime();             \
-  } while (0)
 #else
-#define DUST_TLP(p, k) \
-  do {                 \
-  } while (0)
 #define DUST_STAMP(p, k) \
   do {                   \
   } while (0)
@@ -639,8 +631,8 @@ __device__ __forceinline__ void philox_normal4(uint64_t seed, uint32_t c0, uint3
   z[3] = rb * __builtin_amdgcn_sinf(u3);
 }
 
-// EIGHT standard normals from one Philox block: the policy-noise stream of the rollout kernels (rollout.hpp, persist.hpp, tick2.hpp,
-// skid.hpp - element j of a row comes from block j >> 3, lane element j & 7; all four draw the same stream).  Each 32-bit word gives one
+// EIGHT standard normals from one Philox block: the policy-noise stream of the rollout kernels (rollout.hpp, tick2.hpp, skid.hpp -
+// element j of a row comes from block j >> 3, lane element j & 7; all three draw the same stream).  Each 32-bit word gives one
 // Box-Muller pair from two 16-bit uniforms - radius from the low half, angle from the high half: 65 536 radii up to 4.85 sigma times
 // 65 536 angles per pair.  Against four normals per block from 24-bit uniforms (rounds 1-3) this halves the Philox rounds per normal -
 // the integer multiplies are a third of the draw - at the price of a tail cut at 4.85 sigma (2.4e-6 of the mass of a pair) and a

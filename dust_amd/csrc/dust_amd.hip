@@ -95,11 +95,10 @@ struct dust_ctx {
   int N, S, M, H, da, ds, P, D, n0, nloc;
   hipStream_t stream;
   bool own_stream;
-  hipStream_t stream2;  // side stream: the prior pass runs beside the rollout kernel (both only read theta)
+  hipStream_t stream2;  // side stream: query_order_kernel of large sets (launch_gram_score), the sharded tick's all-gathers
   hipEvent_t ev_fork, ev_join;
   hipEvent_t ev_order;   // behind the side stream's query_order_kernel (pairwise_packed.hpp); order_pending: nobody has waited for it yet
   bool order_pending;
-  hipStream_t pair_stream;  // stream the next pairwise launch goes to (stream or stream2)
   // particles / prior / controller state
   float *theta, *thetaT, *mu, *muT, *logmix, *mixw;
   float *thetaT_alt;     // K2: the transposed particles of the next iteration, written by the phi + update launch (ping-pong with thetaT)
@@ -176,7 +175,7 @@ struct dust_ctx {
   bool stein_dirty;
   // one-launch SVGD iteration (fused.hpp svgd_iter_kernel): two sets of [tiles | JS | tiles] counter lines, then the time-out flag
   unsigned int *iter_cnt;
-  int iter_tiles, iter_js, iter_set;
+  int iter_tiles, iter_set;
   float *score_hs;  // [2][N][D] score rows handed over as data inside the one-launch iteration (sentinel-filled between uses)
   // C-side RCCL communicator of a sharded context (dust_comm_init): the sharded tick issues its all-gathers on the context's stream
   void *comm;  // ncclComm_t
@@ -205,15 +204,14 @@ struct dust_ctx {
   // not commit - makes every LATER one-launch tick of the context abort at its start as well (the kernels compare the device's abort
   // count with the value the host knew when it launched them: `expect_aborts`), so the ticks that have to be replayed are always the
   // tail of this queue and are replayed in their order, each with its own inputs.
-  // Development switches and test hooks (environment variables), read ONCE when the context is created or cloned - the tick entry
-  // points called getenv() several times per control tick before.  -1: unset, otherwise atoi of the value.
+  // Development switches and test hooks (environment variables; INTEGRATION.md lists them), read ONCE when the context is created or
+  // cloned (env_read) - no other code of the context reads the environment.  -1: unset, otherwise atoi of the value.
   struct EnvSw {
-    int comm_force, pair_big, pair_fused, states_form, dense, far, logp_mfma, no_fuse, no_persist, no_tick2,
-        tick2_test_abort, tick2_test_timeout, no_comm_overlap;
+    int comm_force, pair_big, pair_fused, states_form, dense, far, logp_mfma, no_fuse, no_tick2, tick2_test_abort, tick2_test_timeout,
+        no_comm_overlap;
     int noise_general;  // DUST_NOISE_GENERAL=1 (development switch): control-channel noise always through particle_general.hpp's first pass
     int k2_form;     // DUST_K2_FORM=0 (development switch): K2's bandwidth launch stays behind the prior + rollout launch (rounds 1-5);
                      // default: the bandwidths ride in that launch, phi reads the row-major particles (round 6)
-    int logp_pack;   // DUST_LOGP_PACK=0 / 1: the log-p pass never / always walks run lists (default: from 8 192 local rows on)
     int pack_order;  // DUST_PACK_ORDER=0: the queries stay in index order (development switch)
     int pack_merge;  // DUST_PACK_MERGE=0: PLAIN run lists even below the exact-zero threshold (development switch)
     float far_t;  // DUST_FAR_T: the far pre-pass' threshold (pairwise_far.hpp), default DUST_FAR_T_DEFAULT
@@ -259,7 +257,6 @@ struct dust_ctx {
   bool states_valid, states_f16;  // the last rollout launch left states [M][S][N][H+1][ds] in `states` (binary16 when states_f16)
   bool k2_inline_want;  // K2, set by step_device around its score launch: the prior + rollout launch may carry the bandwidth role
   bool k2_bw_inline;    // K2: ... and did (the bandwidths of the current theta are in c->bw; no transposed copy was made)
-  bool k2_bw_ahead;   // K2: transpose + bandwidths of the current theta are already in flight on the side stream
   float k2_fixed_h;   // > 0: fixed-bandwidth RBF (dust_set_k2_bandwidth), else the median trick
   float k2_min_bw;    // RBF(minimum_bw=): clamp of the median-trick bandwidths (0: the reference's default 1e-5)
   bool noise_f16;     // the eps / actions handed to the current call are binary16 (DUST_EPS_F16), set by the API entry points
@@ -536,14 +533,12 @@ static void env_read(dust_ctx *c) {
   c->env.far = env_int("DUST_FAR");
   c->env.logp_mfma = env_int("DUST_LOGP_MFMA");
   c->env.no_fuse = env_int("DUST_NO_FUSE");
-  c->env.no_persist = env_int("DUST_NO_PERSIST");
-  c->env.no_tick2 = env_int("DUST_NO_TICK2");
+  c->env.no_tick2 = std::max(env_int("DUST_NO_TICK2"), env_int("DUST_NO_PERSIST"));  // (DUST_NO_PERSIST: its former name)
   c->env.tick2_test_abort = env_int("DUST_TICK2_TEST_ABORT");
   c->env.tick2_test_timeout = env_int("DUST_TICK2_TEST_TIMEOUT");
   c->env.no_comm_overlap = env_int("DUST_NO_COMM_OVERLAP");
   c->env.pack_merge = env_int("DUST_PACK_MERGE");
   c->env.pack_order = env_int("DUST_PACK_ORDER");
-  c->env.logp_pack = env_int("DUST_LOGP_PACK");
   c->env.k2_form = env_int("DUST_K2_FORM");
   c->env.noise_general = env_int("DUST_NOISE_GENERAL");
   const char *ft = getenv("DUST_FAR_T");
@@ -569,11 +564,11 @@ static int sharded_steps(dust_ctx *c, const float *state, int n_steps, const flo
 static bool tick2_shape_ok(dust_ctx *c, int n_steps);
 static int sharded_forward(dust_ctx *c);
 
-// One-launch ticks (persist.hpp, tick2.hpp) spin on their own workgroups: every workgroup of the launch must be resident.  Two contexts
-// of ONE process ticking on the same device from two threads would interleave their grids (tick2.hpp then aborts and replays - late
-// but correct; persist.hpp has no such protocol and would time out).  So as soon as a second context lives on a device, the one-launch
-// kernels of that device are chained across streams with an event: launch k + 1 waits for launch k, whichever context issued it.  A
-// single context (the common case, the bench) pays nothing.  Other PROCESSES on the device remain tick2.hpp's start barrier's business.
+// One-launch ticks (tick2.hpp) spin on their own workgroups: every workgroup of the launch must be resident.  Two contexts of ONE
+// process ticking on the same device from two threads would interleave their grids (tick2.hpp then aborts and replays - late but
+// correct).  So as soon as a second context lives on a device, the one-launch kernels of that device are chained across streams with
+// an event: launch k + 1 waits for launch k, whichever context issued it.  A single context (the common case, the bench) pays nothing.
+// Other PROCESSES on the device remain tick2.hpp's start barrier's business.
 enum { DUST_MAX_DEV = 64 };
 static std::atomic<int> g_live_ctx[DUST_MAX_DEV];
 static std::mutex g_persist_mu[DUST_MAX_DEV];
@@ -670,8 +665,7 @@ extern "C" void dust_destroy(dust_ctx *c) {
 }
 
 PersistChain::PersistChain(dust_ctx *c_) : c(c_), dev(c_->cfg.device), on(false), locked(false) {
-  static const bool off = getenv("DUST_NO_CHAIN") != nullptr;  // development switch
-  if (off || dev < 0 || dev >= DUST_MAX_DEV) return;
+  if (dev < 0 || dev >= DUST_MAX_DEV) return;
   // (the tenant count is tested UNDER the device's mutex, which dust_create holds while it counts itself in and drains the device:
   //  a launch cannot slip unchained between another thread's increment and its first kernel - ADVICE r3)
   g_persist_mu[dev].lock();
@@ -740,7 +734,6 @@ static int create_impl(const dust_config *cfg, dust_ctx **out) {
   HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
   HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
   HIP_TRY(hipEventCreateWithFlags(&c->ev_order, hipEventDisableTiming));
-  c->pair_stream = c->stream;
   HIP_TRY(hipEventCreate(&c->ev0));
   HIP_TRY(hipEventCreate(&c->ev1));
   const size_t ND = (size_t)c->N * c->D, SN = (size_t)c->S * c->N;
@@ -891,7 +884,7 @@ extern "C" int dust_sync(dust_ctx *c) {
   }
   if (c->iter_cnt) {
     unsigned int flag = 0;
-    HIP_TRY(hipMemcpy(&flag, c->iter_cnt + (size_t)2 * (2 * c->iter_tiles + c->iter_js) * CNT_STRIDE, sizeof flag, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&flag, c->iter_cnt + (size_t)2 * (2 * c->iter_tiles) * CNT_STRIDE, sizeof flag, hipMemcpyDeviceToHost));
     if (flag) return handoff_timeout(c, "one-launch SVGD iteration: hand-off spin timed out (results of that tick are invalid); the device seems to be shared with another process: this context runs plain kernels from here on");
   }
   if (c->t2_cnt) {
@@ -919,7 +912,6 @@ extern "C" int dust_set_stream(dust_ctx *c, void *s) {
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (c->own_stream) HIP_TRY(hipStreamDestroy(c->stream));
   c->stream = (hipStream_t)s;
-  c->pair_stream = c->stream;
   c->own_stream = false;
   return DUST_OK;
 }
@@ -1239,7 +1231,7 @@ struct SampleOpts {
 static int pair_dpb(int D) { return D <= 32 ? 32 : 64; }
 static int fused_dpb(int D) { return D <= 32 ? 32 : (D <= 64 ? 64 : 80); }
 static int fused_tq(int D) { return D <= 32 ? FusedGeom<32>::TQ : (D <= 64 ? FusedGeom<64>::TQ : FusedGeom<80>::TQ); }
-// "large key set": none of the small-N launch fusions (fused.hpp, persist.hpp) applies
+// "large key set": none of the small-N launch fusions (fused.hpp, tick2.hpp) applies
 static bool pair_is_big(const dust_ctx *c) {
   // development switch DUST_PAIR_BIG: 0 forces the 32 x 64 kernel, 1 the large-set path from N = 2048 on
   if (c->env.pair_big == 0) return false;
@@ -1984,7 +1976,7 @@ static int launch_pair(dust_ctx *c, const PairArgs &a, int tiles) {
   do {                                                                                                                            \
     if (lds > 64 * 1024 && !c->capturing)                                                                                         \
       HIP_TRY(hipFuncSetAttribute((const void *)pairwise_kernel<MODE, CPT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    pairwise_kernel<MODE, CPT><<<grid, PAIR_NT, lds, c->pair_stream>>>(a);                                                             \
+    pairwise_kernel<MODE, CPT><<<grid, PAIR_NT, lds, c->stream>>>(a);                                                                  \
   } while (0)
   if (cpt == 4) DUST_LAUNCH_PAIR(4);
   else if (cpt == 8) DUST_LAUNCH_PAIR(8);
@@ -2001,7 +1993,7 @@ static int launch_pair_big(dust_ctx *c, const PairArgs &a, int tiles) {
   TRY(ensure(&c->xpad, &c->xpad_cap, (size_t)c->N * dpb));
   {
     const int n = c->N * dpb;
-    pad_rows_kernel<<<(n + 255) / 256, 256, 0, c->pair_stream>>>(a.X, c->xpad, c->N, a.D, dpb);
+    pad_rows_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(a.X, c->xpad, c->N, a.D, dpb);
     HIP_TRY(hipGetLastError());
   }
   PairBigArgs b;
@@ -2017,7 +2009,7 @@ static int launch_pair_big(dust_ctx *c, const PairArgs &a, int tiles) {
   do {                                                                                                                               \
     if (lds > 64 * 1024 && !c->capturing)                                                                                            \
       HIP_TRY(hipFuncSetAttribute((const void *)pairwise_big_kernel<MODE, DPB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    pairwise_big_kernel<MODE, DPB><<<grid, PAIR_NT, lds, c->pair_stream>>>(b);                                                       \
+    pairwise_big_kernel<MODE, DPB><<<grid, PAIR_NT, lds, c->stream>>>(b);                                                            \
   } while (0)
   if (dpb == 32) DUST_LAUNCH_BIG(32);
   else DUST_LAUNCH_BIG(64);
@@ -2033,7 +2025,6 @@ static int far_counts_alloc(dust_ctx *c);
 static int order_join(dust_ctx *c) {
   if (!c->order_pending) return DUST_OK;
   HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_order, 0));
-  if (c->pair_stream != c->stream) HIP_TRY(hipStreamWaitEvent(c->pair_stream, c->ev_order, 0));
   c->order_pending = false;
   return DUST_OK;
 }
@@ -2047,8 +2038,6 @@ __global__ void iota_kernel(int *p, int n) {
 // slice has units, at most 24 partial rows per particle for the merge kernels.  Static - a function of the shape alone: the
 // summation order does not depend on the data, and a captured tick keeps its grid.
 static int packed_slices(const dust_ctx *c, int tiles, int chunks) {
-  static const char *env = getenv("DUST_PACK_JS");  // development switch
-  if (env) return std::max(1, std::min(chunks, atoi(env)));
   const int want = (4 * device_cus(c) + tiles - 1) / tiles;
   // (fewer slices for the short merged lists were measured on a rank of 8: 8 slices 378-391 us per tick, 4 slices 456-460, against
   //  360-396 at 24 - a rank's tiles are less coherent than one GPU's, its lists longer)
@@ -2064,7 +2053,7 @@ static int launch_pair_fused(dust_ctx *c, const PairArgs &a, int tiles) {
   const bool whole_rows = a.D == dpb;  // (D = 80: the rows are their own padded copy - no pad_rows launch, 7 us per pass at N = 16 384)
   if (!whole_rows) {
     const int n = c->N * dpb;
-    pad_rows_kernel<<<(n + 255) / 256, 256, 0, c->pair_stream>>>(a.X, c->xpad, c->N, a.D, dpb);
+    pad_rows_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(a.X, c->xpad, c->N, a.D, dpb);
     HIP_TRY(hipGetLastError());
   }
   PairPackedArgs b;
@@ -2092,8 +2081,8 @@ static int launch_pair_fused(dust_ctx *c, const PairArgs &a, int tiles) {
     TRY(ensure(&c->pk_perm, &c->pk_perm_cap, (size_t)c->nloc));
     TRY(ensure(&c->pk_lead, &c->pk_lead_cap, (size_t)c->nloc));
     if (fresh) {  // index order, no leaders yet
-      iota_kernel<<<(c->nloc + 255) / 256, 256, 0, c->pair_stream>>>(reinterpret_cast<int *>(c->pk_perm), c->nloc);
-      HIP_TRY(hipMemsetAsync(c->pk_lead, 0x7f, (size_t)c->nloc * sizeof(int), c->pair_stream));
+      iota_kernel<<<(c->nloc + 255) / 256, 256, 0, c->stream>>>(reinterpret_cast<int *>(c->pk_perm), c->nloc);
+      HIP_TRY(hipMemsetAsync(c->pk_lead, 0x7f, (size_t)c->nloc * sizeof(int), c->stream));
     }
   }
   c->pk_order = order;
@@ -2143,10 +2132,10 @@ static int launch_pair_fused(dust_ctx *c, const PairArgs &a, int tiles) {
     const int nq = std::min(c->N - a.i0, tiles * tq);
 #define DUST_LAUNCH_FAR(DPB)                                                                         \
   do {                                                                                               \
-    far_lb_kernel<DPB><<<(nq + 63) / 64, 64 * DUST_FAR_LB_WAVES, 0, c->pair_stream>>>(f);            \
+    far_lb_kernel<DPB><<<(nq + 63) / 64, 64 * DUST_FAR_LB_WAVES, 0, c->stream>>>(f);                 \
     if (flags) {                                                                                     \
-      far_prep_kernel<DPB><<<(c->N + 3) / 4, 256, 0, c->pair_stream>>>(f);                           \
-      far_flags_kernel<DPB, FusedGeom<DPB>::TQ, true><<<fgrid, 256, far_flags_lds_bytes<DPB>(), c->pair_stream>>>(f); \
+      far_prep_kernel<DPB><<<(c->N + 3) / 4, 256, 0, c->stream>>>(f);                                \
+      far_flags_kernel<DPB, FusedGeom<DPB>::TQ, true><<<fgrid, 256, far_flags_lds_bytes<DPB>(), c->stream>>>(f);      \
     }                                                                                                \
   } while (0)
     if (dpb == 32) DUST_LAUNCH_FAR(32);
@@ -2183,7 +2172,7 @@ static int launch_pair_fused(dust_ctx *c, const PairArgs &a, int tiles) {
   pk.uq = reinterpret_cast<unsigned int *>(c->pk_uq);
   pk.soff = reinterpret_cast<int *>(c->pk_soff);
   pk.goff = reinterpret_cast<int *>(c->pk_goff);
-  far_pack_kernel<<<tiles, 1024, far_pack_lds_bytes(chunks), c->pair_stream>>>(pk);
+  far_pack_kernel<<<tiles, 1024, far_pack_lds_bytes(chunks), c->stream>>>(pk);
   HIP_TRY(hipGetLastError());
   c->pk_tiles = tiles;
   c->pk_umax = chunks;
@@ -2213,7 +2202,7 @@ static int launch_pair_fused(dust_ctx *c, const PairArgs &a, int tiles) {
     const size_t lds = pairwise_packed_lds_bytes<DPB>();                                                                                       \
     if (lds > 64 * 1024 && !c->capturing)                                                                                                      \
       HIP_TRY(hipFuncSetAttribute((const void *)pairwise_packed_kernel<MODE, DPB, SK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    pairwise_packed_kernel<MODE, DPB, SK><<<grid, PAIR_NT, lds, c->pair_stream>>>(b);                                                          \
+    pairwise_packed_kernel<MODE, DPB, SK><<<grid, PAIR_NT, lds, c->stream>>>(b);                                                               \
   } while (0)
 #define DUST_LAUNCH_FUSED(MODE, DPB)                   \
   do {                                                 \
@@ -2250,7 +2239,7 @@ static int far_counts_alloc(dust_ctx *c) {
   HIP_TRY(hipHostMalloc((void **)&c->far_cnt_host, 8 * sizeof(unsigned int), hipHostMallocCoherent | hipHostMallocMapped));
   memset(c->far_cnt_host, 0, 8 * sizeof(unsigned int));
   TRY(ensure(&c->far_cnt, &c->far_cnt_cap, 8));
-  HIP_TRY(hipMemsetAsync(c->far_cnt, 0, 8 * sizeof(unsigned int), c->pair_stream));
+  HIP_TRY(hipMemsetAsync(c->far_cnt, 0, 8 * sizeof(unsigned int), c->stream));
   return DUST_OK;
 }
 static bool logp_pack_ok(const dust_ctx *c);
@@ -2268,10 +2257,7 @@ static bool logp_far_decide(dust_ctx *c) {
   unsigned int spins = 0u;
   while (hc[2] != c->far_logp_issued) {  // the last pre-pass issued has not reported yet (back-to-back ticks): wait for it
     DUST_CPU_PAUSE();
-    if ((++spins & 1023u) == 0u && host_now() - t0 > 0.05) {  // (device stalled or gone: the next synchronisation will say)
-      if (getenv("DUST_DEBUG_FAR")) fprintf(stderr, "logp_far_decide: report %u awaited, %u seen\n", c->far_logp_issued, hc[2]);
-      return true;
-    }
+    if ((++spins & 1023u) == 0u && host_now() - t0 > 0.05) return true;  // (device stalled or gone: the next synchronisation will say)
   }
   std::atomic_thread_fence(std::memory_order_acquire);
   const unsigned int fa = hc[0], al = hc[1];
@@ -2287,7 +2273,6 @@ static bool logp_far_decide(dust_ctx *c) {
 // Large sets only: a rank's 2 048 rows cost 52 us dense and the pre-pass alone 45.
 static bool logp_pack_ok(const dust_ctx *c) {
   if (c->env.far == 0 || c->env.dense >= 0 || c->env.pack_merge == 0 || !(c->env.far_t < DUST_FAR_T_EXACT)) return false;
-  if (c->env.logp_pack >= 0) return c->env.logp_pack != 0;
   return c->nloc >= 8192;
 }
 static int launch_pair_logp_packed(dust_ctx *c, const PairArgs &a) {
@@ -2386,11 +2371,11 @@ static int launch_pair_logp_packed(dust_ctx *c, const PairArgs &a) {
   dim3 grid(groups, JS);
 #define DUST_LAUNCH_LOGPP(DPB)                                                                                                       \
   do {                                                                                                                              \
-    logp_prep_far_kernel<DPB><<<(c->N + 3) / 4, 256, 0, c->pair_stream>>>(b, f);                                                    \
-    far_lb_kernel<DPB><<<(std::min(c->N - a.i0, f.q_rows) + 63) / 64, 64 * DUST_FAR_LB_WAVES, 0, c->pair_stream>>>(f);              \
-    far_flags_kernel<DPB, 64, true><<<fgrid, 256, far_flags_lds_bytes<DPB>(), c->pair_stream>>>(f);                                 \
-    far_pack_kernel<<<groups, 1024, far_pack_lds_bytes(chunks), c->pair_stream>>>(pk);                                               \
-    pairwise_logp_packed_kernel<DPB><<<grid, 256, pairwise_logp_packed_lds_bytes<DPB>(), c->pair_stream>>>(p);                      \
+    logp_prep_far_kernel<DPB><<<(c->N + 3) / 4, 256, 0, c->stream>>>(b, f);                                                         \
+    far_lb_kernel<DPB><<<(std::min(c->N - a.i0, f.q_rows) + 63) / 64, 64 * DUST_FAR_LB_WAVES, 0, c->stream>>>(f);                   \
+    far_flags_kernel<DPB, 64, true><<<fgrid, 256, far_flags_lds_bytes<DPB>(), c->stream>>>(f);                                      \
+    far_pack_kernel<<<groups, 1024, far_pack_lds_bytes(chunks), c->stream>>>(pk);                                                    \
+    pairwise_logp_packed_kernel<DPB><<<grid, 256, pairwise_logp_packed_lds_bytes<DPB>(), c->stream>>>(p);                           \
   } while (0)
   if (dpb == 16) DUST_LAUNCH_LOGPP(16);
   else if (dpb == 32) DUST_LAUNCH_LOGPP(32);
@@ -2484,13 +2469,13 @@ static int launch_pair_logp_mfma(dust_ctx *c, const PairArgs &a) {
 #define DUST_LAUNCH_LOGPM(DPB)                                                                                                 \
   do {                                                                                                                          \
     if (flags) {                                                                                                                \
-      logp_prep_far_kernel<DPB><<<(c->N + 3) / 4, 256, 0, c->pair_stream>>>(b, f);                                              \
-      far_lb_kernel<DPB><<<(std::min(c->N - a.i0, f.q_rows) + 63) / 64, 64 * DUST_FAR_LB_WAVES, 0, c->pair_stream>>>(f);        \
-      far_flags_kernel<DPB, 64, false><<<fgrid, 256, far_flags_lds_bytes<DPB>(), c->pair_stream>>>(f);                                 \
+      logp_prep_far_kernel<DPB><<<(c->N + 3) / 4, 256, 0, c->stream>>>(b, f);                                                   \
+      far_lb_kernel<DPB><<<(std::min(c->N - a.i0, f.q_rows) + 63) / 64, 64 * DUST_FAR_LB_WAVES, 0, c->stream>>>(f);             \
+      far_flags_kernel<DPB, 64, false><<<fgrid, 256, far_flags_lds_bytes<DPB>(), c->stream>>>(f);                                      \
     } else {                                                                                                                    \
-      logp_prep_kernel<DPB><<<(c->N + 3) / 4, 256, 0, c->pair_stream>>>(b);                                                     \
+      logp_prep_kernel<DPB><<<(c->N + 3) / 4, 256, 0, c->stream>>>(b);                                                          \
     }                                                                                                                           \
-    pairwise_logp_mfma_kernel<DPB><<<grid, 256, pairwise_logp_mfma_lds_bytes<DPB>(), c->pair_stream>>>(b);                      \
+    pairwise_logp_mfma_kernel<DPB><<<grid, 256, pairwise_logp_mfma_lds_bytes<DPB>(), c->stream>>>(b);                           \
   } while (0)
   if (dpb == 16) DUST_LAUNCH_LOGPM(16);
   else if (dpb == 32) DUST_LAUNCH_LOGPM(32);
@@ -2510,7 +2495,7 @@ static int launch_pair_logp_big(dust_ctx *c, const PairArgs &a, int tiles) {
   const bool whole_rows = a.D == dpb;  // (D = 80: the rows are their own padded copy - no pad_rows launch, 7 us per pass at N = 16 384)
   if (!whole_rows) {
     const int n = c->N * dpb;
-    pad_rows_kernel<<<(n + 255) / 256, 256, 0, c->pair_stream>>>(a.X, c->xpad, c->N, a.D, dpb);
+    pad_rows_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(a.X, c->xpad, c->N, a.D, dpb);
     HIP_TRY(hipGetLastError());
   }
   PairFusedArgs b;
@@ -2521,7 +2506,7 @@ static int launch_pair_logp_big(dust_ctx *c, const PairArgs &a, int tiles) {
   b.wP[0] = a.inv_s[0] * a.inv_s[0];
   b.wP[1] = a.da == 2 ? a.inv_s[1] * a.inv_s[1] : b.wP[0];
   dim3 grid(tiles, a.JS);
-#define DUST_LAUNCH_LOGP(DPB) pairwise_logp_big_kernel<DPB><<<grid, PAIR_NT, pairwise_logp_big_lds_bytes<DPB>(), c->pair_stream>>>(b)
+#define DUST_LAUNCH_LOGP(DPB) pairwise_logp_big_kernel<DPB><<<grid, PAIR_NT, pairwise_logp_big_lds_bytes<DPB>(), c->stream>>>(b)
   if (dpb == 32) DUST_LAUNCH_LOGP(32);
   else if (dpb == 64) DUST_LAUNCH_LOGP(64);
   else DUST_LAUNCH_LOGP(80);
@@ -2607,8 +2592,8 @@ static int launch_whiten(dust_ctx *c) {
   TRY(ensure_whitened(c));
   const int n_pairs = c->N * c->H;
   const float *L = c->cfg.chol_p;
-  whiten_rows_kernel<<<(n_pairs + 255) / 256, 256, 0, c->pair_stream>>>(c->theta, c->theta_w, n_pairs, L[0], L[1], L[2]);
-  if (!c->mu_aliased) whiten_rows_kernel<<<(n_pairs + 255) / 256, 256, 0, c->pair_stream>>>(c->mu, c->mu_w, n_pairs, L[0], L[1], L[2]);
+  whiten_rows_kernel<<<(n_pairs + 255) / 256, 256, 0, c->stream>>>(c->theta, c->theta_w, n_pairs, L[0], L[1], L[2]);
+  if (!c->mu_aliased) whiten_rows_kernel<<<(n_pairs + 255) / 256, 256, 0, c->stream>>>(c->mu, c->mu_w, n_pairs, L[0], L[1], L[2]);
   HIP_TRY(hipGetLastError());
   return DUST_OK;
 }
@@ -2666,8 +2651,7 @@ static K2Args k2_args(dust_ctx *c);
 static int launch_fused(dust_ctx *c, const SampleOpts &o, bool *done) {
   *done = false;
   if (two_pass_family(c)) return DUST_OK;  // (these families run on the launch-per-iteration path: skid.hpp, particle_general.hpp)
-  static const bool off = getenv("DUST_NO_FUSE") != nullptr;  // development switch
-  if (off || c->no_handoff || c->handoff_banned || c->prof || o.want_actions || o.want_states || o.want_omega || o.costs_in || pair_is_big(c)) return DUST_OK;
+  if (c->env.no_fuse >= 0 || c->no_handoff || c->handoff_banned || c->prof || o.want_actions || o.want_states || o.want_omega || o.costs_in || pair_is_big(c)) return DUST_OK;
   FusedArgs f;
   memset(&f, 0, sizeof f);
   int nt;
@@ -2735,7 +2719,7 @@ static int launch_fused(dust_ctx *c, const SampleOpts &o, bool *done) {
   c->fused_dirty = true;
   c->stein_dirty = false;
   c->actions_valid = false;
-  if (k2_role) c->k2_bw_ahead = c->k2_bw_inline = true;
+  if (k2_role) c->k2_bw_inline = true;
   *done = true;
   return DUST_OK;
 }
@@ -2823,15 +2807,15 @@ static int launch_stein_update(dust_ctx *c, int apply, bool in_loop = false /* K
       const K2Args k = k2_args(c);
       // the bandwidths came with the prior + rollout launch (k2_inline_want): phi needs no transposed copy either when the update can go
       // to the other particle buffer (unsharded contexts: nobody else holds theta's address)
-      const bool inline_bw = c->k2_bw_ahead && c->k2_bw_inline;
+      const bool inline_bw = c->k2_bw_inline;
       const bool rows = inline_bw && apply && c->nloc == c->N && !c->theta_pinned && c->theta_alt && !k.shared;
-      if (!c->k2_bw_ahead) {  // (else: the bandwidths of this theta were computed beside the rollouts - in their launch, or step_device's forked form)
+      if (!inline_bw) {  // (else: the bandwidths of this theta were computed beside the rollouts, in their launch)
         if (!(in_loop && c->k2_thetaT_fresh)) TRY(launch_transpose(c, c->theta, c->thetaT, c->N, c->D));  // (fresh: the last update launch wrote it)
         TRY(launch_k2_bandwidth(c->stream, k));
-      } else if (inline_bw && !rows) {
+      } else if (!rows) {
         if (!(in_loop && c->k2_thetaT_fresh)) TRY(launch_transpose(c, c->theta, c->thetaT, c->N, c->D));
       }
-      c->k2_bw_ahead = c->k2_bw_inline = false;
+      c->k2_bw_inline = false;
       K2Args kp = k;
       if (apply) {  // the optimiser step rides in the phi kernel (no update_from_phi launch)
         const UpdateArgs u = update_args(c, 1);
@@ -2883,10 +2867,9 @@ static int launch_stein_update(dust_ctx *c, int apply, bool in_loop = false /* K
     a.pA = c->pA;
     a.pB = c->pB;
     a.stamps = c->stamps_dev ? c->stamps_dev + 16 * DUST_K_STEIN : nullptr;
-    static const bool no_fuse = getenv("DUST_NO_FUSE") != nullptr;  // development switch
     const int cpt = cpt_for(a.D);
     const size_t lds = pairwise_lds_bytes(PAIR_K1, cpt);
-    bool fuse = apply && !c->prof && !c->no_handoff && !c->handoff_banned && !no_fuse && cpt <= 8 && !pair_is_big(c);  // D <= 64: >= 2 workgroups per CU co-resident
+    bool fuse = apply && !c->prof && !c->no_handoff && !c->handoff_banned && c->env.no_fuse < 0 && cpt <= 8 && !pair_is_big(c);  // D <= 64: >= 2 workgroups per CU co-resident
     if (fuse && (!c->stein_cnt || c->stein_tiles != tiles)) {
       if (c->capturing) fuse = false;
       else {
@@ -2904,21 +2887,18 @@ static int launch_stein_update(dust_ctx *c, int apply, bool in_loop = false /* K
       // More key slices for the Stein tiles than for the prior tiles (which share their launch with the rollouts and are better off
       // few): a Stein workgroup is a chain of dependent chunk passes, and at ~500 of them the chip holds 2 waves per SIMD - cfg5
       // (64 tiles x 8 slices of 4 chunks): 26.5 us; 16 slices of 2: 24.7 (round 6).  The update role sums the slices this launch wrote.
-      static const bool stein_fine = getenv("DUST_STEIN_JS") == nullptr || atoi(getenv("DUST_STEIN_JS")) != 0;  // development switch
-      if (stein_fine) {
-        int js2 = a.JS, sl2 = a.slice;
-        while (tiles * js2 < 1024 && js2 * 2 <= 16 && sl2 >= 2 * PAIR_JC && (sl2 / 2) % PAIR_JC == 0) {
-          sl2 /= 2;
-          js2 = (c->N + sl2 - 1) / sl2;
-        }
-        const size_t need = (size_t)js2 * c->nloc * 8 * cpt;
-        if (js2 != a.JS && js2 <= 16 && (!c->capturing || (c->pA_cap >= need && c->pB_cap >= need))) {
-          TRY(ensure_partials(c, js2));
-          a.JS = js2;
-          a.slice = sl2;
-          a.pA = c->pA;
-          a.pB = c->pB;
-        }
+      int js2 = a.JS, sl2 = a.slice;
+      while (tiles * js2 < 1024 && js2 * 2 <= 16 && sl2 >= 2 * PAIR_JC && (sl2 / 2) % PAIR_JC == 0) {
+        sl2 /= 2;
+        js2 = (c->N + sl2 - 1) / sl2;
+      }
+      const size_t need = (size_t)js2 * c->nloc * 8 * cpt;
+      if (js2 != a.JS && js2 <= 16 && (!c->capturing || (c->pA_cap >= need && c->pB_cap >= need))) {
+        TRY(ensure_partials(c, js2));
+        a.JS = js2;
+        a.slice = sl2;
+        a.pA = c->pA;
+        a.pB = c->pB;
       }
       SteinUpdateArgs f;
       memset(&f, 0, sizeof f);
@@ -3012,41 +2992,10 @@ extern "C" int dust_svmpc_phi(dust_ctx *c, const float *costs, const float *acti
 
 // local half of one SVGD iteration: prior partials -> rollout (+ merge) -> score rows of this shard
 static int local_score_device(dust_ctx *c, const float *noise_dev, int param_set) {
-  // The prior pass and the rollout kernel both only READ theta: fork the prior pass onto the side stream, run the
-  // rollout kernel on the main stream, join, then combine (prior_finish: score = grad_lik + grad_pri).  With per-kernel
-  // event timing on (dust_profile_enable) everything stays on one stream so the timings remain attributable.
-  // Measured on MI355X (round 1): the cross-stream event waits cost more than the overlap gains at cfg2 sizes
-  // (2 695 vs 3 010 ticks/s), so the fork/join form is opt-in and the default folds the combine into rollout_kernel.
-  static const bool env_on = getenv("DUST_OVERLAP") != nullptr;
-  const bool overlap = !c->prof && env_on;
-  if (!overlap) {
-    SampleOpts of;
-    memset(&of, 0, sizeof of);
-    of.noise_mode = noise_dev ? NOISE_EPS : NOISE_PHILOX;
-    of.noise_dev = noise_dev;
-    of.base = c->theta;
-    of.update_a_mat = 1;
-    of.bump_adam = 1;
-    float *sv = c->params_dev;
-    if (c->params_dev) c->params_dev += (size_t)param_set * c->M * c->P;
-    bool done = false;
-    int sf = launch_fused(c, of, &done);
-    c->params_dev = sv;
-    TRY(sf);
-    if (done) {
-      c->have_sample = true;
-      return DUST_OK;
-    }
-  }
-  if (overlap) {
-    HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
-    HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-    c->pair_stream = c->stream2;
-  }
-  int sp = launch_prior(c);
-  c->pair_stream = c->stream;
-  TRY(sp);
-  if (overlap) HIP_TRY(hipEventRecord(c->ev_join, c->stream2));
+  // The prior pass and the rollout kernel both only READ theta: one launch for both where the shape allows it (launch_fused),
+  // else the prior pass, then the rollout kernel with the combine folded in (score = grad_lik + grad_pri), on one stream.
+  // Measured on MI355X (round 1): a fork / join form over two streams lost more to the cross-stream event waits than the
+  // overlap gained at cfg2 sizes (2 695 vs 3 010 ticks/s).
   SampleOpts o;
   memset(&o, 0, sizeof o);
   o.noise_mode = noise_dev ? NOISE_EPS : NOISE_PHILOX;
@@ -3054,16 +3003,18 @@ static int local_score_device(dust_ctx *c, const float *noise_dev, int param_set
   o.base = c->theta;
   o.update_a_mat = 1;
   o.bump_adam = 1;
-  const bool split = overlap || full_cov(c);  // (full prior covariance: the merge epilogue of the rollout kernel has no back-substitution)
+  const bool split = full_cov(c);  // (full prior covariance: the merge epilogue of the rollout kernel has no back-substitution)
   o.merge_prior = split ? 0 : 1;
   float *save = c->params_dev;
   if (c->params_dev) c->params_dev += (size_t)param_set * c->M * c->P;
-  int s = launch_rollout(c, o);
+  bool fused = false;
+  int s = launch_fused(c, o, &fused);
+  if (s == DUST_OK && !fused) s = launch_prior(c);
+  if (s == DUST_OK && !fused) s = launch_rollout(c, o);
   c->params_dev = save;
   TRY(s);
   c->have_sample = true;
-  if (overlap) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_join, 0));
-  if (split) TRY(launch_prior_finish(c, true, false));
+  if (!fused && split) TRY(launch_prior_finish(c, true, false));
   return DUST_OK;
 }
 
@@ -3072,8 +3023,7 @@ static int local_score_device(dust_ctx *c, const float *noise_dev, int param_set
 static int launch_iter(dust_ctx *c, const float *noise_dev, int param_set, bool *done) {
   *done = false;
   if (two_pass_family(c)) return DUST_OK;  // (these families run on the launch-per-iteration path: skid.hpp, particle_general.hpp)
-  static const bool off = getenv("DUST_NO_FUSE") != nullptr || getenv("DUST_NO_ITER") != nullptr;  // development switches
-  if (off || c->no_handoff || c->handoff_banned || c->prof || pair_is_big(c) || c->nloc != c->N || c->theta_pinned || !c->theta_alt) return DUST_OK;
+  if (c->env.no_fuse >= 0 || c->no_handoff || c->handoff_banned || c->prof || pair_is_big(c) || c->nloc != c->N || c->theta_pinned || !c->theta_alt) return DUST_OK;
   if (c->cfg.kernel != DUST_KERNEL_K1_RBF && c->cfg.kernel != DUST_KERNEL_IMQ) return DUST_OK;
   const int cpt = cpt_for(c->D);
   if (cpt > 8) return DUST_OK;
@@ -3108,28 +3058,26 @@ static int launch_iter(dust_ctx *c, const float *noise_dev, int param_set, bool 
   f.lds_roll_floats = (int)((lds_r / sizeof(float) + 3) & ~(size_t)3);
   const size_t lds = std::max(lds_p, (size_t)f.per_block * f.lds_roll_floats * sizeof(float));
   if (lds > 72 * 1024) return DUST_OK;
-  const int JS = f.prior.JS, lines = 2 * f.tiles + JS;
+  const int JS = f.prior.JS, lines = 2 * f.tiles;  // per counter set: the prior tiles' lines, then the Stein tiles'
   {
     const size_t nd = (size_t)JS * c->nloc * 8 * cpt;
     if (c->pS_cap < nd && c->capturing) return DUST_OK;
     TRY(ensure(&c->pS, &c->pS_cap, nd));
   }
-  if (!c->iter_cnt || c->iter_tiles != f.tiles || c->iter_js != JS) {
+  if (!c->iter_cnt || c->iter_tiles != f.tiles) {
     if (c->capturing) return DUST_OK;
     if (c->iter_cnt) HIP_TRY(hipFree(c->iter_cnt));
     c->iter_cnt = nullptr;
     TRY(dalloc(&c->iter_cnt, ((size_t)2 * lines + 1) * CNT_STRIDE));
     HIP_TRY(hipMemsetAsync(c->iter_cnt, 0, ((size_t)2 * lines + 1) * CNT_STRIDE * sizeof(unsigned int), c->stream));
     c->iter_tiles = f.tiles;
-    c->iter_js = JS;
     c->iter_set = 0;
     if (!c->score_hs) TRY(dalloc(&c->score_hs, (size_t)2 * c->N * c->D));
     HIP_TRY(hipMemsetAsync(c->score_hs, 0xFF, (size_t)2 * c->N * c->D * sizeof(float), c->stream));  // SCORE_SENTINEL in every word
   }
-  // Stein role: same geometry as the prior pass (pair_geometry), keys = queries = theta, values = the score rows
+  // Stein role: same geometry as the prior pass (pair_geometry), keys = queries = theta; the score rows arrive through score_pub
   f.stein = f.prior;
   f.stein.Y = c->theta;
-  f.stein.V = c->score;
   f.stein.logmix = nullptr;
   {
     const float ell = c->cfg.kernel == DUST_KERNEL_IMQ ? c->cfg.imq_ell : 0.69314718055994531f;
@@ -3149,17 +3097,13 @@ static int launch_iter(dust_ctx *c, const float *noise_dev, int param_set, bool 
   f.n_roll_blocks = c->nloc / f.per_block;
   unsigned int *set = c->iter_cnt + (size_t)c->iter_set * lines * CNT_STRIDE;
   f.cnt_prior = set;
-  f.cnt_score = set + (size_t)f.tiles * CNT_STRIDE;
-  f.cnt_stein = set + (size_t)(f.tiles + JS) * CNT_STRIDE;
+  f.cnt_stein = set + (size_t)f.tiles * CNT_STRIDE;
   f.zero_base = c->iter_cnt + (size_t)(1 - c->iter_set) * lines * CNT_STRIDE;
   f.zero_lines = lines;
   f.timeout_flag = c->iter_cnt + (size_t)2 * lines * CNT_STRIDE;
-  static const bool score_by_counter = getenv("DUST_SCORE_CNT") != nullptr;  // development switch: counter hand-off of the score rows
-  if (!score_by_counter) {
-    f.score_pub = c->score_hs + (size_t)c->iter_set * c->N * c->D;
-    f.score_reset = reinterpret_cast<unsigned int *>(c->score_hs + (size_t)(1 - c->iter_set) * c->N * c->D);
-    f.score_elems = c->N * c->D;
-  }
+  f.score_pub = c->score_hs + (size_t)c->iter_set * c->N * c->D;
+  f.score_reset = reinterpret_cast<unsigned int *>(c->score_hs + (size_t)(1 - c->iter_set) * c->N * c->D);
+  f.score_elems = c->N * c->D;
   f.tl = c->tl_dev;
   const int n = c->nloc * c->D;
   const int grid = 2 * f.n_pair_blocks + f.n_roll_blocks + (n + PAIR_NT - 1) / PAIR_NT;
@@ -3198,33 +3142,15 @@ static int step_device(dust_ctx *c, const float *noise_dev, int param_set) {
   // K2: the per-dimension median bandwidths read theta only.  Rounds 2-3 ran them on a side stream beside the prior + rollout launch;
   // the kernel trace of round 4 (profiles/round4_k2_kernel_stats.csv) shows what that bought: both kernels 30-40 % slower
   // side by side (24 / 24 us against 22 / 17 alone) and 10 us of cross-queue join in front of every phi launch - 55 us per iteration
-  // either way.  One stream, launches back to back, is the default now (DUST_K2_FORK=1: the forked form).
-  static const bool k2_fork = getenv("DUST_K2_FORK") != nullptr && getenv("DUST_NO_FUSE") == nullptr;  // development switch
+  // either way.  So they run on the context's stream.
   const bool k2 = c->cfg.kernel == DUST_KERNEL_K2_IIDMP || c->cfg.kernel == DUST_KERNEL_K2_SHARED;
   if (k2 && param_set == 0) c->k2_thetaT_fresh = false;  // (a new loop: whatever happened to theta since the last K2 update is not in thetaT)
-  if (k2 && k2_fork && !c->prof && c->stream2 && c->own_stream) {
-    HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
-    HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-    const int n = c->N * c->D;
-    if (!c->k2_thetaT_fresh) {
-      transpose_kernel<<<(n + 255) / 256, 256, 0, c->stream2>>>(c->theta, c->thetaT, c->N, c->D);
-      HIP_TRY(hipGetLastError());
-    }
-    c->k2_thetaT_fresh = false;
-    TRY(launch_k2_bandwidth(c->stream2, k2_args(c)));
-    HIP_TRY(hipEventRecord(c->ev_join, c->stream2));
-    int s = local_score_device(c, noise_dev, param_set);
-    HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_join, 0));  // (join even on failure: the capture, if any, must see the side stream return)
-    TRY(s);
-    c->k2_bw_ahead = true;
-    return launch_stein_update(c, 1, true);
-  }
   // K2, one dimension per kernel (every demo), N <= 1024: the bandwidths as a role of the prior + rollout launch (when that launch is taken)
-  c->k2_inline_want = c->cfg.kernel == DUST_KERNEL_K2_IIDMP && c->env.k2_form != 0 && c->env.k2_form != 3 && !c->prof && c->N <= 1024 &&
+  c->k2_inline_want = c->cfg.kernel == DUST_KERNEL_K2_IIDMP && c->env.k2_form != 0 && !c->prof && c->N <= 1024 &&
                       c->k2_fixed_h <= 0.f && c->da <= 2;
   int sl = local_score_device(c, noise_dev, param_set);
   c->k2_inline_want = false;
-  if (sl != DUST_OK) c->k2_bw_ahead = c->k2_bw_inline = false;  // (no phi launch will consume the bandwidths of this theta)
+  if (sl != DUST_OK) c->k2_bw_inline = false;  // (no phi launch will consume the bandwidths of this theta)
   TRY(sl);
   TRY(launch_stein_update(c, 1, true));
   return DUST_OK;
@@ -3314,7 +3240,7 @@ static RollArgs roll_args(dust_ctx *c, int steps, int strategy, const float *las
   r.s0_restart = opt_restart_s0(c->opt);
   if (c->iter_cnt) {
     r.rearm = c->iter_cnt;
-    r.rearm_lines = 2 * (2 * c->iter_tiles + c->iter_js);
+    r.rearm_lines = 2 * (2 * c->iter_tiles);
     r.hs = reinterpret_cast<unsigned int *>(c->score_hs);
     r.hs_n = 2 * c->N * c->D;
   }
@@ -3464,10 +3390,10 @@ extern "C" int dust_svmpc_forward_ex(dust_ctx *c, int steps, const float *resamp
 
 // ---------------------------------------------------------------------------------------------------------------
 // One launch per control tick, owner-computes form (tick2.hpp): two all-to-all hand-offs per SVGD iteration instead of four.
-// *done stays false when the shape / configuration does not qualify (persist.hpp's form or the launch-per-iteration path run).
+// *done stays false when the shape / configuration does not qualify (the launch-per-iteration path runs).
 // the static part of launch_tick2's eligibility (everything but "the prior means alias the particles")
 static bool tick2_shape_ok(dust_ctx *c, int n_steps) {
-  if (c->env.no_tick2 >= 0 || c->env.no_fuse >= 0 || c->env.no_persist >= 0) return false;
+  if (c->env.no_tick2 >= 0 || c->env.no_fuse >= 0) return false;
   if (c->prof || c->handoff_banned || c->nloc != c->N || c->theta_pinned || n_steps < 1) return false;
   if ((c->cfg.model != DUST_MODEL_PENDULUM && c->cfg.model != DUST_MODEL_PARTICLE) || two_pass_family(c)) return false;
   if (c->cfg.kernel != DUST_KERNEL_K1_RBF && c->cfg.kernel != DUST_KERNEL_IMQ) return false;
@@ -3488,7 +3414,7 @@ static bool tick2_shape_ok(dust_ctx *c, int n_steps) {
 static int launch_tick2(dust_ctx *c, const float *state, int n_steps, const float *eps_dev, bool do_forward, bool *done) {
   *done = false;
   if (two_pass_family(c)) return DUST_OK;  // (these families run on the launch-per-iteration path: skid.hpp, particle_general.hpp)
-  if (c->env.no_tick2 >= 0 || c->env.no_fuse >= 0 || c->env.no_persist >= 0) return DUST_OK;  // development switches
+  if (c->env.no_tick2 >= 0 || c->env.no_fuse >= 0) return DUST_OK;  // development switches
   if (c->prof || c->nloc != c->N || c->theta_pinned || c->capturing || !c->mu_aliased) return DUST_OK;
   if (c->cfg.kernel != DUST_KERNEL_K1_RBF && c->cfg.kernel != DUST_KERNEL_IMQ) return DUST_OK;
   if (n_steps < 0 || (n_steps == 0 && !do_forward)) return DUST_OK;
@@ -4118,7 +4044,7 @@ static void t2_queue_push(dust_ctx *c, const float *state4, int steps, bool fwd,
 static int try_persistent(dust_ctx *c, const float *state, int n_steps, const float *eps, const float *params, int flags, bool do_forward,
                           bool *done) {
   *done = false;
-  const bool off = c->env.no_fuse >= 0 || c->env.no_persist >= 0 || c->params_staged;
+  const bool off = c->env.no_fuse >= 0 || c->env.no_tick2 >= 0 || c->params_staged;
   if (off || c->no_handoff || c->handoff_banned || c->prof || c->nloc != c->N || c->theta_pinned || n_steps < 0 || (flags & DUST_EPS_F16)) return DUST_OK;
   if (c->cfg.kernel != DUST_KERNEL_K1_RBF && c->cfg.kernel != DUST_KERNEL_IMQ) return DUST_OK;
   if (c->N > 4096 || c->D > 64 || pair_is_big(c) || two_pass_family(c)) return DUST_OK;
@@ -4156,7 +4082,7 @@ static int tick_outputs(dust_ctx *c, float *a_seq, float *p_weights) {
     if (c->fused_cnt) HIP_TRY(hipMemcpyAsync(lf + 0, c->fused_cnt + (size_t)c->fused_tiles * CNT_STRIDE, 4, hipMemcpyDeviceToHost, c->stream));
     if (c->stein_cnt) HIP_TRY(hipMemcpyAsync(lf + 1, c->stein_cnt + ((size_t)c->stein_tiles + 1) * CNT_STRIDE, 4, hipMemcpyDeviceToHost, c->stream));
     if (c->iter_cnt)
-      HIP_TRY(hipMemcpyAsync(lf + 2, c->iter_cnt + (size_t)2 * (2 * c->iter_tiles + c->iter_js) * CNT_STRIDE, 4, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipMemcpyAsync(lf + 2, c->iter_cnt + (size_t)2 * (2 * c->iter_tiles) * CNT_STRIDE, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const unsigned int *st = reinterpret_cast<const unsigned int *>(c->out_pinned + c->out_floats - 32);
     if (st[0] && c->t2_inflight && c->t2_transactional) {  // the owner-computes kernel commits nothing when a wait gave up (tick2.hpp COMMIT): replayed below
@@ -4179,7 +4105,7 @@ static int tick_outputs(dust_ctx *c, float *a_seq, float *p_weights) {
   if (lf[0] | lf[1] | lf[2]) {  // reported once: clear the device words (the kernels that set them are not launched again)
     if (c->fused_cnt) (void)hipMemsetAsync(c->fused_cnt + (size_t)c->fused_tiles * CNT_STRIDE, 0, 4, c->stream);
     if (c->stein_cnt) (void)hipMemsetAsync(c->stein_cnt + ((size_t)c->stein_tiles + 1) * CNT_STRIDE, 0, 4, c->stream);
-    if (c->iter_cnt) (void)hipMemsetAsync(c->iter_cnt + (size_t)2 * (2 * c->iter_tiles + c->iter_js) * CNT_STRIDE, 0, 4, c->stream);
+    if (c->iter_cnt) (void)hipMemsetAsync(c->iter_cnt + (size_t)2 * (2 * c->iter_tiles) * CNT_STRIDE, 0, 4, c->stream);
   }
   if (lf[0] | lf[1] | lf[2]) return handoff_timeout(c, "a fused launch's in-kernel hand-off timed out (results of this tick are invalid); the device seems to be shared with another process: this context runs plain kernels from here on");
   if (a_seq) memcpy(a_seq, c->out_pinned, c->D * sizeof(float));
@@ -4457,7 +4383,7 @@ extern "C" int dust_svmpc_tick(dust_ctx *c, const float *state, int n_steps, con
   } else if (c->armed || c->cancel_unsettled) {
     TRY(settle_pending(c));  // (a call the armed launch was not made for)
   }
-  {  // one persistent launch for the whole tick when the shape allows it (persist.hpp)
+  {  // one persistent launch for the whole tick when the shape allows it (tick2.hpp)
     bool done = false;
     TRY(try_persistent(c, state, n_steps, eps, params, flags, /*do_forward=*/true, &done));
     if (done) {
@@ -4466,11 +4392,10 @@ extern "C" int dust_svmpc_tick(dust_ctx *c, const float *state, int n_steps, con
     }
   }
   TRY(settle_pending(c));  // (plain kernels / a captured graph from here on)
-  static const bool no_graph = getenv("DUST_NO_GRAPH") != nullptr;  // development switch
   // (a second context on the device: the in-launch hand-off kernels are chained across streams at every launch - PersistChain - which a
   //  replayed capture would not be)
   const bool tenants = c->cfg.device >= 0 && c->cfg.device < DUST_MAX_DEV && g_live_ctx[c->cfg.device].load() >= 2;
-  const bool graphable = !no_graph && !c->prof && c->nloc == c->N && n_steps > 0 && (eps == nullptr || (flags & DUST_PTR_DEVICE)) &&
+  const bool graphable = !c->prof && c->nloc == c->N && n_steps > 0 && (eps == nullptr || (flags & DUST_PTR_DEVICE)) &&
                          c->mu_aliased && c->own_stream && !tenants && c->cz_next >= c->cz_sets /* no recorded control noise pending */;
   struct FarTick {  // this tick's log-p pre-pass decision, taken once (see logp_far_decide)
     dust_ctx *c;

@@ -55,7 +55,7 @@ __global__ __launch_bounds__(PAIR_NT, (CPT <= 4 ? 4 : 2)) void fused_prior_rollo
     const int nb = (int)gridDim.x - f.n_k2_blocks - f.n_pair_blocks;
     const int b = (f.n_pair_blocks & 7) ? bx - f.n_pair_blocks : xcd_contiguous(bx - f.n_pair_blocks, nb);
     const int sub = (int)threadIdx.x / f.sub_nt, tid = (int)threadIdx.x - sub * f.sub_nt;
-    const FusedWait fw{f.cnt, (unsigned int)f.pa.JS, f.timeout_flag, nullptr, 1, 0, nullptr, nullptr};
+    const FusedWait fw{f.cnt, (unsigned int)f.pa.JS, f.timeout_flag, nullptr, nullptr};
     rollout_body<MODEL, 12, GROUPS, true>(f.ra, lds + (size_t)sub * f.lds_roll_floats, tid, f.sub_nt, b * f.per_block + sub, &fw);
   }
 }
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(PAIR_NT, (CPT <= 4 ? 4 : 2)) void stein_update_kern
 // One launch per SVGD iteration (K1 / IMQ, D <= 64, N < 2048, single-chunk key slices, ping-ponged theta).  Roles by
 // workgroup index, producers before consumers:
 //   [0, P)            prior tiles              -> prior partials   (cnt_prior[tile], JS arrivals)
-//   [P, P + R)        rollouts                 -> score rows       (cnt_score[key slice], `slice` arrivals)
+//   [P, P + R)        rollouts                 -> score rows       (published as data: score_pub)
 //   [P + R, 2P + R)   Stein tiles              -> Stein partials   (cnt_stein[tile], JS arrivals)
 //   [2P + R, ...)     optimiser update (256 elements each), writes the OTHER theta buffer
 // Every input of the launch that is written inside it travels write-through (sc1 stores, sc1 loads, one arrival counter per
@@ -136,7 +136,7 @@ struct IterArgs {
   UpdateArgs ua;
   int tiles, n_pair_blocks, n_roll_blocks;
   int sub_nt, per_block, lds_roll_floats;
-  unsigned int *cnt_prior, *cnt_score, *cnt_stein;  // this launch's set
+  unsigned int *cnt_prior, *cnt_stein;             // this launch's set
   unsigned int *zero_base;                          // the other set ...
   int zero_lines;                                   // ... of this many 128-byte lines
   unsigned int *timeout_flag;
@@ -156,8 +156,7 @@ __global__ __launch_bounds__(PAIR_NT, (CPT <= 4 ? 4 : 2)) void svgd_iter_kernel(
   if (b0 < f.n_pair_blocks) {
     if (b0 == 0)
       for (int t = threadIdx.x; t < f.zero_lines; t += PAIR_NT) f.zero_base[t * CNT_STRIDE] = 0u;
-    if (f.score_reset)
-      for (int e = b0 * PAIR_NT + (int)threadIdx.x; e < f.score_elems; e += f.n_pair_blocks * PAIR_NT) f.score_reset[e] = SCORE_SENTINEL;
+    for (int e = b0 * PAIR_NT + (int)threadIdx.x; e < f.score_elems; e += f.n_pair_blocks * PAIR_NT) f.score_reset[e] = SCORE_SENTINEL;
     const int tile_x = b0 % f.tiles, js = b0 / f.tiles;
     pairwise_body<PAIR_PRIOR, CPT>(f.prior, lds, tile_x, js, /*write_through=*/true);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -168,13 +167,13 @@ __global__ __launch_bounds__(PAIR_NT, (CPT <= 4 ? 4 : 2)) void svgd_iter_kernel(
     const int br = b0 - f.n_pair_blocks;
     const int b = ((f.n_pair_blocks | f.n_roll_blocks) & 7) ? br : xcd_contiguous(br, f.n_roll_blocks);
     const int sub = (int)threadIdx.x / f.sub_nt, tid = (int)threadIdx.x - sub * f.sub_nt;
-    const FusedWait fw{f.cnt_prior, (unsigned int)f.prior.JS, f.timeout_flag, f.cnt_score, f.stein.slice, f.per_block, f.tl, f.score_pub};
+    const FusedWait fw{f.cnt_prior, (unsigned int)f.prior.JS, f.timeout_flag, f.tl, f.score_pub};
     rollout_body<MODEL, 12, false, true>(f.ra, lds + (size_t)sub * f.lds_roll_floats, tid, f.sub_nt, b * f.per_block + sub, &fw);
     DUST_TL(f.tl, 3);
   } else if (b0 < 2 * f.n_pair_blocks + f.n_roll_blocks) {
     const int bs = b0 - f.n_pair_blocks - f.n_roll_blocks;
     const int tile_x = bs % f.tiles, js = bs / f.tiles;
-    stein_split_body<MODE, CPT>(f.stein, lds, tile_x, js, f.cnt_score, f.score_pub, f.timeout_flag, f.tl);
+    stein_split_body<MODE, CPT>(f.stein, lds, tile_x, js, f.score_pub, f.timeout_flag, f.tl);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     wg_sync();
     if (threadIdx.x == 0) __hip_atomic_fetch_add(f.cnt_stein + tile_x * CNT_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

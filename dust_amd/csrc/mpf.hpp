@@ -903,7 +903,23 @@ struct dust_mpf {
   float *hpin;            // pinned host staging: gradient norms [4096] + status words
   bool grid_banned;       // a wait of the grid form timed out once (device shared with another process): single-workgroup kernel from then on
   long long n_grid, n_grid_fallback;
+  // development switches and test hooks, read ONCE by dust_mpf_create (mpf_env_read): atoi of the value
+  struct {
+    int grid;       // DUST_MPF_GRID (-1: unset)
+    int poll;       // DUST_MPF_POLL (-1: unset)
+    int grid_test;  // DUST_MPF_GRID_TEST (0: unset)
+  } env;
 };
+
+static int mpf_env_int(const char *name, int unset) {
+  const char *v = getenv(name);
+  return v ? atoi(v) : unset;
+}
+static void mpf_env_read(dust_mpf *m) {
+  m->env.grid = mpf_env_int("DUST_MPF_GRID", -1);
+  m->env.poll = mpf_env_int("DUST_MPF_POLL", -1);
+  m->env.grid_test = mpf_env_int("DUST_MPF_GRID_TEST", 0);
+}
 
 static DevModel mpf_dev_model(const dust_mpf *m) {
   dust_ctx fake;
@@ -960,6 +976,7 @@ extern "C" int dust_mpf_create(const dust_mpf_config *cfg, const float *init_par
   m->opt = optim_plain(DUST_OPT_SGD, cfg->lr, 0.f, 0.f, 0.f);
   m->Mp = cfg->n_particles;
   m->P = cfg->dim_p;
+  mpf_env_read(m);
   *out = m;
   HIP_TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
   TRY(dalloc(&m->x, (size_t)m->Mp * m->P));
@@ -1063,9 +1080,8 @@ enum { MPF_GCNT_WORDS = (2 * dust::MPF_G_NSH + 2) * dust::MPF_G_LINE };
 // DUST_MPF_GRID=0 / 1: never / from 8 particles on (tests); DUST_MPF_POLL=0: the counter form.
 static bool mpf_grid_ok(const dust_mpf *m, int n_steps, bool optimise) {
   if (!optimise || n_steps < 2 || m->grid_banned) return false;
-  const char *env = getenv("DUST_MPF_GRID");
-  if (env && atoi(env) == 0) return false;
-  return m->Mp >= ((env && atoi(env) == 1) ? 8 : 96);
+  if (m->env.grid == 0) return false;
+  return m->Mp >= (m->env.grid == 1 ? 8 : 96);
 }
 
 // Effective action of every SVGD step of the coming launch when the model carries control noise: acts = past_action + dyn_std * z, one
@@ -1147,7 +1163,7 @@ static int mpf_launch(dust_mpf *m, float bw, float lr, int n_steps, float *gn_de
   }
   a.t0 = m->opt_t;
   // the data-polled form (keys in registers) unless DUST_MPF_POLL=0, which selects the counter form
-  if (grid && m->Mp <= MPF_POLL_MAX && !(getenv("DUST_MPF_POLL") && atoi(getenv("DUST_MPF_POLL")) == 0)) {
+  if (grid && m->Mp <= MPF_POLL_MAX && m->env.poll != 0) {
     const int NP = (m->P + 1) / 2, NX = NP + 1;
     const size_t fx = (size_t)2 * m->Mp * NX * 4, fs = (size_t)2 * m->Mp * NP * 4;  // floats
     if (!m->pbuf) {
@@ -1171,7 +1187,7 @@ static int mpf_launch(dust_mpf *m, float bw, float lr, int n_steps, float *gn_de
     g.status = m->gcnt + MPF_GCNT_WORDS;
     g.seq = ++m->pseq;
     g.tag0 = g.seq * 8192u;  // (n_steps <= 4096: 2 tags per step)
-    if (const char *t = getenv("DUST_MPF_GRID_TEST")) g.test = atoi(t);
+    g.test = m->env.grid_test;
     const int G = (m->Mp + MPF_G_WAVES - 1) / MPF_G_WAVES;
 #define DUST_LAUNCH_MPFP(PP)                                                                       \
   do {                                                                                              \
@@ -1208,7 +1224,7 @@ static int mpf_launch(dust_mpf *m, float bw, float lr, int n_steps, float *gn_de
     g.n2g = m->gbuf + 4 * np;
     g.cnt = m->gcnt;
     g.status = m->gcnt + MPF_GCNT_WORDS;
-    if (const char *t = getenv("DUST_MPF_GRID_TEST")) g.test = atoi(t);
+    g.test = m->env.grid_test;
     const int G = (m->Mp + MPF_G_WAVES - 1) / MPF_G_WAVES;
     const size_t lds = sizeof(float) * ((size_t)2 * np + m->Mp + 8);
     if (m->P == 1) mpf_optimize_grid_kernel<1><<<G, MPF_G_NT, lds, m->stream>>>(g);

@@ -1,5 +1,5 @@
 // particle_general.hpp - the Particle rollouts the specialised kernels (rollout.hpp packed pairs, rollout_states.hpp whole lines,
-// persist.hpp) do not take: control-channel noise and velocity control.
+// tick2.hpp) do not take: control-channel noise and velocity control.
 //
 // Replaces (reference file:line): Particle.step particle.py:117-166 in full -
 //   * `if not self.deterministic: acts += self.dyn_std * torch.randn_like(acts)` (particle.py:145-148; deterministic=False is the

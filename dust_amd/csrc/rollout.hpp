@@ -98,14 +98,10 @@ struct FusedWait {
   const unsigned int *cnt;  // [tiles][CNT_STRIDE]
   unsigned int target;
   unsigned int *timeout_flag;
-  // one-launch SVGD iteration (fused.hpp svgd_iter_kernel): the score rows are published to the Stein tiles of the SAME launch -
-  // written through (sc1), then one arrival per workgroup on the counter of the key slice its particles belong to
-  unsigned int *score_cnt;  // [JS][CNT_STRIDE] or nullptr
-  int score_slice;          // keys per slice (a multiple of the particles per workgroup)
-  int score_add;            // particles per workgroup
   unsigned long long *tl;   // diagnostic build only: launch timeline words
-  // score rows published AS DATA: written through into a buffer that holds a sentinel in every word until then; the Stein
-  // tiles poll the rows themselves - no drain, no barrier, no counter between the last store and the consumer (or nullptr)
+  // one-launch SVGD iteration (fused.hpp svgd_iter_kernel): the score rows are published AS DATA to the Stein tiles of the SAME
+  // launch - written through into a buffer that holds a sentinel in every word until then; the Stein tiles poll the rows
+  // themselves - no drain, no barrier, no counter between the last store and the consumer (or nullptr)
   float *score_pub;
 };
 
@@ -723,7 +719,7 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs &a, float *lds, c
     // ahead of the prior-partial loads below: vector-memory operations retire in order, so the wait on those loads (which the
     // score needs) also covers this add, and the score rows - the update role's only way to learn that the rollouts are done -
     // cannot become visible before it
-    if (fw && (fw->score_cnt || fw->score_pub)) __hip_atomic_fetch_add(a.ctr + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (fw && fw->score_pub) __hip_atomic_fetch_add(a.ctr + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else a.ctr[2] += 1u;
   }
   // prior partials of this row: the (independent) loads are issued HERE - after the softmax, whose wave reductions would
@@ -836,8 +832,6 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs &a, float *lds, c
       if (fw && fw->score_pub) {
         a.score[o] = gs + gp;
         __hip_atomic_store(fw->score_pub + o, gs + gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      } else if (fw && fw->score_cnt) {
-        __hip_atomic_store(a.score + o, gs + gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       } else {
         a.score[o] = gs + gp;
       }
@@ -847,13 +841,6 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs &a, float *lds, c
     for (int t = tid; t < a.rearm_n; t += nt) a.rearm[t * CNT_STRIDE] = 0u;
   DUST_STAMP(a.stamps, 5);
   DUST_TL(fw ? fw->tl : nullptr, 2);
-  if (fw && fw->score_cnt && !fw->score_pub) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its write-through stores ...
-    wg_sync();                                    // ... before the one lane that signals for the workgroup
-    if (threadIdx.x == 0)
-      __hip_atomic_fetch_add(fw->score_cnt + (nl / fw->score_slice) * CNT_STRIDE, (unsigned int)fw->score_add, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
-  }
 }
 
 // XCD-aware block -> work-item map.  Consecutive workgroup ids are dealt round-robin to the 8 XCDs (each with its own

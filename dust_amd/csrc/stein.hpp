@@ -65,8 +65,7 @@ struct RowLane {
   static constexpr int RB = NT / W;
   static constexpr int NB = TR / RB;
 };
-// SC1: the rows were written (write-through) by other workgroups of the SAME launch: every load bypasses this CU's L1
-template <int TR, int DP, int NT, bool SC1 = false>
+template <int TR, int DP, int NT>
 __device__ __forceinline__ void rowlane_issue(const float *__restrict__ src, int r0, int nrows, int D, float (&v)[RowLane<TR, DP, NT>::NB],
                                               const int tx = (int)threadIdx.x) {
   using RL = RowLane<TR, DP, NT>;
@@ -75,7 +74,7 @@ __device__ __forceinline__ void rowlane_issue(const float *__restrict__ src, int
 #pragma unroll
   for (int u = 0; u < RL::NB; ++u) {
     const float *p = base + (size_t)min(u * RL::RB + lr, nrows - 1) * D;
-    v[u] = SC1 ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p;
+    v[u] = *p;
   }
 }
 template <int TR, int DP, int LS, int NT, bool SCALE>
@@ -93,12 +92,8 @@ __device__ __forceinline__ void rowlane_commit(const float (&v)[RowLane<TR, DP, 
   }
 }
 
-template <int MODE, int CPT /* columns per lane in pass B: multiple of 4, 8*CPT >= D */, bool SC1 = false /* X / Y were written inside this launch */>
-__device__ __forceinline__ void pairwise_body(const PairArgs &a, float *lds, const int tile_x, const int js, const bool write_through = false,
-                                              const float *Xo = nullptr, const float *Yo = nullptr /* override a.X / a.Y (persistent tick) */,
-                                              const int tx = (int)threadIdx.x /* lane index; the persistent tick passes an opaque copy per
-                                              iteration so that the lane-derived addresses of every body are not all hoisted out of its loop */,
-                                              unsigned long long *tlp = nullptr /* diagnostic build: timeline slots */) {
+template <int MODE, int CPT /* columns per lane in pass B: multiple of 4, 8*CPT >= D */>
+__device__ __forceinline__ void pairwise_body(const PairArgs &a, float *lds, const int tile_x, const int js, const bool write_through = false) {
   constexpr int TI = PAIR_TI, JC = PAIR_JC, NT = PAIR_NT;
   constexpr bool PRI = MODE == PAIR_PRIOR || MODE == PAIR_LOGP;  // softmax-weighted passes over the prior mixture
   constexpr bool LOGP = MODE == PAIR_LOGP;                        // ... of which forward needs only the log-density
@@ -111,7 +106,7 @@ __device__ __forceinline__ void pairwise_body(const PairArgs &a, float *lds, con
   float *Vs = Ys + JC * YS;         // [JC][YS]   score (Stein), unscaled
   float *kv = Vs + (PRI ? 0 : JC * YS);  // [TI][JC + 1]
   float *mrow = kv + TI * (JC + 1); // [TI] running max
-  const int tid = tx;
+  const int tid = threadIdx.x;
   const int D = a.D, da = a.da, N = a.N;
   const int ib = a.i0 + tile_x * TI;  // first query (global index)
   const int jbeg = js * a.slice, jend = min(N, jbeg + a.slice);
@@ -121,9 +116,9 @@ __device__ __forceinline__ void pairwise_body(const PairArgs &a, float *lds, con
   const int nq = min(TI, a.i0 + a.n_local - ib), jc0 = min(JC, jend - jbeg);
   {
     float vx[RowLane<TI, DP, NT>::NB], vy[RowLane<JC, DP, NT>::NB], vv[RowLane<JC, DP, NT>::NB];
-    rowlane_issue<TI, DP, NT, SC1>(Xo ? Xo : a.X, ib, nq, D, vx, tid);
-    rowlane_issue<JC, DP, NT, SC1>(Yo ? Yo : a.Y, jbeg, jc0, D, vy, tid);
-    if (!PRI) rowlane_issue<JC, DP, NT, SC1>(a.V, jbeg, jc0, D, vv, tid);
+    rowlane_issue<TI, DP, NT>(a.X, ib, nq, D, vx, tid);
+    rowlane_issue<JC, DP, NT>(a.Y, jbeg, jc0, D, vy, tid);
+    if (!PRI) rowlane_issue<JC, DP, NT>(a.V, jbeg, jc0, D, vv, tid);
     if (tid < TI) mrow[tid] = -INFINITY;
     rowlane_commit<TI, DP, DP, NT, true>(vx, nq, D, da, a.inv_s, Xs, tid);
     rowlane_commit<JC, DP, YS, NT, true>(vy, jc0, D, da, a.inv_s, Ys, tid);
@@ -159,14 +154,13 @@ __device__ __forceinline__ void pairwise_body(const PairArgs &a, float *lds, con
     const float lm = (PRI) ? a.logmix[j0 + min(jA, jc - 1)] : 0.f;  // issued with the tile loads
     if (j0 != jbeg) {  // later chunks of a long slice (the first one was staged with the query tile)
       float vy[RowLane<JC, DP, NT>::NB], vv[RowLane<JC, DP, NT>::NB];
-      rowlane_issue<JC, DP, NT, SC1>(Yo ? Yo : a.Y, j0, jc, D, vy, tid);
-      if (!PRI) rowlane_issue<JC, DP, NT, SC1>(a.V, j0, jc, D, vv, tid);
+      rowlane_issue<JC, DP, NT>(a.Y, j0, jc, D, vy, tid);
+      if (!PRI) rowlane_issue<JC, DP, NT>(a.V, j0, jc, D, vv, tid);
       rowlane_commit<JC, DP, YS, NT, true>(vy, jc, D, da, a.inv_s, Ys, tid);  // the barrier that ended the previous chunk's pass B
       if (!PRI) rowlane_commit<JC, DP, YS, NT, false>(vv, jc, D, da, a.inv_s, Vs, tid);  // protects these writes
       wg_sync();
     }
     DUST_STAMP(a.stamps, 2);
-    DUST_TLP(tlp, 3);
     // ---- pass A: lane = key j, QPG queries per lane; packed math: 2 dims per v_pk_add / v_pk_fma ----
     {
       // packed math: 2 dims per v_pk_add / v_pk_fma.  (The Gram value uses the bare v_exp_f32: inlining ocml expf eight
@@ -197,7 +191,6 @@ __device__ __forceinline__ void pairwise_body(const PairArgs &a, float *lds, con
       }
     }
     wg_sync();
-    DUST_TLP(tlp, 4);
     if (PRI) {
       // online softmax over key chunks: row max (8 lanes per query), rescale, exponentiate in place
       float m = -INFINITY;
@@ -228,7 +221,6 @@ __device__ __forceinline__ void pairwise_body(const PairArgs &a, float *lds, con
       wg_sync();
     }
     DUST_STAMP(a.stamps, 3);
-    DUST_TLP(tlp, 5);
     // ---- pass B: lane = (query, 8 column groups); packed math ----
     if (MFMA_A) {
       // A[i = col][k = key] = S[key][col] (lane: i = l % 16, k = l / 16), B[k = key][j = query] = K[query][key] (lane:
@@ -272,7 +264,6 @@ __device__ __forceinline__ void pairwise_body(const PairArgs &a, float *lds, con
   }
 
   DUST_STAMP(a.stamps, 4);
-  DUST_TLP(tlp, 6);
   // ---- partial outputs (differences were accumulated in scaled coordinates: undo the 1/s_d) ----
   const int il = tile_x * TI + iB;  // local row
   if (il < a.n_local) {
@@ -316,7 +307,6 @@ __device__ __forceinline__ void pairwise_body(const PairArgs &a, float *lds, con
     }
   }
   DUST_STAMP(a.stamps, 5);
-  DUST_TLP(tlp, 7);
 }
 
 // Stein tile of the one-launch SVGD iteration (fused.hpp svgd_iter_kernel): the same arithmetic as pairwise_body<K1|IMQ> on a
@@ -324,18 +314,9 @@ __device__ __forceinline__ void pairwise_body(const PairArgs &a, float *lds, con
 // theta - the Gram values (pass A) and the repulsive term sum_j k'_ij (x_i - x_j) - runs BEFORE the wait on the score rows,
 // i.e. underneath the rollouts of the same launch; after the wait only the score tile load, the Gram x score MFMAs and the
 // 16-byte partial stores remain on the critical path.  Accumulation orders are those of pairwise_body (bitwise equal).
-// arrival lines [line0, line0 + nlines) of `cnt` (one counter per 128-byte line), each with its own target
-struct LineGate {
-  const unsigned int *cnt;
-  int line0, nlines;
-  unsigned int target0, target1;
-};
-
-template <int MODE, int CPT, bool SC1 = false>
-__device__ __forceinline__ void stein_split_body(const PairArgs &a, float *lds, const int tile_x, const int js, const unsigned int *score_cnt,
-                                                 const float *score_pub, unsigned int *timeout_flag, unsigned long long *tl,
-                                                 const LineGate *gate = nullptr, const float *XYo = nullptr /* override a.X = a.Y */,
-                                                 const int tx = (int)threadIdx.x, unsigned long long *tlp = nullptr) {
+template <int MODE, int CPT>
+__device__ __forceinline__ void stein_split_body(const PairArgs &a, float *lds, const int tile_x, const int js, const float *score_pub,
+                                                 unsigned int *timeout_flag, unsigned long long *tl) {
   static_assert(MODE == PAIR_K1 || MODE == PAIR_IMQ, "Stein modes only");
   static_assert(CPT <= 8, "the Gram x score product runs on the matrix cores (D <= 64)");
   constexpr int TI = PAIR_TI, JC = PAIR_JC, NT = PAIR_NT;
@@ -344,15 +325,15 @@ __device__ __forceinline__ void stein_split_body(const PairArgs &a, float *lds, 
   float *Ys = Xs + TI * DP;          // [JC][YS]  keys / ell
   float *Vs = Ys + JC * YS;          // [JC][YS]  score rows
   float *kv = Vs + JC * YS;          // [TI][JC + 1] Gram values
-  const int tid = tx;
+  const int tid = threadIdx.x;
   const int D = a.D, da = a.da, N = a.N;
   const int ib = a.i0 + tile_x * TI;
   const int jbeg = js * a.slice, jend = min(N, jbeg + a.slice);
   const int nq = min(TI, a.i0 + a.n_local - ib), jc = min(JC, jend - jbeg);
   {
     float vx[RowLane<TI, DP, NT>::NB], vy[RowLane<JC, DP, NT>::NB];
-    rowlane_issue<TI, DP, NT, SC1>(XYo ? XYo : a.X, ib, nq, D, vx, tid);
-    rowlane_issue<JC, DP, NT, SC1>(XYo ? XYo : a.Y, jbeg, jc, D, vy, tid);
+    rowlane_issue<TI, DP, NT>(a.X, ib, nq, D, vx, tid);
+    rowlane_issue<JC, DP, NT>(a.Y, jbeg, jc, D, vy, tid);
     rowlane_commit<TI, DP, DP, NT, true>(vx, nq, D, da, a.inv_s, Xs, tid);
     rowlane_commit<JC, DP, YS, NT, true>(vy, jc, D, da, a.inv_s, Ys, tid);
   }
@@ -362,7 +343,6 @@ __device__ __forceinline__ void stein_split_body(const PairArgs &a, float *lds, 
   for (int c = 0; c < CPT / 2; ++c) accB[c] = v2f{0.f, 0.f};
   const int mw = tid >> 6, ml = tid & 63, mqh = mw >> 1, mct0 = (mw & 1) * TPW;
   wg_sync();
-  DUST_TLP(tlp, 8);
   v2f xB[CPT / 2];
 #pragma unroll
   for (int c = 0; c < CPT / 2; ++c) xB[c] = *reinterpret_cast<const v2f *>(&Xs[iB * DP + cB + 2 * c]);
@@ -393,7 +373,6 @@ __device__ __forceinline__ void stein_split_body(const PairArgs &a, float *lds, 
     }
   }
   wg_sync();
-  DUST_TLP(tlp, 9);
   // repulsive term: lane = (query, 8 column groups)
 #pragma unroll 4
   for (int jj = 0; jj < JC; ++jj) {
@@ -425,56 +404,31 @@ __device__ __forceinline__ void stein_split_body(const PairArgs &a, float *lds, 
   }
   // ---- the score rows of this key slice, published by the rollout role of this launch ----
   DUST_TL(tl, 1);
-  DUST_TLP(tlp, 10);
   using RLV = RowLane<JC, DP, NT>;
   float vv[RLV::NB];
   const int vlr = tid / RLV::W, vlc = min(tid % RLV::W, D - 1);
-  if (score_pub) {
-    // handed over as data: every word of the buffer holds SCORE_SENTINEL until its row is written (through) by the rollout
-    // role.  A cheap look at the last word of each row until all 64 have landed, then the tile is loaded and EVERY word is
-    // checked (a row is several memory transactions; no assumption on their order or granularity); bounded.
-    const float *base = score_pub + (size_t)jbeg * D + vlc;
-    unsigned int spins = 0;
-    for (;;) {
-      {
-        int any = 0;
+  // handed over as data: every word of the buffer holds SCORE_SENTINEL until its row is written (through) by the rollout
+  // role.  A cheap look at the last word of each row until all 64 have landed, then the tile is loaded and EVERY word is
+  // checked (a row is several memory transactions; no assumption on their order or granularity); bounded.
+  const float *base = score_pub + (size_t)jbeg * D + vlc;
+  unsigned int spins = 0;
+  for (;;) {
+    {
+      int any = 0;
 #pragma unroll
-        for (int u = 0; u < RLV::NB; ++u) {
-          vv[u] = __hip_atomic_load(base + (size_t)min(u * RLV::RB + vlr, jc - 1) * D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          any |= __float_as_uint(vv[u]) == SCORE_SENTINEL;
-        }
-        if (!__syncthreads_or(any)) break;
+      for (int u = 0; u < RLV::NB; ++u) {
+        vv[u] = __hip_atomic_load(base + (size_t)min(u * RLV::RB + vlr, jc - 1) * D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        any |= __float_as_uint(vv[u]) == SCORE_SENTINEL;
       }
-      __builtin_amdgcn_s_sleep(4);
-      if (++spins > (1u << 22)) {
-        if (tid == 0) *timeout_flag = 1u;
-        break;
-      }
+      if (!__syncthreads_or(any)) break;
     }
-    DUST_TL(tl, 2);
-  } else {
-    if (gate) {  // persistent tick (persist.hpp): the keys' score rows are counted per 32-particle group
-      if (tid < gate->nlines) spin_until(gate->cnt + (size_t)(gate->line0 + tid) * 32, tid == 0 ? gate->target0 : gate->target1, timeout_flag);
-    } else if (tid == 0) {
-      const unsigned int target = (unsigned int)(jend - jbeg);
-      unsigned int spins = 0;
-      while (__hip_atomic_load(score_cnt + js * 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {  // 32 = CNT_STRIDE (rollout.hpp)
-        __builtin_amdgcn_s_sleep(4);
-        if (++spins > (1u << 24)) {
-          *timeout_flag = 1u;
-          break;
-        }
-      }
+    __builtin_amdgcn_s_sleep(4);
+    if (++spins > (1u << 22)) {
+      if (tid == 0) *timeout_flag = 1u;
+      break;
     }
-    DUST_TL(tl, 2);
-    wg_sync();
-    // row-lane staging with sc1 loads (the rows were written through by other CUs in this launch)
-    const float *base = a.V + (size_t)jbeg * D + vlc;
-#pragma unroll
-    for (int u = 0; u < RLV::NB; ++u) vv[u] = __hip_atomic_load(base + (size_t)min(u * RLV::RB + vlr, jc - 1) * D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  DUST_TLP(tlp, 11);
-  if (gate) __builtin_amdgcn_s_setprio(3);  // persistent tick: from here on the tile is on the critical path
+  DUST_TL(tl, 2);
   rowlane_commit<JC, DP, YS, NT, false>(vv, jc, D, da, a.inv_s, Vs, tid);
   wg_sync();
   v4f accM[TPW];
@@ -524,7 +478,6 @@ struct PriorMerge {
   float Lp[3];  // l00, l10, l11
 };
 // loads are issued in batches of 8 with clamped (never predicated) indices so they overlap instead of serialising
-template <bool SC1 = false /* the partials were written (write-through) inside this launch */>
 __device__ __forceinline__ void prior_merge_row(const PriorMerge &pm, int il, float *m_out, float *l_out) {
   float m = -INFINITY, l = 0.f;
   for (int q0 = 0; q0 < pm.JS; q0 += 16) {  // 32 independent loads in flight: one round trip for JS <= 16
@@ -532,8 +485,8 @@ __device__ __forceinline__ void prior_merge_row(const PriorMerge &pm, int il, fl
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
       const size_t r = (size_t)min(q0 + u, pm.JS - 1) * pm.n_local + il;
-      mq[u] = SC1 ? __hip_atomic_load(pm.pM + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : pm.pM[r];
-      lq[u] = SC1 ? __hip_atomic_load(pm.pL + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : pm.pL[r];
+      mq[u] = pm.pM[r];
+      lq[u] = pm.pL[r];
     }
     float mc = -INFINITY;
 #pragma unroll

@@ -25,7 +25,7 @@ CASES = [
 ]
 IDS = ["sgd_nesterov", "sgd_damp_wd_max", "adam_ams_wd", "adamw_max", "adamw_ams", "rmsprop_centered_mom", "rmsprop_wd_max",
        "adagrad_decay_init", "adagrad_wd_max"]
-ENV_KEYS = ("DUST_NO_TICK2", "DUST_NO_PERSIST")
+ENV_KEYS = ("DUST_NO_TICK2",)
 
 
 def _state(model):

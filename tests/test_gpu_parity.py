@@ -669,9 +669,9 @@ def test_c_side_rccl_tick_world1(model, N, S, M, H):
     kw = dict(model=model, N=N, S=S, M=M, H=H, kernel="K1", lr=0.5, sigma_a=1.0, sigma_p=1.0, uncertain_params=up, grid=grid, seed=11)
     res = []
     # (third run: the particle all-gather on the main stream instead of under the next iteration's rollouts - DUST_NO_COMM_OVERLAP)
-    for env, sharded in (({"DUST_NO_PERSIST": "1"}, False), ({"DUST_COMM_FORCE": "1"}, True),
+    for env, sharded in (({"DUST_NO_TICK2": "1"}, False), ({"DUST_COMM_FORCE": "1"}, True),
                          ({"DUST_COMM_FORCE": "1", "DUST_NO_COMM_OVERLAP": "1"}, True)):
-        saved = {k: os.environ.pop(k, None) for k in ("DUST_NO_PERSIST", "DUST_COMM_FORCE", "DUST_NO_COMM_OVERLAP")}
+        saved = {k: os.environ.pop(k, None) for k in ("DUST_NO_TICK2", "DUST_COMM_FORCE", "DUST_NO_COMM_OVERLAP")}
         os.environ.update(env)
         try:
             c = Context(shard_offset=0, shard_size=N, **kw) if sharded else Context(**kw)
@@ -682,7 +682,7 @@ def test_c_side_rccl_tick_world1(model, N, S, M, H):
             res.append((c.get_theta(), outs))
             c.close()
         finally:
-            for k in ("DUST_NO_PERSIST", "DUST_COMM_FORCE", "DUST_NO_COMM_OVERLAP"):
+            for k in ("DUST_NO_TICK2", "DUST_COMM_FORCE", "DUST_NO_COMM_OVERLAP"):
                 os.environ.pop(k, None)
                 if saved[k] is not None:
                     os.environ[k] = saved[k]
@@ -721,7 +721,7 @@ def test_fused_launches_equal_unfused_bitwise(model, N, S, M, H, kernel, optimiz
         grid = grid_4x4_map()
 
     def run(env, unfused, n_ticks):
-        saved = {k: os.environ.pop(k, None) for k in ("DUST_NO_PERSIST", "DUST_NO_TICK2")}
+        saved = {k: os.environ.pop(k, None) for k in ("DUST_NO_TICK2",)}
         os.environ.update(env)
         os.environ["DUST_NO_TICK2"] = "1"
         try:
@@ -740,13 +740,13 @@ def test_fused_launches_equal_unfused_bitwise(model, N, S, M, H, kernel, optimiz
             c.close()
             return out
         finally:
-            for k in ("DUST_NO_PERSIST", "DUST_NO_TICK2"):
+            for k in ("DUST_NO_TICK2",):
                 os.environ.pop(k, None)
                 if saved[k] is not None:
                     os.environ[k] = saved[k]
 
     ref = run({}, True, 6)
-    for env in ({}, {"DUST_NO_PERSIST": "1"}):
+    for env in ({}, {"DUST_NO_TICK2": "1"}):
         got = run(env, False, 6)
         for a, b, what in zip(got, ref, ("theta", "score", "a_mat", "a_seq", "p_weights")):
             assert np.array_equal(a, b), (env, what)

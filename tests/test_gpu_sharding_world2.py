@@ -92,8 +92,8 @@ def test_c_side_sharded_tick_in_separate_processes(ci, world, overlap, gather, f
     from dust_amd import Context
 
     kw, mu, th, state, eps, params = case_inputs(case)
-    saved = os.environ.get("DUST_NO_PERSIST")
-    os.environ["DUST_NO_PERSIST"] = "1"  # launch-per-iteration path: the kernels the sharded tick runs
+    saved = os.environ.get("DUST_NO_TICK2")
+    os.environ["DUST_NO_TICK2"] = "1"  # launch-per-iteration path: the kernels the sharded tick runs
     try:
         ref = Context(**kw)
         ref.set_theta(th); ref.set_prior(mu); ref.set_a_mat(th)
@@ -101,9 +101,9 @@ def test_c_side_sharded_tick_in_separate_processes(ci, world, overlap, gather, f
         rt, ra = ref.get_theta(), ref.get_a_mat()
         ref.close()
     finally:
-        os.environ.pop("DUST_NO_PERSIST", None)
+        os.environ.pop("DUST_NO_TICK2", None)
         if saved is not None:
-            os.environ["DUST_NO_PERSIST"] = saved
+            os.environ["DUST_NO_TICK2"] = saved
     n_loc = case["N"] // world
     for r in range(world):
         for t in range(case["T"]):

@@ -52,7 +52,7 @@ def _snapshot(c):
 
 
 def _run(env, model, N, S, H, iters, ticks, ext_noise, M=1, **kw):
-    saved = {k: os.environ.pop(k, None) for k in ("DUST_NO_TICK2", "DUST_NO_PERSIST")}
+    saved = {k: os.environ.pop(k, None) for k in ("DUST_NO_TICK2",)}
     os.environ.update(env)
     try:
         c, rng = _make(model, N, S, H, M=M, **kw)
@@ -71,7 +71,7 @@ def _run(env, model, N, S, H, iters, ticks, ext_noise, M=1, **kw):
         c.close()
         return outs, stats
     finally:
-        for k in ("DUST_NO_TICK2", "DUST_NO_PERSIST"):
+        for k in ("DUST_NO_TICK2",):
             os.environ.pop(k, None)
             if saved[k] is not None:
                 os.environ[k] = saved[k]
@@ -94,12 +94,12 @@ SHAPES = [
 
 def _make_with_env(env, *a, **kw):
     """a context created under the given development switches (the library reads them once, at dust_create)"""
-    saved = {k: os.environ.pop(k, None) for k in ("DUST_NO_TICK2", "DUST_NO_PERSIST")}
+    saved = {k: os.environ.pop(k, None) for k in ("DUST_NO_TICK2",)}
     os.environ.update(env)
     try:
         return _make(*a, **kw)
     finally:
-        for k in ("DUST_NO_TICK2", "DUST_NO_PERSIST"):
+        for k in ("DUST_NO_TICK2",):
             os.environ.pop(k, None)
             if saved[k] is not None:
                 os.environ[k] = saved[k]
@@ -390,7 +390,7 @@ def test_tick2_open_loop_queue_aborts_in_order():
     assert np.isfinite(e0).all() and abs(float(p0.sum()) - 1.0) < 1e-3
 
 
-@pytest.mark.parametrize("env", [{}, {"DUST_NO_TICK2": "1"}, {"DUST_NO_PERSIST": "1"}], ids=["tick2", "fused-launches", "launch-per-iteration"])
+@pytest.mark.parametrize("env", [{}, {"DUST_NO_TICK2": "1"}, {"DUST_NO_TICK2": "1"}], ids=["tick2", "fused-launches", "launch-per-iteration"])
 def test_contexts_tick_concurrently(env):
     """Three contexts on one device ticking from three host threads.  Every one-launch form spins on its own
     workgroups and needs them co-resident; with a second context on the device the library chains those launches across the
@@ -401,7 +401,7 @@ def test_contexts_tick_concurrently(env):
 
     N, S, H, T, C = 1024, 128, 30, 120, 3
     st = _state("pendulum")
-    saved = {k: os.environ.pop(k, None) for k in ("DUST_NO_TICK2", "DUST_NO_PERSIST")}
+    saved = {k: os.environ.pop(k, None) for k in ("DUST_NO_TICK2",)}
     os.environ.update(env)
     try:
         ctxs = [_make("pendulum", N, S, H, seed=s)[0] for s in range(C)]
@@ -430,7 +430,7 @@ def test_contexts_tick_concurrently(env):
             ctxs[i].close()
         print("replayed ticks:", [s["replayed"] for s in stats])
     finally:
-        for k in ("DUST_NO_TICK2", "DUST_NO_PERSIST"):
+        for k in ("DUST_NO_TICK2",):
             os.environ.pop(k, None)
             if saved[k] is not None:
                 os.environ[k] = saved[k]
@@ -439,7 +439,7 @@ def test_contexts_tick_concurrently(env):
                                                     ("particle", 2048, 16, 16, 2, 1, {})])
 def test_n2048_short_rows_default_path_equals_the_other_paths(model, N, S, H, iters, M, kw):
     """N = 2048 with N D <= 65 536 runs the small-set kernels by default since round 3 (dust_amd.hip pair_is_big) - whichever launch form
-    that is for the shape (tiled one-launch tick, fused launches): the same two ticks through the launch-per-iteration kernels
+    that is for the shape (fused launches): the same two ticks through the launch-per-iteration kernels
     (DUST_NO_FUSE) and through the large-set path (DUST_PAIR_BIG=1, the default until then and the one the oracle tests of
     test_gpu_parity.py pin at this size) must agree."""
     outs = {}

@@ -6,7 +6,7 @@ import numpy as np
 from dust_amd import Context
 
 def run(env, sharded, steps=300):
-    for k in ("DUST_NO_PERSIST", "DUST_COMM_FORCE"):
+    for k in ("DUST_NO_TICK2", "DUST_COMM_FORCE"):
         os.environ.pop(k, None)
     os.environ.update(env)
     rng = np.random.default_rng(0)
@@ -32,7 +32,7 @@ def run(env, sharded, steps=300):
 
 if __name__ == "__main__":
     a = run({}, False)
-    b = run({"DUST_NO_PERSIST": "1"}, False)
+    b = run({"DUST_NO_TICK2": "1"}, False)
     d = run({"DUST_COMM_FORCE": "1"}, True)
     print("cfg2 us/tick: persistent %.1f | launch-per-iteration (graph) %.1f | sharded world-1 with RCCL %.1f  -> 12 all-gathers + sharded kernels cost %.1f us over the graph path"
           % (a, b, d, d - b))

@@ -21,10 +21,10 @@ loop("open loop (no outputs, no sync)", lambda: c.svmpc_tick(st,5,want_outputs=F
 loop("no outputs + sync per tick", lambda: (c.svmpc_tick(st,5,want_outputs=False), c.sync()))
 for rep in range(4): loop("outputs (D2H + sync) per tick #%d" % rep, lambda: c.svmpc_tick(st,5,want_outputs=True))
 loop("sync only", lambda: c.sync())
-os.environ["DUST_NO_PERSIST"]="1"
+os.environ["DUST_NO_TICK2"]="1"
 loop("launch-per-iteration: outputs per tick", lambda: c.svmpc_tick(st,5,want_outputs=True))
 loop("launch-per-iteration: open loop", lambda: c.svmpc_tick(st,5,want_outputs=False))
-os.environ.pop("DUST_NO_PERSIST")
+os.environ.pop("DUST_NO_TICK2")
 import bench
 stt = st.copy()
 def cl():
