@@ -4879,6 +4879,49 @@ extern "C" int dust_debug_far_logp(dust_ctx *c, long long *out2) {
   return DUST_OK;
 }
 
+// The device's own generators (common.hpp) at given counters: kind 0 philox4x32<7> words [n][4], 1 philox4x32_10 words [n][4],
+// 2 philox_normal4 [n][4], 3 philox_normal8 [n][8].  A test hook (not in include/dust_amd.h): tests/philox_ref.py restates the
+// Philox rounds and the noise layouts on the host, and the control-noise tests assemble the device's exact normals from this.
+__global__ void debug_philox_kernel(int kind, uint64_t seed, const uint32_t *ctr, int n, uint32_t *out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t c0 = ctr[4 * i], c1 = ctr[4 * i + 1], c2 = ctr[4 * i + 2], c3 = ctr[4 * i + 3];
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  if (kind == 3) {
+    float z[8];
+    philox_normal8(seed, c0, c1, c2, c3, z);
+    for (int q = 0; q < 8; ++q) out[8 * i + q] = __float_as_uint(z[q]);
+    return;
+  }
+  uint32_t r[4];
+  if (kind == 0) philox4x32<7>(c0, c1, c2, c3, k0, k1, r);
+  else if (kind == 1) philox4x32_10(c0, c1, c2, c3, k0, k1, r);
+  else {
+    float z[4];
+    philox_normal4(seed, c0, c1, c2, c3, z);
+    for (int q = 0; q < 4; ++q) r[q] = __float_as_uint(z[q]);
+  }
+  for (int q = 0; q < 4; ++q) out[4 * i + q] = r[q];
+}
+extern "C" int dust_debug_philox(int kind, unsigned long long seed, const unsigned int *ctr, int n, void *out) {
+  if (!ctr || !out || n < 0 || kind < 0 || kind > 3) return fail(DUST_ERR_INVALID, "bad argument");
+  if (n == 0) return DUST_OK;
+  const size_t words = (size_t)n * (kind == 3 ? 8 : 4);
+  uint32_t *d_ctr = nullptr, *d_out = nullptr;
+  hipError_t e = hipMalloc((void **)&d_ctr, (size_t)n * 4 * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc((void **)&d_out, words * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMemcpy(d_ctr, ctr, (size_t)n * 4 * sizeof(uint32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    debug_philox_kernel<<<(n + 255) / 256, 256>>>(kind, (uint64_t)seed, d_ctr, n, d_out);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(out, d_out, words * sizeof(uint32_t), hipMemcpyDeviceToHost);
+  if (d_ctr) (void)hipFree(d_ctr);
+  if (d_out) (void)hipFree(d_out);
+  if (e != hipSuccess) return fail(DUST_ERR_HIP, "dust_debug_philox: %s", hipGetErrorString(e));
+  return DUST_OK;
+}
+
 #ifdef DUST_STAMPS
 // diagnostic build only (not part of include/dust_amd.h): s_memtime phase stamps of block 0 of the last launch of a kernel
 extern "C" int dust_debug_stamps(dust_ctx *c, int kernel_id, unsigned long long *out16) {
