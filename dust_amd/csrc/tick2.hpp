@@ -141,6 +141,12 @@ enum { T2_PASS_PRIOR = 0, T2_PASS_STEIN = 1, T2_PASS_LOGP = 2 };
 #ifndef T2_PRIO_PPASS
 #define T2_PRIO_PPASS 0
 #endif
+#ifndef T2_PRIO_PPASS_TURNS
+#define T2_PRIO_PPASS_TURNS 1  // the two prior-pass waves of a SIMD alternate between T2_PRIO_PPASS + 1 and T2_PRIO_PPASS (t2_prior_pass_w)
+#endif
+#ifndef T2_PRIO_STEIN
+#define T2_PRIO_STEIN 1  // the Stein pass, above the rollout waves' noise draw (their draw has until barrier B4; the pass decides when B4 falls)
+#endif
 #ifndef T2_NOISE_SPLIT
 #define T2_NOISE_SPLIT 1
 #endif
@@ -379,6 +385,15 @@ __device__ __forceinline__ void t2_prior_pass_w(const T2ArgPtr f, const int gen,
     v4f ya[4], yb[4];
     issue(0, ya);
     for (int t = 0; t < steps; t += 2) {  // (steps is a multiple of 8; the last group re-reads its last rows: no branch in the loop)
+      // The two P waves of a SIMD (units u and u + 4) take turns at wave priority 1, one pair of steps each.  At equal priority the
+      // issue slots the rollouts leave go to the OLDER wave first: waves 8-11 finished the pass 0.9 us ahead of waves 12-15, which ran
+      // its end alone, one wave per SIMD, latencies exposed (7.0 / 7.9 us into the iteration).  A static priority for the younger half
+      // only swaps the roles (+1.2 us per tick); taking turns they reach barrier B1 together.  The rollout waves (T2_PRIO_ROLL = 1,
+      // older) still win every slot they can use.
+      if (T2_PRIO_PPASS_TURNS) {
+        if (((t >> 1) ^ (pw >> 2)) & 1) DUST_PRIO(T2_PRIO_PPASS + 1);
+        else DUST_PRIO(T2_PRIO_PPASS);
+      }
       issue(t + 1, yb);
       step(t, ya);
       issue(min(t + 2, steps - 1), ya);
@@ -454,11 +469,10 @@ __device__ __forceinline__ void t2_logp_pass_w(const T2ArgPtr f, const int gen, 
   };
   {
     v4f ya[4], yb[4];
-    issue(0, ya);
-    for (int t = 0; t < steps; t += 2) {  // (steps is even: f->steps is a multiple of 16)
-      issue(t + 1, yb);
-      step(t, ya);
-      issue(min(t + 2, steps - 1), ya);
+    for (int t = 0; t < steps; t += 2) {  // (steps is even: f->steps is a multiple of 16 - and IS 16 wherever this kernel runs, i.e. one
+      issue(t, ya);                        //  group: both steps in flight in front of its arithmetic and nothing read behind it.  The form
+      issue(t + 1, yb);                    //  that prefetched the next group re-read the last rows once per tick for nothing: the loads
+      step(t, ya);                         //  sat in front of wave 8's vmcnt(0) of the log-weight hand-off, +1.1 us per cfg2 tick)
       step(t + 1, yb);
     }
   }
@@ -1149,9 +1163,11 @@ __global__ __launch_bounds__(T2_NT, 4) void svmpc_tick2_kernel(const Tick2Args f
       //  their noise draw, with the owner waves idle: +4.5 us per tick, the workgroups drift apart; an idle wave polling the score
       //  counters from the moment the rows are published: the hop takes 5.8 instead of 2.5 us - the polls sit on the arrivals' lines)
       float rb[4];
+      DUST_PRIO(T2_PRIO_STEIN);
       if (N != f->steps * 64) t2_pair_pass<MODE, T2_PASS_STEIN, true>(f, k, th, ksl, lml, wave - 8, lane, lm_ref, rb);
       else t2_pair_pass<MODE, T2_PASS_STEIN, false>(f, k, th, ksl, lml, wave - 8, lane, lm_ref, rb);
       rpart[((wave - 8) * 16 + reduce_u16_index<16>(0, lane)) * 4 + (lane & 3)] = rb[0];
+      DUST_PRIO(0);
       T2_TL(8, 16 * k + 11);
       T2_TL(15, 16 * k + 6);
     }
@@ -1296,6 +1312,7 @@ __global__ __launch_bounds__(T2_NT, 4) void svmpc_tick2_kernel(const Tick2Args f
       if (lane == 0) t2_lds_st(sig + 1, (unsigned int)(kf + 1));
     }
     while (t2_lds_ld(sig + 1) < (unsigned int)(kf + 1)) __builtin_amdgcn_s_sleep(1);
+    T2_TL(0, 16 * kf + 3);
     float red[4];
 #ifdef T2_LOGP_NARROW
     t2_pair_pass<MODE, T2_PASS_LOGP, true>(f, kf, th, ksl, lml, wave, lane, lm_ref, red);

@@ -53,7 +53,7 @@ for k in range(IT):
     for i in order:
         show(names[i], 16 * k + i)
 print("forward:")
-for i, nm in enumerate(["log-density pass done", "log-weights arrived", "end"]):
+for i, nm in [(3, "generation n_iters seen (w0)"), (0, "log-density pass done"), (1, "log-weights arrived"), (2, "end")]:
     show(nm, 16 * IT + i)
 print("last stamp: %.2f us" % us(t.max()))
 c.close()
