@@ -117,3 +117,23 @@ class RecordedDraws:
 
     def next_mpf_noise(self):
         return self._next("mpf_noise")
+
+
+# ---- fixtures of tests/golden/make_golden_mpf_sizes.py (the reference's filter beyond 12 particles)
+MPF_SIZE_CASES = ["pend_g3_lin", "pend_g3_log", "pend_m1_log", "pend_lm_600", "pend_lm_1024", "pend_sat", "pend_sat_split", "part_lin",
+                  "part_acc_sat", "part_vel_sat", "part_acc_split", "part_in_obst", "part_log_1021", "pend_adam_300", "part_adam_130"]
+
+
+def mpf_size_err(got, g, q):
+    """elemerr of `got` against quantity q of such a fixture: the smaller of the distances to the reference's fp32 and float64 values
+    (both are the reference), to be held below g['tol_' + q] - the tolerance the generator measured from the reference alone."""
+    e = elemerr(got, g[q])
+    return min(e, elemerr(got, g[q + "_f64"])) if q + "_f64" in g else e
+
+
+def mpf_size_disp_err(x2, g):
+    """the two-step DISPLACEMENT x_2 - x0 against the reference's (fp32 or float64 run), by elemerr; bound: g['tol_disp_2']"""
+    x0 = np.asarray(g["x0"], np.float64)
+    d = np.asarray(x2, np.float64) - x0
+    e = elemerr(d, np.asarray(g["x_2"], np.float64) - x0)
+    return min(e, elemerr(d, np.asarray(g["x_2_f64"], np.float64) - x0)) if "x_2_f64" in g else e

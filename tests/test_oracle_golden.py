@@ -9,7 +9,7 @@ import pytest
 
 import oracle
 from oracle import Oracle
-from helpers import ctrl_noise_of, elemerr, is_adam, relerr, scenario_kwargs
+from helpers import MPF_SIZE_CASES, ctrl_noise_of, elemerr, is_adam, mpf_size_disp_err, mpf_size_err, relerr, scenario_kwargs
 
 TOL = 1e-5
 SVMPC_CASES = ["pend_k1", "pend_k1_close", "pend_k2", "pend_k1_params", "pend_k1_expcost", "pend_k1_ctrlpen", "pend_k1_mean",
@@ -249,6 +249,90 @@ def test_mpf_adam(golden, name):
     # restarting the optimiser state at the second call (what SVMPC does at every roll) must NOT reproduce the reference here
     x2r, *_ = o.mpf_optimize_adam(x, pm, pbw, g["obs1"], g["action2"], g["obs2"], float(g["obs_std"]), ls, bw, lr, n)
     assert relerr(x2r, g["x_final2"]) > 10 * TOL
+
+
+def _branch_census(g):
+    """How many (particle, channel) pairs of a size fixture sit on each side of the model's clamps, from the fixture's inputs alone
+    (float64 restatement of the one-step prediction's clamp conditions: pendulum.py:93-98, particle.py:150-165)."""
+    x = np.asarray(g["x0"], np.float64)
+    v = np.exp(x) if int(g["log_space"]) else x
+    if str(g["model_kind"]) == "pendulum":
+        names = str(g["uncertain"]).split(",")
+        par = {k: (v[:, names.index(k)] if k in names else np.full(len(v), d)) for k, d in (("g", 9.8), ("mass", 1.0), ("length", 1.0))}
+        u = np.clip(float(g["action"][0]), -2.0, 2.0)
+        thd = g["obs0"][1] + 0.05 * (-3 * par["g"] / (2 * par["length"]) * np.sin(g["obs0"][0] + np.pi) + 3.0 / (par["mass"] * par["length"] ** 2) * u)
+        return dict(speed=int((np.abs(thd) > 8.0).sum()), n=len(v))
+    acc = np.asarray(g["action"], np.float64)[None, :] / v
+    vel = np.asarray(g["obs0"], np.float64)[None, 2:] + np.clip(acc, -10, 10) * 0.015
+    return dict(acc=(np.abs(acc) > 10).sum(0).tolist(), vel=(np.abs(vel) > 5).sum(0).tolist(), n=len(v))
+
+
+def test_mpf_size_fixtures_reach_their_branches(golden):
+    """Each clamp fixture of make_golden_mpf_sizes.py has the particles on the side of the clamp its name says - all of them, or a real
+    split per particle (and per channel for the Particle) - and the obstacle fixture starts inside an obstacle."""
+    c = {n: _branch_census(golden("mpf_sz_" + n)) for n in MPF_SIZE_CASES}
+    assert c["pend_sat"]["speed"] == 130 and 20 <= c["pend_sat_split"]["speed"] <= 110
+    assert all(c[n]["speed"] == 0 for n in MPF_SIZE_CASES if n.startswith("pend") and "sat" not in n)
+    assert c["part_acc_sat"]["acc"] == [130, 0] and c["part_acc_sat"]["vel"] == [0, 0]
+    assert c["part_vel_sat"]["acc"] == [0, 0] and c["part_vel_sat"]["vel"] == [130, 0]
+    a = c["part_acc_split"]["acc"]
+    assert 30 <= a[0] <= 270 and 30 <= a[1] <= 270 and a[0] != a[1] and c["part_acc_split"]["vel"] == [0, 0]
+    # ... and the OBSERVED speed is off the clamp, so the clamped particles keep a residual y - f on that channel: with y - f = 0 there
+    # the likelihood score J^T (y - f) would be zero whatever the mask does, and the fixture could not tell a kernel that ignores it
+    g = golden
+    assert abs(g("mpf_sz_pend_sat")["obs1"][1]) < 7.9 and abs(g("mpf_sz_pend_sat_split")["obs1"][1]) < 7.9
+    assert g("mpf_sz_part_vel_sat")["obs1"][2] < 4.995
+    a = g("mpf_sz_part_acc_sat")
+    assert 0.05 < float(a["obs1"][2] - a["obs0"][2]) < 0.99 * 10.0 * 0.015  # (the true acceleration is below max_acc)
+    for n in ("part_lin", "part_in_obst", "part_adam_130"):
+        assert c[n]["acc"] == [0, 0] and c[n]["vel"] == [0, 0], n
+    # (part_log_1021 spreads its masses widely - its kernel bandwidth is small - so a minority of its light particles clamp as well)
+    assert c["part_log_1021"]["acc"][0] < 50 and c["part_log_1021"]["acc"][1] < 200 and c["part_log_1021"]["vel"] == [0, 0]
+    o = Oracle(model="particle", uncertain_params=("mass",))
+    assert o.get_collisions(golden("mpf_sz_part_in_obst")["obs0"][None, :2])[0] == 1.0
+    assert o.get_collisions(golden("mpf_sz_part_in_obst")["obs1"][None, :2])[0] == 0.0
+    assert all(o.get_collisions(golden("mpf_sz_" + n)["obs0"][None, :2])[0] == 0.0 for n in MPF_SIZE_CASES if n.startswith("part") and n != "part_in_obst")
+
+
+@pytest.mark.parametrize("name", MPF_SIZE_CASES)
+def test_mpf_sizes(golden, name):
+    """The oracle's filter against the reference's own MPF at 70 ... 1 024 particles and on the Jacobian branches no earlier fixture
+    reaches (tests/golden/make_golden_mpf_sizes.py: the g column and P = 3, the P = 1 pendulum, the pendulum's log chain, the clamp
+    masks of both models, the obstacle factor, linear-space Particle mass).  The oracle's step_jacobian and the device's are the same
+    closed forms written twice: only the reference's autograd can say whether they are right.  Every tolerance is the one stored in the
+    fixture - measured from the reference alone (its response to a one-ulp move of x0, and fp32 against float64) - and a quantity
+    passes within it of the reference's fp32 OR float64 value."""
+    g = golden("mpf_sz_" + name)
+    kind, up = str(g["model_kind"]), tuple(str(g["uncertain"]).split(","))
+    o = Oracle(model=kind, uncertain_params=up, mass=2.0 if kind == "particle" else 1.0)
+    bw, ls, lr, n, std = float(g["bw"]), bool(int(g["log_space"])), float(g["lr"]), int(g["n_steps"]), float(g["obs_std"])
+    adam = str(g["optimizer"]) == "Adam"
+    x0 = g["x0"]
+    assert x0.shape == (int(g["Mp"]), len(up))
+    phi0 = o.mpf_phi(x0, x0, bw, g["obs0"], g["action"], g["obs1"], std, ls, bw)
+    assert mpf_size_err(phi0, g, "phi0") < float(g["tol_phi0"])
+    # (the fixture has power: the reference's phi with the branch ignored is at least ten tolerances away - asserted by the generator too)
+    off = g["phi0_off"]
+    assert elemerr(off, g["phi0"][:off.shape[0]]) >= 10 * max(float(g["tol_phi0"]), float(g["tol_disp_2"]))
+
+    def call(x, pm, pbw, past, act, obs, steps, state=None):
+        if adam:
+            m, v, st = state or (None, None, 0)
+            x, pm, pbw, gn, m, v, st = o.mpf_optimize_adam(x, pm, pbw, past, act, obs, std, ls, bw, lr, steps, m=m, v=v, step=st)
+            return x, pm, pbw, gn, (m, v, st)
+        return o.mpf_optimize(x, pm, pbw, past, act, obs, std, ls, bw, lr, steps) + (None,)
+
+    x2, _, _, gn_2, _ = call(x0, x0, bw, g["obs0"], g["action"], g["obs1"], 2)
+    assert mpf_size_err(x2, g, "x_2") < float(g["tol_x_2"])
+    assert mpf_size_disp_err(x2, g) < float(g["tol_disp_2"])
+    assert mpf_size_err(gn_2, g, "grad_norms_2") < float(g["tol_grad_norms_2"])
+    x, pm, pbw, gn, st = call(x0, x0, bw, g["obs0"], g["action"], g["obs1"], n)
+    assert mpf_size_err(x, g, "x_n") < float(g["tol_x_n"])
+    assert mpf_size_err(gn, g, "grad_norms") < float(g["tol_grad_norms"])
+    xb, pmb, _, gnb, st = call(x, pm, pbw, g["obs1"], g["action2"], g["obs2"], n, st)
+    assert mpf_size_err(xb, g, "x_n2") < float(g["tol_x_n2"])
+    assert mpf_size_err(gnb, g, "grad_norms2") < float(g["tol_grad_norms2"])
+    assert mpf_size_err(Oracle.gmm_log_prob(g["probe"], pmb, bw), g, "probe_log_prob") < float(g["tol_probe_log_prob"])
 
 
 def _noisy_actions(action, dyn_std, z):
