@@ -174,6 +174,7 @@ SYMBOLS = {
     "dust_mpf_set_particles": (C.c_int, [VP, FP]),
     "dust_mpf_get_prior": (C.c_int, [VP, FP, FP]),
     "dust_set_skid_steer": (C.c_int, [VP, C.POINTER(SkidConfig)]),
+    "dust_mpf_set_skid_steer": (C.c_int, [VP, C.POINTER(SkidConfig)]),
     "dust_mpf_set_prior_bw": (C.c_int, [VP, FP, C.c_int]),
     "dust_mpf_get_prior_bw": (C.c_int, [VP, FP]),
     "dust_mpf_stats": (C.c_int, [VP, C.POINTER(C.c_longlong)]),

@@ -565,6 +565,9 @@ class MpfContext:
         h = L.VP()
         L.check(lib.dust_mpf_create(C.byref(c), _p(x), _p(_f(initial_obs, (c.dim_s,))), C.byref(h)))
         self._h = h
+        if c.model == L.MODEL_SKID_STEER:
+            self.set_skid_steer(uncertain_params=uncertain_params, min_a=c.model_cfg.min_a, max_a=c.model_cfg.max_a,
+                                **{k: model_kw[k] for k in ("x_icr", "wheel_radius", "axial_distance") if k in model_kw})
         if grid is not None:
             g = _f(grid)
             L.check(lib.dust_mpf_set_grid(self._h, _p(g), g.shape[0], g.shape[1], float(int(g.shape[0] / 2)), float(int(g.shape[1] / 2))))
@@ -588,6 +591,20 @@ class MpfContext:
             self.close()
         except Exception:
             pass
+
+    def set_skid_steer(self, x_icr=0.2, wheel_radius=0.0625, axial_distance=0.475, min_a=(-0.5, -0.5), max_a=(0.5, 0.5), uncertain_params=()):
+        """The filter's SkidSteerRobot (dust_mpf_set_skid_steer): `uncertain_params` name the particle columns, in order; the other
+        parameters stay at the given values; min_a / max_a are the wheel-speed bounds."""
+        up = list(uncertain_params or ())
+        g = L.SkidConfig()
+
+        def par(name, value):
+            return L.Param(L.PARAM_SAMPLED, up.index(name), float(value)) if name in up else L.Param(L.PARAM_PYFLOAT, 0, float(value))
+
+        g.x_icr, g.wheel_radius, g.axial_distance = par("x_icr", x_icr), par("wheel_radius", wheel_radius), par("axial_distance", axial_distance)
+        for d in range(2):
+            g.min_wheel_speed[d], g.max_wheel_speed[d] = float(min_a[d]), float(max_a[d])
+        L.check(L.load().dust_mpf_set_skid_steer(self._h, C.byref(g)))
 
     def silverman(self):
         """silvermans_rule of the pooled particles times bw_scale, on the device (dust_mpf_silverman)."""

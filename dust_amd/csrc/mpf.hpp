@@ -3,7 +3,8 @@
 // Replaces (reference file:line): MPF.phi / step / optimize / update_prior mpf.py:26-86, GaussianLikelihood.sample /
 // log_prob / condition likelihoods.py:30-64, default_kernel + squared_distance svgd.py:28-39, 92-99, and the autograd
 // calls at mpf.py:45 and mpf.py:50 (closed forms: GMM responsibilities; J^T (y - f(x)) / sigma_o^2 with the analytic
-// Jacobian of one model step w.r.t. the uncertain parameters).
+// Jacobian of one model step w.r.t. the uncertain parameters).  Models: Pendulum, Particle (step_jacobian below) and SkidSteerRobot
+// (mpf_skid_score below, over skid.hpp's step).
 //
 // The problem is tiny (M_p <= 1024 particles x P <= 4 parameters, n_steps ~ 20 dependent SVGD steps), i.e. pure launch
 // latency on a GPU: ALL n_steps run inside ONE single-workgroup kernel with the particles, scores and squared norms in
@@ -21,7 +22,8 @@ struct MpfArgs {
   int Mp, P, ds, da, n_steps, log_space, have_past;
   float prior_bwv[4];  // prior bandwidth per parameter dimension (equal after the first update_prior; MPF(bw=None) starts per-dimension)
   float bw, obs_std;
-  float past_obs[4], past_action[2], obs[4];
+  float past_obs[4], past_action[2], obs[4];  // (Pendulum / Particle: up to four wide; the skid-steer model's five are in *skl)
+  const struct SkidLik *skl;  // DUST_MODEL_SKID_STEER: the likelihood's per-call constants, in device memory (below)
   // control-channel noise of the one-step prediction (Particle(deterministic=False), particle.py:145-148 reached through
   // likelihoods.py:30-46): `acts` there is the bare action vector, so ONE d_a-vector is drawn per phi() call - i.e. per SVGD step -
   // and shared by all filter particles.  act_seq[step][2] = fl(past_action + fl(dyn_std * z_step)), prepared by the host, or nullptr
@@ -100,6 +102,69 @@ __device__ __forceinline__ void step_jacobian(const DevModel &dm, const float *x
   }
 }
 
+// The likelihood score J^T (y - f(x)) / sigma_o^2 of ONE particle under the skid-steer model (state x, y, theta, v, omega: five wide).
+// Prediction: skid_step in fp32, as the rollout kernel takes it.  Jacobian in fp64 from the closed forms, r, l the wheel speeds after
+// the clamp (it acts on the action, not on a parameter: no mask), c = cos(theta), s = sin(theta) of the past state:
+//   lin = (r + l) pi wr        ang = 2 pi (r - l) wr / ad        fwd = lin dt        lat = -ang x_icr dt
+//   d lin / d wr = (r + l) pi     d ang / d wr = 2 pi (r - l) / ad     d ang / d ad = -ang / ad
+//   d lat / d x_icr = -ang dt     d lat / d p = -x_icr dt d ang / d p  (p = wr, ad)
+//   rows (x, y, theta, v, omega) = (d fwd c - d lat s, d fwd s + d lat c, d ang dt, d lin, d ang);  log space: column p times p's value.
+// With e = y - f(x):  J_p^T e = d lin (dt (c e_x + s e_y) + e_v) + d lat (c e_y - s e_x) + d ang (dt e_theta + e_omega).
+// Every parameter is sampled (column `col` of the particle) or fixed; the columns are placed by selects, as add_col does.
+// What does not depend on the particle - the clamped wheel speeds, c, s, (r + l) pi, 2 pi (r - l), the two observations - is prepared
+// by the host (mpf_skid_prepare; the heading's fp32 cosine and sine by mpf_skid_heading_kernel, with the rollout's own fast_cosf /
+// fast_sinf) and read from DEVICE MEMORY inside the model's branch: as kernel arguments these 40 words were loaded ahead of the branch
+// and held in scalar registers through the whole kernel, and the trigonometric code inside the branch raised its register peak - both
+// cost the Pendulum and Particle paths spilled registers (the register table).
+struct SkidLik {
+  int smp[3], col[3];        // x_icr, wheel_radius, axial_distance: sampled?  its particle column
+  float fix_f[3];            // ... its value when fixed, as the fp32 scalar the step sees
+  float r, l, dt;            // wheel speeds after the clamp; (float)delta_t
+  float cs, sn;              // fast_cosf / fast_sinf of past theta (mpf_skid_heading_kernel)
+  float past[5], obs[5];     // past observation (the state the step starts from), new observation
+  double fix_d[3];
+  double c, s, sum, dif, dtd;  // cos / sin of past theta, (r + l) pi, 2 pi (r - l), delta_t
+};
+// (the four entries are read first: a load per arm of the select is folded into ONE load from a selected address, and the array then
+// lives in scratch memory)
+__device__ __forceinline__ float sel4f(const float *v, int c) {
+  const float v0 = v[0], v1 = v[1], v2 = v[2], v3 = v[3];
+  return c == 0 ? v0 : (c == 1 ? v1 : (c == 2 ? v2 : v3));
+}
+template <int P>
+__device__ __forceinline__ void mpf_skid_score(const SkidLik *k, const int log_space, const float *xp, const double inv_obs2, double *out) {
+  const bool sx = k->smp[0] != 0, sw = k->smp[1] != 0, sa = k->smp[2] != 0;
+  const int cx = k->col[0], cw = k->col[1], ca = k->col[2];
+  const float rx = sel4f(xp, cx), rw = sel4f(xp, cw), ra = sel4f(xp, ca);
+  const float fx = sx ? (log_space ? expf(rx) : rx) : k->fix_f[0], fw = sw ? (log_space ? expf(rw) : rw) : k->fix_f[1],
+              fa = sa ? (log_space ? expf(ra) : ra) : k->fix_f[2];
+  float pred[5];
+#pragma unroll
+  for (int q = 0; q < 5; ++q) pred[q] = k->past[q];
+  skid_step_cs(pred, k->r, k->l, fx, fw, fa, k->dt, k->cs, k->sn);
+  double e[5];
+#pragma unroll
+  for (int q = 0; q < 5; ++q) e[q] = (double)k->obs[q] - (double)pred[q];
+  // (a sampled parameter enters the Jacobian with the fp32 value the prediction was taken at - in log space expf's, as the reference's
+  // fp32 autograd differentiates at theta.exp() in fp32)
+  const double xicr = sx ? (double)fx : k->fix_d[0], wr = sw ? (double)fw : k->fix_d[1], ad = sa ? (double)fa : k->fix_d[2];
+  const double c = k->c, s = k->s, dt = k->dtd;
+  const double t_lin = dt * (c * e[0] + s * e[1]) + e[3], t_lat = c * e[1] - s * e[0], t_ang = dt * e[2] + e[4];
+  const double dang_w = k->dif / ad, ang = dang_w * wr, dang_a = -ang / ad;
+  const double gx = sx ? (-ang * dt * t_lat) * (log_space ? xicr : 1.0) : 0.0;
+  const double gw = sw ? (k->sum * t_lin + dang_w * (t_ang - xicr * dt * t_lat)) * (log_space ? wr : 1.0) : 0.0;
+  const double ga = sa ? (dang_a * (t_ang - xicr * dt * t_lat)) * (log_space ? ad : 1.0) : 0.0;
+#pragma unroll
+  for (int p = 0; p < P; ++p) out[p] = ((sx && cx == p ? gx : 0.0) + (sw && cw == p ? gw : 0.0) + (sa && ca == p ? ga : 0.0)) * inv_obs2;
+}
+
+__global__ void mpf_skid_heading_kernel(SkidLik *k) {
+  if (threadIdx.x == 0) {
+    k->cs = fast_cosf(k->past[2]);
+    k->sn = fast_sinf(k->past[2]);
+  }
+}
+
 // Lane = (particle i, slice r of the other particles): R = blockDim / Mpad slices share the O(M_p) loops of a particle and
 // their partial sums are combined in slice order through LDS (fixed order: reproducible).  No divisions or fp64
 // transcendentals inside the O(M_p^2) loops: reciprocals are hoisted (fp64, error 1e-16), weights use expf.
@@ -167,20 +232,26 @@ __global__ __launch_bounds__(1024) void mpf_optimize_kernel(const MpfArgs a) {
       double s[4];
       _Pragma("unroll") for (int p = 0; p < P; ++p) s[p] = acc[p] / zs * inv_pbw2[p];
       // likelihood score (mpf.py:46-50, likelihoods.py:30-49)
-      float pred[4];
-      for (int k = 0; k < 4; ++k) pred[k] = k < a.ds ? a.past_obs[k] : 0.f;
-      const Coef cf = make_coef(a.dm, xi);
-      const float pa[2] = {a.act_seq ? a.act_seq[2 * it] : a.past_action[0], a.act_seq ? a.act_seq[2 * it + 1] : a.past_action[1]};
-      if (a.dm.model == DUST_MODEL_PENDULUM) model_step<DUST_MODEL_PENDULUM>(a.dm, cf, pred, pa);
-      else model_step<DUST_MODEL_PARTICLE>(a.dm, cf, pred, pa);
-      double J[4][4];
-      step_jacobian<P>(a.dm, a.past_obs, pa, xi, J);
-      _Pragma("unroll") for (int p = 0; p < P; ++p) {
-        double g = 0.0;
-        _Pragma("unroll") for (int k = 0; k < 4; ++k)
-          if (k < a.ds) g += J[k][p] * ((double)a.obs[k] - (double)pred[k]);
-        s[p] += g * inv_obs2;
-        sc[i * P + p] = (float)s[p];
+      if (a.dm.model == DUST_MODEL_SKID_STEER) {
+        double gl[4];
+        mpf_skid_score<P>(a.skl, a.log_space, xi, inv_obs2, gl);
+        _Pragma("unroll") for (int p = 0; p < P; ++p) sc[i * P + p] = (float)(s[p] + gl[p]);
+      } else {
+        float pred[4];
+        for (int k = 0; k < 4; ++k) pred[k] = k < a.ds ? a.past_obs[k] : 0.f;
+        const Coef cf = make_coef(a.dm, xi);
+        const float pa[2] = {a.act_seq ? a.act_seq[2 * it] : a.past_action[0], a.act_seq ? a.act_seq[2 * it + 1] : a.past_action[1]};
+        if (a.dm.model == DUST_MODEL_PENDULUM) model_step<DUST_MODEL_PENDULUM>(a.dm, cf, pred, pa);
+        else model_step<DUST_MODEL_PARTICLE>(a.dm, cf, pred, pa);
+        double J[4][4];
+        step_jacobian<P>(a.dm, a.past_obs, pa, xi, J);
+        _Pragma("unroll") for (int p = 0; p < P; ++p) {
+          double g = 0.0;
+          _Pragma("unroll") for (int k = 0; k < 4; ++k)
+            if (k < a.ds) g += J[k][p] * ((double)a.obs[k] - (double)pred[k]);
+          s[p] += g * inv_obs2;
+          sc[i * P + p] = (float)s[p];
+        }
       }
       float nn = 0.f;
       _Pragma("unroll") for (int p = 0; p < P; ++p) nn = nn + xi[p] * xi[p];
@@ -365,10 +436,14 @@ __global__ __launch_bounds__(MPF_G_NT) void mpf_optimize_grid_kernel(const MpfGr
   // It depends on the particle alone, so the term of step it + 1 is computed behind the particle store of step it, under the hop.
   double glik[4] = {0, 0, 0, 0};
   auto lik = [&](const float *xp, const int step) {
+    const float pa[2] = {a.act_seq ? a.act_seq[2 * step] : a.past_action[0], a.act_seq ? a.act_seq[2 * step + 1] : a.past_action[1]};
+    if (a.dm.model == DUST_MODEL_SKID_STEER) {
+      mpf_skid_score<P>(a.skl, a.log_space, xp, inv_obs2, glik);
+      return;
+    }
     float pred[4];
     for (int k = 0; k < 4; ++k) pred[k] = k < a.ds ? a.past_obs[k] : 0.f;
     const Coef cf = make_coef(a.dm, xp);
-    const float pa[2] = {a.act_seq ? a.act_seq[2 * step] : a.past_action[0], a.act_seq ? a.act_seq[2 * step + 1] : a.past_action[1]};
     if (a.dm.model == DUST_MODEL_PENDULUM) model_step<DUST_MODEL_PENDULUM>(a.dm, cf, pred, pa);
     else model_step<DUST_MODEL_PARTICLE>(a.dm, cf, pred, pa);
     double J[4][4];
@@ -633,10 +708,14 @@ __global__ __launch_bounds__(MPF_G_NT) void mpf_optimize_poll_kernel(const MpfPo
   const double inv_obs2 = 1.0 / ((double)a.obs_std * (double)a.obs_std);
   double glik[4] = {0, 0, 0, 0};
   auto lik = [&](const float *xp, const int step) {
+    const float pa[2] = {a.act_seq ? a.act_seq[2 * step] : a.past_action[0], a.act_seq ? a.act_seq[2 * step + 1] : a.past_action[1]};
+    if (a.dm.model == DUST_MODEL_SKID_STEER) {
+      mpf_skid_score<P>(a.skl, a.log_space, xp, inv_obs2, glik);
+      return;
+    }
     float pred[4];
     for (int k = 0; k < 4; ++k) pred[k] = k < a.ds ? a.past_obs[k] : 0.f;
     const Coef cf = make_coef(a.dm, xp);
-    const float pa[2] = {a.act_seq ? a.act_seq[2 * step] : a.past_action[0], a.act_seq ? a.act_seq[2 * step + 1] : a.past_action[1]};
     if (a.dm.model == DUST_MODEL_PENDULUM) model_step<DUST_MODEL_PENDULUM>(a.dm, cf, pred, pa);
     else model_step<DUST_MODEL_PARTICLE>(a.dm, cf, pred, pa);
     double J[4][4];
@@ -885,8 +964,11 @@ struct dust_mpf {
   int nx, ny;
   float off_x, off_y;
   float prior_bwv[4];          // per parameter dimension; equal once update_prior(bw) has run (mpf.py:85)
-  float loc[4], past_obs[4], past_action[2];
+  float loc[5], past_obs[5], past_action[2];  // (five wide: the skid-steer state)
   bool have_past;
+  dust::SkidModel skid;     // DUST_MODEL_SKID_STEER: parameters and wheel-speed bounds (dust_mpf_set_skid_steer)
+  dust::SkidLik skl_host;   // ... the likelihood's per-call constants (mpf_skid_prepare) and their device copy
+  dust::SkidLik *skl_dev;
   // control-channel noise of the one-step prediction (model_cfg.ctrl_noise; particle.py:145-148 through likelihoods.py:30-46)
   std::vector<float> *cz;   // recorded draws [n][da] (dust_mpf_set_ctrl_noise), consumed one per SVGD step
   size_t cz_next;
@@ -911,6 +993,7 @@ struct dust_mpf {
   } env;
 };
 
+static float clampf_host(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }  // (common.hpp clampf, for the host)
 static int mpf_env_int(const char *name, int unset) {
   const char *v = getenv(name);
   return v ? atoi(v) : unset;
@@ -945,6 +1028,7 @@ extern "C" void dust_mpf_destroy(dust_mpf *m) {
   if (m->grid_bits) (void)hipFree(m->grid_bits);
   if (m->hpin) (void)hipHostFree(m->hpin);
   if (m->act_seq) (void)hipFree(m->act_seq);
+  if (m->skl_dev) (void)hipFree(m->skl_dev);
   if (m->stream) (void)hipStreamDestroy(m->stream);
   delete m->cz;
   delete m->rng;
@@ -958,8 +1042,13 @@ extern "C" int dust_mpf_create(const dust_mpf_config *cfg, const float *init_par
   if (cfg->n_particles < 1 || cfg->n_particles > 1024) return fail(DUST_ERR_UNSUPPORTED, "MPF supports 1..1024 particles (one workgroup)");
   if (cfg->dim_p < 1 || cfg->dim_p > 4) return fail(DUST_ERR_INVALID, "dim_p must be 1..4");
   if (!(cfg->init_bw > 0.f)) return fail(DUST_ERR_INVALID, "init_bw must be > 0 (the host layer evaluates bw_silverman)");
-  if (cfg->model_cfg.model != DUST_MODEL_PENDULUM && cfg->model_cfg.model != DUST_MODEL_PARTICLE)
-    return fail(DUST_ERR_UNSUPPORTED, "MPF's one-step prediction and its Jacobian exist for the Pendulum and Particle models only");
+  if (cfg->model_cfg.model != DUST_MODEL_PENDULUM && cfg->model_cfg.model != DUST_MODEL_PARTICLE && cfg->model_cfg.model != DUST_MODEL_SKID_STEER)
+    return fail(DUST_ERR_UNSUPPORTED, "MPF's one-step prediction and its Jacobian exist for the Pendulum, Particle and SkidSteerRobot models only");
+  if (cfg->model_cfg.model == DUST_MODEL_SKID_STEER) {
+    if (cfg->dim_s != 5 || cfg->dim_a != 2) return fail(DUST_ERR_INVALID, "the skid-steer model has dim_s = 5, dim_a = 2");
+    if (cfg->dim_p > 3) return fail(DUST_ERR_INVALID, "the skid-steer model has three parameters: dim_p must be 1..3");
+    if (!(cfg->model_cfg.dt > 0.0)) return fail(DUST_ERR_INVALID, "the skid-steer model needs model_cfg.dt > 0 (SkidSteerRobot(delta_t=) has no default)");
+  }
   if (!(cfg->obs_std > 0.f)) return fail(DUST_ERR_INVALID, "obs_std must be > 0");
   if (cfg->model_cfg.model == DUST_MODEL_PARTICLE && cfg->model_cfg.control_type != DUST_CONTROL_ACCELERATION)
     return fail(DUST_ERR_UNSUPPORTED, "MPF over Particle(control_type='velocity'): the mass does not enter that model's step (particle.py:152-153), there is nothing to filter");
@@ -985,8 +1074,57 @@ extern "C" int dust_mpf_create(const dust_mpf_config *cfg, const float *init_par
   HIP_TRY(hipMemcpyAsync(m->x, init_particles, (size_t)m->Mp * m->P * sizeof(float), hipMemcpyHostToDevice, m->stream));
   HIP_TRY(hipStreamSynchronize(m->stream));
   for (int p = 0; p < 4; ++p) m->prior_bwv[p] = cfg->init_bw;
-  for (int k = 0; k < cfg->dim_s && k < 4; ++k) m->loc[k] = initial_obs[k];
+  for (int k = 0; k < cfg->dim_s && k < 5; ++k) m->loc[k] = initial_obs[k];
   m->have_past = false;
+  if (cfg->model_cfg.model == DUST_MODEL_SKID_STEER) {  // SkidSteerRobot.__init__ defaults (skid_steer_robot.py:19-28), nothing sampled
+    m->skid.x_icr = DevParam{DUST_PARAM_PYFLOAT, 0, 0.2};
+    m->skid.wheel_radius = DevParam{DUST_PARAM_PYFLOAT, 0, 0.0625};
+    m->skid.axial_distance = DevParam{DUST_PARAM_PYFLOAT, 0, 0.475};
+    for (int d = 0; d < 2; ++d) {
+      m->skid.lo[d] = -0.5f;
+      m->skid.hi[d] = 0.5f;
+    }
+  }
+  return DUST_OK;
+}
+
+// The filter's SkidSteerRobot: the three parameters (kind / column / value) and the wheel-speed bounds; validated as dust_set_skid_steer
+// does.  The cost fields of the struct are not read.
+extern "C" int dust_mpf_set_skid_steer(dust_mpf *m, const dust_skid_config *g) {
+  if (!m || !g) return fail(DUST_ERR_INVALID, "null argument");
+  if (m->cfg.model_cfg.model != DUST_MODEL_SKID_STEER) return fail(DUST_ERR_STATE, "the filter's model is not DUST_MODEL_SKID_STEER");
+  const dust_param *ps[3] = {&g->x_icr, &g->wheel_radius, &g->axial_distance};
+  unsigned seen = 0u;
+  for (const dust_param *p : ps) {
+    if (p->kind < 0 || p->kind > DUST_PARAM_TENSOR0D) return fail(DUST_ERR_INVALID, "bad parameter kind %d", p->kind);
+    if (p->kind != DUST_PARAM_SAMPLED) continue;
+    if (p->column < 0 || p->column >= m->P) return fail(DUST_ERR_INVALID, "sampled parameter column %d outside dim_p = %d", p->column, m->P);
+    if (seen & (1u << p->column)) return fail(DUST_ERR_INVALID, "two sampled parameters name column %d", p->column);
+    seen |= 1u << p->column;
+  }
+  for (int d = 0; d < 2; ++d)
+    if (!(g->min_wheel_speed[d] <= g->max_wheel_speed[d])) return fail(DUST_ERR_INVALID, "wheel speed bounds: min > max");
+  HIP_TRY(hipSetDevice(m->cfg.device));
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  m->skid.x_icr = DevParam{g->x_icr.kind, g->x_icr.column, g->x_icr.value};
+  m->skid.wheel_radius = DevParam{g->wheel_radius.kind, g->wheel_radius.column, g->wheel_radius.value};
+  m->skid.axial_distance = DevParam{g->axial_distance.kind, g->axial_distance.column, g->axial_distance.value};
+  for (int d = 0; d < 2; ++d) {
+    m->skid.lo[d] = g->min_wheel_speed[d];
+    m->skid.hi[d] = g->max_wheel_speed[d];
+  }
+  return DUST_OK;
+}
+
+// A skid-steer filter can run once its sampled parameters name every particle column (dust_mpf_set_skid_steer)
+static int mpf_model_ready(const dust_mpf *m) {
+  if (m->cfg.model_cfg.model != DUST_MODEL_SKID_STEER) return DUST_OK;
+  unsigned seen = 0u;
+  const DevParam *ps[3] = {&m->skid.x_icr, &m->skid.wheel_radius, &m->skid.axial_distance};
+  for (const DevParam *p : ps)
+    if (p->kind == DUST_PARAM_SAMPLED) seen |= 1u << p->col;
+  if (seen == 0u) return fail(DUST_ERR_STATE, "skid-steer filter: no parameter is sampled - call dust_mpf_set_skid_steer first");
+  if (seen != (1u << m->P) - 1u) return fail(DUST_ERR_STATE, "skid-steer filter: the sampled parameters do not cover the dim_p = %d particle columns", m->P);
   return DUST_OK;
 }
 
@@ -1050,6 +1188,7 @@ extern "C" int dust_mpf_clone(const dust_mpf *src, dust_mpf **out) {
   memcpy(m->past_obs, src->past_obs, sizeof m->past_obs);
   memcpy(m->past_action, src->past_action, sizeof m->past_action);
   m->have_past = src->have_past;
+  m->skid = src->skid;
   if (memcmp(&src->opt, &m->opt, sizeof m->opt) != 0) {
     TRY(dust_mpf_set_optimizer_ex(m, &src->opt));
     const size_t nb = (size_t)src->Mp * src->P * sizeof(float);
@@ -1126,6 +1265,39 @@ extern "C" int dust_mpf_set_ctrl_noise(dust_mpf *m, const float *z, int n) {
   return DUST_OK;
 }
 
+// The particle-independent part of the skid-steer likelihood for the coming launch (SkidLik), copied to the device on the filter's
+// stream; the heading's fp32 cosine and sine are added there by a one-lane kernel.  (The host copy is a member: every filter call
+// synchronises the stream before it returns, so the copy has been read by the time the next call rewrites it.)
+static int mpf_skid_prepare(dust_mpf *m, const dust::SkidLik **dev) {
+  if (!m->skl_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->skl_dev), sizeof(dust::SkidLik)));
+  dust::SkidLik &k = m->skl_host;
+  memset(&k, 0, sizeof k);
+  const DevParam *ps[3] = {&m->skid.x_icr, &m->skid.wheel_radius, &m->skid.axial_distance};
+  for (int q = 0; q < 3; ++q) {
+    k.smp[q] = ps[q]->kind == DUST_PARAM_SAMPLED;
+    k.col[q] = k.smp[q] ? ps[q]->col : 0;
+    k.fix_f[q] = (float)ps[q]->value;
+    k.fix_d[q] = ps[q]->value;
+  }
+  k.r = clampf_host(m->past_action[0], m->skid.lo[0], m->skid.hi[0]);
+  k.l = clampf_host(m->past_action[1], m->skid.lo[1], m->skid.hi[1]);
+  k.dt = (float)m->cfg.model_cfg.dt;
+  for (int q = 0; q < 5; ++q) {
+    k.past[q] = m->past_obs[q];
+    k.obs[q] = m->loc[q];
+  }
+  k.c = std::cos((double)m->past_obs[2]);
+  k.s = std::sin((double)m->past_obs[2]);
+  k.sum = ((double)k.r + (double)k.l) * M_PI;
+  k.dif = 2.0 * M_PI * ((double)k.r - (double)k.l);
+  k.dtd = m->cfg.model_cfg.dt;
+  HIP_TRY(hipMemcpyAsync(m->skl_dev, &k, sizeof k, hipMemcpyHostToDevice, m->stream));
+  dust::mpf_skid_heading_kernel<<<1, 64, 0, m->stream>>>(m->skl_dev);
+  HIP_TRY(hipGetLastError());
+  *dev = m->skl_dev;
+  return DUST_OK;
+}
+
 static int mpf_launch(dust_mpf *m, float bw, float lr, int n_steps, float *gn_dev, float *phi_dev, bool optimise = true, bool grid = false,
                       const float *act_seq_dev = nullptr) {
   serve_cancel_device(m->cfg.device);  // (an armed control tick - closed-loop serving - would hold every CU until its plant state arrives)
@@ -1147,6 +1319,7 @@ static int mpf_launch(dust_mpf *m, float bw, float lr, int n_steps, float *gn_de
     a.past_obs[k] = m->past_obs[k];
     a.obs[k] = m->loc[k];
   }
+  if (m->cfg.model_cfg.model == DUST_MODEL_SKID_STEER) TRY(mpf_skid_prepare(m, &a.skl));
   a.past_action[0] = m->past_action[0];
   a.past_action[1] = m->past_action[1];
   a.act_seq = act_seq_dev;
@@ -1256,11 +1429,12 @@ extern "C" int dust_mpf_optimize(dust_mpf *m, const float *action, const float *
   if (!m) return fail(DUST_ERR_INVALID, "null mpf");
   if (n_steps < 0 || n_steps > 4096) return fail(DUST_ERR_INVALID, "n_steps out of range");
   if (!(bw > 0.f)) return fail(DUST_ERR_INVALID, "bw must be > 0 (the host layer evaluates silvermans_rule when bw is None)");
+  TRY(mpf_model_ready(m));
   HIP_TRY(hipSetDevice(m->cfg.device));
   if (new_obs) {  // GaussianLikelihood.condition likelihoods.py:51-64
     if (!action) return fail(DUST_ERR_INVALID, "condition() needs the action that produced new_obs");
     memcpy(m->past_obs, m->loc, sizeof m->past_obs);
-    for (int k = 0; k < m->cfg.dim_s && k < 4; ++k) m->loc[k] = new_obs[k];
+    for (int k = 0; k < m->cfg.dim_s && k < 5; ++k) m->loc[k] = new_obs[k];
     for (int k = 0; k < 2; ++k) m->past_action[k] = k < m->cfg.dim_a ? action[k] : 0.f;
     m->have_past = true;
   }
@@ -1311,6 +1485,7 @@ extern "C" int dust_mpf_stats(dust_mpf *m, long long out[2]) {
 
 extern "C" int dust_mpf_phi(dust_mpf *m, float bw, float *phi) {
   if (!m || !phi) return fail(DUST_ERR_INVALID, "null argument");
+  TRY(mpf_model_ready(m));
   if (!m->have_past) return fail(DUST_ERR_STATE, "Previous action is None. Need at least one observation to start sampling.");
   HIP_TRY(hipSetDevice(m->cfg.device));
   const float *acts = nullptr;
@@ -1325,7 +1500,7 @@ extern "C" int dust_mpf_phi(dust_mpf *m, float bw, float *phi) {
 extern "C" int dust_mpf_condition(dust_mpf *m, const float *action, const float *new_obs) {
   if (!m || !new_obs) return fail(DUST_ERR_INVALID, "null argument");
   memcpy(m->past_obs, m->loc, sizeof m->past_obs);
-  for (int k = 0; k < m->cfg.dim_s && k < 4; ++k) m->loc[k] = new_obs[k];
+  for (int k = 0; k < m->cfg.dim_s && k < 5; ++k) m->loc[k] = new_obs[k];
   if (action) {
     for (int k = 0; k < 2; ++k) m->past_action[k] = k < m->cfg.dim_a ? action[k] : 0.f;
     m->have_past = true;
@@ -1429,6 +1604,12 @@ extern "C" int dust_dual_tick(dust_ctx *c, dust_mpf *m, const float *state, cons
   if (n_steps < 1 || mpf_steps < 0) return fail(DUST_ERR_INVALID, "bad step counts");
   if (c->cfg.dim_p != m->P) return fail(DUST_ERR_INVALID, "the controller samples dim_p = %d dynamics parameters, the filter carries P = %d", c->cfg.dim_p, m->P);
   if (c->cfg.device != m->cfg.device) return fail(DUST_ERR_INVALID, "controller and filter live on different devices");
+  if (c->cfg.model == DUST_MODEL_SKID_STEER && m->cfg.model_cfg.model == DUST_MODEL_SKID_STEER) {  // the filter's columns are the controller's
+    const DevParam *pc[3] = {&c->skid.x_icr, &c->skid.wheel_radius, &c->skid.axial_distance}, *pm[3] = {&m->skid.x_icr, &m->skid.wheel_radius, &m->skid.axial_distance};
+    for (int k = 0; k < 3; ++k)
+      if ((pc[k]->kind == DUST_PARAM_SAMPLED) != (pm[k]->kind == DUST_PARAM_SAMPLED) || (pc[k]->kind == DUST_PARAM_SAMPLED && pc[k]->col != pm[k]->col))
+        return fail(DUST_ERR_INVALID, "controller and filter name different uncertain skid-steer parameters (or in another column order)");
+  }
   if (comm_active(c)) return fail(DUST_ERR_UNSUPPORTED, "the dual tick runs on an unsharded controller (the filter is replicated: tick it per rank)");
   HIP_TRY(hipSetDevice(c->cfg.device));
   float bw = bw_in;

@@ -52,6 +52,28 @@ __device__ __forceinline__ float skid_param(const DevParam &p, const float *prow
   return (float)p.value;
 }
 
+// One SkidSteerRobot.step (skid_steer_robot.py:93-122) in place, operation by operation as the header states it; r, l: the wheel speeds
+// AFTER the clamp to the action bounds.  The rollout kernel below and the filter's one-step prediction (mpf.hpp) share it.
+// skid_step_cs takes the heading's cosine and sine from its caller: the filter steps every particle from ONE past state, so it evaluates
+// them once per call (mpf_skid_heading_kernel) instead of carrying fast_cosf / fast_sinf - with their huge-argument fall-back - in its
+// optimisation kernels.
+__device__ __forceinline__ void skid_step_cs(float x[5], const float r, const float l, const float xicr, const float wr, const float ad, const float dt,
+                                             const float cs, const float sn) {
+  const float lin = ((r + l) * PI_F) * wr;
+  const float ang = ((((r - l) * 2.0f) * PI_F) * wr) / ad;
+  const float fwd = lin * dt, lat = ((-ang) * xicr) * dt;
+  const float nx = (x[0] + fwd * cs) - lat * sn;
+  const float ny = (x[1] + fwd * sn) + lat * cs;
+  x[2] = x[2] + ang * dt;
+  x[0] = nx;
+  x[1] = ny;
+  x[3] = lin;
+  x[4] = ang;
+}
+__device__ __forceinline__ void skid_step(float x[5], const float r, const float l, const float xicr, const float wr, const float ad, const float dt) {
+  skid_step_cs(x, r, l, xicr, wr, ad, dt, fast_cosf(x[2]), fast_sinf(x[2]));
+}
+
 __global__ __launch_bounds__(256) void skid_rollout_kernel(const SkidArgs a) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= a.n_local * a.S) return;
@@ -97,18 +119,7 @@ __global__ __launch_bounds__(256) void skid_rollout_kernel(const SkidArgs a) {
       }
       const double cc = (double)((a0 * a0) * a.sk.w_ctrl[0]) + (double)((a1 * a1) * a.sk.w_ctrl[1]);
       tot += (double)((float)sc + (float)cc);
-      const float r = clampf(a0, a.sk.lo[0], a.sk.hi[0]), l = clampf(a1, a.sk.lo[1], a.sk.hi[1]);
-      const float lin = ((r + l) * PI_F) * wr;
-      const float ang = ((((r - l) * 2.0f) * PI_F) * wr) / ad;
-      const float fwd = lin * a.dt, lat = ((-ang) * xicr) * a.dt;
-      const float cs = fast_cosf(x[2]), sn = fast_sinf(x[2]);
-      const float nx = (x[0] + fwd * cs) - lat * sn;
-      const float ny = (x[1] + fwd * sn) + lat * cs;
-      x[2] = x[2] + ang * a.dt;
-      x[0] = nx;
-      x[1] = ny;
-      x[3] = lin;
-      x[4] = ang;
+      skid_step(x, clampf(a0, a.sk.lo[0], a.sk.hi[0]), clampf(a1, a.sk.lo[1], a.sk.hi[1]), xicr, wr, ad, a.dt);
       if (so)
 #pragma unroll
         for (int k = 0; k < 5; ++k) so[(size_t)(t + 1) * 5 + k] = x[k];

@@ -139,7 +139,8 @@ typedef struct dust_config {
  * this model, its MultiDISCO takes any callable (disco.py:294-346); the family is what dust_amd.costs.QuadraticCost evaluates:
  *   inst(x, a) = sum_k w_state[k] (x_k - goal_k)^2 + sum_d w_ctrl[d] a_d^2 ,   term(x) = sum_k w_term[k] (x_k - goal_k)^2 .
  * dust_create gives the reference's constructor defaults; dust_set_skid_steer replaces them.  Sampled parameters
- * (kind DUST_PARAM_SAMPLED) name columns of the `params` rows in the order of `uncertain_params`. */
+ * (kind DUST_PARAM_SAMPLED) name columns of the `params` rows in the order of `uncertain_params`.
+ * The dynamics filter takes the same struct (dust_mpf_set_skid_steer: parameters and bounds; the cost fields are ignored there). */
 typedef struct dust_skid_config {
   dust_param x_icr, wheel_radius, axial_distance;
   float min_wheel_speed[2], max_wheel_speed[2]; /* action_space bounds: the step clamps the wheel speeds to them */
@@ -381,7 +382,16 @@ typedef struct dust_mpf_config {
   float init_bw;       /* MPF(bw=): bandwidth of the initial prior; <= 0: bw_silverman of the particles (svgd.py:55-81) */
   dust_config model_cfg; /* only the model fields are read */
 } dust_mpf_config;
+/* Models: DUST_MODEL_PENDULUM, DUST_MODEL_PARTICLE (acceleration control) and DUST_MODEL_SKID_STEER (dim_s = 5, dim_a = 2, dim_p = 1..3;
+ * model_cfg.dt is SkidSteerRobot's delta_t; model_cfg.ctrl_noise stays a Particle field). */
 int dust_mpf_create(const dust_mpf_config *cfg, const float *init_particles, const float *initial_obs, dust_mpf **out);
+/* The filter's SkidSteerRobot (skid_steer_robot.py:19-52): the three parameters with kind / column / value - a sampled one names its
+ * particle column, in any order - and the wheel-speed bounds; the cost fields of the struct are ignored.  Validated as
+ * dust_set_skid_steer validates (a sampled column outside dim_p, or named twice: DUST_ERR_INVALID).  Until the call the constructor's
+ * defaults hold with nothing sampled, and dust_mpf_phi / dust_mpf_optimize return DUST_ERR_STATE; they do so as well while the sampled
+ * columns do not cover dim_p.  dust_mpf_clone copies the model.  dust_dual_tick takes a skid-steer controller and filter that name the
+ * same uncertain parameters in the same columns. */
+int dust_mpf_set_skid_steer(dust_mpf *mpf, const dust_skid_config *cfg);
 int dust_mpf_clone(const dust_mpf *src, dust_mpf **out);
 /* MPF(optimizer_class=, **opt_args) svgd.py:108-122, mpf.py:24: DUST_OPT_SGD (default here, the demos' choice) or DUST_OPT_ADAM (the
  * reference's class default; betas / eps as torch.optim.Adam).  The optimiser state starts at zero and persists across
