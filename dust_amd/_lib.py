@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("DUST_AMD_LIB", os.path.join(_HERE, "libdust_amd.so"))
 
 ABI_VERSION = 2
 OK, ERR_INVALID, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_HIP, ERR_STATE = range(6)
-MODEL_PENDULUM, MODEL_PARTICLE, MODEL_SKID_STEER = 0, 1, 2
+MODEL_PENDULUM, MODEL_PARTICLE, MODEL_SKID_STEER, MODEL_CARTPOLE = 0, 1, 2, 3
 COST_PENDULUM_QUADCOS, COST_PARTICLE_DEFAULT, COST_QUADRATIC = 0, 1, 2
 KERNEL_K1_RBF, KERNEL_K2_IIDMP, KERNEL_K2_SHARED, KERNEL_IMQ = 0, 1, 2, 3
 LIK_EXP_UTILITY, LIK_EXPECTED_COST = 0, 1
@@ -40,6 +40,11 @@ class SkidConfig(C.Structure):  # dust_skid_config
     _fields_ = [("x_icr", Param), ("wheel_radius", Param), ("axial_distance", Param), ("min_wheel_speed", C.c_float * 2),
                 ("max_wheel_speed", C.c_float * 2), ("goal", C.c_float * 5), ("w_state", C.c_float * 5), ("w_term", C.c_float * 5),
                 ("w_ctrl", C.c_float * 2)]
+
+
+class CartPoleConfig(C.Structure):  # dust_cartpole_config
+    _fields_ = [("g", Param), ("f_mag", Param), ("mass_cart", Param), ("mass_pole", Param), ("length", Param), ("mu_c", Param),
+                ("mu_p", Param), ("goal", C.c_float * 4), ("w_state", C.c_float * 4), ("w_term", C.c_float * 4), ("w_ctrl", C.c_float * 1)]
 
 
 class Config(C.Structure):
@@ -175,6 +180,8 @@ SYMBOLS = {
     "dust_mpf_get_prior": (C.c_int, [VP, FP, FP]),
     "dust_set_skid_steer": (C.c_int, [VP, C.POINTER(SkidConfig)]),
     "dust_mpf_set_skid_steer": (C.c_int, [VP, C.POINTER(SkidConfig)]),
+    "dust_set_cartpole": (C.c_int, [VP, C.POINTER(CartPoleConfig)]),
+    "dust_mpf_set_cartpole": (C.c_int, [VP, C.POINTER(CartPoleConfig)]),
     "dust_mpf_set_prior_bw": (C.c_int, [VP, FP, C.c_int]),
     "dust_mpf_get_prior_bw": (C.c_int, [VP, FP]),
     "dust_mpf_stats": (C.c_int, [VP, C.POINTER(C.c_longlong)]),

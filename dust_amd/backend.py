@@ -36,6 +36,16 @@ def _vp(a):
     return None if a is None else C.cast(a.ctypes.data_as(L.FP), L.VP)
 
 
+# What make_config needs to know of a family: ids, (dim_a, dim_s), the action bound without min_a / max_a (None: Particle's max_accel)
+# and the default dt (None: the family has none)
+_FAMILIES = {
+    "pendulum": dict(model=L.MODEL_PENDULUM, cost=L.COST_PENDULUM_QUADCOS, dims=(1, 2), bound=2.0, dt=0.05),
+    "particle": dict(model=L.MODEL_PARTICLE, cost=L.COST_PARTICLE_DEFAULT, dims=(2, 4), bound=None, dt=0.015),
+    "skid_steer": dict(model=L.MODEL_SKID_STEER, cost=L.COST_QUADRATIC, dims=(2, 5), bound=0.5, dt=None),
+    "cartpole": dict(model=L.MODEL_CARTPOLE, cost=L.COST_QUADRATIC, dims=(1, 4), bound=1.0, dt=0.05),
+}
+
+
 def make_config(model="pendulum", N=1, S=1, M=1, H=1, uncertain_params=None, params_scalar_event=False,
                 params_log_space=False, kernel="K1", likelihood="ExponentiatedUtility", optimizer="SGD", lr=1.0,
                 alpha=1.0, temperature=None, ctrl_penalty=1.0, sigma_a=1.0, sigma_p=1.0, chol_a=None, a_pre=None,
@@ -50,18 +60,17 @@ def make_config(model="pendulum", N=1, S=1, M=1, H=1, uncertain_params=None, par
     c = L.Config()
     c.abi_version = L.ABI_VERSION
     c.device = device
-    pend = model == "pendulum"
-    skid = model == "skid_steer"
-    if model not in ("pendulum", "particle", "skid_steer"):
+    if model not in _FAMILIES:
         raise ValueError("unknown model family %r" % (model,))
-    c.model = L.MODEL_PENDULUM if pend else (L.MODEL_SKID_STEER if skid else L.MODEL_PARTICLE)
-    c.cost = L.COST_PENDULUM_QUADCOS if pend else (L.COST_QUADRATIC if skid else L.COST_PARTICLE_DEFAULT)
+    fam = _FAMILIES[model]
+    skid, cart, part = (model == k for k in ("skid_steer", "cartpole", "particle"))
+    c.model, c.cost = fam["model"], fam["cost"]
     c.n_policies, c.n_samples, c.n_params, c.horizon = N, S, M, H
     if control_type not in ("acceleration", "velocity"):
         raise IOError('control_type "{}" not recognized'.format(control_type))  # particle.py:59-60
-    vel = control_type == "velocity" and not pend and not skid
-    c.dim_a, c.dim_s = (1, 2) if pend else ((2, 5) if skid else ((2, 2) if vel else (2, 4)))
-    if not pend and not skid:  # Particle(control_type=, deterministic=, noise_std=) particle.py:13-31
+    vel = control_type == "velocity" and part
+    c.dim_a, c.dim_s = (2, 2) if vel else fam["dims"]
+    if part:  # Particle(control_type=, deterministic=, noise_std=) particle.py:13-31
         c.control_type = L.CONTROL_VELOCITY if vel else L.CONTROL_ACCELERATION
         c.ctrl_noise = int(not deterministic)
         ns = np.broadcast_to(np.asarray(noise_std, np.float32).reshape(-1), (2,))
@@ -107,24 +116,27 @@ def make_config(model="pendulum", N=1, S=1, M=1, H=1, uncertain_params=None, par
         elif c.dim_a > 2 or not torch.equal(ac, torch.diag(torch.diag(ac))) or not torch.equal(pc, torch.diag(torch.diag(pc))):
             raise NotImplementedError("full covariances are implemented for dim_a = 2")
     c.bw_scale, c.imq_ell = bw_scale, imq_ell
-    lo = np.broadcast_to(np.asarray((-2.0 if pend else (-0.5 if skid else -max_accel)) if min_a is None else min_a, np.float32), (c.dim_a,))
-    hi = np.broadcast_to(np.asarray((2.0 if pend else (0.5 if skid else max_accel)) if max_a is None else max_a, np.float32), (c.dim_a,))
+    bound = max_accel if fam["bound"] is None else fam["bound"]
+    lo = np.broadcast_to(np.asarray(-bound if min_a is None else min_a, np.float32), (c.dim_a,))
+    hi = np.broadcast_to(np.asarray(bound if max_a is None else max_a, np.float32), (c.dim_a,))
     for d in range(c.dim_a):
         c.min_a[d], c.max_a[d] = lo[d], hi[d]
     c.seed = seed
     if skid and dt is None:
         raise ValueError("SkidSteerRobot(delta_t=...) has no default: pass dt")
-    c.dt = (0.05 if pend else 0.015) if dt is None else dt
+    c.dt = fam["dt"] if dt is None else dt
 
     def par(name, value):
         if use_params and name in up:
             return L.Param(L.PARAM_SAMPLED, up.index(name), float(value))
         return L.Param(L.PARAM_TENSOR0D if (mass_0dim and name == "mass") else L.PARAM_PYFLOAT, 0, float(value))
 
+    if cart:  # (its seven parameters travel through dust_set_cartpole; the Pendulum fields stay at their defaults)
+        up, g, length = [], 9.8, 1.0
     c.g, c.mass, c.length = par("g", g), par("mass", mass), par("length", length)
     c.max_torque, c.max_speed_pend, c.w_cos, c.w_vel = 2.0, 8.0, w_cos, w_vel
     c.max_speed, c.max_accel = max_speed, max_accel
-    c.can_crash, c.with_obstacle = int(can_crash), int(with_obstacle and not pend and not skid)
+    c.can_crash, c.with_obstacle = int(can_crash), int(with_obstacle and part)
     c.cell_size = cell_size
     pad4 = lambda v: (list(np.asarray(v, np.float32).reshape(-1)) + [0.0] * 4)[:4]  # (velocity control: two-entry target / weights)
     c.target[:] = pad4(target)
@@ -135,6 +147,23 @@ def make_config(model="pendulum", N=1, S=1, M=1, H=1, uncertain_params=None, par
     return c
 
 
+CARTPOLE_PARAMS = ("g", "f_mag", "mass_cart", "mass_pole", "length", "mu_c", "mu_p")  # CartPoleModel.__init__ order, cartpole.py:42-51
+
+
+def _cartpole_struct(values, sampled):
+    """dust_cartpole_config with the seven parameters: the names in `sampled` become particle / params columns in that order."""
+    unknown = [k for k in sampled if k not in CARTPOLE_PARAMS]
+    if unknown:
+        raise ValueError("CartPoleModel has no parameter %r" % (unknown[0],))
+    if len(sampled) > 4:
+        raise ValueError("at most 4 uncertain parameters (dim_p <= 4), got %d" % len(sampled))
+    g = L.CartPoleConfig()
+    for name in CARTPOLE_PARAMS:
+        v = float(values[name])
+        setattr(g, name, L.Param(L.PARAM_SAMPLED, sampled.index(name), v) if name in sampled else L.Param(L.PARAM_PYFLOAT, 0, v))
+    return g
+
+
 class Context:
     def __init__(self, cfg=None, grid=None, _handle=None, **kw):
         self._h = None
@@ -143,6 +172,7 @@ class Context:
         optim = kw.pop("optim", None)  # dust_amd.optim.optimizer_config(...): an optimiser beyond dust_config's plain SGD / Adam
         skid_kw = {k: kw.pop(k) for k in ("x_icr", "wheel_radius", "axial_distance", "goal", "w_quad_state", "w_quad_term", "w_quad_ctrl")
                    if k in kw}
+        cart_kw = {k: kw[k] for k in CARTPOLE_PARAMS if k in kw} if kw.get("model") == "cartpole" else {}
         if _handle is not None:
             self._h = _handle
         else:
@@ -167,6 +197,9 @@ class Context:
             self.set_grid(grid)
         if _handle is None and got.model == L.MODEL_SKID_STEER:
             self.set_skid_steer(uncertain_params=kw.get("uncertain_params"), sampling=kw.get("sampling"), **skid_kw)
+        if _handle is None and got.model == L.MODEL_CARTPOLE:
+            cart_kw.update({k: v for k, v in skid_kw.items() if k in ("goal", "w_quad_state", "w_quad_term", "w_quad_ctrl")})
+            self.set_cartpole(uncertain_params=kw.get("uncertain_params"), sampling=kw.get("sampling"), **cart_kw)
         # iid_mp(RBF(bandwidth >= 0)): fixed bandwidth instead of the median trick; RBF(minimum_bw=): the clamp of either (base_kernels.py:44-92)
         if (k2_bw is not None and float(k2_bw) >= 0) or (_handle is None and float(k2_min) != 1e-5 and got.kernel in (L.KERNEL_K2_IIDMP, L.KERNEL_K2_SHARED)):
             L.check(lib.dust_set_k2_bandwidth(self._h, float(-1.0 if k2_bw is None else k2_bw), float(k2_min)))
@@ -295,6 +328,19 @@ class Context:
         g.w_term[:] = [float(v) for v in w_quad_term]
         g.w_ctrl[:] = [float(v) for v in w_quad_ctrl]
         L.check(L.load().dust_set_skid_steer(self._h, C.byref(g)))
+
+    def set_cartpole(self, g=9.8, f_mag=10.0, mass_cart=1.0, mass_pole=0.1, length=1.0, mu_c=0.5e-3, mu_p=2e-6, goal=(0, 0, 0, 0),
+                     w_quad_state=(1, 1, 1, 1), w_quad_term=(1, 1, 1, 1), w_quad_ctrl=(0,), uncertain_params=None, sampling=None):
+        """CartPoleModel parameters (cartpole.py:42-51; `uncertain_params` name the sampled ones, in column order) and the quadratic
+        cost family (dust_amd.costs.QuadraticCost: 4 state entries, 1 control weight)."""
+        up = list(uncertain_params) if uncertain_params else []
+        use = bool(up) if sampling is None else bool(sampling)
+        cfg = _cartpole_struct(dict(g=g, f_mag=f_mag, mass_cart=mass_cart, mass_pole=mass_pole, length=length, mu_c=mu_c, mu_p=mu_p), up if use else [])
+        cfg.goal[:] = [float(v) for v in goal]
+        cfg.w_state[:] = [float(v) for v in w_quad_state]
+        cfg.w_term[:] = [float(v) for v in w_quad_term]
+        cfg.w_ctrl[:] = [float(v) for v in w_quad_ctrl]
+        L.check(L.load().dust_set_cartpole(self._h, C.byref(cfg)))
 
     def set_ctrl_noise(self, z):
         """Recorded control-channel noise for the next rollouts of a Particle(deterministic=False) context (particle.py:145-148):
@@ -568,6 +614,8 @@ class MpfContext:
         if c.model == L.MODEL_SKID_STEER:
             self.set_skid_steer(uncertain_params=uncertain_params, min_a=c.model_cfg.min_a, max_a=c.model_cfg.max_a,
                                 **{k: model_kw[k] for k in ("x_icr", "wheel_radius", "axial_distance") if k in model_kw})
+        if c.model == L.MODEL_CARTPOLE:
+            self.set_cartpole(uncertain_params=uncertain_params, **{k: model_kw[k] for k in CARTPOLE_PARAMS if k in model_kw})
         if grid is not None:
             g = _f(grid)
             L.check(lib.dust_mpf_set_grid(self._h, _p(g), g.shape[0], g.shape[1], float(int(g.shape[0] / 2)), float(int(g.shape[1] / 2))))
@@ -605,6 +653,13 @@ class MpfContext:
         for d in range(2):
             g.min_wheel_speed[d], g.max_wheel_speed[d] = float(min_a[d]), float(max_a[d])
         L.check(L.load().dust_mpf_set_skid_steer(self._h, C.byref(g)))
+
+    def set_cartpole(self, g=9.8, f_mag=10.0, mass_cart=1.0, mass_pole=0.1, length=1.0, mu_c=0.5e-3, mu_p=2e-6, uncertain_params=()):
+        """The filter's CartPoleModel (dust_mpf_set_cartpole): `uncertain_params` name the particle columns, in order; the other
+        parameters stay at the given values."""
+        cfg = _cartpole_struct(dict(g=g, f_mag=f_mag, mass_cart=mass_cart, mass_pole=mass_pole, length=length, mu_c=mu_c, mu_p=mu_p),
+                               list(uncertain_params or ()))
+        L.check(L.load().dust_mpf_set_cartpole(self._h, C.byref(cfg)))
 
     def silverman(self):
         """silvermans_rule of the pooled particles times bw_scale, on the device (dust_mpf_silverman)."""

@@ -76,7 +76,7 @@ class MultiDISCO:
 
     # ------------------------------------------------------------------ context management
     def _config(self, model, params_dist):
-        if model.family not in ("pendulum", "particle", "skid_steer"):
+        if model.family not in ("pendulum", "particle", "skid_steer", "cartpole"):
             raise NotImplementedError("no rollout kernel family for %s" % type(model).__name__)
         chol = torch.linalg.cholesky(self.a_dist.covariance_matrix).diag()
         sigma = self.a_dist.covariance_matrix.diag().sqrt()  # svmpc.py:107-111
@@ -98,6 +98,10 @@ class MultiDISCO:
         pd = model.params_dict
         for k in ("x_icr", "wheel_radius", "axial_distance"):  # SkidSteerRobot (skid_steer_robot.py:40-44)
             if k in pd:
+                cfg[k] = float(pd[k])
+        if model.family == "cartpole":  # CartPoleModel (cartpole.py:79-87); g and length follow below
+            model.check_device_params()
+            for k in ("f_mag", "mass_cart", "mass_pole", "mu_c", "mu_p"):
                 cfg[k] = float(pd[k])
         for k in ("g", "mass", "length"):
             if k in pd:

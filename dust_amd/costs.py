@@ -25,7 +25,7 @@ class PendulumQuadCos:
 
 
 class QuadraticCost:
-    """Quadratic state / control cost for any model (the skid-steer family uses it: the reference ships no cost for that model and
+    """Quadratic state / control cost for any model (the skid-steer and cart-pole families use it: the reference ships no cost for these models and
     its MultiDISCO takes any callable with this signature, disco.py:294-346):
         inst(x, a) = sum_k w_state[k] (x_k - goal_k)^2 + sum_d w_ctrl[d] a_d^2        term(x) = sum_k w_term[k] (x_k - goal_k)^2
     `inst_cost` / `term_cost` are plain torch, so the same object drives the reference's controller and this one's kernels."""
@@ -98,6 +98,18 @@ def recognise(model, inst_cost_fn, term_cost_fn):
         if owner.goal.numel() != 5 or owner.w_state.numel() != 5 or owner.w_term.numel() != 5:
             raise ValueError("QuadraticCost for SkidSteerRobot needs 5 state entries (x, y, theta, v, omega)")
         wc = owner.w_ctrl if owner.w_ctrl is not None else torch.zeros(2)
+        return dict(goal=tuple(float(v) for v in owner.goal), w_quad_state=tuple(float(v) for v in owner.w_state),
+                    w_quad_term=tuple(float(v) for v in owner.w_term), w_quad_ctrl=tuple(float(v) for v in wc))
+    if fam == "cartpole":
+        owner = getattr(inst_cost_fn, "__self__", None)
+        if not isinstance(owner, QuadraticCost) or getattr(term_cost_fn, "__self__", None) is not owner:
+            raise NotImplementedError("CartPoleModel runs with dust_amd.costs.QuadraticCost(...).inst_cost / .term_cost (an opaque "
+                                      "callable cannot run on the device and there is no CPU fallback)")
+        if owner.goal.numel() != 4 or owner.w_state.numel() != 4 or owner.w_term.numel() != 4:
+            raise ValueError("QuadraticCost for CartPoleModel needs 4 state entries (x, x_d, theta, theta_d)")
+        if owner.w_ctrl is not None and owner.w_ctrl.numel() != 1:
+            raise ValueError("QuadraticCost for CartPoleModel needs 1 control weight")
+        wc = owner.w_ctrl if owner.w_ctrl is not None else torch.zeros(1)
         return dict(goal=tuple(float(v) for v in owner.goal), w_quad_state=tuple(float(v) for v in owner.w_state),
                     w_quad_term=tuple(float(v) for v in owner.w_term), w_quad_ctrl=tuple(float(v) for v in wc))
     raise NotImplementedError("model family %r has no HIP kernel" % (fam,))

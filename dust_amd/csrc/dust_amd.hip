@@ -36,6 +36,7 @@
 #include "pairwise_packed.hpp"
 #include "peer_gather.hpp"
 #include "skid.hpp"
+#include "cartpole.hpp"
 #include "particle_general.hpp"
 #include "rollout.hpp"
 #include "stein.hpp"
@@ -129,6 +130,7 @@ struct dust_ctx {
   bool no_handoff;           // replay of a tick that found the device shared: plain kernels only, nothing that spins on its own grid
   unsigned long persist_declined;  // key of the (shape, state) for which the one-launch ticks last declined: no staging for it again
   SkidModel skid;            // DUST_MODEL_SKID_STEER: model parameters and the quadratic cost (dust_set_skid_steer)
+  CartModel cart;            // DUST_MODEL_CARTPOLE: model parameters and the quadratic cost (dust_set_cartpole)
   // pairwise_packed.hpp: the near-key lists of the last large-set pass 1 - key indices [tiles][chunks * 64], unit offsets
   // [tiles][chunks + 1], unit query masks [tiles][chunks][4], slice boundaries of pass 1 / pass 2, non-zero flags of the units' kernel blocks
   float *pk_idx, *pk_uoff, *pk_uq, *pk_soff, *pk_goff, *pk_nzu, *pk_perm, *pk_lead;
@@ -272,6 +274,28 @@ struct dust_ctx {
 };
 
 static DevParam dev_param(const dust_param &p) { return DevParam{p.kind, p.column, p.value}; }
+
+// CartPoleModel.__init__ defaults in params_dict order (cartpole.py:42-51, 79-87)
+static void cartpole_defaults(DevParam par[CP_NPAR]) {
+  const double v[CP_NPAR] = {9.8, 1.0, 0.1, 1.0, 0.5e-3, 2e-6, 10.0};
+  for (int q = 0; q < CP_NPAR; ++q) par[q] = DevParam{DUST_PARAM_PYFLOAT, 0, v[q]};
+}
+// dust_cartpole_config's parameters in params_dict order, checked: kinds, sampled columns inside dim_p, no column named twice
+static int cartpole_params(const dust_cartpole_config *g, int P, DevParam par[CP_NPAR]) {
+  const dust_param *ps[CP_NPAR] = {&g->g, &g->mass_cart, &g->mass_pole, &g->length, &g->mu_c, &g->mu_p, &g->f_mag};
+  unsigned seen = 0u;
+  for (int q = 0; q < CP_NPAR; ++q) {
+    const dust_param *p = ps[q];
+    if (p->kind < 0 || p->kind > DUST_PARAM_TENSOR0D) return fail(DUST_ERR_INVALID, "bad parameter kind %d", p->kind);
+    if (p->kind == DUST_PARAM_SAMPLED) {
+      if (p->column < 0 || p->column >= P) return fail(DUST_ERR_INVALID, "sampled parameter column %d outside dim_p = %d", p->column, P);
+      if (seen & (1u << p->column)) return fail(DUST_ERR_INVALID, "two sampled parameters name column %d", p->column);
+      seen |= 1u << p->column;
+    }
+    par[q] = dev_param(*p);
+  }
+  return DUST_OK;
+}
 
 static DevModel make_dev_model(const dust_ctx *c) {
   const dust_config &g = c->cfg;
@@ -457,6 +481,10 @@ static int validate(const dust_config *g) {
     if (g->dim_a != 2 || g->dim_s != 5) return fail(DUST_ERR_INVALID, "SkidSteerRobot has dim_a=2, dim_s=5");
     if (g->cost != DUST_COST_QUADRATIC) return fail(DUST_ERR_UNSUPPORTED, "the skid-steer model runs with the quadratic cost family (DUST_COST_QUADRATIC)");
     if (g->dim_p > 3) return fail(DUST_ERR_INVALID, "SkidSteerRobot has 3 parameters");
+  } else if (g->model == DUST_MODEL_CARTPOLE) {
+    if (g->dim_a != 1 || g->dim_s != 4) return fail(DUST_ERR_INVALID, "CartPoleModel has dim_a=1, dim_s=4");
+    if (g->cost != DUST_COST_QUADRATIC) return fail(DUST_ERR_UNSUPPORTED, "the cart-pole model runs with the quadratic cost family (DUST_COST_QUADRATIC)");
+    if (g->full_cov) return fail(DUST_ERR_UNSUPPORTED, "the cart-pole model has one action: a_cov is 1 x 1");
   } else {
     return fail(DUST_ERR_UNSUPPORTED, "unknown model id %d", g->model);
   }
@@ -555,7 +583,9 @@ static bool particle_general(const dust_ctx *c) {
 // ... and contexts with a FULL 2 x 2 action / prior covariance (disco.py:91-98, svgd.py:84-89): the one-launch and fused forms carry the
 // diagonal arithmetic only - the launch-per-iteration kernels take the off-diagonal terms (rollout.hpp stage 1, the whitened prior pass)
 static bool full_cov(const dust_ctx *c) { return c->cfg.full_cov != 0; }
-static bool two_pass_family(const dust_ctx *c) { return c->cfg.model == DUST_MODEL_SKID_STEER || particle_general(c) || full_cov(c); }
+static bool two_pass_family(const dust_ctx *c) {
+  return c->cfg.model == DUST_MODEL_SKID_STEER || c->cfg.model == DUST_MODEL_CARTPOLE || particle_general(c) || full_cov(c);
+}
 static bool comm_active(const dust_ctx *c) { return c->comm && (c->comm_world > 1 || c->env.comm_force >= 0); }
 static void comm_release(dust_ctx *c);
 extern "C" int dust_comm_peer_gather(dust_ctx *c, int on);
@@ -722,6 +752,11 @@ static int create_impl(const dust_config *cfg, dust_ctx **out) {
       c->skid.hi[d] = 0.5f;
     }
     for (int k = 0; k < 5; ++k) c->skid.w_state[k] = c->skid.w_term[k] = 1.0f;
+  }
+  if (cfg->model == DUST_MODEL_CARTPOLE) {  // CartPoleModel.__init__ defaults (cartpole.py:42-51); unit state weights, no goal
+    memset(&c->cart, 0, sizeof c->cart);
+    cartpole_defaults(c->cart.par);
+    for (int k = 0; k < 4; ++k) c->cart.w_state[k] = c->cart.w_term[k] = 1.0f;
   }
   c->P = cfg->dim_p > 0 ? cfg->dim_p : 1;
   c->D = c->H * c->da;
@@ -967,6 +1002,7 @@ extern "C" int dust_clone(const dust_ctx *src, dust_ctx **out) {
   c->mu_aliased = src->mu_aliased;
   c->have_sample = src->have_sample;
   c->skid = src->skid;
+  c->cart = src->cart;
   c->k2_fixed_h = src->k2_fixed_h;  // (dust_set_k2_bandwidth: RBF(bandwidth=, minimum_bw=) - a deep-copied controller keeps its kernel)
   c->k2_min_bw = src->k2_min_bw;
   if (src->cz_dev && src->cz_sets > 0) {  // recorded control-noise draws not consumed yet (dust_set_ctrl_noise)
@@ -1526,6 +1562,46 @@ static int launch_rollout(dust_ctx *c, const SampleOpts &o_in) {
       TRY(rollout_args(c, o, a, &nt, &lds));
     }
   }
+  if (c->cfg.model == DUST_MODEL_CARTPOLE) {
+    // pass 1 (cartpole.hpp): rollouts + costs (+ states); pass 2 (below): the regular kernel in its injected-costs mode
+    if (a.noise_f16 || o.store_f16) return fail(DUST_ERR_UNSUPPORTED, "binary16 storage is not implemented for the cart-pole family");
+    if (a.mw) return fail(DUST_ERR_UNSUPPORTED, "sigma-point weights are not implemented for the cart-pole family");
+    if (o.costs_in == nullptr) {
+      Prof ps(c, DUST_K_ROLLOUT_STATES);
+      CartArgs k;
+      memset(&k, 0, sizeof k);
+      k.cp = c->cart;
+      k.N_total = c->N;
+      k.n0 = c->n0;
+      k.n_local = c->nloc;
+      k.S = c->S;
+      k.M = c->M;
+      k.H = c->H;
+      k.D = c->D;
+      k.P = c->P;
+      k.noise_mode = a.noise_mode;
+      k.log_space = c->cfg.params_log_space;
+      k.interleave = c->cfg.params_interleave;
+      k.dt = (float)c->cfg.dt;
+      k.chol_a = a.chol_a[0];
+      k.seed = a.seed;
+      k.ctr = a.ctr;
+      k.noise = a.noise;
+      k.theta = a.theta;
+      k.state = a.state;
+      k.params = a.params;
+      k.costs_sn = c->costs_stage;
+      k.costsT = c->costsT;
+      k.states_out = a.states_out;
+      const int nthr = c->nloc * c->S;
+      cartpole_rollout_kernel<<<(nthr + 255) / 256, 256, 0, c->stream>>>(k);
+      HIP_TRY(hipGetLastError());
+      o.want_states = false;
+      o.costs_in = c->costs_stage;
+      o.costs_own = true;
+      TRY(rollout_args(c, o, a, &nt, &lds));
+    }
+  }
   // Control-channel noise with acceleration control, drawn on the device, nothing but costs wanted: the regular kernel draws it inside
   // its own rollout loops (rollout.hpp, round 6: the packed pair path keeps its 40 instructions per step and sample and adds one
   // eight-normal Philox block per two steps of a pair) - no first pass.  Recorded draws (the goldens), stored states, velocity control:
@@ -1711,7 +1787,8 @@ static int launch_rollout(dust_ctx *c, const SampleOpts &o_in) {
       else DUST_PICK_ROLLOUT3(MODEL, false, false);                  \
     }                                                                \
   } while (0)
-  if (c->cfg.model == DUST_MODEL_PENDULUM) DUST_PICK_ROLLOUT(DUST_MODEL_PENDULUM);
+  // (the cart-pole family reaches this kernel in its injected-costs mode only: the one-action instance)
+  if (c->cfg.model == DUST_MODEL_PENDULUM || c->cfg.model == DUST_MODEL_CARTPOLE) DUST_PICK_ROLLOUT(DUST_MODEL_PENDULUM);
   else DUST_PICK_ROLLOUT(DUST_MODEL_PARTICLE);
 #undef DUST_PICK_ROLLOUT3
 #undef DUST_PICK_ROLLOUT
@@ -4175,6 +4252,25 @@ extern "C" int dust_set_skid_steer(dust_ctx *c, const dust_skid_config *g) {
     c->skid.goal[k] = g->goal[k];
     c->skid.w_state[k] = g->w_state[k];
     c->skid.w_term[k] = g->w_term[k];
+  }
+  if (c->graph_exec || c->graph_exec_alt) graph_drop(c);  // (the captured kernel arguments hold the old model)
+  return DUST_OK;
+}
+
+// CartPoleModel's seven parameters (cartpole.py:79-87) with the quadratic cost; validated as dust_set_skid_steer validates, and a column
+// named twice is refused
+extern "C" int dust_set_cartpole(dust_ctx *c, const dust_cartpole_config *g) {
+  if (!c || !g) return fail(DUST_ERR_INVALID, "null argument");
+  if (c->cfg.model != DUST_MODEL_CARTPOLE) return fail(DUST_ERR_STATE, "the context's model is not DUST_MODEL_CARTPOLE");
+  TRY(settle_pending(c));
+  DevParam par[CP_NPAR];
+  TRY(cartpole_params(g, c->P, par));
+  for (int q = 0; q < CP_NPAR; ++q) c->cart.par[q] = par[q];
+  c->cart.w_ctrl[0] = g->w_ctrl[0];
+  for (int k = 0; k < 4; ++k) {
+    c->cart.goal[k] = g->goal[k];
+    c->cart.w_state[k] = g->w_state[k];
+    c->cart.w_term[k] = g->w_term[k];
   }
   if (c->graph_exec || c->graph_exec_alt) graph_drop(c);  // (the captured kernel arguments hold the old model)
   return DUST_OK;

@@ -3,8 +3,8 @@
 // Replaces (reference file:line): MPF.phi / step / optimize / update_prior mpf.py:26-86, GaussianLikelihood.sample /
 // log_prob / condition likelihoods.py:30-64, default_kernel + squared_distance svgd.py:28-39, 92-99, and the autograd
 // calls at mpf.py:45 and mpf.py:50 (closed forms: GMM responsibilities; J^T (y - f(x)) / sigma_o^2 with the analytic
-// Jacobian of one model step w.r.t. the uncertain parameters).  Models: Pendulum, Particle (step_jacobian below) and SkidSteerRobot
-// (mpf_skid_score below, over skid.hpp's step).
+// Jacobian of one model step w.r.t. the uncertain parameters).  Models: Pendulum, Particle (step_jacobian below), SkidSteerRobot
+// (mpf_skid_score below, over skid.hpp's step) and CartPoleModel (mpf_cart_score, over cartpole.hpp's step).
 //
 // The problem is tiny (M_p <= 1024 particles x P <= 4 parameters, n_steps ~ 20 dependent SVGD steps), i.e. pure launch
 // latency on a GPU: ALL n_steps run inside ONE single-workgroup kernel with the particles, scores and squared norms in
@@ -23,7 +23,10 @@ struct MpfArgs {
   float prior_bwv[4];  // prior bandwidth per parameter dimension (equal after the first update_prior; MPF(bw=None) starts per-dimension)
   float bw, obs_std;
   float past_obs[4], past_action[2], obs[4];  // (Pendulum / Particle: up to four wide; the skid-steer model's five are in *skl)
-  const struct SkidLik *skl;  // DUST_MODEL_SKID_STEER: the likelihood's per-call constants, in device memory (below)
+  union {  // the likelihood's per-call constants, in device memory (below); one word for both: the argument block keeps its layout
+    const struct SkidLik *skl;  // DUST_MODEL_SKID_STEER
+    const struct CartLik *cpl;  // DUST_MODEL_CARTPOLE
+  };
   // control-channel noise of the one-step prediction (Particle(deterministic=False), particle.py:145-148 reached through
   // likelihoods.py:30-46): `acts` there is the bare action vector, so ONE d_a-vector is drawn per phi() call - i.e. per SVGD step -
   // and shared by all filter particles.  act_seq[step][2] = fl(past_action + fl(dyn_std * z_step)), prepared by the host, or nullptr
@@ -165,12 +168,103 @@ __global__ void mpf_skid_heading_kernel(SkidLik *k) {
   }
 }
 
+// The likelihood score J^T (y - f(x)) / sigma_o^2 of ONE particle under the cart-pole model (cartpole.py:126-172 through
+// likelihoods.py:30-49).  Prediction: cartpole_step in fp32, as the rollout kernel takes it.  Jacobian in fp64 from the closed forms;
+// a = the action after the clamp (it acts on the action, not on a parameter: no mask), s, c = sin, cos of the past angle, w = th_d,
+// sg = sign(x_d), mass = 2 m_c, pm = m_p L:
+//   fac = (a F + pm s w^2 - mu_c sg) / mass     pf = mu_p w / pm     num = g s - c fac - pf     den = L (4/3 - m_p c^2 / mass)
+//   tdd = num / den                             xdd = fac - pm tdd c / mass
+// Only the x_d' = x_d + xdd dt and th_d' = th_d + tdd dt rows depend on a parameter.  With A = dt e_xd, B = dt e_thd (e = y - f(x)),
+//   Q = (B - A c pm / mass) / den,  R = A - c Q,  T = tdd Q,  U = A (c / mass) tdd
+// the seven columns of J^T e are (from d tdd = (d num - tdd d den) / den and d xdd = d fac - (c / mass)(d pm tdd + pm d tdd) - pm tdd c d(1 / mass)):
+//   g: s Q      m_c: -(fac / m_c) R - T L m_p c^2 / (mass m_c) + U pm / m_c      m_p: (L s w^2 / mass) R + (pf / m_p) Q + T L c^2 / mass - U L
+//   L: (m_p s w^2 / mass) R + (pf / L) Q - T den / L - U m_p      mu_c: -(sg / mass) R      mu_p: -(w / pm) Q      F: (a / mass) R
+// and in log space column p is multiplied by p's value.  A sampled parameter is a particle column: `par_of_col` names the parameter of
+// each column, so P exponentials are taken, not seven.  What does not depend on the particle - the clamped action, s and c in both
+// precisions, w, w^2, sg, the observations - is prepared per call (mpf_cart_prepare on the host, mpf_cart_angle_kernel for the fp32
+// sine and cosine) and read from DEVICE MEMORY inside the model's branch, as SkidLik is.
+struct CartLik {
+  int par_of_col[4];         // parameter index (CP_*) carried by particle column p
+  float fix_f[CP_NPAR];      // the seven values as the fp32 scalars the step sees (a sampled one: replaced per particle)
+  float ac, dt;              // action after the clamp; (float)dt
+  float cs, sn;              // fast_cosf / fast_sinf of past theta (mpf_cart_angle_kernel)
+  float past[4], obs[4];     // past observation (the state the step starts from), new observation
+  int pm_py, pad;            // m_p and L are both fixed Python floats: their product is a Python float
+  double pm_d;
+  double fix_d[CP_NPAR];
+  double c, s, w, w2, sg, a, dtd;
+};
+template <int P>
+__device__ __forceinline__ void mpf_cart_score(const CartLik *k, const int log_space, const float *xp, const double inv_obs2, double *out) {
+  float vf[CP_NPAR];
+  double vd[CP_NPAR];
+#pragma unroll
+  for (int q = 0; q < CP_NPAR; ++q) {
+    vf[q] = k->fix_f[q];
+    vd[q] = k->fix_d[q];
+  }
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    const int which = k->par_of_col[p];
+    const float v = log_space ? expf(xp[p]) : xp[p];
+    // (a sampled parameter enters the Jacobian with the fp32 value the prediction was taken at - in log space expf's)
+#pragma unroll
+    for (int q = 0; q < CP_NPAR; ++q) {
+      vf[q] = q == which ? v : vf[q];
+      vd[q] = q == which ? (double)v : vd[q];
+    }
+  }
+  const CartCoef kf = cartpole_coef(vf, k->pm_py != 0, k->pm_d, k->dt);
+  float pred[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) pred[q] = k->past[q];
+  cartpole_step(pred, k->ac, kf, k->sn, k->cs);
+  const double dt = k->dtd, c = k->c, s = k->s, w = k->w, w2 = k->w2, sg = k->sg;
+  const double A = dt * ((double)k->obs[1] - (double)pred[1]), B = dt * ((double)k->obs[3] - (double)pred[3]);
+  const double g = vd[CP_G], mc = vd[CP_MC], mp = vd[CP_MP], L = vd[CP_LEN], muc = vd[CP_MUC], mup = vd[CP_MUP], F = vd[CP_FMAG];
+  const double imass = 1.0 / (mc + mc), pm = mp * L, ipm = 1.0 / pm;
+  const double fac = (k->a * F + pm * s * w2 - muc * sg) * imass, pf = mup * w * ipm;
+  const double den0 = 4.0 / 3 - mp * c * c * imass, den = L * den0, iden = 1.0 / den;
+  const double tdd = (g * s - c * fac - pf) * iden;
+  const double Q = (B - A * c * pm * imass) * iden, R = A - c * Q, T = tdd * Q, U = A * (c * imass) * tdd;
+  const double imc = 1.0 / mc;
+  double gj[CP_NPAR];
+  gj[CP_G] = s * Q;
+  gj[CP_MC] = (-(fac * imc) * R - T * L * mp * c * c * imass * imc + U * pm * imc);
+  gj[CP_MP] = (L * s * w2 * imass) * R + (pf / mp) * Q + T * L * c * c * imass - U * L;
+  gj[CP_LEN] = (mp * s * w2 * imass) * R + (pf / L) * Q - T * den0 - U * mp;
+  gj[CP_MUC] = -(sg * imass) * R;
+  gj[CP_MUP] = -(w * ipm) * Q;
+  gj[CP_FMAG] = (k->a * imass) * R;
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    const int which = k->par_of_col[p];
+    double gsel = 0.0, vsel = 1.0;
+#pragma unroll
+    for (int q = 0; q < CP_NPAR; ++q) {
+      gsel = q == which ? gj[q] : gsel;
+      vsel = q == which ? vd[q] : vsel;
+    }
+    out[p] = gsel * (log_space ? vsel : 1.0) * inv_obs2;
+  }
+}
+
+__global__ void mpf_cart_angle_kernel(CartLik *k) {
+  if (threadIdx.x == 0) {
+    k->cs = fast_cosf(k->past[2]);
+    k->sn = fast_sinf(k->past[2]);
+  }
+}
+
 // Lane = (particle i, slice r of the other particles): R = blockDim / Mpad slices share the O(M_p) loops of a particle and
 // their partial sums are combined in slice order through LDS (fixed order: reproducible).  No divisions or fp64
 // transcendentals inside the O(M_p^2) loops: reciprocals are hoisted (fp64, error 1e-16), weights use expf.
 // P is a template parameter: with a run-time P the per-lane arrays are indexed dynamically and live in scratch memory
 // (measured: 3 us per inner-loop iteration instead of ~50 ns).
-template <int P>
+// CART: the cart-pole instances.  The model's score is a template branch, not one more run-time branch: as a run-time branch it cost
+// every instance of the one-workgroup kernel spilled registers (P = 1: 4 -> 19) and the P = 4, KC = 16 poll kernel 32 bytes of scratch;
+// with it compiled out the Pendulum / Particle / skid-steer instances are the parent's (the register table).
+template <int P, bool CART = false>
 __global__ __launch_bounds__(1024) void mpf_optimize_kernel(const MpfArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int Mp = a.Mp;
@@ -232,7 +326,11 @@ __global__ __launch_bounds__(1024) void mpf_optimize_kernel(const MpfArgs a) {
       double s[4];
       _Pragma("unroll") for (int p = 0; p < P; ++p) s[p] = acc[p] / zs * inv_pbw2[p];
       // likelihood score (mpf.py:46-50, likelihoods.py:30-49)
-      if (a.dm.model == DUST_MODEL_SKID_STEER) {
+      if (CART) {
+        double gl[4];
+        mpf_cart_score<P>(a.cpl, a.log_space, xi, inv_obs2, gl);
+        _Pragma("unroll") for (int p = 0; p < P; ++p) sc[i * P + p] = (float)(s[p] + gl[p]);
+      } else if (a.dm.model == DUST_MODEL_SKID_STEER) {
         double gl[4];
         mpf_skid_score<P>(a.skl, a.log_space, xi, inv_obs2, gl);
         _Pragma("unroll") for (int p = 0; p < P; ++p) sc[i * P + p] = (float)(s[p] + gl[p]);
@@ -344,7 +442,7 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
   return v;
 }
 
-template <int P>
+template <int P, bool CART = false>
 __global__ __launch_bounds__(MPF_G_NT) void mpf_optimize_grid_kernel(const MpfGridArgs g) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const MpfArgs &a = g.a;
@@ -436,6 +534,10 @@ __global__ __launch_bounds__(MPF_G_NT) void mpf_optimize_grid_kernel(const MpfGr
   // It depends on the particle alone, so the term of step it + 1 is computed behind the particle store of step it, under the hop.
   double glik[4] = {0, 0, 0, 0};
   auto lik = [&](const float *xp, const int step) {
+    if (CART) {
+      mpf_cart_score<P>(a.cpl, a.log_space, xp, inv_obs2, glik);
+      return;
+    }
     const float pa[2] = {a.act_seq ? a.act_seq[2 * step] : a.past_action[0], a.act_seq ? a.act_seq[2 * step + 1] : a.past_action[1]};
     if (a.dm.model == DUST_MODEL_SKID_STEER) {
       mpf_skid_score<P>(a.skl, a.log_space, xp, inv_obs2, glik);
@@ -584,7 +686,7 @@ struct MpfPollArgs {
   int test;
 };
 
-template <int P, int KC>
+template <int P, int KC, bool CART = false>
 __global__ __launch_bounds__(MPF_G_NT) void mpf_optimize_poll_kernel(const MpfPollArgs g) {
   constexpr int NP = (P + 1) / 2, NX = NP + 1;
   __shared__ unsigned int sig[2];
@@ -708,6 +810,10 @@ __global__ __launch_bounds__(MPF_G_NT) void mpf_optimize_poll_kernel(const MpfPo
   const double inv_obs2 = 1.0 / ((double)a.obs_std * (double)a.obs_std);
   double glik[4] = {0, 0, 0, 0};
   auto lik = [&](const float *xp, const int step) {
+    if (CART) {
+      mpf_cart_score<P>(a.cpl, a.log_space, xp, inv_obs2, glik);
+      return;
+    }
     const float pa[2] = {a.act_seq ? a.act_seq[2 * step] : a.past_action[0], a.act_seq ? a.act_seq[2 * step + 1] : a.past_action[1]};
     if (a.dm.model == DUST_MODEL_SKID_STEER) {
       mpf_skid_score<P>(a.skl, a.log_space, xp, inv_obs2, glik);
@@ -969,6 +1075,9 @@ struct dust_mpf {
   dust::SkidModel skid;     // DUST_MODEL_SKID_STEER: parameters and wheel-speed bounds (dust_mpf_set_skid_steer)
   dust::SkidLik skl_host;   // ... the likelihood's per-call constants (mpf_skid_prepare) and their device copy
   dust::SkidLik *skl_dev;
+  dust::CartModel cart;     // DUST_MODEL_CARTPOLE: the seven parameters (dust_mpf_set_cartpole; its cost fields stay unused)
+  dust::CartLik cpl_host;   // ... the likelihood's per-call constants (mpf_cart_prepare) and their device copy
+  dust::CartLik *cpl_dev;
   // control-channel noise of the one-step prediction (model_cfg.ctrl_noise; particle.py:145-148 through likelihoods.py:30-46)
   std::vector<float> *cz;   // recorded draws [n][da] (dust_mpf_set_ctrl_noise), consumed one per SVGD step
   size_t cz_next;
@@ -1029,6 +1138,7 @@ extern "C" void dust_mpf_destroy(dust_mpf *m) {
   if (m->hpin) (void)hipHostFree(m->hpin);
   if (m->act_seq) (void)hipFree(m->act_seq);
   if (m->skl_dev) (void)hipFree(m->skl_dev);
+  if (m->cpl_dev) (void)hipFree(m->cpl_dev);
   if (m->stream) (void)hipStreamDestroy(m->stream);
   delete m->cz;
   delete m->rng;
@@ -1042,8 +1152,13 @@ extern "C" int dust_mpf_create(const dust_mpf_config *cfg, const float *init_par
   if (cfg->n_particles < 1 || cfg->n_particles > 1024) return fail(DUST_ERR_UNSUPPORTED, "MPF supports 1..1024 particles (one workgroup)");
   if (cfg->dim_p < 1 || cfg->dim_p > 4) return fail(DUST_ERR_INVALID, "dim_p must be 1..4");
   if (!(cfg->init_bw > 0.f)) return fail(DUST_ERR_INVALID, "init_bw must be > 0 (the host layer evaluates bw_silverman)");
-  if (cfg->model_cfg.model != DUST_MODEL_PENDULUM && cfg->model_cfg.model != DUST_MODEL_PARTICLE && cfg->model_cfg.model != DUST_MODEL_SKID_STEER)
-    return fail(DUST_ERR_UNSUPPORTED, "MPF's one-step prediction and its Jacobian exist for the Pendulum, Particle and SkidSteerRobot models only");
+  if (cfg->model_cfg.model != DUST_MODEL_PENDULUM && cfg->model_cfg.model != DUST_MODEL_PARTICLE && cfg->model_cfg.model != DUST_MODEL_SKID_STEER &&
+      cfg->model_cfg.model != DUST_MODEL_CARTPOLE)
+    return fail(DUST_ERR_UNSUPPORTED, "MPF's one-step prediction and its Jacobian exist for the Pendulum, Particle, SkidSteerRobot and CartPoleModel models only");
+  if (cfg->model_cfg.model == DUST_MODEL_CARTPOLE) {
+    if (cfg->dim_s != 4 || cfg->dim_a != 1) return fail(DUST_ERR_INVALID, "the cart-pole model has dim_s = 4, dim_a = 1");
+    if (!(cfg->model_cfg.dt > 0.0)) return fail(DUST_ERR_INVALID, "the cart-pole model needs model_cfg.dt > 0 (base.py:33)");
+  }
   if (cfg->model_cfg.model == DUST_MODEL_SKID_STEER) {
     if (cfg->dim_s != 5 || cfg->dim_a != 2) return fail(DUST_ERR_INVALID, "the skid-steer model has dim_s = 5, dim_a = 2");
     if (cfg->dim_p > 3) return fail(DUST_ERR_INVALID, "the skid-steer model has three parameters: dim_p must be 1..3");
@@ -1085,6 +1200,20 @@ extern "C" int dust_mpf_create(const dust_mpf_config *cfg, const float *init_par
       m->skid.hi[d] = 0.5f;
     }
   }
+  if (cfg->model_cfg.model == DUST_MODEL_CARTPOLE) cartpole_defaults(m->cart.par);  // cartpole.py:42-51, nothing sampled
+  return DUST_OK;
+}
+
+// The filter's CartPoleModel: the seven parameters (kind / column / value), validated as dust_set_cartpole does.  The cost fields of the
+// struct are not read.
+extern "C" int dust_mpf_set_cartpole(dust_mpf *m, const dust_cartpole_config *g) {
+  if (!m || !g) return fail(DUST_ERR_INVALID, "null argument");
+  if (m->cfg.model_cfg.model != DUST_MODEL_CARTPOLE) return fail(DUST_ERR_STATE, "the filter's model is not DUST_MODEL_CARTPOLE");
+  DevParam par[dust::CP_NPAR];
+  TRY(cartpole_params(g, m->P, par));
+  HIP_TRY(hipSetDevice(m->cfg.device));
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  for (int q = 0; q < dust::CP_NPAR; ++q) m->cart.par[q] = par[q];
   return DUST_OK;
 }
 
@@ -1118,6 +1247,14 @@ extern "C" int dust_mpf_set_skid_steer(dust_mpf *m, const dust_skid_config *g) {
 
 // A skid-steer filter can run once its sampled parameters name every particle column (dust_mpf_set_skid_steer)
 static int mpf_model_ready(const dust_mpf *m) {
+  if (m->cfg.model_cfg.model == DUST_MODEL_CARTPOLE) {  // (dust_mpf_set_cartpole has refused a column named twice)
+    unsigned seen = 0u;
+    for (const DevParam &p : m->cart.par)
+      if (p.kind == DUST_PARAM_SAMPLED) seen |= 1u << p.col;
+    if (seen == 0u) return fail(DUST_ERR_STATE, "cart-pole filter: no parameter is sampled - call dust_mpf_set_cartpole first");
+    if (seen != (1u << m->P) - 1u) return fail(DUST_ERR_STATE, "cart-pole filter: the sampled parameters do not cover the dim_p = %d particle columns", m->P);
+    return DUST_OK;
+  }
   if (m->cfg.model_cfg.model != DUST_MODEL_SKID_STEER) return DUST_OK;
   unsigned seen = 0u;
   const DevParam *ps[3] = {&m->skid.x_icr, &m->skid.wheel_radius, &m->skid.axial_distance};
@@ -1189,6 +1326,7 @@ extern "C" int dust_mpf_clone(const dust_mpf *src, dust_mpf **out) {
   memcpy(m->past_action, src->past_action, sizeof m->past_action);
   m->have_past = src->have_past;
   m->skid = src->skid;
+  m->cart = src->cart;
   if (memcmp(&src->opt, &m->opt, sizeof m->opt) != 0) {
     TRY(dust_mpf_set_optimizer_ex(m, &src->opt));
     const size_t nb = (size_t)src->Mp * src->P * sizeof(float);
@@ -1298,6 +1436,40 @@ static int mpf_skid_prepare(dust_mpf *m, const dust::SkidLik **dev) {
   return DUST_OK;
 }
 
+// ... and of the cart-pole likelihood (CartLik); the fp32 sine and cosine of the past angle are added on the device
+static int mpf_cart_prepare(dust_mpf *m, const dust::CartLik **dev) {
+  if (!m->cpl_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->cpl_dev), sizeof(dust::CartLik)));
+  dust::CartLik &k = m->cpl_host;
+  memset(&k, 0, sizeof k);
+  for (int q = 0; q < dust::CP_NPAR; ++q) {
+    const DevParam &p = m->cart.par[q];
+    k.fix_f[q] = (float)p.value;
+    k.fix_d[q] = p.kind == DUST_PARAM_TENSOR0D ? (double)(float)p.value : p.value;
+    if (p.kind == DUST_PARAM_SAMPLED) k.par_of_col[p.col] = q;
+  }
+  const DevParam &pmp = m->cart.par[dust::CP_MP], &pl = m->cart.par[dust::CP_LEN];
+  k.pm_py = pmp.kind == DUST_PARAM_PYFLOAT && pl.kind == DUST_PARAM_PYFLOAT;
+  k.pm_d = pmp.value * pl.value;
+  k.ac = clampf_host(m->past_action[0], -1.0f, 1.0f);
+  k.dt = (float)m->cfg.model_cfg.dt;
+  for (int q = 0; q < 4; ++q) {
+    k.past[q] = m->past_obs[q];
+    k.obs[q] = m->loc[q];
+  }
+  k.c = std::cos((double)m->past_obs[2]);
+  k.s = std::sin((double)m->past_obs[2]);
+  k.w = (double)m->past_obs[3];
+  k.w2 = k.w * k.w;
+  k.sg = m->past_obs[1] > 0.f ? 1.0 : (m->past_obs[1] < 0.f ? -1.0 : 0.0);
+  k.a = (double)k.ac;
+  k.dtd = m->cfg.model_cfg.dt;
+  HIP_TRY(hipMemcpyAsync(m->cpl_dev, &k, sizeof k, hipMemcpyHostToDevice, m->stream));
+  dust::mpf_cart_angle_kernel<<<1, 64, 0, m->stream>>>(m->cpl_dev);
+  HIP_TRY(hipGetLastError());
+  *dev = m->cpl_dev;
+  return DUST_OK;
+}
+
 static int mpf_launch(dust_mpf *m, float bw, float lr, int n_steps, float *gn_dev, float *phi_dev, bool optimise = true, bool grid = false,
                       const float *act_seq_dev = nullptr) {
   serve_cancel_device(m->cfg.device);  // (an armed control tick - closed-loop serving - would hold every CU until its plant state arrives)
@@ -1320,6 +1492,8 @@ static int mpf_launch(dust_mpf *m, float bw, float lr, int n_steps, float *gn_de
     a.obs[k] = m->loc[k];
   }
   if (m->cfg.model_cfg.model == DUST_MODEL_SKID_STEER) TRY(mpf_skid_prepare(m, &a.skl));
+  const bool cart = m->cfg.model_cfg.model == DUST_MODEL_CARTPOLE;
+  if (cart) TRY(mpf_cart_prepare(m, &a.cpl));
   a.past_action[0] = m->past_action[0];
   a.past_action[1] = m->past_action[1];
   a.act_seq = act_seq_dev;
@@ -1362,17 +1536,23 @@ static int mpf_launch(dust_mpf *m, float bw, float lr, int n_steps, float *gn_de
     g.tag0 = g.seq * 8192u;  // (n_steps <= 4096: 2 tags per step)
     g.test = m->env.grid_test;
     const int G = (m->Mp + MPF_G_WAVES - 1) / MPF_G_WAVES;
-#define DUST_LAUNCH_MPFP(PP)                                                                       \
-  do {                                                                                              \
-    if (m->Mp <= 256) mpf_optimize_poll_kernel<PP, 4><<<G, MPF_G_NT, 0, m->stream>>>(g);            \
-    else if (m->Mp <= 512) mpf_optimize_poll_kernel<PP, 8><<<G, MPF_G_NT, 0, m->stream>>>(g);       \
-    else mpf_optimize_poll_kernel<PP, 16><<<G, MPF_G_NT, 0, m->stream>>>(g);                        \
+#define DUST_LAUNCH_MPFP2(PP, CART)                                                                    \
+  do {                                                                                                  \
+    if (m->Mp <= 256) mpf_optimize_poll_kernel<PP, 4, CART><<<G, MPF_G_NT, 0, m->stream>>>(g);          \
+    else if (m->Mp <= 512) mpf_optimize_poll_kernel<PP, 8, CART><<<G, MPF_G_NT, 0, m->stream>>>(g);     \
+    else mpf_optimize_poll_kernel<PP, 16, CART><<<G, MPF_G_NT, 0, m->stream>>>(g);                      \
+  } while (0)
+#define DUST_LAUNCH_MPFP(PP)              \
+  do {                                    \
+    if (cart) DUST_LAUNCH_MPFP2(PP, true); \
+    else DUST_LAUNCH_MPFP2(PP, false);    \
   } while (0)
     if (m->P == 1) DUST_LAUNCH_MPFP(1);
     else if (m->P == 2) DUST_LAUNCH_MPFP(2);
     else if (m->P == 3) DUST_LAUNCH_MPFP(3);
     else DUST_LAUNCH_MPFP(4);
 #undef DUST_LAUNCH_MPFP
+#undef DUST_LAUNCH_MPFP2
     HIP_TRY(hipGetLastError());
     return DUST_OK;
   }
@@ -1400,10 +1580,16 @@ static int mpf_launch(dust_mpf *m, float bw, float lr, int n_steps, float *gn_de
     g.test = m->env.grid_test;
     const int G = (m->Mp + MPF_G_WAVES - 1) / MPF_G_WAVES;
     const size_t lds = sizeof(float) * ((size_t)2 * np + m->Mp + 8);
-    if (m->P == 1) mpf_optimize_grid_kernel<1><<<G, MPF_G_NT, lds, m->stream>>>(g);
-    else if (m->P == 2) mpf_optimize_grid_kernel<2><<<G, MPF_G_NT, lds, m->stream>>>(g);
-    else if (m->P == 3) mpf_optimize_grid_kernel<3><<<G, MPF_G_NT, lds, m->stream>>>(g);
-    else mpf_optimize_grid_kernel<4><<<G, MPF_G_NT, lds, m->stream>>>(g);
+#define DUST_LAUNCH_MPFG(PP)                                                                      \
+  do {                                                                                            \
+    if (cart) mpf_optimize_grid_kernel<PP, true><<<G, MPF_G_NT, lds, m->stream>>>(g);              \
+    else mpf_optimize_grid_kernel<PP><<<G, MPF_G_NT, lds, m->stream>>>(g);                        \
+  } while (0)
+    if (m->P == 1) DUST_LAUNCH_MPFG(1);
+    else if (m->P == 2) DUST_LAUNCH_MPFG(2);
+    else if (m->P == 3) DUST_LAUNCH_MPFG(3);
+    else DUST_LAUNCH_MPFG(4);
+#undef DUST_LAUNCH_MPFG
     HIP_TRY(hipGetLastError());
     return DUST_OK;
   }
@@ -1411,16 +1597,22 @@ static int mpf_launch(dust_mpf *m, float bw, float lr, int n_steps, float *gn_de
   int R = 1;
   while (mpad * R * 2 <= 1024) R *= 2;
   const size_t lds = sizeof(double) * (size_t)R * mpad * 2 * m->P + sizeof(float) * ((size_t)2 * m->Mp * m->P + m->Mp + 32);
-#define DUST_LAUNCH_MPF(PP)                                                                                                        \
+#define DUST_LAUNCH_MPF2(PP, CART)                                                                                                 \
   do {                                                                                                                              \
-    if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)mpf_optimize_kernel<PP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    mpf_optimize_kernel<PP><<<1, mpad * R, lds, m->stream>>>(a);                                                                    \
+    if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)mpf_optimize_kernel<PP, CART>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+    mpf_optimize_kernel<PP, CART><<<1, mpad * R, lds, m->stream>>>(a);                                                              \
+  } while (0)
+#define DUST_LAUNCH_MPF(PP)              \
+  do {                                   \
+    if (cart) DUST_LAUNCH_MPF2(PP, true); \
+    else DUST_LAUNCH_MPF2(PP, false);    \
   } while (0)
   if (m->P == 1) DUST_LAUNCH_MPF(1);
   else if (m->P == 2) DUST_LAUNCH_MPF(2);
   else if (m->P == 3) DUST_LAUNCH_MPF(3);
   else DUST_LAUNCH_MPF(4);
 #undef DUST_LAUNCH_MPF
+#undef DUST_LAUNCH_MPF2
   HIP_TRY(hipGetLastError());
   return DUST_OK;
 }
@@ -1609,6 +1801,15 @@ extern "C" int dust_dual_tick(dust_ctx *c, dust_mpf *m, const float *state, cons
     for (int k = 0; k < 3; ++k)
       if ((pc[k]->kind == DUST_PARAM_SAMPLED) != (pm[k]->kind == DUST_PARAM_SAMPLED) || (pc[k]->kind == DUST_PARAM_SAMPLED && pc[k]->col != pm[k]->col))
         return fail(DUST_ERR_INVALID, "controller and filter name different uncertain skid-steer parameters (or in another column order)");
+  }
+  if ((c->cfg.model == DUST_MODEL_CARTPOLE) != (m->cfg.model_cfg.model == DUST_MODEL_CARTPOLE))
+    return fail(DUST_ERR_INVALID, "a cart-pole controller takes a cart-pole filter, and no other");
+  if (c->cfg.model == DUST_MODEL_CARTPOLE) {
+    for (int k = 0; k < dust::CP_NPAR; ++k) {
+      const DevParam &pc = c->cart.par[k], &pm = m->cart.par[k];
+      if ((pc.kind == DUST_PARAM_SAMPLED) != (pm.kind == DUST_PARAM_SAMPLED) || (pc.kind == DUST_PARAM_SAMPLED && pc.col != pm.col))
+        return fail(DUST_ERR_INVALID, "controller and filter name different uncertain cart-pole parameters (or in another column order)");
+    }
   }
   if (comm_active(c)) return fail(DUST_ERR_UNSUPPORTED, "the dual tick runs on an unsharded controller (the filter is replicated: tick it per rank)");
   HIP_TRY(hipSetDevice(c->cfg.device));

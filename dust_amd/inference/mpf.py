@@ -74,6 +74,9 @@ class MPF:
         if model.family == "skid_steer":  # params_dict, uncertain_params (above), the action space's bounds and dt describe the model
             kw.update({k: float(model.params_dict[k]) for k in ("x_icr", "wheel_radius", "axial_distance")})
             kw.update(min_a=tuple(float(v) for v in model.action_space.low), max_a=tuple(float(v) for v in model.action_space.high))
+        if model.family == "cartpole":  # the seven parameters of params_dict (cartpole.py:79-87) and dt describe the model
+            model.check_device_params()
+            kw.update({k: float(model.params_dict[k]) for k in ("f_mag", "mass_cart", "mass_pole", "mu_c", "mu_p")})
         if model.family == "particle":
             kw.update(max_speed=float(model._max_speed), max_accel=float(model._max_acc), can_crash=bool(model.can_crash),
                       with_obstacle=bool(model.with_obstacle), cell_size=float(model.map_cell_size or 0.1),

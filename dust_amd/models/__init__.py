@@ -186,3 +186,61 @@ class SkidSteerRobot(BaseModel):
         new_y = y + forward * torch.sin(theta) + lateral * torch.cos(theta)
         new_theta = theta + angular * self.dt
         return torch.cat([new_x, new_y, new_theta, linear.expand_as(x), angular.expand_as(x)], dim=1)
+
+
+class CartPoleModel(BaseModel):
+    """dust/models/cartpole.py:8-172 (Barto, Sutton & Anderson's cart-pole with a continuous push).  State (x, x_d, theta, theta_d),
+    one action, clamped to +-1 inside the step and scaled by `f_mag`.  The reference's `step` reads a name-mangled attribute its base
+    class never set (cartpole.py:151/156); with that attribute supplied it runs, and `step` below repeats its torch operations in the
+    same order - `mass = m_c + m_c` (cartpole.py:161) included.  Batched rollouts run on the device (csrc/cartpole.hpp) with
+    `dust_amd.costs.QuadraticCost` as the cost family; `step` is the plant-side host form."""
+
+    family = "cartpole"
+    PARAM_NAMES = ("g", "mass_cart", "mass_pole", "length", "mu_c", "mu_p", "f_mag")  # params_dict order, cartpole.py:79-87
+
+    def __init__(self, g=9.8, f_mag=10.0, mass_cart=1.0, mass_pole=0.1, length=1.0, mu_c=0.5e-3, mu_p=2e-6, **kwargs):
+        given = dict(g=g, f_mag=f_mag, mass_cart=mass_cart, mass_pole=mass_pole, length=length, mu_c=mu_c, mu_p=mu_p)
+        super().__init__(params_dict={k: given[k] for k in self.PARAM_NAMES}, **kwargs)
+        keys = self.uncertain_params
+        if keys is not None:
+            unknown = [k for k in keys if k not in self.PARAM_NAMES]
+            if unknown:
+                raise ValueError("CartPoleModel has no parameter %r (it has %s)" % (unknown[0], ", ".join(self.PARAM_NAMES)))
+            if len(set(keys)) != len(keys):
+                raise ValueError("uncertain_params names a parameter twice: %r" % (tuple(keys),))
+        # the reference's spaces (cartpole.py:90-106): the action in [-1, 1]; the cart within +-4.8 m and the pole within +-24 degrees -
+        # twice the 2.4 m and 12 degrees at which the classic task ends an episode - both velocities unbounded
+        inf = float("inf")
+        bounds = torch.tensor([4.8, inf, math.radians(24.0), inf])
+        self._observation_space = Box(dim=4, low=-bounds, high=bounds, dtype=torch.float)
+        self._action_space = Box(dim=1, low=-1.0, high=1.0, dtype=torch.float)
+
+    observation_space = property(lambda self: self._observation_space)
+    action_space = property(lambda self: self._action_space)
+
+    def check_device_params(self):
+        """The device kernels take up to four sampled columns (dim_p <= 4); `step` on the host takes any number."""
+        keys = self.uncertain_params or ()
+        if len(keys) > 4:
+            raise ValueError("at most 4 uncertain parameters run on the device (dim_p <= 4), got %d" % len(keys))
+
+    def step(self, states, actions, params_dict=None):
+        """cartpole.py:148-172 in the notation of csrc/cartpole.hpp (u, cf, pf, fac, num, den), one torch operation per reference
+        operation in the reference's order; sine and cosine of the angle are taken once (the reference takes them two and three times
+        on the same argument)."""
+        p = self._merged(params_dict)
+        g, m_c, m_p, length, mu_c, mu_p, f_mag = (p[k] for k in self.PARAM_NAMES)
+        state = torch.as_tensor(states, dtype=torch.float)
+        _, x_d, th, th_d = state.chunk(4, dim=1)
+        sn, cs = th.sin(), th.cos()
+        u = torch.as_tensor(actions, dtype=torch.float).clamp(-1, 1) * f_mag
+        mass = m_c + m_c  # (sic, cartpole.py:161)
+        pm = m_p * length
+        cf = mu_c * x_d.sign()
+        pf = (mu_p * th_d) / pm
+        fac = ((u + (pm * sn) * th_d ** 2) - cf) / mass
+        num = (g * sn - cs * fac) - pf
+        den = length * (4.0 / 3 - (m_p * cs ** 2) / mass)
+        th_dd = num / den
+        x_dd = fac - ((pm * th_dd) * cs) / mass
+        return state + torch.cat((x_d, x_dd, th_d, th_dd), dim=1) * self.dt

@@ -38,7 +38,7 @@ enum dust_status {
   DUST_ERR_STATE = 5 /* call order (e.g. phi before any likelihood sample) */
 };
 
-enum dust_model { DUST_MODEL_PENDULUM = 0, DUST_MODEL_PARTICLE = 1, DUST_MODEL_SKID_STEER = 2 };
+enum dust_model { DUST_MODEL_PENDULUM = 0, DUST_MODEL_PARTICLE = 1, DUST_MODEL_SKID_STEER = 2, DUST_MODEL_CARTPOLE = 3 };
 /* cost families: pendulum demo cost (demo/pendulum_example.py:21-28), Particle.default_*_cost (particle.py:170-225) */
 enum dust_cost { DUST_COST_PENDULUM_QUADCOS = 0, DUST_COST_PARTICLE_DEFAULT = 1, DUST_COST_QUADRATIC = 2 };
 /* K1: gpytorch RBFKernel semantics, lengthscale ln 2 (svmpc.py:76-83); K2: iid_mp(RBF) per-dimension median bandwidth
@@ -147,6 +147,20 @@ typedef struct dust_skid_config {
   float goal[5], w_state[5], w_term[5], w_ctrl[2];
 } dust_skid_config;
 
+/* CartPoleModel (dust/models/cartpole.py:42-106, step :126-172; model = DUST_MODEL_CARTPOLE, dim_s = 4: x, x_d, theta, theta_d; dim_a = 1:
+ * the push, clamped to +-1 INSIDE the step, cartpole.py:159) with the quadratic cost family DUST_COST_QUADRATIC of dust_skid_config
+ * (4 state entries, 1 control weight).  The reference's step reads a name-mangled attribute the base class never set
+ * (cartpole.py:151/156); with that attribute supplied on the instance it runs, and the kernels follow it operation by operation -
+ * `mass = m_c + m_c` (cartpole.py:161) included.  dust_create gives the constructor's defaults (g 9.8, f_mag 10, mass_cart 1,
+ * mass_pole 0.1, length 1, mu_c 5e-4, mu_p 2e-6), unit state weights and no goal; dust_set_cartpole replaces them.  Any of the seven
+ * parameters may be sampled (kind DUST_PARAM_SAMPLED): it names a column of the `params` rows, in the order of `uncertain_params`
+ * (base.py params_to_dict), dim_p <= 4 of them at once.  The dynamics filter takes the same struct (dust_mpf_set_cartpole: the cost
+ * fields are ignored there). */
+typedef struct dust_cartpole_config {
+  dust_param g, f_mag, mass_cart, mass_pole, length, mu_c, mu_p; /* CartPoleModel.__init__ order, cartpole.py:42-51 */
+  float goal[4], w_state[4], w_term[4], w_ctrl[1];
+} dust_cartpole_config;
+
 /* A torch.optim optimiser with its options (dust_set_optimizer, dust_mpf_set_optimizer_ex).  Each step follows the installed torch's
  * single-tensor CPU function operation by operation - torch/optim/sgd.py _single_tensor_sgd, adam.py _single_tensor_adam (AdamW
  * included), rmsprop.py _single_tensor_rmsprop, adagrad.py _single_tensor_adagrad - on grad = -phi: Python-float scalars are formed
@@ -194,6 +208,10 @@ int dust_set_model_param(dust_ctx *ctx, const char *name, double value, int kind
  * of the mean.  NULL switches back to the mean over sampled parameters. */
 int dust_set_param_weights(dust_ctx *ctx, const float *w);
 int dust_set_skid_steer(dust_ctx *ctx, const dust_skid_config *cfg);
+/* CartPoleModel(g, f_mag, ...) cartpole.py:42-88 and its quadratic cost.  A sampled column outside dim_p, or named by two parameters:
+ * DUST_ERR_INVALID.  The family runs the launch-per-iteration path (pass 1: cartpole.hpp, pass 2: the regular kernel on injected
+ * costs); binary16 storage and sigma-point weights return DUST_ERR_UNSUPPORTED.  dust_clone copies the model. */
+int dust_set_cartpole(dust_ctx *ctx, const dust_cartpole_config *cfg);
 /* Recorded control-channel noise for the NEXT rollouts of a Particle(deterministic=False) context (particle.py:145-148): z holds n_sets
  * tensors [H][M*S*N][da] of standard-normal draws in the reference's own order - one `torch.randn_like(acts)` per model.step call of
  * MultiDISCO._rollout (disco.py:193-200), rollout r = (m*S + s)*N + n, N = n_policies (all shards).  Every rollout launch that follows
@@ -382,8 +400,9 @@ typedef struct dust_mpf_config {
   float init_bw;       /* MPF(bw=): bandwidth of the initial prior; <= 0: bw_silverman of the particles (svgd.py:55-81) */
   dust_config model_cfg; /* only the model fields are read */
 } dust_mpf_config;
-/* Models: DUST_MODEL_PENDULUM, DUST_MODEL_PARTICLE (acceleration control) and DUST_MODEL_SKID_STEER (dim_s = 5, dim_a = 2, dim_p = 1..3;
- * model_cfg.dt is SkidSteerRobot's delta_t; model_cfg.ctrl_noise stays a Particle field). */
+/* Models: DUST_MODEL_PENDULUM, DUST_MODEL_PARTICLE (acceleration control), DUST_MODEL_SKID_STEER (dim_s = 5, dim_a = 2, dim_p = 1..3;
+ * model_cfg.dt is SkidSteerRobot's delta_t; model_cfg.ctrl_noise stays a Particle field) and DUST_MODEL_CARTPOLE (dim_s = 4, dim_a = 1,
+ * dim_p = 1..4; dust_mpf_set_cartpole). */
 int dust_mpf_create(const dust_mpf_config *cfg, const float *init_particles, const float *initial_obs, dust_mpf **out);
 /* The filter's SkidSteerRobot (skid_steer_robot.py:19-52): the three parameters with kind / column / value - a sampled one names its
  * particle column, in any order - and the wheel-speed bounds; the cost fields of the struct are ignored.  Validated as
@@ -392,6 +411,13 @@ int dust_mpf_create(const dust_mpf_config *cfg, const float *init_particles, con
  * columns do not cover dim_p.  dust_mpf_clone copies the model.  dust_dual_tick takes a skid-steer controller and filter that name the
  * same uncertain parameters in the same columns. */
 int dust_mpf_set_skid_steer(dust_mpf *mpf, const dust_skid_config *cfg);
+/* The filter's CartPoleModel (cartpole.py:42-88; likelihoods.py:30-46 steps every particle once from the past observation): the seven
+ * parameters with kind / column / value; the cost fields are ignored.  Validated as dust_set_cartpole validates.  Until the call the
+ * constructor's defaults hold with nothing sampled, and dust_mpf_phi / dust_mpf_optimize return DUST_ERR_STATE; they do so as well
+ * while the sampled columns do not cover dim_p.  model_cfg.dt is the model's dt (0.05 in the reference, base.py); model_cfg.ctrl_noise
+ * stays a Particle field.  dust_mpf_clone copies the model.  dust_dual_tick takes a cart-pole controller and filter that name the same
+ * uncertain parameters in the same columns. */
+int dust_mpf_set_cartpole(dust_mpf *mpf, const dust_cartpole_config *cfg);
 int dust_mpf_clone(const dust_mpf *src, dust_mpf **out);
 /* MPF(optimizer_class=, **opt_args) svgd.py:108-122, mpf.py:24: DUST_OPT_SGD (default here, the demos' choice) or DUST_OPT_ADAM (the
  * reference's class default; betas / eps as torch.optim.Adam).  The optimiser state starts at zero and persists across
