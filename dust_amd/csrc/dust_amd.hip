@@ -1453,65 +1453,195 @@ static int rollout_args(dust_ctx *c, const SampleOpts &o, RolloutArgs &a, int *n
   return DUST_OK;
 }
 
-// The whole-line stored-states form (rollout_states.hpp): Particle, fp32 in and out, 8-particle groups that are whole lines.
-static bool states_whole_lines(const dust_ctx *c, const SampleOpts &o, const RolloutArgs &a, int *gw_out, size_t *lds_out) {
-  if (c->env.states_form == 0) return false;  // development switch DUST_STATES_FORM: 0 keeps the per-particle staging kernel
-  if (c->cfg.model != DUST_MODEL_PARTICLE || !a.states_out || a.costs_in || a.mw || a.tile_scratch) return false;
-  if (o.store_f16 || a.noise_f16 || a.noise_mode == NOISE_PHILOX || !a.noise || a.a_reg != 0.0f || a.dm.interleave) return false;
-  if (((c->H + 1) & 1) == 0 || c->H + 1 < 9) return false;
-  if ((c->N % 8) || (c->n0 % 8) || (c->nloc % 8)) return false;
-  if (a.dm.with_obstacle && a.grid_words == 0) return false;
-  int gw = 4;
-  while (gw > 1 && c->M % (2 * gw)) gw >>= 1;
-  if (c->M % (2 * gw)) return false;
-  const size_t lds = particle_states_lds_bytes(c->D, c->M, a.grid_words, gw);
-  if (lds > 80 * 1024) return false;
-  *gw_out = gw;
-  *lds_out = lds;
-  return true;
+// A rollout launch may begin with a FIRST PASS: a kernel of another header that rolls out and writes costs (+ states) to costs_stage,
+// after which the regular kernel runs in its injected-costs mode - softmax, weights, score.  At most one runs: first_pass() names it,
+// with its launch numbers.
+enum FirstPassKind { FP_NONE = 0, FP_SKID, FP_CART, FP_PARTGEN, FP_PART_LINES, FP_PART_LINES_F16, FP_PEND_LINES, FP_PEND_LINES_F16 };
+struct FirstPass {
+  int kind = FP_NONE;
+  int gw = 0;      // Particle whole-line forms: waves per workgroup; particle_general.hpp: lanes per (sample, policy) pair (its mc)
+  size_t lds = 0;  // dynamic LDS bytes
+  int blocks = 0;
+};
+
+// Control-channel noise with acceleration control, drawn on the device, nothing but costs wanted: the regular kernel draws it inside
+// its own rollout loops (rollout.hpp, round 6: the packed pair path keeps its 40 instructions per step and sample and adds one
+// eight-normal Philox block per two steps of a pair) - no first pass.  Recorded draws (the goldens), stored states, velocity control:
+// particle_general.hpp.
+static bool ctrl_noise_inline(const dust_ctx *c, const SampleOpts &o, const RolloutArgs &a) {
+  return particle_general(c) && o.costs_in == nullptr && c->cfg.control_type != DUST_CONTROL_VELOCITY && !o.want_states && !a.mw &&
+         !(c->cz_dev && c->cz_next < c->cz_sets) && c->env.noise_general <= 0;
 }
 
-// ... its binary16 form (DUST_STORE_F16): 8-byte states, 16-particle groups (rollout_states.hpp particle_states_f16_kernel)
-static bool states_whole_lines_f16(const dust_ctx *c, const SampleOpts &o, const RolloutArgs &a, int *gw_out, size_t *lds_out) {
-  if (c->env.states_form == 0) return false;
-  if (c->cfg.model != DUST_MODEL_PARTICLE || !a.states_out || a.costs_in || a.mw || a.tile_scratch) return false;
-  if (!o.store_f16 || a.noise_f16 || a.noise_mode == NOISE_PHILOX || !a.noise || a.a_reg != 0.0f || a.dm.interleave) return false;
-  if (((c->H + 1) & 1) == 0 || c->H < 16) return false;
-  if ((c->N % 16) || (c->n0 % 16) || (c->nloc % 16)) return false;
-  if (a.dm.with_obstacle && a.grid_words == 0) return false;
-  int gw = 4;
-  while (gw > 1 && c->M % (2 * gw)) gw >>= 1;
-  if (c->M % (2 * gw)) return false;
-  const size_t lds = particle_states_f16_lds_bytes(c->D, c->M, a.grid_words, gw);
-  if (lds > 80 * 1024) return false;
-  *gw_out = gw;
-  *lds_out = lds;
-  return true;
+static FirstPass first_pass(const dust_ctx *c, const SampleOpts &o, const RolloutArgs &a) {
+  FirstPass fp;
+  if (a.costs_in) return fp;  // the costs are there already
+  const int model = c->cfg.model, nthr = c->nloc * c->S;
+  if (model == DUST_MODEL_SKID_STEER || model == DUST_MODEL_CARTPOLE) {  // skid.hpp / cartpole.hpp
+    fp.kind = model == DUST_MODEL_SKID_STEER ? FP_SKID : FP_CART;
+    fp.blocks = (nthr + 255) / 256;
+    return fp;
+  }
+  if (particle_general(c)) {  // particle_general.hpp: rollouts with control noise / velocity control
+    if (ctrl_noise_inline(c, o, a)) return fp;
+    fp.kind = FP_PARTGEN;
+    fp.gw = c->M >= 8 ? 8 : (c->M >= 4 ? 4 : (c->M >= 2 ? 2 : 1));
+    const int pg_gw = (a.dm.with_obstacle && a.dm.grid_bits) ? (a.dm.nx * a.dm.ny + 31) / 32 : 0;
+    fp.lds = particle_general_lds_bytes(c->D, pg_gw, fp.gw);
+    const int pg_rows = PARTGEN_NT / fp.gw;
+    fp.blocks = (nthr + pg_rows - 1) / pg_rows;
+    return fp;
+  }
+  // The whole-line stored-states forms (rollout_states.hpp): groups of adjacent particles whose rows are whole 128-byte lines
+  if (c->env.states_form == 0) return fp;  // development switch DUST_STATES_FORM: 0 keeps the per-particle staging kernel
+  if ((model != DUST_MODEL_PARTICLE && model != DUST_MODEL_PENDULUM) || !a.states_out || a.mw || a.tile_scratch) return fp;
+  if (a.noise_f16 || a.noise_mode == NOISE_PHILOX || !a.noise || a.a_reg != 0.0f || a.dm.interleave) return fp;
+  const bool part = model == DUST_MODEL_PARTICLE, f16 = o.store_f16;
+  static const struct {
+    int kind, group, per_wg;  // particles per group, samples per workgroup
+    bool odd_rows;            // H + 1 must be odd
+    int min_h;
+  } forms[2][2] = {
+      {{FP_PART_LINES, 8, 8, true, 8},         // Particle, fp32 in and out: 8-particle groups (H + 1 >= 9)
+       {FP_PART_LINES_F16, 16, 4, true, 16}},  // ... its binary16 form (DUST_STORE_F16): 8-byte states, 16-particle groups
+      {{FP_PEND_LINES, 16, 16, true, 16},      // ... its Pendulum counterpart: 16-particle groups of 8 (H+1)-byte rows
+       {FP_PEND_LINES_F16, 32, 8, false, 0}},  // ... and the binary16 form of the Pendulum states: 32-particle groups of 4 (H+1)-byte rows
+  };
+  const auto &f = forms[part ? 0 : 1][f16 ? 1 : 0];
+  if ((f.odd_rows && ((c->H + 1) & 1) == 0) || c->H < f.min_h) return fp;
+  if ((c->N % f.group) || (c->n0 % f.group) || (c->nloc % f.group)) return fp;
+  int gw = 0;
+  size_t lds;
+  if (part) {
+    if (a.dm.with_obstacle && a.grid_words == 0) return fp;
+    gw = 4;
+    while (gw > 1 && c->M % (2 * gw)) gw >>= 1;
+    if (c->M % (2 * gw)) return fp;
+    lds = f16 ? particle_states_f16_lds_bytes(c->D, c->M, a.grid_words, gw) : particle_states_lds_bytes(c->D, c->M, a.grid_words, gw);
+  } else {
+    lds = f16 ? pendulum_states_f16_lds_bytes(c->D, c->M, c->H) : pendulum_states_lds_bytes(c->D, c->M);
+  }
+  if (lds > 80 * 1024) return fp;
+  fp.kind = f.kind;
+  fp.gw = gw;
+  fp.lds = lds;
+  fp.blocks = (c->nloc / f.group) * ((c->S + f.per_wg - 1) / f.per_wg);
+  return fp;
 }
 
-// ... and its Pendulum counterpart: 16-particle groups of 8 (H+1)-byte rows
-static bool states_whole_lines_pend(const dust_ctx *c, const SampleOpts &o, const RolloutArgs &a, size_t *lds_out) {
-  if (c->env.states_form == 0) return false;
-  if (c->cfg.model != DUST_MODEL_PENDULUM || !a.states_out || a.costs_in || a.mw || a.tile_scratch) return false;
-  if (o.store_f16 || a.noise_f16 || a.noise_mode == NOISE_PHILOX || !a.noise || a.a_reg != 0.0f || a.dm.interleave) return false;
-  if (((c->H + 1) & 1) == 0 || c->H < 16) return false;
-  if ((c->N % 16) || (c->n0 % 16) || (c->nloc % 16)) return false;
-  const size_t lds = pendulum_states_lds_bytes(c->D, c->M);
-  if (lds > 80 * 1024) return false;
-  *lds_out = lds;
-  return true;
+// what SkidArgs, CartArgs and PartGenArgs have in common
+template <class Args>
+static void first_pass_args(const dust_ctx *c, const RolloutArgs &a, Args &k) {
+  memset(&k, 0, sizeof k);
+  k.N_total = c->N;
+  k.n0 = c->n0;
+  k.n_local = c->nloc;
+  k.S = c->S;
+  k.M = c->M;
+  k.H = c->H;
+  k.D = c->D;
+  k.noise_mode = a.noise_mode;
+  k.seed = a.seed;
+  k.ctr = a.ctr;
+  k.noise = a.noise;
+  k.theta = a.theta;
+  k.state = a.state;
+  k.params = a.params;
+  k.costs_sn = c->costs_stage;
+  k.costsT = c->costsT;
+  k.states_out = a.states_out;
+}
+// ... and the two families with parameter structs of their own
+template <class Args>
+static void first_pass_param_args(const dust_ctx *c, Args &k) {
+  k.P = c->P;
+  k.log_space = c->cfg.params_log_space;
+  k.interleave = c->cfg.params_interleave;
+  k.dt = (float)c->cfg.dt;
 }
 
-// ... and the binary16 form of the Pendulum states (DUST_STORE_F16): 32-particle groups of 4 (H+1)-byte rows
-static bool states_whole_lines_pend_f16(const dust_ctx *c, const SampleOpts &o, const RolloutArgs &a, size_t *lds_out) {
-  if (c->env.states_form == 0) return false;
-  if (c->cfg.model != DUST_MODEL_PENDULUM || !a.states_out || a.costs_in || a.mw || a.tile_scratch) return false;
-  if (!o.store_f16 || a.noise_f16 || a.noise_mode == NOISE_PHILOX || !a.noise || a.a_reg != 0.0f || a.dm.interleave) return false;
-  if ((c->N % 32) || (c->n0 % 32) || (c->nloc % 32)) return false;
-  const size_t lds = pendulum_states_f16_lds_bytes(c->D, c->M, c->H);
-  if (lds > 80 * 1024) return false;
-  *lds_out = lds;
-  return true;
+// A whole-line first pass: the fast instance, then the general one, in which only the workgroups the fast kernel flagged (non-finite
+// operands) do any work.  `mid`: the kernel's arguments between costs_sn and wg_flags.
+template <class K, class... Mid>
+static int launch_whole_lines(dust_ctx *c, const FirstPass &fp, const RolloutArgs &a, int threads, K fast, K general, Mid... mid) {
+  TRY(ensure(&c->wg_flags, &c->wg_flags_cap, (size_t)fp.blocks));
+  unsigned int *fl = reinterpret_cast<unsigned int *>(c->wg_flags);
+  for (K k : {fast, general}) {
+    if (fp.lds > 64 * 1024 && !c->capturing) HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp.lds));
+    k<<<fp.blocks, threads, fp.lds, c->stream>>>(a, c->costs_stage, mid..., fl);
+  }
+  HIP_TRY(hipGetLastError());
+  return DUST_OK;
+}
+
+static int launch_first_pass(dust_ctx *c, const FirstPass &fp, const RolloutArgs &a) {
+  Prof ps(c, DUST_K_ROLLOUT_STATES);
+  switch (fp.kind) {
+    case FP_SKID: {
+      SkidArgs k;
+      first_pass_args(c, a, k);
+      first_pass_param_args(c, k);
+      k.sk = c->skid;
+      k.chol_a[0] = a.chol_a[0];
+      k.chol_a[1] = a.chol_a[1];
+      k.chol_off = a.chol_off;
+      skid_rollout_kernel<<<fp.blocks, 256, 0, c->stream>>>(k);
+      break;
+    }
+    case FP_CART: {
+      CartArgs k;
+      first_pass_args(c, a, k);
+      first_pass_param_args(c, k);
+      k.cp = c->cart;
+      k.chol_a = a.chol_a[0];
+      cartpole_rollout_kernel<<<fp.blocks, 256, 0, c->stream>>>(k);
+      break;
+    }
+    case FP_PARTGEN: {
+      PartGenArgs k;
+      first_pass_args(c, a, k);
+      k.dm = a.dm;
+      k.noise_f16 = a.noise_f16;
+      k.store_f16 = a.store_f16;
+      k.velocity = c->cfg.control_type == DUST_CONTROL_VELOCITY;
+      k.ctrl_noise = c->cfg.ctrl_noise && (c->cfg.dyn_std[0] != 0.f || c->cfg.dyn_std[1] != 0.f);
+      for (int d = 0; d < 2; ++d) {
+        k.dyn_std[d] = c->cfg.dyn_std[d];
+        k.chol_a[d] = a.chol_a[d];
+        k.a_pre[d] = a.a_pre[d];
+      }
+      k.a_reg = a.a_reg;
+      k.chol_off = a.chol_off;
+      k.a_pre_off = a.a_pre_off;
+      if (k.ctrl_noise && c->cz_dev && c->cz_next < c->cz_sets) {  // recorded draws: one set per rollout launch
+        if (c->capturing) return fail(DUST_ERR_STATE, "recorded control noise cannot be replayed from a captured graph");
+        k.cz = c->cz_dev + (size_t)c->cz_next * c->H * c->M * c->S * c->N * 2;
+        c->cz_next++;
+      }
+      k.a_seq = a.a_seq;
+      k.a_mat = a.a_mat;
+      k.mc = fp.gw;
+      if (fp.lds > 160 * 1024) return fail(DUST_ERR_UNSUPPORTED, "occupancy grid of %d x %d cells: the control-noise / velocity-control rollouts keep it in LDS", k.dm.nx, k.dm.ny);
+      if (fp.lds > 64 * 1024 && !c->capturing)
+        HIP_TRY(hipFuncSetAttribute((const void *)particle_general_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp.lds));
+      particle_general_kernel<<<fp.blocks, PARTGEN_NT, fp.lds, c->stream>>>(k);
+      break;
+    }
+    case FP_PART_LINES: {
+      const auto fast = !a.dm.with_obstacle ? particle_states_kernel<SP_FAST_FREE>
+                                            : (a.dm.can_crash ? particle_states_kernel<SP_FAST_CRASH> : particle_states_kernel<SP_FAST_OBST>);
+      return launch_whole_lines(c, fp, a, 64 * fp.gw, fast, particle_states_kernel<SP_GENERAL>, fp.gw);
+    }
+    case FP_PART_LINES_F16: {
+      const auto fast = !a.dm.with_obstacle ? particle_states_f16_kernel<SP_FAST_FREE>
+                                            : (a.dm.can_crash ? particle_states_f16_kernel<SP_FAST_CRASH> : particle_states_f16_kernel<SP_FAST_OBST>);
+      return launch_whole_lines(c, fp, a, 64 * fp.gw, fast, particle_states_f16_kernel<SP_GENERAL>, fp.gw);
+    }
+    case FP_PEND_LINES: return launch_whole_lines(c, fp, a, 256, pendulum_states_kernel<false>, pendulum_states_kernel<true>);
+    case FP_PEND_LINES_F16: return launch_whole_lines(c, fp, a, 256, pendulum_states_f16_kernel<false>, pendulum_states_f16_kernel<true>);
+  }
+  HIP_TRY(hipGetLastError());
+  return DUST_OK;
 }
 
 static int launch_rollout(dust_ctx *c, const SampleOpts &o_in) {
@@ -1520,243 +1650,25 @@ static int launch_rollout(dust_ctx *c, const SampleOpts &o_in) {
   int nt;
   size_t lds;
   TRY(rollout_args(c, o, a, &nt, &lds));
-  if (c->cfg.model == DUST_MODEL_SKID_STEER) {
-    // pass 1 (skid.hpp): rollouts + costs (+ states); pass 2 (below): the regular kernel in its injected-costs mode
-    if (a.noise_f16 || o.store_f16) return fail(DUST_ERR_UNSUPPORTED, "binary16 storage is not implemented for the skid-steer family");
-    if (a.mw) return fail(DUST_ERR_UNSUPPORTED, "sigma-point weights are not implemented for the skid-steer family");
-    if (o.costs_in == nullptr) {
-      Prof ps(c, DUST_K_ROLLOUT_STATES);
-      SkidArgs k;
-      memset(&k, 0, sizeof k);
-      k.sk = c->skid;
-      k.N_total = c->N;
-      k.n0 = c->n0;
-      k.n_local = c->nloc;
-      k.S = c->S;
-      k.M = c->M;
-      k.H = c->H;
-      k.D = c->D;
-      k.P = c->P;
-      k.noise_mode = a.noise_mode;
-      k.log_space = c->cfg.params_log_space;
-      k.interleave = c->cfg.params_interleave;
-      k.dt = (float)c->cfg.dt;
-      k.chol_a[0] = a.chol_a[0];
-      k.chol_a[1] = a.chol_a[1];
-      k.chol_off = a.chol_off;
-      k.seed = a.seed;
-      k.ctr = a.ctr;
-      k.noise = a.noise;
-      k.theta = a.theta;
-      k.state = a.state;
-      k.params = a.params;
-      k.costs_sn = c->costs_stage;
-      k.costsT = c->costsT;
-      k.states_out = a.states_out;
-      const int nthr = c->nloc * c->S;
-      skid_rollout_kernel<<<(nthr + 255) / 256, 256, 0, c->stream>>>(k);
-      HIP_TRY(hipGetLastError());
-      o.want_states = false;
-      o.costs_in = c->costs_stage;
-      o.costs_own = true;
-      TRY(rollout_args(c, o, a, &nt, &lds));
-    }
+  if (c->cfg.model == DUST_MODEL_SKID_STEER || c->cfg.model == DUST_MODEL_CARTPOLE) {
+    const char *family = c->cfg.model == DUST_MODEL_SKID_STEER ? "skid-steer" : "cart-pole";
+    if (a.noise_f16 || o.store_f16) return fail(DUST_ERR_UNSUPPORTED, "binary16 storage is not implemented for the %s family", family);
+    if (a.mw) return fail(DUST_ERR_UNSUPPORTED, "sigma-point weights are not implemented for the %s family", family);
   }
-  if (c->cfg.model == DUST_MODEL_CARTPOLE) {
-    // pass 1 (cartpole.hpp): rollouts + costs (+ states); pass 2 (below): the regular kernel in its injected-costs mode
-    if (a.noise_f16 || o.store_f16) return fail(DUST_ERR_UNSUPPORTED, "binary16 storage is not implemented for the cart-pole family");
-    if (a.mw) return fail(DUST_ERR_UNSUPPORTED, "sigma-point weights are not implemented for the cart-pole family");
-    if (o.costs_in == nullptr) {
-      Prof ps(c, DUST_K_ROLLOUT_STATES);
-      CartArgs k;
-      memset(&k, 0, sizeof k);
-      k.cp = c->cart;
-      k.N_total = c->N;
-      k.n0 = c->n0;
-      k.n_local = c->nloc;
-      k.S = c->S;
-      k.M = c->M;
-      k.H = c->H;
-      k.D = c->D;
-      k.P = c->P;
-      k.noise_mode = a.noise_mode;
-      k.log_space = c->cfg.params_log_space;
-      k.interleave = c->cfg.params_interleave;
-      k.dt = (float)c->cfg.dt;
-      k.chol_a = a.chol_a[0];
-      k.seed = a.seed;
-      k.ctr = a.ctr;
-      k.noise = a.noise;
-      k.theta = a.theta;
-      k.state = a.state;
-      k.params = a.params;
-      k.costs_sn = c->costs_stage;
-      k.costsT = c->costsT;
-      k.states_out = a.states_out;
-      const int nthr = c->nloc * c->S;
-      cartpole_rollout_kernel<<<(nthr + 255) / 256, 256, 0, c->stream>>>(k);
-      HIP_TRY(hipGetLastError());
-      o.want_states = false;
-      o.costs_in = c->costs_stage;
-      o.costs_own = true;
-      TRY(rollout_args(c, o, a, &nt, &lds));
-    }
-  }
-  // Control-channel noise with acceleration control, drawn on the device, nothing but costs wanted: the regular kernel draws it inside
-  // its own rollout loops (rollout.hpp, round 6: the packed pair path keeps its 40 instructions per step and sample and adds one
-  // eight-normal Philox block per two steps of a pair) - no first pass.  Recorded draws (the goldens), stored states, velocity control:
-  // particle_general.hpp below.
-  const bool noise_inline = particle_general(c) && o.costs_in == nullptr && c->cfg.control_type != DUST_CONTROL_VELOCITY && !o.want_states &&
-                            !a.mw && !(c->cz_dev && c->cz_next < c->cz_sets) && c->env.noise_general <= 0;
-  if (noise_inline) {
-    a.ctrl_noise = 1;
-    a.dyn_std[0] = c->cfg.dyn_std[0];
-    a.dyn_std[1] = c->cfg.dyn_std[1];
-  }
-  if (particle_general(c) && o.costs_in == nullptr && !noise_inline) {
-    // pass 1 (particle_general.hpp): rollouts with control noise / velocity control + costs (+ states); pass 2: the regular kernel in
-    // its injected-costs mode
-    if (a.mw) return fail(DUST_ERR_UNSUPPORTED, "sigma-point weights are not implemented for Particle rollouts with control noise / velocity control");
-    Prof ps(c, DUST_K_ROLLOUT_STATES);
-    PartGenArgs k;
-    memset(&k, 0, sizeof k);
-    k.dm = a.dm;
-    k.N_total = c->N;
-    k.n0 = c->n0;
-    k.n_local = c->nloc;
-    k.S = c->S;
-    k.M = c->M;
-    k.H = c->H;
-    k.D = c->D;
-    k.noise_mode = a.noise_mode;
-    k.noise_f16 = a.noise_f16;
-    k.store_f16 = a.store_f16;
-    k.velocity = c->cfg.control_type == DUST_CONTROL_VELOCITY;
-    k.ctrl_noise = c->cfg.ctrl_noise && (c->cfg.dyn_std[0] != 0.f || c->cfg.dyn_std[1] != 0.f);
-    for (int d = 0; d < 2; ++d) {
-      k.dyn_std[d] = c->cfg.dyn_std[d];
-      k.chol_a[d] = a.chol_a[d];
-      k.a_pre[d] = a.a_pre[d];
-    }
-    k.a_reg = a.a_reg;
-    k.chol_off = a.chol_off;
-    k.a_pre_off = a.a_pre_off;
-    k.seed = a.seed;
-    k.ctr = a.ctr;
-    k.noise = a.noise;
-    k.theta = a.theta;
-    k.state = a.state;
-    k.params = a.params;
-    if (k.ctrl_noise && c->cz_dev && c->cz_next < c->cz_sets) {  // recorded draws: one set per rollout launch
-      if (c->capturing) return fail(DUST_ERR_STATE, "recorded control noise cannot be replayed from a captured graph");
-      k.cz = c->cz_dev + (size_t)c->cz_next * c->H * c->M * c->S * c->N * 2;
-      c->cz_next++;
-    }
-    k.a_seq = a.a_seq;
-    k.a_mat = a.a_mat;
-    k.costs_sn = c->costs_stage;
-    k.costsT = c->costsT;
-    k.states_out = a.states_out;
-    const int nthr = c->nloc * c->S;
-    const int pg_gw = (k.dm.with_obstacle && k.dm.grid_bits) ? (k.dm.nx * k.dm.ny + 31) / 32 : 0;
-    k.mc = c->M >= 8 ? 8 : (c->M >= 4 ? 4 : (c->M >= 2 ? 2 : 1));
-    const size_t pg_lds = particle_general_lds_bytes(c->D, pg_gw, k.mc);
-    if (pg_lds > 160 * 1024) return fail(DUST_ERR_UNSUPPORTED, "occupancy grid of %d x %d cells: the control-noise / velocity-control rollouts keep it in LDS", k.dm.nx, k.dm.ny);
-    if (pg_lds > 64 * 1024 && !c->capturing)
-      HIP_TRY(hipFuncSetAttribute((const void *)particle_general_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pg_lds));
-    const int pg_rows = PARTGEN_NT / k.mc;
-    particle_general_kernel<<<(nthr + pg_rows - 1) / pg_rows, PARTGEN_NT, pg_lds, c->stream>>>(k);
-    HIP_TRY(hipGetLastError());
+  if (particle_general(c) && o.costs_in == nullptr && a.mw)
+    return fail(DUST_ERR_UNSUPPORTED, "sigma-point weights are not implemented for Particle rollouts with control noise / velocity control");
+  const FirstPass fp = first_pass(c, o, a);
+  if (fp.kind != FP_NONE) {
+    // pass 1: rollouts + costs (+ states); pass 2 (below): the regular kernel in its injected-costs mode
+    TRY(launch_first_pass(c, fp, a));
     o.want_states = false;
     o.costs_in = c->costs_stage;
     o.costs_own = true;
     TRY(rollout_args(c, o, a, &nt, &lds));
-  }
-  {
-    int gw;
-    size_t lds_s;
-    if (states_whole_lines(c, o, a, &gw, &lds_s)) {
-      // pass 1: rollouts + states + costs; pass 2 (below): the regular kernel in its injected-costs mode - softmax, weights, score
-      {
-        Prof ps(c, DUST_K_ROLLOUT_STATES);
-        const int blocks = (c->nloc / 8) * ((c->S + 7) / 8);
-        TRY(ensure(&c->wg_flags, &c->wg_flags_cap, (size_t)blocks));
-#define DUST_LAUNCH_STATES(MODE)                                                                                                             \
-  do {                                                                                                                                       \
-    if (lds_s > 64 * 1024 && !c->capturing)                                                                                                  \
-      HIP_TRY(hipFuncSetAttribute((const void *)particle_states_kernel<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));      \
-    particle_states_kernel<MODE><<<blocks, 64 * gw, lds_s, c->stream>>>(a, c->costs_stage, gw, reinterpret_cast<unsigned int *>(c->wg_flags));                                 \
-  } while (0)
-        if (!a.dm.with_obstacle) DUST_LAUNCH_STATES(SP_FAST_FREE);
-        else if (a.dm.can_crash) DUST_LAUNCH_STATES(SP_FAST_CRASH);
-        else DUST_LAUNCH_STATES(SP_FAST_OBST);
-        DUST_LAUNCH_STATES(SP_GENERAL);  // only the workgroups the fast kernel flagged (non-finite operands) do any work here
-#undef DUST_LAUNCH_STATES
-        HIP_TRY(hipGetLastError());
-      }
-      o.want_states = false;
-      o.costs_in = c->costs_stage;
-      o.costs_own = true;
-      TRY(rollout_args(c, o, a, &nt, &lds));
-    } else if (states_whole_lines_f16(c, o, a, &gw, &lds_s)) {
-      {
-        Prof ps(c, DUST_K_ROLLOUT_STATES);
-        const int blocks = (c->nloc / 16) * ((c->S + 3) / 4);
-        TRY(ensure(&c->wg_flags, &c->wg_flags_cap, (size_t)blocks));
-#define DUST_LAUNCH_STATES(MODE)                                                                                                                 \
-  do {                                                                                                                                           \
-    if (lds_s > 64 * 1024 && !c->capturing)                                                                                                      \
-      HIP_TRY(hipFuncSetAttribute((const void *)particle_states_f16_kernel<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));      \
-    particle_states_f16_kernel<MODE><<<blocks, 64 * gw, lds_s, c->stream>>>(a, c->costs_stage, gw, reinterpret_cast<unsigned int *>(c->wg_flags)); \
-  } while (0)
-        if (!a.dm.with_obstacle) DUST_LAUNCH_STATES(SP_FAST_FREE);
-        else if (a.dm.can_crash) DUST_LAUNCH_STATES(SP_FAST_CRASH);
-        else DUST_LAUNCH_STATES(SP_FAST_OBST);
-        DUST_LAUNCH_STATES(SP_GENERAL);  // only the workgroups the fast kernel flagged (non-finite operands) do any work here
-#undef DUST_LAUNCH_STATES
-        HIP_TRY(hipGetLastError());
-      }
-      o.want_states = false;
-      o.costs_in = c->costs_stage;
-      o.costs_own = true;
-      TRY(rollout_args(c, o, a, &nt, &lds));
-    } else if (states_whole_lines_pend(c, o, a, &lds_s)) {
-      {
-        Prof ps(c, DUST_K_ROLLOUT_STATES);
-        const int blocks = (c->nloc / 16) * ((c->S + 15) / 16);
-        TRY(ensure(&c->wg_flags, &c->wg_flags_cap, (size_t)blocks));
-        unsigned int *fl = reinterpret_cast<unsigned int *>(c->wg_flags);
-        if (lds_s > 64 * 1024 && !c->capturing) {
-          HIP_TRY(hipFuncSetAttribute((const void *)pendulum_states_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
-          HIP_TRY(hipFuncSetAttribute((const void *)pendulum_states_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
-        }
-        pendulum_states_kernel<false><<<blocks, 256, lds_s, c->stream>>>(a, c->costs_stage, fl);
-        pendulum_states_kernel<true><<<blocks, 256, lds_s, c->stream>>>(a, c->costs_stage, fl);  // flagged workgroups only
-        HIP_TRY(hipGetLastError());
-      }
-      o.want_states = false;
-      o.costs_in = c->costs_stage;
-      o.costs_own = true;
-      TRY(rollout_args(c, o, a, &nt, &lds));
-    } else if (states_whole_lines_pend_f16(c, o, a, &lds_s)) {
-      {
-        Prof ps(c, DUST_K_ROLLOUT_STATES);
-        const int blocks = (c->nloc / 32) * ((c->S + 7) / 8);
-        TRY(ensure(&c->wg_flags, &c->wg_flags_cap, (size_t)blocks));
-        unsigned int *fl = reinterpret_cast<unsigned int *>(c->wg_flags);
-        if (lds_s > 64 * 1024 && !c->capturing) {
-          HIP_TRY(hipFuncSetAttribute((const void *)pendulum_states_f16_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
-          HIP_TRY(hipFuncSetAttribute((const void *)pendulum_states_f16_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
-        }
-        pendulum_states_f16_kernel<false><<<blocks, 256, lds_s, c->stream>>>(a, c->costs_stage, fl);
-        pendulum_states_f16_kernel<true><<<blocks, 256, lds_s, c->stream>>>(a, c->costs_stage, fl);  // flagged workgroups only
-        HIP_TRY(hipGetLastError());
-      }
-      o.want_states = false;
-      o.costs_in = c->costs_stage;
-      o.costs_own = true;
-      TRY(rollout_args(c, o, a, &nt, &lds));
-    }
+  } else if (ctrl_noise_inline(c, o, a)) {
+    a.ctrl_noise = 1;
+    a.dyn_std[0] = c->cfg.dyn_std[0];
+    a.dyn_std[1] = c->cfg.dyn_std[1];
   }
   Prof p(c, DUST_K_ROLLOUT);
 #define DUST_LAUNCH_ROLLOUT(KERNEL)                                                                                            \
