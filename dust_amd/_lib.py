@@ -105,6 +105,7 @@ SYMBOLS = {
     "dust_get_config": (C.c_int, [VP, C.POINTER(Config)]),
     "dust_set_model_param": (C.c_int, [VP, C.c_char_p, C.c_double, C.c_int]),
     "dust_set_param_weights": (C.c_int, [VP, FP]),
+    "dust_set_sigma_scale": (C.c_int, [VP, C.c_float]),
     "dust_set_grid": (C.c_int, [VP, FP, C.c_int, C.c_int, C.c_float, C.c_float]),
     "dust_set_ctrl_noise": (C.c_int, [VP, FP, C.c_int]),
     "dust_mpf_set_ctrl_noise": (C.c_int, [VP, FP, C.c_int]),
@@ -186,6 +187,7 @@ SYMBOLS = {
     "dust_mpf_get_prior_bw": (C.c_int, [VP, FP]),
     "dust_mpf_stats": (C.c_int, [VP, C.POINTER(C.c_longlong)]),
     "dust_mpf_prior_sample": (C.c_int, [VP, C.c_int, C.c_uint64, FP]),
+    "dust_mpf_sigma_points": (C.c_int, [VP, C.c_float, FP]),
     "dust_mpf_prior_log_prob": (C.c_int, [VP, C.c_int, FP, FP]),
     "dust_mpf_silverman": (C.c_int, [VP, FP]),
     "dust_dual_tick": (C.c_int, [VP, VP, FP, FP, C.c_int, C.c_int, C.c_float, C.c_uint64, FP, FP, FP]),

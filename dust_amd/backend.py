@@ -356,6 +356,10 @@ class Context:
         """Unscented-transform weights of the n_params dynamics samples (None: plain mean)."""
         L.check(L.load().dust_set_param_weights(self._h, _p(None if w is None else _f(w, (self.M,)))))
 
+    def set_sigma_scale(self, scale):
+        """lambda + n of the transform whose weights set_param_weights set (dual_tick computes the filter's sigma points with it); 0 clears."""
+        L.check(L.load().dust_set_sigma_scale(self._h, float(scale)))
+
     def set_model_param(self, name, value, kind=-1):
         L.check(L.load().dust_set_model_param(self._h, name.encode(), float(value), kind))
 
@@ -736,6 +740,12 @@ class MpfContext:
     def prior_sample(self, n, seed=0):
         out = np.empty((n, self.P), np.float32)
         L.check(L.load().dust_mpf_prior_sample(self._h, n, seed, _p(out)))
+        return out
+
+    def sigma_points(self, scale):
+        """[2P + 1, P] sigma points of the prior's mean and diagonal variance for a Merwe transform with lambda + n = scale."""
+        out = np.empty((2 * self.P + 1, self.P), np.float32)
+        L.check(L.load().dust_mpf_sigma_points(self._h, float(scale), _p(out)))
         return out
 
     def prior_log_prob(self, x):

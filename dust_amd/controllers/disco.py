@@ -134,6 +134,7 @@ class MultiDISCO:
         self._ctx_key = key
         if self._tf is not None:
             self._ctx.set_param_weights(self._tf.loc_weights.numpy())
+            self._ctx.set_sigma_scale(self._tf.scale)
         if state is None:
             self._ctx.set_a_mat(self._a_mat.numpy())
             self._ctx.set_a_seq(self._a_seq.numpy())

@@ -12,7 +12,8 @@ such class, so the names below are new and the SEMANTICS are 
 Both halves run on the MI355X through the C ABI (dust_svmpc_tick / dust_svmpc_optimize + forward; dust_mpf_optimize;
 dust_mpf_prior_sample).  `fused=True` (round 6) runs a whole control period - the filter update for the action just applied, Silverman's
 bandwidth ON THE DEVICE when none is given, the controller's dynamics samples drawn from the refreshed filter prior on the device, the
-control tick - in ONE C call (dust_dual_tick): step() then only notes (action, new_state) and the next forward() carries it out; the
+control tick (a sigma-point controller, `MerweScaledUTF`: the sigma points of that prior, computed on the device; a custom `sqrt_method`
+stays on the unfused path) - in ONE C call (dust_dual_tick): step() then only notes (action, new_state) and the next forward() carries it out; the
 filter's particles are current again after that forward().  The draws come from the library's Philox stream (not torch's), so a run
 with recorded draws (`draw_source`) stays on the unfused path.  `serve=True` turns on closed-loop serving for the control half when its shape allows it (nominal dynamics only:
 a filter-coupled controller samples dynamics parameters per tick, which serving does not take - then it is a no-op)."""
@@ -61,6 +62,10 @@ class DualSVMPC:
     # ---- the control half of a tick (simulations.py:108-123)
     def _can_fuse(self):
         ctrl = self.controller
+        tf = getattr(ctrl, "_tf", None)
+        # a sigma-point controller: the device computes the points of the filter's diagonal prior for the default (Cholesky) root only
+        if tf is not None and (self.mpf is None or not tf.default_sqrt or tf.n != self.mpf._dev.P):
+            return False
         return (self.fused and self.mpf is not None and self.dyn_dist is self.mpf.prior and getattr(ctrl, "draw_source", None) is None
                 and self.mpf.draw_source is None and self.svmpc.roll_strategy != "resample" and self.ticks >= self.warm_up)
 

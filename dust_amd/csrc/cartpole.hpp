@@ -53,6 +53,7 @@ struct CartArgs {
   float *costs_sn;      // [S][N]
   float *costsT;        // [N][S] the context's cost record (the regular kernel does not write it in its injected-costs mode)
   float *states_out;    // [M][S][N][H+1][4] or nullptr
+  const float *mw;      // [M] unscented-transform weights (params: the M sigma points) or nullptr: plain mean over m (last: the other offsets stay)
 };
 
 // mass, pm, 4/3 from the seven fp32 parameter values; pm_py: both factors of pm are Python floats, so is their product (double)
@@ -90,7 +91,15 @@ __device__ __forceinline__ void cartpole_step(float x[4], const float ac, const 
   x[3] = thd + thdd * k.dt;
 }
 
-__global__ __launch_bounds__(256) void cartpole_rollout_kernel(const CartArgs a) {
+// UT: the sigma-point form (MultiDISCO._sigma_rollout, disco.py:211-292; the weighted costs of _compute_cost, disco.py:312-323): row m of
+// `params` is sigma point m and the lane's cost is the weighted SUM
+//     sum_m sum_t mw[(m H + t) mod M] inst(x_{m,t}) + sum_m mw[m] term(x_{m,H})
+// - the reference views its flat [rollout][step] block of instantaneous costs as rows of M consecutive entries, and rollout
+// (s N + n) M + m runs sigma point m, so entry (m, t) meets weight (m H + t) mod M (rollout.hpp has the Pendulum's form of the rule).
+// Weighted terms accumulate in double (CostAcc::add_weighted); the two parts are rounded and added in fp32 as the regular kernel does.
+// A template parameter, not a run-time branch: the plain instance is the kernel it was before the sigma-point form existed.
+template <bool UT>
+__device__ __forceinline__ void cartpole_rollout_body(const CartArgs &a) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= a.n_local * a.S) return;
   const int s = idx / a.n_local, n = a.n0 + (idx - s * a.n_local);  // (n fastest: the rows of one sample are adjacent)
@@ -106,7 +115,7 @@ __global__ __launch_bounds__(256) void cartpole_rollout_kernel(const CartArgs a)
   const bool pm_py = (a.cp.par[CP_MP].kind == DUST_PARAM_PYFLOAT || (a.cp.par[CP_MP].kind == DUST_PARAM_SAMPLED && !have_rows)) &&
                      (a.cp.par[CP_LEN].kind == DUST_PARAM_PYFLOAT || (a.cp.par[CP_LEN].kind == DUST_PARAM_SAMPLED && !have_rows));
   const double pm_d = a.cp.par[CP_MP].value * a.cp.par[CP_LEN].value;
-  double acc = 0.0;
+  double acc = 0.0, ut_term = 0.0;
   for (int m = 0; m < a.M; ++m) {
     // scalar-event params_dist quirk (disco.py:177-179): rollout r = (m, s, n) flattened uses params[r % M]
     const int mi = a.interleave ? (int)((((long)m * a.S + s) * N + n) % a.M) : m;
@@ -144,7 +153,8 @@ __global__ __launch_bounds__(256) void cartpole_rollout_kernel(const CartArgs a)
         sc += (double)((d * d) * a.cp.w_state[k]);
       }
       const double cc = (double)((a0 * a0) * a.cp.w_ctrl[0]);
-      tot += (double)((float)sc + (float)cc);
+      if (UT) tot += (double)a.mw[((long)m * H + t) % a.M] * (double)((float)sc + (float)cc);
+      else tot += (double)((float)sc + (float)cc);
       cartpole_step(x, clampf(a0, -1.0f, 1.0f), kf, fast_sinf(x[2]), fast_cosf(x[2]));
       if (so)
 #pragma unroll
@@ -156,11 +166,19 @@ __global__ __launch_bounds__(256) void cartpole_rollout_kernel(const CartArgs a)
       const float d = x[k] - a.cp.goal[k];
       tc += (double)((d * d) * a.cp.w_term[k]);
     }
-    acc += (double)((float)tot + (float)tc);
+    if (UT) {  // weighted instantaneous and terminal parts are summed separately over the sigma points (disco.py:314-321)
+      ut_term += (double)a.mw[m] * (double)(float)tc;
+      acc += tot;
+    } else {
+      acc += (double)((float)tot + (float)tc);
+    }
   }
-  const float cost = a.M == 1 ? (float)acc : (float)(acc / a.M);
+  const float cost = UT ? (float)acc + (float)ut_term : (a.M == 1 ? (float)acc : (float)(acc / a.M));
   a.costs_sn[(size_t)s * N + n] = cost;
   a.costsT[(size_t)n * a.S + s] = cost;
 }
+
+__global__ __launch_bounds__(256) void cartpole_rollout_kernel(const CartArgs a) { cartpole_rollout_body<false>(a); }
+__global__ __launch_bounds__(256) void cartpole_ut_rollout_kernel(const CartArgs a) { cartpole_rollout_body<true>(a); }
 
 }  // namespace dust

@@ -116,6 +116,7 @@ struct dust_ctx {
   float *pS;                 // Gram x score partials of the one-launch iteration (pA still holds the prior's while its Stein tiles run)
   size_t pS_cap;
   float *mw_dev;             // [M] unscented-transform weights of the dynamics samples (nullptr: mean)
+  float sigma_scale;         // lambda + n of the transform whose weights mw_dev holds (dust_set_sigma_scale; 0: not given)
   float *theta_w, *mu_w;     // full prior covariance: whitened copies L_p^-1 x of the particles / prior means, refreshed before each prior pass
   float *cz_dev;             // recorded control-noise draws [cz_sets][H][M*S*N][da] (dust_set_ctrl_noise), consumed one set per rollout launch
   size_t cz_cap;
@@ -1033,6 +1034,7 @@ extern "C" int dust_clone(const dust_ctx *src, dust_ctx **out) {
   if (src->mw_dev) {
     TRY(dalloc(&c->mw_dev, (size_t)c->M));
     TRY(d2d(c, c->mw_dev, src->mw_dev, (size_t)c->M * sizeof(float)));
+    c->sigma_scale = src->sigma_scale;
   }
   HIP_TRY(hipStreamSynchronize(c->stream));
   return DUST_OK;
@@ -1064,11 +1066,20 @@ extern "C" int dust_set_param_weights(dust_ctx *c, const float *w) {
       HIP_TRY(hipFree(c->mw_dev));
       c->mw_dev = nullptr;
     }
+    c->sigma_scale = 0.f;  // (the scale belongs to the transform the weights came from)
     return DUST_OK;
   }
   if (c->cfg.dim_p <= 0) return fail(DUST_ERR_STATE, "parameter weights need sampled parameters (dim_p > 0)");
   if (!c->mw_dev) TRY(dalloc(&c->mw_dev, (size_t)c->M));
   return h2d(c, c->mw_dev, w, (size_t)c->M * sizeof(float));
+}
+
+extern "C" int dust_set_sigma_scale(dust_ctx *c, float scale) {
+  if (!c) return fail(DUST_ERR_INVALID, "null ctx");
+  if (!(scale >= 0.f)) return fail(DUST_ERR_INVALID, "the sigma-point scale lambda + n must be > 0 (0 clears it), got %g", (double)scale);
+  if (scale > 0.f && !c->mw_dev) return fail(DUST_ERR_STATE, "the sigma-point scale belongs to unscented-transform weights: dust_set_param_weights first");
+  c->sigma_scale = scale;
+  return DUST_OK;
 }
 
 extern "C" int dust_set_ctrl_noise(dust_ctx *c, const float *z, int n_sets) {
@@ -1558,6 +1569,7 @@ static void first_pass_param_args(const dust_ctx *c, Args &k) {
   k.log_space = c->cfg.params_log_space;
   k.interleave = c->cfg.params_interleave;
   k.dt = (float)c->cfg.dt;
+  k.mw = c->mw_dev;
 }
 
 // A whole-line first pass: the fast instance, then the general one, in which only the workgroups the fast kernel flagged (non-finite
@@ -1585,7 +1597,8 @@ static int launch_first_pass(dust_ctx *c, const FirstPass &fp, const RolloutArgs
       k.chol_a[0] = a.chol_a[0];
       k.chol_a[1] = a.chol_a[1];
       k.chol_off = a.chol_off;
-      skid_rollout_kernel<<<fp.blocks, 256, 0, c->stream>>>(k);
+      if (k.mw) skid_ut_rollout_kernel<<<fp.blocks, 256, 0, c->stream>>>(k);
+      else skid_rollout_kernel<<<fp.blocks, 256, 0, c->stream>>>(k);
       break;
     }
     case FP_CART: {
@@ -1594,7 +1607,8 @@ static int launch_first_pass(dust_ctx *c, const FirstPass &fp, const RolloutArgs
       first_pass_param_args(c, k);
       k.cp = c->cart;
       k.chol_a = a.chol_a[0];
-      cartpole_rollout_kernel<<<fp.blocks, 256, 0, c->stream>>>(k);
+      if (k.mw) cartpole_ut_rollout_kernel<<<fp.blocks, 256, 0, c->stream>>>(k);
+      else cartpole_rollout_kernel<<<fp.blocks, 256, 0, c->stream>>>(k);
       break;
     }
     case FP_PARTGEN: {
@@ -1653,7 +1667,16 @@ static int launch_rollout(dust_ctx *c, const SampleOpts &o_in) {
   if (c->cfg.model == DUST_MODEL_SKID_STEER || c->cfg.model == DUST_MODEL_CARTPOLE) {
     const char *family = c->cfg.model == DUST_MODEL_SKID_STEER ? "skid-steer" : "cart-pole";
     if (a.noise_f16 || o.store_f16) return fail(DUST_ERR_UNSUPPORTED, "binary16 storage is not implemented for the %s family", family);
-    if (a.mw) return fail(DUST_ERR_UNSUPPORTED, "sigma-point weights are not implemented for the %s family", family);
+    if (a.mw) {  // sigma-point rollouts: the two cases the reference cannot compute either
+      const bool skid = c->cfg.model == DUST_MODEL_SKID_STEER;
+      const bool ctrl = skid ? (c->skid.w_ctrl[0] != 0.f || c->skid.w_ctrl[1] != 0.f) : c->cart.w_ctrl[0] != 0.f;
+      if (ctrl)
+        return fail(DUST_ERR_UNSUPPORTED, "sigma-point weights with a non-zero control weight (%s family): the reference hands its cost function S N pts H states "
+                                          "and S N H actions (disco.py:306-309) and raises", family);
+      if (a.a_reg != 0.0f)
+        return fail(DUST_ERR_UNSUPPORTED, "sigma-point weights with a_reg != 0 (%s family): the reference's control cost reads actions[0], the first sample only "
+                                          "(disco.py:338-340)", family);
+    }
   }
   if (particle_general(c) && o.costs_in == nullptr && a.mw)
     return fail(DUST_ERR_UNSUPPORTED, "sigma-point weights are not implemented for Particle rollouts with control noise / velocity control");

@@ -992,6 +992,69 @@ __global__ void mpf_sample_kernel(const float *means, int K, int P, const MpfBw 
   for (int p = 0; p < P; ++p) out[i * P + p] = means[k * P + p] + bw.v[p] * z[p];
 }
 
+// Sigma points of mpf.prior for a Merwe scaled unscented transform (MultiDISCO._sigma_rollout, disco.py:240-251, on the prior that
+// MPF.update_prior builds, mpf.py:26-38): the mixture's mean and variance (MixtureSameFamily.mean / .variance, uniform weights),
+//     mean_p = sum_j x_jp / Mp          var_p = bw_p^2 + sum_j (x_jp - mean_p)^2 / Mp
+// and, the covariance being diagonal (so that the reference's upper Cholesky factor is an element-wise square root), the 2P + 1 points
+// of MerweScaledUTF.compute_sigma_points (utf.py:93-123) with scale = lambda + n:
+//     row 0: mean          row 1 + p: mean + sqrt(scale var_p) e_p          row 1 + P + p: mean - sqrt(scale var_p) e_p
+// written `reps` times in a row ([reps][2P + 1][P]: one set per SVGD iteration of the tick that consumes them).  One workgroup; sums in
+// double, per-lane strided partials then an LDS tree - a fixed order, the same bits for the same particles.  Mp <= 1024, P <= 4.
+__global__ __launch_bounds__(256) void mpf_sigma_points_kernel(const float *x, const int Mp, const int P, const MpfBw bw, const float scale, const int reps,
+                                                               float *out) {
+  __shared__ double red[4][256];
+  __shared__ double stat[2][4];  // mean, variance
+  const int tid = threadIdx.x;
+  auto block_sum = [&](const double (&v)[4], double *dst) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p) red[p][tid] = v[p];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+      if (tid < o)
+#pragma unroll
+        for (int p = 0; p < 4; ++p) red[p][tid] += red[p][tid + o];
+      __syncthreads();
+    }
+    if (tid < 4) dst[tid] = red[tid][0];
+    __syncthreads();
+  };
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int j = tid; j < Mp; j += 256)
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+      if (p < P) acc[p] += (double)x[(size_t)j * P + p];
+  block_sum(acc, stat[0]);
+  double mean[4];
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    mean[p] = stat[0][p] / (double)Mp;
+    acc[p] = 0.0;
+  }
+  for (int j = tid; j < Mp; j += 256)
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+      if (p < P) {
+        const double d = (double)x[(size_t)j * P + p] - mean[p];
+        acc[p] += d * d;
+      }
+  block_sum(acc, stat[1]);
+  const int pts = 2 * P + 1, per = pts * P;
+  for (int i = tid; i < reps * per; i += 256) {
+    const int e = i % per, row = e / P, p = e - row * P;
+    const float mu = (float)mean[p];
+    float v = mu;
+    if (row >= 1) {
+      const int q = row <= P ? row - 1 : row - 1 - P;  // the axis this point moves along
+      if (q == p) {
+        const double var = (double)bw.v[p] * (double)bw.v[p] + stat[1][p] / (double)Mp;
+        const float u = (float)sqrt((double)scale * var);
+        v = row <= P ? mu + u : mu - u;
+      }
+    }
+    out[i] = v;
+  }
+}
+
 // KDEpy 1.1.0 `silvermans_rule` of the pooled particle values (mpf.py:68-73: `silvermans_rule(self.x.view(-1, 1))`; restated in
 // oracle/ref_shim.py - third party, parity unpinned) on the device: sigma = min(std(ddof = 1), IQR / 1.349) (the positive one when one
 // of them is 0), bw = sigma (3 n / 4)^(-1/5), times bw_scale; 1 when n = 1 or both spreads are 0.  float64 throughout, as the host rule
@@ -1765,6 +1828,20 @@ extern "C" int dust_mpf_prior_log_prob(dust_mpf *m, int n, const float *x, float
   return DUST_OK;
 }
 
+// tf.compute_sigma_points(mpf.prior.mean, mpf.prior.variance.diag()) (disco.py:240-251, utf.py:93-123) on the device; scale = lambda + n
+extern "C" int dust_mpf_sigma_points(dust_mpf *m, float scale, float *out) {
+  if (!m || !out) return fail(DUST_ERR_INVALID, "null argument");
+  if (!(scale > 0.f)) return fail(DUST_ERR_INVALID, "the sigma-point scale lambda + n must be > 0, got %g", (double)scale);
+  HIP_TRY(hipSetDevice(m->cfg.device));
+  const size_t n = (size_t)(2 * m->P + 1) * m->P;
+  TRY(ensure(&m->tmp, &m->tmp_cap, n));
+  mpf_sigma_points_kernel<<<1, 256, 0, m->stream>>>(m->x, m->Mp, m->P, mpf_bw(m), scale, 1, m->tmp);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out, m->tmp, n * sizeof(float), hipMemcpyDeviceToHost, m->stream));
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  return DUST_OK;
+}
+
 // MPF.optimize's `bw = silvermans_rule(self.x.view(-1, 1)) * self.bw_scale` (mpf.py:68-73) on the device: one launch and a 4-byte read-back
 // instead of a copy of the particles and a host percentile.
 extern "C" int dust_mpf_silverman(dust_mpf *m, float *bw) {
@@ -1812,6 +1889,13 @@ extern "C" int dust_dual_tick(dust_ctx *c, dust_mpf *m, const float *state, cons
     }
   }
   if (comm_active(c)) return fail(DUST_ERR_UNSUPPORTED, "the dual tick runs on an unsharded controller (the filter is replicated: tick it per rank)");
+  if (c->mw_dev) {  // a sigma-point controller: its dynamics samples are the sigma points of the filter's prior, not draws from it
+    if (!(c->sigma_scale > 0.f))
+      return fail(DUST_ERR_UNSUPPORTED, "the dual tick over sigma-point weights needs the transform's scale lambda + n (dust_set_sigma_scale): the "
+                                        "dynamics samples are the sigma points of the filter's prior (disco.py:240-251)");
+    if (c->M != 2 * m->P + 1) return fail(DUST_ERR_INVALID, "sigma-point weights over P = %d parameters take M = 2 P + 1 = %d samples, the controller has M = %d", m->P, 2 * m->P + 1, c->M);
+    if (c->cfg.params_log_space) return fail(DUST_ERR_UNSUPPORTED, "sigma points of a log-space parameter distribution: the reference asserts against it (disco.py:125)");
+  }
   HIP_TRY(hipSetDevice(c->cfg.device));
   float bw = bw_in;
   if (action_prev) {
@@ -1822,7 +1906,9 @@ extern "C" int dust_dual_tick(dust_ctx *c, dust_mpf *m, const float *state, cons
   TRY(settle_pending(c));
   const int n = n_steps * c->M;
   TRY(ensure(&c->params_dev, &c->params_cap, (size_t)n * c->P));
-  dust::mpf_sample_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(m->x, m->Mp, m->P, mpf_bw(m), seed, n, c->params_dev);
+  // (sigma points: the same 2P + 1 points for every SVGD iteration - MultiDISCO._sigma_rollout recomputes them per call; seed unused)
+  if (c->mw_dev) dust::mpf_sigma_points_kernel<<<1, 256, 0, c->stream>>>(m->x, m->Mp, m->P, mpf_bw(m), c->sigma_scale, n_steps, c->params_dev);
+  else dust::mpf_sample_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(m->x, m->Mp, m->P, mpf_bw(m), seed, n, c->params_dev);
   HIP_TRY(hipGetLastError());
   c->params_staged = true;  // (dust_svmpc_tick finds its dynamics samples in place: no host copy, no one-launch tick - its replay record keeps host samples)
   const int st = dust_svmpc_tick(c, state, n_steps, nullptr, c->params_dev, 0, a_seq, p_weights);

@@ -42,6 +42,7 @@ struct SkidArgs {
   float *costsT;        // [N][S] the context's cost record (the regular kernel does not write it in its injected-costs mode)
   float *states_out;    // [M][S][N][H+1][5] or nullptr
   float *actions_out;   // [S][N][D] or nullptr
+  const float *mw;      // [M] unscented-transform weights (params: the M sigma points) or nullptr: plain mean over m (last: the other offsets stay)
 };
 
 __device__ __forceinline__ float skid_param(const DevParam &p, const float *prow, int log_space) {
@@ -74,7 +75,15 @@ __device__ __forceinline__ void skid_step(float x[5], const float r, const float
   skid_step_cs(x, r, l, xicr, wr, ad, dt, fast_cosf(x[2]), fast_sinf(x[2]));
 }
 
-__global__ __launch_bounds__(256) void skid_rollout_kernel(const SkidArgs a) {
+// UT: the sigma-point form (MultiDISCO._sigma_rollout, disco.py:211-292; the weighted costs of _compute_cost, disco.py:312-323): row m of
+// `params` is sigma point m and the lane's cost is the weighted SUM
+//     sum_m sum_t mw[(m H + t) mod M] inst(x_{m,t}) + sum_m mw[m] term(x_{m,H})
+// - the reference views its flat [rollout][step] block of instantaneous costs as rows of M consecutive entries, and rollout
+// (s N + n) M + m runs sigma point m, so entry (m, t) meets weight (m H + t) mod M (rollout.hpp has the Pendulum's form of the rule).
+// Weighted terms accumulate in double (CostAcc::add_weighted); the two parts are rounded and added in fp32 as the regular kernel does.
+// A template parameter, not a run-time branch: the plain instance is the kernel it was before the sigma-point form existed.
+template <bool UT>
+__device__ __forceinline__ void skid_rollout_body(const SkidArgs &a) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= a.n_local * a.S) return;
   const int s = idx / a.n_local, n = a.n0 + (idx - s * a.n_local);  // (n fastest: the rows of one sample are adjacent)
@@ -94,7 +103,7 @@ __global__ __launch_bounds__(256) void skid_rollout_kernel(const SkidArgs a) {
   float x0[5];
 #pragma unroll
   for (int k = 0; k < 5; ++k) x0[k] = a.state[k];
-  double acc = 0.0;
+  double acc = 0.0, ut_term = 0.0;
   for (int m = 0; m < a.M; ++m) {
     // scalar-event params_dist quirk (disco.py:177-179): rollout r = (m, s, n) flattened uses params[r % M]
     const int mi = a.interleave ? (int)((((long)m * a.S + s) * N + n) % a.M) : m;
@@ -118,7 +127,8 @@ __global__ __launch_bounds__(256) void skid_rollout_kernel(const SkidArgs a) {
         sc += (double)((d * d) * a.sk.w_state[k]);
       }
       const double cc = (double)((a0 * a0) * a.sk.w_ctrl[0]) + (double)((a1 * a1) * a.sk.w_ctrl[1]);
-      tot += (double)((float)sc + (float)cc);
+      if (UT) tot += (double)a.mw[((long)m * H + t) % a.M] * (double)((float)sc + (float)cc);
+      else tot += (double)((float)sc + (float)cc);
       skid_step(x, clampf(a0, a.sk.lo[0], a.sk.hi[0]), clampf(a1, a.sk.lo[1], a.sk.hi[1]), xicr, wr, ad, a.dt);
       if (so)
 #pragma unroll
@@ -130,11 +140,19 @@ __global__ __launch_bounds__(256) void skid_rollout_kernel(const SkidArgs a) {
       const float d = x[k] - a.sk.goal[k];
       tc += (double)((d * d) * a.sk.w_term[k]);
     }
-    acc += (double)((float)tot + (float)tc);
+    if (UT) {  // weighted instantaneous and terminal parts are summed separately over the sigma points (disco.py:314-321)
+      ut_term += (double)a.mw[m] * (double)(float)tc;
+      acc += tot;
+    } else {
+      acc += (double)((float)tot + (float)tc);
+    }
   }
-  const float cost = a.M == 1 ? (float)acc : (float)(acc / a.M);
+  const float cost = UT ? (float)acc + (float)ut_term : (a.M == 1 ? (float)acc : (float)(acc / a.M));
   a.costs_sn[(size_t)s * N + n] = cost;
   a.costsT[(size_t)n * a.S + s] = cost;
 }
+
+__global__ __launch_bounds__(256) void skid_rollout_kernel(const SkidArgs a) { skid_rollout_body<false>(a); }
+__global__ __launch_bounds__(256) void skid_ut_rollout_kernel(const SkidArgs a) { skid_rollout_body<true>(a); }
 
 }  // namespace dust

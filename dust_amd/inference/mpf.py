@@ -37,6 +37,11 @@ class _DevicePrior:
     def mean(self):
         return torch.from_numpy(self._mpf._dev.get_prior()[0]).mean(0)
 
+    @property
+    def variance(self):  # MixtureSameFamily.variance of uniform components N(x_j, diag(bw^2)): what a sigma-point controller reads
+        x = torch.from_numpy(self._mpf._dev.get_prior()[0])
+        return torch.from_numpy(self._mpf._dev.get_prior_bw()) ** 2 + ((x - x.mean(0)) ** 2).mean(0)
+
     def sample(self, shape):
         n = int(np.prod(shape)) if len(shape) else 1
         self._seed += 1

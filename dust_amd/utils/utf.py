@@ -10,8 +10,10 @@ class MerweScaledUTF:
         self.n, self.pts = n, 2 * n + 1
         self.alpha, self.beta, self.kappa = alpha, beta, kappa
         # upper-triangular square root U with U^T U = A, as the reference's default (utf.py:51-57)
+        self.default_sqrt = sqrt_method is None  # (the device computes the points of a diagonal covariance for this root only)
         self.sqrt = sqrt_method or (lambda A: torch.linalg.cholesky(A.transpose(-2, -1).conj()).transpose(-2, -1).conj())
         lam = alpha ** 2 * (n + kappa) - n
+        self.scale = lam + n  # (lambda + n: compute_sigma_points' factor on the covariance)
         c = 0.5 / (n + lam)
         self._loc = torch.full((self.pts,), c, dtype=torch.float)
         self._cov = torch.full((self.pts,), c, dtype=torch.float)

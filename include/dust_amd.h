@@ -207,10 +207,16 @@ int dust_set_model_param(dust_ctx *ctx, const char *name, double value, int kind
  * combination with `w[n_params]` (utf.py loc_weights; the reference's (sigma, step) weight pattern is reproduced) instead
  * of the mean.  NULL switches back to the mean over sampled parameters. */
 int dust_set_param_weights(dust_ctx *ctx, const float *w);
+/* lambda + n of the transform whose weights dust_set_param_weights set (utf.py:93-123: the sigma points are the mean +- the columns of
+ * sqrt((lambda + n) K)).  dust_dual_tick needs it to compute the sigma points of the filter's prior on the device (disco.py:240-251);
+ * rollouts with host-computed sigma points do not.  0 clears it; so does dust_set_param_weights(NULL).  dust_clone carries it.
+ * DUST_ERR_INVALID for a negative or non-finite scale, DUST_ERR_STATE without weights. */
+int dust_set_sigma_scale(dust_ctx *ctx, float scale);
 int dust_set_skid_steer(dust_ctx *ctx, const dust_skid_config *cfg);
 /* CartPoleModel(g, f_mag, ...) cartpole.py:42-88 and its quadratic cost.  A sampled column outside dim_p, or named by two parameters:
  * DUST_ERR_INVALID.  The family runs the launch-per-iteration path (pass 1: cartpole.hpp, pass 2: the regular kernel on injected
- * costs); binary16 storage and sigma-point weights return DUST_ERR_UNSUPPORTED.  dust_clone copies the model. */
+ * costs); binary16 storage returns DUST_ERR_UNSUPPORTED, and so do sigma-point weights together with a non-zero control weight or
+ * a_reg != 0 (disco.py:306-309, 338-340: the reference cannot compute either).  dust_clone copies the model. */
 int dust_set_cartpole(dust_ctx *ctx, const dust_cartpole_config *cfg);
 /* Recorded control-channel noise for the NEXT rollouts of a Particle(deterministic=False) context (particle.py:145-148): z holds n_sets
  * tensors [H][M*S*N][da] of standard-normal draws in the reference's own order - one `torch.randn_like(acts)` per model.step call of
@@ -457,12 +463,19 @@ int dust_mpf_prior_log_prob(dust_mpf *mpf, int n, const float *x, float *log_pro
 /* MPF.optimize's default bandwidth, `silvermans_rule(self.x.view(-1, 1)) * self.bw_scale` (mpf.py:68-73; KDEpy 1.1.0, third party: parity
  * unpinned), evaluated on the device (float64, numpy's linear-interpolation quartiles): one launch + a 4-byte read-back. */
 int dust_mpf_silverman(dust_mpf *mpf, float *bw);
+/* tf.compute_sigma_points(mpf.prior.mean, mpf.prior.variance.diag()) (disco.py:240-251 on the prior of mpf.py:26-38; utf.py:93-123) on
+ * the device: mean and variance of the particle mixture (variance = bw^2 + the particles' spread), then the mean and mean +-
+ * sqrt(scale var_p) e_p with scale = lambda + n.  out [2P + 1][P], host.  DUST_ERR_INVALID unless scale > 0. */
+int dust_mpf_sigma_points(dust_mpf *mpf, float scale, float *out);
 /* One control period of the dual loop (simulations.py:104-138; BASELINE north_star "DualSVMPC step() / forward()") in ONE call:
  * mpf.optimize(action_prev, state, bw, mpf_steps) (skipped when action_prev is NULL: the first period; mpf_bw <= 0: Silverman's rule of
  * the filter's particles, on the device) -> the controller's n_steps x [M][P] dynamics samples drawn from the filter's refreshed prior on
  * the device, into the controller's parameter buffer (dyn_dist = mpf.prior: simulations.py:79, disco.py:171) -> svmpc.optimize(n_steps) +
  * svmpc.forward().  a_seq [H][da], p_weights [N] or NULL; *bw_used (or NULL): the bandwidth of the filter update.  seed: Philox key of the
- * period's draws (the stream of dust_mpf_prior_sample). */
+ * period's draws (the stream of dust_mpf_prior_sample).
+ * A controller with sigma-point weights (dust_set_param_weights) takes the sigma points of the filter's prior instead of draws
+ * (MultiDISCO._sigma_rollout, disco.py:240-251; the same points for each of the n_steps iterations; seed unused): DUST_ERR_UNSUPPORTED
+ * without dust_set_sigma_scale or with params_log_space (disco.py:125), DUST_ERR_INVALID unless M = 2P + 1. */
 int dust_dual_tick(dust_ctx *ctx, dust_mpf *mpf, const float *state, const float *action_prev, int n_steps, int mpf_steps, float mpf_bw,
                    uint64_t seed, float *a_seq, float *p_weights, float *bw_used);
 
