@@ -10,7 +10,7 @@ import sys
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DUST_AMD_LIB", os.path.join(_HERE, "libdust_amd.so"))  # override: diagnostic builds only
 
-ABI_VERSION = 2
+ABI_VERSION = 3
 OK, ERR_INVALID, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_HIP, ERR_STATE = range(6)
 MODEL_PENDULUM, MODEL_PARTICLE, MODEL_SKID_STEER, MODEL_CARTPOLE = 0, 1, 2, 3
 COST_PENDULUM_QUADCOS, COST_PARTICLE_DEFAULT, COST_QUADRATIC = 0, 1, 2
@@ -22,8 +22,8 @@ ROLL_REPEAT, ROLL_MEAN, ROLL_RESAMPLE = 0, 1, 2
 STEP_ARGMAX, STEP_AVERAGE, STEP_EXTERNAL = 0, 1, 2
 PARAM_PYFLOAT, PARAM_SAMPLED, PARAM_TENSOR0D = 0, 1, 2
 CONTROL_ACCELERATION, CONTROL_VELOCITY = 0, 1
-PTR_DEVICE, STORE_STATES, EPS_AROUND_A_MAT, EPS_F16, STORE_F16 = 1, 2, 4, 8, 16
-K_ROLLOUT, K_PRIOR_SCORE, K_STEIN, K_UPDATE, K_FORWARD, K_BANDWIDTH, K_MPF, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 8
+PTR_DEVICE, STORE_STATES, EPS_AROUND_A_MAT, EPS_F16, STORE_F16, AMPPI_PARAMS_SHARED = 1, 2, 4, 8, 16, 32
+K_ROLLOUT, K_PRIOR_SCORE, K_STEIN, K_UPDATE, K_FORWARD, K_BANDWIDTH, K_MPF, K_ROLLOUT_STATES, K_AMPPI, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 
 
 class DustError(RuntimeError):
@@ -134,6 +134,8 @@ SYMBOLS = {
     "dust_svmpc_tick": (C.c_int, [VP, FP, C.c_int, VP, FP, C.c_int, FP, FP]),
     "dust_svmpc_serve_start": (C.c_int, [VP, C.c_int, C.c_double]),
     "dust_svmpc_serve_stop": (C.c_int, [VP]),
+    "dust_amppi_update": (C.c_int, [VP, FP, VP, FP, C.c_int, FP, FP, FP]),
+    "dust_amppi_roll": (C.c_int, [VP, C.c_int]),
     "dust_get_costs": (C.c_int, [VP, FP]),
     "dust_get_actions": (C.c_int, [VP, FP]),
     "dust_get_states_rows": (C.c_int, [VP, C.POINTER(C.c_longlong), C.c_int, VP]),

@@ -527,6 +527,36 @@ class Context:
         L.check(L.load().dust_svmpc_tick(self._h, _p(st), n_steps, e, _p(pr), flags, _p(a_seq), _p(pw)))
         return a_seq, pw
 
+    # ---- AMPPI (amppi.py:227-260, base.py:68-80)
+    def amppi_update(self, state, actions=None, params=None, shared_params=False, want_states=False, want_actions=False, want_outputs=True):
+        """One AMPPI.update_actions tick (dust_amppi_update).  actions [S, H, da] or None (drawn on the device); params None ("none"),
+        one row with shared_params ("single"), [S, P] ("extended") or the [2P + 1, P] sigma points of a context with parameter weights.
+        -> (costs [S], omega [S], a_seq [H, da] after the update, states [S pts, H + 1, ds] or None, acts [S, H, da] or None);
+        want_outputs=False reads nothing back (the tick stays asynchronous on the context's stream)."""
+        st = _f(state, (self.ds,))
+        act = None if actions is None else _f(actions, (self.S, self.H, self.da))
+        pr = None if params is None else _f(params, (-1, max(self.P, 1)))  # (rows for a context without uncertain parameters: the library refuses)
+        pts = self.M  # (an AMPPI context has n_params > 1 only as the 2P + 1 sigma points: the library refuses it without their weights)
+        want_rows = None if pr is None else (pts if pts > 1 else (1 if shared_params else self.S))
+        if pr is not None and pr.shape[0] < want_rows:
+            raise ValueError("params has %d rows, the tick reads %d" % (pr.shape[0], want_rows))
+        if pr is not None and shared_params:
+            pr = pr[:1].copy()
+        flags = (L.AMPPI_PARAMS_SHARED if shared_params else 0) | (L.STORE_STATES if want_states else 0)
+        costs, omega, a_seq = ((np.empty(self.S, np.float32), np.empty(self.S, np.float32), np.empty((self.H, self.da), np.float32))
+                               if want_outputs else (None, None, None))
+        L.check(L.load().dust_amppi_update(self._h, _p(st), _vp(act), _p(pr), flags, _p(costs), _p(omega), _p(a_seq)))
+        states = acts = None
+        if want_states:
+            states = self.get_states_rows(np.arange(self.S * pts))
+        if want_actions:
+            acts = self._get(L.load().dust_get_actions, (self.S, self.H, self.da))
+        return costs, omega, a_seq, states, acts
+
+    def amppi_roll(self, steps=1):
+        """BaseController.roll(steps): the sequence moves `steps` rows forward, zeros behind (dust_amppi_roll)."""
+        L.check(L.load().dust_amppi_roll(self._h, int(steps)))
+
     def get_costs(self):
         return self._get(L.load().dust_get_costs, (self.S, self.N))
 

@@ -1,0 +1,189 @@
+"""`AMPPI` with the reference's constructor, attributes and `update_actions` / `roll` signatures
+(dust/controllers/amppi.py:6-260, dust/controllers/base.py:4-80): the single-policy information-theoretic MPC of Williams et al.
+2017, one kernel launch per tick on the MI355X (csrc/amppi.hpp).
+
+The controller owns one device context; `a_seq` lives there.  Parameter draws come from `model.sample_params(n)` on the host
+(n = 1 or n_samples rows of a handful of columns: base.py:149-171), sigma points from `model.params_dist` through
+`dust_amd.utils.utf.MerweScaledUTF`; everything else of the tick - noise, rollouts, costs, weights, the update - runs on the device.
+`copy.deepcopy(controller)` clones the context."""
+import copy
+
+import numpy as np
+import torch
+
+from ..backend import Context
+from ..costs import QuadraticCost, recognise
+from ..utils.utf import MerweScaledUTF
+
+
+class AMPPI:
+    def __init__(self, observation_space, action_space, hz_len, n_samples, lambda_=1.0, a_cov=None, inst_cost_fn=None, term_cost_fn=None,
+                 params_sampling="extended", init_actions=None, device=0, seed=0):
+        self.hz_len = hz_len
+        self.dim_s, self.dim_a = observation_space.dim, action_space.dim
+        self.min_a, self.max_a = action_space.low, action_space.high
+        # (the reference's `if not init_actions` raises on a tensor, base.py:34: None means zeros, a tensor is taken)
+        if init_actions is None:
+            self._a_seq = torch.zeros((hz_len, self.dim_a))
+        else:
+            self._a_seq = torch.as_tensor(init_actions, dtype=torch.float).detach().clone()
+            assert self._a_seq.shape == (hz_len, self.dim_a), "Initial actions shape mismatch."
+        if inst_cost_fn is None and term_cost_fn is None:
+            raise ValueError("Specify at least one cost function")
+        self.inst_cost_fn, self.term_cost_fn = inst_cost_fn, term_cost_fn
+        self.n_samples = n_samples
+        self.lambda_ = lambda_
+        if a_cov is None:
+            a_cov = torch.eye(self.dim_a)
+        a_cov = torch.as_tensor(a_cov, dtype=torch.float)
+        if not torch.equal(a_cov, torch.diag(torch.diag(a_cov))) and self.dim_a != 2:
+            raise NotImplementedError("a full a_cov has a HIP kernel for dim_a = 2 (no CPU fallback)")
+        self.a_dist = torch.distributions.multivariate_normal.MultivariateNormal(torch.zeros(self.dim_a), a_cov)
+        self.a_pre = torch.inverse(a_cov)
+        if not params_sampling or params_sampling == "none":
+            self._sample_shape, self._tf = None, None
+        elif params_sampling == "single":
+            self._sample_shape, self._tf = 1, None
+        elif params_sampling == "extended":
+            self._sample_shape, self._tf = n_samples, None
+        elif isinstance(params_sampling, MerweScaledUTF):
+            self._sample_shape, self._tf = None, params_sampling
+        else:
+            raise ValueError("Invalid value for 'params_sampling': {}".format(params_sampling))
+        self._params_sampling = params_sampling
+        # update_actions returns (costs, states, acts, omega) like the reference; callers that ignore the trajectories set this False:
+        # the kernel then stores no states and nothing but costs / omega is copied back (states / acts come back as None)
+        self.return_rollouts = True
+        self._ctx, self._ctx_key = None, None
+        self._device, self._seed = device, seed
+
+    @property
+    def params_sampling(self):
+        return self._params_sampling
+
+    # ------------------------------------------------------------------ context management
+    def _config(self, model):
+        fam = getattr(model, "family", None)
+        if fam not in ("pendulum", "particle", "skid_steer", "cartpole"):
+            raise NotImplementedError("no AMPPI kernel family for %s" % type(model).__name__)
+        if fam == "particle" and not model.deterministic:
+            raise NotImplementedError("AMPPI runs Particle(deterministic=True): control-channel noise inside the tick is not implemented")
+        if fam == "particle" and model.control_type != "acceleration":
+            raise NotImplementedError("AMPPI runs Particle(control_type='acceleration')")
+        owner = getattr(self.inst_cost_fn, "__self__", None)
+        if isinstance(owner, QuadraticCost) and owner.w_ctrl is not None and bool((owner.w_ctrl != 0).any()):
+            raise NotImplementedError("AMPPI's instantaneous cost sees no action (amppi.py:205); its control cost is the lambda term: "
+                                      "QuadraticCost(w_ctrl=...) cannot be honoured")
+        sampled = self._sample_shape is not None or self._tf is not None
+        up = tuple(model.uncertain_params or ()) if sampled else ()
+        if sampled and not up:
+            raise ValueError("params_sampling is on but the model names no uncertain_params")
+        if len(up) > 4:
+            raise NotImplementedError("at most 4 uncertain parameters run on the device, got %d" % len(up))
+        if self.hz_len * self.dim_a > 128:
+            raise NotImplementedError("hz_len * dim_a = %d > 128 is not supported by the kernels" % (self.hz_len * self.dim_a))
+        if not 1 <= self.n_samples <= 65536:
+            raise NotImplementedError("n_samples = %d outside [1, 65536]" % self.n_samples)
+        cov = self.a_dist.covariance_matrix
+        cfg = dict(model=fam, N=1, S=self.n_samples, M=self._tf.pts if self._tf is not None else 1, H=self.hz_len,
+                   temperature=float(self.lambda_), alpha=1.0 / float(self.lambda_), a_cov=cov.numpy(),  # (make_config factors a_cov itself)
+                   min_a=torch.as_tensor(self.min_a, dtype=torch.float).reshape(-1).numpy(),
+                   max_a=torch.as_tensor(self.max_a, dtype=torch.float).reshape(-1).numpy(),
+                   device=self._device, seed=self._seed, dt=model.dt, sampling=sampled, uncertain_params=up)
+        pd = model.params_dict
+        for k in ("x_icr", "wheel_radius", "axial_distance"):
+            if k in pd:
+                cfg[k] = float(pd[k])
+        if fam == "cartpole":
+            for k in ("f_mag", "mass_cart", "mass_pole", "mu_c", "mu_p"):
+                cfg[k] = float(pd[k])
+        for k in ("g", "mass", "length"):
+            if k in pd:
+                cfg[k] = float(pd[k])
+                if k == "mass" and isinstance(pd[k], torch.Tensor):
+                    cfg["mass_0dim"] = True
+        if fam == "particle":
+            cfg.update(max_speed=float(model._max_speed), max_accel=float(model._max_acc), can_crash=bool(model.can_crash),
+                       with_obstacle=bool(model.with_obstacle), cell_size=float(model.map_cell_size or 0.1), control_type="acceleration",
+                       deterministic=True)
+        cfg.update(recognise(model, self.inst_cost_fn, self.term_cost_fn))
+        return cfg
+
+    def _ensure_ctx(self, model):
+        cfg = self._config(model)
+        key = repr(sorted((k, np.asarray(v).tolist() if not isinstance(v, (str, bool, int, float, tuple)) else v) for k, v in cfg.items()))
+        if self._ctx is not None and key == self._ctx_key:
+            return self._ctx
+        a_seq = self.a_seq.numpy()
+        if self._ctx is not None:
+            self._ctx.close()
+        grid = model.obst_map.map.astype(np.float32) if getattr(model, "obst_map", None) is not None else None
+        self._ctx, self._ctx_key = Context(grid=grid, **cfg), key
+        if self._tf is not None:
+            self._ctx.set_param_weights(self._tf.loc_weights.numpy())
+        self._ctx.set_a_seq(a_seq)
+        return self._ctx
+
+    def __deepcopy__(self, memo):
+        new = copy.copy(self)
+        memo[id(self)] = new
+        for k, v in self.__dict__.items():
+            if k == "_ctx":
+                new._ctx = None if v is None else v.clone()
+            elif k in ("inst_cost_fn", "term_cost_fn"):
+                setattr(new, k, v)
+            else:
+                setattr(new, k, copy.deepcopy(v, memo))
+        return new
+
+    # ------------------------------------------------------------------ BaseController
+    @property
+    def a_seq(self):
+        return torch.from_numpy(self._ctx.get_a_seq()) if self._ctx is not None else self._a_seq
+
+    @a_seq.setter
+    def a_seq(self, v):
+        self._a_seq = torch.as_tensor(v, dtype=torch.float).detach().clone().reshape(self.hz_len, self.dim_a)
+        if self._ctx is not None:
+            self._ctx.set_a_seq(self._a_seq.numpy())
+
+    def roll(self, steps=1):  # base.py:68-80
+        if steps < 1:
+            raise ValueError("roll(steps=%d): steps >= 1" % steps)
+        if self._ctx is not None:
+            self._ctx.amppi_roll(steps)
+        else:
+            self._a_seq = torch.cat((self._a_seq[steps:], torch.zeros(min(steps, self.hz_len), self.dim_a)), 0)
+
+    # ------------------------------------------------------------------ amppi.py:227-260
+    def _sigma_points(self, model):
+        """amppi.py:164-175 -> [pts, P]"""
+        pd = model.params_dist
+        if pd is None:
+            raise ValueError("a sigma-point controller reads model.params_dist: assign the parameter distribution to the model")
+        try:
+            cov, mean = pd.covariance_matrix, pd.mean
+        except AttributeError:
+            try:
+                cov, mean = pd.variance.diag(), pd.mean
+            except AttributeError:
+                # (the reference's third form, `.a` / `.xs[i].S`, belongs to a mixture class it does not ship)
+                raise NotImplementedError("model.params_dist has neither covariance_matrix nor variance")
+        return self._tf.compute_sigma_points(mean, cov).T.contiguous().numpy()
+
+    def update_actions(self, model, state, actions=None):
+        """amppi.py:227-260 -> (costs [S], states [S pts, H + 1, ds], acts [S, H, da], omega [S]); `a_seq` is updated on the device.
+        With `return_rollouts = False` nothing but costs and omega is stored or copied back: states and acts are None."""
+        ctx = self._ensure_ctx(model)
+        state = torch.as_tensor(state, dtype=torch.float).reshape(-1)
+        acts = None if actions is None else torch.as_tensor(actions, dtype=torch.float).numpy()
+        params, shared = None, False
+        if self._tf is not None:
+            params = self._sigma_points(model)
+        elif self._sample_shape:
+            params = model.dict_to_params(model.sample_params(self._sample_shape)).numpy()
+            shared = self._params_sampling == "single"
+        want = bool(self.return_rollouts)
+        costs, omega, _, states, acts_out = ctx.amppi_update(state.numpy(), acts, params, shared_params=shared, want_states=want, want_actions=want)
+        t = torch.from_numpy
+        return t(costs), (t(states) if want else None), (t(acts_out) if want else None), t(omega)

@@ -1,0 +1,255 @@
+// amppi.hpp - AMPPI.update_actions (dust/controllers/amppi.py:227-260) in ONE launch: the single-policy information-theoretic MPC of
+// Williams et al. 2017 on the four model families.  S independent trajectories, one softmax, one weighted sum.
+//
+// Phase 1, one LANE per trajectory s (sigma points looped, see below):
+//   acts[s] = a_seq + L z (Philox, common.hpp philox_normal8: block j >> 3 of row s) or the caller's actions; eps[s] = acts[s] - a_seq in
+//   BOTH cases (amppi.py:129; for drawn noise the reference keeps the draw itself, amppi.py:125-126 - taking the difference makes a tick
+//   from returned actions repeat the tick that drew them bit for bit).  Actions are NOT clamped here: the models clamp inside their step.
+//   H steps of the family's own device step (common.hpp model_step, skid.hpp skid_step, cartpole.hpp cartpole_step) with this
+//   trajectory's parameter row: none (the model's values) / row 0 for everybody / row s / every one of the pts = 2P + 1 sigma points.
+//   Costs as amppi.py:193-225: the instantaneous cost on states 1 .. H with NO action (Particle: actions = 0), the terminal cost on
+//   state H; sigma points combine as sum_k w_k (sum_t inst[s, k, t]) and sum_k w_k term[s, k] (amppi.py:208-215: a clean [S, pts] view);
+//   ctrl[s] = lambda sum_t (a_seq[t] a_pre) . eps[s, t] with the full a_pre (amppi.py:221-223); cost = (term + inst) + ctrl.
+// Phase 2, the LAST-ARRIVING workgroup (nobody waits for anybody: nothing can spin):
+//   beta = min costs, omega_s = -(costs_s - beta) / lambda - logsumexp, a_seq = clamp(a_seq + sum_s e^omega_s eps[s], min_a, max_a)
+//   (amppi.py:250-259).  Every sum runs in an order fixed by (S, D) alone, so the result does not depend on who arrived last.
+//
+// Hand-off (per-XCD L2s are not coherent): every lane stores its cost (and its drawn actions) with plain stores, every wave drains
+// vmcnt, workgroup barrier, lane 0 makes an agent-scope release, drains again and takes a ticket with a relaxed agent-scope add on a
+// word that a memset node zeroed ahead of the launch; the workgroup that draws the last ticket makes an agent-scope acquire and reads
+// everything with plain loads.
+//
+// Lane mapping: one lane per TRAJECTORY with the sigma points in a loop, not one lane per (trajectory, point).  The actions of a
+// trajectory then exist once (in HBM / L1: D <= 128 values do not fit registers under a run-time index), the weighted combination of the
+// points is a lane-local sum in a fixed order, and S - not S pts - decides the grid; the price is a serial chain pts times longer in the
+// sigma-point mode, which is the rare one.  256 lanes per workgroup (one wave per SIMD of a CU) is an UNMEASURED choice: lane s reads
+// acts[s * D + t], a stride of D values between neighbouring lanes, so a wave's action load touches up to 64 cache lines per step, and
+// more waves per SIMD - or 64-lane workgroups, which would spread S = 1024 over 16 CUs instead of 4 - may hide that latency better.
+// A transposed [D][S] copy of the actions would coalesce the reads.  Neither alternative has been timed.
+#pragma once
+#include "cartpole.hpp"
+#include "handoff.hpp"
+
+namespace dust {
+
+enum { AMPPI_PARAMS_NONE = 0, AMPPI_PARAMS_SINGLE = 1, AMPPI_PARAMS_EXTENDED = 2, AMPPI_PARAMS_SIGMA = 3 };
+#define AMPPI_THREADS 256
+#define AMPPI_MAX_SAMPLES 65536
+
+struct AmppiArgs {
+  DevModel dm;   // Pendulum / Particle
+  SkidModel sk;  // skid-steer: parameters, wheel-speed bounds, quadratic cost
+  CartModel cp;  // cart-pole: parameters, quadratic cost
+  int S, H, da, D, P, pts;
+  int mode;    // AMPPI_PARAMS_*
+  int philox;  // draw the actions (otherwise `acts` holds the caller's)
+  float lambda, dt;
+  float chol[3];  // cholesky(a_cov): L00, L10, L11
+  float pre[3];   // inverse(a_cov): P00, P01 (= P10), P11
+  float min_a[2], max_a[2];
+  float state[8];
+  uint64_t seed;
+  uint32_t *ctr;        // {tick, iter, ..}: Philox stream position; the reducer advances iter after a drawing tick
+  const float *params;  // [1 | S | pts][P] or nullptr
+  const float *mw;      // [pts] sigma weights (AMPPI_PARAMS_SIGMA)
+  float *acts;          // [S][D]
+  float *a_seq;         // [D] in / out
+  float *costs, *omega;  // [S]
+  float *states_out;     // [S * pts][H + 1][ds] or nullptr
+  unsigned int *ticket;
+};
+
+// sum_k w[k] (x_k - goal_k)^2 as the quadratic family's kernels form it (skid.hpp / cartpole.hpp), without the control term
+template <int DS>
+__device__ __forceinline__ float amppi_quad(const float *x, const float *goal, const float *w) {
+  double sc = 0.0;
+#pragma unroll
+  for (int k = 0; k < DS; ++k) {
+    const float d = x[k] - goal[k];
+    sc += (double)((d * d) * w[k]);
+  }
+  return (float)sc;
+}
+
+template <int MODEL>
+struct AmppiDims {
+  static constexpr int DS = MODEL == DUST_MODEL_PENDULUM ? 2 : (MODEL == DUST_MODEL_SKID_STEER ? 5 : 4);
+};
+
+// One trajectory on one parameter row: -> sum_t inst(x_t), t = 1 .. H, and term(x_H); `so`: its [H + 1][DS] states or nullptr
+template <int MODEL>
+__device__ __forceinline__ void amppi_traj(const AmppiArgs &a, const float *acts, const float *prow, float *so, float *inst_out, float *term_out) {
+  constexpr int DS = AmppiDims<MODEL>::DS;
+  const int H = a.H;
+  float x[DS];
+#pragma unroll
+  for (int k = 0; k < DS; ++k) x[k] = a.state[k];
+  if (so)
+#pragma unroll
+    for (int k = 0; k < DS; ++k) so[k] = x[k];
+  double tot = 0.0;
+  if constexpr (MODEL == DUST_MODEL_PENDULUM || MODEL == DUST_MODEL_PARTICLE) {
+    const Coef c = make_coef(a.dm, prow);
+    const float zero[2] = {0.f, 0.f};  // (Particle.default_inst_cost(states): actions = 0, particle.py:170)
+    for (int t = 0; t < H; ++t) {
+      float u[2];
+      u[0] = acts[t * a.da];
+      u[1] = MODEL == DUST_MODEL_PARTICLE ? acts[t * a.da + 1] : 0.f;
+      model_step<MODEL>(a.dm, c, x, u);
+      tot += (double)inst_cost<MODEL>(a.dm, x, zero);
+      if (so)
+#pragma unroll
+        for (int k = 0; k < DS; ++k) so[(size_t)(t + 1) * DS + k] = x[k];
+    }
+    *term_out = term_cost<MODEL>(a.dm, x);
+  } else if constexpr (MODEL == DUST_MODEL_SKID_STEER) {
+    const float xicr = skid_param(a.sk.x_icr, prow, 0), wr = skid_param(a.sk.wheel_radius, prow, 0), ad = skid_param(a.sk.axial_distance, prow, 0);
+    for (int t = 0; t < H; ++t) {
+      const float a0 = acts[2 * t], a1 = acts[2 * t + 1];
+      skid_step(x, clampf(a0, a.sk.lo[0], a.sk.hi[0]), clampf(a1, a.sk.lo[1], a.sk.hi[1]), xicr, wr, ad, a.dt);
+      tot += (double)amppi_quad<DS>(x, a.sk.goal, a.sk.w_state);
+      if (so)
+#pragma unroll
+        for (int k = 0; k < DS; ++k) so[(size_t)(t + 1) * DS + k] = x[k];
+    }
+    *term_out = amppi_quad<DS>(x, a.sk.goal, a.sk.w_term);
+  } else {
+    const bool have_rows = prow != nullptr;  // (as cartpole.hpp: without rows a parameter named as sampled stays the constructor's Python float)
+    const bool pm_py = (a.cp.par[CP_MP].kind == DUST_PARAM_PYFLOAT || (a.cp.par[CP_MP].kind == DUST_PARAM_SAMPLED && !have_rows)) &&
+                       (a.cp.par[CP_LEN].kind == DUST_PARAM_PYFLOAT || (a.cp.par[CP_LEN].kind == DUST_PARAM_SAMPLED && !have_rows));
+    float v[CP_NPAR];
+#pragma unroll
+    for (int q = 0; q < CP_NPAR; ++q) v[q] = skid_param(a.cp.par[q], prow, 0);
+    const CartCoef kf = cartpole_coef(v, pm_py, a.cp.par[CP_MP].value * a.cp.par[CP_LEN].value, a.dt);
+    for (int t = 0; t < H; ++t) {
+      cartpole_step(x, clampf(acts[t], -1.0f, 1.0f), kf, fast_sinf(x[2]), fast_cosf(x[2]));
+      tot += (double)amppi_quad<DS>(x, a.cp.goal, a.cp.w_state);
+      if (so)
+#pragma unroll
+        for (int k = 0; k < DS; ++k) so[(size_t)(t + 1) * DS + k] = x[k];
+    }
+    *term_out = amppi_quad<DS>(x, a.cp.goal, a.cp.w_term);
+  }
+  *inst_out = (float)tot;
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(AMPPI_THREADS) void amppi_kernel(const AmppiArgs a) {
+  constexpr int DS = AmppiDims<MODEL>::DS;
+  // ONE LDS object: [0] "this workgroup is the reducer", [1, 9) block_reduce's scratch, [9, 13) wave partials, [16, 16 + 256) column partials
+  __shared__ double lds[16 + AMPPI_THREADS];
+  const int tid = (int)threadIdx.x, s = (int)blockIdx.x * AMPPI_THREADS + tid;
+  const int D = a.D, H = a.H, da = a.da, S = a.S;
+
+  if (s < S) {
+    float *acts = a.acts + (size_t)s * D;
+    if (a.philox) {
+      const uint32_t ctr_tick = a.ctr[0], ctr_iter = a.ctr[1];
+      for (int j0 = 0; j0 < D; j0 += 8) {
+        float z[8];
+        philox_normal8(a.seed, (uint32_t)(j0 >> 3), (uint32_t)s, ctr_iter, ctr_tick, z);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const int j = j0 + i;
+          if (j >= D) break;
+          // a_seq + L z: an odd column of a 2 x 2 factor takes its partner draw too (D is even then: pairs never straddle a block)
+          const float lz = (da == 2 && (i & 1)) ? (a.chol[1] * z[i - 1] + a.chol[2] * z[i]) : a.chol[0] * z[i];
+          acts[j] = a.a_seq[j] + lz;
+        }
+      }
+    }
+    double cc = 0.0;
+    for (int t = 0; t < H; ++t) {
+      if (da == 1) {
+        const float e0 = acts[t] - a.a_seq[t];
+        cc += (double)((a.a_seq[t] * a.pre[0]) * e0);
+      } else {
+        const float u0 = a.a_seq[2 * t], u1 = a.a_seq[2 * t + 1];
+        const float e0 = acts[2 * t] - u0, e1 = acts[2 * t + 1] - u1;
+        const float p0 = u0 * a.pre[0] + u1 * a.pre[1], p1 = u0 * a.pre[1] + u1 * a.pre[2];
+        cc += (double)(p0 * e0 + p1 * e1);
+      }
+    }
+    const float ctrl = a.lambda * (float)cc;
+    float inst = 0.f, term = 0.f;
+    if (a.mode == AMPPI_PARAMS_SIGMA) {
+      double wi = 0.0, wt = 0.0;
+      for (int k = 0; k < a.pts; ++k) {
+        float ik, tk;
+        float *so = a.states_out ? a.states_out + ((size_t)s * a.pts + k) * (size_t)(H + 1) * DS : nullptr;
+        amppi_traj<MODEL>(a, acts, a.params + (size_t)k * a.P, so, &ik, &tk);
+        wi += (double)a.mw[k] * (double)ik;
+        wt += (double)a.mw[k] * (double)tk;
+      }
+      inst = (float)wi;
+      term = (float)wt;
+    } else {
+      const float *prow = a.mode == AMPPI_PARAMS_NONE ? nullptr : (a.mode == AMPPI_PARAMS_SINGLE ? a.params : a.params + (size_t)s * a.P);
+      float *so = a.states_out ? a.states_out + (size_t)s * (size_t)(H + 1) * DS : nullptr;
+      amppi_traj<MODEL>(a, acts, prow, so, &inst, &term);
+    }
+    a.costs[s] = (term + inst) + ctrl;  // amppi.py:224
+  }
+
+  // ---- publish, take a ticket
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wg_sync();
+  unsigned int *is_last = reinterpret_cast<unsigned int *>(lds);
+  if (tid == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned int t = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned int last = t + 1u == gridDim.x ? 1u : 0u;
+    if (last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    *is_last = last;
+  }
+  wg_sync();
+  if (*is_last == 0u) return;
+
+  // ---- phase 2: the reducer
+  float *red = reinterpret_cast<float *>(lds + 1);
+  float mn = INFINITY;
+  for (int i = tid; i < S; i += AMPPI_THREADS) mn = fminf(mn, a.costs[i]);
+  const float beta = block_reduce<RED_MIN>(mn, red);
+  const float nil = (float)(-1.0 / (double)a.lambda);  // (-1 / lambda_) is a Python float, amppi.py:251
+  double z = 0.0;
+  for (int i = tid; i < S; i += AMPPI_THREADS) z += (double)expf(nil * (a.costs[i] - beta));
+  z = wave_sum_d(z);
+  wg_sync();
+  if ((tid & 63) == 0) lds[9 + (tid >> 6)] = z;
+  wg_sync();
+  const float eta = (float)log(((lds[9] + lds[10]) + lds[11]) + lds[12]);  // logsumexp: the largest entry of log_costs is 0
+  for (int i = tid; i < S; i += AMPPI_THREADS) a.omega[i] = nil * (a.costs[i] - beta) - eta;
+  // a_seq += tensordot(exp(omega), eps): column j by lane (q, j), q strides the samples; the q partials are added in order
+  const int nq = AMPPI_THREADS / D, q = tid / D, j = tid - q * D;
+  double acc = 0.0;
+  if (q < nq) {
+    const float aj = a.a_seq[j];
+    for (int i = q; i < S; i += nq) {
+      const float w = expf((nil * (a.costs[i] - beta)) - eta);
+      acc += (double)w * (double)(a.acts[(size_t)i * D + j] - aj);
+    }
+  }
+  lds[16 + tid] = acc;
+  wg_sync();
+  if (tid < D) {
+    double sum = 0.0;
+    for (int k = 0; k < nq; ++k) sum += lds[16 + k * D + tid];
+    const int d = da == 2 ? (tid & 1) : 0;
+    a.a_seq[tid] = clampf(a.a_seq[tid] + (float)sum, a.min_a[d], a.max_a[d]);
+  }
+  if (tid == 0 && a.philox) a.ctr[1] += 1u;
+}
+
+// BaseController.roll(steps) (base.py:68-80) for 1 <= steps: shift the sequence left by `steps` rows, zeros behind
+__global__ void amppi_roll_kernel(float *a_seq, const int D, const int shift) {
+  const int j = (int)threadIdx.x;
+  const float v = (j < D && j + shift < D) ? a_seq[j + shift] : 0.f;
+  wg_sync();
+  if (j < D) a_seq[j] = v;
+}
+
+}  // namespace dust

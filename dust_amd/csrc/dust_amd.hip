@@ -37,6 +37,7 @@
 #include "peer_gather.hpp"
 #include "skid.hpp"
 #include "cartpole.hpp"
+#include "amppi.hpp"
 #include "particle_general.hpp"
 #include "rollout.hpp"
 #include "stein.hpp"
@@ -78,7 +79,7 @@ extern "C" int dust_device_count(int *count) {
 }
 
 static const char *k_names[DUST_K_COUNT] = {"rollout_kernel", "pairwise_kernel<PRIOR>", "pairwise_kernel<STEIN>", "update_kernel",
-                                            "forward(finalize+roll)", "bandwidth_kernel", "mpf_kernel", "states_kernel"};
+                                            "forward(finalize+roll)", "bandwidth_kernel", "mpf_kernel", "states_kernel", "amppi_kernel"};
 extern "C" const char *dust_kernel_name(int id) { return (id >= 0 && id < DUST_K_COUNT) ? k_names[id] : ""; }
 
 // peer_gather.hpp: the peers' buffers of the three exchanges (score rows, particles, log-weights) and arrival words, mapped through HIP IPC
@@ -173,6 +174,7 @@ struct dust_ctx {
   float *theta_home, *theta_alt;  // theta ping-pong of the fused Stein+update launch (theta == one of the two)
   bool theta_pinned;              // dust_gather_buffers handed theta's address out: no ping-pong any more
   const float *graph_theta;       // theta at the start of the captured tick
+  unsigned int *amppi_ticket;  // dust_amppi_update: the arrival word of its workgroups (zeroed by a memset node ahead of every launch)
   unsigned int *stein_cnt;  // [tiles + 1]: arrival counters of the Stein+update launch (re-armed by the next rollout launch)
   int stein_tiles;
   bool stein_dirty;
@@ -527,6 +529,7 @@ static void free_all(dust_ctx *c) {
   if (c->ctr_dev) (void)hipFree(c->ctr_dev);
   if (c->fused_cnt) (void)hipFree(c->fused_cnt);
   if (c->stein_cnt) (void)hipFree(c->stein_cnt);
+  if (c->amppi_ticket) (void)hipFree(c->amppi_ticket);
   if (c->iter_cnt) (void)hipFree(c->iter_cnt);
   if (c->score_hs) (void)hipFree(c->score_hs);
   if (c->t2_cnt) (void)hipFree(c->t2_cnt);
@@ -1250,6 +1253,125 @@ extern "C" int dust_set_a_seq(dust_ctx *c, const float *a) {
 extern "C" int dust_get_a_seq(dust_ctx *c, float *a) {
   if (!c || !a) return fail(DUST_ERR_INVALID, "null argument");
   return d2h(c, a, c->a_seq, c->D * sizeof(float));
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// AMPPI (dust/controllers/amppi.py): one launch per update_actions (amppi.hpp)
+static int amppi_check(const dust_ctx *c) {
+  if (c->N != 1) return fail(DUST_ERR_INVALID, "an AMPPI context has n_policies = 1 (got %d)", c->N);
+  if (c->S > AMPPI_MAX_SAMPLES) return fail(DUST_ERR_UNSUPPORTED, "n_samples = %d > %d: the AMPPI tick's reducer is one workgroup", c->S, AMPPI_MAX_SAMPLES);
+  if (c->D > 128) return fail(DUST_ERR_UNSUPPORTED, "H*da = %d > 128 not supported by the kernels", c->D);
+  if (c->cfg.dim_p > 4) return fail(DUST_ERR_UNSUPPORTED, "dim_p = %d > 4 uncertain parameters", c->cfg.dim_p);
+  if (c->nloc != c->N || comm_active(c)) return fail(DUST_ERR_UNSUPPORTED, "an AMPPI tick is not sharded over GPUs");
+  if (c->cfg.params_log_space) return fail(DUST_ERR_UNSUPPORTED, "AMPPI has no params_log_space (amppi.py:134-139 hands the samples to the model as drawn)");
+  if (c->cfg.model == DUST_MODEL_PARTICLE && (c->cfg.control_type != DUST_CONTROL_ACCELERATION || particle_general(c)))
+    return fail(DUST_ERR_UNSUPPORTED, "the AMPPI tick runs Particle with acceleration control and no control-channel noise");
+  return DUST_OK;
+}
+
+extern "C" int dust_amppi_update(dust_ctx *c, const float *state, const float *actions, const float *params, int flags,
+                                 float *costs, float *omega, float *a_seq) {
+  if (!c || !state) return fail(DUST_ERR_INVALID, "null argument");
+  TRY(amppi_check(c));
+  if (flags & (DUST_EPS_F16 | DUST_STORE_F16)) return fail(DUST_ERR_UNSUPPORTED, "the AMPPI tick has no binary16 storage");
+  const int S = c->S, D = c->D, P = c->cfg.dim_p;
+  int mode = AMPPI_PARAMS_NONE, pts = 1;
+  size_t prows = 0;
+  if (c->mw_dev) {
+    if (!params) return fail(DUST_ERR_INVALID, "sigma-point weights are set: pass the [2P + 1][P] sigma points");
+    if (P < 1 || c->M != 2 * P + 1) return fail(DUST_ERR_INVALID, "sigma points of %d parameters are n_params = %d rows, the context has %d", P, 2 * P + 1, c->M);
+    mode = AMPPI_PARAMS_SIGMA;
+    prows = (size_t)(pts = c->M);
+  } else if (c->M != 1) {
+    return fail(DUST_ERR_INVALID, "n_params = %d > 1 is the sigma-point form of an AMPPI context: dust_set_param_weights first", c->M);
+  } else if (params) {
+    if (P < 1) return fail(DUST_ERR_INVALID, "parameter rows without uncertain parameters (dim_p = 0)");
+    mode = (flags & DUST_AMPPI_PARAMS_SHARED) ? AMPPI_PARAMS_SINGLE : AMPPI_PARAMS_EXTENDED;
+    prows = mode == AMPPI_PARAMS_SINGLE ? 1 : (size_t)S;
+  }
+  TRY(settle_pending(c));
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  if (!c->amppi_ticket) TRY(dalloc(&c->amppi_ticket, (size_t)1));
+  TRY(ensure(&c->actions, &c->actions_cap, (size_t)S * D));
+  if (actions) {
+    if (flags & DUST_PTR_DEVICE) TRY(d2d(c, c->actions, actions, (size_t)S * D * sizeof(float)));
+    else TRY(h2d(c, c->actions, actions, (size_t)S * D * sizeof(float)));
+  }
+  if (prows) {
+    TRY(ensure(&c->params_dev, &c->params_cap, prows * P));
+    TRY(h2d(c, c->params_dev, params, prows * P * sizeof(float)));
+  }
+  const bool want_states = (flags & DUST_STORE_STATES) != 0;
+  if (want_states) TRY(ensure(&c->states, &c->states_cap, (size_t)S * pts * (c->H + 1) * c->ds));
+  AmppiArgs a;
+  memset(&a, 0, sizeof a);
+  a.dm = make_dev_model(c);
+  a.dm.log_space = 0;
+  a.sk = c->skid;
+  a.cp = c->cart;
+  a.S = S;
+  a.H = c->H;
+  a.da = c->da;
+  a.D = D;
+  a.P = P;
+  a.pts = pts;
+  a.mode = mode;
+  a.philox = actions ? 0 : 1;
+  a.lambda = c->cfg.temperature;
+  a.dt = (float)c->cfg.dt;
+  a.chol[0] = c->cfg.chol_a[0];
+  a.chol[1] = c->da == 2 ? c->cfg.chol_a_off : 0.f;
+  a.chol[2] = c->da == 2 ? c->cfg.chol_a[1] : 0.f;
+  a.pre[0] = c->cfg.a_pre[0];
+  a.pre[1] = c->da == 2 ? c->cfg.a_pre_off : 0.f;
+  a.pre[2] = c->da == 2 ? c->cfg.a_pre[1] : 0.f;
+  for (int d = 0; d < 2; ++d) {
+    a.min_a[d] = c->cfg.min_a[d];
+    a.max_a[d] = c->cfg.max_a[d];
+  }
+  for (int k = 0; k < 8; ++k) a.state[k] = k < c->ds ? state[k] : 0.f;  // (a kernel ARGUMENT: no copy, no launch of its own)
+  a.seed = c->cfg.seed;
+  a.ctr = c->ctr_dev;
+  a.params = prows ? c->params_dev : nullptr;
+  a.mw = c->mw_dev;
+  a.acts = c->actions;
+  a.a_seq = c->a_seq;
+  a.costs = c->costsT;  // ([N][S] with N = 1)
+  a.omega = c->omegaT;
+  a.states_out = want_states ? c->states : nullptr;
+  a.ticket = c->amppi_ticket;
+  const int grid = (S + AMPPI_THREADS - 1) / AMPPI_THREADS;
+  HIP_TRY(hipMemsetAsync(c->amppi_ticket, 0, sizeof(unsigned int), c->stream));
+  {
+    Prof pr(c, DUST_K_AMPPI);
+    switch (c->cfg.model) {
+      case DUST_MODEL_PENDULUM: amppi_kernel<DUST_MODEL_PENDULUM><<<grid, AMPPI_THREADS, 0, c->stream>>>(a); break;
+      case DUST_MODEL_PARTICLE: amppi_kernel<DUST_MODEL_PARTICLE><<<grid, AMPPI_THREADS, 0, c->stream>>>(a); break;
+      case DUST_MODEL_SKID_STEER: amppi_kernel<DUST_MODEL_SKID_STEER><<<grid, AMPPI_THREADS, 0, c->stream>>>(a); break;
+      default: amppi_kernel<DUST_MODEL_CARTPOLE><<<grid, AMPPI_THREADS, 0, c->stream>>>(a); break;
+    }
+    HIP_TRY(hipGetLastError());
+  }
+  c->have_sample = true;
+  c->actions_valid = true;
+  c->actions_f16 = false;
+  c->states_valid = want_states;
+  c->states_f16 = false;
+  if (costs) TRY(d2h(c, costs, c->costsT, (size_t)S * sizeof(float)));
+  if (omega) TRY(d2h(c, omega, c->omegaT, (size_t)S * sizeof(float)));
+  if (a_seq) TRY(d2h(c, a_seq, c->a_seq, (size_t)D * sizeof(float)));
+  return DUST_OK;
+}
+
+extern "C" int dust_amppi_roll(dust_ctx *c, int steps) {
+  if (!c) return fail(DUST_ERR_INVALID, "null ctx");
+  if (steps < 1) return fail(DUST_ERR_INVALID, "roll(steps = %d): steps >= 1", steps);
+  TRY(settle_pending(c));
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  const long shift = (long)steps * c->da;
+  amppi_roll_kernel<<<1, 128, 0, c->stream>>>(c->a_seq, c->D, shift > c->D ? c->D : (int)shift);
+  HIP_TRY(hipGetLastError());
+  return DUST_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------

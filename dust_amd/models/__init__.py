@@ -18,6 +18,9 @@ class BaseModel:
         self._dt = dt
         self._params_dict = dict(params_dict or {})
         self._params_keys = uncertain_params
+        # the distribution over the uncertain parameters: the reference's users assign it on the instance (sample_params, base.py:163,
+        # and AMPPI's sigma points, amppi.py:164-170, read it)
+        self.params_dist = None
 
     @property
     def dt(self):
@@ -40,6 +43,30 @@ class BaseModel:
 
     def dict_to_params(self, params_dict):  # base.py:179-183
         return torch.cat([params_dict[key] for key in self._params_keys], dim=1)
+
+    # AMPPI._sample_sigma_trajectories calls `model.to_params_dict` (amppi.py:182), which the reference never defines: the method it
+    # meant is params_to_dict
+    to_params_dict = params_to_dict
+
+    def rejection_sampling(self, num_samples, x_min=-float("inf"), x_max=float("inf")):
+        """base.py:102-147: draws from `params_dist` until num_samples rows lie inside (x_min, x_max) in every column.
+        -> ([num_samples, P] samples, number of draws)"""
+        dim_params = len(self._params_keys)
+        samples, n_accepts, n_attempts = torch.zeros(0, dim_params), 0, 0
+        while n_accepts < num_samples:
+            draw = self.params_dist.sample([num_samples - n_accepts]).reshape(-1, dim_params)
+            keep = ((x_min < draw) & (x_max > draw)).all(dim=1)
+            samples = torch.cat((samples, draw[keep].to(samples.dtype)), 0)
+            n_accepts = samples.shape[0]
+            n_attempts += 1
+        return samples.reshape(num_samples, dim_params), n_attempts
+
+    def sample_params(self, num_samples, x_min=-float("inf"), x_max=float("inf")):
+        """base.py:149-171: a dict of [num_samples, 1] columns, one per uncertain parameter."""
+        assert self.params_dist is not None, "No sampling distribution specified"
+        assert num_samples > 0, "Need at least one sample."
+        samples, _ = self.rejection_sampling(num_samples, x_min=x_min, x_max=x_max)
+        return {key: samples[:, idx].reshape(-1, 1) for (idx, key) in enumerate(self._params_keys)}
 
     def _merged(self, params_dict):
         if params_dict is None:

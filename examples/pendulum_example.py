@@ -11,6 +11,7 @@ a PendulumModel with the episode's true (length, mass) and gym's g = 10.  `--con
 keys (demo/pendulum_config.yaml); the defaults below are that file's values.
 
     python examples/pendulum_example.py --steps 50 --case dual
+    python examples/pendulum_example.py --steps 50 --case amppi
 """
 import argparse
 import copy
@@ -51,7 +52,7 @@ def main():
     ap.add_argument("--config", default=None)
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--particles", type=int, default=None)
-    ap.add_argument("--case", choices=["dual", "svmpc", "mppi", "disco"], default="dual")
+    ap.add_argument("--case", choices=["dual", "svmpc", "mppi", "disco", "amppi"], default="dual")
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
     cfg = copy.deepcopy(DEFAULTS)
@@ -75,6 +76,32 @@ def main():
     dynamics_prior = dist.Independent(dist.Uniform(torch.tensor([0.6, 0.6]), torch.tensor([1.3, 1.3])), 1)
     true_params = dynamics_prior.sample()
 
+    if args.case == "amppi":
+        # the reference's single-policy IT-MPC (dust/controllers/amppi.py): one launch per tick - S trajectories with their own
+        # (length, mass) draw each, one softmax, one weighted sum - then the first action to the plant and roll(1).  lambda_ = 100:
+        # the pendulum's costs run into the hundreds, and at lambda_ = 1 / alpha = 1 one trajectory would take every weight
+        from dust_amd.controllers import AMPPI
+
+        model = PendulumModel(length=float(dynamics_prior.mean[0]), mass=float(dynamics_prior.mean[1]), uncertain_params=("length", "mass"))
+        model.params_dist = dynamics_prior
+        controller = AMPPI(env_model.observation_space, env_model.action_space, hz_len=H, n_samples=S, lambda_=100.0,
+                           a_cov=e["ctrl_sigma"] ** 2 * torch.eye(e["ctrl_dim"]), inst_cost_fn=inst_cost, term_cost_fn=term_cost,
+                           params_sampling="extended", seed=args.seed)
+        controller.return_rollouts = False
+        plant = PendulumModel(g=10.0, length=float(true_params[0]), mass=float(true_params[1]))
+        state, total_cost, t0 = init_state.unsqueeze(0), 0.0, time.perf_counter()
+        for step in range(steps):
+            controller.update_actions(model, state.view(-1))
+            action = controller.a_seq[0]
+            state = plant.step(state, action.view(1, 1))
+            controller.roll(1)
+            total_cost += float(inst_cost(state.view(1, -1)))
+            if step % 20 == 0:
+                print("step %3d  theta %+.3f  theta_dot %+.3f  action %+.2f" % (step, float(state[0, 0]), float(state[0, 1]), float(action)))
+        el = time.perf_counter() - t0
+        print("amppi: %d ticks, avg cost %.2f, %.1f ticks/s incl. host plumbing (true length %.2f mass %.2f)"
+              % (steps, total_cost / steps, steps / el, float(true_params[0]), float(true_params[1])))
+        return
     if args.case in ("mppi", "disco"):
         # the reference's "MPPI Baseline" / "DISCO" cases (pendulum_example.py:217-261): one policy, no SVGD; DISCO rolls the
         # sigma points of the dynamics prior out (unscented transform, yaml utf block: n = 2, alpha = 0.5)

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define DUST_ABI_VERSION 2
+#define DUST_ABI_VERSION 3
 
 enum dust_status {
   DUST_OK = 0,
@@ -72,7 +72,9 @@ enum dust_flags {
    * device) - the rollout kernel's HBM read traffic halves.  DUST_STORE_F16: the stored `states` / `actions_out` are binary16
    * (the caller's output buffers receive binary16 values, half the bytes; 5.5 GB instead of 11 GB of states at config 3). */
   DUST_EPS_F16 = 8,
-  DUST_STORE_F16 = 16
+  DUST_STORE_F16 = 16,
+  /* ABI 3, dust_amppi_update: `params` is ONE row that every trajectory uses (AMPPI(params_sampling="single"), amppi.py:91-93) */
+  DUST_AMPPI_PARAMS_SHARED = 32
 };
 
 typedef struct dust_param {
@@ -311,6 +313,39 @@ int dust_svmpc_tick(dust_ctx *ctx, const float *state, int n_steps, const float 
 int dust_svmpc_serve_start(dust_ctx *ctx, int n_steps, double wait_us);
 int dust_svmpc_serve_stop(dust_ctx *ctx);
 
+/* ---- AMPPI (dust/controllers/amppi.py): the single-policy information-theoretic MPC of Williams et al. 2017, ABI 3 ----
+ * An AMPPI controller is a context created with n_policies = 1: n_samples = S trajectories, temperature = lambda_ (amppi.py:79),
+ * chol_a / chol_a_off and a_pre / a_pre_off the factors of a_cov (amppi.py:83-86; a full 2 x 2 a_cov: full_cov = 1), min_a / max_a the
+ * action space, seed the Philox key of device-drawn noise.  dust_set_a_seq / dust_get_a_seq hold BaseController.a_seq (base.py:34-37),
+ * dust_set_grid / dust_set_skid_steer / dust_set_cartpole / dust_set_model_param describe the model as for any context, dust_clone is
+ * copy.deepcopy(controller), and dust_profile_* counts the tick's kernel as DUST_K_AMPPI.  The cost families are the context's, with
+ * the instantaneous cost ACTION-FREE (amppi.py:205 hands it states only: Particle's runs with actions = 0, the quadratic family's
+ * control weights must be zero) and on states 1 .. H, so that state H takes the instantaneous and the terminal cost (amppi.py:205-207).
+ *
+ * dust_amppi_update = AMPPI.update_actions(model, state, actions) amppi.py:227-260 in ONE kernel launch (dust_amd/csrc/amppi.hpp):
+ *   actions [S][H][da] (NULL: a_seq + L z drawn on the device, amppi.py:123-126; host pointer, or device with DUST_PTR_DEVICE); they are
+ *     not clamped - the models clamp inside their step - and eps = actions - a_seq (amppi.py:129).  DUST_PTR_DEVICE speaks of `actions`
+ *     alone: `state` and `params` are ALWAYS host pointers;
+ *   params selects AMPPI(params_sampling=) amppi.py:88-104:
+ *     NULL                                         "none": the model's own values (amppi.py:137);
+ *     [1][P] with DUST_AMPPI_PARAMS_SHARED         "single": one row for every trajectory;
+ *     [S][P]                                       "extended": row s for trajectory s (amppi.py:134-139);
+ *     [2P + 1][P] after dust_set_param_weights     a MerweScaledUTF: every trajectory rolls all sigma points with the same actions and
+ *                                                  their costs combine with the weights (amppi.py:142-191, 208-215); the context was
+ *                                                  created with n_params = 2P + 1;
+ *   outputs, each may be NULL: costs [S] (amppi.py:224), omega [S] (amppi.py:255), a_seq [H][da] AFTER the update (amppi.py:256-259).
+ *   With DUST_STORE_STATES the trajectories stay on the device for dust_get_states_rows, row s * pts + k = trajectory s, sigma point k
+ *   (the reference's [S pts][H + 1][ds], amppi.py:183-190; pts = 1 without a transform); dust_get_actions gives `acts` [S][H][da] and
+ *   dust_get_costs the costs again.
+ * DUST_ERR_UNSUPPORTED: S > 65536, H * da > 128 (dust_create), dim_p > 4, sharded contexts, params_log_space, binary16 storage,
+ * Particle with velocity control or control-channel noise.  DUST_ERR_INVALID: n_policies != 1, params without uncertain parameters,
+ * sigma weights without params or with n_params != 2 dim_p + 1, n_params > 1 without sigma weights (dim_p > 4: dust_create). */
+int dust_amppi_update(dust_ctx *ctx, const float *state, const float *actions, const float *params, int flags,
+                      float *costs, float *omega, float *a_seq);
+/* BaseController.roll(steps) base.py:68-80: a_seq moves `steps` rows towards the front, the rows behind it are zeros.  steps >= 1
+ * (the reference's slice arithmetic gives steps = 0 an all-zero sequence and negative steps a mixture: DUST_ERR_INVALID here). */
+int dust_amppi_roll(dust_ctx *ctx, int steps);
+
 /* stage outputs of the last call, for parity tests ([S][N] / [N][H][da] / [N]) */
 int dust_get_costs(dust_ctx *ctx, float *costs);
 int dust_get_actions(dust_ctx *ctx, float *actions);
@@ -376,7 +411,7 @@ int dust_set_stream(dust_ctx *ctx, void *hip_stream);
 /* timing / roofline support: HIP-event timing of each kernel family on the context's stream */
 enum dust_kernel_id {
   DUST_K_ROLLOUT = 0, DUST_K_PRIOR_SCORE = 1, DUST_K_STEIN = 2, DUST_K_UPDATE = 3, DUST_K_FORWARD = 4, DUST_K_BANDWIDTH = 5,
-  DUST_K_MPF = 6, DUST_K_ROLLOUT_STATES = 7 /* whole-line stored-states rollouts */, DUST_K_COUNT = 8
+  DUST_K_MPF = 6, DUST_K_ROLLOUT_STATES = 7 /* whole-line stored-states rollouts */, DUST_K_AMPPI = 8 /* dust_amppi_update */, DUST_K_COUNT = 9
 };
 int dust_profile_enable(dust_ctx *ctx, int on);
 int dust_profile_get(dust_ctx *ctx, int kernel_id, double *total_ms, int64_t *launches);
