@@ -1810,6 +1810,9 @@ static int launch_rollout(dust_ctx *c, const SampleOpts &o_in) {
     o.costs_in = c->costs_stage;
     o.costs_own = true;
     TRY(rollout_args(c, o, a, &nt, &lds));
+    // skid.hpp and cartpole.hpp write state costs: pass 2 adds the control-regularisation term to them (rollout.hpp, costs_own);
+    // particle_general.hpp has added it itself (the whole-line forms do not run with a_reg != 0)
+    if (fp.kind == FP_PARTGEN) a.a_reg = 0.0f;
   } else if (ctrl_noise_inline(c, o, a)) {
     a.ctrl_noise = 1;
     a.dyn_std[0] = c->cfg.dyn_std[0];

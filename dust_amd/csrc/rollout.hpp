@@ -78,7 +78,8 @@ struct RolloutArgs {
   float *costsT;        // [N_total][S]
   const float *costs_in; // [S][N_total] or nullptr: stage-wise mode (SVMPC.phi with a user log_p): skip the rollouts
   int costs_own;         // costs_in holds THIS sample's costs (a first pass of the same call rolled them out: rollout_states.hpp,
-                         // skid.hpp): the likelihood record (logl, eta) is refreshed as after a one-pass sample
+                         // skid.hpp): the likelihood record (logl, eta) is refreshed as after a one-pass sample, and with a_reg != 0 the
+                         // control-regularisation term is added to them (the host clears a_reg when the first pass has added it)
   float *grad_lik;      // [N_total][D]
   float *grad_pri;      // [N_total][D] (merge_prior)
   float *score;         // [N_total][D] (merge_prior)
@@ -325,7 +326,13 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs &a, float *lds, c
     const int s = live ? s_raw : S - 1;
     float *act = tile + s * Dp;
     if (f_costs_in) {
-      if (mg == 0 && live) cst[s] = f_costs_in[(size_t)s * N + n];
+      if (mg == 0 && live) {
+        const float c_in = f_costs_in[(size_t)s * N + n];
+        // a first pass of this call rolled the costs out (skid.hpp, cartpole.hpp): they are state costs, and the control-regularisation
+        // term joins them here, where the action tile is - the record behind get_costs takes the sum.  A caller's costs stay as they are.
+        if (a.costs_own && f_a_reg != 0.0f) finish_cost(s, (double)c_in, true);
+        else cst[s] = c_in;
+      }
       continue;
     }
     double acc_m = 0.0, ut_term = 0.0;

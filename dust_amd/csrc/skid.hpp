@@ -39,7 +39,7 @@ struct SkidArgs {
   const float *state;   // [5]
   const float *params;  // [M][P] raw samples or nullptr
   float *costs_sn;      // [S][N]
-  float *costsT;        // [N][S] the context's cost record (the regular kernel does not write it in its injected-costs mode)
+  float *costsT;        // [N][S] the context's cost record (the regular kernel rewrites it in its injected-costs mode only when it adds the a_reg term)
   float *states_out;    // [M][S][N][H+1][5] or nullptr
   float *actions_out;   // [S][N][D] or nullptr
   const float *mw;      // [M] unscented-transform weights (params: the M sigma points) or nullptr: plain mean over m (last: the other offsets stay)

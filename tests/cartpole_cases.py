@@ -5,7 +5,8 @@ mpf_cartpole_*.npz.  Data and seeded numpy only: nothing here imports the refere
 Controller scenarios (ROLLOUTS, TICKS) are dicts:
   tag, N, S, H, M, up (uncertain parameter names, in column order; () = nominal), dist ("uniform" / "lognormal" / "scalar" / None) with
   lo / hi or loc / scale per column, log (params_log_space), fixed (the seven constructor values), off: what costs_off ignores
-  ("clamp" / "mass" / "mu_c" / "mu_p" / "interleave"), seed; TICKS add kernel ("K1" / "K2"), opt ("SGD" / "Adam"), lr, alpha.
+  ("clamp" / "mass" / "mu_c" / "mu_p" / "interleave" / "areg"), seed, optionally ctrl_penalty (1.0) and a_seq (a non-zero a_seq0 is set on the
+  controller); TICKS add kernel ("K1" / "K2"), opt ("SGD" / "Adam"), lr, alpha.
 Filter scenarios (SCENARIOS, sweep_scenario) follow tests/mpf_skid_cases.py:
   tag, up, Mp, log, bw, lr, n, obs0 / action (past state and the push applied to it), fixed, dt, opt, seed, obs_std, spread, off: what
   phi0_off ignores (see make_golden_mpf_cartpole.py).
@@ -48,6 +49,9 @@ ROLLOUTS = [
     R("ragged", 37, 9, 31, 2, ("mu_c", "f_mag"), "uniform", "mu_c", 34, fixed=FRICTION, lo=(0.03, 8.0), hi=(0.08, 12.0)),
     # a scalar-event params_dist: rollout r uses params[r % M] (disco.py:177-179); N S = 77 is no multiple of M = 3
     R("scalar", 7, 11, 10, 3, ("length",), "scalar", "interleave", 35, loc=(1.0,), scale=(0.15,)),
+    # ctrl_penalty != 1: the control-regularisation term of disco.py:338-346, around a non-zero a_seq0 (otherwise `params`)
+    R("areg", 6, 16, 10, 3, ("mass_cart", "mass_pole", "length"), "uniform", "areg", 36, lo=(0.8, 0.08, 0.8), hi=(1.3, 0.14, 1.2), ctrl_penalty=0.6,
+      a_seq=True),
 ]
 ROLLOUT_NAMES = [s["tag"] for s in ROLLOUTS]
 ROLLOUT_BY_TAG = {s["tag"]: s for s in ROLLOUTS}
@@ -77,6 +81,9 @@ TICKS = [
       alpha=0.25),
     R("tick_k1_adam", 8, 16, 12, 3, ("mu_c", "f_mag"), "uniform", "mu_c", 43, fixed=FRICTION, lo=(0.03, 8.0), hi=(0.08, 12.0), kernel="K1", opt="Adam",
       lr=0.01, alpha=0.25),
+    # tick_k1_sgd with ctrl_penalty != 1: every iteration's costs carry the term, through the a_mat the iteration before left
+    R("tick_areg", 8, 16, 12, 3, ("mass_pole", "length"), "uniform", "areg", 44, lo=(0.08, 0.8), hi=(0.14, 1.2), kernel="K1", opt="SGD", lr=0.05,
+      alpha=0.25, ctrl_penalty=0.6),
 ]
 TICK_NAMES = [s["tag"] for s in TICKS]
 TICK_BY_TAG = {s["tag"]: s for s in TICKS}
@@ -87,7 +94,7 @@ TICK_QUANT = ("costs", "score", "phi", "theta_after", "log_l", "log_p", "p_weigh
 def controller_kwargs(s, **kw):
     """Context keywords of a controller scenario"""
     d = dict(model="cartpole", N=s["N"], S=s["S"], M=s["M"], H=s["H"], dt=DT, sigma_a=SIGMA_A, sigma_p=SIGMA_A, temperature=TEMPERATURE,
-             alpha=1.0 / TEMPERATURE, uncertain_params=s["up"] or None, params_log_space=s["log"], params_scalar_event=s["dist"] == "scalar",
+             alpha=1.0 / TEMPERATURE, ctrl_penalty=s.get("ctrl_penalty", 1.0), uncertain_params=s["up"] or None, params_log_space=s["log"], params_scalar_event=s["dist"] == "scalar",
              goal=GOAL, w_quad_state=W_STATE, w_quad_term=W_TERM, w_quad_ctrl=W_CTRL, **s["fixed"])
     d.update(kw)
     return d

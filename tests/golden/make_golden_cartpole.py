@@ -86,7 +86,8 @@ def draw_params(s, rng, n):
 
 
 def controller(s, model, cost):
-    return mg.MultiDISCO(model.observation_space, model.action_space, s["H"], s["N"], s["S"], temperature=cases.TEMPERATURE, ctrl_penalty=1.0,
+    return mg.MultiDISCO(model.observation_space, model.action_space, s["H"], s["N"], s["S"], temperature=cases.TEMPERATURE,
+                         ctrl_penalty=s.get("ctrl_penalty", 1.0),
                          a_cov=cases.SIGMA_A ** 2 * torch.eye(1), inst_cost_fn=cost.inst, term_cost_fn=cost.term, params_sampling=bool(s["up"]),
                          params_samples=s["M"], params_log_space=s["log"])
 
@@ -109,6 +110,8 @@ def rollout_inputs(s):
     p = draw_params(s, rng, 1)
     if p is not None:
         inp["params"] = p[0]
+    # (a generator of its own: the draws above are those of the fixtures made before scenarios carried an a_seq0)
+    inp["a_seq0"] = (0.3 * np.random.default_rng(7000 + s["seed"]).standard_normal((H, 1)) if s.get("a_seq") else np.zeros((H, 1))).astype(np.float32)
     return inp
 
 
@@ -118,6 +121,7 @@ def ref_forward(s, inp, dt=torch.float32):
         model, cost = ref_model(s["fixed"], s["up"]), QuadCost()
         ctrl = controller(s, model, cost)
         ctrl.a_mat = t(inp["a_mat0"]).clone()  # (forward updates it in place)
+        ctrl.a_seq = t(inp["a_seq0"]).clone()
         pd = pdist_of(s, [inp["params"]] if "params" in inp else None, t)
         with torch.no_grad():
             costs, states, actions, omega, _ = ctrl.forward(t(inp["state"]), model, pd, ext_actions=t(inp["ext_actions"]))
@@ -126,6 +130,8 @@ def ref_forward(s, inp, dt=torch.float32):
 
 def restated(s, inp, off=None):
     """MultiDISCO._rollout + _compute_cost over CartPoleModel.step in fp32 torch, operation by operation; `off` ignores one thing.
+    With ctrl_penalty != 1 the costs carry the control-regularisation term (disco.py:338-346) through inp["a_mat0"], the a_mat the call
+    sees, and inp["a_seq0"] (absent: zeros); off = "areg" leaves it out.
     -> dict(costs [S, N], states [M, S, N, H + 1, 4])"""
     N, S, H, M = s["N"], s["S"], s["H"], s["M"]
     f = torch.from_numpy
@@ -160,7 +166,13 @@ def restated(s, inp, off=None):
         x = x + torch.cat([x_d, x_dd, th_d, th_dd], dim=1) * cases.DT
         traj.append(x)
     # (the reference sums the H instantaneous costs of a rollout in one .sum(-1); accumulated here step by step - equal within an ulp)
-    return dict(costs=mg.npf((tot + cost.term(x)).view(M, S, N).mean(0)), states=mg.npf(torch.stack(traj, 1).view(M, S, N, H + 1, 4)))
+    costs = (tot + cost.term(x)).view(M, S, N).mean(0)
+    a_reg = cases.TEMPERATURE * (1 - s.get("ctrl_penalty", 1.0))
+    if a_reg != 0 and off != "areg":
+        e = torch.add(f(inp["ext_actions"]), -(f(inp["a_seq0"]) if "a_seq0" in inp else torch.zeros(H, 1)))
+        a_pre = torch.inverse(cases.SIGMA_A ** 2 * torch.eye(1))
+        costs = costs + (a_reg * torch.tensordot(-e, f(inp["a_mat0"]) @ a_pre, dims=([-2, -1], [-2, -1]))).diagonal(dim1=-2, dim2=-1)
+    return dict(costs=mg.npf(costs), states=mg.npf(torch.stack(traj, 1).view(M, S, N, H + 1, 4)))
 
 
 def tolerances(runs, quant, g, per_slice=()):
@@ -193,9 +205,9 @@ def moved(inp, seed, keys):
 def run_rollout(s, write=True):
     inp = rollout_inputs(s)
     r32 = ref_forward(s, inp)
-    rp = ref_forward(s, moved(inp, 2000 + s["seed"], ("state", "a_mat0", "ext_actions", "params")))
+    rp = ref_forward(s, moved(inp, 2000 + s["seed"], ("state", "a_mat0", "ext_actions", "params") + (("a_seq0",) if s.get("a_seq") else ())))
     r64 = ref_forward(s, inp, torch.float64)
-    g = dict(N=s["N"], S=s["S"], H=s["H"], M=s["M"], uncertain=",".join(s["up"]), off=s["off"], a_seq0=np.zeros((s["H"], 1), np.float32),
+    g = dict(N=s["N"], S=s["S"], H=s["H"], M=s["M"], uncertain=",".join(s["up"]), off=s["off"],
              clamped_fraction=np.float32((np.abs(inp["ext_actions"]) > 1).mean()), **inp)
     bad, row = tolerances((r32, rp, r64), cases.ROLLOUT_QUANT, g)
     # storage (the file's size): the float64 twin of the states as its scaled difference from the fp32 states in binary16, which
@@ -306,7 +318,8 @@ def run_tick(s, write=True):
     srt = np.sort(r32["p_weights"])
     assert srt[-1] > 1.05 * srt[-2], "the top weight is not separated: choose another seed"
     # power: the last iteration's costs with one thing ignored
-    last = dict(state=inp["state"], ext_actions=r32["actions"][-1], params=inp["params"][-1])
+    K = cases.TICK_ITERS
+    last = dict(state=inp["state"], ext_actions=r32["actions"][-1], params=inp["params"][-1], a_mat0=r32["a_mat"][K - 2] if K > 1 else inp["theta0"])
     on = restated(s, last)["costs"]
     assert elemerr(on, g["costs"][-1]) < 2e-7, elemerr(on, g["costs"][-1])
     g["costs_off"] = restated(s, last, s["off"])["costs"]

@@ -43,6 +43,7 @@ def test_rollout_family_vs_reference(golden, name, mode):
     states, omega, the a_mat update, a_mix - from recorded actions, and the costs from recorded eps (actions = theta + L eps, bit for bit)."""
     g, s = golden("cartpole_" + name), ROLLOUT_BY_TAG[name]
     c = _ctx(s)
+    c.set_a_seq(g["a_seq0"])
     params = g["params"] if s["up"] else None
     if mode == "actions":
         c.set_a_mat(g["a_mat0"])
