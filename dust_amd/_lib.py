@@ -107,6 +107,7 @@ SYMBOLS = {
     "dust_set_param_weights": (C.c_int, [VP, FP]),
     "dust_set_sigma_scale": (C.c_int, [VP, C.c_float]),
     "dust_set_grid": (C.c_int, [VP, FP, C.c_int, C.c_int, C.c_float, C.c_float]),
+    "dust_set_obstacle_cost": (C.c_int, [VP, C.c_float]),
     "dust_set_ctrl_noise": (C.c_int, [VP, FP, C.c_int]),
     "dust_mpf_set_ctrl_noise": (C.c_int, [VP, FP, C.c_int]),
     "dust_set_theta": (C.c_int, [VP, FP]),

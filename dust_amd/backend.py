@@ -173,6 +173,8 @@ class Context:
         skid_kw = {k: kw.pop(k) for k in ("x_icr", "wheel_radius", "axial_distance", "goal", "w_quad_state", "w_quad_term", "w_quad_ctrl")
                    if k in kw}
         cart_kw = {k: kw[k] for k in CARTPOLE_PARAMS if k in kw} if kw.get("model") == "cartpole" else {}
+        # skid-steer: w_obs is the navigation family's obstacle weight (dust_set_obstacle_cost), not Particle's dust_config field
+        nav_w_obs = kw.pop("w_obs", None) if kw.get("model") == "skid_steer" else None
         if _handle is not None:
             self._h = _handle
         else:
@@ -197,6 +199,8 @@ class Context:
             self.set_grid(grid)
         if _handle is None and got.model == L.MODEL_SKID_STEER:
             self.set_skid_steer(uncertain_params=kw.get("uncertain_params"), sampling=kw.get("sampling"), **skid_kw)
+            if nav_w_obs is not None:
+                self.set_obstacle_cost(nav_w_obs)
         if _handle is None and got.model == L.MODEL_CARTPOLE:
             cart_kw.update({k: v for k, v in skid_kw.items() if k in ("goal", "w_quad_state", "w_quad_term", "w_quad_ctrl")})
             self.set_cartpole(uncertain_params=kw.get("uncertain_params"), sampling=kw.get("sampling"), **cart_kw)
@@ -306,6 +310,11 @@ class Context:
         nx, ny = g.shape
         ox, oy = (int(nx / 2), int(ny / 2)) if off is None else off
         L.check(L.load().dust_set_grid(self._h, _p(g), nx, ny, float(ox), float(oy)))
+
+    def set_obstacle_cost(self, w_obs):
+        """The obstacle weight of a skid-steer context's cost (dust_set_obstacle_cost; dust_amd.costs.NavigationCost): w_obs occ(x, y) on
+        the map of set_grid with the configuration's cell_size joins the instantaneous and the terminal cost; 0 returns to the plain kernels."""
+        L.check(L.load().dust_set_obstacle_cost(self._h, float(w_obs)))
 
     def set_skid_steer(self, x_icr=0.2, wheel_radius=0.0625, axial_distance=0.475, goal=(0, 0, 0, 0, 0), w_quad_state=(1, 1, 1, 1, 1),
                        w_quad_term=(1, 1, 1, 1, 1), w_quad_ctrl=(0, 0), uncertain_params=None, sampling=None):

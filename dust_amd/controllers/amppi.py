@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from ..backend import Context
-from ..costs import QuadraticCost, recognise
+from ..costs import QuadraticCost, cost_grid, cost_grid_key, recognise
 from ..utils.utf import MerweScaledUTF
 
 
@@ -107,6 +107,9 @@ class AMPPI:
                        with_obstacle=bool(model.with_obstacle), cell_size=float(model.map_cell_size or 0.1), control_type="acceleration",
                        deterministic=True)
         cfg.update(recognise(model, self.inst_cost_fn, self.term_cost_fn))
+        nav = cost_grid_key(self.inst_cost_fn)
+        if nav is not None:  # (part of the context key: a changed map rebuilds the context)
+            cfg["nav_map"] = nav
         return cfg
 
     def _ensure_ctx(self, model):
@@ -118,7 +121,9 @@ class AMPPI:
         if self._ctx is not None:
             self._ctx.close()
         grid = model.obst_map.map.astype(np.float32) if getattr(model, "obst_map", None) is not None else None
-        self._ctx, self._ctx_key = Context(grid=grid, **cfg), key
+        if grid is None:  # the skid-steer model has no map of its own: a NavigationCost brings it
+            grid = cost_grid(self.inst_cost_fn)
+        self._ctx, self._ctx_key = Context(grid=grid, **{k: v for k, v in cfg.items() if k != "nav_map"}), key
         if self._tf is not None:
             self._ctx.set_param_weights(self._tf.loc_weights.numpy())
         self._ctx.set_a_seq(a_seq)

@@ -11,7 +11,7 @@ import torch
 
 from .. import _lib as L
 from ..backend import Context
-from ..costs import recognise
+from ..costs import cost_grid, cost_grid_key, recognise
 from ..utils.utf import MerweScaledUTF
 
 Empty = torch.Size([])
@@ -117,6 +117,9 @@ class MultiDISCO:
                        noise_std=tuple(float(v) for v in torch.as_tensor(model.dyn_std, dtype=torch.float).reshape(-1).expand(2)))
         cfg.update(recognise(model, self.inst_cost_fn, self.term_cost_fn))
         cfg.update(self._svmpc_cfg)
+        nav = cost_grid_key(self.inst_cost_fn)
+        if nav is not None:  # (part of the context key: a changed map rebuilds the context)
+            cfg["nav_map"] = nav
         return cfg
 
     def _ensure_ctx(self, model, params_dist=None):
@@ -130,7 +133,9 @@ class MultiDISCO:
             state = dict(theta=old.get_theta(), prior=old.get_prior(), a_mat=old.get_a_mat(), a_seq=old.get_a_seq())
             old.close()
         grid = model.obst_map.map.astype(np.float32) if getattr(model, "obst_map", None) is not None else None
-        self._ctx = Context(grid=grid, **cfg)
+        if grid is None:  # the skid-steer model has no map of its own: a NavigationCost brings it
+            grid = cost_grid(self.inst_cost_fn)
+        self._ctx = Context(grid=grid, **{k: v for k, v in cfg.items() if k != "nav_map"})
         self._ctx_key = key
         if self._tf is not None:
             self._ctx.set_param_weights(self._tf.loc_weights.numpy())

@@ -48,6 +48,71 @@ class QuadraticCost:
         return (((states - self.goal) ** 2) * self.w_term).sum(-1)
 
 
+class NavigationCost(QuadraticCost):
+    """The quadratic family plus the obstacle term of Particle.default_inst_cost / default_term_cost (particle.py:170-225) on the position
+    plane states[..., 0:2] - the skid-steer family's navigation cost:
+        inst(x, a) = quad(x) + ctrl(a) + w_obs * obst_map.get_collisions(x[..., 0:2])        term(x) = quad(x) + w_obs * get_collisions(...)
+    `obst_map` is anything with get_collisions, .map and .cell_size (obstacle_map.py:64-93): this package's ObstacleMap or the reference's.
+    Plain torch like QuadraticCost, so the same object drives the reference's controllers."""
+
+    family = "navigation"
+
+    def __init__(self, goal, w_state, w_term=None, w_ctrl=None, obst_map=None, w_obs=0.0):
+        super().__init__(goal, w_state, w_term, w_ctrl)
+        self.obst_map, self.w_obs = obst_map, float(w_obs)
+
+    def _obst(self, states):
+        if self.obst_map is None:
+            if self.w_obs != 0.0:
+                raise ValueError("NavigationCost(w_obs != 0) needs an obst_map (particle.py:172-175 reads self.obst_map)")
+            return 0.0
+        if getattr(self.obst_map, "map_torch", None) is None:
+            self.obst_map.convert_map()
+        return self.w_obs * self.obst_map.get_collisions(states[..., 0:2])
+
+    def inst_cost(self, states, controls=None, n_pol=1, debug=None):
+        return QuadraticCost.inst_cost(self, states, controls) + self._obst(states)  # particle.py:197: state + control + obstacle
+
+    def term_cost(self, states, n_pol=1, debug=None):
+        return QuadraticCost.term_cost(self, states) + self._obst(states)  # particle.py:225
+
+    def grid(self):
+        """The occupancy grid as the fp32 array Context(grid=) takes, or None without a map."""
+        import numpy as np
+
+        return None if self.obst_map is None else np.ascontiguousarray(np.asarray(self.obst_map.map, dtype=np.float32))
+
+    def grid_key(self):
+        """(shape, SHA-1 of the fp32 map) for a controller's context key, or None without a map.  The controllers ask on every tick, so
+        the digest is kept and taken again only when the map is another one: obst_map.map reassigned (another array object; the last one
+        is held, so its id cannot return), another shape, or - an edit in place - other row or column sums."""
+        import hashlib
+
+        import numpy as np
+
+        if self.obst_map is None:
+            return None
+        m = np.asarray(self.obst_map.map)
+        cols, rows = m.sum(axis=0, dtype=np.float64), m.sum(axis=1, dtype=np.float64)
+        stamp = (m.shape, str(m.dtype), float(cols @ np.arange(1.0, cols.size + 1.0)), float(rows @ np.arange(1.0, rows.size + 1.0)))
+        kept = getattr(self, "_grid_key", None)
+        if kept is None or kept[0] is not self.obst_map.map or kept[1] != stamp:
+            kept = self._grid_key = (self.obst_map.map, stamp, (m.shape, hashlib.sha1(self.grid().tobytes()).hexdigest()))
+        return kept[2]
+
+
+def cost_grid(inst_cost_fn):
+    """The map a cost object carries (NavigationCost: the skid-steer model has none of its own), or None."""
+    owner = getattr(inst_cost_fn, "__self__", None)
+    return owner.grid() if isinstance(owner, NavigationCost) else None
+
+
+def cost_grid_key(inst_cost_fn):
+    """What identifies that map in a controller's context key (NavigationCost.grid_key: kept between ticks), or None."""
+    owner = getattr(inst_cost_fn, "__self__", None)
+    return owner.grid_key() if isinstance(owner, NavigationCost) else None
+
+
 def _probe_quadcos(fn):
     pts = torch.tensor([[0.3, 0.0], [0.0, 1.7], [2.1, -0.4], [-1.2, 3.3], [5.9, -7.1], [3.14159, 0.5]])
     try:
@@ -98,10 +163,29 @@ def recognise(model, inst_cost_fn, term_cost_fn):
         if owner.goal.numel() != 5 or owner.w_state.numel() != 5 or owner.w_term.numel() != 5:
             raise ValueError("QuadraticCost for SkidSteerRobot needs 5 state entries (x, y, theta, v, omega)")
         wc = owner.w_ctrl if owner.w_ctrl is not None else torch.zeros(2)
-        return dict(goal=tuple(float(v) for v in owner.goal), w_quad_state=tuple(float(v) for v in owner.w_state),
-                    w_quad_term=tuple(float(v) for v in owner.w_term), w_quad_ctrl=tuple(float(v) for v in wc))
+        out = dict(goal=tuple(float(v) for v in owner.goal), w_quad_state=tuple(float(v) for v in owner.w_state),
+                   w_quad_term=tuple(float(v) for v in owner.w_term), w_quad_ctrl=tuple(float(v) for v in wc))
+        if type(owner) is QuadraticCost:
+            return out
+        # A subclass adds terms the quadratic kernels do not evaluate: only the navigation family's own methods are known
+        if (type(owner) is not NavigationCost or getattr(inst_cost_fn, "__func__", None) is not NavigationCost.inst_cost or
+                getattr(term_cost_fn, "__func__", None) is not NavigationCost.term_cost):
+            raise NotImplementedError("%s extends QuadraticCost: the device evaluates QuadraticCost and NavigationCost themselves, and "
+                                      "whatever a subclass adds would be dropped silently (no CPU fallback)" % type(owner).__name__)
+        if not 0.0 <= owner.w_obs < float("inf"):
+            raise ValueError("NavigationCost(w_obs=%r): a finite weight >= 0" % (owner.w_obs,))
+        if owner.w_obs != 0.0 and owner.obst_map is None:
+            raise ValueError("NavigationCost(w_obs=%g) without obst_map: the obstacle term reads obst_map.get_collisions "
+                             "(particle.py:172-175, obstacle_map.py:64-93)" % owner.w_obs)
+        out["w_obs"] = owner.w_obs
+        if owner.obst_map is not None:
+            out["cell_size"] = float(owner.obst_map.cell_size)
+        return out
     if fam == "cartpole":
         owner = getattr(inst_cost_fn, "__self__", None)
+        if isinstance(owner, NavigationCost):
+            raise NotImplementedError("NavigationCost on CartPoleModel: the obstacle term reads the position plane states[..., 0:2] "
+                                      "(particle.py:174), which the cart-pole's state (x, x_d, theta, theta_d) does not have")
         if not isinstance(owner, QuadraticCost) or getattr(term_cost_fn, "__self__", None) is not owner:
             raise NotImplementedError("CartPoleModel runs with dust_amd.costs.QuadraticCost(...).inst_cost / .term_cost (an opaque "
                                       "callable cannot run on the device and there is no CPU fallback)")

@@ -77,8 +77,10 @@ struct AmppiDims {
 };
 
 // One trajectory on one parameter row: -> sum_t inst(x_t), t = 1 .. H, and term(x_H); `so`: its [H + 1][DS] states or nullptr
-template <int MODEL>
-__device__ __forceinline__ void amppi_traj(const AmppiArgs &a, const float *acts, const float *prow, float *so, float *inst_out, float *term_out) {
+// NAV (skid-steer only): the navigation cost family of skid.hpp - w_obs occ(x_0, x_1) joins both parts; `nav` and `map` are read by it alone
+template <int MODEL, bool NAV>
+__device__ __forceinline__ void amppi_traj(const AmppiArgs &a, const float *acts, const float *prow, float *so, float *inst_out, float *term_out,
+                                           const SkidNav *nav, const DevModel *map) {
   constexpr int DS = AmppiDims<MODEL>::DS;
   const int H = a.H;
   float x[DS];
@@ -107,12 +109,14 @@ __device__ __forceinline__ void amppi_traj(const AmppiArgs &a, const float *acts
     for (int t = 0; t < H; ++t) {
       const float a0 = acts[2 * t], a1 = acts[2 * t + 1];
       skid_step(x, clampf(a0, a.sk.lo[0], a.sk.hi[0]), clampf(a1, a.sk.lo[1], a.sk.hi[1]), xicr, wr, ad, a.dt);
-      tot += (double)amppi_quad<DS>(x, a.sk.goal, a.sk.w_state);
+      if constexpr (NAV) tot += (double)(amppi_quad<DS>(x, a.sk.goal, a.sk.w_state) + nav->w_obs * collision(*map, x[0], x[1]));
+      else tot += (double)amppi_quad<DS>(x, a.sk.goal, a.sk.w_state);
       if (so)
 #pragma unroll
         for (int k = 0; k < DS; ++k) so[(size_t)(t + 1) * DS + k] = x[k];
     }
-    *term_out = amppi_quad<DS>(x, a.sk.goal, a.sk.w_term);
+    if constexpr (NAV) *term_out = amppi_quad<DS>(x, a.sk.goal, a.sk.w_term) + nav->w_obs * collision(*map, x[0], x[1]);
+    else *term_out = amppi_quad<DS>(x, a.sk.goal, a.sk.w_term);
   } else {
     const bool have_rows = prow != nullptr;  // (as cartpole.hpp: without rows a parameter named as sampled stays the constructor's Python float)
     const bool pm_py = (a.cp.par[CP_MP].kind == DUST_PARAM_PYFLOAT || (a.cp.par[CP_MP].kind == DUST_PARAM_SAMPLED && !have_rows)) &&
@@ -135,113 +139,24 @@ __device__ __forceinline__ void amppi_traj(const AmppiArgs &a, const float *acts
 
 template <int MODEL>
 __global__ __launch_bounds__(AMPPI_THREADS) void amppi_kernel(const AmppiArgs a) {
-  constexpr int DS = AmppiDims<MODEL>::DS;
-  // ONE LDS object: [0] "this workgroup is the reducer", [1, 9) block_reduce's scratch, [9, 13) wave partials, [16, 16 + 256) column partials
-  __shared__ double lds[16 + AMPPI_THREADS];
-  const int tid = (int)threadIdx.x, s = (int)blockIdx.x * AMPPI_THREADS + tid;
-  const int D = a.D, H = a.H, da = a.da, S = a.S;
+  constexpr bool NAV = false;
+  const SkidNav *const nav = nullptr;
+  uint32_t *const grid_lds = nullptr;
+#include "amppi_body.inc"
+}
 
-  if (s < S) {
-    float *acts = a.acts + (size_t)s * D;
-    if (a.philox) {
-      const uint32_t ctr_tick = a.ctr[0], ctr_iter = a.ctr[1];
-      for (int j0 = 0; j0 < D; j0 += 8) {
-        float z[8];
-        philox_normal8(a.seed, (uint32_t)(j0 >> 3), (uint32_t)s, ctr_iter, ctr_tick, z);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const int j = j0 + i;
-          if (j >= D) break;
-          // a_seq + L z: an odd column of a 2 x 2 factor takes its partner draw too (D is even then: pairs never straddle a block)
-          const float lz = (da == 2 && (i & 1)) ? (a.chol[1] * z[i - 1] + a.chol[2] * z[i]) : a.chol[0] * z[i];
-          acts[j] = a.a_seq[j] + lz;
-        }
-      }
-    }
-    double cc = 0.0;
-    for (int t = 0; t < H; ++t) {
-      if (da == 1) {
-        const float e0 = acts[t] - a.a_seq[t];
-        cc += (double)((a.a_seq[t] * a.pre[0]) * e0);
-      } else {
-        const float u0 = a.a_seq[2 * t], u1 = a.a_seq[2 * t + 1];
-        const float e0 = acts[2 * t] - u0, e1 = acts[2 * t + 1] - u1;
-        const float p0 = u0 * a.pre[0] + u1 * a.pre[1], p1 = u0 * a.pre[1] + u1 * a.pre[2];
-        cc += (double)(p0 * e0 + p1 * e1);
-      }
-    }
-    const float ctrl = a.lambda * (float)cc;
-    float inst = 0.f, term = 0.f;
-    if (a.mode == AMPPI_PARAMS_SIGMA) {
-      double wi = 0.0, wt = 0.0;
-      for (int k = 0; k < a.pts; ++k) {
-        float ik, tk;
-        float *so = a.states_out ? a.states_out + ((size_t)s * a.pts + k) * (size_t)(H + 1) * DS : nullptr;
-        amppi_traj<MODEL>(a, acts, a.params + (size_t)k * a.P, so, &ik, &tk);
-        wi += (double)a.mw[k] * (double)ik;
-        wt += (double)a.mw[k] * (double)tk;
-      }
-      inst = (float)wi;
-      term = (float)wt;
-    } else {
-      const float *prow = a.mode == AMPPI_PARAMS_NONE ? nullptr : (a.mode == AMPPI_PARAMS_SINGLE ? a.params : a.params + (size_t)s * a.P);
-      float *so = a.states_out ? a.states_out + (size_t)s * (size_t)(H + 1) * DS : nullptr;
-      amppi_traj<MODEL>(a, acts, prow, so, &inst, &term);
-    }
-    a.costs[s] = (term + inst) + ctrl;  // amppi.py:224
-  }
-
-  // ---- publish, take a ticket
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  wg_sync();
-  unsigned int *is_last = reinterpret_cast<unsigned int *>(lds);
-  if (tid == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned int t = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned int last = t + 1u == gridDim.x ? 1u : 0u;
-    if (last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    *is_last = last;
-  }
-  wg_sync();
-  if (*is_last == 0u) return;
-
-  // ---- phase 2: the reducer
-  float *red = reinterpret_cast<float *>(lds + 1);
-  float mn = INFINITY;
-  for (int i = tid; i < S; i += AMPPI_THREADS) mn = fminf(mn, a.costs[i]);
-  const float beta = block_reduce<RED_MIN>(mn, red);
-  const float nil = (float)(-1.0 / (double)a.lambda);  // (-1 / lambda_) is a Python float, amppi.py:251
-  double z = 0.0;
-  for (int i = tid; i < S; i += AMPPI_THREADS) z += (double)expf(nil * (a.costs[i] - beta));
-  z = wave_sum_d(z);
-  wg_sync();
-  if ((tid & 63) == 0) lds[9 + (tid >> 6)] = z;
-  wg_sync();
-  const float eta = (float)log(((lds[9] + lds[10]) + lds[11]) + lds[12]);  // logsumexp: the largest entry of log_costs is 0
-  for (int i = tid; i < S; i += AMPPI_THREADS) a.omega[i] = nil * (a.costs[i] - beta) - eta;
-  // a_seq += tensordot(exp(omega), eps): column j by lane (q, j), q strides the samples; the q partials are added in order
-  const int nq = AMPPI_THREADS / D, q = tid / D, j = tid - q * D;
-  double acc = 0.0;
-  if (q < nq) {
-    const float aj = a.a_seq[j];
-    for (int i = q; i < S; i += nq) {
-      const float w = expf((nil * (a.costs[i] - beta)) - eta);
-      acc += (double)w * (double)(a.acts[(size_t)i * D + j] - aj);
-    }
-  }
-  lds[16 + tid] = acc;
-  wg_sync();
-  if (tid < D) {
-    double sum = 0.0;
-    for (int k = 0; k < nq; ++k) sum += lds[16 + k * D + tid];
-    const int d = da == 2 ? (tid & 1) : 0;
-    a.a_seq[tid] = clampf(a.a_seq[tid] + (float)sum, a.min_a[d], a.max_a[d]);
-  }
-  if (tid == 0 && a.philox) a.ctr[1] += 1u;
+// The skid-steer tick with the navigation cost family: dynamic LDS of 4 nav.grid_words bytes behind the static object
+struct AmppiNavArgs {
+  AmppiArgs a;
+  SkidNav nav;
+};
+__global__ __launch_bounds__(AMPPI_THREADS) void amppi_skid_nav_kernel(const AmppiNavArgs k) {
+  constexpr int MODEL = DUST_MODEL_SKID_STEER;
+  constexpr bool NAV = true;
+  const AmppiArgs &a = k.a;
+  const SkidNav *const nav = &k.nav;
+  extern __shared__ __attribute__((aligned(16))) uint32_t grid_lds[];
+#include "amppi_body.inc"
 }
 
 // BaseController.roll(steps) (base.py:68-80) for 1 <= steps: shift the sequence left by `steps` rows, zeros behind

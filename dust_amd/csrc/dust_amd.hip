@@ -132,6 +132,7 @@ struct dust_ctx {
   bool no_handoff;           // replay of a tick that found the device shared: plain kernels only, nothing that spins on its own grid
   unsigned long persist_declined;  // key of the (shape, state) for which the one-launch ticks last declined: no staging for it again
   SkidModel skid;            // DUST_MODEL_SKID_STEER: model parameters and the quadratic cost (dust_set_skid_steer)
+  float skid_w_obs;          // ... and the obstacle weight of the navigation cost family (dust_set_obstacle_cost); 0: the plain kernels
   CartModel cart;            // DUST_MODEL_CARTPOLE: model parameters and the quadratic cost (dust_set_cartpole)
   // pairwise_packed.hpp: the near-key lists of the last large-set pass 1 - key indices [tiles][chunks * 64], unit offsets
   // [tiles][chunks + 1], unit query masks [tiles][chunks][4], slice boundaries of pass 1 / pass 2, non-zero flags of the units' kernel blocks
@@ -214,6 +215,7 @@ struct dust_ctx {
   struct EnvSw {
     int comm_force, pair_big, pair_fused, states_form, dense, far, logp_mfma, no_fuse, no_tick2, tick2_test_abort, tick2_test_timeout,
         no_comm_overlap;
+    int nav_grid_hbm;   // DUST_NAV_GRID_HBM=1 (development switch): the skid-steer navigation kernels read the map from device memory at any size
     int noise_general;  // DUST_NOISE_GENERAL=1 (development switch): control-channel noise always through particle_general.hpp's first pass
     int k2_form;     // DUST_K2_FORM=0 (development switch): K2's bandwidth launch stays behind the prior + rollout launch (rounds 1-5);
                      // default: the bandwidths ride in that launch, phi reads the row-major particles (round 6)
@@ -573,6 +575,7 @@ static void env_read(dust_ctx *c) {
   c->env.pack_order = env_int("DUST_PACK_ORDER");
   c->env.k2_form = env_int("DUST_K2_FORM");
   c->env.noise_general = env_int("DUST_NOISE_GENERAL");
+  c->env.nav_grid_hbm = env_int("DUST_NAV_GRID_HBM");
   const char *ft = getenv("DUST_FAR_T");
   c->env.far_t = (ft && *ft) ? (float)atof(ft) : DUST_FAR_T_DEFAULT;
 }
@@ -1006,6 +1009,7 @@ extern "C" int dust_clone(const dust_ctx *src, dust_ctx **out) {
   c->mu_aliased = src->mu_aliased;
   c->have_sample = src->have_sample;
   c->skid = src->skid;
+  c->skid_w_obs = src->skid_w_obs;
   c->cart = src->cart;
   c->k2_fixed_h = src->k2_fixed_h;  // (dust_set_k2_bandwidth: RBF(bandwidth=, minimum_bw=) - a deep-copied controller keeps its kernel)
   c->k2_min_bw = src->k2_min_bw;
@@ -1121,6 +1125,36 @@ extern "C" int dust_set_grid(dust_ctx *c, const float *grid, int nx, int ny, flo
   c->ny = ny;
   c->off_x = off_x;
   c->off_y = off_y;
+  return DUST_OK;
+}
+
+extern "C" int dust_set_obstacle_cost(dust_ctx *c, float w_obs) {
+  if (!c) return fail(DUST_ERR_INVALID, "null ctx");
+  if (c->cfg.model != DUST_MODEL_SKID_STEER)
+    return fail(DUST_ERR_UNSUPPORTED, "dust_set_obstacle_cost is the skid-steer family's (Particle carries w_obs in dust_config; the Pendulum and the cart-pole have no position plane)");
+  if (!std::isfinite(w_obs) || w_obs < 0.f) return fail(DUST_ERR_INVALID, "w_obs = %g: a finite weight >= 0", (double)w_obs);
+  // (the lookups scale by 1 / cell_size: a configuration that left the field 0 would send every state to cell 0 without an error)
+  if (w_obs != 0.f && !(std::isfinite(c->cfg.cell_size) && c->cfg.cell_size > 0.f))
+    return fail(DUST_ERR_INVALID, "dust_config.cell_size = %g: the obstacle term needs a finite cell size > 0", (double)c->cfg.cell_size);
+  TRY(settle_pending(c));
+  if (c->graph_exec || c->graph_exec_alt) graph_drop(c);
+  c->skid_w_obs = w_obs;
+  return DUST_OK;
+}
+
+// The navigation cost family of a skid-steer context (skid.hpp SkidNav): the map of dust_set_grid with dust_config.cell_size, staged into
+// LDS up to the size the regular kernel stages Particle's (rollout_args: 4096 words), otherwise - or with DUST_NAV_GRID_HBM=1 - read in place
+static int skid_nav_args(const dust_ctx *c, SkidNav &nv) {
+  if (!c->grid_bits) return fail(DUST_ERR_STATE, "with_obstacle is set but no occupancy grid was supplied (dust_set_grid)");
+  nv.inv_cell = (float)(1.0 / c->cfg.cell_size);
+  nv.off_x = c->off_x;
+  nv.off_y = c->off_y;
+  nv.w_obs = c->skid_w_obs;
+  nv.nx = c->nx;
+  nv.ny = c->ny;
+  const int words = (c->nx * c->ny + 31) / 32;
+  nv.grid_words = (words <= 4096 && c->env.nav_grid_hbm <= 0) ? ((words + 3) & ~3) : 0;
+  nv.grid_bits = c->grid_bits;
   return DUST_OK;
 }
 
@@ -1341,10 +1375,17 @@ extern "C" int dust_amppi_update(dust_ctx *c, const float *state, const float *a
   a.states_out = want_states ? c->states : nullptr;
   a.ticket = c->amppi_ticket;
   const int grid = (S + AMPPI_THREADS - 1) / AMPPI_THREADS;
+  const bool nav = c->cfg.model == DUST_MODEL_SKID_STEER && c->skid_w_obs != 0.f;
+  AmppiNavArgs kn;
+  if (nav) {
+    kn.a = a;
+    TRY(skid_nav_args(c, kn.nav));
+  }
   HIP_TRY(hipMemsetAsync(c->amppi_ticket, 0, sizeof(unsigned int), c->stream));
   {
     Prof pr(c, DUST_K_AMPPI);
-    switch (c->cfg.model) {
+    if (nav) amppi_skid_nav_kernel<<<grid, AMPPI_THREADS, (size_t)kn.nav.grid_words * sizeof(uint32_t), c->stream>>>(kn);
+    else switch (c->cfg.model) {
       case DUST_MODEL_PENDULUM: amppi_kernel<DUST_MODEL_PENDULUM><<<grid, AMPPI_THREADS, 0, c->stream>>>(a); break;
       case DUST_MODEL_PARTICLE: amppi_kernel<DUST_MODEL_PARTICLE><<<grid, AMPPI_THREADS, 0, c->stream>>>(a); break;
       case DUST_MODEL_SKID_STEER: amppi_kernel<DUST_MODEL_SKID_STEER><<<grid, AMPPI_THREADS, 0, c->stream>>>(a); break;
@@ -1484,6 +1525,8 @@ static int rollout_args(dust_ctx *c, const SampleOpts &o, RolloutArgs &a, int *n
   memset(&a, 0, sizeof a);
   a.dm = make_dev_model(c);
   if (c->cfg.model == DUST_MODEL_PARTICLE && c->cfg.with_obstacle && !c->grid_bits)
+    return fail(DUST_ERR_STATE, "with_obstacle is set but no occupancy grid was supplied (dust_set_grid)");
+  if (c->cfg.model == DUST_MODEL_SKID_STEER && c->skid_w_obs != 0.f && !c->grid_bits)  // (dust_set_obstacle_cost: the navigation family)
     return fail(DUST_ERR_STATE, "with_obstacle is set but no occupancy grid was supplied (dust_set_grid)");
   a.N_total = c->N;
   a.n0 = c->n0;
@@ -1719,6 +1762,15 @@ static int launch_first_pass(dust_ctx *c, const FirstPass &fp, const RolloutArgs
       k.chol_a[0] = a.chol_a[0];
       k.chol_a[1] = a.chol_a[1];
       k.chol_off = a.chol_off;
+      if (c->skid_w_obs != 0.f) {  // the navigation cost family: instances of their own
+        SkidNavArgs kn;
+        kn.r = k;
+        TRY(skid_nav_args(c, kn.nav));
+        const size_t lds = (size_t)kn.nav.grid_words * sizeof(uint32_t);
+        if (k.mw) skid_ut_nav_rollout_kernel<<<fp.blocks, 256, lds, c->stream>>>(kn);
+        else skid_nav_rollout_kernel<<<fp.blocks, 256, lds, c->stream>>>(kn);
+        break;
+      }
       if (k.mw) skid_ut_rollout_kernel<<<fp.blocks, 256, 0, c->stream>>>(k);
       else skid_rollout_kernel<<<fp.blocks, 256, 0, c->stream>>>(k);
       break;

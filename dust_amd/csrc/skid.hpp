@@ -45,6 +45,41 @@ struct SkidArgs {
   const float *mw;      // [M] unscented-transform weights (params: the M sigma points) or nullptr: plain mean over m (last: the other offsets stay)
 };
 
+// The navigation cost family (dust_amd.costs.NavigationCost): the quadratic family plus the obstacle term of Particle.default_inst_cost /
+// default_term_cost (particle.py:170-225) on the position plane (x_0, x_1),
+//     inst(x, a) = (quad + ctrl) + w_obs occ(x_0, x_1)          term(x) = quad + w_obs occ(x_0, x_1)
+// with occ = ObstacleMap.get_collisions (obstacle_map.py:64-93; common.hpp collision()).  It travels BESIDE SkidArgs / AmppiArgs, in a
+// struct of its own, so that the kernels without the term keep their argument layout - and their instructions.
+struct SkidNav {
+  float inv_cell, off_x, off_y, w_obs;
+  int nx, ny;
+  int grid_words;             // words of the bit-packed map the workgroup stages into dynamic LDS, or 0: the lookups read device memory
+  const uint32_t *grid_bits;  // bit-packed [nx][ny] occupancy, as DevModel's
+};
+
+struct SkidNavArgs {
+  SkidArgs r;
+  SkidNav nav;
+};
+
+// The map for collision(): staged into `lds` by the whole workgroup (every lane calls this, then the barrier) or left in device memory
+__device__ __forceinline__ DevModel skid_nav_map(const SkidNav &nv, uint32_t *lds) {
+  DevModel dm;
+  dm.inv_cell = nv.inv_cell;
+  dm.off_x = nv.off_x;
+  dm.off_y = nv.off_y;
+  dm.nx = nv.nx;
+  dm.ny = nv.ny;
+  dm.grid_bits = nv.grid_bits;
+  if (nv.grid_words > 0) {
+    const int words = (nv.nx * nv.ny + 31) >> 5;  // (grid_words is this rounded up to 4: the allocation ends at `words`)
+    for (int w = (int)threadIdx.x; w < words; w += (int)blockDim.x) lds[w] = nv.grid_bits[w];
+    dm.grid_bits = lds;
+    __syncthreads();
+  }
+  return dm;
+}
+
 __device__ __forceinline__ float skid_param(const DevParam &p, const float *prow, int log_space) {
   if (p.kind == DUST_PARAM_SAMPLED && prow) {
     const float v = prow[p.col];
@@ -82,8 +117,11 @@ __device__ __forceinline__ void skid_step(float x[5], const float r, const float
 // (s N + n) M + m runs sigma point m, so entry (m, t) meets weight (m H + t) mod M (rollout.hpp has the Pendulum's form of the rule).
 // Weighted terms accumulate in double (CostAcc::add_weighted); the two parts are rounded and added in fp32 as the regular kernel does.
 // A template parameter, not a run-time branch: the plain instance is the kernel it was before the sigma-point form existed.
-template <bool UT>
-__device__ __forceinline__ void skid_rollout_body(const SkidArgs &a) {
+// NAV: the navigation family above; `nav` / `lds` are read by that instance alone.
+template <bool UT, bool NAV>
+__device__ __forceinline__ void skid_rollout_body(const SkidArgs &a, const SkidNav *nav, uint32_t *lds) {
+  DevModel dm;
+  if constexpr (NAV) dm = skid_nav_map(*nav, lds);  // (ahead of the bounds check: the lanes past the end stage their share)
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= a.n_local * a.S) return;
   const int s = idx / a.n_local, n = a.n0 + (idx - s * a.n_local);  // (n fastest: the rows of one sample are adjacent)
@@ -127,8 +165,14 @@ __device__ __forceinline__ void skid_rollout_body(const SkidArgs &a) {
         sc += (double)((d * d) * a.sk.w_state[k]);
       }
       const double cc = (double)((a0 * a0) * a.sk.w_ctrl[0]) + (double)((a1 * a1) * a.sk.w_ctrl[1]);
-      if (UT) tot += (double)a.mw[((long)m * H + t) % a.M] * (double)((float)sc + (float)cc);
-      else tot += (double)((float)sc + (float)cc);
+      if constexpr (NAV) {  // (quad + ctrl) + obst, the reference callable's order
+        const float ic = ((float)sc + (float)cc) + nav->w_obs * collision(dm, x[0], x[1]);
+        if (UT) tot += (double)a.mw[((long)m * H + t) % a.M] * (double)ic;
+        else tot += (double)ic;
+      } else {
+        if (UT) tot += (double)a.mw[((long)m * H + t) % a.M] * (double)((float)sc + (float)cc);
+        else tot += (double)((float)sc + (float)cc);
+      }
       skid_step(x, clampf(a0, a.sk.lo[0], a.sk.hi[0]), clampf(a1, a.sk.lo[1], a.sk.hi[1]), xicr, wr, ad, a.dt);
       if (so)
 #pragma unroll
@@ -140,7 +184,15 @@ __device__ __forceinline__ void skid_rollout_body(const SkidArgs &a) {
       const float d = x[k] - a.sk.goal[k];
       tc += (double)((d * d) * a.sk.w_term[k]);
     }
-    if (UT) {  // weighted instantaneous and terminal parts are summed separately over the sigma points (disco.py:314-321)
+    if constexpr (NAV) {
+      const float tcn = (float)tc + nav->w_obs * collision(dm, x[0], x[1]);
+      if (UT) {
+        ut_term += (double)a.mw[m] * (double)tcn;
+        acc += tot;
+      } else {
+        acc += (double)((float)tot + tcn);
+      }
+    } else if (UT) {  // weighted instantaneous and terminal parts are summed separately over the sigma points (disco.py:314-321)
       ut_term += (double)a.mw[m] * (double)(float)tc;
       acc += tot;
     } else {
@@ -152,7 +204,16 @@ __device__ __forceinline__ void skid_rollout_body(const SkidArgs &a) {
   a.costsT[(size_t)n * a.S + s] = cost;
 }
 
-__global__ __launch_bounds__(256) void skid_rollout_kernel(const SkidArgs a) { skid_rollout_body<false>(a); }
-__global__ __launch_bounds__(256) void skid_ut_rollout_kernel(const SkidArgs a) { skid_rollout_body<true>(a); }
+__global__ __launch_bounds__(256) void skid_rollout_kernel(const SkidArgs a) { skid_rollout_body<false, false>(a, nullptr, nullptr); }
+__global__ __launch_bounds__(256) void skid_ut_rollout_kernel(const SkidArgs a) { skid_rollout_body<true, false>(a, nullptr, nullptr); }
+// The navigation instances: dynamic LDS of 4 nav.grid_words bytes (0: the map stays in device memory)
+__global__ __launch_bounds__(256) void skid_nav_rollout_kernel(const SkidNavArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t skid_nav_lds[];
+  skid_rollout_body<false, true>(a.r, &a.nav, skid_nav_lds);
+}
+__global__ __launch_bounds__(256) void skid_ut_nav_rollout_kernel(const SkidNavArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t skid_nav_lds[];
+  skid_rollout_body<true, true>(a.r, &a.nav, skid_nav_lds);
+}
 
 }  // namespace dust

@@ -228,6 +228,14 @@ int dust_set_cartpole(dust_ctx *ctx, const dust_cartpole_config *cfg);
 int dust_set_ctrl_noise(dust_ctx *ctx, const float *z, int n_sets);
 /* ObstacleMap occupancy grid [nx][ny] (obstacle_map.py:13-43); offsets are the map centre in cells */
 int dust_set_grid(dust_ctx *ctx, const float *grid, int nx, int ny, float off_x, float off_y);
+/* The obstacle term of a skid-steer context's cost (the navigation family, dust_amd.costs.NavigationCost): w_obs occ(x, y) joins the
+ * instantaneous and the terminal cost as in Particle.default_inst_cost / default_term_cost (particle.py:170-225), occ =
+ * ObstacleMap.get_collisions (obstacle_map.py:64-93) on the map of dust_set_grid with dust_config.cell_size.  w_obs = 0 (the default)
+ * returns the context to the kernels without the term.  Skid-steer contexts only: DUST_ERR_UNSUPPORTED for every other model (Particle
+ * carries w_obs in dust_config; the Pendulum and the cart-pole have no position plane).  DUST_ERR_INVALID for a negative or non-finite
+ * weight, and for a weight != 0 on a context whose dust_config.cell_size is not a finite size > 0.  With w_obs != 0 and no map the first rollout returns DUST_ERR_STATE.  Pending launches are settled and captured graphs
+ * dropped, as by dust_set_grid; dust_clone copies the weight with the map. */
+int dust_set_obstacle_cost(dust_ctx *ctx, float w_obs);
 
 /* particle / prior / controller state (all [N][H][da] or [N]) */
 int dust_set_theta(dust_ctx *ctx, const float *theta);                                /* SVMPC.theta svmpc.py:25 */
