@@ -562,6 +562,26 @@ class Context:
             acts = self._get(L.load().dust_get_actions, (self.S, self.H, self.da))
         return costs, omega, a_seq, states, acts
 
+    def amppi_dual_tick(self, mpf, state, action_prev=None, actions=None, shared_params=False, mpf_steps=20, mpf_bw=None, seed=0, roll=0,
+                        want_outputs=True, want_params=False):
+        """One control period of the dual loop over an AMPPI context in one C call (dust_amppi_dual_tick): the filter update for
+        (action_prev, state) - skipped when action_prev is None -, the parameters from the refreshed prior (drawn inside the tick's
+        kernel; one staged row with shared_params; staged sigma points for a context with parameter weights and a sigma scale), the
+        update, the roll.  -> (costs [S], omega [S], a_seq [H, da] before the roll, params or None, bw_used); want_outputs=False
+        reads nothing back."""
+        st = _f(state, (self.ds,))
+        ap = None if action_prev is None else _f(action_prev).reshape(-1)
+        act = None if actions is None else _f(actions, (self.S, self.H, self.da))
+        costs, omega, a_seq = ((np.empty(self.S, np.float32), np.empty(self.S, np.float32), np.empty((self.H, self.da), np.float32))
+                               if want_outputs else (None, None, None))
+        rows = self.M if self.M > 1 else (1 if shared_params else self.S)
+        pout = np.empty((rows, max(self.P, 1)), np.float32) if want_params else None
+        bw = C.c_float(0.0)
+        L.check(L.load().dust_amppi_dual_tick(self._h, mpf._h, _p(st), _p(ap), _vp(act), L.AMPPI_PARAMS_SHARED if shared_params else 0,
+                                              int(mpf_steps), float(-1.0 if mpf_bw is None else mpf_bw), int(seed), int(roll), _p(costs),
+                                              _p(omega), _p(a_seq), _p(pout), C.cast(C.byref(bw), L.FP)))
+        return costs, omega, a_seq, pout, float(bw.value)
+
     def amppi_roll(self, steps=1):
         """BaseController.roll(steps): the sequence moves `steps` rows forward, zeros behind (dust_amppi_roll)."""
         L.check(L.load().dust_amppi_roll(self._h, int(steps)))

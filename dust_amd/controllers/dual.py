@@ -118,3 +118,123 @@ class DualSVMPC:
         new_state = plant(state, action)
         self.step(action, new_state)
         return action, new_state, pw
+
+
+class DualAMPPI:
+    """The dual loop over an `AMPPI` controller: the reference composes it by hand in its simulation loop (dust/utils/simulations.py:
+    104-138 with dust/controllers/amppi.py:227-260 as the controller) -
+
+        forward(state)            model.params_dist = mpf.prior; controller.update_actions(model, state)   -> (a_seq [H, da], omega [S]);
+                                  controller.roll(roll) follows, so `a_seq` is the sequence BEFORE the roll (its row 0 is the action)
+        step(action, new_state)   mpf.optimize(action, new_state, bw, n_steps)                              -> (grad_norms, bw)
+
+    `fused=True` carries a whole period out in ONE C call (dust_amppi_dual_tick): step() only notes (action, new_state), the next
+    forward() runs the filter update, Silverman's bandwidth on the device when none is given, the parameters from the refreshed prior
+    ON THE DEVICE - "extended": every trajectory's row is drawn inside the tick's kernel, no S x P rows cross the bus; "single": one
+    staged row; a `MerweScaledUTF`: the prior's sigma points -, the update and the roll.  Reading `dyn_particles` in between carries
+    the noted update out first.  The fused draws come from the library's Philox stream under `seed` (one key per period).  A transform
+    with a custom `sqrt_method`, or over another number of parameters than the filter's, stays on the unfused path.  Both paths draw the
+    action noise on the device and return no rollouts (the controller's `return_rollouts` is not consulted: the loop reads `a_seq` and
+    `omega` alone); `last_costs` holds the tick's costs.  Fused and unfused count their Philox keys alike (seed + 1, + 2, ... against the
+    prior's own counter 1, 2, ...), so at `seed=0` and with a fixed `mpf_bw` the two run the same numbers."""
+
+    def __init__(self, controller, model, mpf, mpf_bw=None, mpf_steps=20, fused=False, seed=0, roll=1):
+        if getattr(controller, "_sample_shape", None) is None and getattr(controller, "_tf", None) is None:
+            raise ValueError("DualAMPPI needs a controller that samples dynamics parameters: params_sampling='none' reads no filter")
+        if bool(getattr(mpf.likelihood, "log_space", False)):
+            raise NotImplementedError("a log-space filter under AMPPI: the controller hands samples to the model as drawn (amppi.py:134-139)")
+        if int(roll) < 0:
+            raise ValueError("roll=%d: roll >= 0" % roll)
+        self.controller, self.model, self.mpf = controller, model, mpf
+        self.mpf_bw, self.mpf_steps, self.roll = mpf_bw, int(mpf_steps), int(roll)
+        self.fused, self._seed, self._pending = bool(fused), int(seed), None
+        self.ticks = 0
+        self.last_bw = None
+        self.last_costs = None
+
+    def __deepcopy__(self, memo):
+        new = copy.copy(self)
+        memo[id(self)] = new
+        new.mpf = copy.deepcopy(self.mpf, memo)
+        new.controller = copy.deepcopy(self.controller, memo)
+        new.model = copy.deepcopy(self.model, memo)
+        new.mpf.prior._seed = self.mpf.prior._seed  # (the unfused draws are keyed by the prior's own counter: the copy continues the stream)
+        if getattr(self.model, "params_dist", None) is self.mpf.prior:
+            new.model.params_dist = new.mpf.prior
+        return new
+
+    @property
+    def a_seq(self):
+        return self.controller.a_seq
+
+    @property
+    def dyn_particles(self):
+        self._flush()
+        return self.mpf.x
+
+    def _can_fuse(self):
+        tf = getattr(self.controller, "_tf", None)
+        if tf is not None and (not tf.default_sqrt or tf.n != self.mpf._dev.P):
+            return False
+        return self.fused and self.mpf.draw_source is None
+
+    def forward(self, state, actions=None):
+        """actions [S, H, da]: recorded action samples in place of device-drawn noise (update_actions's third argument)"""
+        ctrl = self.controller
+        if self._can_fuse():
+            self.model.params_dist = self.mpf.prior  # (what the context's configuration and an unfused period read)
+            ctx = ctrl._ensure_ctx(self.model)
+            if ctrl._tf is not None:
+                ctx.set_sigma_scale(ctrl._tf.scale)
+            pend = self._pending
+            st = torch.as_tensor(state, dtype=torch.float).reshape(-1).numpy()
+            acts = None if actions is None else torch.as_tensor(actions, dtype=torch.float).numpy()
+            costs, omega, a_seq, _, bw = ctx.amppi_dual_tick(self.mpf._dev, st, None if pend is None else pend[0], acts,
+                                                            shared_params=ctrl.params_sampling == "single", mpf_steps=self.mpf_steps,
+                                                            mpf_bw=self.mpf_bw, seed=self._seed + 1, roll=self.roll)
+            self._seed, self._pending = self._seed + 1, None  # (a refused call consumes neither the key nor the noted update)
+            if pend is not None:
+                self.last_bw = bw
+            self.last_costs = torch.from_numpy(costs)
+            self.ticks += 1
+            return torch.from_numpy(a_seq), torch.from_numpy(omega)
+        self._flush()
+        self.model.params_dist = self.mpf.prior
+        keep, ctrl.return_rollouts = ctrl.return_rollouts, False
+        try:
+            costs, _, _, omega = ctrl.update_actions(self.model, state, actions)
+        finally:
+            ctrl.return_rollouts = keep
+        a_seq = ctrl.a_seq
+        if self.roll > 0:
+            ctrl.roll(self.roll)
+        self.last_costs = costs
+        self.ticks += 1
+        return a_seq, omega
+
+    def _flush(self):
+        """A filter update noted by a fused step() and not carried out yet: run it now."""
+        pend, self._pending = self._pending, None
+        if pend is not None:
+            a = torch.as_tensor(pend[0], dtype=torch.float).reshape(-1)
+            _, self.last_bw = self.mpf.optimize(a.squeeze() if a.numel() == 1 else a, pend[1], bw=self.mpf_bw, n_steps=self.mpf_steps)
+
+    def step(self, action, new_state):
+        if self._can_fuse():  # carried out by the next forward(new_state)
+            self._flush()
+            self._pending = (torch.as_tensor(action, dtype=torch.float).reshape(-1).numpy().copy(),
+                             torch.as_tensor(new_state, dtype=torch.float).reshape(-1).clone())
+            return None, None
+        a = torch.as_tensor(action, dtype=torch.float).reshape(-1)
+        grads, bw = self.mpf.optimize(a.squeeze() if a.numel() == 1 else a, new_state, bw=self.mpf_bw, n_steps=self.mpf_steps)
+        self.last_bw = bw
+        return grads, bw
+
+    def tick(self, state, plant):
+        """One loop iteration with a host plant callable `plant(state, action) -> new_state`: forward, plant, step.
+        Returns (action, new_state, omega)."""
+        a_seq, omega = self.forward(state)
+        action = a_seq[0]
+        new_state = plant(state, action)
+        self.step(action, new_state)
+        return action, new_state, omega

@@ -59,6 +59,15 @@ struct AmppiArgs {
   unsigned int *ticket;
 };
 
+// The filter's prior beside AmppiArgs (PRIOR instances): a uniform mixture of K normals N(means[k], diag(bw)^2) over P <= 4 columns
+struct AmppiPrior {
+  const float *means;  // [K][P]: the filter's particles, read in place
+  int K, P;
+  float bw[4];
+  uint64_t seed;      // the Philox key of dust_mpf_prior_sample(m, S, seed)
+  float *params_out;  // [S][P] or nullptr: the rows as drawn
+};
+
 // sum_k w[k] (x_k - goal_k)^2 as the quadratic family's kernels form it (skid.hpp / cartpole.hpp), without the control term
 template <int DS>
 __device__ __forceinline__ float amppi_quad(const float *x, const float *goal, const float *w) {
@@ -76,9 +85,40 @@ struct AmppiDims {
   static constexpr int DS = MODEL == DUST_MODEL_PENDULUM ? 2 : (MODEL == DUST_MODEL_SKID_STEER ? 5 : 4);
 };
 
+// ---- a parameter row held in registers (the filter-coupled "extended" mode: AmppiPrior).  A local float[4] read as row[p.col] goes to
+// scratch memory; the four entries are read first and the column picks among them (the pattern of mpf.hpp's sel4f).
+__device__ __forceinline__ float amppi_row_at(const float *row, const int c) {
+  const float v0 = row[0], v1 = row[1], v2 = row[2], v3 = row[3];
+  return c == 0 ? v0 : (c == 1 ? v1 : (c == 2 ? v2 : v3));
+}
+// skid_param(p, row, 0) on such a row
+__device__ __forceinline__ float amppi_row_param(const DevParam &p, const float *row) {
+  return p.kind == DUST_PARAM_SAMPLED ? amppi_row_at(row, p.col) : (float)p.value;
+}
+// make_coef(dm, row) (common.hpp) on such a row, log_space = 0
+__device__ __forceinline__ Val amppi_row_val(const DevParam &p, const float *row) {
+  if (p.kind == DUST_PARAM_SAMPLED) return v_t(amppi_row_at(row, p.col));
+  if (p.kind == DUST_PARAM_TENSOR0D) return v_t((float)p.value);
+  return v_py(p.value);
+}
+__device__ __forceinline__ Coef amppi_row_coef(const DevModel &dm, const float *row) {
+  Coef c;
+  if (dm.model == DUST_MODEL_PENDULUM) {
+    Val g = amppi_row_val(dm.g, row), m = amppi_row_val(dm.mass, row), l = amppi_row_val(dm.length, row);
+    c.c0 = tof(v_div(v_mul(v_py(-3.0), g), v_mul(v_py(2.0), l)));
+    c.c1 = tof(v_div(v_py(3.0), v_mul(m, v_sq(l))));
+  } else {
+    c.c0 = tof(amppi_row_val(dm.mass, row));
+    c.c1 = 0.f;
+  }
+  return c;
+}
+
 // One trajectory on one parameter row: -> sum_t inst(x_t), t = 1 .. H, and term(x_H); `so`: its [H + 1][DS] states or nullptr
 // NAV (skid-steer only): the navigation cost family of skid.hpp - w_obs occ(x_0, x_1) joins both parts; `nav` and `map` are read by it alone
-template <int MODEL, bool NAV>
+// ROW: `prow` is a parameter row the lane drew itself (AmppiPrior below), a local float[4]: its run-time columns are read through selects
+// (amppi_row_at), so that the row stays in registers
+template <int MODEL, bool NAV, bool ROW = false>
 __device__ __forceinline__ void amppi_traj(const AmppiArgs &a, const float *acts, const float *prow, float *so, float *inst_out, float *term_out,
                                            const SkidNav *nav, const DevModel *map) {
   constexpr int DS = AmppiDims<MODEL>::DS;
@@ -91,7 +131,9 @@ __device__ __forceinline__ void amppi_traj(const AmppiArgs &a, const float *acts
     for (int k = 0; k < DS; ++k) so[k] = x[k];
   double tot = 0.0;
   if constexpr (MODEL == DUST_MODEL_PENDULUM || MODEL == DUST_MODEL_PARTICLE) {
-    const Coef c = make_coef(a.dm, prow);
+    Coef c;
+    if constexpr (ROW) c = amppi_row_coef(a.dm, prow);
+    else c = make_coef(a.dm, prow);
     const float zero[2] = {0.f, 0.f};  // (Particle.default_inst_cost(states): actions = 0, particle.py:170)
     for (int t = 0; t < H; ++t) {
       float u[2];
@@ -105,7 +147,16 @@ __device__ __forceinline__ void amppi_traj(const AmppiArgs &a, const float *acts
     }
     *term_out = term_cost<MODEL>(a.dm, x);
   } else if constexpr (MODEL == DUST_MODEL_SKID_STEER) {
-    const float xicr = skid_param(a.sk.x_icr, prow, 0), wr = skid_param(a.sk.wheel_radius, prow, 0), ad = skid_param(a.sk.axial_distance, prow, 0);
+    float xicr, wr, ad;
+    if constexpr (ROW) {
+      xicr = amppi_row_param(a.sk.x_icr, prow);
+      wr = amppi_row_param(a.sk.wheel_radius, prow);
+      ad = amppi_row_param(a.sk.axial_distance, prow);
+    } else {
+      xicr = skid_param(a.sk.x_icr, prow, 0);
+      wr = skid_param(a.sk.wheel_radius, prow, 0);
+      ad = skid_param(a.sk.axial_distance, prow, 0);
+    }
     for (int t = 0; t < H; ++t) {
       const float a0 = acts[2 * t], a1 = acts[2 * t + 1];
       skid_step(x, clampf(a0, a.sk.lo[0], a.sk.hi[0]), clampf(a1, a.sk.lo[1], a.sk.hi[1]), xicr, wr, ad, a.dt);
@@ -123,7 +174,10 @@ __device__ __forceinline__ void amppi_traj(const AmppiArgs &a, const float *acts
                        (a.cp.par[CP_LEN].kind == DUST_PARAM_PYFLOAT || (a.cp.par[CP_LEN].kind == DUST_PARAM_SAMPLED && !have_rows));
     float v[CP_NPAR];
 #pragma unroll
-    for (int q = 0; q < CP_NPAR; ++q) v[q] = skid_param(a.cp.par[q], prow, 0);
+    for (int q = 0; q < CP_NPAR; ++q) {
+      if constexpr (ROW) v[q] = amppi_row_param(a.cp.par[q], prow);
+      else v[q] = skid_param(a.cp.par[q], prow, 0);
+    }
     const CartCoef kf = cartpole_coef(v, pm_py, a.cp.par[CP_MP].value * a.cp.par[CP_LEN].value, a.dt);
     for (int t = 0; t < H; ++t) {
       cartpole_step(x, clampf(acts[t], -1.0f, 1.0f), kf, fast_sinf(x[2]), fast_cosf(x[2]));
@@ -139,8 +193,9 @@ __device__ __forceinline__ void amppi_traj(const AmppiArgs &a, const float *acts
 
 template <int MODEL>
 __global__ __launch_bounds__(AMPPI_THREADS) void amppi_kernel(const AmppiArgs a) {
-  constexpr bool NAV = false;
+  constexpr bool NAV = false, PRIOR = false;
   const SkidNav *const nav = nullptr;
+  const AmppiPrior *const pri = nullptr;
   uint32_t *const grid_lds = nullptr;
 #include "amppi_body.inc"
 }
@@ -152,9 +207,40 @@ struct AmppiNavArgs {
 };
 __global__ __launch_bounds__(AMPPI_THREADS) void amppi_skid_nav_kernel(const AmppiNavArgs k) {
   constexpr int MODEL = DUST_MODEL_SKID_STEER;
-  constexpr bool NAV = true;
+  constexpr bool NAV = true, PRIOR = false;
   const AmppiArgs &a = k.a;
   const SkidNav *const nav = &k.nav;
+  const AmppiPrior *const pri = nullptr;
+  extern __shared__ __attribute__((aligned(16))) uint32_t grid_lds[];
+#include "amppi_body.inc"
+}
+
+// The "extended" mode coupled to a dynamics filter (dust_amppi_dual_tick): lane s draws row s of mpf.prior.sample([S]) itself - the
+// stream of mpf_sample_kernel (mpf.hpp), bit for bit - and rolls its trajectory out on it: no parameter buffer, no launch of its own.
+struct AmppiPriorArgs {
+  AmppiArgs a;
+  AmppiPrior pr;
+};
+template <int MODEL>
+__global__ __launch_bounds__(AMPPI_THREADS) void amppi_prior_kernel(const AmppiPriorArgs k) {
+  constexpr bool NAV = false, PRIOR = true;
+  const AmppiArgs &a = k.a;
+  const SkidNav *const nav = nullptr;
+  const AmppiPrior *const pri = &k.pr;
+  uint32_t *const grid_lds = nullptr;
+#include "amppi_body.inc"
+}
+struct AmppiNavPriorArgs {
+  AmppiArgs a;
+  SkidNav nav;
+  AmppiPrior pr;
+};
+__global__ __launch_bounds__(AMPPI_THREADS) void amppi_skid_nav_prior_kernel(const AmppiNavPriorArgs k) {
+  constexpr int MODEL = DUST_MODEL_SKID_STEER;
+  constexpr bool NAV = true, PRIOR = true;
+  const AmppiArgs &a = k.a;
+  const SkidNav *const nav = &k.nav;
+  const AmppiPrior *const pri = &k.pr;
   extern __shared__ __attribute__((aligned(16))) uint32_t grid_lds[];
 #include "amppi_body.inc"
 }

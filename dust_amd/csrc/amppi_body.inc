@@ -2,6 +2,7 @@
 // them: amppi_kernel<MODEL> and amppi_skid_nav_kernel.  Text, not a function: hipcc schedules the plain instances differently once their
 // body is an inlined callee, and they are to stay the instructions they were.  In scope at the point of inclusion:
 //   MODEL (int), NAV (constexpr bool), a (const AmppiArgs &), nav (const SkidNav *, NAV only), grid_lds (uint32_t *: dynamic LDS, NAV only)
+//   PRIOR (constexpr bool), pri (const AmppiPrior *, PRIOR only): the lane draws its own parameter row from the filter's prior
 // The static __shared__ object below is declared once per including kernel; the NAV kernel's dynamic LDS lies behind it.
 // BEFORE turning this text into a function (or moving a declaration out of it): build both ways for gfx950 and compare the disassembly and
 // the register metadata of the four amppi_kernel instances - as a force-inlined callee they came out 2-3 instructions longer, with another
@@ -49,7 +50,22 @@
     }
     const float ctrl = a.lambda * (float)cc;
     float inst = 0.f, term = 0.f;
-    if (a.mode == AMPPI_PARAMS_SIGMA) {
+    if constexpr (PRIOR) {
+      // row s of mpf.prior.sample([S]) as mpf_sample_kernel (mpf.hpp) draws it: the same counters, the same operations in the same order
+      uint32_t r[4];
+      philox4x32_10((uint32_t)s, 0x6d7066u, 0u, 0u, (uint32_t)pri->seed, (uint32_t)(pri->seed >> 32), r);
+      const int kc = (int)(((unsigned long long)r[0] * (unsigned long long)pri->K) >> 32);
+      float zp[4], row[4];
+      philox_normal4(pri->seed, (uint32_t)s, 0x6d7067u, 1u, 0u, zp);
+#pragma unroll
+      for (int p = 0; p < 4; ++p) row[p] = p < pri->P ? pri->means[kc * pri->P + p] + pri->bw[p] * zp[p] : 0.f;
+      if (pri->params_out)
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+          if (p < pri->P) pri->params_out[(size_t)s * pri->P + p] = row[p];
+      float *so = a.states_out ? a.states_out + (size_t)s * (size_t)(H + 1) * DS : nullptr;
+      amppi_traj<MODEL, NAV, true>(a, acts, row, so, &inst, &term, nav, map);
+    } else if (a.mode == AMPPI_PARAMS_SIGMA) {
       double wi = 0.0, wt = 0.0;
       for (int k = 0; k < a.pts; ++k) {
         float ik, tk;

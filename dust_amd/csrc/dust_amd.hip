@@ -175,6 +175,7 @@ struct dust_ctx {
   float *theta_home, *theta_alt;  // theta ping-pong of the fused Stein+update launch (theta == one of the two)
   bool theta_pinned;              // dust_gather_buffers handed theta's address out: no ping-pong any more
   const float *graph_theta;       // theta at the start of the captured tick
+  hipEvent_t ev_dual;          // dust_amppi_dual_tick without output copies: behind the kernels that read the filter's particles (created on first use)
   unsigned int *amppi_ticket;  // dust_amppi_update: the arrival word of its workgroups (zeroed by a memset node ahead of every launch)
   unsigned int *stein_cnt;  // [tiles + 1]: arrival counters of the Stein+update launch (re-armed by the next rollout launch)
   int stein_tiles;
@@ -548,6 +549,7 @@ static void free_all(dust_ctx *c) {
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   if (c->ev_join) (void)hipEventDestroy(c->ev_join);
   if (c->ev_order) (void)hipEventDestroy(c->ev_order);
+  if (c->ev_dual) (void)hipEventDestroy(c->ev_dual);
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
 }
 
@@ -1303,8 +1305,11 @@ static int amppi_check(const dust_ctx *c) {
   return DUST_OK;
 }
 
-extern "C" int dust_amppi_update(dust_ctx *c, const float *state, const float *actions, const float *params, int flags,
-                                 float *costs, float *omega, float *a_seq) {
+// dust_amppi_update's body.  dust_amppi_dual_tick (mpf.hpp) enters with `staged` (the parameter rows already sit in params_dev, written
+// there on the context's stream: `params` is then only "there are rows") or with `prior` (the lanes draw their rows themselves from the
+// filter's prior, "extended": no parameter buffer at all; prior->params_out, when set, has room for [S][P])
+static int amppi_update_impl(dust_ctx *c, const float *state, const float *actions, const float *params, int flags, float *costs, float *omega,
+                             float *a_seq, const bool staged, const dust::AmppiPrior *prior) {
   if (!c || !state) return fail(DUST_ERR_INVALID, "null argument");
   TRY(amppi_check(c));
   if (flags & (DUST_EPS_F16 | DUST_STORE_F16)) return fail(DUST_ERR_UNSUPPORTED, "the AMPPI tick has no binary16 storage");
@@ -1318,11 +1323,15 @@ extern "C" int dust_amppi_update(dust_ctx *c, const float *state, const float *a
     prows = (size_t)(pts = c->M);
   } else if (c->M != 1) {
     return fail(DUST_ERR_INVALID, "n_params = %d > 1 is the sigma-point form of an AMPPI context: dust_set_param_weights first", c->M);
+  } else if (prior) {
+    if (P < 1 || P != prior->P) return fail(DUST_ERR_INVALID, "a prior over %d parameters for a context with dim_p = %d", prior->P, P);
+    mode = AMPPI_PARAMS_EXTENDED;
   } else if (params) {
     if (P < 1) return fail(DUST_ERR_INVALID, "parameter rows without uncertain parameters (dim_p = 0)");
     mode = (flags & DUST_AMPPI_PARAMS_SHARED) ? AMPPI_PARAMS_SINGLE : AMPPI_PARAMS_EXTENDED;
     prows = mode == AMPPI_PARAMS_SINGLE ? 1 : (size_t)S;
   }
+  if (prior && mode != AMPPI_PARAMS_EXTENDED) return fail(DUST_ERR_INVALID, "in-kernel parameter draws are the \"extended\" mode");
   TRY(settle_pending(c));
   HIP_TRY(hipSetDevice(c->cfg.device));
   if (!c->amppi_ticket) TRY(dalloc(&c->amppi_ticket, (size_t)1));
@@ -1333,7 +1342,7 @@ extern "C" int dust_amppi_update(dust_ctx *c, const float *state, const float *a
   }
   if (prows) {
     TRY(ensure(&c->params_dev, &c->params_cap, prows * P));
-    TRY(h2d(c, c->params_dev, params, prows * P * sizeof(float)));
+    if (!staged) TRY(h2d(c, c->params_dev, params, prows * P * sizeof(float)));
   }
   const bool want_states = (flags & DUST_STORE_STATES) != 0;
   if (want_states) TRY(ensure(&c->states, &c->states_cap, (size_t)S * pts * (c->H + 1) * c->ds));
@@ -1382,7 +1391,27 @@ extern "C" int dust_amppi_update(dust_ctx *c, const float *state, const float *a
     TRY(skid_nav_args(c, kn.nav));
   }
   HIP_TRY(hipMemsetAsync(c->amppi_ticket, 0, sizeof(unsigned int), c->stream));
-  {
+  if (prior) {
+    Prof pr(c, DUST_K_AMPPI);
+    if (nav) {
+      AmppiNavPriorArgs kp;
+      kp.a = a;
+      kp.nav = kn.nav;
+      kp.pr = *prior;
+      amppi_skid_nav_prior_kernel<<<grid, AMPPI_THREADS, (size_t)kn.nav.grid_words * sizeof(uint32_t), c->stream>>>(kp);
+    } else {
+      AmppiPriorArgs kp;
+      kp.a = a;
+      kp.pr = *prior;
+      switch (c->cfg.model) {
+        case DUST_MODEL_PENDULUM: amppi_prior_kernel<DUST_MODEL_PENDULUM><<<grid, AMPPI_THREADS, 0, c->stream>>>(kp); break;
+        case DUST_MODEL_PARTICLE: amppi_prior_kernel<DUST_MODEL_PARTICLE><<<grid, AMPPI_THREADS, 0, c->stream>>>(kp); break;
+        case DUST_MODEL_SKID_STEER: amppi_prior_kernel<DUST_MODEL_SKID_STEER><<<grid, AMPPI_THREADS, 0, c->stream>>>(kp); break;
+        default: amppi_prior_kernel<DUST_MODEL_CARTPOLE><<<grid, AMPPI_THREADS, 0, c->stream>>>(kp); break;
+      }
+    }
+    HIP_TRY(hipGetLastError());
+  } else {
     Prof pr(c, DUST_K_AMPPI);
     if (nav) amppi_skid_nav_kernel<<<grid, AMPPI_THREADS, (size_t)kn.nav.grid_words * sizeof(uint32_t), c->stream>>>(kn);
     else switch (c->cfg.model) {
@@ -1402,6 +1431,11 @@ extern "C" int dust_amppi_update(dust_ctx *c, const float *state, const float *a
   if (omega) TRY(d2h(c, omega, c->omegaT, (size_t)S * sizeof(float)));
   if (a_seq) TRY(d2h(c, a_seq, c->a_seq, (size_t)D * sizeof(float)));
   return DUST_OK;
+}
+
+extern "C" int dust_amppi_update(dust_ctx *c, const float *state, const float *actions, const float *params, int flags,
+                                 float *costs, float *omega, float *a_seq) {
+  return amppi_update_impl(c, state, actions, params, flags, costs, omega, a_seq, false, nullptr);
 }
 
 extern "C" int dust_amppi_roll(dust_ctx *c, int steps) {

@@ -1860,17 +1860,8 @@ extern "C" int dust_mpf_silverman(dust_mpf *m, float *bw) {
   return DUST_OK;
 }
 
-// One control period of the DUAL loop (simulations.py:104-138) in one call: the filter update for the action just applied and the state
-// it led to (mpf.optimize(action, state, bw, n_steps): skipped when action_prev is NULL - the first period), then the controller's
-// dynamics samples drawn from the filter's refreshed prior ON THE DEVICE, straight into the controller's parameter buffer (n_steps
-// draws of [M][P]: disco.py:171, one per SVGD iteration), then the control tick (optimize + forward).  mpf_bw <= 0: Silverman's rule of
-// the filter's particles (mpf.py:68-73), evaluated on the device.  Host round trips: the 4-byte bandwidth and the filter's status words
-// (the stream is idle there: the caller has just used the previous tick's outputs), then the tick's outputs.  seed: the Philox key of
-// this period's draws (dust_mpf_prior_sample's stream).  *bw_used: the bandwidth the filter update ran with (0: no update).
-extern "C" int dust_dual_tick(dust_ctx *c, dust_mpf *m, const float *state, const float *action_prev, int n_steps, int mpf_steps, float bw_in,
-                              uint64_t seed, float *a_seq, float *p_weights, float *bw_used) {
-  if (!c || !m || !state) return fail(DUST_ERR_INVALID, "null argument");
-  if (n_steps < 1 || mpf_steps < 0) return fail(DUST_ERR_INVALID, "bad step counts");
+// What a controller and a filter must agree on before one call runs a period of both (dust_dual_tick, dust_amppi_dual_tick)
+static int dual_pair_check(const dust_ctx *c, const dust_mpf *m) {
   if (c->cfg.dim_p != m->P) return fail(DUST_ERR_INVALID, "the controller samples dim_p = %d dynamics parameters, the filter carries P = %d", c->cfg.dim_p, m->P);
   if (c->cfg.device != m->cfg.device) return fail(DUST_ERR_INVALID, "controller and filter live on different devices");
   if (c->cfg.model == DUST_MODEL_SKID_STEER && m->cfg.model_cfg.model == DUST_MODEL_SKID_STEER) {  // the filter's columns are the controller's
@@ -1888,6 +1879,21 @@ extern "C" int dust_dual_tick(dust_ctx *c, dust_mpf *m, const float *state, cons
         return fail(DUST_ERR_INVALID, "controller and filter name different uncertain cart-pole parameters (or in another column order)");
     }
   }
+  return DUST_OK;
+}
+
+// One control period of the DUAL loop (simulations.py:104-138) in one call: the filter update for the action just applied and the state
+// it led to (mpf.optimize(action, state, bw, n_steps): skipped when action_prev is NULL - the first period), then the controller's
+// dynamics samples drawn from the filter's refreshed prior ON THE DEVICE, straight into the controller's parameter buffer (n_steps
+// draws of [M][P]: disco.py:171, one per SVGD iteration), then the control tick (optimize + forward).  mpf_bw <= 0: Silverman's rule of
+// the filter's particles (mpf.py:68-73), evaluated on the device.  Host round trips: the 4-byte bandwidth and the filter's status words
+// (the stream is idle there: the caller has just used the previous tick's outputs), then the tick's outputs.  seed: the Philox key of
+// this period's draws (dust_mpf_prior_sample's stream).  *bw_used: the bandwidth the filter update ran with (0: no update).
+extern "C" int dust_dual_tick(dust_ctx *c, dust_mpf *m, const float *state, const float *action_prev, int n_steps, int mpf_steps, float bw_in,
+                              uint64_t seed, float *a_seq, float *p_weights, float *bw_used) {
+  if (!c || !m || !state) return fail(DUST_ERR_INVALID, "null argument");
+  if (n_steps < 1 || mpf_steps < 0) return fail(DUST_ERR_INVALID, "bad step counts");
+  TRY(dual_pair_check(c, m));
   if (comm_active(c)) return fail(DUST_ERR_UNSUPPORTED, "the dual tick runs on an unsharded controller (the filter is replicated: tick it per rank)");
   if (c->mw_dev) {  // a sigma-point controller: its dynamics samples are the sigma points of the filter's prior, not draws from it
     if (!(c->sigma_scale > 0.f))
@@ -1914,4 +1920,82 @@ extern "C" int dust_dual_tick(dust_ctx *c, dust_mpf *m, const float *state, cons
   const int st = dust_svmpc_tick(c, state, n_steps, nullptr, c->params_dev, 0, a_seq, p_weights);
   c->params_staged = false;
   return st;
+}
+
+// One control period of the dual loop over an AMPPI controller (simulations.py:104-138 with amppi.py:227-260 as the controller) in one
+// call: the filter update for (action_prev, state) - skipped when action_prev is NULL; bw_in <= 0: Silverman's rule on the device -, the
+// parameters from the refreshed prior, the AMPPI update, the outputs, the roll.  The parameters:
+//   "extended" (no flag)            lane s of the tick's kernel draws row s of dust_mpf_prior_sample(m, S, seed) itself (amppi.hpp:
+//                                   amppi_prior_kernel): no parameter buffer, no launch besides the tick's;
+//   DUST_AMPPI_PARAMS_SHARED        one row (mpf_sample_kernel, n = 1) staged into the controller's parameter buffer on ITS stream;
+//   sigma weights + a scale         the 2P + 1 sigma points of the prior (mpf_sigma_points_kernel), staged the same way.
+// params_out (host, or NULL): the rows the tick used - [S][P], [1][P], [2P + 1][P].  a_seq: the sequence after the update, BEFORE the roll.
+// The tick's kernels read the filter's particles in place on the controller's stream; the next filter update writes them on the filter's
+// stream.  A host copy of an output drains the controller's stream; without one the filter's stream is made to wait for an event behind
+// the kernels.
+extern "C" int dust_amppi_dual_tick(dust_ctx *c, dust_mpf *m, const float *state, const float *action_prev, const float *actions, int flags,
+                                    int mpf_steps, float bw_in, uint64_t seed, int roll_steps, float *costs, float *omega, float *a_seq,
+                                    float *params_out, float *bw_used) {
+  if (!c || !m || !state) return fail(DUST_ERR_INVALID, "null argument");
+  if (mpf_steps < 0 || roll_steps < 0) return fail(DUST_ERR_INVALID, "bad step counts");
+  TRY(amppi_check(c));  // (n_policies = 1, not sharded, no params_log_space, ...)
+  TRY(dual_pair_check(c, m));
+  if (m->cfg.log_space) return fail(DUST_ERR_UNSUPPORTED, "a log-space filter under AMPPI: the controller hands samples to the model as drawn (amppi.py:134-139)");
+  if (flags & DUST_STORE_STATES) return fail(DUST_ERR_UNSUPPORTED, "the AMPPI dual tick stores no trajectories");
+  if (flags & (DUST_EPS_F16 | DUST_STORE_F16)) return fail(DUST_ERR_UNSUPPORTED, "the AMPPI tick has no binary16 storage");  // (ahead of any staging launch)
+  const bool sigma = c->mw_dev != nullptr, shared = (flags & DUST_AMPPI_PARAMS_SHARED) != 0;
+  if (sigma) {
+    if (!(c->sigma_scale > 0.f))
+      return fail(DUST_ERR_UNSUPPORTED, "the dual tick over sigma-point weights needs the transform's scale lambda + n (dust_set_sigma_scale)");
+    if (c->M != 2 * m->P + 1) return fail(DUST_ERR_INVALID, "sigma-point weights over P = %d parameters take M = 2 P + 1 = %d samples, the controller has M = %d", m->P, 2 * m->P + 1, c->M);
+  } else if (c->M != 1) {
+    return fail(DUST_ERR_INVALID, "n_params = %d > 1 is the sigma-point form of an AMPPI context: dust_set_param_weights first", c->M);
+  }
+  if (m->P < 1 || m->P > 4 || m->Mp > 1024) return fail(DUST_ERR_UNSUPPORTED, "the AMPPI dual tick takes a filter of up to 1024 particles over 1 .. 4 parameters");
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  float bw = bw_in;
+  if (action_prev) {
+    if (!(bw > 0.f)) TRY(dust_mpf_silverman(m, &bw));
+    TRY(dust_mpf_optimize(m, action_prev, state, bw, mpf_steps, nullptr));  // (synchronises the filter's stream: its particles are final)
+  } else {  // no update: whatever wrote the particles last on the filter's stream comes first - without waiting on the host
+    if (!c->ev_dual) HIP_TRY(hipEventCreateWithFlags(&c->ev_dual, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(c->ev_dual, m->stream));
+    HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_dual, 0));
+  }
+  if (bw_used) *bw_used = action_prev ? bw : 0.f;
+  TRY(settle_pending(c));
+  const int P = m->P;
+  const size_t prows = sigma ? (size_t)c->M : (shared ? (size_t)1 : (size_t)c->S);
+  if (sigma || shared || params_out) TRY(ensure(&c->params_dev, &c->params_cap, prows * P));
+  int st;
+  if (sigma || shared) {
+    if (sigma) dust::mpf_sigma_points_kernel<<<1, 256, 0, c->stream>>>(m->x, m->Mp, P, mpf_bw(m), c->sigma_scale, 1, c->params_dev);
+    else dust::mpf_sample_kernel<<<1, 256, 0, c->stream>>>(m->x, m->Mp, P, mpf_bw(m), seed, 1, c->params_dev);
+    HIP_TRY(hipGetLastError());
+    st = amppi_update_impl(c, state, actions, c->params_dev, flags, nullptr, nullptr, nullptr, true, nullptr);
+  } else {
+    dust::AmppiPrior pr;
+    memset(&pr, 0, sizeof pr);
+    pr.means = m->x;
+    pr.K = m->Mp;
+    pr.P = P;
+    const dust::MpfBw b = mpf_bw(m);
+    for (int p = 0; p < 4; ++p) pr.bw[p] = b.v[p];
+    pr.seed = seed;
+    pr.params_out = params_out ? c->params_dev : nullptr;
+    st = amppi_update_impl(c, state, actions, nullptr, flags, nullptr, nullptr, nullptr, false, &pr);
+  }
+  if (st != DUST_OK) return st;
+  const bool copies = costs || omega || a_seq || params_out;
+  if (costs) TRY(d2h(c, costs, c->costsT, (size_t)c->S * sizeof(float)));
+  if (omega) TRY(d2h(c, omega, c->omegaT, (size_t)c->S * sizeof(float)));
+  if (a_seq) TRY(d2h(c, a_seq, c->a_seq, (size_t)c->D * sizeof(float)));
+  if (params_out) TRY(d2h(c, params_out, c->params_dev, prows * P * sizeof(float)));
+  if (roll_steps > 0) TRY(dust_amppi_roll(c, roll_steps));
+  if (!copies) {  // nothing drained the controller's stream: the filter's next update waits for the kernels that read its particles
+    if (!c->ev_dual) HIP_TRY(hipEventCreateWithFlags(&c->ev_dual, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(c->ev_dual, c->stream));
+    HIP_TRY(hipStreamWaitEvent(m->stream, c->ev_dual, 0));
+  }
+  return DUST_OK;
 }

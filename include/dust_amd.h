@@ -521,6 +521,26 @@ int dust_mpf_sigma_points(dust_mpf *mpf, float scale, float *out);
  * without dust_set_sigma_scale or with params_log_space (disco.py:125), DUST_ERR_INVALID unless M = 2P + 1. */
 int dust_dual_tick(dust_ctx *ctx, dust_mpf *mpf, const float *state, const float *action_prev, int n_steps, int mpf_steps, float mpf_bw,
                    uint64_t seed, float *a_seq, float *p_weights, float *bw_used);
+/* One control period of the dual loop over an AMPPI controller (simulations.py:104-138 around amppi.py:227-260) in ONE call, ABI 3:
+ *   1. mpf.optimize(action_prev, state, bw, mpf_steps) - skipped when action_prev is NULL; mpf_bw <= 0: Silverman's rule on the device;
+ *   2. the parameters from the refreshed prior (model.params_dist = mpf.prior):
+ *        no flag                      "extended": trajectory s rolls out on row s of dust_mpf_prior_sample(mpf, S, seed), which its lane
+ *                                     draws inside the tick's kernel - no parameter buffer, no extra launch, no host copy;
+ *        DUST_AMPPI_PARAMS_SHARED     "single": row 0 of dust_mpf_prior_sample(mpf, 1, seed), staged on the device;
+ *        sigma weights and a scale    (dust_set_param_weights, dust_set_sigma_scale) the 2P + 1 points of dust_mpf_sigma_points(mpf, scale),
+ *                                     staged on the device; seed unused;
+ *   3. dust_amppi_update(state, actions, those parameters); actions NULL: device-drawn noise from the context's own stream;
+ *   4. outputs, each may be NULL: costs [S], omega [S], a_seq [H][da] after the update and BEFORE the roll, params_out - the rows the
+ *      tick used ([S][P], [1][P] or [2P + 1][P]) -, *bw_used (0 without a filter update);
+ *   5. dust_amppi_roll(roll_steps) when roll_steps > 0.
+ * DUST_ERR_INVALID / DUST_ERR_UNSUPPORTED: whatever dust_amppi_update refuses (n_policies != 1, sharded contexts, ...), dim_p != the
+ * filter's P (this covers "none"), different devices, controller and filter naming different skid-steer / cart-pole parameters or column
+ * orders (as dust_dual_tick), a log-space filter (amppi.py:134-139 hands samples to the model as drawn), sigma weights without a scale or
+ * with n_params != 2P + 1, DUST_STORE_STATES.  With every output NULL the call returns without waiting for the device; the filter's
+ * stream is ordered behind the tick's kernels, which read its particles in place. */
+int dust_amppi_dual_tick(dust_ctx *ctx, dust_mpf *mpf, const float *state, const float *action_prev, const float *actions, int flags,
+                         int mpf_steps, float mpf_bw, uint64_t seed, int roll_steps, float *costs, float *omega, float *a_seq,
+                         float *params_out, float *bw_used);
 
 #ifdef __cplusplus
 }
