@@ -137,6 +137,15 @@ SYMBOLS = {
     "dust_svmpc_serve_stop": (C.c_int, [VP]),
     "dust_amppi_update": (C.c_int, [VP, FP, VP, FP, C.c_int, FP, FP, FP]),
     "dust_amppi_roll": (C.c_int, [VP, C.c_int]),
+    "dust_amppi_batch_create": (C.c_int, [VP, C.c_int, C.POINTER(C.c_uint64), C.POINTER(VP)]),
+    "dust_amppi_batch_destroy": (None, [VP]),
+    "dust_amppi_batch_clone": (C.c_int, [VP, C.POINTER(VP)]),
+    "dust_amppi_batch_set_a_seq": (C.c_int, [VP, FP]),
+    "dust_amppi_batch_get_a_seq": (C.c_int, [VP, FP]),
+    "dust_amppi_batch_ctx": (C.c_int, [VP, C.POINTER(VP)]),
+    "dust_amppi_batch_update": (C.c_int, [VP, FP, VP, FP, C.c_int, C.POINTER(C.c_ubyte), FP, FP, FP]),
+    "dust_amppi_batch_roll": (C.c_int, [VP, C.c_int, C.POINTER(C.c_ubyte)]),
+    "dust_amppi_batch_get_actions": (C.c_int, [VP, FP]),
     "dust_get_costs": (C.c_int, [VP, FP]),
     "dust_get_actions": (C.c_int, [VP, FP]),
     "dust_get_states_rows": (C.c_int, [VP, C.POINTER(C.c_longlong), C.c_int, VP]),

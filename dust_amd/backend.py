@@ -270,7 +270,8 @@ class Context:
 
     def close(self):
         if self._h is not None:
-            L.load().dust_destroy(self._h)
+            if not getattr(self, "_borrowed", False):  # (an AmppiBatch's inner context belongs to the batch)
+                L.load().dust_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -586,6 +587,11 @@ class Context:
         """BaseController.roll(steps): the sequence moves `steps` rows forward, zeros behind (dust_amppi_roll)."""
         L.check(L.load().dust_amppi_roll(self._h, int(steps)))
 
+    def amppi_batch(self, n_envs, seeds=None):
+        """`n_envs` independent AMPPI controllers of this context's configuration, one kernel launch per tick (dust_amppi_batch_create):
+        the batch keeps its own copy of the context.  seeds [n_envs] (None: this context's seed + b)."""
+        return AmppiBatch(self, n_envs, seeds)
+
     def get_costs(self):
         return self._get(L.load().dust_get_costs, (self.S, self.N))
 
@@ -653,6 +659,104 @@ class Context:
 
     def device_free(self, ptr):
         L.check(L.load().dust_device_free(self._h, L.VP(ptr)))
+
+
+def _mask(active, B):
+    """the active mask as [B] bytes (None: everybody) -> (array or None, ctypes pointer or None)"""
+    if active is None:
+        return None, None
+    m = np.ascontiguousarray(np.asarray(active).reshape(-1) != 0, dtype=np.uint8)
+    if m.shape != (B,):
+        raise ValueError("active has %d entries, the batch has %d environments" % (m.size, B))
+    return m, m.ctypes.data_as(C.POINTER(C.c_ubyte))
+
+
+class AmppiBatch:
+    """B independent AMPPI ticks in one launch (dust_amppi_batch_*): per environment a state, a nominal sequence, a noise stream and
+    parameter rows; model, cost, horizon, S, lambda and a_cov are the prototype context's.  `ctx` is the batch's inner context
+    (borrowed) for sync() and profile() / profile_get()."""
+
+    def __init__(self, proto=None, n_envs=1, seeds=None, _handle=None):
+        self._h = None
+        lib = L.load()
+        if _handle is None:
+            sd = None
+            if seeds is not None:
+                sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
+                if sd.size != int(n_envs):
+                    raise ValueError("seeds has %d entries for %d environments" % (sd.size, int(n_envs)))
+            h = L.VP()
+            L.check(lib.dust_amppi_batch_create(proto._h, int(n_envs), None if sd is None else sd.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(h)))
+            _handle = h
+        self._h = _handle
+        self.B = int(n_envs)
+        inner = L.VP()
+        L.check(lib.dust_amppi_batch_ctx(self._h, C.byref(inner)))
+        self.ctx = Context(_handle=inner)
+        self.ctx._borrowed = True
+        c = self.ctx
+        self.S, self.H, self.da, self.ds, self.P, self.M = c.S, c.H, c.da, c.ds, c.P, c.M
+
+    def close(self):
+        if self._h is not None:
+            self.ctx.close()
+            L.load().dust_amppi_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def clone(self):
+        h = L.VP()
+        L.check(L.load().dust_amppi_batch_clone(self._h, C.byref(h)))
+        return AmppiBatch(n_envs=self.B, _handle=h)
+
+    def __deepcopy__(self, memo):
+        return self.clone()
+
+    def set_a_seq(self, a):
+        L.check(L.load().dust_amppi_batch_set_a_seq(self._h, _p(_f(a, (self.B, self.H, self.da)))))
+
+    def get_a_seq(self):
+        out = np.empty((self.B, self.H, self.da), np.float32)
+        L.check(L.load().dust_amppi_batch_get_a_seq(self._h, _p(out)))
+        return out
+
+    def update(self, states, actions=None, params=None, shared_params=False, active=None, want_actions=False, want_outputs=True, flags=0):
+        """One tick of every active environment (dust_amppi_batch_update).  states [B, ds]; actions [B, S, H, da] or None (drawn on the
+        device); params None ("none"), [B, 1, P] with shared_params ("single"), [B, S, P] ("extended") or [B, 2P + 1, P] sigma points;
+        active [B] or None.  -> (costs [B, S], omega [B, S], a_seq [B, H, da] after the update, acts [B, S, H, da] or None); the rows of
+        inactive environments are NaN.  want_outputs=False reads nothing back (the tick stays asynchronous on the batch's stream)."""
+        B, S = self.B, self.S
+        st = None if states is None else _f(states, (B, self.ds))  # (None: the library refuses)
+        act = None if actions is None else _f(actions, (B, S, self.H, self.da))
+        pr = None
+        if params is not None:
+            rows = self.M if self.M > 1 else (1 if shared_params else S)
+            pr = _f(params)
+            if pr.ndim != 3 or pr.shape[0] != B or pr.shape[1] != rows or pr.shape[2] != max(self.P, 1):
+                raise ValueError("params has shape %s, the tick reads [%d, %d, %d]" % (pr.shape, B, rows, max(self.P, 1)))
+        m, mp = _mask(active, B)
+        fl = int(flags) | (L.AMPPI_PARAMS_SHARED if shared_params else 0)
+        costs = omega = a_seq = None
+        if want_outputs:
+            costs, omega, a_seq = (np.full(sh, np.nan, np.float32) for sh in ((B, S), (B, S), (B, self.H, self.da)))
+        L.check(L.load().dust_amppi_batch_update(self._h, _p(st), _vp(act), _p(pr), fl, mp, _p(costs), _p(omega), _p(a_seq)))
+        return costs, omega, a_seq, (self.get_actions() if want_actions else None)
+
+    def get_actions(self):
+        """[B, S, H, da] actions of the last tick; NaN rows for the environments that were inactive in it."""
+        out = np.full((self.B, self.S, self.H, self.da), np.nan, np.float32)
+        L.check(L.load().dust_amppi_batch_get_actions(self._h, _p(out)))
+        return out
+
+    def roll(self, steps=1, active=None):
+        """BaseController.roll(steps) of every active environment in one launch (dust_amppi_batch_roll)."""
+        _, mp = _mask(active, self.B)
+        L.check(L.load().dust_amppi_batch_roll(self._h, int(steps), mp))
 
 
 class MpfContext:

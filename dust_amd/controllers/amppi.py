@@ -112,20 +112,29 @@ class AMPPI:
             cfg["nav_map"] = nav
         return cfg
 
+    def _new_ctx(self, model, cfg):
+        """a fresh context of configuration cfg (`_config`), with the map and the sigma weights"""
+        grid = model.obst_map.map.astype(np.float32) if getattr(model, "obst_map", None) is not None else None
+        if grid is None:  # the skid-steer model has no map of its own: a NavigationCost brings it
+            grid = cost_grid(self.inst_cost_fn)
+        ctx = Context(grid=grid, **{k: v for k, v in cfg.items() if k != "nav_map"})
+        if self._tf is not None:
+            ctx.set_param_weights(self._tf.loc_weights.numpy())
+        return ctx
+
+    @staticmethod
+    def _key(cfg):
+        return repr(sorted((k, np.asarray(v).tolist() if not isinstance(v, (str, bool, int, float, tuple)) else v) for k, v in cfg.items()))
+
     def _ensure_ctx(self, model):
         cfg = self._config(model)
-        key = repr(sorted((k, np.asarray(v).tolist() if not isinstance(v, (str, bool, int, float, tuple)) else v) for k, v in cfg.items()))
+        key = self._key(cfg)
         if self._ctx is not None and key == self._ctx_key:
             return self._ctx
         a_seq = self.a_seq.numpy()
         if self._ctx is not None:
             self._ctx.close()
-        grid = model.obst_map.map.astype(np.float32) if getattr(model, "obst_map", None) is not None else None
-        if grid is None:  # the skid-steer model has no map of its own: a NavigationCost brings it
-            grid = cost_grid(self.inst_cost_fn)
-        self._ctx, self._ctx_key = Context(grid=grid, **{k: v for k, v in cfg.items() if k != "nav_map"}), key
-        if self._tf is not None:
-            self._ctx.set_param_weights(self._tf.loc_weights.numpy())
+        self._ctx, self._ctx_key = self._new_ctx(model, cfg), key
         self._ctx.set_a_seq(a_seq)
         return self._ctx
 
@@ -192,3 +201,107 @@ class AMPPI:
         costs, omega, _, states, acts_out = ctx.amppi_update(state.numpy(), acts, params, shared_params=shared, want_states=want, want_actions=want)
         t = torch.from_numpy
         return t(costs), (t(states) if want else None), (t(acts_out) if want else None), t(omega)
+
+
+class BatchAMPPI(AMPPI):
+    """`n_envs` independent AMPPI controllers of one configuration - the deep copies the reference makes per episode
+    (simulations.py) - ticking in ONE kernel launch (csrc/amppi.hpp amppi_batch_kernel).  Every environment has its own state, nominal
+    sequence, noise stream (`seeds`, default seed + b) and parameter rows; environment b computes what an `AMPPI(seed=seeds[b])`
+    computes on its inputs, bit for bit.  The constructor takes AMPPI's arguments behind `n_envs` and refuses what AMPPI refuses."""
+
+    def __init__(self, n_envs, *args, seeds=None, **kw):
+        super().__init__(*args, **kw)
+        if not 1 <= int(n_envs) <= 65535:
+            raise ValueError("n_envs = %d outside [1, 65535]" % int(n_envs))
+        self.n_envs = int(n_envs)
+        if seeds is not None and len(seeds) != self.n_envs:
+            raise ValueError("seeds has %d entries for %d environments" % (len(seeds), self.n_envs))
+        self._seeds = None if seeds is None else [int(v) for v in seeds]
+        self._a_seq = self._a_seq[None].repeat(self.n_envs, 1, 1)  # [B, H, da]
+        self._batch = None
+
+    def _ensure_batch(self, model):
+        cfg = self._config(model)
+        key = self._key(cfg)
+        if self._batch is not None and key == self._ctx_key:
+            return self._batch
+        a_seq = self.a_seq.numpy()
+        if self._batch is not None:
+            self._batch.close()
+        proto = self._new_ctx(model, cfg)
+        try:
+            self._batch, self._ctx_key = proto.amppi_batch(self.n_envs, self._seeds), key
+        finally:
+            proto.close()  # (the batch keeps its own copy)
+        self._batch.set_a_seq(a_seq)
+        return self._batch
+
+    def __deepcopy__(self, memo):
+        new = copy.copy(self)
+        memo[id(self)] = new
+        for k, v in self.__dict__.items():
+            if k == "_batch":
+                new._batch = None if v is None else v.clone()
+            elif k in ("inst_cost_fn", "term_cost_fn"):
+                setattr(new, k, v)
+            else:
+                setattr(new, k, copy.deepcopy(v, memo))
+        return new
+
+    @property
+    def a_seq(self):
+        """[B, H, da]"""
+        return torch.from_numpy(self._batch.get_a_seq()) if self._batch is not None else self._a_seq
+
+    @a_seq.setter
+    def a_seq(self, v):
+        self._a_seq = torch.as_tensor(v, dtype=torch.float).detach().clone().reshape(self.n_envs, self.hz_len, self.dim_a)
+        if self._batch is not None:
+            self._batch.set_a_seq(self._a_seq.numpy())
+
+    def _active(self, active):
+        if active is None:
+            return np.ones(self.n_envs, bool)
+        a = np.asarray(active).reshape(-1) != 0
+        if a.shape != (self.n_envs,):
+            raise ValueError("active has %d entries for %d environments" % (a.size, self.n_envs))
+        return a
+
+    def roll(self, steps=1, active=None):
+        if steps < 1:
+            raise ValueError("roll(steps=%d): steps >= 1" % steps)
+        if self._batch is not None:
+            self._batch.roll(steps, active)
+            return
+        on = torch.from_numpy(self._active(active))
+        rolled = torch.cat((self._a_seq[:, steps:], torch.zeros(self.n_envs, min(steps, self.hz_len), self.dim_a)), 1)
+        self._a_seq = torch.where(on.view(-1, 1, 1), rolled, self._a_seq)
+
+    def update_actions(self, model, states, actions=None, active=None, params=None):
+        """One tick of every active environment -> (costs [B, S], None, acts [B, S, H, da], omega [B, S]); the rows of inactive
+        environments are NaN, and `acts` is None with `return_rollouts = False`.  states [B, ds]; actions [B, S, H, da] or None (drawn
+        on the device); params [B, rows, P] overrides the class's own parameter draws - one parameter distribution per environment;
+        without it the class makes the draws AMPPI makes, once per active environment in environment order."""
+        batch = self._ensure_batch(model)
+        B = self.n_envs
+        states = torch.as_tensor(states, dtype=torch.float).reshape(B, -1)
+        acts = None if actions is None else torch.as_tensor(actions, dtype=torch.float).numpy()
+        on = self._active(active)
+        shared = self._params_sampling == "single"
+        if params is not None:
+            params = torch.as_tensor(params, dtype=torch.float).numpy()
+        elif self._tf is not None:
+            params = np.repeat(self._sigma_points(model)[None], B, 0)
+        elif self._sample_shape:
+            rows = [model.dict_to_params(model.sample_params(self._sample_shape)).numpy() if on[b] else None for b in range(B)]
+            shape = next((r.shape for r in rows if r is not None), None)
+            if shape is not None:
+                params = np.stack([r if r is not None else np.zeros(shape, np.float32) for r in rows])
+        want = bool(self.return_rollouts)
+        if params is None and (self._tf is not None or self._sample_shape) and not on.any():  # nobody ticks: nothing to launch
+            nan = lambda *sh: torch.full(sh, float("nan"))
+            return (nan(B, self.n_samples), None, nan(B, self.n_samples, self.hz_len, self.dim_a) if want else None, nan(B, self.n_samples))
+        costs, omega, _, acts_out = batch.update(states.numpy(), acts, params, shared_params=shared and params is not None,
+                                                 active=None if active is None else on, want_actions=want)
+        t = torch.from_numpy
+        return t(costs), None, (t(acts_out) if want else None), t(omega)

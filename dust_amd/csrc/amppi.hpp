@@ -26,6 +26,10 @@
 // acts[s * D + t], a stride of D values between neighbouring lanes, so a wave's action load touches up to 64 cache lines per step, and
 // more waves per SIMD - or 64-lane workgroups, which would spread S = 1024 over 16 CUs instead of 4 - may hide that latency better.
 // A transposed [D][S] copy of the actions would coalesce the reads.  Neither alternative has been timed.
+// The batched tick below (amppi_batch_kernel: B environments on a grid of (ceil(S / 256), B)) fills the idle CUs with OTHER
+// environments' workgroups and runs their reducers side by side (DESIGN.md section 5 has the measured environment-ticks/s); it changes
+// nothing inside an environment - the same 256 lanes per workgroup, the same stride-D reads, the same one-workgroup phase 2 - so the
+// choice above stays unmeasured, for the lone tick and for every environment of a batch.
 #pragma once
 #include "cartpole.hpp"
 #include "handoff.hpp"
@@ -118,8 +122,9 @@ __device__ __forceinline__ Coef amppi_row_coef(const DevModel &dm, const float *
 // NAV (skid-steer only): the navigation cost family of skid.hpp - w_obs occ(x_0, x_1) joins both parts; `nav` and `map` are read by it alone
 // ROW: `prow` is a parameter row the lane drew itself (AmppiPrior below), a local float[4]: its run-time columns are read through selects
 // (amppi_row_at), so that the row stays in registers
-template <int MODEL, bool NAV, bool ROW = false>
-__device__ __forceinline__ void amppi_traj(const AmppiArgs &a, const float *acts, const float *prow, float *so, float *inst_out, float *term_out,
+// ARGS: AmppiArgs, or the per-environment view of a batched tick (AmppiEnvArgs below): the same member names
+template <int MODEL, bool NAV, bool ROW = false, class ARGS = AmppiArgs>
+__device__ __forceinline__ void amppi_traj(const ARGS &a, const float *acts, const float *prow, float *so, float *inst_out, float *term_out,
                                            const SkidNav *nav, const DevModel *map) {
   constexpr int DS = AmppiDims<MODEL>::DS;
   const int H = a.H;
@@ -251,6 +256,92 @@ __global__ void amppi_roll_kernel(float *a_seq, const int D, const int shift) {
   const float v = (j < D && j + shift < D) ? a_seq[j + shift] : 0.f;
   wg_sync();
   if (j < D) a_seq[j] = v;
+}
+
+// ---- B independent ticks in ONE launch (dust_amppi_batch_update): grid (ceil(S / 256), B), blockIdx.y is the environment.  A workgroup
+// makes itself the arguments of a lone tick on its environment's slices - states [B][8] (ds values, zero-padded), a_seq [B][D],
+// acts [B][S][D], costs / omega [B][S], params [B][rows][P], ticket [B], ctr [B][4], seeds [B] - and runs the SAME body text on them: the
+// arithmetic, its order and the hand-off are the lone kernel's, per environment (the workgroup that draws ticket gridDim.x - 1 of
+// ticket[b] reduces environment b; the B reducers run side by side and nobody waits for anybody).  Model, cost, lambda, chol, pre, the
+// bounds and the sigma weights are shared.  The workgroups of an environment whose `active` byte is 0 return before they touch anything.
+struct AmppiBatchArgs {
+  AmppiArgs a;                  // the shared fields; its per-environment pointers are environment 0's, `state` and `seed` are unused
+  const float *states;          // [B][8]
+  const uint64_t *seeds;        // [B]
+  const unsigned char *active;  // [B] or nullptr: everybody
+  int prow_stride;              // values between two environments' parameter rows (rows * P)
+};
+// What the body text reads through `a`, for ONE environment: AmppiArgs' member names.  The shared structs and arrays stay where the
+// launch put them (references and pointers into the kernel's arguments: a local COPY of AmppiArgs goes to scratch memory as a whole -
+// 704 bytes per lane - because the body indexes min_a / max_a at run time); the environment's own values are plain members.
+struct AmppiEnvArgs {
+  const DevModel &dm;
+  const SkidModel &sk;
+  const CartModel &cp;
+  int S, H, da, D, P, pts, mode, philox;
+  float lambda, dt;
+  const float *chol, *pre, *min_a, *max_a;
+  float state[8];
+  uint64_t seed;
+  uint32_t *ctr;
+  const float *params, *mw;
+  float *acts, *a_seq, *costs, *omega, *states_out;
+  unsigned int *ticket;
+};
+__device__ __forceinline__ AmppiEnvArgs amppi_env_view(const AmppiBatchArgs &k, const int env) {
+  const AmppiArgs &g = k.a;
+  const float *st = k.states + (size_t)env * 8;
+  return AmppiEnvArgs{g.dm, g.sk, g.cp, g.S, g.H, g.da, g.D, g.P, g.pts, g.mode, g.philox, g.lambda, g.dt, g.chol, g.pre, g.min_a, g.max_a,
+                      {st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7]},
+                      k.seeds[env],
+                      g.ctr + (size_t)env * 4,
+                      g.params ? g.params + (size_t)env * (size_t)k.prow_stride : nullptr,
+                      g.mw,
+                      g.acts + (size_t)env * (size_t)g.S * (size_t)g.D,
+                      g.a_seq + (size_t)env * (size_t)g.D,
+                      g.costs + (size_t)env * (size_t)g.S,
+                      g.omega + (size_t)env * (size_t)g.S,
+                      nullptr,
+                      g.ticket + env};
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(AMPPI_THREADS) void amppi_batch_kernel(const AmppiBatchArgs k) {
+  constexpr bool NAV = false, PRIOR = false;
+  const SkidNav *const nav = nullptr;
+  const AmppiPrior *const pri = nullptr;
+  uint32_t *const grid_lds = nullptr;
+  const int env = (int)blockIdx.y;
+  if (k.active && k.active[env] == 0) return;
+  const AmppiEnvArgs a = amppi_env_view(k, env);
+#include "amppi_body.inc"
+}
+// ... with the navigation cost family: every workgroup stages the one map into its LDS, as the lone navigation kernel does
+struct AmppiNavBatchArgs {
+  AmppiBatchArgs k;
+  SkidNav nav;
+};
+__global__ __launch_bounds__(AMPPI_THREADS) void amppi_skid_nav_batch_kernel(const AmppiNavBatchArgs kn) {
+  constexpr int MODEL = DUST_MODEL_SKID_STEER;
+  constexpr bool NAV = true, PRIOR = false;
+  const SkidNav *const nav = &kn.nav;
+  const AmppiPrior *const pri = nullptr;
+  extern __shared__ __attribute__((aligned(16))) uint32_t grid_lds[];
+  const int env = (int)blockIdx.y;
+  if (kn.k.active && kn.k.active[env] == 0) return;
+  const AmppiEnvArgs a = amppi_env_view(kn.k, env);
+#include "amppi_body.inc"
+}
+
+// dust_amppi_batch_roll: amppi_roll_kernel on a_seq [B][D], one workgroup per environment; inactive environments keep their sequence
+__global__ void amppi_batch_roll_kernel(float *a_seq, const int D, const int shift, const unsigned char *active) {
+  const int env = (int)blockIdx.x;
+  if (active && active[env] == 0) return;
+  float *row = a_seq + (size_t)env * D;
+  const int j = (int)threadIdx.x;
+  const float v = (j < D && j + shift < D) ? row[j + shift] : 0.f;
+  wg_sync();
+  if (j < D) row[j] = v;
 }
 
 }  // namespace dust

@@ -1,7 +1,8 @@
 // amppi_body.inc - the statements of the AMPPI tick's kernel (amppi.hpp has the account), included TEXTUALLY into each kernel that runs
-// them: amppi_kernel<MODEL> and amppi_skid_nav_kernel.  Text, not a function: hipcc schedules the plain instances differently once their
+// them: amppi_kernel<MODEL>, amppi_skid_nav_kernel, their PRIOR and their batched forms.  Text, not a function: hipcc schedules the plain instances differently once their
 // body is an inlined callee, and they are to stay the instructions they were.  In scope at the point of inclusion:
-//   MODEL (int), NAV (constexpr bool), a (const AmppiArgs &), nav (const SkidNav *, NAV only), grid_lds (uint32_t *: dynamic LDS, NAV only)
+//   MODEL (int), NAV (constexpr bool), a (const AmppiArgs &; the batched kernels: AmppiEnvArgs, one environment's view with the same member
+//   names), nav (const SkidNav *, NAV only), grid_lds (uint32_t *: dynamic LDS, NAV only)
 //   PRIOR (constexpr bool), pri (const AmppiPrior *, PRIOR only): the lane draws its own parameter row from the filter's prior
 // The static __shared__ object below is declared once per including kernel; the NAV kernel's dynamic LDS lies behind it.
 // BEFORE turning this text into a function (or moving a declaration out of it): build both ways for gfx950 and compare the disassembly and

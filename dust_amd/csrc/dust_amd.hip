@@ -1305,15 +1305,10 @@ static int amppi_check(const dust_ctx *c) {
   return DUST_OK;
 }
 
-// dust_amppi_update's body.  dust_amppi_dual_tick (mpf.hpp) enters with `staged` (the parameter rows already sit in params_dev, written
-// there on the context's stream: `params` is then only "there are rows") or with `prior` (the lanes draw their rows themselves from the
-// filter's prior, "extended": no parameter buffer at all; prior->params_out, when set, has room for [S][P])
-static int amppi_update_impl(dust_ctx *c, const float *state, const float *actions, const float *params, int flags, float *costs, float *omega,
-                             float *a_seq, const bool staged, const dust::AmppiPrior *prior) {
-  if (!c || !state) return fail(DUST_ERR_INVALID, "null argument");
-  TRY(amppi_check(c));
-  if (flags & (DUST_EPS_F16 | DUST_STORE_F16)) return fail(DUST_ERR_UNSUPPORTED, "the AMPPI tick has no binary16 storage");
-  const int S = c->S, D = c->D, P = c->cfg.dim_p;
+// AMPPI(params_sampling=) of a tick (amppi.py:88-104) from what the caller handed in -> mode, sigma points per trajectory, rows read
+static int amppi_params_mode(const dust_ctx *c, const bool params, const int flags, const dust::AmppiPrior *prior, int *mode_out, int *pts_out,
+                             size_t *prows_out) {
+  const int S = c->S, P = c->cfg.dim_p;
   int mode = AMPPI_PARAMS_NONE, pts = 1;
   size_t prows = 0;
   if (c->mw_dev) {
@@ -1332,6 +1327,51 @@ static int amppi_update_impl(dust_ctx *c, const float *state, const float *actio
     prows = mode == AMPPI_PARAMS_SINGLE ? 1 : (size_t)S;
   }
   if (prior && mode != AMPPI_PARAMS_EXTENDED) return fail(DUST_ERR_INVALID, "in-kernel parameter draws are the \"extended\" mode");
+  *mode_out = mode;
+  *pts_out = pts;
+  *prows_out = prows;
+  return DUST_OK;
+}
+
+// What every trajectory of a tick shares: model, cost, sizes, lambda, the factors of a_cov, the bounds, the sigma weights
+static void amppi_shared_args(const dust_ctx *c, dust::AmppiArgs &a) {
+  memset(&a, 0, sizeof a);
+  a.dm = make_dev_model(c);
+  a.dm.log_space = 0;
+  a.sk = c->skid;
+  a.cp = c->cart;
+  a.S = c->S;
+  a.H = c->H;
+  a.da = c->da;
+  a.D = c->D;
+  a.P = c->cfg.dim_p;
+  a.lambda = c->cfg.temperature;
+  a.dt = (float)c->cfg.dt;
+  a.chol[0] = c->cfg.chol_a[0];
+  a.chol[1] = c->da == 2 ? c->cfg.chol_a_off : 0.f;
+  a.chol[2] = c->da == 2 ? c->cfg.chol_a[1] : 0.f;
+  a.pre[0] = c->cfg.a_pre[0];
+  a.pre[1] = c->da == 2 ? c->cfg.a_pre_off : 0.f;
+  a.pre[2] = c->da == 2 ? c->cfg.a_pre[1] : 0.f;
+  for (int d = 0; d < 2; ++d) {
+    a.min_a[d] = c->cfg.min_a[d];
+    a.max_a[d] = c->cfg.max_a[d];
+  }
+  a.mw = c->mw_dev;
+}
+
+// dust_amppi_update's body.  dust_amppi_dual_tick (mpf.hpp) enters with `staged` (the parameter rows already sit in params_dev, written
+// there on the context's stream: `params` is then only "there are rows") or with `prior` (the lanes draw their rows themselves from the
+// filter's prior, "extended": no parameter buffer at all; prior->params_out, when set, has room for [S][P])
+static int amppi_update_impl(dust_ctx *c, const float *state, const float *actions, const float *params, int flags, float *costs, float *omega,
+                             float *a_seq, const bool staged, const dust::AmppiPrior *prior) {
+  if (!c || !state) return fail(DUST_ERR_INVALID, "null argument");
+  TRY(amppi_check(c));
+  if (flags & (DUST_EPS_F16 | DUST_STORE_F16)) return fail(DUST_ERR_UNSUPPORTED, "the AMPPI tick has no binary16 storage");
+  const int S = c->S, D = c->D, P = c->cfg.dim_p;
+  int mode = AMPPI_PARAMS_NONE, pts = 1;
+  size_t prows = 0;
+  TRY(amppi_params_mode(c, params != nullptr, flags, prior, &mode, &pts, &prows));
   TRY(settle_pending(c));
   HIP_TRY(hipSetDevice(c->cfg.device));
   if (!c->amppi_ticket) TRY(dalloc(&c->amppi_ticket, (size_t)1));
@@ -1347,36 +1387,14 @@ static int amppi_update_impl(dust_ctx *c, const float *state, const float *actio
   const bool want_states = (flags & DUST_STORE_STATES) != 0;
   if (want_states) TRY(ensure(&c->states, &c->states_cap, (size_t)S * pts * (c->H + 1) * c->ds));
   AmppiArgs a;
-  memset(&a, 0, sizeof a);
-  a.dm = make_dev_model(c);
-  a.dm.log_space = 0;
-  a.sk = c->skid;
-  a.cp = c->cart;
-  a.S = S;
-  a.H = c->H;
-  a.da = c->da;
-  a.D = D;
-  a.P = P;
+  amppi_shared_args(c, a);
   a.pts = pts;
   a.mode = mode;
   a.philox = actions ? 0 : 1;
-  a.lambda = c->cfg.temperature;
-  a.dt = (float)c->cfg.dt;
-  a.chol[0] = c->cfg.chol_a[0];
-  a.chol[1] = c->da == 2 ? c->cfg.chol_a_off : 0.f;
-  a.chol[2] = c->da == 2 ? c->cfg.chol_a[1] : 0.f;
-  a.pre[0] = c->cfg.a_pre[0];
-  a.pre[1] = c->da == 2 ? c->cfg.a_pre_off : 0.f;
-  a.pre[2] = c->da == 2 ? c->cfg.a_pre[1] : 0.f;
-  for (int d = 0; d < 2; ++d) {
-    a.min_a[d] = c->cfg.min_a[d];
-    a.max_a[d] = c->cfg.max_a[d];
-  }
   for (int k = 0; k < 8; ++k) a.state[k] = k < c->ds ? state[k] : 0.f;  // (a kernel ARGUMENT: no copy, no launch of its own)
   a.seed = c->cfg.seed;
   a.ctr = c->ctr_dev;
   a.params = prows ? c->params_dev : nullptr;
-  a.mw = c->mw_dev;
   a.acts = c->actions;
   a.a_seq = c->a_seq;
   a.costs = c->costsT;  // ([N][S] with N = 1)
@@ -1446,6 +1464,277 @@ extern "C" int dust_amppi_roll(dust_ctx *c, int steps) {
   const long shift = (long)steps * c->da;
   amppi_roll_kernel<<<1, 128, 0, c->stream>>>(c->a_seq, c->D, shift > c->D ? c->D : (int)shift);
   HIP_TRY(hipGetLastError());
+  return DUST_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// AMPPI over a batch of plants: B independent ticks in one launch (amppi.hpp amppi_batch_kernel).  The batch owns a private clone of
+// the prototype context - model, cost, map, sigma weights, stream, profile counters - and the per-environment device rows.
+struct dust_amppi_batch {
+  dust_ctx *c;
+  int B;
+  float *a_seq;           // [B][D]
+  float *acts;            // [B][S][D]
+  float *costs, *omega;   // [B][S]
+  float *params;          // [B][rows][P]
+  size_t params_cap;
+  uint32_t *ctr;          // [B][4]: every environment's Philox stream position {tick, iter, .., ..}
+  uint64_t *seeds;        // [B]
+  unsigned int *ticket;   // [B]
+  // per-call inputs travel through pinned host memory - the call does not wait for its own copy.  Two slots, each with the event behind
+  // its copy: a slot is written again only once that copy has run
+  float *in_dev;          // [B][8] states, then [B] bytes of the active mask
+  float *in_host[2];
+  hipEvent_t in_ev[2];
+  int in_slot;
+  std::vector<unsigned char> last_active;  // the mask of the last tick (dust_amppi_batch_get_actions writes the rows of that tick's environments)
+  bool acts_valid;
+};
+
+static size_t batch_in_bytes(int B) { return (size_t)B * 8 * sizeof(float) + (size_t)B; }
+
+static void batch_free(dust_amppi_batch *b) {
+  if (!b) return;
+  if (b->c) {
+    (void)hipSetDevice(b->c->cfg.device);
+    (void)hipStreamSynchronize(b->c->stream);
+  }
+  void *dev[] = {b->a_seq, b->acts, b->costs, b->omega, b->params, b->ctr, b->seeds, b->ticket, b->in_dev};
+  for (void *p : dev)
+    if (p) (void)hipFree(p);
+  for (int k = 0; k < 2; ++k) {
+    if (b->in_host[k]) (void)hipHostFree(b->in_host[k]);
+    if (b->in_ev[k]) (void)hipEventDestroy(b->in_ev[k]);
+  }
+  if (b->c) dust_destroy(b->c);
+  delete b;
+}
+
+// the batch around an inner context it takes over: buffers allocated, nothing filled yet
+static int batch_alloc(dust_ctx *inner, int n_env, dust_amppi_batch **out) {
+  dust_amppi_batch *b = new dust_amppi_batch();
+  b->c = inner;
+  b->B = n_env;
+  *out = b;
+  const size_t B = (size_t)n_env, S = (size_t)inner->S, D = (size_t)inner->D;
+  HIP_TRY(hipSetDevice(inner->cfg.device));
+  TRY(dalloc(&b->a_seq, B * D));
+  TRY(dalloc(&b->acts, B * S * D));
+  TRY(dalloc(&b->costs, B * S));
+  TRY(dalloc(&b->omega, B * S));
+  TRY(dalloc(&b->ctr, B * 4));
+  TRY(dalloc(&b->seeds, B));
+  TRY(dalloc(&b->ticket, B));
+  TRY(dalloc(&b->in_dev, (batch_in_bytes(n_env) + 3) / 4));
+  for (int k = 0; k < 2; ++k) {
+    HIP_TRY(hipHostMalloc((void **)&b->in_host[k], batch_in_bytes(n_env), hipHostMallocDefault));
+    HIP_TRY(hipEventCreateWithFlags(&b->in_ev[k], hipEventDisableTiming));
+  }
+  return DUST_OK;
+}
+
+static int batch_null(const dust_amppi_batch *b) { return b ? DUST_OK : fail(DUST_ERR_INVALID, "null batch"); }
+
+extern "C" int dust_amppi_batch_create(const dust_ctx *proto, int n_env, const uint64_t *seeds, dust_amppi_batch **out) {
+  if (!proto || !out) return fail(DUST_ERR_INVALID, "null argument");
+  *out = nullptr;
+  TRY(amppi_check(proto));
+  if (n_env < 1 || n_env > 65535) return fail(DUST_ERR_INVALID, "n_env = %d outside [1, 65535] (one grid row per environment)", n_env);
+  dust_ctx *inner = nullptr;
+  TRY(dust_clone(proto, &inner));
+  dust_amppi_batch *b = nullptr;
+  int st = batch_alloc(inner, n_env, &b);
+  if (st == DUST_OK) {
+    const size_t D = (size_t)inner->D;
+    std::vector<float> seq(D), seq_all((size_t)n_env * D);
+    std::vector<uint32_t> ctr(4), ctr_all((size_t)n_env * 4);
+    std::vector<uint64_t> sd((size_t)n_env);
+    st = d2h(inner, seq.data(), inner->a_seq, D * sizeof(float));
+    if (st == DUST_OK) st = d2h(inner, ctr.data(), inner->ctr_dev, 4 * sizeof(uint32_t));
+    for (int e = 0; e < n_env; ++e) {
+      std::copy(seq.begin(), seq.end(), seq_all.begin() + (size_t)e * D);
+      std::copy(ctr.begin(), ctr.end(), ctr_all.begin() + (size_t)e * 4);
+      sd[e] = seeds ? seeds[e] : inner->cfg.seed + (uint64_t)e;
+    }
+    if (st == DUST_OK) st = h2d(inner, b->a_seq, seq_all.data(), seq_all.size() * sizeof(float));
+    if (st == DUST_OK) st = h2d(inner, b->ctr, ctr_all.data(), ctr_all.size() * sizeof(uint32_t));
+    if (st == DUST_OK) st = h2d(inner, b->seeds, sd.data(), sd.size() * sizeof(uint64_t));
+  }
+  if (st != DUST_OK) {
+    batch_free(b);
+    return st;
+  }
+  *out = b;
+  return DUST_OK;
+}
+
+extern "C" void dust_amppi_batch_destroy(dust_amppi_batch *b) { batch_free(b); }
+
+extern "C" int dust_amppi_batch_clone(const dust_amppi_batch *src, dust_amppi_batch **out) {
+  if (!src || !out) return fail(DUST_ERR_INVALID, "null argument");
+  *out = nullptr;
+  dust_ctx *inner = nullptr;
+  TRY(dust_clone(src->c, &inner));  // (waits for the source's stream)
+  dust_amppi_batch *b = nullptr;
+  int st = batch_alloc(inner, src->B, &b);
+  const size_t B = (size_t)src->B, S = (size_t)inner->S, D = (size_t)inner->D;
+  if (st == DUST_OK) st = d2d(inner, b->a_seq, src->a_seq, B * D * sizeof(float));
+  if (st == DUST_OK) st = d2d(inner, b->ctr, src->ctr, B * 4 * sizeof(uint32_t));
+  if (st == DUST_OK) st = d2d(inner, b->seeds, src->seeds, B * sizeof(uint64_t));
+  if (st == DUST_OK && src->acts_valid) {  // (dust_amppi_batch_get_actions of the copy gives what the source's would)
+    st = d2d(inner, b->acts, src->acts, B * S * D * sizeof(float));
+    b->acts_valid = true;
+    b->last_active = src->last_active;
+  }
+  if (st == DUST_OK && hipStreamSynchronize(inner->stream) != hipSuccess) st = fail(DUST_ERR_HIP, "hipStreamSynchronize failed");
+  if (st != DUST_OK) {
+    batch_free(b);
+    return st;
+  }
+  *out = b;
+  return DUST_OK;
+}
+
+extern "C" int dust_amppi_batch_ctx(dust_amppi_batch *b, dust_ctx **out) {
+  if (!b || !out) return fail(DUST_ERR_INVALID, "null argument");
+  *out = b->c;
+  return DUST_OK;
+}
+
+extern "C" int dust_amppi_batch_set_a_seq(dust_amppi_batch *b, const float *a_seq) {
+  if (!b || !a_seq) return fail(DUST_ERR_INVALID, "null argument");
+  HIP_TRY(hipSetDevice(b->c->cfg.device));
+  return h2d(b->c, b->a_seq, a_seq, (size_t)b->B * b->c->D * sizeof(float));
+}
+extern "C" int dust_amppi_batch_get_a_seq(dust_amppi_batch *b, float *a_seq) {
+  if (!b || !a_seq) return fail(DUST_ERR_INVALID, "null argument");
+  HIP_TRY(hipSetDevice(b->c->cfg.device));
+  return d2h(b->c, a_seq, b->a_seq, (size_t)b->B * b->c->D * sizeof(float));
+}
+
+// states [B][ds] and / or the active mask [B] -> in_dev through the next pinned slot, on the context's stream; nobody waits
+static int batch_stage_inputs(dust_amppi_batch *b, const float *states, const unsigned char *active) {
+  dust_ctx *c = b->c;
+  const int slot = b->in_slot;
+  b->in_slot ^= 1;
+  HIP_TRY(hipEventSynchronize(b->in_ev[slot]));  // (the copy out of this slot two calls ago; an event never recorded is complete)
+  const size_t sbytes = (size_t)b->B * 8 * sizeof(float);
+  unsigned char *hb = reinterpret_cast<unsigned char *>(b->in_host[slot]);
+  unsigned char *db = reinterpret_cast<unsigned char *>(b->in_dev);
+  if (states) {
+    float *hs = b->in_host[slot];
+    for (int e = 0; e < b->B; ++e)
+      for (int k = 0; k < 8; ++k) hs[(size_t)e * 8 + k] = k < c->ds ? states[(size_t)e * c->ds + k] : 0.f;
+  }
+  if (active) memcpy(hb + sbytes, active, (size_t)b->B);
+  const size_t from = states ? 0 : sbytes, to = active ? sbytes + (size_t)b->B : sbytes;
+  if (to > from) HIP_TRY(hipMemcpyAsync(db + from, hb + from, to - from, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipEventRecord(b->in_ev[slot], c->stream));
+  return DUST_OK;
+}
+
+// rows of `row` floats per environment, device -> host, for the environments of `active` (nullptr: all): one copy per run of them
+static int batch_rows_d2h(dust_amppi_batch *b, float *dst, const float *src, size_t row, const unsigned char *active) {
+  for (int e = 0; e < b->B;) {
+    if (active && !active[e]) {
+      ++e;
+      continue;
+    }
+    int f = e + 1;
+    while (f < b->B && (!active || active[f])) ++f;
+    HIP_TRY(hipMemcpyAsync(dst + (size_t)e * row, src + (size_t)e * row, (size_t)(f - e) * row * sizeof(float), hipMemcpyDeviceToHost, b->c->stream));
+    e = f;
+  }
+  return DUST_OK;
+}
+
+extern "C" int dust_amppi_batch_update(dust_amppi_batch *b, const float *states, const float *actions, const float *params, int flags,
+                                       const unsigned char *active, float *costs, float *omega, float *a_seq) {
+  TRY(batch_null(b));
+  if (!states) return fail(DUST_ERR_INVALID, "null argument");
+  dust_ctx *c = b->c;
+  TRY(amppi_check(c));
+  if (flags & (DUST_EPS_F16 | DUST_STORE_F16)) return fail(DUST_ERR_UNSUPPORTED, "the AMPPI tick has no binary16 storage");
+  if (flags & DUST_STORE_STATES) return fail(DUST_ERR_UNSUPPORTED, "the batched AMPPI tick does not store its trajectories (DUST_STORE_STATES): run a lone dust_amppi_update for them");
+  int mode = AMPPI_PARAMS_NONE, pts = 1;
+  size_t prows = 0;
+  TRY(amppi_params_mode(c, params != nullptr, flags, nullptr, &mode, &pts, &prows));
+  const size_t B = (size_t)b->B, S = (size_t)c->S, D = (size_t)c->D, P = (size_t)c->cfg.dim_p;
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  if (actions) {
+    if (flags & DUST_PTR_DEVICE) TRY(d2d(c, b->acts, actions, B * S * D * sizeof(float)));
+    else TRY(h2d(c, b->acts, actions, B * S * D * sizeof(float)));
+  }
+  if (prows) {
+    TRY(ensure(&b->params, &b->params_cap, B * prows * P));
+    TRY(h2d(c, b->params, params, B * prows * P * sizeof(float)));
+  }
+  TRY(batch_stage_inputs(b, states, active));
+  AmppiNavBatchArgs kn;
+  AmppiBatchArgs &k = kn.k;
+  amppi_shared_args(c, k.a);
+  k.a.pts = pts;
+  k.a.mode = mode;
+  k.a.philox = actions ? 0 : 1;
+  k.a.ctr = b->ctr;
+  k.a.params = prows ? b->params : nullptr;
+  k.a.acts = b->acts;
+  k.a.a_seq = b->a_seq;
+  k.a.costs = b->costs;
+  k.a.omega = b->omega;
+  k.a.ticket = b->ticket;
+  k.states = b->in_dev;
+  k.seeds = b->seeds;
+  k.active = active ? reinterpret_cast<const unsigned char *>(b->in_dev) + B * 8 * sizeof(float) : nullptr;
+  k.prow_stride = (int)(prows * P);
+  const dim3 grid((unsigned)((S + AMPPI_THREADS - 1) / AMPPI_THREADS), (unsigned)B);
+  const bool nav = c->cfg.model == DUST_MODEL_SKID_STEER && c->skid_w_obs != 0.f;
+  if (nav) TRY(skid_nav_args(c, kn.nav));
+  HIP_TRY(hipMemsetAsync(b->ticket, 0, B * sizeof(unsigned int), c->stream));
+  {
+    Prof pr(c, DUST_K_AMPPI);
+    if (nav) amppi_skid_nav_batch_kernel<<<grid, AMPPI_THREADS, (size_t)kn.nav.grid_words * sizeof(uint32_t), c->stream>>>(kn);
+    else switch (c->cfg.model) {
+      case DUST_MODEL_PENDULUM: amppi_batch_kernel<DUST_MODEL_PENDULUM><<<grid, AMPPI_THREADS, 0, c->stream>>>(k); break;
+      case DUST_MODEL_PARTICLE: amppi_batch_kernel<DUST_MODEL_PARTICLE><<<grid, AMPPI_THREADS, 0, c->stream>>>(k); break;
+      case DUST_MODEL_SKID_STEER: amppi_batch_kernel<DUST_MODEL_SKID_STEER><<<grid, AMPPI_THREADS, 0, c->stream>>>(k); break;
+      default: amppi_batch_kernel<DUST_MODEL_CARTPOLE><<<grid, AMPPI_THREADS, 0, c->stream>>>(k); break;
+    }
+    HIP_TRY(hipGetLastError());
+  }
+  b->acts_valid = true;
+  if (active) b->last_active.assign(active, active + B);
+  else b->last_active.clear();
+  if (!costs && !omega && !a_seq) return DUST_OK;
+  if (costs) TRY(batch_rows_d2h(b, costs, b->costs, S, active));
+  if (omega) TRY(batch_rows_d2h(b, omega, b->omega, S, active));
+  if (a_seq) TRY(batch_rows_d2h(b, a_seq, b->a_seq, D, active));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return DUST_OK;
+}
+
+extern "C" int dust_amppi_batch_roll(dust_amppi_batch *b, int steps, const unsigned char *active) {
+  TRY(batch_null(b));
+  if (steps < 1) return fail(DUST_ERR_INVALID, "roll(steps = %d): steps >= 1", steps);
+  dust_ctx *c = b->c;
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  if (active) TRY(batch_stage_inputs(b, nullptr, active));
+  const unsigned char *mask = active ? reinterpret_cast<const unsigned char *>(b->in_dev) + (size_t)b->B * 8 * sizeof(float) : nullptr;
+  const long shift = (long)steps * c->da;
+  {
+    Prof pr(c, DUST_K_FORWARD);
+    amppi_batch_roll_kernel<<<b->B, 128, 0, c->stream>>>(b->a_seq, c->D, shift > c->D ? c->D : (int)shift, mask);
+    HIP_TRY(hipGetLastError());
+  }
+  return DUST_OK;
+}
+
+extern "C" int dust_amppi_batch_get_actions(dust_amppi_batch *b, float *actions) {
+  if (!b || !actions) return fail(DUST_ERR_INVALID, "null argument");
+  if (!b->acts_valid) return fail(DUST_ERR_STATE, "no batched tick has run yet: there are no actions");
+  HIP_TRY(hipSetDevice(b->c->cfg.device));
+  TRY(batch_rows_d2h(b, actions, b->acts, (size_t)b->c->S * b->c->D, b->last_active.empty() ? nullptr : b->last_active.data()));
+  HIP_TRY(hipStreamSynchronize(b->c->stream));
   return DUST_OK;
 }
 

@@ -354,6 +354,49 @@ int dust_amppi_update(dust_ctx *ctx, const float *state, const float *actions, c
  * (the reference's slice arithmetic gives steps = 0 an all-zero sequence and negative steps a mixture: DUST_ERR_INVALID here). */
 int dust_amppi_roll(dust_ctx *ctx, int steps);
 
+/* ---- AMPPI over a batch of plants: B independent controllers of one configuration, ONE kernel launch per tick (ABI 3, additive) ----
+ * The reference evaluates a controller over many episodes with a deep copy each (simulations.py); a batch is those B copies on one
+ * device: every environment has its own state, nominal sequence, Philox stream and parameter rows, while the model, the cost, the
+ * horizon, S, lambda and a_cov are shared.  The launch is a grid of (ceil(S / 256), B) workgroups (dust_amd/csrc/amppi.hpp
+ * amppi_batch_kernel); environment b computes exactly what a lone dust_amppi_update computes on its inputs, bit for bit, and its
+ * device-drawn noise continues the stream of a lone context created with seed seeds[b] that has made the same drawing calls.
+ *
+ * dust_amppi_batch_create: the batch keeps a private dust_clone of `proto` (model, cost, occupancy grid, navigation cost, sigma
+ *   weights, profile counters): `proto` may be destroyed afterwards and later changes to it do not reach the batch.  seeds [n_env]
+ *   (NULL: proto's seed + b); every environment starts from proto's a_seq and proto's stream position.  DUST_ERR_INVALID:
+ *   n_env outside [1, 65535], n_policies != 1; DUST_ERR_UNSUPPORTED: whatever dust_amppi_update refuses of a context (sharded,
+ *   params_log_space, Particle with velocity control or control-channel noise, ...).
+ * dust_amppi_batch_clone: copy.deepcopy - an independent batch with the same sequences, stream positions and last actions.
+ * dust_amppi_batch_set_a_seq / _get_a_seq: the nominal sequences [B][H][da].
+ * dust_amppi_batch_ctx: the inner context, BORROWED (never dust_destroy it), for dust_sync and dust_profile_*: a batched tick counts
+ *   as one DUST_K_AMPPI launch, a batched roll as one DUST_K_FORWARD launch. */
+typedef struct dust_amppi_batch dust_amppi_batch;
+int dust_amppi_batch_create(const dust_ctx *proto, int n_env, const uint64_t *seeds, dust_amppi_batch **out);
+void dust_amppi_batch_destroy(dust_amppi_batch *batch);
+int dust_amppi_batch_clone(const dust_amppi_batch *batch, dust_amppi_batch **out);
+int dust_amppi_batch_set_a_seq(dust_amppi_batch *batch, const float *a_seq);
+int dust_amppi_batch_get_a_seq(dust_amppi_batch *batch, float *a_seq);
+int dust_amppi_batch_ctx(dust_amppi_batch *batch, dust_ctx **ctx);
+/* dust_amppi_batch_update = B x dust_amppi_update in ONE launch behind ONE memset node that zeroes the B arrival words:
+ *   states [B][ds], host;
+ *   actions [B][S][H][da] (NULL: drawn on the device, environment b with key seeds[b] and its own counters; host pointer, or device
+ *     with DUST_PTR_DEVICE, which speaks of `actions` alone);
+ *   params by mode, host: NULL "none"; [B][1][P] with DUST_AMPPI_PARAMS_SHARED "single"; [B][S][P] "extended"; [B][2P + 1][P] sigma
+ *     points of a prototype with dust_set_param_weights - one parameter distribution per environment;
+ *   active [B] bytes, host, or NULL (all): the workgroups of an environment with active[b] = 0 return at once - its a_seq, its stream
+ *     position and its device rows stay untouched, and its rows of the outputs are NOT written;
+ *   outputs, each may be NULL: costs [B][S], omega [B][S], a_seq [B][H][da] after the update.  With all three NULL - and actions
+ *     and params NULL or on the device - the call returns without waiting for the device.
+ * DUST_ERR_UNSUPPORTED (before any launch): DUST_STORE_STATES, binary16 storage (DUST_EPS_F16 / DUST_STORE_F16), and what
+ * dust_amppi_update refuses; the filter-coupled tick (dust_amppi_dual_tick) has no batched form.  DUST_ERR_INVALID: NULL states,
+ * params without uncertain parameters, sigma weights without params. */
+int dust_amppi_batch_update(dust_amppi_batch *batch, const float *states, const float *actions, const float *params, int flags,
+                            const unsigned char *active, float *costs, float *omega, float *a_seq);
+/* dust_amppi_roll on every environment with active[b] != 0 (NULL: all) in one launch; steps >= 1. */
+int dust_amppi_batch_roll(dust_amppi_batch *batch, int steps, const unsigned char *active);
+/* The actions the last tick used, [B][S][H][da]; the rows of environments that were inactive in that tick are not written. */
+int dust_amppi_batch_get_actions(dust_amppi_batch *batch, float *actions);
+
 /* stage outputs of the last call, for parity tests ([S][N] / [N][H][da] / [N]) */
 int dust_get_costs(dust_ctx *ctx, float *costs);
 int dust_get_actions(dust_ctx *ctx, float *actions);
