@@ -146,6 +146,17 @@ SYMBOLS = {
     "dust_amppi_batch_update": (C.c_int, [VP, FP, VP, FP, C.c_int, C.POINTER(C.c_ubyte), FP, FP, FP]),
     "dust_amppi_batch_roll": (C.c_int, [VP, C.c_int, C.POINTER(C.c_ubyte)]),
     "dust_amppi_batch_get_actions": (C.c_int, [VP, FP]),
+    "dust_mpf_batch_create": (C.c_int, [VP, C.c_int, C.POINTER(VP)]),
+    "dust_mpf_batch_destroy": (None, [VP]),
+    "dust_mpf_batch_clone": (C.c_int, [VP, C.POINTER(VP)]),
+    "dust_mpf_batch_set_particles": (C.c_int, [VP, FP]),
+    "dust_mpf_batch_get_particles": (C.c_int, [VP, FP]),
+    "dust_mpf_batch_set_obs": (C.c_int, [VP, FP]),
+    "dust_mpf_batch_get_prior_bw": (C.c_int, [VP, FP]),
+    "dust_mpf_batch_stats": (C.c_int, [VP, C.POINTER(C.c_longlong)]),
+    "dust_mpf_batch_optimize": (C.c_int, [VP, FP, FP, C.c_float, C.c_int, C.POINTER(C.c_ubyte), FP, FP]),
+    "dust_amppi_dual_batch_tick": (C.c_int, [VP, VP, FP, FP, VP, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_ubyte),
+                                             FP, FP, FP, FP, FP]),
     "dust_get_costs": (C.c_int, [VP, FP]),
     "dust_get_actions": (C.c_int, [VP, FP]),
     "dust_get_states_rows": (C.c_int, [VP, C.POINTER(C.c_longlong), C.c_int, VP]),

@@ -747,6 +747,35 @@ class AmppiBatch:
         L.check(L.load().dust_amppi_batch_update(self._h, _p(st), _vp(act), _p(pr), fl, mp, _p(costs), _p(omega), _p(a_seq)))
         return costs, omega, a_seq, (self.get_actions() if want_actions else None)
 
+    def dual_tick(self, mpf, states, actions_prev=None, actions=None, shared_params=False, mpf_steps=20, mpf_bw=None, seeds=None, roll=0,
+                  active=None, want_outputs=True, want_params=False, flags=0):
+        """One control period of the dual loop for every active environment in one C call (dust_amppi_dual_batch_tick): the filters'
+        update for (actions_prev[b], states[b]) - skipped when actions_prev is None -, the parameters from every refreshed prior (drawn
+        inside the tick's kernel; one staged row per environment with shared_params; staged sigma points for a context with parameter
+        weights and a sigma scale), the update, the roll.  mpf: an `MpfBatch` of B environments; seeds [B]: the Philox key of every
+        environment's draws.  -> (costs [B, S], omega [B, S], a_seq [B, H, da] before the roll, params or None, bw_used [B]); the rows
+        of inactive environments are NaN.  want_outputs=False reads nothing back: the call does not wait for the device."""
+        B, S = self.B, self.S
+        st = None if states is None else _f(states, (B, self.ds))
+        ap = None if actions_prev is None else _f(actions_prev, (B, self.da))
+        act = None if actions is None else _f(actions, (B, S, self.H, self.da))
+        sd = None
+        if seeds is not None:
+            sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
+            if sd.size != B:
+                raise ValueError("seeds has %d entries for %d environments" % (sd.size, B))
+        _, mp = _mask(active, B)
+        costs = omega = a_seq = bw = None
+        if want_outputs:
+            costs, omega, a_seq, bw = (np.full(sh, np.nan, np.float32) for sh in ((B, S), (B, S), (B, self.H, self.da), (B,)))
+        rows = self.M if self.M > 1 else (1 if shared_params else S)
+        pout = np.full((B, rows, max(self.P, 1)), np.nan, np.float32) if want_params else None
+        L.check(L.load().dust_amppi_dual_batch_tick(self._h, mpf._h, _p(st), _p(ap), _vp(act), int(flags) | (L.AMPPI_PARAMS_SHARED if shared_params else 0),
+                                                    int(mpf_steps), float(-1.0 if mpf_bw is None else mpf_bw),
+                                                    None if sd is None else sd.ctypes.data_as(C.POINTER(C.c_uint64)), int(roll), mp,
+                                                    _p(costs), _p(omega), _p(a_seq), _p(pout), _p(bw)))
+        return costs, omega, a_seq, pout, bw
+
     def get_actions(self):
         """[B, S, H, da] actions of the last tick; NaN rows for the environments that were inactive in it."""
         out = np.full((self.B, self.S, self.H, self.da), np.nan, np.float32)
@@ -757,6 +786,78 @@ class AmppiBatch:
         """BaseController.roll(steps) of every active environment in one launch (dust_amppi_batch_roll)."""
         _, mp = _mask(active, self.B)
         L.check(L.load().dust_amppi_batch_roll(self._h, int(steps), mp))
+
+
+class MpfBatch:
+    """B dynamics filters of one configuration, updated in one launch (dust_mpf_batch_*): per environment its particles, optimiser
+    state, observations, past action and bandwidths; model, obs_std, optimiser options, Mp and P are the prototype filter's.
+    Environment b computes what a lone `MpfContext` created under DUST_MPF_GRID=0 computes on its inputs, bit for bit."""
+
+    def __init__(self, proto=None, n_envs=1, _handle=None, _like=None):
+        self._h = None
+        like = proto if _like is None else _like
+        self.Mp, self.P, self.ds, self.da = like.Mp, like.P, like.ds, like.da
+        self.B = int(n_envs)
+        if _handle is None:
+            h = L.VP()
+            L.check(L.load().dust_mpf_batch_create(proto._h, self.B, C.byref(h)))
+            _handle = h
+        self._h = _handle
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            L.load().dust_mpf_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def clone(self):
+        h = L.VP()
+        L.check(L.load().dust_mpf_batch_clone(self._h, C.byref(h)))
+        return MpfBatch(n_envs=self.B, _handle=h, _like=self)
+
+    def __deepcopy__(self, memo):
+        return self.clone()
+
+    def set_particles(self, x):
+        L.check(L.load().dust_mpf_batch_set_particles(self._h, _p(_f(x, (self.B, self.Mp, self.P)))))
+
+    def get_particles(self):
+        out = np.empty((self.B, self.Mp, self.P), np.float32)
+        L.check(L.load().dust_mpf_batch_get_particles(self._h, _p(out)))
+        return out
+
+    def set_obs(self, obs):
+        """Every environment's observation [B, ds]: the state the next update's one-step prediction starts from."""
+        L.check(L.load().dust_mpf_batch_set_obs(self._h, _p(_f(obs, (self.B, self.ds)))))
+
+    def get_prior_bw(self):
+        """[B, P] bandwidths of every environment's current prior."""
+        out = np.empty((self.B, 4), np.float32)
+        L.check(L.load().dust_mpf_batch_get_prior_bw(self._h, _p(out)))
+        return out[:, :self.P].copy()
+
+    def stats(self):
+        """{'launches': kernel launches made for the filter side, 'calls': updates and dual ticks}."""
+        n = (C.c_longlong * 2)()
+        L.check(L.load().dust_mpf_batch_stats(self._h, n))
+        return {"launches": int(n[0]), "calls": int(n[1])}
+
+    def optimize(self, actions, new_obs, bw, n_steps, active=None):
+        """B x MpfContext.optimize in one launch (dust_mpf_batch_optimize).  actions [B, da], new_obs [B, ds]; bw None or <= 0:
+        Silverman's rule per environment on the device.  -> (grad_norms [B, n_steps], bw_used [B]); NaN rows for inactive environments."""
+        a = None if actions is None else _f(actions, (self.B, self.da))
+        o = None if new_obs is None else _f(new_obs, (self.B, self.ds))
+        _, mp = _mask(active, self.B)
+        gn = np.full((self.B, max(int(n_steps), 1)), np.nan, np.float32)
+        bwu = np.full(self.B, np.nan, np.float32)
+        L.check(L.load().dust_mpf_batch_optimize(self._h, _p(a), _p(o), float(-1.0 if bw is None else bw), int(n_steps), mp, _p(bwu),
+                                                 _p(gn) if n_steps > 0 else None))
+        return gn[:, :n_steps], bwu
 
 
 class MpfContext:
@@ -843,6 +944,11 @@ class MpfContext:
 
     def __deepcopy__(self, memo):
         return self.clone()
+
+    def batch(self, n_envs):
+        """`n_envs` copies of this filter - particles, observations, optimiser state, bandwidths - updated in one launch
+        (dust_mpf_batch_create): the batch keeps its own copy of the filter."""
+        return MpfBatch(self, n_envs)
 
     def condition(self, action, new_obs):
         a = None if action is None else _f(action).reshape(-1)

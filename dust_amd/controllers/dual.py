@@ -238,3 +238,133 @@ class DualAMPPI:
         new_state = plant(state, action)
         self.step(action, new_state)
         return action, new_state, omega
+
+
+class BatchDualAMPPI:
+    """The dual loop over `B = controller.n_envs` plants at once: a `BatchAMPPI` and B copies of one `MPF` - the deep copies of controller
+    and filter the reference makes per episode (dust/utils/simulations.py:62,78) - with a whole control period of all of them in ONE C
+    call (dust_amppi_dual_batch_tick): the B filter updates in one launch, Silverman's bandwidths on the device when none is given, the
+    parameters from every refreshed prior on the device, the B ticks in one launch, the roll.  Environment b runs what a
+    `DualAMPPI(fused=True)` over `AMPPI(seed=seeds[b])` and a filter of its own runs, bit for bit when that filter takes the
+    single-workgroup kernel (DUST_MPF_GRID=0), under the prior keys `seed + (b << 32) + t` in period t = 1, 2, ...: the lone class's
+    `seed + t` on a per-environment base, so that two environments never meet on one key at different times.
+
+        forward(states, actions=None, active=None)   -> (a_seq [B, H, da] before the roll, omega [B, S]); NaN rows for inactive environments
+        step(actions [B, da], new_states [B, ds])    notes the update; the next forward() carries it out
+        tick(states, plant)                          forward, `plant(states, actions) -> new_states`, step
+
+    `mpf` is the prototype: every environment starts from its particles (or from `init_particles[b]`, [B, Mp, P]), optimiser state and
+    bandwidths; the first forward()'s states are the observations the first update's predictions start from.  There is no unfused path:
+    what the fused call does not take is refused."""
+
+    def __init__(self, controller, model, mpf, mpf_bw=None, mpf_steps=20, seed=0, roll=1, init_particles=None):
+        from .amppi import BatchAMPPI
+
+        if not isinstance(controller, BatchAMPPI):
+            raise TypeError("BatchDualAMPPI needs a BatchAMPPI controller, got %s" % type(controller).__name__)
+        if getattr(controller, "_sample_shape", None) is None and getattr(controller, "_tf", None) is None:
+            raise ValueError("BatchDualAMPPI needs a controller that samples dynamics parameters: params_sampling='none' reads no filter")
+        if bool(getattr(mpf.likelihood, "log_space", False)):
+            raise NotImplementedError("a log-space filter under AMPPI: the controller hands samples to the model as drawn (amppi.py:134-139)")
+        if int(roll) < 0:
+            raise ValueError("roll=%d: roll >= 0" % roll)
+        tf = getattr(controller, "_tf", None)
+        if tf is not None and (not tf.default_sqrt or tf.n != mpf._dev.P):
+            raise NotImplementedError("a sigma-point transform with a custom sqrt_method, or over another number of parameters than the "
+                                      "filter's, has no fused form - and a batch has no other")
+        self.controller, self.model, self.mpf = controller, model, mpf
+        self.n_envs = controller.n_envs
+        self.mpf_bw, self.mpf_steps, self.roll = mpf_bw, int(mpf_steps), int(roll)
+        self._seed, self._t, self._pending = int(seed), 0, None
+        if init_particles is not None:
+            init_particles = torch.as_tensor(init_particles, dtype=torch.float).detach().clone()
+            want = (self.n_envs, mpf._dev.Mp, mpf._dev.P)
+            if tuple(init_particles.shape) != want:
+                raise ValueError("init_particles has shape %s, the batch takes %s" % (tuple(init_particles.shape), want))
+        self._init_particles = init_particles
+        self._mb = None
+        self.ticks = 0
+        self.last_bw = None
+        self.last_costs = None
+
+    def prior_keys(self, t):
+        """The Philox keys of period t = 1, 2, ...: seed + (b << 32) + t for environment b (modulo 2^64)."""
+        return [(self._seed + (b << 32) + int(t)) & 0xFFFFFFFFFFFFFFFF for b in range(self.n_envs)]
+
+    def __deepcopy__(self, memo):
+        new = copy.copy(self)
+        memo[id(self)] = new
+        new.controller = copy.deepcopy(self.controller, memo)
+        new.model = copy.deepcopy(self.model, memo)
+        new.mpf = copy.deepcopy(self.mpf, memo)
+        if getattr(self.model, "params_dist", None) is self.mpf.prior:
+            new.model.params_dist = new.mpf.prior
+        new._mb = None if self._mb is None else self._mb.clone()
+        new._pending = None if self._pending is None else tuple(v.copy() for v in self._pending)
+        return new
+
+    def _filters(self, states=None):
+        if self._mb is None:
+            if self.mpf.draw_source is not None:
+                raise NotImplementedError("recorded filter draws (draw_source) have no batched form")
+            mb = self.mpf._dev.batch(self.n_envs)
+            if self._init_particles is not None:
+                mb.set_particles(self._init_particles.numpy())
+            if states is not None:
+                mb.set_obs(states)
+            self._mb = mb
+        return self._mb
+
+    @property
+    def a_seq(self):
+        """[B, H, da]"""
+        return self.controller.a_seq
+
+    @property
+    def dyn_particles(self):
+        """[B, Mp, P]; a noted update is carried out first"""
+        self._flush()
+        return torch.from_numpy(self._filters().get_particles())
+
+    def _flush(self):
+        pend = self._pending
+        if pend is not None:
+            _, bw = self._filters().optimize(pend[0], pend[1], self.mpf_bw, self.mpf_steps)
+            self._pending, self.last_bw = None, torch.from_numpy(bw)
+
+    def forward(self, states, actions=None, active=None):
+        """actions [B, S, H, da]: recorded action samples in place of device-drawn noise; active [B]: the environments that tick"""
+        ctrl = self.controller
+        self.model.params_dist = self.mpf.prior  # (what the context's configuration reads)
+        batch = ctrl._ensure_batch(self.model)
+        if ctrl._tf is not None:
+            batch.ctx.set_sigma_scale(ctrl._tf.scale)
+        st = torch.as_tensor(states, dtype=torch.float).reshape(self.n_envs, -1).numpy()
+        mb = self._filters(st)
+        acts = None if actions is None else torch.as_tensor(actions, dtype=torch.float).numpy()
+        pend = self._pending
+        costs, omega, a_seq, _, bw = batch.dual_tick(mb, st, None if pend is None else pend[0], acts,
+                                                     shared_params=ctrl.params_sampling == "single", mpf_steps=self.mpf_steps,
+                                                     mpf_bw=self.mpf_bw, seeds=self.prior_keys(self._t + 1), roll=self.roll, active=active)
+        self._t, self._pending = self._t + 1, None  # (a refused call consumes neither the keys nor the noted update)
+        if pend is not None:
+            self.last_bw = torch.from_numpy(bw)
+        self.last_costs = torch.from_numpy(costs)
+        self.ticks += 1
+        return torch.from_numpy(a_seq), torch.from_numpy(omega)
+
+    def step(self, actions, new_states):
+        self._flush()
+        B = self.n_envs
+        self._pending = (torch.as_tensor(actions, dtype=torch.float).reshape(B, -1).numpy().copy(),
+                         torch.as_tensor(new_states, dtype=torch.float).reshape(B, -1).numpy().copy())
+        return None, None
+
+    def tick(self, states, plant):
+        """One loop iteration with a host plant callable `plant(states [B, ds], actions [B, da]) -> new_states [B, ds]`: forward,
+        plant, step.  Returns (actions, new_states, omega)."""
+        a_seq, omega = self.forward(states)
+        actions = a_seq[:, 0]
+        new_states = plant(states, actions)
+        self.step(actions, new_states)
+        return actions, new_states, omega

@@ -333,6 +333,56 @@ __global__ __launch_bounds__(AMPPI_THREADS) void amppi_skid_nav_batch_kernel(con
 #include "amppi_body.inc"
 }
 
+// ---- the batched tick coupled to B dynamics filters (dust_amppi_dual_batch_tick, "extended"): the grid of amppi_batch_kernel with
+// PRIOR = true.  Lane s of environment b draws row s of dust_mpf_prior_sample(filter b, S, prior_seeds[b]) itself: means at
+// x + b K P, the bandwidths of environment b's prior_bwv (device memory: the batched filter kernel wrote them just ahead on the same
+// stream), the key prior_seeds[b].  A workgroup makes itself the AmppiPrior of its environment - the body reads it by AmppiPrior's names.
+struct AmppiPriorBatch {
+  const float *means;     // [B][K][P]: the filters' particles, read in place
+  int K, P;
+  const float *bwv;       // [B][4]
+  const uint64_t *seeds;  // [B]
+  float *params_out;      // [B][S][P] or nullptr
+};
+__device__ __forceinline__ AmppiPrior amppi_env_prior(const AmppiPriorBatch &p, const int env, const int S) {
+  const float *b = p.bwv + (size_t)env * 4;
+  return AmppiPrior{p.means + (size_t)env * (size_t)p.K * (size_t)p.P, p.K, p.P, {b[0], b[1], b[2], b[3]}, p.seeds[env],
+                    p.params_out ? p.params_out + (size_t)env * (size_t)S * (size_t)p.P : nullptr};
+}
+struct AmppiPriorBatchArgs {
+  AmppiBatchArgs k;
+  AmppiPriorBatch pr;
+};
+template <int MODEL>
+__global__ __launch_bounds__(AMPPI_THREADS) void amppi_prior_batch_kernel(const AmppiPriorBatchArgs kp) {
+  constexpr bool NAV = false, PRIOR = true;
+  const SkidNav *const nav = nullptr;
+  uint32_t *const grid_lds = nullptr;
+  const int env = (int)blockIdx.y;
+  if (kp.k.active && kp.k.active[env] == 0) return;
+  const AmppiEnvArgs a = amppi_env_view(kp.k, env);
+  const AmppiPrior pe = amppi_env_prior(kp.pr, env, a.S);
+  const AmppiPrior *const pri = &pe;
+#include "amppi_body.inc"
+}
+struct AmppiNavPriorBatchArgs {
+  AmppiBatchArgs k;
+  SkidNav nav;
+  AmppiPriorBatch pr;
+};
+__global__ __launch_bounds__(AMPPI_THREADS) void amppi_skid_nav_prior_batch_kernel(const AmppiNavPriorBatchArgs kp) {
+  constexpr int MODEL = DUST_MODEL_SKID_STEER;
+  constexpr bool NAV = true, PRIOR = true;
+  const SkidNav *const nav = &kp.nav;
+  extern __shared__ __attribute__((aligned(16))) uint32_t grid_lds[];
+  const int env = (int)blockIdx.y;
+  if (kp.k.active && kp.k.active[env] == 0) return;
+  const AmppiEnvArgs a = amppi_env_view(kp.k, env);
+  const AmppiPrior pe = amppi_env_prior(kp.pr, env, a.S);
+  const AmppiPrior *const pri = &pe;
+#include "amppi_body.inc"
+}
+
 // dust_amppi_batch_roll: amppi_roll_kernel on a_seq [B][D], one workgroup per environment; inactive environments keep their sequence
 __global__ void amppi_batch_roll_kernel(float *a_seq, const int D, const int shift, const unsigned char *active) {
   const int env = (int)blockIdx.x;

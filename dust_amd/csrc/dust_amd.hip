@@ -1648,8 +1648,11 @@ static int batch_rows_d2h(dust_amppi_batch *b, float *dst, const float *src, siz
   return DUST_OK;
 }
 
-extern "C" int dust_amppi_batch_update(dust_amppi_batch *b, const float *states, const float *actions, const float *params, int flags,
-                                       const unsigned char *active, float *costs, float *omega, float *a_seq) {
+// dust_amppi_batch_update up to and including its launch.  dust_amppi_dual_batch_tick (mpf.hpp) enters with `staged` (the parameter rows
+// already sit in b->params, written there on the batch's stream: `params` is then only "there are rows") or with `prior` (the lanes draw
+// their rows themselves from their environment's filter prior, "extended"; prior->params_out, when set, has room for [B][S][P])
+static int batch_update_launch(dust_amppi_batch *b, const float *states, const float *actions, const float *params, int flags,
+                               const unsigned char *active, const bool staged, const dust::AmppiPriorBatch *prior) {
   TRY(batch_null(b));
   if (!states) return fail(DUST_ERR_INVALID, "null argument");
   dust_ctx *c = b->c;
@@ -1658,7 +1661,10 @@ extern "C" int dust_amppi_batch_update(dust_amppi_batch *b, const float *states,
   if (flags & DUST_STORE_STATES) return fail(DUST_ERR_UNSUPPORTED, "the batched AMPPI tick does not store its trajectories (DUST_STORE_STATES): run a lone dust_amppi_update for them");
   int mode = AMPPI_PARAMS_NONE, pts = 1;
   size_t prows = 0;
-  TRY(amppi_params_mode(c, params != nullptr, flags, nullptr, &mode, &pts, &prows));
+  dust::AmppiPrior one;  // (amppi_params_mode reads the prior's P alone)
+  memset(&one, 0, sizeof one);
+  if (prior) one.P = prior->P;
+  TRY(amppi_params_mode(c, params != nullptr, flags, prior ? &one : nullptr, &mode, &pts, &prows));
   const size_t B = (size_t)b->B, S = (size_t)c->S, D = (size_t)c->D, P = (size_t)c->cfg.dim_p;
   HIP_TRY(hipSetDevice(c->cfg.device));
   if (actions) {
@@ -1667,7 +1673,7 @@ extern "C" int dust_amppi_batch_update(dust_amppi_batch *b, const float *states,
   }
   if (prows) {
     TRY(ensure(&b->params, &b->params_cap, B * prows * P));
-    TRY(h2d(c, b->params, params, B * prows * P * sizeof(float)));
+    if (!staged) TRY(h2d(c, b->params, params, B * prows * P * sizeof(float)));
   }
   TRY(batch_stage_inputs(b, states, active));
   AmppiNavBatchArgs kn;
@@ -1691,7 +1697,27 @@ extern "C" int dust_amppi_batch_update(dust_amppi_batch *b, const float *states,
   const bool nav = c->cfg.model == DUST_MODEL_SKID_STEER && c->skid_w_obs != 0.f;
   if (nav) TRY(skid_nav_args(c, kn.nav));
   HIP_TRY(hipMemsetAsync(b->ticket, 0, B * sizeof(unsigned int), c->stream));
-  {
+  if (prior) {
+    Prof pr(c, DUST_K_AMPPI);
+    if (nav) {
+      AmppiNavPriorBatchArgs kp;
+      kp.k = k;
+      kp.nav = kn.nav;
+      kp.pr = *prior;
+      amppi_skid_nav_prior_batch_kernel<<<grid, AMPPI_THREADS, (size_t)kn.nav.grid_words * sizeof(uint32_t), c->stream>>>(kp);
+    } else {
+      AmppiPriorBatchArgs kp;
+      kp.k = k;
+      kp.pr = *prior;
+      switch (c->cfg.model) {
+        case DUST_MODEL_PENDULUM: amppi_prior_batch_kernel<DUST_MODEL_PENDULUM><<<grid, AMPPI_THREADS, 0, c->stream>>>(kp); break;
+        case DUST_MODEL_PARTICLE: amppi_prior_batch_kernel<DUST_MODEL_PARTICLE><<<grid, AMPPI_THREADS, 0, c->stream>>>(kp); break;
+        case DUST_MODEL_SKID_STEER: amppi_prior_batch_kernel<DUST_MODEL_SKID_STEER><<<grid, AMPPI_THREADS, 0, c->stream>>>(kp); break;
+        default: amppi_prior_batch_kernel<DUST_MODEL_CARTPOLE><<<grid, AMPPI_THREADS, 0, c->stream>>>(kp); break;
+      }
+    }
+    HIP_TRY(hipGetLastError());
+  } else {
     Prof pr(c, DUST_K_AMPPI);
     if (nav) amppi_skid_nav_batch_kernel<<<grid, AMPPI_THREADS, (size_t)kn.nav.grid_words * sizeof(uint32_t), c->stream>>>(kn);
     else switch (c->cfg.model) {
@@ -1705,6 +1731,14 @@ extern "C" int dust_amppi_batch_update(dust_amppi_batch *b, const float *states,
   b->acts_valid = true;
   if (active) b->last_active.assign(active, active + B);
   else b->last_active.clear();
+  return DUST_OK;
+}
+
+extern "C" int dust_amppi_batch_update(dust_amppi_batch *b, const float *states, const float *actions, const float *params, int flags,
+                                       const unsigned char *active, float *costs, float *omega, float *a_seq) {
+  TRY(batch_update_launch(b, states, actions, params, flags, active, false, nullptr));
+  dust_ctx *c = b->c;
+  const size_t S = (size_t)c->S, D = (size_t)c->D;
   if (!costs && !omega && !a_seq) return DUST_OK;
   if (costs) TRY(batch_rows_d2h(b, costs, b->costs, S, active));
   if (omega) TRY(batch_rows_d2h(b, omega, b->omega, S, active));

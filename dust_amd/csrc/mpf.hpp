@@ -249,6 +249,16 @@ __device__ __forceinline__ void mpf_cart_score(const CartLik *k, const int log_s
   }
 }
 
+// ... for the B environments of a batched filter in one launch: lane b, the same fast_cosf / fast_sinf (LIK: SkidLik or CartLik - both
+// keep the past heading / angle in past[2])
+template <class LIK>
+__global__ void mpf_lik_angle_batch_kernel(LIK *k, const int B, const unsigned char *active) {
+  const int env = blockIdx.x * blockDim.x + threadIdx.x;
+  if (env >= B || (active && active[env] == 0)) return;
+  k[env].cs = fast_cosf(k[env].past[2]);
+  k[env].sn = fast_sinf(k[env].past[2]);
+}
+
 __global__ void mpf_cart_angle_kernel(CartLik *k) {
   if (threadIdx.x == 0) {
     k->cs = fast_cosf(k->past[2]);
@@ -266,150 +276,100 @@ __global__ void mpf_cart_angle_kernel(CartLik *k) {
 // with it compiled out the Pendulum / Particle / skid-steer instances are the parent's (the register table).
 template <int P, bool CART = false>
 __global__ __launch_bounds__(1024) void mpf_optimize_kernel(const MpfArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int Mp = a.Mp;
-  const int Mpad = (Mp + 63) & ~63, R = blockDim.x / Mpad;
-  const int r = __builtin_amdgcn_readfirstlane((int)threadIdx.x / Mpad), i = (int)threadIdx.x - r * Mpad;
-  double *dbuf = reinterpret_cast<double *>(sm);  // [R][Mpad][2 P] partial sums (prior: zs + acc[P]; Stein: gk[P] + ks[P])
-  float *xs = reinterpret_cast<float *>(dbuf + (size_t)R * Mpad * 2 * P);  // [Mp][P]
-  float *sc = xs + Mp * P;    // [Mp][P] scores
-  float *nrm = sc + Mp * P;   // [Mp] squared norms
-  float *red = nrm + Mp;      // [32]
-  const bool on = i < Mp;
-  const int per = (Mp + R - 1) / R, k0 = r * per, k1 = min(Mp, k0 + per);
-  if (on && r == 0)
-    _Pragma("unroll") for (int p = 0; p < P; ++p) xs[i * P + p] = a.x[i * P + p];
+#define MPF_UNIFORM(v) (v)
+#include "mpf_body.inc"
+#undef MPF_UNIFORM
+}
+
+// ---- B filters in ONE launch (dust_mpf_batch_optimize, dust_amppi_dual_batch_tick): one workgroup per environment, blockIdx.x is the
+// environment.  A workgroup makes itself the arguments of a lone call on its environment's slices - particles and optimiser slots
+// [B][Mp][P], the observations, the action, the steps taken so far (MpfEnvIn [B], staged by the host per call), the prior bandwidths
+// [B][4], the kernel bandwidth [B] (Silverman's, written by mpf_silverman_batch_kernel just ahead on the same stream; or the call's fixed
+// one), grad_norms [B][gn_stride], SkidLik / CartLik [B] - and runs the SAME body text on them: the arithmetic and its order are the lone
+// kernel's, per environment.  Model, grid bits, obs_std, the optimiser's options, Mp and P are shared.  Behind the body lane 0 does what
+// the host does after a lone call: the prior bandwidths become the kernel bandwidth (update_prior(bw), mpf.py:85) and bw_used[b] records
+// it.  The workgroup of an environment whose `active` byte is 0 returns before it touches anything.  No workgroup talks to another one.
+// MODEL, LOG, ADAM: the shared model - with it the widths of state and action -, log_space and whether the optimiser is Adam (its step
+// takes two fp64 powers per parameter: the other register peak beside the likelihood's) are known to the launch, so each instance is
+// told them (assumptions on the arguments, not another text): the other families' branches of the body, the other parameter space's and
+// the other optimisers' fold away, and with them the spilled registers the lone kernel's instances carry.  Instances exist for as many
+// particle columns as the model has parameters (Pendulum 3, Particle 1, skid-steer 3, cart-pole 4: mpfb_limits refuses the rest).
+struct MpfEnvIn {
+  float past_obs[4], obs[4], past_action[2];
+  int t0, pad;
+};
+struct MpfBatchArgs {
+  MpfArgs a;                    // the shared fields; x, grad_norms and the optimiser slots are environment 0's; the per-call values are unused
+  const MpfEnvIn *in;           // [B]
+  float *prior_bwv;             // [B][4] in / out
+  float *bw;                    // [B]: the bandwidth of this call, in (bw_fixed <= 0) / out
+  float bw_fixed;               // > 0: every environment's bandwidth
+  int gn_stride;
+  const SkidLik *skl;           // [B] (DUST_MODEL_SKID_STEER)
+  const CartLik *cpl;           // [B] (DUST_MODEL_CARTPOLE)
+  const unsigned char *active;  // [B] or nullptr: everybody
+};
+// What the body text reads through `a`, for ONE environment: MpfArgs' member names.  The shared structs stay where the launch put them
+// (references into the kernel's arguments, as AmppiEnvArgs keeps them: a local COPY of the whole argument block goes to scratch memory);
+// the environment's own values are plain members, every array among them read at compile-time indices only.
+struct MpfEnvArgs {
+  const DevModel &dm;
+  int Mp, P, ds, da, n_steps, log_space;
+  float prior_bwv[4];
+  float bw, obs_std;
+  float past_obs[4], past_action[2], obs[4];
+  const SkidLik *skl;
+  const CartLik *cpl;
+  const float *act_seq;
+  float *x, *grad_norms, *phi_out;
+  const OptArgs &opt;
+  int t0;
+  float *opt_s0, *opt_s1, *opt_s2;
+};
+__device__ __forceinline__ MpfEnvArgs mpf_env_view(const MpfBatchArgs &k, const int env) {
+  const MpfArgs &g = k.a;
+  const MpfEnvIn &in = k.in[env];
+  const float *pb = k.prior_bwv + (size_t)env * 4;
+  const size_t np = (size_t)env * (size_t)g.Mp * (size_t)g.P;
+  return MpfEnvArgs{g.dm, g.Mp, g.P, g.ds, g.da, g.n_steps, g.log_space,
+                    {pb[0], pb[1], pb[2], pb[3]},
+                    k.bw_fixed > 0.f ? k.bw_fixed : k.bw[env], g.obs_std,
+                    {in.past_obs[0], in.past_obs[1], in.past_obs[2], in.past_obs[3]},
+                    {in.past_action[0], in.past_action[1]},
+                    {in.obs[0], in.obs[1], in.obs[2], in.obs[3]},
+                    k.skl + env, k.cpl + env, nullptr,
+                    g.x + np, g.grad_norms + (size_t)env * (size_t)k.gn_stride, nullptr,
+                    g.opt, in.t0,
+                    g.opt_s0 ? g.opt_s0 + np : nullptr, g.opt_s1 ? g.opt_s1 + np : nullptr, g.opt_s2 ? g.opt_s2 + np : nullptr};
+}
+// a value that every lane of the workgroup holds alike, moved to scalar registers (the bits stay)
+__device__ __forceinline__ float mpf_uniform(const float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+__device__ __forceinline__ double mpf_uniform(const double v) {
+  const long long b = __double_as_longlong(v);
+  const unsigned int lo = (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)(b & 0xffffffffll));
+  const unsigned int hi = (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)((unsigned long long)b >> 32));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | (unsigned long long)lo));
+}
+template <int P, bool CART, int MODEL, bool LOG, bool ADAM>
+__global__ __launch_bounds__(1024) void mpf_optimize_batch_kernel(const MpfBatchArgs k) {
+  const int env = (int)blockIdx.x;
+  if (k.active && k.active[env] == 0) return;
+  __builtin_assume(k.a.dm.model == MODEL);
+  __builtin_assume(k.a.ds == (MODEL == DUST_MODEL_PENDULUM ? 2 : (MODEL == DUST_MODEL_SKID_STEER ? 5 : 4)));
+  __builtin_assume(k.a.da == (MODEL == DUST_MODEL_PENDULUM || MODEL == DUST_MODEL_CARTPOLE ? 1 : 2));
+  __builtin_assume(k.a.dm.log_space == (LOG ? 1 : 0));
+  __builtin_assume(k.a.log_space == (LOG ? 1 : 0));
+  __builtin_assume(ADAM ? k.a.opt.kind == DUST_OPT_ADAM : k.a.opt.kind != DUST_OPT_ADAM);
+  const MpfEnvArgs a = mpf_env_view(k, env);
+#define MPF_UNIFORM(v) mpf_uniform(v)
+#include "mpf_body.inc"
+#undef MPF_UNIFORM
+  // (every lane has read prior_bwv and bw into registers ahead of a barrier when n_steps > 0; the barrier here covers n_steps = 0)
   wg_sync();
-  const float bw2 = (float)((double)a.bw * (double)a.bw);
-  double inv_pbw[4], inv_pbw2[4];
-  _Pragma("unroll") for (int p = 0; p < 4; ++p) {
-    inv_pbw[p] = 1.0 / (double)a.prior_bwv[p < P ? p : 0];
-    inv_pbw2[p] = inv_pbw[p] * inv_pbw[p];
-  }
-  const double inv_bw2 = 1.0 / ((double)a.bw * (double)a.bw), inv_obs2 = 1.0 / ((double)a.obs_std * (double)a.obs_std);
-  float am[4] = {0.f, 0.f, 0.f, 0.f}, av[4] = {0.f, 0.f, 0.f, 0.f}, a2[4] = {0.f, 0.f, 0.f, 0.f};  // optimiser state of this lane's particle (registers for the whole launch)
-  if (on && r == 0)
-    _Pragma("unroll") for (int p = 0; p < P; ++p) {
-      if (a.opt_s0) am[p] = a.opt_s0[i * P + p];
-      if (a.opt_s1) av[p] = a.opt_s1[i * P + p];
-      if (a.opt_s2) a2[p] = a.opt_s2[i * P + p];
-    }
-  for (int it = 0; it < a.n_steps; ++it) {
-    float xi[4] = {0.f, 0.f, 0.f, 0.f};
-    if (on) {
-      _Pragma("unroll") for (int p = 0; p < P; ++p) xi[p] = xs[i * P + p];
-      // prior score (mpf.py:45): means alias the CURRENT particles (covariance prior_bw^2 I, uniform mixture), so the
-      // i-th logit is exactly 0 and no other is larger: the softmax needs no max pass
-      double zs = 0.0, acc[4] = {0, 0, 0, 0};
-      for (int k = k0; k < k1; ++k) {
-        double q = 0.0;
-        _Pragma("unroll") for (int p = 0; p < P; ++p) {
-          const double z = ((double)xi[p] - (double)xs[k * P + p]) * inv_pbw[p];
-          q += z * z;
-        }
-        const double w = (double)expf((float)(-0.5 * q));
-        zs += w;
-        _Pragma("unroll") for (int p = 0; p < P; ++p) acc[p] += w * ((double)xs[k * P + p] - (double)xi[p]);
-      }
-      double *d = dbuf + ((size_t)r * Mpad + i) * 2 * P;
-      d[0] = zs;
-      _Pragma("unroll") for (int p = 0; p < P; ++p) d[1 + p] = acc[p];  // 1 + P <= 2 P slots
-    }
-    wg_sync();
-    if (on && r == 0) {
-      double zs = 0.0, acc[4] = {0, 0, 0, 0};
-      for (int rr = 0; rr < R; ++rr) {
-        const double *d = dbuf + ((size_t)rr * Mpad + i) * 2 * P;
-        zs += d[0];
-        _Pragma("unroll") for (int p = 0; p < P; ++p) acc[p] += d[1 + p];
-      }
-      double s[4];
-      _Pragma("unroll") for (int p = 0; p < P; ++p) s[p] = acc[p] / zs * inv_pbw2[p];
-      // likelihood score (mpf.py:46-50, likelihoods.py:30-49)
-      if (CART) {
-        double gl[4];
-        mpf_cart_score<P>(a.cpl, a.log_space, xi, inv_obs2, gl);
-        _Pragma("unroll") for (int p = 0; p < P; ++p) sc[i * P + p] = (float)(s[p] + gl[p]);
-      } else if (a.dm.model == DUST_MODEL_SKID_STEER) {
-        double gl[4];
-        mpf_skid_score<P>(a.skl, a.log_space, xi, inv_obs2, gl);
-        _Pragma("unroll") for (int p = 0; p < P; ++p) sc[i * P + p] = (float)(s[p] + gl[p]);
-      } else {
-        float pred[4];
-        for (int k = 0; k < 4; ++k) pred[k] = k < a.ds ? a.past_obs[k] : 0.f;
-        const Coef cf = make_coef(a.dm, xi);
-        const float pa[2] = {a.act_seq ? a.act_seq[2 * it] : a.past_action[0], a.act_seq ? a.act_seq[2 * it + 1] : a.past_action[1]};
-        if (a.dm.model == DUST_MODEL_PENDULUM) model_step<DUST_MODEL_PENDULUM>(a.dm, cf, pred, pa);
-        else model_step<DUST_MODEL_PARTICLE>(a.dm, cf, pred, pa);
-        double J[4][4];
-        step_jacobian<P>(a.dm, a.past_obs, pa, xi, J);
-        _Pragma("unroll") for (int p = 0; p < P; ++p) {
-          double g = 0.0;
-          _Pragma("unroll") for (int k = 0; k < 4; ++k)
-            if (k < a.ds) g += J[k][p] * ((double)a.obs[k] - (double)pred[k]);
-          s[p] += g * inv_obs2;
-          sc[i * P + p] = (float)s[p];
-        }
-      }
-      float nn = 0.f;
-      _Pragma("unroll") for (int p = 0; p < P; ++p) nn = nn + xi[p] * xi[p];
-      nrm[i] = nn;
-    }
-    wg_sync();
-    // kernel + phi (svgd.py:92-99, mpf.py:52-56).  squared_distance's fp32 addmm rounding is followed: it is part of the
-    // reference's result (d^2 / bw^2 amplifies it) - dot as an fma chain, then |b|^2 - 2 a.b, then + |a|^2, clamp 0.
-    if (on) {
-      double gk[4] = {0, 0, 0, 0}, ks[4] = {0, 0, 0, 0};
-      const float ni = nrm[i];
-      for (int j = k0; j < k1; ++j) {
-        float dot = xi[0] * xs[j * P];
-        _Pragma("unroll") for (int q = 1; q < P; ++q) dot = fmaf(xi[q], xs[j * P + q], dot);
-        float q = (nrm[j] + (-2.0f * dot)) + ni;
-        q = fmaxf(q, 0.f);
-        const double k = (double)expf(((-q) / bw2) / 2.0f);
-        _Pragma("unroll") for (int p = 0; p < P; ++p) {
-          gk[p] -= k * ((double)xi[p] - (double)xs[j * P + p]);
-          ks[p] += k * (double)sc[j * P + p];
-        }
-      }
-      double *d = dbuf + ((size_t)r * Mpad + i) * 2 * P;
-      _Pragma("unroll") for (int p = 0; p < P; ++p) {
-        d[p] = gk[p];
-        d[P + p] = ks[p];
-      }
-    }
-    wg_sync();
-    float ph[4] = {0.f, 0.f, 0.f, 0.f};
-    if (on && r == 0) {
-      double gk[4] = {0, 0, 0, 0}, ks[4] = {0, 0, 0, 0};
-      for (int rr = 0; rr < R; ++rr) {
-        const double *d = dbuf + ((size_t)rr * Mpad + i) * 2 * P;
-        _Pragma("unroll") for (int p = 0; p < P; ++p) {
-          gk[p] += d[p];
-          ks[p] += d[P + p];
-        }
-      }
-      _Pragma("unroll") for (int p = 0; p < P; ++p) ph[p] = (float)(gk[p] * inv_bw2 + ks[p] / Mp);
-    }
-    float n2 = 0.f;
-    _Pragma("unroll") for (int p = 0; p < P; ++p) n2 += ph[p] * ph[p];
-    n2 = block_reduce<RED_SUM>(n2, red);
-    if (threadIdx.x == 0 && a.grad_norms) a.grad_norms[it] = sqrtf(n2);
-    if (on && r == 0 && it == 0 && a.phi_out)
-      _Pragma("unroll") for (int p = 0; p < P; ++p) a.phi_out[i * P + p] = ph[p];
-    if (on && r == 0) {
-      // x.grad = -phi; optimizer.step() (mpf.py:59-62)
-      _Pragma("unroll") for (int p = 0; p < P; ++p) xs[i * P + p] = opt_step(a.opt, xi[p], -ph[p], am[p], av[p], a2[p], (float)(a.t0 + it + 1));
-    }
-    wg_sync();
-  }
-  if (on && r == 0) {
-    _Pragma("unroll") for (int p = 0; p < P; ++p) a.x[i * P + p] = xs[i * P + p];
-    _Pragma("unroll") for (int p = 0; p < P; ++p) {
-      if (a.opt_s0) a.opt_s0[i * P + p] = am[p];
-      if (a.opt_s1) a.opt_s1[i * P + p] = av[p];
-      if (a.opt_s2) a.opt_s2[i * P + p] = a2[p];
-    }
+  if (threadIdx.x == 0) {
+    float *pb = k.prior_bwv + (size_t)env * 4;
+    _Pragma("unroll") for (int p = 0; p < 4; ++p) pb[p] = a.bw;
+    k.bw[env] = a.bw;
   }
 }
 
@@ -992,6 +952,23 @@ __global__ void mpf_sample_kernel(const float *means, int K, int P, const MpfBw 
   for (int p = 0; p < P; ++p) out[i * P + p] = means[k * P + p] + bw.v[p] * z[p];
 }
 
+// mpf_sample_kernel with n = 1 for B filters in one launch (the "single" mode of a batched dual tick): lane b draws row 0 of
+// dust_mpf_prior_sample(filter b, 1, seeds[b]) - the same counters, the same operations in the same order - into out[b * P]
+__global__ void mpf_sample_batch_kernel(const float *means, int K, int P, const float *bwv, const uint64_t *seeds, int B, float *out, const unsigned char *active) {
+  const int env = blockIdx.x * blockDim.x + threadIdx.x;
+  if (env >= B || (active && active[env] == 0)) return;
+  const uint64_t seed = seeds[env];
+  uint32_t r[4];
+  philox4x32_10(0u, 0x6d7066u, 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+  const int k = (int)(((unsigned long long)r[0] * (unsigned long long)K) >> 32);
+  float z[4];
+  philox_normal4(seed, 0u, 0x6d7067u, 1u, 0u, z);
+  const float *mu = means + ((size_t)env * (size_t)K + (size_t)k) * (size_t)P;
+#pragma unroll
+  for (int p = 0; p < 4; ++p)
+    if (p < P) out[(size_t)env * P + p] = mu[p] + bwv[(size_t)env * 4 + p] * z[p];
+}
+
 // Sigma points of mpf.prior for a Merwe scaled unscented transform (MultiDISCO._sigma_rollout, disco.py:240-251, on the prior that
 // MPF.update_prior builds, mpf.py:26-38): the mixture's mean and variance (MixtureSameFamily.mean / .variance, uniform weights),
 //     mean_p = sum_j x_jp / Mp          var_p = bw_p^2 + sum_j (x_jp - mean_p)^2 / Mp
@@ -1000,8 +977,8 @@ __global__ void mpf_sample_kernel(const float *means, int K, int P, const MpfBw 
 //     row 0: mean          row 1 + p: mean + sqrt(scale var_p) e_p          row 1 + P + p: mean - sqrt(scale var_p) e_p
 // written `reps` times in a row ([reps][2P + 1][P]: one set per SVGD iteration of the tick that consumes them).  One workgroup; sums in
 // double, per-lane strided partials then an LDS tree - a fixed order, the same bits for the same particles.  Mp <= 1024, P <= 4.
-__global__ __launch_bounds__(256) void mpf_sigma_points_kernel(const float *x, const int Mp, const int P, const MpfBw bw, const float scale, const int reps,
-                                                               float *out) {
+__device__ __forceinline__ void mpf_sigma_points_body(const float *x, const int Mp, const int P, const MpfBw &bw, const float scale, const int reps,
+                                                      float *out) {
   __shared__ double red[4][256];
   __shared__ double stat[2][4];  // mean, variance
   const int tid = threadIdx.x;
@@ -1054,6 +1031,20 @@ __global__ __launch_bounds__(256) void mpf_sigma_points_kernel(const float *x, c
     out[i] = v;
   }
 }
+__global__ __launch_bounds__(256) void mpf_sigma_points_kernel(const float *x, const int Mp, const int P, const MpfBw bw, const float scale, const int reps,
+                                                               float *out) {
+  mpf_sigma_points_body(x, Mp, P, bw, scale, reps, out);
+}
+// ... of B filters' priors in one launch, one workgroup per environment: particles [B][Mp][P], prior bandwidths [B][4] in device memory,
+// one set of points per environment into the batched tick's parameter rows [B][2P + 1][P]
+__global__ __launch_bounds__(256) void mpf_sigma_points_batch_kernel(const float *x, const int Mp, const int P, const float *bwv, const float scale, float *out,
+                                                                     const unsigned char *active) {
+  const int env = (int)blockIdx.x;
+  if (active && active[env] == 0) return;
+  const float *b = bwv + (size_t)env * 4;
+  const MpfBw bw{{b[0], b[1], b[2], b[3]}};
+  mpf_sigma_points_body(x + (size_t)env * (size_t)Mp * (size_t)P, Mp, P, bw, scale, 1, out + (size_t)env * (size_t)(2 * P + 1) * (size_t)P);
+}
 
 // KDEpy 1.1.0 `silvermans_rule` of the pooled particle values (mpf.py:68-73: `silvermans_rule(self.x.view(-1, 1))`; restated in
 // oracle/ref_shim.py - third party, parity unpinned) on the device: sigma = min(std(ddof = 1), IQR / 1.349) (the positive one when one
@@ -1061,7 +1052,7 @@ __global__ __launch_bounds__(256) void mpf_sigma_points_kernel(const float *x, c
 // (numpy on the float64 copy): mean and squared deviations in two passes, the quartiles by numpy's linear interpolation
 // (`a + (b - a) t`, from the upper end when t >= 1/2) between the order statistics around q (n - 1), which are found by RANK (every lane
 // counts the values below its own: n <= 4096 values, n^2 comparisons - 0.26 M at 256 particles x 2 parameters).  One workgroup.
-__global__ __launch_bounds__(1024) void mpf_silverman_kernel(const float *x, const int n, const float bw_scale, float *out) {
+__device__ __forceinline__ void mpf_silverman_body(const float *x, const int n, const float bw_scale, float *out) {
   extern __shared__ float sv_x[];  // [n]
   __shared__ double red[16];
   __shared__ double quart[4];      // order statistics floor / ceil of the two quartile positions
@@ -1116,6 +1107,15 @@ __global__ __launch_bounds__(1024) void mpf_silverman_kernel(const float *x, con
     }
     out[0] = bw;
   }
+}
+__global__ __launch_bounds__(1024) void mpf_silverman_kernel(const float *x, const int n, const float bw_scale, float *out) {
+  mpf_silverman_body(x, n, bw_scale, out);
+}
+// ... of B filters' particles x [B][n] in one launch, one workgroup per environment: bw[b], where the batched filter kernel reads it
+__global__ __launch_bounds__(1024) void mpf_silverman_batch_kernel(const float *x, const int n, const float bw_scale, float *bw, const unsigned char *active) {
+  const int env = (int)blockIdx.x;
+  if (active && active[env] == 0) return;
+  mpf_silverman_body(x + (size_t)env * (size_t)n, n, bw_scale, bw + env);
 }
 
 }  // namespace dust
@@ -1469,9 +1469,8 @@ extern "C" int dust_mpf_set_ctrl_noise(dust_mpf *m, const float *z, int n) {
 // The particle-independent part of the skid-steer likelihood for the coming launch (SkidLik), copied to the device on the filter's
 // stream; the heading's fp32 cosine and sine are added there by a one-lane kernel.  (The host copy is a member: every filter call
 // synchronises the stream before it returns, so the copy has been read by the time the next call rewrites it.)
-static int mpf_skid_prepare(dust_mpf *m, const dust::SkidLik **dev) {
-  if (!m->skl_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->skl_dev), sizeof(dust::SkidLik)));
-  dust::SkidLik &k = m->skl_host;
+// (the host part: `m` gives the model, the rest is one environment's - a batched filter fills one SkidLik per environment with it)
+static void mpf_skid_lik(const dust_mpf *m, const float *past_action, const float *past_obs, const float *loc, dust::SkidLik &k) {
   memset(&k, 0, sizeof k);
   const DevParam *ps[3] = {&m->skid.x_icr, &m->skid.wheel_radius, &m->skid.axial_distance};
   for (int q = 0; q < 3; ++q) {
@@ -1480,18 +1479,23 @@ static int mpf_skid_prepare(dust_mpf *m, const dust::SkidLik **dev) {
     k.fix_f[q] = (float)ps[q]->value;
     k.fix_d[q] = ps[q]->value;
   }
-  k.r = clampf_host(m->past_action[0], m->skid.lo[0], m->skid.hi[0]);
-  k.l = clampf_host(m->past_action[1], m->skid.lo[1], m->skid.hi[1]);
+  k.r = clampf_host(past_action[0], m->skid.lo[0], m->skid.hi[0]);
+  k.l = clampf_host(past_action[1], m->skid.lo[1], m->skid.hi[1]);
   k.dt = (float)m->cfg.model_cfg.dt;
   for (int q = 0; q < 5; ++q) {
-    k.past[q] = m->past_obs[q];
-    k.obs[q] = m->loc[q];
+    k.past[q] = past_obs[q];
+    k.obs[q] = loc[q];
   }
-  k.c = std::cos((double)m->past_obs[2]);
-  k.s = std::sin((double)m->past_obs[2]);
+  k.c = std::cos((double)past_obs[2]);
+  k.s = std::sin((double)past_obs[2]);
   k.sum = ((double)k.r + (double)k.l) * M_PI;
   k.dif = 2.0 * M_PI * ((double)k.r - (double)k.l);
   k.dtd = m->cfg.model_cfg.dt;
+}
+static int mpf_skid_prepare(dust_mpf *m, const dust::SkidLik **dev) {
+  if (!m->skl_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->skl_dev), sizeof(dust::SkidLik)));
+  dust::SkidLik &k = m->skl_host;
+  mpf_skid_lik(m, m->past_action, m->past_obs, m->loc, k);
   HIP_TRY(hipMemcpyAsync(m->skl_dev, &k, sizeof k, hipMemcpyHostToDevice, m->stream));
   dust::mpf_skid_heading_kernel<<<1, 64, 0, m->stream>>>(m->skl_dev);
   HIP_TRY(hipGetLastError());
@@ -1500,9 +1504,7 @@ static int mpf_skid_prepare(dust_mpf *m, const dust::SkidLik **dev) {
 }
 
 // ... and of the cart-pole likelihood (CartLik); the fp32 sine and cosine of the past angle are added on the device
-static int mpf_cart_prepare(dust_mpf *m, const dust::CartLik **dev) {
-  if (!m->cpl_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->cpl_dev), sizeof(dust::CartLik)));
-  dust::CartLik &k = m->cpl_host;
+static void mpf_cart_lik(const dust_mpf *m, const float *past_action, const float *past_obs, const float *loc, dust::CartLik &k) {
   memset(&k, 0, sizeof k);
   for (int q = 0; q < dust::CP_NPAR; ++q) {
     const DevParam &p = m->cart.par[q];
@@ -1513,19 +1515,24 @@ static int mpf_cart_prepare(dust_mpf *m, const dust::CartLik **dev) {
   const DevParam &pmp = m->cart.par[dust::CP_MP], &pl = m->cart.par[dust::CP_LEN];
   k.pm_py = pmp.kind == DUST_PARAM_PYFLOAT && pl.kind == DUST_PARAM_PYFLOAT;
   k.pm_d = pmp.value * pl.value;
-  k.ac = clampf_host(m->past_action[0], -1.0f, 1.0f);
+  k.ac = clampf_host(past_action[0], -1.0f, 1.0f);
   k.dt = (float)m->cfg.model_cfg.dt;
   for (int q = 0; q < 4; ++q) {
-    k.past[q] = m->past_obs[q];
-    k.obs[q] = m->loc[q];
+    k.past[q] = past_obs[q];
+    k.obs[q] = loc[q];
   }
-  k.c = std::cos((double)m->past_obs[2]);
-  k.s = std::sin((double)m->past_obs[2]);
-  k.w = (double)m->past_obs[3];
+  k.c = std::cos((double)past_obs[2]);
+  k.s = std::sin((double)past_obs[2]);
+  k.w = (double)past_obs[3];
   k.w2 = k.w * k.w;
-  k.sg = m->past_obs[1] > 0.f ? 1.0 : (m->past_obs[1] < 0.f ? -1.0 : 0.0);
+  k.sg = past_obs[1] > 0.f ? 1.0 : (past_obs[1] < 0.f ? -1.0 : 0.0);
   k.a = (double)k.ac;
   k.dtd = m->cfg.model_cfg.dt;
+}
+static int mpf_cart_prepare(dust_mpf *m, const dust::CartLik **dev) {
+  if (!m->cpl_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->cpl_dev), sizeof(dust::CartLik)));
+  dust::CartLik &k = m->cpl_host;
+  mpf_cart_lik(m, m->past_action, m->past_obs, m->loc, k);
   HIP_TRY(hipMemcpyAsync(m->cpl_dev, &k, sizeof k, hipMemcpyHostToDevice, m->stream));
   dust::mpf_cart_angle_kernel<<<1, 64, 0, m->stream>>>(m->cpl_dev);
   HIP_TRY(hipGetLastError());
@@ -1997,5 +2004,514 @@ extern "C" int dust_amppi_dual_tick(dust_ctx *c, dust_mpf *m, const float *state
     HIP_TRY(hipEventRecord(c->ev_dual, c->stream));
     HIP_TRY(hipStreamWaitEvent(m->stream, c->ev_dual, 0));
   }
+  return DUST_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// B dynamics filters of one configuration (dust_mpf_batch_*): the deep copies of the MPF the reference makes per episode
+// (simulations.py:62,78), updated in ONE launch (mpf_optimize_batch_kernel: one workgroup per environment, the single-workgroup form's
+// arithmetic).  The batch owns a private clone of the prototype filter - configuration, model, occupancy bits, optimiser options, stream -
+// and the per-environment rows: particles, optimiser slots, prior bandwidths and the kernel bandwidth on the device; observations, past
+// action and steps taken on the host (they reach the kernel through pinned memory per call: nobody waits for that copy).
+struct dust_mpf_batch {
+  dust_mpf *m;
+  int B;
+  float *x;            // [B][Mp][P]
+  float *opt_s[3];     // [B][Mp][P] or nullptr
+  float *bw;           // [B] the bandwidth of the last update
+  float *prior_bwv;    // [B][4]
+  float *gn;           // [B][n_steps] of the last update
+  size_t gn_cap;
+  std::vector<float> loc, past_obs, past_action;  // [B][5], [B][5], [B][2]
+  std::vector<unsigned char> have_past;
+  std::vector<int> opt_t;
+  // per-call inputs: MpfEnvIn [B] | prior seeds [B] | SkidLik / CartLik [B] | active mask [B]; two pinned slots, each with the event behind its copy
+  unsigned char *in_dev, *in_host[2];
+  hipEvent_t in_ev[2];
+  int in_slot;
+  hipEvent_t ev_ext;   // behind the last work a dual tick put on an AMPPI batch's stream
+  long long n_launch, n_calls;
+};
+
+static size_t mpfb_lik_bytes(const dust_mpf *m) {
+  const int model = m->cfg.model_cfg.model;
+  return model == DUST_MODEL_SKID_STEER ? sizeof(dust::SkidLik) : (model == DUST_MODEL_CARTPOLE ? sizeof(dust::CartLik) : 0);
+}
+static size_t mpfb_off_seeds(int B) { return (size_t)B * sizeof(dust::MpfEnvIn); }
+static size_t mpfb_off_lik(int B) { return mpfb_off_seeds(B) + (size_t)B * sizeof(uint64_t); }
+static size_t mpfb_off_mask(const dust_mpf_batch *mb) { return mpfb_off_lik(mb->B) + (size_t)mb->B * mpfb_lik_bytes(mb->m); }
+static size_t mpfb_in_bytes(const dust_mpf_batch *mb) { return mpfb_off_mask(mb) + (size_t)mb->B; }
+
+static void mpfb_free(dust_mpf_batch *mb) {
+  if (!mb) return;
+  if (mb->m) {
+    (void)hipSetDevice(mb->m->cfg.device);
+    if (mb->ev_ext) (void)hipEventSynchronize(mb->ev_ext);
+    (void)hipStreamSynchronize(mb->m->stream);
+  }
+  void *dev[] = {mb->x, mb->opt_s[0], mb->opt_s[1], mb->opt_s[2], mb->bw, mb->prior_bwv, mb->gn, mb->in_dev};
+  for (void *p : dev)
+    if (p) (void)hipFree(p);
+  for (int k = 0; k < 2; ++k) {
+    if (mb->in_host[k]) (void)hipHostFree(mb->in_host[k]);
+    if (mb->in_ev[k]) (void)hipEventDestroy(mb->in_ev[k]);
+  }
+  if (mb->ev_ext) (void)hipEventDestroy(mb->ev_ext);
+  if (mb->m) dust_mpf_destroy(mb->m);
+  delete mb;
+}
+
+// the batch around a filter it takes over: buffers allocated, nothing filled yet
+static int mpfb_alloc(dust_mpf *inner, int n_env, dust_mpf_batch **out) {
+  dust_mpf_batch *mb = new dust_mpf_batch();
+  mb->m = inner;
+  mb->B = n_env;
+  *out = mb;
+  const size_t B = (size_t)n_env, np = (size_t)inner->Mp * inner->P;
+  HIP_TRY(hipSetDevice(inner->cfg.device));
+  TRY(dalloc(&mb->x, B * np));
+  float *const slots[3] = {inner->opt_s0, inner->opt_s1, inner->opt_s2};
+  for (int k = 0; k < 3; ++k)
+    if (slots[k]) TRY(dalloc(&mb->opt_s[k], B * np));
+  TRY(dalloc(&mb->bw, B));
+  TRY(dalloc(&mb->prior_bwv, B * 4));
+  HIP_TRY(hipMemset(mb->bw, 0, B * sizeof(float)));
+  TRY(dalloc(&mb->in_dev, mpfb_in_bytes(mb)));
+  for (int k = 0; k < 2; ++k) {
+    HIP_TRY(hipHostMalloc((void **)&mb->in_host[k], mpfb_in_bytes(mb), hipHostMallocDefault));
+    HIP_TRY(hipEventCreateWithFlags(&mb->in_ev[k], hipEventDisableTiming));
+  }
+  HIP_TRY(hipEventCreateWithFlags(&mb->ev_ext, hipEventDisableTiming));
+  mb->loc.assign(B * 5, 0.f);
+  mb->past_obs.assign(B * 5, 0.f);
+  mb->past_action.assign(B * 2, 0.f);
+  mb->have_past.assign(B, 0);
+  mb->opt_t.assign(B, 0);
+  return DUST_OK;
+}
+
+// work a dual tick left on an AMPPI batch's stream comes first; the filters' own entries are synchronous on their own stream
+static int mpfb_settle(dust_mpf_batch *mb) {
+  HIP_TRY(hipSetDevice(mb->m->cfg.device));
+  HIP_TRY(hipEventSynchronize(mb->ev_ext));
+  return DUST_OK;
+}
+
+static int mpfb_limits(const dust_mpf *m, int n_env) {
+  if (n_env < 1 || n_env > 65535) return fail(DUST_ERR_INVALID, "n_env = %d outside [1, 65535] (one workgroup per environment)", n_env);
+  if (m->Mp > 1024 || m->P < 1 || m->P > 4) return fail(DUST_ERR_UNSUPPORTED, "a batched filter takes up to 1024 particles over 1 .. 4 parameters");
+  // (the batched kernel's instances are told their model's widths: mpf_optimize_batch_kernel)
+  const int model = m->cfg.model_cfg.model, want_ds = model == DUST_MODEL_PENDULUM ? 2 : (model == DUST_MODEL_SKID_STEER ? 5 : 4),
+            want_da = (model == DUST_MODEL_PENDULUM || model == DUST_MODEL_CARTPOLE) ? 1 : 2;
+  // one particle column per uncertain parameter, as mpf_model_ready asks of a skid-steer or cart-pole filter: the kernel is instantiated
+  // for as many columns as the model has parameters
+  const int max_p = model == DUST_MODEL_PENDULUM ? 3 : (model == DUST_MODEL_PARTICLE ? 1 : (model == DUST_MODEL_SKID_STEER ? 3 : 4));
+  if (m->P > max_p)
+    return fail(DUST_ERR_UNSUPPORTED, "a batched filter carries one particle column per uncertain parameter: this model has %d, the filter has dim_p = %d", max_p, m->P);
+  if (m->cfg.dim_s != want_ds || m->cfg.dim_a != want_da)
+    return fail(DUST_ERR_INVALID, "a batched filter over this model has dim_s = %d, dim_a = %d (got %d, %d)", want_ds, want_da, m->cfg.dim_s, m->cfg.dim_a);
+  if (m->cfg.model_cfg.model == DUST_MODEL_PARTICLE && m->cfg.model_cfg.ctrl_noise)
+    return fail(DUST_ERR_UNSUPPORTED, "a filter whose model carries control-channel noise draws its per-step actions on the host: no batched form");
+  return DUST_OK;
+}
+
+extern "C" int dust_mpf_batch_create(const dust_mpf *proto, int n_env, dust_mpf_batch **out) {
+  if (!proto || !out) return fail(DUST_ERR_INVALID, "null argument");
+  *out = nullptr;
+  TRY(mpfb_limits(proto, n_env));
+  dust_mpf *inner = nullptr;
+  TRY(dust_mpf_clone(proto, &inner));  // (particles, optimiser state, model, occupancy bits)
+  dust_mpf_batch *mb = nullptr;
+  int st = mpfb_alloc(inner, n_env, &mb);
+  if (st == DUST_OK) {
+    const size_t np = (size_t)inner->Mp * inner->P;
+    float *const slots[3] = {inner->opt_s0, inner->opt_s1, inner->opt_s2};
+    std::vector<float> pb((size_t)n_env * 4);
+    for (int e = 0; e < n_env && st == DUST_OK; ++e) {
+      if (hipMemcpy(mb->x + (size_t)e * np, inner->x, np * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess) st = fail(DUST_ERR_HIP, "hipMemcpy failed");
+      for (int k = 0; k < 3 && st == DUST_OK; ++k)
+        if (slots[k] && hipMemcpy(mb->opt_s[k] + (size_t)e * np, slots[k], np * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess)
+          st = fail(DUST_ERR_HIP, "hipMemcpy failed");
+      for (int p = 0; p < 4; ++p) pb[(size_t)e * 4 + p] = inner->prior_bwv[p];
+      for (int q = 0; q < 5; ++q) {
+        mb->loc[(size_t)e * 5 + q] = inner->loc[q];
+        mb->past_obs[(size_t)e * 5 + q] = inner->past_obs[q];
+      }
+      for (int q = 0; q < 2; ++q) mb->past_action[(size_t)e * 2 + q] = inner->past_action[q];
+      mb->have_past[e] = inner->have_past ? 1 : 0;
+      mb->opt_t[e] = inner->opt_t;
+    }
+    if (st == DUST_OK && hipMemcpy(mb->prior_bwv, pb.data(), pb.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) st = fail(DUST_ERR_HIP, "hipMemcpy failed");
+  }
+  if (st != DUST_OK) {
+    mpfb_free(mb);
+    return st;
+  }
+  *out = mb;
+  return DUST_OK;
+}
+
+extern "C" void dust_mpf_batch_destroy(dust_mpf_batch *mb) { mpfb_free(mb); }
+
+extern "C" int dust_mpf_batch_clone(const dust_mpf_batch *src, dust_mpf_batch **out) {
+  if (!src || !out) return fail(DUST_ERR_INVALID, "null argument");
+  *out = nullptr;
+  HIP_TRY(hipSetDevice(src->m->cfg.device));
+  HIP_TRY(hipEventSynchronize(src->ev_ext));
+  dust_mpf *inner = nullptr;
+  TRY(dust_mpf_clone(src->m, &inner));
+  dust_mpf_batch *mb = nullptr;
+  int st = mpfb_alloc(inner, src->B, &mb);
+  if (st == DUST_OK) {
+    const size_t B = (size_t)src->B, np = (size_t)inner->Mp * inner->P;
+    struct { void *d; const void *s; size_t n; } cp[] = {{mb->x, src->x, B * np * 4}, {mb->opt_s[0], src->opt_s[0], B * np * 4}, {mb->opt_s[1], src->opt_s[1], B * np * 4},
+                                                         {mb->opt_s[2], src->opt_s[2], B * np * 4}, {mb->bw, src->bw, B * 4}, {mb->prior_bwv, src->prior_bwv, B * 16}};
+    for (auto &c : cp)
+      if (st == DUST_OK && c.d && c.s && hipMemcpy(c.d, c.s, c.n, hipMemcpyDeviceToDevice) != hipSuccess) st = fail(DUST_ERR_HIP, "hipMemcpy failed");
+    mb->loc = src->loc;
+    mb->past_obs = src->past_obs;
+    mb->past_action = src->past_action;
+    mb->have_past = src->have_past;
+    mb->opt_t = src->opt_t;
+  }
+  if (st != DUST_OK) {
+    mpfb_free(mb);
+    return st;
+  }
+  *out = mb;
+  return DUST_OK;
+}
+
+extern "C" int dust_mpf_batch_set_particles(dust_mpf_batch *mb, const float *x) {
+  if (!mb || !x) return fail(DUST_ERR_INVALID, "null argument");
+  TRY(mpfb_settle(mb));
+  HIP_TRY(hipMemcpyAsync(mb->x, x, (size_t)mb->B * mb->m->Mp * mb->m->P * sizeof(float), hipMemcpyHostToDevice, mb->m->stream));
+  HIP_TRY(hipStreamSynchronize(mb->m->stream));
+  return DUST_OK;
+}
+extern "C" int dust_mpf_batch_get_particles(dust_mpf_batch *mb, float *x) {
+  if (!mb || !x) return fail(DUST_ERR_INVALID, "null argument");
+  TRY(mpfb_settle(mb));
+  HIP_TRY(hipMemcpyAsync(x, mb->x, (size_t)mb->B * mb->m->Mp * mb->m->P * sizeof(float), hipMemcpyDeviceToHost, mb->m->stream));
+  HIP_TRY(hipStreamSynchronize(mb->m->stream));
+  return DUST_OK;
+}
+extern "C" int dust_mpf_batch_set_obs(dust_mpf_batch *mb, const float *obs) {
+  if (!mb || !obs) return fail(DUST_ERR_INVALID, "null argument");
+  const int ds = mb->m->cfg.dim_s;
+  for (int e = 0; e < mb->B; ++e)
+    for (int q = 0; q < ds && q < 5; ++q) mb->loc[(size_t)e * 5 + q] = obs[(size_t)e * ds + q];
+  return DUST_OK;
+}
+extern "C" int dust_mpf_batch_get_prior_bw(dust_mpf_batch *mb, float *bw) {
+  if (!mb || !bw) return fail(DUST_ERR_INVALID, "null argument");
+  TRY(mpfb_settle(mb));
+  HIP_TRY(hipMemcpyAsync(bw, mb->prior_bwv, (size_t)mb->B * 4 * sizeof(float), hipMemcpyDeviceToHost, mb->m->stream));
+  HIP_TRY(hipStreamSynchronize(mb->m->stream));
+  return DUST_OK;
+}
+extern "C" int dust_mpf_batch_stats(dust_mpf_batch *mb, long long out[2]) {
+  if (!mb || !out) return fail(DUST_ERR_INVALID, "null argument");
+  out[0] = mb->n_launch;
+  out[1] = mb->n_calls;
+  return DUST_OK;
+}
+
+// what a batched update refuses, ahead of any copy or launch
+static int mpfb_update_check(const dust_mpf_batch *mb, const float *actions, const float *new_obs, int n_steps, const unsigned char *active) {
+  const dust_mpf *m = mb->m;
+  if (n_steps < 0 || n_steps > 4096) return fail(DUST_ERR_INVALID, "n_steps out of range");
+  TRY(mpf_model_ready(m));
+  if (new_obs && !actions) return fail(DUST_ERR_INVALID, "condition() needs the action that produced new_obs");
+  if (!new_obs)
+    for (int e = 0; e < mb->B; ++e)
+      if ((!active || active[e]) && !mb->have_past[e]) return fail(DUST_ERR_STATE, "Previous action is None. Need at least one observation to start sampling.");
+  if (m->cfg.model_cfg.model == DUST_MODEL_PARTICLE && m->cfg.model_cfg.with_obstacle && m->cfg.model_cfg.can_crash && !m->grid_bits)
+    return fail(DUST_ERR_STATE, "Particle model with obstacles: call dust_mpf_set_grid first");
+  return DUST_OK;
+}
+
+// The per-call inputs through the next pinned slot and - with `update` - the filter side of a period on `stream`: GaussianLikelihood.condition
+// of every active environment (likelihoods.py:51-64, on the host rows), the heading / angle terms of all environments in one launch
+// (skid-steer, cart-pole), Silverman's rule of all in one launch (bw <= 0), the update of all in one launch.  Nothing waits for the device.
+// The host rows an update moves on (observations, past action, steps taken): mpfb_enqueue fills them, the caller commits them once every
+// launch of its call has been enqueued - a call that fails on the way leaves the filters' host rows where they were.
+struct MpfbRows {
+  std::vector<float> loc, past_obs, past_action;
+  std::vector<unsigned char> have_past;
+  std::vector<int> opt_t;
+  bool filled = false;
+};
+static void mpfb_commit(dust_mpf_batch *mb, MpfbRows &w) {
+  if (!w.filled) return;
+  mb->loc.swap(w.loc);
+  mb->past_obs.swap(w.past_obs);
+  mb->past_action.swap(w.past_action);
+  mb->have_past.swap(w.have_past);
+  mb->opt_t.swap(w.opt_t);
+}
+
+static int mpfb_enqueue(dust_mpf_batch *mb, hipStream_t stream, const bool update, const float *actions, const float *new_obs, const float bw,
+                        const int n_steps, const unsigned char *active, const uint64_t *seeds, MpfbRows &w) {
+  dust_mpf *m = mb->m;
+  const int B = mb->B, ds = m->cfg.dim_s, da = m->cfg.dim_a, model = m->cfg.model_cfg.model;
+  const int slot = mb->in_slot;
+  mb->in_slot ^= 1;
+  HIP_TRY(hipEventSynchronize(mb->in_ev[slot]));  // (the copy out of this slot two calls ago; an event never recorded is complete)
+  unsigned char *hb = mb->in_host[slot];
+  dust::MpfEnvIn *in = reinterpret_cast<dust::MpfEnvIn *>(hb);
+  if (seeds) memcpy(hb + mpfb_off_seeds(B), seeds, (size_t)B * sizeof(uint64_t));
+  if (active) memcpy(hb + mpfb_off_mask(mb), active, (size_t)B);
+  if (update) {
+    w.loc = mb->loc;
+    w.past_obs = mb->past_obs;
+    w.past_action = mb->past_action;
+    w.have_past = mb->have_past;
+    w.opt_t = mb->opt_t;
+    w.filled = true;
+    for (int e = 0; e < B; ++e) {
+      float *loc = &w.loc[(size_t)e * 5], *past = &w.past_obs[(size_t)e * 5], *pa = &w.past_action[(size_t)e * 2];
+      const bool on = !active || active[e];
+      if (on && new_obs) {
+        memcpy(past, loc, 5 * sizeof(float));
+        for (int q = 0; q < ds && q < 5; ++q) loc[q] = new_obs[(size_t)e * ds + q];
+        for (int q = 0; q < 2; ++q) pa[q] = q < da ? actions[(size_t)e * da + q] : 0.f;
+        w.have_past[e] = 1;
+      }
+      memset(&in[e], 0, sizeof in[e]);
+      for (int q = 0; q < 4; ++q) {
+        in[e].past_obs[q] = past[q];
+        in[e].obs[q] = loc[q];
+      }
+      in[e].past_action[0] = pa[0];
+      in[e].past_action[1] = pa[1];
+      in[e].t0 = w.opt_t[e];
+      if (model == DUST_MODEL_SKID_STEER) mpf_skid_lik(m, pa, past, loc, reinterpret_cast<dust::SkidLik *>(hb + mpfb_off_lik(B))[e]);
+      if (model == DUST_MODEL_CARTPOLE) mpf_cart_lik(m, pa, past, loc, reinterpret_cast<dust::CartLik *>(hb + mpfb_off_lik(B))[e]);
+      if (on) w.opt_t[e] += n_steps;
+    }
+  }
+  const size_t from = update ? 0 : mpfb_off_seeds(B), to = active ? mpfb_in_bytes(mb) : mpfb_off_mask(mb);
+  // (without an update the likelihood rows between the seeds and the mask are not read: the copy may carry whatever the slot holds)
+  HIP_TRY(hipMemcpyAsync(mb->in_dev + from, hb + from, to - from, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipEventRecord(mb->in_ev[slot], stream));
+  if (!update) return DUST_OK;
+  serve_cancel_device(m->cfg.device);  // (as mpf_launch: an armed control tick would hold every CU until its plant state arrives)
+  const unsigned char *mask = active ? mb->in_dev + mpfb_off_mask(mb) : nullptr;
+  const bool cart = model == DUST_MODEL_CARTPOLE;
+  if (model == DUST_MODEL_SKID_STEER) {
+    dust::mpf_lik_angle_batch_kernel<dust::SkidLik><<<(B + 255) / 256, 256, 0, stream>>>(reinterpret_cast<dust::SkidLik *>(mb->in_dev + mpfb_off_lik(B)), B, mask);
+    HIP_TRY(hipGetLastError());
+    mb->n_launch++;
+  }
+  if (cart) {
+    dust::mpf_lik_angle_batch_kernel<dust::CartLik><<<(B + 255) / 256, 256, 0, stream>>>(reinterpret_cast<dust::CartLik *>(mb->in_dev + mpfb_off_lik(B)), B, mask);
+    HIP_TRY(hipGetLastError());
+    mb->n_launch++;
+  }
+  const int n = m->Mp * m->P;
+  if (!(bw > 0.f)) {
+    dust::mpf_silverman_batch_kernel<<<B, 1024, (size_t)n * sizeof(float), stream>>>(mb->x, n, m->cfg.bw_scale, mb->bw, mask);
+    HIP_TRY(hipGetLastError());
+    mb->n_launch++;
+  }
+  MpfBatchArgs k;
+  memset(&k, 0, sizeof k);
+  MpfArgs &a = k.a;
+  a.dm = mpf_dev_model(m);
+  a.Mp = m->Mp;
+  a.P = m->P;
+  a.ds = ds;
+  a.da = da;
+  a.n_steps = n_steps;
+  a.log_space = m->cfg.log_space ? 1 : 0;  // (0 / 1: the instance is told which)
+  a.dm.log_space = a.log_space;
+  a.obs_std = m->cfg.obs_std;
+  a.x = mb->x;
+  a.grad_norms = mb->gn;
+  a.opt = m->opt;
+  a.opt_s0 = mb->opt_s[0];
+  a.opt_s1 = mb->opt_s[1];
+  a.opt_s2 = mb->opt_s[2];
+  k.in = reinterpret_cast<const dust::MpfEnvIn *>(mb->in_dev);
+  k.prior_bwv = mb->prior_bwv;
+  k.bw = mb->bw;
+  k.bw_fixed = bw > 0.f ? bw : 0.f;
+  k.gn_stride = n_steps;
+  k.skl = reinterpret_cast<const dust::SkidLik *>(mb->in_dev + mpfb_off_lik(B));
+  k.cpl = reinterpret_cast<const dust::CartLik *>(mb->in_dev + mpfb_off_lik(B));
+  k.active = mask;
+  // block size and dynamic LDS: the lone launch's own formulas (mpf_launch)
+  const int mpad = ((m->Mp + 63) / 64) * 64;
+  int R = 1;
+  while (mpad * R * 2 <= 1024) R *= 2;
+  const size_t lds = sizeof(double) * (size_t)R * mpad * 2 * m->P + sizeof(float) * ((size_t)2 * m->Mp * m->P + m->Mp + 32);
+#define DUST_LAUNCH_MPFB4(PP, CART, MODEL, LOG, ADAM)                                                                                    \
+  do {                                                                                                                                    \
+    if (lds > 64 * 1024)                                                                                                                  \
+      HIP_TRY(hipFuncSetAttribute((const void *)mpf_optimize_batch_kernel<PP, CART, MODEL, LOG, ADAM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+    mpf_optimize_batch_kernel<PP, CART, MODEL, LOG, ADAM><<<B, mpad * R, lds, stream>>>(k);                                               \
+  } while (0)
+#define DUST_LAUNCH_MPFB3(PP, CART, MODEL, LOG)                                        \
+  do {                                                                                 \
+    if (m->opt.kind == DUST_OPT_ADAM) DUST_LAUNCH_MPFB4(PP, CART, MODEL, LOG, true);   \
+    else DUST_LAUNCH_MPFB4(PP, CART, MODEL, LOG, false);                               \
+  } while (0)
+#define DUST_LAUNCH_MPFB2(PP, CART, MODEL)                          \
+  do {                                                              \
+    if (m->cfg.log_space) DUST_LAUNCH_MPFB3(PP, CART, MODEL, true); \
+    else DUST_LAUNCH_MPFB3(PP, CART, MODEL, false);                 \
+  } while (0)
+  // (P up to the model's parameter count: mpfb_limits has refused the rest)
+  if (cart) {
+    if (m->P == 1) DUST_LAUNCH_MPFB2(1, true, DUST_MODEL_CARTPOLE);
+    else if (m->P == 2) DUST_LAUNCH_MPFB2(2, true, DUST_MODEL_CARTPOLE);
+    else if (m->P == 3) DUST_LAUNCH_MPFB2(3, true, DUST_MODEL_CARTPOLE);
+    else DUST_LAUNCH_MPFB2(4, true, DUST_MODEL_CARTPOLE);
+  } else if (model == DUST_MODEL_SKID_STEER) {
+    if (m->P == 1) DUST_LAUNCH_MPFB2(1, false, DUST_MODEL_SKID_STEER);
+    else if (m->P == 2) DUST_LAUNCH_MPFB2(2, false, DUST_MODEL_SKID_STEER);
+    else if (m->P == 3) DUST_LAUNCH_MPFB2(3, false, DUST_MODEL_SKID_STEER);
+    else return fail(DUST_ERR_UNSUPPORTED, "no batched filter kernel for a skid-steer filter over %d particle columns", m->P);
+  } else if (model == DUST_MODEL_PARTICLE) {
+    if (m->P == 1) DUST_LAUNCH_MPFB2(1, false, DUST_MODEL_PARTICLE);
+    else return fail(DUST_ERR_UNSUPPORTED, "no batched filter kernel for a Particle filter over %d particle columns", m->P);
+  } else {
+    if (m->P == 1) DUST_LAUNCH_MPFB2(1, false, DUST_MODEL_PENDULUM);
+    else if (m->P == 2) DUST_LAUNCH_MPFB2(2, false, DUST_MODEL_PENDULUM);
+    else if (m->P == 3) DUST_LAUNCH_MPFB2(3, false, DUST_MODEL_PENDULUM);
+    else return fail(DUST_ERR_UNSUPPORTED, "no batched filter kernel for a Pendulum filter over %d particle columns", m->P);
+  }
+#undef DUST_LAUNCH_MPFB2
+#undef DUST_LAUNCH_MPFB3
+#undef DUST_LAUNCH_MPFB4
+  HIP_TRY(hipGetLastError());
+  mb->n_launch++;
+  return DUST_OK;
+}
+
+// room for grad_norms [B][n_steps] (a reallocation frees behind the device's queued work)
+static int mpfb_gn_room(dust_mpf_batch *mb, int n_steps) { return ensure(&mb->gn, &mb->gn_cap, (size_t)mb->B * (size_t)(n_steps > 0 ? n_steps : 1)); }
+
+// rows of `row` floats per environment, device -> host on `stream`, for the environments of `active` (nullptr: all): one copy per run of them
+static int mpfb_rows_d2h(int B, hipStream_t stream, float *dst, const float *src, size_t row, const unsigned char *active) {
+  for (int e = 0; e < B;) {
+    if (active && !active[e]) {
+      ++e;
+      continue;
+    }
+    int f = e + 1;
+    while (f < B && (!active || active[f])) ++f;
+    HIP_TRY(hipMemcpyAsync(dst + (size_t)e * row, src + (size_t)e * row, (size_t)(f - e) * row * sizeof(float), hipMemcpyDeviceToHost, stream));
+    e = f;
+  }
+  return DUST_OK;
+}
+
+// B x dust_mpf_optimize in one launch (plus one for Silverman's rule when bw <= 0, plus one for the heading / angle terms of a skid-steer /
+// cart-pole filter): environment b computes what a lone filter under DUST_MPF_GRID=0 computes on its inputs, bit for bit.
+extern "C" int dust_mpf_batch_optimize(dust_mpf_batch *mb, const float *actions, const float *new_obs, float bw, int n_steps, const unsigned char *active,
+                                       float *bw_used, float *grad_norms) {
+  if (!mb) return fail(DUST_ERR_INVALID, "null batch");
+  TRY(mpfb_update_check(mb, actions, new_obs, n_steps, active));
+  TRY(mpfb_settle(mb));
+  TRY(mpfb_gn_room(mb, n_steps));
+  hipStream_t st = mb->m->stream;
+  MpfbRows rows;
+  TRY(mpfb_enqueue(mb, st, true, actions, new_obs, bw, n_steps, active, nullptr, rows));
+  mpfb_commit(mb, rows);
+  mb->n_calls++;
+  if (bw_used) TRY(mpfb_rows_d2h(mb->B, st, bw_used, mb->bw, 1, active));
+  if (grad_norms && n_steps > 0) TRY(mpfb_rows_d2h(mb->B, st, grad_norms, mb->gn, (size_t)n_steps, active));
+  HIP_TRY(hipStreamSynchronize(st));
+  return DUST_OK;
+}
+
+// One control period of the dual loop for B environments in one call (B x dust_amppi_dual_tick): on the AMPPI batch's stream, in launch
+// order and without an event or a wait in between - the filters' update for (actions_prev[b], states[b]) (skipped when actions_prev is
+// NULL; mpf_bw <= 0: Silverman's rule per environment, on the device, handed to the update in device memory), the parameters from every
+// environment's refreshed prior ("extended": drawn inside the tick's kernel, amppi_prior_batch_kernel; DUST_AMPPI_PARAMS_SHARED: one
+// staged row per environment; sigma weights + a scale: staged sigma points), the B ticks, the outputs, the roll.  The number of launches
+// does not depend on B.  Environment b's draws take the key prior_seeds[b].  An environment with active[b] = 0 keeps its particles,
+// optimiser state, bandwidths, sequence and stream position, and its output rows are not written.  With every output NULL the call
+// returns without waiting for the device.
+extern "C" int dust_amppi_dual_batch_tick(dust_amppi_batch *b, dust_mpf_batch *mb, const float *states, const float *actions_prev, const float *actions,
+                                          int flags, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds, int roll_steps, const unsigned char *active,
+                                          float *costs, float *omega, float *a_seq, float *params_out, float *bw_used) {
+  if (!b || !mb || !states) return fail(DUST_ERR_INVALID, "null argument");
+  if (mpf_steps < 0 || roll_steps < 0) return fail(DUST_ERR_INVALID, "bad step counts");
+  dust_ctx *c = b->c;
+  dust_mpf *m = mb->m;
+  TRY(amppi_check(c));
+  TRY(dual_pair_check(c, m));
+  if (b->B != mb->B) return fail(DUST_ERR_INVALID, "the AMPPI batch has %d environments, the filter batch %d", b->B, mb->B);
+  if (m->cfg.log_space) return fail(DUST_ERR_UNSUPPORTED, "a log-space filter under AMPPI: the controller hands samples to the model as drawn (amppi.py:134-139)");
+  if (flags & DUST_STORE_STATES) return fail(DUST_ERR_UNSUPPORTED, "the AMPPI dual tick stores no trajectories");
+  if (flags & (DUST_EPS_F16 | DUST_STORE_F16)) return fail(DUST_ERR_UNSUPPORTED, "the AMPPI tick has no binary16 storage");
+  const bool sigma = c->mw_dev != nullptr, shared = (flags & DUST_AMPPI_PARAMS_SHARED) != 0;
+  if (sigma) {
+    if (!(c->sigma_scale > 0.f))
+      return fail(DUST_ERR_UNSUPPORTED, "the dual tick over sigma-point weights needs the transform's scale lambda + n (dust_set_sigma_scale)");
+    if (c->M != 2 * m->P + 1) return fail(DUST_ERR_INVALID, "sigma-point weights over P = %d parameters take M = 2 P + 1 = %d samples, the controller has M = %d", m->P, 2 * m->P + 1, c->M);
+  } else if (c->M != 1) {
+    return fail(DUST_ERR_INVALID, "n_params = %d > 1 is the sigma-point form of an AMPPI context: dust_set_param_weights first", c->M);
+  } else if (!prior_seeds) {
+    return fail(DUST_ERR_INVALID, "null argument: the draws from the filters' priors need prior_seeds [B]");
+  }
+  TRY(mpfb_limits(m, mb->B));
+  if (actions_prev) TRY(mpfb_update_check(mb, actions_prev, states, mpf_steps, active));
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  TRY(settle_pending(c));
+  const size_t B = (size_t)b->B, S = (size_t)c->S, D = (size_t)c->D, P = (size_t)m->P;
+  const size_t prows = sigma ? (size_t)c->M : (shared ? (size_t)1 : S);
+  // (reallocations free behind the device's queued work; they happen in the first period only)
+  if (sigma || shared || params_out) TRY(ensure(&b->params, &b->params_cap, B * prows * P));
+  if (actions_prev) TRY(mpfb_gn_room(mb, mpf_steps));
+  HIP_TRY(hipStreamWaitEvent(c->stream, mb->ev_ext, 0));  // (another AMPPI batch's tick on these filters: its stream first, without a host wait)
+  MpfbRows rows;
+  TRY(mpfb_enqueue(mb, c->stream, actions_prev != nullptr, actions_prev, states, mpf_bw, mpf_steps, active, prior_seeds, rows));
+  mb->n_calls++;
+  const unsigned char *mask = active ? mb->in_dev + mpfb_off_mask(mb) : nullptr;
+  int st;
+  if (sigma || shared) {
+    if (sigma) dust::mpf_sigma_points_batch_kernel<<<b->B, 256, 0, c->stream>>>(mb->x, m->Mp, m->P, mb->prior_bwv, c->sigma_scale, b->params, mask);
+    else
+      dust::mpf_sample_batch_kernel<<<(b->B + 255) / 256, 256, 0, c->stream>>>(mb->x, m->Mp, m->P, mb->prior_bwv,
+                                                                               reinterpret_cast<const uint64_t *>(mb->in_dev + mpfb_off_seeds(mb->B)), b->B, b->params, mask);
+    HIP_TRY(hipGetLastError());
+    mb->n_launch++;
+    st = batch_update_launch(b, states, actions, b->params, flags, active, true, nullptr);
+  } else {
+    dust::AmppiPriorBatch pr;
+    memset(&pr, 0, sizeof pr);
+    pr.means = mb->x;
+    pr.K = m->Mp;
+    pr.P = m->P;
+    pr.bwv = mb->prior_bwv;
+    pr.seeds = reinterpret_cast<const uint64_t *>(mb->in_dev + mpfb_off_seeds(mb->B));
+    pr.params_out = params_out ? b->params : nullptr;
+    st = batch_update_launch(b, states, actions, nullptr, flags, active, false, &pr);
+  }
+  if (st != DUST_OK) return st;
+  mpfb_commit(mb, rows);  // (every launch of the period is enqueued)
+  const bool bw_dev = bw_used && actions_prev && !(mpf_bw > 0.f);
+  if (bw_used && !bw_dev)
+    for (size_t e = 0; e < B; ++e)
+      if (!active || active[e]) bw_used[e] = actions_prev ? mpf_bw : 0.f;
+  const bool copies = costs || omega || a_seq || params_out || bw_dev;
+  if (costs) TRY(batch_rows_d2h(b, costs, b->costs, S, active));
+  if (omega) TRY(batch_rows_d2h(b, omega, b->omega, S, active));
+  if (a_seq) TRY(batch_rows_d2h(b, a_seq, b->a_seq, D, active));
+  if (params_out) TRY(batch_rows_d2h(b, params_out, b->params, prows * P, active));
+  if (bw_dev) TRY(batch_rows_d2h(b, bw_used, mb->bw, 1, active));
+  if (roll_steps > 0) {  // (dust_amppi_batch_roll on the mask this call has staged already)
+    const long shift = (long)roll_steps * c->da;
+    Prof pr(c, DUST_K_FORWARD);
+    amppi_batch_roll_kernel<<<b->B, 128, 0, c->stream>>>(b->a_seq, c->D, shift > c->D ? c->D : (int)shift,
+                                                         active ? reinterpret_cast<const unsigned char *>(b->in_dev) + B * 8 * sizeof(float) : nullptr);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(mb->ev_ext, c->stream));  // (the filters' own entries wait for it on the host)
+  if (copies) HIP_TRY(hipStreamSynchronize(c->stream));
   return DUST_OK;
 }

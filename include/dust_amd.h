@@ -388,7 +388,7 @@ int dust_amppi_batch_ctx(dust_amppi_batch *batch, dust_ctx **ctx);
  *   outputs, each may be NULL: costs [B][S], omega [B][S], a_seq [B][H][da] after the update.  With all three NULL - and actions
  *     and params NULL or on the device - the call returns without waiting for the device.
  * DUST_ERR_UNSUPPORTED (before any launch): DUST_STORE_STATES, binary16 storage (DUST_EPS_F16 / DUST_STORE_F16), and what
- * dust_amppi_update refuses; the filter-coupled tick (dust_amppi_dual_tick) has no batched form.  DUST_ERR_INVALID: NULL states,
+ * dust_amppi_update refuses; the filter-coupled tick of a batch is dust_amppi_dual_batch_tick (below).  DUST_ERR_INVALID: NULL states,
  * params without uncertain parameters, sigma weights without params. */
 int dust_amppi_batch_update(dust_amppi_batch *batch, const float *states, const float *actions, const float *params, int flags,
                             const unsigned char *active, float *costs, float *omega, float *a_seq);
@@ -584,6 +584,46 @@ int dust_dual_tick(dust_ctx *ctx, dust_mpf *mpf, const float *state, const float
 int dust_amppi_dual_tick(dust_ctx *ctx, dust_mpf *mpf, const float *state, const float *action_prev, const float *actions, int flags,
                          int mpf_steps, float mpf_bw, uint64_t seed, int roll_steps, float *costs, float *omega, float *a_seq,
                          float *params_out, float *bw_used);
+
+/* ---- B dynamics filters of one configuration: the deep copies of the MPF the reference makes per episode (simulations.py:62,78) ----
+ * One workgroup per environment runs the single-workgroup form of dust_mpf_optimize (mpf.hpp mpf_optimize_batch_kernel): environment b
+ * computes what a lone filter created under DUST_MPF_GRID=0 computes on its inputs, bit for bit.  Limits: up to 1024 particles over
+ * 1 .. 4 parameters, n_env in [1, 65535], no control-channel noise in the filter's model (its per-step actions are drawn on the host),
+ * and one particle column per uncertain parameter of the model - at most 3 (Pendulum: g, mass, length), 1 (Particle: mass), 3
+ * (skid-steer), 4 (cart-pole); a filter with more columns than its model has parameters is DUST_ERR_UNSUPPORTED.
+ * dust_mpf_batch_create copies everything `proto` holds into every environment - particles, observation, past observation and past
+ *   action, prior bandwidths, optimiser configuration, state and step count, model and occupancy grid; `proto` may be destroyed afterwards.
+ * dust_mpf_batch_clone: copy.deepcopy.  _set_particles / _get_particles: [B][Mp][P].  _set_obs: every environment's observation [B][ds]
+ *   (the state the next update's prediction starts from).  _get_prior_bw: [B][4] (the first P of a row are the environment's).
+ * dust_mpf_batch_stats: out[0] kernel launches made for the filter side so far, out[1] calls (updates and dual ticks).
+ * dust_mpf_batch_optimize = B x dust_mpf_optimize(action[b], new_obs[b], bw, n_steps) in one launch - plus one for Silverman's rule of
+ *   every environment's particles when bw <= 0 (the bandwidths stay in device memory), plus one for the heading / angle terms of a
+ *   skid-steer / cart-pole filter.  active [B] bytes or NULL: an environment with active[b] = 0 keeps everything, and its rows of
+ *   bw_used [B] and grad_norms [B][n_steps] (each may be NULL) are not written. */
+typedef struct dust_mpf_batch dust_mpf_batch;
+int dust_mpf_batch_create(const dust_mpf *proto, int n_env, dust_mpf_batch **out);
+void dust_mpf_batch_destroy(dust_mpf_batch *batch);
+int dust_mpf_batch_clone(const dust_mpf_batch *batch, dust_mpf_batch **out);
+int dust_mpf_batch_set_particles(dust_mpf_batch *batch, const float *x);
+int dust_mpf_batch_get_particles(dust_mpf_batch *batch, float *x);
+int dust_mpf_batch_set_obs(dust_mpf_batch *batch, const float *obs);
+int dust_mpf_batch_get_prior_bw(dust_mpf_batch *batch, float *bw);
+int dust_mpf_batch_stats(dust_mpf_batch *batch, long long out[2]);
+int dust_mpf_batch_optimize(dust_mpf_batch *batch, const float *actions, const float *new_obs, float bw, int n_steps, const unsigned char *active,
+                            float *bw_used, float *grad_norms);
+/* One control period of the dual loop for B environments in one call = B x dust_amppi_dual_tick, on the AMPPI batch's stream in launch
+ * order with no event, no synchronisation and no host round trip between the filters and the ticks; the number of kernel launches does
+ * not depend on B.  states [B][ds]; actions_prev [B][da] or NULL (no filter update: the first period); actions [B][S][H][da] or NULL
+ * (drawn on the device); mpf_bw <= 0: Silverman's rule per environment on the device; prior_seeds [B]: the Philox key of every
+ * environment's draws (unused by sigma points).  Parameters as dust_amppi_dual_tick: "extended" drawn inside the tick's kernel
+ * (amppi_prior_batch_kernel), DUST_AMPPI_PARAMS_SHARED and sigma points staged for all B by one launch.  Outputs, each may be NULL:
+ * costs / omega [B][S], a_seq [B][H][da] after the update and before the roll, params_out [B][rows][P], bw_used [B] (0: no update).
+ * An environment with active[b] = 0 keeps its particles, optimiser state, bandwidths, sequence and stream position; its output rows are
+ * not written.  With every output NULL the call returns without waiting for the device.  Refused before any launch: what
+ * dust_amppi_dual_tick and dust_amppi_batch_update refuse, batches of different n_env or on different devices. */
+int dust_amppi_dual_batch_tick(dust_amppi_batch *batch, dust_mpf_batch *mpf, const float *states, const float *actions_prev, const float *actions,
+                               int flags, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds, int roll_steps, const unsigned char *active,
+                               float *costs, float *omega, float *a_seq, float *params_out, float *bw_used);
 
 #ifdef __cplusplus
 }
