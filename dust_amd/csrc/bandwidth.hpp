@@ -123,6 +123,7 @@ __device__ __forceinline__ float k2_sorted_bandwidth(const K2Args &a, const int 
   // answer is the (Wc - Clo)-th smallest of the Chi - Clo pair distances in between (Wc: the rank in pairs - count(v) = N + 2 C(v))
   const unsigned Wc = (unsigned)((want - (unsigned long long)N + 1ull) / 2ull);
   unsigned Clo = 0u, Chi = (unsigned)(((unsigned long long)N * (N - 1)) / 2ull);
+  if (Wc == 0u) hi = 0u;  // two particles: the rank falls on the diagonal's zeros - no pair is wanted and the bracket's invariant Clo < Wc cannot hold
   // Warm start (round 3): between two SVGD iterations the particles move by lr * phi, so the median moves by a fraction of a
   // percent.  a.h[c] still holds the previous bandwidth: two probes at v_prev (1 -+ 2^-7) - if they bracket the rank, the bisection
   // starts from 2^17 bit patterns instead of 2^31 (17 rounds instead of 31; the median moves 0.2-0.8 % per iteration at cfg2: +-2^-9 misses too often, +-2^-5 costs two more rounds); if
@@ -502,6 +503,7 @@ __device__ __forceinline__ void k2_bandwidth256(const K2Args &a, const int c, fl
   };
   const unsigned Wc = (unsigned)((want - (unsigned long long)N + 1ull) / 2ull);
   unsigned Clo = 0u, Chi = (unsigned)(((unsigned long long)N * (N - 1)) / 2ull);
+  if (Wc == 0u) hi = 0u;  // two particles: the answer is one of the diagonal's zeros (see k2_sorted_bandwidth)
   {  // warm start from the previous bandwidth (see k2_sorted_bandwidth)
     const float hp = a.h_prev[c];
     const float vp = hp > a.min_bw && a.bw_scale > 0.f ? (hp / a.bw_scale) * a.log_n1 : 0.f;
@@ -705,6 +707,7 @@ __global__ __launch_bounds__(1024) void k2_bandwidth_sorted_big_kernel(const K2A
 }
 
 // K2_SHARED: one workgroup per timestep, O(N^2) count per bisection step
+enum { K2_PAIRS_STATIC_LDS = 16 * 8 + 32 * 4 };  // red64 + redf below, beside the da * N floats of dynamic LDS (launch_k2_bandwidth)
 __global__ __launch_bounds__(1024) void k2_bandwidth_pairs_kernel(const K2Args a) {
   extern __shared__ __attribute__((aligned(16))) float xs[];  // [da][N]
   __shared__ unsigned long long red64[16];
@@ -992,7 +995,11 @@ static inline int launch_k2_bandwidth(hipStream_t stream, const K2Args &a) {
     return hipGetLastError() != hipSuccess ? DUST_ERR_HIP : DUST_OK;
   }
   if (a.shared) {
-    k2_bandwidth_pairs_kernel<<<G, 1024, (size_t)a.da * a.N * sizeof(float), stream>>>(a);
+    // the group's coordinates live in dynamic LDS beside the kernel's static reduction slots, and nobody raises the function's limit:
+    // beyond 64 KB (d_a = 2: above ~ 8 160 particles) the shape is refused here, before any launch
+    const size_t lds = (size_t)a.da * a.N * sizeof(float);
+    if (lds + K2_PAIRS_STATIC_LDS > 64 * 1024) return DUST_ERR_UNSUPPORTED;
+    k2_bandwidth_pairs_kernel<<<G, 1024, lds, stream>>>(a);
   } else {
     int np = 1;
     while (np < a.N) np <<= 1;

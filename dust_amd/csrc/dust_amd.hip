@@ -3357,7 +3357,11 @@ static int launch_stein_update(dust_ctx *c, int apply, bool in_loop = false /* K
       const bool rows = inline_bw && apply && c->nloc == c->N && !c->theta_pinned && c->theta_alt && !k.shared;
       if (!inline_bw) {  // (else: the bandwidths of this theta were computed beside the rollouts, in their launch)
         if (!(in_loop && c->k2_thetaT_fresh)) TRY(launch_transpose(c, c->theta, c->thetaT, c->N, c->D));  // (fresh: the last update launch wrote it)
-        TRY(launch_k2_bandwidth(c->stream, k));
+        const int sb = launch_k2_bandwidth(c->stream, k);
+        if (sb == DUST_ERR_UNSUPPORTED && c->da <= 2)
+          return fail(DUST_ERR_UNSUPPORTED, "K2 bandwidths of %d particles with d_a = %d: the median pass of the shared kernel keeps a group's coordinates in 64 KB of LDS "
+                                            "(dust_set_k2_bandwidth with a fixed bandwidth needs no median pass)", c->N, c->da);
+        TRY(sb);
       } else if (!rows) {
         if (!(in_loop && c->k2_thetaT_fresh)) TRY(launch_transpose(c, c->theta, c->thetaT, c->N, c->D));
       }

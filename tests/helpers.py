@@ -25,6 +25,17 @@ def elemerr(a, b, floor=None):
     return float((np.abs(a - b) / (np.abs(b) + floor + 1e-300)).max())
 
 
+def k2_tolerance(theta, h, shared, da):
+    """K2's reference side (dust/kernels/base_kernels.py:53-89) forms (x_i - x_j)^2 as -2XY + XX + YY in fp32: cancellation noise
+    ~ 4 eps x^2 on every pair distance, i.e. that much over h RELATIVE noise on the kernel values.  The oracle follows the
+    reference's formula (and meets 1e-5); the HIP kernel uses exact differences and can only agree to that bound."""
+    x = np.asarray(theta, np.float64).reshape(theta.shape[0], -1)
+    x2 = (x * x).max(0)  # per flattened dimension
+    if shared:
+        x2 = x2.reshape(-1, da).sum(1)
+    return max(1e-5, 4 * 6e-8 * float((x2 / np.asarray(h, np.float64)).max()))
+
+
 def scenario_kwargs(g):
     """Oracle/ctx constructor kwargs for a golden SVMPC scenario (tests/golden/make_golden.py:run_svmpc)."""
     kind = str(g["model_kind"])

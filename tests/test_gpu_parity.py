@@ -9,7 +9,7 @@ import pytest
 
 import os
 
-from helpers import feed_ctrl_noise, tick2_ticks_expected, elemerr, is_adam, relerr, scenario_kwargs
+from helpers import feed_ctrl_noise, tick2_ticks_expected, elemerr, is_adam, k2_tolerance, relerr, scenario_kwargs
 from test_oracle_golden import K1_F64_CASES, SVMPC_CASES, _prior_at, k1_tolerance
 
 pytestmark = pytest.mark.gpu
@@ -31,17 +31,6 @@ def ctx_kwargs(g):
     if "k2_minimum_bw" in g:
         kw["k2_minimum_bw"] = float(g["k2_minimum_bw"])  # RBF(minimum_bw=): the clamp of the median-trick bandwidths
     return kw
-
-
-def k2_tolerance(theta, h, shared, da):
-    """K2's reference side (dust/kernels/base_kernels.py:53-89) forms (x_i - x_j)^2 as -2XY + XX + YY in fp32: cancellation noise
-    ~ 4 eps x^2 on every pair distance, i.e. that much over h RELATIVE noise on the kernel values.  The oracle follows the
-    reference's formula (and meets 1e-5); the HIP kernel uses exact differences and can only agree to that bound."""
-    x = np.asarray(theta, np.float64).reshape(theta.shape[0], -1)
-    x2 = (x * x).max(0)  # per flattened dimension
-    if shared:
-        x2 = x2.reshape(-1, da).sum(1)
-    return max(TOL, 4 * 6e-8 * float((x2 / np.asarray(h, np.float64)).max()))
 
 
 def make_ctx(g, name=""):
@@ -617,11 +606,13 @@ def _synthetic_case(model, N, S, M, H, seed=3):
 
 
 @pytest.mark.parametrize("model,N,S,M,H,kernel", [("pendulum", 256, 64, 1, 12, "K1"), ("particle", 128, 64, 4, 40, "K1"),
-                                                  ("particle", 96, 32, 1, 40, "IMQ"), ("pendulum", 128, 64, 1, 10, "K2")])
+                                                  ("particle", 96, 32, 1, 40, "IMQ"), ("pendulum", 128, 64, 1, 10, "K2"),
+                                                  ("particle", 130, 32, 1, 3, "K2shared"), ("particle", 132, 32, 1, 3, "K2shared")])
 def test_sharded_ticks_equal_unsharded_synthetic(model, N, S, M, H, kernel):
     """Particle sharding on ONE GPU (2 and 4 sharded contexts in one process, all-gathers as slice copies) beyond the Pendulum
     golden: Particle with D = H * da = 80 (the cfg4 shape), the IMQ kernel, and K2, whose per-dimension median bandwidths are
-    GLOBAL order statistics over every rank's particles."""
+    GLOBAL order statistics over every rank's particles.  K2shared on Particle (k2_phi_kernel<2>, a non-zero i0) with ragged
+    shards: 130 = 2 x 65 (a second 64-query tile with one query; shards are equal, so world 2 only), 132 = 2 x 66 = 4 x 33."""
     from dust_amd import Context
     from dust_amd.parallel import DeviceShard, LocalComm, tick
 
@@ -636,7 +627,7 @@ def test_sharded_ticks_equal_unsharded_synthetic(model, N, S, M, H, kernel):
     for t in range(T):
         outs.append(ref.svmpc_tick(state, K, eps[t], None if params is None else params[t]))
     rt = ref.get_theta()
-    for world in (2, 4):
+    for world in (w for w in (2, 4) if N % w == 0):
         shards = tuple(DeviceShard(dict(kw, grid=grid), r, world) for r in range(world))
         for sh in shards:
             sh.set_state(th, mu, th)
