@@ -11,6 +11,7 @@
 #include <new>
 #include <random>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include <atomic>
 #include <chrono>
@@ -1360,6 +1361,59 @@ static void amppi_shared_args(const dust_ctx *c, dust::AmppiArgs &a) {
   a.mw = c->mw_dev;
 }
 
+// The tick's kernels come in two families of four, lone and batched (amppi.hpp); amppi_launch chooses within the family it is given
+struct AmppiLone {
+  using Args = AmppiArgs;
+  using Prior = AmppiPrior;
+  using NavArgs = AmppiNavArgs;
+  using PriorArgs = AmppiPriorArgs;
+  using NavPriorArgs = AmppiNavPriorArgs;
+  template <int MODEL>
+  static constexpr auto plain = amppi_kernel<MODEL>;
+  template <int MODEL>
+  static constexpr auto prior = amppi_prior_kernel<MODEL>;
+  static constexpr auto nav = amppi_skid_nav_kernel;
+  static constexpr auto nav_prior = amppi_skid_nav_prior_kernel;
+};
+struct AmppiBatched {
+  using Args = AmppiBatchArgs;
+  using Prior = AmppiPriorBatch;
+  using NavArgs = AmppiNavBatchArgs;
+  using PriorArgs = AmppiPriorBatchArgs;
+  using NavPriorArgs = AmppiNavPriorBatchArgs;
+  template <int MODEL>
+  static constexpr auto plain = amppi_batch_kernel<MODEL>;
+  template <int MODEL>
+  static constexpr auto prior = amppi_prior_batch_kernel<MODEL>;
+  static constexpr auto nav = amppi_skid_nav_batch_kernel;
+  static constexpr auto nav_prior = amppi_skid_nav_prior_batch_kernel;
+};
+
+// The tick's launch: its tickets zeroed, then navigation cost or not x in-kernel prior draws or not x model, all on the context's stream
+template <class F>
+static int amppi_launch(dust_ctx *c, const dim3 grid, const typename F::Args &k, const typename F::Prior *prior, unsigned int *tickets, size_t n_tickets) {
+  const bool nav = c->cfg.model == DUST_MODEL_SKID_STEER && c->skid_w_obs != 0.f;
+  SkidNav nv;
+  if (nav) TRY(skid_nav_args(c, nv));
+  HIP_TRY(hipMemsetAsync(tickets, 0, n_tickets * sizeof(unsigned int), c->stream));
+  Prof pr(c, DUST_K_AMPPI);
+  const size_t map_lds = nav ? (size_t)nv.grid_words * sizeof(uint32_t) : 0;
+  auto model = [&](auto M) {
+    if (prior) F::template prior<M()><<<grid, AMPPI_THREADS, 0, c->stream>>>(typename F::PriorArgs{k, *prior});
+    else F::template plain<M()><<<grid, AMPPI_THREADS, 0, c->stream>>>(k);
+  };
+  if (nav && prior) F::nav_prior<<<grid, AMPPI_THREADS, map_lds, c->stream>>>(typename F::NavPriorArgs{k, nv, *prior});
+  else if (nav) F::nav<<<grid, AMPPI_THREADS, map_lds, c->stream>>>(typename F::NavArgs{k, nv});
+  else switch (c->cfg.model) {
+    case DUST_MODEL_PENDULUM: model(std::integral_constant<int, DUST_MODEL_PENDULUM>()); break;
+    case DUST_MODEL_PARTICLE: model(std::integral_constant<int, DUST_MODEL_PARTICLE>()); break;
+    case DUST_MODEL_SKID_STEER: model(std::integral_constant<int, DUST_MODEL_SKID_STEER>()); break;
+    default: model(std::integral_constant<int, DUST_MODEL_CARTPOLE>()); break;
+  }
+  HIP_TRY(hipGetLastError());
+  return DUST_OK;
+}
+
 // dust_amppi_update's body.  dust_amppi_dual_tick (mpf.hpp) enters with `staged` (the parameter rows already sit in params_dev, written
 // there on the context's stream: `params` is then only "there are rows") or with `prior` (the lanes draw their rows themselves from the
 // filter's prior, "extended": no parameter buffer at all; prior->params_out, when set, has room for [S][P])
@@ -1401,45 +1455,7 @@ static int amppi_update_impl(dust_ctx *c, const float *state, const float *actio
   a.omega = c->omegaT;
   a.states_out = want_states ? c->states : nullptr;
   a.ticket = c->amppi_ticket;
-  const int grid = (S + AMPPI_THREADS - 1) / AMPPI_THREADS;
-  const bool nav = c->cfg.model == DUST_MODEL_SKID_STEER && c->skid_w_obs != 0.f;
-  AmppiNavArgs kn;
-  if (nav) {
-    kn.a = a;
-    TRY(skid_nav_args(c, kn.nav));
-  }
-  HIP_TRY(hipMemsetAsync(c->amppi_ticket, 0, sizeof(unsigned int), c->stream));
-  if (prior) {
-    Prof pr(c, DUST_K_AMPPI);
-    if (nav) {
-      AmppiNavPriorArgs kp;
-      kp.a = a;
-      kp.nav = kn.nav;
-      kp.pr = *prior;
-      amppi_skid_nav_prior_kernel<<<grid, AMPPI_THREADS, (size_t)kn.nav.grid_words * sizeof(uint32_t), c->stream>>>(kp);
-    } else {
-      AmppiPriorArgs kp;
-      kp.a = a;
-      kp.pr = *prior;
-      switch (c->cfg.model) {
-        case DUST_MODEL_PENDULUM: amppi_prior_kernel<DUST_MODEL_PENDULUM><<<grid, AMPPI_THREADS, 0, c->stream>>>(kp); break;
-        case DUST_MODEL_PARTICLE: amppi_prior_kernel<DUST_MODEL_PARTICLE><<<grid, AMPPI_THREADS, 0, c->stream>>>(kp); break;
-        case DUST_MODEL_SKID_STEER: amppi_prior_kernel<DUST_MODEL_SKID_STEER><<<grid, AMPPI_THREADS, 0, c->stream>>>(kp); break;
-        default: amppi_prior_kernel<DUST_MODEL_CARTPOLE><<<grid, AMPPI_THREADS, 0, c->stream>>>(kp); break;
-      }
-    }
-    HIP_TRY(hipGetLastError());
-  } else {
-    Prof pr(c, DUST_K_AMPPI);
-    if (nav) amppi_skid_nav_kernel<<<grid, AMPPI_THREADS, (size_t)kn.nav.grid_words * sizeof(uint32_t), c->stream>>>(kn);
-    else switch (c->cfg.model) {
-      case DUST_MODEL_PENDULUM: amppi_kernel<DUST_MODEL_PENDULUM><<<grid, AMPPI_THREADS, 0, c->stream>>>(a); break;
-      case DUST_MODEL_PARTICLE: amppi_kernel<DUST_MODEL_PARTICLE><<<grid, AMPPI_THREADS, 0, c->stream>>>(a); break;
-      case DUST_MODEL_SKID_STEER: amppi_kernel<DUST_MODEL_SKID_STEER><<<grid, AMPPI_THREADS, 0, c->stream>>>(a); break;
-      default: amppi_kernel<DUST_MODEL_CARTPOLE><<<grid, AMPPI_THREADS, 0, c->stream>>>(a); break;
-    }
-    HIP_TRY(hipGetLastError());
-  }
+  TRY(amppi_launch<AmppiLone>(c, dim3((unsigned)((S + AMPPI_THREADS - 1) / AMPPI_THREADS)), a, prior, c->amppi_ticket, 1));
   c->have_sample = true;
   c->actions_valid = true;
   c->actions_f16 = false;
@@ -1468,6 +1484,59 @@ extern "C" int dust_amppi_roll(dust_ctx *c, int steps) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// What the batches (dust_amppi_batch here, dust_mpf_batch in mpf.hpp) share.
+// Per-call inputs of a batch travel through pinned host memory - the call does not wait for its own copy.  Two slots, each with the event
+// behind its copy: a slot is written again only once that copy has run
+struct PinnedStage {
+  unsigned char *dev, *host[2];
+  hipEvent_t ev[2];
+  int slot;
+  int alloc(size_t bytes) {
+    TRY(dalloc(&dev, bytes));
+    for (int k = 0; k < 2; ++k) {
+      HIP_TRY(hipHostMalloc((void **)&host[k], bytes, hipHostMallocDefault));
+      HIP_TRY(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
+    }
+    return DUST_OK;
+  }
+  void free() {
+    if (dev) (void)hipFree(dev);
+    for (int k = 0; k < 2; ++k) {
+      if (host[k]) (void)hipHostFree(host[k]);
+      if (ev[k]) (void)hipEventDestroy(ev[k]);
+    }
+  }
+  // the next slot's host bytes, once the copy out of them two calls ago has run (an event never recorded is complete)
+  int next(unsigned char **hb) {
+    slot ^= 1;
+    HIP_TRY(hipEventSynchronize(ev[slot]));
+    *hb = host[slot];
+    return DUST_OK;
+  }
+  // bytes [from, to) of the slot next() handed out -> dev on `stream`, and the slot's event behind them (also when there is nothing to copy)
+  int send(size_t from, size_t to, hipStream_t stream) {
+    if (to > from) HIP_TRY(hipMemcpyAsync(dev + from, host[slot] + from, to - from, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(ev[slot], stream));
+    return DUST_OK;
+  }
+};
+
+// rows of `row` floats per environment, device -> host on `stream`, for the environments of `active` (nullptr: all): one copy per run of them
+static int rows_d2h(int B, hipStream_t stream, float *dst, const float *src, size_t row, const unsigned char *active) {
+  for (int e = 0; e < B;) {
+    if (active && !active[e]) {
+      ++e;
+      continue;
+    }
+    int f = e + 1;
+    while (f < B && (!active || active[f])) ++f;
+    HIP_TRY(hipMemcpyAsync(dst + (size_t)e * row, src + (size_t)e * row, (size_t)(f - e) * row * sizeof(float), hipMemcpyDeviceToHost, stream));
+    e = f;
+  }
+  return DUST_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // AMPPI over a batch of plants: B independent ticks in one launch (amppi.hpp amppi_batch_kernel).  The batch owns a private clone of
 // the prototype context - model, cost, map, sigma weights, stream, profile counters - and the per-environment device rows.
 struct dust_amppi_batch {
@@ -1481,17 +1550,16 @@ struct dust_amppi_batch {
   uint32_t *ctr;          // [B][4]: every environment's Philox stream position {tick, iter, .., ..}
   uint64_t *seeds;        // [B]
   unsigned int *ticket;   // [B]
-  // per-call inputs travel through pinned host memory - the call does not wait for its own copy.  Two slots, each with the event behind
-  // its copy: a slot is written again only once that copy has run
-  float *in_dev;          // [B][8] states, then [B] bytes of the active mask
-  float *in_host[2];
-  hipEvent_t in_ev[2];
-  int in_slot;
+  PinnedStage in;         // per-call inputs: [B][8] states, then [B] bytes of the active mask
   std::vector<unsigned char> last_active;  // the mask of the last tick (dust_amppi_batch_get_actions writes the rows of that tick's environments)
   bool acts_valid;
 };
 
 static size_t batch_in_bytes(int B) { return (size_t)B * 8 * sizeof(float) + (size_t)B; }
+// where the kernels find the mask a call has staged (nullptr: the call had none - everybody is active)
+static const unsigned char *batch_mask_dev(const dust_amppi_batch *b, const unsigned char *active) {
+  return active ? b->in.dev + (size_t)b->B * 8 * sizeof(float) : nullptr;
+}
 
 static void batch_free(dust_amppi_batch *b) {
   if (!b) return;
@@ -1499,13 +1567,10 @@ static void batch_free(dust_amppi_batch *b) {
     (void)hipSetDevice(b->c->cfg.device);
     (void)hipStreamSynchronize(b->c->stream);
   }
-  void *dev[] = {b->a_seq, b->acts, b->costs, b->omega, b->params, b->ctr, b->seeds, b->ticket, b->in_dev};
+  void *dev[] = {b->a_seq, b->acts, b->costs, b->omega, b->params, b->ctr, b->seeds, b->ticket};
   for (void *p : dev)
     if (p) (void)hipFree(p);
-  for (int k = 0; k < 2; ++k) {
-    if (b->in_host[k]) (void)hipHostFree(b->in_host[k]);
-    if (b->in_ev[k]) (void)hipEventDestroy(b->in_ev[k]);
-  }
+  b->in.free();
   if (b->c) dust_destroy(b->c);
   delete b;
 }
@@ -1525,12 +1590,7 @@ static int batch_alloc(dust_ctx *inner, int n_env, dust_amppi_batch **out) {
   TRY(dalloc(&b->ctr, B * 4));
   TRY(dalloc(&b->seeds, B));
   TRY(dalloc(&b->ticket, B));
-  TRY(dalloc(&b->in_dev, (batch_in_bytes(n_env) + 3) / 4));
-  for (int k = 0; k < 2; ++k) {
-    HIP_TRY(hipHostMalloc((void **)&b->in_host[k], batch_in_bytes(n_env), hipHostMallocDefault));
-    HIP_TRY(hipEventCreateWithFlags(&b->in_ev[k], hipEventDisableTiming));
-  }
-  return DUST_OK;
+  return b->in.alloc(batch_in_bytes(n_env));
 }
 
 static int batch_null(const dust_amppi_batch *b) { return b ? DUST_OK : fail(DUST_ERR_INVALID, "null batch"); }
@@ -1612,39 +1672,28 @@ extern "C" int dust_amppi_batch_get_a_seq(dust_amppi_batch *b, float *a_seq) {
   return d2h(b->c, a_seq, b->a_seq, (size_t)b->B * b->c->D * sizeof(float));
 }
 
-// states [B][ds] and / or the active mask [B] -> in_dev through the next pinned slot, on the context's stream; nobody waits
+// states [B][ds] and / or the active mask [B] -> b->in.dev through the next pinned slot, on the context's stream; nobody waits
 static int batch_stage_inputs(dust_amppi_batch *b, const float *states, const unsigned char *active) {
-  dust_ctx *c = b->c;
-  const int slot = b->in_slot;
-  b->in_slot ^= 1;
-  HIP_TRY(hipEventSynchronize(b->in_ev[slot]));  // (the copy out of this slot two calls ago; an event never recorded is complete)
+  const dust_ctx *c = b->c;
+  unsigned char *hb;
+  TRY(b->in.next(&hb));
   const size_t sbytes = (size_t)b->B * 8 * sizeof(float);
-  unsigned char *hb = reinterpret_cast<unsigned char *>(b->in_host[slot]);
-  unsigned char *db = reinterpret_cast<unsigned char *>(b->in_dev);
   if (states) {
-    float *hs = b->in_host[slot];
+    float *hs = reinterpret_cast<float *>(hb);
     for (int e = 0; e < b->B; ++e)
       for (int k = 0; k < 8; ++k) hs[(size_t)e * 8 + k] = k < c->ds ? states[(size_t)e * c->ds + k] : 0.f;
   }
   if (active) memcpy(hb + sbytes, active, (size_t)b->B);
-  const size_t from = states ? 0 : sbytes, to = active ? sbytes + (size_t)b->B : sbytes;
-  if (to > from) HIP_TRY(hipMemcpyAsync(db + from, hb + from, to - from, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipEventRecord(b->in_ev[slot], c->stream));
-  return DUST_OK;
+  return b->in.send(states ? 0 : sbytes, active ? sbytes + (size_t)b->B : sbytes, c->stream);
 }
 
-// rows of `row` floats per environment, device -> host, for the environments of `active` (nullptr: all): one copy per run of them
-static int batch_rows_d2h(dust_amppi_batch *b, float *dst, const float *src, size_t row, const unsigned char *active) {
-  for (int e = 0; e < b->B;) {
-    if (active && !active[e]) {
-      ++e;
-      continue;
-    }
-    int f = e + 1;
-    while (f < b->B && (!active || active[f])) ++f;
-    HIP_TRY(hipMemcpyAsync(dst + (size_t)e * row, src + (size_t)e * row, (size_t)(f - e) * row * sizeof(float), hipMemcpyDeviceToHost, b->c->stream));
-    e = f;
-  }
+// amppi_batch_roll_kernel over the environments of the mask the call has staged (`active`: whether it had one)
+static int batch_roll_launch(dust_amppi_batch *b, int steps, const unsigned char *active) {
+  dust_ctx *c = b->c;
+  const long shift = (long)steps * c->da;
+  Prof pr(c, DUST_K_FORWARD);
+  amppi_batch_roll_kernel<<<b->B, 128, 0, c->stream>>>(b->a_seq, c->D, shift > c->D ? c->D : (int)shift, batch_mask_dev(b, active));
+  HIP_TRY(hipGetLastError());
   return DUST_OK;
 }
 
@@ -1676,8 +1725,7 @@ static int batch_update_launch(dust_amppi_batch *b, const float *states, const f
     if (!staged) TRY(h2d(c, b->params, params, B * prows * P * sizeof(float)));
   }
   TRY(batch_stage_inputs(b, states, active));
-  AmppiNavBatchArgs kn;
-  AmppiBatchArgs &k = kn.k;
+  AmppiBatchArgs k;
   amppi_shared_args(c, k.a);
   k.a.pts = pts;
   k.a.mode = mode;
@@ -1689,45 +1737,11 @@ static int batch_update_launch(dust_amppi_batch *b, const float *states, const f
   k.a.costs = b->costs;
   k.a.omega = b->omega;
   k.a.ticket = b->ticket;
-  k.states = b->in_dev;
+  k.states = reinterpret_cast<const float *>(b->in.dev);
   k.seeds = b->seeds;
-  k.active = active ? reinterpret_cast<const unsigned char *>(b->in_dev) + B * 8 * sizeof(float) : nullptr;
+  k.active = batch_mask_dev(b, active);
   k.prow_stride = (int)(prows * P);
-  const dim3 grid((unsigned)((S + AMPPI_THREADS - 1) / AMPPI_THREADS), (unsigned)B);
-  const bool nav = c->cfg.model == DUST_MODEL_SKID_STEER && c->skid_w_obs != 0.f;
-  if (nav) TRY(skid_nav_args(c, kn.nav));
-  HIP_TRY(hipMemsetAsync(b->ticket, 0, B * sizeof(unsigned int), c->stream));
-  if (prior) {
-    Prof pr(c, DUST_K_AMPPI);
-    if (nav) {
-      AmppiNavPriorBatchArgs kp;
-      kp.k = k;
-      kp.nav = kn.nav;
-      kp.pr = *prior;
-      amppi_skid_nav_prior_batch_kernel<<<grid, AMPPI_THREADS, (size_t)kn.nav.grid_words * sizeof(uint32_t), c->stream>>>(kp);
-    } else {
-      AmppiPriorBatchArgs kp;
-      kp.k = k;
-      kp.pr = *prior;
-      switch (c->cfg.model) {
-        case DUST_MODEL_PENDULUM: amppi_prior_batch_kernel<DUST_MODEL_PENDULUM><<<grid, AMPPI_THREADS, 0, c->stream>>>(kp); break;
-        case DUST_MODEL_PARTICLE: amppi_prior_batch_kernel<DUST_MODEL_PARTICLE><<<grid, AMPPI_THREADS, 0, c->stream>>>(kp); break;
-        case DUST_MODEL_SKID_STEER: amppi_prior_batch_kernel<DUST_MODEL_SKID_STEER><<<grid, AMPPI_THREADS, 0, c->stream>>>(kp); break;
-        default: amppi_prior_batch_kernel<DUST_MODEL_CARTPOLE><<<grid, AMPPI_THREADS, 0, c->stream>>>(kp); break;
-      }
-    }
-    HIP_TRY(hipGetLastError());
-  } else {
-    Prof pr(c, DUST_K_AMPPI);
-    if (nav) amppi_skid_nav_batch_kernel<<<grid, AMPPI_THREADS, (size_t)kn.nav.grid_words * sizeof(uint32_t), c->stream>>>(kn);
-    else switch (c->cfg.model) {
-      case DUST_MODEL_PENDULUM: amppi_batch_kernel<DUST_MODEL_PENDULUM><<<grid, AMPPI_THREADS, 0, c->stream>>>(k); break;
-      case DUST_MODEL_PARTICLE: amppi_batch_kernel<DUST_MODEL_PARTICLE><<<grid, AMPPI_THREADS, 0, c->stream>>>(k); break;
-      case DUST_MODEL_SKID_STEER: amppi_batch_kernel<DUST_MODEL_SKID_STEER><<<grid, AMPPI_THREADS, 0, c->stream>>>(k); break;
-      default: amppi_batch_kernel<DUST_MODEL_CARTPOLE><<<grid, AMPPI_THREADS, 0, c->stream>>>(k); break;
-    }
-    HIP_TRY(hipGetLastError());
-  }
+  TRY(amppi_launch<AmppiBatched>(c, dim3((unsigned)((S + AMPPI_THREADS - 1) / AMPPI_THREADS), (unsigned)B), k, prior, b->ticket, B));
   b->acts_valid = true;
   if (active) b->last_active.assign(active, active + B);
   else b->last_active.clear();
@@ -1740,9 +1754,9 @@ extern "C" int dust_amppi_batch_update(dust_amppi_batch *b, const float *states,
   dust_ctx *c = b->c;
   const size_t S = (size_t)c->S, D = (size_t)c->D;
   if (!costs && !omega && !a_seq) return DUST_OK;
-  if (costs) TRY(batch_rows_d2h(b, costs, b->costs, S, active));
-  if (omega) TRY(batch_rows_d2h(b, omega, b->omega, S, active));
-  if (a_seq) TRY(batch_rows_d2h(b, a_seq, b->a_seq, D, active));
+  if (costs) TRY(rows_d2h(b->B, c->stream, costs, b->costs, S, active));
+  if (omega) TRY(rows_d2h(b->B, c->stream, omega, b->omega, S, active));
+  if (a_seq) TRY(rows_d2h(b->B, c->stream, a_seq, b->a_seq, D, active));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return DUST_OK;
 }
@@ -1753,21 +1767,14 @@ extern "C" int dust_amppi_batch_roll(dust_amppi_batch *b, int steps, const unsig
   dust_ctx *c = b->c;
   HIP_TRY(hipSetDevice(c->cfg.device));
   if (active) TRY(batch_stage_inputs(b, nullptr, active));
-  const unsigned char *mask = active ? reinterpret_cast<const unsigned char *>(b->in_dev) + (size_t)b->B * 8 * sizeof(float) : nullptr;
-  const long shift = (long)steps * c->da;
-  {
-    Prof pr(c, DUST_K_FORWARD);
-    amppi_batch_roll_kernel<<<b->B, 128, 0, c->stream>>>(b->a_seq, c->D, shift > c->D ? c->D : (int)shift, mask);
-    HIP_TRY(hipGetLastError());
-  }
-  return DUST_OK;
+  return batch_roll_launch(b, steps, active);
 }
 
 extern "C" int dust_amppi_batch_get_actions(dust_amppi_batch *b, float *actions) {
   if (!b || !actions) return fail(DUST_ERR_INVALID, "null argument");
   if (!b->acts_valid) return fail(DUST_ERR_STATE, "no batched tick has run yet: there are no actions");
   HIP_TRY(hipSetDevice(b->c->cfg.device));
-  TRY(batch_rows_d2h(b, actions, b->acts, (size_t)b->c->S * b->c->D, b->last_active.empty() ? nullptr : b->last_active.data()));
+  TRY(rows_d2h(b->B, b->c->stream, actions, b->acts, (size_t)b->c->S * b->c->D, b->last_active.empty() ? nullptr : b->last_active.data()));
   HIP_TRY(hipStreamSynchronize(b->c->stream));
   return DUST_OK;
 }

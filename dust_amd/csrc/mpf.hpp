@@ -1540,12 +1540,21 @@ static int mpf_cart_prepare(dust_mpf *m, const dust::CartLik **dev) {
   return DUST_OK;
 }
 
-static int mpf_launch(dust_mpf *m, float bw, float lr, int n_steps, float *gn_dev, float *phi_dev, bool optimise = true, bool grid = false,
-                      const float *act_seq_dev = nullptr) {
-  serve_cancel_device(m->cfg.device);  // (an armed control tick - closed-loop serving - would hold every CU until its plant state arrives)
+// The run-time P and a yes / no (cart-pole or not; the batch: log space or not) as compile-time constants: f(p, flag) with p() the P among
+// Ps and flag() the bool; false: P is none of Ps.  Ps is what the call site instantiates its kernel for.
+template <int... Ps, class F>
+static bool mpf_pick(int P, bool flag, F &&f) {
+  return ((P == Ps && ((flag ? f(std::integral_constant<int, Ps>(), std::true_type()) : f(std::integral_constant<int, Ps>(), std::false_type())), true)) || ...);
+}
+
+static int mpf_grid_ready(const dust_mpf *m) {
   if (m->cfg.model_cfg.model == DUST_MODEL_PARTICLE && m->cfg.model_cfg.with_obstacle && m->cfg.model_cfg.can_crash && !m->grid_bits)
     return fail(DUST_ERR_STATE, "Particle model with obstacles: call dust_mpf_set_grid first");
-  MpfArgs a;
+  return DUST_OK;
+}
+
+// What a lone filter's launch and a batch's share of MpfArgs: everything else zero
+static void mpf_shared_args(const dust_mpf *m, int n_steps, MpfArgs &a) {
   memset(&a, 0, sizeof a);
   a.dm = mpf_dev_model(m);
   a.Mp = m->Mp;
@@ -1554,9 +1563,35 @@ static int mpf_launch(dust_mpf *m, float bw, float lr, int n_steps, float *gn_de
   a.da = m->cfg.dim_a;
   a.n_steps = n_steps;
   a.log_space = m->cfg.log_space;
+  a.obs_std = m->cfg.obs_std;
+}
+
+// The single-workgroup form (mpf_optimize_kernel; one workgroup per environment: mpf_optimize_batch_kernel): block size, dynamic LDS, launch
+struct MpfWg {
+  int threads;
+  size_t lds;
+};
+static MpfWg mpf_wg(const dust_mpf *m) {
+  const int mpad = ((m->Mp + 63) / 64) * 64;
+  int R = 1;
+  while (mpad * R * 2 <= 1024) R *= 2;
+  return MpfWg{mpad * R, sizeof(double) * (size_t)R * mpad * 2 * m->P + sizeof(float) * ((size_t)2 * m->Mp * m->P + m->Mp + 32)};
+}
+template <class K, class Args>
+static int mpf_wg_launch(K kernel, int blocks, const MpfWg &wg, hipStream_t stream, const Args &a) {
+  if (wg.lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg.lds));
+  kernel<<<blocks, wg.threads, wg.lds, stream>>>(a);
+  return DUST_OK;
+}
+
+static int mpf_launch(dust_mpf *m, float bw, float lr, int n_steps, float *gn_dev, float *phi_dev, bool optimise = true, bool grid = false,
+                      const float *act_seq_dev = nullptr) {
+  serve_cancel_device(m->cfg.device);  // (an armed control tick - closed-loop serving - would hold every CU until its plant state arrives)
+  TRY(mpf_grid_ready(m));
+  MpfArgs a;
+  mpf_shared_args(m, n_steps, a);
   for (int p = 0; p < 4; ++p) a.prior_bwv[p] = m->prior_bwv[p];
   a.bw = bw;
-  a.obs_std = m->cfg.obs_std;
   for (int k = 0; k < 4; ++k) {
     a.past_obs[k] = m->past_obs[k];
     a.obs[k] = m->loc[k];
@@ -1606,23 +1641,11 @@ static int mpf_launch(dust_mpf *m, float bw, float lr, int n_steps, float *gn_de
     g.tag0 = g.seq * 8192u;  // (n_steps <= 4096: 2 tags per step)
     g.test = m->env.grid_test;
     const int G = (m->Mp + MPF_G_WAVES - 1) / MPF_G_WAVES;
-#define DUST_LAUNCH_MPFP2(PP, CART)                                                                    \
-  do {                                                                                                  \
-    if (m->Mp <= 256) mpf_optimize_poll_kernel<PP, 4, CART><<<G, MPF_G_NT, 0, m->stream>>>(g);          \
-    else if (m->Mp <= 512) mpf_optimize_poll_kernel<PP, 8, CART><<<G, MPF_G_NT, 0, m->stream>>>(g);     \
-    else mpf_optimize_poll_kernel<PP, 16, CART><<<G, MPF_G_NT, 0, m->stream>>>(g);                      \
-  } while (0)
-#define DUST_LAUNCH_MPFP(PP)              \
-  do {                                    \
-    if (cart) DUST_LAUNCH_MPFP2(PP, true); \
-    else DUST_LAUNCH_MPFP2(PP, false);    \
-  } while (0)
-    if (m->P == 1) DUST_LAUNCH_MPFP(1);
-    else if (m->P == 2) DUST_LAUNCH_MPFP(2);
-    else if (m->P == 3) DUST_LAUNCH_MPFP(3);
-    else DUST_LAUNCH_MPFP(4);
-#undef DUST_LAUNCH_MPFP
-#undef DUST_LAUNCH_MPFP2
+    mpf_pick<1, 2, 3, 4>(m->P, cart, [&](auto p, auto ct) {
+      if (m->Mp <= 256) mpf_optimize_poll_kernel<p(), 4, ct()><<<G, MPF_G_NT, 0, m->stream>>>(g);
+      else if (m->Mp <= 512) mpf_optimize_poll_kernel<p(), 8, ct()><<<G, MPF_G_NT, 0, m->stream>>>(g);
+      else mpf_optimize_poll_kernel<p(), 16, ct()><<<G, MPF_G_NT, 0, m->stream>>>(g);
+    });
     HIP_TRY(hipGetLastError());
     return DUST_OK;
   }
@@ -1650,39 +1673,13 @@ static int mpf_launch(dust_mpf *m, float bw, float lr, int n_steps, float *gn_de
     g.test = m->env.grid_test;
     const int G = (m->Mp + MPF_G_WAVES - 1) / MPF_G_WAVES;
     const size_t lds = sizeof(float) * ((size_t)2 * np + m->Mp + 8);
-#define DUST_LAUNCH_MPFG(PP)                                                                      \
-  do {                                                                                            \
-    if (cart) mpf_optimize_grid_kernel<PP, true><<<G, MPF_G_NT, lds, m->stream>>>(g);              \
-    else mpf_optimize_grid_kernel<PP><<<G, MPF_G_NT, lds, m->stream>>>(g);                        \
-  } while (0)
-    if (m->P == 1) DUST_LAUNCH_MPFG(1);
-    else if (m->P == 2) DUST_LAUNCH_MPFG(2);
-    else if (m->P == 3) DUST_LAUNCH_MPFG(3);
-    else DUST_LAUNCH_MPFG(4);
-#undef DUST_LAUNCH_MPFG
+    mpf_pick<1, 2, 3, 4>(m->P, cart, [&](auto p, auto ct) { mpf_optimize_grid_kernel<p(), ct()><<<G, MPF_G_NT, lds, m->stream>>>(g); });
     HIP_TRY(hipGetLastError());
     return DUST_OK;
   }
-  const int mpad = ((m->Mp + 63) / 64) * 64;
-  int R = 1;
-  while (mpad * R * 2 <= 1024) R *= 2;
-  const size_t lds = sizeof(double) * (size_t)R * mpad * 2 * m->P + sizeof(float) * ((size_t)2 * m->Mp * m->P + m->Mp + 32);
-#define DUST_LAUNCH_MPF2(PP, CART)                                                                                                 \
-  do {                                                                                                                              \
-    if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)mpf_optimize_kernel<PP, CART>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    mpf_optimize_kernel<PP, CART><<<1, mpad * R, lds, m->stream>>>(a);                                                              \
-  } while (0)
-#define DUST_LAUNCH_MPF(PP)              \
-  do {                                   \
-    if (cart) DUST_LAUNCH_MPF2(PP, true); \
-    else DUST_LAUNCH_MPF2(PP, false);    \
-  } while (0)
-  if (m->P == 1) DUST_LAUNCH_MPF(1);
-  else if (m->P == 2) DUST_LAUNCH_MPF(2);
-  else if (m->P == 3) DUST_LAUNCH_MPF(3);
-  else DUST_LAUNCH_MPF(4);
-#undef DUST_LAUNCH_MPF
-#undef DUST_LAUNCH_MPF2
+  int st = DUST_OK;
+  mpf_pick<1, 2, 3, 4>(m->P, cart, [&](auto p, auto ct) { st = mpf_wg_launch(mpf_optimize_kernel<p(), ct()>, 1, mpf_wg(m), m->stream, a); });
+  TRY(st);
   HIP_TRY(hipGetLastError());
   return DUST_OK;
 }
@@ -1889,6 +1886,43 @@ static int dual_pair_check(const dust_ctx *c, const dust_mpf *m) {
   return DUST_OK;
 }
 
+// The filter update of a period (skipped without an action: the first period) with Silverman's rule of the filter's particles on demand
+// (bw <= 0; mpf.py:68-73, on the device).  *bw_used: the bandwidth the update ran with (0: no update).
+static int dual_filter_update(dust_mpf *m, const float *action_prev, const float *state, float bw, int mpf_steps, float *bw_used) {
+  if (action_prev) {
+    if (!(bw > 0.f)) TRY(dust_mpf_silverman(m, &bw));
+    TRY(dust_mpf_optimize(m, action_prev, state, bw, mpf_steps, nullptr));  // (synchronises the filter's stream: its particles are final)
+  }
+  if (bw_used) *bw_used = action_prev ? bw : 0.f;
+  return DUST_OK;
+}
+
+// `waiter` goes on only behind what `ahead` holds now - without waiting on the host
+static int dual_stream_after(dust_ctx *c, hipStream_t waiter, hipStream_t ahead) {
+  if (!c->ev_dual) HIP_TRY(hipEventCreateWithFlags(&c->ev_dual, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(c->ev_dual, ahead));
+  HIP_TRY(hipStreamWaitEvent(waiter, c->ev_dual, 0));
+  return DUST_OK;
+}
+
+// What dust_amppi_dual_tick and dust_amppi_dual_batch_tick both refuse, ahead of any staging launch -> where the parameters come from
+static int amppi_dual_check(const dust_ctx *c, const dust_mpf *m, int flags, bool *sigma_out, bool *shared_out) {
+  if (m->cfg.log_space) return fail(DUST_ERR_UNSUPPORTED, "a log-space filter under AMPPI: the controller hands samples to the model as drawn (amppi.py:134-139)");
+  if (flags & DUST_STORE_STATES) return fail(DUST_ERR_UNSUPPORTED, "the AMPPI dual tick stores no trajectories");
+  if (flags & (DUST_EPS_F16 | DUST_STORE_F16)) return fail(DUST_ERR_UNSUPPORTED, "the AMPPI tick has no binary16 storage");
+  const bool sigma = c->mw_dev != nullptr;
+  if (sigma) {
+    if (!(c->sigma_scale > 0.f))
+      return fail(DUST_ERR_UNSUPPORTED, "the dual tick over sigma-point weights needs the transform's scale lambda + n (dust_set_sigma_scale)");
+    if (c->M != 2 * m->P + 1) return fail(DUST_ERR_INVALID, "sigma-point weights over P = %d parameters take M = 2 P + 1 = %d samples, the controller has M = %d", m->P, 2 * m->P + 1, c->M);
+  } else if (c->M != 1) {
+    return fail(DUST_ERR_INVALID, "n_params = %d > 1 is the sigma-point form of an AMPPI context: dust_set_param_weights first", c->M);
+  }
+  *sigma_out = sigma;
+  *shared_out = (flags & DUST_AMPPI_PARAMS_SHARED) != 0;
+  return DUST_OK;
+}
+
 // One control period of the DUAL loop (simulations.py:104-138) in one call: the filter update for the action just applied and the state
 // it led to (mpf.optimize(action, state, bw, n_steps): skipped when action_prev is NULL - the first period), then the controller's
 // dynamics samples drawn from the filter's refreshed prior ON THE DEVICE, straight into the controller's parameter buffer (n_steps
@@ -1910,12 +1944,7 @@ extern "C" int dust_dual_tick(dust_ctx *c, dust_mpf *m, const float *state, cons
     if (c->cfg.params_log_space) return fail(DUST_ERR_UNSUPPORTED, "sigma points of a log-space parameter distribution: the reference asserts against it (disco.py:125)");
   }
   HIP_TRY(hipSetDevice(c->cfg.device));
-  float bw = bw_in;
-  if (action_prev) {
-    if (!(bw > 0.f)) TRY(dust_mpf_silverman(m, &bw));
-    TRY(dust_mpf_optimize(m, action_prev, state, bw, mpf_steps, nullptr));  // (synchronises the filter's stream: its particles are final)
-  }
-  if (bw_used) *bw_used = action_prev ? bw : 0.f;
+  TRY(dual_filter_update(m, action_prev, state, bw_in, mpf_steps, bw_used));
   TRY(settle_pending(c));
   const int n = n_steps * c->M;
   TRY(ensure(&c->params_dev, &c->params_cap, (size_t)n * c->P));
@@ -1947,29 +1976,13 @@ extern "C" int dust_amppi_dual_tick(dust_ctx *c, dust_mpf *m, const float *state
   if (mpf_steps < 0 || roll_steps < 0) return fail(DUST_ERR_INVALID, "bad step counts");
   TRY(amppi_check(c));  // (n_policies = 1, not sharded, no params_log_space, ...)
   TRY(dual_pair_check(c, m));
-  if (m->cfg.log_space) return fail(DUST_ERR_UNSUPPORTED, "a log-space filter under AMPPI: the controller hands samples to the model as drawn (amppi.py:134-139)");
-  if (flags & DUST_STORE_STATES) return fail(DUST_ERR_UNSUPPORTED, "the AMPPI dual tick stores no trajectories");
-  if (flags & (DUST_EPS_F16 | DUST_STORE_F16)) return fail(DUST_ERR_UNSUPPORTED, "the AMPPI tick has no binary16 storage");  // (ahead of any staging launch)
-  const bool sigma = c->mw_dev != nullptr, shared = (flags & DUST_AMPPI_PARAMS_SHARED) != 0;
-  if (sigma) {
-    if (!(c->sigma_scale > 0.f))
-      return fail(DUST_ERR_UNSUPPORTED, "the dual tick over sigma-point weights needs the transform's scale lambda + n (dust_set_sigma_scale)");
-    if (c->M != 2 * m->P + 1) return fail(DUST_ERR_INVALID, "sigma-point weights over P = %d parameters take M = 2 P + 1 = %d samples, the controller has M = %d", m->P, 2 * m->P + 1, c->M);
-  } else if (c->M != 1) {
-    return fail(DUST_ERR_INVALID, "n_params = %d > 1 is the sigma-point form of an AMPPI context: dust_set_param_weights first", c->M);
-  }
+  bool sigma, shared;
+  TRY(amppi_dual_check(c, m, flags, &sigma, &shared));
   if (m->P < 1 || m->P > 4 || m->Mp > 1024) return fail(DUST_ERR_UNSUPPORTED, "the AMPPI dual tick takes a filter of up to 1024 particles over 1 .. 4 parameters");
   HIP_TRY(hipSetDevice(c->cfg.device));
-  float bw = bw_in;
-  if (action_prev) {
-    if (!(bw > 0.f)) TRY(dust_mpf_silverman(m, &bw));
-    TRY(dust_mpf_optimize(m, action_prev, state, bw, mpf_steps, nullptr));  // (synchronises the filter's stream: its particles are final)
-  } else {  // no update: whatever wrote the particles last on the filter's stream comes first - without waiting on the host
-    if (!c->ev_dual) HIP_TRY(hipEventCreateWithFlags(&c->ev_dual, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(c->ev_dual, m->stream));
-    HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_dual, 0));
-  }
-  if (bw_used) *bw_used = action_prev ? bw : 0.f;
+  TRY(dual_filter_update(m, action_prev, state, bw_in, mpf_steps, bw_used));
+  // no update: whatever wrote the particles last on the filter's stream comes first
+  if (!action_prev) TRY(dual_stream_after(c, c->stream, m->stream));
   TRY(settle_pending(c));
   const int P = m->P;
   const size_t prows = sigma ? (size_t)c->M : (shared ? (size_t)1 : (size_t)c->S);
@@ -1999,11 +2012,8 @@ extern "C" int dust_amppi_dual_tick(dust_ctx *c, dust_mpf *m, const float *state
   if (a_seq) TRY(d2h(c, a_seq, c->a_seq, (size_t)c->D * sizeof(float)));
   if (params_out) TRY(d2h(c, params_out, c->params_dev, prows * P * sizeof(float)));
   if (roll_steps > 0) TRY(dust_amppi_roll(c, roll_steps));
-  if (!copies) {  // nothing drained the controller's stream: the filter's next update waits for the kernels that read its particles
-    if (!c->ev_dual) HIP_TRY(hipEventCreateWithFlags(&c->ev_dual, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(c->ev_dual, c->stream));
-    HIP_TRY(hipStreamWaitEvent(m->stream, c->ev_dual, 0));
-  }
+  // nothing drained the controller's stream: the filter's next update waits for the kernels that read its particles
+  if (!copies) TRY(dual_stream_after(c, m->stream, c->stream));
   return DUST_OK;
 }
 
@@ -2025,10 +2035,7 @@ struct dust_mpf_batch {
   std::vector<float> loc, past_obs, past_action;  // [B][5], [B][5], [B][2]
   std::vector<unsigned char> have_past;
   std::vector<int> opt_t;
-  // per-call inputs: MpfEnvIn [B] | prior seeds [B] | SkidLik / CartLik [B] | active mask [B]; two pinned slots, each with the event behind its copy
-  unsigned char *in_dev, *in_host[2];
-  hipEvent_t in_ev[2];
-  int in_slot;
+  PinnedStage in;      // per-call inputs: MpfEnvIn [B] | prior seeds [B] | SkidLik / CartLik [B] | active mask [B]
   hipEvent_t ev_ext;   // behind the last work a dual tick put on an AMPPI batch's stream
   long long n_launch, n_calls;
 };
@@ -2041,6 +2048,9 @@ static size_t mpfb_off_seeds(int B) { return (size_t)B * sizeof(dust::MpfEnvIn);
 static size_t mpfb_off_lik(int B) { return mpfb_off_seeds(B) + (size_t)B * sizeof(uint64_t); }
 static size_t mpfb_off_mask(const dust_mpf_batch *mb) { return mpfb_off_lik(mb->B) + (size_t)mb->B * mpfb_lik_bytes(mb->m); }
 static size_t mpfb_in_bytes(const dust_mpf_batch *mb) { return mpfb_off_mask(mb) + (size_t)mb->B; }
+// where the kernels find the mask a call has staged (nullptr: the call had none - everybody is active), and the prior seeds
+static const unsigned char *mpfb_mask_dev(const dust_mpf_batch *mb, const unsigned char *active) { return active ? mb->in.dev + mpfb_off_mask(mb) : nullptr; }
+static const uint64_t *mpfb_seeds_dev(const dust_mpf_batch *mb) { return reinterpret_cast<const uint64_t *>(mb->in.dev + mpfb_off_seeds(mb->B)); }
 
 static void mpfb_free(dust_mpf_batch *mb) {
   if (!mb) return;
@@ -2049,13 +2059,10 @@ static void mpfb_free(dust_mpf_batch *mb) {
     if (mb->ev_ext) (void)hipEventSynchronize(mb->ev_ext);
     (void)hipStreamSynchronize(mb->m->stream);
   }
-  void *dev[] = {mb->x, mb->opt_s[0], mb->opt_s[1], mb->opt_s[2], mb->bw, mb->prior_bwv, mb->gn, mb->in_dev};
+  void *dev[] = {mb->x, mb->opt_s[0], mb->opt_s[1], mb->opt_s[2], mb->bw, mb->prior_bwv, mb->gn};
   for (void *p : dev)
     if (p) (void)hipFree(p);
-  for (int k = 0; k < 2; ++k) {
-    if (mb->in_host[k]) (void)hipHostFree(mb->in_host[k]);
-    if (mb->in_ev[k]) (void)hipEventDestroy(mb->in_ev[k]);
-  }
+  mb->in.free();
   if (mb->ev_ext) (void)hipEventDestroy(mb->ev_ext);
   if (mb->m) dust_mpf_destroy(mb->m);
   delete mb;
@@ -2076,11 +2083,7 @@ static int mpfb_alloc(dust_mpf *inner, int n_env, dust_mpf_batch **out) {
   TRY(dalloc(&mb->bw, B));
   TRY(dalloc(&mb->prior_bwv, B * 4));
   HIP_TRY(hipMemset(mb->bw, 0, B * sizeof(float)));
-  TRY(dalloc(&mb->in_dev, mpfb_in_bytes(mb)));
-  for (int k = 0; k < 2; ++k) {
-    HIP_TRY(hipHostMalloc((void **)&mb->in_host[k], mpfb_in_bytes(mb), hipHostMallocDefault));
-    HIP_TRY(hipEventCreateWithFlags(&mb->in_ev[k], hipEventDisableTiming));
-  }
+  TRY(mb->in.alloc(mpfb_in_bytes(mb)));
   HIP_TRY(hipEventCreateWithFlags(&mb->ev_ext, hipEventDisableTiming));
   mb->loc.assign(B * 5, 0.f);
   mb->past_obs.assign(B * 5, 0.f);
@@ -2226,9 +2229,7 @@ static int mpfb_update_check(const dust_mpf_batch *mb, const float *actions, con
   if (!new_obs)
     for (int e = 0; e < mb->B; ++e)
       if ((!active || active[e]) && !mb->have_past[e]) return fail(DUST_ERR_STATE, "Previous action is None. Need at least one observation to start sampling.");
-  if (m->cfg.model_cfg.model == DUST_MODEL_PARTICLE && m->cfg.model_cfg.with_obstacle && m->cfg.model_cfg.can_crash && !m->grid_bits)
-    return fail(DUST_ERR_STATE, "Particle model with obstacles: call dust_mpf_set_grid first");
-  return DUST_OK;
+  return mpf_grid_ready(m);
 }
 
 // The per-call inputs through the next pinned slot and - with `update` - the filter side of a period on `stream`: GaussianLikelihood.condition
@@ -2251,14 +2252,22 @@ static void mpfb_commit(dust_mpf_batch *mb, MpfbRows &w) {
   mb->opt_t.swap(w.opt_t);
 }
 
+// mpf_optimize_batch_kernel of one model, instantiated for the particle columns Ps, x log space or not x Adam or not; false: P is none of Ps
+template <int MODEL, int... Ps>
+static bool mpfb_launch(const dust_mpf *m, int B, hipStream_t stream, const MpfBatchArgs &k, int *st) {
+  constexpr bool CART = MODEL == DUST_MODEL_CARTPOLE;
+  return mpf_pick<Ps...>(m->P, m->cfg.log_space != 0, [&](auto p, auto lg) {
+    if (m->opt.kind == DUST_OPT_ADAM) *st = mpf_wg_launch(mpf_optimize_batch_kernel<p(), CART, MODEL, lg(), true>, B, mpf_wg(m), stream, k);
+    else *st = mpf_wg_launch(mpf_optimize_batch_kernel<p(), CART, MODEL, lg(), false>, B, mpf_wg(m), stream, k);
+  });
+}
+
 static int mpfb_enqueue(dust_mpf_batch *mb, hipStream_t stream, const bool update, const float *actions, const float *new_obs, const float bw,
                         const int n_steps, const unsigned char *active, const uint64_t *seeds, MpfbRows &w) {
   dust_mpf *m = mb->m;
   const int B = mb->B, ds = m->cfg.dim_s, da = m->cfg.dim_a, model = m->cfg.model_cfg.model;
-  const int slot = mb->in_slot;
-  mb->in_slot ^= 1;
-  HIP_TRY(hipEventSynchronize(mb->in_ev[slot]));  // (the copy out of this slot two calls ago; an event never recorded is complete)
-  unsigned char *hb = mb->in_host[slot];
+  unsigned char *hb;
+  TRY(mb->in.next(&hb));
   dust::MpfEnvIn *in = reinterpret_cast<dust::MpfEnvIn *>(hb);
   if (seeds) memcpy(hb + mpfb_off_seeds(B), seeds, (size_t)B * sizeof(uint64_t));
   if (active) memcpy(hb + mpfb_off_mask(mb), active, (size_t)B);
@@ -2291,21 +2300,20 @@ static int mpfb_enqueue(dust_mpf_batch *mb, hipStream_t stream, const bool updat
       if (on) w.opt_t[e] += n_steps;
     }
   }
-  const size_t from = update ? 0 : mpfb_off_seeds(B), to = active ? mpfb_in_bytes(mb) : mpfb_off_mask(mb);
-  // (without an update the likelihood rows between the seeds and the mask are not read: the copy may carry whatever the slot holds)
-  HIP_TRY(hipMemcpyAsync(mb->in_dev + from, hb + from, to - from, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipEventRecord(mb->in_ev[slot], stream));
+  // (without an update the likelihood rows between the seeds and the mask are not read: the copy may carry whatever the slot holds; the
+  // seeds lie in the range either way: there is always something to copy)
+  TRY(mb->in.send(update ? 0 : mpfb_off_seeds(B), active ? mpfb_in_bytes(mb) : mpfb_off_mask(mb), stream));
   if (!update) return DUST_OK;
   serve_cancel_device(m->cfg.device);  // (as mpf_launch: an armed control tick would hold every CU until its plant state arrives)
-  const unsigned char *mask = active ? mb->in_dev + mpfb_off_mask(mb) : nullptr;
+  const unsigned char *mask = mpfb_mask_dev(mb, active);
   const bool cart = model == DUST_MODEL_CARTPOLE;
   if (model == DUST_MODEL_SKID_STEER) {
-    dust::mpf_lik_angle_batch_kernel<dust::SkidLik><<<(B + 255) / 256, 256, 0, stream>>>(reinterpret_cast<dust::SkidLik *>(mb->in_dev + mpfb_off_lik(B)), B, mask);
+    dust::mpf_lik_angle_batch_kernel<dust::SkidLik><<<(B + 255) / 256, 256, 0, stream>>>(reinterpret_cast<dust::SkidLik *>(mb->in.dev + mpfb_off_lik(B)), B, mask);
     HIP_TRY(hipGetLastError());
     mb->n_launch++;
   }
   if (cart) {
-    dust::mpf_lik_angle_batch_kernel<dust::CartLik><<<(B + 255) / 256, 256, 0, stream>>>(reinterpret_cast<dust::CartLik *>(mb->in_dev + mpfb_off_lik(B)), B, mask);
+    dust::mpf_lik_angle_batch_kernel<dust::CartLik><<<(B + 255) / 256, 256, 0, stream>>>(reinterpret_cast<dust::CartLik *>(mb->in.dev + mpfb_off_lik(B)), B, mask);
     HIP_TRY(hipGetLastError());
     mb->n_launch++;
   }
@@ -2318,73 +2326,38 @@ static int mpfb_enqueue(dust_mpf_batch *mb, hipStream_t stream, const bool updat
   MpfBatchArgs k;
   memset(&k, 0, sizeof k);
   MpfArgs &a = k.a;
-  a.dm = mpf_dev_model(m);
-  a.Mp = m->Mp;
-  a.P = m->P;
-  a.ds = ds;
-  a.da = da;
-  a.n_steps = n_steps;
+  mpf_shared_args(m, n_steps, a);
   a.log_space = m->cfg.log_space ? 1 : 0;  // (0 / 1: the instance is told which)
   a.dm.log_space = a.log_space;
-  a.obs_std = m->cfg.obs_std;
   a.x = mb->x;
   a.grad_norms = mb->gn;
   a.opt = m->opt;
   a.opt_s0 = mb->opt_s[0];
   a.opt_s1 = mb->opt_s[1];
   a.opt_s2 = mb->opt_s[2];
-  k.in = reinterpret_cast<const dust::MpfEnvIn *>(mb->in_dev);
+  k.in = reinterpret_cast<const dust::MpfEnvIn *>(mb->in.dev);
   k.prior_bwv = mb->prior_bwv;
   k.bw = mb->bw;
   k.bw_fixed = bw > 0.f ? bw : 0.f;
   k.gn_stride = n_steps;
-  k.skl = reinterpret_cast<const dust::SkidLik *>(mb->in_dev + mpfb_off_lik(B));
-  k.cpl = reinterpret_cast<const dust::CartLik *>(mb->in_dev + mpfb_off_lik(B));
+  k.skl = reinterpret_cast<const dust::SkidLik *>(mb->in.dev + mpfb_off_lik(B));
+  k.cpl = reinterpret_cast<const dust::CartLik *>(mb->in.dev + mpfb_off_lik(B));
   k.active = mask;
-  // block size and dynamic LDS: the lone launch's own formulas (mpf_launch)
-  const int mpad = ((m->Mp + 63) / 64) * 64;
-  int R = 1;
-  while (mpad * R * 2 <= 1024) R *= 2;
-  const size_t lds = sizeof(double) * (size_t)R * mpad * 2 * m->P + sizeof(float) * ((size_t)2 * m->Mp * m->P + m->Mp + 32);
-#define DUST_LAUNCH_MPFB4(PP, CART, MODEL, LOG, ADAM)                                                                                    \
-  do {                                                                                                                                    \
-    if (lds > 64 * 1024)                                                                                                                  \
-      HIP_TRY(hipFuncSetAttribute((const void *)mpf_optimize_batch_kernel<PP, CART, MODEL, LOG, ADAM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    mpf_optimize_batch_kernel<PP, CART, MODEL, LOG, ADAM><<<B, mpad * R, lds, stream>>>(k);                                               \
-  } while (0)
-#define DUST_LAUNCH_MPFB3(PP, CART, MODEL, LOG)                                        \
-  do {                                                                                 \
-    if (m->opt.kind == DUST_OPT_ADAM) DUST_LAUNCH_MPFB4(PP, CART, MODEL, LOG, true);   \
-    else DUST_LAUNCH_MPFB4(PP, CART, MODEL, LOG, false);                               \
-  } while (0)
-#define DUST_LAUNCH_MPFB2(PP, CART, MODEL)                          \
-  do {                                                              \
-    if (m->cfg.log_space) DUST_LAUNCH_MPFB3(PP, CART, MODEL, true); \
-    else DUST_LAUNCH_MPFB3(PP, CART, MODEL, false);                 \
-  } while (0)
   // (P up to the model's parameter count: mpfb_limits has refused the rest)
+  int st = DUST_OK;
   if (cart) {
-    if (m->P == 1) DUST_LAUNCH_MPFB2(1, true, DUST_MODEL_CARTPOLE);
-    else if (m->P == 2) DUST_LAUNCH_MPFB2(2, true, DUST_MODEL_CARTPOLE);
-    else if (m->P == 3) DUST_LAUNCH_MPFB2(3, true, DUST_MODEL_CARTPOLE);
-    else DUST_LAUNCH_MPFB2(4, true, DUST_MODEL_CARTPOLE);
+    mpfb_launch<DUST_MODEL_CARTPOLE, 1, 2, 3, 4>(m, B, stream, k, &st);
   } else if (model == DUST_MODEL_SKID_STEER) {
-    if (m->P == 1) DUST_LAUNCH_MPFB2(1, false, DUST_MODEL_SKID_STEER);
-    else if (m->P == 2) DUST_LAUNCH_MPFB2(2, false, DUST_MODEL_SKID_STEER);
-    else if (m->P == 3) DUST_LAUNCH_MPFB2(3, false, DUST_MODEL_SKID_STEER);
-    else return fail(DUST_ERR_UNSUPPORTED, "no batched filter kernel for a skid-steer filter over %d particle columns", m->P);
+    if (!mpfb_launch<DUST_MODEL_SKID_STEER, 1, 2, 3>(m, B, stream, k, &st))
+      return fail(DUST_ERR_UNSUPPORTED, "no batched filter kernel for a skid-steer filter over %d particle columns", m->P);
   } else if (model == DUST_MODEL_PARTICLE) {
-    if (m->P == 1) DUST_LAUNCH_MPFB2(1, false, DUST_MODEL_PARTICLE);
-    else return fail(DUST_ERR_UNSUPPORTED, "no batched filter kernel for a Particle filter over %d particle columns", m->P);
+    if (!mpfb_launch<DUST_MODEL_PARTICLE, 1>(m, B, stream, k, &st))
+      return fail(DUST_ERR_UNSUPPORTED, "no batched filter kernel for a Particle filter over %d particle columns", m->P);
   } else {
-    if (m->P == 1) DUST_LAUNCH_MPFB2(1, false, DUST_MODEL_PENDULUM);
-    else if (m->P == 2) DUST_LAUNCH_MPFB2(2, false, DUST_MODEL_PENDULUM);
-    else if (m->P == 3) DUST_LAUNCH_MPFB2(3, false, DUST_MODEL_PENDULUM);
-    else return fail(DUST_ERR_UNSUPPORTED, "no batched filter kernel for a Pendulum filter over %d particle columns", m->P);
+    if (!mpfb_launch<DUST_MODEL_PENDULUM, 1, 2, 3>(m, B, stream, k, &st))
+      return fail(DUST_ERR_UNSUPPORTED, "no batched filter kernel for a Pendulum filter over %d particle columns", m->P);
   }
-#undef DUST_LAUNCH_MPFB2
-#undef DUST_LAUNCH_MPFB3
-#undef DUST_LAUNCH_MPFB4
+  TRY(st);
   HIP_TRY(hipGetLastError());
   mb->n_launch++;
   return DUST_OK;
@@ -2392,21 +2365,6 @@ static int mpfb_enqueue(dust_mpf_batch *mb, hipStream_t stream, const bool updat
 
 // room for grad_norms [B][n_steps] (a reallocation frees behind the device's queued work)
 static int mpfb_gn_room(dust_mpf_batch *mb, int n_steps) { return ensure(&mb->gn, &mb->gn_cap, (size_t)mb->B * (size_t)(n_steps > 0 ? n_steps : 1)); }
-
-// rows of `row` floats per environment, device -> host on `stream`, for the environments of `active` (nullptr: all): one copy per run of them
-static int mpfb_rows_d2h(int B, hipStream_t stream, float *dst, const float *src, size_t row, const unsigned char *active) {
-  for (int e = 0; e < B;) {
-    if (active && !active[e]) {
-      ++e;
-      continue;
-    }
-    int f = e + 1;
-    while (f < B && (!active || active[f])) ++f;
-    HIP_TRY(hipMemcpyAsync(dst + (size_t)e * row, src + (size_t)e * row, (size_t)(f - e) * row * sizeof(float), hipMemcpyDeviceToHost, stream));
-    e = f;
-  }
-  return DUST_OK;
-}
 
 // B x dust_mpf_optimize in one launch (plus one for Silverman's rule when bw <= 0, plus one for the heading / angle terms of a skid-steer /
 // cart-pole filter): environment b computes what a lone filter under DUST_MPF_GRID=0 computes on its inputs, bit for bit.
@@ -2421,8 +2379,8 @@ extern "C" int dust_mpf_batch_optimize(dust_mpf_batch *mb, const float *actions,
   TRY(mpfb_enqueue(mb, st, true, actions, new_obs, bw, n_steps, active, nullptr, rows));
   mpfb_commit(mb, rows);
   mb->n_calls++;
-  if (bw_used) TRY(mpfb_rows_d2h(mb->B, st, bw_used, mb->bw, 1, active));
-  if (grad_norms && n_steps > 0) TRY(mpfb_rows_d2h(mb->B, st, grad_norms, mb->gn, (size_t)n_steps, active));
+  if (bw_used) TRY(rows_d2h(mb->B, st, bw_used, mb->bw, 1, active));
+  if (grad_norms && n_steps > 0) TRY(rows_d2h(mb->B, st, grad_norms, mb->gn, (size_t)n_steps, active));
   HIP_TRY(hipStreamSynchronize(st));
   return DUST_OK;
 }
@@ -2445,19 +2403,9 @@ extern "C" int dust_amppi_dual_batch_tick(dust_amppi_batch *b, dust_mpf_batch *m
   TRY(amppi_check(c));
   TRY(dual_pair_check(c, m));
   if (b->B != mb->B) return fail(DUST_ERR_INVALID, "the AMPPI batch has %d environments, the filter batch %d", b->B, mb->B);
-  if (m->cfg.log_space) return fail(DUST_ERR_UNSUPPORTED, "a log-space filter under AMPPI: the controller hands samples to the model as drawn (amppi.py:134-139)");
-  if (flags & DUST_STORE_STATES) return fail(DUST_ERR_UNSUPPORTED, "the AMPPI dual tick stores no trajectories");
-  if (flags & (DUST_EPS_F16 | DUST_STORE_F16)) return fail(DUST_ERR_UNSUPPORTED, "the AMPPI tick has no binary16 storage");
-  const bool sigma = c->mw_dev != nullptr, shared = (flags & DUST_AMPPI_PARAMS_SHARED) != 0;
-  if (sigma) {
-    if (!(c->sigma_scale > 0.f))
-      return fail(DUST_ERR_UNSUPPORTED, "the dual tick over sigma-point weights needs the transform's scale lambda + n (dust_set_sigma_scale)");
-    if (c->M != 2 * m->P + 1) return fail(DUST_ERR_INVALID, "sigma-point weights over P = %d parameters take M = 2 P + 1 = %d samples, the controller has M = %d", m->P, 2 * m->P + 1, c->M);
-  } else if (c->M != 1) {
-    return fail(DUST_ERR_INVALID, "n_params = %d > 1 is the sigma-point form of an AMPPI context: dust_set_param_weights first", c->M);
-  } else if (!prior_seeds) {
-    return fail(DUST_ERR_INVALID, "null argument: the draws from the filters' priors need prior_seeds [B]");
-  }
+  bool sigma, shared;
+  TRY(amppi_dual_check(c, m, flags, &sigma, &shared));
+  if (!sigma && !prior_seeds) return fail(DUST_ERR_INVALID, "null argument: the draws from the filters' priors need prior_seeds [B]");
   TRY(mpfb_limits(m, mb->B));
   if (actions_prev) TRY(mpfb_update_check(mb, actions_prev, states, mpf_steps, active));
   HIP_TRY(hipSetDevice(c->cfg.device));
@@ -2471,13 +2419,11 @@ extern "C" int dust_amppi_dual_batch_tick(dust_amppi_batch *b, dust_mpf_batch *m
   MpfbRows rows;
   TRY(mpfb_enqueue(mb, c->stream, actions_prev != nullptr, actions_prev, states, mpf_bw, mpf_steps, active, prior_seeds, rows));
   mb->n_calls++;
-  const unsigned char *mask = active ? mb->in_dev + mpfb_off_mask(mb) : nullptr;
+  const unsigned char *mask = mpfb_mask_dev(mb, active);
   int st;
   if (sigma || shared) {
     if (sigma) dust::mpf_sigma_points_batch_kernel<<<b->B, 256, 0, c->stream>>>(mb->x, m->Mp, m->P, mb->prior_bwv, c->sigma_scale, b->params, mask);
-    else
-      dust::mpf_sample_batch_kernel<<<(b->B + 255) / 256, 256, 0, c->stream>>>(mb->x, m->Mp, m->P, mb->prior_bwv,
-                                                                               reinterpret_cast<const uint64_t *>(mb->in_dev + mpfb_off_seeds(mb->B)), b->B, b->params, mask);
+    else dust::mpf_sample_batch_kernel<<<(b->B + 255) / 256, 256, 0, c->stream>>>(mb->x, m->Mp, m->P, mb->prior_bwv, mpfb_seeds_dev(mb), b->B, b->params, mask);
     HIP_TRY(hipGetLastError());
     mb->n_launch++;
     st = batch_update_launch(b, states, actions, b->params, flags, active, true, nullptr);
@@ -2488,7 +2434,7 @@ extern "C" int dust_amppi_dual_batch_tick(dust_amppi_batch *b, dust_mpf_batch *m
     pr.K = m->Mp;
     pr.P = m->P;
     pr.bwv = mb->prior_bwv;
-    pr.seeds = reinterpret_cast<const uint64_t *>(mb->in_dev + mpfb_off_seeds(mb->B));
+    pr.seeds = mpfb_seeds_dev(mb);
     pr.params_out = params_out ? b->params : nullptr;
     st = batch_update_launch(b, states, actions, nullptr, flags, active, false, &pr);
   }
@@ -2499,18 +2445,12 @@ extern "C" int dust_amppi_dual_batch_tick(dust_amppi_batch *b, dust_mpf_batch *m
     for (size_t e = 0; e < B; ++e)
       if (!active || active[e]) bw_used[e] = actions_prev ? mpf_bw : 0.f;
   const bool copies = costs || omega || a_seq || params_out || bw_dev;
-  if (costs) TRY(batch_rows_d2h(b, costs, b->costs, S, active));
-  if (omega) TRY(batch_rows_d2h(b, omega, b->omega, S, active));
-  if (a_seq) TRY(batch_rows_d2h(b, a_seq, b->a_seq, D, active));
-  if (params_out) TRY(batch_rows_d2h(b, params_out, b->params, prows * P, active));
-  if (bw_dev) TRY(batch_rows_d2h(b, bw_used, mb->bw, 1, active));
-  if (roll_steps > 0) {  // (dust_amppi_batch_roll on the mask this call has staged already)
-    const long shift = (long)roll_steps * c->da;
-    Prof pr(c, DUST_K_FORWARD);
-    amppi_batch_roll_kernel<<<b->B, 128, 0, c->stream>>>(b->a_seq, c->D, shift > c->D ? c->D : (int)shift,
-                                                         active ? reinterpret_cast<const unsigned char *>(b->in_dev) + B * 8 * sizeof(float) : nullptr);
-    HIP_TRY(hipGetLastError());
-  }
+  if (costs) TRY(rows_d2h(b->B, c->stream, costs, b->costs, S, active));
+  if (omega) TRY(rows_d2h(b->B, c->stream, omega, b->omega, S, active));
+  if (a_seq) TRY(rows_d2h(b->B, c->stream, a_seq, b->a_seq, D, active));
+  if (params_out) TRY(rows_d2h(b->B, c->stream, params_out, b->params, prows * P, active));
+  if (bw_dev) TRY(rows_d2h(b->B, c->stream, bw_used, mb->bw, 1, active));
+  if (roll_steps > 0) TRY(batch_roll_launch(b, roll_steps, active));  // (dust_amppi_batch_roll on the mask this call has staged already)
   HIP_TRY(hipEventRecord(mb->ev_ext, c->stream));  // (the filters' own entries wait for it on the host)
   if (copies) HIP_TRY(hipStreamSynchronize(c->stream));
   return DUST_OK;
