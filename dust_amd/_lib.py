@@ -22,8 +22,11 @@ ROLL_REPEAT, ROLL_MEAN, ROLL_RESAMPLE = 0, 1, 2
 STEP_ARGMAX, STEP_AVERAGE, STEP_EXTERNAL = 0, 1, 2
 PARAM_PYFLOAT, PARAM_SAMPLED, PARAM_TENSOR0D = 0, 1, 2
 CONTROL_ACCELERATION, CONTROL_VELOCITY = 0, 1
-PTR_DEVICE, STORE_STATES, EPS_AROUND_A_MAT, EPS_F16, STORE_F16, AMPPI_PARAMS_SHARED = 1, 2, 4, 8, 16, 32
+PTR_DEVICE, STORE_STATES, EPS_AROUND_A_MAT, EPS_F16, STORE_F16, AMPPI_PARAMS_SHARED, SVMPC_BATCH_KEEP_ACTIONS = 1, 2, 4, 8, 16, 32, 64
 K_ROLLOUT, K_PRIOR_SCORE, K_STEIN, K_UPDATE, K_FORWARD, K_BANDWIDTH, K_MPF, K_ROLLOUT_STATES, K_AMPPI, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
+K_SVMPC_BATCH, K_ALL = 9, 10  # appended behind ABI 3's first list (K_COUNT is that list's length); every id is < K_ALL
+(SVB_THETA, SVB_PRIOR_MEANS, SVB_PRIOR_MIX, SVB_A_MAT, SVB_COSTS, SVB_SCORE, SVB_PHI, SVB_LOG_L, SVB_LOG_P, SVB_A_MIX,
+ SVB_ACTIONS) = range(11)
 
 
 class DustError(RuntimeError):
@@ -146,6 +149,15 @@ SYMBOLS = {
     "dust_amppi_batch_update": (C.c_int, [VP, FP, VP, FP, C.c_int, C.POINTER(C.c_ubyte), FP, FP, FP]),
     "dust_amppi_batch_roll": (C.c_int, [VP, C.c_int, C.POINTER(C.c_ubyte)]),
     "dust_amppi_batch_get_actions": (C.c_int, [VP, FP]),
+    "dust_svmpc_batch_create": (C.c_int, [VP, C.c_int, C.POINTER(C.c_uint64), C.POINTER(VP)]),
+    "dust_svmpc_batch_destroy": (None, [VP]),
+    "dust_svmpc_batch_clone": (C.c_int, [VP, C.POINTER(VP)]),
+    "dust_svmpc_batch_ctx": (C.c_int, [VP, C.POINTER(VP)]),
+    "dust_svmpc_batch_set": (C.c_int, [VP, C.c_int, FP]),
+    "dust_svmpc_batch_get": (C.c_int, [VP, C.c_int, FP]),
+    "dust_svmpc_batch_optimize": (C.c_int, [VP, FP, C.c_int, VP, FP, C.c_int, C.POINTER(C.c_ubyte)]),
+    "dust_svmpc_batch_forward": (C.c_int, [VP, C.POINTER(C.c_ubyte), FP, FP]),
+    "dust_svmpc_batch_tick": (C.c_int, [VP, FP, C.c_int, VP, FP, C.c_int, C.POINTER(C.c_ubyte), FP, FP]),
     "dust_mpf_batch_create": (C.c_int, [VP, C.c_int, C.POINTER(VP)]),
     "dust_mpf_batch_destroy": (None, [VP]),
     "dust_mpf_batch_clone": (C.c_int, [VP, C.POINTER(VP)]),

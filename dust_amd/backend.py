@@ -592,6 +592,12 @@ class Context:
         the batch keeps its own copy of the context.  seeds [n_envs] (None: this context's seed + b)."""
         return AmppiBatch(self, n_envs, seeds)
 
+    def svmpc_batch(self, n_envs, seeds=None):
+        """`n_envs` independent SVMPC controllers of this context's configuration - particles, prior, a_mat, optimiser state and noise
+        stream each -, one kernel launch per optimize / forward / tick (dust_svmpc_batch_create): the batch keeps its own copy of the
+        context.  seeds [n_envs] (None: this context's seed + b)."""
+        return SvmpcBatch(self, n_envs, seeds)
+
     def get_costs(self):
         return self._get(L.load().dust_get_costs, (self.S, self.N))
 
@@ -630,7 +636,7 @@ class Context:
 
     def profile_get(self):
         out = {}
-        for k in range(L.K_COUNT):
+        for k in range(L.K_ALL):
             ms, n = C.c_double(0), C.c_int64(0)
             L.check(L.load().dust_profile_get(self._h, k, C.byref(ms), C.byref(n)))
             if n.value:
@@ -786,6 +792,110 @@ class AmppiBatch:
         """BaseController.roll(steps) of every active environment in one launch (dust_amppi_batch_roll)."""
         _, mp = _mask(active, self.B)
         L.check(L.load().dust_amppi_batch_roll(self._h, int(steps), mp))
+
+
+class SvmpcBatch:
+    """B independent SVMPC ticks in one launch (dust_svmpc_batch_*): per environment a state, particles, a prior, a_mat, optimiser
+    state, a noise stream and dynamics samples; everything else is the prototype context's.  `ctx` is the batch's inner context
+    (borrowed) for sync() and profile() / profile_get()."""
+
+    def __init__(self, proto=None, n_envs=1, seeds=None, _handle=None):
+        self._h = None
+        lib = L.load()
+        if _handle is None:
+            sd = None
+            if seeds is not None:
+                sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
+                if sd.size != int(n_envs):
+                    raise ValueError("seeds has %d entries for %d environments" % (sd.size, int(n_envs)))
+            h = L.VP()
+            L.check(lib.dust_svmpc_batch_create(proto._h, int(n_envs), None if sd is None else sd.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(h)))
+            _handle = h
+        self._h = _handle
+        self.B = int(n_envs)
+        inner = L.VP()
+        L.check(lib.dust_svmpc_batch_ctx(self._h, C.byref(inner)))
+        self.ctx = Context(_handle=inner)
+        self.ctx._borrowed = True
+        c = self.ctx
+        self.N, self.S, self.H, self.da, self.ds, self.P, self.M = c.N, c.S, c.H, c.da, c.ds, c.P, c.M
+        B, N, S, H, da = self.B, self.N, self.S, self.H, self.da
+        self._shapes = {L.SVB_THETA: (B, N, H, da), L.SVB_PRIOR_MEANS: (B, N, H, da), L.SVB_PRIOR_MIX: (B, N), L.SVB_A_MAT: (B, N, H, da),
+                        L.SVB_COSTS: (B, S, N), L.SVB_SCORE: (B, N, H, da), L.SVB_PHI: (B, N, H, da), L.SVB_LOG_L: (B, N),
+                        L.SVB_LOG_P: (B, N), L.SVB_A_MIX: (B, N), L.SVB_ACTIONS: (B, S, N, H, da)}
+
+    def close(self):
+        if self._h is not None:
+            self.ctx.close()
+            L.load().dust_svmpc_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def clone(self):
+        h = L.VP()
+        L.check(L.load().dust_svmpc_batch_clone(self._h, C.byref(h)))
+        return SvmpcBatch(n_envs=self.B, _handle=h)
+
+    def __deepcopy__(self, memo):
+        return self.clone()
+
+    def set(self, what, value):
+        """THETA / PRIOR_MEANS / A_MAT [B, N, H, da], PRIOR_MIX [B, N] (`what`: _lib.SVB_*)"""
+        L.check(L.load().dust_svmpc_batch_set(self._h, int(what), _p(_f(value, self._shapes[int(what)]))))
+
+    def get(self, what):
+        """any of _lib.SVB_*: a settable quantity, or a record of the last iteration / forward"""
+        out = np.empty(self._shapes[int(what)], np.float32)
+        L.check(L.load().dust_svmpc_batch_get(self._h, int(what), _p(out)))
+        return out
+
+    def _inputs(self, states, n_steps, eps, params, eps_dev_ptr, keep_actions):
+        B = self.B
+        st = None if states is None else _f(states, (B, self.ds))  # (None: the library refuses)
+        fl = L.SVMPC_BATCH_KEEP_ACTIONS if keep_actions else 0
+        if eps_dev_ptr:
+            e, fl = L.VP(eps_dev_ptr), fl | L.PTR_DEVICE
+        else:
+            e = None if eps is None else _f(eps, (B, n_steps, self.S, self.N, self.H, self.da))  # (the array: it stays alive through the call)
+        pr = None
+        if params is not None:
+            pr = _f(params)
+            want = (B, n_steps, self.M, max(self.P, 1))
+            if pr.shape != want:
+                raise ValueError("params has shape %s, the call reads %s" % (pr.shape, want))
+        return st, e, pr, fl
+
+    def optimize(self, states, n_steps, eps=None, params=None, active=None, eps_dev_ptr=None, keep_actions=False):
+        """n_steps SVGD iterations of every active environment in one launch (dust_svmpc_batch_optimize).  states [B, ds]; eps
+        [B, n_steps, S, N, H, da] or None (drawn on the device); params [B, n_steps, M, P] or None (no uncertain parameters)."""
+        st, e, pr, fl = self._inputs(states, n_steps, eps, params, eps_dev_ptr, keep_actions)
+        m, mp = _mask(active, self.B)
+        L.check(L.load().dust_svmpc_batch_optimize(self._h, _p(st), int(n_steps), e if eps_dev_ptr else _vp(e), _p(pr), fl, mp))
+
+    def forward(self, active=None, want_outputs=True):
+        """SVMPC.forward of every active environment in one launch -> (a_seq [B, H, da], p_weights [B, N]); the rows of inactive
+        environments are NaN.  want_outputs=False reads nothing back: the call does not wait for the device."""
+        m, mp = _mask(active, self.B)
+        a_seq = pw = None
+        if want_outputs:
+            a_seq, pw = np.full((self.B, self.H, self.da), np.nan, np.float32), np.full((self.B, self.N), np.nan, np.float32)
+        L.check(L.load().dust_svmpc_batch_forward(self._h, mp, _p(a_seq), _p(pw)))
+        return a_seq, pw
+
+    def tick(self, states, n_steps, eps=None, params=None, active=None, eps_dev_ptr=None, keep_actions=False, want_outputs=True):
+        """optimize + forward in ONE launch (dust_svmpc_batch_tick) -> (a_seq, p_weights) as forward()."""
+        st, e, pr, fl = self._inputs(states, n_steps, eps, params, eps_dev_ptr, keep_actions)
+        m, mp = _mask(active, self.B)
+        a_seq = pw = None
+        if want_outputs:
+            a_seq, pw = np.full((self.B, self.H, self.da), np.nan, np.float32), np.full((self.B, self.N), np.nan, np.float32)
+        L.check(L.load().dust_svmpc_batch_tick(self._h, _p(st), int(n_steps), e if eps_dev_ptr else _vp(e), _p(pr), fl, mp, _p(a_seq), _p(pw)))
+        return a_seq, pw
 
 
 class MpfBatch:

@@ -39,6 +39,7 @@
 #include "skid.hpp"
 #include "cartpole.hpp"
 #include "amppi.hpp"
+#include "svmpc_batch.hpp"
 #include "particle_general.hpp"
 #include "rollout.hpp"
 #include "stein.hpp"
@@ -79,9 +80,10 @@ extern "C" int dust_device_count(int *count) {
   return DUST_OK;
 }
 
-static const char *k_names[DUST_K_COUNT] = {"rollout_kernel", "pairwise_kernel<PRIOR>", "pairwise_kernel<STEIN>", "update_kernel",
-                                            "forward(finalize+roll)", "bandwidth_kernel", "mpf_kernel", "states_kernel", "amppi_kernel"};
-extern "C" const char *dust_kernel_name(int id) { return (id >= 0 && id < DUST_K_COUNT) ? k_names[id] : ""; }
+static const char *k_names[DUST_K_ALL] = {"rollout_kernel", "pairwise_kernel<PRIOR>", "pairwise_kernel<STEIN>", "update_kernel",
+                                          "forward(finalize+roll)", "bandwidth_kernel", "mpf_kernel", "states_kernel", "amppi_kernel",
+                                          "svmpc_batch_kernel"};
+extern "C" const char *dust_kernel_name(int id) { return (id >= 0 && id < DUST_K_ALL) ? k_names[id] : ""; }
 
 // peer_gather.hpp: the peers' buffers of the three exchanges (score rows, particles, log-weights) and arrival words, mapped through HIP IPC
 struct PeerState {
@@ -276,8 +278,8 @@ struct dust_ctx {
   // profiling
   bool prof;
   hipEvent_t ev0, ev1;
-  double prof_ms[DUST_K_COUNT];
-  int64_t prof_n[DUST_K_COUNT];
+  double prof_ms[DUST_K_ALL];
+  int64_t prof_n[DUST_K_ALL];
 };
 
 static DevParam dev_param(const dust_param &p) { return DevParam{p.kind, p.column, p.value}; }
@@ -5183,7 +5185,7 @@ extern "C" int dust_profile_reset(dust_ctx *c) {
   return DUST_OK;
 }
 extern "C" int dust_profile_get(dust_ctx *c, int id, double *ms, int64_t *n) {
-  if (!c || id < 0 || id >= DUST_K_COUNT) return fail(DUST_ERR_INVALID, "bad argument");
+  if (!c || id < 0 || id >= DUST_K_ALL) return fail(DUST_ERR_INVALID, "bad argument");
   if (ms) *ms = c->prof_ms[id];
   if (n) *n = c->prof_n[id];
   return DUST_OK;
@@ -5517,5 +5519,408 @@ extern "C" int dust_debug_stamps(dust_ctx *c, int kernel_id, unsigned long long 
   return DUST_OK;
 }
 #endif
+
+// ---------------------------------------------------------------------------------------------------------------
+// SVMPC over a batch of plants: B independent ticks in one launch (svmpc_batch.hpp svmpc_batch_kernel).  The batch owns a private clone
+// of the prototype context - model, cost, map, stream, profile counters - and every environment's device rows.
+struct dust_svmpc_batch {
+  dust_ctx *c;
+  int B;
+  float *theta, *mu, *a_mat;  // [B][N][D]
+  float *mixw, *logmix;       // [B][N]
+  int *alias;                 // [B]
+  uint32_t *ctr;              // [B][4]
+  uint64_t *seeds;            // [B]
+  float *opt_s[3];            // [B][N][D] or nullptr
+  float *acts;                // [B][S][N][D]
+  float *costs, *wts, *omg;   // [B][S][N]
+  float *score, *phi;         // [B][N][D]
+  float *logl, *logp, *eta, *a_mix, *pw;  // [B][N]
+  float *a_seq_out;           // [B][D]
+  float *eps, *params;        // staged inputs of a call
+  size_t eps_cap, params_cap;
+  PinnedStage in;             // per-call inputs: [B][8] states, then [B] bytes of the active mask
+  bool have_costs, have_forward, acts_kept;
+};
+
+// the box of svmpc_batch.hpp
+static int svb_check(const dust_ctx *c) {
+  const dust_config &g = c->cfg;
+  if (c->N < 1 || c->N > SVB_MAX_N) return fail(DUST_ERR_UNSUPPORTED, "n_policies = %d outside [1, %d]: a batched SVMPC tick keeps the N x N passes in one workgroup", c->N, SVB_MAX_N);
+  if (c->S < 1 || c->S > SVB_MAX_S) return fail(DUST_ERR_UNSUPPORTED, "n_samples = %d outside [1, %d] for a batched SVMPC tick", c->S, SVB_MAX_S);
+  if (c->M < 1 || c->M > SVB_MAX_M) return fail(DUST_ERR_UNSUPPORTED, "n_params = %d outside [1, %d] for a batched SVMPC tick", c->M, SVB_MAX_M);
+  if (c->D > 128) return fail(DUST_ERR_UNSUPPORTED, "H*da = %d > 128 not supported by the kernels", c->D);
+  if (g.dim_p > 4) return fail(DUST_ERR_UNSUPPORTED, "dim_p = %d > 4 uncertain parameters", g.dim_p);
+  if (g.kernel != DUST_KERNEL_K1_RBF && g.kernel != DUST_KERNEL_IMQ) return fail(DUST_ERR_UNSUPPORTED, "a batched SVMPC tick has the K1 and the IMQ kernel (K2 kernels: lone contexts)");
+  if (g.a_reg != 0.f) return fail(DUST_ERR_UNSUPPORTED, "a batched SVMPC tick has no control-cost term: ctrl_penalty = 1 (a_reg = 0), got a_reg = %g", (double)g.a_reg);
+  if (g.full_cov) return fail(DUST_ERR_UNSUPPORTED, "a batched SVMPC tick has diagonal covariances only");
+  if (c->mw_dev) return fail(DUST_ERR_UNSUPPORTED, "a batched SVMPC tick has no sigma-point rollouts");
+  if (g.model == DUST_MODEL_SKID_STEER && c->skid_w_obs != 0.f) return fail(DUST_ERR_UNSUPPORTED, "a batched SVMPC tick has no navigation cost family");
+  if (particle_general(c)) return fail(DUST_ERR_UNSUPPORTED, "a batched SVMPC tick runs Particle with acceleration control and no control-channel noise");
+  if (g.roll_strategy == DUST_ROLL_RESAMPLE) return fail(DUST_ERR_UNSUPPORTED, "a batched SVMPC tick rolls with 'repeat' or 'mean' ('resample' draws on the host)");
+  if (c->nloc != c->N || comm_active(c)) return fail(DUST_ERR_UNSUPPORTED, "a batched SVMPC tick is not sharded over GPUs");
+  if (c->serve_on) return fail(DUST_ERR_UNSUPPORTED, "the context is serving (dust_svmpc_serve_stop first)");
+  if (g.model == DUST_MODEL_PARTICLE && g.with_obstacle && !c->grid_bits)
+    return fail(DUST_ERR_STATE, "with_obstacle is set but no occupancy grid was supplied (dust_set_grid)");
+  return DUST_OK;
+}
+
+static size_t svb_in_bytes(int B) { return (size_t)B * 8 * sizeof(float) + (size_t)B; }
+
+static void svb_free(dust_svmpc_batch *b) {
+  if (!b) return;
+  if (b->c) {
+    (void)hipSetDevice(b->c->cfg.device);
+    (void)hipStreamSynchronize(b->c->stream);
+  }
+  void *dev[] = {b->theta, b->mu, b->a_mat, b->mixw, b->logmix, b->alias, b->ctr, b->seeds, b->opt_s[0], b->opt_s[1], b->opt_s[2], b->acts,
+                 b->costs, b->wts, b->omg, b->score, b->phi, b->logl, b->logp, b->eta, b->a_mix, b->pw, b->a_seq_out, b->eps, b->params};
+  for (void *p : dev)
+    if (p) (void)hipFree(p);
+  b->in.free();
+  if (b->c) dust_destroy(b->c);
+  delete b;
+}
+
+// the batch around an inner context it takes over: buffers allocated, nothing filled yet
+static int svb_alloc(dust_ctx *inner, int n_env, dust_svmpc_batch **out) {
+  dust_svmpc_batch *b = new dust_svmpc_batch();
+  b->c = inner;
+  b->B = n_env;
+  *out = b;
+  const size_t B = (size_t)n_env, N = (size_t)inner->N, S = (size_t)inner->S, D = (size_t)inner->D;
+  HIP_TRY(hipSetDevice(inner->cfg.device));
+  float **nd[] = {&b->theta, &b->mu, &b->a_mat, &b->score, &b->phi};
+  for (float **p : nd) TRY(dalloc(p, B * N * D));
+  float **nn[] = {&b->mixw, &b->logmix, &b->logl, &b->logp, &b->eta, &b->a_mix, &b->pw};
+  for (float **p : nn) TRY(dalloc(p, B * N));
+  float **sn[] = {&b->costs, &b->wts, &b->omg};
+  for (float **p : sn) TRY(dalloc(p, B * S * N));
+  TRY(dalloc(&b->acts, B * S * N * D));
+  TRY(dalloc(&b->a_seq_out, B * D));
+  TRY(dalloc(&b->alias, B));
+  TRY(dalloc(&b->ctr, B * 4));
+  TRY(dalloc(&b->seeds, B));
+  TRY(optim_slots_alloc(inner->opt, b->opt_s, B * N * D));
+  HIP_TRY(hipMemsetAsync(b->a_mix, 0, B * N * sizeof(float), inner->stream));
+  return b->in.alloc(svb_in_bytes(n_env));
+}
+
+extern "C" int dust_svmpc_batch_create(const dust_ctx *proto, int n_env, const uint64_t *seeds, dust_svmpc_batch **out) {
+  if (!proto || !out) return fail(DUST_ERR_INVALID, "null argument");
+  *out = nullptr;
+  TRY(svb_check(proto));
+  if (n_env < 1 || n_env > 65535) return fail(DUST_ERR_INVALID, "n_env = %d outside [1, 65535] (one workgroup per environment)", n_env);
+  dust_ctx *inner = nullptr;
+  TRY(dust_clone(proto, &inner));  // (settles and waits for the prototype's stream)
+  dust_svmpc_batch *b = nullptr;
+  int st = svb_alloc(inner, n_env, &b);
+  if (st == DUST_OK) {
+    const size_t B = (size_t)n_env, N = (size_t)inner->N, ND = N * (size_t)inner->D;
+    // every environment starts from the prototype's rows: one row read back, B copies sent
+    auto spread = [&](void *dst, const void *src, size_t bytes) -> int {
+      std::vector<unsigned char> one(bytes), all(bytes * B);
+      TRY(d2h(inner, one.data(), src, bytes));
+      for (size_t e = 0; e < B; ++e) memcpy(all.data() + e * bytes, one.data(), bytes);
+      return h2d(inner, dst, all.data(), all.size());
+    };
+    st = spread(b->theta, inner->theta, ND * sizeof(float));
+    if (st == DUST_OK) st = spread(b->mu, inner->mu_aliased ? inner->theta : inner->mu, ND * sizeof(float));
+    if (st == DUST_OK) st = spread(b->a_mat, inner->a_mat, ND * sizeof(float));
+    if (st == DUST_OK) st = spread(b->mixw, inner->mixw, N * sizeof(float));
+    if (st == DUST_OK) st = spread(b->logmix, inner->logmix, N * sizeof(float));
+    if (st == DUST_OK) st = spread(b->ctr, inner->ctr_dev, 4 * sizeof(uint32_t));
+    const float *const ss[3] = {inner->opt_s0, inner->opt_s1, inner->opt_s2};
+    for (int k = 0; k < 3 && st == DUST_OK; ++k)
+      if (b->opt_s[k] && ss[k]) st = spread(b->opt_s[k], ss[k], ND * sizeof(float));
+    std::vector<int> al(B, inner->mu_aliased ? 1 : 0);
+    std::vector<uint64_t> sd(B);
+    for (size_t e = 0; e < B; ++e) sd[e] = seeds ? seeds[e] : inner->cfg.seed + (uint64_t)e;
+    if (st == DUST_OK) st = h2d(inner, b->alias, al.data(), B * sizeof(int));
+    if (st == DUST_OK) st = h2d(inner, b->seeds, sd.data(), B * sizeof(uint64_t));
+  }
+  if (st != DUST_OK) {
+    svb_free(b);
+    return st;
+  }
+  *out = b;
+  return DUST_OK;
+}
+
+extern "C" void dust_svmpc_batch_destroy(dust_svmpc_batch *b) { svb_free(b); }
+
+extern "C" int dust_svmpc_batch_clone(const dust_svmpc_batch *src, dust_svmpc_batch **out) {
+  if (!src || !out) return fail(DUST_ERR_INVALID, "null argument");
+  *out = nullptr;
+  dust_ctx *inner = nullptr;
+  TRY(dust_clone(src->c, &inner));  // (waits for the source's stream)
+  dust_svmpc_batch *b = nullptr;
+  int st = svb_alloc(inner, src->B, &b);
+  const size_t B = (size_t)src->B, N = (size_t)inner->N, S = (size_t)inner->S, D = (size_t)inner->D, f = sizeof(float);
+  struct {
+    void *dst;
+    const void *s;
+    size_t bytes;
+  } cp[] = {{b->theta, src->theta, B * N * D * f}, {b->mu, src->mu, B * N * D * f}, {b->a_mat, src->a_mat, B * N * D * f},
+            {b->score, src->score, B * N * D * f}, {b->phi, src->phi, B * N * D * f}, {b->mixw, src->mixw, B * N * f},
+            {b->logmix, src->logmix, B * N * f}, {b->logl, src->logl, B * N * f}, {b->logp, src->logp, B * N * f},
+            {b->eta, src->eta, B * N * f}, {b->a_mix, src->a_mix, B * N * f}, {b->pw, src->pw, B * N * f},
+            {b->costs, src->costs, B * S * N * f}, {b->a_seq_out, src->a_seq_out, B * D * f}, {b->alias, src->alias, B * sizeof(int)},
+            {b->ctr, src->ctr, B * 4 * sizeof(uint32_t)}, {b->seeds, src->seeds, B * sizeof(uint64_t)},
+            {b->opt_s[0], src->opt_s[0], B * N * D * f}, {b->opt_s[1], src->opt_s[1], B * N * D * f}, {b->opt_s[2], src->opt_s[2], B * N * D * f}};
+  for (auto &e : cp)
+    if (st == DUST_OK && e.dst && e.s) st = d2d(inner, e.dst, e.s, e.bytes);
+  if (st == DUST_OK && src->acts_kept) st = d2d(inner, b->acts, src->acts, B * S * N * D * f);
+  if (st == DUST_OK) {
+    b->have_costs = src->have_costs;
+    b->have_forward = src->have_forward;
+    b->acts_kept = src->acts_kept;
+  }
+  if (st == DUST_OK && hipStreamSynchronize(inner->stream) != hipSuccess) st = fail(DUST_ERR_HIP, "hipStreamSynchronize failed");
+  if (st != DUST_OK) {
+    svb_free(b);
+    return st;
+  }
+  *out = b;
+  return DUST_OK;
+}
+
+extern "C" int dust_svmpc_batch_ctx(dust_svmpc_batch *b, dust_ctx **out) {
+  if (!b || !out) return fail(DUST_ERR_INVALID, "null argument");
+  *out = b->c;
+  return DUST_OK;
+}
+
+extern "C" int dust_svmpc_batch_set(dust_svmpc_batch *b, int what, const float *in) {
+  if (!b || !in) return fail(DUST_ERR_INVALID, "null argument");
+  dust_ctx *c = b->c;
+  const size_t B = (size_t)b->B, N = (size_t)c->N, ND = N * (size_t)c->D;
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  switch (what) {
+    case DUST_SVB_THETA:
+      TRY(h2d(c, b->theta, in, B * ND * sizeof(float)));
+      svmpc_batch_theta_set_kernel<<<b->B, 256, 0, c->stream>>>(b->theta, b->mu, b->alias, b->ctr, (int)ND);
+      HIP_TRY(hipGetLastError());
+      return optim_restart(c->opt, b->opt_s, B * ND, c->stream);  // (a new parameter tensor: the optimiser's state restarts)
+    case DUST_SVB_PRIOR_MEANS:
+      TRY(h2d(c, b->mu, in, B * ND * sizeof(float)));
+      HIP_TRY(hipMemsetAsync(b->alias, 0, B * sizeof(int), c->stream));
+      return DUST_OK;
+    case DUST_SVB_PRIOR_MIX:
+      for (size_t i = 0; i < B * N; ++i)
+        if (!(in[i] >= 0.f)) return fail(DUST_ERR_INVALID, "mixture weights must be >= 0 (torch.distributions.Categorical)");
+      TRY(h2d(c, b->mixw, in, B * N * sizeof(float)));
+      svmpc_batch_logmix_kernel<<<b->B, 64, 0, c->stream>>>(b->mixw, b->logmix, c->N);
+      HIP_TRY(hipGetLastError());
+      return DUST_OK;
+    case DUST_SVB_A_MAT: return h2d(c, b->a_mat, in, B * ND * sizeof(float));
+    default: return fail(DUST_ERR_INVALID, "dust_svmpc_batch_set: %d is not a settable quantity", what);
+  }
+}
+
+extern "C" int dust_svmpc_batch_get(dust_svmpc_batch *b, int what, float *out) {
+  if (!b || !out) return fail(DUST_ERR_INVALID, "null argument");
+  dust_ctx *c = b->c;
+  const size_t B = (size_t)b->B, N = (size_t)c->N, S = (size_t)c->S, ND = N * (size_t)c->D, f = sizeof(float);
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  if (what >= DUST_SVB_COSTS && what <= DUST_SVB_ACTIONS && what != DUST_SVB_LOG_P && !b->have_costs)
+    return fail(DUST_ERR_STATE, "no step of the batch has run yet: there is no such record");
+  switch (what) {
+    case DUST_SVB_THETA: return d2h(c, out, b->theta, B * ND * f);
+    case DUST_SVB_PRIOR_MEANS: return d2h(c, out, b->mu, B * ND * f);
+    case DUST_SVB_PRIOR_MIX: {
+      TRY(d2h(c, out, b->mixw, B * N * f));
+      for (size_t e = 0; e < B; ++e) {  // (dust_get_prior's normalisation)
+        double s = 0;
+        for (size_t i = 0; i < N; ++i) s += out[e * N + i];
+        for (size_t i = 0; i < N; ++i) out[e * N + i] = out[e * N + i] / (float)s;
+      }
+      return DUST_OK;
+    }
+    case DUST_SVB_A_MAT: return d2h(c, out, b->a_mat, B * ND * f);
+    case DUST_SVB_COSTS: return d2h(c, out, b->costs, B * S * N * f);
+    case DUST_SVB_SCORE: return d2h(c, out, b->score, B * ND * f);
+    case DUST_SVB_PHI: return d2h(c, out, b->phi, B * ND * f);
+    case DUST_SVB_LOG_L: return d2h(c, out, b->logl, B * N * f);
+    case DUST_SVB_LOG_P:
+      if (!b->have_forward) return fail(DUST_ERR_STATE, "no forward of the batch has run yet: there is no log_p");
+      return d2h(c, out, b->logp, B * N * f);
+    case DUST_SVB_A_MIX: return d2h(c, out, b->a_mix, B * N * f);
+    case DUST_SVB_ACTIONS:
+      if (!b->acts_kept) return fail(DUST_ERR_STATE, "the last call did not keep its actions (DUST_SVMPC_BATCH_KEEP_ACTIONS)");
+      return d2h(c, out, b->acts, B * S * ND * f);
+    default: return fail(DUST_ERR_INVALID, "dust_svmpc_batch_get: %d is not a quantity of the batch", what);
+  }
+}
+
+// lane groups of phase C: the G that needs the fewest rounds of rollouts per lane (ties: the smaller), G N S partials in LDS
+static int svb_groups(int NS, int M) {
+  auto rounds = [&](int g) { return (long)((NS * (long)g + SVB_THREADS - 1) / SVB_THREADS) * ((M + g - 1) / g); };
+  int G = 1;
+  for (int g = 2; g <= M && (long)NS * g <= SVB_PART; ++g)
+    if (rounds(g) < rounds(G)) G = g;
+  return G;
+}
+
+// optimize (n_steps >= 1), forward, or both: every check, the staging of the inputs and the ONE launch
+static int svb_launch(dust_svmpc_batch *b, const float *states, int n_steps, const void *eps, const float *params, int flags,
+                      const unsigned char *active, bool do_forward) {
+  if (!b) return fail(DUST_ERR_INVALID, "null batch");
+  dust_ctx *c = b->c;
+  if (n_steps < 0) return fail(DUST_ERR_INVALID, "n_steps < 0");
+  if (n_steps > 0 && !states) return fail(DUST_ERR_INVALID, "null argument");
+  if (flags & (DUST_EPS_F16 | DUST_STORE_F16)) return fail(DUST_ERR_UNSUPPORTED, "the batched SVMPC tick has no binary16 storage");
+  if (flags & DUST_STORE_STATES) return fail(DUST_ERR_UNSUPPORTED, "the batched SVMPC tick does not store its trajectories (DUST_STORE_STATES)");
+  if (n_steps > 0 && c->cfg.dim_p > 0 && !params) return fail(DUST_ERR_INVALID, "params_sampling is on: pass [B][n_steps][M][P] parameter samples");
+  if (c->cfg.dim_p == 0 && params) return fail(DUST_ERR_INVALID, "parameter rows without uncertain parameters (dim_p = 0)");
+  if (do_forward && n_steps == 0 && !b->have_costs) return fail(DUST_ERR_STATE, "forward() needs the costs of a previous optimize step");
+  TRY(svb_check(c));
+  const size_t B = (size_t)b->B, N = (size_t)c->N, S = (size_t)c->S, D = (size_t)c->D, M = (size_t)c->M, P = (size_t)c->cfg.dim_p;
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  const float *eps_dev = nullptr;
+  if (n_steps > 0 && eps) {
+    if (flags & DUST_PTR_DEVICE) eps_dev = static_cast<const float *>(eps);
+    else {
+      const size_t n = B * (size_t)n_steps * S * N * D;
+      TRY(ensure(&b->eps, &b->eps_cap, n));
+      TRY(h2d(c, b->eps, eps, n * sizeof(float)));
+      eps_dev = b->eps;
+    }
+  }
+  if (n_steps > 0 && params) {
+    const size_t n = B * (size_t)n_steps * M * P;
+    TRY(ensure(&b->params, &b->params_cap, n));
+    TRY(h2d(c, b->params, params, n * sizeof(float)));
+  }
+  {  // states [B][ds] and / or the mask -> the next pinned slot, on the context's stream; nobody waits
+    unsigned char *hb;
+    TRY(b->in.next(&hb));
+    const size_t sbytes = B * 8 * sizeof(float);
+    if (states) {
+      float *hs = reinterpret_cast<float *>(hb);
+      for (size_t e = 0; e < B; ++e)
+        for (int k = 0; k < 8; ++k) hs[e * 8 + k] = k < c->ds ? states[e * c->ds + k] : 0.f;
+    }
+    if (active) memcpy(hb + sbytes, active, B);
+    TRY(b->in.send(states ? 0 : sbytes, active ? sbytes + B : sbytes, c->stream));
+  }
+  SvmpcBatchArgs k;
+  memset(&k, 0, sizeof k);
+  k.dm = make_dev_model(c);
+  k.sk = c->skid;
+  k.cp = c->cart;
+  k.opt = c->opt;
+  k.N = c->N;
+  k.S = c->S;
+  k.M = c->M;
+  k.H = c->H;
+  k.da = c->da;
+  k.D = c->D;
+  k.P = c->cfg.dim_p;
+  k.n_steps = n_steps;
+  k.do_forward = do_forward ? 1 : 0;
+  k.philox = eps_dev ? 0 : 1;
+  k.kernel = c->cfg.kernel == DUST_KERNEL_IMQ ? PAIR_IMQ : PAIR_K1;
+  k.lik = c->cfg.likelihood;
+  k.roll_strategy = c->cfg.roll_strategy;
+  k.weighted_prior = c->cfg.weighted_prior;
+  k.G = svb_groups(c->N * c->S, c->M);
+  k.Q = c->N * c->D >= SVB_THREADS ? 1 : std::max(1, std::min(SVB_THREADS / (c->N * c->D), c->S));
+  k.alpha = c->cfg.alpha;
+  k.temp = c->cfg.temperature;
+  k.dt = (float)c->cfg.dt;
+  double logdet = 0;
+  for (int d = 0; d < 2; ++d) {
+    const int dd = d < c->da ? d : 0;
+    k.chol_a[d] = c->cfg.chol_a[dd];
+    k.sigma_a[d] = c->cfg.sigma_a[dd];
+    k.inv_sp[d] = 1.0f / c->cfg.sigma_p[dd];
+    k.inv_sp2[d] = 1.0f / (c->cfg.sigma_p[dd] * c->cfg.sigma_p[dd]);
+    if (d < c->da) logdet += log((double)c->cfg.sigma_p[d]);
+  }
+  k.log_norm = (float)(-c->H * logdet - 0.5 * c->D * log(2.0 * M_PI));  // (prior_merge_args' constant)
+  const float ell = c->cfg.kernel == DUST_KERNEL_IMQ ? c->cfg.imq_ell : 0.69314718055994531f;  // softplus(0) = ln 2 (update_args)
+  k.inv_ell = 1.0f / ell;
+  k.inv_l2 = 1.0f / (ell * ell);
+  k.inv_n = 1.0f / c->N;
+  k.s0_restart = opt_restart_s0(c->opt);
+  k.states = reinterpret_cast<const float *>(b->in.dev);
+  k.seeds = b->seeds;
+  k.active = active ? b->in.dev + B * 8 * sizeof(float) : nullptr;
+  k.eps = eps_dev;
+  k.params = (n_steps > 0 && params) ? b->params : nullptr;
+  k.a_seq = c->a_seq;
+  k.theta = b->theta;
+  k.mu = b->mu;
+  k.a_mat = b->a_mat;
+  k.mixw = b->mixw;
+  k.logmix = b->logmix;
+  k.alias = b->alias;
+  k.ctr = b->ctr;
+  k.opt_s0 = b->opt_s[0];
+  k.opt_s1 = b->opt_s[1];
+  k.opt_s2 = b->opt_s[2];
+  k.acts = b->acts;
+  k.costs = b->costs;
+  k.wts = b->wts;
+  k.omg = b->omg;
+  k.score = b->score;
+  k.phi = b->phi;
+  k.logl = b->logl;
+  k.logp = b->logp;
+  k.eta = b->eta;
+  k.a_mix = b->a_mix;
+  k.pw = b->pw;
+  k.a_seq_out = b->a_seq_out;
+  const size_t lds = svmpc_batch_lds_bytes(c->N, c->D, c->M);
+  {
+    Prof pr(c, DUST_K_SVMPC_BATCH);
+    auto go = [&](auto kernel) -> int {
+      if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      kernel<<<b->B, SVB_THREADS, lds, c->stream>>>(k);
+      HIP_TRY(hipGetLastError());
+      return DUST_OK;
+    };
+    switch (c->cfg.model) {
+      case DUST_MODEL_PENDULUM: TRY(go(svmpc_batch_kernel<DUST_MODEL_PENDULUM>)); break;
+      case DUST_MODEL_PARTICLE: TRY(go(svmpc_batch_kernel<DUST_MODEL_PARTICLE>)); break;
+      case DUST_MODEL_SKID_STEER: TRY(go(svmpc_batch_kernel<DUST_MODEL_SKID_STEER>)); break;
+      default: TRY(go(svmpc_batch_kernel<DUST_MODEL_CARTPOLE>)); break;
+    }
+  }
+  if (n_steps > 0) {
+    b->have_costs = true;
+    b->acts_kept = (flags & DUST_SVMPC_BATCH_KEEP_ACTIONS) != 0;
+  }
+  if (do_forward) b->have_forward = true;
+  return DUST_OK;
+}
+
+static int svb_outputs(dust_svmpc_batch *b, const unsigned char *active, float *a_seq, float *p_weights) {
+  if (!a_seq && !p_weights) return DUST_OK;
+  dust_ctx *c = b->c;
+  if (a_seq) TRY(rows_d2h(b->B, c->stream, a_seq, b->a_seq_out, (size_t)c->D, active));
+  if (p_weights) TRY(rows_d2h(b->B, c->stream, p_weights, b->pw, (size_t)c->N, active));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return DUST_OK;
+}
+
+extern "C" int dust_svmpc_batch_optimize(dust_svmpc_batch *b, const float *states, int n_steps, const void *eps, const float *params, int flags,
+                                         const unsigned char *active) {
+  if (b && n_steps == 0) return DUST_OK;  // (dust_svmpc_optimize with no step: nothing to do)
+  return svb_launch(b, states, n_steps, eps, params, flags, active, false);
+}
+
+extern "C" int dust_svmpc_batch_forward(dust_svmpc_batch *b, const unsigned char *active, float *a_seq, float *p_weights) {
+  TRY(svb_launch(b, nullptr, 0, nullptr, nullptr, 0, active, true));
+  return svb_outputs(b, active, a_seq, p_weights);
+}
+
+extern "C" int dust_svmpc_batch_tick(dust_svmpc_batch *b, const float *states, int n_steps, const void *eps, const float *params, int flags,
+                                     const unsigned char *active, float *a_seq, float *p_weights) {
+  if (n_steps < 1) return fail(DUST_ERR_INVALID, "a tick has n_steps >= 1 (got %d)", n_steps);
+  TRY(svb_launch(b, states, n_steps, eps, params, flags, active, true));
+  return svb_outputs(b, active, a_seq, p_weights);
+}
 
 #include "mpf.hpp"

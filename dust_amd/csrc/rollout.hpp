@@ -47,7 +47,7 @@ struct RolloutArgs {
   int eps_base_mode; // 0: eps = a - a_seq (ext actions, disco.py:161-164); 1: eps = a - a_mat[n] (internal noise, 155-160)
   int update_a_mat;
   int merge_prior;   // combine the prior-pass partials and write grad_pri / score = grad_lik + grad_pri
-  uint32_t magicD;   // floor(2^32 / D) + 1: exact division of tile indices by D
+  uint32_t magicD;   // floor(2^32 / D) + 1: exact division of tile indices by D (div_magic; D = 1 has no such 32-bit multiplier)
   float alpha, temp, a_reg;
   float chol_a[4], sigma_a[4], a_pre[4];
   int full_cov;        // full 2 x 2 a_cov (disco.py:91-98): actions = theta + L eps with L[1][0] = chol_off, control cost through the full
@@ -92,6 +92,12 @@ struct RolloutArgs {
   uint64_t seed;
   unsigned long long *stamps;  // diagnostic build only
 };
+
+// idx / D through RolloutArgs::magicD.  floor(2^32 / D) + 1 is 2^32 + 1 at D = 1, which a 32-bit word cannot hold (it wraps to 1, and every
+// quotient came out 0: at H d_a = 1 the weighted reductions summed lanes that own no column): there the quotient is the index itself.
+__device__ __forceinline__ int div_magic(const uint32_t idx, const uint32_t magic, const int D) {
+  return D == 1 ? (int)idx : (int)__umulhi(idx, magic);
+}
 
 // In-launch hand-off from the prior-pass workgroups of a fused launch (fused.hpp): per query tile, a monotonic arrival
 // counter; `target` arrivals mean every key slice of that tile has published its partials.
@@ -629,7 +635,7 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs &a, float *lds, c
   wg_sync();
   if (f_actions) {
     for (int idx = tid; idx < S * D; idx += nt) {
-      const int s = (int)__umulhi((uint32_t)idx, a.magicD), j = idx - s * D;
+      const int s = div_magic((uint32_t)idx, a.magicD, D), j = idx - s * D;
       if (a.store_f16) reinterpret_cast<_Float16 *>(f_actions)[((size_t)s * N + n) * D + j] = (_Float16)tile[s * Dp + j];
       else f_actions[((size_t)s * N + n) * D + j] = tile[s * Dp + j];
     }
@@ -759,7 +765,7 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs &a, float *lds, c
   // ---- 4. weighted reductions over s: grad_lik (svmpc.py:52-54) and a_mat += sum_s omega eps (disco.py:387-392) ----
   const int Q = nt / D > 0 ? nt / D : 1;
   float g = 0.f, am = 0.f;
-  const int q = (int)__umulhi((uint32_t)tid, a.magicD), j = tid - q * D;
+  const int q = div_magic((uint32_t)tid, a.magicD, D), j = tid - q * D;
   if (q < Q) {
     const float thj = th[j];
     const float is2 = 1.0f / (pick_da<DA>(a.sigma_a, j) * pick_da<DA>(a.sigma_a, j));  // (a - x) / sigma^2 as a multiply: <= 1 ulp apart

@@ -239,7 +239,7 @@ __global__ void __launch_bounds__(256, 2) particle_states_kernel(const RolloutAr
   // action rows: actions[s][n][:] = theta[n][:] + chol_a * eps[s][n][:] (or the caller's actions); the 8 particles of a sample are
   // one contiguous 8 D run
   for (int idx = tid; idx < 64 * D; idx += nt) {
-    const int row = (int)__umulhi((uint32_t)idx, a.magicD), k = idx - row * D;
+    const int row = div_magic((uint32_t)idx, a.magicD, D), k = idx - row * D;
     const int s = min(sb * 8 + (row >> 3), S - 1), n = n_first + (row & 7);
     const float e = a.noise[((size_t)s * N + n) * D + k];
     const float thk = a.noise_mode == NOISE_EPS ? a.theta[(size_t)n * D + k] : 0.f;
@@ -319,7 +319,7 @@ __global__ void __launch_bounds__(256, 2) pendulum_states_kernel(const RolloutAr
     bad |= !(fabsf(cf.c0) <= 3.0e38f && fabsf(cf.c1) <= 3.0e38f);
   }
   for (int idx = tid; idx < 256 * D; idx += nt) {
-    const int row = (int)__umulhi((uint32_t)idx, a.magicD), k = idx - row * D;
+    const int row = div_magic((uint32_t)idx, a.magicD, D), k = idx - row * D;
     const int s = min(sb * 16 + (row >> 6) * 4 + ((row & 63) >> 4), S - 1), n = n_first + (row & 15);
     const float e = a.noise[((size_t)s * N + n) * D + k];
     const float thk = a.noise_mode == NOISE_EPS ? a.theta[(size_t)n * D + k] : 0.f;
@@ -501,7 +501,7 @@ __global__ void __launch_bounds__(256, 2) pendulum_states_f16_kernel(const Rollo
     bad |= !(fabsf(cf.c0) <= 3.0e38f && fabsf(cf.c1) <= 3.0e38f);
   }
   for (int idx = tid; idx < 256 * D; idx += nt) {
-    const int row = (int)__umulhi((uint32_t)idx, a.magicD), k = idx - row * D;
+    const int row = div_magic((uint32_t)idx, a.magicD, D), k = idx - row * D;
     const int s = min(sb * 8 + (row >> 6) * 2 + ((row & 63) >> 5), S - 1), n = n_first + (row & 31);
     const float e = a.noise[((size_t)s * N + n) * D + k];
     const float thk = a.noise_mode == NOISE_EPS ? a.theta[(size_t)n * D + k] : 0.f;
@@ -634,7 +634,7 @@ __global__ void __launch_bounds__(256, 2) particle_states_f16_kernel(const Rollo
     for (int i = tid; i < words; i += nt) gridl[i] = a.dm.grid_bits[i];
   }
   for (int idx = tid; idx < 64 * D; idx += nt) {  // the 16 particles of a sample are one contiguous 16 D run
-    const int row = (int)__umulhi((uint32_t)idx, a.magicD), k = idx - row * D;
+    const int row = div_magic((uint32_t)idx, a.magicD, D), k = idx - row * D;
     const int s = min(sb * 4 + (row >> 4), S - 1), n = n_first + (row & 15);
     const float e = a.noise[((size_t)s * N + n) * D + k];
     const float thk = a.noise_mode == NOISE_EPS ? a.theta[(size_t)n * D + k] : 0.f;

@@ -170,3 +170,182 @@ class SVMPC:
             a_seq, pw = ctx.svmpc_tick(self._state(state), n_steps, eps, params)
         self._prior_stale = True
         return torch.from_numpy(a_seq), torch.from_numpy(pw)
+
+
+class BatchSVMPC:
+    """`n_envs` independent `SVMPC` controllers of one configuration - the deep copies the reference makes per episode
+    (simulations.py:62,78) - whose optimize / forward / tick are ONE kernel launch each (csrc/svmpc_batch.hpp svmpc_batch_kernel).
+    Every environment has its own state, particles, prior, a_mat, optimiser state, noise stream (`seeds`, default seed + b) and
+    dynamics samples.  The constructor takes SVMPC's arguments behind `n_envs` and refuses what lies outside the kernel's box
+    (K1 / IMQ kernel, N <= 64, S <= 1024, M <= 64, H d_a <= 128, ctrl_penalty = 1, diagonal covariances, no sigma points, roll
+    'repeat' / 'mean') before any device is touched."""
+
+    def __init__(self, n_envs, init_particles, prior, likelihood, roll_strategy="repeat", weighted_prior=False, kernel=None, bw_scale=1.0,
+                 n_particles=None, n_steps=100, optimizer_class=torch.optim.Adam, seeds=None, **opt_args):
+        if not 1 <= int(n_envs) <= 65535:
+            raise ValueError("n_envs = %d outside [1, 65535]" % int(n_envs))
+        self.n_envs = int(n_envs)
+        if seeds is not None and len(seeds) != self.n_envs:
+            raise ValueError("seeds has %d entries for %d environments" % (len(seeds), self.n_envs))
+        self._seeds = None if seeds is None else [int(v) for v in seeds]
+        if roll_strategy not in ("repeat", "mean", "resample"):
+            raise ValueError("{} is an invalid roll strategy.".format(roll_strategy))
+        if roll_strategy == "resample":
+            raise NotImplementedError("a batched SVMPC tick rolls with 'repeat' or 'mean': 'resample' draws on the host between the two halves")
+        kc = kernel_config(kernel)
+        if kc["kernel"] not in ("K1", "IMQ"):
+            raise NotImplementedError("a batched SVMPC tick has the K1 (RBFKernel) and the IMQ kernel; %s runs on lone SVMPC objects" % kc["kernel"])
+        ctrl = likelihood.controller
+        if ctrl._tf is not None:
+            raise NotImplementedError("a batched SVMPC tick has no sigma-point rollouts (params_sampling=MerweScaledUTF)")
+        if float(ctrl._ctrl_penalty) != 1.0:
+            raise NotImplementedError("a batched SVMPC tick has no control-cost term: ctrl_penalty = 1 (got %g)" % float(ctrl._ctrl_penalty))
+        a_cov = ctrl.a_dist.covariance_matrix
+        comp = prior.component_distribution.base_dist
+        cov = comp.covariance_matrix
+        cov = cov.reshape(-1, cov.shape[-2], cov.shape[-1])[0]
+        if not torch.equal(a_cov, torch.diag(torch.diag(a_cov))) or not torch.equal(cov, torch.diag(torch.diag(cov))):
+            raise NotImplementedError("a batched SVMPC tick has diagonal covariances only (a full a_cov / prior covariance: lone SVMPC objects)")
+        init_particles = torch.as_tensor(init_particles, dtype=torch.float).detach().clone()
+        N = int(init_particles.shape[-3])
+        for name, v, hi in (("n_particles", N, 64), ("action_samples", ctrl.n_actions, 1024), ("params_samples", ctrl.n_params, 64),
+                            ("hz_len * dim_a", ctrl.hz_len * ctrl.dim_a, 128)):
+            if not 1 <= int(v) <= hi:
+                raise ValueError("%s = %d outside [1, %d] for a batched SVMPC tick" % (name, int(v), hi))
+        if N != ctrl.n_pol:
+            raise ValueError("init_particles has %d particles, the controller has n_policies = %d" % (N, ctrl.n_pol))
+        self.likelihood = likelihood
+        self.kernel, self.bw_scale = kernel, bw_scale
+        self.n_particles = n_particles if n_particles is not None else N
+        self.n_steps = n_steps
+        self.optimizer_class, self.opt_args = optimizer_class, opt_args
+        self.w_prior, self.roll_strategy = weighted_prior, roll_strategy
+        self._optim = optimizer_config(optimizer_class, opt_args)
+        oc = self._optim
+        opt = dict(optimizer="Adam" if oc["kind"] == "Adam" else "SGD", lr=oc["lr"], optim=oc)
+        if oc["kind"] == "Adam":
+            opt["adam"] = (oc["beta1"], oc["beta2"], oc["eps"])
+        ctrl._svmpc_cfg.update(opt, likelihood=likelihood.kind, alpha=float(likelihood.alpha), weighted_prior=bool(weighted_prior),
+                               roll_strategy=roll_strategy, sigma_p=cov.diag().sqrt().numpy(), p_cov=cov.detach().numpy().copy(), **kc)
+        B = self.n_envs
+        shape = (N, ctrl.hz_len, ctrl.dim_a)
+        self._theta0 = (init_particles if init_particles.ndim == 4 else init_particles[None].repeat(B, 1, 1, 1)).reshape((B,) + shape).clone()
+        self._prior0 = (comp.loc.detach().clone().reshape(shape), prior.mixture_distribution.probs.detach().clone().reshape(N))
+        self._prior_cov = cov
+        self._batch = None
+        self._key = None
+        self.optimizer = optimizer_class(params=[torch.zeros(1, requires_grad=True)], **opt_args)
+        self._opt_group = group_options(self.optimizer)
+
+    # -- device plumbing
+    def _ensure_batch(self, params_dist=None):
+        ctrl = self.likelihood.controller
+        cfg = ctrl._config(self.likelihood.model, params_dist)
+        key = repr(sorted((k, np.asarray(v).tolist() if not isinstance(v, (str, bool, int, float, tuple)) else v) for k, v in cfg.items()))
+        if self._batch is not None and key == self._key:
+            return self._batch
+        from .. import _lib as L
+
+        carry = None
+        if self._batch is not None:  # configuration changed: carry every environment's state over
+            old = self._batch
+            carry = [old.get(w) for w in (L.SVB_THETA, L.SVB_PRIOR_MEANS, L.SVB_PRIOR_MIX, L.SVB_A_MAT)]
+            old.close()
+            self._batch = None
+        proto = ctrl._ensure_ctx(self.likelihood.model, params_dist)
+        try:
+            proto.set_theta(self._theta0[0].numpy())
+            proto.set_prior(self._prior0[0].numpy(), self._prior0[1].numpy())
+            self._batch, self._key = proto.svmpc_batch(self.n_envs, self._seeds), key
+        finally:
+            proto.close()  # (the batch keeps its own copy)
+            ctrl._ctx = ctrl._ctx_key = None
+        if carry is not None:
+            for w, v in zip((L.SVB_THETA, L.SVB_PRIOR_MEANS, L.SVB_PRIOR_MIX, L.SVB_A_MAT), carry):
+                self._batch.set(w, v)
+        elif not all(torch.equal(self._theta0[b], self._theta0[0]) for b in range(1, self.n_envs)):
+            self._batch.set(L.SVB_THETA, self._theta0.numpy())
+        return self._batch
+
+    def __deepcopy__(self, memo):
+        import copy
+
+        new = copy.copy(self)
+        memo[id(self)] = new
+        for k, v in self.__dict__.items():
+            if k == "_batch":
+                new._batch = None if v is None else v.clone()
+            elif k in ("kernel", "optimizer_class"):
+                setattr(new, k, v)
+            else:
+                setattr(new, k, copy.deepcopy(v, memo))
+        return new
+
+    @property
+    def theta(self):
+        """[B, N, H, da]"""
+        if self._batch is None:
+            return self._theta0
+        from .. import _lib as L
+
+        return torch.from_numpy(self._batch.get(L.SVB_THETA))
+
+    @theta.setter
+    def theta(self, v):
+        self._theta0 = torch.as_tensor(v, dtype=torch.float).detach().clone().reshape(self._theta0.shape)
+        if self._batch is not None:
+            from .. import _lib as L
+
+            self._batch.set(L.SVB_THETA, self._theta0.numpy())
+
+    def _states(self, states):
+        return torch.as_tensor(states, dtype=torch.float).reshape(self.n_envs, -1).numpy()
+
+    def _active(self, active):
+        if active is None:
+            return np.ones(self.n_envs, bool)
+        a = np.asarray(active).reshape(-1) != 0
+        if a.shape != (self.n_envs,):
+            raise ValueError("active has %d entries for %d environments" % (a.size, self.n_envs))
+        return a
+
+    def _params(self, params_dist, n_steps, on, params):
+        """[B, n_steps, M, P]: the caller's rows, or the draws SVMPC makes, once per active environment in environment order"""
+        ctrl = self.likelihood.controller
+        if params is not None:
+            return np.asarray(torch.as_tensor(params, dtype=torch.float).numpy(), np.float32)
+        if not ctrl._sampling:
+            return None
+        rows = [ctrl._sample_params(params_dist, n_steps)[0] if on[b] else None for b in range(self.n_envs)]
+        shape = next(r for r in rows if r is not None).shape if on.any() else (n_steps, ctrl.n_params, 1)
+        return np.stack([np.zeros(shape, np.float32) if r is None else np.asarray(r, np.float32) for r in rows])
+
+    def _eps(self, eps):
+        return None if eps is None else np.asarray(eps, np.float32)
+
+    # -- svmpc.py:87-126 for every environment
+    def optimize(self, states, params_dist, n_steps=None, eps=None, active=None, params=None):
+        """states [B, ds]; eps [B, n_steps, S, N, H, da] or None (device noise); params [B, n_steps, M, P] overrides the class's own
+        draws from `params_dist` - one parameter distribution per environment."""
+        check_optimizer(self.optimizer, self._opt_group)
+        batch = self._ensure_batch(params_dist)
+        n_steps = self.n_steps if n_steps is None else n_steps
+        on = self._active(active)
+        batch.optimize(self._states(states), n_steps, self._eps(eps), self._params(params_dist, n_steps, on, params), None if active is None else on)
+
+    # -- svmpc.py:172-200 for every environment
+    def forward(self, states, params_dist, active=None):
+        """-> (a_seq [B, H, da], p_weights [B, N]); the rows of inactive environments are NaN"""
+        batch = self._ensure_batch(params_dist)
+        a_seq, pw = batch.forward(None if active is None else self._active(active))
+        return torch.from_numpy(a_seq), torch.from_numpy(pw)
+
+    def tick(self, states, params_dist, n_steps=None, eps=None, active=None, params=None):
+        """optimize + forward of every active environment in ONE launch (dust_svmpc_batch_tick)"""
+        check_optimizer(self.optimizer, self._opt_group)
+        batch = self._ensure_batch(params_dist)
+        n_steps = self.n_steps if n_steps is None else n_steps
+        on = self._active(active)
+        a_seq, pw = batch.tick(self._states(states), n_steps, self._eps(eps), self._params(params_dist, n_steps, on, params),
+                               None if active is None else on)
+        return torch.from_numpy(a_seq), torch.from_numpy(pw)

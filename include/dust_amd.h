@@ -74,7 +74,9 @@ enum dust_flags {
   DUST_EPS_F16 = 8,
   DUST_STORE_F16 = 16,
   /* ABI 3, dust_amppi_update: `params` is ONE row that every trajectory uses (AMPPI(params_sampling="single"), amppi.py:91-93) */
-  DUST_AMPPI_PARAMS_SHARED = 32
+  DUST_AMPPI_PARAMS_SHARED = 32,
+  /* ABI 3, dust_svmpc_batch_optimize / _tick: keep the last iteration's actions for dust_svmpc_batch_get(DUST_SVB_ACTIONS) */
+  DUST_SVMPC_BATCH_KEEP_ACTIONS = 64
 };
 
 typedef struct dust_param {
@@ -397,6 +399,69 @@ int dust_amppi_batch_roll(dust_amppi_batch *batch, int steps, const unsigned cha
 /* The actions the last tick used, [B][S][H][da]; the rows of environments that were inactive in that tick are not written. */
 int dust_amppi_batch_get_actions(dust_amppi_batch *batch, float *actions);
 
+/* ---- SVMPC over a batch of plants: B independent SVMPC controllers of one configuration, ONE kernel launch per call (ABI 3, additive) ----
+ * The reference evaluates a controller over many episodes with a deep copy of the controller each (simulations.py:62,78); a batch is
+ * those B copies on one device.  Every environment has its own state, particles, prior (means and mixture), a_mat, optimiser state,
+ * Philox stream and dynamics samples; the model, the cost, N, S, M, H, the covariances, the Stein kernel and the optimiser's options
+ * are shared.  The launch is a grid of B workgroups (dust_amd/csrc/svmpc_batch.hpp svmpc_batch_kernel): workgroup b runs the whole
+ * call for environment b and talks to no other workgroup.  Environment b's results do not depend on B, on its slot or on its
+ * neighbours, bit for bit; against a lone context on the same inputs they agree to rounding (other summation orders), and its
+ * device-drawn noise continues the stream of a lone context created with seed seeds[b] that has made the same calls.
+ *
+ * The box (DUST_ERR_UNSUPPORTED / DUST_ERR_INVALID from dust_svmpc_batch_create, before anything is allocated): 1 <= n_policies <= 64,
+ * 1 <= n_samples <= 1024, 1 <= n_params <= 64, H dim_a <= 128, dim_p <= 4, 1 <= n_env <= 65535, the K1 or the IMQ kernel, a_reg = 0
+ * (ctrl_penalty = 1), diagonal covariances.  Not supported: sigma-point weights, the navigation cost family, Particle with velocity
+ * control or control-channel noise, binary16 storage, DUST_STORE_STATES, roll strategy "resample", sharded contexts, contexts that
+ * are serving.
+ *
+ * dust_svmpc_batch_create: the batch keeps a private dust_clone of `proto`: `proto` may be destroyed afterwards and later changes to it
+ *   do not reach the batch.  Every environment starts from proto's particles, prior, a_mat, optimiser configuration and state, and
+ *   stream position.  seeds [n_env] (NULL: proto's seed + b).
+ * dust_svmpc_batch_clone: copy.deepcopy - an independent batch that continues exactly as its source would.
+ * dust_svmpc_batch_ctx: the inner context, BORROWED (never dust_destroy it), for dust_sync and dust_profile_*: each of optimize,
+ *   forward and tick counts as one DUST_K_SVMPC_BATCH launch. */
+typedef struct dust_svmpc_batch dust_svmpc_batch;
+enum dust_svmpc_batch_what {
+  DUST_SVB_THETA = 0,       /* [B][N][H][da] set / get; set restarts the optimiser state, as dust_set_theta does */
+  DUST_SVB_PRIOR_MEANS = 1, /* [B][N][H][da] set / get; after a forward the means ARE the particles (svgd.py:87) until they are set */
+  DUST_SVB_PRIOR_MIX = 2,   /* [B][N] set: mixture weights >= 0; get: the probabilities */
+  DUST_SVB_A_MAT = 3,       /* [B][N][H][da] set / get */
+  /* get only, of the last iteration (DUST_ERR_STATE before one) or forward: */
+  DUST_SVB_COSTS = 4,       /* [B][S][N] */
+  DUST_SVB_SCORE = 5,       /* [B][N][H][da] */
+  DUST_SVB_PHI = 6,         /* [B][N][H][da] */
+  DUST_SVB_LOG_L = 7,       /* [B][N] */
+  DUST_SVB_LOG_P = 8,       /* [B][N], of the last forward */
+  DUST_SVB_A_MIX = 9,       /* [B][N] */
+  DUST_SVB_ACTIONS = 10     /* [B][S][N][H][da], kept only when the call carried DUST_SVMPC_BATCH_KEEP_ACTIONS */
+};
+int dust_svmpc_batch_create(const dust_ctx *proto, int n_env, const uint64_t *seeds, dust_svmpc_batch **out);
+void dust_svmpc_batch_destroy(dust_svmpc_batch *batch);
+int dust_svmpc_batch_clone(const dust_svmpc_batch *batch, dust_svmpc_batch **out);
+int dust_svmpc_batch_ctx(dust_svmpc_batch *batch, dust_ctx **ctx);
+int dust_svmpc_batch_set(dust_svmpc_batch *batch, int what, const float *in);
+int dust_svmpc_batch_get(dust_svmpc_batch *batch, int what, float *out);
+/* dust_svmpc_batch_optimize = B x dust_svmpc_optimize in ONE launch (no memset node: there are no arrival words):
+ *   states [B][ds], host;
+ *   eps [B][n_steps][S][N][H][da], host, or device with DUST_PTR_DEVICE (which speaks of `eps` alone), or NULL: environment b draws
+ *     with key seeds[b] in the lone kernels' counter layout;
+ *   params [B][n_steps][M][P], host; NULL exactly when dim_p = 0 - one parameter distribution per environment;
+ *   flags: DUST_PTR_DEVICE, DUST_SVMPC_BATCH_KEEP_ACTIONS;
+ *   active [B] bytes, host, or NULL (all): the workgroup of an environment with active[b] = 0 returns at once and everything of that
+ *     environment stays as it was.
+ * The call returns without waiting for the device when eps and params are NULL or on the device.
+ * dust_svmpc_batch_forward = B x dust_svmpc_forward in one launch: a_seq [B][H][da] (the best particle BEFORE the roll) and p_weights
+ *   [B][N], each may be NULL; the rows of inactive environments are NOT written; with both NULL the call does not wait for the device.
+ *   DUST_ERR_STATE before any step of the batch has produced costs.
+ * dust_svmpc_batch_tick = optimize + forward in ONE launch.
+ * DUST_ERR_UNSUPPORTED (before any launch): DUST_STORE_STATES, DUST_EPS_F16 / DUST_STORE_F16.  DUST_ERR_INVALID: NULL states,
+ * n_steps < 0 (tick: < 1), params without uncertain parameters or uncertain parameters without params. */
+int dust_svmpc_batch_optimize(dust_svmpc_batch *batch, const float *states, int n_steps, const void *eps, const float *params, int flags,
+                              const unsigned char *active);
+int dust_svmpc_batch_forward(dust_svmpc_batch *batch, const unsigned char *active, float *a_seq, float *p_weights);
+int dust_svmpc_batch_tick(dust_svmpc_batch *batch, const float *states, int n_steps, const void *eps, const float *params, int flags,
+                          const unsigned char *active, float *a_seq, float *p_weights);
+
 /* stage outputs of the last call, for parity tests ([S][N] / [N][H][da] / [N]) */
 int dust_get_costs(dust_ctx *ctx, float *costs);
 int dust_get_actions(dust_ctx *ctx, float *actions);
@@ -462,7 +527,9 @@ int dust_set_stream(dust_ctx *ctx, void *hip_stream);
 /* timing / roofline support: HIP-event timing of each kernel family on the context's stream */
 enum dust_kernel_id {
   DUST_K_ROLLOUT = 0, DUST_K_PRIOR_SCORE = 1, DUST_K_STEIN = 2, DUST_K_UPDATE = 3, DUST_K_FORWARD = 4, DUST_K_BANDWIDTH = 5,
-  DUST_K_MPF = 6, DUST_K_ROLLOUT_STATES = 7 /* whole-line stored-states rollouts */, DUST_K_AMPPI = 8 /* dust_amppi_update */, DUST_K_COUNT = 9
+  DUST_K_MPF = 6, DUST_K_ROLLOUT_STATES = 7 /* whole-line stored-states rollouts */, DUST_K_AMPPI = 8 /* dust_amppi_update */, DUST_K_COUNT = 9 /* the ids of ABI 3's first list, above: frozen */,
+  /* appended behind that list: */
+  DUST_K_SVMPC_BATCH = 9 /* dust_svmpc_batch_optimize / _forward / _tick */, DUST_K_ALL = 10 /* every id is < DUST_K_ALL */
 };
 int dust_profile_enable(dust_ctx *ctx, int on);
 int dust_profile_get(dust_ctx *ctx, int kernel_id, double *total_ms, int64_t *launches);
