@@ -897,6 +897,33 @@ class SvmpcBatch:
         L.check(L.load().dust_svmpc_batch_tick(self._h, _p(st), int(n_steps), e if eps_dev_ptr else _vp(e), _p(pr), fl, mp, _p(a_seq), _p(pw)))
         return a_seq, pw
 
+    def dual_tick(self, mpf, states, actions_prev=None, n_steps=1, eps=None, mpf_steps=20, mpf_bw=None, seeds=None, active=None,
+                  want_outputs=True, want_params=False, flags=0, eps_dev_ptr=None, keep_actions=False):
+        """One control period of the DuSt-MPC loop for every active environment in one C call (dust_svmpc_dual_batch_tick): the filters'
+        update for (actions_prev[b], states[b]) - skipped when actions_prev is None -, then ONE launch of n_steps SVGD iterations, whose
+        dynamics samples are drawn inside the kernel from every environment's refreshed prior, and forward().  mpf: an `MpfBatch` of B
+        environments; seeds [B]: the Philox key of every environment's draws; eps as tick().  -> (a_seq [B, H, da] before the roll,
+        p_weights [B, N], params [B, n_steps, M, P] or None, bw_used [B]); the rows of inactive environments are NaN.
+        want_outputs=False reads nothing back: the call does not wait for the device."""
+        B = self.B
+        st, e, _, fl = self._inputs(states, n_steps, eps, None, eps_dev_ptr, keep_actions)
+        ap = None if actions_prev is None else _f(actions_prev, (B, self.da))
+        sd = None
+        if seeds is not None:
+            sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
+            if sd.size != B:
+                raise ValueError("seeds has %d entries for %d environments" % (sd.size, B))
+        _, mp = _mask(active, B)
+        a_seq = pw = bw = None
+        if want_outputs:
+            a_seq, pw, bw = (np.full(sh, np.nan, np.float32) for sh in ((B, self.H, self.da), (B, self.N), (B,)))
+        pout = np.full((B, int(n_steps), self.M, max(self.P, 1)), np.nan, np.float32) if want_params else None
+        L.check(L.load().dust_svmpc_dual_batch_tick(self._h, mpf._h, _p(st), _p(ap), int(n_steps), e if eps_dev_ptr else _vp(e), int(flags) | fl,
+                                                    int(mpf_steps), float(-1.0 if mpf_bw is None else mpf_bw),
+                                                    None if sd is None else sd.ctypes.data_as(C.POINTER(C.c_uint64)), mp,
+                                                    _p(a_seq), _p(pw), _p(pout), _p(bw)))
+        return a_seq, pw, pout, bw
+
 
 class MpfBatch:
     """B dynamics filters of one configuration, updated in one launch (dust_mpf_batch_*): per environment its particles, optimiser

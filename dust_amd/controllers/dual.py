@@ -368,3 +368,129 @@ class BatchDualAMPPI:
         new_states = plant(states, actions)
         self.step(actions, new_states)
         return actions, new_states, omega
+
+
+class BatchDualSVMPC:
+    """The DuSt-MPC loop over `B = svmpc.n_envs` plants at once: a `BatchSVMPC` and B copies of one `MPF` - the deep copies of controller
+    and filter the reference makes per episode (dust/utils/simulations.py:62,78) - with a whole control period of all of them in ONE C
+    call (dust_svmpc_dual_batch_tick): the B filter updates in one launch, Silverman's bandwidths on the device when none is given, then
+    the B ticks (n_steps SVGD iterations and forward()) in one launch whose workgroups draw their dynamics samples from their own
+    environment's refreshed prior.  Nothing crosses the bus between the filters and the ticks, and the launch count does not depend on B.
+    Environment b draws what a `DualSVMPC(fused=True, seed=seed + (b << 32))` over a filter of its own draws, bit for bit when that
+    filter takes the single-workgroup kernel, under the prior keys `seed + (b << 32) + t` in period t = 1, 2, ...: the lone class's
+    `seed + t` on a per-environment base, so that two environments never meet on one key at different times.  (The lone and the batched
+    SVMPC kernels add in different orders: the controllers agree to rounding.)
+
+        forward(states, eps=None, active=None)      -> (a_seq [B, H, da]: the best particle before the roll, p_weights [B, N]); NaN rows
+                                                    for inactive environments
+        step(actions [B, da], new_states [B, ds])   notes the update; the next forward() carries it out
+        tick(states, plant)                         forward, `plant(states, actions) -> new_states`, step
+
+    `mpf` is the prototype: every environment starts from its particles (or from `init_particles[b]`, [B, Mp, P]), optimiser state and
+    bandwidths; the first forward()'s states are the observations the first update's predictions start from.  There is no unfused path
+    and no `warm_up`: what the fused call does not take (a sigma-point controller, recorded draws) is refused."""
+
+    def __init__(self, svmpc, mpf, mpf_bw=None, mpf_steps=20, n_steps=None, seed=0, init_particles=None):
+        from ..inference.svmpc import BatchSVMPC
+
+        if not isinstance(svmpc, BatchSVMPC):
+            raise TypeError("BatchDualSVMPC needs a BatchSVMPC controller, got %s" % type(svmpc).__name__)
+        if not svmpc.likelihood.controller._sampling:
+            raise ValueError("BatchDualSVMPC needs a controller that samples dynamics parameters: params_sampling=None reads no filter")
+        if mpf.draw_source is not None:
+            raise NotImplementedError("recorded filter draws (draw_source) have no batched form")
+        self.svmpc, self.mpf = svmpc, mpf
+        self.n_envs = svmpc.n_envs
+        self.mpf_bw, self.mpf_steps, self.n_steps = mpf_bw, int(mpf_steps), n_steps
+        self._seed, self._t, self._pending = int(seed), 0, None
+        if init_particles is not None:
+            init_particles = torch.as_tensor(init_particles, dtype=torch.float).detach().clone()
+            want = (self.n_envs, mpf._dev.Mp, mpf._dev.P)
+            if tuple(init_particles.shape) != want:
+                raise ValueError("init_particles has shape %s, the batch takes %s" % (tuple(init_particles.shape), want))
+        self._init_particles = init_particles
+        self._mb = None
+        self.ticks = 0
+        self.last_bw = None
+
+    def prior_keys(self, t):
+        """The Philox keys of period t = 1, 2, ...: seed + (b << 32) + t for environment b (modulo 2^64)."""
+        return [(self._seed + (b << 32) + int(t)) & 0xFFFFFFFFFFFFFFFF for b in range(self.n_envs)]
+
+    def __deepcopy__(self, memo):
+        new = copy.copy(self)
+        memo[id(self)] = new
+        new.svmpc = copy.deepcopy(self.svmpc, memo)
+        new.mpf = copy.deepcopy(self.mpf, memo)
+        new._mb = None if self._mb is None else self._mb.clone()
+        new._pending = None if self._pending is None else tuple(v.copy() for v in self._pending)
+        return new
+
+    def _filters(self, states=None):
+        if self._mb is None:
+            if self.mpf.draw_source is not None:
+                raise NotImplementedError("recorded filter draws (draw_source) have no batched form")
+            mb = self.mpf._dev.batch(self.n_envs)
+            if self._init_particles is not None:
+                mb.set_particles(self._init_particles.numpy())
+            if states is not None:
+                mb.set_obs(states)
+            self._mb = mb
+        return self._mb
+
+    @property
+    def theta(self):
+        """[B, N, H, da]"""
+        return self.svmpc.theta
+
+    @property
+    def controller(self):
+        return self.svmpc.likelihood.controller
+
+    @property
+    def dyn_particles(self):
+        """[B, Mp, P]; a noted update is carried out first"""
+        self._flush()
+        return torch.from_numpy(self._filters().get_particles())
+
+    def _flush(self):
+        pend = self._pending
+        if pend is not None:
+            _, bw = self._filters().optimize(pend[0], pend[1], self.mpf_bw, self.mpf_steps)
+            self._pending, self.last_bw = None, torch.from_numpy(bw)
+
+    def forward(self, states, eps=None, active=None):
+        """eps [B, n_steps, S, N, H, da]: recorded noise in place of device-drawn noise; active [B]: the environments that tick"""
+        from ..inference.svmpc import check_optimizer
+
+        sv = self.svmpc
+        check_optimizer(sv.optimizer, sv._opt_group)
+        batch = sv._ensure_batch(self.mpf.prior)
+        n_steps = sv.n_steps if self.n_steps is None else self.n_steps
+        st = sv._states(states)
+        mb = self._filters(st)
+        pend = self._pending
+        a_seq, pw, _, bw = batch.dual_tick(mb, st, None if pend is None else pend[0], n_steps=n_steps, eps=sv._eps(eps),
+                                           mpf_steps=self.mpf_steps, mpf_bw=self.mpf_bw, seeds=self.prior_keys(self._t + 1),
+                                           active=None if active is None else sv._active(active))
+        self._t, self._pending = self._t + 1, None  # (a refused call consumes neither the keys nor the noted update)
+        if pend is not None:
+            self.last_bw = torch.from_numpy(bw)
+        self.ticks += 1
+        return torch.from_numpy(a_seq), torch.from_numpy(pw)
+
+    def step(self, actions, new_states):
+        self._flush()
+        B = self.n_envs
+        self._pending = (torch.as_tensor(actions, dtype=torch.float).reshape(B, -1).numpy().copy(),
+                         torch.as_tensor(new_states, dtype=torch.float).reshape(B, -1).numpy().copy())
+        return None, None
+
+    def tick(self, states, plant):
+        """One loop iteration with a host plant callable `plant(states [B, ds], actions [B, da]) -> new_states [B, ds]`: forward,
+        plant, step.  Returns (actions, new_states, p_weights)."""
+        a_seq, pw = self.forward(states)
+        actions = a_seq[:, 0]
+        new_states = plant(states, actions)
+        self.step(actions, new_states)
+        return actions, new_states, pw

@@ -5762,29 +5762,37 @@ static int svb_groups(int NS, int M) {
   return G;
 }
 
-// optimize (n_steps >= 1), forward, or both: every check, the staging of the inputs and the ONE launch
-static int svb_launch(dust_svmpc_batch *b, const float *states, int n_steps, const void *eps, const float *params, int flags,
-                      const unsigned char *active, bool do_forward) {
+// What a call of the batch refuses, ahead of any copy or launch.  from_prior: the dynamics samples are drawn from filters inside the
+// kernel (dust_svmpc_dual_batch_tick), there are no rows to pass
+static int svb_call_check(const dust_svmpc_batch *b, const float *states, int n_steps, const float *params, bool from_prior, int flags, bool do_forward) {
   if (!b) return fail(DUST_ERR_INVALID, "null batch");
-  dust_ctx *c = b->c;
+  const dust_ctx *c = b->c;
   if (n_steps < 0) return fail(DUST_ERR_INVALID, "n_steps < 0");
   if (n_steps > 0 && !states) return fail(DUST_ERR_INVALID, "null argument");
   if (flags & (DUST_EPS_F16 | DUST_STORE_F16)) return fail(DUST_ERR_UNSUPPORTED, "the batched SVMPC tick has no binary16 storage");
   if (flags & DUST_STORE_STATES) return fail(DUST_ERR_UNSUPPORTED, "the batched SVMPC tick does not store its trajectories (DUST_STORE_STATES)");
-  if (n_steps > 0 && c->cfg.dim_p > 0 && !params) return fail(DUST_ERR_INVALID, "params_sampling is on: pass [B][n_steps][M][P] parameter samples");
-  if (c->cfg.dim_p == 0 && params) return fail(DUST_ERR_INVALID, "parameter rows without uncertain parameters (dim_p = 0)");
+  if (!from_prior) {
+    if (n_steps > 0 && c->cfg.dim_p > 0 && !params) return fail(DUST_ERR_INVALID, "params_sampling is on: pass [B][n_steps][M][P] parameter samples");
+    if (c->cfg.dim_p == 0 && params) return fail(DUST_ERR_INVALID, "parameter rows without uncertain parameters (dim_p = 0)");
+  }
   if (do_forward && n_steps == 0 && !b->have_costs) return fail(DUST_ERR_STATE, "forward() needs the costs of a previous optimize step");
-  TRY(svb_check(c));
+  return svb_check(c);
+}
+
+// The caller's host rows -> the batch's device buffers (eps, params: either may be NULL); *eps_dev: where the kernel finds the noise, or
+// NULL (drawn on the device).  The copies wait for the stream: the caller owns the host buffers.
+static int svb_stage(dust_svmpc_batch *b, int n_steps, const void *eps, const float *params, int flags, const float **eps_dev) {
+  dust_ctx *c = b->c;
   const size_t B = (size_t)b->B, N = (size_t)c->N, S = (size_t)c->S, D = (size_t)c->D, M = (size_t)c->M, P = (size_t)c->cfg.dim_p;
   HIP_TRY(hipSetDevice(c->cfg.device));
-  const float *eps_dev = nullptr;
+  *eps_dev = nullptr;
   if (n_steps > 0 && eps) {
-    if (flags & DUST_PTR_DEVICE) eps_dev = static_cast<const float *>(eps);
+    if (flags & DUST_PTR_DEVICE) *eps_dev = static_cast<const float *>(eps);
     else {
       const size_t n = B * (size_t)n_steps * S * N * D;
       TRY(ensure(&b->eps, &b->eps_cap, n));
       TRY(h2d(c, b->eps, eps, n * sizeof(float)));
-      eps_dev = b->eps;
+      *eps_dev = b->eps;
     }
   }
   if (n_steps > 0 && params) {
@@ -5792,6 +5800,16 @@ static int svb_launch(dust_svmpc_batch *b, const float *states, int n_steps, con
     TRY(ensure(&b->params, &b->params_cap, n));
     TRY(h2d(c, b->params, params, n * sizeof(float)));
   }
+  return DUST_OK;
+}
+
+// States and mask through the next pinned slot, the kernel's arguments and the ONE launch; nothing waits for the device.  params_dev: the
+// staged parameter rows or NULL; prior: the filters the PRIOR instances draw their rows from, or NULL
+static int svb_go(dust_svmpc_batch *b, const float *states, int n_steps, const float *eps_dev, const float *params_dev, int flags,
+                  const unsigned char *active, bool do_forward, const dust::SvbPrior *prior) {
+  dust_ctx *c = b->c;
+  const size_t B = (size_t)b->B;
+  HIP_TRY(hipSetDevice(c->cfg.device));
   {  // states [B][ds] and / or the mask -> the next pinned slot, on the context's stream; nobody waits
     unsigned char *hb;
     TRY(b->in.next(&hb));
@@ -5848,7 +5866,7 @@ static int svb_launch(dust_svmpc_batch *b, const float *states, int n_steps, con
   k.seeds = b->seeds;
   k.active = active ? b->in.dev + B * 8 * sizeof(float) : nullptr;
   k.eps = eps_dev;
-  k.params = (n_steps > 0 && params) ? b->params : nullptr;
+  k.params = params_dev;
   k.a_seq = c->a_seq;
   k.theta = b->theta;
   k.mu = b->mu;
@@ -5875,17 +5893,28 @@ static int svb_launch(dust_svmpc_batch *b, const float *states, int n_steps, con
   const size_t lds = svmpc_batch_lds_bytes(c->N, c->D, c->M);
   {
     Prof pr(c, DUST_K_SVMPC_BATCH);
-    auto go = [&](auto kernel) -> int {
+    auto go = [&](auto kernel, const auto &args) -> int {
       if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      kernel<<<b->B, SVB_THREADS, lds, c->stream>>>(k);
+      kernel<<<b->B, SVB_THREADS, lds, c->stream>>>(args);
       HIP_TRY(hipGetLastError());
       return DUST_OK;
     };
-    switch (c->cfg.model) {
-      case DUST_MODEL_PENDULUM: TRY(go(svmpc_batch_kernel<DUST_MODEL_PENDULUM>)); break;
-      case DUST_MODEL_PARTICLE: TRY(go(svmpc_batch_kernel<DUST_MODEL_PARTICLE>)); break;
-      case DUST_MODEL_SKID_STEER: TRY(go(svmpc_batch_kernel<DUST_MODEL_SKID_STEER>)); break;
-      default: TRY(go(svmpc_batch_kernel<DUST_MODEL_CARTPOLE>)); break;
+    auto by_model = [&](auto from_prior, const auto &args) -> int {  // the model's instance of either kernel (svb_instance)
+      constexpr bool PR = decltype(from_prior)::value;
+      switch (c->cfg.model) {
+        case DUST_MODEL_PENDULUM: return go(svb_instance<DUST_MODEL_PENDULUM, PR>(), args);
+        case DUST_MODEL_PARTICLE: return go(svb_instance<DUST_MODEL_PARTICLE, PR>(), args);
+        case DUST_MODEL_SKID_STEER: return go(svb_instance<DUST_MODEL_SKID_STEER, PR>(), args);
+        default: return go(svb_instance<DUST_MODEL_CARTPOLE, PR>(), args);
+      }
+    };
+    if (prior) {
+      SvmpcPriorBatchArgs kp;
+      kp.k = k;
+      kp.pr = *prior;
+      TRY(by_model(std::true_type(), kp));
+    } else {
+      TRY(by_model(std::false_type(), k));
     }
   }
   if (n_steps > 0) {
@@ -5894,6 +5923,15 @@ static int svb_launch(dust_svmpc_batch *b, const float *states, int n_steps, con
   }
   if (do_forward) b->have_forward = true;
   return DUST_OK;
+}
+
+// optimize (n_steps >= 1), forward, or both: every check, the staging of the inputs and the ONE launch
+static int svb_launch(dust_svmpc_batch *b, const float *states, int n_steps, const void *eps, const float *params, int flags,
+                      const unsigned char *active, bool do_forward) {
+  TRY(svb_call_check(b, states, n_steps, params, false, flags, do_forward));
+  const float *eps_dev;
+  TRY(svb_stage(b, n_steps, eps, params, flags, &eps_dev));
+  return svb_go(b, states, n_steps, eps_dev, (n_steps > 0 && params) ? b->params : nullptr, flags, active, do_forward, nullptr);
 }
 
 static int svb_outputs(dust_svmpc_batch *b, const unsigned char *active, float *a_seq, float *p_weights) {

@@ -2036,7 +2036,7 @@ struct dust_mpf_batch {
   std::vector<unsigned char> have_past;
   std::vector<int> opt_t;
   PinnedStage in;      // per-call inputs: MpfEnvIn [B] | prior seeds [B] | SkidLik / CartLik [B] | active mask [B]
-  hipEvent_t ev_ext;   // behind the last work a dual tick put on an AMPPI batch's stream
+  hipEvent_t ev_ext;   // behind the last work a dual tick put on a controller batch's stream (AMPPI or SVMPC)
   long long n_launch, n_calls;
 };
 
@@ -2093,7 +2093,7 @@ static int mpfb_alloc(dust_mpf *inner, int n_env, dust_mpf_batch **out) {
   return DUST_OK;
 }
 
-// work a dual tick left on an AMPPI batch's stream comes first; the filters' own entries are synchronous on their own stream
+// work a dual tick left on a controller batch's stream comes first; the filters' own entries are synchronous on their own stream
 static int mpfb_settle(dust_mpf_batch *mb) {
   HIP_TRY(hipSetDevice(mb->m->cfg.device));
   HIP_TRY(hipEventSynchronize(mb->ev_ext));
@@ -2452,6 +2452,66 @@ extern "C" int dust_amppi_dual_batch_tick(dust_amppi_batch *b, dust_mpf_batch *m
   if (bw_dev) TRY(rows_d2h(b->B, c->stream, bw_used, mb->bw, 1, active));
   if (roll_steps > 0) TRY(batch_roll_launch(b, roll_steps, active));  // (dust_amppi_batch_roll on the mask this call has staged already)
   HIP_TRY(hipEventRecord(mb->ev_ext, c->stream));  // (the filters' own entries wait for it on the host)
+  if (copies) HIP_TRY(hipStreamSynchronize(c->stream));
+  return DUST_OK;
+}
+
+// One control period of the DuSt-MPC loop (simulations.py:104-138) for B environments in one call (B x dust_dual_tick): on the SVMPC
+// batch's stream, in launch order and without an event or a wait in between - the filters' update for (actions_prev[b], states[b])
+// (skipped when actions_prev is NULL; mpf_bw <= 0: Silverman's rule per environment, on the device), then ONE launch of
+// svmpc_prior_batch_kernel: n_steps SVGD iterations, whose dynamics samples every workgroup draws from its environment's refreshed prior
+// (row it M + m of dust_mpf_prior_sample(filter b, n_steps M, prior_seeds[b])), and forward().  Recorded noise from the host is staged
+// AHEAD of the filters' launches (that copy waits for the stream).  The number of launches does not depend on B.  An environment with
+// active[b] = 0 keeps everything on both sides, and its output rows are not written.  With every output NULL the call returns without
+// waiting for the device.
+extern "C" int dust_svmpc_dual_batch_tick(dust_svmpc_batch *b, dust_mpf_batch *mb, const float *states, const float *actions_prev, int n_steps,
+                                          const void *eps, int flags, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds,
+                                          const unsigned char *active, float *a_seq, float *p_weights, float *params_out, float *bw_used) {
+  if (!b || !mb || !states) return fail(DUST_ERR_INVALID, "null argument");
+  if (n_steps < 1 || mpf_steps < 0) return fail(DUST_ERR_INVALID, "bad step counts");
+  dust_ctx *c = b->c;
+  dust_mpf *m = mb->m;
+  TRY(svb_call_check(b, states, n_steps, nullptr, true, flags, true));  // (sigma-point weights among it: no batched sigma rollouts)
+  TRY(dual_pair_check(c, m));
+  if (b->B != mb->B) return fail(DUST_ERR_INVALID, "the SVMPC batch has %d environments, the filter batch %d", b->B, mb->B);
+  if (!prior_seeds) return fail(DUST_ERR_INVALID, "null argument: the draws from the filters' priors need prior_seeds [B]");
+  TRY(mpfb_limits(m, mb->B));
+  if (actions_prev) TRY(mpfb_update_check(mb, actions_prev, states, mpf_steps, active));
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  TRY(settle_pending(c));
+  const size_t B = (size_t)b->B, N = (size_t)c->N, D = (size_t)c->D, prow = (size_t)n_steps * (size_t)c->M * (size_t)m->P;
+  // (reallocations free behind the device's queued work; they happen in the first period only)
+  if (params_out) TRY(ensure(&b->params, &b->params_cap, B * prow));
+  if (actions_prev) TRY(mpfb_gn_room(mb, mpf_steps));
+  const float *eps_dev;
+  TRY(svb_stage(b, n_steps, eps, nullptr, flags, &eps_dev));
+  HIP_TRY(hipStreamWaitEvent(c->stream, mb->ev_ext, 0));  // (another batch's tick on these filters: its stream first, without a host wait)
+  MpfbRows rows;
+  TRY(mpfb_enqueue(mb, c->stream, actions_prev != nullptr, actions_prev, states, mpf_bw, mpf_steps, active, prior_seeds, rows));
+  mb->n_calls++;
+  dust::SvbPrior pr;
+  memset(&pr, 0, sizeof pr);
+  pr.means = mb->x;
+  pr.K = m->Mp;
+  pr.P = m->P;
+  pr.bwv = mb->prior_bwv;
+  pr.seeds = mpfb_seeds_dev(mb);
+  pr.params_out = params_out ? b->params : nullptr;
+  // (a REFUSAL cannot come from here on: every check ran above.  A runtime error of svb_go - a pinned slot, a failed launch - leaves the
+  // filters' update enqueued without mpfb_commit: their host rows (loc / past / opt_t) then lag the device, as under
+  // dust_amppi_dual_batch_tick; such an error is not recoverable for the pair)
+  TRY(svb_go(b, states, n_steps, eps_dev, nullptr, flags, active, true, &pr));
+  mpfb_commit(mb, rows);  // (every launch of the period is enqueued)
+  const bool bw_dev = bw_used && actions_prev && !(mpf_bw > 0.f);
+  if (bw_used && !bw_dev)
+    for (size_t e = 0; e < B; ++e)
+      if (!active || active[e]) bw_used[e] = actions_prev ? mpf_bw : 0.f;
+  const bool copies = a_seq || p_weights || params_out || bw_dev;
+  if (a_seq) TRY(rows_d2h(b->B, c->stream, a_seq, b->a_seq_out, D, active));
+  if (p_weights) TRY(rows_d2h(b->B, c->stream, p_weights, b->pw, N, active));
+  if (params_out) TRY(rows_d2h(b->B, c->stream, params_out, b->params, prow, active));
+  if (bw_dev) TRY(rows_d2h(b->B, c->stream, bw_used, mb->bw, 1, active));
+  HIP_TRY(hipEventRecord(mb->ev_ext, c->stream));  // (the filters' own entries, and another batch's tick on these filters, wait for it)
   if (copies) HIP_TRY(hipStreamSynchronize(c->stream));
   return DUST_OK;
 }

@@ -6,7 +6,8 @@
 // MultiDISCO._rollout / _compute_cost / forward disco.py:139-394, SVMPC.get_weights / roll / update_prior / forward svmpc.py:128-200.
 //
 // One SVGD iteration, phases separated by workgroup barriers only:
-//   0  particles, prior means, mixture log-weights and the M dynamics samples' coefficients -> LDS
+//   0  particles, prior means, mixture log-weights and the M dynamics samples' coefficients -> LDS (svmpc_prior_batch_kernel: lane m < M
+//      first draws sample m from its environment's dynamics filter, the stream of mpf.hpp mpf_sample_kernel)
 //   A  actions[s][n] = theta[n] + chol_a eps[s][n] (eps recorded, or Philox: the lone kernels' counter layout - block j >> 3 of row
 //      s N + n, common.hpp philox_normal8) -> the environment's action rows in device memory;
 //      prior logits[i][k] = logmix[k] - |theta_i - mu_k|^2 / (2 sigma_p^2) -> LDS
@@ -264,8 +265,41 @@ __device__ __forceinline__ void svb_prior_logits(const SvmpcBatchArgs &a, const 
   }
 }
 
-template <int MODEL>
-__global__ __launch_bounds__(SVB_THREADS) void svmpc_batch_kernel(const SvmpcBatchArgs a) {
+// Where svmpc_prior_batch_kernel finds its dynamics samples (dust_svmpc_dual_batch_tick): the B filters' particles and prior bandwidths,
+// read in place - the batched filter kernel wrote them just ahead on the same stream - and the Philox key of every environment's draws
+struct SvbPrior {
+  const float *means;     // [B][K][P]
+  int K, P;
+  const float *bwv;       // [B][4]
+  const uint64_t *seeds;  // [B]
+  float *params_out;      // [B][n_steps][M][P] or nullptr
+};
+struct SvmpcPriorBatchArgs {
+  SvmpcBatchArgs k;
+  SvbPrior pr;
+};
+
+// Row i = it M + m of mpf.prior.sample([n_steps M]) of environment env's filter as mpf_sample_kernel (mpf.hpp) draws it under the key
+// seeds[env] - the same counters, the same operations in the same order - into row[4]
+__device__ __forceinline__ void svb_draw_row(const SvmpcBatchArgs &a, const SvbPrior &pri, const int env, const int it, const int m, float *row) {
+  const uint32_t i = (uint32_t)(it * a.M + m);
+  const uint64_t key = pri.seeds[env];
+  uint32_t r[4];
+  philox4x32_10(i, 0x6d7066u, 0u, 0u, (uint32_t)key, (uint32_t)(key >> 32), r);
+  const int kc = (int)(((unsigned long long)r[0] * (unsigned long long)pri.K) >> 32);
+  float zp[4];
+  philox_normal4(key, i, 0x6d7067u, 1u, 0u, zp);
+  const float *mean = pri.means + ((size_t)env * (size_t)pri.K + (size_t)kc) * (size_t)pri.P;
+  const float *bw = pri.bwv + (size_t)env * 4;
+#pragma unroll
+  for (int p = 0; p < 4; ++p)
+    if (p < pri.P) row[p] = mean[p] + bw[p] * zp[p];
+}
+
+// The tick of environment blockIdx.x.  PRIOR: the dynamics samples are drawn in phase 0 from the environment's filter (`pri`), not read
+// from a.params; nothing else differs.
+template <int MODEL, bool PRIOR>
+__device__ __forceinline__ void svb_body(const SvmpcBatchArgs &a, const SvbPrior *pri) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int DS = SvbDims<MODEL>::DS;
   constexpr int T = SVB_THREADS;
@@ -313,6 +347,14 @@ __global__ __launch_bounds__(SVB_THREADS) void svmpc_batch_kernel(const SvmpcBat
 
   for (int it = 0; it < a.n_steps; ++it) {
     // ---- 0: stage
+    if constexpr (PRIOR) {
+      // one lane per dynamics sample (M <= SVB_MAX_M < T).  The row waits in the partial sums' LDS - idle in this phase - for svb_coef,
+      // which indexes it by the parameters' columns (a register row would go to scratch); the caller's copy leaves behind the barrier.
+      // (The argument block keeps ~380 scalars in spilled lanes, and the register allocator is sensitive to what this phase adds: with
+      // the copy written here, or with the key forced into vector registers, it leaves 36 - 68 bytes of never-used stack slots behind
+      // in one or two of the instances.  tests/test_svmpc_dual_batch_cpu.py holds all four to a private segment of 0.)
+      if (tid < M) svb_draw_row(a, *pri, env, it, tid, part + tid * 4);
+    }
     for (int i = tid; i < ND; i += T) {
       const float v = g_th[i];
       th[i] = v;
@@ -320,7 +362,7 @@ __global__ __launch_bounds__(SVB_THREADS) void svmpc_batch_kernel(const SvmpcBat
     }
     for (int i = tid; i < N; i += T) lmx[i] = a.logmix[(size_t)env * N + i];
     for (int m = tid; m < M; m += T) {
-      const float *prow = a.params ? a.params + (((size_t)env * a.n_steps + it) * M + m) * a.P : nullptr;
+      const float *prow = PRIOR ? part + m * 4 : (a.params ? a.params + (((size_t)env * a.n_steps + it) * M + m) * a.P : nullptr);
       float cf[SVB_COEF];
       svb_coef<MODEL>(a, prow, cf);
       constexpr int NC = (MODEL == DUST_MODEL_PENDULUM || MODEL == DUST_MODEL_PARTICLE) ? 2 : (MODEL == DUST_MODEL_SKID_STEER ? 3 : SVB_COEF);
@@ -328,6 +370,12 @@ __global__ __launch_bounds__(SVB_THREADS) void svmpc_batch_kernel(const SvmpcBat
       for (int q = 0; q < NC; ++q) coef[m * SVB_COEF + q] = cf[q];
     }
     svb_sync();
+    if constexpr (PRIOR) {  // the drawn rows for the caller: [n_steps][M][P] of this environment, M P <= 256 floats
+      if (pri->params_out && tid < M * pri->P) {
+        const int m = tid / pri->P, p = tid - m * pri->P;
+        pri->params_out[(((size_t)env * a.n_steps + it) * M + m) * (size_t)pri->P + p] = part[m * 4 + p];
+      }
+    }
 
     // ---- A: actions, prior logits
     if (a.philox) {
@@ -615,6 +663,23 @@ __global__ __launch_bounds__(SVB_THREADS) void svmpc_batch_kernel(const SvmpcBat
     ctr[1] = ctr_iter;
     ctr[2] = opt_t;
   }
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(SVB_THREADS) void svmpc_batch_kernel(const SvmpcBatchArgs a) {
+  svb_body<MODEL, false>(a, nullptr);
+}
+// ... coupled to B dynamics filters (dust_svmpc_dual_batch_tick): in iteration `it`, lane m < M draws row it M + m of
+// dust_mpf_prior_sample(filter env, n_steps M, seeds[env]) itself - no parameter buffer, no launch besides the tick's
+template <int MODEL>
+__global__ __launch_bounds__(SVB_THREADS) void svmpc_prior_batch_kernel(const SvmpcPriorBatchArgs kp) {
+  svb_body<MODEL, true>(kp.k, &kp.pr);
+}
+// the instance of either kernel for a model (the host's launch names the model once for both)
+template <int MODEL, bool PRIOR>
+static constexpr auto svb_instance() {
+  if constexpr (PRIOR) return &svmpc_prior_batch_kernel<MODEL>;
+  else return &svmpc_batch_kernel<MODEL>;
 }
 
 // dust_svmpc_batch_set(THETA): while an environment's prior means alias its particles they follow them (svgd.py:87); a new parameter

@@ -691,6 +691,22 @@ int dust_mpf_batch_optimize(dust_mpf_batch *batch, const float *actions, const f
 int dust_amppi_dual_batch_tick(dust_amppi_batch *batch, dust_mpf_batch *mpf, const float *states, const float *actions_prev, const float *actions,
                                int flags, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds, int roll_steps, const unsigned char *active,
                                float *costs, float *omega, float *a_seq, float *params_out, float *bw_used);
+/* One control period of the DuSt-MPC loop for B environments in one call = B x dust_dual_tick, on the SVMPC batch's stream in launch
+ * order with no event, no synchronisation and no host round trip between the filters and the ticks; the number of kernel launches does
+ * not depend on B.  states [B][ds]; actions_prev [B][da] or NULL (no filter update: the first period); mpf_bw <= 0: Silverman's rule per
+ * environment on the device; then ONE launch of n_steps SVGD iterations and forward() (svmpc_prior_batch_kernel, counted under
+ * DUST_K_SVMPC_BATCH).  In iteration `it` the dynamics sample m of environment b is row it M + m of
+ * dust_mpf_prior_sample(filter b after its update, n_steps M, prior_seeds[b]), drawn inside the tick's kernel.  eps
+ * [B][n_steps][S][N][H][da] on the host, on the device with DUST_PTR_DEVICE, or NULL (drawn on the device from every environment's own
+ * stream); DUST_SVMPC_BATCH_KEEP_ACTIONS as dust_svmpc_batch_tick.  Outputs, each may be NULL: a_seq [B][H][da] (the best particle
+ * before the roll), p_weights [B][N], params_out [B][n_steps][M][P], bw_used [B] (0: no update; mpf_bw when that was given).  An
+ * environment with active[b] = 0 keeps everything on both sides; its output rows are not written.  With every output NULL the call
+ * returns without waiting for the device.  Refused before anything is staged or launched: what dust_svmpc_batch_tick refuses (sigma-point
+ * weights among it: a batch does not run the sigma mode of dust_dual_tick), what dust_dual_tick refuses of a controller / filter pair,
+ * what dust_mpf_batch_optimize refuses, batches of different n_env, NULL prior_seeds, n_steps < 1, mpf_steps < 0. */
+int dust_svmpc_dual_batch_tick(dust_svmpc_batch *batch, dust_mpf_batch *mpf, const float *states, const float *actions_prev, int n_steps,
+                               const void *eps, int flags, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds,
+                               const unsigned char *active, float *a_seq, float *p_weights, float *params_out, float *bw_used);
 
 #ifdef __cplusplus
 }
