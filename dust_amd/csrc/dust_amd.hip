@@ -1240,13 +1240,14 @@ extern "C" int dust_get_theta(dust_ctx *c, float *theta) {
 }
 extern "C" int dust_set_prior(dust_ctx *c, const float *means, const float *w) {
   if (!c || !means) return fail(DUST_ERR_INVALID, "null argument");
+  if (w)  // (refused before anything is written: a refused call leaves the prior as it was)
+    for (int i = 0; i < c->N; ++i)
+      if (!(w[i] >= 0.f)) return fail(DUST_ERR_INVALID, "mixture weights must be >= 0 (torch.distributions.Categorical)");
   if (c->graph_exec || c->graph_exec_alt) graph_drop(c);
   HIP_TRY(hipSetDevice(c->cfg.device));
   TRY(h2d(c, c->mu, means, (size_t)c->N * c->D * sizeof(float)));
   c->mu_aliased = false;
   if (w) {
-    for (int i = 0; i < c->N; ++i)
-      if (!(w[i] >= 0.f)) return fail(DUST_ERR_INVALID, "mixture weights must be >= 0 (torch.distributions.Categorical)");
     TRY(h2d(c, c->mixw, w, c->N * sizeof(float)));
   } else {
     std::vector<float> ones((size_t)c->N, 1.0f);
@@ -5084,6 +5085,7 @@ extern "C" int dust_disco_step(dust_ctx *c, int strategy, int steps, const float
   }
   s.a_mat = c->a_mat;
   s.a_seq = c->a_seq;
+  TRY(ensure(&c->tmp, &c->tmp_cap, (size_t)steps * c->da));  // (dust_create sizes tmp for S * N floats: fewer than steps * da for a small set)
   s.next = c->tmp;
   disco_step_kernel<<<1, 1024, c->D * sizeof(float), c->stream>>>(s);
   HIP_TRY(hipGetLastError());

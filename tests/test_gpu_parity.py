@@ -504,6 +504,19 @@ def test_seeded_vs_oracle(model, N, S, M, H):
         assert elemerr(phi, ref_phi) < TOL, kernel
         if kernel == "K2":
             assert relerr(c.get_bandwidths(), o.phi_k2(theta, sc)[1]) < TOL
+        # forward: the oracle fed the DEVICE's costs (stage-local), at test_forward_vs_reference's tolerances
+        fw = o.forward(costs, theta, mu, np.ones(N, np.float32), sg, alpha)
+        a_seq, pw = c.svmpc_forward()
+        ll, lp = c.get_log_weights()
+        assert elemerr(ll, fw["log_l"]) < TOL and elemerr(lp, fw["log_p"]) < TOL, kernel
+        assert relerr(pw, fw["p_weights"]) < 5e-3
+        srt = np.sort(fw["p_weights"])
+        if srt[-1] - srt[-2] > 2 * 5e-3 * srt[-1]:  # (a top pair closer than the weights' own tolerance decides nothing)
+            assert int(np.argmax(pw)) == fw["i_star"] and np.array_equal(a_seq, fw["a_seq"])
+        assert relerr(c.get_theta(), fw["theta"]) < 1e-6
+        means, probs = c.get_prior()
+        assert relerr(means, fw["mu"]) < 1e-6
+        assert relerr(probs, fw["mix"] / fw["mix"].sum()) < 5e-3
 
 
 @pytest.mark.parametrize("model,N,S,M,H", [("pendulum", 64, 128, 1, 30), ("particle", 32, 64, 2, 20), ("pendulum", 33, 40, 3, 7)])
