@@ -14,14 +14,17 @@
 //   * one 1024-lane workgroup per CU, N / 4 workgroups, all resident (start barrier below);
 //   * waves 0-7 (R): rollouts of the 4 particles, lane = action sample (tick_owner's arithmetic), then - wave-locally - their
 //     samples' softmax pieces and weighted sums; policy noise kept in an LDS tile, every wave redrawing the rows of its own samples
-//     (Philox) half while the score hop is in flight and half while the owner lanes update the particles;
+//     (Philox) half while the score hop is in flight and half while the owner lanes update the particles (waves 0-1 carry the owner
+//     lanes and are busy then: pair waves 8-9 draw that half of their rows for them);
 //   * waves 8-15 (P): the theta-only half of SVMPC.phi in two passes over all N keys (exact differences to two query rows per
 //     wave): the PRIOR pass underneath the rollouts - lane = (key of a 32-key step, column half), squared distances -> LDS, the
 //     prior's softmax-weighted sum and mass in registers (t2_prior_pass_w) - and, while the score rows travel, the STEIN pass -
 //     lane = (key of 16, column quarter), k_ij -> LDS in place of the distances, repulsion in registers (t2_pair_pass).  Sums over
 //     the key lanes leave a wave through the butterflies of tick2_reduce.hpp;
-//   * the owner lanes (waves 8-9, lane = (particle, column)) finish the score rows behind the prior pass (at wave priority 3:
-//     every other workgroup waits for them) and publish them; after the score hop all 16 waves stream the score rows:
+//   * the owner lanes (the 128 lanes of waves 0-1, lane = (particle, column); five values per lane in registers for the tick) finish
+//     the score rows behind the prior pass (at wave priority 3: every other workgroup waits for them) and publish them, while all
+//     eight pair waves are in the Stein pass already - hosted by two pair waves the stage made those two the last to finish the pass,
+//     and barrier B4 waited for them and not for the score arrivals; after the score hop all 16 waves stream the score rows:
 //     sum_j k_ij s_j, then phi and the optimiser step by the owner lanes, who publish the new particles.
 //   The theta hop of iteration k+1 hides under its rollouts (which need only the workgroup's own particles): ONE exposed hop
 //   per iteration.  DESIGN.md 4.R has the timeline (15.9 us per iteration at cfg2) and what was tried around it.
@@ -552,11 +555,11 @@ __global__ __launch_bounds__(T2_NT, 4) void svmpc_tick2_kernel(const Tick2Args f
   if (b == 0)
     for (int t = tid0; t < T2_SETS; t += T2_NT) f->zero_base[(size_t)t * T2_CNT_STRIDE] = 0u;
   if (tid0 == 15 * 64) __hip_atomic_fetch_add(cnt_start + (size_t)sh * T2_CNT_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  T2_TL(0, 120);
+  T2_TL(2, 120);  // (wave 2, as every stamp that would sit in front of a publish of the owner lanes on waves 0-1: its store would be drained there)
 
-  // owner lanes: waves 8-9, lane -> (particle op, column od); they keep theta / a_mat / Adam moments in registers for the tick
-  const bool isown = wave == 8 || wave == 9;
-  const int ol = tid0 - 512, op = (ol >> 5) & 3, od = ol & 31;
+  // owner lanes: waves 0-1, lane -> (particle op, column od); they keep theta / a_mat / Adam moments in registers for the tick
+  const bool isown = wave == 0 || wave == 1;
+  const int ol = tid0, op = (ol >> 5) & 3, od = ol & 31;
   const bool ownv = isown && od < D;
   const size_t no = (size_t)(n_first + op) * D + (ownv ? od : 0);
   float thv = 0.f, amv = 0.f, adm = 0.f, adv = 0.f, ad2 = 0.f;  // (the optimiser's state slots: adm, adv, ad2)
@@ -592,12 +595,12 @@ __global__ __launch_bounds__(T2_NT, 4) void svmpc_tick2_kernel(const Tick2Args f
   }
   lds_barrier();  // orders the flag reset against the first noise staging; the loads above stay in flight across it
 
-  // publish rows of the workgroup's particles held in LDS ([4][32]) as whole 128-byte lines: waves 8 / 9 take two rows each
+  // publish rows of the workgroup's particles held in LDS ([4][32]) as whole 128-byte lines: waves 0 / 1 (the owner lanes') take two rows each
   auto publish_rows = [&](const float *src, const float *dst, unsigned int *lines) {
     const __amdgpu_buffer_rsrc_t r = t2_rsrc(dst, N * T2_ROW);
     const int lane = tid0 & 63;
     if (lane < 16) {
-      const int pl = (wave - 8) * 2 + (lane >> 3), c = lane & 7;
+      const int pl = wave * 2 + (lane >> 3), c = lane & 7;
       const float4 v = *reinterpret_cast<const float4 *>(&src[pl * T2_ROW + 4 * c]);
       t2_st16(r, ((n_first + pl) * T2_ROW + 4 * c) * 4, v4f{v.x, v.y, v.z, v.w});
     }
@@ -805,7 +808,11 @@ __global__ __launch_bounds__(T2_NT, 4) void svmpc_tick2_kernel(const Tick2Args f
   const float lm_ref = wave_max((tid0 & 63) < T2_NT / 64 ? wred[tid0 & 63] : -INFINITY);
   const bool same_w = (f->alpha * f->temp == 1.0f);
   const int lane0 = tid0 & 63;
-  if (own_first && wave < 8) draw_own_rows(f, 0, wave, lane0);  // (the pair waves are on their way to the first hand-off meanwhile)
+  // (the pair waves are on their way to the first hand-off meanwhile.  Tried: pair wave 8 + w draws half of wave w's rows here and
+  //  raises an LDS word that wave w sleeps on in front of its rollouts - the rollouts end 0.4 us earlier, wave 15 sees generation 0
+  //  2.8 us later, and barrier B1 of iteration 0 falls where it fell: the prior pass decides it, not the rollouts.  No gain, not kept:
+  //  profiles/tick2_owner_waves.txt)
+  if (own_first && wave < 8) draw_own_rows(f, 0, wave, lane0);
 
   const int wave0 = wave;
   for (int k = 0; k < f->n_iters; ++k) {
@@ -816,8 +823,8 @@ __global__ __launch_bounds__(T2_NT, 4) void svmpc_tick2_kernel(const Tick2Args f
     const int tid = opaque(tid0);
     const int wave = opaque_s(wave0);
     const int lane = tid & 63;
-    const bool isown = wave == 8 || wave == 9;
-    const int ol = tid - 512, op = (ol >> 5) & 3, od = ol & 31;
+    const bool isown = wave == 0 || wave == 1;
+    const int ol = tid, op = (ol >> 5) & 3, od = ol & 31;
     const bool ownv = isown && od < D;
     const size_t no = (size_t)(n_first + op) * D + (ownv ? od : 0);
     T2_TL(0, 16 * k + 0);
@@ -1095,7 +1102,7 @@ __global__ __launch_bounds__(T2_NT, 4) void svmpc_tick2_kernel(const Tick2Args f
     }
     wg_sync();  // B1
     f = t2_args();
-    T2_TL(0, 16 * k + 4);
+    T2_TL(2, 16 * k + 4);
     if (sig[0] == 2u || (k == 0 && sig[3] == 2u)) {  // (uniform: no workgroup wrote anything)
       if (b == 0 && tid0 == 0) {
         // an armed launch whose state never came (cancelled by the host, or the bound ran out) counts as one that did not start
@@ -1104,9 +1111,12 @@ __global__ __launch_bounds__(T2_NT, 4) void svmpc_tick2_kernel(const Tick2Args f
       }
       return;
     }
-    // ================= phase 4: score rows out (waves 8-9) | score arrivals (wave 10) | next noise (R) =================
+    // ================= phase 4: score rows out (waves 0-1) | Stein pass (P) | score arrivals (wave 10) | next noise (R) =================
     // The owner lanes finish both halves of the score themselves (no barrier between the prior pass and the published row): grad_pri from
     // the pass partials of the four waves that hold the query, grad_lik from the two R waves' pieces of the particle's sample softmax.
+    // They ride rollout waves 0-1, whose only other work in this phase - their share of the next noise - has until barrier B4: all eight
+    // pair waves enter the Stein pass straight behind B1 (on waves 8-9 the stage held two of the pass's units back by its own length,
+    // and those two decided when B4 fell).
     float gs_keep = 0.f, gp_keep = 0.f;
     if (isown) {
       DUST_PRIO(T2_PRIO_OWNERSTAGE);  // the score rows are what every other workgroup waits for: ahead of the Stein pass and the noise draw
@@ -1151,7 +1161,7 @@ __global__ __launch_bounds__(T2_NT, 4) void svmpc_tick2_kernel(const Tick2Args f
       scl[op * T2_ROW + od] = ownv ? gs + gp_keep : 0.f;
       publish_rows(scl, f->sq + (size_t)k * N * T2_ROW, cnt_score);
       DUST_PRIO(0);
-      T2_TL(8, 16 * k + 7);
+      T2_TL(0, 16 * k + 7);
       if (ownv && k + 1 == f->n_iters) {
         f->score[no] = gs_keep + gp_keep;
         f->grad_lik[no] = gs_keep;
@@ -1159,9 +1169,10 @@ __global__ __launch_bounds__(T2_NT, 4) void svmpc_tick2_kernel(const Tick2Args f
       }
     }
     if (wave >= 8) {  // the Stein half of the theta-only work, while the score rows travel
-      // (tried: the owner waves' two units - they start 1.7 us late and finish last - cut in four and handed to the rollout waves behind
-      //  their noise draw, with the owner waves idle: +4.5 us per tick, the workgroups drift apart; an idle wave polling the score
-      //  counters from the moment the rows are published: the hop takes 5.8 instead of 2.5 us - the polls sit on the arrivals' lines)
+      // (tried, while the owner lanes sat on waves 8-9: their two units - they started 1.7 us late and finished last - cut in four and
+      //  handed to the rollout waves behind their noise draw, with the owner waves idle: +4.5 us per tick, the workgroups drift apart;
+      //  an idle wave polling the score counters from the moment the rows are published: the hop takes 5.8 instead of 2.5 us - the
+      //  polls sit on the arrivals' lines)
       float rb[4];
       DUST_PRIO(T2_PRIO_STEIN);
       if (N != f->steps * 64) t2_pair_pass<MODE, T2_PASS_STEIN, true>(f, k, th, ksl, lml, wave - 8, lane, lm_ref, rb);
@@ -1172,6 +1183,8 @@ __global__ __launch_bounds__(T2_NT, 4) void svmpc_tick2_kernel(const Tick2Args f
       T2_TL(15, 16 * k + 6);
     }
     if (wave == 10) {
+      // (the first poll comes as soon as the wave's Stein unit ends; held back by s_sleep 6 or 14 it measured the same:
+      //  profiles/tick2_owner_waves.txt)
       t2_poll(cnt_score + rep_off, 2u, (unsigned int)(k + 1), G, lane, tflag);
       T2_TL(10, 16 * k + 8);
     } else if (wave < 8) {
@@ -1233,8 +1246,8 @@ __global__ __launch_bounds__(T2_NT, 4) void svmpc_tick2_kernel(const Tick2Args f
     }
     wg_sync();  // B5
     f = t2_args();
-    T2_TL(0, 16 * k + 12);
-    // ================= phase 6: phi, optimiser step, theta rows out (waves 8-9) =================
+    T2_TL(2, 16 * k + 12);
+    // ================= phase 6: phi, optimiser step, theta rows out (waves 0-1) =================
     float phi_keep = 0.f;
     if (isown) {
       float sa = 0.f;
@@ -1261,12 +1274,13 @@ __global__ __launch_bounds__(T2_NT, 4) void svmpc_tick2_kernel(const Tick2Args f
     }
     if (isown) {
       if (k + 1 < f->n_iters || f->do_forward) publish_rows(th, f->xq + (size_t)(k + 1) * N * T2_ROW, cnt_theta);
-      T2_TL(8, 16 * k + 13);
+      T2_TL(0, 16 * k + 13);
       if (ownv && k + 1 == f->n_iters) f->phi[no] = phi_keep;
-    } else if (T2_NOISE_SPLIT && wave < 8 && k + 1 < f->n_iters && f->eps == nullptr) {
+    } else if (T2_NOISE_SPLIT && wave < 10 && k + 1 < f->n_iters && f->eps == nullptr) {
       // the second half of the next iteration's noise, by the rollout waves, while the owner lanes update and publish: in phase 4 the whole
-      // draw competed with the Stein pass for issue slots, here nothing else runs
-      draw_own_rows(f, k + 1, wave, lane, 1);
+      // draw competed with the Stein pass for issue slots, here nothing else runs.  Waves 0-1 are the ones updating and publishing: pair
+      // waves 8-9 stand in for them (Philox is counter-addressed: the same rows; barrier B6 orders the tile for the rollouts)
+      draw_own_rows(f, k + 1, wave < 8 ? wave : wave - 8, lane, 1);
     }
     wg_sync();  // B6  (tried twice: the barrier in front of the publish, so that the rollout waves start ~1 us earlier - +1.3 us per tick; with the
                 // publish at wave priority 3: no gain either)

@@ -36,16 +36,16 @@ lib.dust_debug_stamps(c._h, -(2048 * 32), buf.ctypes.data_as(C.c_void_p))
 t = buf.reshape(2048, 128).astype(np.int64)[:W]
 t0 = t[:, 120][t[:, 120] > 0].min()
 us = lambda x: (x - t0) / 100.0
-names = {0: "iteration start (w0)", 1: "rollouts done (w0)", 2: "theta arrived (w8)", 3: "prior pass done (w8)", 15: "prior pass done (w15)", 4: "after B1",
-         5: "weighted sums done (w0)", 7: "score rows published (w8)", 8: "score arrivals seen (w10)", 9: "next noise drawn (w0)",
-         11: "Stein pass done (w8)", 6: "Stein pass done (w15)", 10: "after B4", 12: "after B5: K x score", 13: "theta rows published (w8)", 14: "after B6"}
+names = {0: "iteration start (w0)", 1: "rollouts done (w0)", 2: "theta arrived (w8)", 3: "prior pass done (w8)", 15: "prior pass done (w15)", 4: "after B1 (w2)",
+         5: "weighted sums done (w0)", 7: "score rows published (w0)", 8: "score arrivals seen (w10)", 9: "next noise drawn (w0, behind its owner stage)",
+         11: "Stein pass done (w8)", 6: "Stein pass done (w15)", 10: "after B4", 12: "after B5: K x score (w2)", 13: "theta rows published (w0)", 14: "after B6"}
 order = [0, 2, 1, 5, 3, 15, 4, 7, 9, 11, 6, 8, 10, 12, 13, 14]
 def show(label, col):
     v = t[:, col]
     v = v[v > 0]
     if len(v):
         print("   %-34s median %7.2f  min %7.2f  max %7.2f" % (label, float(np.median(us(v))), us(v.min()), us(v.max())))
-show("launch start", 120)
+show("launch start (w2)", 120)
 show("before the first noise", 122)
 show("after the initial barrier", 121)
 for k in range(IT):
