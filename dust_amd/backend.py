@@ -595,7 +595,8 @@ class Context:
     def svmpc_batch(self, n_envs, seeds=None):
         """`n_envs` independent SVMPC controllers of this context's configuration - particles, prior, a_mat, optimiser state and noise
         stream each -, one kernel launch per optimize / forward / tick (dust_svmpc_batch_create): the batch keeps its own copy of the
-        context.  seeds [n_envs] (None: this context's seed + b)."""
+        context.  seeds [n_envs] (None: this context's seed + b).  A skid-steer context with an obstacle weight (set_obstacle_cost)
+        runs the navigation instance on its one map (set_grid; without a map: ERR_STATE)."""
         return SvmpcBatch(self, n_envs, seeds)
 
     def get_costs(self):

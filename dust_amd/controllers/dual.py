@@ -388,7 +388,8 @@ class BatchDualSVMPC:
 
     `mpf` is the prototype: every environment starts from its particles (or from `init_particles[b]`, [B, Mp, P]), optimiser state and
     bandwidths; the first forward()'s states are the observations the first update's predictions start from.  There is no unfused path
-    and no `warm_up`: what the fused call does not take (a sigma-point controller, recorded draws) is refused."""
+    and no `warm_up`: what the fused call does not take (a sigma-point controller, recorded draws) is refused.  The controller's cost
+    is any `BatchSVMPC` runs: a skid-steer `NavigationCost` ticks in svmpc_skid_nav_prior_batch_kernel, one map for the B robots."""
 
     def __init__(self, svmpc, mpf, mpf_bw=None, mpf_steps=20, n_steps=None, seed=0, init_particles=None):
         from ..inference.svmpc import BatchSVMPC

@@ -5545,6 +5545,9 @@ struct dust_svmpc_batch {
   bool have_costs, have_forward, acts_kept;
 };
 
+// the skid-steer tick with the navigation cost family: svmpc_skid_nav_batch_kernel / svmpc_skid_nav_prior_batch_kernel
+static bool svb_nav(const dust_ctx *c) { return c->cfg.model == DUST_MODEL_SKID_STEER && c->skid_w_obs != 0.f; }
+
 // the box of svmpc_batch.hpp
 static int svb_check(const dust_ctx *c) {
   const dust_config &g = c->cfg;
@@ -5557,13 +5560,16 @@ static int svb_check(const dust_ctx *c) {
   if (g.a_reg != 0.f) return fail(DUST_ERR_UNSUPPORTED, "a batched SVMPC tick has no control-cost term: ctrl_penalty = 1 (a_reg = 0), got a_reg = %g", (double)g.a_reg);
   if (g.full_cov) return fail(DUST_ERR_UNSUPPORTED, "a batched SVMPC tick has diagonal covariances only");
   if (c->mw_dev) return fail(DUST_ERR_UNSUPPORTED, "a batched SVMPC tick has no sigma-point rollouts");
-  if (g.model == DUST_MODEL_SKID_STEER && c->skid_w_obs != 0.f) return fail(DUST_ERR_UNSUPPORTED, "a batched SVMPC tick has no navigation cost family");
   if (particle_general(c)) return fail(DUST_ERR_UNSUPPORTED, "a batched SVMPC tick runs Particle with acceleration control and no control-channel noise");
   if (g.roll_strategy == DUST_ROLL_RESAMPLE) return fail(DUST_ERR_UNSUPPORTED, "a batched SVMPC tick rolls with 'repeat' or 'mean' ('resample' draws on the host)");
   if (c->nloc != c->N || comm_active(c)) return fail(DUST_ERR_UNSUPPORTED, "a batched SVMPC tick is not sharded over GPUs");
   if (c->serve_on) return fail(DUST_ERR_UNSUPPORTED, "the context is serving (dust_svmpc_serve_stop first)");
   if (g.model == DUST_MODEL_PARTICLE && g.with_obstacle && !c->grid_bits)
     return fail(DUST_ERR_STATE, "with_obstacle is set but no occupancy grid was supplied (dust_set_grid)");
+  if (svb_nav(c)) {  // the navigation cost family needs its map (skid_nav_args' refusal, ahead of any launch)
+    SkidNav nv;
+    TRY(skid_nav_args(c, nv));
+  }
   return DUST_OK;
 }
 
@@ -5892,7 +5898,11 @@ static int svb_go(dust_svmpc_batch *b, const float *states, int n_steps, const f
   k.a_mix = b->a_mix;
   k.pw = b->pw;
   k.a_seq_out = b->a_seq_out;
-  const size_t lds = svmpc_batch_lds_bytes(c->N, c->D, c->M);
+  const bool nav = svb_nav(c);
+  SkidNav nv;
+  memset(&nv, 0, sizeof nv);
+  if (nav) TRY(skid_nav_args(c, nv));
+  const size_t lds = svmpc_batch_lds_bytes(c->N, c->D, c->M) + (size_t)nv.grid_words * sizeof(uint32_t);  // the map behind the tick's own LDS
   {
     Prof pr(c, DUST_K_SVMPC_BATCH);
     auto go = [&](auto kernel, const auto &args) -> int {
@@ -5910,7 +5920,18 @@ static int svb_go(dust_svmpc_batch *b, const float *states, int n_steps, const f
         default: return go(svb_instance<DUST_MODEL_CARTPOLE, PR>(), args);
       }
     };
-    if (prior) {
+    if (nav && prior) {  // the navigation cost family: instances of their own, in both forms
+      SvmpcNavPriorBatchArgs kp;
+      kp.k = k;
+      kp.pr = *prior;
+      kp.nav = nv;
+      TRY(go(&svmpc_skid_nav_prior_batch_kernel, kp));
+    } else if (nav) {
+      SvmpcNavBatchArgs kn;
+      kn.k = k;
+      kn.nav = nv;
+      TRY(go(&svmpc_skid_nav_batch_kernel, kn));
+    } else if (prior) {
       SvmpcPriorBatchArgs kp;
       kp.k = k;
       kp.pr = *prior;

@@ -13,7 +13,8 @@
 //      prior logits[i][k] = logmix[k] - |theta_i - mu_k|^2 / (2 sigma_p^2) -> LDS
 //   B  grad_pri[i] = sum_k softmax_k(logits[i]) (mu_k - theta_i) / sigma_p^2 -> LDS (lane = (particle, column))
 //   C  the N S M rollouts through the family's own device step and cost functions (common.hpp step_with_cost / term_cost and the
-//      Pendulum's shared-reduction trig of rollout.hpp, skid.hpp skid_step, cartpole.hpp cartpole_step): lane = (sample s, particle n,
+//      Pendulum's shared-reduction trig of rollout.hpp, skid.hpp skid_step - in the navigation instances with w_obs collision() on
+//      every state, skid_rollout_body<false, true>'s arithmetic -, cartpole.hpp cartpole_step): lane = (sample s, particle n,
 //      dynamics group g), the group's samples m = g, g + G, .. in sequence; costs[s][n] = mean over m, the G group partials (doubles
 //      in LDS) added in the order g = 0 .. G - 1
 //   D  per particle (one wave each, round-robin): min and sum of its S costs, w = exp(-alpha (c - min)), omega = exp(-(c - min) /
@@ -47,6 +48,11 @@
 //     coefficients of the M dynamics samples and 16 KiB of partial sums - 135 KiB at N = 64, D = 128 (of 160 KiB), 19 KiB at the demo.
 //   * Particle's occupancy map is read in place (device memory, one map for the whole batch); a copy in LDS, as rollout.hpp keeps up to
 //     16 KiB of it, has not been timed.
+//   * The skid-steer navigation instances (svmpc_skid_nav_batch_kernel / svmpc_skid_nav_prior_batch_kernel) follow skid.hpp instead: a
+//     map of up to 4096 words is staged once per launch into the LDS behind the tick's own (135 KiB + 16 KiB at the corner of the box, of
+//     160 KiB), a larger one - or any map under DUST_NAV_GRID_HBM=1 - is read in place.  Both paths, and the plain instance on the same
+//     shape, HAVE been timed, once (tools/svmpc_batch_time.py skid / skid_nav / skid_nav_hbm at B = 1 .. 256: DESIGN.md section 5 has
+//     the run).  Not measured: what the lookups cost inside phase C (no counters were read), and a per-iteration restaging.
 //   * Phases B and F walk the N x N pairs on the VALU; N <= 64 here, far below where the MFMA passes of stein.hpp pay.
 #pragma once
 #include "cartpole.hpp"
@@ -135,9 +141,13 @@ __device__ __forceinline__ void svb_coef(const SvmpcBatchArgs &a, const float *p
   }
 }
 
-// One rollout: the trajectory cost sum_t inst(x_t, a_t) + term(x_H) of action row `act` [H][da] under the coefficients `cf`
-template <int MODEL>
-__device__ __forceinline__ float svb_traj(const SvmpcBatchArgs &a, const float *act, const float *cf, const float *x0, const bool fast_trig) {
+// One rollout: the trajectory cost sum_t inst(x_t, a_t) + term(x_H) of action row `act` [H][da] under the coefficients `cf`.
+// NAV (skid-steer alone): the navigation cost family of skid.hpp, skid_rollout_body<false, true>'s arithmetic operation by operation -
+// inst = (quad + ctrl) + w_obs occ(x_0, x_1) on the state BEFORE the step, term = quad + w_obs occ(x_0, x_1); `map`: where collision()
+// finds the occupancy bits (LDS or device memory).  A template parameter: the plain instances keep their instructions.
+template <int MODEL, bool NAV = false>
+__device__ __forceinline__ float svb_traj(const SvmpcBatchArgs &a, const float *act, const float *cf, const float *x0, const bool fast_trig,
+                                          const float w_obs = 0.f, const DevModel *map = nullptr) {
   constexpr int DS = SvbDims<MODEL>::DS;
   const int H = a.H;
   float x[DS];
@@ -205,7 +215,8 @@ __device__ __forceinline__ float svb_traj(const SvmpcBatchArgs &a, const float *
         sc += (double)((d * d) * a.sk.w_state[k]);
       }
       const double cc = (double)((a0 * a0) * a.sk.w_ctrl[0]) + (double)((a1 * a1) * a.sk.w_ctrl[1]);
-      tot += (double)((float)sc + (float)cc);
+      if constexpr (NAV) tot += (double)(((float)sc + (float)cc) + w_obs * collision(*map, x[0], x[1]));  // (quad + ctrl) + obst
+      else tot += (double)((float)sc + (float)cc);
       skid_step(x, clampf(a0, a.sk.lo[0], a.sk.hi[0]), clampf(a1, a.sk.lo[1], a.sk.hi[1]), xicr, wr, ad, a.dt);
     }
     double tc = 0.0;
@@ -214,7 +225,8 @@ __device__ __forceinline__ float svb_traj(const SvmpcBatchArgs &a, const float *
       const float d = x[k] - a.sk.goal[k];
       tc += (double)((d * d) * a.sk.w_term[k]);
     }
-    return (float)tot + (float)tc;
+    if constexpr (NAV) return (float)tot + ((float)tc + w_obs * collision(*map, x[0], x[1]));
+    else return (float)tot + (float)tc;
   } else {
     CartCoef kf;
     kf.g = cf[0];
@@ -297,9 +309,12 @@ __device__ __forceinline__ void svb_draw_row(const SvmpcBatchArgs &a, const SvbP
 }
 
 // The tick of environment blockIdx.x.  PRIOR: the dynamics samples are drawn in phase 0 from the environment's filter (`pri`), not read
-// from a.params; nothing else differs.
-template <int MODEL, bool PRIOR>
-__device__ __forceinline__ void svb_body(const SvmpcBatchArgs &a, const SvbPrior *pri) {
+// from a.params; nothing else differs.  NAV: the skid-steer tick with the navigation cost family (`nav`; one map for the whole batch) -
+// a map of nav->grid_words > 0 words is staged ONCE per launch into the dynamic LDS behind the tick's own, ahead of the iteration loop;
+// otherwise the lookups of phase C read it in place.
+template <int MODEL, bool PRIOR, bool NAV = false>
+__device__ __forceinline__ void svb_body(const SvmpcBatchArgs &a, const SvbPrior *pri, const SkidNav *nav = nullptr) {
+  static_assert(!NAV || MODEL == DUST_MODEL_SKID_STEER, "the navigation cost family is the skid-steer robot's");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int DS = SvbDims<MODEL>::DS;
   constexpr int T = SVB_THREADS;
@@ -344,6 +359,24 @@ __device__ __forceinline__ void svb_body(const SvmpcBatchArgs &a, const SvbPrior
                          (fabsf(x0[0]) + a.dm.max_speed_pend * (float)a.dm.dt * (float)H < 5.0e4f);
   const bool same_w = (a.alpha * a.temp == 1.0f);  // temperature = 1 / alpha (every demo): omega and w are the same softmax
   auto col2 = [&](const float *v, const int j) { return (da == 2 && (j & 1)) ? v[1] : v[0]; };
+  DevModel map;    // (NAV alone) what collision() reads: skid.hpp skid_nav_map's fields
+  float w_obs = 0.f;
+  if constexpr (NAV) {
+    map.inv_cell = nav->inv_cell;
+    map.off_x = nav->off_x;
+    map.off_y = nav->off_y;
+    map.nx = nav->nx;
+    map.ny = nav->ny;
+    map.grid_bits = nav->grid_bits;
+    w_obs = nav->w_obs;
+    if (nav->grid_words > 0 && a.n_steps > 0) {  // (the same for every lane of the launch; a lone forward() looks nothing up)
+      uint32_t *grid = reinterpret_cast<uint32_t *>(misc + 4);  // behind svmpc_batch_lds_bytes(): 4 nav->grid_words bytes
+      const int words = (nav->nx * nav->ny + 31) >> 5;          // (grid_words is this rounded up to 4: the allocation ends at `words`)
+      for (int w = tid; w < words; w += T) grid[w] = nav->grid_bits[w];
+      map.grid_bits = grid;
+      svb_sync();
+    }
+  }
 
   for (int it = 0; it < a.n_steps; ++it) {
     // ---- 0: stage
@@ -426,7 +459,8 @@ __device__ __forceinline__ void svb_body(const SvmpcBatchArgs &a, const SvbPrior
         for (int m = g; m < M; m += G) {
           // scalar-event params_dist quirk (disco.py:177-179): rollout r = (m, s, n) flattened uses params[r % M]
           const int pidx = a.dm.interleave ? (int)(((long)m * NS + row) % M) : m;
-          acc += (double)svb_traj<MODEL>(a, act, coef + pidx * SVB_COEF, x0, fast_trig);
+          if constexpr (NAV) acc += (double)svb_traj<MODEL, true>(a, act, coef + pidx * SVB_COEF, x0, fast_trig, w_obs, &map);
+          else acc += (double)svb_traj<MODEL>(a, act, coef + pidx * SVB_COEF, x0, fast_trig);
         }
         if (G == 1) g_costs[row] = M == 1 ? (float)acc : (float)(acc / M);
         else accp[w] = acc;
@@ -674,6 +708,24 @@ __global__ __launch_bounds__(SVB_THREADS) void svmpc_batch_kernel(const SvmpcBat
 template <int MODEL>
 __global__ __launch_bounds__(SVB_THREADS) void svmpc_prior_batch_kernel(const SvmpcPriorBatchArgs kp) {
   svb_body<MODEL, true>(kp.k, &kp.pr);
+}
+// The skid-steer tick with the navigation cost family (dust_amd.costs.NavigationCost), in both forms.  The SkidNav travels BESIDE the
+// arguments above, as skid.hpp's SkidNavArgs does: the eight instances without the term keep their argument layout - and their
+// instructions.  Dynamic LDS: svmpc_batch_lds_bytes() + 4 nav.grid_words bytes.
+struct SvmpcNavBatchArgs {
+  SvmpcBatchArgs k;
+  SkidNav nav;
+};
+struct SvmpcNavPriorBatchArgs {
+  SvmpcBatchArgs k;
+  SvbPrior pr;
+  SkidNav nav;
+};
+__global__ __launch_bounds__(SVB_THREADS) void svmpc_skid_nav_batch_kernel(const SvmpcNavBatchArgs kn) {
+  svb_body<DUST_MODEL_SKID_STEER, false, true>(kn.k, nullptr, &kn.nav);
+}
+__global__ __launch_bounds__(SVB_THREADS) void svmpc_skid_nav_prior_batch_kernel(const SvmpcNavPriorBatchArgs kp) {
+  svb_body<DUST_MODEL_SKID_STEER, true, true>(kp.k, &kp.pr, &kp.nav);
 }
 // the instance of either kernel for a model (the host's launch names the model once for both)
 template <int MODEL, bool PRIOR>

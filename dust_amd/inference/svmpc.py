@@ -178,7 +178,8 @@ class BatchSVMPC:
     Every environment has its own state, particles, prior, a_mat, optimiser state, noise stream (`seeds`, default seed + b) and
     dynamics samples.  The constructor takes SVMPC's arguments behind `n_envs` and refuses what lies outside the kernel's box
     (K1 / IMQ kernel, N <= 64, S <= 1024, M <= 64, H d_a <= 128, ctrl_penalty = 1, diagonal covariances, no sigma points, roll
-    'repeat' / 'mean') before any device is touched."""
+    'repeat' / 'mean') before any device is touched.  Every model family's cost runs in the batch, the skid-steer robot's
+    `NavigationCost` among them (svmpc_skid_nav_batch_kernel): its one occupancy map serves all `n_envs` environments."""
 
     def __init__(self, n_envs, init_particles, prior, likelihood, roll_strategy="repeat", weighted_prior=False, kernel=None, bw_scale=1.0,
                  n_particles=None, n_steps=100, optimizer_class=torch.optim.Adam, seeds=None, **opt_args):

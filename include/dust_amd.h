@@ -410,9 +410,13 @@ int dust_amppi_batch_get_actions(dust_amppi_batch *batch, float *actions);
  *
  * The box (DUST_ERR_UNSUPPORTED / DUST_ERR_INVALID from dust_svmpc_batch_create, before anything is allocated): 1 <= n_policies <= 64,
  * 1 <= n_samples <= 1024, 1 <= n_params <= 64, H dim_a <= 128, dim_p <= 4, 1 <= n_env <= 65535, the K1 or the IMQ kernel, a_reg = 0
- * (ctrl_penalty = 1), diagonal covariances.  Not supported: sigma-point weights, the navigation cost family, Particle with velocity
- * control or control-channel noise, binary16 storage, DUST_STORE_STATES, roll strategy "resample", sharded contexts, contexts that
- * are serving.
+ * (ctrl_penalty = 1), diagonal covariances.  Not supported: sigma-point weights, Particle with velocity control or control-channel
+ * noise, binary16 storage, DUST_STORE_STATES, roll strategy "resample", sharded contexts, contexts that are serving.
+ * Every model family's cost runs in the batch.  A skid-steer prototype with an obstacle weight (dust_set_obstacle_cost: the navigation
+ * cost family) ticks in instances of its own (svmpc_skid_nav_batch_kernel, svmpc_skid_nav_prior_batch_kernel, counted under
+ * DUST_K_SVMPC_BATCH like the others): ONE map, the prototype's (dust_set_grid), serves the B environments - staged into the workgroup's
+ * LDS up to 4096 words, read in place from device memory beyond (or with DUST_NAV_GRID_HBM=1), the same bits either way.  Without a map
+ * dust_svmpc_batch_create and every call of the batch answer DUST_ERR_STATE ("no occupancy grid was supplied") before any launch.
  *
  * dust_svmpc_batch_create: the batch keeps a private dust_clone of `proto`: `proto` may be destroyed afterwards and later changes to it
  *   do not reach the batch.  Every environment starts from proto's particles, prior, a_mat, optimiser configuration and state, and
@@ -702,7 +706,8 @@ int dust_amppi_dual_batch_tick(dust_amppi_batch *batch, dust_mpf_batch *mpf, con
  * before the roll), p_weights [B][N], params_out [B][n_steps][M][P], bw_used [B] (0: no update; mpf_bw when that was given).  An
  * environment with active[b] = 0 keeps everything on both sides; its output rows are not written.  With every output NULL the call
  * returns without waiting for the device.  Refused before anything is staged or launched: what dust_svmpc_batch_tick refuses (sigma-point
- * weights among it: a batch does not run the sigma mode of dust_dual_tick), what dust_dual_tick refuses of a controller / filter pair,
+ * weights among it: a batch does not run the sigma mode of dust_dual_tick; the navigation cost family is NOT among it - it ticks in
+ * svmpc_skid_nav_prior_batch_kernel on the batch's one map), what dust_dual_tick refuses of a controller / filter pair,
  * what dust_mpf_batch_optimize refuses, batches of different n_env, NULL prior_seeds, n_steps < 1, mpf_steps < 0. */
 int dust_svmpc_dual_batch_tick(dust_svmpc_batch *batch, dust_mpf_batch *mpf, const float *states, const float *actions_prev, int n_steps,
                                const void *eps, int flags, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds,
