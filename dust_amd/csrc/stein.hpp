@@ -92,6 +92,32 @@ __device__ __forceinline__ void rowlane_commit(const float (&v)[RowLane<TR, DP, 
   }
 }
 
+// Where the 1/s_d scale of a pass enters.  d_a <= 2 (every model family the library has): the tiles are staged AS STORED and the
+// differences x - y are formed on those values - exact in fp32 for nearby rows, wherever the cloud sits - and the scale is applied to the
+// SUMS: pass A keeps the squares of even and odd columns in the two halves of its packed accumulator (column d has scale s_{d & 1}), so
+// |z|^2 = q0 sum_even + q1 sum_odd with q = 1 / s^2; the difference sums of pass B leave the kernel unscaled (as before, where 1 / s was
+// multiplied back).  Pre-scaled tiles (x / s - y / s) round each operand at its own magnitude: 2^-24 |x / s| per term, which at a
+// centre of 50 and a cloud width of 0.13 is 2e-5 of every difference (grad_pri 1.4e-5 off its float64 value; tests/pairwise_cases.py,
+// the "offset" family).  d_a > 2 keeps the pre-scaled tiles (four column classes would double pass A's accumulators).
+struct PairScale {
+  float q0, q1;  // 1 / s^2 of even / odd columns (1 when the tiles are pre-scaled)
+  bool post;     // the tiles are staged as stored
+};
+__device__ __forceinline__ PairScale pair_scale(const PairArgs &a) {
+  PairScale s;
+  s.post = a.da <= 2;
+  s.q0 = s.post ? a.inv_s[0] * a.inv_s[0] : 1.0f;
+  s.q1 = s.post ? (a.da == 2 ? a.inv_s[1] * a.inv_s[1] : s.q0) : 1.0f;
+  return s;
+}
+// a staged tile: as stored, or (d_a > 2) pre-scaled by the per-column 1 / s_d; the choice is uniform over the launch
+template <int TR, int DP, int LS, int NT>
+__device__ __forceinline__ void rowlane_commit_ps(const PairScale &ps, const float (&v)[RowLane<TR, DP, NT>::NB], int nrows, int D, int da,
+                                                  const float *inv_s, float *dst, const int tx) {
+  if (ps.post) rowlane_commit<TR, DP, LS, NT, false>(v, nrows, D, da, inv_s, dst, tx);
+  else rowlane_commit<TR, DP, LS, NT, true>(v, nrows, D, da, inv_s, dst, tx);
+}
+
 template <int MODE, int CPT /* columns per lane in pass B: multiple of 4, 8*CPT >= D */>
 __device__ __forceinline__ void pairwise_body(const PairArgs &a, float *lds, const int tile_x, const int js, const bool write_through = false) {
   constexpr int TI = PAIR_TI, JC = PAIR_JC, NT = PAIR_NT;
@@ -101,8 +127,8 @@ __device__ __forceinline__ void pairwise_body(const PairArgs &a, float *lds, con
   constexpr int YS = DP + 4;
   constexpr int QG = NT / JC;      // query groups in pass A (4)
   constexpr int QPG = TI / QG;     // queries per group (8)
-  float *Xs = lds;                  // [TI][DP]   queries, pre-scaled by 1/s_d
-  float *Ys = Xs + TI * DP;         // [JC][YS]   keys, pre-scaled by 1/s_d
+  float *Xs = lds;                  // [TI][DP]   queries (as stored; d_a > 2: pre-scaled by 1/s_d - PairScale)
+  float *Ys = Xs + TI * DP;         // [JC][YS]   keys, likewise
   float *Vs = Ys + JC * YS;         // [JC][YS]   score (Stein), unscaled
   float *kv = Vs + (PRI ? 0 : JC * YS);  // [TI][JC + 1]
   float *mrow = kv + TI * (JC + 1); // [TI] running max
@@ -110,6 +136,7 @@ __device__ __forceinline__ void pairwise_body(const PairArgs &a, float *lds, con
   const int D = a.D, da = a.da, N = a.N;
   const int ib = a.i0 + tile_x * TI;  // first query (global index)
   const int jbeg = js * a.slice, jend = min(N, jbeg + a.slice);
+  const PairScale ps = pair_scale(a);
 
   DUST_STAMP(a.stamps, 0);
   // ---- query tile + first key chunk -> LDS: all first-batch loads are in flight before the first wait ----
@@ -120,8 +147,8 @@ __device__ __forceinline__ void pairwise_body(const PairArgs &a, float *lds, con
     rowlane_issue<JC, DP, NT>(a.Y, jbeg, jc0, D, vy, tid);
     if (!PRI) rowlane_issue<JC, DP, NT>(a.V, jbeg, jc0, D, vv, tid);
     if (tid < TI) mrow[tid] = -INFINITY;
-    rowlane_commit<TI, DP, DP, NT, true>(vx, nq, D, da, a.inv_s, Xs, tid);
-    rowlane_commit<JC, DP, YS, NT, true>(vy, jc0, D, da, a.inv_s, Ys, tid);
+    rowlane_commit_ps<TI, DP, DP, NT>(ps, vx, nq, D, da, a.inv_s, Xs, tid);
+    rowlane_commit_ps<JC, DP, YS, NT>(ps, vy, jc0, D, da, a.inv_s, Ys, tid);
     if (!PRI) rowlane_commit<JC, DP, YS, NT, false>(vv, jc0, D, da, a.inv_s, Vs, tid);
   }
 
@@ -156,7 +183,7 @@ __device__ __forceinline__ void pairwise_body(const PairArgs &a, float *lds, con
       float vy[RowLane<JC, DP, NT>::NB], vv[RowLane<JC, DP, NT>::NB];
       rowlane_issue<JC, DP, NT>(a.Y, j0, jc, D, vy, tid);
       if (!PRI) rowlane_issue<JC, DP, NT>(a.V, j0, jc, D, vv, tid);
-      rowlane_commit<JC, DP, YS, NT, true>(vy, jc, D, da, a.inv_s, Ys, tid);  // the barrier that ended the previous chunk's pass B
+      rowlane_commit_ps<JC, DP, YS, NT>(ps, vy, jc, D, da, a.inv_s, Ys, tid);  // the barrier that ended the previous chunk's pass B
       if (!PRI) rowlane_commit<JC, DP, YS, NT, false>(vv, jc, D, da, a.inv_s, Vs, tid);  // protects these writes
       wg_sync();
     }
@@ -182,7 +209,7 @@ __device__ __forceinline__ void pairwise_body(const PairArgs &a, float *lds, con
       }
 #pragma unroll
       for (int ii = 0; ii < QPG; ++ii) {
-        const float dd = d2[ii].x + d2[ii].y;
+        const float dd = fmaf(d2[ii].x, ps.q0, d2[ii].y * ps.q1);  // (even / odd columns: PairScale)
         float v;
         if (PRI) v = (jA < jc) ? lm - 0.5f * dd : -INFINITY;
         else if (MODE == PAIR_K1) v = (jA < jc) ? __builtin_amdgcn_exp2f(-0.72134752044448170f * dd) : 0.f;  // exp(-dd/2) = 2^(-dd/(2 ln 2)); bare v_exp_f32, rel. error ~|x| 2^-24
@@ -264,7 +291,7 @@ __device__ __forceinline__ void pairwise_body(const PairArgs &a, float *lds, con
   }
 
   DUST_STAMP(a.stamps, 4);
-  // ---- partial outputs (differences were accumulated in scaled coordinates: undo the 1/s_d) ----
+  // ---- partial outputs (d_a > 2: differences were accumulated in scaled coordinates: undo the 1/s_d) ----
   const int il = tile_x * TI + iB;  // local row
   if (il < a.n_local) {
     // partial rows are padded to DP floats: every lane stores whole 16-byte groups, the 8 lanes of a row one contiguous
@@ -277,7 +304,7 @@ __device__ __forceinline__ void pairwise_body(const PairArgs &a, float *lds, con
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const int col = cB + c + k;
-        const float un = 1.0f / a.inv_s[da == 1 ? 0 : (da == 2 ? (col & 1) : col % da)];
+        const float un = ps.post ? 1.0f : 1.0f / a.inv_s[da == 1 ? 0 : (da == 2 ? (col & 1) : col % da)];
         const float va = ((c + k) & 1) ? accA[(c + k) / 2].y : accA[(c + k) / 2].x;
         const float vb = ((c + k) & 1) ? accB[(c + k) / 2].y : accB[(c + k) / 2].x;
         oa[k] = (PRI) ? va * un : va;
@@ -321,8 +348,8 @@ __device__ __forceinline__ void stein_split_body(const PairArgs &a, float *lds, 
   static_assert(CPT <= 8, "the Gram x score product runs on the matrix cores (D <= 64)");
   constexpr int TI = PAIR_TI, JC = PAIR_JC, NT = PAIR_NT;
   constexpr int DP = 8 * CPT, YS = DP + 4, QG = NT / JC, QPG = TI / QG, TPW = DP / 32;
-  float *Xs = lds;                   // [TI][DP]  queries / ell
-  float *Ys = Xs + TI * DP;          // [JC][YS]  keys / ell
+  float *Xs = lds;                   // [TI][DP]  queries (as stored: PairScale)
+  float *Ys = Xs + TI * DP;          // [JC][YS]  keys
   float *Vs = Ys + JC * YS;          // [JC][YS]  score rows
   float *kv = Vs + JC * YS;          // [TI][JC + 1] Gram values
   const int tid = threadIdx.x;
@@ -330,12 +357,13 @@ __device__ __forceinline__ void stein_split_body(const PairArgs &a, float *lds, 
   const int ib = a.i0 + tile_x * TI;
   const int jbeg = js * a.slice, jend = min(N, jbeg + a.slice);
   const int nq = min(TI, a.i0 + a.n_local - ib), jc = min(JC, jend - jbeg);
+  const PairScale ps = pair_scale(a);
   {
     float vx[RowLane<TI, DP, NT>::NB], vy[RowLane<JC, DP, NT>::NB];
     rowlane_issue<TI, DP, NT>(a.X, ib, nq, D, vx, tid);
     rowlane_issue<JC, DP, NT>(a.Y, jbeg, jc, D, vy, tid);
-    rowlane_commit<TI, DP, DP, NT, true>(vx, nq, D, da, a.inv_s, Xs, tid);
-    rowlane_commit<JC, DP, YS, NT, true>(vy, jc, D, da, a.inv_s, Ys, tid);
+    rowlane_commit_ps<TI, DP, DP, NT>(ps, vx, nq, D, da, a.inv_s, Xs, tid);
+    rowlane_commit_ps<JC, DP, YS, NT>(ps, vy, jc, D, da, a.inv_s, Ys, tid);
   }
   const int iB = tid >> 3, cB = (tid & 7) * CPT;
   v2f accB[CPT / 2];
@@ -365,7 +393,7 @@ __device__ __forceinline__ void stein_split_body(const PairArgs &a, float *lds, 
     }
 #pragma unroll
     for (int ii = 0; ii < QPG; ++ii) {
-      const float dd = d2[ii].x + d2[ii].y;
+      const float dd = fmaf(d2[ii].x, ps.q0, d2[ii].y * ps.q1);  // (even / odd columns: PairScale)
       float v;
       if (MODE == PAIR_K1) v = (jA < jc) ? __builtin_amdgcn_exp2f(-0.72134752044448170f * dd) : 0.f;
       else v = (jA < jc) ? __builtin_amdgcn_rsqf(1.0f + dd) : 0.f;
@@ -396,7 +424,7 @@ __device__ __forceinline__ void stein_split_body(const PairArgs &a, float *lds, 
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const int col = cB + c + k;
-        const float un = 1.0f / a.inv_s[da == 1 ? 0 : (da == 2 ? (col & 1) : col % da)];
+        const float un = ps.post ? 1.0f : 1.0f / a.inv_s[da == 1 ? 0 : (da == 2 ? (col & 1) : col % da)];
         ob[k] = (((c + k) & 1) ? accB[(c + k) / 2].y : accB[(c + k) / 2].x) * un;
       }
       store16(a.pB + row + cB + c, ob, true);

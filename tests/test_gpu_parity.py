@@ -870,7 +870,9 @@ def test_k2_bandwidth_is_the_exact_order_statistic(N):
 def test_large_key_set_pairwise_vs_oracle(model, N, H, kernel, monkeypatch):
     """N >= 2048 takes the register-blocked pairwise kernel (pairwise_big.hpp): prior score, log p and phi against the
     oracle for both padded widths (D = 30 / 17 -> 32, 40 -> 64), D = 80 (which stays on the 32 x 64 kernel), ragged N, and
-    log p through a forward pass."""
+    log p through a forward pass.  At these inputs (theta = mu + 0.4 N(0, 1) round mu ~ N(0, 1)) the K1 Gram matrix is the IDENTITY
+    (largest off-diagonal row mass below 1e-5, asserted in test_pairwise_cases_cpu.py): the K1 rows hold plumbing and the IMQ row its
+    heavy tails; the passes over a DENSE Gram matrix are held in tests/test_gpu_pairwise_sizes.py."""
     monkeypatch.setenv("DUST_PAIR_BIG", "1")  # (N D <= 65536 runs the small-set launches by default: this test is about the large-set kernels)
     from dust_amd import Context
     from oracle import Oracle, grid_4x4_map

@@ -301,7 +301,11 @@ def test_tick2_stage_parity_vs_oracle(model, N, S, H, M, kernel, optimizer):
     of ONE iteration through `svmpc_tick2_kernel` with caller-supplied noise: a one-iteration launch is stage-local - the costs depend
     on theta and eps only, the score on the costs, phi on the score - so every stage is compared with the oracle fed the stage before it
     (the policy of DESIGN.md section 2: one ulp of a cost of 1e3 is 1e-4 on a softmax weight).  Reference path: SVMPC.step svmpc.py:87-95
-    -> likelihood.sample likelihoods.py:81-101 -> MultiDISCO._rollout / _compute_cost disco.py:139-346 -> SVMPC.phi svmpc.py:38-83."""
+    -> likelihood.sample likelihoods.py:81-101 -> MultiDISCO._rollout / _compute_cost disco.py:139-346 -> SVMPC.phi svmpc.py:38-83.
+    At these inputs (theta = mu + sigma N(0, 1), K1's lengthscale ln 2) the K1 Gram matrix is the IDENTITY - the largest off-diagonal
+    row mass is 1e-30 - so phi_i = score_i / N whatever the kernel does with the other keys, and the aliased prior's responsibilities
+    are the identity too: rollouts, costs, score and step are held here; the Stein and prior passes over a DENSE Gram matrix are held
+    in tests/test_gpu_pairwise_sizes.py (test_pairwise_cases_cpu.py asserts this fact)."""
     from dust_amd import Context
     from oracle import Oracle, grid_4x4_map
     from test_oracle_golden import k1_tolerance
