@@ -19,8 +19,9 @@
 //   * waves 8-15 (P): the theta-only half of SVMPC.phi in two passes over all N keys (exact differences to two query rows per
 //     wave): the PRIOR pass underneath the rollouts - lane = (key of a 32-key step, column half), squared distances -> LDS, the
 //     prior's softmax-weighted sum and mass in registers (t2_prior_pass_w) - and, while the score rows travel, the STEIN pass -
-//     lane = (key of 16, column quarter), k_ij -> LDS in place of the distances, repulsion in registers (t2_pair_pass).  Sums over
-//     the key lanes leave a wave through the butterflies of tick2_reduce.hpp;
+//     lane = (key of 16, column quarter), k_ij -> LDS in place of the distances, repulsion in registers (t2_pair_pass: the key rows
+//     of two step pairs ping-pong through 32 registers, requested two steps ahead).  Sums over the key lanes leave a wave through the
+//     butterflies of tick2_reduce.hpp;
 //   * the owner lanes (the 128 lanes of waves 0-1, lane = (particle, column); five values per lane in registers for the tick) finish
 //     the score rows behind the prior pass (at wave priority 3: every other workgroup waits for them) and publish them, while all
 //     eight pair waves are in the Stein pass already - hosted by two pair waves the stage made those two the last to finish the pass,
@@ -169,7 +170,7 @@ __device__ __forceinline__ void t2_pair_pass(const T2ArgPtr f, const int gen /* 
                                              float *dk /* LDS [keys][4]: |y_j - x_q|^2 (PRIOR) -> k_qj (STEIN) */, const float *lml /* LDS [keys] log pi_j */,
                                              const int pw /* unit: (query half, key quarter), or the wave (LOGP) */, const int lane, const float lm_ref,
                                              float (&red)[4] /* PRIOR: reduce_u16<32> of a | L; STEIN: reduce_u16<16> of b; LOGP: L of the 4 queries */,
-                                             const int t_begin = 0, const int t_end = -1 /* the unit's steps [t_begin, t_end): even bounds; -1: all */) {
+                                             const int t_begin = 0, const int t_end = -1 /* the unit's steps [t_begin, t_end): a multiple of four of them; -1: all */) {
   constexpr int NQ = PASS == T2_PASS_LOGP ? 4 : 2;   // queries per wave
   constexpr int NKW = PASS == T2_PASS_LOGP ? 16 : 4;  // waves that share the keys (forward: all 16 waves of the workgroup)
   const int u = lane >> 2, c = lane & 3, N = f->N;
@@ -240,29 +241,53 @@ __device__ __forceinline__ void t2_pair_pass(const T2ArgPtr f, const int gen /* 
     }
   };
   {
-    constexpr int PF = 2;  // key steps in flight (deeper prefetch - four steps in registers, an LDS-DMA ring of three: tools/ldsdma_probe.hip -
-    v4f ya[PF], yb[PF];    // was measured and bought nothing: the passes follow the bytes they pull through the CU's vector memory path)
+    // Two pairs of key steps, A and B, take turns (an explicit ping-pong over a trip of four steps): a pair's rows are requested while the
+    // other pair's steps run, two steps ahead of their use, and land in the registers the pair's last steps have just released - 16 row
+    // registers live and 16 incoming, no copy of a loaded row and no full vmcnt drain at the loop's end (with one group of registers
+    // reloaded while its old contents were still to be read, every trip ended with 16 - 18 v_mov_b32 behind a vmcnt(0): a quarter of the
+    // Stein loop's vector instructions).  Deeper prefetch - four steps in registers, an LDS-DMA ring of three: tools/ldsdma_probe.hip -
+    // was measured and bought nothing: the passes follow the bytes they pull through the CU's vector memory path.
+    v4f a0[2], a1[2], b0[2], b1[2];
     const int tb = t_begin, te = t_end < 0 ? steps : t_end;
     auto issue = [&](const int t, v4f &y0, v4f &y1) {
       const int j = min((t * NKW + kw) * 16 + u, N - 1);
       y0 = t2_ld16(rx, (j * T2_ROW + 8 * c) * 4);
       y1 = t2_ld16(rx, (j * T2_ROW + 8 * c + 4) * 4);
     };
-#pragma unroll
-    for (int p = 0; p < PF; ++p) issue(min(tb + p, te - 1), ya[p], yb[p]);
-    for (int t0 = tb; t0 < te; t0 += PF) {
-#pragma unroll
-      for (int p = 0; p < PF; ++p) {
-        const int t = t0 + p;
-        const v4f y0 = ya[p], y1 = yb[p];
-        issue(min(t + PF, te - 1), ya[p], yb[p]);  // (the last group re-reads its last rows: no branch in the loop)
-        v2f dq = {0.f, 0.f};
-        if (PASS == T2_PASS_STEIN) {
-          const float2 d = *reinterpret_cast<const float2 *>(&dk[(size_t)((t * NKW + kw) * 16 + u) * 4 + q0]);
-          dq = v2f{d.x, d.y};
-        }
-        step(t, y0, y1, dq);
+    auto run = [&](const int t, const v4f y0, const v4f y1) {
+      v2f dq = {0.f, 0.f};
+      if (PASS == T2_PASS_STEIN) {
+        const float2 d = *reinterpret_cast<const float2 *>(&dk[(size_t)((t * NKW + kw) * 16 + u) * 4 + q0]);
+        dq = v2f{d.x, d.y};
       }
+      step(t, y0, y1, dq);
+    };
+    // a pair's accumulation ends HERE: the steps store to LDS under a lane mask, i.e. in blocks of their own, and the accumulation, needed
+    // only behind the loop, sinks out of them to the trip's end - past the request for the pair's next rows, whose registers it still reads
+    auto pin = [&]() {
+      if (PASS != T2_PASS_LOGP) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+#pragma unroll
+          for (int h = 0; h < 4; ++h) asm volatile("" : "+v"(acc[q][h]));
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    };
+#pragma unroll
+    for (int p = 0; p < 2; ++p) issue(min(tb + p, te - 1), a0[p], a1[p]);
+    for (int t0 = tb; t0 < te; t0 += 4) {
+#pragma unroll
+      for (int p = 0; p < 2; ++p) issue(t0 + 2 + p, b0[p], b1[p]);
+      __builtin_amdgcn_sched_barrier(0);  // (left to itself the scheduler requests a pair's next rows ABOVE its steps, into registers of their own)
+#pragma unroll
+      for (int p = 0; p < 2; ++p) run(t0 + p, a0[p], a1[p]);
+      pin();
+#pragma unroll
+      for (int p = 0; p < 2; ++p) issue(min(t0 + 4 + p, te - 1), a0[p], a1[p]);  // (the last trip re-reads its last rows: no branch in the loop)
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int p = 0; p < 2; ++p) run(t0 + 2 + p, b0[p], b1[p]);
+      pin();
     }
   }
   if (PASS == T2_PASS_PRIOR) {
@@ -1041,6 +1066,9 @@ __global__ __launch_bounds__(T2_NT, 4) void svmpc_tick2_kernel(const Tick2Args f
           // (L / sigma^2) sum_s w_s eps_s and sum_s omega_s (a_s - base) = (theta - base) sum_s omega_s + L sum_s omega_s eps_s, up to the
           // rounding of a_s = fl(theta + L eps_s) that the per-sample form (below, -DT2_WSUM_PER_SAMPLE) carries through (<= 1e-6 relative per
           // term; all parity tests unchanged): 2 instead of 6 vector instructions per sample - 94.4 -> 91.2 us per cfg2 tick (round 5)
+          // (tried: `same_w` decided outside the loop and the LDS reads of eight samples issued together, the chains behind them in the
+          //  samples' order - 48 instead of 116 instructions and 1 instead of 15 waits per 8 samples, bit-identical, and the tick 1.2 %
+          //  SLOWER on top of the Stein loop's ping-pong, with or without the single wait: profiles/tick2_hot_loops.txt.  Not kept.)
           {
             float ge = 0.f, oe = 0.f, so = 0.f;
             for (int s0 = (wave & 1) * 64; s0 < S; s0 += 128) {
@@ -1181,6 +1209,7 @@ __global__ __launch_bounds__(T2_NT, 4) void svmpc_tick2_kernel(const Tick2Args f
       DUST_PRIO(0);
       T2_TL(8, 16 * k + 11);
       T2_TL(15, 16 * k + 6);
+      T2_TL(wave, k == 2 ? 88 + wave : 128);  // iteration 2: every pair wave's Stein unit, words 96-103 (tools/tick2_timeline.py)
     }
     if (wave == 10) {
       // (the first poll comes as soon as the wave's Stein unit ends; held back by s_sleep 6 or 14 it measured the same:
@@ -1196,6 +1225,9 @@ __global__ __launch_bounds__(T2_NT, 4) void svmpc_tick2_kernel(const Tick2Args f
     } else if (wave == 11) {
       if (k + 1 < f->n_iters) make_coefs(f, k + 1);
     }
+    // (tried: wave 10 raises an LDS word behind its poll, every wave sleeps on it once its phase-4 work is done and requests its score rows
+    //  in front of B4 - 32 row registers held across the barrier, no spill: -0.5 % against the build without it, not kept:
+    //  profiles/tick2_hot_loops.txt)
     wg_sync();  // B4
     f = t2_args();
     T2_TL(0, 16 * k + 10);

@@ -52,6 +52,9 @@ for k in range(IT):
     print("iteration %d:" % k)
     for i in order:
         show(names[i], 16 * k + i)
+    if k == 2:  # every pair wave's Stein unit (words 96-103): which of them B4 waits for
+        for w in range(8, 16):
+            show("Stein pass done (w%d)" % w, 88 + w)
 print("forward:")
 for i, nm in [(3, "generation n_iters seen (w0)"), (0, "log-density pass done"), (1, "log-weights arrived"), (2, "end")]:
     show(nm, 16 * IT + i)
