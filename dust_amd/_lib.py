@@ -158,6 +158,7 @@ SYMBOLS = {
     "dust_svmpc_batch_optimize": (C.c_int, [VP, FP, C.c_int, VP, FP, C.c_int, C.POINTER(C.c_ubyte)]),
     "dust_svmpc_batch_forward": (C.c_int, [VP, C.POINTER(C.c_ubyte), FP, FP]),
     "dust_svmpc_batch_tick": (C.c_int, [VP, FP, C.c_int, VP, FP, C.c_int, C.POINTER(C.c_ubyte), FP, FP]),
+    "dust_svmpc_batch_episode": (C.c_int, [VP, FP, C.c_int, C.c_int, FP, FP, C.c_int, C.POINTER(C.c_ubyte), FP, FP, FP, FP]),
     "dust_mpf_batch_create": (C.c_int, [VP, C.c_int, C.POINTER(VP)]),
     "dust_mpf_batch_destroy": (None, [VP]),
     "dust_mpf_batch_clone": (C.c_int, [VP, C.POINTER(VP)]),

@@ -898,6 +898,32 @@ class SvmpcBatch:
         L.check(L.load().dust_svmpc_batch_tick(self._h, _p(st), int(n_steps), e if eps_dev_ptr else _vp(e), _p(pr), fl, mp, _p(a_seq), _p(pw)))
         return a_seq, pw
 
+    def episode(self, states, n_periods, n_steps, params=None, plant_params=None, active=None, want_pw=True, flags=0):
+        """n_periods closed-loop periods of every active environment in ONE launch (dust_svmpc_batch_episode): per period the tick (noise
+        drawn on the device), the plant's step with the first action of the chosen sequence under the environment's true parameters,
+        the new state into the next tick.  states [B, ds]; params [T, B, n_steps, M, P] or None (no uncertain parameters);
+        plant_params [B, P] or None (nominal plants).  -> (states [T, B, ds] after every step, actions [T, B, da], p_weights [T, B, N]
+        or None, a_seq [B, H, da] of the last period); the rows of inactive environments are NaN.  flags: none is defined (the library
+        refuses any)."""
+        B, T = self.B, int(n_periods)
+        st = None if states is None else _f(states, (B, self.ds))  # (None: the library refuses)
+        pr = pl = None
+        if params is not None:
+            pr = _f(params)
+            want = (T, B, int(n_steps), self.M, max(self.P, 1))
+            if pr.shape != want:
+                raise ValueError("params has shape %s, the call reads %s" % (pr.shape, want))
+        if plant_params is not None:
+            pl = _f(plant_params)
+            if pl.shape != (B, max(self.P, 1)):
+                raise ValueError("plant_params has shape %s, the call reads %s" % (pl.shape, (B, max(self.P, 1))))
+        _, mp = _mask(active, B)
+        rows = max(T, 0)  # (n_periods < 1: the library refuses before it writes anything)
+        xs, acts, a_seq = (np.full(sh, np.nan, np.float32) for sh in ((rows, B, self.ds), (rows, B, self.da), (B, self.H, self.da)))
+        pw = np.full((rows, B, self.N), np.nan, np.float32) if want_pw else None
+        L.check(L.load().dust_svmpc_batch_episode(self._h, _p(st), T, int(n_steps), _p(pr), _p(pl), int(flags), mp, _p(xs), _p(acts), _p(pw), _p(a_seq)))
+        return xs, acts, pw, a_seq
+
     def dual_tick(self, mpf, states, actions_prev=None, n_steps=1, eps=None, mpf_steps=20, mpf_bw=None, seeds=None, active=None,
                   want_outputs=True, want_params=False, flags=0, eps_dev_ptr=None, keep_actions=False):
         """One control period of the DuSt-MPC loop for every active environment in one C call (dust_svmpc_dual_batch_tick): the filters'

@@ -40,6 +40,7 @@
 #include "cartpole.hpp"
 #include "amppi.hpp"
 #include "svmpc_batch.hpp"
+#include "svmpc_episode.hpp"
 #include "particle_general.hpp"
 #include "rollout.hpp"
 #include "stein.hpp"
@@ -5541,6 +5542,8 @@ struct dust_svmpc_batch {
   float *a_seq_out;           // [B][D]
   float *eps, *params;        // staged inputs of a call
   size_t eps_cap, params_cap;
+  float *plant, *rec;         // dust_svmpc_batch_episode: [B][P] true parameter rows; the records [T][B][ds], [T][B][da], [T][B][N]
+  size_t plant_cap, rec_cap;
   PinnedStage in;             // per-call inputs: [B][8] states, then [B] bytes of the active mask
   bool have_costs, have_forward, acts_kept;
 };
@@ -5582,7 +5585,7 @@ static void svb_free(dust_svmpc_batch *b) {
     (void)hipStreamSynchronize(b->c->stream);
   }
   void *dev[] = {b->theta, b->mu, b->a_mat, b->mixw, b->logmix, b->alias, b->ctr, b->seeds, b->opt_s[0], b->opt_s[1], b->opt_s[2], b->acts,
-                 b->costs, b->wts, b->omg, b->score, b->phi, b->logl, b->logp, b->eta, b->a_mix, b->pw, b->a_seq_out, b->eps, b->params};
+                 b->costs, b->wts, b->omg, b->score, b->phi, b->logl, b->logp, b->eta, b->a_mix, b->pw, b->a_seq_out, b->eps, b->params, b->plant, b->rec};
   for (void *p : dev)
     if (p) (void)hipFree(p);
   b->in.free();
@@ -5812,9 +5815,10 @@ static int svb_stage(dust_svmpc_batch *b, int n_steps, const void *eps, const fl
 }
 
 // States and mask through the next pinned slot, the kernel's arguments and the ONE launch; nothing waits for the device.  params_dev: the
-// staged parameter rows or NULL; prior: the filters the PRIOR instances draw their rows from, or NULL
+// staged parameter rows or NULL; prior: the filters the PRIOR instances draw their rows from, or NULL; episode: the launch runs
+// episode->T ticks, each followed by the plant's step (svmpc_episode.hpp), not one
 static int svb_go(dust_svmpc_batch *b, const float *states, int n_steps, const float *eps_dev, const float *params_dev, int flags,
-                  const unsigned char *active, bool do_forward, const dust::SvbPrior *prior) {
+                  const unsigned char *active, bool do_forward, const dust::SvbPrior *prior, const dust::SvbEpisode *episode = nullptr) {
   dust_ctx *c = b->c;
   const size_t B = (size_t)b->B;
   HIP_TRY(hipSetDevice(c->cfg.device));
@@ -5920,7 +5924,25 @@ static int svb_go(dust_svmpc_batch *b, const float *states, int n_steps, const f
         default: return go(svb_instance<DUST_MODEL_CARTPOLE, PR>(), args);
       }
     };
-    if (nav && prior) {  // the navigation cost family: instances of their own, in both forms
+    if (episode) {
+      if (nav) {
+        SvmpcNavEpisodeArgs ke;
+        ke.k = k;
+        ke.ep = *episode;
+        ke.nav = nv;
+        TRY(go(&svmpc_skid_nav_episode_kernel, ke));
+      } else {
+        SvmpcEpisodeArgs ke;
+        ke.k = k;
+        ke.ep = *episode;
+        switch (c->cfg.model) {
+          case DUST_MODEL_PENDULUM: TRY(go(&svmpc_episode_kernel<DUST_MODEL_PENDULUM>, ke)); break;
+          case DUST_MODEL_PARTICLE: TRY(go(&svmpc_episode_kernel<DUST_MODEL_PARTICLE>, ke)); break;
+          case DUST_MODEL_SKID_STEER: TRY(go(&svmpc_episode_kernel<DUST_MODEL_SKID_STEER>, ke)); break;
+          default: TRY(go(&svmpc_episode_kernel<DUST_MODEL_CARTPOLE>, ke)); break;
+        }
+      }
+    } else if (nav && prior) {  // the navigation cost family: instances of their own, in both forms
       SvmpcNavPriorBatchArgs kp;
       kp.k = k;
       kp.pr = *prior;
@@ -5982,6 +6004,60 @@ extern "C" int dust_svmpc_batch_tick(dust_svmpc_batch *b, const float *states, i
   if (n_steps < 1) return fail(DUST_ERR_INVALID, "a tick has n_steps >= 1 (got %d)", n_steps);
   TRY(svb_launch(b, states, n_steps, eps, params, flags, active, true));
   return svb_outputs(b, active, a_seq, p_weights);
+}
+
+// T closed-loop periods (tick, plant step, records) of every active environment in ONE launch: svmpc_episode.hpp
+extern "C" int dust_svmpc_batch_episode(dust_svmpc_batch *b, const float *states, int n_periods, int n_steps, const float *params,
+                                        const float *plant_params, int flags, const unsigned char *active, float *states_out, float *actions_out,
+                                        float *pw_out, float *a_seq) {
+  if (!b) return fail(DUST_ERR_INVALID, "null batch");
+  if (!states || !states_out || !actions_out) return fail(DUST_ERR_INVALID, "null argument");
+  if (n_steps < 1) return fail(DUST_ERR_INVALID, "a tick has n_steps >= 1 (got %d)", n_steps);
+  if (n_periods < 1 || n_periods > 4096)
+    return fail(DUST_ERR_INVALID, "n_periods = %d outside [1, 4096] (one launch stays short on a shared device: split a longer episode)", n_periods);
+  if (flags != 0) return fail(DUST_ERR_UNSUPPORTED, "an episode draws its noise on the device and keeps no actions: flags must be 0 (got %d)", flags);
+  dust_ctx *c = b->c;
+  if (c->cfg.dim_p == 0 && plant_params) return fail(DUST_ERR_INVALID, "plant parameter rows without uncertain parameters (dim_p = 0)");
+  TRY(svb_call_check(b, states, n_steps, params, false, 0, true));
+  const size_t T = (size_t)n_periods, B = (size_t)b->B, N = (size_t)c->N, M = (size_t)c->M, P = (size_t)c->cfg.dim_p;
+  const size_t ds = (size_t)c->ds, da = (size_t)c->da;
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  if (params) {
+    const size_t n = T * B * (size_t)n_steps * M * P;
+    TRY(ensure(&b->params, &b->params_cap, n));
+    TRY(h2d(c, b->params, params, n * sizeof(float)));
+  }
+  if (plant_params) {
+    TRY(ensure(&b->plant, &b->plant_cap, B * P));
+    TRY(h2d(c, b->plant, plant_params, B * P * sizeof(float)));
+  }
+  const size_t n_rec = T * B * (ds + da + (pw_out ? N : 0));
+  TRY(ensure(&b->rec, &b->rec_cap, n_rec));
+  SvbEpisode ep;
+  ep.T = n_periods;
+  ep.plant = plant_params ? b->plant : nullptr;
+  ep.states_out = b->rec;
+  ep.actions_out = ep.states_out + T * B * ds;
+  ep.pw_out = pw_out ? ep.actions_out + T * B * da : nullptr;
+  TRY(svb_go(b, states, n_steps, nullptr, params ? b->params : nullptr, 0, active, true, nullptr, &ep));
+  // the records come back once; the rows of inactive environments stay out of the caller's arrays
+  std::vector<float> host(n_rec);
+  HIP_TRY(hipMemcpyAsync(host.data(), b->rec, n_rec * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (a_seq) TRY(rows_d2h(b->B, c->stream, a_seq, b->a_seq_out, (size_t)c->D, active));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  auto rows = [&](float *dst, const float *src, size_t row) {
+    if (!active) {
+      memcpy(dst, src, T * B * row * sizeof(float));
+      return;
+    }
+    for (size_t t = 0; t < T; ++t)
+      for (size_t e = 0; e < B; ++e)
+        if (active[e]) memcpy(dst + (t * B + e) * row, src + (t * B + e) * row, row * sizeof(float));
+  };
+  rows(states_out, host.data(), ds);
+  rows(actions_out, host.data() + T * B * ds, da);
+  if (pw_out) rows(pw_out, host.data() + T * B * (ds + da), N);
+  return DUST_OK;
 }
 
 #include "mpf.hpp"

@@ -103,6 +103,9 @@ struct SvbDims {
   static constexpr int DS = MODEL == DUST_MODEL_PENDULUM ? 2 : (MODEL == DUST_MODEL_SKID_STEER ? 5 : 4);
 };
 
+// floats of the tick's dynamic LDS (svb_tick lays them out); a staged navigation map lies behind them
+__host__ __device__ __forceinline__ int svb_lds_floats(int N, int D, int M) { return 2 * SVB_PART + 3 * N * D + N * N + M * SVB_COEF + 4 * N + 4; }
+
 // the barrier between two phases: device-memory rows written in one are read in the next (same CU: one L1), LDS likewise
 __device__ __forceinline__ void svb_sync() {
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -308,19 +311,29 @@ __device__ __forceinline__ void svb_draw_row(const SvmpcBatchArgs &a, const SvbP
     if (p < pri.P) row[p] = mean[p] + bw[p] * zp[p];
 }
 
-// The tick of environment blockIdx.x.  PRIOR: the dynamics samples are drawn in phase 0 from the environment's filter (`pri`), not read
-// from a.params; nothing else differs.  NAV: the skid-steer tick with the navigation cost family (`nav`; one map for the whole batch) -
-// a map of nav->grid_words > 0 words is staged ONCE per launch into the dynamic LDS behind the tick's own, ahead of the iteration loop;
-// otherwise the lookups of phase C read it in place.
-template <int MODEL, bool PRIOR, bool NAV = false>
-__device__ __forceinline__ void svb_body(const SvmpcBatchArgs &a, const SvbPrior *pri, const SkidNav *nav = nullptr) {
-  static_assert(!NAV || MODEL == DUST_MODEL_SKID_STEER, "the navigation cost family is the skid-steer robot's");
+// What one tick of an environment starts from and hands to the next beside its device rows: the state, the Philox position {tick, iter},
+// the optimiser's step count and whether the prior means alias the particles.  Every lane keeps the same copy in registers; svb_begin
+// reads it, svb_tick advances it, svb_end stores it (lane 0).  A kernel that runs several ticks in one launch (svmpc_episode.hpp) keeps
+// it in registers between them: these words sit at one address per environment, and a uniform-address read of what lane 0 stored a
+// tick earlier could be served by the scalar cache.
+template <int MODEL>
+struct SvbCarry {
+  float x0[SvbDims<MODEL>::DS];
+  uint32_t ctr_tick, ctr_iter, opt_t;
+  bool alias;
+};
+
+// The tick of environment blockIdx.x from the carry `cy`.  PRIOR: the dynamics samples are drawn in phase 0 from the environment's filter
+// (`pri`), not read from `params` ([B][n_steps][M][P], this tick's rows); nothing else differs.  NAV: the skid-steer tick with the
+// navigation cost family - `map`, `w_obs`: what svb_begin made of the SkidNav.  EPISODE (svmpc_episode.hpp): forward() also hands out the
+// first action of the sequence it chose (`act0` [da], every lane) and writes its particle weights to `pw_rec` ([N] or nullptr) too.
+template <int MODEL, bool PRIOR, bool NAV, bool EPISODE>
+__device__ __forceinline__ void svb_tick(const SvmpcBatchArgs &a, const SvbPrior *pri, const float *params, SvbCarry<MODEL> &cy, const DevModel &map,
+                                         const float w_obs, float *pw_rec = nullptr, float *act0 = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  constexpr int DS = SvbDims<MODEL>::DS;
   constexpr int T = SVB_THREADS;
   constexpr float LOG2E = 1.44269504088896340736f;
   const int env = (int)blockIdx.x;
-  if (a.active && a.active[env] == 0) return;
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int N = a.N, S = a.S, M = a.M, H = a.H, da = a.da, D = a.D;
   const int ND = N * D, NS = N * S;
@@ -348,35 +361,14 @@ __device__ __forceinline__ void svb_body(const SvmpcBatchArgs &a, const SvbPrior
   float *s0p = a.opt_s0 ? a.opt_s0 + (size_t)env * ND : nullptr;
   float *s1p = a.opt_s1 ? a.opt_s1 + (size_t)env * ND : nullptr;
   float *s2p = a.opt_s2 ? a.opt_s2 + (size_t)env * ND : nullptr;
-  uint32_t *ctr = a.ctr + (size_t)env * 4;
-  const bool alias = a.alias[env] != 0;
+  const bool alias = cy.alias;
   const uint64_t seed = a.seeds[env];
-  uint32_t ctr_tick = ctr[0], ctr_iter = ctr[1], opt_t = ctr[2];  // every lane keeps the same copy; lane 0 stores it at the end
-  float x0[DS];
-#pragma unroll
-  for (int k = 0; k < DS; ++k) x0[k] = a.states[(size_t)env * 8 + k];
+  uint32_t &ctr_tick = cy.ctr_tick, &ctr_iter = cy.ctr_iter, &opt_t = cy.opt_t;
+  const float *x0 = cy.x0;
   const bool fast_trig = MODEL == DUST_MODEL_PENDULUM && fabsf(x0[1]) <= 3.0e38f &&
                          (fabsf(x0[0]) + a.dm.max_speed_pend * (float)a.dm.dt * (float)H < 5.0e4f);
   const bool same_w = (a.alpha * a.temp == 1.0f);  // temperature = 1 / alpha (every demo): omega and w are the same softmax
   auto col2 = [&](const float *v, const int j) { return (da == 2 && (j & 1)) ? v[1] : v[0]; };
-  DevModel map;    // (NAV alone) what collision() reads: skid.hpp skid_nav_map's fields
-  float w_obs = 0.f;
-  if constexpr (NAV) {
-    map.inv_cell = nav->inv_cell;
-    map.off_x = nav->off_x;
-    map.off_y = nav->off_y;
-    map.nx = nav->nx;
-    map.ny = nav->ny;
-    map.grid_bits = nav->grid_bits;
-    w_obs = nav->w_obs;
-    if (nav->grid_words > 0 && a.n_steps > 0) {  // (the same for every lane of the launch; a lone forward() looks nothing up)
-      uint32_t *grid = reinterpret_cast<uint32_t *>(misc + 4);  // behind svmpc_batch_lds_bytes(): 4 nav->grid_words bytes
-      const int words = (nav->nx * nav->ny + 31) >> 5;          // (grid_words is this rounded up to 4: the allocation ends at `words`)
-      for (int w = tid; w < words; w += T) grid[w] = nav->grid_bits[w];
-      map.grid_bits = grid;
-      svb_sync();
-    }
-  }
 
   for (int it = 0; it < a.n_steps; ++it) {
     // ---- 0: stage
@@ -395,7 +387,7 @@ __device__ __forceinline__ void svb_body(const SvmpcBatchArgs &a, const SvbPrior
     }
     for (int i = tid; i < N; i += T) lmx[i] = a.logmix[(size_t)env * N + i];
     for (int m = tid; m < M; m += T) {
-      const float *prow = PRIOR ? part + m * 4 : (a.params ? a.params + (((size_t)env * a.n_steps + it) * M + m) * a.P : nullptr);
+      const float *prow = PRIOR ? part + m * 4 : (params ? params + (((size_t)env * a.n_steps + it) * M + m) * a.P : nullptr);
       float cf[SVB_COEF];
       svb_coef<MODEL>(a, prow, cf);
       constexpr int NC = (MODEL == DUST_MODEL_PENDULUM || MODEL == DUST_MODEL_PARTICLE) ? 2 : (MODEL == DUST_MODEL_SKID_STEER ? 3 : SVB_COEF);
@@ -635,6 +627,9 @@ __device__ __forceinline__ void svb_body(const SvmpcBatchArgs &a, const SvbPrior
       const float lz = m + logf(z);
       const float p = lane < N ? expf(v - lz) : 0.f;
       if (lane < N) g_pw[lane] = p;
+      if constexpr (EPISODE) {
+        if (pw_rec && lane < N) pw_rec[lane] = p;
+      }
       float best = lane < N ? p : -INFINITY;  // first index of the maximum (torch.argmax on CPU)
       int bi = lane < N ? lane : 0x7fffffff;
       for (int o = 32; o > 0; o >>= 1) {
@@ -672,6 +667,10 @@ __device__ __forceinline__ void svb_body(const SvmpcBatchArgs &a, const SvbPrior
     svb_sync();
     const int bi = misc[0];
     for (int d = tid; d < D; d += T) a.a_seq_out[(size_t)env * D + d] = th[bi * D + d];
+    if constexpr (EPISODE) {  // a_seq[0] for the plant, from the LDS row every lane can read
+      act0[0] = th[bi * D];
+      if (da == 2) act0[1] = th[bi * D + 1];
+    }
     for (int e = tid; e < ND; e += T) {  // theta.roll(-1, dims=-2), the last row by strategy (svmpc.py:142-158)
       const int n = e / D, j = e - n * D, t = j / da, c = j - t * da;
       const float *row = th + n * D;
@@ -688,15 +687,70 @@ __device__ __forceinline__ void svb_body(const SvmpcBatchArgs &a, const SvbPrior
       if (s2p) s2p[e] = 0.f;
     }
     if (tid == 0) a.alias[env] = 1;
+    cy.alias = true;
     ctr_tick += 1u;
     ctr_iter = 0u;
     opt_t = 0u;
   }
-  if (tid == 0) {
-    ctr[0] = ctr_tick;
-    ctr[1] = ctr_iter;
-    ctr[2] = opt_t;
+}
+
+// The carry of environment blockIdx.x from its device words and the call's state.  NAV: `map` / `w_obs` from the SkidNav (one map for
+// the whole batch) - a map of nav->grid_words > 0 words is staged ONCE per launch into the dynamic LDS behind the tick's own, ahead of
+// the iteration loop; otherwise the lookups of phase C read it in place.
+template <int MODEL, bool NAV>
+__device__ __forceinline__ void svb_begin(const SvmpcBatchArgs &a, const SkidNav *nav, SvbCarry<MODEL> &cy, DevModel &map, float &w_obs) {
+  static_assert(!NAV || MODEL == DUST_MODEL_SKID_STEER, "the navigation cost family is the skid-steer robot's");
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  constexpr int DS = SvbDims<MODEL>::DS;
+  const int env = (int)blockIdx.x;
+  const uint32_t *ctr = a.ctr + (size_t)env * 4;
+  cy.alias = a.alias[env] != 0;
+  cy.ctr_tick = ctr[0];
+  cy.ctr_iter = ctr[1];
+  cy.opt_t = ctr[2];
+#pragma unroll
+  for (int k = 0; k < DS; ++k) cy.x0[k] = a.states[(size_t)env * 8 + k];
+  w_obs = 0.f;
+  if constexpr (NAV) {  // what collision() reads: skid.hpp skid_nav_map's fields
+    map.inv_cell = nav->inv_cell;
+    map.off_x = nav->off_x;
+    map.off_y = nav->off_y;
+    map.nx = nav->nx;
+    map.ny = nav->ny;
+    map.grid_bits = nav->grid_bits;
+    w_obs = nav->w_obs;
+    if (nav->grid_words > 0 && a.n_steps > 0) {  // (the same for every lane of the launch; a lone forward() looks nothing up)
+      // behind svmpc_batch_lds_bytes(): 4 nav->grid_words bytes
+      uint32_t *grid = reinterpret_cast<uint32_t *>(lds + svb_lds_floats(a.N, a.D, a.M));
+      const int words = (nav->nx * nav->ny + 31) >> 5;  // (grid_words is this rounded up to 4: the allocation ends at `words`)
+      for (int w = (int)threadIdx.x; w < words; w += SVB_THREADS) grid[w] = nav->grid_bits[w];
+      map.grid_bits = grid;
+      svb_sync();
+    }
   }
+}
+
+// lane 0 stores the carry's counters (the alias flag: forward() stored it)
+template <int MODEL>
+__device__ __forceinline__ void svb_end(const SvmpcBatchArgs &a, const SvbCarry<MODEL> &cy) {
+  if (threadIdx.x == 0) {
+    uint32_t *ctr = a.ctr + (size_t)blockIdx.x * 4;
+    ctr[0] = cy.ctr_tick;
+    ctr[1] = cy.ctr_iter;
+    ctr[2] = cy.opt_t;
+  }
+}
+
+// one tick per launch: optimize, forward, or both
+template <int MODEL, bool PRIOR, bool NAV = false>
+__device__ __forceinline__ void svb_body(const SvmpcBatchArgs &a, const SvbPrior *pri, const SkidNav *nav = nullptr) {
+  if (a.active && a.active[blockIdx.x] == 0) return;
+  SvbCarry<MODEL> cy;
+  DevModel map;
+  float w_obs;
+  svb_begin<MODEL, NAV>(a, nav, cy, map, w_obs);
+  svb_tick<MODEL, PRIOR, NAV, false>(a, pri, a.params, cy, map, w_obs);
+  svb_end(a, cy);
 }
 
 template <int MODEL>
@@ -757,8 +811,6 @@ __global__ __launch_bounds__(64) void svmpc_batch_logmix_kernel(const float *w, 
   if (lane < N) logmix[(size_t)env * N + lane] = l - (lm + logf(zs));
 }
 
-static inline size_t svmpc_batch_lds_bytes(int N, int D, int M) {
-  return sizeof(float) * ((size_t)2 * SVB_PART + (size_t)3 * N * D + (size_t)N * N + (size_t)M * SVB_COEF + (size_t)4 * N + 4);
-}
+static inline size_t svmpc_batch_lds_bytes(int N, int D, int M) { return sizeof(float) * (size_t)svb_lds_floats(N, D, M); }
 
 }  // namespace dust

@@ -1,0 +1,109 @@
+// svmpc_episode.hpp - closed-loop episodes on the device: T control periods of B independent environments in ONE launch.
+// Workgroup b runs, for t = 0 .. T - 1, the loop of the reference's run_simulation (dust/utils/simulations.py:104-130) on environment b:
+//   1  the tick of svmpc_batch.hpp (svb_tick, the very function svmpc_batch_kernel runs: n_steps SVGD iterations and forward()) from the
+//      state the previous period left, with the dynamics rows params[t][b][it][m][:] and device-drawn noise - forward() moves the Philox
+//      position to {tick + 1, 0}, so period t draws what the t-th successive dust_svmpc_batch_tick would draw;
+//   2  the plant: x <- step(x, a_seq[0]) with the first action of the sequence forward() chose BEFORE the roll, through the family's own
+//      device step - the one the rollouts of phase C call (common.hpp model_step, skid.hpp skid_step, cartpole.hpp cartpole_step; for
+//      Particle with the collision freeze on its occupancy grid), the action clamped as the rollouts clamp it - under the coefficients
+//      svb_coef makes of the environment's TRUE parameter row plant[b][:] (the columns and the space of `params`; NULL: the prototype's
+//      nominal model).  Plants are deterministic;
+//   3  the records states_out[t][b][:] (the state after the step), actions_out[t][b][:] (the raw a_seq[0]) and pw_out[t][b][:] (the
+//      particle weights of forward()).
+// As in the batched tick there is no arrival word, nothing to spin on and no traffic between workgroups; the loop is bounded by T.
+//
+// What a period hands to the next never passes through memory that one lane writes and all lanes re-read at one address: the state, the
+// Philox position, the optimiser's step count and the alias flag stay in registers (SvbCarry: every lane computes the same plant step
+// from the same a_seq[0], which it reads from the particles' LDS rows); the particles, prior means, mixture log-weights, a_mat and
+// optimiser state are per-lane rows in device memory, read by vector loads behind the period's closing svb_sync().  So no scalar load
+// can return the previous period's value.
+//
+// Launch shape: the batched tick's - 512 lanes, one workgroup per environment, svmpc_batch_lds_bytes() of dynamic LDS (plus the map in
+// the navigation instance).  The navigation instance stages its map ONCE per launch, ahead of the period loop, as the batched tick
+// does ahead of its iteration loop; restaging it every period has not been measured, nor has the difference.
+#pragma once
+#include "svmpc_batch.hpp"
+
+namespace dust {
+
+struct SvbEpisode {
+  int T;               // periods
+  const float *plant;  // [B][P] true parameter rows or nullptr (nominal plants)
+  float *states_out;   // [T][B][ds]
+  float *actions_out;  // [T][B][da]
+  float *pw_out;       // [T][B][N] or nullptr
+};
+struct SvmpcEpisodeArgs {
+  SvmpcBatchArgs k;  // params: [T][B][n_steps][M][P]; n_steps >= 1, do_forward and philox set
+  SvbEpisode ep;
+};
+struct SvmpcNavEpisodeArgs {
+  SvmpcBatchArgs k;
+  SvbEpisode ep;
+  SkidNav nav;
+};
+
+// x <- step(x, act) of the family's plant under the coefficients cf (svb_coef); `act` is the raw action
+template <int MODEL>
+__device__ __forceinline__ void svb_plant_step(const SvmpcBatchArgs &a, const float *cf, float *x, const float *act) {
+  if constexpr (MODEL == DUST_MODEL_PENDULUM || MODEL == DUST_MODEL_PARTICLE) {
+    Coef c;
+    c.c0 = cf[0];
+    c.c1 = cf[1];
+    model_step<MODEL>(a.dm, c, x, act);
+  } else if constexpr (MODEL == DUST_MODEL_SKID_STEER) {
+    skid_step(x, clampf(act[0], a.sk.lo[0], a.sk.hi[0]), clampf(act[1], a.sk.lo[1], a.sk.hi[1]), cf[0], cf[1], cf[2], a.dt);
+  } else {
+    CartCoef kf;
+    kf.g = cf[0];
+    kf.mp = cf[1];
+    kf.len = cf[2];
+    kf.muc = cf[3];
+    kf.mup = cf[4];
+    kf.fmag = cf[5];
+    kf.mass = cf[6];
+    kf.pm = cf[7];
+    kf.k43 = cf[8];
+    kf.dt = cf[9];
+    cartpole_step(x, clampf(act[0], -1.0f, 1.0f), kf, fast_sinf(x[2]), fast_cosf(x[2]));
+  }
+}
+
+template <int MODEL, bool NAV>
+__device__ __forceinline__ void svb_episode_body(const SvmpcBatchArgs &a, const SvbEpisode &ep, const SkidNav *nav) {
+  constexpr int DS = SvbDims<MODEL>::DS;
+  const int env = (int)blockIdx.x, B = (int)gridDim.x;
+  if (a.active && a.active[env] == 0) return;
+  SvbCarry<MODEL> cy;
+  DevModel map;
+  float w_obs;
+  svb_begin<MODEL, NAV>(a, nav, cy, map, w_obs);
+  float cf[SVB_COEF];
+  svb_coef<MODEL>(a, ep.plant ? ep.plant + (size_t)env * a.P : nullptr, cf);
+  const size_t per = (size_t)B * a.n_steps * a.M * a.P;  // parameter rows of one period
+  for (int t = 0; t < ep.T; ++t) {
+    const size_t row = (size_t)t * B + env;
+    float act[2] = {0.f, 0.f};
+    svb_tick<MODEL, false, NAV, true>(a, nullptr, a.params ? a.params + (size_t)t * per : nullptr, cy, map, w_obs,
+                                      ep.pw_out ? ep.pw_out + row * a.N : nullptr, act);
+    svb_plant_step<MODEL>(a, cf, cy.x0, act);
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int k = 0; k < DS; ++k) ep.states_out[row * DS + k] = cy.x0[k];
+      ep.actions_out[row * a.da] = act[0];
+      if (a.da == 2) ep.actions_out[row * 2 + 1] = act[1];
+    }
+    svb_sync();  // the roll has read the particles' LDS rows, the next period's phase 0 overwrites them
+  }
+  svb_end(a, cy);
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(SVB_THREADS) void svmpc_episode_kernel(const SvmpcEpisodeArgs ka) {
+  svb_episode_body<MODEL, false>(ka.k, ka.ep, nullptr);
+}
+__global__ __launch_bounds__(SVB_THREADS) void svmpc_skid_nav_episode_kernel(const SvmpcNavEpisodeArgs ka) {
+  svb_episode_body<DUST_MODEL_SKID_STEER, true>(ka.k, ka.ep, &ka.nav);
+}
+
+}  // namespace dust

@@ -350,3 +350,35 @@ class BatchSVMPC:
         a_seq, pw = batch.tick(self._states(states), n_steps, self._eps(eps), self._params(params_dist, n_steps, on, params),
                                None if active is None else on)
         return torch.from_numpy(a_seq), torch.from_numpy(pw)
+
+    # -- simulations.py:104-130 for every environment: optimize, forward, first action to the plant, new state, repeat
+    def run_episodes(self, states, params_dist, n_periods, plant_params=None, n_steps=None, active=None, params=None):
+        """`n_periods` closed-loop periods of every active environment in ONE launch (dust_svmpc_batch_episode): the plants are stepped
+        on the device, with the first action of every period's sequence, by the model's own step under the environment's TRUE
+        parameters `plant_params` [B, P] (the columns and the space of the controller's dynamics samples; None: the nominal model),
+        without process noise.  states [B, ds]: where the episodes start.  The dynamics samples are drawn as `n_periods` successive
+        draws of tick() in period order - under one torch.manual_seed the call consumes the torch stream exactly as `n_periods` calls
+        of tick() do - unless `params` [T, B, n_steps, M, P] overrides them.
+        -> (states [T, B, ds] after every step, actions [T, B, da], p_weights [T, B, N], a_seq [B, H, da] of the last period); the rows
+        of inactive environments are NaN."""
+        check_optimizer(self.optimizer, self._opt_group)
+        ctrl = self.likelihood.controller
+        T = int(n_periods)
+        if not 1 <= T <= 4096:
+            raise ValueError("n_periods = %d outside [1, 4096]: one launch runs one episode piece, split a longer one" % T)
+        on = self._active(active)
+        P = len(self.likelihood.model.uncertain_params or ()) if ctrl._sampling else 0
+        if plant_params is not None:
+            plant_params = np.asarray(torch.as_tensor(plant_params, dtype=torch.float).numpy(), np.float32)
+            if P == 0 or plant_params.shape != (self.n_envs, P):
+                raise ValueError("plant_params has shape %s, the plants read %s" % (plant_params.shape, (self.n_envs, P) if P else "none"))
+        n_steps = self.n_steps if n_steps is None else n_steps
+        batch = self._ensure_batch(params_dist)
+        if params is not None:
+            rows = np.asarray(torch.as_tensor(params, dtype=torch.float).numpy(), np.float32)
+        elif ctrl._sampling:
+            rows = np.stack([self._params(params_dist, n_steps, on, None) for _ in range(T)])
+        else:
+            rows = None
+        xs, acts, pw, a_seq = batch.episode(self._states(states), T, n_steps, rows, plant_params, None if active is None else on)
+        return torch.from_numpy(xs), torch.from_numpy(acts), torch.from_numpy(pw), torch.from_numpy(a_seq)

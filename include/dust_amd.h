@@ -465,6 +465,25 @@ int dust_svmpc_batch_optimize(dust_svmpc_batch *batch, const float *states, int 
 int dust_svmpc_batch_forward(dust_svmpc_batch *batch, const unsigned char *active, float *a_seq, float *p_weights);
 int dust_svmpc_batch_tick(dust_svmpc_batch *batch, const float *states, int n_steps, const void *eps, const float *params, int flags,
                           const unsigned char *active, float *a_seq, float *p_weights);
+/* dust_svmpc_batch_episode = T closed-loop periods of simulations.py:104-130 for every active environment in ONE launch
+ * (dust_amd/csrc/svmpc_episode.hpp): per period the tick dust_svmpc_batch_tick runs, with device-drawn noise - period t draws what the
+ * t-th successive tick would draw -, then the plant's step x <- step(x, a_seq[0]) through the family's own device step (the one the
+ * rollouts call, Particle's collision freeze included; the action clamped as the rollouts clamp it) under the environment's TRUE
+ * parameters, then the new state into the next tick.  Plants are deterministic.
+ *   states [B][ds], host: where the episodes start;
+ *   params [T][B][n_steps][M][P], host: params[t] is what dust_svmpc_batch_tick takes for period t; NULL exactly when dim_p = 0;
+ *   plant_params [B][P], host, in the columns and the space (params_log_space) of `params`; NULL: the prototype's nominal model;
+ *   flags: 0;
+ *   records, host, copied back once after the launch; the rows of inactive environments are NOT written: states_out [T][B][ds] (the
+ *     state after the step), actions_out [T][B][da] (the raw a_seq[0]), pw_out [T][B][N] or NULL (the particle weights), a_seq
+ *     [B][H][da] of the LAST period (before the roll) or NULL.
+ * Afterwards the batch is in the state T ticks would have left it in (getters, counters, noise streams).  The call waits for the device.
+ * DUST_ERR_INVALID (before any launch): NULL states / states_out / actions_out, n_steps < 1, n_periods outside [1, 4096] (a launch runs
+ * T ticks' worth of time; the cap keeps one launch on a shared device short - split a longer episode, the pieces concatenate bit for
+ * bit), params or plant_params with dim_p = 0, missing params with dim_p > 0.  DUST_ERR_UNSUPPORTED: any flag. */
+int dust_svmpc_batch_episode(dust_svmpc_batch *batch, const float *states, int n_periods, int n_steps, const float *params,
+                             const float *plant_params, int flags, const unsigned char *active, float *states_out, float *actions_out,
+                             float *pw_out, float *a_seq);
 
 /* stage outputs of the last call, for parity tests ([S][N] / [N][H][da] / [N]) */
 int dust_get_costs(dust_ctx *ctx, float *costs);
