@@ -678,36 +678,27 @@ def _mask(active, B):
     return m, m.ctypes.data_as(C.POINTER(C.c_ubyte))
 
 
-class AmppiBatch:
-    """B independent AMPPI ticks in one launch (dust_amppi_batch_*): per environment a state, a nominal sequence, a noise stream and
-    parameter rows; model, cost, horizon, S, lambda and a_cov are the prototype context's.  `ctx` is the batch's inner context
-    (borrowed) for sync() and profile() / profile_get()."""
+def _seeds(seeds, B):
+    """the environments' Philox keys as [B] uint64 (None: the library's default) -> (array or None, ctypes pointer or None)"""
+    if seeds is None:
+        return None, None
+    sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
+    if sd.size != B:
+        raise ValueError("seeds has %d entries for %d environments" % (sd.size, B))
+    return sd, sd.ctypes.data_as(C.POINTER(C.c_uint64))
 
-    def __init__(self, proto=None, n_envs=1, seeds=None, _handle=None):
-        self._h = None
-        lib = L.load()
-        if _handle is None:
-            sd = None
-            if seeds is not None:
-                sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
-                if sd.size != int(n_envs):
-                    raise ValueError("seeds has %d entries for %d environments" % (sd.size, int(n_envs)))
-            h = L.VP()
-            L.check(lib.dust_amppi_batch_create(proto._h, int(n_envs), None if sd is None else sd.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(h)))
-            _handle = h
-        self._h = _handle
-        self.B = int(n_envs)
-        inner = L.VP()
-        L.check(lib.dust_amppi_batch_ctx(self._h, C.byref(inner)))
-        self.ctx = Context(_handle=inner)
-        self.ctx._borrowed = True
-        c = self.ctx
-        self.S, self.H, self.da, self.ds, self.P, self.M = c.S, c.H, c.da, c.ds, c.P, c.M
+
+class _BatchHandle:
+    """The lifetime of a batch's C handle `_h`; a class names its library symbols in `_destroy` and `_clone`.  A controller batch's
+    borrowed inner context `ctx` is closed ahead of the handle."""
+
+    _destroy = _clone = None
 
     def close(self):
-        if self._h is not None:
-            self.ctx.close()
-            L.load().dust_amppi_batch_destroy(self._h)
+        if getattr(self, "_h", None) is not None:
+            if getattr(self, "ctx", None) is not None:
+                self.ctx.close()
+            getattr(L.load(), self._destroy)(self._h)
             self._h = None
 
     def __del__(self):
@@ -718,11 +709,36 @@ class AmppiBatch:
 
     def clone(self):
         h = L.VP()
-        L.check(L.load().dust_amppi_batch_clone(self._h, C.byref(h)))
-        return AmppiBatch(n_envs=self.B, _handle=h)
+        L.check(getattr(L.load(), self._clone)(self._h, C.byref(h)))
+        return type(self)(self, n_envs=self.B, _handle=h)  # (the source in the prototype's place: a filter batch reads its sizes there)
 
     def __deepcopy__(self, memo):
         return self.clone()
+
+
+class AmppiBatch(_BatchHandle):
+    """B independent AMPPI ticks in one launch (dust_amppi_batch_*): per environment a state, a nominal sequence, a noise stream and
+    parameter rows; model, cost, horizon, S, lambda and a_cov are the prototype context's.  `ctx` is the batch's inner context
+    (borrowed) for sync() and profile() / profile_get()."""
+
+    _destroy, _clone = "dust_amppi_batch_destroy", "dust_amppi_batch_clone"
+
+    def __init__(self, proto=None, n_envs=1, seeds=None, _handle=None):
+        self._h = None
+        lib = L.load()
+        if _handle is None:
+            sd, sp = _seeds(seeds, int(n_envs))
+            h = L.VP()
+            L.check(lib.dust_amppi_batch_create(proto._h, int(n_envs), sp, C.byref(h)))
+            _handle = h
+        self._h = _handle
+        self.B = int(n_envs)
+        inner = L.VP()
+        L.check(lib.dust_amppi_batch_ctx(self._h, C.byref(inner)))
+        self.ctx = Context(_handle=inner)
+        self.ctx._borrowed = True
+        c = self.ctx
+        self.S, self.H, self.da, self.ds, self.P, self.M = c.S, c.H, c.da, c.ds, c.P, c.M
 
     def set_a_seq(self, a):
         L.check(L.load().dust_amppi_batch_set_a_seq(self._h, _p(_f(a, (self.B, self.H, self.da)))))
@@ -766,11 +782,7 @@ class AmppiBatch:
         st = None if states is None else _f(states, (B, self.ds))
         ap = None if actions_prev is None else _f(actions_prev, (B, self.da))
         act = None if actions is None else _f(actions, (B, S, self.H, self.da))
-        sd = None
-        if seeds is not None:
-            sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
-            if sd.size != B:
-                raise ValueError("seeds has %d entries for %d environments" % (sd.size, B))
+        sd, sp = _seeds(seeds, B)
         _, mp = _mask(active, B)
         costs = omega = a_seq = bw = None
         if want_outputs:
@@ -778,8 +790,7 @@ class AmppiBatch:
         rows = self.M if self.M > 1 else (1 if shared_params else S)
         pout = np.full((B, rows, max(self.P, 1)), np.nan, np.float32) if want_params else None
         L.check(L.load().dust_amppi_dual_batch_tick(self._h, mpf._h, _p(st), _p(ap), _vp(act), int(flags) | (L.AMPPI_PARAMS_SHARED if shared_params else 0),
-                                                    int(mpf_steps), float(-1.0 if mpf_bw is None else mpf_bw),
-                                                    None if sd is None else sd.ctypes.data_as(C.POINTER(C.c_uint64)), int(roll), mp,
+                                                    int(mpf_steps), float(-1.0 if mpf_bw is None else mpf_bw), sp, int(roll), mp,
                                                     _p(costs), _p(omega), _p(a_seq), _p(pout), _p(bw)))
         return costs, omega, a_seq, pout, bw
 
@@ -795,22 +806,20 @@ class AmppiBatch:
         L.check(L.load().dust_amppi_batch_roll(self._h, int(steps), mp))
 
 
-class SvmpcBatch:
+class SvmpcBatch(_BatchHandle):
     """B independent SVMPC ticks in one launch (dust_svmpc_batch_*): per environment a state, particles, a prior, a_mat, optimiser
     state, a noise stream and dynamics samples; everything else is the prototype context's.  `ctx` is the batch's inner context
     (borrowed) for sync() and profile() / profile_get()."""
+
+    _destroy, _clone = "dust_svmpc_batch_destroy", "dust_svmpc_batch_clone"
 
     def __init__(self, proto=None, n_envs=1, seeds=None, _handle=None):
         self._h = None
         lib = L.load()
         if _handle is None:
-            sd = None
-            if seeds is not None:
-                sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
-                if sd.size != int(n_envs):
-                    raise ValueError("seeds has %d entries for %d environments" % (sd.size, int(n_envs)))
+            sd, sp = _seeds(seeds, int(n_envs))
             h = L.VP()
-            L.check(lib.dust_svmpc_batch_create(proto._h, int(n_envs), None if sd is None else sd.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(h)))
+            L.check(lib.dust_svmpc_batch_create(proto._h, int(n_envs), sp, C.byref(h)))
             _handle = h
         self._h = _handle
         self.B = int(n_envs)
@@ -824,26 +833,6 @@ class SvmpcBatch:
         self._shapes = {L.SVB_THETA: (B, N, H, da), L.SVB_PRIOR_MEANS: (B, N, H, da), L.SVB_PRIOR_MIX: (B, N), L.SVB_A_MAT: (B, N, H, da),
                         L.SVB_COSTS: (B, S, N), L.SVB_SCORE: (B, N, H, da), L.SVB_PHI: (B, N, H, da), L.SVB_LOG_L: (B, N),
                         L.SVB_LOG_P: (B, N), L.SVB_A_MIX: (B, N), L.SVB_ACTIONS: (B, S, N, H, da)}
-
-    def close(self):
-        if self._h is not None:
-            self.ctx.close()
-            L.load().dust_svmpc_batch_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def clone(self):
-        h = L.VP()
-        L.check(L.load().dust_svmpc_batch_clone(self._h, C.byref(h)))
-        return SvmpcBatch(n_envs=self.B, _handle=h)
-
-    def __deepcopy__(self, memo):
-        return self.clone()
 
     def set(self, what, value):
         """THETA / PRIOR_MEANS / A_MAT [B, N, H, da], PRIOR_MIX [B, N] (`what`: _lib.SVB_*)"""
@@ -935,27 +924,24 @@ class SvmpcBatch:
         B = self.B
         st, e, _, fl = self._inputs(states, n_steps, eps, None, eps_dev_ptr, keep_actions)
         ap = None if actions_prev is None else _f(actions_prev, (B, self.da))
-        sd = None
-        if seeds is not None:
-            sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
-            if sd.size != B:
-                raise ValueError("seeds has %d entries for %d environments" % (sd.size, B))
+        sd, sp = _seeds(seeds, B)
         _, mp = _mask(active, B)
         a_seq = pw = bw = None
         if want_outputs:
             a_seq, pw, bw = (np.full(sh, np.nan, np.float32) for sh in ((B, self.H, self.da), (B, self.N), (B,)))
         pout = np.full((B, int(n_steps), self.M, max(self.P, 1)), np.nan, np.float32) if want_params else None
         L.check(L.load().dust_svmpc_dual_batch_tick(self._h, mpf._h, _p(st), _p(ap), int(n_steps), e if eps_dev_ptr else _vp(e), int(flags) | fl,
-                                                    int(mpf_steps), float(-1.0 if mpf_bw is None else mpf_bw),
-                                                    None if sd is None else sd.ctypes.data_as(C.POINTER(C.c_uint64)), mp,
+                                                    int(mpf_steps), float(-1.0 if mpf_bw is None else mpf_bw), sp, mp,
                                                     _p(a_seq), _p(pw), _p(pout), _p(bw)))
         return a_seq, pw, pout, bw
 
 
-class MpfBatch:
+class MpfBatch(_BatchHandle):
     """B dynamics filters of one configuration, updated in one launch (dust_mpf_batch_*): per environment its particles, optimiser
     state, observations, past action and bandwidths; model, obs_std, optimiser options, Mp and P are the prototype filter's.
     Environment b computes what a lone `MpfContext` created under DUST_MPF_GRID=0 computes on its inputs, bit for bit."""
+
+    _destroy, _clone = "dust_mpf_batch_destroy", "dust_mpf_batch_clone"
 
     def __init__(self, proto=None, n_envs=1, _handle=None, _like=None):
         self._h = None
@@ -967,25 +953,6 @@ class MpfBatch:
             L.check(L.load().dust_mpf_batch_create(proto._h, self.B, C.byref(h)))
             _handle = h
         self._h = _handle
-
-    def close(self):
-        if getattr(self, "_h", None) is not None:
-            L.load().dust_mpf_batch_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def clone(self):
-        h = L.VP()
-        L.check(L.load().dust_mpf_batch_clone(self._h, C.byref(h)))
-        return MpfBatch(n_envs=self.B, _handle=h, _like=self)
-
-    def __deepcopy__(self, memo):
-        return self.clone()
 
     def set_particles(self, x):
         L.check(L.load().dust_mpf_batch_set_particles(self._h, _p(_f(x, (self.B, self.Mp, self.P)))))

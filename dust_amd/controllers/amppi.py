@@ -13,6 +13,7 @@ import torch
 
 from ..backend import Context
 from ..costs import QuadraticCost, cost_grid, cost_grid_key, recognise
+from ..inference.svmpc import _active
 from ..utils.utf import MerweScaledUTF
 
 
@@ -260,12 +261,7 @@ class BatchAMPPI(AMPPI):
             self._batch.set_a_seq(self._a_seq.numpy())
 
     def _active(self, active):
-        if active is None:
-            return np.ones(self.n_envs, bool)
-        a = np.asarray(active).reshape(-1) != 0
-        if a.shape != (self.n_envs,):
-            raise ValueError("active has %d entries for %d environments" % (a.size, self.n_envs))
-        return a
+        return _active(active, self.n_envs)
 
     def roll(self, steps=1, active=None):
         if steps < 1:

@@ -240,7 +240,69 @@ class DualAMPPI:
         return action, new_state, omega
 
 
-class BatchDualAMPPI:
+class _BatchDual:
+    """What the batched dual loops share: the B filters behind the prototype `mpf` (made by the first forward()), the prior keys of a
+    period and the update a step() notes for the next forward().  A class copies its own parts in `_copy_parts(new, memo)`."""
+
+    def __init__(self, n_envs, mpf, mpf_bw, mpf_steps, seed, init_particles):
+        self.mpf, self.n_envs = mpf, n_envs
+        self.mpf_bw, self.mpf_steps = mpf_bw, int(mpf_steps)
+        self._seed, self._t, self._pending = int(seed), 0, None
+        if init_particles is not None:
+            init_particles = torch.as_tensor(init_particles, dtype=torch.float).detach().clone()
+            want = (self.n_envs, mpf._dev.Mp, mpf._dev.P)
+            if tuple(init_particles.shape) != want:
+                raise ValueError("init_particles has shape %s, the batch takes %s" % (tuple(init_particles.shape), want))
+        self._init_particles = init_particles
+        self._mb = None
+        self.ticks = 0
+        self.last_bw = None
+
+    def prior_keys(self, t):
+        """The Philox keys of period t = 1, 2, ...: seed + (b << 32) + t for environment b (modulo 2^64)."""
+        return [(self._seed + (b << 32) + int(t)) & 0xFFFFFFFFFFFFFFFF for b in range(self.n_envs)]
+
+    def __deepcopy__(self, memo):
+        new = copy.copy(self)
+        memo[id(self)] = new
+        self._copy_parts(new, memo)
+        new._mb = None if self._mb is None else self._mb.clone()
+        new._pending = None if self._pending is None else tuple(v.copy() for v in self._pending)
+        return new
+
+    def _filters(self, states=None):
+        if self._mb is None:
+            if self.mpf.draw_source is not None:
+                raise NotImplementedError("recorded filter draws (draw_source) have no batched form")
+            mb = self.mpf._dev.batch(self.n_envs)
+            if self._init_particles is not None:
+                mb.set_particles(self._init_particles.numpy())
+            if states is not None:
+                mb.set_obs(states)
+            self._mb = mb
+        return self._mb
+
+    @property
+    def dyn_particles(self):
+        """[B, Mp, P]; a noted update is carried out first"""
+        self._flush()
+        return torch.from_numpy(self._filters().get_particles())
+
+    def _flush(self):
+        pend = self._pending
+        if pend is not None:
+            _, bw = self._filters().optimize(pend[0], pend[1], self.mpf_bw, self.mpf_steps)
+            self._pending, self.last_bw = None, torch.from_numpy(bw)
+
+    def step(self, actions, new_states):
+        self._flush()
+        B = self.n_envs
+        self._pending = (torch.as_tensor(actions, dtype=torch.float).reshape(B, -1).numpy().copy(),
+                         torch.as_tensor(new_states, dtype=torch.float).reshape(B, -1).numpy().copy())
+        return None, None
+
+
+class BatchDualAMPPI(_BatchDual):
     """The dual loop over `B = controller.n_envs` plants at once: a `BatchAMPPI` and B copies of one `MPF` - the deep copies of controller
     and filter the reference makes per episode (dust/utils/simulations.py:62,78) - with a whole control period of all of them in ONE C
     call (dust_amppi_dual_batch_tick): the B filter updates in one launch, Silverman's bandwidths on the device when none is given, the
@@ -272,65 +334,21 @@ class BatchDualAMPPI:
         if tf is not None and (not tf.default_sqrt or tf.n != mpf._dev.P):
             raise NotImplementedError("a sigma-point transform with a custom sqrt_method, or over another number of parameters than the "
                                       "filter's, has no fused form - and a batch has no other")
-        self.controller, self.model, self.mpf = controller, model, mpf
-        self.n_envs = controller.n_envs
-        self.mpf_bw, self.mpf_steps, self.roll = mpf_bw, int(mpf_steps), int(roll)
-        self._seed, self._t, self._pending = int(seed), 0, None
-        if init_particles is not None:
-            init_particles = torch.as_tensor(init_particles, dtype=torch.float).detach().clone()
-            want = (self.n_envs, mpf._dev.Mp, mpf._dev.P)
-            if tuple(init_particles.shape) != want:
-                raise ValueError("init_particles has shape %s, the batch takes %s" % (tuple(init_particles.shape), want))
-        self._init_particles = init_particles
-        self._mb = None
-        self.ticks = 0
-        self.last_bw = None
+        _BatchDual.__init__(self, controller.n_envs, mpf, mpf_bw, mpf_steps, seed, init_particles)
+        self.controller, self.model, self.roll = controller, model, int(roll)
         self.last_costs = None
 
-    def prior_keys(self, t):
-        """The Philox keys of period t = 1, 2, ...: seed + (b << 32) + t for environment b (modulo 2^64)."""
-        return [(self._seed + (b << 32) + int(t)) & 0xFFFFFFFFFFFFFFFF for b in range(self.n_envs)]
-
-    def __deepcopy__(self, memo):
-        new = copy.copy(self)
-        memo[id(self)] = new
+    def _copy_parts(self, new, memo):
         new.controller = copy.deepcopy(self.controller, memo)
         new.model = copy.deepcopy(self.model, memo)
         new.mpf = copy.deepcopy(self.mpf, memo)
         if getattr(self.model, "params_dist", None) is self.mpf.prior:
             new.model.params_dist = new.mpf.prior
-        new._mb = None if self._mb is None else self._mb.clone()
-        new._pending = None if self._pending is None else tuple(v.copy() for v in self._pending)
-        return new
-
-    def _filters(self, states=None):
-        if self._mb is None:
-            if self.mpf.draw_source is not None:
-                raise NotImplementedError("recorded filter draws (draw_source) have no batched form")
-            mb = self.mpf._dev.batch(self.n_envs)
-            if self._init_particles is not None:
-                mb.set_particles(self._init_particles.numpy())
-            if states is not None:
-                mb.set_obs(states)
-            self._mb = mb
-        return self._mb
 
     @property
     def a_seq(self):
         """[B, H, da]"""
         return self.controller.a_seq
-
-    @property
-    def dyn_particles(self):
-        """[B, Mp, P]; a noted update is carried out first"""
-        self._flush()
-        return torch.from_numpy(self._filters().get_particles())
-
-    def _flush(self):
-        pend = self._pending
-        if pend is not None:
-            _, bw = self._filters().optimize(pend[0], pend[1], self.mpf_bw, self.mpf_steps)
-            self._pending, self.last_bw = None, torch.from_numpy(bw)
 
     def forward(self, states, actions=None, active=None):
         """actions [B, S, H, da]: recorded action samples in place of device-drawn noise; active [B]: the environments that tick"""
@@ -353,13 +371,6 @@ class BatchDualAMPPI:
         self.ticks += 1
         return torch.from_numpy(a_seq), torch.from_numpy(omega)
 
-    def step(self, actions, new_states):
-        self._flush()
-        B = self.n_envs
-        self._pending = (torch.as_tensor(actions, dtype=torch.float).reshape(B, -1).numpy().copy(),
-                         torch.as_tensor(new_states, dtype=torch.float).reshape(B, -1).numpy().copy())
-        return None, None
-
     def tick(self, states, plant):
         """One loop iteration with a host plant callable `plant(states [B, ds], actions [B, da]) -> new_states [B, ds]`: forward,
         plant, step.  Returns (actions, new_states, omega)."""
@@ -370,7 +381,7 @@ class BatchDualAMPPI:
         return actions, new_states, omega
 
 
-class BatchDualSVMPC:
+class BatchDualSVMPC(_BatchDual):
     """The DuSt-MPC loop over `B = svmpc.n_envs` plants at once: a `BatchSVMPC` and B copies of one `MPF` - the deep copies of controller
     and filter the reference makes per episode (dust/utils/simulations.py:62,78) - with a whole control period of all of them in ONE C
     call (dust_svmpc_dual_batch_tick): the B filter updates in one launch, Silverman's bandwidths on the device when none is given, then
@@ -400,44 +411,12 @@ class BatchDualSVMPC:
             raise ValueError("BatchDualSVMPC needs a controller that samples dynamics parameters: params_sampling=None reads no filter")
         if mpf.draw_source is not None:
             raise NotImplementedError("recorded filter draws (draw_source) have no batched form")
-        self.svmpc, self.mpf = svmpc, mpf
-        self.n_envs = svmpc.n_envs
-        self.mpf_bw, self.mpf_steps, self.n_steps = mpf_bw, int(mpf_steps), n_steps
-        self._seed, self._t, self._pending = int(seed), 0, None
-        if init_particles is not None:
-            init_particles = torch.as_tensor(init_particles, dtype=torch.float).detach().clone()
-            want = (self.n_envs, mpf._dev.Mp, mpf._dev.P)
-            if tuple(init_particles.shape) != want:
-                raise ValueError("init_particles has shape %s, the batch takes %s" % (tuple(init_particles.shape), want))
-        self._init_particles = init_particles
-        self._mb = None
-        self.ticks = 0
-        self.last_bw = None
+        _BatchDual.__init__(self, svmpc.n_envs, mpf, mpf_bw, mpf_steps, seed, init_particles)
+        self.svmpc, self.n_steps = svmpc, n_steps
 
-    def prior_keys(self, t):
-        """The Philox keys of period t = 1, 2, ...: seed + (b << 32) + t for environment b (modulo 2^64)."""
-        return [(self._seed + (b << 32) + int(t)) & 0xFFFFFFFFFFFFFFFF for b in range(self.n_envs)]
-
-    def __deepcopy__(self, memo):
-        new = copy.copy(self)
-        memo[id(self)] = new
+    def _copy_parts(self, new, memo):
         new.svmpc = copy.deepcopy(self.svmpc, memo)
         new.mpf = copy.deepcopy(self.mpf, memo)
-        new._mb = None if self._mb is None else self._mb.clone()
-        new._pending = None if self._pending is None else tuple(v.copy() for v in self._pending)
-        return new
-
-    def _filters(self, states=None):
-        if self._mb is None:
-            if self.mpf.draw_source is not None:
-                raise NotImplementedError("recorded filter draws (draw_source) have no batched form")
-            mb = self.mpf._dev.batch(self.n_envs)
-            if self._init_particles is not None:
-                mb.set_particles(self._init_particles.numpy())
-            if states is not None:
-                mb.set_obs(states)
-            self._mb = mb
-        return self._mb
 
     @property
     def theta(self):
@@ -447,18 +426,6 @@ class BatchDualSVMPC:
     @property
     def controller(self):
         return self.svmpc.likelihood.controller
-
-    @property
-    def dyn_particles(self):
-        """[B, Mp, P]; a noted update is carried out first"""
-        self._flush()
-        return torch.from_numpy(self._filters().get_particles())
-
-    def _flush(self):
-        pend = self._pending
-        if pend is not None:
-            _, bw = self._filters().optimize(pend[0], pend[1], self.mpf_bw, self.mpf_steps)
-            self._pending, self.last_bw = None, torch.from_numpy(bw)
 
     def forward(self, states, eps=None, active=None):
         """eps [B, n_steps, S, N, H, da]: recorded noise in place of device-drawn noise; active [B]: the environments that tick"""
@@ -479,13 +446,6 @@ class BatchDualSVMPC:
             self.last_bw = torch.from_numpy(bw)
         self.ticks += 1
         return torch.from_numpy(a_seq), torch.from_numpy(pw)
-
-    def step(self, actions, new_states):
-        self._flush()
-        B = self.n_envs
-        self._pending = (torch.as_tensor(actions, dtype=torch.float).reshape(B, -1).numpy().copy(),
-                         torch.as_tensor(new_states, dtype=torch.float).reshape(B, -1).numpy().copy())
-        return None, None
 
     def tick(self, states, plant):
         """One loop iteration with a host plant callable `plant(states [B, ds], actions [B, da]) -> new_states [B, ds]`: forward,

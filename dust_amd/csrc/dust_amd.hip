@@ -1393,10 +1393,23 @@ struct AmppiBatched {
   static constexpr auto nav_prior = amppi_skid_nav_prior_batch_kernel;
 };
 
+// f(std::integral_constant<int, MODEL>()) for the context's model: where a launch chooses the model's instance of a kernel
+template <class F>
+static auto by_model(const dust_ctx *c, F &&f) {
+  switch (c->cfg.model) {
+    case DUST_MODEL_PENDULUM: return f(std::integral_constant<int, DUST_MODEL_PENDULUM>());
+    case DUST_MODEL_PARTICLE: return f(std::integral_constant<int, DUST_MODEL_PARTICLE>());
+    case DUST_MODEL_SKID_STEER: return f(std::integral_constant<int, DUST_MODEL_SKID_STEER>());
+    default: return f(std::integral_constant<int, DUST_MODEL_CARTPOLE>());
+  }
+}
+// the skid-steer tick with the navigation cost: the kernels of that family (AMPPI and batched SVMPC) take the map as an argument of their own
+static bool skid_nav_on(const dust_ctx *c) { return c->cfg.model == DUST_MODEL_SKID_STEER && c->skid_w_obs != 0.f; }
+
 // The tick's launch: its tickets zeroed, then navigation cost or not x in-kernel prior draws or not x model, all on the context's stream
 template <class F>
 static int amppi_launch(dust_ctx *c, const dim3 grid, const typename F::Args &k, const typename F::Prior *prior, unsigned int *tickets, size_t n_tickets) {
-  const bool nav = c->cfg.model == DUST_MODEL_SKID_STEER && c->skid_w_obs != 0.f;
+  const bool nav = skid_nav_on(c);
   SkidNav nv;
   if (nav) TRY(skid_nav_args(c, nv));
   HIP_TRY(hipMemsetAsync(tickets, 0, n_tickets * sizeof(unsigned int), c->stream));
@@ -1408,12 +1421,7 @@ static int amppi_launch(dust_ctx *c, const dim3 grid, const typename F::Args &k,
   };
   if (nav && prior) F::nav_prior<<<grid, AMPPI_THREADS, map_lds, c->stream>>>(typename F::NavPriorArgs{k, nv, *prior});
   else if (nav) F::nav<<<grid, AMPPI_THREADS, map_lds, c->stream>>>(typename F::NavArgs{k, nv});
-  else switch (c->cfg.model) {
-    case DUST_MODEL_PENDULUM: model(std::integral_constant<int, DUST_MODEL_PENDULUM>()); break;
-    case DUST_MODEL_PARTICLE: model(std::integral_constant<int, DUST_MODEL_PARTICLE>()); break;
-    case DUST_MODEL_SKID_STEER: model(std::integral_constant<int, DUST_MODEL_SKID_STEER>()); break;
-    default: model(std::integral_constant<int, DUST_MODEL_CARTPOLE>()); break;
-  }
+  else by_model(c, model);
   HIP_TRY(hipGetLastError());
   return DUST_OK;
 }
@@ -1525,6 +1533,33 @@ struct PinnedStage {
   }
 };
 
+// The per-call inputs of a controller batch (dust_amppi_batch, dust_svmpc_batch): [B][8] states, then [B] bytes of the active mask
+struct BatchInputs {
+  PinnedStage pin;
+  int B;
+  int alloc(int n_env) {
+    B = n_env;
+    return pin.alloc((size_t)B * 8 * sizeof(float) + (size_t)B);
+  }
+  void free() { pin.free(); }
+  // states [B][ds] and / or the active mask [B] -> the device through the next pinned slot, on the context's stream; nobody waits
+  int stage(const dust_ctx *c, const float *states, const unsigned char *active) {
+    unsigned char *hb;
+    TRY(pin.next(&hb));
+    const size_t sbytes = (size_t)B * 8 * sizeof(float);
+    if (states) {
+      float *hs = reinterpret_cast<float *>(hb);
+      for (int e = 0; e < B; ++e)
+        for (int k = 0; k < 8; ++k) hs[(size_t)e * 8 + k] = k < c->ds ? states[(size_t)e * c->ds + k] : 0.f;
+    }
+    if (active) memcpy(hb + sbytes, active, (size_t)B);
+    return pin.send(states ? 0 : sbytes, active ? sbytes + (size_t)B : sbytes, c->stream);
+  }
+  const float *states_dev() const { return reinterpret_cast<const float *>(pin.dev); }
+  // where the kernels find the mask a call has staged (nullptr: the call had none - everybody is active)
+  const unsigned char *mask_dev(const unsigned char *active) const { return active ? pin.dev + (size_t)B * 8 * sizeof(float) : nullptr; }
+};
+
 // rows of `row` floats per environment, device -> host on `stream`, for the environments of `active` (nullptr: all): one copy per run of them
 static int rows_d2h(int B, hipStream_t stream, float *dst, const float *src, size_t row, const unsigned char *active) {
   for (int e = 0; e < B;) {
@@ -1538,6 +1573,25 @@ static int rows_d2h(int B, hipStream_t stream, float *dst, const float *src, siz
     e = f;
   }
   return DUST_OK;
+}
+
+// What the creates of the controller batches share.  `unit`: what a launch spends per environment
+static int batch_n_env_check(int n_env, const char *unit) {
+  if (n_env < 1 || n_env > 65535) return fail(DUST_ERR_INVALID, "n_env = %d outside [1, 65535] (%s)", n_env, unit);
+  return DUST_OK;
+}
+// every environment starts from the prototype's row: one row read back, B copies sent
+static int spread(dust_ctx *c, size_t B, void *dst, const void *src, size_t bytes) {
+  std::vector<unsigned char> one(bytes), all(bytes * B);
+  TRY(d2h(c, one.data(), src, bytes));
+  for (size_t e = 0; e < B; ++e) memcpy(all.data() + e * bytes, one.data(), bytes);
+  return h2d(c, dst, all.data(), all.size());
+}
+// the environments' Philox keys: the caller's, or the prototype's seed + e
+static int batch_seeds_set(dust_ctx *c, size_t B, const uint64_t *seeds, uint64_t *dev) {
+  std::vector<uint64_t> sd(B);
+  for (size_t e = 0; e < B; ++e) sd[e] = seeds ? seeds[e] : c->cfg.seed + (uint64_t)e;
+  return h2d(c, dev, sd.data(), B * sizeof(uint64_t));
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1554,16 +1608,10 @@ struct dust_amppi_batch {
   uint32_t *ctr;          // [B][4]: every environment's Philox stream position {tick, iter, .., ..}
   uint64_t *seeds;        // [B]
   unsigned int *ticket;   // [B]
-  PinnedStage in;         // per-call inputs: [B][8] states, then [B] bytes of the active mask
+  BatchInputs in;         // per-call inputs
   std::vector<unsigned char> last_active;  // the mask of the last tick (dust_amppi_batch_get_actions writes the rows of that tick's environments)
   bool acts_valid;
 };
-
-static size_t batch_in_bytes(int B) { return (size_t)B * 8 * sizeof(float) + (size_t)B; }
-// where the kernels find the mask a call has staged (nullptr: the call had none - everybody is active)
-static const unsigned char *batch_mask_dev(const dust_amppi_batch *b, const unsigned char *active) {
-  return active ? b->in.dev + (size_t)b->B * 8 * sizeof(float) : nullptr;
-}
 
 static void batch_free(dust_amppi_batch *b) {
   if (!b) return;
@@ -1594,7 +1642,7 @@ static int batch_alloc(dust_ctx *inner, int n_env, dust_amppi_batch **out) {
   TRY(dalloc(&b->ctr, B * 4));
   TRY(dalloc(&b->seeds, B));
   TRY(dalloc(&b->ticket, B));
-  return b->in.alloc(batch_in_bytes(n_env));
+  return b->in.alloc(n_env);
 }
 
 static int batch_null(const dust_amppi_batch *b) { return b ? DUST_OK : fail(DUST_ERR_INVALID, "null batch"); }
@@ -1603,27 +1651,14 @@ extern "C" int dust_amppi_batch_create(const dust_ctx *proto, int n_env, const u
   if (!proto || !out) return fail(DUST_ERR_INVALID, "null argument");
   *out = nullptr;
   TRY(amppi_check(proto));
-  if (n_env < 1 || n_env > 65535) return fail(DUST_ERR_INVALID, "n_env = %d outside [1, 65535] (one grid row per environment)", n_env);
+  TRY(batch_n_env_check(n_env, "one grid row per environment"));
   dust_ctx *inner = nullptr;
   TRY(dust_clone(proto, &inner));
   dust_amppi_batch *b = nullptr;
   int st = batch_alloc(inner, n_env, &b);
-  if (st == DUST_OK) {
-    const size_t D = (size_t)inner->D;
-    std::vector<float> seq(D), seq_all((size_t)n_env * D);
-    std::vector<uint32_t> ctr(4), ctr_all((size_t)n_env * 4);
-    std::vector<uint64_t> sd((size_t)n_env);
-    st = d2h(inner, seq.data(), inner->a_seq, D * sizeof(float));
-    if (st == DUST_OK) st = d2h(inner, ctr.data(), inner->ctr_dev, 4 * sizeof(uint32_t));
-    for (int e = 0; e < n_env; ++e) {
-      std::copy(seq.begin(), seq.end(), seq_all.begin() + (size_t)e * D);
-      std::copy(ctr.begin(), ctr.end(), ctr_all.begin() + (size_t)e * 4);
-      sd[e] = seeds ? seeds[e] : inner->cfg.seed + (uint64_t)e;
-    }
-    if (st == DUST_OK) st = h2d(inner, b->a_seq, seq_all.data(), seq_all.size() * sizeof(float));
-    if (st == DUST_OK) st = h2d(inner, b->ctr, ctr_all.data(), ctr_all.size() * sizeof(uint32_t));
-    if (st == DUST_OK) st = h2d(inner, b->seeds, sd.data(), sd.size() * sizeof(uint64_t));
-  }
+  if (st == DUST_OK) st = spread(inner, (size_t)n_env, b->a_seq, inner->a_seq, (size_t)inner->D * sizeof(float));
+  if (st == DUST_OK) st = spread(inner, (size_t)n_env, b->ctr, inner->ctr_dev, 4 * sizeof(uint32_t));
+  if (st == DUST_OK) st = batch_seeds_set(inner, (size_t)n_env, seeds, b->seeds);
   if (st != DUST_OK) {
     batch_free(b);
     return st;
@@ -1676,27 +1711,12 @@ extern "C" int dust_amppi_batch_get_a_seq(dust_amppi_batch *b, float *a_seq) {
   return d2h(b->c, a_seq, b->a_seq, (size_t)b->B * b->c->D * sizeof(float));
 }
 
-// states [B][ds] and / or the active mask [B] -> b->in.dev through the next pinned slot, on the context's stream; nobody waits
-static int batch_stage_inputs(dust_amppi_batch *b, const float *states, const unsigned char *active) {
-  const dust_ctx *c = b->c;
-  unsigned char *hb;
-  TRY(b->in.next(&hb));
-  const size_t sbytes = (size_t)b->B * 8 * sizeof(float);
-  if (states) {
-    float *hs = reinterpret_cast<float *>(hb);
-    for (int e = 0; e < b->B; ++e)
-      for (int k = 0; k < 8; ++k) hs[(size_t)e * 8 + k] = k < c->ds ? states[(size_t)e * c->ds + k] : 0.f;
-  }
-  if (active) memcpy(hb + sbytes, active, (size_t)b->B);
-  return b->in.send(states ? 0 : sbytes, active ? sbytes + (size_t)b->B : sbytes, c->stream);
-}
-
 // amppi_batch_roll_kernel over the environments of the mask the call has staged (`active`: whether it had one)
 static int batch_roll_launch(dust_amppi_batch *b, int steps, const unsigned char *active) {
   dust_ctx *c = b->c;
   const long shift = (long)steps * c->da;
   Prof pr(c, DUST_K_FORWARD);
-  amppi_batch_roll_kernel<<<b->B, 128, 0, c->stream>>>(b->a_seq, c->D, shift > c->D ? c->D : (int)shift, batch_mask_dev(b, active));
+  amppi_batch_roll_kernel<<<b->B, 128, 0, c->stream>>>(b->a_seq, c->D, shift > c->D ? c->D : (int)shift, b->in.mask_dev(active));
   HIP_TRY(hipGetLastError());
   return DUST_OK;
 }
@@ -1728,7 +1748,7 @@ static int batch_update_launch(dust_amppi_batch *b, const float *states, const f
     TRY(ensure(&b->params, &b->params_cap, B * prows * P));
     if (!staged) TRY(h2d(c, b->params, params, B * prows * P * sizeof(float)));
   }
-  TRY(batch_stage_inputs(b, states, active));
+  TRY(b->in.stage(c, states, active));
   AmppiBatchArgs k;
   amppi_shared_args(c, k.a);
   k.a.pts = pts;
@@ -1741,9 +1761,9 @@ static int batch_update_launch(dust_amppi_batch *b, const float *states, const f
   k.a.costs = b->costs;
   k.a.omega = b->omega;
   k.a.ticket = b->ticket;
-  k.states = reinterpret_cast<const float *>(b->in.dev);
+  k.states = b->in.states_dev();
   k.seeds = b->seeds;
-  k.active = batch_mask_dev(b, active);
+  k.active = b->in.mask_dev(active);
   k.prow_stride = (int)(prows * P);
   TRY(amppi_launch<AmppiBatched>(c, dim3((unsigned)((S + AMPPI_THREADS - 1) / AMPPI_THREADS), (unsigned)B), k, prior, b->ticket, B));
   b->acts_valid = true;
@@ -1770,7 +1790,7 @@ extern "C" int dust_amppi_batch_roll(dust_amppi_batch *b, int steps, const unsig
   if (steps < 1) return fail(DUST_ERR_INVALID, "roll(steps = %d): steps >= 1", steps);
   dust_ctx *c = b->c;
   HIP_TRY(hipSetDevice(c->cfg.device));
-  if (active) TRY(batch_stage_inputs(b, nullptr, active));
+  if (active) TRY(b->in.stage(c, nullptr, active));
   return batch_roll_launch(b, steps, active);
 }
 
@@ -5544,12 +5564,9 @@ struct dust_svmpc_batch {
   size_t eps_cap, params_cap;
   float *plant, *rec;         // dust_svmpc_batch_episode: [B][P] true parameter rows; the records [T][B][ds], [T][B][da], [T][B][N]
   size_t plant_cap, rec_cap;
-  PinnedStage in;             // per-call inputs: [B][8] states, then [B] bytes of the active mask
+  BatchInputs in;             // per-call inputs
   bool have_costs, have_forward, acts_kept;
 };
-
-// the skid-steer tick with the navigation cost family: svmpc_skid_nav_batch_kernel / svmpc_skid_nav_prior_batch_kernel
-static bool svb_nav(const dust_ctx *c) { return c->cfg.model == DUST_MODEL_SKID_STEER && c->skid_w_obs != 0.f; }
 
 // the box of svmpc_batch.hpp
 static int svb_check(const dust_ctx *c) {
@@ -5569,14 +5586,12 @@ static int svb_check(const dust_ctx *c) {
   if (c->serve_on) return fail(DUST_ERR_UNSUPPORTED, "the context is serving (dust_svmpc_serve_stop first)");
   if (g.model == DUST_MODEL_PARTICLE && g.with_obstacle && !c->grid_bits)
     return fail(DUST_ERR_STATE, "with_obstacle is set but no occupancy grid was supplied (dust_set_grid)");
-  if (svb_nav(c)) {  // the navigation cost family needs its map (skid_nav_args' refusal, ahead of any launch)
+  if (skid_nav_on(c)) {  // the navigation cost family needs its map (skid_nav_args' refusal, ahead of any launch)
     SkidNav nv;
     TRY(skid_nav_args(c, nv));
   }
   return DUST_OK;
 }
-
-static size_t svb_in_bytes(int B) { return (size_t)B * 8 * sizeof(float) + (size_t)B; }
 
 static void svb_free(dust_svmpc_batch *b) {
   if (!b) return;
@@ -5614,41 +5629,32 @@ static int svb_alloc(dust_ctx *inner, int n_env, dust_svmpc_batch **out) {
   TRY(dalloc(&b->seeds, B));
   TRY(optim_slots_alloc(inner->opt, b->opt_s, B * N * D));
   HIP_TRY(hipMemsetAsync(b->a_mix, 0, B * N * sizeof(float), inner->stream));
-  return b->in.alloc(svb_in_bytes(n_env));
+  return b->in.alloc(n_env);
 }
 
 extern "C" int dust_svmpc_batch_create(const dust_ctx *proto, int n_env, const uint64_t *seeds, dust_svmpc_batch **out) {
   if (!proto || !out) return fail(DUST_ERR_INVALID, "null argument");
   *out = nullptr;
   TRY(svb_check(proto));
-  if (n_env < 1 || n_env > 65535) return fail(DUST_ERR_INVALID, "n_env = %d outside [1, 65535] (one workgroup per environment)", n_env);
+  TRY(batch_n_env_check(n_env, "one workgroup per environment"));
   dust_ctx *inner = nullptr;
   TRY(dust_clone(proto, &inner));  // (settles and waits for the prototype's stream)
   dust_svmpc_batch *b = nullptr;
   int st = svb_alloc(inner, n_env, &b);
   if (st == DUST_OK) {
     const size_t B = (size_t)n_env, N = (size_t)inner->N, ND = N * (size_t)inner->D;
-    // every environment starts from the prototype's rows: one row read back, B copies sent
-    auto spread = [&](void *dst, const void *src, size_t bytes) -> int {
-      std::vector<unsigned char> one(bytes), all(bytes * B);
-      TRY(d2h(inner, one.data(), src, bytes));
-      for (size_t e = 0; e < B; ++e) memcpy(all.data() + e * bytes, one.data(), bytes);
-      return h2d(inner, dst, all.data(), all.size());
-    };
-    st = spread(b->theta, inner->theta, ND * sizeof(float));
-    if (st == DUST_OK) st = spread(b->mu, inner->mu_aliased ? inner->theta : inner->mu, ND * sizeof(float));
-    if (st == DUST_OK) st = spread(b->a_mat, inner->a_mat, ND * sizeof(float));
-    if (st == DUST_OK) st = spread(b->mixw, inner->mixw, N * sizeof(float));
-    if (st == DUST_OK) st = spread(b->logmix, inner->logmix, N * sizeof(float));
-    if (st == DUST_OK) st = spread(b->ctr, inner->ctr_dev, 4 * sizeof(uint32_t));
+    st = spread(inner, B, b->theta, inner->theta, ND * sizeof(float));
+    if (st == DUST_OK) st = spread(inner, B, b->mu, inner->mu_aliased ? inner->theta : inner->mu, ND * sizeof(float));
+    if (st == DUST_OK) st = spread(inner, B, b->a_mat, inner->a_mat, ND * sizeof(float));
+    if (st == DUST_OK) st = spread(inner, B, b->mixw, inner->mixw, N * sizeof(float));
+    if (st == DUST_OK) st = spread(inner, B, b->logmix, inner->logmix, N * sizeof(float));
+    if (st == DUST_OK) st = spread(inner, B, b->ctr, inner->ctr_dev, 4 * sizeof(uint32_t));
     const float *const ss[3] = {inner->opt_s0, inner->opt_s1, inner->opt_s2};
     for (int k = 0; k < 3 && st == DUST_OK; ++k)
-      if (b->opt_s[k] && ss[k]) st = spread(b->opt_s[k], ss[k], ND * sizeof(float));
+      if (b->opt_s[k] && ss[k]) st = spread(inner, B, b->opt_s[k], ss[k], ND * sizeof(float));
     std::vector<int> al(B, inner->mu_aliased ? 1 : 0);
-    std::vector<uint64_t> sd(B);
-    for (size_t e = 0; e < B; ++e) sd[e] = seeds ? seeds[e] : inner->cfg.seed + (uint64_t)e;
     if (st == DUST_OK) st = h2d(inner, b->alias, al.data(), B * sizeof(int));
-    if (st == DUST_OK) st = h2d(inner, b->seeds, sd.data(), B * sizeof(uint64_t));
+    if (st == DUST_OK) st = batch_seeds_set(inner, B, seeds, b->seeds);
   }
   if (st != DUST_OK) {
     svb_free(b);
@@ -5792,6 +5798,11 @@ static int svb_call_check(const dust_svmpc_batch *b, const float *states, int n_
 
 // The caller's host rows -> the batch's device buffers (eps, params: either may be NULL); *eps_dev: where the kernel finds the noise, or
 // NULL (drawn on the device).  The copies wait for the stream: the caller owns the host buffers.
+// svb_stage_params: the parameter rows alone, `n` floats of them (a tick's [B][n_steps][M][P]; an episode's, for each of its periods)
+static int svb_stage_params(dust_svmpc_batch *b, const float *params, size_t n) {
+  TRY(ensure(&b->params, &b->params_cap, n));
+  return h2d(b->c, b->params, params, n * sizeof(float));
+}
 static int svb_stage(dust_svmpc_batch *b, int n_steps, const void *eps, const float *params, int flags, const float **eps_dev) {
   dust_ctx *c = b->c;
   const size_t B = (size_t)b->B, N = (size_t)c->N, S = (size_t)c->S, D = (size_t)c->D, M = (size_t)c->M, P = (size_t)c->cfg.dim_p;
@@ -5806,11 +5817,7 @@ static int svb_stage(dust_svmpc_batch *b, int n_steps, const void *eps, const fl
       *eps_dev = b->eps;
     }
   }
-  if (n_steps > 0 && params) {
-    const size_t n = B * (size_t)n_steps * M * P;
-    TRY(ensure(&b->params, &b->params_cap, n));
-    TRY(h2d(c, b->params, params, n * sizeof(float)));
-  }
+  if (n_steps > 0 && params) TRY(svb_stage_params(b, params, B * (size_t)n_steps * M * P));
   return DUST_OK;
 }
 
@@ -5820,20 +5827,8 @@ static int svb_stage(dust_svmpc_batch *b, int n_steps, const void *eps, const fl
 static int svb_go(dust_svmpc_batch *b, const float *states, int n_steps, const float *eps_dev, const float *params_dev, int flags,
                   const unsigned char *active, bool do_forward, const dust::SvbPrior *prior, const dust::SvbEpisode *episode = nullptr) {
   dust_ctx *c = b->c;
-  const size_t B = (size_t)b->B;
   HIP_TRY(hipSetDevice(c->cfg.device));
-  {  // states [B][ds] and / or the mask -> the next pinned slot, on the context's stream; nobody waits
-    unsigned char *hb;
-    TRY(b->in.next(&hb));
-    const size_t sbytes = B * 8 * sizeof(float);
-    if (states) {
-      float *hs = reinterpret_cast<float *>(hb);
-      for (size_t e = 0; e < B; ++e)
-        for (int k = 0; k < 8; ++k) hs[e * 8 + k] = k < c->ds ? states[e * c->ds + k] : 0.f;
-    }
-    if (active) memcpy(hb + sbytes, active, B);
-    TRY(b->in.send(states ? 0 : sbytes, active ? sbytes + B : sbytes, c->stream));
-  }
+  TRY(b->in.stage(c, states, active));
   SvmpcBatchArgs k;
   memset(&k, 0, sizeof k);
   k.dm = make_dev_model(c);
@@ -5874,9 +5869,9 @@ static int svb_go(dust_svmpc_batch *b, const float *states, int n_steps, const f
   k.inv_l2 = 1.0f / (ell * ell);
   k.inv_n = 1.0f / c->N;
   k.s0_restart = opt_restart_s0(c->opt);
-  k.states = reinterpret_cast<const float *>(b->in.dev);
+  k.states = b->in.states_dev();
   k.seeds = b->seeds;
-  k.active = active ? b->in.dev + B * 8 * sizeof(float) : nullptr;
+  k.active = b->in.mask_dev(active);
   k.eps = eps_dev;
   k.params = params_dev;
   k.a_seq = c->a_seq;
@@ -5902,7 +5897,7 @@ static int svb_go(dust_svmpc_batch *b, const float *states, int n_steps, const f
   k.a_mix = b->a_mix;
   k.pw = b->pw;
   k.a_seq_out = b->a_seq_out;
-  const bool nav = svb_nav(c);
+  const bool nav = skid_nav_on(c);
   SkidNav nv;
   memset(&nv, 0, sizeof nv);
   if (nav) TRY(skid_nav_args(c, nv));
@@ -5915,15 +5910,6 @@ static int svb_go(dust_svmpc_batch *b, const float *states, int n_steps, const f
       HIP_TRY(hipGetLastError());
       return DUST_OK;
     };
-    auto by_model = [&](auto from_prior, const auto &args) -> int {  // the model's instance of either kernel (svb_instance)
-      constexpr bool PR = decltype(from_prior)::value;
-      switch (c->cfg.model) {
-        case DUST_MODEL_PENDULUM: return go(svb_instance<DUST_MODEL_PENDULUM, PR>(), args);
-        case DUST_MODEL_PARTICLE: return go(svb_instance<DUST_MODEL_PARTICLE, PR>(), args);
-        case DUST_MODEL_SKID_STEER: return go(svb_instance<DUST_MODEL_SKID_STEER, PR>(), args);
-        default: return go(svb_instance<DUST_MODEL_CARTPOLE, PR>(), args);
-      }
-    };
     if (episode) {
       if (nav) {
         SvmpcNavEpisodeArgs ke;
@@ -5935,12 +5921,7 @@ static int svb_go(dust_svmpc_batch *b, const float *states, int n_steps, const f
         SvmpcEpisodeArgs ke;
         ke.k = k;
         ke.ep = *episode;
-        switch (c->cfg.model) {
-          case DUST_MODEL_PENDULUM: TRY(go(&svmpc_episode_kernel<DUST_MODEL_PENDULUM>, ke)); break;
-          case DUST_MODEL_PARTICLE: TRY(go(&svmpc_episode_kernel<DUST_MODEL_PARTICLE>, ke)); break;
-          case DUST_MODEL_SKID_STEER: TRY(go(&svmpc_episode_kernel<DUST_MODEL_SKID_STEER>, ke)); break;
-          default: TRY(go(&svmpc_episode_kernel<DUST_MODEL_CARTPOLE>, ke)); break;
-        }
+        TRY(by_model(c, [&](auto M) { return go(&svmpc_episode_kernel<M()>, ke); }));
       }
     } else if (nav && prior) {  // the navigation cost family: instances of their own, in both forms
       SvmpcNavPriorBatchArgs kp;
@@ -5957,9 +5938,9 @@ static int svb_go(dust_svmpc_batch *b, const float *states, int n_steps, const f
       SvmpcPriorBatchArgs kp;
       kp.k = k;
       kp.pr = *prior;
-      TRY(by_model(std::true_type(), kp));
+      TRY(by_model(c, [&](auto M) { return go(svb_instance<M(), true>(), kp); }));  // the model's instance of either kernel (svb_instance)
     } else {
-      TRY(by_model(std::false_type(), k));
+      TRY(by_model(c, [&](auto M) { return go(svb_instance<M(), false>(), k); }));
     }
   }
   if (n_steps > 0) {
@@ -5979,12 +5960,18 @@ static int svb_launch(dust_svmpc_batch *b, const float *states, int n_steps, con
   return svb_go(b, states, n_steps, eps_dev, (n_steps > 0 && params) ? b->params : nullptr, flags, active, do_forward, nullptr);
 }
 
-static int svb_outputs(dust_svmpc_batch *b, const unsigned char *active, float *a_seq, float *p_weights) {
-  if (!a_seq && !p_weights) return DUST_OK;
+// the outputs of forward() the caller asked for: svb_outputs_copy enqueues the copies behind the launch (the dual tick and the episode have
+// more to copy before they wait), svb_outputs waits for them as well
+static int svb_outputs_copy(dust_svmpc_batch *b, const unsigned char *active, float *a_seq, float *p_weights) {
   dust_ctx *c = b->c;
   if (a_seq) TRY(rows_d2h(b->B, c->stream, a_seq, b->a_seq_out, (size_t)c->D, active));
   if (p_weights) TRY(rows_d2h(b->B, c->stream, p_weights, b->pw, (size_t)c->N, active));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  return DUST_OK;
+}
+static int svb_outputs(dust_svmpc_batch *b, const unsigned char *active, float *a_seq, float *p_weights) {
+  if (!a_seq && !p_weights) return DUST_OK;
+  TRY(svb_outputs_copy(b, active, a_seq, p_weights));
+  HIP_TRY(hipStreamSynchronize(b->c->stream));
   return DUST_OK;
 }
 
@@ -6022,11 +6009,7 @@ extern "C" int dust_svmpc_batch_episode(dust_svmpc_batch *b, const float *states
   const size_t T = (size_t)n_periods, B = (size_t)b->B, N = (size_t)c->N, M = (size_t)c->M, P = (size_t)c->cfg.dim_p;
   const size_t ds = (size_t)c->ds, da = (size_t)c->da;
   HIP_TRY(hipSetDevice(c->cfg.device));
-  if (params) {
-    const size_t n = T * B * (size_t)n_steps * M * P;
-    TRY(ensure(&b->params, &b->params_cap, n));
-    TRY(h2d(c, b->params, params, n * sizeof(float)));
-  }
+  if (params) TRY(svb_stage_params(b, params, T * B * (size_t)n_steps * M * P));
   if (plant_params) {
     TRY(ensure(&b->plant, &b->plant_cap, B * P));
     TRY(h2d(c, b->plant, plant_params, B * P * sizeof(float)));
@@ -6043,7 +6026,7 @@ extern "C" int dust_svmpc_batch_episode(dust_svmpc_batch *b, const float *states
   // the records come back once; the rows of inactive environments stay out of the caller's arrays
   std::vector<float> host(n_rec);
   HIP_TRY(hipMemcpyAsync(host.data(), b->rec, n_rec * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  if (a_seq) TRY(rows_d2h(b->B, c->stream, a_seq, b->a_seq_out, (size_t)c->D, active));
+  TRY(svb_outputs_copy(b, active, a_seq, nullptr));
   HIP_TRY(hipStreamSynchronize(c->stream));
   auto rows = [&](float *dst, const float *src, size_t row) {
     if (!active) {

@@ -2385,6 +2385,69 @@ extern "C" int dust_mpf_batch_optimize(dust_mpf_batch *mb, const float *actions,
   return DUST_OK;
 }
 
+// What the dual ticks of the two controller batches (dust_amppi_dual_batch_tick, dust_svmpc_dual_batch_tick) share.
+// The pair: controller and filters agree, and there are as many of one as of the other.  `kind`: the controller batch's name.  (Each
+// entry's own refusals lie between these and the filters' in dual_batch_filters.)
+static int dual_batch_pair_check(const dust_ctx *c, const char *kind, int B, const dust_mpf_batch *mb) {
+  TRY(dual_pair_check(c, mb->m));
+  if (B != mb->B) return fail(DUST_ERR_INVALID, "the %s batch has %d environments, the filter batch %d", kind, B, mb->B);
+  return DUST_OK;
+}
+
+// The filter side of a period on the controller batch's stream: the filters' refusals, ahead of any copy or launch; the controller's
+// pending work settled; stage() - what the entry allocates or copies ahead of the filters' launches; then, behind another batch's tick
+// on these filters (its stream first, without a host wait), the per-call inputs and the update (skipped when actions_prev is NULL)
+template <class Stage>
+static int dual_batch_filters(dust_ctx *c, dust_mpf_batch *mb, const float *states, const float *actions_prev, int mpf_steps, float mpf_bw,
+                              const uint64_t *prior_seeds, const unsigned char *active, MpfbRows &rows, Stage stage) {
+  TRY(mpfb_limits(mb->m, mb->B));
+  if (actions_prev) TRY(mpfb_update_check(mb, actions_prev, states, mpf_steps, active));
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  TRY(settle_pending(c));
+  // (reallocations free behind the device's queued work; they happen in the first period only)
+  if (actions_prev) TRY(mpfb_gn_room(mb, mpf_steps));
+  TRY(stage());
+  HIP_TRY(hipStreamWaitEvent(c->stream, mb->ev_ext, 0));
+  TRY(mpfb_enqueue(mb, c->stream, actions_prev != nullptr, actions_prev, states, mpf_bw, mpf_steps, active, prior_seeds, rows));
+  mb->n_calls++;
+  return DUST_OK;
+}
+
+// the filters' priors as either tick's kernels take them (AmppiPriorBatch, SvbPrior: two types with these fields)
+template <class Prior>
+static void dual_batch_prior(const dust_mpf_batch *mb, float *params_out, Prior &pr) {
+  memset(&pr, 0, sizeof pr);
+  pr.means = mb->x;
+  pr.K = mb->m->Mp;
+  pr.P = mb->m->P;
+  pr.bwv = mb->prior_bwv;
+  pr.seeds = mpfb_seeds_dev(mb);
+  pr.params_out = params_out;
+}
+
+// The close of a period, in two steps.  dual_batch_bw, behind the tick's launch and the entry's own output copies: the filters' host
+// rows move on (every launch of the period is enqueued) and bw_used is answered - on the host where the call fixed the bandwidth or
+// skipped the update, else by a copy of Silverman's values on the stream (*copies is then set).  dual_batch_close: ev_ext behind all of
+// it (the filters' own entries, and another batch's tick on these filters, wait for it), and the wait where something was copied out
+static int dual_batch_bw(dust_ctx *c, dust_mpf_batch *mb, MpfbRows &rows, const float *actions_prev, float mpf_bw, const unsigned char *active,
+                         float *bw_used, bool *copies) {
+  mpfb_commit(mb, rows);
+  const bool bw_dev = bw_used && actions_prev && !(mpf_bw > 0.f);
+  if (bw_used && !bw_dev)
+    for (int e = 0; e < mb->B; ++e)
+      if (!active || active[e]) bw_used[e] = actions_prev ? mpf_bw : 0.f;
+  if (bw_dev) {
+    TRY(rows_d2h(mb->B, c->stream, bw_used, mb->bw, 1, active));
+    *copies = true;
+  }
+  return DUST_OK;
+}
+static int dual_batch_close(dust_ctx *c, dust_mpf_batch *mb, bool copies) {
+  HIP_TRY(hipEventRecord(mb->ev_ext, c->stream));
+  if (copies) HIP_TRY(hipStreamSynchronize(c->stream));
+  return DUST_OK;
+}
+
 // One control period of the dual loop for B environments in one call (B x dust_amppi_dual_tick): on the AMPPI batch's stream, in launch
 // order and without an event or a wait in between - the filters' update for (actions_prev[b], states[b]) (skipped when actions_prev is
 // NULL; mpf_bw <= 0: Silverman's rule per environment, on the device, handed to the update in device memory), the parameters from every
@@ -2401,24 +2464,16 @@ extern "C" int dust_amppi_dual_batch_tick(dust_amppi_batch *b, dust_mpf_batch *m
   dust_ctx *c = b->c;
   dust_mpf *m = mb->m;
   TRY(amppi_check(c));
-  TRY(dual_pair_check(c, m));
-  if (b->B != mb->B) return fail(DUST_ERR_INVALID, "the AMPPI batch has %d environments, the filter batch %d", b->B, mb->B);
+  TRY(dual_batch_pair_check(c, "AMPPI", b->B, mb));
   bool sigma, shared;
   TRY(amppi_dual_check(c, m, flags, &sigma, &shared));
   if (!sigma && !prior_seeds) return fail(DUST_ERR_INVALID, "null argument: the draws from the filters' priors need prior_seeds [B]");
-  TRY(mpfb_limits(m, mb->B));
-  if (actions_prev) TRY(mpfb_update_check(mb, actions_prev, states, mpf_steps, active));
-  HIP_TRY(hipSetDevice(c->cfg.device));
-  TRY(settle_pending(c));
   const size_t B = (size_t)b->B, S = (size_t)c->S, D = (size_t)c->D, P = (size_t)m->P;
   const size_t prows = sigma ? (size_t)c->M : (shared ? (size_t)1 : S);
-  // (reallocations free behind the device's queued work; they happen in the first period only)
-  if (sigma || shared || params_out) TRY(ensure(&b->params, &b->params_cap, B * prows * P));
-  if (actions_prev) TRY(mpfb_gn_room(mb, mpf_steps));
-  HIP_TRY(hipStreamWaitEvent(c->stream, mb->ev_ext, 0));  // (another AMPPI batch's tick on these filters: its stream first, without a host wait)
   MpfbRows rows;
-  TRY(mpfb_enqueue(mb, c->stream, actions_prev != nullptr, actions_prev, states, mpf_bw, mpf_steps, active, prior_seeds, rows));
-  mb->n_calls++;
+  TRY(dual_batch_filters(c, mb, states, actions_prev, mpf_steps, mpf_bw, prior_seeds, active, rows, [&]() -> int {
+    return sigma || shared || params_out ? ensure(&b->params, &b->params_cap, B * prows * P) : DUST_OK;
+  }));
   const unsigned char *mask = mpfb_mask_dev(mb, active);
   int st;
   if (sigma || shared) {
@@ -2429,31 +2484,18 @@ extern "C" int dust_amppi_dual_batch_tick(dust_amppi_batch *b, dust_mpf_batch *m
     st = batch_update_launch(b, states, actions, b->params, flags, active, true, nullptr);
   } else {
     dust::AmppiPriorBatch pr;
-    memset(&pr, 0, sizeof pr);
-    pr.means = mb->x;
-    pr.K = m->Mp;
-    pr.P = m->P;
-    pr.bwv = mb->prior_bwv;
-    pr.seeds = mpfb_seeds_dev(mb);
-    pr.params_out = params_out ? b->params : nullptr;
+    dual_batch_prior(mb, params_out ? b->params : nullptr, pr);
     st = batch_update_launch(b, states, actions, nullptr, flags, active, false, &pr);
   }
   if (st != DUST_OK) return st;
-  mpfb_commit(mb, rows);  // (every launch of the period is enqueued)
-  const bool bw_dev = bw_used && actions_prev && !(mpf_bw > 0.f);
-  if (bw_used && !bw_dev)
-    for (size_t e = 0; e < B; ++e)
-      if (!active || active[e]) bw_used[e] = actions_prev ? mpf_bw : 0.f;
-  const bool copies = costs || omega || a_seq || params_out || bw_dev;
+  bool copies = costs || omega || a_seq || params_out;
   if (costs) TRY(rows_d2h(b->B, c->stream, costs, b->costs, S, active));
   if (omega) TRY(rows_d2h(b->B, c->stream, omega, b->omega, S, active));
   if (a_seq) TRY(rows_d2h(b->B, c->stream, a_seq, b->a_seq, D, active));
   if (params_out) TRY(rows_d2h(b->B, c->stream, params_out, b->params, prows * P, active));
-  if (bw_dev) TRY(rows_d2h(b->B, c->stream, bw_used, mb->bw, 1, active));
+  TRY(dual_batch_bw(c, mb, rows, actions_prev, mpf_bw, active, bw_used, &copies));
   if (roll_steps > 0) TRY(batch_roll_launch(b, roll_steps, active));  // (dust_amppi_batch_roll on the mask this call has staged already)
-  HIP_TRY(hipEventRecord(mb->ev_ext, c->stream));  // (the filters' own entries wait for it on the host)
-  if (copies) HIP_TRY(hipStreamSynchronize(c->stream));
-  return DUST_OK;
+  return dual_batch_close(c, mb, copies);
 }
 
 // One control period of the DuSt-MPC loop (simulations.py:104-138) for B environments in one call (B x dust_dual_tick): on the SVMPC
@@ -2470,48 +2512,25 @@ extern "C" int dust_svmpc_dual_batch_tick(dust_svmpc_batch *b, dust_mpf_batch *m
   if (!b || !mb || !states) return fail(DUST_ERR_INVALID, "null argument");
   if (n_steps < 1 || mpf_steps < 0) return fail(DUST_ERR_INVALID, "bad step counts");
   dust_ctx *c = b->c;
-  dust_mpf *m = mb->m;
   TRY(svb_call_check(b, states, n_steps, nullptr, true, flags, true));  // (sigma-point weights among it: no batched sigma rollouts)
-  TRY(dual_pair_check(c, m));
-  if (b->B != mb->B) return fail(DUST_ERR_INVALID, "the SVMPC batch has %d environments, the filter batch %d", b->B, mb->B);
+  TRY(dual_batch_pair_check(c, "SVMPC", b->B, mb));
   if (!prior_seeds) return fail(DUST_ERR_INVALID, "null argument: the draws from the filters' priors need prior_seeds [B]");
-  TRY(mpfb_limits(m, mb->B));
-  if (actions_prev) TRY(mpfb_update_check(mb, actions_prev, states, mpf_steps, active));
-  HIP_TRY(hipSetDevice(c->cfg.device));
-  TRY(settle_pending(c));
-  const size_t B = (size_t)b->B, N = (size_t)c->N, D = (size_t)c->D, prow = (size_t)n_steps * (size_t)c->M * (size_t)m->P;
-  // (reallocations free behind the device's queued work; they happen in the first period only)
-  if (params_out) TRY(ensure(&b->params, &b->params_cap, B * prow));
-  if (actions_prev) TRY(mpfb_gn_room(mb, mpf_steps));
+  const size_t prow = (size_t)n_steps * (size_t)c->M * (size_t)mb->m->P;
   const float *eps_dev;
-  TRY(svb_stage(b, n_steps, eps, nullptr, flags, &eps_dev));
-  HIP_TRY(hipStreamWaitEvent(c->stream, mb->ev_ext, 0));  // (another batch's tick on these filters: its stream first, without a host wait)
   MpfbRows rows;
-  TRY(mpfb_enqueue(mb, c->stream, actions_prev != nullptr, actions_prev, states, mpf_bw, mpf_steps, active, prior_seeds, rows));
-  mb->n_calls++;
+  TRY(dual_batch_filters(c, mb, states, actions_prev, mpf_steps, mpf_bw, prior_seeds, active, rows, [&]() -> int {
+    if (params_out) TRY(ensure(&b->params, &b->params_cap, (size_t)b->B * prow));
+    return svb_stage(b, n_steps, eps, nullptr, flags, &eps_dev);
+  }));
   dust::SvbPrior pr;
-  memset(&pr, 0, sizeof pr);
-  pr.means = mb->x;
-  pr.K = m->Mp;
-  pr.P = m->P;
-  pr.bwv = mb->prior_bwv;
-  pr.seeds = mpfb_seeds_dev(mb);
-  pr.params_out = params_out ? b->params : nullptr;
+  dual_batch_prior(mb, params_out ? b->params : nullptr, pr);
   // (a REFUSAL cannot come from here on: every check ran above.  A runtime error of svb_go - a pinned slot, a failed launch - leaves the
   // filters' update enqueued without mpfb_commit: their host rows (loc / past / opt_t) then lag the device, as under
   // dust_amppi_dual_batch_tick; such an error is not recoverable for the pair)
   TRY(svb_go(b, states, n_steps, eps_dev, nullptr, flags, active, true, &pr));
-  mpfb_commit(mb, rows);  // (every launch of the period is enqueued)
-  const bool bw_dev = bw_used && actions_prev && !(mpf_bw > 0.f);
-  if (bw_used && !bw_dev)
-    for (size_t e = 0; e < B; ++e)
-      if (!active || active[e]) bw_used[e] = actions_prev ? mpf_bw : 0.f;
-  const bool copies = a_seq || p_weights || params_out || bw_dev;
-  if (a_seq) TRY(rows_d2h(b->B, c->stream, a_seq, b->a_seq_out, D, active));
-  if (p_weights) TRY(rows_d2h(b->B, c->stream, p_weights, b->pw, N, active));
+  bool copies = a_seq || p_weights || params_out;
+  TRY(svb_outputs_copy(b, active, a_seq, p_weights));
   if (params_out) TRY(rows_d2h(b->B, c->stream, params_out, b->params, prow, active));
-  if (bw_dev) TRY(rows_d2h(b->B, c->stream, bw_used, mb->bw, 1, active));
-  HIP_TRY(hipEventRecord(mb->ev_ext, c->stream));  // (the filters' own entries, and another batch's tick on these filters, wait for it)
-  if (copies) HIP_TRY(hipStreamSynchronize(c->stream));
-  return DUST_OK;
+  TRY(dual_batch_bw(c, mb, rows, actions_prev, mpf_bw, active, bw_used, &copies));
+  return dual_batch_close(c, mb, copies);
 }

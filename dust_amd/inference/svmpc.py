@@ -6,6 +6,27 @@ from ..kernels import kernel_config
 from ..optim import check_optimizer, group_options, optimizer_config
 
 
+def _configure(oc, likelihood, cov, weighted_prior, roll_strategy, kernel_cfg):
+    """The optimiser's options `oc` (optimizer_config) and SVMPC's own into the controller's configuration; plain SGD / Adam keep
+    dust_config's own fields."""
+    opt = dict(optimizer="Adam" if oc["kind"] == "Adam" else "SGD", lr=oc["lr"], optim=oc)
+    if oc["kind"] == "Adam":
+        opt["adam"] = (oc["beta1"], oc["beta2"], oc["eps"])
+    likelihood.controller._svmpc_cfg.update(opt, likelihood=likelihood.kind, alpha=float(likelihood.alpha), weighted_prior=bool(weighted_prior),
+                                            roll_strategy=roll_strategy, sigma_p=cov.diag().sqrt().numpy(), p_cov=cov.detach().numpy().copy(),
+                                            **kernel_cfg)
+
+
+def _active(active, n_envs):
+    """the active mask as [n_envs] bools (None: everybody)"""
+    if active is None:
+        return np.ones(n_envs, bool)
+    a = np.asarray(active).reshape(-1) != 0
+    if a.shape != (n_envs,):
+        raise ValueError("active has %d entries for %d environments" % (a.size, n_envs))
+    return a
+
+
 class SVMPC:
     def __init__(self, init_particles, prior, likelihood, roll_strategy="repeat", weighted_prior=False, kernel=None, bw_scale=1.0,
                  n_particles=None, n_steps=100, optimizer_class=torch.optim.Adam, **opt_args):
@@ -17,21 +38,13 @@ class SVMPC:
         self.w_prior, self.roll_strategy = weighted_prior, roll_strategy
         if roll_strategy not in ("repeat", "mean", "resample"):
             raise ValueError("{} is an invalid roll strategy.".format(roll_strategy))
-        # every option reaches the device or raises (dust_amd/optim.py); plain SGD / Adam keep dust_config's own fields
-        self._optim = optimizer_config(optimizer_class, opt_args)
-        oc = self._optim
-        opt = dict(optimizer="Adam" if oc["kind"] == "Adam" else "SGD", lr=oc["lr"], optim=oc)
-        if oc["kind"] == "Adam":
-            opt["adam"] = (oc["beta1"], oc["beta2"], oc["eps"])
+        self._optim = optimizer_config(optimizer_class, opt_args)  # every option reaches the device or raises (dust_amd/optim.py)
         comp = prior.component_distribution.base_dist
         cov = comp.covariance_matrix
         cov = cov.reshape(-1, cov.shape[-2], cov.shape[-1])[0]
         if not torch.equal(cov, torch.diag(torch.diag(cov))) and cov.shape[-1] != 2:
             raise NotImplementedError("a full prior covariance has a HIP kernel for dim_a = 2")
-        ctrl = likelihood.controller
-        ctrl._svmpc_cfg.update(opt, likelihood=likelihood.kind, alpha=float(likelihood.alpha), weighted_prior=bool(weighted_prior),
-                               roll_strategy=roll_strategy, sigma_p=cov.diag().sqrt().numpy(), p_cov=cov.detach().numpy().copy(),
-                               **kernel_config(kernel))
+        _configure(self._optim, likelihood, cov, weighted_prior, roll_strategy, kernel_config(kernel))
         self._theta0 = torch.as_tensor(init_particles, dtype=torch.float).detach().clone()
         self._prior0 = (comp.loc.detach().clone(), prior.mixture_distribution.probs.detach().clone())
         self._uploaded = False
@@ -222,12 +235,7 @@ class BatchSVMPC:
         self.optimizer_class, self.opt_args = optimizer_class, opt_args
         self.w_prior, self.roll_strategy = weighted_prior, roll_strategy
         self._optim = optimizer_config(optimizer_class, opt_args)
-        oc = self._optim
-        opt = dict(optimizer="Adam" if oc["kind"] == "Adam" else "SGD", lr=oc["lr"], optim=oc)
-        if oc["kind"] == "Adam":
-            opt["adam"] = (oc["beta1"], oc["beta2"], oc["eps"])
-        ctrl._svmpc_cfg.update(opt, likelihood=likelihood.kind, alpha=float(likelihood.alpha), weighted_prior=bool(weighted_prior),
-                               roll_strategy=roll_strategy, sigma_p=cov.diag().sqrt().numpy(), p_cov=cov.detach().numpy().copy(), **kc)
+        _configure(self._optim, likelihood, cov, weighted_prior, roll_strategy, kc)
         B = self.n_envs
         shape = (N, ctrl.hz_len, ctrl.dim_a)
         self._theta0 = (init_particles if init_particles.ndim == 4 else init_particles[None].repeat(B, 1, 1, 1)).reshape((B,) + shape).clone()
@@ -303,12 +311,7 @@ class BatchSVMPC:
         return torch.as_tensor(states, dtype=torch.float).reshape(self.n_envs, -1).numpy()
 
     def _active(self, active):
-        if active is None:
-            return np.ones(self.n_envs, bool)
-        a = np.asarray(active).reshape(-1) != 0
-        if a.shape != (self.n_envs,):
-            raise ValueError("active has %d entries for %d environments" % (a.size, self.n_envs))
-        return a
+        return _active(active, self.n_envs)
 
     def _params(self, params_dist, n_steps, on, params):
         """[B, n_steps, M, P]: the caller's rows, or the draws SVMPC makes, once per active environment in environment order"""
