@@ -96,6 +96,12 @@ struct PeerState {
   unsigned int seq[PEER_BUFS];
 };
 
+// the five buffers of one set of run lists (pairwise_packed.hpp far_pack_kernel), with their capacities in floats
+struct RunLists {
+  float *idx, *uoff, *uq, *soff, *goff;
+  size_t idx_cap, uoff_cap, uq_cap, soff_cap, goff_cap;
+};
+
 struct dust_ctx {
   dust_config cfg;
   int N, S, M, H, da, ds, P, D, n0, nloc;
@@ -140,10 +146,10 @@ struct dust_ctx {
   CartModel cart;            // DUST_MODEL_CARTPOLE: model parameters and the quadratic cost (dust_set_cartpole)
   // pairwise_packed.hpp: the near-key lists of the last large-set pass 1 - key indices [tiles][chunks * 64], unit offsets
   // [tiles][chunks + 1], unit query masks [tiles][chunks][4], slice boundaries of pass 1 / pass 2, non-zero flags of the units' kernel blocks
-  float *pk_idx, *pk_uoff, *pk_uq, *pk_soff, *pk_goff, *pk_nzu, *pk_perm, *pk_lead;
-  size_t pk_idx_cap, pk_uoff_cap, pk_uq_cap, pk_soff_cap, pk_goff_cap, pk_nzu_cap, pk_perm_cap, pk_lead_cap;
-  float *lp_idx, *lp_uoff, *lp_uq, *lp_soff, *lp_goff;  // the log-p pass' own run lists (64-query groups of the UPDATED particles)
-  size_t lp_idx_cap, lp_uoff_cap, lp_uq_cap, lp_soff_cap, lp_goff_cap;
+  RunLists pk;
+  float *pk_nzu, *pk_perm, *pk_lead;
+  size_t pk_nzu_cap, pk_perm_cap, pk_lead_cap;
+  RunLists lp;  // the log-p pass' own run lists (64-query groups of the UPDATED particles)
   bool params_staged;             // inside dust_dual_tick: the tick's dynamics samples already sit in params_dev (drawn there by the filter's kernel)
   bool stagewise;                 // inside dust_svmpc_phi (a stage-wise call on caller-supplied inputs): index order - the same inputs give the same bits, call after call
   bool pk_order;                  // pass 1 walks its queries in tile order (pk_perm) and notes their leaders (pk_lead) for the next order
@@ -526,7 +532,7 @@ static void free_all(dust_ctx *c) {
   float **fp[] = {&c->theta, &c->theta_alt, &c->thetaT, &c->thetaT_alt, &c->mu, &c->muT, &c->logmix, &c->mixw, &c->a_mat, &c->a_seq, &c->a_mix, &c->eta,
                   &c->costsT, &c->omegaT, &c->grad_lik, &c->grad_pri, &c->score, &c->phi, &c->logl, &c->logp, &c->lw,
                   &c->outblk, &c->bw, &c->opt_s0, &c->opt_s1, &c->opt_s2, &c->noise_stage, &c->actions, &c->states, &c->params_dev,
-                  &c->state_dev, &c->tmp, &c->costs_stage, &c->tile_scratch, &c->wg_flags, &c->pA, &c->pB, &c->pM, &c->pL, &c->pS, &c->xpad, &c->kmat, &c->pk_idx, &c->pk_uoff, &c->pk_uq, &c->pk_soff, &c->pk_goff, &c->pk_nzu, &c->pk_perm, &c->pk_lead, &c->lp_idx, &c->lp_uoff, &c->lp_uq, &c->lp_soff, &c->lp_goff, &c->far_z, &c->far_n, &c->far_f, &c->far_g, &c->far_q, &c->far_cnt, &c->mw_dev, &c->cz_dev, &c->theta_w, &c->mu_w};
+                  &c->state_dev, &c->tmp, &c->costs_stage, &c->tile_scratch, &c->wg_flags, &c->pA, &c->pB, &c->pM, &c->pL, &c->pS, &c->xpad, &c->kmat, &c->pk.idx, &c->pk.uoff, &c->pk.uq, &c->pk.soff, &c->pk.goff, &c->pk_nzu, &c->pk_perm, &c->pk_lead, &c->lp.idx, &c->lp.uoff, &c->lp.uq, &c->lp.soff, &c->lp.goff, &c->far_z, &c->far_n, &c->far_f, &c->far_g, &c->far_q, &c->far_cnt, &c->mw_dev, &c->cz_dev, &c->theta_w, &c->mu_w};
   for (auto p : fp)
     if (*p) (void)hipFree(*p);
   if (c->graph_exec) (void)hipGraphExecDestroy(c->graph_exec);
@@ -1393,16 +1399,62 @@ struct AmppiBatched {
   static constexpr auto nav_prior = amppi_skid_nav_prior_batch_kernel;
 };
 
+// f(std::integral_constant<int, V>()) for the V among Vs that equals v; the LAST one is the default (the caller has excluded every other
+// value, or the widest instance serves the rest).  Where a launch chooses a kernel instance by a padded width or a column count.
+template <int V, int... Vs, class F>
+static auto pick_int(int v, F &&f) {
+  if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V>());
+  else return v == V ? f(std::integral_constant<int, V>()) : pick_int<Vs...>(v, f);
+}
+// ... and a yes / no as std::bool_constant
+template <class F>
+static auto pick_bool(bool v, F &&f) {
+  return v ? f(std::true_type()) : f(std::false_type());
+}
 // f(std::integral_constant<int, MODEL>()) for the context's model: where a launch chooses the model's instance of a kernel
 template <class F>
 static auto by_model(const dust_ctx *c, F &&f) {
-  switch (c->cfg.model) {
-    case DUST_MODEL_PENDULUM: return f(std::integral_constant<int, DUST_MODEL_PENDULUM>());
-    case DUST_MODEL_PARTICLE: return f(std::integral_constant<int, DUST_MODEL_PARTICLE>());
-    case DUST_MODEL_SKID_STEER: return f(std::integral_constant<int, DUST_MODEL_SKID_STEER>());
-    default: return f(std::integral_constant<int, DUST_MODEL_CARTPOLE>());
-  }
+  return pick_int<DUST_MODEL_PENDULUM, DUST_MODEL_PARTICLE, DUST_MODEL_SKID_STEER, DUST_MODEL_CARTPOLE>(c->cfg.model, f);
 }
+// ... and the pairwise mode of its Stein kernel (handoff.hpp): IMQ, or K1 where the caller has excluded everything else
+template <class F>
+static auto by_stein_mode(const dust_ctx *c, F &&f) {
+  return pick_int<PAIR_IMQ, PAIR_K1>(c->cfg.kernel == DUST_KERNEL_IMQ ? PAIR_IMQ : PAIR_K1, f);
+}
+// the Stein kernels' length scale: softplus(0) = ln 2 for K1 (svmpc.py:78 typo keeps it)
+static float stein_ell(const dust_ctx *c) { return c->cfg.kernel == DUST_KERNEL_IMQ ? c->cfg.imq_ell : 0.69314718055994531f; }
+
+// Every kernel launch with dynamic LDS: more than 64 KB needs the kernel's limit raised first (never during a graph capture), and the
+// launch's status is returned.  Chain: what brackets the enqueue alone - PersistChain for the one-launch kernels, nothing otherwise.
+struct NoChain {
+  explicit NoChain(dust_ctx *) {}
+};
+template <class Chain, class... P, class... A>
+static hipError_t launch_as(dust_ctx *chain_ctx, hipStream_t stream, bool capturing, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, const A &...args) {
+  if (lds > 64 * 1024 && !capturing) {
+    const hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  {
+    Chain chain(chain_ctx);
+    kernel<<<grid, block, lds, stream>>>(args...);
+  }
+  return hipGetLastError();
+}
+template <class... P, class... A>
+static hipError_t launch_on(hipStream_t stream, bool capturing, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, const A &...args) {
+  return launch_as<NoChain>(nullptr, stream, capturing, kernel, grid, block, lds, args...);
+}
+template <class... P, class... A>
+static hipError_t launch(dust_ctx *c, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, const A &...args) {
+  return launch_on(c->stream, c->capturing, kernel, grid, block, lds, args...);
+}
+// a one-launch kernel (fused.hpp, tick2.hpp): chained behind the device's other tenants, the mutex held across the enqueue
+template <class... P, class... A>
+static hipError_t launch_chained(dust_ctx *c, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, const A &...args) {
+  return launch_as<PersistChain>(c, c->stream, c->capturing, kernel, grid, block, lds, args...);
+}
+
 // the skid-steer tick with the navigation cost: the kernels of that family (AMPPI and batched SVMPC) take the map as an argument of their own
 static bool skid_nav_on(const dust_ctx *c) { return c->cfg.model == DUST_MODEL_SKID_STEER && c->skid_w_obs != 0.f; }
 
@@ -1827,7 +1879,7 @@ struct SampleOpts {
 // Round 2: once the prior means alias theta (every tick after the first) large sets take the fused pair of launches of
 // pairwise_fused.hpp - one distance pass for prior + repulsion + the Gram matrix, then Gram x score as a GEMM - for D <= 80.
 static int pair_dpb(int D) { return D <= 32 ? 32 : 64; }
-static int fused_dpb(int D) { return D <= 32 ? 32 : (D <= 64 ? 64 : 80); }
+static constexpr int fused_dpb(int D) { return D <= 32 ? 32 : (D <= 64 ? 64 : 80); }
 static int fused_tq(int D) { return D <= 32 ? FusedGeom<32>::TQ : (D <= 64 ? FusedGeom<64>::TQ : FusedGeom<80>::TQ); }
 // "large key set": none of the small-N launch fusions (fused.hpp, tick2.hpp) applies
 static bool pair_is_big(const dust_ctx *c) {
@@ -2131,11 +2183,7 @@ template <class K, class... Mid>
 static int launch_whole_lines(dust_ctx *c, const FirstPass &fp, const RolloutArgs &a, int threads, K fast, K general, Mid... mid) {
   TRY(ensure(&c->wg_flags, &c->wg_flags_cap, (size_t)fp.blocks));
   unsigned int *fl = reinterpret_cast<unsigned int *>(c->wg_flags);
-  for (K k : {fast, general}) {
-    if (fp.lds > 64 * 1024 && !c->capturing) HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp.lds));
-    k<<<fp.blocks, threads, fp.lds, c->stream>>>(a, c->costs_stage, mid..., fl);
-  }
-  HIP_TRY(hipGetLastError());
+  for (K k : {fast, general}) HIP_TRY(launch(c, k, fp.blocks, threads, fp.lds, a, c->costs_stage, mid..., fl));
   return DUST_OK;
 }
 
@@ -2198,9 +2246,7 @@ static int launch_first_pass(dust_ctx *c, const FirstPass &fp, const RolloutArgs
       k.a_mat = a.a_mat;
       k.mc = fp.gw;
       if (fp.lds > 160 * 1024) return fail(DUST_ERR_UNSUPPORTED, "occupancy grid of %d x %d cells: the control-noise / velocity-control rollouts keep it in LDS", k.dm.nx, k.dm.ny);
-      if (fp.lds > 64 * 1024 && !c->capturing)
-        HIP_TRY(hipFuncSetAttribute((const void *)particle_general_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp.lds));
-      particle_general_kernel<<<fp.blocks, PARTGEN_NT, fp.lds, c->stream>>>(k);
+      HIP_TRY(launch(c, particle_general_kernel, fp.blocks, PARTGEN_NT, fp.lds, k));
       break;
     }
     case FP_PART_LINES: {
@@ -2219,6 +2265,14 @@ static int launch_first_pass(dust_ctx *c, const FirstPass &fp, const RolloutArgs
   HIP_TRY(hipGetLastError());
   return DUST_OK;
 }
+
+// Particle with obstacles: the LEAN and STATES rollout bodies read the occupancy grid from LDS
+static bool rollout_grid_ok(const dust_ctx *c, const RolloutArgs &a) {
+  return c->cfg.model != DUST_MODEL_PARTICLE || !a.dm.with_obstacle || a.grid_words > 0;
+}
+// The LEAN rollout body (rollout.hpp: the optional features compiled out) can serve these arguments: the only body the one-launch
+// forms carry (launch_fused, launch_iter, launch_tick2), and launch_rollout's instance when no output asks for more
+static bool rollout_lean_ok(const dust_ctx *c, const RolloutArgs &a) { return a.a_reg == 0.0f && !a.mw && !a.omegaT && rollout_grid_ok(c, a); }
 
 static int launch_rollout(dust_ctx *c, const SampleOpts &o_in) {
   SampleOpts o = o_in;
@@ -2259,41 +2313,24 @@ static int launch_rollout(dust_ctx *c, const SampleOpts &o_in) {
     a.dyn_std[1] = c->cfg.dyn_std[1];
   }
   Prof p(c, DUST_K_ROLLOUT);
-#define DUST_LAUNCH_ROLLOUT(KERNEL)                                                                                            \
-  do {                                                                                                                          \
-    if (lds > 64 * 1024 && !c->capturing)                                                                                       \
-      HIP_TRY(hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                 \
-    KERNEL<<<c->nloc, nt, lds, c->stream>>>(a);                                                                                 \
-  } while (0)
   const bool stream_form = a.noise_mode == NOISE_EPS;
   // LEAN instances: the optional features compiled out (rollout.hpp); STATES: the stored-states form (states staged through LDS,
   // the Particle map in LDS); both need the occupancy grid in LDS when there is one
-  const bool grid_ok = c->cfg.model != DUST_MODEL_PARTICLE || !a.dm.with_obstacle || a.grid_words > 0;
-  const bool lean = !a.states_out && !a.actions_out && !a.costs_in && a.a_reg == 0.0f && !a.mw && !a.tile_scratch && !a.omegaT && grid_ok;
-  const bool states_form = a.states_out && !a.costs_in && !a.mw && !a.tile_scratch && grid_ok && stream_form;
-#define DUST_PICK_ROLLOUT3(MODEL, GR, LN)                                                            \
-  do {                                                                                              \
-    if (states_form) DUST_LAUNCH_ROLLOUT((rollout_stream_kernel<MODEL, GR, false, true>));           \
-    else if (stream_form) DUST_LAUNCH_ROLLOUT((rollout_stream_kernel<MODEL, GR, LN>));               \
-    else DUST_LAUNCH_ROLLOUT((rollout_kernel<MODEL, GR, LN>));                                       \
-  } while (0)
-#define DUST_PICK_ROLLOUT(MODEL)                                     \
-  do {                                                               \
-    if (a.G > 1) {                                                   \
-      if (lean) DUST_PICK_ROLLOUT3(MODEL, true, true);               \
-      else DUST_PICK_ROLLOUT3(MODEL, true, false);                   \
-    } else {                                                         \
-      if (lean) DUST_PICK_ROLLOUT3(MODEL, false, true);              \
-      else DUST_PICK_ROLLOUT3(MODEL, false, false);                  \
-    }                                                                \
-  } while (0)
+  const bool lean = !a.states_out && !a.actions_out && !a.costs_in && !a.tile_scratch && rollout_lean_ok(c, a);
+  const bool states_form = a.states_out && !a.costs_in && !a.mw && !a.tile_scratch && rollout_grid_ok(c, a) && stream_form;
   // (the cart-pole family reaches this kernel in its injected-costs mode only: the one-action instance)
-  if (c->cfg.model == DUST_MODEL_PENDULUM || c->cfg.model == DUST_MODEL_CARTPOLE) DUST_PICK_ROLLOUT(DUST_MODEL_PENDULUM);
-  else DUST_PICK_ROLLOUT(DUST_MODEL_PARTICLE);
-#undef DUST_PICK_ROLLOUT3
-#undef DUST_PICK_ROLLOUT
-#undef DUST_LAUNCH_ROLLOUT
-  HIP_TRY(hipGetLastError());
+  const int model = c->cfg.model == DUST_MODEL_CARTPOLE ? DUST_MODEL_PENDULUM : c->cfg.model;
+  const auto kernel = pick_int<DUST_MODEL_PENDULUM, DUST_MODEL_PARTICLE>(model, [&](auto m) {
+    return pick_bool(a.G > 1, [&](auto gr) {
+      return pick_bool(lean, [&](auto ln) {
+        constexpr int MODEL = decltype(m)::value;
+        constexpr bool GR = decltype(gr)::value, LN = decltype(ln)::value;
+        if (states_form) return rollout_stream_kernel<MODEL, GR, false, true>;
+        return stream_form ? rollout_stream_kernel<MODEL, GR, LN> : rollout_kernel<MODEL, GR, LN>;
+      });
+    });
+  });
+  HIP_TRY(launch(c, kernel, c->nloc, nt, lds, a));
   c->actions_valid = o.want_actions;
   c->actions_f16 = o.want_actions && o.store_f16;
   c->states_valid = o_in.want_states;
@@ -2548,50 +2585,39 @@ static int launch_pair(dust_ctx *c, const PairArgs &a, int tiles) {
   tiles = (a.n_local + PAIR_TI - 1) / PAIR_TI;  // (the caller's count is the primary kernel's: pair_geometry)
   const int cpt = cpt_for(a.D);
   const size_t lds = pairwise_lds_bytes(MODE, cpt);
-  dim3 grid(tiles, a.JS);
-#define DUST_LAUNCH_PAIR(CPT)                                                                                                    \
-  do {                                                                                                                            \
-    if (lds > 64 * 1024 && !c->capturing)                                                                                         \
-      HIP_TRY(hipFuncSetAttribute((const void *)pairwise_kernel<MODE, CPT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    pairwise_kernel<MODE, CPT><<<grid, PAIR_NT, lds, c->stream>>>(a);                                                                  \
-  } while (0)
-  if (cpt == 4) DUST_LAUNCH_PAIR(4);
-  else if (cpt == 8) DUST_LAUNCH_PAIR(8);
-  else if (cpt == 12) DUST_LAUNCH_PAIR(12);
-  else DUST_LAUNCH_PAIR(16);
-#undef DUST_LAUNCH_PAIR
-  HIP_TRY(hipGetLastError());
+  const auto kernel = pick_int<4, 8, 12, 16>(cpt, [](auto k) { return pairwise_kernel<MODE, k()>; });
+  HIP_TRY(launch(c, kernel, dim3(tiles, a.JS), PAIR_NT, lds, a));
   return DUST_OK;
+}
+
+// The rows padded to `dpb` columns (the large-set passes read whole padded rows): a copy in xpad - or, where the caller allows it
+// and D is the padded width already, the rows themselves (D = 80: no pad_rows launch, 7 us per pass at N = 16 384)
+static int padded_rows(dust_ctx *c, const PairArgs &a, int dpb, bool alias_ok, const float **Xp) {
+  TRY(ensure(&c->xpad, &c->xpad_cap, (size_t)c->N * dpb));
+  *Xp = a.X;
+  if (alias_ok && a.D == dpb) return DUST_OK;
+  const int n = c->N * dpb;
+  HIP_TRY(launch(c, pad_rows_kernel, (n + 255) / 256, 256, 0, a.X, c->xpad, c->N, a.D, dpb));
+  *Xp = c->xpad;
+  return DUST_OK;
+}
+// the prior metric's weights: squared inverse scales, one per action dimension
+static void metric_weights(const PairArgs &a, float w[2]) {
+  w[0] = a.inv_s[0] * a.inv_s[0];
+  w[1] = a.da == 2 ? a.inv_s[1] * a.inv_s[1] : w[0];
 }
 
 template <int MODE>
 static int launch_pair_big(dust_ctx *c, const PairArgs &a, int tiles) {
   const int dpb = pair_dpb(a.D);
-  TRY(ensure(&c->xpad, &c->xpad_cap, (size_t)c->N * dpb));
-  {
-    const int n = c->N * dpb;
-    pad_rows_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(a.X, c->xpad, c->N, a.D, dpb);
-    HIP_TRY(hipGetLastError());
-  }
   PairBigArgs b;
   memset(&b, 0, sizeof b);
   b.p = a;
-  b.Xp = c->xpad;
+  TRY(padded_rows(c, a, dpb, false, &b.Xp));
   b.ldp = 8 * cpt_for(a.D);
-  b.w[0] = a.inv_s[0] * a.inv_s[0];
-  b.w[1] = a.da == 2 ? a.inv_s[1] * a.inv_s[1] : b.w[0];
-  const size_t lds = pairwise_big_lds_bytes(MODE, dpb);
-  dim3 grid(tiles, a.JS);
-#define DUST_LAUNCH_BIG(DPB)                                                                                                        \
-  do {                                                                                                                               \
-    if (lds > 64 * 1024 && !c->capturing)                                                                                            \
-      HIP_TRY(hipFuncSetAttribute((const void *)pairwise_big_kernel<MODE, DPB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    pairwise_big_kernel<MODE, DPB><<<grid, PAIR_NT, lds, c->stream>>>(b);                                                            \
-  } while (0)
-  if (dpb == 32) DUST_LAUNCH_BIG(32);
-  else DUST_LAUNCH_BIG(64);
-#undef DUST_LAUNCH_BIG
-  HIP_TRY(hipGetLastError());
+  metric_weights(a, b.w);
+  const auto kernel = pick_int<32, 64>(dpb, [](auto d) { return pairwise_big_kernel<MODE, d()>; });
+  HIP_TRY(launch(c, kernel, dim3(tiles, a.JS), PAIR_NT, pairwise_big_lds_bytes(MODE, dpb), b));
   return DUST_OK;
 }
 
@@ -2621,27 +2647,104 @@ static int packed_slices(const dust_ctx *c, int tiles, int chunks) {
   return std::max(1, std::min(std::min(chunks, 24), want));
 }
 
+// The far pre-pass' arguments (pairwise_far.hpp): what its three callers share.  The caller has zeroed f and set what is its own: tiles,
+// q_rows, lscale, sg[], Xp, wP[] and qperm.  logp: the log-p passes' unit flags and counter slot (far_g, +4), else pass 1's (far_f, +0);
+// masks: query / key masks per unit; counted: the launch reports its {far, all} units (where the counters exist: f.count says).
+static int far_args(dust_ctx *c, const PairArgs &a, int dpb, int chunks, bool logp, bool masks, bool counted, FarArgs &f, dim3 *fgrid) {
+  f.N = c->N;
+  f.D = a.D;
+  f.i0 = a.i0;
+  f.n_local = a.n_local;
+  f.chunks = chunks;
+  f.X = a.X;
+  f.logmix = a.logmix;
+  f.T = c->env.far_t * f.lscale;
+  TRY(ensure(&c->far_z, &c->far_z_cap, ((size_t)c->N * far_zh(dpb) + 1) / 2));
+  TRY(ensure(&c->far_n, &c->far_n_cap, 3 * (size_t)c->N + chunks));
+  TRY(ensure(logp ? &c->far_g : &c->far_f, logp ? &c->far_g_cap : &c->far_f_cap, ((size_t)f.tiles * chunks + 3) / 4));
+  f.Z = reinterpret_cast<_Float16 *>(c->far_z);
+  f.nrm = c->far_n;
+  f.lms = c->far_n + c->N;
+  f.m0 = c->far_n + 2 * (size_t)c->N;
+  f.far = reinterpret_cast<unsigned char *>(logp ? c->far_g : c->far_f);
+  if (masks) {
+    TRY(ensure(&c->far_q, &c->far_q_cap, (size_t)f.tiles * chunks * 8));
+    f.qmask = reinterpret_cast<unsigned int *>(c->far_q);
+  }
+  if (counted) {
+    TRY(far_counts_alloc(c));
+    if (c->far_cnt_host) {
+      f.count = reinterpret_cast<unsigned int *>(c->far_cnt) + (logp ? 4 : 0);
+      f.host_count = c->far_cnt_host + (logp ? 4 : 0);
+    }
+  }
+  const int gx = (f.tiles + 3) / 4;
+  const int want = std::max(1, (3 * device_cus(c) + gx - 1) / gx);  // (three resident workgroups per CU: the launch is bound by the latency of its key loads)
+  f.cps = std::max(1, (chunks + want - 1) / want);
+  *fgrid = dim3(gx, (chunks + f.cps - 1) / f.cps);
+  return DUST_OK;
+}
+template <int DPB>
+static hipError_t launch_far_lb(dust_ctx *c, const FarArgs &f) {
+  return launch(c, far_lb_kernel<DPB>, (std::min(f.N - f.i0, f.q_rows) + 63) / 64, 64 * DUST_FAR_LB_WAVES, 0, f);
+}
+
+// One set of run lists: its buffers sized, far_pack_kernel's arguments for it (pk.far / pk.qmask are the caller's: the far pre-pass' outputs)
+static int pack_args(dust_ctx *c, RunLists &r, int tiles, int chunks, int JS, int merge, PackArgs &pk) {
+  pk.N = c->N;
+  pk.tiles = tiles;
+  pk.chunks = chunks;
+  pk.merge = merge;
+  pk.JS = JS;
+  pk.JSG = JS;
+  pk.ldi = chunks * 64;
+  TRY(ensure(&r.idx, &r.idx_cap, (size_t)tiles * pk.ldi));
+  TRY(ensure(&r.uoff, &r.uoff_cap, (size_t)tiles * (chunks + 1)));
+  TRY(ensure(&r.uq, &r.uq_cap, (size_t)tiles * chunks * 4));
+  TRY(ensure(&r.soff, &r.soff_cap, (size_t)tiles * (JS + 1)));
+  TRY(ensure(&r.goff, &r.goff_cap, (size_t)tiles * (JS + 1)));
+  pk.kidx = reinterpret_cast<int *>(r.idx);
+  pk.uoff = reinterpret_cast<int *>(r.uoff);
+  pk.uq = reinterpret_cast<unsigned int *>(r.uq);
+  pk.soff = reinterpret_cast<int *>(r.soff);
+  pk.goff = reinterpret_cast<int *>(r.goff);
+  return DUST_OK;
+}
+
+// What the two matrix-core log-p passes share of LogpMfmaArgs (zeroed by the caller); the slice rule that gave JS is the caller's own
+static int logp_mfma_args(dust_ctx *c, const PairArgs &a, int dpb, int JS, LogpMfmaArgs &b) {
+  TRY(ensure(&c->xpad, &c->xpad_cap, (size_t)c->N * dpb + 2 * (size_t)c->N));
+  b.N = c->N;
+  b.D = a.D;
+  b.i0 = a.i0;
+  b.n_local = a.n_local;
+  b.JS = JS;
+  TRY(ensure_partials(c, JS));
+  c->prior_js = JS;
+  b.X = a.X;
+  b.logmix = a.logmix;
+  b.sw[0] = a.inv_s[0] * 1.2011224087864498f;  // sqrt(log2 e) / sigma_p
+  b.sw[1] = a.da == 2 ? a.inv_s[1] * 1.2011224087864498f : b.sw[0];
+  b.Z = c->xpad;
+  b.hq = c->xpad + (size_t)c->N * dpb;
+  b.hj = b.hq + c->N;
+  b.pM = c->pM;
+  b.pL = c->pL;
+  return DUST_OK;
+}
+
 // pass 1 of the fused pair (pairwise_packed.hpp): prior partials + repulsion partials + the kernel blocks of the current theta
 static int launch_pair_fused(dust_ctx *c, const PairArgs &a, int tiles) {
   const int dpb = fused_dpb(a.D), tq = fused_tq(a.D);
   const int chunks = (c->N + PAIR_JC - 1) / PAIR_JC;
-  TRY(ensure(&c->xpad, &c->xpad_cap, (size_t)c->N * dpb));
-  TRY(ensure(&c->kmat, &c->kmat_cap, (size_t)tiles * chunks * tq * 64));  // [tiles][chunks][TQ][64]: touched only where units exist
-  const bool whole_rows = a.D == dpb;  // (D = 80: the rows are their own padded copy - no pad_rows launch, 7 us per pass at N = 16 384)
-  if (!whole_rows) {
-    const int n = c->N * dpb;
-    pad_rows_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(a.X, c->xpad, c->N, a.D, dpb);
-    HIP_TRY(hipGetLastError());
-  }
   PairPackedArgs b;
   memset(&b, 0, sizeof b);
   b.p = a;
-  b.Xp = whole_rows ? a.X : c->xpad;
+  TRY(padded_rows(c, a, dpb, true, &b.Xp));
+  TRY(ensure(&c->kmat, &c->kmat_cap, (size_t)tiles * chunks * tq * 64));  // [tiles][chunks][TQ][64]: touched only where units exist
   b.ldp = 8 * cpt_for(a.D);
-  b.wP[0] = a.inv_s[0] * a.inv_s[0];
-  b.wP[1] = a.da == 2 ? a.inv_s[1] * a.inv_s[1] : b.wP[0];
-  const float ell = c->cfg.kernel == DUST_KERNEL_IMQ ? c->cfg.imq_ell : 0.69314718055994531f;
-  b.wS[0] = b.wS[1] = (1.0f / ell) * (1.0f / ell);
+  metric_weights(a, b.wP);
+  b.wS[0] = b.wS[1] = (1.0f / stein_ell(c)) * (1.0f / stein_ell(c));
   b.Kp = c->kmat;
   b.tiles = tiles;
   b.umax = chunks;
@@ -2668,58 +2771,24 @@ static int launch_pair_fused(dust_ctx *c, const PairArgs &a, int tiles) {
     const bool flags = !dense && c->env.far != 0;  // (DUST_FAR=0 / DUST_DENSE=1: visit all)
     FarArgs f;
     memset(&f, 0, sizeof f);
-    f.N = c->N;
-    f.D = a.D;
-    f.i0 = a.i0;
-    f.n_local = c->nloc;
     f.tiles = tiles;
     f.q_rows = tiles * tq;
     f.lscale = 1.0f;
-    f.chunks = chunks;
-    f.X = a.X;
-    f.logmix = a.logmix;
     f.sg[0] = sqrtf(std::min(b.wS[0], b.wP[0]));
     f.sg[1] = sqrtf(std::min(b.wS[1], b.wP[1]));
-    TRY(ensure(&c->far_z, &c->far_z_cap, ((size_t)c->N * far_zh(dpb) + 1) / 2));
-    TRY(ensure(&c->far_n, &c->far_n_cap, 3 * (size_t)c->N + chunks));
-    TRY(ensure(&c->far_f, &c->far_f_cap, ((size_t)tiles * chunks + 3) / 4));
-    f.Z = reinterpret_cast<_Float16 *>(c->far_z);
-    f.nrm = c->far_n;
-    f.lms = c->far_n + c->N;
-    f.m0 = c->far_n + 2 * (size_t)c->N;
-    f.T = c->env.far_t;
     f.Xp = b.Xp;
     f.wP[0] = b.wP[0];
     f.wP[1] = b.wP[1];
-    f.far = reinterpret_cast<unsigned char *>(c->far_f);
     f.qperm = order ? reinterpret_cast<const int *>(c->pk_perm) : nullptr;
-    if (flags) {
-      TRY(ensure(&c->far_q, &c->far_q_cap, (size_t)tiles * chunks * 8));
-      f.qmask = reinterpret_cast<unsigned int *>(c->far_q);
-      TRY(far_counts_alloc(c));
-      if (c->far_cnt_host) {  // {far units, all units} of this pass (dust_debug_far_units)
-        f.count = reinterpret_cast<unsigned int *>(c->far_cnt);
-        f.host_count = c->far_cnt_host;
-      }
-    }
-    const int gx = (tiles + 3) / 4;
-    const int want = std::max(1, (3 * device_cus(c) + gx - 1) / gx);  // (three resident workgroups per CU: the launch is bound by the latency of its key loads)
-    f.cps = std::max(1, (chunks + want - 1) / want);
-    dim3 fgrid(gx, (chunks + f.cps - 1) / f.cps);
-    const int nq = std::min(c->N - a.i0, tiles * tq);
-#define DUST_LAUNCH_FAR(DPB)                                                                         \
-  do {                                                                                               \
-    far_lb_kernel<DPB><<<(nq + 63) / 64, 64 * DUST_FAR_LB_WAVES, 0, c->stream>>>(f);                 \
-    if (flags) {                                                                                     \
-      far_prep_kernel<DPB><<<(c->N + 3) / 4, 256, 0, c->stream>>>(f);                                \
-      far_flags_kernel<DPB, FusedGeom<DPB>::TQ, true><<<fgrid, 256, far_flags_lds_bytes<DPB>(), c->stream>>>(f);      \
-    }                                                                                                \
-  } while (0)
-    if (dpb == 32) DUST_LAUNCH_FAR(32);
-    else if (dpb == 64) DUST_LAUNCH_FAR(64);
-    else DUST_LAUNCH_FAR(80);
-#undef DUST_LAUNCH_FAR
-    HIP_TRY(hipGetLastError());
+    dim3 fgrid;
+    TRY(far_args(c, a, dpb, chunks, false, flags, flags, f, &fgrid));  // ({far units, all units} of this pass: dust_debug_far_units)
+    TRY((pick_int<32, 64, 80>(dpb, [&](auto d) {
+      HIP_TRY(launch_far_lb<d()>(c, f));
+      if (!flags) return (int)DUST_OK;
+      HIP_TRY(launch(c, far_prep_kernel<d()>, (c->N + 3) / 4, 256, 0, f));
+      HIP_TRY(launch(c, far_flags_kernel<d(), FusedGeom<d()>::TQ, true>, fgrid, 256, far_flags_lds_bytes<d()>(), f));
+      return (int)DUST_OK;
+    })));
     b.m0 = f.m0;
     if (flags) {
       pk.far = f.far;
@@ -2731,26 +2800,9 @@ static int launch_pair_fused(dust_ctx *c, const PairArgs &a, int tiles) {
   // the run lists: MERGED below the exact-zero threshold, PLAIN (bit-identical to visiting every chunk) otherwise
   const int JS = packed_slices(c, tiles, chunks);
   b.p.JS = JS;
-  pk.N = c->N;
-  pk.tiles = tiles;
-  pk.chunks = chunks;
-  pk.merge = (pk.qmask != nullptr && merge_mode) ? 1 : 0;
-  pk.JS = JS;
-  pk.JSG = JS;
-  pk.ldi = chunks * 64;
-  TRY(ensure(&c->pk_idx, &c->pk_idx_cap, (size_t)tiles * pk.ldi));
-  TRY(ensure(&c->pk_uoff, &c->pk_uoff_cap, (size_t)tiles * (chunks + 1)));
-  TRY(ensure(&c->pk_uq, &c->pk_uq_cap, (size_t)tiles * chunks * 4));
-  TRY(ensure(&c->pk_soff, &c->pk_soff_cap, (size_t)tiles * (JS + 1)));
-  TRY(ensure(&c->pk_goff, &c->pk_goff_cap, (size_t)tiles * (JS + 1)));
+  TRY(pack_args(c, c->pk, tiles, chunks, JS, (pk.qmask != nullptr && merge_mode) ? 1 : 0, pk));
   TRY(ensure(&c->pk_nzu, &c->pk_nzu_cap, ((size_t)tiles * chunks + 3) / 4));
-  pk.kidx = reinterpret_cast<int *>(c->pk_idx);
-  pk.uoff = reinterpret_cast<int *>(c->pk_uoff);
-  pk.uq = reinterpret_cast<unsigned int *>(c->pk_uq);
-  pk.soff = reinterpret_cast<int *>(c->pk_soff);
-  pk.goff = reinterpret_cast<int *>(c->pk_goff);
-  far_pack_kernel<<<tiles, 1024, far_pack_lds_bytes(chunks), c->stream>>>(pk);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch(c, far_pack_kernel, tiles, 1024, far_pack_lds_bytes(chunks), pk));
   c->pk_tiles = tiles;
   c->pk_umax = chunks;
   c->pk_jsg = JS;
@@ -2773,31 +2825,14 @@ static int launch_pair_fused(dust_ctx *c, const PairArgs &a, int tiles) {
   // the kernel blocks are streamed past the caches when they exceed what L2 + Infinity Cache would hand to pass 2 anyway
   const bool stream_k = !pk.merge && (size_t)c->nloc * chunks * 64 * sizeof(float) > ((size_t)128 << 20);
   b.pB = c->pB;
-  dim3 grid(tiles, JS);
-#define DUST_LAUNCH_FUSED2(MODE, DPB, SK)                                                                                                      \
-  do {                                                                                                                                         \
-    const size_t lds = pairwise_packed_lds_bytes<DPB>();                                                                                       \
-    if (lds > 64 * 1024 && !c->capturing)                                                                                                      \
-      HIP_TRY(hipFuncSetAttribute((const void *)pairwise_packed_kernel<MODE, DPB, SK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    pairwise_packed_kernel<MODE, DPB, SK><<<grid, PAIR_NT, lds, c->stream>>>(b);                                                               \
-  } while (0)
-#define DUST_LAUNCH_FUSED(MODE, DPB)                   \
-  do {                                                 \
-    if (stream_k) DUST_LAUNCH_FUSED2(MODE, DPB, true); \
-    else DUST_LAUNCH_FUSED2(MODE, DPB, false);         \
-  } while (0)
-#define DUST_PICK_FUSED(MODE)                  \
-  do {                                         \
-    if (dpb == 32) DUST_LAUNCH_FUSED(MODE, 32); \
-    else if (dpb == 64) DUST_LAUNCH_FUSED(MODE, 64); \
-    else DUST_LAUNCH_FUSED(MODE, 80);          \
-  } while (0)
-  if (c->cfg.kernel == DUST_KERNEL_IMQ) DUST_PICK_FUSED(PAIR_IMQ);
-  else DUST_PICK_FUSED(PAIR_K1);
-#undef DUST_PICK_FUSED
-#undef DUST_LAUNCH_FUSED
-#undef DUST_LAUNCH_FUSED2
-  HIP_TRY(hipGetLastError());
+  TRY(by_stein_mode(c, [&](auto mode) {
+    return pick_int<32, 64, 80>(dpb, [&](auto d) {
+      constexpr int MODE = decltype(mode)::value, DPB = decltype(d)::value;
+      const auto kernel = stream_k ? pairwise_packed_kernel<MODE, DPB, true> : pairwise_packed_kernel<MODE, DPB, false>;
+      HIP_TRY(launch(c, kernel, dim3(tiles, JS), PAIR_NT, pairwise_packed_lds_bytes<DPB>(), b));
+      return (int)DUST_OK;
+    });
+  }));
   c->kmat_valid = true;
   return DUST_OK;
 }
@@ -2854,90 +2889,33 @@ static bool logp_pack_ok(const dust_ctx *c) {
 }
 static int launch_pair_logp_packed(dust_ctx *c, const PairArgs &a) {
   const int dpb = std::max(16, ((a.D + 15) / 16) * 16);
-  TRY(ensure(&c->xpad, &c->xpad_cap, (size_t)c->N * dpb + 2 * (size_t)c->N));
   const int groups = (a.n_local + 63) / 64, chunks = (c->N + 63) / 64;
   LogpPackedArgs p;
   memset(&p, 0, sizeof p);
   LogpMfmaArgs &b = p.a;
-  b.N = c->N;
-  b.D = a.D;
-  b.i0 = a.i0;
-  b.n_local = a.n_local;
   const int JS = std::max(1, std::min(std::min(chunks, 8), (2 * device_cus(c) + groups - 1) / groups));
-  b.JS = JS;
-  TRY(ensure_partials(c, JS));
-  c->prior_js = JS;
-  b.X = a.X;
-  b.logmix = a.logmix;
-  b.sw[0] = a.inv_s[0] * 1.2011224087864498f;  // sqrt(log2 e) / sigma_p
-  b.sw[1] = a.da == 2 ? a.inv_s[1] * 1.2011224087864498f : b.sw[0];
-  b.Z = c->xpad;
-  b.hq = c->xpad + (size_t)c->N * dpb;
-  b.hj = b.hq + c->N;
-  b.pM = c->pM;
-  b.pL = c->pL;
+  TRY(logp_mfma_args(c, a, dpb, JS, b));
   FarArgs f;
   memset(&f, 0, sizeof f);
-  f.N = c->N;
-  f.D = a.D;
-  f.i0 = a.i0;
-  f.n_local = a.n_local;
   f.tiles = groups;
   f.q_rows = groups * 64;
   f.lscale = 1.44269504088896340736f;
-  f.chunks = chunks;
-  f.X = a.X;
-  f.logmix = a.logmix;
   f.sg[0] = b.sw[0];
   f.sg[1] = b.sw[1];
-  f.T = c->env.far_t * 1.44269504088896340736f;
-  TRY(ensure(&c->far_z, &c->far_z_cap, ((size_t)c->N * far_zh(dpb) + 1) / 2));
-  TRY(ensure(&c->far_n, &c->far_n_cap, 3 * (size_t)c->N + chunks));
-  TRY(ensure(&c->far_g, &c->far_g_cap, ((size_t)groups * chunks + 3) / 4));
-  TRY(ensure(&c->far_q, &c->far_q_cap, (size_t)groups * chunks * 8));
-  f.Z = reinterpret_cast<_Float16 *>(c->far_z);
-  f.nrm = c->far_n;
-  f.lms = c->far_n + c->N;
-  f.m0 = c->far_n + 2 * (size_t)c->N;
   f.Xp = b.Z;  // the scaled rows: unit metric
   f.wP[0] = f.wP[1] = 1.0f;
-  f.far = reinterpret_cast<unsigned char *>(c->far_g);
-  f.qmask = reinterpret_cast<unsigned int *>(c->far_q);
   const bool order = c->pk_order && c->pk_perm && !c->stagewise;  // pass 1's tile order (the one in force this tick)
   f.qperm = order ? reinterpret_cast<const int *>(c->pk_perm) : nullptr;
-  TRY(far_counts_alloc(c));
-  if (c->far_cnt_host) {
-    f.count = reinterpret_cast<unsigned int *>(c->far_cnt) + 4;
-    f.host_count = c->far_cnt_host + 4;
-    if (!c->capturing) c->far_logp_issued++;
-  }
-  const int gx = (groups + 3) / 4;
-  const int want = std::max(1, (3 * device_cus(c) + gx - 1) / gx);
-  f.cps = std::max(1, (chunks + want - 1) / want);
-  dim3 fgrid(gx, (chunks + f.cps - 1) / f.cps);
+  dim3 fgrid;
+  TRY(far_args(c, a, dpb, chunks, true, true, true, f, &fgrid));
+  if (f.count && !c->capturing) c->far_logp_issued++;
   c->far_groups = groups;
   c->far_gchunks = chunks;
   PackArgs pk;
   memset(&pk, 0, sizeof pk);
-  pk.N = c->N;
-  pk.tiles = groups;
-  pk.chunks = chunks;
-  pk.merge = 1;
-  pk.JS = JS;
-  pk.JSG = JS;
   pk.far = f.far;
   pk.qmask = f.qmask;
-  pk.ldi = chunks * 64;
-  TRY(ensure(&c->lp_idx, &c->lp_idx_cap, (size_t)groups * pk.ldi));
-  TRY(ensure(&c->lp_uoff, &c->lp_uoff_cap, (size_t)groups * (chunks + 1)));
-  TRY(ensure(&c->lp_uq, &c->lp_uq_cap, (size_t)groups * chunks * 4));
-  TRY(ensure(&c->lp_soff, &c->lp_soff_cap, (size_t)groups * (JS + 1)));
-  TRY(ensure(&c->lp_goff, &c->lp_goff_cap, (size_t)groups * (JS + 1)));
-  pk.kidx = reinterpret_cast<int *>(c->lp_idx);
-  pk.uoff = reinterpret_cast<int *>(c->lp_uoff);
-  pk.uq = reinterpret_cast<unsigned int *>(c->lp_uq);
-  pk.soff = reinterpret_cast<int *>(c->lp_soff);
-  pk.goff = reinterpret_cast<int *>(c->lp_goff);
+  TRY(pack_args(c, c->lp, groups, chunks, JS, 1, pk));
   p.kidx = pk.kidx;
   p.ldi = pk.ldi;
   p.umax = chunks;
@@ -2945,53 +2923,28 @@ static int launch_pair_logp_packed(dust_ctx *c, const PairArgs &a) {
   p.uq = pk.uq;
   p.soff = pk.soff;
   p.qperm = f.qperm;
-  dim3 grid(groups, JS);
-#define DUST_LAUNCH_LOGPP(DPB)                                                                                                       \
-  do {                                                                                                                              \
-    logp_prep_far_kernel<DPB><<<(c->N + 3) / 4, 256, 0, c->stream>>>(b, f);                                                         \
-    far_lb_kernel<DPB><<<(std::min(c->N - a.i0, f.q_rows) + 63) / 64, 64 * DUST_FAR_LB_WAVES, 0, c->stream>>>(f);                   \
-    far_flags_kernel<DPB, 64, true><<<fgrid, 256, far_flags_lds_bytes<DPB>(), c->stream>>>(f);                                      \
-    far_pack_kernel<<<groups, 1024, far_pack_lds_bytes(chunks), c->stream>>>(pk);                                                    \
-    pairwise_logp_packed_kernel<DPB><<<grid, 256, pairwise_logp_packed_lds_bytes<DPB>(), c->stream>>>(p);                           \
-  } while (0)
-  if (dpb == 16) DUST_LAUNCH_LOGPP(16);
-  else if (dpb == 32) DUST_LAUNCH_LOGPP(32);
-  else if (dpb == 48) DUST_LAUNCH_LOGPP(48);
-  else if (dpb == 64) DUST_LAUNCH_LOGPP(64);
-  else DUST_LAUNCH_LOGPP(80);
-#undef DUST_LAUNCH_LOGPP
-  HIP_TRY(hipGetLastError());
-  return DUST_OK;
+  return pick_int<16, 32, 48, 64, 80>(dpb, [&](auto d) {
+    HIP_TRY(launch(c, logp_prep_far_kernel<d()>, (c->N + 3) / 4, 256, 0, b, f));
+    HIP_TRY(launch_far_lb<d()>(c, f));
+    HIP_TRY(launch(c, far_flags_kernel<d(), 64, true>, fgrid, 256, far_flags_lds_bytes<d()>(), f));
+    HIP_TRY(launch(c, far_pack_kernel, groups, 1024, far_pack_lds_bytes(chunks), pk));
+    HIP_TRY(launch(c, pairwise_logp_packed_kernel<d()>, dim3(groups, JS), 256, pairwise_logp_packed_lds_bytes<d()>(), p));
+    return (int)DUST_OK;
+  });
 }
 
 // log p(theta) only, large aliased sets (SVMPC.forward): product-form distances on the matrix cores + log-sum-exp
 // (pairwise_logp_mfma.hpp).  DUST_LOGP_MFMA=0 keeps the exact-difference pass of pairwise_fused.hpp (development switch).
 static int launch_pair_logp_mfma(dust_ctx *c, const PairArgs &a) {
   const int dpb = std::max(16, ((a.D + 15) / 16) * 16);
-  TRY(ensure(&c->xpad, &c->xpad_cap, (size_t)c->N * dpb + 2 * (size_t)c->N));
   LogpMfmaArgs b;
   memset(&b, 0, sizeof b);
-  b.N = c->N;
-  b.D = a.D;
-  b.i0 = a.i0;
-  b.n_local = a.n_local;
   const int tiles = (a.n_local + 255) / 256, chunks = (c->N + 63) / 64;
   // key slices: one resident round of two workgroups per CU when the set allows it
   int js = std::max(1, std::min(chunks, (2 * device_cus(c)) / tiles));
   const int cps = (chunks + js - 1) / js;
   b.slice = cps * 64;
-  b.JS = (c->N + b.slice - 1) / b.slice;
-  TRY(ensure_partials(c, b.JS));
-  c->prior_js = b.JS;
-  b.X = a.X;
-  b.logmix = a.logmix;
-  b.sw[0] = a.inv_s[0] * 1.2011224087864498f;  // sqrt(log2 e) / sigma_p
-  b.sw[1] = a.da == 2 ? a.inv_s[1] * 1.2011224087864498f : b.sw[0];
-  b.Z = c->xpad;
-  b.hq = c->xpad + (size_t)c->N * dpb;
-  b.hj = b.hq + c->N;
-  b.pM = c->pM;
-  b.pL = c->pL;
+  TRY(logp_mfma_args(c, a, dpb, (c->N + b.slice - 1) / b.slice, b));
   dim3 grid(tiles, b.JS);
   // pairwise_far.hpp: (64-query group, key chunk) blocks whose terms are all negligible against the group's known max logits
   // (DUST_FAR=0 / DUST_DENSE=1: visit all).  Base-2 logits here: log weights and the threshold scaled by log2 e.
@@ -3005,91 +2958,47 @@ static int launch_pair_logp_mfma(dust_ctx *c, const PairArgs &a) {
   c->far_groups = c->far_gchunks = 0;
   dim3 fgrid(1, 1);
   if (flags) {
-    f.N = c->N;
-    f.D = a.D;
-    f.i0 = a.i0;
-    f.n_local = a.n_local;
     f.tiles = (a.n_local + 63) / 64;
     f.q_rows = f.tiles * 64;
     f.lscale = 1.44269504088896340736f;
-    f.chunks = chunks;
-    f.X = a.X;
-    f.logmix = a.logmix;
     f.sg[0] = b.sw[0];
     f.sg[1] = b.sw[1];
-    f.T = c->env.far_t * 1.44269504088896340736f;
-    TRY(ensure(&c->far_z, &c->far_z_cap, ((size_t)c->N * far_zh(dpb) + 1) / 2));
-    TRY(ensure(&c->far_n, &c->far_n_cap, 3 * (size_t)c->N + chunks));
-    TRY(ensure(&c->far_g, &c->far_g_cap, ((size_t)f.tiles * chunks + 3) / 4));
-    f.Z = reinterpret_cast<_Float16 *>(c->far_z);
-    f.nrm = c->far_n;
-    f.lms = c->far_n + c->N;
-    f.m0 = c->far_n + 2 * (size_t)c->N;
     f.Xp = b.Z;  // the scaled rows: unit metric
     f.wP[0] = f.wP[1] = 1.0f;
-    f.far = reinterpret_cast<unsigned char *>(c->far_g);
-    const int gx = (f.tiles + 3) / 4;
-    const int want = std::max(1, (3 * device_cus(c) + gx - 1) / gx);  // (three resident workgroups per CU: the launch is bound by the latency of its key loads)
-    f.cps = std::max(1, (chunks + want - 1) / want);
-    fgrid = dim3(gx, (chunks + f.cps - 1) / f.cps);
-    if (c->far_cnt_host) {
-      f.count = reinterpret_cast<unsigned int *>(c->far_cnt) + 4;
-      f.host_count = c->far_cnt_host + 4;
-      if (!c->capturing) c->far_logp_issued++;  // (a captured launch reports when its graph runs: dust_svmpc_tick counts those)
-    }
+    TRY(far_args(c, a, dpb, chunks, true, false, true, f, &fgrid));
+    if (f.count && !c->capturing) c->far_logp_issued++;  // (a captured launch reports when its graph runs: dust_svmpc_tick counts those)
     b.far = f.far;
     b.groups = f.tiles;
     b.chunks = chunks;
     c->far_groups = f.tiles;
     c->far_gchunks = chunks;
   }
-#define DUST_LAUNCH_LOGPM(DPB)                                                                                                 \
-  do {                                                                                                                          \
-    if (flags) {                                                                                                                \
-      logp_prep_far_kernel<DPB><<<(c->N + 3) / 4, 256, 0, c->stream>>>(b, f);                                                   \
-      far_lb_kernel<DPB><<<(std::min(c->N - a.i0, f.q_rows) + 63) / 64, 64 * DUST_FAR_LB_WAVES, 0, c->stream>>>(f);             \
-      far_flags_kernel<DPB, 64, false><<<fgrid, 256, far_flags_lds_bytes<DPB>(), c->stream>>>(f);                                      \
-    } else {                                                                                                                    \
-      logp_prep_kernel<DPB><<<(c->N + 3) / 4, 256, 0, c->stream>>>(b);                                                          \
-    }                                                                                                                           \
-    pairwise_logp_mfma_kernel<DPB><<<grid, 256, pairwise_logp_mfma_lds_bytes<DPB>(), c->stream>>>(b);                           \
-  } while (0)
-  if (dpb == 16) DUST_LAUNCH_LOGPM(16);
-  else if (dpb == 32) DUST_LAUNCH_LOGPM(32);
-  else if (dpb == 48) DUST_LAUNCH_LOGPM(48);
-  else if (dpb == 64) DUST_LAUNCH_LOGPM(64);
-  else DUST_LAUNCH_LOGPM(80);
-#undef DUST_LAUNCH_LOGPM
-  HIP_TRY(hipGetLastError());
-
-  return DUST_OK;
+  return pick_int<16, 32, 48, 64, 80>(dpb, [&](auto d) {
+    if (flags) {
+      HIP_TRY(launch(c, logp_prep_far_kernel<d()>, (c->N + 3) / 4, 256, 0, b, f));
+      HIP_TRY(launch_far_lb<d()>(c, f));
+      HIP_TRY(launch(c, far_flags_kernel<d(), 64, false>, fgrid, 256, far_flags_lds_bytes<d()>(), f));
+    } else {
+      HIP_TRY(launch(c, logp_prep_kernel<d()>, (c->N + 3) / 4, 256, 0, b));
+    }
+    HIP_TRY(launch(c, pairwise_logp_mfma_kernel<d()>, grid, 256, pairwise_logp_mfma_lds_bytes<d()>(), b));
+    return (int)DUST_OK;
+  });
 }
 
 // log p(theta) only, large aliased sets (SVMPC.forward): the distance pass + log-sum-exp of pairwise_fused.hpp
 static int launch_pair_logp_big(dust_ctx *c, const PairArgs &a, int tiles) {
   const int dpb = fused_dpb(a.D);
-  TRY(ensure(&c->xpad, &c->xpad_cap, (size_t)c->N * dpb));
-  const bool whole_rows = a.D == dpb;  // (D = 80: the rows are their own padded copy - no pad_rows launch, 7 us per pass at N = 16 384)
-  if (!whole_rows) {
-    const int n = c->N * dpb;
-    pad_rows_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(a.X, c->xpad, c->N, a.D, dpb);
-    HIP_TRY(hipGetLastError());
-  }
   PairFusedArgs b;
   memset(&b, 0, sizeof b);
   b.p = a;
-  b.Xp = whole_rows ? a.X : c->xpad;
+  TRY(padded_rows(c, a, dpb, true, &b.Xp));
   b.ldp = 8 * cpt_for(a.D);
-  b.wP[0] = a.inv_s[0] * a.inv_s[0];
-  b.wP[1] = a.da == 2 ? a.inv_s[1] * a.inv_s[1] : b.wP[0];
-  dim3 grid(tiles, a.JS);
-#define DUST_LAUNCH_LOGP(DPB) pairwise_logp_big_kernel<DPB><<<grid, PAIR_NT, pairwise_logp_big_lds_bytes<DPB>(), c->stream>>>(b)
-  if (dpb == 32) DUST_LAUNCH_LOGP(32);
-  else if (dpb == 64) DUST_LAUNCH_LOGP(64);
-  else DUST_LAUNCH_LOGP(80);
-#undef DUST_LAUNCH_LOGP
-  HIP_TRY(hipGetLastError());
-  return DUST_OK;
+  metric_weights(a, b.wP);
+  return pick_int<32, 64, 80>(dpb, [&](auto d) {
+    HIP_TRY(launch(c, pairwise_logp_big_kernel<d()>, dim3(tiles, a.JS), PAIR_NT, pairwise_logp_big_lds_bytes<d()>(), b));
+    return (int)DUST_OK;
+  });
 }
 
 // pass 2: pA = K x score over the run lists of pass 1 (matrix cores; pairwise_packed.hpp)
@@ -3107,40 +3016,32 @@ static int launch_gram_score(dust_ctx *c, const PairArgs &a, int *JS_out) {
   g.Kp = c->kmat;
   g.V = c->score;
   g.pA = c->pA;
-  g.kidx = reinterpret_cast<const int *>(c->pk_idx);
+  g.kidx = reinterpret_cast<const int *>(c->pk.idx);
   g.ldi = c->pk_umax * 64;
-  g.uoff = reinterpret_cast<const int *>(c->pk_uoff);
-  g.uq = c->pk_masks ? reinterpret_cast<const unsigned int *>(c->pk_uq) : nullptr;
-  g.goff = reinterpret_cast<const int *>(c->pk_goff);
+  g.uoff = reinterpret_cast<const int *>(c->pk.uoff);
+  g.uq = c->pk_masks ? reinterpret_cast<const unsigned int *>(c->pk.uq) : nullptr;
+  g.goff = reinterpret_cast<const int *>(c->pk.goff);
   g.qperm = c->pk_order ? reinterpret_cast<const int *>(c->pk_perm) : nullptr;
   g.nzu = c->pk_dense ? nullptr : reinterpret_cast<const unsigned char *>(c->pk_nzu);
-  dim3 grid(g.tiles, g.JS);
   // (its own column padding: whole 16-column MFMA tiles, not the 32 / 64 / 80 of pass 1 - D = 40 runs 3 column tiles instead of 4;
   //  the query tile is pass 1's: 128 / 112 / 96 rows at D <= 32 / 64 / 80)
-#define DUST_LAUNCH_GS(DPG, TQ) gram_packed_kernel<DPG, TQ><<<grid, GramGeom<TQ>::NT, gram_packed_lds_bytes<DPG, TQ>(), c->stream>>>(g)
-  const int dpg = ((a.D + 15) / 16) * 16;
-  if (dpg == 16) DUST_LAUNCH_GS(16, FusedGeom<32>::TQ);
-  else if (dpg == 32) DUST_LAUNCH_GS(32, FusedGeom<32>::TQ);
-  else if (dpg == 48) DUST_LAUNCH_GS(48, FusedGeom<64>::TQ);
-  else if (dpg == 64) DUST_LAUNCH_GS(64, FusedGeom<64>::TQ);
-  else DUST_LAUNCH_GS(80, FusedGeom<80>::TQ);
-#undef DUST_LAUNCH_GS
-  HIP_TRY(hipGetLastError());
+  TRY((pick_int<16, 32, 48, 64, 80>(((a.D + 15) / 16) * 16, [&](auto d) {
+    constexpr int DPG = decltype(d)::value, TQ = FusedGeom<fused_dpb(DPG)>::TQ;
+    HIP_TRY(launch(c, gram_packed_kernel<DPG, TQ>, dim3(g.tiles, g.JS), GramGeom<TQ>::NT, gram_packed_lds_bytes<DPG, TQ>(), g));
+    return (int)DUST_OK;
+  })));
   if (c->pk_order) {
     // The next tick's tile order, from the leaders pass 1 noted.  One workgroup, 8 us at 2 048 rows and 42 us at 16 384, and nothing
     // in this tick needs its result: large sets run it on the side stream beside the update and the log-p pass; the tick's last
     // launches (forward_finish_device) - or the next pass 1, whichever comes first - wait for it.
-    const size_t lds = query_order_lds_bytes(c->nloc);
-    if (lds > 64 * 1024 && !c->capturing)
-      HIP_TRY(hipFuncSetAttribute((const void *)query_order_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const bool side = c->stream2 && !c->prof && c->nloc >= 8192;  // (below that the kernel is shorter than the two cross-stream waits: 8 us at 2 048 rows)
     hipStream_t qs = side ? c->stream2 : c->stream;
     if (side) {
       HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
       HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
     }
-    query_order_kernel<<<1, 1024, lds, qs>>>(reinterpret_cast<int *>(c->pk_lead), reinterpret_cast<int *>(c->pk_perm), c->nloc, c->n0, c->N);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_on(qs, c->capturing, query_order_kernel, 1, 1024, query_order_lds_bytes(c->nloc), reinterpret_cast<int *>(c->pk_lead),
+                      reinterpret_cast<int *>(c->pk_perm), c->nloc, c->n0, c->N));
     if (side) {
       HIP_TRY(hipEventRecord(c->ev_order, c->stream2));
       c->order_pending = true;
@@ -3239,8 +3140,7 @@ static int launch_fused(dust_ctx *c, const SampleOpts &o, bool *done) {
   oo.merge_prior = 1;
   TRY(rollout_args(c, oo, f.ra, &nt, &lds_r));
   if (f.ra.tile_scratch || (PAIR_NT % nt) != 0) return DUST_OK;
-  if (f.ra.a_reg != 0.0f || f.ra.mw || f.ra.omegaT) return DUST_OK;  // the fused launch carries the LEAN rollout body only
-  if (c->cfg.model == DUST_MODEL_PARTICLE && f.ra.dm.with_obstacle && f.ra.grid_words == 0) return DUST_OK;  // (LEAN: map in LDS)
+  if (!rollout_lean_ok(c, f.ra)) return DUST_OK;  // the fused launch carries the LEAN rollout body only
   f.sub_nt = nt;
   f.per_block = PAIR_NT / nt;
   if (c->nloc % f.per_block || PAIR_TI % f.per_block) return DUST_OK;
@@ -3271,28 +3171,13 @@ static int launch_fused(dust_ctx *c, const SampleOpts &o, bool *done) {
   f.cnt = c->fused_cnt;
   f.timeout_flag = c->fused_cnt + (size_t)f.tiles * CNT_STRIDE;
   const int grid = f.n_k2_blocks + f.n_pair_blocks + c->nloc / f.per_block;
-#define DUST_LAUNCH_FUSED2(MODEL, CPT, GR)                                                                                                \
-  do {                                                                                                                                  \
-    if (lds > 64 * 1024 && !c->capturing)                                                                                               \
-      HIP_TRY(hipFuncSetAttribute((const void *)fused_prior_rollout_kernel<MODEL, CPT, GR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    PersistChain chain(c);                                                                                                              \
-    fused_prior_rollout_kernel<MODEL, CPT, GR><<<grid, PAIR_NT, lds, c->stream>>>(f);                                                  \
-  } while (0)
-#define DUST_LAUNCH_FUSED(MODEL, CPT)                   \
-  do {                                                   \
-    if (f.ra.G > 1) DUST_LAUNCH_FUSED2(MODEL, CPT, true); \
-    else DUST_LAUNCH_FUSED2(MODEL, CPT, false);           \
-  } while (0)
-  if (c->cfg.model == DUST_MODEL_PENDULUM) {
-    if (cpt == 4) DUST_LAUNCH_FUSED(DUST_MODEL_PENDULUM, 4);
-    else DUST_LAUNCH_FUSED(DUST_MODEL_PENDULUM, 8);
-  } else {
-    if (cpt == 4) DUST_LAUNCH_FUSED(DUST_MODEL_PARTICLE, 4);
-    else DUST_LAUNCH_FUSED(DUST_MODEL_PARTICLE, 8);
-  }
-#undef DUST_LAUNCH_FUSED2
-#undef DUST_LAUNCH_FUSED
-  HIP_TRY(hipGetLastError());
+  const auto kernel = pick_int<DUST_MODEL_PENDULUM, DUST_MODEL_PARTICLE>(c->cfg.model, [&](auto m) {
+    return pick_int<4, 8>(cpt, [&](auto k) {
+      constexpr int MODEL = decltype(m)::value, CPT = decltype(k)::value;
+      return f.ra.G > 1 ? fused_prior_rollout_kernel<MODEL, CPT, true> : fused_prior_rollout_kernel<MODEL, CPT, false>;
+    });
+  });
+  HIP_TRY(launch_chained(c, kernel, grid, PAIR_NT, lds, f));
   c->fused_dirty = true;
   c->stein_dirty = false;
   c->actions_valid = false;
@@ -3333,8 +3218,7 @@ static UpdateArgs update_args(dust_ctx *c, int apply) {
   u.n_local = c->nloc;
   u.apply = apply;
   u.opt = c->opt;
-  const float ell = c->cfg.kernel == DUST_KERNEL_IMQ ? c->cfg.imq_ell : 0.69314718055994531f;  // softplus(0) = ln 2 (svmpc.py:78 typo keeps it)
-  u.inv_l2 = 1.0f / (ell * ell);
+  u.inv_l2 = 1.0f / (stein_ell(c) * stein_ell(c));
   u.inv_n = 1.0f / c->N;
   u.ldp = 8 * cpt_for(c->D);
   u.pA = c->pA;
@@ -3443,8 +3327,7 @@ static int launch_stein_update(dust_ctx *c, int apply, bool in_loop = false /* K
     a.Y = c->theta;
     a.V = c->score;
     a.magicD = (uint32_t)((1ull << 32) / (uint64_t)c->D) + 1u;
-    const float ell = c->cfg.kernel == DUST_KERNEL_IMQ ? c->cfg.imq_ell : 0.69314718055994531f;
-    for (int d = 0; d < 4; ++d) a.inv_s[d] = 1.0f / ell;
+    for (int d = 0; d < 4; ++d) a.inv_s[d] = 1.0f / stein_ell(c);
     a.pA = c->pA;
     a.pB = c->pB;
     a.stamps = c->stamps_dev ? c->stamps_dev + 16 * DUST_K_STEIN : nullptr;
@@ -3496,20 +3379,10 @@ static int launch_stein_update(dust_ctx *c, int apply, bool in_loop = false /* K
       f.cnt = c->stein_cnt;
       f.timeout_flag = c->stein_cnt + ((size_t)tiles + 1) * CNT_STRIDE;
       const int grid = f.n_pair_blocks + (n + PAIR_NT - 1) / PAIR_NT;
-#define DUST_LAUNCH_SU(MODE, CPT)                                            \
-  do {                                                                        \
-    PersistChain chain(c);                                                    \
-    stein_update_kernel<MODE, CPT><<<grid, PAIR_NT, lds, c->stream>>>(f);     \
-  } while (0)
-      if (c->cfg.kernel == DUST_KERNEL_IMQ) {
-        if (cpt == 4) DUST_LAUNCH_SU(PAIR_IMQ, 4);
-        else DUST_LAUNCH_SU(PAIR_IMQ, 8);
-      } else {
-        if (cpt == 4) DUST_LAUNCH_SU(PAIR_K1, 4);
-        else DUST_LAUNCH_SU(PAIR_K1, 8);
-      }
-#undef DUST_LAUNCH_SU
-      HIP_TRY(hipGetLastError());
+      const auto kernel = by_stein_mode(c, [&](auto mode) {
+        return pick_int<4, 8>(cpt, [](auto k) { return stein_update_kernel<decltype(mode)::value, k()>; });
+      });
+      HIP_TRY(launch_chained(c, kernel, grid, PAIR_NT, lds, f));
       if (pingpong) std::swap(c->theta, c->theta_alt);
       c->stein_dirty = true;
       c->fused_dirty = false;
@@ -3571,12 +3444,8 @@ extern "C" int dust_svmpc_phi(dust_ctx *c, const float *costs, const float *acti
   return DUST_OK;
 }
 
-// local half of one SVGD iteration: prior partials -> rollout (+ merge) -> score rows of this shard
-static int local_score_device(dust_ctx *c, const float *noise_dev, int param_set) {
-  // The prior pass and the rollout kernel both only READ theta: one launch for both where the shape allows it (launch_fused),
-  // else the prior pass, then the rollout kernel with the combine folded in (score = grad_lik + grad_pri), on one stream.
-  // Measured on MI355X (round 1): a fork / join form over two streams lost more to the cross-stream event waits than the
-  // overlap gained at cfg2 sizes (2 695 vs 3 010 ticks/s).
+// The score pass' sampling options: this iteration's noise around the particles, a_mat refreshed, Adam's step counted (merge_prior: the caller's)
+static SampleOpts score_opts(const dust_ctx *c, const float *noise_dev) {
   SampleOpts o;
   memset(&o, 0, sizeof o);
   o.noise_mode = noise_dev ? NOISE_EPS : NOISE_PHILOX;
@@ -3584,16 +3453,34 @@ static int local_score_device(dust_ctx *c, const float *noise_dev, int param_set
   o.base = c->theta;
   o.update_a_mat = 1;
   o.bump_adam = 1;
+  return o;
+}
+// c->params_dev at set `param_set` of the tick's dynamics samples ([n_sets][M][P]) while the guard lives
+struct ParamSet {
+  dust_ctx *c;
+  float *save;
+  ParamSet(dust_ctx *c_, int param_set) : c(c_), save(c_->params_dev) {
+    if (c->params_dev) c->params_dev += (size_t)param_set * c->M * c->P;
+  }
+  ~ParamSet() { c->params_dev = save; }
+};
+
+// local half of one SVGD iteration: prior partials -> rollout (+ merge) -> score rows of this shard
+static int local_score_device(dust_ctx *c, const float *noise_dev, int param_set) {
+  // The prior pass and the rollout kernel both only READ theta: one launch for both where the shape allows it (launch_fused),
+  // else the prior pass, then the rollout kernel with the combine folded in (score = grad_lik + grad_pri), on one stream.
+  // Measured on MI355X (round 1): a fork / join form over two streams lost more to the cross-stream event waits than the
+  // overlap gained at cfg2 sizes (2 695 vs 3 010 ticks/s).
+  SampleOpts o = score_opts(c, noise_dev);
   const bool split = full_cov(c);  // (full prior covariance: the merge epilogue of the rollout kernel has no back-substitution)
   o.merge_prior = split ? 0 : 1;
-  float *save = c->params_dev;
-  if (c->params_dev) c->params_dev += (size_t)param_set * c->M * c->P;
   bool fused = false;
-  int s = launch_fused(c, o, &fused);
-  if (s == DUST_OK && !fused) s = launch_prior(c);
-  if (s == DUST_OK && !fused) s = launch_rollout(c, o);
-  c->params_dev = save;
-  TRY(s);
+  {
+    ParamSet at(c, param_set);
+    TRY(launch_fused(c, o, &fused));
+    if (!fused) TRY(launch_prior(c));
+    if (!fused) TRY(launch_rollout(c, o));
+  }
   c->have_sample = true;
   if (!fused && split) TRY(launch_prior_finish(c, true, false));
   return DUST_OK;
@@ -3612,24 +3499,16 @@ static int launch_iter(dust_ctx *c, const float *noise_dev, int param_set, bool 
   memset(&f, 0, sizeof f);
   TRY(prior_args(c, f.prior, &f.tiles));
   if (f.prior.JS > 16 || f.prior.slice > PAIR_JC) return DUST_OK;  // single-chunk key slices (stein_split_body)
-  SampleOpts o;
-  memset(&o, 0, sizeof o);
-  o.noise_mode = noise_dev ? NOISE_EPS : NOISE_PHILOX;
-  o.noise_dev = noise_dev;
-  o.base = c->theta;
-  o.update_a_mat = 1;
-  o.bump_adam = 1;
+  SampleOpts o = score_opts(c, noise_dev);
   o.merge_prior = 1;
   int nt;
   size_t lds_r;
-  float *sv = c->params_dev;
-  if (c->params_dev) c->params_dev += (size_t)param_set * c->M * c->P;
-  int sr = rollout_args(c, o, f.ra, &nt, &lds_r);
-  c->params_dev = sv;
-  TRY(sr);
+  {
+    ParamSet at(c, param_set);
+    TRY(rollout_args(c, o, f.ra, &nt, &lds_r));
+  }
   if (f.ra.tile_scratch || (PAIR_NT % nt) != 0 || f.ra.G > 1) return DUST_OK;
-  if (f.ra.a_reg != 0.0f || f.ra.mw || f.ra.omegaT) return DUST_OK;  // LEAN rollout body only
-  if (c->cfg.model == DUST_MODEL_PARTICLE && f.ra.dm.with_obstacle && f.ra.grid_words == 0) return DUST_OK;  // (LEAN: map in LDS)
+  if (!rollout_lean_ok(c, f.ra)) return DUST_OK;  // LEAN rollout body only
   f.ra.rearm = nullptr;
   f.ra.rearm_n = 0;
   f.sub_nt = nt;
@@ -3660,10 +3539,7 @@ static int launch_iter(dust_ctx *c, const float *noise_dev, int param_set, bool 
   f.stein = f.prior;
   f.stein.Y = c->theta;
   f.stein.logmix = nullptr;
-  {
-    const float ell = c->cfg.kernel == DUST_KERNEL_IMQ ? c->cfg.imq_ell : 0.69314718055994531f;
-    for (int d = 0; d < 4; ++d) f.stein.inv_s[d] = 1.0f / ell;
-  }
+  for (int d = 0; d < 4; ++d) f.stein.inv_s[d] = 1.0f / stein_ell(c);
   f.stein.pA = c->pS;  // own buffer: pA holds the prior partials, which the rollout role may still be reading
   f.stein.pB = c->pB;
   f.stein.pM = nullptr;
@@ -3688,26 +3564,12 @@ static int launch_iter(dust_ctx *c, const float *noise_dev, int param_set, bool 
   f.tl = c->tl_dev;
   const int n = c->nloc * c->D;
   const int grid = 2 * f.n_pair_blocks + f.n_roll_blocks + (n + PAIR_NT - 1) / PAIR_NT;
-#define DUST_LAUNCH_ITER(MODEL, MODE, CPT)                                          \
-  do {                                                                              \
-    PersistChain chain(c);                                                          \
-    svgd_iter_kernel<MODEL, MODE, CPT><<<grid, PAIR_NT, lds, c->stream>>>(f);       \
-  } while (0)
-#define DUST_PICK_ITER(MODEL)                                       \
-  do {                                                              \
-    if (c->cfg.kernel == DUST_KERNEL_IMQ) {                         \
-      if (cpt == 4) DUST_LAUNCH_ITER(MODEL, PAIR_IMQ, 4);           \
-      else DUST_LAUNCH_ITER(MODEL, PAIR_IMQ, 8);                    \
-    } else {                                                        \
-      if (cpt == 4) DUST_LAUNCH_ITER(MODEL, PAIR_K1, 4);            \
-      else DUST_LAUNCH_ITER(MODEL, PAIR_K1, 8);                     \
-    }                                                               \
-  } while (0)
-  if (c->cfg.model == DUST_MODEL_PENDULUM) DUST_PICK_ITER(DUST_MODEL_PENDULUM);
-  else DUST_PICK_ITER(DUST_MODEL_PARTICLE);
-#undef DUST_PICK_ITER
-#undef DUST_LAUNCH_ITER
-  HIP_TRY(hipGetLastError());
+  const auto kernel = pick_int<DUST_MODEL_PENDULUM, DUST_MODEL_PARTICLE>(c->cfg.model, [&](auto m) {
+    return by_stein_mode(c, [&](auto mode) {
+      return pick_int<4, 8>(cpt, [](auto k) { return svgd_iter_kernel<decltype(m)::value, decltype(mode)::value, k()>; });
+    });
+  });
+  HIP_TRY(launch_chained(c, kernel, grid, PAIR_NT, lds, f));
   c->iter_set ^= 1;
   std::swap(c->theta, c->theta_alt);
   c->actions_valid = false;
@@ -3972,16 +3834,15 @@ extern "C" int dust_svmpc_forward_ex(dust_ctx *c, int steps, const float *resamp
 // ---------------------------------------------------------------------------------------------------------------
 // One launch per control tick, owner-computes form (tick2.hpp): two all-to-all hand-offs per SVGD iteration instead of four.
 // *done stays false when the shape / configuration does not qualify (the launch-per-iteration path runs).
-// the static part of launch_tick2's eligibility (everything but "the prior means alias the particles")
-static bool tick2_shape_ok(dust_ctx *c, int n_steps) {
-  if (c->env.no_tick2 >= 0 || c->env.no_fuse >= 0) return false;
-  if (c->prof || c->handoff_banned || c->nloc != c->N || c->theta_pinned || n_steps < 1) return false;
-  if ((c->cfg.model != DUST_MODEL_PENDULUM && c->cfg.model != DUST_MODEL_PARTICLE) || two_pass_family(c)) return false;
+// The part of the one-launch tick's eligibility that is a function of the context alone: what launch_tick2 takes and closed-loop
+// serving promises (tick2_shape_ok) cannot drift apart
+static bool tick2_shape(dust_ctx *c) {
+  if ((c->cfg.model != DUST_MODEL_PENDULUM && c->cfg.model != DUST_MODEL_PARTICLE) || two_pass_family(c)) return false;  // (launch-per-iteration families: skid.hpp, particle_general.hpp)
   if (c->cfg.kernel != DUST_KERNEL_K1_RBF && c->cfg.kernel != DUST_KERNEL_IMQ) return false;
-  if (c->cfg.roll_strategy == DUST_ROLL_RESAMPLE || c->cfg.a_reg != 0.0f || c->mw_dev) return false;
+  if (c->cfg.roll_strategy == DUST_ROLL_RESAMPLE) return false;
   if (c->N % T2_PW || c->D > T2_ROW || c->N / T2_PW > device_cus(c) || c->M > T2_MAXM) return false;
   for (int d = 1; d < c->da; ++d)
-    if (c->cfg.sigma_p[d] != c->cfg.sigma_p[0]) return false;
+    if (c->cfg.sigma_p[d] != c->cfg.sigma_p[0]) return false;  // isotropic prior scale: one squared distance serves both kernels
   const int steps = (((c->N + 63) / 64) + 15) & ~15;
   int gw = 0;
   if (c->cfg.model == DUST_MODEL_PARTICLE && c->cfg.with_obstacle && c->grid_bits) {
@@ -3991,32 +3852,29 @@ static bool tick2_shape_ok(dust_ctx *c, int n_steps) {
   }
   return (size_t)tick2_lds(c->S, c->D, steps, gw).total * sizeof(float) <= 160 * 1024;
 }
+// the static part of launch_tick2's eligibility (everything but "the prior means alias the particles")
+static bool tick2_shape_ok(dust_ctx *c, int n_steps) {
+  if (c->env.no_tick2 >= 0 || c->env.no_fuse >= 0) return false;
+  if (c->prof || c->handoff_banned || c->nloc != c->N || c->theta_pinned || n_steps < 1) return false;
+  if (c->cfg.a_reg != 0.0f || c->mw_dev) return false;  // (launch_tick2 reads the same two through rollout_args: rollout_lean_ok)
+  return tick2_shape(c);
+}
 
 static int launch_tick2(dust_ctx *c, const float *state, int n_steps, const float *eps_dev, bool do_forward, bool *done) {
   *done = false;
-  if (two_pass_family(c)) return DUST_OK;  // (these families run on the launch-per-iteration path: skid.hpp, particle_general.hpp)
   if (c->env.no_tick2 >= 0 || c->env.no_fuse >= 0) return DUST_OK;  // development switches
   if (c->prof || c->nloc != c->N || c->theta_pinned || c->capturing || !c->mu_aliased) return DUST_OK;
-  if (c->cfg.kernel != DUST_KERNEL_K1_RBF && c->cfg.kernel != DUST_KERNEL_IMQ) return DUST_OK;
   if (n_steps < 0 || (n_steps == 0 && !do_forward)) return DUST_OK;
-  if (c->cfg.roll_strategy == DUST_ROLL_RESAMPLE) return DUST_OK;
   if (do_forward && !c->have_sample && n_steps == 0) return DUST_OK;
   if (c->noise_f16 && eps_dev) return DUST_OK;
-  if (c->N % T2_PW || c->D > T2_ROW || c->N / T2_PW > device_cus(c)) return DUST_OK;
-  for (int d = 1; d < c->da; ++d)
-    if (c->cfg.sigma_p[d] != c->cfg.sigma_p[0]) return DUST_OK;  // isotropic prior scale: one squared distance serves both kernels
-  SampleOpts o;
-  memset(&o, 0, sizeof o);
-  o.noise_mode = eps_dev ? NOISE_EPS : NOISE_PHILOX;
-  o.noise_dev = eps_dev;
-  o.base = c->theta;
-  o.update_a_mat = 1;
+  if (!tick2_shape(c)) return DUST_OK;
+  SampleOpts o = score_opts(c, eps_dev);
+  o.bump_adam = 0;  // (tick2.hpp steps the optimiser itself, n_iters times)
   RolloutArgs ra;
   int nt;
   size_t lds_r;
   TRY(rollout_args(c, o, ra, &nt, &lds_r));
-  if (ra.a_reg != 0.0f || ra.mw || ra.omegaT) return DUST_OK;
-  if (c->cfg.model == DUST_MODEL_PARTICLE && ra.dm.with_obstacle && ra.grid_words == 0) return DUST_OK;
+  if (!rollout_lean_ok(c, ra)) return DUST_OK;
   Tick2Args f;
   memset(&f, 0, sizeof f);
   f.dm = ra.dm;
@@ -4053,7 +3911,6 @@ static int launch_tick2(dust_ctx *c, const float *state, int n_steps, const floa
     f.sigma_a[d] = ra.sigma_a[d];
   }
   const size_t lds = (size_t)tick2_lds(c->S, c->D, f.steps, f.grid_words).total * sizeof(float);
-  if (lds > 160 * 1024 || c->M > T2_MAXM) return DUST_OK;
   const int mode = c->cfg.kernel == DUST_KERNEL_IMQ ? PAIR_IMQ : PAIR_K1;
   HIP_TRY(hipSetDevice(c->cfg.device));
   if (!c->t2_occ || c->t2_occ_lds != lds) {
@@ -4083,7 +3940,7 @@ static int launch_tick2(dust_ctx *c, const float *state, int n_steps, const floa
     HIP_TRY(hipMemsetAsync(c->t2_cnt, 0, (size_t)2 * T2_SETS * T2_CNT_STRIDE * sizeof(unsigned int), c->stream));
     c->t2_set = 0;
   }
-  const float ell = c->cfg.kernel == DUST_KERNEL_IMQ ? c->cfg.imq_ell : 0.69314718055994531f;
+  const float ell = stein_ell(c);
   const float sp = c->cfg.sigma_p[0];
   f.inv_sp2 = 1.0f / (sp * sp);
   f.cP = (float)(-0.5 * 1.4426950408889634 / ((double)sp * (double)sp));
@@ -4557,18 +4414,10 @@ static int sharded_steps(dust_ctx *c, const float *state, int n_steps, const flo
     TRY(stage_noise(c, eps ? eps + (size_t)k * slice : nullptr, flags, &nd));
     if (gather_in_flight) {
       // rollouts first (own rows only, no merge of prior partials), then the prior pass once every rank's particles have landed
-      SampleOpts o;
-      memset(&o, 0, sizeof o);
-      o.noise_mode = nd ? NOISE_EPS : NOISE_PHILOX;
-      o.noise_dev = nd;
-      o.base = c->theta;
-      o.update_a_mat = 1;
-      o.bump_adam = 1;
-      float *save = c->params_dev;
-      if (c->params_dev) c->params_dev += (size_t)k * c->M * c->P;
-      const int st = launch_rollout(c, o);
-      c->params_dev = save;
-      TRY(st);
+      {
+        ParamSet at(c, k);
+        TRY(launch_rollout(c, score_opts(c, nd)));
+      }
       c->have_sample = true;
       if (gather_in_flight == 2) TRY(peer_wait(c, GATHER_THETA));
       else HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_join, 0));
@@ -5150,15 +4999,7 @@ extern "C" int dust_svmpc_local_rollout(dust_ctx *c, const float *state, const f
   TRY(upload_state_params(c, state, params, 1));
   const float *nd = nullptr;
   TRY(stage_noise(c, eps, flags, &nd));
-  SampleOpts o;
-  memset(&o, 0, sizeof o);
-  o.noise_mode = nd ? NOISE_EPS : NOISE_PHILOX;
-  o.noise_dev = nd;
-  o.base = c->theta;
-  o.update_a_mat = 1;
-  o.bump_adam = 1;
-  o.merge_prior = 0;
-  TRY(launch_rollout(c, o));
+  TRY(launch_rollout(c, score_opts(c, nd)));  // (merge_prior = 0)
   c->have_sample = true;
   return DUST_OK;
 }
@@ -5427,7 +5268,7 @@ extern "C" int dust_debug_pack_lists(dust_ctx *c, int tile, int *n_units, int *j
   const int JS = c->pk_jsg, um = c->pk_umax;
   if (tile == -1) {  // totals: *n_units = the units of all tiles, *js = tiles x chunks (what visiting every unit would walk)
     std::vector<int> all((size_t)c->pk_tiles * (JS + 1));
-    HIP_TRY(hipMemcpy(all.data(), c->pk_soff, all.size() * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(all.data(), c->pk.soff, all.size() * sizeof(int), hipMemcpyDeviceToHost));
     long tot = 0;
     for (int t = 0; t < c->pk_tiles; ++t) tot += all[(size_t)t * (JS + 1) + JS];
     *n_units = (int)tot;
@@ -5435,16 +5276,16 @@ extern "C" int dust_debug_pack_lists(dust_ctx *c, int tile, int *n_units, int *j
     return DUST_OK;
   }
   std::vector<int> so((size_t)JS + 1);
-  HIP_TRY(hipMemcpy(so.data(), reinterpret_cast<int *>(c->pk_soff) + (size_t)tile * (JS + 1), so.size() * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(so.data(), reinterpret_cast<int *>(c->pk.soff) + (size_t)tile * (JS + 1), so.size() * sizeof(int), hipMemcpyDeviceToHost));
   const int U = so[JS];
   *n_units = U;
   *js = JS;
   if (soff) memcpy(soff, so.data(), so.size() * sizeof(int));
   std::vector<int> uo((size_t)U + 1);
-  HIP_TRY(hipMemcpy(uo.data(), reinterpret_cast<int *>(c->pk_uoff) + (size_t)tile * (um + 1), uo.size() * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(uo.data(), reinterpret_cast<int *>(c->pk.uoff) + (size_t)tile * (um + 1), uo.size() * sizeof(int), hipMemcpyDeviceToHost));
   if (uoff) memcpy(uoff, uo.data(), uo.size() * sizeof(int));
-  if (kidx && uo[U] > 0) HIP_TRY(hipMemcpy(kidx, reinterpret_cast<int *>(c->pk_idx) + (size_t)tile * um * 64, (size_t)uo[U] * sizeof(int), hipMemcpyDeviceToHost));
-  if (uq && U > 0) HIP_TRY(hipMemcpy(uq, reinterpret_cast<unsigned int *>(c->pk_uq) + (size_t)tile * um * 4, (size_t)U * 4 * sizeof(unsigned int), hipMemcpyDeviceToHost));
+  if (kidx && uo[U] > 0) HIP_TRY(hipMemcpy(kidx, reinterpret_cast<int *>(c->pk.idx) + (size_t)tile * um * 64, (size_t)uo[U] * sizeof(int), hipMemcpyDeviceToHost));
+  if (uq && U > 0) HIP_TRY(hipMemcpy(uq, reinterpret_cast<unsigned int *>(c->pk.uq) + (size_t)tile * um * 4, (size_t)U * 4 * sizeof(unsigned int), hipMemcpyDeviceToHost));
   return DUST_OK;
 }
 
@@ -5864,7 +5705,7 @@ static int svb_go(dust_svmpc_batch *b, const float *states, int n_steps, const f
     if (d < c->da) logdet += log((double)c->cfg.sigma_p[d]);
   }
   k.log_norm = (float)(-c->H * logdet - 0.5 * c->D * log(2.0 * M_PI));  // (prior_merge_args' constant)
-  const float ell = c->cfg.kernel == DUST_KERNEL_IMQ ? c->cfg.imq_ell : 0.69314718055994531f;  // softplus(0) = ln 2 (update_args)
+  const float ell = stein_ell(c);
   k.inv_ell = 1.0f / ell;
   k.inv_l2 = 1.0f / (ell * ell);
   k.inv_n = 1.0f / c->N;
@@ -5905,9 +5746,7 @@ static int svb_go(dust_svmpc_batch *b, const float *states, int n_steps, const f
   {
     Prof pr(c, DUST_K_SVMPC_BATCH);
     auto go = [&](auto kernel, const auto &args) -> int {
-      if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      kernel<<<b->B, SVB_THREADS, lds, c->stream>>>(args);
-      HIP_TRY(hipGetLastError());
+      HIP_TRY(launch_on(c->stream, false, kernel, b->B, SVB_THREADS, lds, args));  // (the batches are never captured)
       return DUST_OK;
     };
     if (episode) {

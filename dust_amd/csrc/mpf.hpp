@@ -1579,8 +1579,7 @@ static MpfWg mpf_wg(const dust_mpf *m) {
 }
 template <class K, class Args>
 static int mpf_wg_launch(K kernel, int blocks, const MpfWg &wg, hipStream_t stream, const Args &a) {
-  if (wg.lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg.lds));
-  kernel<<<blocks, wg.threads, wg.lds, stream>>>(a);
+  HIP_TRY(launch_on(stream, false, kernel, blocks, wg.threads, wg.lds, a));  // (the filters are never captured)
   return DUST_OK;
 }
 

@@ -5,29 +5,28 @@
 
 namespace dust {
 
-template <int MODEL, int MODE>
-static int occ_of(size_t lds, int *occ) {
+// the kernel's instance for a model (Pendulum, else Particle) and a pairwise mode (IMQ, else K1)
+static auto tick2_instance(int model, int mode) {
+  if (model == DUST_MODEL_PENDULUM) return mode == PAIR_IMQ ? svmpc_tick2_kernel<DUST_MODEL_PENDULUM, PAIR_IMQ> : svmpc_tick2_kernel<DUST_MODEL_PENDULUM, PAIR_K1>;
+  return mode == PAIR_IMQ ? svmpc_tick2_kernel<DUST_MODEL_PARTICLE, PAIR_IMQ> : svmpc_tick2_kernel<DUST_MODEL_PARTICLE, PAIR_K1>;
+}
+
+// (the attribute is set here, before the first launch: the occupancy query needs it, and launch_tick2 asks once per LDS size)
+static int occ_of(const void *kernel, size_t lds, int *occ) {
   hipError_t e = hipSuccess;
-  if (lds > 64 * 1024)
-    e = hipFuncSetAttribute((const void *)svmpc_tick2_kernel<MODEL, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, (const void *)svmpc_tick2_kernel<MODEL, MODE>, T2_NT, lds);
+  if (lds > 64 * 1024) e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, kernel, T2_NT, lds);
   return (int)e;
 }
 
 int tick2_occupancy(int model, int mode, size_t lds, int *occ) {
   *occ = 0;
-  if (model == DUST_MODEL_PENDULUM) return mode == PAIR_IMQ ? occ_of<DUST_MODEL_PENDULUM, PAIR_IMQ>(lds, occ) : occ_of<DUST_MODEL_PENDULUM, PAIR_K1>(lds, occ);
-  return mode == PAIR_IMQ ? occ_of<DUST_MODEL_PARTICLE, PAIR_IMQ>(lds, occ) : occ_of<DUST_MODEL_PARTICLE, PAIR_K1>(lds, occ);
+  return occ_of((const void *)tick2_instance(model, mode), lds, occ);
 }
 
 int tick2_launch(const Tick2Args &f, int model, int mode, int grid, size_t lds, hipStream_t stream) {
-  if (model == DUST_MODEL_PENDULUM) {
-    if (mode == PAIR_IMQ) svmpc_tick2_kernel<DUST_MODEL_PENDULUM, PAIR_IMQ><<<grid, T2_NT, lds, stream>>>(f);
-    else svmpc_tick2_kernel<DUST_MODEL_PENDULUM, PAIR_K1><<<grid, T2_NT, lds, stream>>>(f);
-  } else {
-    if (mode == PAIR_IMQ) svmpc_tick2_kernel<DUST_MODEL_PARTICLE, PAIR_IMQ><<<grid, T2_NT, lds, stream>>>(f);
-    else svmpc_tick2_kernel<DUST_MODEL_PARTICLE, PAIR_K1><<<grid, T2_NT, lds, stream>>>(f);
-  }
+  const auto kernel = tick2_instance(model, mode);
+  kernel<<<grid, T2_NT, lds, stream>>>(f);
   return (int)hipGetLastError();
 }
 
