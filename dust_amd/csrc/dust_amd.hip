@@ -2860,8 +2860,9 @@ static bool logp_far_decide(dust_ctx *c) {
   if (logp_pack_ok(c)) return true;  // (run lists: the pre-pass always pays there)
   if (c->env.far >= 2 || !c->far_cnt_host) return true;
   if (c->far_logp_skip > 0) {
-    --c->far_logp_skip;
-    return false;
+    // the pass that set the count was the first of the 15 without a pre-pass; the one that brings it to 0 is the probe.  (Falling
+    // through to the report here would read the report that set the count again - no pre-pass has run since - and never probe.)
+    return --c->far_logp_skip == 0;
   }
   volatile unsigned int *hc = c->far_cnt_host + 4;
   if (c->far_logp_issued == 0u) return true;

@@ -25,6 +25,21 @@ def elemerr(a, b, floor=None):
     return float((np.abs(a - b) / (np.abs(b) + floor + 1e-300)).max())
 
 
+def far_logp(ctx):
+    """(far, all) (64-query group, key chunk) blocks of the context's last log-p pass (dust_debug_far_logp: not part of the C ABI);
+    (0, 0) when that pass ran without the far pre-pass."""
+    import ctypes as C
+
+    from dust_amd import _lib as L
+
+    lib = L.load()
+    lib.dust_debug_far_logp.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+    lib.dust_debug_far_logp.restype = C.c_int
+    out = (C.c_longlong * 2)()
+    assert lib.dust_debug_far_logp(ctx._h, out) == 0
+    return int(out[0]), int(out[1])
+
+
 def k2_tolerance(theta, h, shared, da):
     """K2's reference side (dust/kernels/base_kernels.py:53-89) forms (x_i - x_j)^2 as -2XY + XX + YY in fp32: cancellation noise
     ~ 4 eps x^2 on every pair distance, i.e. that much over h RELATIVE noise on the kernel values.  The oracle follows the

@@ -10,6 +10,7 @@ import pytest
 import os
 
 from helpers import feed_ctrl_noise, tick2_ticks_expected, elemerr, is_adam, k2_tolerance, relerr, scenario_kwargs
+from helpers import far_logp as _far_logp
 from test_oracle_golden import K1_F64_CASES, SVMPC_CASES, _prior_at, k1_tolerance
 
 pytestmark = pytest.mark.gpu
@@ -1426,19 +1427,6 @@ def test_fused_pairwise_zero_blocks_bitwise(model, N, H, kind, monkeypatch):
         assert np.array_equal(x, y)
     nzfrac = float((np.abs(got[""][0]) > 0).mean())
     assert nzfrac > 0.5  # (phi itself is dense: K_ii = 1 carries the score)
-
-
-def _far_logp(ctx):
-    import ctypes as C
-
-    from dust_amd import _lib as L
-
-    lib = L.load()
-    lib.dust_debug_far_logp.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
-    lib.dust_debug_far_logp.restype = C.c_int
-    out = (C.c_longlong * 2)()
-    assert lib.dust_debug_far_logp(ctx._h, out) == 0
-    return int(out[0]), int(out[1])
 
 
 def _pack_lists(ctx, tile):
