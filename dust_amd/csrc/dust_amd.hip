@@ -26,6 +26,7 @@
 
 #include "bandwidth.hpp"
 #include "common.hpp"
+#include "devbuf.hpp"
 #include "forward.hpp"
 #include "fused.hpp"
 #include "pairwise_big.hpp"
@@ -96,10 +97,10 @@ struct PeerState {
   unsigned int seq[PEER_BUFS];
 };
 
-// the five buffers of one set of run lists (pairwise_packed.hpp far_pack_kernel), with their capacities in floats
+// the five buffers of one set of run lists (pairwise_packed.hpp far_pack_kernel)
 struct RunLists {
-  float *idx, *uoff, *uq, *soff, *goff;
-  size_t idx_cap, uoff_cap, uq_cap, soff_cap, goff_cap;
+  DevBuf<int> idx, uoff, soff, goff;
+  DevBuf<unsigned int> uq;
 };
 
 struct dust_ctx {
@@ -112,30 +113,26 @@ struct dust_ctx {
   hipEvent_t ev_order;   // behind the side stream's query_order_kernel (pairwise_packed.hpp); order_pending: nobody has waited for it yet
   bool order_pending;
   // particles / prior / controller state
-  float *theta, *thetaT, *mu, *muT, *logmix, *mixw;
-  float *thetaT_alt;     // K2: the transposed particles of the next iteration, written by the phi + update launch (ping-pong with thetaT)
+  DevBuf<float> theta, thetaT, mu, muT, logmix, mixw;  // (sizes of every owner: elements of its type - DESIGN.md section 3)
+  DevBuf<float> thetaT_alt;     // K2: the transposed particles of the next iteration, written by the phi + update launch (ping-pong with thetaT)
   bool k2_thetaT_fresh;  // thetaT is the transpose of theta as the last K2 update left it (valid from one iteration to the next of ONE loop only)
   bool mu_aliased;  // reference quirk: after update_prior the GMM means alias theta's storage (svgd.py:87, svmpc.py:160-170)
-  float *a_mat, *a_seq, *a_mix, *eta;
+  DevBuf<float> a_mat, a_seq, a_mix, eta;
   // per-iteration products
-  float *costsT, *omegaT, *grad_lik, *grad_pri, *score, *phi, *logl, *logp, *lw, *pw, *a_seq_out, *bw;
-  int *istar;
+  DevBuf<float> costsT, omegaT, grad_lik, grad_pri, score, phi, logl, logp, lw, bw;
+  float *pw, *a_seq_out;  // not owned: views into outblk
+  DevBuf<int> istar;
   dust_optim_config opt;             // the optimiser (dust_config's plain SGD / Adam until dust_set_optimizer)
-  float *opt_s0, *opt_s1, *opt_s2;   // its state slots [N][D] (handoff.hpp opt_step) or nullptr
-  float *pA, *pB, *pM, *pL;  // slice partials of the tiled pairwise passes
-  size_t pA_cap, pB_cap, pM_cap, pL_cap;
-  float *pS;                 // Gram x score partials of the one-launch iteration (pA still holds the prior's while its Stein tiles run)
-  size_t pS_cap;
-  float *mw_dev;             // [M] unscented-transform weights of the dynamics samples (nullptr: mean)
+  DevBuf<float> opt_s[3];            // its state slots [N][D] (handoff.hpp opt_step) or empty
+  DevBuf<float> pA, pB, pM, pL;  // slice partials of the tiled pairwise passes
+  DevBuf<float> pS;              // Gram x score partials of the one-launch iteration (pA still holds the prior's while its Stein tiles run)
+  DevBuf<float> mw_dev;             // [M] unscented-transform weights of the dynamics samples (nullptr: mean)
   float sigma_scale;         // lambda + n of the transform whose weights mw_dev holds (dust_set_sigma_scale; 0: not given)
-  float *theta_w, *mu_w;     // full prior covariance: whitened copies L_p^-1 x of the particles / prior means, refreshed before each prior pass
-  float *cz_dev;             // recorded control-noise draws [cz_sets][H][M*S*N][da] (dust_set_ctrl_noise), consumed one set per rollout launch
-  size_t cz_cap;
+  DevBuf<float> theta_w, mu_w;  // full prior covariance: whitened copies L_p^-1 x of the particles / prior means, refreshed before each prior pass
+  DevBuf<float> cz_dev;      // recorded control-noise draws [cz_sets][H][M*S*N][da] (dust_set_ctrl_noise), consumed one set per rollout launch
   int cz_sets, cz_next;
-  float *xpad;               // [N][DPB] zero-padded query rows of the large-N pairwise kernel
-  size_t xpad_cap;
-  float *kmat;               // [n_local][ldK] Stein kernel values of the current theta (pairwise_fused.hpp), valid while kmat_valid
-  size_t kmat_cap;
+  DevBuf<float> xpad;        // [N][DPB] zero-padded query rows of the large-N pairwise kernel; the log-p passes add a [2N] tail of floats behind them (logp_mfma_args)
+  DevBuf<float> kmat;        // [n_local][ldK] Stein kernel values of the current theta (pairwise_fused.hpp), valid while kmat_valid
   bool kmat_valid;
   bool t2_mu_aliased;        // the prior means aliased the particles BEFORE the last one-launch tick (its replay starts from that state)
   bool handoff_banned;       // an in-launch wait timed out once (the device is shared with another process): plain kernels from then on
@@ -147,67 +144,67 @@ struct dust_ctx {
   // pairwise_packed.hpp: the near-key lists of the last large-set pass 1 - key indices [tiles][chunks * 64], unit offsets
   // [tiles][chunks + 1], unit query masks [tiles][chunks][4], slice boundaries of pass 1 / pass 2, non-zero flags of the units' kernel blocks
   RunLists pk;
-  float *pk_nzu, *pk_perm, *pk_lead;
-  size_t pk_nzu_cap, pk_perm_cap, pk_lead_cap;
+  DevBuf<unsigned char> pk_nzu;
+  DevBuf<int> pk_perm, pk_lead;
   RunLists lp;  // the log-p pass' own run lists (64-query groups of the UPDATED particles)
   bool params_staged;             // inside dust_dual_tick: the tick's dynamics samples already sit in params_dev (drawn there by the filter's kernel)
   bool stagewise;                 // inside dust_svmpc_phi (a stage-wise call on caller-supplied inputs): index order - the same inputs give the same bits, call after call
   bool pk_order;                  // pass 1 walks its queries in tile order (pk_perm) and notes their leaders (pk_lead) for the next order
   int pk_tiles, pk_umax, pk_jsg;  // geometry of those lists
   bool pk_masks, pk_dense;        // the units carry query masks / pass 2 visits every unit (DUST_DENSE)
-  float *far_z, *far_n, *far_f;  // pairwise_far.hpp: binary16 rows, (norms, log weights), unit flags [tiles][chunks] bytes
-  size_t far_z_cap, far_n_cap, far_f_cap;
+  DevBuf<_Float16> far_z;       // pairwise_far.hpp: binary16 rows
+  DevBuf<float> far_n;          // ... norms [N] | log weights [2N + chunks]: one block, the kernels take the second part as far_n + N
+  DevBuf<unsigned char> far_f;  // ... unit flags [tiles][chunks]
   int far_tiles, far_chunks;  // geometry of the flags the last fused pass used (0: none)
-  float *far_q;               // per-unit near-query masks of the fused pass [tiles][chunks][4] words
-  size_t far_q_cap;
-  size_t far_cnt_cap;
-  float *far_cnt;             // [4] device counters {far, all} of the fused pass' and the log-p pass' last pre-pass
-  unsigned int *far_cnt_host; // pinned copy (arrives a tick late at worst: it only steers whether the NEXT pre-pass is worth its launches)
+  DevBuf<unsigned int> far_q;    // per-unit near-query masks of the fused pass [tiles][chunks][4] words
+  DevBuf<unsigned int> far_cnt;  // [4] device counters {far, all} of the fused pass' and the log-p pass' last pre-pass
+  PinBuf<unsigned int> far_cnt_host; // pinned copy (arrives a tick late at worst: it only steers whether the NEXT pre-pass is worth its launches)
   int far_logp_skip;          // log-p pre-pass: launches left to skip before the next probe
   unsigned int far_logp_issued;  // counted log-p pre-passes issued so far (the report the next decision reads carries this number)
-  float *far_g;               // the flags of the last log-p pass [groups][chunks] bytes
-  size_t far_g_cap;
+  DevBuf<unsigned char> far_g;  // the flags of the last log-p pass [groups][chunks]
   int far_groups, far_gchunks;
   int fused_js;  // slices of the repulsion partials of the last pairwise_packed_kernel launch (update_kernel merges them)
   int prior_js;  // slices of the prior partials when pairwise_packed_kernel wrote them (its own split); 0 = pair_geometry's
   // staging
-  float *noise_stage, *actions, *states, *params_dev, *state_dev, *tmp, *costs_stage, *tile_scratch;
-  size_t noise_cap, actions_cap, states_cap, params_cap, tmp_cap, tile_cap;
-  float *wg_flags;  // one word per workgroup of the whole-line stored-states kernel: "take the general path" (rollout_states.hpp)
-  size_t wg_flags_cap;
-  uint32_t *grid_bits;
+  DevBuf<float> noise_stage, params_dev, state_dev, costs_stage, tile_scratch;
+  DevBuf<float> actions, states;  // float or binary16 values (actions_f16 / states_f16): sized in floats, the rollout kernels take either through one pointer
+  DevBuf<float> tmp;              // scratch; dust_get_states_rows lays 64-bit row indices in front of its output rows (rows_idx_view)
+  size_t params_off;              // the set of dynamics samples inside params_dev that the launches read: params_cur (ParamSet moves it)
+  DevBuf<unsigned int> wg_flags;  // one word per workgroup of the whole-line stored-states kernel: "take the general path" (rollout_states.hpp)
+  DevBuf<uint32_t> grid_bits;
   int nx, ny;
   float off_x, off_y;
-  uint32_t *ctr_dev;  // device counters {tick, iter, adam_step, pad}
-  unsigned int *fused_cnt;  // [tiles + 1]: per-tile arrival counters of the fused launch, last word = spin-timeout flag
+  DevBuf<uint32_t> ctr_dev;  // device counters {tick, iter, adam_step, pad}
+  DevBuf<unsigned int> fused_cnt;  // [tiles + 1]: per-tile arrival counters of the fused launch, last word = spin-timeout flag
   int fused_tiles;
   bool fused_dirty;   // a fused launch ran and no update kernel has re-armed the counters yet
-  float *theta_home, *theta_alt;  // theta ping-pong of the fused Stein+update launch (theta == one of the two)
+  DevBuf<float> theta_alt;        // theta ping-pong of the fused Stein+update launch: the two owners swap
+  float *theta_home;              // not owned: the block theta held when the context was created (the ping-pong's parity)
   bool theta_pinned;              // dust_gather_buffers handed theta's address out: no ping-pong any more
-  const float *graph_theta;       // theta at the start of the captured tick
+  const float *graph_theta;       // not owned: theta at the start of the captured tick
   hipEvent_t ev_dual;          // dust_amppi_dual_tick without output copies: behind the kernels that read the filter's particles (created on first use)
-  unsigned int *amppi_ticket;  // dust_amppi_update: the arrival word of its workgroups (zeroed by a memset node ahead of every launch)
-  unsigned int *stein_cnt;  // [tiles + 1]: arrival counters of the Stein+update launch (re-armed by the next rollout launch)
+  DevBuf<unsigned int> amppi_ticket;  // dust_amppi_update: the arrival word of its workgroups (zeroed by a memset node ahead of every launch)
+  DevBuf<unsigned int> stein_cnt;  // [tiles + 1]: arrival counters of the Stein+update launch (re-armed by the next rollout launch)
   int stein_tiles;
   bool stein_dirty;
   // one-launch SVGD iteration (fused.hpp svgd_iter_kernel): two sets of [tiles | JS | tiles] counter lines, then the time-out flag
-  unsigned int *iter_cnt;
+  DevBuf<unsigned int> iter_cnt;
   int iter_tiles, iter_set;
-  float *score_hs;  // [2][N][D] score rows handed over as data inside the one-launch iteration (sentinel-filled between uses)
+  DevBuf<float> score_hs;  // [2][N][D] score rows handed over as data inside the one-launch iteration (sentinel-filled between uses: score_hs_words)
   // C-side RCCL communicator of a sharded context (dust_comm_init): the sharded tick issues its all-gathers on the context's stream
   void *comm;  // ncclComm_t
   int comm_rank, comm_world;
   struct PeerState *peer;  // direct peer-store all-gathers (peer_gather.hpp), or nullptr: the collective library's
   // tick outputs: a_seq_out | p_weights | time-out word of the persistent tick live in ONE device block, copied with ONE
   // hipMemcpyAsync into a pinned host buffer (then one stream synchronisation per tick that returns outputs)
-  float *outblk;
+  DevBuf<float> outblk;  // a_seq | pw | status words (unsigned): out_status
   size_t out_floats;   // a_seq (D rounded up to 32) + N + 32
-  float *out_pinned;   // host, pinned: out_floats + 4 words for the hand-off flags of the launch-per-iteration paths
+  PinBuf<float> out_pinned;   // host, pinned: out_floats + 4 words for the hand-off flags of the launch-per-iteration paths (unsigned: out_pinned_words)
   int tick_occ;       // resident workgroups per CU of the instantiation in use (0: not queried yet)
   size_t tick_occ_lds;
   // owner-computes persistent tick (tick2.hpp): exchange buffers, two counter sets, bookkeeping of ticks that did not start
-  float *t2_xq, *t2_sq, *t2_lwq;
-  unsigned int *t2_cnt;
+  DevBuf<float> t2_xq, t2_sq, t2_lwq;
+  DevBuf<unsigned int> t2_cnt;
   int t2_set, t2_occ, t2_gens;
   size_t t2_occ_lds;
   unsigned int t2_aborts_seen;  // value of the device-side "did not start" counter already accounted for
@@ -241,13 +238,13 @@ struct dust_ctx {
     bool cancelled;             // an armed launch the host cancelled (or whose state never came): nobody asked for this tick - dropped, not replayed
     std::vector<float> params;  // host copy of the caller's [steps][M][P] dynamics samples (empty: none)
   };
-  std::vector<T2Replay> *t2_queue;  // (a pointer: the context block is zero-filled as a whole when it is created)
+  std::vector<T2Replay> t2_queue;
   // closed-loop serving (dust_svmpc_serve_start; tick2_args.hpp): outputs straight to pinned host memory + a done word the host spins on,
   // and the NEXT tick launched ahead of its plant state ("armed": its rollout waves wait for the state in a pinned mailbox)
   bool serve_on;
   int serve_steps;
   unsigned long long serve_wait_ticks;  // bound of an armed launch's wait for its state (100 MHz ticks)
-  float *serve_host;                    // pinned: [out_floats] output mirror | [32 words] done | [32 words] T2Mbox
+  PinBuf<float> serve_host;             // pinned: [out_floats] output mirror | [32 words] done | [32 words] T2Mbox
   unsigned int serve_seq;               // sequence number of the last launch that reports to the done word
   bool serve_pw;                        // the served calls ask for the particle weights as well (decided by the first served call)
   int t2_launch_mode;                   // what the next launch_tick2 call adds: 0 nothing, 1 outputs + done word in pinned memory, 2 the same, armed
@@ -280,14 +277,24 @@ struct dust_ctx {
   bool noise_f16;     // the eps / actions handed to the current call are binary16 (DUST_EPS_F16), set by the API entry points
   bool actions_f16;   // the kept actions were stored as binary16
   int graph_flags;
-  unsigned long long *stamps_dev;  // diagnostic build only: [DUST_K_COUNT][16]
-  unsigned long long *tl_dev;      // diagnostic build only: [8192][4] launch timeline of svgd_iter_kernel
+  DevBuf<unsigned long long> stamps_dev;  // diagnostic build only: [DUST_K_COUNT][16]
+  DevBuf<unsigned long long> tl_dev;      // diagnostic build only: [8192][4] launch timeline of svgd_iter_kernel
   // profiling
   bool prof;
   hipEvent_t ev0, ev1;
   double prof_ms[DUST_K_ALL];
   int64_t prof_n[DUST_K_ALL];
 };
+
+// the current set of dynamics samples (not owned: a view into params_dev), or nullptr
+static float *params_cur(const dust_ctx *c) { return c->params_dev ? c->params_dev + c->params_off : nullptr; }
+// dust_get_states_rows: 64-bit row indices at the front of tmp
+static long long *rows_idx_view(const dust_ctx *c) { return reinterpret_cast<long long *>(c->tmp.get()); }  // (hipMalloc'd: 256-byte aligned)
+// the status words behind a_seq | pw in outblk: {time-out flag, aborts, commits, ..} of the persistent ticks
+static unsigned int *out_status(const dust_ctx *c) { return reinterpret_cast<unsigned int *>(c->outblk + (c->out_floats - 32)); }
+// ... the host's copy of them (at = out_floats - 32) and the 4 hand-off flag words behind it (at = out_floats); score_hs' half `set` as the bit patterns of its sentinel
+static unsigned int *out_pinned_words(const dust_ctx *c, size_t at) { return reinterpret_cast<unsigned int *>(c->out_pinned + at); }
+static unsigned int *score_hs_words(const dust_ctx *c, int set) { return reinterpret_cast<unsigned int *>(c->score_hs + (size_t)set * c->N * c->D); }
 
 static DevParam dev_param(const dust_param &p) { return DevParam{p.kind, p.column, p.value}; }
 
@@ -313,12 +320,17 @@ static int cartpole_params(const dust_cartpole_config *g, int P, DevParam par[CP
   return DUST_OK;
 }
 
-static DevModel make_dev_model(const dust_ctx *c) {
-  const dust_config &g = c->cfg;
+// the occupancy bits a model reads and their frame (not owned: a view of the context's or the filter's map)
+struct MapView {
+  uint32_t *grid_bits;
+  int nx, ny;
+  float off_x, off_y;
+};
+static DevModel make_dev_model(const dust_config &g, int P, const MapView &map) {
   DevModel m;
   memset(&m, 0, sizeof m);
   m.model = g.model;
-  m.P = c->P;
+  m.P = P;
   m.log_space = g.params_log_space;
   m.interleave = g.params_interleave;
   m.dt = g.dt;
@@ -332,13 +344,13 @@ static DevModel make_dev_model(const dust_ctx *c) {
   m.max_speed = g.max_speed;
   m.max_acc = g.max_accel;
   m.can_crash = g.can_crash;
-  m.with_obstacle = g.with_obstacle && c->grid_bits != nullptr;
+  m.with_obstacle = g.with_obstacle && map.grid_bits != nullptr;
   m.inv_cell = (float)(1.0 / g.cell_size);
-  m.off_x = c->off_x;
-  m.off_y = c->off_y;
-  m.nx = c->nx;
-  m.ny = c->ny;
-  m.grid_bits = c->grid_bits;
+  m.off_x = map.off_x;
+  m.off_y = map.off_y;
+  m.nx = map.nx;
+  m.ny = map.ny;
+  m.grid_bits = map.grid_bits;
   for (int k = 0; k < 4; ++k) {
     m.target[k] = g.target[k];
     m.w_state[k] = g.w_state[k];
@@ -349,6 +361,7 @@ static DevModel make_dev_model(const dust_ctx *c) {
   m.w_obs = g.w_obs;
   return m;
 }
+static DevModel make_dev_model(const dust_ctx *c) { return make_dev_model(c->cfg, c->P, MapView{c->grid_bits, c->nx, c->ny, c->off_x, c->off_y}); }
 
 // Host evaluation of the model coefficients when no parameter is sampled (same Python-float / fp32-tensor rules as the
 // device make_coef in common.hpp; pendulum.py:93-96, particle.py:152).
@@ -385,13 +398,17 @@ static int dalloc(T **p, size_t n) {
   HIP_TRY(hipMalloc((void **)p, n * sizeof(T)));
   return DUST_OK;
 }
-static int ensure(float **p, size_t *cap, size_t n) {
-  if (*cap >= n) return DUST_OK;
-  if (*p) HIP_TRY(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  TRY(dalloc(p, n));
-  *cap = n;
+namespace dust {  // the allocator seam of devbuf.hpp: every block the handle types own comes and goes through these four
+int devbuf_dev_alloc(void **p, size_t bytes) { HIP_TRY(hipMalloc(p, bytes)); return DUST_OK; }
+int devbuf_dev_free(void *p) { HIP_TRY(hipFree(p)); return DUST_OK; }
+int devbuf_pin_alloc(void **p, size_t bytes, unsigned flags) { HIP_TRY(hipHostMalloc(p, bytes, flags)); return DUST_OK; }
+int devbuf_pin_free(void *p) { HIP_TRY(hipHostFree(p)); return DUST_OK; }
+}  // namespace dust
+// Test hook (not in include/dust_amd.h): blocks and bytes the owners hold, process-wide
+extern "C" int dust_debug_live_allocs(long long out[2]) {
+  if (!out) return fail(DUST_ERR_INVALID, "null argument");
+  out[0] = g_live_allocs.load();
+  out[1] = g_live_bytes.load();
   return DUST_OK;
 }
 
@@ -439,24 +456,23 @@ static unsigned optim_slots(const dust_optim_config &o) {
   }
 }
 // (re)allocates exactly the slots `o` uses (n floats each; an unused slot is null, which the kernels read as "not in use")
-static int optim_slots_alloc(const dust_optim_config &o, float *s[3], size_t n) {
+static int optim_slots_alloc(const dust_optim_config &o, DevBuf<float> s[3], size_t n) {
   const unsigned m = optim_slots(o);
   for (int k = 0; k < 3; ++k) {
     if ((m >> k) & 1u) {
-      if (!s[k]) TRY(dalloc(&s[k], n));
-    } else if (s[k]) {
-      HIP_TRY(hipFree(s[k]));
-      s[k] = nullptr;
+      if (!s[k]) TRY(s[k].alloc(n));
+    } else {
+      TRY(s[k].reset());
     }
   }
   return DUST_OK;
 }
 // the state a fresh torch optimiser starts with: slot 0 at opt_restart_s0 (Adagrad's initial_accumulator_value), the others at zero
-static int optim_restart(const dust_optim_config &o, float *const s[3], size_t n, hipStream_t st) {
+static int optim_restart(const dust_optim_config &o, const DevBuf<float> s[3], size_t n, hipStream_t st) {
   const float v0 = opt_restart_s0(o);
   uint32_t bits;
   memcpy(&bits, &v0, 4);
-  if (s[0]) HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s[0]), (int)bits, n, st));
+  if (s[0]) HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s[0].get()), (int)bits, n, st));
   for (int k = 1; k < 3; ++k)
     if (s[k]) HIP_TRY(hipMemsetAsync(s[k], 0, n * sizeof(float), st));
   return DUST_OK;
@@ -527,32 +543,12 @@ static int validate(const dust_config *g) {
   return DUST_OK;
 }
 
+// what a context holds besides memory (the DevBuf / PinBuf members free themselves when the context is deleted, after this)
 static void free_all(dust_ctx *c) {
-  // {theta, theta_alt} are always the two particle buffers, whichever is current
-  float **fp[] = {&c->theta, &c->theta_alt, &c->thetaT, &c->thetaT_alt, &c->mu, &c->muT, &c->logmix, &c->mixw, &c->a_mat, &c->a_seq, &c->a_mix, &c->eta,
-                  &c->costsT, &c->omegaT, &c->grad_lik, &c->grad_pri, &c->score, &c->phi, &c->logl, &c->logp, &c->lw,
-                  &c->outblk, &c->bw, &c->opt_s0, &c->opt_s1, &c->opt_s2, &c->noise_stage, &c->actions, &c->states, &c->params_dev,
-                  &c->state_dev, &c->tmp, &c->costs_stage, &c->tile_scratch, &c->wg_flags, &c->pA, &c->pB, &c->pM, &c->pL, &c->pS, &c->xpad, &c->kmat, &c->pk.idx, &c->pk.uoff, &c->pk.uq, &c->pk.soff, &c->pk.goff, &c->pk_nzu, &c->pk_perm, &c->pk_lead, &c->lp.idx, &c->lp.uoff, &c->lp.uq, &c->lp.soff, &c->lp.goff, &c->far_z, &c->far_n, &c->far_f, &c->far_g, &c->far_q, &c->far_cnt, &c->mw_dev, &c->cz_dev, &c->theta_w, &c->mu_w};
-  for (auto p : fp)
-    if (*p) (void)hipFree(*p);
   if (c->graph_exec) (void)hipGraphExecDestroy(c->graph_exec);
   if (c->graph) (void)hipGraphDestroy(c->graph);
   if (c->graph_exec_alt) (void)hipGraphExecDestroy(c->graph_exec_alt);
   if (c->graph_alt) (void)hipGraphDestroy(c->graph_alt);
-  if (c->ctr_dev) (void)hipFree(c->ctr_dev);
-  if (c->fused_cnt) (void)hipFree(c->fused_cnt);
-  if (c->stein_cnt) (void)hipFree(c->stein_cnt);
-  if (c->amppi_ticket) (void)hipFree(c->amppi_ticket);
-  if (c->iter_cnt) (void)hipFree(c->iter_cnt);
-  if (c->score_hs) (void)hipFree(c->score_hs);
-  if (c->t2_cnt) (void)hipFree(c->t2_cnt);
-  if (c->t2_xq) (void)hipFree(c->t2_xq);
-  if (c->t2_sq) (void)hipFree(c->t2_sq);
-  if (c->t2_lwq) (void)hipFree(c->t2_lwq);
-  if (c->out_pinned) (void)hipHostFree(c->out_pinned);
-  if (c->far_cnt_host) (void)hipHostFree(c->far_cnt_host);
-  if (c->istar) (void)hipFree(c->istar);
-  if (c->grid_bits) (void)hipFree(c->grid_bits);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->stream2) (void)hipStreamDestroy(c->stream2);
@@ -674,7 +670,7 @@ static void serve_cancel_locked(dust_ctx *c) {
   serve_post(c, c->armed_seq, 2u, nullptr);
   c->armed = false;
   c->cancel_unsettled = true;
-  if (!c->t2_queue->empty()) c->t2_queue->back().cancelled = true;
+  if (!c->t2_queue.empty()) c->t2_queue.back().cancelled = true;
   const int dev = c->cfg.device;
   if (dev >= 0 && dev < DUST_MAX_DEV && g_armed[dev] == c) g_armed[dev] = nullptr;
 }
@@ -708,8 +704,6 @@ extern "C" void dust_destroy(dust_ctx *c) {
   if (c->stream2) (void)hipStreamSynchronize(c->stream2);
   comm_release(c);
   free_all(c);
-  if (c->serve_host) (void)hipHostFree(c->serve_host);
-  delete c->t2_queue;
   delete c;
 }
 
@@ -747,13 +741,7 @@ static int create_impl(const dust_config *cfg, dust_ctx **out) {
   HIP_TRY(hipSetDevice(cfg->device));
   dust_ctx *c = new (std::nothrow) dust_ctx();
   if (!c) return fail(DUST_ERR_HIP, "out of host memory");
-  memset((void *)c, 0, sizeof *c);
   env_read(c);
-  c->t2_queue = new (std::nothrow) std::vector<dust_ctx::T2Replay>();
-  if (!c->t2_queue) {
-    delete c;
-    return fail(DUST_ERR_HIP, "out of host memory");
-  }
   c->cfg = *cfg;
   c->N = cfg->n_policies;
   c->S = cfg->n_samples;
@@ -791,50 +779,43 @@ static int create_impl(const dust_config *cfg, dust_ctx **out) {
   HIP_TRY(hipEventCreate(&c->ev0));
   HIP_TRY(hipEventCreate(&c->ev1));
   const size_t ND = (size_t)c->N * c->D, SN = (size_t)c->S * c->N;
-  float **nd[] = {&c->theta, &c->thetaT, &c->mu, &c->muT, &c->a_mat, &c->grad_lik, &c->grad_pri, &c->score, &c->phi};
+  DevBuf<float> *nd[] = {&c->theta, &c->thetaT, &c->mu, &c->muT, &c->a_mat, &c->grad_lik, &c->grad_pri, &c->score, &c->phi};
   for (auto p : nd) {
-    TRY(dalloc(p, ND));
-    HIP_TRY(hipMemsetAsync(*p, 0, ND * sizeof(float), c->stream));
+    TRY(p->alloc(ND));
+    HIP_TRY(hipMemsetAsync(p->get(), 0, ND * sizeof(float), c->stream));
   }
-  TRY(dalloc(&c->theta_alt, ND));
-  if (cfg->kernel == DUST_KERNEL_K2_IIDMP || cfg->kernel == DUST_KERNEL_K2_SHARED) TRY(dalloc(&c->thetaT_alt, ND));
+  TRY(c->theta_alt.alloc(ND));
+  if (cfg->kernel == DUST_KERNEL_K2_IIDMP || cfg->kernel == DUST_KERNEL_K2_SHARED) TRY(c->thetaT_alt.alloc(ND));
   c->theta_home = c->theta;
-  float **nn[] = {&c->logmix, &c->mixw, &c->a_mix, &c->eta, &c->logl, &c->logp, &c->lw};
+  DevBuf<float> *nn[] = {&c->logmix, &c->mixw, &c->a_mix, &c->eta, &c->logl, &c->logp, &c->lw};
   for (auto p : nn) {
-    TRY(dalloc(p, (size_t)c->N));
-    HIP_TRY(hipMemsetAsync(*p, 0, c->N * sizeof(float), c->stream));
+    TRY(p->alloc((size_t)c->N));
+    HIP_TRY(hipMemsetAsync(p->get(), 0, c->N * sizeof(float), c->stream));
   }
-  TRY(dalloc(&c->a_seq, (size_t)c->D));
+  TRY(c->a_seq.alloc((size_t)c->D));
   {
     const size_t dpad = ((size_t)c->D + 31) & ~(size_t)31;
     c->out_floats = dpad + (size_t)c->N + 32;
-    TRY(dalloc(&c->outblk, c->out_floats));
+    TRY(c->outblk.alloc(c->out_floats));
     HIP_TRY(hipMemsetAsync(c->outblk, 0, c->out_floats * sizeof(float), c->stream));
     c->a_seq_out = c->outblk;
     c->pw = c->outblk + dpad;
-    HIP_TRY(hipHostMalloc((void **)&c->out_pinned, (c->out_floats + 4) * sizeof(float), hipHostMallocDefault));
+    TRY(c->out_pinned.alloc(c->out_floats + 4, hipHostMallocDefault));
   }
-  TRY(dalloc(&c->bw, (size_t)c->D));
+  TRY(c->bw.alloc((size_t)c->D));
   HIP_TRY(hipMemsetAsync(c->bw, 0, c->D * sizeof(float), c->stream));  // (no previous bandwidth: the sorted kernels' warm start stands down)
   HIP_TRY(hipMemsetAsync(c->a_seq, 0, c->D * sizeof(float), c->stream));
-  TRY(dalloc(&c->costsT, SN));
-  TRY(dalloc(&c->omegaT, SN));
-  TRY(dalloc(&c->tmp, SN));
-  c->tmp_cap = SN;
-  TRY(dalloc(&c->costs_stage, SN));
-  TRY(dalloc(&c->state_dev, (size_t)8));
-  TRY(dalloc(&c->istar, (size_t)1));
-  TRY(dalloc(&c->ctr_dev, (size_t)4));
+  TRY(c->costsT.alloc(SN));
+  TRY(c->omegaT.alloc(SN));
+  TRY(c->tmp.alloc(SN));
+  TRY(c->costs_stage.alloc(SN));
+  TRY(c->state_dev.alloc((size_t)8));
+  TRY(c->istar.alloc((size_t)1));
+  TRY(c->ctr_dev.alloc((size_t)4));
   HIP_TRY(hipMemsetAsync(c->ctr_dev, 0, 4 * sizeof(uint32_t), c->stream));
   c->opt = optim_plain(cfg->optimizer, cfg->lr, cfg->adam_beta1, cfg->adam_beta2, cfg->adam_eps);
-  {
-    float *slots[3] = {nullptr, nullptr, nullptr};
-    TRY(optim_slots_alloc(c->opt, slots, ND));
-    c->opt_s0 = slots[0];
-    c->opt_s1 = slots[1];
-    c->opt_s2 = slots[2];
-    TRY(optim_restart(c->opt, slots, ND, c->stream));
-  }
+  TRY(optim_slots_alloc(c->opt, c->opt_s, ND));
+  TRY(optim_restart(c->opt, c->opt_s, ND, c->stream));
   // a_mix starts as ones (disco.py:110); uniform prior weights until set_prior
   std::vector<float> ones((size_t)c->N, 1.0f);
   HIP_TRY(hipMemcpyAsync(c->a_mix, ones.data(), c->N * sizeof(float), hipMemcpyHostToDevice, c->stream));
@@ -859,7 +840,7 @@ extern "C" int dust_create(const dust_config *cfg, dust_ctx **out) {
   if (s != DUST_OK && *out) {
     std::string keep = g_err;
     free_all(*out);
-    delete *out;
+    delete *out;  // (memory, pinned blocks and the replay queue go with the context)
     *out = nullptr;
     g_err = keep;
   }
@@ -885,9 +866,9 @@ static void handoff_ban(dust_ctx *c) {
 #define T2_TORN_MSG "persistent tick kernel: a hand-off wait timed out while some workgroups were committing (results of this tick are invalid: re-seed the particles); the device seems to be shared with another process: this context runs plain kernels from here on"
 static int t2_timed_out(dust_ctx *c, bool *whole) {
   unsigned int w[3] = {0u, 0u, 0u};
-  HIP_TRY(hipMemcpy(w, c->outblk + c->out_floats - 32, sizeof w, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(w, out_status(c), sizeof w, hipMemcpyDeviceToHost));
   const unsigned int zero[3] = {0u, w[1], 0u};
-  HIP_TRY(hipMemcpy(c->outblk + c->out_floats - 32, zero, sizeof zero, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(out_status(c), zero, sizeof zero, hipMemcpyHostToDevice));
   handoff_ban(c);
   *whole = c->t2_grid > 0 && (w[2] % (unsigned int)c->t2_grid) == 0u;
   return DUST_OK;
@@ -906,8 +887,8 @@ extern "C" int dust_sync(dust_ctx *c) {
   if (c->t2_inflight) {  // owner-computes ticks that did not start (device shared with another context) run now, on the other path
     // (the status words ride behind the launches into pinned memory: one stream synchronisation instead of a synchronisation and two
     //  blocking copies of a few bytes - 128 -> 110 us per tick for a caller that synchronises after every open-loop tick)
-    unsigned int *w = reinterpret_cast<unsigned int *>(c->out_pinned + c->out_floats);
-    HIP_TRY(hipMemcpyAsync(w, c->outblk + c->out_floats - 32, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+    unsigned int *w = out_pinned_words(c, c->out_floats);
+    HIP_TRY(hipMemcpyAsync(w, out_status(c), 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     have_flag = true;
     flag0 = w[0];
@@ -943,9 +924,9 @@ extern "C" int dust_sync(dust_ctx *c) {
   }
   if (c->t2_cnt) {
     unsigned int flag = flag0;
-    if (!have_flag) HIP_TRY(hipMemcpy(&flag, c->outblk + c->out_floats - 32, sizeof flag, hipMemcpyDeviceToHost));
+    if (!have_flag) HIP_TRY(hipMemcpy(&flag, out_status(c), sizeof flag, hipMemcpyDeviceToHost));
     if (flag) {
-      HIP_TRY(hipMemset(c->outblk + c->out_floats - 32, 0, sizeof flag));  // reported: clear
+      HIP_TRY(hipMemset(out_status(c), 0, sizeof flag));  // reported: clear
       return handoff_timeout(c, "persistent tick kernel: a hand-off wait timed out (results of that tick are invalid); the device seems to be shared with another process: this context runs plain kernels from here on");
     }
   }
@@ -994,11 +975,26 @@ static int d2h(dust_ctx *c, void *dst, const void *src, size_t bytes) {
   return DUST_OK;
 }
 
+static int clone_fill(const dust_ctx *src, dust_ctx *c);
 extern "C" int dust_clone(const dust_ctx *src, dust_ctx **out) {
   if (!src || !out) return fail(DUST_ERR_INVALID, "null argument");
+  *out = nullptr;
   TRY(settle_pending(const_cast<dust_ctx *>(src)));
-  TRY(dust_create(&src->cfg, out));
-  dust_ctx *c = *out;
+  dust_ctx *c = nullptr;
+  TRY(dust_create(&src->cfg, &c));
+  const int st = clone_fill(src, c);
+  if (st != DUST_OK) {  // nothing half-copied reaches the caller; the first error's message stays
+    const std::string keep = g_err;
+    dust_destroy(c);
+    g_err = keep;
+    return st;
+  }
+  *out = c;
+  return DUST_OK;
+}
+
+// the state a copy takes over from its source (c: fresh from dust_create with the source's configuration)
+static int clone_fill(const dust_ctx *src, dust_ctx *c) {
   HIP_TRY(hipStreamSynchronize(src->stream));
   const size_t ND = (size_t)c->N * c->D * sizeof(float), Nb = c->N * sizeof(float), SN = (size_t)c->S * c->N * sizeof(float);
   struct {
@@ -1011,12 +1007,8 @@ extern "C" int dust_clone(const dust_ctx *src, dust_ctx **out) {
             {c->logl, src->logl, Nb}, {c->a_seq, src->a_seq, c->D * sizeof(float)}, {c->costsT, src->costsT, SN}};
   for (auto &e : cp) TRY(d2d(c, e.dst, e.s, e.b));
   if (memcmp(&src->opt, &c->opt, sizeof c->opt) != 0) TRY(dust_set_optimizer(c, &src->opt));
-  {
-    float *const ds[3] = {c->opt_s0, c->opt_s1, c->opt_s2};
-    const float *const ss[3] = {src->opt_s0, src->opt_s1, src->opt_s2};
-    for (int k = 0; k < 3; ++k)
-      if (ss[k]) TRY(d2d(c, ds[k], ss[k], ND));
-  }
+  for (int k = 0; k < 3; ++k)
+    if (src->opt_s[k]) TRY(d2d(c, c->opt_s[k], src->opt_s[k], ND));
   TRY(d2d(c, c->ctr_dev, src->ctr_dev, 4 * sizeof(uint32_t)));
   c->mu_aliased = src->mu_aliased;
   c->have_sample = src->have_sample;
@@ -1027,31 +1019,31 @@ extern "C" int dust_clone(const dust_ctx *src, dust_ctx **out) {
   c->k2_min_bw = src->k2_min_bw;
   if (src->cz_dev && src->cz_sets > 0) {  // recorded control-noise draws not consumed yet (dust_set_ctrl_noise)
     const size_t n = (size_t)src->cz_sets * c->H * c->M * c->S * c->N * 2;
-    TRY(ensure(&c->cz_dev, &c->cz_cap, n));
+    TRY(c->cz_dev.ensure(n));
     TRY(d2d(c, c->cz_dev, src->cz_dev, n * sizeof(float)));
     c->cz_sets = src->cz_sets;
     c->cz_next = src->cz_next;
   }
   if (src->grid_bits) {
     const size_t words = ((size_t)src->nx * src->ny + 31) / 32;
-    TRY(dalloc(&c->grid_bits, words));
+    TRY(c->grid_bits.alloc(words));
     TRY(d2d(c, c->grid_bits, src->grid_bits, words * 4));
     c->nx = src->nx;
     c->ny = src->ny;
     c->off_x = src->off_x;
     c->off_y = src->off_y;
   }
-  if (src->pk_perm && src->pk_lead && src->pk_perm_cap >= (size_t)c->nloc && src->pk_lead_cap >= (size_t)c->nloc) {
+  if (src->pk_perm && src->pk_lead && src->pk_perm.cap() >= (size_t)c->nloc && src->pk_lead.cap() >= (size_t)c->nloc) {
     // the tile order of the large-set passes and the leaders noted for the next one (pairwise_packed.hpp): a copy continues with the
     // same run lists - the same grouping of every sum - as its source
     if (src->stream2) HIP_TRY(hipStreamSynchronize(src->stream2));  // (the side stream's query_order_kernel)
-    TRY(ensure(&c->pk_perm, &c->pk_perm_cap, (size_t)c->nloc));
-    TRY(ensure(&c->pk_lead, &c->pk_lead_cap, (size_t)c->nloc));
+    TRY(c->pk_perm.ensure((size_t)c->nloc));
+    TRY(c->pk_lead.ensure((size_t)c->nloc));
     TRY(d2d(c, c->pk_perm, src->pk_perm, (size_t)c->nloc * sizeof(int)));
     TRY(d2d(c, c->pk_lead, src->pk_lead, (size_t)c->nloc * sizeof(int)));
   }
   if (src->mw_dev) {
-    TRY(dalloc(&c->mw_dev, (size_t)c->M));
+    TRY(c->mw_dev.alloc((size_t)c->M));
     TRY(d2d(c, c->mw_dev, src->mw_dev, (size_t)c->M * sizeof(float)));
     c->sigma_scale = src->sigma_scale;
   }
@@ -1082,14 +1074,13 @@ extern "C" int dust_set_param_weights(dust_ctx *c, const float *w) {
   if (!w) {
     if (c->mw_dev) {
       HIP_TRY(hipStreamSynchronize(c->stream));
-      HIP_TRY(hipFree(c->mw_dev));
-      c->mw_dev = nullptr;
+      TRY(c->mw_dev.reset());
     }
     c->sigma_scale = 0.f;  // (the scale belongs to the transform the weights came from)
     return DUST_OK;
   }
   if (c->cfg.dim_p <= 0) return fail(DUST_ERR_STATE, "parameter weights need sampled parameters (dim_p > 0)");
-  if (!c->mw_dev) TRY(dalloc(&c->mw_dev, (size_t)c->M));
+  if (!c->mw_dev) TRY(c->mw_dev.alloc((size_t)c->M));
   return h2d(c, c->mw_dev, w, (size_t)c->M * sizeof(float));
 }
 
@@ -1111,7 +1102,7 @@ extern "C" int dust_set_ctrl_noise(dust_ctx *c, const float *z, int n_sets) {
   if (!z || n_sets <= 0) return DUST_OK;
   HIP_TRY(hipSetDevice(c->cfg.device));
   const size_t n = (size_t)n_sets * c->H * c->M * c->S * c->N * 2;
-  TRY(ensure(&c->cz_dev, &c->cz_cap, n));
+  TRY(c->cz_dev.ensure(n));
   TRY(h2d(c, c->cz_dev, z, n * sizeof(float)));
   c->cz_sets = n_sets;
   return DUST_OK;
@@ -1129,9 +1120,7 @@ extern "C" int dust_set_grid(dust_ctx *c, const float *grid, int nx, int ny, flo
     else if (grid[i] != 0.0f) return fail(DUST_ERR_UNSUPPORTED, "occupancy grid must be binary (ObstacleMap writes 0/1)");
   }
   HIP_TRY(hipSetDevice(c->cfg.device));
-  if (c->grid_bits) HIP_TRY(hipFree(c->grid_bits));
-  c->grid_bits = nullptr;
-  TRY(dalloc(&c->grid_bits, words));
+  TRY(c->grid_bits.alloc(words));
   TRY(h2d(c, c->grid_bits, bits.data(), words * 4));
   c->nx = nx;
   c->ny = ny;
@@ -1182,9 +1171,8 @@ extern "C" int dust_set_theta(dust_ctx *c, const float *theta) {
   HIP_TRY(hipSetDevice(c->cfg.device));
   TRY(h2d(c, c->theta, theta, (size_t)c->N * c->D * sizeof(float)));
   c->kmat_valid = false;
-  if (c->opt_s0 || c->opt_s1 || c->opt_s2) {  // (a new parameter tensor: the optimiser's state and step count restart)
-    float *const slots[3] = {c->opt_s0, c->opt_s1, c->opt_s2};
-    TRY(optim_restart(c->opt, slots, (size_t)c->N * c->D, c->stream));
+  if (c->opt_s[0] || c->opt_s[1] || c->opt_s[2]) {  // (a new parameter tensor: the optimiser's state and step count restart)
+    TRY(optim_restart(c->opt, c->opt_s, (size_t)c->N * c->D, c->stream));
     HIP_TRY(hipMemsetAsync(c->ctr_dev + 2, 0, sizeof(uint32_t), c->stream));
   }
   return DUST_OK;
@@ -1196,14 +1184,10 @@ extern "C" int dust_set_optimizer(dust_ctx *c, const dust_optim_config *opt) {
   HIP_TRY(hipSetDevice(c->cfg.device));
   TRY(settle_pending(c));
   const size_t ND = (size_t)c->N * c->D;
-  float *slots[3] = {c->opt_s0, c->opt_s1, c->opt_s2};
   HIP_TRY(hipStreamSynchronize(c->stream));  // (slots about to be freed may still be read by queued work)
-  TRY(optim_slots_alloc(*opt, slots, ND));
-  c->opt_s0 = slots[0];
-  c->opt_s1 = slots[1];
-  c->opt_s2 = slots[2];
+  TRY(optim_slots_alloc(*opt, c->opt_s, ND));
   c->opt = *opt;
-  TRY(optim_restart(c->opt, slots, ND, c->stream));
+  TRY(optim_restart(c->opt, c->opt_s, ND, c->stream));
   HIP_TRY(hipMemsetAsync(c->ctr_dev + 2, 0, sizeof(uint32_t), c->stream));
   if (c->graph_exec || c->graph_exec_alt) graph_drop(c);  // (captured launches carry the optimiser and its slots by value)
   c->persist_declined = 0;
@@ -1492,18 +1476,18 @@ static int amppi_update_impl(dust_ctx *c, const float *state, const float *actio
   TRY(amppi_params_mode(c, params != nullptr, flags, prior, &mode, &pts, &prows));
   TRY(settle_pending(c));
   HIP_TRY(hipSetDevice(c->cfg.device));
-  if (!c->amppi_ticket) TRY(dalloc(&c->amppi_ticket, (size_t)1));
-  TRY(ensure(&c->actions, &c->actions_cap, (size_t)S * D));
+  if (!c->amppi_ticket) TRY(c->amppi_ticket.alloc((size_t)1));
+  TRY(c->actions.ensure((size_t)S * D));
   if (actions) {
     if (flags & DUST_PTR_DEVICE) TRY(d2d(c, c->actions, actions, (size_t)S * D * sizeof(float)));
     else TRY(h2d(c, c->actions, actions, (size_t)S * D * sizeof(float)));
   }
   if (prows) {
-    TRY(ensure(&c->params_dev, &c->params_cap, prows * P));
+    TRY(c->params_dev.ensure(prows * P));
     if (!staged) TRY(h2d(c, c->params_dev, params, prows * P * sizeof(float)));
   }
   const bool want_states = (flags & DUST_STORE_STATES) != 0;
-  if (want_states) TRY(ensure(&c->states, &c->states_cap, (size_t)S * pts * (c->H + 1) * c->ds));
+  if (want_states) TRY(c->states.ensure((size_t)S * pts * (c->H + 1) * c->ds));
   AmppiArgs a;
   amppi_shared_args(c, a);
   a.pts = pts;
@@ -1512,7 +1496,7 @@ static int amppi_update_impl(dust_ctx *c, const float *state, const float *actio
   for (int k = 0; k < 8; ++k) a.state[k] = k < c->ds ? state[k] : 0.f;  // (a kernel ARGUMENT: no copy, no launch of its own)
   a.seed = c->cfg.seed;
   a.ctr = c->ctr_dev;
-  a.params = prows ? c->params_dev : nullptr;
+  a.params = prows ? params_cur(c) : nullptr;
   a.acts = c->actions;
   a.a_seq = c->a_seq;
   a.costs = c->costsT;  // ([N][S] with N = 1)
@@ -1552,23 +1536,21 @@ extern "C" int dust_amppi_roll(dust_ctx *c, int steps) {
 // Per-call inputs of a batch travel through pinned host memory - the call does not wait for its own copy.  Two slots, each with the event
 // behind its copy: a slot is written again only once that copy has run
 struct PinnedStage {
-  unsigned char *dev, *host[2];
-  hipEvent_t ev[2];
-  int slot;
+  DevBuf<unsigned char> dev;  // bytes: the batch's layout of floats and mask bytes is its owner's (BatchInputs, dust_mpf_batch)
+  PinBuf<unsigned char> host[2];
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  int slot = 0;
   int alloc(size_t bytes) {
-    TRY(dalloc(&dev, bytes));
+    TRY(dev.alloc(bytes));
     for (int k = 0; k < 2; ++k) {
-      HIP_TRY(hipHostMalloc((void **)&host[k], bytes, hipHostMallocDefault));
+      TRY(host[k].alloc(bytes, hipHostMallocDefault));
       HIP_TRY(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
     }
     return DUST_OK;
   }
-  void free() {
-    if (dev) (void)hipFree(dev);
-    for (int k = 0; k < 2; ++k) {
-      if (host[k]) (void)hipHostFree(host[k]);
+  ~PinnedStage() {
+    for (int k = 0; k < 2; ++k)
       if (ev[k]) (void)hipEventDestroy(ev[k]);
-    }
   }
   // the next slot's host bytes, once the copy out of them two calls ago has run (an event never recorded is complete)
   int next(unsigned char **hb) {
@@ -1593,7 +1575,6 @@ struct BatchInputs {
     B = n_env;
     return pin.alloc((size_t)B * 8 * sizeof(float) + (size_t)B);
   }
-  void free() { pin.free(); }
   // states [B][ds] and / or the active mask [B] -> the device through the next pinned slot, on the context's stream; nobody waits
   int stage(const dust_ctx *c, const float *states, const unsigned char *active) {
     unsigned char *hb;
@@ -1607,7 +1588,7 @@ struct BatchInputs {
     if (active) memcpy(hb + sbytes, active, (size_t)B);
     return pin.send(states ? 0 : sbytes, active ? sbytes + (size_t)B : sbytes, c->stream);
   }
-  const float *states_dev() const { return reinterpret_cast<const float *>(pin.dev); }
+  const float *states_dev() const { return reinterpret_cast<const float *>(pin.dev.get()); }
   // where the kernels find the mask a call has staged (nullptr: the call had none - everybody is active)
   const unsigned char *mask_dev(const unsigned char *active) const { return active ? pin.dev + (size_t)B * 8 * sizeof(float) : nullptr; }
 };
@@ -1652,14 +1633,13 @@ static int batch_seeds_set(dust_ctx *c, size_t B, const uint64_t *seeds, uint64_
 struct dust_amppi_batch {
   dust_ctx *c;
   int B;
-  float *a_seq;           // [B][D]
-  float *acts;            // [B][S][D]
-  float *costs, *omega;   // [B][S]
-  float *params;          // [B][rows][P]
-  size_t params_cap;
-  uint32_t *ctr;          // [B][4]: every environment's Philox stream position {tick, iter, .., ..}
-  uint64_t *seeds;        // [B]
-  unsigned int *ticket;   // [B]
+  DevBuf<float> a_seq;           // [B][D]
+  DevBuf<float> acts;            // [B][S][D]
+  DevBuf<float> costs, omega;    // [B][S]
+  DevBuf<float> params;          // [B][rows][P]
+  DevBuf<uint32_t> ctr;          // [B][4]: every environment's Philox stream position {tick, iter, .., ..}
+  DevBuf<uint64_t> seeds;        // [B]
+  DevBuf<unsigned int> ticket;   // [B]
   BatchInputs in;         // per-call inputs
   std::vector<unsigned char> last_active;  // the mask of the last tick (dust_amppi_batch_get_actions writes the rows of that tick's environments)
   bool acts_valid;
@@ -1671,12 +1651,9 @@ static void batch_free(dust_amppi_batch *b) {
     (void)hipSetDevice(b->c->cfg.device);
     (void)hipStreamSynchronize(b->c->stream);
   }
-  void *dev[] = {b->a_seq, b->acts, b->costs, b->omega, b->params, b->ctr, b->seeds, b->ticket};
-  for (void *p : dev)
-    if (p) (void)hipFree(p);
-  b->in.free();
-  if (b->c) dust_destroy(b->c);
-  delete b;
+  dust_ctx *inner = b->c;
+  delete b;  // the batch's own rows first, then the context they were allocated beside
+  if (inner) dust_destroy(inner);
 }
 
 // the batch around an inner context it takes over: buffers allocated, nothing filled yet
@@ -1687,13 +1664,13 @@ static int batch_alloc(dust_ctx *inner, int n_env, dust_amppi_batch **out) {
   *out = b;
   const size_t B = (size_t)n_env, S = (size_t)inner->S, D = (size_t)inner->D;
   HIP_TRY(hipSetDevice(inner->cfg.device));
-  TRY(dalloc(&b->a_seq, B * D));
-  TRY(dalloc(&b->acts, B * S * D));
-  TRY(dalloc(&b->costs, B * S));
-  TRY(dalloc(&b->omega, B * S));
-  TRY(dalloc(&b->ctr, B * 4));
-  TRY(dalloc(&b->seeds, B));
-  TRY(dalloc(&b->ticket, B));
+  TRY(b->a_seq.alloc(B * D));
+  TRY(b->acts.alloc(B * S * D));
+  TRY(b->costs.alloc(B * S));
+  TRY(b->omega.alloc(B * S));
+  TRY(b->ctr.alloc(B * 4));
+  TRY(b->seeds.alloc(B));
+  TRY(b->ticket.alloc(B));
   return b->in.alloc(n_env);
 }
 
@@ -1797,7 +1774,7 @@ static int batch_update_launch(dust_amppi_batch *b, const float *states, const f
     else TRY(h2d(c, b->acts, actions, B * S * D * sizeof(float)));
   }
   if (prows) {
-    TRY(ensure(&b->params, &b->params_cap, B * prows * P));
+    TRY(b->params.ensure(B * prows * P));
     if (!staged) TRY(h2d(c, b->params, params, B * prows * P * sizeof(float)));
   }
   TRY(b->in.stage(c, states, active));
@@ -2001,7 +1978,7 @@ static int rollout_args(dust_ctx *c, const SampleOpts &o, RolloutArgs &a, int *n
   a.state = c->state_dev;
   a.theta = o.base;
   a.noise = o.noise_dev;
-  a.params = (c->cfg.dim_p > 0 && c->params_dev) ? c->params_dev : nullptr;
+  a.params = c->cfg.dim_p > 0 ? params_cur(c) : nullptr;
   a.mw = c->mw_dev;
   a.a_seq = c->a_seq;
   a.a_mat = c->a_mat;
@@ -2013,11 +1990,11 @@ static int rollout_args(dust_ctx *c, const SampleOpts &o, RolloutArgs &a, int *n
   a.eta = c->eta;
   a.omegaT = o.want_omega ? c->omegaT : nullptr;
   if (o.want_actions) {
-    TRY(ensure(&c->actions, &c->actions_cap, ((size_t)c->S * c->N * c->D + (o.store_f16 ? 1 : 0)) >> (o.store_f16 ? 1 : 0)));
+    TRY(c->actions.ensure(((size_t)c->S * c->N * c->D + (o.store_f16 ? 1 : 0)) >> (o.store_f16 ? 1 : 0)));
     a.actions_out = c->actions;
   }
   if (o.want_states) {
-    TRY(ensure(&c->states, &c->states_cap, ((size_t)c->M * c->S * c->N * (c->H + 1) * c->ds) >> (o.store_f16 ? 1 : 0)));
+    TRY(c->states.ensure(((size_t)c->M * c->S * c->N * (c->H + 1) * c->ds) >> (o.store_f16 ? 1 : 0)));
     a.states_out = c->states;
   }
   a.seed = c->cfg.seed;
@@ -2055,7 +2032,7 @@ static int rollout_args(dust_ctx *c, const SampleOpts &o, RolloutArgs &a, int *n
   const int stage_b = stage_states ? rollout_stage_bytes_per_lane(c->cfg.model) : 0;
   size_t lds = rollout_lds_bytes(c->S, c->D, c->M, nt, true, stage_b, a.grid_words);
   if (lds > 96 * 1024) {  // keep >= 1 workgroup per CU resident with room to spare; larger tiles go to an HBM slab
-    TRY(ensure(&c->tile_scratch, &c->tile_cap, (size_t)c->nloc * c->S * (c->D | 1)));
+    TRY(c->tile_scratch.ensure((size_t)c->nloc * c->S * (c->D | 1)));
     a.tile_scratch = c->tile_scratch;
     lds = rollout_lds_bytes(c->S, c->D, c->M, nt, false, stage_b, a.grid_words);  // (HBM tile: full-feature kernel)
     if (lds > 160 * 1024) return fail(DUST_ERR_UNSUPPORTED, "n_samples too large for one workgroup (%zu B of LDS)", lds);
@@ -2181,8 +2158,8 @@ static void first_pass_param_args(const dust_ctx *c, Args &k) {
 // operands) do any work.  `mid`: the kernel's arguments between costs_sn and wg_flags.
 template <class K, class... Mid>
 static int launch_whole_lines(dust_ctx *c, const FirstPass &fp, const RolloutArgs &a, int threads, K fast, K general, Mid... mid) {
-  TRY(ensure(&c->wg_flags, &c->wg_flags_cap, (size_t)fp.blocks));
-  unsigned int *fl = reinterpret_cast<unsigned int *>(c->wg_flags);
+  TRY(c->wg_flags.ensure((size_t)fp.blocks));
+  unsigned int *fl = c->wg_flags.get();
   for (K k : {fast, general}) HIP_TRY(launch(c, k, fp.blocks, threads, fp.lds, a, c->costs_stage, mid..., fl));
   return DUST_OK;
 }
@@ -2359,7 +2336,7 @@ static int upload_state_params(dust_ctx *c, const float *state, const float *par
   if (c->params_staged) params = nullptr;  // (dust_dual_tick: the samples are in params_dev already)
   const size_t np = (c->cfg.dim_p > 0 && c->M >= 1 && params) ? (size_t)n_sets * c->M * c->P : 0;
   if (np > 0 && np <= 240) {
-    TRY(ensure(&c->params_dev, &c->params_cap, np));
+    TRY(c->params_dev.ensure(np));
     StateParamsWord w;
     for (int k = 0; k < 8; ++k) w.v[k] = (state && k < c->ds) ? state[k] : 0.f;
     memcpy(w.p, params, np * sizeof(float));
@@ -2377,7 +2354,7 @@ static int upload_state_params(dust_ctx *c, const float *state, const float *par
   }
   if (c->cfg.dim_p > 0 && c->M >= 1) {
     if (params) {
-      TRY(ensure(&c->params_dev, &c->params_cap, (size_t)n_sets * c->M * c->P));
+      TRY(c->params_dev.ensure((size_t)n_sets * c->M * c->P));
       TRY(h2d(c, c->params_dev, params, (size_t)n_sets * c->M * c->P * sizeof(float)));
     }
   }
@@ -2396,7 +2373,7 @@ static int stage_noise(dust_ctx *c, const float *src, int flags, const float **d
     *dev = src;
     return DUST_OK;
   }
-  TRY(ensure(&c->noise_stage, &c->noise_cap, n));
+  TRY(c->noise_stage.ensure(n));
   TRY(h2d(c, c->noise_stage, src, n * ((flags & DUST_EPS_F16) ? 2 : sizeof(float))));
   *dev = c->noise_stage;
   return DUST_OK;
@@ -2430,8 +2407,8 @@ extern "C" int dust_get_states_rows(dust_ctx *c, const long long *rows, int n_ro
   HIP_TRY(hipSetDevice(c->cfg.device));
   const int row_elems = (c->H + 1) * c->ds, eb = c->states_f16 ? 2 : 4;
   const size_t idx_floats = ((size_t)n_rows * sizeof(long long) + 3) / 4, out_floats = ((size_t)n_rows * row_elems * eb + 3) / 4;
-  TRY(ensure(&c->tmp, &c->tmp_cap, idx_floats + 2 + out_floats));
-  long long *idx_dev = reinterpret_cast<long long *>(c->tmp);  // (hipMalloc'd: 256-byte aligned)
+  TRY(c->tmp.ensure(idx_floats + 2 + out_floats));
+  long long *idx_dev = rows_idx_view(c);
   void *dst = c->tmp + ((idx_floats + 1) & ~(size_t)1);
   TRY(h2d(c, idx_dev, rows, (size_t)n_rows * sizeof(long long)));
   gather_rows_kernel<<<n_rows, 64, 0, c->stream>>>(c->states, dst, idx_dev, n_rows, row_elems, eb);
@@ -2593,7 +2570,7 @@ static int launch_pair(dust_ctx *c, const PairArgs &a, int tiles) {
 // The rows padded to `dpb` columns (the large-set passes read whole padded rows): a copy in xpad - or, where the caller allows it
 // and D is the padded width already, the rows themselves (D = 80: no pad_rows launch, 7 us per pass at N = 16 384)
 static int padded_rows(dust_ctx *c, const PairArgs &a, int dpb, bool alias_ok, const float **Xp) {
-  TRY(ensure(&c->xpad, &c->xpad_cap, (size_t)c->N * dpb));
+  TRY(c->xpad.ensure((size_t)c->N * dpb));
   *Xp = a.X;
   if (alias_ok && a.D == dpb) return DUST_OK;
   const int n = c->N * dpb;
@@ -2659,22 +2636,23 @@ static int far_args(dust_ctx *c, const PairArgs &a, int dpb, int chunks, bool lo
   f.X = a.X;
   f.logmix = a.logmix;
   f.T = c->env.far_t * f.lscale;
-  TRY(ensure(&c->far_z, &c->far_z_cap, ((size_t)c->N * far_zh(dpb) + 1) / 2));
-  TRY(ensure(&c->far_n, &c->far_n_cap, 3 * (size_t)c->N + chunks));
-  TRY(ensure(logp ? &c->far_g : &c->far_f, logp ? &c->far_g_cap : &c->far_f_cap, ((size_t)f.tiles * chunks + 3) / 4));
-  f.Z = reinterpret_cast<_Float16 *>(c->far_z);
+  DevBuf<unsigned char> &flags = logp ? c->far_g : c->far_f;
+  TRY(c->far_z.ensure((size_t)c->N * far_zh(dpb)));  // (far_zh is a multiple of 32: whole words without rounding)
+  TRY(c->far_n.ensure(3 * (size_t)c->N + chunks));
+  TRY(flags.ensure((size_t)f.tiles * chunks));  // (read and written byte by byte, [tile][chunk] only: no rounded tail)
+  f.Z = c->far_z.get();
   f.nrm = c->far_n;
   f.lms = c->far_n + c->N;
   f.m0 = c->far_n + 2 * (size_t)c->N;
-  f.far = reinterpret_cast<unsigned char *>(logp ? c->far_g : c->far_f);
+  f.far = flags.get();
   if (masks) {
-    TRY(ensure(&c->far_q, &c->far_q_cap, (size_t)f.tiles * chunks * 8));
-    f.qmask = reinterpret_cast<unsigned int *>(c->far_q);
+    TRY(c->far_q.ensure((size_t)f.tiles * chunks * 8));
+    f.qmask = c->far_q.get();
   }
   if (counted) {
     TRY(far_counts_alloc(c));
     if (c->far_cnt_host) {
-      f.count = reinterpret_cast<unsigned int *>(c->far_cnt) + (logp ? 4 : 0);
+      f.count = c->far_cnt.get() + (logp ? 4 : 0);
       f.host_count = c->far_cnt_host + (logp ? 4 : 0);
     }
   }
@@ -2698,22 +2676,22 @@ static int pack_args(dust_ctx *c, RunLists &r, int tiles, int chunks, int JS, in
   pk.JS = JS;
   pk.JSG = JS;
   pk.ldi = chunks * 64;
-  TRY(ensure(&r.idx, &r.idx_cap, (size_t)tiles * pk.ldi));
-  TRY(ensure(&r.uoff, &r.uoff_cap, (size_t)tiles * (chunks + 1)));
-  TRY(ensure(&r.uq, &r.uq_cap, (size_t)tiles * chunks * 4));
-  TRY(ensure(&r.soff, &r.soff_cap, (size_t)tiles * (JS + 1)));
-  TRY(ensure(&r.goff, &r.goff_cap, (size_t)tiles * (JS + 1)));
-  pk.kidx = reinterpret_cast<int *>(r.idx);
-  pk.uoff = reinterpret_cast<int *>(r.uoff);
-  pk.uq = reinterpret_cast<unsigned int *>(r.uq);
-  pk.soff = reinterpret_cast<int *>(r.soff);
-  pk.goff = reinterpret_cast<int *>(r.goff);
+  TRY(r.idx.ensure((size_t)tiles * pk.ldi));
+  TRY(r.uoff.ensure((size_t)tiles * (chunks + 1)));
+  TRY(r.uq.ensure((size_t)tiles * chunks * 4));
+  TRY(r.soff.ensure((size_t)tiles * (JS + 1)));
+  TRY(r.goff.ensure((size_t)tiles * (JS + 1)));
+  pk.kidx = r.idx.get();
+  pk.uoff = r.uoff.get();
+  pk.uq = r.uq.get();
+  pk.soff = r.soff.get();
+  pk.goff = r.goff.get();
   return DUST_OK;
 }
 
 // What the two matrix-core log-p passes share of LogpMfmaArgs (zeroed by the caller); the slice rule that gave JS is the caller's own
 static int logp_mfma_args(dust_ctx *c, const PairArgs &a, int dpb, int JS, LogpMfmaArgs &b) {
-  TRY(ensure(&c->xpad, &c->xpad_cap, (size_t)c->N * dpb + 2 * (size_t)c->N));
+  TRY(c->xpad.ensure((size_t)c->N * dpb + 2 * (size_t)c->N));
   b.N = c->N;
   b.D = a.D;
   b.i0 = a.i0;
@@ -2741,7 +2719,7 @@ static int launch_pair_fused(dust_ctx *c, const PairArgs &a, int tiles) {
   memset(&b, 0, sizeof b);
   b.p = a;
   TRY(padded_rows(c, a, dpb, true, &b.Xp));
-  TRY(ensure(&c->kmat, &c->kmat_cap, (size_t)tiles * chunks * tq * 64));  // [tiles][chunks][TQ][64]: touched only where units exist
+  TRY(c->kmat.ensure((size_t)tiles * chunks * tq * 64));  // [tiles][chunks][TQ][64]: touched only where units exist
   b.ldp = 8 * cpt_for(a.D);
   metric_weights(a, b.wP);
   b.wS[0] = b.wS[1] = (1.0f / stein_ell(c)) * (1.0f / stein_ell(c));
@@ -2756,12 +2734,12 @@ static int launch_pair_fused(dust_ctx *c, const PairArgs &a, int tiles) {
   const bool merge_mode = c->cfg.kernel == DUST_KERNEL_K1_RBF && !dense && c->env.far != 0 && c->env.far_t < DUST_FAR_T_EXACT && c->env.pack_merge != 0;
   const bool order = merge_mode && c->env.pack_order != 0 && !c->stagewise;
   if (order) {
-    const bool fresh = c->pk_perm_cap < (size_t)c->nloc || c->pk_lead_cap < (size_t)c->nloc;
+    const bool fresh = c->pk_perm.cap() < (size_t)c->nloc || c->pk_lead.cap() < (size_t)c->nloc;
     if (fresh && c->capturing) return fail(DUST_ERR_STATE, "tile-order buffers must exist before a capture");
-    TRY(ensure(&c->pk_perm, &c->pk_perm_cap, (size_t)c->nloc));
-    TRY(ensure(&c->pk_lead, &c->pk_lead_cap, (size_t)c->nloc));
+    TRY(c->pk_perm.ensure((size_t)c->nloc));
+    TRY(c->pk_lead.ensure((size_t)c->nloc));
     if (fresh) {  // index order, no leaders yet
-      iota_kernel<<<(c->nloc + 255) / 256, 256, 0, c->stream>>>(reinterpret_cast<int *>(c->pk_perm), c->nloc);
+      iota_kernel<<<(c->nloc + 255) / 256, 256, 0, c->stream>>>(c->pk_perm.get(), c->nloc);
       HIP_TRY(hipMemsetAsync(c->pk_lead, 0x7f, (size_t)c->nloc * sizeof(int), c->stream));
     }
   }
@@ -2779,7 +2757,7 @@ static int launch_pair_fused(dust_ctx *c, const PairArgs &a, int tiles) {
     f.Xp = b.Xp;
     f.wP[0] = b.wP[0];
     f.wP[1] = b.wP[1];
-    f.qperm = order ? reinterpret_cast<const int *>(c->pk_perm) : nullptr;
+    f.qperm = order ? c->pk_perm.get() : nullptr;
     dim3 fgrid;
     TRY(far_args(c, a, dpb, chunks, false, flags, flags, f, &fgrid));  // ({far units, all units} of this pass: dust_debug_far_units)
     TRY((pick_int<32, 64, 80>(dpb, [&](auto d) {
@@ -2801,7 +2779,7 @@ static int launch_pair_fused(dust_ctx *c, const PairArgs &a, int tiles) {
   const int JS = packed_slices(c, tiles, chunks);
   b.p.JS = JS;
   TRY(pack_args(c, c->pk, tiles, chunks, JS, (pk.qmask != nullptr && merge_mode) ? 1 : 0, pk));
-  TRY(ensure(&c->pk_nzu, &c->pk_nzu_cap, ((size_t)tiles * chunks + 3) / 4));
+  TRY(c->pk_nzu.ensure((size_t)tiles * chunks));  // (bytes [tile][unit], as the flags)
   HIP_TRY(launch(c, far_pack_kernel, tiles, 1024, far_pack_lds_bytes(chunks), pk));
   c->pk_tiles = tiles;
   c->pk_umax = chunks;
@@ -2813,9 +2791,9 @@ static int launch_pair_fused(dust_ctx *c, const PairArgs &a, int tiles) {
   b.uoff = pk.uoff;
   b.uq = c->pk_masks ? pk.uq : nullptr;
   b.soff = pk.soff;
-  b.nzu = c->pk_dense ? nullptr : reinterpret_cast<unsigned char *>(c->pk_nzu);
-  b.qperm = order ? reinterpret_cast<const int *>(c->pk_perm) : nullptr;
-  b.lead = order ? reinterpret_cast<int *>(c->pk_lead) : nullptr;
+  b.nzu = c->pk_dense ? nullptr : c->pk_nzu.get();
+  b.qperm = order ? c->pk_perm.get() : nullptr;
+  b.lead = order ? c->pk_lead.get() : nullptr;
   c->fused_js = JS;
   TRY(ensure_partials(c, std::max(a.JS, JS)));  // before anything is written: pass 2 adds its pA rows later
   b.p.pA = c->pA;
@@ -2848,9 +2826,9 @@ static int launch_pair_fused(dust_ctx *c, const PairArgs &a, int tiles) {
 // variant).  DUST_FAR=2: always on.
 static int far_counts_alloc(dust_ctx *c) {
   if (c->far_cnt_host || c->capturing) return DUST_OK;
-  HIP_TRY(hipHostMalloc((void **)&c->far_cnt_host, 8 * sizeof(unsigned int), hipHostMallocCoherent | hipHostMallocMapped));
+  TRY(c->far_cnt_host.alloc(8, hipHostMallocCoherent | hipHostMallocMapped));
   memset(c->far_cnt_host, 0, 8 * sizeof(unsigned int));
-  TRY(ensure(&c->far_cnt, &c->far_cnt_cap, 8));
+  TRY(c->far_cnt.ensure(8));
   HIP_TRY(hipMemsetAsync(c->far_cnt, 0, 8 * sizeof(unsigned int), c->stream));
   return DUST_OK;
 }
@@ -2906,7 +2884,7 @@ static int launch_pair_logp_packed(dust_ctx *c, const PairArgs &a) {
   f.Xp = b.Z;  // the scaled rows: unit metric
   f.wP[0] = f.wP[1] = 1.0f;
   const bool order = c->pk_order && c->pk_perm && !c->stagewise;  // pass 1's tile order (the one in force this tick)
-  f.qperm = order ? reinterpret_cast<const int *>(c->pk_perm) : nullptr;
+  f.qperm = order ? c->pk_perm.get() : nullptr;
   dim3 fgrid;
   TRY(far_args(c, a, dpb, chunks, true, true, true, f, &fgrid));
   if (f.count && !c->capturing) c->far_logp_issued++;
@@ -3017,13 +2995,13 @@ static int launch_gram_score(dust_ctx *c, const PairArgs &a, int *JS_out) {
   g.Kp = c->kmat;
   g.V = c->score;
   g.pA = c->pA;
-  g.kidx = reinterpret_cast<const int *>(c->pk.idx);
+  g.kidx = c->pk.idx.get();
   g.ldi = c->pk_umax * 64;
-  g.uoff = reinterpret_cast<const int *>(c->pk.uoff);
-  g.uq = c->pk_masks ? reinterpret_cast<const unsigned int *>(c->pk.uq) : nullptr;
-  g.goff = reinterpret_cast<const int *>(c->pk.goff);
-  g.qperm = c->pk_order ? reinterpret_cast<const int *>(c->pk_perm) : nullptr;
-  g.nzu = c->pk_dense ? nullptr : reinterpret_cast<const unsigned char *>(c->pk_nzu);
+  g.uoff = c->pk.uoff.get();
+  g.uq = c->pk_masks ? c->pk.uq.get() : nullptr;
+  g.goff = c->pk.goff.get();
+  g.qperm = c->pk_order ? c->pk_perm.get() : nullptr;
+  g.nzu = c->pk_dense ? nullptr : c->pk_nzu.get();
   // (its own column padding: whole 16-column MFMA tiles, not the 32 / 64 / 80 of pass 1 - D = 40 runs 3 column tiles instead of 4;
   //  the query tile is pass 1's: 128 / 112 / 96 rows at D <= 32 / 64 / 80)
   TRY((pick_int<16, 32, 48, 64, 80>(((a.D + 15) / 16) * 16, [&](auto d) {
@@ -3041,8 +3019,8 @@ static int launch_gram_score(dust_ctx *c, const PairArgs &a, int *JS_out) {
       HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
       HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
     }
-    HIP_TRY(launch_on(qs, c->capturing, query_order_kernel, 1, 1024, query_order_lds_bytes(c->nloc), reinterpret_cast<int *>(c->pk_lead),
-                      reinterpret_cast<int *>(c->pk_perm), c->nloc, c->n0, c->N));
+    HIP_TRY(launch_on(qs, c->capturing, query_order_kernel, 1, 1024, query_order_lds_bytes(c->nloc), c->pk_lead.get(),
+                      c->pk_perm.get(), c->nloc, c->n0, c->N));
     if (side) {
       HIP_TRY(hipEventRecord(c->ev_order, c->stream2));
       c->order_pending = true;
@@ -3053,18 +3031,18 @@ static int launch_gram_score(dust_ctx *c, const PairArgs &a, int *JS_out) {
 
 static int ensure_partials(dust_ctx *c, int JS) {
   const size_t nd = (size_t)JS * c->nloc * 8 * cpt_for(c->D), nn = (size_t)JS * c->nloc;
-  TRY(ensure(&c->pA, &c->pA_cap, nd));
-  TRY(ensure(&c->pB, &c->pB_cap, nd));
-  TRY(ensure(&c->pM, &c->pM_cap, nn));
-  TRY(ensure(&c->pL, &c->pL_cap, nn));
+  TRY(c->pA.ensure(nd));
+  TRY(c->pB.ensure(nd));
+  TRY(c->pM.ensure(nn));
+  TRY(c->pL.ensure(nn));
   return DUST_OK;
 }
 
 // prior pass: writes slice partials (pA, pM, pL); combined by rollout_kernel (merge_prior) or prior_finish_kernel
 static int ensure_whitened(dust_ctx *c) {
   const size_t nd = (size_t)c->N * c->D;
-  if (!c->theta_w) TRY(dalloc(&c->theta_w, nd));
-  if (!c->mu_w) TRY(dalloc(&c->mu_w, nd));
+  if (!c->theta_w) TRY(c->theta_w.alloc(nd));
+  if (!c->mu_w) TRY(c->mu_w.alloc(nd));
   return DUST_OK;
 }
 static int launch_whiten(dust_ctx *c) {
@@ -3159,9 +3137,7 @@ static int launch_fused(dust_ctx *c, const SampleOpts &o, bool *done) {
   }
   if (!c->fused_cnt || c->fused_tiles != f.tiles) {
     if (c->capturing) return DUST_OK;
-    if (c->fused_cnt) HIP_TRY(hipFree(c->fused_cnt));
-    c->fused_cnt = nullptr;
-    TRY(dalloc(&c->fused_cnt, ((size_t)f.tiles + 1) * CNT_STRIDE));
+    TRY(c->fused_cnt.alloc(((size_t)f.tiles + 1) * CNT_STRIDE));
     HIP_TRY(hipMemsetAsync(c->fused_cnt, 0, ((size_t)f.tiles + 1) * CNT_STRIDE * sizeof(unsigned int), c->stream));  // incl. the time-out word
     c->fused_tiles = f.tiles;
     c->fused_dirty = true;
@@ -3227,9 +3203,9 @@ static UpdateArgs update_args(dust_ctx *c, int apply) {
   u.phi = c->phi;
   u.theta = c->theta;
   u.theta_out = c->theta;
-  u.opt_s0 = c->opt_s0;
-  u.opt_s1 = c->opt_s1;
-  u.opt_s2 = c->opt_s2;
+  u.opt_s0 = c->opt_s[0];
+  u.opt_s1 = c->opt_s[1];
+  u.opt_s2 = c->opt_s[2];
   u.ctr = c->ctr_dev;
   u.fused_cnt = c->fused_cnt;
   u.fused_tiles = c->fused_cnt ? c->fused_tiles : 0;
@@ -3303,9 +3279,9 @@ static int launch_stein_update(dust_ctx *c, int apply, bool in_loop = false /* K
       }
       TRY(launch_k2_phi(c->stream, kp));
       c->k2_thetaT_fresh = false;
-      if (rows) std::swap(c->theta, c->theta_alt);
+      if (rows) c->theta.swap(c->theta_alt);
       if (kp.thetaT_out) {
-        std::swap(c->thetaT, c->thetaT_alt);
+        c->thetaT.swap(c->thetaT_alt);
         c->k2_thetaT_fresh = true;
       }
     }
@@ -3338,9 +3314,7 @@ static int launch_stein_update(dust_ctx *c, int apply, bool in_loop = false /* K
     if (fuse && (!c->stein_cnt || c->stein_tiles != tiles)) {
       if (c->capturing) fuse = false;
       else {
-        if (c->stein_cnt) HIP_TRY(hipFree(c->stein_cnt));
-        c->stein_cnt = nullptr;
-        TRY(dalloc(&c->stein_cnt, ((size_t)tiles + 2) * CNT_STRIDE));
+        TRY(c->stein_cnt.alloc(((size_t)tiles + 2) * CNT_STRIDE));
         HIP_TRY(hipMemsetAsync(c->stein_cnt, 0, ((size_t)tiles + 2) * CNT_STRIDE * sizeof(unsigned int), c->stream));  // incl. the time-out word
         c->stein_tiles = tiles;
         c->stein_dirty = true;  // the rollout launch that preceded this call did not know the buffer
@@ -3358,7 +3332,7 @@ static int launch_stein_update(dust_ctx *c, int apply, bool in_loop = false /* K
         js2 = (c->N + sl2 - 1) / sl2;
       }
       const size_t need = (size_t)js2 * c->nloc * 8 * cpt;
-      if (js2 != a.JS && js2 <= 16 && (!c->capturing || (c->pA_cap >= need && c->pB_cap >= need))) {
+      if (js2 != a.JS && js2 <= 16 && (!c->capturing || (c->pA.cap() >= need && c->pB.cap() >= need))) {
         TRY(ensure_partials(c, js2));
         a.JS = js2;
         a.slice = sl2;
@@ -3384,7 +3358,7 @@ static int launch_stein_update(dust_ctx *c, int apply, bool in_loop = false /* K
         return pick_int<4, 8>(cpt, [](auto k) { return stein_update_kernel<decltype(mode)::value, k()>; });
       });
       HIP_TRY(launch_chained(c, kernel, grid, PAIR_NT, lds, f));
-      if (pingpong) std::swap(c->theta, c->theta_alt);
+      if (pingpong) c->theta.swap(c->theta_alt);
       c->stein_dirty = true;
       c->fused_dirty = false;
       return DUST_OK;
@@ -3456,14 +3430,12 @@ static SampleOpts score_opts(const dust_ctx *c, const float *noise_dev) {
   o.bump_adam = 1;
   return o;
 }
-// c->params_dev at set `param_set` of the tick's dynamics samples ([n_sets][M][P]) while the guard lives
+// params_cur at set `param_set` of the tick's dynamics samples ([n_sets][M][P]) while the guard lives
 struct ParamSet {
   dust_ctx *c;
-  float *save;
-  ParamSet(dust_ctx *c_, int param_set) : c(c_), save(c_->params_dev) {
-    if (c->params_dev) c->params_dev += (size_t)param_set * c->M * c->P;
-  }
-  ~ParamSet() { c->params_dev = save; }
+  size_t save;
+  ParamSet(dust_ctx *c_, int param_set) : c(c_), save(c_->params_off) { c->params_off += (size_t)param_set * c->M * c->P; }
+  ~ParamSet() { c->params_off = save; }
 };
 
 // local half of one SVGD iteration: prior partials -> rollout (+ merge) -> score rows of this shard
@@ -3522,18 +3494,16 @@ static int launch_iter(dust_ctx *c, const float *noise_dev, int param_set, bool 
   const int JS = f.prior.JS, lines = 2 * f.tiles;  // per counter set: the prior tiles' lines, then the Stein tiles'
   {
     const size_t nd = (size_t)JS * c->nloc * 8 * cpt;
-    if (c->pS_cap < nd && c->capturing) return DUST_OK;
-    TRY(ensure(&c->pS, &c->pS_cap, nd));
+    if (c->pS.cap() < nd && c->capturing) return DUST_OK;
+    TRY(c->pS.ensure(nd));
   }
   if (!c->iter_cnt || c->iter_tiles != f.tiles) {
     if (c->capturing) return DUST_OK;
-    if (c->iter_cnt) HIP_TRY(hipFree(c->iter_cnt));
-    c->iter_cnt = nullptr;
-    TRY(dalloc(&c->iter_cnt, ((size_t)2 * lines + 1) * CNT_STRIDE));
+    TRY(c->iter_cnt.alloc(((size_t)2 * lines + 1) * CNT_STRIDE));
     HIP_TRY(hipMemsetAsync(c->iter_cnt, 0, ((size_t)2 * lines + 1) * CNT_STRIDE * sizeof(unsigned int), c->stream));
     c->iter_tiles = f.tiles;
     c->iter_set = 0;
-    if (!c->score_hs) TRY(dalloc(&c->score_hs, (size_t)2 * c->N * c->D));
+    if (!c->score_hs) TRY(c->score_hs.alloc((size_t)2 * c->N * c->D));
     HIP_TRY(hipMemsetAsync(c->score_hs, 0xFF, (size_t)2 * c->N * c->D * sizeof(float), c->stream));  // SCORE_SENTINEL in every word
   }
   // Stein role: same geometry as the prior pass (pair_geometry), keys = queries = theta; the score rows arrive through score_pub
@@ -3560,7 +3530,7 @@ static int launch_iter(dust_ctx *c, const float *noise_dev, int param_set, bool 
   f.zero_lines = lines;
   f.timeout_flag = c->iter_cnt + (size_t)2 * lines * CNT_STRIDE;
   f.score_pub = c->score_hs + (size_t)c->iter_set * c->N * c->D;
-  f.score_reset = reinterpret_cast<unsigned int *>(c->score_hs + (size_t)(1 - c->iter_set) * c->N * c->D);
+  f.score_reset = score_hs_words(c, 1 - c->iter_set);
   f.score_elems = c->N * c->D;
   f.tl = c->tl_dev;
   const int n = c->nloc * c->D;
@@ -3572,7 +3542,7 @@ static int launch_iter(dust_ctx *c, const float *noise_dev, int param_set, bool 
   });
   HIP_TRY(launch_chained(c, kernel, grid, PAIR_NT, lds, f));
   c->iter_set ^= 1;
-  std::swap(c->theta, c->theta_alt);
+  c->theta.swap(c->theta_alt);
   c->actions_valid = false;
   c->have_sample = true;
   *done = true;
@@ -3678,24 +3648,21 @@ static RollArgs roll_args(dust_ctx *c, int steps, int strategy, const float *las
   r.i0 = c->n0;
   r.n_local = c->nloc;
   r.ctr = c->ctr_dev;
-  r.opt_s0 = c->opt_s0;
-  r.opt_s1 = c->opt_s1;
-  r.opt_s2 = c->opt_s2;
+  r.opt_s0 = c->opt_s[0];
+  r.opt_s1 = c->opt_s[1];
+  r.opt_s2 = c->opt_s[2];
   r.s0_restart = opt_restart_s0(c->opt);
   if (c->iter_cnt) {
     r.rearm = c->iter_cnt;
     r.rearm_lines = 2 * (2 * c->iter_tiles);
-    r.hs = reinterpret_cast<unsigned int *>(c->score_hs);
+    r.hs = score_hs_words(c, 0);
     r.hs_n = 2 * c->N * c->D;
   }
   return r;
 }
 static void roll_done(dust_ctx *c) {
   c->kmat_valid = false;  // theta rolled: the Gram matrix of pairwise_fused.hpp belongs to the old particles
-  if (c->theta != c->theta_home) {
-    c->theta_alt = c->theta;
-    c->theta = c->theta_home;
-  }
+  if (c->theta != c->theta_home) c->theta.swap(c->theta_alt);  // (the two blocks of the ping-pong: theta_alt held the home block)
 }
 
 // weights + argmax (+ prior refresh), then the roll: SVMPC.forward's tail (svmpc.py:190-200)
@@ -3729,7 +3696,7 @@ static int resample_rows(dust_ctx *c, const float *host_rows, const float **dev)
   *dev = nullptr;
   if (c->cfg.roll_strategy != DUST_ROLL_RESAMPLE && !host_rows) return DUST_OK;
   if (!host_rows) return fail(DUST_ERR_INVALID, "roll strategy 'resample' needs the last action of a prior sample per particle ([N][da])");
-  TRY(ensure(&c->tmp, &c->tmp_cap, (size_t)c->N * c->da));
+  TRY(c->tmp.ensure((size_t)c->N * c->da));
   TRY(h2d(c, c->tmp, host_rows, (size_t)c->N * c->da * sizeof(float)));
   *dev = c->tmp;
   return DUST_OK;
@@ -3758,7 +3725,7 @@ extern "C" int dust_svmpc_roll(dust_ctx *c, int steps, int strategy, const float
   const float *lr = nullptr;
   if (strategy == DUST_ROLL_RESAMPLE) {
     if (!last_row) return fail(DUST_ERR_INVALID, "strategy 'resample' needs last_row [N][da]");
-    TRY(ensure(&c->tmp, &c->tmp_cap, (size_t)c->N * c->da));
+    TRY(c->tmp.ensure((size_t)c->N * c->da));
     TRY(h2d(c, c->tmp, last_row, (size_t)c->N * c->da * sizeof(float)));
     lr = c->tmp;
   }
@@ -3926,18 +3893,17 @@ static int launch_tick2(dust_ctx *c, const float *state, int n_steps, const floa
   if (!c->t2_xq || c->t2_gens < n_steps + 1) {  // one [N][32] block per generation of particles / score rows (tick2.hpp t2_ld16)
     if (c->t2_xq) {
       HIP_TRY(hipStreamSynchronize(c->stream));
-      (void)hipFree(c->t2_xq);
-      (void)hipFree(c->t2_sq);
-      c->t2_xq = c->t2_sq = nullptr;
+      (void)c->t2_xq.reset();
+      (void)c->t2_sq.reset();
     }
     const int gens = std::max(n_steps + 1, 8);
-    TRY(dalloc(&c->t2_xq, (size_t)gens * c->N * T2_ROW));
-    TRY(dalloc(&c->t2_sq, (size_t)gens * c->N * T2_ROW));
+    TRY(c->t2_xq.alloc((size_t)gens * c->N * T2_ROW));
+    TRY(c->t2_sq.alloc((size_t)gens * c->N * T2_ROW));
     c->t2_gens = gens;
   }
   if (!c->t2_cnt) {
-    TRY(dalloc(&c->t2_lwq, (size_t)c->N));
-    TRY(dalloc(&c->t2_cnt, (size_t)2 * T2_SETS * T2_CNT_STRIDE));
+    TRY(c->t2_lwq.alloc((size_t)c->N));
+    TRY(c->t2_cnt.alloc((size_t)2 * T2_SETS * T2_CNT_STRIDE));
     HIP_TRY(hipMemsetAsync(c->t2_cnt, 0, (size_t)2 * T2_SETS * T2_CNT_STRIDE * sizeof(unsigned int), c->stream));
     c->t2_set = 0;
   }
@@ -3959,7 +3925,7 @@ static int launch_tick2(dust_ctx *c, const float *state, int n_steps, const floa
   f.ctr = c->ctr_dev;
   f.eps = eps_dev;
   f.eps_stride = (size_t)c->S * c->N * c->D;
-  f.params = (c->cfg.dim_p > 0 && c->params_dev) ? c->params_dev : nullptr;
+  f.params = c->cfg.dim_p > 0 ? params_cur(c) : nullptr;
   f.a_seq = c->a_seq;
   f.theta = c->theta;
   f.xq = c->t2_xq;
@@ -3968,9 +3934,9 @@ static int launch_tick2(dust_ctx *c, const float *state, int n_steps, const floa
   f.logmix = c->logmix;
   f.mixw = c->mixw;
   f.a_mat = c->a_mat;
-  f.opt_s0 = c->opt_s0;
-  f.opt_s1 = c->opt_s1;
-  f.opt_s2 = c->opt_s2;
+  f.opt_s0 = c->opt_s[0];
+  f.opt_s1 = c->opt_s[1];
+  f.opt_s2 = c->opt_s[2];
   f.costsT = c->costsT;
   f.grad_lik = c->grad_lik;
   f.grad_pri = c->grad_pri;
@@ -3985,7 +3951,7 @@ static int launch_tick2(dust_ctx *c, const float *state, int n_steps, const floa
   f.istar = c->istar;
   f.cnt = c->t2_cnt + (size_t)c->t2_set * T2_SETS * T2_CNT_STRIDE;
   f.zero_base = c->t2_cnt + (size_t)(1 - c->t2_set) * T2_SETS * T2_CNT_STRIDE;
-  f.status = reinterpret_cast<unsigned int *>(c->outblk + c->out_floats - 32);
+  f.status = out_status(c);
   f.tl = c->tl_dev ? c->tl_dev + (size_t)(c->n_tick2 & 1) * 1024 * 128 : nullptr;  // (diagnostic build: consecutive launches stamp alternate halves)
   if (c->t2_launch_mode && c->serve_host && do_forward) {  // closed-loop serving: outputs and the done word go straight to pinned host memory
     f.host_out = c->serve_host;
@@ -4125,8 +4091,7 @@ extern "C" int dust_comm_init(dust_ctx *c, const void *id, int rank, int world) 
   // the collectives gather IN PLACE in the context's [N][D] buffers: theta stays in one buffer from here on
   if (c->theta != c->theta_home) {
     TRY(d2d(c, c->theta_home, c->theta, (size_t)c->N * c->D * sizeof(float)));
-    c->theta_alt = c->theta;
-    c->theta = c->theta_home;
+    c->theta.swap(c->theta_alt);  // (the two blocks of the ping-pong: theta_alt held the home block)
   }
   if (c->graph_exec || c->graph_exec_alt) graph_drop(c);
   c->theta_pinned = true;
@@ -4468,7 +4433,7 @@ static void t2_queue_push(dust_ctx *c, const float *state4, int steps, bool fwd,
   r.mu_aliased = mu_aliased;
   r.cancelled = false;
   if (c->t2_params_host && c->cfg.dim_p > 0) r.params.assign(c->t2_params_host, c->t2_params_host + (size_t)steps * c->M * c->cfg.dim_p);
-  c->t2_queue->push_back(std::move(r));
+  c->t2_queue.push_back(std::move(r));
 }
 
 // stage the caller's inputs and try the persistent launch; *done = false -> nothing was launched
@@ -4486,14 +4451,14 @@ static int try_persistent(dust_ctx *c, const float *state, int n_steps, const fl
                             (c->have_sample ? 1ul : 0ul) * 1000003ul;
   if (c->persist_declined == key) return DUST_OK;
   HIP_TRY(hipSetDevice(c->cfg.device));
-  if (c->t2_queue->size() >= 4096) TRY(dust_sync(c));  // (an open-loop caller that never reads outputs: settle now and then)
+  if (c->t2_queue.size() >= 4096) TRY(dust_sync(c));  // (an open-loop caller that never reads outputs: settle now and then)
   TRY(upload_state_params(c, nullptr, params, n_steps));
   c->t2_params_host = params;
   const float *eps_dev = eps;
   c->noise_f16 = false;
   if (eps && !(flags & DUST_PTR_DEVICE)) {
     const size_t n = (size_t)n_steps * c->S * c->N * c->D;
-    TRY(ensure(&c->noise_stage, &c->noise_cap, n));
+    TRY(c->noise_stage.ensure(n));
     TRY(h2d(c, c->noise_stage, eps, n * sizeof(float)));
     eps_dev = c->noise_stage;
   }
@@ -4506,7 +4471,7 @@ static int try_persistent(dust_ctx *c, const float *state, int n_steps, const fl
 // synchronisation.  A timed-out in-kernel hand-off (persistent tick, or any of the launch-per-iteration fused forms) is an ERROR
 // here - the outputs of that tick are invalid and must not reach the plant.
 static int tick_outputs(dust_ctx *c, float *a_seq, float *p_weights) {
-  unsigned int *lf = reinterpret_cast<unsigned int *>(c->out_pinned + c->out_floats);
+  unsigned int *lf = out_pinned_words(c, c->out_floats);
   for (int pass = 0; pass < 2; ++pass) {
     HIP_TRY(hipMemcpyAsync(c->out_pinned, c->outblk, c->out_floats * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     lf[0] = lf[1] = lf[2] = 0u;
@@ -4515,7 +4480,7 @@ static int tick_outputs(dust_ctx *c, float *a_seq, float *p_weights) {
     if (c->iter_cnt)
       HIP_TRY(hipMemcpyAsync(lf + 2, c->iter_cnt + (size_t)2 * (2 * c->iter_tiles) * CNT_STRIDE, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    const unsigned int *st = reinterpret_cast<const unsigned int *>(c->out_pinned + c->out_floats - 32);
+    const unsigned int *st = out_pinned_words(c, c->out_floats - 32);
     if (st[0] && c->t2_inflight && c->t2_transactional) {  // the owner-computes kernel commits nothing when a wait gave up (tick2.hpp COMMIT): replayed below
       bool whole = false;
       TRY(t2_timed_out(c, &whole));
@@ -4524,7 +4489,7 @@ static int tick_outputs(dust_ctx *c, float *a_seq, float *p_weights) {
         return fail(DUST_ERR_HIP, "%s", T2_TORN_MSG);
       }
     } else if (st[0]) {
-      HIP_TRY(hipMemset(c->outblk + c->out_floats - 32, 0, 4));
+      HIP_TRY(hipMemset(out_status(c), 0, 4));
       c->t2_inflight = false;
       return handoff_timeout(c, "persistent tick kernel: a hand-off wait timed out (results of this tick are invalid); the device seems to be shared with another process: this context runs plain kernels from here on");
     }
@@ -4554,7 +4519,7 @@ static int t2_settle(dust_ctx *c, unsigned int aborts_now, bool *replayed) {
   const unsigned int n = aborts_now - c->t2_aborts_seen;
   c->t2_aborts_seen = aborts_now;
   std::vector<dust_ctx::T2Replay> q;
-  q.swap(*c->t2_queue);
+  q.swap(c->t2_queue);
   if (!n) return DUST_OK;
   // every one-launch tick behind the first one that did not start (or commit) aborted as well (`expect_aborts`): the last n entries
   if (n > q.size()) return fail(DUST_ERR_STATE, "%u one-launch tick(s) reported as not started, %zu on record", n, q.size());
@@ -4666,7 +4631,7 @@ static void graph_drop(dust_ctx *c) {
 static int serve_alloc(dust_ctx *c) {
   if (c->serve_host) return DUST_OK;
   // (the GPU polls the mailbox and the host polls the done word: fine-grained coherent memory whatever HIP_HOST_COHERENT says - ADVICE r5)
-  HIP_TRY(hipHostMalloc((void **)&c->serve_host, (c->out_floats + 64) * sizeof(float), hipHostMallocCoherent | hipHostMallocMapped));
+  TRY(c->serve_host.alloc(c->out_floats + 64, hipHostMallocCoherent | hipHostMallocMapped));
   memset(c->serve_host, 0, (c->out_floats + 64) * sizeof(float));
   return DUST_OK;
 }
@@ -4691,7 +4656,7 @@ static int serve_tick(dust_ctx *c, const float *state, float *a_seq, float *p_we
       serve_post(c, this_seq, 1u, state);
       c->armed = false;
       if (g_armed[dev] == c) g_armed[dev] = nullptr;
-      dust_ctx::T2Replay &r = c->t2_queue->back();
+      dust_ctx::T2Replay &r = c->t2_queue.back();
       for (int k = 0; k < 4; ++k) r.state[k] = k < c->ds ? state[k] : 0.f;
       was_armed = true;
       // a state that comes after the launch's bound may find it gone (it then reports "did not start" and is replayed below): a loop
@@ -4712,7 +4677,7 @@ static int serve_tick(dust_ctx *c, const float *state, float *a_seq, float *p_we
   *done = true;
   // the next tick, armed, behind this one (single tenant only: a chained launch of another context could stand behind it)
   const bool tenants = dev >= 0 && dev < DUST_MAX_DEV && g_live_ctx[dev].load() >= 2;
-  if (!tenants && c->serve_misses < 3 && c->serve_wait_ticks > 0 && c->t2_queue->size() < 4000) {
+  if (!tenants && c->serve_misses < 3 && c->serve_wait_ticks > 0 && c->t2_queue.size() < 4000) {
     bool d2 = false;
     c->t2_launch_mode = 2;
     c->t2_params_host = nullptr;
@@ -4756,9 +4721,9 @@ static int serve_tick(dust_ctx *c, const float *state, float *a_seq, float *p_we
     // count and the entry off together (dropped here, the next launch aborted on a count the host had never seen).  The
     // canceller writes these fields under the device's mutex, so the bookkeeping takes it too.
     std::lock_guard<std::mutex> lk(g_armed_mu[dev >= 0 && dev < DUST_MAX_DEV ? dev : 0]);
-    const bool tail_pending = c->armed || c->cancel_unsettled || (!c->t2_queue->empty() && c->t2_queue->back().cancelled);
+    const bool tail_pending = c->armed || c->cancel_unsettled || (!c->t2_queue.empty() && c->t2_queue.back().cancelled);
     const size_t keep = tail_pending ? 1u : 0u;
-    if (c->t2_queue->size() > keep) c->t2_queue->erase(c->t2_queue->begin(), c->t2_queue->end() - keep);
+    if (c->t2_queue.size() > keep) c->t2_queue.erase(c->t2_queue.begin(), c->t2_queue.end() - keep);
     if (!tail_pending) c->t2_inflight = false;
     c->n_served++;
     if (was_armed) c->n_armed_hit++;
@@ -4956,7 +4921,7 @@ extern "C" int dust_disco_step(dust_ctx *c, int strategy, int steps, const float
   }
   s.a_mat = c->a_mat;
   s.a_seq = c->a_seq;
-  TRY(ensure(&c->tmp, &c->tmp_cap, (size_t)steps * c->da));  // (dust_create sizes tmp for S * N floats: fewer than steps * da for a small set)
+  TRY(c->tmp.ensure((size_t)steps * c->da));  // (dust_create sizes tmp for S * N floats: fewer than steps * da for a small set)
   s.next = c->tmp;
   disco_step_kernel<<<1, 1024, c->D * sizeof(float), c->stream>>>(s);
   HIP_TRY(hipGetLastError());
@@ -4974,8 +4939,7 @@ extern "C" int dust_gather_buffers(dust_ctx *c, void **theta_all, void **score_a
   if (c->theta != c->theta_home) {
     HIP_TRY(hipSetDevice(c->cfg.device));
     TRY(d2d(c, c->theta_home, c->theta, (size_t)c->N * c->D * sizeof(float)));
-    c->theta_alt = c->theta;
-    c->theta = c->theta_home;
+    c->theta.swap(c->theta_alt);  // (the two blocks of the ping-pong: theta_alt held the home block)
   }
   if (c->graph_exec || c->graph_exec_alt) graph_drop(c);
   c->theta_pinned = true;
@@ -5164,7 +5128,7 @@ extern "C" int dust_device_noise_alloc(dust_ctx *c, size_t n, uint64_t seed, int
 }
 extern "C" int dust_device_free(dust_ctx *c, void *p) {
   if (!c) return fail(DUST_ERR_INVALID, "null ctx");
-  if (p) HIP_TRY(hipFree(p));
+  if (p) HIP_TRY(hipFree(p));  // (dust_device_noise_alloc's blocks only: what a DevBuf holds is never freed through a pointer taken from it)
   return DUST_OK;
 }
 
@@ -5277,16 +5241,16 @@ extern "C" int dust_debug_pack_lists(dust_ctx *c, int tile, int *n_units, int *j
     return DUST_OK;
   }
   std::vector<int> so((size_t)JS + 1);
-  HIP_TRY(hipMemcpy(so.data(), reinterpret_cast<int *>(c->pk.soff) + (size_t)tile * (JS + 1), so.size() * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(so.data(), c->pk.soff.get() + (size_t)tile * (JS + 1), so.size() * sizeof(int), hipMemcpyDeviceToHost));
   const int U = so[JS];
   *n_units = U;
   *js = JS;
   if (soff) memcpy(soff, so.data(), so.size() * sizeof(int));
   std::vector<int> uo((size_t)U + 1);
-  HIP_TRY(hipMemcpy(uo.data(), reinterpret_cast<int *>(c->pk.uoff) + (size_t)tile * (um + 1), uo.size() * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(uo.data(), c->pk.uoff.get() + (size_t)tile * (um + 1), uo.size() * sizeof(int), hipMemcpyDeviceToHost));
   if (uoff) memcpy(uoff, uo.data(), uo.size() * sizeof(int));
-  if (kidx && uo[U] > 0) HIP_TRY(hipMemcpy(kidx, reinterpret_cast<int *>(c->pk.idx) + (size_t)tile * um * 64, (size_t)uo[U] * sizeof(int), hipMemcpyDeviceToHost));
-  if (uq && U > 0) HIP_TRY(hipMemcpy(uq, reinterpret_cast<unsigned int *>(c->pk.uq) + (size_t)tile * um * 4, (size_t)U * 4 * sizeof(unsigned int), hipMemcpyDeviceToHost));
+  if (kidx && uo[U] > 0) HIP_TRY(hipMemcpy(kidx, c->pk.idx.get() + (size_t)tile * um * 64, (size_t)uo[U] * sizeof(int), hipMemcpyDeviceToHost));
+  if (uq && U > 0) HIP_TRY(hipMemcpy(uq, c->pk.uq.get() + (size_t)tile * um * 4, (size_t)U * 4 * sizeof(unsigned int), hipMemcpyDeviceToHost));
   return DUST_OK;
 }
 
@@ -5369,9 +5333,9 @@ extern "C" int dust_debug_philox(int kind, unsigned long long seed, const unsign
 // diagnostic build only (not part of include/dust_amd.h): s_memtime phase stamps of block 0 of the last launch of a kernel
 extern "C" int dust_debug_stamps(dust_ctx *c, int kernel_id, unsigned long long *out16) {
   if (!c->stamps_dev) {
-    HIP_TRY(hipMalloc((void **)&c->stamps_dev, 16 * DUST_K_COUNT * sizeof(unsigned long long)));
+    TRY(c->stamps_dev.alloc(16 * DUST_K_COUNT));
     HIP_TRY(hipMemset(c->stamps_dev, 0, 16 * DUST_K_COUNT * sizeof(unsigned long long)));
-    HIP_TRY(hipMalloc((void **)&c->tl_dev, 2048 * 128 * sizeof(unsigned long long)));  // (the tick kernel stamps 128 words per workgroup)
+    TRY(c->tl_dev.alloc(2048 * 128));  // (the tick kernel stamps 128 words per workgroup)
     HIP_TRY(hipMemset(c->tl_dev, 0, 2048 * 128 * sizeof(unsigned long long)));
     return DUST_OK;
   }
@@ -5391,21 +5355,19 @@ extern "C" int dust_debug_stamps(dust_ctx *c, int kernel_id, unsigned long long 
 struct dust_svmpc_batch {
   dust_ctx *c;
   int B;
-  float *theta, *mu, *a_mat;  // [B][N][D]
-  float *mixw, *logmix;       // [B][N]
-  int *alias;                 // [B]
-  uint32_t *ctr;              // [B][4]
-  uint64_t *seeds;            // [B]
-  float *opt_s[3];            // [B][N][D] or nullptr
-  float *acts;                // [B][S][N][D]
-  float *costs, *wts, *omg;   // [B][S][N]
-  float *score, *phi;         // [B][N][D]
-  float *logl, *logp, *eta, *a_mix, *pw;  // [B][N]
-  float *a_seq_out;           // [B][D]
-  float *eps, *params;        // staged inputs of a call
-  size_t eps_cap, params_cap;
-  float *plant, *rec;         // dust_svmpc_batch_episode: [B][P] true parameter rows; the records [T][B][ds], [T][B][da], [T][B][N]
-  size_t plant_cap, rec_cap;
+  DevBuf<float> theta, mu, a_mat;  // [B][N][D]
+  DevBuf<float> mixw, logmix;      // [B][N]
+  DevBuf<int> alias;               // [B]
+  DevBuf<uint32_t> ctr;            // [B][4]
+  DevBuf<uint64_t> seeds;          // [B]
+  DevBuf<float> opt_s[3];          // [B][N][D] or empty
+  DevBuf<float> acts;              // [B][S][N][D]
+  DevBuf<float> costs, wts, omg;   // [B][S][N]
+  DevBuf<float> score, phi;        // [B][N][D]
+  DevBuf<float> logl, logp, eta, a_mix, pw;  // [B][N]
+  DevBuf<float> a_seq_out;         // [B][D]
+  DevBuf<float> eps, params;       // staged inputs of a call
+  DevBuf<float> plant, rec;        // dust_svmpc_batch_episode: [B][P] true parameter rows; the records [T][B][ds], [T][B][da], [T][B][N]
   BatchInputs in;             // per-call inputs
   bool have_costs, have_forward, acts_kept;
 };
@@ -5441,13 +5403,9 @@ static void svb_free(dust_svmpc_batch *b) {
     (void)hipSetDevice(b->c->cfg.device);
     (void)hipStreamSynchronize(b->c->stream);
   }
-  void *dev[] = {b->theta, b->mu, b->a_mat, b->mixw, b->logmix, b->alias, b->ctr, b->seeds, b->opt_s[0], b->opt_s[1], b->opt_s[2], b->acts,
-                 b->costs, b->wts, b->omg, b->score, b->phi, b->logl, b->logp, b->eta, b->a_mix, b->pw, b->a_seq_out, b->eps, b->params, b->plant, b->rec};
-  for (void *p : dev)
-    if (p) (void)hipFree(p);
-  b->in.free();
-  if (b->c) dust_destroy(b->c);
-  delete b;
+  dust_ctx *inner = b->c;
+  delete b;  // the batch's own rows first, then the context they were allocated beside
+  if (inner) dust_destroy(inner);
 }
 
 // the batch around an inner context it takes over: buffers allocated, nothing filled yet
@@ -5458,17 +5416,17 @@ static int svb_alloc(dust_ctx *inner, int n_env, dust_svmpc_batch **out) {
   *out = b;
   const size_t B = (size_t)n_env, N = (size_t)inner->N, S = (size_t)inner->S, D = (size_t)inner->D;
   HIP_TRY(hipSetDevice(inner->cfg.device));
-  float **nd[] = {&b->theta, &b->mu, &b->a_mat, &b->score, &b->phi};
-  for (float **p : nd) TRY(dalloc(p, B * N * D));
-  float **nn[] = {&b->mixw, &b->logmix, &b->logl, &b->logp, &b->eta, &b->a_mix, &b->pw};
-  for (float **p : nn) TRY(dalloc(p, B * N));
-  float **sn[] = {&b->costs, &b->wts, &b->omg};
-  for (float **p : sn) TRY(dalloc(p, B * S * N));
-  TRY(dalloc(&b->acts, B * S * N * D));
-  TRY(dalloc(&b->a_seq_out, B * D));
-  TRY(dalloc(&b->alias, B));
-  TRY(dalloc(&b->ctr, B * 4));
-  TRY(dalloc(&b->seeds, B));
+  DevBuf<float> *nd[] = {&b->theta, &b->mu, &b->a_mat, &b->score, &b->phi};
+  for (auto p : nd) TRY(p->alloc(B * N * D));
+  DevBuf<float> *nn[] = {&b->mixw, &b->logmix, &b->logl, &b->logp, &b->eta, &b->a_mix, &b->pw};
+  for (auto p : nn) TRY(p->alloc(B * N));
+  DevBuf<float> *sn[] = {&b->costs, &b->wts, &b->omg};
+  for (auto p : sn) TRY(p->alloc(B * S * N));
+  TRY(b->acts.alloc(B * S * N * D));
+  TRY(b->a_seq_out.alloc(B * D));
+  TRY(b->alias.alloc(B));
+  TRY(b->ctr.alloc(B * 4));
+  TRY(b->seeds.alloc(B));
   TRY(optim_slots_alloc(inner->opt, b->opt_s, B * N * D));
   HIP_TRY(hipMemsetAsync(b->a_mix, 0, B * N * sizeof(float), inner->stream));
   return b->in.alloc(n_env);
@@ -5491,9 +5449,8 @@ extern "C" int dust_svmpc_batch_create(const dust_ctx *proto, int n_env, const u
     if (st == DUST_OK) st = spread(inner, B, b->mixw, inner->mixw, N * sizeof(float));
     if (st == DUST_OK) st = spread(inner, B, b->logmix, inner->logmix, N * sizeof(float));
     if (st == DUST_OK) st = spread(inner, B, b->ctr, inner->ctr_dev, 4 * sizeof(uint32_t));
-    const float *const ss[3] = {inner->opt_s0, inner->opt_s1, inner->opt_s2};
     for (int k = 0; k < 3 && st == DUST_OK; ++k)
-      if (b->opt_s[k] && ss[k]) st = spread(inner, B, b->opt_s[k], ss[k], ND * sizeof(float));
+      if (b->opt_s[k] && inner->opt_s[k]) st = spread(inner, B, b->opt_s[k], inner->opt_s[k], ND * sizeof(float));
     std::vector<int> al(B, inner->mu_aliased ? 1 : 0);
     if (st == DUST_OK) st = h2d(inner, b->alias, al.data(), B * sizeof(int));
     if (st == DUST_OK) st = batch_seeds_set(inner, B, seeds, b->seeds);
@@ -5642,7 +5599,7 @@ static int svb_call_check(const dust_svmpc_batch *b, const float *states, int n_
 // NULL (drawn on the device).  The copies wait for the stream: the caller owns the host buffers.
 // svb_stage_params: the parameter rows alone, `n` floats of them (a tick's [B][n_steps][M][P]; an episode's, for each of its periods)
 static int svb_stage_params(dust_svmpc_batch *b, const float *params, size_t n) {
-  TRY(ensure(&b->params, &b->params_cap, n));
+  TRY(b->params.ensure(n));
   return h2d(b->c, b->params, params, n * sizeof(float));
 }
 static int svb_stage(dust_svmpc_batch *b, int n_steps, const void *eps, const float *params, int flags, const float **eps_dev) {
@@ -5654,7 +5611,7 @@ static int svb_stage(dust_svmpc_batch *b, int n_steps, const void *eps, const fl
     if (flags & DUST_PTR_DEVICE) *eps_dev = static_cast<const float *>(eps);
     else {
       const size_t n = B * (size_t)n_steps * S * N * D;
-      TRY(ensure(&b->eps, &b->eps_cap, n));
+      TRY(b->eps.ensure(n));
       TRY(h2d(c, b->eps, eps, n * sizeof(float)));
       *eps_dev = b->eps;
     }
@@ -5851,11 +5808,11 @@ extern "C" int dust_svmpc_batch_episode(dust_svmpc_batch *b, const float *states
   HIP_TRY(hipSetDevice(c->cfg.device));
   if (params) TRY(svb_stage_params(b, params, T * B * (size_t)n_steps * M * P));
   if (plant_params) {
-    TRY(ensure(&b->plant, &b->plant_cap, B * P));
+    TRY(b->plant.ensure(B * P));
     TRY(h2d(c, b->plant, plant_params, B * P * sizeof(float)));
   }
   const size_t n_rec = T * B * (ds + da + (pw_out ? N : 0));
-  TRY(ensure(&b->rec, &b->rec_cap, n_rec));
+  TRY(b->rec.ensure(n_rec));
   SvbEpisode ep;
   ep.T = n_periods;
   ep.plant = plant_params ? b->plant : nullptr;

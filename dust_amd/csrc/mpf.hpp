@@ -1124,12 +1124,11 @@ struct dust_mpf {
   dust_mpf_config cfg;
   int Mp, P;
   hipStream_t stream;
-  float *x, *gn, *phi, *tmp;
-  size_t tmp_cap;
+  DevBuf<float> x, gn, phi, tmp;
   dust_optim_config opt;       // dust_mpf_set_optimizer(_ex); plain SGD at cfg.lr until then
   int opt_t;                   // steps taken so far
-  float *opt_s0, *opt_s1, *opt_s2;  // state slots [Mp][P] or nullptr
-  uint32_t *grid_bits;
+  DevBuf<float> opt_s[3];      // state slots [Mp][P] or empty
+  DevBuf<uint32_t> grid_bits;
   int nx, ny;
   float off_x, off_y;
   float prior_bwv[4];          // per parameter dimension; equal once update_prior(bw) has run (mpf.py:85)
@@ -1137,24 +1136,24 @@ struct dust_mpf {
   bool have_past;
   dust::SkidModel skid;     // DUST_MODEL_SKID_STEER: parameters and wheel-speed bounds (dust_mpf_set_skid_steer)
   dust::SkidLik skl_host;   // ... the likelihood's per-call constants (mpf_skid_prepare) and their device copy
-  dust::SkidLik *skl_dev;
+  DevBuf<dust::SkidLik> skl_dev;
   dust::CartModel cart;     // DUST_MODEL_CARTPOLE: the seven parameters (dust_mpf_set_cartpole; its cost fields stay unused)
   dust::CartLik cpl_host;   // ... the likelihood's per-call constants (mpf_cart_prepare) and their device copy
-  dust::CartLik *cpl_dev;
+  DevBuf<dust::CartLik> cpl_dev;
   // control-channel noise of the one-step prediction (model_cfg.ctrl_noise; particle.py:145-148 through likelihoods.py:30-46)
-  std::vector<float> *cz;   // recorded draws [n][da] (dust_mpf_set_ctrl_noise), consumed one per SVGD step
+  std::vector<float> cz;    // recorded draws [n][da] (dust_mpf_set_ctrl_noise), consumed one per SVGD step
   size_t cz_next;
-  std::mt19937_64 *rng;     // draws once the recorded ones are used up
-  float *act_seq;           // device: effective action per step of the current launch [steps][2]
-  int act_seq_cap;
+  std::mt19937_64 rng;      // draws once the recorded ones are used up (seeded on first use: rng_seeded)
+  bool rng_seeded;
+  DevBuf<float> act_seq;    // device: effective action per step of the current launch [steps][2]
   // the multi-workgroup form of the optimisation (mpf_optimize_grid_kernel): exchange buffers, counters, status; lazily allocated
-  float *gbuf;            // xg [2][Mp][P] | scg [2][Mp][P] | n2g [gsteps][Mp]
-  unsigned int *gcnt;     // counters (zeroed per launch) followed by the 4 status words
+  DevBuf<float> gbuf;     // xg [2][Mp][P] | scg [2][Mp][P] | n2g [gsteps][Mp]
+  DevBuf<unsigned int> gcnt;  // counters (zeroed per launch) followed by the 4 status words
   int gsteps;             // rows of n2g allocated
-  float *pbuf;            // data-polled form (experimental): particle pieces | score pieces
-  unsigned int *pcnt;     // ... its start counter and go word (monotonic over launches)
+  DevBuf<float> pbuf;     // data-polled form (experimental): particle pieces | score pieces
+  DevBuf<unsigned int> pcnt;  // ... its start counter and go word (monotonic over launches)
   unsigned int pseq;
-  float *hpin;            // pinned host staging: gradient norms [4096] + status words
+  PinBuf<float> hpin;     // pinned host staging: gradient norms [4096] + status words (unsigned, at hpin + 4096)
   bool grid_banned;       // a wait of the grid form timed out once (device shared with another process): single-workgroup kernel from then on
   long long n_grid, n_grid_fallback;
   // development switches and test hooks, read ONCE by dust_mpf_create (mpf_env_read): atoi of the value
@@ -1177,35 +1176,18 @@ static void mpf_env_read(dust_mpf *m) {
 }
 
 static DevModel mpf_dev_model(const dust_mpf *m) {
-  dust_ctx fake;
-  memset((void *)&fake, 0, sizeof fake);
-  fake.cfg = m->cfg.model_cfg;
-  fake.cfg.params_log_space = m->cfg.log_space;
-  fake.P = m->P;
-  fake.grid_bits = m->grid_bits;
-  fake.nx = m->nx;
-  fake.ny = m->ny;
-  fake.off_x = m->off_x;
-  fake.off_y = m->off_y;
-  return make_dev_model(&fake);
+  dust_config g = m->cfg.model_cfg;
+  g.params_log_space = m->cfg.log_space;
+  return make_dev_model(g, m->P, MapView{m->grid_bits, m->nx, m->ny, m->off_x, m->off_y});
 }
 
 extern "C" void dust_mpf_destroy(dust_mpf *m) {
   if (!m) return;
   (void)hipSetDevice(m->cfg.device);
   if (m->stream) (void)hipStreamSynchronize(m->stream);
-  float *fp[] = {m->x, m->gn, m->phi, m->tmp, m->opt_s0, m->opt_s1, m->opt_s2, m->gbuf, reinterpret_cast<float *>(m->gcnt), m->pbuf, reinterpret_cast<float *>(m->pcnt)};
-  for (float *p : fp)
-    if (p) (void)hipFree(p);
-  if (m->grid_bits) (void)hipFree(m->grid_bits);
-  if (m->hpin) (void)hipHostFree(m->hpin);
-  if (m->act_seq) (void)hipFree(m->act_seq);
-  if (m->skl_dev) (void)hipFree(m->skl_dev);
-  if (m->cpl_dev) (void)hipFree(m->cpl_dev);
-  if (m->stream) (void)hipStreamDestroy(m->stream);
-  delete m->cz;
-  delete m->rng;
-  delete m;
+  const hipStream_t stream = m->stream;
+  delete m;  // (memory first, then the stream it was used on - the order this function always had)
+  if (stream) (void)hipStreamDestroy(stream);
 }
 
 extern "C" int dust_mpf_create(const dust_mpf_config *cfg, const float *init_particles, const float *initial_obs, dust_mpf **out) {
@@ -1238,7 +1220,6 @@ extern "C" int dust_mpf_create(const dust_mpf_config *cfg, const float *init_par
   HIP_TRY(hipSetDevice(cfg->device));
   dust_mpf *m = new (std::nothrow) dust_mpf();
   if (!m) return fail(DUST_ERR_HIP, "out of host memory");
-  memset((void *)m, 0, sizeof *m);
   m->cfg = *cfg;
   m->opt = optim_plain(DUST_OPT_SGD, cfg->lr, 0.f, 0.f, 0.f);
   m->Mp = cfg->n_particles;
@@ -1246,9 +1227,9 @@ extern "C" int dust_mpf_create(const dust_mpf_config *cfg, const float *init_par
   mpf_env_read(m);
   *out = m;
   HIP_TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
-  TRY(dalloc(&m->x, (size_t)m->Mp * m->P));
-  TRY(dalloc(&m->phi, (size_t)m->Mp * m->P));
-  TRY(dalloc(&m->gn, (size_t)4096));
+  TRY(m->x.alloc((size_t)m->Mp * m->P));
+  TRY(m->phi.alloc((size_t)m->Mp * m->P));
+  TRY(m->gn.alloc((size_t)4096));
   HIP_TRY(hipMemcpyAsync(m->x, init_particles, (size_t)m->Mp * m->P * sizeof(float), hipMemcpyHostToDevice, m->stream));
   HIP_TRY(hipStreamSynchronize(m->stream));
   for (int p = 0; p < 4; ++p) m->prior_bwv[p] = cfg->init_bw;
@@ -1337,9 +1318,7 @@ extern "C" int dust_mpf_set_grid(dust_mpf *m, const float *grid, int nx, int ny,
     else if (grid[i] != 0.0f) return fail(DUST_ERR_UNSUPPORTED, "occupancy grid must be binary");
   }
   HIP_TRY(hipSetDevice(m->cfg.device));
-  if (m->grid_bits) HIP_TRY(hipFree(m->grid_bits));
-  m->grid_bits = nullptr;
-  TRY(dalloc(&m->grid_bits, words));
+  TRY(m->grid_bits.alloc(words));
   HIP_TRY(hipMemcpyAsync(m->grid_bits, bits.data(), words * 4, hipMemcpyHostToDevice, m->stream));
   HIP_TRY(hipStreamSynchronize(m->stream));
   m->nx = nx;
@@ -1363,16 +1342,12 @@ extern "C" int dust_mpf_set_optimizer_ex(dust_mpf *m, const dust_optim_config *o
   TRY(validate_optim(opt));
   HIP_TRY(hipSetDevice(m->cfg.device));
   const size_t n = (size_t)m->Mp * m->P;
-  float *slots[3] = {m->opt_s0, m->opt_s1, m->opt_s2};
   HIP_TRY(hipStreamSynchronize(m->stream));  // (slots about to be freed may still be read by queued work)
-  TRY(optim_slots_alloc(*opt, slots, n));
-  m->opt_s0 = slots[0];
-  m->opt_s1 = slots[1];
-  m->opt_s2 = slots[2];
+  TRY(optim_slots_alloc(*opt, m->opt_s, n));
   m->opt = *opt;
   m->cfg.lr = (float)opt->lr;
   m->opt_t = 0;
-  TRY(optim_restart(m->opt, slots, n, m->stream));
+  TRY(optim_restart(m->opt, m->opt_s, n, m->stream));
   return DUST_OK;
 }
 
@@ -1394,15 +1369,13 @@ extern "C" int dust_mpf_clone(const dust_mpf *src, dust_mpf **out) {
     TRY(dust_mpf_set_optimizer_ex(m, &src->opt));
     const size_t nb = (size_t)src->Mp * src->P * sizeof(float);
     HIP_TRY(hipStreamSynchronize(m->stream));
-    float *const ds[3] = {m->opt_s0, m->opt_s1, m->opt_s2};
-    const float *const ss[3] = {src->opt_s0, src->opt_s1, src->opt_s2};
     for (int k = 0; k < 3; ++k)
-      if (ss[k]) HIP_TRY(hipMemcpy(ds[k], ss[k], nb, hipMemcpyDeviceToDevice));
+      if (src->opt_s[k]) HIP_TRY(hipMemcpy(m->opt_s[k], src->opt_s[k], nb, hipMemcpyDeviceToDevice));
     m->opt_t = src->opt_t;
   }
   if (src->grid_bits) {
     const size_t words = ((size_t)src->nx * src->ny + 31) / 32;
-    TRY(dalloc(&m->grid_bits, words));
+    TRY(m->grid_bits.alloc(words));
     HIP_TRY(hipMemcpy(m->grid_bits, src->grid_bits, words * 4, hipMemcpyDeviceToDevice));
     m->nx = src->nx;
     m->ny = src->ny;
@@ -1430,21 +1403,17 @@ static int mpf_noisy_actions(dust_mpf *m, int n_steps, const float **dev) {
   *dev = nullptr;
   const dust_config &g = m->cfg.model_cfg;
   if (g.model != DUST_MODEL_PARTICLE || !g.ctrl_noise || (g.dyn_std[0] == 0.f && g.dyn_std[1] == 0.f) || n_steps < 1) return DUST_OK;
-  if (!m->act_seq || m->act_seq_cap < n_steps) {
-    if (m->act_seq) HIP_TRY(hipFree(m->act_seq));
-    m->act_seq = nullptr;
-    m->act_seq_cap = std::max(n_steps, 64);
-    TRY(dalloc(&m->act_seq, (size_t)2 * m->act_seq_cap));
-  }
+  if (m->act_seq.cap() < (size_t)2 * n_steps) TRY(m->act_seq.alloc((size_t)2 * std::max(n_steps, 64)));
   std::vector<float> h((size_t)2 * n_steps);
   for (int it = 0; it < n_steps; ++it)
     for (int d = 0; d < 2; ++d) {
       float z;
-      if (m->cz && m->cz_next < m->cz->size()) {
-        z = (*m->cz)[m->cz_next++];
+      if (m->cz_next < m->cz.size()) {
+        z = m->cz[m->cz_next++];
       } else {
-        if (!m->rng) m->rng = new std::mt19937_64(g.seed ^ 0x6d70666e6f697365ull);
-        z = std::normal_distribution<float>(0.f, 1.f)(*m->rng);
+        if (!m->rng_seeded) m->rng.seed(g.seed ^ 0x6d70666e6f697365ull);
+        m->rng_seeded = true;
+        z = std::normal_distribution<float>(0.f, 1.f)(m->rng);
       }
       const float nz = g.dyn_std[d] * z;
       h[(size_t)2 * it + d] = m->past_action[d] + nz;
@@ -1459,10 +1428,9 @@ extern "C" int dust_mpf_set_ctrl_noise(dust_mpf *m, const float *z, int n) {
   if (!m) return fail(DUST_ERR_INVALID, "null mpf");
   if (m->cfg.model_cfg.model != DUST_MODEL_PARTICLE || !m->cfg.model_cfg.ctrl_noise)
     return fail(DUST_ERR_STATE, "control noise belongs to a Particle(deterministic=False) model (model_cfg.ctrl_noise)");
-  if (!m->cz) m->cz = new std::vector<float>();
-  m->cz->clear();
+  m->cz.clear();
   m->cz_next = 0;
-  if (z && n > 0) m->cz->assign(z, z + (size_t)n * m->cfg.dim_a);
+  if (z && n > 0) m->cz.assign(z, z + (size_t)n * m->cfg.dim_a);
   return DUST_OK;
 }
 
@@ -1493,7 +1461,7 @@ static void mpf_skid_lik(const dust_mpf *m, const float *past_action, const floa
   k.dtd = m->cfg.model_cfg.dt;
 }
 static int mpf_skid_prepare(dust_mpf *m, const dust::SkidLik **dev) {
-  if (!m->skl_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->skl_dev), sizeof(dust::SkidLik)));
+  if (!m->skl_dev) TRY(m->skl_dev.alloc(1));
   dust::SkidLik &k = m->skl_host;
   mpf_skid_lik(m, m->past_action, m->past_obs, m->loc, k);
   HIP_TRY(hipMemcpyAsync(m->skl_dev, &k, sizeof k, hipMemcpyHostToDevice, m->stream));
@@ -1530,7 +1498,7 @@ static void mpf_cart_lik(const dust_mpf *m, const float *past_action, const floa
   k.dtd = m->cfg.model_cfg.dt;
 }
 static int mpf_cart_prepare(dust_mpf *m, const dust::CartLik **dev) {
-  if (!m->cpl_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->cpl_dev), sizeof(dust::CartLik)));
+  if (!m->cpl_dev) TRY(m->cpl_dev.alloc(1));
   dust::CartLik &k = m->cpl_host;
   mpf_cart_lik(m, m->past_action, m->past_obs, m->loc, k);
   HIP_TRY(hipMemcpyAsync(m->cpl_dev, &k, sizeof k, hipMemcpyHostToDevice, m->stream));
@@ -1606,9 +1574,9 @@ static int mpf_launch(dust_mpf *m, float bw, float lr, int n_steps, float *gn_de
   a.phi_out = phi_dev;
   if (optimise) {
     a.opt = m->opt;  // (its lr is the lr passed, m->cfg.lr, kept in double)
-    a.opt_s0 = m->opt_s0;
-    a.opt_s1 = m->opt_s1;
-    a.opt_s2 = m->opt_s2;
+    a.opt_s0 = m->opt_s[0];
+    a.opt_s1 = m->opt_s[1];
+    a.opt_s2 = m->opt_s[2];
   } else {  // the bare phi evaluation takes no step
     a.opt = optim_plain(DUST_OPT_SGD, lr, 0.f, 0.f, 0.f);
   }
@@ -1618,15 +1586,15 @@ static int mpf_launch(dust_mpf *m, float bw, float lr, int n_steps, float *gn_de
     const int NP = (m->P + 1) / 2, NX = NP + 1;
     const size_t fx = (size_t)2 * m->Mp * NX * 4, fs = (size_t)2 * m->Mp * NP * 4;  // floats
     if (!m->pbuf) {
-      TRY(dalloc(&m->pbuf, fx + fs));
+      TRY(m->pbuf.alloc(fx + fs));
       HIP_TRY(hipMemsetAsync(m->pbuf, 0, (fx + fs) * sizeof(float), m->stream));  // (tag 0 is never waited for)
     }
     if (!m->pcnt) {
-      TRY(dalloc(&m->pcnt, (size_t)2 * MPF_G_LINE));
+      TRY(m->pcnt.alloc((size_t)2 * MPF_G_LINE));
       HIP_TRY(hipMemsetAsync(m->pcnt, 0, (size_t)2 * MPF_G_LINE * sizeof(unsigned int), m->stream));
     }
     if (!m->gcnt) {
-      TRY(dalloc(&m->gcnt, (size_t)MPF_GCNT_WORDS + 4));
+      TRY(m->gcnt.alloc((size_t)MPF_GCNT_WORDS + 4));
       HIP_TRY(hipMemsetAsync(m->gcnt, 0, ((size_t)MPF_GCNT_WORDS + 4) * sizeof(unsigned int), m->stream));
     }
     MpfPollArgs g;
@@ -1651,13 +1619,11 @@ static int mpf_launch(dust_mpf *m, float bw, float lr, int n_steps, float *gn_de
   if (grid) {
     const size_t np = (size_t)m->Mp * m->P;
     if (!m->gbuf || m->gsteps < n_steps) {
-      if (m->gbuf) HIP_TRY(hipFree(m->gbuf));
-      m->gbuf = nullptr;
       m->gsteps = std::max(n_steps, 32);
-      TRY(dalloc(&m->gbuf, 4 * np + (size_t)m->gsteps * m->Mp));
+      TRY(m->gbuf.alloc(4 * np + (size_t)m->gsteps * m->Mp));
     }
     if (!m->gcnt) {
-      TRY(dalloc(&m->gcnt, (size_t)MPF_GCNT_WORDS + 4));
+      TRY(m->gcnt.alloc((size_t)MPF_GCNT_WORDS + 4));
       HIP_TRY(hipMemsetAsync(m->gcnt, 0, ((size_t)MPF_GCNT_WORDS + 4) * sizeof(unsigned int), m->stream));
     }
     HIP_TRY(hipMemsetAsync(m->gcnt, 0, (size_t)MPF_GCNT_WORDS * sizeof(unsigned int), m->stream));
@@ -1702,7 +1668,7 @@ extern "C" int dust_mpf_optimize(dust_mpf *m, const float *action, const float *
   TRY(mpf_noisy_actions(m, n_steps, &acts));
   TRY(mpf_launch(m, bw, m->cfg.lr, n_steps, m->gn, nullptr, true, grid, acts));
   const bool want_gn = grad_norms && n_steps > 0;
-  if (!m->hpin) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&m->hpin), (4096 + 8) * sizeof(float), hipHostMallocDefault));
+  if (!m->hpin) TRY(m->hpin.alloc(4096 + 8, hipHostMallocDefault));
   bool gn_read = false;
   if (grid) {  // did the grid form start, and did it commit?  (tick2.hpp's protocol; this call is synchronous anyway)
     // status and gradient norms come back through pinned memory behind ONE synchronisation
@@ -1812,7 +1778,7 @@ extern "C" int dust_mpf_get_prior(dust_mpf *m, float *means, float *bw) {
 extern "C" int dust_mpf_prior_sample(dust_mpf *m, int n, uint64_t seed, float *samples) {
   if (!m || !samples || n < 1) return fail(DUST_ERR_INVALID, "bad argument");
   HIP_TRY(hipSetDevice(m->cfg.device));
-  TRY(ensure(&m->tmp, &m->tmp_cap, (size_t)n * m->P));
+  TRY(m->tmp.ensure((size_t)n * m->P));
   mpf_sample_kernel<<<(n + 255) / 256, 256, 0, m->stream>>>(m->x, m->Mp, m->P, mpf_bw(m), seed, n, m->tmp);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(samples, m->tmp, (size_t)n * m->P * sizeof(float), hipMemcpyDeviceToHost, m->stream));
@@ -1822,7 +1788,7 @@ extern "C" int dust_mpf_prior_sample(dust_mpf *m, int n, uint64_t seed, float *s
 extern "C" int dust_mpf_prior_log_prob(dust_mpf *m, int n, const float *x, float *log_prob) {
   if (!m || !x || !log_prob || n < 1) return fail(DUST_ERR_INVALID, "bad argument");
   HIP_TRY(hipSetDevice(m->cfg.device));
-  TRY(ensure(&m->tmp, &m->tmp_cap, (size_t)n * (m->P + 1)));
+  TRY(m->tmp.ensure((size_t)n * (m->P + 1)));
   HIP_TRY(hipMemcpyAsync(m->tmp, x, (size_t)n * m->P * sizeof(float), hipMemcpyHostToDevice, m->stream));
   mpf_log_prob_kernel<<<(n + 255) / 256, 256, 0, m->stream>>>(m->tmp, m->x, n, m->Mp, m->P, mpf_bw(m), m->tmp + (size_t)n * m->P);
   HIP_TRY(hipGetLastError());
@@ -1837,7 +1803,7 @@ extern "C" int dust_mpf_sigma_points(dust_mpf *m, float scale, float *out) {
   if (!(scale > 0.f)) return fail(DUST_ERR_INVALID, "the sigma-point scale lambda + n must be > 0, got %g", (double)scale);
   HIP_TRY(hipSetDevice(m->cfg.device));
   const size_t n = (size_t)(2 * m->P + 1) * m->P;
-  TRY(ensure(&m->tmp, &m->tmp_cap, n));
+  TRY(m->tmp.ensure(n));
   mpf_sigma_points_kernel<<<1, 256, 0, m->stream>>>(m->x, m->Mp, m->P, mpf_bw(m), scale, 1, m->tmp);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, m->tmp, n * sizeof(float), hipMemcpyDeviceToHost, m->stream));
@@ -1852,8 +1818,8 @@ extern "C" int dust_mpf_silverman(dust_mpf *m, float *bw) {
   HIP_TRY(hipSetDevice(m->cfg.device));
   const int n = m->Mp * m->P;
   if (n > 4096) return fail(DUST_ERR_UNSUPPORTED, "Silverman's rule on the device takes up to 4096 pooled values (%d particles x %d parameters)", m->Mp, m->P);
-  if (!m->hpin) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&m->hpin), (4096 + 8) * sizeof(float), hipHostMallocDefault));
-  TRY(ensure(&m->tmp, &m->tmp_cap, 4));
+  if (!m->hpin) TRY(m->hpin.alloc(4096 + 8, hipHostMallocDefault));
+  TRY(m->tmp.ensure(4));
   mpf_silverman_kernel<<<1, 1024, (size_t)n * sizeof(float), m->stream>>>(m->x, n, m->cfg.bw_scale, m->tmp);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(m->hpin + 4096 + 4, m->tmp, sizeof(float), hipMemcpyDeviceToHost, m->stream));
@@ -1946,7 +1912,7 @@ extern "C" int dust_dual_tick(dust_ctx *c, dust_mpf *m, const float *state, cons
   TRY(dual_filter_update(m, action_prev, state, bw_in, mpf_steps, bw_used));
   TRY(settle_pending(c));
   const int n = n_steps * c->M;
-  TRY(ensure(&c->params_dev, &c->params_cap, (size_t)n * c->P));
+  TRY(c->params_dev.ensure((size_t)n * c->P));
   // (sigma points: the same 2P + 1 points for every SVGD iteration - MultiDISCO._sigma_rollout recomputes them per call; seed unused)
   if (c->mw_dev) dust::mpf_sigma_points_kernel<<<1, 256, 0, c->stream>>>(m->x, m->Mp, m->P, mpf_bw(m), c->sigma_scale, n_steps, c->params_dev);
   else dust::mpf_sample_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(m->x, m->Mp, m->P, mpf_bw(m), seed, n, c->params_dev);
@@ -1985,7 +1951,7 @@ extern "C" int dust_amppi_dual_tick(dust_ctx *c, dust_mpf *m, const float *state
   TRY(settle_pending(c));
   const int P = m->P;
   const size_t prows = sigma ? (size_t)c->M : (shared ? (size_t)1 : (size_t)c->S);
-  if (sigma || shared || params_out) TRY(ensure(&c->params_dev, &c->params_cap, prows * P));
+  if (sigma || shared || params_out) TRY(c->params_dev.ensure(prows * P));
   int st;
   if (sigma || shared) {
     if (sigma) dust::mpf_sigma_points_kernel<<<1, 256, 0, c->stream>>>(m->x, m->Mp, P, mpf_bw(m), c->sigma_scale, 1, c->params_dev);
@@ -2025,12 +1991,11 @@ extern "C" int dust_amppi_dual_tick(dust_ctx *c, dust_mpf *m, const float *state
 struct dust_mpf_batch {
   dust_mpf *m;
   int B;
-  float *x;            // [B][Mp][P]
-  float *opt_s[3];     // [B][Mp][P] or nullptr
-  float *bw;           // [B] the bandwidth of the last update
-  float *prior_bwv;    // [B][4]
-  float *gn;           // [B][n_steps] of the last update
-  size_t gn_cap;
+  DevBuf<float> x;          // [B][Mp][P]
+  DevBuf<float> opt_s[3];   // [B][Mp][P] or empty
+  DevBuf<float> bw;         // [B] the bandwidth of the last update
+  DevBuf<float> prior_bwv;  // [B][4]
+  DevBuf<float> gn;         // [B][n_steps] of the last update
   std::vector<float> loc, past_obs, past_action;  // [B][5], [B][5], [B][2]
   std::vector<unsigned char> have_past;
   std::vector<int> opt_t;
@@ -2048,8 +2013,12 @@ static size_t mpfb_off_lik(int B) { return mpfb_off_seeds(B) + (size_t)B * sizeo
 static size_t mpfb_off_mask(const dust_mpf_batch *mb) { return mpfb_off_lik(mb->B) + (size_t)mb->B * mpfb_lik_bytes(mb->m); }
 static size_t mpfb_in_bytes(const dust_mpf_batch *mb) { return mpfb_off_mask(mb) + (size_t)mb->B; }
 // where the kernels find the mask a call has staged (nullptr: the call had none - everybody is active), and the prior seeds
-static const unsigned char *mpfb_mask_dev(const dust_mpf_batch *mb, const unsigned char *active) { return active ? mb->in.dev + mpfb_off_mask(mb) : nullptr; }
-static const uint64_t *mpfb_seeds_dev(const dust_mpf_batch *mb) { return reinterpret_cast<const uint64_t *>(mb->in.dev + mpfb_off_seeds(mb->B)); }
+static const unsigned char *mpfb_mask_dev(const dust_mpf_batch *mb, const unsigned char *active) { return active ? mb->in.dev.get() + mpfb_off_mask(mb) : nullptr; }
+static const uint64_t *mpfb_seeds_dev(const dust_mpf_batch *mb) { return reinterpret_cast<const uint64_t *>(mb->in.dev.get() + mpfb_off_seeds(mb->B)); }
+// the typed rows of the stage's bytes (base: a host slot or the device copy): MpfEnvIn [B] in front, SkidLik or CartLik [B], by the model, behind the seeds
+static dust::MpfEnvIn *mpfb_in_view(unsigned char *base) { return reinterpret_cast<dust::MpfEnvIn *>(base); }
+template <class L>
+static L *mpfb_lik_view(unsigned char *base, int B) { return reinterpret_cast<L *>(base + mpfb_off_lik(B)); }
 
 static void mpfb_free(dust_mpf_batch *mb) {
   if (!mb) return;
@@ -2058,13 +2027,11 @@ static void mpfb_free(dust_mpf_batch *mb) {
     if (mb->ev_ext) (void)hipEventSynchronize(mb->ev_ext);
     (void)hipStreamSynchronize(mb->m->stream);
   }
-  void *dev[] = {mb->x, mb->opt_s[0], mb->opt_s[1], mb->opt_s[2], mb->bw, mb->prior_bwv, mb->gn};
-  for (void *p : dev)
-    if (p) (void)hipFree(p);
-  mb->in.free();
-  if (mb->ev_ext) (void)hipEventDestroy(mb->ev_ext);
-  if (mb->m) dust_mpf_destroy(mb->m);
-  delete mb;
+  dust_mpf *inner = mb->m;
+  const hipEvent_t ev = mb->ev_ext;
+  delete mb;  // the batch's own rows first, then its event and the filter
+  if (ev) (void)hipEventDestroy(ev);
+  if (inner) dust_mpf_destroy(inner);
 }
 
 // the batch around a filter it takes over: buffers allocated, nothing filled yet
@@ -2075,12 +2042,12 @@ static int mpfb_alloc(dust_mpf *inner, int n_env, dust_mpf_batch **out) {
   *out = mb;
   const size_t B = (size_t)n_env, np = (size_t)inner->Mp * inner->P;
   HIP_TRY(hipSetDevice(inner->cfg.device));
-  TRY(dalloc(&mb->x, B * np));
-  float *const slots[3] = {inner->opt_s0, inner->opt_s1, inner->opt_s2};
+  TRY(mb->x.alloc(B * np));
+  const DevBuf<float> *const slots = inner->opt_s;
   for (int k = 0; k < 3; ++k)
-    if (slots[k]) TRY(dalloc(&mb->opt_s[k], B * np));
-  TRY(dalloc(&mb->bw, B));
-  TRY(dalloc(&mb->prior_bwv, B * 4));
+    if (slots[k]) TRY(mb->opt_s[k].alloc(B * np));
+  TRY(mb->bw.alloc(B));
+  TRY(mb->prior_bwv.alloc(B * 4));
   HIP_TRY(hipMemset(mb->bw, 0, B * sizeof(float)));
   TRY(mb->in.alloc(mpfb_in_bytes(mb)));
   HIP_TRY(hipEventCreateWithFlags(&mb->ev_ext, hipEventDisableTiming));
@@ -2127,7 +2094,7 @@ extern "C" int dust_mpf_batch_create(const dust_mpf *proto, int n_env, dust_mpf_
   int st = mpfb_alloc(inner, n_env, &mb);
   if (st == DUST_OK) {
     const size_t np = (size_t)inner->Mp * inner->P;
-    float *const slots[3] = {inner->opt_s0, inner->opt_s1, inner->opt_s2};
+    const DevBuf<float> *const slots = inner->opt_s;
     std::vector<float> pb((size_t)n_env * 4);
     for (int e = 0; e < n_env && st == DUST_OK; ++e) {
       if (hipMemcpy(mb->x + (size_t)e * np, inner->x, np * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess) st = fail(DUST_ERR_HIP, "hipMemcpy failed");
@@ -2267,7 +2234,7 @@ static int mpfb_enqueue(dust_mpf_batch *mb, hipStream_t stream, const bool updat
   const int B = mb->B, ds = m->cfg.dim_s, da = m->cfg.dim_a, model = m->cfg.model_cfg.model;
   unsigned char *hb;
   TRY(mb->in.next(&hb));
-  dust::MpfEnvIn *in = reinterpret_cast<dust::MpfEnvIn *>(hb);
+  dust::MpfEnvIn *in = mpfb_in_view(hb);
   if (seeds) memcpy(hb + mpfb_off_seeds(B), seeds, (size_t)B * sizeof(uint64_t));
   if (active) memcpy(hb + mpfb_off_mask(mb), active, (size_t)B);
   if (update) {
@@ -2294,8 +2261,8 @@ static int mpfb_enqueue(dust_mpf_batch *mb, hipStream_t stream, const bool updat
       in[e].past_action[0] = pa[0];
       in[e].past_action[1] = pa[1];
       in[e].t0 = w.opt_t[e];
-      if (model == DUST_MODEL_SKID_STEER) mpf_skid_lik(m, pa, past, loc, reinterpret_cast<dust::SkidLik *>(hb + mpfb_off_lik(B))[e]);
-      if (model == DUST_MODEL_CARTPOLE) mpf_cart_lik(m, pa, past, loc, reinterpret_cast<dust::CartLik *>(hb + mpfb_off_lik(B))[e]);
+      if (model == DUST_MODEL_SKID_STEER) mpf_skid_lik(m, pa, past, loc, mpfb_lik_view<dust::SkidLik>(hb, B)[e]);
+      if (model == DUST_MODEL_CARTPOLE) mpf_cart_lik(m, pa, past, loc, mpfb_lik_view<dust::CartLik>(hb, B)[e]);
       if (on) w.opt_t[e] += n_steps;
     }
   }
@@ -2307,12 +2274,12 @@ static int mpfb_enqueue(dust_mpf_batch *mb, hipStream_t stream, const bool updat
   const unsigned char *mask = mpfb_mask_dev(mb, active);
   const bool cart = model == DUST_MODEL_CARTPOLE;
   if (model == DUST_MODEL_SKID_STEER) {
-    dust::mpf_lik_angle_batch_kernel<dust::SkidLik><<<(B + 255) / 256, 256, 0, stream>>>(reinterpret_cast<dust::SkidLik *>(mb->in.dev + mpfb_off_lik(B)), B, mask);
+    dust::mpf_lik_angle_batch_kernel<dust::SkidLik><<<(B + 255) / 256, 256, 0, stream>>>(mpfb_lik_view<dust::SkidLik>(mb->in.dev.get(), B), B, mask);
     HIP_TRY(hipGetLastError());
     mb->n_launch++;
   }
   if (cart) {
-    dust::mpf_lik_angle_batch_kernel<dust::CartLik><<<(B + 255) / 256, 256, 0, stream>>>(reinterpret_cast<dust::CartLik *>(mb->in.dev + mpfb_off_lik(B)), B, mask);
+    dust::mpf_lik_angle_batch_kernel<dust::CartLik><<<(B + 255) / 256, 256, 0, stream>>>(mpfb_lik_view<dust::CartLik>(mb->in.dev.get(), B), B, mask);
     HIP_TRY(hipGetLastError());
     mb->n_launch++;
   }
@@ -2334,13 +2301,13 @@ static int mpfb_enqueue(dust_mpf_batch *mb, hipStream_t stream, const bool updat
   a.opt_s0 = mb->opt_s[0];
   a.opt_s1 = mb->opt_s[1];
   a.opt_s2 = mb->opt_s[2];
-  k.in = reinterpret_cast<const dust::MpfEnvIn *>(mb->in.dev);
+  k.in = mpfb_in_view(mb->in.dev.get());
   k.prior_bwv = mb->prior_bwv;
   k.bw = mb->bw;
   k.bw_fixed = bw > 0.f ? bw : 0.f;
   k.gn_stride = n_steps;
-  k.skl = reinterpret_cast<const dust::SkidLik *>(mb->in.dev + mpfb_off_lik(B));
-  k.cpl = reinterpret_cast<const dust::CartLik *>(mb->in.dev + mpfb_off_lik(B));
+  k.skl = mpfb_lik_view<dust::SkidLik>(mb->in.dev.get(), B);
+  k.cpl = mpfb_lik_view<dust::CartLik>(mb->in.dev.get(), B);
   k.active = mask;
   // (P up to the model's parameter count: mpfb_limits has refused the rest)
   int st = DUST_OK;
@@ -2363,7 +2330,7 @@ static int mpfb_enqueue(dust_mpf_batch *mb, hipStream_t stream, const bool updat
 }
 
 // room for grad_norms [B][n_steps] (a reallocation frees behind the device's queued work)
-static int mpfb_gn_room(dust_mpf_batch *mb, int n_steps) { return ensure(&mb->gn, &mb->gn_cap, (size_t)mb->B * (size_t)(n_steps > 0 ? n_steps : 1)); }
+static int mpfb_gn_room(dust_mpf_batch *mb, int n_steps) { return mb->gn.ensure((size_t)mb->B * (size_t)(n_steps > 0 ? n_steps : 1)); }
 
 // B x dust_mpf_optimize in one launch (plus one for Silverman's rule when bw <= 0, plus one for the heading / angle terms of a skid-steer /
 // cart-pole filter): environment b computes what a lone filter under DUST_MPF_GRID=0 computes on its inputs, bit for bit.
@@ -2471,7 +2438,7 @@ extern "C" int dust_amppi_dual_batch_tick(dust_amppi_batch *b, dust_mpf_batch *m
   const size_t prows = sigma ? (size_t)c->M : (shared ? (size_t)1 : S);
   MpfbRows rows;
   TRY(dual_batch_filters(c, mb, states, actions_prev, mpf_steps, mpf_bw, prior_seeds, active, rows, [&]() -> int {
-    return sigma || shared || params_out ? ensure(&b->params, &b->params_cap, B * prows * P) : DUST_OK;
+    return sigma || shared || params_out ? b->params.ensure(B * prows * P) : DUST_OK;
   }));
   const unsigned char *mask = mpfb_mask_dev(mb, active);
   int st;
@@ -2518,7 +2485,7 @@ extern "C" int dust_svmpc_dual_batch_tick(dust_svmpc_batch *b, dust_mpf_batch *m
   const float *eps_dev;
   MpfbRows rows;
   TRY(dual_batch_filters(c, mb, states, actions_prev, mpf_steps, mpf_bw, prior_seeds, active, rows, [&]() -> int {
-    if (params_out) TRY(ensure(&b->params, &b->params_cap, (size_t)b->B * prow));
+    if (params_out) TRY(b->params.ensure((size_t)b->B * prow));
     return svb_stage(b, n_steps, eps, nullptr, flags, &eps_dev);
   }));
   dust::SvbPrior pr;
