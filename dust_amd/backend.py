@@ -935,6 +935,35 @@ class SvmpcBatch(_BatchHandle):
                                                     _p(a_seq), _p(pw), _p(pout), _p(bw)))
         return a_seq, pw, pout, bw
 
+    def dual_episode(self, mpf, states, n_periods, n_steps, actions_prev=None, mpf_steps=20, mpf_bw=None, seeds=None, plant_params=None,
+                     active=None, want_pw=True):
+        """n_periods control periods of the DuSt-MPC loop for every active environment in one C call (dust_svmpc_dual_batch_episode): per
+        period the filters' update for (a_{t-1}, x_t) - period 0: actions_prev, skipped when it is None -, the tick of dual_tick() with
+        the noise drawn on the device, the plant's step with the first action of the chosen sequence under the environment's true
+        parameters; no host round trip between periods.  states [B, ds]; seeds [T, B]: period t's Philox keys; plant_params [B, P] or
+        None (nominal plants).  -> (states [T, B, ds] after every step, actions [T, B, da], p_weights [T, B, N] or None, bw [T, B],
+        a_seq [B, H, da] of the last period); the rows of inactive environments are NaN.  The pair (actions[-1], states[-1]) is still
+        to be folded into the filters: hand it to the next call."""
+        B, T = self.B, int(n_periods)
+        st = None if states is None else _f(states, (B, self.ds))  # (None: the library refuses)
+        ap = None if actions_prev is None else _f(actions_prev, (B, self.da))
+        rows = max(T, 0)  # (n_periods < 1: the library refuses before it reads or writes anything)
+        if seeds is not None and np.shape(seeds) != (rows, B):
+            raise ValueError("seeds has shape %s, the call reads %s" % (np.shape(seeds), (rows, B)))
+        sd, sp = _seeds(seeds, rows * B)
+        pl = None
+        if plant_params is not None:
+            pl = _f(plant_params)
+            if pl.shape != (B, max(self.P, 1)):
+                raise ValueError("plant_params has shape %s, the call reads %s" % (pl.shape, (B, max(self.P, 1))))
+        _, mp = _mask(active, B)
+        xs, acts, bw, a_seq = (np.full(sh, np.nan, np.float32) for sh in ((rows, B, self.ds), (rows, B, self.da), (rows, B), (B, self.H, self.da)))
+        pw = np.full((rows, B, self.N), np.nan, np.float32) if want_pw else None
+        L.check(L.load().dust_svmpc_dual_batch_episode(self._h, mpf._h, _p(st), _p(ap), T, int(n_steps), int(mpf_steps),
+                                                       float(-1.0 if mpf_bw is None else mpf_bw), sp, _p(pl), 0, mp,
+                                                       _p(xs), _p(acts), _p(pw), _p(bw), _p(a_seq)))
+        return xs, acts, pw, bw, a_seq
+
 
 class MpfBatch(_BatchHandle):
     """B dynamics filters of one configuration, updated in one launch (dust_mpf_batch_*): per environment its particles, optimiser

@@ -19,6 +19,7 @@ with recorded draws (`draw_source`) stays on the unfused path.  `serve=True` tur
 a filter-coupled controller samples dynamics parameters per tick, which serving does not take - then it is a no-op)."""
 import copy
 
+import numpy as np
 import torch
 
 
@@ -455,3 +456,52 @@ class BatchDualSVMPC(_BatchDual):
         new_states = plant(states, actions)
         self.step(actions, new_states)
         return actions, new_states, pw
+
+    # -- simulations.py:104-138 for every environment, the plants on the device
+    def run_episodes(self, states, n_periods, plant_params=None, n_steps=None, active=None):
+        """`n_periods` control periods of every active environment in one C call (dust_svmpc_dual_batch_episode): what `n_periods` calls
+        of tick() run, with the plants stepped on the device by the model's own step under the environment's TRUE parameters
+        `plant_params` [B, P] (the columns and the space of the filters' particles; None: the nominal model), without process or
+        observation noise - no host round trip between the periods.  states [B, ds]: where the piece starts; a noted update is period
+        0's, with `states` as its observation, as in forward().  Period t draws under `prior_keys(_t + 1 + t)`.
+        -> (states [T, B, ds] after every step, actions [T, B, da], p_weights [T, B, N], a_seq [B, H, da] of the last period); the rows
+        of inactive environments are NaN.  Afterwards (actions[-1], states[-1]) is the noted update: forward(states[-1]), tick() or
+        another run_episodes(states[-1], ...) continue the same loop.  Pendulum and Particle; a skid-steer or cart-pole pair is refused
+        (tick() runs those)."""
+        from ..inference.svmpc import check_optimizer
+        from ..models import CartPoleModel, SkidSteerRobot
+
+        sv = self.svmpc
+        T = int(n_periods)
+        if not 1 <= T <= 4096:
+            raise ValueError("n_periods = %d outside [1, 4096]: one call runs one episode piece, chain a longer one" % T)
+        for model in (sv.likelihood.model, getattr(self.mpf.likelihood, "model", None)):
+            if isinstance(model, (SkidSteerRobot, CartPoleModel)):
+                raise NotImplementedError("run_episodes conditions the filters on the device: Pendulum and Particle (a %s pair runs tick())"
+                                          % type(model).__name__)
+        P = self.mpf._dev.P
+        if plant_params is not None:
+            plant_params = np.asarray(torch.as_tensor(plant_params, dtype=torch.float).numpy(), np.float32)
+            if plant_params.shape != (self.n_envs, P):
+                raise ValueError("plant_params has shape %s, the plants read %s" % (plant_params.shape, (self.n_envs, P)))
+        check_optimizer(sv.optimizer, sv._opt_group)
+        batch = sv._ensure_batch(self.mpf.prior)
+        if n_steps is None:
+            n_steps = sv.n_steps if self.n_steps is None else self.n_steps
+        st = sv._states(states)
+        mb = self._filters(st)
+        pend = self._pending
+        keys = np.array([self.prior_keys(self._t + 1 + t) for t in range(T)], np.uint64)
+        xs, acts, pw, bw, a_seq = batch.dual_episode(mb, st, T, n_steps, None if pend is None else pend[0], mpf_steps=self.mpf_steps,
+                                                     mpf_bw=self.mpf_bw, seeds=keys, plant_params=plant_params,
+                                                     active=None if active is None else sv._active(active))
+        # (a refused call consumes neither the keys nor the noted update)
+        a_last, x_last = acts[-1].copy(), xs[-1].copy()
+        if active is not None:  # an inactive environment keeps the pair it came with
+            off = ~sv._active(active)
+            a_last[off], x_last[off] = (0.0 if pend is None else pend[0][off]), st[off]
+        self._t, self._pending = self._t + T, (a_last, x_last)
+        if pend is not None or T > 1:
+            self.last_bw = torch.from_numpy(bw[-1].copy())
+        self.ticks += T
+        return torch.from_numpy(xs), torch.from_numpy(acts), torch.from_numpy(pw), torch.from_numpy(a_seq)

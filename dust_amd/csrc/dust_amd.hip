@@ -5620,15 +5620,10 @@ static int svb_stage(dust_svmpc_batch *b, int n_steps, const void *eps, const fl
   return DUST_OK;
 }
 
-// States and mask through the next pinned slot, the kernel's arguments and the ONE launch; nothing waits for the device.  params_dev: the
-// staged parameter rows or NULL; prior: the filters the PRIOR instances draw their rows from, or NULL; episode: the launch runs
-// episode->T ticks, each followed by the plant's step (svmpc_episode.hpp), not one
-static int svb_go(dust_svmpc_batch *b, const float *states, int n_steps, const float *eps_dev, const float *params_dev, int flags,
-                  const unsigned char *active, bool do_forward, const dust::SvbPrior *prior, const dust::SvbEpisode *episode = nullptr) {
-  dust_ctx *c = b->c;
-  HIP_TRY(hipSetDevice(c->cfg.device));
-  TRY(b->in.stage(c, states, active));
-  SvmpcBatchArgs k;
+// svb_args: the kernel's arguments for the inputs a call has staged (svb_go; the periods of dust_svmpc_dual_batch_episode, mpf.hpp)
+static void svb_args(const dust_svmpc_batch *b, int n_steps, const float *eps_dev, const float *params_dev, const unsigned char *active, bool do_forward,
+                     SvmpcBatchArgs &k) {
+  const dust_ctx *c = b->c;
   memset(&k, 0, sizeof k);
   k.dm = make_dev_model(c);
   k.sk = c->skid;
@@ -5696,6 +5691,17 @@ static int svb_go(dust_svmpc_batch *b, const float *states, int n_steps, const f
   k.a_mix = b->a_mix;
   k.pw = b->pw;
   k.a_seq_out = b->a_seq_out;
+}
+// States and mask through the next pinned slot, the kernel's arguments and the ONE launch; nothing waits for the device.  params_dev: the
+// staged parameter rows or NULL; prior: the filters the PRIOR instances draw their rows from, or NULL; episode: the launch runs
+// episode->T ticks, each followed by the plant's step (svmpc_episode.hpp), not one
+static int svb_go(dust_svmpc_batch *b, const float *states, int n_steps, const float *eps_dev, const float *params_dev, int flags,
+                  const unsigned char *active, bool do_forward, const dust::SvbPrior *prior, const dust::SvbEpisode *episode = nullptr) {
+  dust_ctx *c = b->c;
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  TRY(b->in.stage(c, states, active));
+  SvmpcBatchArgs k;
+  svb_args(b, n_steps, eps_dev, params_dev, active, do_forward, k);
   const bool nav = skid_nav_on(c);
   SkidNav nv;
   memset(&nv, 0, sizeof nv);

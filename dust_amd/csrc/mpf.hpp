@@ -14,6 +14,7 @@
 // Reference quirk kept: MPF.update_prior hands `self.x` itself to MultivariateNormal(loc=...), which aliases the
 // particle storage, and SGD updates x in place - so the prior means are always the CURRENT particles (mpf.py:26-38).
 #pragma once
+#include "mpf_env.hpp"  // MpfEnvIn
 
 namespace dust {
 
@@ -294,10 +295,6 @@ __global__ __launch_bounds__(1024) void mpf_optimize_kernel(const MpfArgs a) {
 // told them (assumptions on the arguments, not another text): the other families' branches of the body, the other parameter space's and
 // the other optimisers' fold away, and with them the spilled registers the lone kernel's instances carry.  Instances exist for as many
 // particle columns as the model has parameters (Pendulum 3, Particle 1, skid-steer 3, cart-pole 4: mpfb_limits refuses the rest).
-struct MpfEnvIn {
-  float past_obs[4], obs[4], past_action[2];
-  int t0, pad;
-};
 struct MpfBatchArgs {
   MpfArgs a;                    // the shared fields; x, grad_norms and the optimiser slots are environment 0's; the per-call values are unused
   const MpfEnvIn *in;           // [B]
@@ -2000,6 +1997,10 @@ struct dust_mpf_batch {
   std::vector<unsigned char> have_past;
   std::vector<int> opt_t;
   PinnedStage in;      // per-call inputs: MpfEnvIn [B] | prior seeds [B] | SkidLik / CartLik [B] | active mask [B]
+  // dust_svmpc_dual_batch_episode: MpfEnvIn [B] - conditioned on the device from period to period - | prior seeds [T][B] | plant rows
+  // [B][P], and the pinned bytes they are staged from, once per call (allocated by the first such call)
+  DevBuf<unsigned char> ep;
+  PinBuf<unsigned char> ep_host;
   hipEvent_t ev_ext;   // behind the last work a dual tick put on a controller batch's stream (AMPPI or SVMPC)
   long long n_launch, n_calls;
 };
@@ -2228,50 +2229,48 @@ static bool mpfb_launch(const dust_mpf *m, int B, hipStream_t stream, const MpfB
   });
 }
 
-static int mpfb_enqueue(dust_mpf_batch *mb, hipStream_t stream, const bool update, const float *actions, const float *new_obs, const float bw,
-                        const int n_steps, const unsigned char *active, const uint64_t *seeds, MpfbRows &w) {
-  dust_mpf *m = mb->m;
+// GaussianLikelihood.condition of every active environment (likelihoods.py:51-64) on copies of the host rows (`w`; new_obs NULL: the
+// rows as they stand), and what the update of `n_steps` steps reads of them: MpfEnvIn [B] in front of the stage's bytes `hb`, and the
+// skid-steer / cart-pole likelihood rows behind the seeds
+static void mpfb_rows(const dust_mpf_batch *mb, const float *actions, const float *new_obs, const int n_steps, const unsigned char *active, unsigned char *hb,
+                      MpfbRows &w) {
+  const dust_mpf *m = mb->m;
   const int B = mb->B, ds = m->cfg.dim_s, da = m->cfg.dim_a, model = m->cfg.model_cfg.model;
-  unsigned char *hb;
-  TRY(mb->in.next(&hb));
   dust::MpfEnvIn *in = mpfb_in_view(hb);
-  if (seeds) memcpy(hb + mpfb_off_seeds(B), seeds, (size_t)B * sizeof(uint64_t));
-  if (active) memcpy(hb + mpfb_off_mask(mb), active, (size_t)B);
-  if (update) {
-    w.loc = mb->loc;
-    w.past_obs = mb->past_obs;
-    w.past_action = mb->past_action;
-    w.have_past = mb->have_past;
-    w.opt_t = mb->opt_t;
-    w.filled = true;
-    for (int e = 0; e < B; ++e) {
-      float *loc = &w.loc[(size_t)e * 5], *past = &w.past_obs[(size_t)e * 5], *pa = &w.past_action[(size_t)e * 2];
-      const bool on = !active || active[e];
-      if (on && new_obs) {
-        memcpy(past, loc, 5 * sizeof(float));
-        for (int q = 0; q < ds && q < 5; ++q) loc[q] = new_obs[(size_t)e * ds + q];
-        for (int q = 0; q < 2; ++q) pa[q] = q < da ? actions[(size_t)e * da + q] : 0.f;
-        w.have_past[e] = 1;
-      }
-      memset(&in[e], 0, sizeof in[e]);
-      for (int q = 0; q < 4; ++q) {
-        in[e].past_obs[q] = past[q];
-        in[e].obs[q] = loc[q];
-      }
-      in[e].past_action[0] = pa[0];
-      in[e].past_action[1] = pa[1];
-      in[e].t0 = w.opt_t[e];
-      if (model == DUST_MODEL_SKID_STEER) mpf_skid_lik(m, pa, past, loc, mpfb_lik_view<dust::SkidLik>(hb, B)[e]);
-      if (model == DUST_MODEL_CARTPOLE) mpf_cart_lik(m, pa, past, loc, mpfb_lik_view<dust::CartLik>(hb, B)[e]);
-      if (on) w.opt_t[e] += n_steps;
+  w.loc = mb->loc;
+  w.past_obs = mb->past_obs;
+  w.past_action = mb->past_action;
+  w.have_past = mb->have_past;
+  w.opt_t = mb->opt_t;
+  w.filled = true;
+  for (int e = 0; e < B; ++e) {
+    float *loc = &w.loc[(size_t)e * 5], *past = &w.past_obs[(size_t)e * 5], *pa = &w.past_action[(size_t)e * 2];
+    const bool on = !active || active[e];
+    if (on && new_obs) {
+      memcpy(past, loc, 5 * sizeof(float));
+      for (int q = 0; q < ds && q < 5; ++q) loc[q] = new_obs[(size_t)e * ds + q];
+      for (int q = 0; q < 2; ++q) pa[q] = q < da ? actions[(size_t)e * da + q] : 0.f;
+      w.have_past[e] = 1;
     }
+    memset(&in[e], 0, sizeof in[e]);
+    for (int q = 0; q < 4; ++q) {
+      in[e].past_obs[q] = past[q];
+      in[e].obs[q] = loc[q];
+    }
+    in[e].past_action[0] = pa[0];
+    in[e].past_action[1] = pa[1];
+    in[e].t0 = w.opt_t[e];
+    if (model == DUST_MODEL_SKID_STEER) mpf_skid_lik(m, pa, past, loc, mpfb_lik_view<dust::SkidLik>(hb, B)[e]);
+    if (model == DUST_MODEL_CARTPOLE) mpf_cart_lik(m, pa, past, loc, mpfb_lik_view<dust::CartLik>(hb, B)[e]);
+    if (on) w.opt_t[e] += n_steps;
   }
-  // (without an update the likelihood rows between the seeds and the mask are not read: the copy may carry whatever the slot holds; the
-  // seeds lie in the range either way: there is always something to copy)
-  TRY(mb->in.send(update ? 0 : mpfb_off_seeds(B), active ? mpfb_in_bytes(mb) : mpfb_off_mask(mb), stream));
-  if (!update) return DUST_OK;
-  serve_cancel_device(m->cfg.device);  // (as mpf_launch: an armed control tick would hold every CU until its plant state arrives)
-  const unsigned char *mask = mpfb_mask_dev(mb, active);
+}
+
+// The launches of an update on `stream`: the heading / angle terms of all environments in one launch (skid-steer, cart-pole), Silverman's
+// rule of all in one launch (bw <= 0), the update of all in one launch.  `in`: the MpfEnvIn rows on the device; `mask`: the staged mask
+static int mpfb_update_launch(dust_mpf_batch *mb, hipStream_t stream, const dust::MpfEnvIn *in, const unsigned char *mask, const float bw, const int n_steps) {
+  dust_mpf *m = mb->m;
+  const int B = mb->B, model = m->cfg.model_cfg.model;
   const bool cart = model == DUST_MODEL_CARTPOLE;
   if (model == DUST_MODEL_SKID_STEER) {
     dust::mpf_lik_angle_batch_kernel<dust::SkidLik><<<(B + 255) / 256, 256, 0, stream>>>(mpfb_lik_view<dust::SkidLik>(mb->in.dev.get(), B), B, mask);
@@ -2301,7 +2300,7 @@ static int mpfb_enqueue(dust_mpf_batch *mb, hipStream_t stream, const bool updat
   a.opt_s0 = mb->opt_s[0];
   a.opt_s1 = mb->opt_s[1];
   a.opt_s2 = mb->opt_s[2];
-  k.in = mpfb_in_view(mb->in.dev.get());
+  k.in = in;
   k.prior_bwv = mb->prior_bwv;
   k.bw = mb->bw;
   k.bw_fixed = bw > 0.f ? bw : 0.f;
@@ -2327,6 +2326,23 @@ static int mpfb_enqueue(dust_mpf_batch *mb, hipStream_t stream, const bool updat
   HIP_TRY(hipGetLastError());
   mb->n_launch++;
   return DUST_OK;
+}
+
+static int mpfb_enqueue(dust_mpf_batch *mb, hipStream_t stream, const bool update, const float *actions, const float *new_obs, const float bw,
+                        const int n_steps, const unsigned char *active, const uint64_t *seeds, MpfbRows &w) {
+  dust_mpf *m = mb->m;
+  const int B = mb->B;
+  unsigned char *hb;
+  TRY(mb->in.next(&hb));
+  if (seeds) memcpy(hb + mpfb_off_seeds(B), seeds, (size_t)B * sizeof(uint64_t));
+  if (active) memcpy(hb + mpfb_off_mask(mb), active, (size_t)B);
+  if (update) mpfb_rows(mb, actions, new_obs, n_steps, active, hb, w);
+  // (without an update the likelihood rows between the seeds and the mask are not read: the copy may carry whatever the slot holds; the
+  // seeds lie in the range either way: there is always something to copy)
+  TRY(mb->in.send(update ? 0 : mpfb_off_seeds(B), active ? mpfb_in_bytes(mb) : mpfb_off_mask(mb), stream));
+  if (!update) return DUST_OK;
+  serve_cancel_device(m->cfg.device);  // (as mpf_launch: an armed control tick would hold every CU until its plant state arrives)
+  return mpfb_update_launch(mb, stream, mpfb_in_view(mb->in.dev.get()), mpfb_mask_dev(mb, active), bw, n_steps);
 }
 
 // room for grad_norms [B][n_steps] (a reallocation frees behind the device's queued work)
@@ -2499,4 +2515,136 @@ extern "C" int dust_svmpc_dual_batch_tick(dust_svmpc_batch *b, dust_mpf_batch *m
   if (params_out) TRY(rows_d2h(b->B, c->stream, params_out, b->params, prow, active));
   TRY(dual_batch_bw(c, mb, rows, actions_prev, mpf_bw, active, bw_used, &copies));
   return dual_batch_close(c, mb, copies);
+}
+
+// T control periods of the DuSt-MPC loop (simulations.py:104-138) for B environments in one call: T successive dust_svmpc_dual_batch_tick
+// calls with device-drawn noise, and between them the plant of dust_svmpc_batch_episode - x_{t+1} = step(x_t, a_t) under the true rows
+// plant_params - stepped on the device.  Everything is staged once (states and mask through the controller batch's pinned slot; the
+// filters' MpfEnvIn rows, the seeds [T][B] and the plant rows through the filter batch's); then, on the controller batch's stream and in
+// launch order, period t is: Silverman's rule (mpf_bw <= 0) and the filters' update, when the period has an action (t >= 1, or
+// actions_prev), reading the MpfEnvIn rows IN DEVICE MEMORY, and one launch of svmpc_dual_period_kernel - the PRIOR tick under the key row
+// prior_seeds + t B, the plant, the records, and the conditioning of the MpfEnvIn rows for period t + 1.  No host wait, event or copy lies
+// between two periods; the call waits once, for the records, reads the MpfEnvIn rows back and moves the filters' host rows to where T
+// ticks leave them: the pair (a_{T-1}, x_T) is NOT folded in (the last period conditions nothing).
+extern "C" int dust_svmpc_dual_batch_episode(dust_svmpc_batch *b, dust_mpf_batch *mb, const float *states, const float *actions_prev, int n_periods,
+                                             int n_steps, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds, const float *plant_params, int flags,
+                                             const unsigned char *active, float *states_out, float *actions_out, float *pw_out, float *bw_out, float *a_seq) {
+  if (!b || !mb || !states || !states_out || !actions_out) return fail(DUST_ERR_INVALID, "null argument");
+  if (!prior_seeds) return fail(DUST_ERR_INVALID, "null argument: the draws from the filters' priors need prior_seeds [T][B]");
+  if (n_periods < 1 || n_periods > 4096)
+    return fail(DUST_ERR_INVALID, "n_periods = %d outside [1, 4096] (the queue of one call stays short on a shared device: chain a longer episode)", n_periods);
+  if (n_steps < 1 || mpf_steps < 0) return fail(DUST_ERR_INVALID, "bad step counts");
+  if (flags != 0) return fail(DUST_ERR_UNSUPPORTED, "a dual episode draws its noise on the device and keeps no actions: flags must be 0 (got %d)", flags);
+  dust_ctx *c = b->c;
+  dust_mpf *m = mb->m;
+  if (c->cfg.dim_p == 0 && plant_params) return fail(DUST_ERR_INVALID, "plant parameter rows without uncertain parameters (dim_p = 0)");
+  TRY(svb_call_check(b, states, n_steps, nullptr, true, 0, true));
+  TRY(dual_batch_pair_check(c, "SVMPC", b->B, mb));
+  auto host_lik = [](int model) { return model == DUST_MODEL_SKID_STEER || model == DUST_MODEL_CARTPOLE; };
+  if (host_lik(c->cfg.model) || host_lik(m->cfg.model_cfg.model))
+    return fail(DUST_ERR_UNSUPPORTED,
+                "a dual episode conditions the filters on the device: Pendulum and Particle pairs (a skid-steer or cart-pole filter's likelihood rows "
+                "carry the host's sin / cos of the past heading: dust_svmpc_dual_batch_tick per period)");
+  TRY(mpfb_limits(m, mb->B));
+  const bool first = actions_prev != nullptr;  // period 0 has an update
+  // (the periods behind the first always have one; its refusals depend on whether its arguments are there, not on their values)
+  if (first || n_periods > 1) TRY(mpfb_update_check(mb, first ? actions_prev : states, states, mpf_steps, active));
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  TRY(settle_pending(c));
+  // ---- room (reallocations free behind the device's queued work)
+  const size_t T = (size_t)n_periods, B = (size_t)b->B, N = (size_t)c->N, P = (size_t)c->cfg.dim_p, ds = (size_t)c->ds, da = (size_t)c->da;
+  const bool silverman = !(mpf_bw > 0.f);
+  TRY(mpfb_gn_room(mb, mpf_steps));
+  const size_t off_seeds = B * sizeof(dust::MpfEnvIn), off_plant = off_seeds + T * B * sizeof(uint64_t), n_stage = off_plant + B * P * sizeof(float);
+  TRY(mb->ep.ensure(n_stage));
+  if (mb->ep_host.cap() < n_stage) TRY(mb->ep_host.alloc(n_stage, hipHostMallocDefault));
+  const bool bw_dev = bw_out && silverman;
+  const size_t n_rec = T * B * (ds + da + (pw_out ? N : 0) + (bw_dev ? 1 : 0));
+  TRY(b->rec.ensure(n_rec));
+  // ---- staged once: states and mask; the filters' rows as period 0's update reads them (or, without one, as they stand), seeds, plants
+  TRY(b->in.stage(c, states, active));
+  unsigned char *hb = mb->ep_host;  // (free: every call that wrote it has waited for its stream)
+  MpfbRows rows;
+  mpfb_rows(mb, actions_prev, first ? states : nullptr, first ? mpf_steps : 0, active, hb, rows);
+  memcpy(hb + off_seeds, prior_seeds, T * B * sizeof(uint64_t));
+  if (plant_params) memcpy(hb + off_plant, plant_params, B * P * sizeof(float));
+  HIP_TRY(hipStreamWaitEvent(c->stream, mb->ev_ext, 0));
+  HIP_TRY(hipMemcpyAsync(mb->ep, hb, plant_params ? n_stage : off_plant, hipMemcpyHostToDevice, c->stream));
+  if (first || n_periods > 1) serve_cancel_device(m->cfg.device);  // (as mpfb_enqueue, once for the call)
+  // ---- the periods
+  dust::MpfEnvIn *in_dev = mpfb_in_view(mb->ep.get());
+  const uint64_t *seeds_dev = reinterpret_cast<const uint64_t *>(mb->ep.get() + off_seeds);
+  const unsigned char *mask = b->in.mask_dev(active);
+  SvmpcDualPeriodArgs ka;
+  svb_args(b, n_steps, nullptr, nullptr, active, true, ka.k);
+  dual_batch_prior(mb, nullptr, ka.pr);
+  float *rec_s = b->rec, *rec_a = rec_s + T * B * ds, *rec_pw = rec_a + T * B * da, *rec_bw = rec_pw + (pw_out ? T * B * N : 0);
+  const size_t lds = svmpc_batch_lds_bytes(c->N, c->D, c->M);
+  for (size_t t = 0; t < T; ++t) {
+    const bool update = t > 0 || first;
+    if (update) TRY(mpfb_update_launch(mb, c->stream, in_dev, mask, mpf_bw, mpf_steps));
+    mb->n_calls++;
+    ka.pr.seeds = seeds_dev + t * B;
+    ka.dp.plant = plant_params ? reinterpret_cast<const float *>(mb->ep.get() + off_plant) : nullptr;
+    ka.dp.state = const_cast<float *>(b->in.states_dev());
+    ka.dp.in = in_dev;
+    ka.dp.states_out = rec_s + t * B * ds;
+    ka.dp.actions_out = rec_a + t * B * da;
+    ka.dp.pw_out = pw_out ? rec_pw + t * B * N : nullptr;
+    ka.dp.bw = bw_dev && update ? mb->bw.get() : nullptr;
+    ka.dp.bw_out = bw_dev ? rec_bw + t * B : nullptr;
+    ka.dp.t0_add = update ? mpf_steps : 0;
+    ka.dp.condition = t + 1 < T ? 1 : 0;
+    Prof pr(c, DUST_K_SVMPC_BATCH);
+    const hipError_t launched = by_model(c, [&](auto M) -> hipError_t {
+      if constexpr (M() == DUST_MODEL_PENDULUM || M() == DUST_MODEL_PARTICLE)
+        return launch_on(c->stream, false, &svmpc_dual_period_kernel<M()>, b->B, SVB_THREADS, lds, ka);
+      else return hipErrorInvalidValue;  // (refused above)
+    });
+    HIP_TRY(launched);
+  }
+  b->have_costs = true;
+  b->acts_kept = false;
+  b->have_forward = true;
+  // ---- the records and the advanced rows come back once; the rows of inactive environments stay out of the caller's arrays
+  std::vector<float> host(n_rec);
+  std::vector<dust::MpfEnvIn> in_host(B);
+  HIP_TRY(hipMemcpyAsync(host.data(), b->rec, n_rec * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(in_host.data(), in_dev, B * sizeof(dust::MpfEnvIn), hipMemcpyDeviceToHost, c->stream));
+  TRY(svb_outputs_copy(b, active, a_seq, nullptr));
+  HIP_TRY(hipEventRecord(mb->ev_ext, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  auto out = [&](float *dst, const float *src, size_t row) {
+    for (size_t t = 0; t < T; ++t)
+      for (size_t e = 0; e < B; ++e)
+        if (!active || active[e]) memcpy(dst + (t * B + e) * row, src + (t * B + e) * row, row * sizeof(float));
+  };
+  out(states_out, host.data(), ds);
+  out(actions_out, host.data() + T * B * ds, da);
+  if (pw_out) out(pw_out, host.data() + T * B * (ds + da), N);
+  if (bw_dev) out(bw_out, host.data() + T * B * (ds + da + (pw_out ? N : 0)), 1);
+  for (size_t e = 0; e < B; ++e) {
+    if (active && !active[e]) continue;
+    if (bw_out) {  // what bw_used of the period's dual tick is: 0 without an update, the fixed bandwidth, or Silverman's (recorded above)
+      if (!first) bw_out[e] = 0.f;
+      if (!silverman)
+        for (size_t t = first ? 0 : 1; t < T; ++t) bw_out[t * B + e] = mpf_bw;
+    }
+    // the filters' host rows: what the last update read, and the steps taken since
+    const dust::MpfEnvIn &r = in_host[e];
+    float *loc = &rows.loc[e * 5], *past = &rows.past_obs[e * 5];
+    if (T > 1) {  // (conditioned on the device at least once: condition() copies the five-wide row, whose fifth column no state here reaches)
+      past[4] = loc[4];
+      rows.have_past[e] = 1;
+    }
+    for (int q = 0; q < 4; ++q) {
+      loc[q] = r.obs[q];
+      past[q] = r.past_obs[q];
+    }
+    rows.past_action[e * 2] = r.past_action[0];
+    rows.past_action[e * 2 + 1] = r.past_action[1];
+    rows.opt_t[e] = r.t0;
+  }
+  mpfb_commit(mb, rows);
+  return DUST_OK;
 }

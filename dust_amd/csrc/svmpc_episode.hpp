@@ -21,7 +21,13 @@
 // Launch shape: the batched tick's - 512 lanes, one workgroup per environment, svmpc_batch_lds_bytes() of dynamic LDS (plus the map in
 // the navigation instance).  The navigation instance stages its map ONCE per launch, ahead of the period loop, as the batched tick
 // does ahead of its iteration loop; restaging it every period has not been measured, nor has the difference.
+//
+// svmpc_dual_period_kernel: ONE period of the dual loop (simulations.py:104-138) per launch, for dust_svmpc_dual_batch_episode.  The filter
+// update of a period is a launch of its own (mpf_optimize_batch_kernel: 1 024 lanes, another order of partial sums), so the periods of
+// that episode are a chain of launches on one stream, with no host in between; what a period hands to the next - the state row and the
+// filters' MpfEnvIn row - is written here by lane 0 and read by LATER launches only, so the carry of one period still lives in registers.
 #pragma once
+#include "mpf_env.hpp"
 #include "svmpc_batch.hpp"
 
 namespace dust {
@@ -104,6 +110,72 @@ __global__ __launch_bounds__(SVB_THREADS) void svmpc_episode_kernel(const SvmpcE
 }
 __global__ __launch_bounds__(SVB_THREADS) void svmpc_skid_nav_episode_kernel(const SvmpcNavEpisodeArgs ka) {
   svb_episode_body<DUST_MODEL_SKID_STEER, true>(ka.k, ka.ep, &ka.nav);
+}
+
+// What a period of the dual episode adds to the PRIOR tick's arguments
+struct SvbDualPeriod {
+  const float *plant;  // [B][P] true parameter rows or nullptr (nominal plants)
+  float *state;        // [B][8]: the rows SvmpcBatchArgs::states names; x_{t+1} for the next period's launch
+  MpfEnvIn *in;        // [B]: what the NEXT period's filter update reads
+  float *states_out;   // [B][ds], this period's rows of the records
+  float *actions_out;  // [B][da]
+  float *pw_out;       // [B][N] or nullptr
+  const float *bw;     // [B] the bandwidths Silverman's rule gave this period's update, or nullptr (no update, or a fixed bandwidth)
+  float *bw_out;       // [B] or nullptr: ... recorded (0 where no update ran)
+  int t0_add;          // the optimiser steps this period's filter update took (0: no update ran)
+  int condition;       // 0 in the call's last period: (a_{T-1}, x_T) stays pending, the row keeps the pair the last update read
+};
+struct SvmpcDualPeriodArgs {
+  SvmpcBatchArgs k;  // states: the device state rows; n_steps >= 1, do_forward and philox set
+  SvbPrior pr;       // seeds: this period's row of prior_seeds
+  SvbDualPeriod dp;
+};
+
+// One period of environment blockIdx.x: the PRIOR tick on the state the previous launch left, the plant's step, the records, and
+// GaussianLikelihood.condition (likelihoods.py:51-64) for the next period's update - mpfb_enqueue's host arithmetic (mpf.hpp) on the
+// environment's device row: past_obs <- obs, obs <- x_{t+1}, past_action <- a_t (zero-padded), t0 advanced by the steps just taken
+template <int MODEL>
+__device__ __forceinline__ void svb_dual_period_body(const SvmpcBatchArgs &a, const SvbPrior &pri, const SvbDualPeriod &dp) {
+  static_assert(MODEL == DUST_MODEL_PENDULUM || MODEL == DUST_MODEL_PARTICLE, "the other families' likelihood rows are made on the host");
+  constexpr int DS = SvbDims<MODEL>::DS;
+  const int env = (int)blockIdx.x;
+  if (a.active && a.active[env] == 0) return;
+  SvbCarry<MODEL> cy;
+  DevModel map;
+  float w_obs;
+  svb_begin<MODEL, false>(a, nullptr, cy, map, w_obs);
+  float cf[SVB_COEF];
+  svb_coef<MODEL>(a, dp.plant ? dp.plant + (size_t)env * a.P : nullptr, cf);
+  float act[2] = {0.f, 0.f};
+  svb_tick<MODEL, true, false, true>(a, &pri, nullptr, cy, map, w_obs, dp.pw_out ? dp.pw_out + (size_t)env * a.N : nullptr, act);
+  svb_plant_step<MODEL>(a, cf, cy.x0, act);
+  if (threadIdx.x == 0) {
+    float *xs = dp.state + (size_t)env * 8;
+    MpfEnvIn *in = dp.in + env;
+#pragma unroll
+    for (int k = 0; k < DS; ++k) {
+      dp.states_out[(size_t)env * DS + k] = cy.x0[k];
+      xs[k] = cy.x0[k];
+    }
+    dp.actions_out[(size_t)env * a.da] = act[0];
+    if (a.da == 2) dp.actions_out[(size_t)env * 2 + 1] = act[1];
+    if (dp.bw_out) dp.bw_out[env] = dp.bw ? dp.bw[env] : 0.f;
+    if (dp.condition) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) in->past_obs[k] = in->obs[k];
+#pragma unroll
+      for (int k = 0; k < DS; ++k) in->obs[k] = cy.x0[k];
+      in->past_action[0] = act[0];
+      in->past_action[1] = act[1];
+    }
+    if (dp.t0_add) in->t0 += dp.t0_add;
+  }
+  svb_end(a, cy);
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(SVB_THREADS) void svmpc_dual_period_kernel(const SvmpcDualPeriodArgs ka) {
+  svb_dual_period_body<MODEL>(ka.k, ka.pr, ka.dp);
 }
 
 }  // namespace dust

@@ -731,6 +731,36 @@ int dust_amppi_dual_batch_tick(dust_amppi_batch *batch, dust_mpf_batch *mpf, con
 int dust_svmpc_dual_batch_tick(dust_svmpc_batch *batch, dust_mpf_batch *mpf, const float *states, const float *actions_prev, int n_steps,
                                const void *eps, int flags, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds,
                                const unsigned char *active, float *a_seq, float *p_weights, float *params_out, float *bw_used);
+/* dust_svmpc_dual_batch_episode = T control periods of the DuSt-MPC loop (simulations.py:104-138) for B environments in one call: T
+ * successive dust_svmpc_dual_batch_tick calls with device-drawn noise (eps NULL), and between them what the host would do -
+ * x_{t+1} = step(x_t, a_t), a_t the raw a_seq[0] chosen before the roll - done on the device: the plant of dust_svmpc_batch_episode (the
+ * family's own device step under the environment's TRUE parameter row, or the nominal model; deterministic).  Period t takes
+ * states = x_t, actions_prev = a_{t-1} (period 0: the call's actions_prev; NULL skips that one update, as in the dual tick) and the key
+ * row prior_seeds + t B.  Bit for bit on both sides: every getter of the SVMPC batch; the filters' particles, prior bandwidths, optimiser
+ * slots, step counts and host rows; the Philox positions; dust_mpf_batch_stats (launches and calls advanced as by the T ticks).
+ *   Flow: everything is staged once ahead of the first launch (states, mask, seeds, plant rows, the filters' per-environment input rows);
+ *   all periods are then enqueued on the controller batch's stream, with no host wait, event or copy between them; the call waits once,
+ *   for the records.  A period launches Silverman's rule (mpf_bw <= 0) and the filters' update when it has one - the kernels of
+ *   dust_mpf_batch_optimize, reading their per-environment rows from device memory - and ONE launch of svmpc_dual_period_kernel
+ *   (dust_amd/csrc/svmpc_episode.hpp, counted under DUST_K_SVMPC_BATCH): the tick of dust_svmpc_dual_batch_tick, the plant's step, the
+ *   records, and GaussianLikelihood.condition (likelihoods.py:51-64) of the filter's row for the next period.  The launch count does not
+ *   depend on B.
+ *   states [B][ds], actions_prev [B][da] or NULL, prior_seeds [T][B], plant_params [B][P] or NULL (the columns and the space of the
+ *   controller's dynamics samples), all host; flags: 0;
+ *   records, host, copied back once after the last launch, the rows of inactive environments NOT written: states_out [T][B][ds] (the
+ *     state after the step), actions_out [T][B][da] (the raw a_seq[0]), pw_out [T][B][N] or NULL, bw_out [T][B] or NULL (bw_used of the
+ *     period's dual tick; 0 where no update ran), a_seq [B][H][da] or NULL (the last period's sequence, before the roll).
+ * The pending pair: after T periods (a_{T-1}, x_T) has NOT been folded into the filters, exactly as after T dual ticks; hand
+ * actions_out[T-1] and states_out[T-1] to the next call as actions_prev and states: two episodes chained that way equal one of T1 + T2
+ * periods (a change of the true parameters mid-episode is two chained calls).
+ * Refused before anything is staged or launched, both batches untouched.  DUST_ERR_INVALID: what dust_svmpc_dual_batch_tick refuses; NULL
+ * states, states_out, actions_out or prior_seeds; n_periods outside [1, 4096]; n_steps < 1; mpf_steps < 0; plant_params with dim_p = 0.
+ * DUST_ERR_UNSUPPORTED: any flag; a skid-steer or cart-pole pair, the navigation cost included (their filters' likelihood rows carry
+ * sin / cos of the past heading from the host's libm: a device-side conditioning would not be bit-equal to the period-by-period loop). */
+int dust_svmpc_dual_batch_episode(dust_svmpc_batch *batch, dust_mpf_batch *mpf, const float *states, const float *actions_prev,
+                                  int n_periods, int n_steps, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds,
+                                  const float *plant_params, int flags, const unsigned char *active,
+                                  float *states_out, float *actions_out, float *pw_out, float *bw_out, float *a_seq);
 
 #ifdef __cplusplus
 }
