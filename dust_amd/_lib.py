@@ -149,6 +149,7 @@ SYMBOLS = {
     "dust_amppi_batch_update": (C.c_int, [VP, FP, VP, FP, C.c_int, C.POINTER(C.c_ubyte), FP, FP, FP]),
     "dust_amppi_batch_roll": (C.c_int, [VP, C.c_int, C.POINTER(C.c_ubyte)]),
     "dust_amppi_batch_get_actions": (C.c_int, [VP, FP]),
+    "dust_amppi_batch_episode": (C.c_int, [VP, FP, C.c_int, FP, C.c_int, C.c_int, FP, C.POINTER(C.c_ubyte), FP, FP, FP, FP, FP]),
     "dust_svmpc_batch_create": (C.c_int, [VP, C.c_int, C.POINTER(C.c_uint64), C.POINTER(VP)]),
     "dust_svmpc_batch_destroy": (None, [VP]),
     "dust_svmpc_batch_clone": (C.c_int, [VP, C.POINTER(VP)]),
@@ -172,6 +173,8 @@ SYMBOLS = {
                                              FP, FP, FP, FP, FP]),
     "dust_svmpc_dual_batch_tick": (C.c_int, [VP, VP, FP, FP, C.c_int, VP, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_uint64), C.POINTER(C.c_ubyte),
                                              FP, FP, FP, FP]),
+    "dust_amppi_dual_batch_episode": (C.c_int, [VP, VP, FP, FP, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_uint64), C.c_int, FP,
+                                      C.POINTER(C.c_ubyte), FP, FP, FP, FP, FP, FP]),
     "dust_svmpc_dual_batch_episode": (C.c_int, [VP, VP, FP, FP, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_uint64), FP, C.c_int,
                                                 C.POINTER(C.c_ubyte), FP, FP, FP, FP, FP]),
     "dust_get_costs": (C.c_int, [VP, FP]),

@@ -748,11 +748,13 @@ class AmppiBatch(_BatchHandle):
         L.check(L.load().dust_amppi_batch_get_a_seq(self._h, _p(out)))
         return out
 
-    def update(self, states, actions=None, params=None, shared_params=False, active=None, want_actions=False, want_outputs=True, flags=0):
+    def update(self, states, actions=None, params=None, shared_params=False, active=None, want_actions=False, want_outputs=True, flags=0,
+               want_costs=True):
         """One tick of every active environment (dust_amppi_batch_update).  states [B, ds]; actions [B, S, H, da] or None (drawn on the
         device); params None ("none"), [B, 1, P] with shared_params ("single"), [B, S, P] ("extended") or [B, 2P + 1, P] sigma points;
         active [B] or None.  -> (costs [B, S], omega [B, S], a_seq [B, H, da] after the update, acts [B, S, H, da] or None); the rows of
-        inactive environments are NaN.  want_outputs=False reads nothing back (the tick stays asynchronous on the batch's stream)."""
+        inactive environments are NaN.  want_outputs=False reads nothing back (the tick stays asynchronous on the batch's stream);
+        want_costs=False reads a_seq alone back (costs and omega come back as None)."""
         B, S = self.B, self.S
         st = None if states is None else _f(states, (B, self.ds))  # (None: the library refuses)
         act = None if actions is None else _f(actions, (B, S, self.H, self.da))
@@ -766,7 +768,9 @@ class AmppiBatch(_BatchHandle):
         fl = int(flags) | (L.AMPPI_PARAMS_SHARED if shared_params else 0)
         costs = omega = a_seq = None
         if want_outputs:
-            costs, omega, a_seq = (np.full(sh, np.nan, np.float32) for sh in ((B, S), (B, S), (B, self.H, self.da)))
+            a_seq = np.full((B, self.H, self.da), np.nan, np.float32)
+            if want_costs:
+                costs, omega = (np.full((B, S), np.nan, np.float32) for _ in range(2))
         L.check(L.load().dust_amppi_batch_update(self._h, _p(st), _vp(act), _p(pr), fl, mp, _p(costs), _p(omega), _p(a_seq)))
         return costs, omega, a_seq, (self.get_actions() if want_actions else None)
 
@@ -804,6 +808,64 @@ class AmppiBatch(_BatchHandle):
         """BaseController.roll(steps) of every active environment in one launch (dust_amppi_batch_roll)."""
         _, mp = _mask(active, self.B)
         L.check(L.load().dust_amppi_batch_roll(self._h, int(steps), mp))
+
+    def episode(self, states, n_periods, params=None, shared_params=False, plant_params=None, active=None, roll_steps=1, want_costs=True,
+                flags=0):
+        """n_periods closed-loop periods of every active environment with the plants on the device (dust_amppi_batch_episode): per
+        period one launch - the tick (noise drawn on the device), the plant's step with the first action of the updated sequence under
+        the environment's true parameters, the records, the roll - and no host between two periods.  states [B, ds]; params None,
+        [T, B, 1, P] with shared_params, [T, B, S, P] or [T, B, 2P + 1, P] sigma points; plant_params [B, P] or None (nominal plants).
+        -> (states [T, B, ds] after every step, actions [T, B, da], costs [T, B, S] or None, omega [T, B, S] or None, a_seq [B, H, da] of
+        the last period before its roll); the rows of inactive environments are NaN."""
+        B, T, S = self.B, int(n_periods), self.S
+        st = None if states is None else _f(states, (B, self.ds))  # (None: the library refuses)
+        pr = pl = None
+        if params is not None:
+            pr = _f(params)
+            want = (T, B, self.M if self.M > 1 else (1 if shared_params else S), max(self.P, 1))
+            if pr.shape != want:
+                raise ValueError("params has shape %s, the call reads %s" % (pr.shape, want))
+        if plant_params is not None:
+            pl = _f(plant_params)
+            if pl.shape != (B, max(self.P, 1)):
+                raise ValueError("plant_params has shape %s, the call reads %s" % (pl.shape, (B, max(self.P, 1))))
+        _, mp = _mask(active, B)
+        rows = max(T, 0)  # (n_periods < 1: the library refuses before it writes anything)
+        xs, acts, a_seq = (np.full(sh, np.nan, np.float32) for sh in ((rows, B, self.ds), (rows, B, self.da), (B, self.H, self.da)))
+        costs, omega = ((np.full((rows, B, S), np.nan, np.float32) for _ in range(2)) if want_costs else (None, None))
+        fl = int(flags) | (L.AMPPI_PARAMS_SHARED if shared_params else 0)
+        L.check(L.load().dust_amppi_batch_episode(self._h, _p(st), T, _p(pr), fl, int(roll_steps), _p(pl), mp, _p(xs), _p(acts), _p(costs),
+                                                  _p(omega), _p(a_seq)))
+        return xs, acts, costs, omega, a_seq
+
+    def dual_episode(self, mpf, states, n_periods, actions_prev=None, shared_params=False, mpf_steps=20, mpf_bw=None, seeds=None, roll_steps=1,
+                     plant_params=None, active=None, want_costs=True):
+        """n_periods control periods of the dual loop for every active environment in one C call (dust_amppi_dual_batch_episode): per
+        period the filters' update - in period 0 only with actions_prev -, the tick with its parameters from the refreshed priors and
+        device-drawn noise, the plant's step with the first action of the updated sequence under the environment's true parameters,
+        the roll; no host round trip between periods.  states [B, ds]; seeds [T, B]: period t's Philox keys; plant_params [B, P] or
+        None (nominal plants).  -> (states [T, B, ds] after every step, actions [T, B, da], costs [T, B, S] or None, omega [T, B, S] or
+        None, bw [T, B], a_seq [B, H, da] of the last period before its roll); the rows of inactive environments are NaN.  The pair
+        (actions[-1], states[-1]) is still to be folded into the filters: hand it to the next call."""
+        B, T, S = self.B, int(n_periods), self.S
+        st = None if states is None else _f(states, (B, self.ds))  # (None: the library refuses)
+        ap = None if actions_prev is None else _f(actions_prev, (B, self.da))
+        rows = max(T, 0)  # (n_periods < 1: the library refuses before it reads or writes anything)
+        if seeds is not None and np.shape(seeds) != (rows, B):
+            raise ValueError("seeds has shape %s, the call reads %s" % (np.shape(seeds), (rows, B)))
+        sd, sp = _seeds(seeds, rows * B)
+        pl = None
+        if plant_params is not None:
+            pl = _f(plant_params)
+            if pl.shape != (B, max(self.P, 1)):
+                raise ValueError("plant_params has shape %s, the call reads %s" % (pl.shape, (B, max(self.P, 1))))
+        _, mp = _mask(active, B)
+        xs, acts, bw, a_seq = (np.full(sh, np.nan, np.float32) for sh in ((rows, B, self.ds), (rows, B, self.da), (rows, B), (B, self.H, self.da)))
+        costs, omega = ((np.full((rows, B, S), np.nan, np.float32) for _ in range(2)) if want_costs else (None, None))
+        L.check(L.load().dust_amppi_dual_batch_episode(self._h, mpf._h, _p(st), _p(ap), T, L.AMPPI_PARAMS_SHARED if shared_params else 0, int(mpf_steps),
+                                                       float(-1.0 if mpf_bw is None else mpf_bw), sp, int(roll_steps), _p(pl), mp,
+                                                       _p(xs), _p(acts), _p(costs), _p(omega), _p(bw), _p(a_seq)))
+        return xs, acts, costs, omega, bw, a_seq
 
 
 class SvmpcBatch(_BatchHandle):

@@ -301,3 +301,44 @@ class BatchAMPPI(AMPPI):
                                                  active=None if active is None else on, want_actions=want)
         t = torch.from_numpy
         return t(costs), None, (t(acts_out) if want else None), t(omega)
+
+    def run_episodes(self, model, states, n_periods, plant_params=None, active=None, roll_steps=1):
+        """`n_periods` closed-loop periods of every active environment with the plants on the device (dust_amppi_batch_episode): per
+        period update_actions with device-drawn noise, the plant's step with the first action of the updated sequence - the model's
+        own step under the environment's TRUE parameters `plant_params` [B, P] (the columns of the controller's parameter rows; None:
+        the nominal model), without process noise - and roll(roll_steps); the host does not come between two periods.  states [B, ds]:
+        where the episodes start.  The parameter rows are the draws `n_periods` calls of update_actions would make, in the same order:
+        under one torch.manual_seed the call consumes the torch stream exactly as they do.
+        -> (states [T, B, ds] after every step, actions [T, B, da], costs [T, B, S], omega [T, B, S]); the rows of inactive
+        environments are NaN."""
+        T, B = int(n_periods), self.n_envs
+        if not 1 <= T <= 4096:
+            raise ValueError("n_periods = %d outside [1, 4096]: one call runs one episode piece, split a longer one" % T)
+        if roll_steps < 1:
+            raise ValueError("roll(steps=%d): steps >= 1" % roll_steps)
+        on = self._active(active)
+        sampled = self._tf is not None or bool(self._sample_shape)
+        P = len(getattr(model, "uncertain_params", None) or ()) if sampled else 0
+        if plant_params is not None:
+            plant_params = np.asarray(torch.as_tensor(plant_params, dtype=torch.float).numpy(), np.float32)
+            if P == 0 or plant_params.shape != (B, P):
+                raise ValueError("plant_params has shape %s, the plants read %s" % (plant_params.shape, (B, P) if P else "none"))
+        states = torch.as_tensor(states, dtype=torch.float).reshape(B, -1)
+        batch = self._ensure_batch(model)
+        params = None
+        if self._tf is not None and on.any():
+            params = np.stack([np.repeat(self._sigma_points(model)[None], B, 0) for _ in range(T)])
+        elif self._sample_shape and on.any():
+            per = []
+            for _ in range(T):  # (update_actions' draws: once per active environment, in environment order)
+                rows = [model.dict_to_params(model.sample_params(self._sample_shape)).numpy() if on[b] else None for b in range(B)]
+                shape = next(r.shape for r in rows if r is not None)
+                per.append(np.stack([r if r is not None else np.zeros(shape, np.float32) for r in rows]))
+            params = np.stack(per)
+        if params is None and sampled:  # nobody ticks: nothing to launch
+            nan = lambda *sh: torch.full(sh, float("nan"))
+            return nan(T, B, states.shape[1]), nan(T, B, self.dim_a), nan(T, B, self.n_samples), nan(T, B, self.n_samples)
+        xs, acts, costs, omega, _ = batch.episode(states.numpy(), T, params, shared_params=self._params_sampling == "single" and params is not None,
+                                                  plant_params=plant_params, active=None if active is None else on, roll_steps=roll_steps)
+        t = torch.from_numpy
+        return t(xs), t(acts), t(costs), t(omega)

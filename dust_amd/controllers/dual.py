@@ -381,6 +381,60 @@ class BatchDualAMPPI(_BatchDual):
         self.step(actions, new_states)
         return actions, new_states, omega
 
+    # -- simulations.py:104-138 for every environment, the plants on the device
+    def run_episodes(self, states, n_periods, plant_params=None, active=None):
+        """`n_periods` control periods of every active environment in one C call (dust_amppi_dual_batch_episode): what `n_periods` calls
+        of tick() run, with the plants stepped on the device by the model's own step under the environment's TRUE parameters
+        `plant_params` [B, P] (the columns of the filters' particles; None: the nominal model), without process or observation noise -
+        no host round trip between the periods.  states [B, ds]: where the piece starts; a noted update is period 0's, with `states`
+        as its observation, as in forward().  Period t draws under `prior_keys(_t + 1 + t)`, the key schedule of
+        `BatchDualSVMPC.run_episodes`.  The roll is the constructor's `roll`, which must be >= 1 here.
+        -> (states [T, B, ds] after every step, actions [T, B, da], costs [T, B, S], omega [T, B, S]); the rows of inactive
+        environments are NaN.  Afterwards (actions[-1], states[-1]) is the noted update: forward(states[-1]), tick() or another
+        run_episodes(states[-1], ...) continue the same loop.  Pendulum and Particle; a skid-steer or cart-pole pair is refused
+        (tick() runs those)."""
+        from ..models import CartPoleModel, SkidSteerRobot
+        from ..inference.svmpc import _active
+
+        ctrl = self.controller
+        T = int(n_periods)
+        if not 1 <= T <= 4096:
+            raise ValueError("n_periods = %d outside [1, 4096]: one call runs one episode piece, chain a longer one" % T)
+        if self.roll < 1:
+            raise ValueError("run_episodes rolls every period: roll=%d, roll >= 1" % self.roll)
+        for model in (self.model, getattr(self.mpf.likelihood, "model", None)):
+            if isinstance(model, (SkidSteerRobot, CartPoleModel)):
+                raise NotImplementedError("run_episodes conditions the filters on the device: Pendulum and Particle (a %s pair runs tick())"
+                                          % type(model).__name__)
+        on = None if active is None else _active(active, self.n_envs)
+        P = self.mpf._dev.P
+        if plant_params is not None:
+            plant_params = np.asarray(torch.as_tensor(plant_params, dtype=torch.float).numpy(), np.float32)
+            if plant_params.shape != (self.n_envs, P):
+                raise ValueError("plant_params has shape %s, the plants read %s" % (plant_params.shape, (self.n_envs, P)))
+        self.model.params_dist = self.mpf.prior  # (what the context's configuration reads)
+        batch = ctrl._ensure_batch(self.model)
+        if ctrl._tf is not None:
+            batch.ctx.set_sigma_scale(ctrl._tf.scale)
+        st = torch.as_tensor(states, dtype=torch.float).reshape(self.n_envs, -1).numpy()
+        mb = self._filters(st)
+        pend = self._pending
+        keys = np.array([self.prior_keys(self._t + 1 + t) for t in range(T)], np.uint64)
+        xs, acts, costs, omega, bw, _ = batch.dual_episode(mb, st, T, None if pend is None else pend[0],
+                                                           shared_params=ctrl.params_sampling == "single", mpf_steps=self.mpf_steps,
+                                                           mpf_bw=self.mpf_bw, seeds=keys, roll_steps=self.roll, plant_params=plant_params, active=on)
+        # (a refused call consumes neither the keys nor the noted update)
+        a_last, x_last = acts[-1].copy(), xs[-1].copy()
+        if on is not None:  # an inactive environment keeps the pair it came with
+            off = ~on
+            a_last[off], x_last[off] = (0.0 if pend is None else pend[0][off]), st[off]
+        self._t, self._pending = self._t + T, (a_last, x_last)
+        if pend is not None or T > 1:
+            self.last_bw = torch.from_numpy(bw[-1].copy())
+        self.last_costs = torch.from_numpy(costs[-1].copy())
+        self.ticks += T
+        return torch.from_numpy(xs), torch.from_numpy(acts), torch.from_numpy(costs), torch.from_numpy(omega)
+
 
 class BatchDualSVMPC(_BatchDual):
     """The DuSt-MPC loop over `B = svmpc.n_envs` plants at once: a `BatchSVMPC` and B copies of one `MPF` - the deep copies of controller

@@ -42,6 +42,7 @@
 #include "amppi.hpp"
 #include "svmpc_batch.hpp"
 #include "svmpc_episode.hpp"
+#include "amppi_episode.hpp"
 #include "particle_general.hpp"
 #include "rollout.hpp"
 #include "stein.hpp"
@@ -1640,6 +1641,7 @@ struct dust_amppi_batch {
   DevBuf<uint32_t> ctr;          // [B][4]: every environment's Philox stream position {tick, iter, .., ..}
   DevBuf<uint64_t> seeds;        // [B]
   DevBuf<unsigned int> ticket;   // [B]
+  DevBuf<float> plant, rec;      // dust_amppi_batch_episode: [B][P] true parameter rows; the records [T][B][ds], [T][B][da], [T][B][S] x 2, [B][D]
   BatchInputs in;         // per-call inputs
   std::vector<unsigned char> last_active;  // the mask of the last tick (dust_amppi_batch_get_actions writes the rows of that tick's environments)
   bool acts_valid;
@@ -1750,6 +1752,27 @@ static int batch_roll_launch(dust_amppi_batch *b, int steps, const unsigned char
   return DUST_OK;
 }
 
+// The batched tick's arguments for the inputs a call has staged: the mode amppi_params_mode found, `prows` parameter rows per environment
+// in b->params, drawn noise or the actions in b->acts, the mask the call has staged (`active`: whether it had one)
+static void batch_tick_args(const dust_amppi_batch *b, int mode, int pts, size_t prows, bool philox, const unsigned char *active, AmppiBatchArgs &k) {
+  const dust_ctx *c = b->c;
+  amppi_shared_args(c, k.a);
+  k.a.pts = pts;
+  k.a.mode = mode;
+  k.a.philox = philox ? 1 : 0;
+  k.a.ctr = b->ctr;
+  k.a.params = prows ? b->params.get() : nullptr;
+  k.a.acts = b->acts;
+  k.a.a_seq = b->a_seq;
+  k.a.costs = b->costs;
+  k.a.omega = b->omega;
+  k.a.ticket = b->ticket;
+  k.states = b->in.states_dev();
+  k.seeds = b->seeds;
+  k.active = b->in.mask_dev(active);
+  k.prow_stride = (int)(prows * (size_t)c->cfg.dim_p);
+}
+
 // dust_amppi_batch_update up to and including its launch.  dust_amppi_dual_batch_tick (mpf.hpp) enters with `staged` (the parameter rows
 // already sit in b->params, written there on the batch's stream: `params` is then only "there are rows") or with `prior` (the lanes draw
 // their rows themselves from their environment's filter prior, "extended"; prior->params_out, when set, has room for [B][S][P])
@@ -1779,21 +1802,7 @@ static int batch_update_launch(dust_amppi_batch *b, const float *states, const f
   }
   TRY(b->in.stage(c, states, active));
   AmppiBatchArgs k;
-  amppi_shared_args(c, k.a);
-  k.a.pts = pts;
-  k.a.mode = mode;
-  k.a.philox = actions ? 0 : 1;
-  k.a.ctr = b->ctr;
-  k.a.params = prows ? b->params : nullptr;
-  k.a.acts = b->acts;
-  k.a.a_seq = b->a_seq;
-  k.a.costs = b->costs;
-  k.a.omega = b->omega;
-  k.a.ticket = b->ticket;
-  k.states = b->in.states_dev();
-  k.seeds = b->seeds;
-  k.active = b->in.mask_dev(active);
-  k.prow_stride = (int)(prows * P);
+  batch_tick_args(b, mode, pts, prows, actions == nullptr, active, k);
   TRY(amppi_launch<AmppiBatched>(c, dim3((unsigned)((S + AMPPI_THREADS - 1) / AMPPI_THREADS), (unsigned)B), k, prior, b->ticket, B));
   b->acts_valid = true;
   if (active) b->last_active.assign(active, active + B);
@@ -1829,6 +1838,97 @@ extern "C" int dust_amppi_batch_get_actions(dust_amppi_batch *b, float *actions)
   HIP_TRY(hipSetDevice(b->c->cfg.device));
   TRY(rows_d2h(b->B, b->c->stream, actions, b->acts, (size_t)b->c->S * b->c->D, b->last_active.empty() ? nullptr : b->last_active.data()));
   HIP_TRY(hipStreamSynchronize(b->c->stream));
+  return DUST_OK;
+}
+
+// T closed-loop periods (tick, plant step, records, roll) of every active environment: amppi_episode.hpp.  One launch of the period
+// kernel per period, chained on the batch's stream behind ONE memset of the arrival words; the parameter rows [T][B][rows][P] are
+// staged once and period t reads its slice; the call waits once, for the records.
+// DUST_AMPPI_EPISODE_MAX_FLOATS bounds the staged rows and the records (each at most 2^28 floats, 1 GiB): a longer episode is split.
+static constexpr size_t DUST_AMPPI_EPISODE_MAX_FLOATS = (size_t)1 << 28;
+extern "C" int dust_amppi_batch_episode(dust_amppi_batch *b, const float *states, int n_periods, const float *params, int flags, int roll_steps,
+                                        const float *plant_params, const unsigned char *active, float *states_out, float *actions_out,
+                                        float *costs_out, float *omega_out, float *a_seq) {
+  TRY(batch_null(b));
+  if (!states || !states_out || !actions_out) return fail(DUST_ERR_INVALID, "null argument");
+  if (n_periods < 1 || n_periods > 4096)
+    return fail(DUST_ERR_INVALID, "n_periods = %d outside [1, 4096] (the queue of one call stays short on a shared device: split a longer episode)", n_periods);
+  if (roll_steps < 1) return fail(DUST_ERR_INVALID, "roll(steps = %d): steps >= 1", roll_steps);
+  if (flags & ~DUST_AMPPI_PARAMS_SHARED)
+    return fail(DUST_ERR_UNSUPPORTED,
+                "an AMPPI episode draws its noise on the device, reads host rows and stores neither trajectories nor binary16: "
+                "flags may hold DUST_AMPPI_PARAMS_SHARED alone (got %d)", flags);
+  dust_ctx *c = b->c;
+  TRY(amppi_check(c));
+  if (c->cfg.dim_p == 0 && plant_params) return fail(DUST_ERR_INVALID, "plant parameter rows without uncertain parameters (dim_p = 0)");
+  int mode = AMPPI_PARAMS_NONE, pts = 1;
+  size_t prows = 0;
+  TRY(amppi_params_mode(c, params != nullptr, flags, nullptr, &mode, &pts, &prows));
+  const size_t T = (size_t)n_periods, B = (size_t)b->B, S = (size_t)c->S, D = (size_t)c->D, P = (size_t)c->cfg.dim_p;
+  const size_t ds = (size_t)c->ds, da = (size_t)c->da;
+  const size_t per = B * prows * P;  // parameter values of one period
+  const size_t n_rec = T * B * (ds + da + (costs_out ? S : 0) + (omega_out ? S : 0)) + (a_seq ? B * D : 0);
+  if (T * per > DUST_AMPPI_EPISODE_MAX_FLOATS)
+    return fail(DUST_ERR_UNSUPPORTED, "%zu parameter values to stage for %d periods exceed %zu: split the episode into shorter calls", T * per, n_periods,
+                DUST_AMPPI_EPISODE_MAX_FLOATS);
+  if (n_rec > DUST_AMPPI_EPISODE_MAX_FLOATS)
+    return fail(DUST_ERR_UNSUPPORTED, "%zu record values for %d periods exceed %zu: split the episode into shorter calls (or leave costs / omega out)", n_rec,
+                n_periods, DUST_AMPPI_EPISODE_MAX_FLOATS);
+  const bool nav = skid_nav_on(c);
+  SkidNav nv;
+  memset(&nv, 0, sizeof nv);
+  if (nav) TRY(skid_nav_args(c, nv));
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  // ---- room, then everything staged once
+  if (prows) TRY(b->params.ensure(T * per));
+  if (plant_params) TRY(b->plant.ensure(B * P));
+  TRY(b->rec.ensure(n_rec));
+  if (prows) TRY(h2d(c, b->params, params, T * per * sizeof(float)));
+  if (plant_params) TRY(h2d(c, b->plant, plant_params, B * P * sizeof(float)));
+  TRY(b->in.stage(c, states, active));
+  HIP_TRY(hipMemsetAsync(b->ticket, 0, B * sizeof(unsigned int), c->stream));
+  // ---- the periods
+  AmppiPeriodArgs kp;
+  memset(&kp.ep, 0, sizeof kp.ep);  // (no filters: the dual episode's fields stay NULL)
+  batch_tick_args(b, mode, pts, prows, true, active, kp.k);
+  float *rec_s = b->rec, *rec_a = rec_s + T * B * ds, *rec_c = rec_a + T * B * da, *rec_o = rec_c + (costs_out ? T * B * S : 0);
+  float *rec_q = rec_o + (omega_out ? T * B * S : 0);
+  const long shift = (long)roll_steps * c->da;
+  kp.ep.plant = plant_params ? b->plant.get() : nullptr;
+  kp.ep.state = const_cast<float *>(b->in.states_dev());
+  kp.ep.shift = shift > c->D ? c->D : (int)shift;
+  const dim3 grid((unsigned)((S + AMPPI_THREADS - 1) / AMPPI_THREADS), (unsigned)B);
+  const size_t map_lds = nav ? (size_t)nv.grid_words * sizeof(uint32_t) : 0;
+  // (ahead of the chain: should a launch in its middle fail, the periods before it have run - sequences, stream positions and the device
+  // state rows have advanced, no record comes back - and dust_amppi_batch_get_actions speaks of this call's environments)
+  b->acts_valid = true;
+  if (active) b->last_active.assign(active, active + B);
+  else b->last_active.clear();
+  for (size_t t = 0; t < T; ++t) {
+    kp.k.a.params = prows ? b->params.get() + t * per : nullptr;
+    kp.ep.states_out = rec_s + t * B * ds;
+    kp.ep.actions_out = rec_a + t * B * da;
+    kp.ep.costs_out = costs_out ? rec_c + t * B * S : nullptr;
+    kp.ep.omega_out = omega_out ? rec_o + t * B * S : nullptr;
+    kp.ep.a_seq_out = a_seq && t + 1 == T ? rec_q : nullptr;
+    Prof pr(c, DUST_K_AMPPI);
+    if (nav) HIP_TRY(launch_on(c->stream, false, &amppi_skid_nav_period_kernel, grid, AMPPI_THREADS, map_lds, AmppiNavPeriodArgs{kp.k, nv, kp.ep}));
+    else HIP_TRY(by_model(c, [&](auto M) { return launch_on(c->stream, false, &amppi_period_kernel<M()>, grid, AMPPI_THREADS, 0, kp); }));
+  }
+  // ---- the records come back once; the rows of inactive environments stay out of the caller's arrays
+  std::vector<float> host(n_rec);
+  HIP_TRY(hipMemcpyAsync(host.data(), b->rec, n_rec * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  auto rows = [&](float *dst, const float *src, size_t n, size_t row) {
+    for (size_t t = 0; t < n; ++t)
+      for (size_t e = 0; e < B; ++e)
+        if (!active || active[e]) memcpy(dst + (t * B + e) * row, src + (t * B + e) * row, row * sizeof(float));
+  };
+  rows(states_out, host.data() + (rec_s - b->rec.get()), T, ds);
+  rows(actions_out, host.data() + (rec_a - b->rec.get()), T, da);
+  if (costs_out) rows(costs_out, host.data() + (rec_c - b->rec.get()), T, S);
+  if (omega_out) rows(omega_out, host.data() + (rec_o - b->rec.get()), T, S);
+  if (a_seq) rows(a_seq, host.data() + (rec_q - b->rec.get()), 1, D);
   return DUST_OK;
 }
 

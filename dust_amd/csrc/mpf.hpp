@@ -2517,6 +2517,36 @@ extern "C" int dust_svmpc_dual_batch_tick(dust_svmpc_batch *b, dust_mpf_batch *m
   return dual_batch_close(c, mb, copies);
 }
 
+// The epilogue of a dual episode (dust_svmpc_dual_batch_episode, dust_amppi_dual_batch_episode) behind its one wait: bw_out where it is
+// answered on the host, and the filters' host rows moved to where T ticks leave them, from the MpfEnvIn rows read back (in_host)
+static void dual_episode_commit(dust_mpf_batch *mb, MpfbRows &rows, const std::vector<dust::MpfEnvIn> &in_host, size_t T, bool first, bool silverman,
+                                float mpf_bw, const unsigned char *active, float *bw_out) {
+  const size_t B = (size_t)mb->B;
+  for (size_t e = 0; e < B; ++e) {
+    if (active && !active[e]) continue;
+    if (bw_out) {  // what bw_used of the period's dual tick is: 0 without an update, the fixed bandwidth, or Silverman's (recorded above)
+      if (!first) bw_out[e] = 0.f;
+      if (!silverman)
+        for (size_t t = first ? 0 : 1; t < T; ++t) bw_out[t * B + e] = mpf_bw;
+    }
+    // the filters' host rows: what the last update read, and the steps taken since
+    const dust::MpfEnvIn &r = in_host[e];
+    float *loc = &rows.loc[e * 5], *past = &rows.past_obs[e * 5];
+    if (T > 1) {  // (conditioned on the device at least once: condition() copies the five-wide row, whose fifth column no state here reaches)
+      past[4] = loc[4];
+      rows.have_past[e] = 1;
+    }
+    for (int q = 0; q < 4; ++q) {
+      loc[q] = r.obs[q];
+      past[q] = r.past_obs[q];
+    }
+    rows.past_action[e * 2] = r.past_action[0];
+    rows.past_action[e * 2 + 1] = r.past_action[1];
+    rows.opt_t[e] = r.t0;
+  }
+  mpfb_commit(mb, rows);
+}
+
 // T control periods of the DuSt-MPC loop (simulations.py:104-138) for B environments in one call: T successive dust_svmpc_dual_batch_tick
 // calls with device-drawn noise, and between them the plant of dust_svmpc_batch_episode - x_{t+1} = step(x_t, a_t) under the true rows
 // plant_params - stepped on the device.  Everything is staged once (states and mask through the controller batch's pinned slot; the
@@ -2623,28 +2653,148 @@ extern "C" int dust_svmpc_dual_batch_episode(dust_svmpc_batch *b, dust_mpf_batch
   out(actions_out, host.data() + T * B * ds, da);
   if (pw_out) out(pw_out, host.data() + T * B * (ds + da), N);
   if (bw_dev) out(bw_out, host.data() + T * B * (ds + da + (pw_out ? N : 0)), 1);
-  for (size_t e = 0; e < B; ++e) {
-    if (active && !active[e]) continue;
-    if (bw_out) {  // what bw_used of the period's dual tick is: 0 without an update, the fixed bandwidth, or Silverman's (recorded above)
-      if (!first) bw_out[e] = 0.f;
-      if (!silverman)
-        for (size_t t = first ? 0 : 1; t < T; ++t) bw_out[t * B + e] = mpf_bw;
+  dual_episode_commit(mb, rows, in_host, T, first, silverman, mpf_bw, active, bw_out);
+  return DUST_OK;
+}
+
+// T control periods of the dual loop over the AMPPI batch for B environments in one call: T successive dust_amppi_dual_batch_tick calls
+// with device-drawn noise and roll_steps >= 1, and between them the plant of dust_amppi_batch_episode, stepped on the device.  Staged
+// once as in dust_svmpc_dual_batch_episode (states and mask through the controller batch's pinned slot; MpfEnvIn rows, seeds [T][B] and
+// plant rows through the filter batch's); then, on the controller batch's stream and in launch order, period t is: Silverman's rule and
+// the filters' update (when the period has an action), reading the MpfEnvIn rows in device memory; in the single and sigma modes the
+// staging launch of the tick's parameter rows under the key row prior_seeds + t B; ONE launch of the period kernel (amppi_episode.hpp:
+// amppi_prior_period_kernel in the "extended" mode, amppi_period_kernel on b->params otherwise), whose reducer also conditions the
+// environment's MpfEnvIn row for period t + 1.  No host wait, event or copy lies between two periods; the call waits once, reads the
+// rows back and commits them as the SVMPC episode does (dual_episode_commit): the pair (a_{T-1}, x_T) is NOT folded in.
+extern "C" int dust_amppi_dual_batch_episode(dust_amppi_batch *b, dust_mpf_batch *mb, const float *states, const float *actions_prev, int n_periods,
+                                             int flags, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds, int roll_steps, const float *plant_params,
+                                             const unsigned char *active, float *states_out, float *actions_out, float *costs_out, float *omega_out,
+                                             float *bw_out, float *a_seq) {
+  if (!b || !mb || !states || !states_out || !actions_out) return fail(DUST_ERR_INVALID, "null argument");
+  if (!prior_seeds) return fail(DUST_ERR_INVALID, "null argument: the draws from the filters' priors need prior_seeds [T][B]");
+  if (n_periods < 1 || n_periods > 4096)
+    return fail(DUST_ERR_INVALID, "n_periods = %d outside [1, 4096] (the queue of one call stays short on a shared device: chain a longer episode)", n_periods);
+  if (mpf_steps < 0) return fail(DUST_ERR_INVALID, "bad step counts");
+  if (roll_steps < 1) return fail(DUST_ERR_INVALID, "roll(steps = %d): steps >= 1", roll_steps);
+  if (flags & ~DUST_AMPPI_PARAMS_SHARED)
+    return fail(DUST_ERR_UNSUPPORTED, "an AMPPI dual episode draws its noise on the device and stores neither trajectories nor binary16: flags may hold "
+                "DUST_AMPPI_PARAMS_SHARED alone (got %d)", flags);
+  dust_ctx *c = b->c;
+  dust_mpf *m = mb->m;
+  TRY(amppi_check(c));
+  if (c->cfg.dim_p == 0 && plant_params) return fail(DUST_ERR_INVALID, "plant parameter rows without uncertain parameters (dim_p = 0)");
+  TRY(dual_batch_pair_check(c, "AMPPI", b->B, mb));
+  bool sigma, shared;
+  TRY(amppi_dual_check(c, m, flags, &sigma, &shared));
+  auto host_lik = [](int model) { return model == DUST_MODEL_SKID_STEER || model == DUST_MODEL_CARTPOLE; };
+  if (host_lik(c->cfg.model) || host_lik(m->cfg.model_cfg.model))
+    return fail(DUST_ERR_UNSUPPORTED,
+                "a dual episode conditions the filters on the device: Pendulum and Particle pairs (a skid-steer or cart-pole filter's likelihood rows "
+                "carry the host's sin / cos of the past heading: dust_amppi_dual_batch_tick per period)");
+  const bool staged = sigma || shared;
+  int mode = AMPPI_PARAMS_NONE, pts = 1;
+  size_t prows = 0;
+  dust::AmppiPrior one;  // (amppi_params_mode reads the prior's P alone)
+  memset(&one, 0, sizeof one);
+  one.P = m->P;
+  TRY(amppi_params_mode(c, staged, flags, staged ? nullptr : &one, &mode, &pts, &prows));
+  TRY(mpfb_limits(m, mb->B));
+  const bool first = actions_prev != nullptr;  // period 0 has an update
+  if (first || n_periods > 1) TRY(mpfb_update_check(mb, first ? actions_prev : states, states, mpf_steps, active));
+  const size_t T = (size_t)n_periods, B = (size_t)b->B, S = (size_t)c->S, D = (size_t)c->D, P = (size_t)m->P, ds = (size_t)c->ds, da = (size_t)c->da;
+  const bool silverman = !(mpf_bw > 0.f);
+  const bool bw_dev = bw_out && silverman;
+  const size_t n_rec = T * B * (ds + da + (costs_out ? S : 0) + (omega_out ? S : 0) + (bw_dev ? 1 : 0)) + (a_seq ? B * D : 0);
+  if (n_rec > DUST_AMPPI_EPISODE_MAX_FLOATS)
+    return fail(DUST_ERR_UNSUPPORTED, "%zu record values for %d periods exceed %zu: split the episode into shorter calls (or leave costs / omega out)", n_rec,
+                n_periods, DUST_AMPPI_EPISODE_MAX_FLOATS);
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  TRY(settle_pending(c));
+  // ---- room (reallocations free behind the device's queued work)
+  TRY(mpfb_gn_room(mb, mpf_steps));
+  const size_t off_seeds = B * sizeof(dust::MpfEnvIn), off_plant = off_seeds + T * B * sizeof(uint64_t), n_stage = off_plant + B * P * sizeof(float);
+  TRY(mb->ep.ensure(n_stage));
+  if (mb->ep_host.cap() < n_stage) TRY(mb->ep_host.alloc(n_stage, hipHostMallocDefault));
+  if (staged) TRY(b->params.ensure(B * prows * P));
+  TRY(b->rec.ensure(n_rec));
+  // ---- staged once
+  TRY(b->in.stage(c, states, active));
+  unsigned char *hb = mb->ep_host;  // (free: every call that wrote it has waited for its stream)
+  MpfbRows rows;
+  mpfb_rows(mb, actions_prev, first ? states : nullptr, first ? mpf_steps : 0, active, hb, rows);
+  memcpy(hb + off_seeds, prior_seeds, T * B * sizeof(uint64_t));
+  if (plant_params) memcpy(hb + off_plant, plant_params, B * P * sizeof(float));
+  HIP_TRY(hipStreamWaitEvent(c->stream, mb->ev_ext, 0));
+  HIP_TRY(hipMemcpyAsync(mb->ep, hb, plant_params ? n_stage : off_plant, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(b->ticket, 0, B * sizeof(unsigned int), c->stream));
+  if (first || n_periods > 1) serve_cancel_device(m->cfg.device);  // (as mpfb_enqueue, once for the call)
+  // ---- the periods
+  dust::MpfEnvIn *in_dev = mpfb_in_view(mb->ep.get());
+  const uint64_t *seeds_dev = reinterpret_cast<const uint64_t *>(mb->ep.get() + off_seeds);
+  const unsigned char *mask = b->in.mask_dev(active);
+  AmppiPriorPeriodArgs ka;
+  batch_tick_args(b, mode, pts, prows, true, active, ka.k);
+  dual_batch_prior(mb, nullptr, ka.pr);
+  memset(&ka.ep, 0, sizeof ka.ep);
+  float *rec_s = b->rec, *rec_a = rec_s + T * B * ds, *rec_c = rec_a + T * B * da, *rec_o = rec_c + (costs_out ? T * B * S : 0);
+  float *rec_bw = rec_o + (omega_out ? T * B * S : 0), *rec_q = rec_bw + (bw_dev ? T * B : 0);
+  const long shift = (long)roll_steps * c->da;
+  ka.ep.plant = plant_params ? reinterpret_cast<const float *>(mb->ep.get() + off_plant) : nullptr;
+  ka.ep.state = const_cast<float *>(b->in.states_dev());
+  ka.ep.shift = shift > c->D ? c->D : (int)shift;
+  ka.ep.in = in_dev;
+  const dim3 grid((unsigned)((S + AMPPI_THREADS - 1) / AMPPI_THREADS), (unsigned)B);
+  b->acts_valid = true;  // (ahead of the chain, as in dust_amppi_batch_episode)
+  if (active) b->last_active.assign(active, active + B);
+  else b->last_active.clear();
+  for (size_t t = 0; t < T; ++t) {
+    const bool update = t > 0 || first;
+    if (update) TRY(mpfb_update_launch(mb, c->stream, in_dev, mask, mpf_bw, mpf_steps));
+    mb->n_calls++;
+    if (staged) {
+      if (sigma) dust::mpf_sigma_points_batch_kernel<<<b->B, 256, 0, c->stream>>>(mb->x, m->Mp, m->P, mb->prior_bwv, c->sigma_scale, b->params, mask);
+      else dust::mpf_sample_batch_kernel<<<(b->B + 255) / 256, 256, 0, c->stream>>>(mb->x, m->Mp, m->P, mb->prior_bwv, seeds_dev + t * B, b->B, b->params, mask);
+      HIP_TRY(hipGetLastError());
+      mb->n_launch++;
     }
-    // the filters' host rows: what the last update read, and the steps taken since
-    const dust::MpfEnvIn &r = in_host[e];
-    float *loc = &rows.loc[e * 5], *past = &rows.past_obs[e * 5];
-    if (T > 1) {  // (conditioned on the device at least once: condition() copies the five-wide row, whose fifth column no state here reaches)
-      past[4] = loc[4];
-      rows.have_past[e] = 1;
-    }
-    for (int q = 0; q < 4; ++q) {
-      loc[q] = r.obs[q];
-      past[q] = r.past_obs[q];
-    }
-    rows.past_action[e * 2] = r.past_action[0];
-    rows.past_action[e * 2 + 1] = r.past_action[1];
-    rows.opt_t[e] = r.t0;
+    ka.pr.seeds = seeds_dev + t * B;
+    ka.ep.states_out = rec_s + t * B * ds;
+    ka.ep.actions_out = rec_a + t * B * da;
+    ka.ep.costs_out = costs_out ? rec_c + t * B * S : nullptr;
+    ka.ep.omega_out = omega_out ? rec_o + t * B * S : nullptr;
+    ka.ep.a_seq_out = a_seq && t + 1 == T ? rec_q : nullptr;
+    ka.ep.bw = bw_dev && update ? mb->bw.get() : nullptr;
+    ka.ep.bw_out = bw_dev ? rec_bw + t * B : nullptr;
+    ka.ep.t0_add = update ? mpf_steps : 0;
+    ka.ep.condition = t + 1 < T ? 1 : 0;
+    Prof pr(c, DUST_K_AMPPI);
+    const hipError_t launched = by_model(c, [&](auto M) -> hipError_t {
+      if constexpr (M() == DUST_MODEL_PENDULUM || M() == DUST_MODEL_PARTICLE) {
+        if (staged) return launch_on(c->stream, false, &amppi_period_kernel<M()>, grid, AMPPI_THREADS, 0, AmppiPeriodArgs{ka.k, ka.ep});
+        return launch_on(c->stream, false, &amppi_prior_period_kernel<M()>, grid, AMPPI_THREADS, 0, ka);
+      } else return hipErrorInvalidValue;  // (refused above)
+    });
+    HIP_TRY(launched);
   }
-  mpfb_commit(mb, rows);
+  // ---- the records and the advanced rows come back once; the rows of inactive environments stay out of the caller's arrays
+  std::vector<float> host(n_rec);
+  std::vector<dust::MpfEnvIn> in_host(B);
+  HIP_TRY(hipMemcpyAsync(host.data(), b->rec, n_rec * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(in_host.data(), in_dev, B * sizeof(dust::MpfEnvIn), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipEventRecord(mb->ev_ext, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  auto out = [&](float *dst, const float *dev, size_t n, size_t row) {
+    const float *src = host.data() + (dev - b->rec.get());
+    for (size_t t = 0; t < n; ++t)
+      for (size_t e = 0; e < B; ++e)
+        if (!active || active[e]) memcpy(dst + (t * B + e) * row, src + (t * B + e) * row, row * sizeof(float));
+  };
+  out(states_out, rec_s, T, ds);
+  out(actions_out, rec_a, T, da);
+  if (costs_out) out(costs_out, rec_c, T, S);
+  if (omega_out) out(omega_out, rec_o, T, S);
+  if (bw_dev) out(bw_out, rec_bw, T, 1);
+  if (a_seq) out(a_seq, rec_q, 1, D);
+  dual_episode_commit(mb, rows, in_host, T, first, silverman, mpf_bw, active, bw_out);
   return DUST_OK;
 }

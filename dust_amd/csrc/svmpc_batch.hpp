@@ -113,8 +113,9 @@ __device__ __forceinline__ void svb_sync() {
 }
 
 // what one dynamics sample keeps constant over its rollouts -> cf[SVB_COEF]
-template <int MODEL>
-__device__ __forceinline__ void svb_coef(const SvmpcBatchArgs &a, const float *prow, float *cf) {
+// ARGS: SvmpcBatchArgs, or an AMPPI environment's view (amppi_episode.hpp): the members dm, sk, cp and dt under the same names
+template <int MODEL, class ARGS>
+__device__ __forceinline__ void svb_coef(const ARGS &a, const float *prow, float *cf) {
   if constexpr (MODEL == DUST_MODEL_PENDULUM || MODEL == DUST_MODEL_PARTICLE) {
     const Coef c = make_coef(a.dm, prow);
     cf[0] = c.c0;

@@ -50,8 +50,9 @@ struct SvmpcNavEpisodeArgs {
 };
 
 // x <- step(x, act) of the family's plant under the coefficients cf (svb_coef); `act` is the raw action
-template <int MODEL>
-__device__ __forceinline__ void svb_plant_step(const SvmpcBatchArgs &a, const float *cf, float *x, const float *act) {
+// ARGS: as svb_coef's
+template <int MODEL, class ARGS>
+__device__ __forceinline__ void svb_plant_step(const ARGS &a, const float *cf, float *x, const float *act) {
   if constexpr (MODEL == DUST_MODEL_PENDULUM || MODEL == DUST_MODEL_PARTICLE) {
     Coef c;
     c.c0 = cf[0];

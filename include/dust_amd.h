@@ -398,6 +398,28 @@ int dust_amppi_batch_update(dust_amppi_batch *batch, const float *states, const 
 int dust_amppi_batch_roll(dust_amppi_batch *batch, int steps, const unsigned char *active);
 /* The actions the last tick used, [B][S][H][da]; the rows of environments that were inactive in that tick are not written. */
 int dust_amppi_batch_get_actions(dust_amppi_batch *batch, float *actions);
+/* dust_amppi_batch_episode: n_periods closed-loop periods of every active environment, the plants stepped on the device - what the
+ * reference's run_pendulum_simulation / run_particle_episode loop does per period (update_actions, the plant's step with the first
+ * planned action, roll), without the host between two periods.  Period t is ONE launch (amppi_episode.hpp): the tick of
+ * dust_amppi_batch_update with device-drawn noise from the state the previous period left, x <- step(x, a_seq[0]) under the environment's
+ * true parameters through the family's own device step, the records, and dust_amppi_batch_roll(roll_steps).  The launches are chained on
+ * the batch's stream behind one memset of the arrival words; the call waits once, for the records.
+ *   states [B][ds], host: where the episodes start;
+ *   params by mode, host, as dust_amppi_batch_update takes them with a leading [T]: NULL; [T][B][1][P] with DUST_AMPPI_PARAMS_SHARED;
+ *     [T][B][S][P]; [T][B][2P + 1][P] sigma points.  Staged ONCE ahead of the first launch: at most 2^28 values (1 GiB) - and at most 2^28
+ *     record values - per call, beyond which the call refuses with DUST_ERR_UNSUPPORTED and asks for a split episode;
+ *   flags: DUST_AMPPI_PARAMS_SHARED alone (recorded actions, DUST_PTR_DEVICE, DUST_STORE_STATES, binary16: DUST_ERR_UNSUPPORTED);
+ *   roll_steps >= 1; n_periods in [1, 4096];
+ *   plant_params [B][P], host: every environment's TRUE parameter row, in the columns of `params`; NULL: the prototype's nominal model;
+ *   active [B] bytes or NULL (all): inactive environments keep everything, and their rows of the outputs are NOT written;
+ *   states_out [T][B][ds] (the state after every step) and actions_out [T][B][da] (the first action of the updated, clamped sequence)
+ *     are required; costs_out / omega_out [T][B][S] and a_seq [B][H][da] (the last period's sequence BEFORE its roll) may be NULL.
+ * Afterwards the batch is where n_periods x (dust_amppi_batch_update on the recorded states, dust_amppi_batch_roll) leave it, bit for
+ * bit: sequences, stream positions, dust_amppi_batch_get_actions (the last period's); the profile counts n_periods DUST_K_AMPPI launches
+ * and no DUST_K_FORWARD launch.  Every refusal comes before anything is staged or launched. */
+int dust_amppi_batch_episode(dust_amppi_batch *batch, const float *states, int n_periods, const float *params, int flags, int roll_steps,
+                             const float *plant_params, const unsigned char *active, float *states_out, float *actions_out, float *costs_out,
+                             float *omega_out, float *a_seq);
 
 /* ---- SVMPC over a batch of plants: B independent SVMPC controllers of one configuration, ONE kernel launch per call (ABI 3, additive) ----
  * The reference evaluates a controller over many episodes with a deep copy of the controller each (simulations.py:62,78); a batch is
@@ -714,6 +736,20 @@ int dust_mpf_batch_optimize(dust_mpf_batch *batch, const float *actions, const f
 int dust_amppi_dual_batch_tick(dust_amppi_batch *batch, dust_mpf_batch *mpf, const float *states, const float *actions_prev, const float *actions,
                                int flags, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds, int roll_steps, const unsigned char *active,
                                float *costs, float *omega, float *a_seq, float *params_out, float *bw_used);
+/* dust_amppi_dual_batch_episode: n_periods periods of the dual loop over the AMPPI batch with the plants on the device - what n_periods
+ * dust_amppi_dual_batch_tick calls with device-drawn noise and roll_steps >= 1 compute, with x_{t+1} = step(x_t, a_t) under the true
+ * rows plant_params between them (dust_amppi_batch_episode's plant).  Arguments as that tick's, minus `actions`; prior_seeds [T][B]:
+ * period t draws under row t; the records as dust_amppi_batch_episode's plus bw_out [T][B] (the bandwidth every period's update ran
+ * with; 0: no update).  Per period, on the controller batch's stream: Silverman's rule and the filters' update reading their rows in
+ * device memory, in the single and sigma modes the staging launch of the parameter rows, ONE launch of the period kernel, whose reducer
+ * also conditions the environment's filter row for the next period.  The call waits once; afterwards both batches are where the ticks
+ * leave them, and the pair (a_{T-1}, x_T) stays pending: pass actions_out[T - 1] as actions_prev of the next call.
+ * Pendulum and Particle pairs; a skid-steer or cart-pole pair is DUST_ERR_UNSUPPORTED (their likelihood rows carry host fp64
+ * trigonometry), as is every flag but DUST_AMPPI_PARAMS_SHARED.  Every refusal comes before anything is staged or launched. */
+int dust_amppi_dual_batch_episode(dust_amppi_batch *batch, dust_mpf_batch *mpf, const float *states, const float *actions_prev, int n_periods,
+                                  int flags, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds, int roll_steps, const float *plant_params,
+                                  const unsigned char *active, float *states_out, float *actions_out, float *costs_out, float *omega_out,
+                                  float *bw_out, float *a_seq);
 /* One control period of the DuSt-MPC loop for B environments in one call = B x dust_dual_tick, on the SVMPC batch's stream in launch
  * order with no event, no synchronisation and no host round trip between the filters and the ticks; the number of kernel launches does
  * not depend on B.  states [B][ds]; actions_prev [B][da] or NULL (no filter update: the first period); mpf_bw <= 0: Silverman's rule per
