@@ -92,6 +92,11 @@ class OptimConfig(C.Structure):
         "lr", "beta1", "beta2", "eps", "weight_decay", "momentum", "dampening", "alpha", "lr_decay", "initial_accumulator_value")]
 
 
+class SvmpcHyper(C.Structure):  # dust_svmpc_hyper: one environment's row of dust_svmpc_batch_set_hyper
+    _fields_ = [("lr", C.c_double), ("alpha", C.c_float), ("temperature", C.c_float), ("sigma_a", C.c_float * 2), ("chol_a", C.c_float * 2),
+                ("sigma_p", C.c_float * 2), ("weighted_prior", C.c_int)]
+
+
 FP = C.POINTER(C.c_float)
 VP = C.c_void_p
 
@@ -160,6 +165,8 @@ SYMBOLS = {
     "dust_svmpc_batch_forward": (C.c_int, [VP, C.POINTER(C.c_ubyte), FP, FP]),
     "dust_svmpc_batch_tick": (C.c_int, [VP, FP, C.c_int, VP, FP, C.c_int, C.POINTER(C.c_ubyte), FP, FP]),
     "dust_svmpc_batch_episode": (C.c_int, [VP, FP, C.c_int, C.c_int, FP, FP, C.c_int, C.POINTER(C.c_ubyte), FP, FP, FP, FP]),
+    "dust_svmpc_batch_set_hyper": (C.c_int, [VP, C.POINTER(SvmpcHyper)]),
+    "dust_svmpc_batch_get_hyper": (C.c_int, [VP, C.POINTER(SvmpcHyper)]),
     "dust_mpf_batch_create": (C.c_int, [VP, C.c_int, C.POINTER(VP)]),
     "dust_mpf_batch_destroy": (None, [VP]),
     "dust_mpf_batch_clone": (C.c_int, [VP, C.POINTER(VP)]),

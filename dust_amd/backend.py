@@ -906,6 +906,52 @@ class SvmpcBatch(_BatchHandle):
         L.check(L.load().dust_svmpc_batch_get(self._h, int(what), _p(out)))
         return out
 
+    HYPER_FIELDS = ("lr", "alpha", "temperature", "sigma_a", "chol_a", "sigma_p", "weighted_prior")
+
+    def set_hyper(self, rows):
+        """Per-environment hyper-parameters (dust_svmpc_batch_set_hyper): `rows` is a dict with every key of HYPER_FIELDS - lr, alpha,
+        temperature and weighted_prior [B], the three sigmas [B], [B, 1] or [B, da] (diagonal) - or None: back to the prototype's values.
+        While rows are set, optimize / forward / tick / episode run environment b under row b; the library refuses invalid rows."""
+        if rows is None:
+            L.check(L.load().dust_svmpc_batch_set_hyper(self._h, None))
+            return
+        B = self.B
+        if sorted(rows) != sorted(self.HYPER_FIELDS):
+            raise ValueError("rows has the keys %s, a row has %s" % (sorted(rows), sorted(self.HYPER_FIELDS)))
+        cols = {}
+        for k in self.HYPER_FIELDS:
+            v = np.asarray(rows[k], np.float64 if k == "lr" else (np.int64 if k == "weighted_prior" else np.float32))
+            if k in ("sigma_a", "chol_a", "sigma_p"):
+                v = v.reshape(B, -1) if v.size in (B, B * self.da) else v
+                if v.shape not in ((B, 1), (B, self.da)):
+                    raise ValueError("%s has shape %s for %d environments with dim_a = %d" % (k, v.shape, B, self.da))
+                v = np.broadcast_to(v, (B, self.da))
+                v = np.concatenate([v, v[:, :1]], 1) if self.da == 1 else v  # (dim_a = 1: entry 1 repeats entry 0, nothing reads it)
+            elif v.shape != (B,):
+                raise ValueError("%s has shape %s for %d environments" % (k, v.shape, B))
+            cols[k] = v
+        arr = (L.SvmpcHyper * B)()
+        for b in range(B):
+            r = arr[b]
+            r.lr, r.alpha, r.temperature = float(cols["lr"][b]), float(cols["alpha"][b]), float(cols["temperature"][b])
+            r.weighted_prior = int(cols["weighted_prior"][b])
+            for k in ("sigma_a", "chol_a", "sigma_p"):
+                getattr(r, k)[:] = [float(cols[k][b, 0]), float(cols[k][b, 1])]
+        L.check(L.load().dust_svmpc_batch_set_hyper(self._h, arr))
+
+    def get_hyper(self):
+        """The rows in force as a dict of arrays (dust_svmpc_batch_get_hyper): lr [B] float64, alpha / temperature [B], sigma_a / chol_a /
+        sigma_p [B, da], weighted_prior [B] int32; the prototype's values where no rows are set."""
+        B = self.B
+        arr = (L.SvmpcHyper * B)()
+        L.check(L.load().dust_svmpc_batch_get_hyper(self._h, arr))
+        out = {"lr": np.array([r.lr for r in arr], np.float64), "alpha": np.array([r.alpha for r in arr], np.float32),
+               "temperature": np.array([r.temperature for r in arr], np.float32),
+               "weighted_prior": np.array([r.weighted_prior for r in arr], np.int32)}
+        for k in ("sigma_a", "chol_a", "sigma_p"):
+            out[k] = np.array([list(getattr(r, k))[:self.da] for r in arr], np.float32).reshape(B, self.da)
+        return out
+
     def _inputs(self, states, n_steps, eps, params, eps_dev_ptr, keep_actions):
         B = self.B
         st = None if states is None else _f(states, (B, self.ds))  # (None: the library refuses)

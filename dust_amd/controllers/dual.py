@@ -466,8 +466,15 @@ class BatchDualSVMPC(_BatchDual):
             raise ValueError("BatchDualSVMPC needs a controller that samples dynamics parameters: params_sampling=None reads no filter")
         if mpf.draw_source is not None:
             raise NotImplementedError("recorded filter draws (draw_source) have no batched form")
+        self._no_rows(svmpc)
         _BatchDual.__init__(self, svmpc.n_envs, mpf, mpf_bw, mpf_steps, seed, init_particles)
         self.svmpc, self.n_steps = svmpc, n_steps
+
+    @staticmethod
+    def _no_rows(svmpc):
+        """the dual loop's kernels read launch-uniform hyper-parameters: refused ahead of any device call"""
+        if getattr(svmpc, "_hyper", None) is not None:
+            raise NotImplementedError("the dual loop has no per-environment hyper-parameters: BatchSVMPC.set_hyper() with no argument first")
 
     def _copy_parts(self, new, memo):
         new.svmpc = copy.deepcopy(self.svmpc, memo)
@@ -487,6 +494,7 @@ class BatchDualSVMPC(_BatchDual):
         from ..inference.svmpc import check_optimizer
 
         sv = self.svmpc
+        self._no_rows(sv)
         check_optimizer(sv.optimizer, sv._opt_group)
         batch = sv._ensure_batch(self.mpf.prior)
         n_steps = sv.n_steps if self.n_steps is None else self.n_steps
@@ -526,6 +534,7 @@ class BatchDualSVMPC(_BatchDual):
         from ..models import CartPoleModel, SkidSteerRobot
 
         sv = self.svmpc
+        self._no_rows(sv)
         T = int(n_periods)
         if not 1 <= T <= 4096:
             raise ValueError("n_periods = %d outside [1, 4096]: one call runs one episode piece, chain a longer one" % T)

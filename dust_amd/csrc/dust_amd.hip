@@ -5470,7 +5470,47 @@ struct dust_svmpc_batch {
   DevBuf<float> plant, rec;        // dust_svmpc_batch_episode: [B][P] true parameter rows; the records [T][B][ds], [T][B][da], [T][B][N]
   BatchInputs in;             // per-call inputs
   bool have_costs, have_forward, acts_kept;
+  std::vector<dust_svmpc_hyper> hyper;  // dust_svmpc_batch_set_hyper: the caller's rows [B], or empty (every environment: the prototype's)
+  DevBuf<SvbHyper> hyper_dev;           // ... what the sweep instances read of them
 };
+
+// What an environment without a row of its own runs under: the prototype's values of the fields a dust_svmpc_hyper row overrides
+static dust_svmpc_hyper svb_proto_hyper(const dust_ctx *c) {
+  dust_svmpc_hyper h;
+  memset(&h, 0, sizeof h);
+  h.lr = c->opt.lr;
+  h.alpha = c->cfg.alpha;
+  h.temperature = c->cfg.temperature;
+  for (int d = 0; d < 2; ++d) {
+    const int dd = d < c->da ? d : 0;
+    h.sigma_a[d] = c->cfg.sigma_a[dd];
+    h.chol_a[d] = c->cfg.chol_a[dd];
+    h.sigma_p[d] = c->cfg.sigma_p[dd];
+  }
+  h.weighted_prior = c->cfg.weighted_prior ? 1 : 0;
+  return h;
+}
+// THE function that makes what a kernel reads of a row - the prior's reciprocals and its normalisation constant among it - for the
+// prototype (svb_args) and for every environment's row (dust_svmpc_batch_set_hyper) alike: equal values, equal bits
+static SvbHyper svb_hyper_row(const dust_ctx *c, const dust_svmpc_hyper &h) {
+  SvbHyper r;
+  memset(&r, 0, sizeof r);
+  r.lr = h.lr;
+  r.alpha = h.alpha;
+  r.temp = h.temperature;
+  double logdet = 0;
+  for (int d = 0; d < 2; ++d) {
+    const int dd = d < c->da ? d : 0;  // (dim_a = 1: entry 1 repeats entry 0, no kernel reads it)
+    r.chol_a[d] = h.chol_a[dd];
+    r.sigma_a[d] = h.sigma_a[dd];
+    r.inv_sp[d] = 1.0f / h.sigma_p[dd];
+    r.inv_sp2[d] = 1.0f / (h.sigma_p[dd] * h.sigma_p[dd]);
+    if (d < c->da) logdet += log((double)h.sigma_p[d]);
+  }
+  r.log_norm = (float)(-c->H * logdet - 0.5 * c->D * log(2.0 * M_PI));  // (prior_merge_args' constant)
+  r.weighted_prior = h.weighted_prior;
+  return r;
+}
 
 // the box of svmpc_batch.hpp
 static int svb_check(const dust_ctx *c) {
@@ -5587,6 +5627,11 @@ extern "C" int dust_svmpc_batch_clone(const dust_svmpc_batch *src, dust_svmpc_ba
   for (auto &e : cp)
     if (st == DUST_OK && e.dst && e.s) st = d2d(inner, e.dst, e.s, e.bytes);
   if (st == DUST_OK && src->acts_kept) st = d2d(inner, b->acts, src->acts, B * S * N * D * f);
+  if (st == DUST_OK && !src->hyper.empty()) {  // the per-environment rows travel with the batch
+    st = b->hyper_dev.alloc(B);
+    if (st == DUST_OK) st = d2d(inner, b->hyper_dev, src->hyper_dev, B * sizeof(SvbHyper));
+    if (st == DUST_OK) b->hyper = src->hyper;
+  }
   if (st == DUST_OK) {
     b->have_costs = src->have_costs;
     b->have_forward = src->have_forward;
@@ -5669,6 +5714,44 @@ extern "C" int dust_svmpc_batch_get(dust_svmpc_batch *b, int what, float *out) {
   }
 }
 
+// Per-environment hyper-parameters: the B trials of a tuning sweep (the reference's demo/pendulum_tuning.py:30-143, demo/particle_tuning.py:
+// 27-99) as the environments of one batch.  The rows are checked whole before anything is stored; nothing else of the batch is touched.
+extern "C" int dust_svmpc_batch_set_hyper(dust_svmpc_batch *b, const dust_svmpc_hyper *rows) {
+  if (!b) return fail(DUST_ERR_INVALID, "null batch");
+  dust_ctx *c = b->c;
+  if (!rows) {  // back to the prototype's: the uniform instances serve the next call
+    b->hyper.clear();
+    return DUST_OK;
+  }
+  const size_t B = (size_t)b->B;
+  std::vector<SvbHyper> dev(B);
+  for (size_t e = 0; e < B; ++e) {
+    const dust_svmpc_hyper &h = rows[e];
+    auto pos = [](double v) { return std::isfinite(v) && v > 0.0; };
+    bool ok = pos(h.lr) && pos((double)h.alpha) && pos((double)h.temperature) && (h.weighted_prior == 0 || h.weighted_prior == 1);
+    for (int d = 0; d < 2; ++d) {
+      if (d < c->da) ok = ok && pos((double)h.sigma_a[d]) && pos((double)h.chol_a[d]) && pos((double)h.sigma_p[d]);
+      else ok = ok && std::isfinite(h.sigma_a[d]) && std::isfinite(h.chol_a[d]) && std::isfinite(h.sigma_p[d]);  // (ignored, but finite)
+    }
+    if (!ok)
+      return fail(DUST_ERR_INVALID, "hyper-parameter row %zu: lr, alpha, temperature, sigma_a, chol_a and sigma_p must be finite and > 0, weighted_prior 0 or 1", e);
+    dev[e] = svb_hyper_row(c, h);
+  }
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  TRY(b->hyper_dev.ensure(B));
+  TRY(h2d(c, b->hyper_dev, dev.data(), B * sizeof(SvbHyper)));  // on the batch's stream, behind every launch that read the old rows
+  b->hyper.assign(rows, rows + B);
+  return DUST_OK;
+}
+
+extern "C" int dust_svmpc_batch_get_hyper(dust_svmpc_batch *b, dust_svmpc_hyper *rows) {
+  if (!b || !rows) return fail(DUST_ERR_INVALID, "null argument");
+  const size_t B = (size_t)b->B;
+  if (!b->hyper.empty()) std::copy(b->hyper.begin(), b->hyper.end(), rows);
+  else std::fill(rows, rows + B, svb_proto_hyper(b->c));
+  return DUST_OK;
+}
+
 // lane groups of phase C: the G that needs the fewest rounds of rollouts per lane (ties: the smaller), G N S partials in LDS
 static int svb_groups(int NS, int M) {
   auto rounds = [&](int g) { return (long)((NS * (long)g + SVB_THREADS - 1) / SVB_THREADS) * ((M + g - 1) / g); };
@@ -5692,6 +5775,10 @@ static int svb_call_check(const dust_svmpc_batch *b, const float *states, int n_
     if (c->cfg.dim_p == 0 && params) return fail(DUST_ERR_INVALID, "parameter rows without uncertain parameters (dim_p = 0)");
   }
   if (do_forward && n_steps == 0 && !b->have_costs) return fail(DUST_ERR_STATE, "forward() needs the costs of a previous optimize step");
+  if (!b->hyper.empty()) {  // per-environment rows: the plain tick and the plain episode have sweep instances, nothing else has
+    if (from_prior) return fail(DUST_ERR_UNSUPPORTED, "the dual loop has no per-environment hyper-parameters (dust_svmpc_batch_set_hyper(batch, NULL) first)");
+    if (skid_nav_on(c)) return fail(DUST_ERR_UNSUPPORTED, "the navigation cost family has no per-environment hyper-parameters (dust_svmpc_batch_set_hyper(batch, NULL) first)");
+  }
   return svb_check(c);
 }
 
@@ -5745,19 +5832,17 @@ static void svb_args(const dust_svmpc_batch *b, int n_steps, const float *eps_de
   k.weighted_prior = c->cfg.weighted_prior;
   k.G = svb_groups(c->N * c->S, c->M);
   k.Q = c->N * c->D >= SVB_THREADS ? 1 : std::max(1, std::min(SVB_THREADS / (c->N * c->D), c->S));
-  k.alpha = c->cfg.alpha;
-  k.temp = c->cfg.temperature;
   k.dt = (float)c->cfg.dt;
-  double logdet = 0;
+  const SvbHyper hr = svb_hyper_row(c, svb_proto_hyper(c));  // the launch-uniform values: the prototype's row
+  k.alpha = hr.alpha;
+  k.temp = hr.temp;
   for (int d = 0; d < 2; ++d) {
-    const int dd = d < c->da ? d : 0;
-    k.chol_a[d] = c->cfg.chol_a[dd];
-    k.sigma_a[d] = c->cfg.sigma_a[dd];
-    k.inv_sp[d] = 1.0f / c->cfg.sigma_p[dd];
-    k.inv_sp2[d] = 1.0f / (c->cfg.sigma_p[dd] * c->cfg.sigma_p[dd]);
-    if (d < c->da) logdet += log((double)c->cfg.sigma_p[d]);
+    k.chol_a[d] = hr.chol_a[d];
+    k.sigma_a[d] = hr.sigma_a[d];
+    k.inv_sp[d] = hr.inv_sp[d];
+    k.inv_sp2[d] = hr.inv_sp2[d];
   }
-  k.log_norm = (float)(-c->H * logdet - 0.5 * c->D * log(2.0 * M_PI));  // (prior_merge_args' constant)
+  k.log_norm = hr.log_norm;
   const float ell = stein_ell(c);
   k.inv_ell = 1.0f / ell;
   k.inv_l2 = 1.0f / (ell * ell);
@@ -5803,6 +5888,7 @@ static int svb_go(dust_svmpc_batch *b, const float *states, int n_steps, const f
   SvmpcBatchArgs k;
   svb_args(b, n_steps, eps_dev, params_dev, active, do_forward, k);
   const bool nav = skid_nav_on(c);
+  if (!b->hyper.empty() && (nav || prior)) return fail(DUST_ERR_UNSUPPORTED, "per-environment hyper-parameters: the plain tick and episode only");
   SkidNav nv;
   memset(&nv, 0, sizeof nv);
   if (nav) TRY(skid_nav_args(c, nv));
@@ -5813,7 +5899,20 @@ static int svb_go(dust_svmpc_batch *b, const float *states, int n_steps, const f
       HIP_TRY(launch_on(c->stream, false, kernel, b->B, SVB_THREADS, lds, args));  // (the batches are never captured)
       return DUST_OK;
     };
-    if (episode) {
+    if (!b->hyper.empty()) {  // per-environment rows (svb_call_check: neither a navigation cost nor a prior): the sweep instances
+      if (episode) {
+        SvmpcSweepEpisodeArgs ke;
+        ke.k = k;
+        ke.ep = *episode;
+        ke.rows = b->hyper_dev;
+        TRY(by_model(c, [&](auto M) { return go(&svmpc_sweep_episode_kernel<M()>, ke); }));
+      } else {
+        SvmpcSweepArgs ks;
+        ks.k = k;
+        ks.rows = b->hyper_dev;
+        TRY(by_model(c, [&](auto M) { return go(&svmpc_sweep_kernel<M()>, ks); }));
+      }
+    } else if (episode) {
       if (nav) {
         SvmpcNavEpisodeArgs ke;
         ke.k = k;

@@ -782,6 +782,50 @@ __global__ __launch_bounds__(SVB_THREADS) void svmpc_skid_nav_batch_kernel(const
 __global__ __launch_bounds__(SVB_THREADS) void svmpc_skid_nav_prior_batch_kernel(const SvmpcNavPriorBatchArgs kp) {
   svb_body<DUST_MODEL_SKID_STEER, true, true>(kp.k, &kp.pr, &kp.nav);
 }
+// Per-environment hyper-parameters (dust_svmpc_batch_set_hyper: the trials of the reference's demo/pendulum_tuning.py:30-143 and
+// demo/particle_tuning.py:27-99 as the environments of one batch).  Row b holds what environment b reads in place of the launch-uniform
+// fields of the same names - the host makes the derived ones (svb_hyper_row, dust_amd.hip: the one function that also makes the
+// prototype's) and writes the rows before the launch; no kernel ever writes them, so the workgroup-uniform load below may be a scalar one.
+// The workgroup patches ITS copy of the arguments and runs svb_body on it: the uniform kernels' text, arithmetic and order, so a row
+// equal to the prototype's gives the uniform kernel's bits.  same_w (svb_tick) is formed from that copy: the one- and the two-softmax
+// path may run side by side in one launch.  The horizon stays per batch: strides, the Philox layout and the LDS plan depend on it.
+// Not measured: passing the row by reference through a template parameter of svb_tick instead of patching a copy.
+// A row is 64 bytes on a 16-byte boundary: the workgroup fetches it whole with one wide load.  The fields are patched by the text of
+// SVB_HYPER_APPLY in the kernel's own body: with the same assignments behind a forceinline function taking the copy by reference the
+// register allocator left 36 bytes of never-used stack slots behind in the skid-steer episode instance - the sensitivity svb_tick's
+// phase 0 notes; tests/test_svmpc_sweep_cpu.py holds all eight instances to a private segment of 0.
+struct alignas(16) SvbHyper {
+  double lr;
+  float alpha, temp;
+  float chol_a[2], sigma_a[2], inv_sp[2], inv_sp2[2];
+  float log_norm;
+  int weighted_prior;
+  int pad[2];
+};
+static_assert(sizeof(SvbHyper) == 64, "one row, one 64-byte load");
+struct SvmpcSweepArgs {
+  SvmpcBatchArgs k;
+  const SvbHyper *rows;  // [B]
+};
+#define SVB_HYPER_APPLY(a, h)         \
+  (a).opt.lr = (h).lr;                \
+  (a).alpha = (h).alpha;              \
+  (a).temp = (h).temp;                \
+  for (int d = 0; d < 2; ++d) {       \
+    (a).chol_a[d] = (h).chol_a[d];    \
+    (a).sigma_a[d] = (h).sigma_a[d];  \
+    (a).inv_sp[d] = (h).inv_sp[d];    \
+    (a).inv_sp2[d] = (h).inv_sp2[d];  \
+  }                                   \
+  (a).log_norm = (h).log_norm;        \
+  (a).weighted_prior = (h).weighted_prior
+template <int MODEL>
+__global__ __launch_bounds__(SVB_THREADS) void svmpc_sweep_kernel(const SvmpcSweepArgs ks) {
+  const SvbHyper h = ks.rows[blockIdx.x];  // (the whole row, ahead of the copy)
+  SvmpcBatchArgs a = ks.k;
+  SVB_HYPER_APPLY(a, h);
+  svb_body<MODEL, false>(a, nullptr);
+}
 // the instance of either kernel for a model (the host's launch names the model once for both)
 template <int MODEL, bool PRIOR>
 static constexpr auto svb_instance() {

@@ -113,6 +113,20 @@ __global__ __launch_bounds__(SVB_THREADS) void svmpc_skid_nav_episode_kernel(con
   svb_episode_body<DUST_MODEL_SKID_STEER, true>(ka.k, ka.ep, &ka.nav);
 }
 
+// ... with per-environment hyper-parameters (svmpc_batch.hpp SvbHyper): the workgroup's own copy of the arguments, the same body
+struct SvmpcSweepEpisodeArgs {
+  SvmpcBatchArgs k;
+  SvbEpisode ep;
+  const SvbHyper *rows;  // [B]
+};
+template <int MODEL>
+__global__ __launch_bounds__(SVB_THREADS) void svmpc_sweep_episode_kernel(const SvmpcSweepEpisodeArgs ka) {
+  const SvbHyper h = ka.rows[blockIdx.x];  // (the whole row, ahead of the copy)
+  SvmpcBatchArgs a = ka.k;
+  SVB_HYPER_APPLY(a, h);
+  svb_episode_body<MODEL, false>(a, ka.ep, nullptr);
+}
+
 // What a period of the dual episode adds to the PRIOR tick's arguments
 struct SvbDualPeriod {
   const float *plant;  // [B][P] true parameter rows or nullptr (nominal plants)

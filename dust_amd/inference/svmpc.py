@@ -192,7 +192,9 @@ class BatchSVMPC:
     dynamics samples.  The constructor takes SVMPC's arguments behind `n_envs` and refuses what lies outside the kernel's box
     (K1 / IMQ kernel, N <= 64, S <= 1024, M <= 64, H d_a <= 128, ctrl_penalty = 1, diagonal covariances, no sigma points, roll
     'repeat' / 'mean') before any device is touched.  Every model family's cost runs in the batch, the skid-steer robot's
-    `NavigationCost` among them (svmpc_skid_nav_batch_kernel): its one occupancy map serves all `n_envs` environments."""
+    `NavigationCost` among them (svmpc_skid_nav_batch_kernel): its one occupancy map serves all `n_envs` environments.
+    `set_hyper` gives every environment its own lr, alpha, temperature, prior_sigma, ctrl_sigma and weighted_prior (svmpc_sweep_kernel):
+    a hyper-parameter sweep is then one `run_episodes` call."""
 
     def __init__(self, n_envs, init_particles, prior, likelihood, roll_strategy="repeat", weighted_prior=False, kernel=None, bw_scale=1.0,
                  n_particles=None, n_steps=100, optimizer_class=torch.optim.Adam, seeds=None, **opt_args):
@@ -243,6 +245,7 @@ class BatchSVMPC:
         self._prior_cov = cov
         self._batch = None
         self._key = None
+        self._hyper = None  # set_hyper(): per-environment rows (a dict of arrays), kept here until - and whenever - a batch is built
         self.optimizer = optimizer_class(params=[torch.zeros(1, requires_grad=True)], **opt_args)
         self._opt_group = group_options(self.optimizer)
 
@@ -274,7 +277,86 @@ class BatchSVMPC:
                 self._batch.set(w, v)
         elif not all(torch.equal(self._theta0[b], self._theta0[0]) for b in range(1, self.n_envs)):
             self._batch.set(L.SVB_THETA, self._theta0.numpy())
+        if self._hyper is not None:  # the per-environment rows belong to this object: a new or a rebuilt batch gets them again
+            self._batch.set_hyper(self._hyper)
         return self._batch
+
+    # -- per-environment hyper-parameters: the trials of a tuning sweep as the environments of one batch
+    def _proto_hyper(self):
+        """the controller's own values as rows, in the expressions make_config uses for diagonal covariances"""
+        from ..optim import is_plain
+
+        ctrl, B, da = self.likelihood.controller, self.n_envs, self.likelihood.controller.dim_a
+        a_cov = ctrl.a_dist.covariance_matrix
+        lr = float(self._optim["lr"])
+        rows = dict(lr=float(np.float32(lr)) if is_plain(self._optim) else lr,  # (dust_config carries a plain optimiser's lr in fp32)
+                    alpha=np.float32(float(self.likelihood.alpha)), temperature=np.float32(float(ctrl.temp)),
+                    sigma_a=a_cov.diag().sqrt().numpy().astype(np.float32), chol_a=torch.linalg.cholesky(a_cov).diag().numpy().astype(np.float32),
+                    sigma_p=self._prior_cov.diag().sqrt().numpy().astype(np.float32), weighted_prior=int(bool(self.w_prior)))
+        wide = ("sigma_a", "chol_a", "sigma_p")
+        return {k: np.broadcast_to(np.asarray(v), (B, da) if k in wide else (B,)).copy() for k, v in rows.items()}
+
+    def set_hyper(self, lr=None, alpha=None, temperature=None, prior_sigma=None, ctrl_sigma=None, weighted_prior=None):
+        """Hyper-parameters per environment - the trials of the reference's demo/pendulum_tuning.py and demo/particle_tuning.py as the
+        environments of ONE batch, so that a sweep is one run_episodes() call.  Each argument is None (the controller's own value), a
+        scalar or [B]; the sigmas (standard deviations of the diagonal prior / action covariances) may be [B, dim_a].  alpha and
+        temperature are independent: the scripts' temperature = 1 / alpha is the caller's line.  With every argument None the batch
+        returns to the controller's values.  The horizon is not per environment (it shapes the launch): sweep it with one batch per
+        value.  Raises ValueError before any device call for wrong lengths and for values that are not finite and > 0."""
+        from ..optim import is_plain
+
+        B, da = self.n_envs, self.likelihood.controller.dim_a
+        given = dict(lr=lr, alpha=alpha, temperature=temperature, sigma_p=prior_sigma, sigma_a=ctrl_sigma, weighted_prior=weighted_prior)
+        names = dict(sigma_p="prior_sigma", sigma_a="ctrl_sigma")
+        if all(v is None for v in given.values()):
+            self._hyper = None
+            if self._batch is not None:
+                self._batch.set_hyper(None)
+            return
+        rows = self._proto_hyper()
+        for k, v in given.items():
+            if v is None:
+                continue
+            name = names.get(k, k)
+            v = np.asarray(torch.as_tensor(v).detach().numpy() if isinstance(v, torch.Tensor) else v)
+            wide = k in ("sigma_a", "sigma_p")
+            if v.ndim == 2 and wide and v.shape in ((B, 1), (B, da)):
+                v = np.broadcast_to(v, (B, da))
+            elif v.ndim == 1 and v.shape == (B,):
+                v = np.broadcast_to(v[:, None], (B, da)) if wide else v
+            elif v.ndim == 0:
+                v = np.broadcast_to(v, (B, da) if wide else (B,))
+            else:
+                raise ValueError("%s has shape %s: a scalar or [%d]%s" % (name, v.shape, B, (" or [%d, %d]" % (B, da)) if wide else ""))
+            if k == "weighted_prior":
+                if not np.isin(v, (0, 1)).all():
+                    raise ValueError("weighted_prior must be False / True (0 / 1)")
+                rows[k] = v.astype(np.int64).copy()
+                continue
+            v = v.astype(np.float64)
+            if not (np.isfinite(v).all() and (v > 0).all()):
+                raise ValueError("%s must be finite and > 0" % name)
+            if k == "lr":
+                rows[k] = v.astype(np.float32).astype(np.float64) if is_plain(self._optim) else v.copy()
+            else:
+                rows[k] = v.astype(np.float32)  # fp32 sigma, as make_config forms it
+            if not (rows[k] > 0).all() or not np.isfinite(rows[k]).all():
+                raise ValueError("%s must be finite and > 0 in float32" % name)
+            if k == "sigma_a":
+                rows["chol_a"] = rows[k].copy()  # (diagonal: cholesky(a_cov) = sigma_a)
+        self._hyper = rows
+        if self._batch is not None:
+            self._batch.set_hyper(rows)
+
+    @property
+    def hyper(self):
+        """The rows in force as a dict of arrays: lr, alpha, temperature, weighted_prior [B]; sigma_a, chol_a, sigma_p [B, dim_a]"""
+        if self._batch is not None:
+            return self._batch.get_hyper()
+        rows = self._proto_hyper() if self._hyper is None else self._hyper
+        out = {k: np.array(v) for k, v in rows.items()}
+        out["weighted_prior"] = np.asarray(out["weighted_prior"], np.int32)
+        return out
 
     def __deepcopy__(self, memo):
         import copy

@@ -506,6 +506,31 @@ int dust_svmpc_batch_tick(dust_svmpc_batch *batch, const float *states, int n_st
 int dust_svmpc_batch_episode(dust_svmpc_batch *batch, const float *states, int n_periods, int n_steps, const float *params,
                              const float *plant_params, int flags, const unsigned char *active, float *states_out, float *actions_out,
                              float *pw_out, float *a_seq);
+/* Per-environment hyper-parameters: a tuning sweep as ONE batch.  The reference tunes by running one episode per trial, each with its
+ * own lr, alpha (temperature = 1 / alpha) and prior_sigma (demo/pendulum_tuning.py:30-143), ctrl_sigma and prior_weighted besides
+ * (demo/particle_tuning.py:27-99); here the B trials are the B environments of a batch and dust_svmpc_batch_episode evaluates them in
+ * one launch.  Row b replaces, for environment b alone, the fields of dust_config / dust_optim_config it names; alpha and temperature are
+ * independent (temperature = 1 / alpha is the caller's line).  The horizon is NOT per environment: strides, the noise streams' layout
+ * and the LDS plan depend on it - a horizon sweep is one batch per value.
+ * dust_svmpc_batch_set_hyper: rows [B], host, copied (and uploaded on the batch's stream) before the call returns; NULL: back to the
+ *   prototype's values.  Nothing else changes: particles, prior, a_mat, optimiser state and step counts, noise streams stay.
+ *   DUST_ERR_INVALID, with the stored rows unchanged: a value that is not finite; lr, alpha, temperature, sigma_a, chol_a or sigma_p
+ *   <= 0 (entry 1 of the three arrays is ignored when dim_a = 1, but must be finite); weighted_prior other than 0 or 1.
+ * dust_svmpc_batch_get_hyper: the rows as they were set, or B times the prototype's values where none are set.
+ * While rows are set, dust_svmpc_batch_optimize / _forward / _tick and dust_svmpc_batch_episode launch instances of their own
+ * (svmpc_sweep_kernel, svmpc_sweep_episode_kernel: one launch per call, counted under DUST_K_SVMPC_BATCH): workgroup b reads row b and
+ * runs the uniform kernels' text on its own copy of the arguments, so an environment whose row equals a prototype's values computes that
+ * prototype's bits, whatever its neighbours' rows.  dust_svmpc_batch_clone copies the rows.  DUST_ERR_UNSUPPORTED while rows are set,
+ * before anything is staged or launched: dust_svmpc_dual_batch_tick, dust_svmpc_dual_batch_episode, and every call of a batch whose
+ * prototype has the navigation cost family. */
+typedef struct dust_svmpc_hyper { /* one environment's row; the fields of dust_config / dust_optim_config it overrides */
+  double lr;
+  float alpha, temperature;
+  float sigma_a[2], chol_a[2], sigma_p[2]; /* diagonal covariances: entry 1 ignored when dim_a = 1 */
+  int weighted_prior;
+} dust_svmpc_hyper;
+int dust_svmpc_batch_set_hyper(dust_svmpc_batch *batch, const dust_svmpc_hyper *rows /* [B], or NULL: back to the prototype's */);
+int dust_svmpc_batch_get_hyper(dust_svmpc_batch *batch, dust_svmpc_hyper *rows /* [B]: the prototype's values where none are set */);
 
 /* stage outputs of the last call, for parity tests ([S][N] / [N][H][da] / [N]) */
 int dust_get_costs(dust_ctx *ctx, float *costs);
