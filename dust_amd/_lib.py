@@ -97,6 +97,10 @@ class SvmpcHyper(C.Structure):  # dust_svmpc_hyper: one environment's row of dus
                 ("sigma_p", C.c_float * 2), ("weighted_prior", C.c_int)]
 
 
+class EpisodeRules(C.Structure):  # dust_episode_rules: the reference's episode rules of dust_svmpc_batch_simulate
+    _fields_ = [("t0", C.c_int), ("warm_up", C.c_int), ("stop_on_crash", C.c_int), ("goal_radius", C.c_float), ("goal", C.c_float * 8)]
+
+
 FP = C.POINTER(C.c_float)
 VP = C.c_void_p
 
@@ -167,6 +171,8 @@ SYMBOLS = {
     "dust_svmpc_batch_episode": (C.c_int, [VP, FP, C.c_int, C.c_int, FP, FP, C.c_int, C.POINTER(C.c_ubyte), FP, FP, FP, FP]),
     "dust_svmpc_batch_set_hyper": (C.c_int, [VP, C.POINTER(SvmpcHyper)]),
     "dust_svmpc_batch_get_hyper": (C.c_int, [VP, C.POINTER(SvmpcHyper)]),
+    "dust_svmpc_batch_simulate": (C.c_int, [VP, FP, C.c_int, C.c_int, FP, FP, C.POINTER(EpisodeRules), C.c_int, C.POINTER(C.c_ubyte), FP, FP, FP,
+                                            FP, FP, C.POINTER(C.c_int), C.POINTER(C.c_int), FP]),
     "dust_mpf_batch_create": (C.c_int, [VP, C.c_int, C.POINTER(VP)]),
     "dust_mpf_batch_destroy": (None, [VP]),
     "dust_mpf_batch_clone": (C.c_int, [VP, C.POINTER(VP)]),

@@ -1021,6 +1021,47 @@ class SvmpcBatch(_BatchHandle):
         L.check(L.load().dust_svmpc_batch_episode(self._h, _p(st), T, int(n_steps), _p(pr), _p(pl), int(flags), mp, _p(xs), _p(acts), _p(pw), _p(a_seq)))
         return xs, acts, pw, a_seq
 
+    def simulate(self, states, n_periods, n_steps, params=None, plant_params=None, t0=0, warm_up=0, goal=None, goal_radius=None,
+                 stop_on_crash=False, loss=None, status=None, active=None, want_pw=True, flags=0):
+        """episode() under the reference's episode rules, still ONE launch (dust_svmpc_batch_simulate).  Period t is period t0 + t of the
+        episode: below warm_up it is optimize alone and the plant gets a zero action; the family's instantaneous cost of every new state
+        goes to `costs` and, as an fp32 running sum, to `loss`; with stop_on_crash a new position on an occupied cell ends the
+        environment with loss = inf, status 2; with goal [ds] and goal_radius > 0, |goal - x|^2 <= radius^2 ends it with status 1.
+        loss / status [B]: where a previous call left them (None: 0).  -> (states [T, B, ds], actions [T, B, da], p_weights [T, B, N] or
+        None, costs [T, B], loss [B], status [B] int32, n_run [B] int32, a_seq [B, H, da]); rows the call did not write - past n_run[b],
+        warm-up rows of p_weights, inactive environments - are NaN (n_run: -1)."""
+        B, T = self.B, int(n_periods)
+        st = None if states is None else _f(states, (B, self.ds))  # (None: the library refuses)
+        pr = pl = None
+        if params is not None:
+            pr = _f(params)
+            want = (T, B, int(n_steps), self.M, max(self.P, 1))
+            if pr.shape != want:
+                raise ValueError("params has shape %s, the call reads %s" % (pr.shape, want))
+        if plant_params is not None:
+            pl = _f(plant_params)
+            if pl.shape != (B, max(self.P, 1)):
+                raise ValueError("plant_params has shape %s, the call reads %s" % (pl.shape, (B, max(self.P, 1))))
+        ru = L.EpisodeRules()
+        ru.t0, ru.warm_up, ru.stop_on_crash = int(t0), int(warm_up), int(bool(stop_on_crash))
+        ru.goal_radius = 0.0 if goal_radius is None else float(goal_radius)
+        if goal is not None:
+            g = np.asarray(goal, np.float32).reshape(-1)
+            if g.shape != (self.ds,):
+                raise ValueError("goal has %d entries, a state has %d" % (g.size, self.ds))
+            ru.goal[:self.ds] = [float(v) for v in g]
+        _, mp = _mask(active, B)
+        rows = max(T, 0)  # (n_periods < 1: the library refuses before it writes anything)
+        xs, acts, costs, a_seq = (np.full(sh, np.nan, np.float32) for sh in ((rows, B, self.ds), (rows, B, self.da), (rows, B), (B, self.H, self.da)))
+        pw = np.full((rows, B, self.N), np.nan, np.float32) if want_pw else None
+        loss = np.zeros(B, np.float32) if loss is None else np.array(_f(loss, (B,)))
+        status = np.zeros(B, np.int32) if status is None else np.ascontiguousarray(np.array(status, np.int32).reshape(B))
+        n_run = np.full(B, -1, np.int32)
+        IP = C.POINTER(C.c_int)
+        L.check(L.load().dust_svmpc_batch_simulate(self._h, _p(st), T, int(n_steps), _p(pr), _p(pl), C.byref(ru), int(flags), mp, _p(xs), _p(acts),
+                                                   _p(pw), _p(costs), _p(loss), status.ctypes.data_as(IP), n_run.ctypes.data_as(IP), _p(a_seq)))
+        return xs, acts, pw, costs, loss, status, n_run, a_seq
+
     def dual_tick(self, mpf, states, actions_prev=None, n_steps=1, eps=None, mpf_steps=20, mpf_bw=None, seeds=None, active=None,
                   want_outputs=True, want_params=False, flags=0, eps_dev_ptr=None, keep_actions=False):
         """One control period of the DuSt-MPC loop for every active environment in one C call (dust_svmpc_dual_batch_tick): the filters'

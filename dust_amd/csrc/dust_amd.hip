@@ -5879,9 +5879,11 @@ static void svb_args(const dust_svmpc_batch *b, int n_steps, const float *eps_de
 }
 // States and mask through the next pinned slot, the kernel's arguments and the ONE launch; nothing waits for the device.  params_dev: the
 // staged parameter rows or NULL; prior: the filters the PRIOR instances draw their rows from, or NULL; episode: the launch runs
-// episode->T ticks, each followed by the plant's step (svmpc_episode.hpp), not one
+// episode->T ticks, each followed by the plant's step (svmpc_episode.hpp), not one; rules (with episode): ... under the reference's
+// episode rules (svb_sim_body)
 static int svb_go(dust_svmpc_batch *b, const float *states, int n_steps, const float *eps_dev, const float *params_dev, int flags,
-                  const unsigned char *active, bool do_forward, const dust::SvbPrior *prior, const dust::SvbEpisode *episode = nullptr) {
+                  const unsigned char *active, bool do_forward, const dust::SvbPrior *prior, const dust::SvbEpisode *episode = nullptr,
+                  const dust::SvbRules *rules = nullptr) {
   dust_ctx *c = b->c;
   HIP_TRY(hipSetDevice(c->cfg.device));
   TRY(b->in.stage(c, states, active));
@@ -5900,7 +5902,14 @@ static int svb_go(dust_svmpc_batch *b, const float *states, int n_steps, const f
       return DUST_OK;
     };
     if (!b->hyper.empty()) {  // per-environment rows (svb_call_check: neither a navigation cost nor a prior): the sweep instances
-      if (episode) {
+      if (rules) {
+        SvmpcRowsSimArgs ke;
+        ke.k = k;
+        ke.ep = *episode;
+        ke.ru = *rules;
+        ke.rows = b->hyper_dev;
+        TRY(by_model(c, [&](auto M) { return go(&svmpc_rows_sim_kernel<M()>, ke); }));
+      } else if (episode) {
         SvmpcSweepEpisodeArgs ke;
         ke.k = k;
         ke.ep = *episode;
@@ -5911,6 +5920,21 @@ static int svb_go(dust_svmpc_batch *b, const float *states, int n_steps, const f
         ks.k = k;
         ks.rows = b->hyper_dev;
         TRY(by_model(c, [&](auto M) { return go(&svmpc_sweep_kernel<M()>, ks); }));
+      }
+    } else if (rules) {  // the episode under the reference's rules (svb_sim_body)
+      if (nav) {
+        SvmpcNavSimArgs ke;
+        ke.k = k;
+        ke.ep = *episode;
+        ke.ru = *rules;
+        ke.nav = nv;
+        TRY(go(&svmpc_skid_nav_sim_kernel, ke));
+      } else {
+        SvmpcSimArgs ke;
+        ke.k = k;
+        ke.ep = *episode;
+        ke.ru = *rules;
+        TRY(by_model(c, [&](auto M) { return go(&svmpc_sim_kernel<M()>, ke); }));
       }
     } else if (episode) {
       if (nav) {
@@ -5995,10 +6019,12 @@ extern "C" int dust_svmpc_batch_tick(dust_svmpc_batch *b, const float *states, i
   return svb_outputs(b, active, a_seq, p_weights);
 }
 
-// T closed-loop periods (tick, plant step, records) of every active environment in ONE launch: svmpc_episode.hpp
-extern "C" int dust_svmpc_batch_episode(dust_svmpc_batch *b, const float *states, int n_periods, int n_steps, const float *params,
-                                        const float *plant_params, int flags, const unsigned char *active, float *states_out, float *actions_out,
-                                        float *pw_out, float *a_seq) {
+// T closed-loop periods (tick, plant step, records) of every active environment in ONE launch: svmpc_episode.hpp.  rules: the episode runs
+// under the reference's rules (dust_svmpc_batch_simulate: svb_sim_body, with costs_out, loss, status and n_run), or NULL (every
+// environment runs its T periods: dust_svmpc_batch_episode)
+static int svb_episode_call(dust_svmpc_batch *b, const float *states, int n_periods, int n_steps, const float *params, const float *plant_params,
+                            const dust_episode_rules *rules, int flags, const unsigned char *active, float *states_out, float *actions_out,
+                            float *pw_out, float *costs_out, float *loss, int *status, int *n_run, float *a_seq) {
   if (!b) return fail(DUST_ERR_INVALID, "null batch");
   if (!states || !states_out || !actions_out) return fail(DUST_ERR_INVALID, "null argument");
   if (n_steps < 1) return fail(DUST_ERR_INVALID, "a tick has n_steps >= 1 (got %d)", n_steps);
@@ -6007,16 +6033,33 @@ extern "C" int dust_svmpc_batch_episode(dust_svmpc_batch *b, const float *states
   if (flags != 0) return fail(DUST_ERR_UNSUPPORTED, "an episode draws its noise on the device and keeps no actions: flags must be 0 (got %d)", flags);
   dust_ctx *c = b->c;
   if (c->cfg.dim_p == 0 && plant_params) return fail(DUST_ERR_INVALID, "plant parameter rows without uncertain parameters (dim_p = 0)");
-  TRY(svb_call_check(b, states, n_steps, params, false, 0, true));
   const size_t T = (size_t)n_periods, B = (size_t)b->B, N = (size_t)c->N, M = (size_t)c->M, P = (size_t)c->cfg.dim_p;
-  const size_t ds = (size_t)c->ds, da = (size_t)c->da;
+  const size_t ds = (size_t)c->ds, da = (size_t)c->da, D = (size_t)c->D;
+  bool forward = true;  // some period of the call runs forward()
+  if (rules) {
+    if (!costs_out || !loss || !status || !n_run) return fail(DUST_ERR_INVALID, "null argument");
+    if (rules->t0 < 0 || rules->warm_up < 0) return fail(DUST_ERR_INVALID, "t0 = %d, warm_up = %d: both are >= 0", rules->t0, rules->warm_up);
+    if (rules->t0 > 0x7fffffff - 4096) return fail(DUST_ERR_INVALID, "t0 = %d: the episode's period index does not fit", rules->t0);
+    bool finite = std::isfinite(rules->goal_radius);
+    for (size_t k = 0; k < ds; ++k) finite = finite && std::isfinite(rules->goal[k]);
+    if (!finite) return fail(DUST_ERR_INVALID, "the goal and its radius must be finite");
+    for (size_t e = 0; e < B; ++e)
+      if ((!active || active[e]) && (status[e] < 0 || status[e] > 2))
+        return fail(DUST_ERR_INVALID, "status[%zu] = %d: 0 (running), 1 (goal) or 2 (crash)", e, status[e]);
+    const bool have_map = (c->cfg.model == DUST_MODEL_PARTICLE && c->cfg.with_obstacle && c->grid_bits) || skid_nav_on(c);
+    if (rules->stop_on_crash && !have_map)
+      return fail(DUST_ERR_UNSUPPORTED, "stop_on_crash needs an occupancy map: Particle with_obstacle, or the skid-steer navigation cost");
+    forward = rules->t0 + n_periods > rules->warm_up;
+  }
+  TRY(svb_call_check(b, states, n_steps, params, false, 0, forward));
   HIP_TRY(hipSetDevice(c->cfg.device));
   if (params) TRY(svb_stage_params(b, params, T * B * (size_t)n_steps * M * P));
   if (plant_params) {
     TRY(b->plant.ensure(B * P));
     TRY(h2d(c, b->plant, plant_params, B * P * sizeof(float)));
   }
-  const size_t n_rec = T * B * (ds + da + (pw_out ? N : 0));
+  // the records, then (rules) the cost rows and the words [B] loss, [B] status, [B] n_run
+  const size_t n_pw = pw_out ? T * B * N : 0, n_cost = rules ? T * B : 0, n_rec = T * B * (ds + da) + n_pw + n_cost + (rules ? 3 * B : 0);
   TRY(b->rec.ensure(n_rec));
   SvbEpisode ep;
   ep.T = n_periods;
@@ -6024,25 +6067,77 @@ extern "C" int dust_svmpc_batch_episode(dust_svmpc_batch *b, const float *states
   ep.states_out = b->rec;
   ep.actions_out = ep.states_out + T * B * ds;
   ep.pw_out = pw_out ? ep.actions_out + T * B * da : nullptr;
-  TRY(svb_go(b, states, n_steps, nullptr, params ? b->params : nullptr, 0, active, true, nullptr, &ep));
+  SvbRules ru;
+  memset(&ru, 0, sizeof ru);
+  const size_t words = T * B * (ds + da) + n_pw + n_cost;  // where loss, status and n_run lie in the records
+  if (rules) {
+    ru.t0 = rules->t0;
+    ru.warm_up = rules->warm_up;
+    ru.stop_on_crash = rules->stop_on_crash ? 1 : 0;
+    ru.goal_on = rules->goal_radius > 0.f ? 1 : 0;
+    ru.r2 = (float)((double)rules->goal_radius * (double)rules->goal_radius);
+    for (int k = 0; k < 8; ++k) ru.goal[k] = (size_t)k < ds ? rules->goal[k] : 0.f;
+    ru.costs_out = ep.actions_out + T * B * da + n_pw;
+    ru.loss = b->rec + words;
+    ru.status = reinterpret_cast<int *>(ru.loss + B);
+    ru.n_run = ru.status + B;
+    std::vector<float> in(3 * B, 0.f);  // (n_run starts at 0: an environment that enters stopped has run no period)
+    memcpy(in.data(), loss, B * sizeof(float));
+    memcpy(in.data() + B, status, B * sizeof(int));
+    TRY(h2d(c, ru.loss, in.data(), 3 * B * sizeof(float)));
+  }
+  TRY(svb_go(b, states, n_steps, nullptr, params ? b->params : nullptr, 0, active, forward, nullptr, &ep, rules ? &ru : nullptr));
   // the records come back once; the rows of inactive environments stay out of the caller's arrays
-  std::vector<float> host(n_rec);
+  std::vector<float> host(n_rec), seq(a_seq ? B * D : 0);
   HIP_TRY(hipMemcpyAsync(host.data(), b->rec, n_rec * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  TRY(svb_outputs_copy(b, active, a_seq, nullptr));
+  if (a_seq && rules) HIP_TRY(hipMemcpyAsync(seq.data(), b->a_seq_out, B * D * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  else TRY(svb_outputs_copy(b, active, a_seq, nullptr));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  auto rows = [&](float *dst, const float *src, size_t row) {
-    if (!active) {
+  const int *ran = rules ? reinterpret_cast<const int *>(host.data() + words + 2 * B) : nullptr;
+  // rows [first, n_run[e]) of an active environment's record (no rules: all T of them)
+  auto rows = [&](float *dst, const float *src, size_t row, size_t first) {
+    if (!active && !ran) {
       memcpy(dst, src, T * B * row * sizeof(float));
       return;
     }
-    for (size_t t = 0; t < T; ++t)
-      for (size_t e = 0; e < B; ++e)
-        if (active[e]) memcpy(dst + (t * B + e) * row, src + (t * B + e) * row, row * sizeof(float));
+    for (size_t e = 0; e < B; ++e) {
+      if (active && !active[e]) continue;
+      for (size_t t = first; t < (ran ? (size_t)ran[e] : T); ++t) memcpy(dst + (t * B + e) * row, src + (t * B + e) * row, row * sizeof(float));
+    }
   };
-  rows(states_out, host.data(), ds);
-  rows(actions_out, host.data() + T * B * ds, da);
-  if (pw_out) rows(pw_out, host.data() + T * B * (ds + da), N);
+  const size_t warm = rules ? (size_t)std::max(0, rules->warm_up - rules->t0) : 0;  // periods without forward(): no particle weights
+  rows(states_out, host.data(), ds, 0);
+  rows(actions_out, host.data() + T * B * ds, da, 0);
+  if (pw_out) rows(pw_out, host.data() + T * B * (ds + da), N, warm);
+  if (rules) {
+    rows(costs_out, host.data() + T * B * (ds + da) + n_pw, 1, 0);
+    for (size_t e = 0; e < B; ++e) {
+      if (active && !active[e]) continue;
+      n_run[e] = ran[e];
+      if (ran[e] == 0) continue;  // (entered with status != 0: nothing of it was written)
+      memcpy(loss + e, host.data() + words + e, sizeof(float));
+      memcpy(status + e, host.data() + words + B + e, sizeof(int));
+      if (a_seq && (size_t)ran[e] > warm) memcpy(a_seq + e * D, seq.data() + e * D, D * sizeof(float));
+    }
+  }
   return DUST_OK;
+}
+
+extern "C" int dust_svmpc_batch_episode(dust_svmpc_batch *b, const float *states, int n_periods, int n_steps, const float *params,
+                                        const float *plant_params, int flags, const unsigned char *active, float *states_out, float *actions_out,
+                                        float *pw_out, float *a_seq) {
+  return svb_episode_call(b, states, n_periods, n_steps, params, plant_params, nullptr, flags, active, states_out, actions_out, pw_out, nullptr,
+                          nullptr, nullptr, nullptr, a_seq);
+}
+
+// ... under the reference's episode rules - warm-up, the cost, crash and goal: B trials of run_particle_episode are one call and B losses
+extern "C" int dust_svmpc_batch_simulate(dust_svmpc_batch *b, const float *states, int n_periods, int n_steps, const float *params,
+                                         const float *plant_params, const dust_episode_rules *rules, int flags, const unsigned char *active,
+                                         float *states_out, float *actions_out, float *pw_out, float *costs_out, float *loss, int *status,
+                                         int *n_run, float *a_seq) {
+  if (!rules) return fail(DUST_ERR_INVALID, "null rules");
+  return svb_episode_call(b, states, n_periods, n_steps, params, plant_params, rules, flags, active, states_out, actions_out, pw_out, costs_out,
+                          loss, status, n_run, a_seq);
 }
 
 #include "mpf.hpp"

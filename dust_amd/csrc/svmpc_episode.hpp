@@ -22,6 +22,15 @@
 // the navigation instance).  The navigation instance stages its map ONCE per launch, ahead of the period loop, as the batched tick
 // does ahead of its iteration loop; restaging it every period has not been measured, nor has the difference.
 //
+// svmpc_sim_kernel / svmpc_skid_nav_sim_kernel / svmpc_rows_sim_kernel (svb_sim_body, dust_svmpc_batch_simulate): the same loop under the
+// rules of the reference's run_particle_episode / run_pendulum_simulation (simulations.py:104-130, 217-260) - while the episode warms
+// up a period is the tick WITHOUT forward() (what dust_svmpc_batch_optimize runs) and the plant gets a zero action; the family's own
+// instantaneous cost of every new state is recorded and summed in fp32 into the loss; a crash (loss = +inf) or the goal ends the
+// environment.  A second body beside svb_episode_body: the kernels above keep their text.  The loop has barriers, so whether a workgroup
+// leaves it is computed by every lane from the carry in its registers and from read-only data (map, rules) - the same in all lanes by
+// construction -, and it is left behind a period's closing svb_sync() alone, through svb_end.  Still no spinning, no traffic between
+// workgroups, at most T periods.
+//
 // svmpc_dual_period_kernel: ONE period of the dual loop (simulations.py:104-138) per launch, for dust_svmpc_dual_batch_episode.  The filter
 // update of a period is a launch of its own (mpf_optimize_batch_kernel: 1 024 lanes, another order of partial sums), so the periods of
 // that episode are a chain of launches on one stream, with no host in between; what a period hands to the next - the state row and the
@@ -191,6 +200,148 @@ __device__ __forceinline__ void svb_dual_period_body(const SvmpcBatchArgs &a, co
 template <int MODEL>
 __global__ __launch_bounds__(SVB_THREADS) void svmpc_dual_period_kernel(const SvmpcDualPeriodArgs ka) {
   svb_dual_period_body<MODEL>(ka.k, ka.pr, ka.dp);
+}
+
+// The reference's episode rules (run_particle_episode / run_pendulum_simulation, simulations.py:104-130, 217-260) for
+// dust_svmpc_batch_simulate: what svb_sim_body adds to svb_episode_body.  Period t of the call is period g = t0 + t of the episode.
+struct SvbRules {
+  int t0, warm_up;    // g < warm_up: optimize only (no forward), the plant gets a zero action
+  int stop_on_crash;  // the new position on an occupied cell: loss = +inf, status 2
+  int goal_on;        // |goal - x|^2 <= r2: status 1
+  float r2;           // (float)(radius * radius), made once on the host
+  float goal[8];
+  float *costs_out;  // [T][B] the instantaneous cost of the state after the step
+  float *loss;       // [B] in-out: the fp32 running sum of the costs in period order
+  int *status;       // [B] in-out: 0 running, 1 goal, 2 crash
+  int *n_run;        // [B] out: the periods this call ran
+};
+struct SvmpcSimArgs {
+  SvmpcBatchArgs k;
+  SvbEpisode ep;
+  SvbRules ru;
+};
+struct SvmpcNavSimArgs {
+  SvmpcBatchArgs k;
+  SvbEpisode ep;
+  SvbRules ru;
+  SkidNav nav;
+};
+struct SvmpcRowsSimArgs {
+  SvmpcBatchArgs k;
+  SvbEpisode ep;
+  SvbRules ru;
+  const SvbHyper *rows;  // [B]
+};
+
+// controller.inst_cost_fn(state) of the plant's new state: the family's own instantaneous cost, the one the rollouts of phase C call, with
+// a zero action (Particle: w_obs collision() included; skid-steer / cart-pole: the quadratic state cost of svb_traj, NAV: plus the map term)
+template <int MODEL, bool NAV>
+__device__ __forceinline__ float svb_state_cost(const SvmpcBatchArgs &a, const float *x, const DevModel &map, const float w_obs) {
+  if constexpr (MODEL == DUST_MODEL_PENDULUM || MODEL == DUST_MODEL_PARTICLE) {
+    const float zero[2] = {0.f, 0.f};
+    return inst_cost<MODEL>(a.dm, x, zero);
+  } else {
+    constexpr int DS = SvbDims<MODEL>::DS;
+    double sc = 0.0;
+#pragma unroll
+    for (int k = 0; k < DS; ++k) {
+      float d, w;
+      if constexpr (MODEL == DUST_MODEL_SKID_STEER) {
+        d = x[k] - a.sk.goal[k];
+        w = a.sk.w_state[k];
+      } else {
+        d = x[k] - a.cp.goal[k];
+        w = a.cp.w_state[k];
+      }
+      sc += (double)((d * d) * w);
+    }
+    if constexpr (NAV) return (float)sc + w_obs * collision(map, x[0], x[1]);
+    else return (float)sc;
+  }
+}
+
+// obst_map.get_collisions(state[:2]) of the new position: Particle on its own map, the skid-steer navigation instance on its own
+template <int MODEL, bool NAV>
+__device__ __forceinline__ bool svb_crashed(const SvmpcBatchArgs &a, const float *x, const DevModel &map) {
+  if constexpr (MODEL == DUST_MODEL_PARTICLE) return collision(a.dm, x[0], x[1]) != 0.f;
+  else if constexpr (NAV) return collision(map, x[0], x[1]) != 0.f;
+  else return false;  // (the host refuses the rule for every other family)
+}
+
+// svb_episode_body's loop under the rules.  Whether an environment leaves the loop is computed by EVERY lane from the carry in its
+// registers (cy.x0) and from read-only data (map, rules) - never from a word one lane stored earlier in the launch -, so the decision is
+// the same in all 512 lanes by construction; the loop is left at a period's end alone, behind its closing svb_sync(), and through svb_end.
+template <int MODEL, bool NAV>
+__device__ __forceinline__ void svb_sim_body(const SvmpcBatchArgs &a, const SvbEpisode &ep, const SvbRules &ru, const SkidNav *nav) {
+  constexpr int DS = SvbDims<MODEL>::DS;
+  const int env = (int)blockIdx.x, B = (int)gridDim.x;
+  if (a.active && a.active[env] == 0) return;
+  if (ru.status[env] != 0) return;  // (written by the host before the launch; this launch stores it once, at its very end)
+  SvbCarry<MODEL> cy;
+  DevModel map;
+  float w_obs;
+  svb_begin<MODEL, NAV>(a, nav, cy, map, w_obs);
+  float cf[SVB_COEF];
+  svb_coef<MODEL>(a, ep.plant ? ep.plant + (size_t)env * a.P : nullptr, cf);
+  const size_t per = (size_t)B * a.n_steps * a.M * a.P;  // parameter rows of one period
+  SvmpcBatchArgs ap = a;                                // the period's own copy: do_forward = 0 while the episode warms up
+  const int warm = ru.warm_up - ru.t0;                  // periods of this call that are still warm-up (<= 0: none)
+  float loss = ru.loss[env];
+  int status = 0, n = 0;
+  for (int t = 0; t < ep.T; ++t) {
+    const size_t row = (size_t)t * B + env;
+    ap.do_forward = t < warm ? 0 : 1;
+    float act[2] = {0.f, 0.f};  // (warm-up: no forward() writes it - the plant gets the zero action)
+    svb_tick<MODEL, false, NAV, true>(ap, nullptr, a.params ? a.params + (size_t)t * per : nullptr, cy, map, w_obs,
+                                      ep.pw_out ? ep.pw_out + row * a.N : nullptr, act);
+    svb_plant_step<MODEL>(a, cf, cy.x0, act);
+    const float cost = svb_state_cost<MODEL, NAV>(a, cy.x0, map, w_obs);
+    loss += cost;
+    if (ru.goal_on) {
+      float s = 0.f;
+#pragma unroll
+      for (int k = 0; k < DS; ++k) {
+        const float d = ru.goal[k] - cy.x0[k];
+        s = k == 0 ? d * d : s + d * d;
+      }
+      if (s <= ru.r2) status = 1;
+    }
+    if (ru.stop_on_crash && svb_crashed<MODEL, NAV>(a, cy.x0, map)) {  // (the crash rule wins)
+      status = 2;
+      loss = INFINITY;
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int k = 0; k < DS; ++k) ep.states_out[row * DS + k] = cy.x0[k];
+      ep.actions_out[row * a.da] = act[0];
+      if (a.da == 2) ep.actions_out[row * 2 + 1] = act[1];
+      ru.costs_out[row] = cost;
+    }
+    n = t + 1;
+    svb_sync();  // the roll has read the particles' LDS rows, the next period's phase 0 overwrites them
+    if (status != 0) break;
+  }
+  svb_end(a, cy);
+  if (threadIdx.x == 0) {
+    ru.n_run[env] = n;
+    ru.status[env] = status;
+    ru.loss[env] = loss;
+  }
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(SVB_THREADS) void svmpc_sim_kernel(const SvmpcSimArgs ka) {
+  svb_sim_body<MODEL, false>(ka.k, ka.ep, ka.ru, nullptr);
+}
+__global__ __launch_bounds__(SVB_THREADS) void svmpc_skid_nav_sim_kernel(const SvmpcNavSimArgs ka) {
+  svb_sim_body<DUST_MODEL_SKID_STEER, true>(ka.k, ka.ep, ka.ru, &ka.nav);
+}
+template <int MODEL>
+__global__ __launch_bounds__(SVB_THREADS) void svmpc_rows_sim_kernel(const SvmpcRowsSimArgs ka) {
+  const SvbHyper h = ka.rows[blockIdx.x];  // (the whole row, ahead of the copy)
+  SvmpcBatchArgs a = ka.k;
+  SVB_HYPER_APPLY(a, h);
+  svb_sim_body<MODEL, false>(a, ka.ep, ka.ru, nullptr);
 }
 
 }  // namespace dust

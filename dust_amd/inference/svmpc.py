@@ -1,4 +1,6 @@
 """`SVMPC` with the reference's constructor and methods (dust/inference/svmpc.py:14-200, svgd.py:109-125)."""
+import collections
+
 import numpy as np
 import torch
 
@@ -467,3 +469,69 @@ class BatchSVMPC:
             rows = None
         xs, acts, pw, a_seq = batch.episode(self._states(states), T, n_steps, rows, plant_params, None if active is None else on)
         return torch.from_numpy(xs), torch.from_numpy(acts), torch.from_numpy(pw), torch.from_numpy(a_seq)
+
+    # -- run_particle_episode / run_pendulum_simulation (simulations.py:104-130, 217-260) for every environment: the episode under the
+    # reference's rules - warm-up, the accumulated cost, crash and goal
+    def simulate(self, states, params_dist, n_periods, warm_up=0, goal=None, goal_radius=None, stop_on_crash=False, plant_params=None,
+                 n_steps=None, active=None, params=None, resume=None):
+        """run_episodes() under the reference's episode rules, still ONE launch (dust_svmpc_batch_simulate).  While the episode's period
+        index is below `warm_up` a period is optimize() alone and the plant gets a zero action; the controller's instantaneous cost of
+        every new state is recorded and summed in fp32 into `loss`, the quantity the tuning scripts minimise; `stop_on_crash`: a new
+        position on an occupied cell of the model's (or the navigation cost's) map ends the environment with loss = inf, status 2;
+        `goal` [ds] with `goal_radius` > 0: an environment within the radius ends with status 1.  `resume`: the result of a previous
+        call - the episode goes on from its loss, status and period index (a changed plant, such as the reference's load at steps // 4,
+        is two calls).  The dynamics samples are drawn as run_episodes() draws them: under one torch.manual_seed the call consumes the
+        torch stream as `n_periods` calls of optimize() / tick() with the same `active` do.
+        -> SimResult(states [T, B, ds], actions [T, B, da], p_weights [T, B, N], costs [T, B], loss [B], status [B], n_run [B], a_seq
+        [B, H, da]) with the attribute t0 (the periods the episode has run); rows the call did not write - past n_run[b], warm-up rows
+        of p_weights, inactive environments - are NaN (n_run: -1)."""
+        check_optimizer(self.optimizer, self._opt_group)
+        ctrl, model = self.likelihood.controller, self.likelihood.model
+        T, warm_up = int(n_periods), int(warm_up)
+        if not 1 <= T <= 4096:
+            raise ValueError("n_periods = %d outside [1, 4096]: one launch runs one episode piece, split a longer one" % T)
+        if warm_up < 0:
+            raise ValueError("warm_up = %d < 0" % warm_up)
+        on = self._active(active)
+        P = len(model.uncertain_params or ()) if ctrl._sampling else 0
+        if plant_params is not None:
+            plant_params = np.asarray(torch.as_tensor(plant_params, dtype=torch.float).numpy(), np.float32)
+            if P == 0 or plant_params.shape != (self.n_envs, P):
+                raise ValueError("plant_params has shape %s, the plants read %s" % (plant_params.shape, (self.n_envs, P) if P else "none"))
+        if (goal is None) != (goal_radius is None):
+            raise ValueError("goal and goal_radius come together")
+        if goal is not None:
+            goal = np.asarray(torch.as_tensor(goal, dtype=torch.float).numpy(), np.float32).reshape(-1)
+            if goal.shape != (ctrl.dim_s,) or not np.isfinite(goal).all():
+                raise ValueError("goal has shape %s: [%d] finite entries" % (goal.shape, ctrl.dim_s))
+            if not (np.isfinite(float(goal_radius)) and float(goal_radius) > 0):
+                raise ValueError("goal_radius must be finite and > 0")
+        if stop_on_crash:
+            from ..costs import cost_grid_key
+
+            has_map = (model.family == "particle" and bool(model.with_obstacle)) or cost_grid_key(ctrl.inst_cost_fn) is not None
+            if not has_map:
+                raise ValueError("stop_on_crash needs an occupancy map: Particle(with_obstacle=True) or a NavigationCost")
+        t0, loss, status = 0, None, None
+        if resume is not None:
+            t0, loss, status = int(resume.t0), resume.loss.numpy(), resume.status.numpy()
+            if loss.shape != (self.n_envs,) or status.shape != (self.n_envs,):
+                raise ValueError("resume carries %d environments, the batch has %d" % (loss.size, self.n_envs))
+        n_steps = self.n_steps if n_steps is None else n_steps
+        batch = self._ensure_batch(params_dist)
+        if params is not None:
+            rows = np.asarray(torch.as_tensor(params, dtype=torch.float).numpy(), np.float32)
+        elif ctrl._sampling:
+            rows = np.stack([self._params(params_dist, n_steps, on, None) for _ in range(T)])
+        else:
+            rows = None
+        out = batch.simulate(self._states(states), T, n_steps, rows, plant_params, t0=t0, warm_up=warm_up, goal=goal, goal_radius=goal_radius,
+                             stop_on_crash=stop_on_crash, loss=loss, status=status, active=None if active is None else on)
+        res = SimResult(*(torch.from_numpy(np.ascontiguousarray(v)) for v in out))
+        res.t0 = t0 + T
+        return res
+
+
+class SimResult(collections.namedtuple("SimResult", "states actions p_weights costs loss status n_run a_seq")):
+    """What BatchSVMPC.simulate returns; `t0`: the periods the episode has run so far (simulate(resume=) goes on from there)"""
+    t0 = 0

@@ -142,3 +142,41 @@ def run_particle_episode(init_state, model, dyn_dist, controller, use_svmpc=True
         if float((system.target - state).norm()) <= 1.0:
             break
     return cum_cost
+
+
+def run_particle_episodes(init_states, model, dyn_dist, batch_svmpc, warm_up=30, load=0, steps=400, plant_params=None):
+    """The batched twin of `run_particle_episode`: environment b of `batch_svmpc` (a `BatchSVMPC` over `model`) runs that episode from
+    init_states[b] on the device (`BatchSVMPC.simulate`: warm-up, accumulated cost, crash - when the model has obstacles - and the goal
+    `model.target` within 1.0), in pieces of at most 4096 periods.  The plants are deterministic and step under `plant_params` [B, P]
+    (the columns and the space of the controller's dynamics samples; None: the nominal model); with `load` != 0 the episode is split at
+    steps // 4 and the true mass grows by `load` from there on, which needs `mass` among the model's uncertain parameters.
+    -> losses [B]: the cumulated cost of every environment, inf after a crash."""
+    import numpy as np
+
+    ctrl = batch_svmpc.likelihood.controller
+    B = batch_svmpc.n_envs
+    state = torch.as_tensor(init_states, dtype=torch.float).reshape(B, -1).clone()
+    steps = int(steps)
+    rows = None if plant_params is None else torch.as_tensor(plant_params, dtype=torch.float).reshape(B, -1).clone()
+    loaded = rows
+    if load != 0:
+        names = tuple(model.uncertain_params or ()) if ctrl._sampling else ()
+        if "mass" not in names:
+            raise ValueError("load != 0 changes the plants' mass: 'mass' must be one of the model's uncertain parameters")
+        log_space = bool(ctrl._params_log_space)
+        if rows is None:
+            nominal = torch.tensor([float(model.params_dict[k]) for k in names])
+            rows = (nominal.log() if log_space else nominal).repeat(B, 1)
+        j = names.index("mass")
+        loaded = rows.clone()
+        loaded[:, j] = (rows[:, j].exp() + load).log() if log_space else rows[:, j] + load
+    cuts = sorted({0, steps} | ({min(steps // 4, steps)} if load != 0 else set()) | set(range(0, steps, 4096)))
+    crash = bool(model.with_obstacle)
+    res = None
+    for lo, hi in zip(cuts[:-1], cuts[1:]):
+        res = batch_svmpc.simulate(state, dyn_dist, hi - lo, warm_up=warm_up, goal=model.target, goal_radius=1.0, stop_on_crash=crash,
+                                   plant_params=loaded if (load != 0 and lo >= steps // 4) else rows, resume=res)
+        n = res.n_run.numpy()
+        for b in np.nonzero(n > 0)[0]:
+            state[b] = res.states[n[b] - 1, b]
+    return res.loss if res is not None else torch.zeros(B)

@@ -531,6 +531,38 @@ typedef struct dust_svmpc_hyper { /* one environment's row; the fields of dust_c
 } dust_svmpc_hyper;
 int dust_svmpc_batch_set_hyper(dust_svmpc_batch *batch, const dust_svmpc_hyper *rows /* [B], or NULL: back to the prototype's */);
 int dust_svmpc_batch_get_hyper(dust_svmpc_batch *batch, dust_svmpc_hyper *rows /* [B]: the prototype's values where none are set */);
+/* dust_svmpc_batch_simulate = dust_svmpc_batch_episode under the reference's episode rules (run_particle_episode / run_pendulum_simulation,
+ * simulations.py:104-130 and 217-260), still ONE launch (svmpc_episode.hpp svb_sim_body).  Period t of the call is period g = t0 + t of
+ * the episode:
+ *   warm-up    g < warm_up: the period is what dust_svmpc_batch_optimize runs (no forward: no roll, no prior refresh; the Philox position
+ *              and the optimiser count move as an optimize call moves them), the plant gets a zero action; pw_out's row and a_seq are
+ *              not written.  Otherwise the period is the tick;
+ *   cost       the family's own instantaneous cost (the rollouts' - Particle with w_obs x collision, skid-steer / cart-pole the
+ *              quadratic state cost, plus the map term under the navigation cost) of the state AFTER the step, with a zero action:
+ *              costs_out[t][b], and loss[b] += cost as an fp32 running sum in period order;
+ *   crash      stop_on_crash: the new position lies on an occupied cell of the batch's map -> loss[b] = +inf, status[b] = 2, stop;
+ *   goal       goal_radius > 0: in fp32, d_k = goal[k] - x[k], s = ((d_0 d_0 + d_1 d_1) + d_2 d_2) + .. over the ds state entries,
+ *              s <= (float)(goal_radius * goal_radius) -> status[b] = 1, stop.  The crash rule wins when both hold.
+ * loss [B] and status [B] are read at entry and written at the end, so calls chain (t0: the periods the episode has run so far); an
+ * environment that enters with status != 0 does nothing and nothing of it is written, except n_run[b] = 0.  n_run[b]: the periods
+ * environment b ran in this call.  Afterwards environment b is where n_run[b] calls would have left it - dust_svmpc_batch_optimize
+ * while warming up, then dust_svmpc_batch_tick: getters, counters, noise streams.  Rows t >= n_run[b] of states_out / actions_out /
+ * pw_out / costs_out are NOT written, nor are the rows of inactive environments (loss, status and n_run included); a_seq [B][H][da] (may
+ * be NULL) receives the row of an environment only when one of its periods ran forward().  With per-environment rows set the sweep
+ * instances launch.  Everything else as dust_svmpc_batch_episode.
+ * Refused before anything is staged, the batch and the in-out arrays unchanged - DUST_ERR_INVALID: what dust_svmpc_batch_episode
+ * refuses; NULL rules, loss, status, n_run or costs_out; t0 < 0 or warm_up < 0; a goal or radius that is not finite; an entry status
+ * outside 0 .. 2.  DUST_ERR_UNSUPPORTED: stop_on_crash on a batch with no occupancy map (Particle's with_obstacle map, or the
+ * navigation cost's). */
+typedef struct dust_episode_rules {
+  int t0, warm_up, stop_on_crash;
+  float goal_radius; /* <= 0: no goal rule */
+  float goal[8];     /* the first ds entries are read */
+} dust_episode_rules;
+int dust_svmpc_batch_simulate(dust_svmpc_batch *batch, const float *states, int n_periods, int n_steps, const float *params,
+                              const float *plant_params, const dust_episode_rules *rules, int flags, const unsigned char *active,
+                              float *states_out, float *actions_out, float *pw_out, float *costs_out /* [T][B] */,
+                              float *loss /* [B] in-out */, int *status /* [B] in-out */, int *n_run /* [B] out */, float *a_seq);
 
 /* stage outputs of the last call, for parity tests ([S][N] / [N][H][da] / [N]) */
 int dust_get_costs(dust_ctx *ctx, float *costs);
