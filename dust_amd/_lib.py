@@ -190,6 +190,11 @@ SYMBOLS = {
                                       C.POINTER(C.c_ubyte), FP, FP, FP, FP, FP, FP]),
     "dust_svmpc_dual_batch_episode": (C.c_int, [VP, VP, FP, FP, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_uint64), FP, C.c_int,
                                                 C.POINTER(C.c_ubyte), FP, FP, FP, FP, FP]),
+    "dust_svmpc_dual_batch_optimize": (C.c_int, [VP, VP, FP, FP, C.c_int, VP, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_uint64), C.POINTER(C.c_ubyte),
+                                                 FP, FP]),
+    "dust_svmpc_dual_batch_simulate": (C.c_int, [VP, VP, FP, FP, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_uint64), FP,
+                                                 C.POINTER(EpisodeRules), C.c_int, C.POINTER(C.c_ubyte), FP, FP, FP, FP, FP, FP, C.POINTER(C.c_int),
+                                                 C.POINTER(C.c_int), FP]),
     "dust_get_costs": (C.c_int, [VP, FP]),
     "dust_get_actions": (C.c_int, [VP, FP]),
     "dust_get_states_rows": (C.c_int, [VP, C.POINTER(C.c_longlong), C.c_int, VP]),

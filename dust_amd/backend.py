@@ -1113,6 +1113,66 @@ class SvmpcBatch(_BatchHandle):
                                                        _p(xs), _p(acts), _p(pw), _p(bw), _p(a_seq)))
         return xs, acts, pw, bw, a_seq
 
+    def dual_optimize(self, mpf, states, actions_prev=None, n_steps=1, eps=None, mpf_steps=20, mpf_bw=None, seeds=None, active=None,
+                      want_outputs=True, want_params=False, flags=0, eps_dev_ptr=None, keep_actions=False):
+        """One WARM-UP period of the DuSt-MPC loop for every active environment in one C call (dust_svmpc_dual_batch_optimize): dual_tick()
+        without forward() - the filters' update, then the n_steps SVGD iterations under rows drawn from the refreshed priors; no roll,
+        no sequence, no weights.  -> (params [B, n_steps, M, P] or None, bw_used [B] or None); the rows of inactive environments are NaN."""
+        B = self.B
+        st, e, _, fl = self._inputs(states, n_steps, eps, None, eps_dev_ptr, keep_actions)
+        ap = None if actions_prev is None else _f(actions_prev, (B, self.da))
+        sd, sp = _seeds(seeds, B)
+        _, mp = _mask(active, B)
+        bw = np.full((B,), np.nan, np.float32) if want_outputs else None
+        pout = np.full((B, int(n_steps), self.M, max(self.P, 1)), np.nan, np.float32) if want_params else None
+        L.check(L.load().dust_svmpc_dual_batch_optimize(self._h, mpf._h, _p(st), _p(ap), int(n_steps), e if eps_dev_ptr else _vp(e), int(flags) | fl,
+                                                        int(mpf_steps), float(-1.0 if mpf_bw is None else mpf_bw), sp, mp, _p(pout), _p(bw)))
+        return pout, bw
+
+    def dual_simulate(self, mpf, states, n_periods, n_steps, actions_prev=None, mpf_steps=20, mpf_bw=None, seeds=None, plant_params=None,
+                      t0=0, warm_up=0, goal=None, goal_radius=None, stop_on_crash=False, loss=None, status=None, active=None, want_pw=True,
+                      flags=0):
+        """dual_episode() under the reference's episode rules, in one C call (dust_svmpc_dual_batch_simulate): period t is period t0 + t of
+        the episode; below warm_up the tick runs without forward() and the plant gets a zero action while the filters keep updating; the
+        cost of every new state goes to `costs` and, as an fp32 running sum, to `loss`; crash (status 2, loss inf) and goal (status 1)
+        stop an environment on both sides - no further filter update, no tick.  loss / status [B]: where a previous call left them.
+        -> (states [T, B, ds], actions [T, B, da], p_weights [T, B, N] or None, bw [T, B], costs [T, B], loss [B], status [B] int32,
+        n_run [B] int32, a_seq [B, H, da]); rows the call did not write - past n_run[b], warm-up rows of p_weights, inactive
+        environments - are NaN (n_run: -1)."""
+        B, T = self.B, int(n_periods)
+        st = None if states is None else _f(states, (B, self.ds))  # (None: the library refuses)
+        ap = None if actions_prev is None else _f(actions_prev, (B, self.da))
+        rows = max(T, 0)  # (n_periods < 1: the library refuses before it reads or writes anything)
+        if seeds is not None and np.shape(seeds) != (rows, B):
+            raise ValueError("seeds has shape %s, the call reads %s" % (np.shape(seeds), (rows, B)))
+        sd, sp = _seeds(seeds, rows * B)
+        pl = None
+        if plant_params is not None:
+            pl = _f(plant_params)
+            if pl.shape != (B, max(self.P, 1)):
+                raise ValueError("plant_params has shape %s, the call reads %s" % (pl.shape, (B, max(self.P, 1))))
+        ru = L.EpisodeRules()
+        ru.t0, ru.warm_up, ru.stop_on_crash = int(t0), int(warm_up), int(bool(stop_on_crash))
+        ru.goal_radius = 0.0 if goal_radius is None else float(goal_radius)
+        if goal is not None:
+            g = np.asarray(goal, np.float32).reshape(-1)
+            if g.shape != (self.ds,):
+                raise ValueError("goal has %d entries, a state has %d" % (g.size, self.ds))
+            ru.goal[:self.ds] = [float(v) for v in g]
+        _, mp = _mask(active, B)
+        xs, acts, bw, costs, a_seq = (np.full(sh, np.nan, np.float32)
+                                      for sh in ((rows, B, self.ds), (rows, B, self.da), (rows, B), (rows, B), (B, self.H, self.da)))
+        pw = np.full((rows, B, self.N), np.nan, np.float32) if want_pw else None
+        loss = np.zeros(B, np.float32) if loss is None else np.array(_f(loss, (B,)))
+        status = np.zeros(B, np.int32) if status is None else np.ascontiguousarray(np.array(status, np.int32).reshape(B))
+        n_run = np.full(B, -1, np.int32)
+        IP = C.POINTER(C.c_int)
+        L.check(L.load().dust_svmpc_dual_batch_simulate(self._h, mpf._h, _p(st), _p(ap), T, int(n_steps), int(mpf_steps),
+                                                        float(-1.0 if mpf_bw is None else mpf_bw), sp, _p(pl), C.byref(ru), int(flags), mp,
+                                                        _p(xs), _p(acts), _p(pw), _p(bw), _p(costs), _p(loss), status.ctypes.data_as(IP),
+                                                        n_run.ctypes.data_as(IP), _p(a_seq)))
+        return xs, acts, pw, bw, costs, loss, status, n_run, a_seq
+
 
 class MpfBatch(_BatchHandle):
     """B dynamics filters of one configuration, updated in one launch (dust_mpf_batch_*): per environment its particles, optimiser

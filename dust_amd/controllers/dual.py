@@ -17,6 +17,7 @@ stays on the unfused path) - in ONE C call (dust_dual_tick): step() then only no
 filter's particles are current again after that forward().  The draws come from the library's Philox stream (not torch's), so a run
 with recorded draws (`draw_source`) stays on the unfused path.  `serve=True` turns on closed-loop serving for the control half when its shape allows it (nominal dynamics only:
 a filter-coupled controller samples dynamics parameters per tick, which serving does not take - then it is a no-op)."""
+import collections
 import copy
 
 import numpy as np
@@ -453,11 +454,15 @@ class BatchDualSVMPC(_BatchDual):
         tick(states, plant)                         forward, `plant(states, actions) -> new_states`, step
 
     `mpf` is the prototype: every environment starts from its particles (or from `init_particles[b]`, [B, Mp, P]), optimiser state and
-    bandwidths; the first forward()'s states are the observations the first update's predictions start from.  There is no unfused path
-    and no `warm_up`: what the fused call does not take (a sigma-point controller, recorded draws) is refused.  The controller's cost
-    is any `BatchSVMPC` runs: a skid-steer `NavigationCost` ticks in svmpc_skid_nav_prior_batch_kernel, one map for the B robots."""
+    bandwidths; the first forward()'s states are the observations the first update's predictions start from.
+    There is no unfused path: what the fused call does not take (a sigma-point controller, recorded draws) is refused.  `warm_up`
+    (simulations.py:104-117):
+    while `ticks < warm_up` forward() is a warm-up period (dust_svmpc_dual_batch_optimize) - the filters update, the particles take
+    their SVGD iterations, nothing rolls - and returns a zero a_seq and None for the weights, the lone `DualSVMPC.forward` contract.
+    The controller's cost is any `BatchSVMPC` runs: a skid-steer `NavigationCost` ticks in svmpc_skid_nav_prior_batch_kernel, one map
+    for the B robots.  simulate() is the whole episode under the reference's rules in one C call."""
 
-    def __init__(self, svmpc, mpf, mpf_bw=None, mpf_steps=20, n_steps=None, seed=0, init_particles=None):
+    def __init__(self, svmpc, mpf, mpf_bw=None, mpf_steps=20, n_steps=None, seed=0, init_particles=None, warm_up=0):
         from ..inference.svmpc import BatchSVMPC
 
         if not isinstance(svmpc, BatchSVMPC):
@@ -467,8 +472,10 @@ class BatchDualSVMPC(_BatchDual):
         if mpf.draw_source is not None:
             raise NotImplementedError("recorded filter draws (draw_source) have no batched form")
         self._no_rows(svmpc)
+        if int(warm_up) < 0:
+            raise ValueError("warm_up = %d < 0" % int(warm_up))
         _BatchDual.__init__(self, svmpc.n_envs, mpf, mpf_bw, mpf_steps, seed, init_particles)
-        self.svmpc, self.n_steps = svmpc, n_steps
+        self.svmpc, self.n_steps, self.warm_up = svmpc, n_steps, int(warm_up)
 
     @staticmethod
     def _no_rows(svmpc):
@@ -501,14 +508,20 @@ class BatchDualSVMPC(_BatchDual):
         st = sv._states(states)
         mb = self._filters(st)
         pend = self._pending
-        a_seq, pw, _, bw = batch.dual_tick(mb, st, None if pend is None else pend[0], n_steps=n_steps, eps=sv._eps(eps),
-                                           mpf_steps=self.mpf_steps, mpf_bw=self.mpf_bw, seeds=self.prior_keys(self._t + 1),
-                                           active=None if active is None else sv._active(active))
+        if self.ticks < self.warm_up:  # a warm-up period: no forward(), a zero sequence for the plant (DualSVMPC.forward's contract)
+            _, bw = batch.dual_optimize(mb, st, None if pend is None else pend[0], n_steps=n_steps, eps=sv._eps(eps),
+                                        mpf_steps=self.mpf_steps, mpf_bw=self.mpf_bw, seeds=self.prior_keys(self._t + 1),
+                                        active=None if active is None else sv._active(active))
+            a_seq, pw = np.zeros((self.n_envs, batch.H, batch.da), np.float32), None
+        else:
+            a_seq, pw, _, bw = batch.dual_tick(mb, st, None if pend is None else pend[0], n_steps=n_steps, eps=sv._eps(eps),
+                                               mpf_steps=self.mpf_steps, mpf_bw=self.mpf_bw, seeds=self.prior_keys(self._t + 1),
+                                               active=None if active is None else sv._active(active))
         self._t, self._pending = self._t + 1, None  # (a refused call consumes neither the keys nor the noted update)
         if pend is not None:
             self.last_bw = torch.from_numpy(bw)
         self.ticks += 1
-        return torch.from_numpy(a_seq), torch.from_numpy(pw)
+        return torch.from_numpy(a_seq), None if pw is None else torch.from_numpy(pw)
 
     def tick(self, states, plant):
         """One loop iteration with a host plant callable `plant(states [B, ds], actions [B, da]) -> new_states [B, ds]`: forward,
@@ -568,3 +581,89 @@ class BatchDualSVMPC(_BatchDual):
             self.last_bw = torch.from_numpy(bw[-1].copy())
         self.ticks += T
         return torch.from_numpy(xs), torch.from_numpy(acts), torch.from_numpy(pw), torch.from_numpy(a_seq)
+
+    # -- run_pendulum_simulation(mpf=...) / the Particle loop of demo/particle_example.py for every environment: the episode under the
+    # reference's rules - warm-up with the filters updating, the accumulated cost, crash and goal
+    def simulate(self, states, n_periods, goal=None, goal_radius=None, stop_on_crash=False, plant_params=None, n_steps=None, active=None,
+                 resume=None):
+        """run_episodes() under the reference's episode rules, in one C call (dust_svmpc_dual_batch_simulate).  The period index starts at
+        `resume.t0` (0 without `resume`); while it is below `self.warm_up` a period is forward()'s warm-up period - the filters update,
+        the plant gets a zero action; the controller's instantaneous cost of every new state is recorded and summed in fp32 into `loss`;
+        `stop_on_crash` (Particle with_obstacle): a new position on an occupied cell ends the environment with loss = inf, status 2;
+        `goal` [ds] with `goal_radius` > 0: an environment within the radius ends with status 1.  A stopped environment takes no
+        further filter update and no tick; environments with `resume.status != 0` are passed as inactive.  Period t draws under
+        `prior_keys(_t + 1 + t)`.
+        -> DualSimResult(states [T, B, ds], actions [T, B, da], p_weights [T, B, N], bw [T, B], costs [T, B], loss [B], status [B],
+        n_run [B], a_seq [B, H, da]) with the attribute t0; rows the call did not write - past n_run[b], warm-up rows of p_weights,
+        inactive environments - are NaN (n_run: -1).  Afterwards the noted update is, per environment, (actions[n_run - 1],
+        states[n_run - 1]), or the pair the environment came with when n_run <= 0.  The filters' particles are not recorded per
+        period: `dyn_particles` reads them after the call (and carries the noted update out first)."""
+        from ..inference.svmpc import check_optimizer
+        from ..models import CartPoleModel, SkidSteerRobot
+
+        sv = self.svmpc
+        self._no_rows(sv)
+        ctrl, model = sv.likelihood.controller, sv.likelihood.model
+        T = int(n_periods)
+        if not 1 <= T <= 4096:
+            raise ValueError("n_periods = %d outside [1, 4096]: one call runs one episode piece, chain a longer one" % T)
+        for mdl in (model, getattr(self.mpf.likelihood, "model", None)):
+            if isinstance(mdl, (SkidSteerRobot, CartPoleModel)):
+                raise NotImplementedError("simulate conditions the filters on the device: Pendulum and Particle (a %s pair runs tick())"
+                                          % type(mdl).__name__)
+        P = self.mpf._dev.P
+        if plant_params is not None:
+            plant_params = np.asarray(torch.as_tensor(plant_params, dtype=torch.float).numpy(), np.float32)
+            if plant_params.shape != (self.n_envs, P):
+                raise ValueError("plant_params has shape %s, the plants read %s" % (plant_params.shape, (self.n_envs, P)))
+        if (goal is None) != (goal_radius is None):
+            raise ValueError("goal and goal_radius come together")
+        if goal is not None:
+            goal = np.asarray(torch.as_tensor(goal, dtype=torch.float).numpy(), np.float32).reshape(-1)
+            if goal.shape != (ctrl.dim_s,) or not np.isfinite(goal).all():
+                raise ValueError("goal has shape %s: [%d] finite entries" % (goal.shape, ctrl.dim_s))
+            if not (np.isfinite(float(goal_radius)) and float(goal_radius) > 0):
+                raise ValueError("goal_radius must be finite and > 0")
+        if stop_on_crash and not (model.family == "particle" and bool(model.with_obstacle)):
+            raise ValueError("stop_on_crash needs an occupancy map: Particle(with_obstacle=True)")
+        B = self.n_envs
+        on = np.ones(B, bool) if active is None else np.array(sv._active(active), bool)
+        t0, loss, status = 0, None, None
+        if resume is not None:
+            t0, loss, status = int(resume.t0), resume.loss.numpy(), resume.status.numpy()
+            if loss.shape != (B,) or status.shape != (B,):
+                raise ValueError("resume carries %d environments, the batch has %d" % (loss.size, B))
+            on = on & (status == 0)
+        check_optimizer(sv.optimizer, sv._opt_group)
+        batch = sv._ensure_batch(self.mpf.prior)
+        if n_steps is None:
+            n_steps = sv.n_steps if self.n_steps is None else self.n_steps
+        st = sv._states(states)
+        mb = self._filters(st)
+        pend = self._pending
+        keys = np.array([self.prior_keys(self._t + 1 + t) for t in range(T)], np.uint64)
+        masked = active is not None or resume is not None
+        out = batch.dual_simulate(mb, st, T, n_steps, None if pend is None else pend[0], mpf_steps=self.mpf_steps, mpf_bw=self.mpf_bw,
+                                  seeds=keys, plant_params=plant_params, t0=t0, warm_up=self.warm_up, goal=goal, goal_radius=goal_radius,
+                                  stop_on_crash=stop_on_crash, loss=loss, status=status, active=on if masked else None)
+        # (a refused call consumes neither the keys nor the noted update)
+        xs, acts, pw, bw, costs, loss, status, n_run, a_seq = out
+        a_last = np.zeros((B, acts.shape[2]), np.float32) if pend is None else pend[0].copy()
+        x_last = np.array(st, np.float32).reshape(B, -1).copy()
+        for e in range(B):
+            n = int(n_run[e])
+            if n > 0:  # (n <= 0: the environment keeps the pair it came with)
+                a_last[e], x_last[e] = acts[n - 1, e], xs[n - 1, e]
+        have = pend is not None or bool((n_run > 0).any())
+        self._t, self._pending = self._t + T, ((a_last, x_last) if have else None)
+        if (pend is not None or T > 1) and bool((n_run == T).any()):
+            self.last_bw = torch.from_numpy(bw[-1].copy())
+        self.ticks += T
+        res = DualSimResult(*(torch.from_numpy(np.ascontiguousarray(v)) for v in (xs, acts, pw, bw, costs, loss, status, n_run, a_seq)))
+        res.t0 = t0 + T
+        return res
+
+
+class DualSimResult(collections.namedtuple("DualSimResult", "states actions p_weights bw costs loss status n_run a_seq")):
+    """What BatchDualSVMPC.simulate returns; `t0`: the periods the episode has run so far (simulate(resume=) goes on from there)"""
+    t0 = 0

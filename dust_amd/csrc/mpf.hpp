@@ -2488,13 +2488,14 @@ extern "C" int dust_amppi_dual_batch_tick(dust_amppi_batch *b, dust_mpf_batch *m
 // AHEAD of the filters' launches (that copy waits for the stream).  The number of launches does not depend on B.  An environment with
 // active[b] = 0 keeps everything on both sides, and its output rows are not written.  With every output NULL the call returns without
 // waiting for the device.
-extern "C" int dust_svmpc_dual_batch_tick(dust_svmpc_batch *b, dust_mpf_batch *mb, const float *states, const float *actions_prev, int n_steps,
-                                          const void *eps, int flags, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds,
-                                          const unsigned char *active, float *a_seq, float *p_weights, float *params_out, float *bw_used) {
+// do_forward = false: the period WITHOUT forward() (dust_svmpc_dual_batch_optimize) - the same launches, svmpc_prior_batch_kernel told so
+static int svb_dual_period_call(dust_svmpc_batch *b, dust_mpf_batch *mb, const float *states, const float *actions_prev, int n_steps, const void *eps,
+                                int flags, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds, const unsigned char *active, const bool do_forward,
+                                float *a_seq, float *p_weights, float *params_out, float *bw_used) {
   if (!b || !mb || !states) return fail(DUST_ERR_INVALID, "null argument");
   if (n_steps < 1 || mpf_steps < 0) return fail(DUST_ERR_INVALID, "bad step counts");
   dust_ctx *c = b->c;
-  TRY(svb_call_check(b, states, n_steps, nullptr, true, flags, true));  // (sigma-point weights among it: no batched sigma rollouts)
+  TRY(svb_call_check(b, states, n_steps, nullptr, true, flags, do_forward));  // (sigma-point weights among it: no batched sigma rollouts)
   TRY(dual_batch_pair_check(c, "SVMPC", b->B, mb));
   if (!prior_seeds) return fail(DUST_ERR_INVALID, "null argument: the draws from the filters' priors need prior_seeds [B]");
   const size_t prow = (size_t)n_steps * (size_t)c->M * (size_t)mb->m->P;
@@ -2509,21 +2510,39 @@ extern "C" int dust_svmpc_dual_batch_tick(dust_svmpc_batch *b, dust_mpf_batch *m
   // (a REFUSAL cannot come from here on: every check ran above.  A runtime error of svb_go - a pinned slot, a failed launch - leaves the
   // filters' update enqueued without mpfb_commit: their host rows (loc / past / opt_t) then lag the device, as under
   // dust_amppi_dual_batch_tick; such an error is not recoverable for the pair)
-  TRY(svb_go(b, states, n_steps, eps_dev, nullptr, flags, active, true, &pr));
+  TRY(svb_go(b, states, n_steps, eps_dev, nullptr, flags, active, do_forward, &pr));
   bool copies = a_seq || p_weights || params_out;
   TRY(svb_outputs_copy(b, active, a_seq, p_weights));
   if (params_out) TRY(rows_d2h(b->B, c->stream, params_out, b->params, prow, active));
   TRY(dual_batch_bw(c, mb, rows, actions_prev, mpf_bw, active, bw_used, &copies));
   return dual_batch_close(c, mb, copies);
 }
+extern "C" int dust_svmpc_dual_batch_tick(dust_svmpc_batch *b, dust_mpf_batch *mb, const float *states, const float *actions_prev, int n_steps,
+                                          const void *eps, int flags, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds,
+                                          const unsigned char *active, float *a_seq, float *p_weights, float *params_out, float *bw_used) {
+  return svb_dual_period_call(b, mb, states, actions_prev, n_steps, eps, flags, mpf_steps, mpf_bw, prior_seeds, active, true, a_seq, p_weights,
+                              params_out, bw_used);
+}
+// One WARM-UP period of the loop (simulations.py:104-117 while step < warm_up): the tick above without forward() - the filters' update,
+// then the one launch of svmpc_prior_batch_kernel with do_forward = 0: n_steps SVGD iterations under rows drawn from the refreshed priors.
+// The batch is left where dust_svmpc_batch_optimize fed params_out leaves it; the Philox position moves by the iterations alone.
+extern "C" int dust_svmpc_dual_batch_optimize(dust_svmpc_batch *b, dust_mpf_batch *mb, const float *states, const float *actions_prev, int n_steps,
+                                              const void *eps, int flags, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds,
+                                              const unsigned char *active, float *params_out, float *bw_used) {
+  return svb_dual_period_call(b, mb, states, actions_prev, n_steps, eps, flags, mpf_steps, mpf_bw, prior_seeds, active, false, nullptr, nullptr,
+                              params_out, bw_used);
+}
 
 // The epilogue of a dual episode (dust_svmpc_dual_batch_episode, dust_amppi_dual_batch_episode) behind its one wait: bw_out where it is
 // answered on the host, and the filters' host rows moved to where T ticks leave them, from the MpfEnvIn rows read back (in_host)
-static void dual_episode_commit(dust_mpf_batch *mb, MpfbRows &rows, const std::vector<dust::MpfEnvIn> &in_host, size_t T, bool first, bool silverman,
-                                float mpf_bw, const unsigned char *active, float *bw_out) {
+// ran (dust_svmpc_dual_batch_simulate): the periods environment e ran, in place of T - none: its rows stay where they were
+static void dual_episode_commit(dust_mpf_batch *mb, MpfbRows &rows, const std::vector<dust::MpfEnvIn> &in_host, size_t n_periods, bool first, bool silverman,
+                                float mpf_bw, const unsigned char *active, float *bw_out, const int *ran = nullptr) {
   const size_t B = (size_t)mb->B;
   for (size_t e = 0; e < B; ++e) {
     if (active && !active[e]) continue;
+    const size_t T = ran ? (size_t)ran[e] : n_periods;
+    if (T == 0) continue;
     if (bw_out) {  // what bw_used of the period's dual tick is: 0 without an update, the fixed bandwidth, or Silverman's (recorded above)
       if (!first) bw_out[e] = 0.f;
       if (!silverman)
@@ -2556,10 +2575,21 @@ static void dual_episode_commit(dust_mpf_batch *mb, MpfbRows &rows, const std::v
 // prior_seeds + t B, the plant, the records, and the conditioning of the MpfEnvIn rows for period t + 1.  No host wait, event or copy lies
 // between two periods; the call waits once, for the records, reads the MpfEnvIn rows back and moves the filters' host rows to where T
 // ticks leave them: the pair (a_{T-1}, x_T) is NOT folded in (the last period conditions nothing).
-extern "C" int dust_svmpc_dual_batch_episode(dust_svmpc_batch *b, dust_mpf_batch *mb, const float *states, const float *actions_prev, int n_periods,
-                                             int n_steps, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds, const float *plant_params, int flags,
-                                             const unsigned char *active, float *states_out, float *actions_out, float *pw_out, float *bw_out, float *a_seq) {
+//
+// rules (dust_svmpc_dual_batch_simulate; NULL: dust_svmpc_dual_batch_episode): the episode under the reference's rules
+// (run_pendulum_simulation(mpf=...), simulations.py:104-138; the Particle loop's crash and goal, 217-260).  The mask that is staged - always,
+// so that it is never NULL - is then the RUN MASK active[b] && status[b] == 0: every launch of the call - Silverman, the update, the period
+// kernel - takes it, and lane 0 of svmpc_dual_sim_period_kernel clears an environment's byte in the period that stops it, so a stopped
+// environment takes no further update and no tick.  The rules' words [B] loss | status | n_run lie behind the records.  The host queues T
+// period launches whatever stops; per launch it sets do_forward = (t0 + t >= warm_up).  Afterwards environment b is, on both sides, where
+// n_run[b] per-period calls would have left it (dust_svmpc_dual_batch_optimize while warming up, dust_svmpc_dual_batch_tick afterwards):
+// the filters' host rows are committed from n_run[b], not from T.
+static int svb_dual_episode_call(dust_svmpc_batch *b, dust_mpf_batch *mb, const float *states, const float *actions_prev, int n_periods, int n_steps,
+                                 int mpf_steps, float mpf_bw, const uint64_t *prior_seeds, const float *plant_params, const dust_episode_rules *rules,
+                                 int flags, const unsigned char *active, float *states_out, float *actions_out, float *pw_out, float *bw_out,
+                                 float *costs_out, float *loss, int *status, int *n_run, float *a_seq) {
   if (!b || !mb || !states || !states_out || !actions_out) return fail(DUST_ERR_INVALID, "null argument");
+  if (rules && (!loss || !status || !n_run || !costs_out)) return fail(DUST_ERR_INVALID, "null argument: loss, status, n_run and costs_out are required");
   if (!prior_seeds) return fail(DUST_ERR_INVALID, "null argument: the draws from the filters' priors need prior_seeds [T][B]");
   if (n_periods < 1 || n_periods > 4096)
     return fail(DUST_ERR_INVALID, "n_periods = %d outside [1, 4096] (the queue of one call stays short on a shared device: chain a longer episode)", n_periods);
@@ -2568,7 +2598,22 @@ extern "C" int dust_svmpc_dual_batch_episode(dust_svmpc_batch *b, dust_mpf_batch
   dust_ctx *c = b->c;
   dust_mpf *m = mb->m;
   if (c->cfg.dim_p == 0 && plant_params) return fail(DUST_ERR_INVALID, "plant parameter rows without uncertain parameters (dim_p = 0)");
-  TRY(svb_call_check(b, states, n_steps, nullptr, true, 0, true));
+  const size_t T = (size_t)n_periods, B = (size_t)b->B, N = (size_t)c->N, P = (size_t)c->cfg.dim_p, ds = (size_t)c->ds, da = (size_t)c->da, D = (size_t)c->D;
+  bool forward = true;  // some period of the call runs forward()
+  if (rules) {
+    if (rules->t0 < 0 || rules->warm_up < 0) return fail(DUST_ERR_INVALID, "t0 = %d, warm_up = %d: both are >= 0", rules->t0, rules->warm_up);
+    if (rules->t0 > 0x7fffffff - 4096) return fail(DUST_ERR_INVALID, "t0 = %d: the episode's period index does not fit", rules->t0);
+    bool finite = std::isfinite(rules->goal_radius);
+    for (size_t k = 0; k < ds && k < 8; ++k) finite = finite && std::isfinite(rules->goal[k]);
+    if (!finite) return fail(DUST_ERR_INVALID, "the goal and its radius must be finite");
+    for (size_t e = 0; e < B; ++e)
+      if ((!active || active[e]) && (status[e] < 0 || status[e] > 2))
+        return fail(DUST_ERR_INVALID, "status[%zu] = %d: 0 (running), 1 (goal) or 2 (crash)", e, status[e]);
+    if (rules->stop_on_crash && !(c->cfg.model == DUST_MODEL_PARTICLE && c->cfg.with_obstacle && c->grid_bits))
+      return fail(DUST_ERR_UNSUPPORTED, "stop_on_crash needs an occupancy map: Particle with_obstacle");
+    forward = rules->t0 + n_periods > rules->warm_up;
+  }
+  TRY(svb_call_check(b, states, n_steps, nullptr, true, 0, forward));
   TRY(dual_batch_pair_check(c, "SVMPC", b->B, mb));
   auto host_lik = [](int model) { return model == DUST_MODEL_SKID_STEER || model == DUST_MODEL_CARTPOLE; };
   if (host_lik(c->cfg.model) || host_lik(m->cfg.model_cfg.model))
@@ -2581,80 +2626,146 @@ extern "C" int dust_svmpc_dual_batch_episode(dust_svmpc_batch *b, dust_mpf_batch
   if (first || n_periods > 1) TRY(mpfb_update_check(mb, first ? actions_prev : states, states, mpf_steps, active));
   HIP_TRY(hipSetDevice(c->cfg.device));
   TRY(settle_pending(c));
+  // ---- who takes part: the caller's mask, or (rules) the run mask
+  std::vector<unsigned char> run(rules ? B : 0);
+  for (size_t e = 0; e < run.size(); ++e) run[e] = ((!active || active[e]) && status[e] == 0) ? 1 : 0;
+  const unsigned char *on = rules ? run.data() : active;
   // ---- room (reallocations free behind the device's queued work)
-  const size_t T = (size_t)n_periods, B = (size_t)b->B, N = (size_t)c->N, P = (size_t)c->cfg.dim_p, ds = (size_t)c->ds, da = (size_t)c->da;
   const bool silverman = !(mpf_bw > 0.f);
   TRY(mpfb_gn_room(mb, mpf_steps));
   const size_t off_seeds = B * sizeof(dust::MpfEnvIn), off_plant = off_seeds + T * B * sizeof(uint64_t), n_stage = off_plant + B * P * sizeof(float);
   TRY(mb->ep.ensure(n_stage));
   if (mb->ep_host.cap() < n_stage) TRY(mb->ep_host.alloc(n_stage, hipHostMallocDefault));
   const bool bw_dev = bw_out && silverman;
-  const size_t n_rec = T * B * (ds + da + (pw_out ? N : 0) + (bw_dev ? 1 : 0));
+  // the records [T][B]: states | actions | weights | bandwidths | (rules) costs, then (rules) the words [B] loss | status | n_run
+  const size_t words = T * B * (ds + da + (pw_out ? N : 0) + (bw_dev ? 1 : 0) + (rules ? 1 : 0)), n_rec = words + (rules ? 3 * B : 0);
   TRY(b->rec.ensure(n_rec));
   // ---- staged once: states and mask; the filters' rows as period 0's update reads them (or, without one, as they stand), seeds, plants
-  TRY(b->in.stage(c, states, active));
+  TRY(b->in.stage(c, states, on));
   unsigned char *hb = mb->ep_host;  // (free: every call that wrote it has waited for its stream)
   MpfbRows rows;
-  mpfb_rows(mb, actions_prev, first ? states : nullptr, first ? mpf_steps : 0, active, hb, rows);
+  mpfb_rows(mb, actions_prev, first ? states : nullptr, first ? mpf_steps : 0, on, hb, rows);
   memcpy(hb + off_seeds, prior_seeds, T * B * sizeof(uint64_t));
   if (plant_params) memcpy(hb + off_plant, plant_params, B * P * sizeof(float));
   HIP_TRY(hipStreamWaitEvent(c->stream, mb->ev_ext, 0));
   HIP_TRY(hipMemcpyAsync(mb->ep, hb, plant_params ? n_stage : off_plant, hipMemcpyHostToDevice, c->stream));
+  float *rec_s = b->rec, *rec_a = rec_s + T * B * ds, *rec_pw = rec_a + T * B * da, *rec_bw = rec_pw + (pw_out ? T * B * N : 0),
+        *rec_c = rec_bw + (bw_dev ? T * B : 0), *rec_w = b->rec + words;
+  if (rules) {
+    std::vector<float> in(3 * B, 0.f);  // (n_run starts at 0: an environment that enters stopped has run no period)
+    memcpy(in.data(), loss, B * sizeof(float));
+    memcpy(in.data() + B, status, B * sizeof(int));
+    TRY(h2d(c, rec_w, in.data(), 3 * B * sizeof(float)));
+  }
   if (first || n_periods > 1) serve_cancel_device(m->cfg.device);  // (as mpfb_enqueue, once for the call)
   // ---- the periods
   dust::MpfEnvIn *in_dev = mpfb_in_view(mb->ep.get());
   const uint64_t *seeds_dev = reinterpret_cast<const uint64_t *>(mb->ep.get() + off_seeds);
-  const unsigned char *mask = b->in.mask_dev(active);
-  SvmpcDualPeriodArgs ka;
-  svb_args(b, n_steps, nullptr, nullptr, active, true, ka.k);
+  const unsigned char *mask = b->in.mask_dev(on);
+  SvmpcDualSimPeriodArgs ka;  // (its first three members are the plain period's arguments)
+  svb_args(b, n_steps, nullptr, nullptr, on, true, ka.k);
   dual_batch_prior(mb, nullptr, ka.pr);
-  float *rec_s = b->rec, *rec_a = rec_s + T * B * ds, *rec_pw = rec_a + T * B * da, *rec_bw = rec_pw + (pw_out ? T * B * N : 0);
+  memset(&ka.ds, 0, sizeof ka.ds);
+  if (rules) {
+    ka.ds.stop_on_crash = rules->stop_on_crash ? 1 : 0;
+    ka.ds.goal_on = rules->goal_radius > 0.f ? 1 : 0;
+    ka.ds.r2 = (float)((double)rules->goal_radius * (double)rules->goal_radius);
+    for (size_t k = 0; k < 8; ++k) ka.ds.goal[k] = k < ds ? rules->goal[k] : 0.f;
+    ka.ds.loss = rec_w;
+    ka.ds.status = reinterpret_cast<int *>(rec_w + B);
+    ka.ds.n_run = ka.ds.status + B;
+    ka.ds.run = const_cast<unsigned char *>(mask);
+  }
   const size_t lds = svmpc_batch_lds_bytes(c->N, c->D, c->M);
+  const size_t warm = rules ? (size_t)std::max(0, rules->warm_up - rules->t0) : 0;  // periods of this call without forward()
   for (size_t t = 0; t < T; ++t) {
     const bool update = t > 0 || first;
     if (update) TRY(mpfb_update_launch(mb, c->stream, in_dev, mask, mpf_bw, mpf_steps));
     mb->n_calls++;
+    ka.k.do_forward = t >= warm ? 1 : 0;
     ka.pr.seeds = seeds_dev + t * B;
     ka.dp.plant = plant_params ? reinterpret_cast<const float *>(mb->ep.get() + off_plant) : nullptr;
     ka.dp.state = const_cast<float *>(b->in.states_dev());
     ka.dp.in = in_dev;
     ka.dp.states_out = rec_s + t * B * ds;
     ka.dp.actions_out = rec_a + t * B * da;
-    ka.dp.pw_out = pw_out ? rec_pw + t * B * N : nullptr;
+    ka.dp.pw_out = pw_out && t >= warm ? rec_pw + t * B * N : nullptr;
     ka.dp.bw = bw_dev && update ? mb->bw.get() : nullptr;
     ka.dp.bw_out = bw_dev ? rec_bw + t * B : nullptr;
     ka.dp.t0_add = update ? mpf_steps : 0;
     ka.dp.condition = t + 1 < T ? 1 : 0;
+    ka.ds.costs_out = rec_c + t * B;
     Prof pr(c, DUST_K_SVMPC_BATCH);
     const hipError_t launched = by_model(c, [&](auto M) -> hipError_t {
-      if constexpr (M() == DUST_MODEL_PENDULUM || M() == DUST_MODEL_PARTICLE)
-        return launch_on(c->stream, false, &svmpc_dual_period_kernel<M()>, b->B, SVB_THREADS, lds, ka);
-      else return hipErrorInvalidValue;  // (refused above)
+      if constexpr (M() == DUST_MODEL_PENDULUM || M() == DUST_MODEL_PARTICLE) {
+        if (rules) return launch_on(c->stream, false, &svmpc_dual_sim_period_kernel<M()>, b->B, SVB_THREADS, lds, ka);
+        SvmpcDualPeriodArgs kp;
+        kp.k = ka.k;
+        kp.pr = ka.pr;
+        kp.dp = ka.dp;
+        return launch_on(c->stream, false, &svmpc_dual_period_kernel<M()>, b->B, SVB_THREADS, lds, kp);
+      } else return hipErrorInvalidValue;  // (refused above)
     });
     HIP_TRY(launched);
   }
   b->have_costs = true;
   b->acts_kept = false;
-  b->have_forward = true;
-  // ---- the records and the advanced rows come back once; the rows of inactive environments stay out of the caller's arrays
-  std::vector<float> host(n_rec);
+  if (forward) b->have_forward = true;
+  // ---- the records, the words and the advanced rows come back once; the rows of inactive environments stay out of the caller's arrays
+  std::vector<float> host(n_rec), seq(a_seq && rules ? B * D : 0);
   std::vector<dust::MpfEnvIn> in_host(B);
   HIP_TRY(hipMemcpyAsync(host.data(), b->rec, n_rec * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(in_host.data(), in_dev, B * sizeof(dust::MpfEnvIn), hipMemcpyDeviceToHost, c->stream));
-  TRY(svb_outputs_copy(b, active, a_seq, nullptr));
+  if (a_seq && rules) HIP_TRY(hipMemcpyAsync(seq.data(), b->a_seq_out, B * D * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  else TRY(svb_outputs_copy(b, active, a_seq, nullptr));
   HIP_TRY(hipEventRecord(mb->ev_ext, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  auto out = [&](float *dst, const float *src, size_t row) {
-    for (size_t t = 0; t < T; ++t)
-      for (size_t e = 0; e < B; ++e)
-        if (!active || active[e]) memcpy(dst + (t * B + e) * row, src + (t * B + e) * row, row * sizeof(float));
+  std::vector<int> ran(rules ? B : 0);  // (rules) the periods every environment ran: nothing of it is written past row ran[e] - 1
+  if (rules) memcpy(ran.data(), host.data() + words + 2 * B, B * sizeof(int));
+  for (size_t e = 0; e < ran.size(); ++e)
+    if (!run[e]) ran[e] = 0;
+  // rows [from, the periods it ran) of a participating environment's record
+  auto out = [&](float *dst, const float *dev, size_t row, size_t from) {
+    const float *src = host.data() + (dev - b->rec.get());
+    for (size_t e = 0; e < B; ++e)
+      for (size_t t = from; (!on || on[e]) && t < (rules ? (size_t)ran[e] : T); ++t)
+        memcpy(dst + (t * B + e) * row, src + (t * B + e) * row, row * sizeof(float));
   };
-  out(states_out, host.data(), ds);
-  out(actions_out, host.data() + T * B * ds, da);
-  if (pw_out) out(pw_out, host.data() + T * B * (ds + da), N);
-  if (bw_dev) out(bw_out, host.data() + T * B * (ds + da + (pw_out ? N : 0)), 1);
-  dual_episode_commit(mb, rows, in_host, T, first, silverman, mpf_bw, active, bw_out);
+  out(states_out, rec_s, ds, 0);
+  out(actions_out, rec_a, da, 0);
+  if (pw_out) out(pw_out, rec_pw, N, warm);
+  if (bw_dev) out(bw_out, rec_bw, 1, 0);
+  if (rules) {
+    out(costs_out, rec_c, 1, 0);
+    for (size_t e = 0; e < B; ++e) {
+      if (active && !active[e]) continue;
+      n_run[e] = ran[e];
+      if (ran[e] == 0) continue;  // (entered with status != 0: nothing else of it is written)
+      memcpy(loss + e, host.data() + words + e, sizeof(float));
+      memcpy(status + e, host.data() + words + B + e, sizeof(int));
+      if (a_seq && (size_t)ran[e] > warm) memcpy(a_seq + e * D, seq.data() + e * D, D * sizeof(float));
+    }
+  }
+  dual_episode_commit(mb, rows, in_host, T, first, silverman, mpf_bw, on, bw_out, rules ? ran.data() : nullptr);
   return DUST_OK;
+}
+
+extern "C" int dust_svmpc_dual_batch_episode(dust_svmpc_batch *b, dust_mpf_batch *mb, const float *states, const float *actions_prev, int n_periods,
+                                             int n_steps, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds, const float *plant_params, int flags,
+                                             const unsigned char *active, float *states_out, float *actions_out, float *pw_out, float *bw_out, float *a_seq) {
+  return svb_dual_episode_call(b, mb, states, actions_prev, n_periods, n_steps, mpf_steps, mpf_bw, prior_seeds, plant_params, nullptr, flags, active,
+                               states_out, actions_out, pw_out, bw_out, nullptr, nullptr, nullptr, nullptr, a_seq);
+}
+
+// ... under the reference's episode rules: warm-up with the filters updating, the cost, crash and goal
+extern "C" int dust_svmpc_dual_batch_simulate(dust_svmpc_batch *b, dust_mpf_batch *mb, const float *states, const float *actions_prev, int n_periods,
+                                              int n_steps, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds, const float *plant_params,
+                                              const dust_episode_rules *rules, int flags, const unsigned char *active, float *states_out,
+                                              float *actions_out, float *pw_out, float *bw_out, float *costs_out, float *loss, int *status, int *n_run,
+                                              float *a_seq) {
+  if (!rules) return fail(DUST_ERR_INVALID, "null rules");
+  return svb_dual_episode_call(b, mb, states, actions_prev, n_periods, n_steps, mpf_steps, mpf_bw, prior_seeds, plant_params, rules, flags, active,
+                               states_out, actions_out, pw_out, bw_out, costs_out, loss, status, n_run, a_seq);
 }
 
 // T control periods of the dual loop over the AMPPI batch for B environments in one call: T successive dust_amppi_dual_batch_tick calls

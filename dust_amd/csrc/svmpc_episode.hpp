@@ -35,6 +35,12 @@
 // update of a period is a launch of its own (mpf_optimize_batch_kernel: 1 024 lanes, another order of partial sums), so the periods of
 // that episode are a chain of launches on one stream, with no host in between; what a period hands to the next - the state row and the
 // filters' MpfEnvIn row - is written here by lane 0 and read by LATER launches only, so the carry of one period still lives in registers.
+//
+// svmpc_dual_sim_period_kernel: that period under the rules of svb_sim_body, for dust_svmpc_dual_batch_simulate.  The host sets do_forward
+// per launch (0 while the episode warms up: the filters still update, the plant gets the zero action); the loss, the status and the count
+// of periods are words in device memory that lane 0 of one launch writes and LATER launches read; a stopping environment clears its
+// byte of the call's run mask with its last store, and every later launch of the call - Silverman's rule, the filters' update, this
+// kernel - skips the environment.  A second body beside svb_dual_period_body: svmpc_dual_period_kernel keeps its text.
 #pragma once
 #include "mpf_env.hpp"
 #include "svmpc_batch.hpp"
@@ -327,6 +333,98 @@ __device__ __forceinline__ void svb_sim_body(const SvmpcBatchArgs &a, const SvbE
     ru.status[env] = status;
     ru.loss[env] = loss;
   }
+}
+
+// What a period of dust_svmpc_dual_batch_simulate adds to svb_dual_period_body's: the rules' words of the call, carried from launch to
+// launch in device memory - written by lane 0 of one launch, read by LATER launches only
+struct SvbDualSim {
+  int stop_on_crash, goal_on;  // as SvbRules'
+  float r2;
+  float goal[8];
+  float *costs_out;    // [B] this period's row of the cost records
+  float *loss;         // [B] the fp32 running sum of the costs in period order
+  int *status;         // [B] 0 running, 1 goal, 2 crash
+  int *n_run;          // [B] the periods this call has run
+  unsigned char *run;  // [B] the run mask every launch of the call takes (SvmpcBatchArgs::active names the same bytes)
+};
+struct SvmpcDualSimPeriodArgs {
+  SvmpcBatchArgs k;  // do_forward: 0 while the episode warms up, set by the host per launch; active: the run mask
+  SvbPrior pr;
+  SvbDualPeriod dp;  // pw_out: nullptr in a warm-up period
+  SvbDualSim ds;
+};
+
+// svb_dual_period_body's period under the rules of svb_sim_body: the PRIOR tick - without forward() while the episode warms up, the plant
+// then gets the zero action -, the plant's step, the cost of the new state, crash and goal, the records, and the conditioning for the next
+// period unless the environment has just stopped: (a_{n-1}, x_n) then stays pending, as behind a call's last period.  Whether it stops is
+// computed by every lane from the carry in its registers and read-only data; lane 0 stores all of it, and clears the environment's byte
+// of the run mask with its LAST store: the filter launches and period launches queued behind this one skip the environment.
+template <int MODEL>
+__device__ __forceinline__ void svb_dual_sim_period_body(const SvmpcBatchArgs &a, const SvbPrior &pri, const SvbDualPeriod &dp, const SvbDualSim &ru) {
+  static_assert(MODEL == DUST_MODEL_PENDULUM || MODEL == DUST_MODEL_PARTICLE, "the other families' likelihood rows are made on the host");
+  constexpr int DS = SvbDims<MODEL>::DS;
+  const int env = (int)blockIdx.x;
+  if (a.active[env] == 0) return;  // (the run mask: never NULL here; an earlier LAUNCH may have cleared the byte)
+  SvbCarry<MODEL> cy;
+  DevModel map;
+  float w_obs;
+  svb_begin<MODEL, false>(a, nullptr, cy, map, w_obs);
+  float cf[SVB_COEF];
+  svb_coef<MODEL>(a, dp.plant ? dp.plant + (size_t)env * a.P : nullptr, cf);
+  float loss = ru.loss[env];
+  float act[2] = {0.f, 0.f};  // (warm-up: no forward() writes it - the plant gets the zero action)
+  svb_tick<MODEL, true, false, true>(a, &pri, nullptr, cy, map, w_obs, dp.pw_out ? dp.pw_out + (size_t)env * a.N : nullptr, act);
+  svb_plant_step<MODEL>(a, cf, cy.x0, act);
+  const float cost = svb_state_cost<MODEL, false>(a, cy.x0, map, w_obs);
+  loss += cost;
+  int status = 0;
+  if (ru.goal_on) {
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < DS; ++k) {
+      const float d = ru.goal[k] - cy.x0[k];
+      s = k == 0 ? d * d : s + d * d;
+    }
+    if (s <= ru.r2) status = 1;
+  }
+  if (ru.stop_on_crash && svb_crashed<MODEL, false>(a, cy.x0, map)) {  // (the crash rule wins)
+    status = 2;
+    loss = INFINITY;
+  }
+  svb_end(a, cy);
+  if (threadIdx.x == 0) {
+    float *xs = dp.state + (size_t)env * 8;
+    MpfEnvIn *in = dp.in + env;
+#pragma unroll
+    for (int k = 0; k < DS; ++k) {
+      dp.states_out[(size_t)env * DS + k] = cy.x0[k];
+      xs[k] = cy.x0[k];
+    }
+    dp.actions_out[(size_t)env * a.da] = act[0];
+    if (a.da == 2) dp.actions_out[(size_t)env * 2 + 1] = act[1];
+    if (dp.bw_out) dp.bw_out[env] = dp.bw ? dp.bw[env] : 0.f;
+    ru.costs_out[env] = cost;
+    ru.loss[env] = loss;
+    ru.n_run[env] += 1;
+    if (dp.condition && status == 0) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) in->past_obs[k] = in->obs[k];
+#pragma unroll
+      for (int k = 0; k < DS; ++k) in->obs[k] = cy.x0[k];
+      in->past_action[0] = act[0];
+      in->past_action[1] = act[1];
+    }
+    if (dp.t0_add) in->t0 += dp.t0_add;
+    if (status != 0) {
+      ru.status[env] = status;
+      ru.run[env] = 0;  // the launch's last store for this environment
+    }
+  }
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(SVB_THREADS) void svmpc_dual_sim_period_kernel(const SvmpcDualSimPeriodArgs ka) {
+  svb_dual_sim_period_body<MODEL>(ka.k, ka.pr, ka.dp, ka.ds);
 }
 
 template <int MODEL>

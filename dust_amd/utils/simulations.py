@@ -144,12 +144,81 @@ def run_particle_episode(init_state, model, dyn_dist, controller, use_svmpc=True
     return cum_cost
 
 
-def run_particle_episodes(init_states, model, dyn_dist, batch_svmpc, warm_up=30, load=0, steps=400, plant_params=None):
+def run_pendulum_simulations(init_state, init_policies, model_kwargs, experiment_params, controller, svmpc_kwargs, lik_kwargs, mpf, mpf_bw=None,
+                             mpf_steps=20, episodes=3, steps=200, warm_up=1, seed=0, init_particles=None, frame=False):
+    """The batched twin of `run_pendulum_simulation(use_svmpc=True, mpf=...)`: the `episodes` become the B environments of one
+    `BatchSVMPC` plus `BatchDualSVMPC`, environment i's plant runs under `experiment_params[i]`, and the whole loop - warm-up periods
+    that only optimize and apply a zero action while the filters keep updating, the cost of every new state - runs on the device, one
+    `BatchDualSVMPC.simulate` call per piece of at most 4096 periods.  `svmpc_kwargs` are SVMPC's keywords (init_particles, prior, ...;
+    `seeds` too), `lik_kwargs` ExponentiatedUtility's, `mpf` the filter prototype every environment copies (`init_particles`
+    [B, Mp, P]: its own start), `seed` the base of the filters' prior keys.
+
+    The plants.  They step the CONTROLLER'S model - `PendulumModel(**model_kwargs)`, the model of all B environments - under the true
+    rows: the columns of its `uncertain_params`, from `experiment_params[i]` (a name it lacks keeps the model's value), without noise and
+    with the action clamped as the rollouts clamp it.  The lone driver's plant is a stand-in for gym's Pendulum-v0 with g = 10;
+    `model_kwargs=dict(g=10.0, ...)` gives this driver the same equations.  The nominal values of the uncertain parameters are never
+    read: every dynamics sample is drawn from the environment's filter.
+
+    -> a dict of arrays under the reference frame's column names, [B, steps] unless stated: `Cost`, `Position`, `Speed`, `Actions`,
+    `Timestep`, `Iteration`, `DynBandwidths`, `Weights` [B, steps, N] (NaN while warming up), `ExpParams` [B, steps, P], `AvgCumCost`,
+    and - the episode is not interrupted to read them - `DynParticles` [B, Mp, P] and `PolParticles` [B, N]: the FINAL filter particles
+    (the last pair folded in) and the final particles' first actions, not one row per period.  frame=True: the reference's pandas
+    frame of the per-period columns, when pandas imports (it is optional here); otherwise the dict."""
+    import numpy as np
+
+    from ..controllers.dual import BatchDualSVMPC
+    from ..inference.svmpc import BatchSVMPC
+
+    B, steps = int(episodes), int(steps)
+    if len(experiment_params) < B:
+        raise ValueError("experiment_params has %d entries for %d episodes" % (len(experiment_params), B))
+    model = PendulumModel(**model_kwargs)
+    names = tuple(model.uncertain_params or ())
+    if not names:
+        raise ValueError("the dual loop estimates the model's uncertain_params: model_kwargs names none")
+    sim_ctrl = deepcopy(controller)
+    sim_ctrl.a_mat = init_policies.detach().clone()
+    sim_ctrl.return_rollouts = False
+    sv = BatchSVMPC(B, likelihood=ExponentiatedUtility(**lik_kwargs, controller=sim_ctrl, model=model), **svmpc_kwargs)
+    dual = BatchDualSVMPC(sv, mpf, mpf_bw=mpf_bw, mpf_steps=mpf_steps, seed=seed, init_particles=init_particles, warm_up=warm_up)
+    true = torch.tensor([[float(experiment_params[i].get(k, model.params_dict[k])) for k in names] for i in range(B)], dtype=torch.float)
+    rows = true.log() if bool(sim_ctrl._params_log_space) else true
+    state = torch.as_tensor(init_state, dtype=torch.float).reshape(1, -1).repeat(B, 1)
+    out, res = [], None
+    for lo in range(0, steps, 4096):
+        res = dual.simulate(state, min(4096, steps - lo), plant_params=rows, resume=res)
+        out.append(res)
+        state = res.states[-1]
+    cat = lambda k: torch.cat([getattr(r, k) for r in out]).transpose(0, 1).numpy()  # [B, steps, ...]
+    xs, cost = cat("states"), cat("costs")
+    t = np.broadcast_to(np.arange(steps), (B, steps))
+    data = {"Cost": cost, "Position": xs[..., 0], "Speed": xs[..., 1], "Actions": cat("actions")[..., 0], "Timestep": t.copy(),
+            "Iteration": np.broadcast_to(np.arange(B)[:, None], (B, steps)).copy(), "DynParticles": dual.dyn_particles.numpy(),
+            "DynBandwidths": cat("bw"), "PolParticles": dual.theta[:, :, 0, 0].numpy(), "Weights": cat("p_weights"),
+            "ExpParams": np.broadcast_to(true.numpy()[:, None], (B, steps, len(names))).copy(),
+            "AvgCumCost": np.round(np.cumsum(cost.astype(np.float64), 1) / (t + 1), 2)}
+    if frame:
+        try:
+            import pandas as pd
+        except ImportError:
+            return data
+        per = ("Cost", "Position", "Speed", "Actions", "Timestep", "Iteration", "DynBandwidths", "AvgCumCost")
+        cols = {k: data[k].reshape(-1) for k in per}
+        cols["Weights"], cols["ExpParams"] = data["Weights"].reshape(B * steps, -1).tolist(), data["ExpParams"].reshape(B * steps, -1).tolist()
+        return pd.DataFrame(index=list(t.reshape(-1)), data=cols)
+    return data
+
+
+def run_particle_episodes(init_states, model, dyn_dist, batch_svmpc, warm_up=30, load=0, steps=400, plant_params=None, mpf=None, mpf_bw=None,
+                          mpf_steps=20):
     """The batched twin of `run_particle_episode`: environment b of `batch_svmpc` (a `BatchSVMPC` over `model`) runs that episode from
     init_states[b] on the device (`BatchSVMPC.simulate`: warm-up, accumulated cost, crash - when the model has obstacles - and the goal
     `model.target` within 1.0), in pieces of at most 4096 periods.  The plants are deterministic and step under `plant_params` [B, P]
     (the columns and the space of the controller's dynamics samples; None: the nominal model); with `load` != 0 the episode is split at
     steps // 4 and the true mass grows by `load` from there on, which needs `mass` among the model's uncertain parameters.
+    `mpf` (a filter prototype, as run_particle_episode's): the episode is the DuSt-MPC loop - every environment a copy of the filter,
+    updated after every plant step, the warm-up periods included, and stopped with its environment - on `BatchDualSVMPC.simulate`;
+    the dynamics samples then come from the filters (`dyn_dist` is not read).  The `load` split stays two calls.
     -> losses [B]: the cumulated cost of every environment, inf after a crash."""
     import numpy as np
 
@@ -173,9 +242,18 @@ def run_particle_episodes(init_states, model, dyn_dist, batch_svmpc, warm_up=30,
     cuts = sorted({0, steps} | ({min(steps // 4, steps)} if load != 0 else set()) | set(range(0, steps, 4096)))
     crash = bool(model.with_obstacle)
     res = None
+    dual = None
+    if mpf is not None:
+        from ..controllers.dual import BatchDualSVMPC
+
+        dual = BatchDualSVMPC(batch_svmpc, mpf, mpf_bw=mpf_bw, mpf_steps=mpf_steps, warm_up=warm_up)
     for lo, hi in zip(cuts[:-1], cuts[1:]):
-        res = batch_svmpc.simulate(state, dyn_dist, hi - lo, warm_up=warm_up, goal=model.target, goal_radius=1.0, stop_on_crash=crash,
-                                   plant_params=loaded if (load != 0 and lo >= steps // 4) else rows, resume=res)
+        plant = loaded if (load != 0 and lo >= steps // 4) else rows
+        if dual is not None:
+            res = dual.simulate(state, hi - lo, goal=model.target, goal_radius=1.0, stop_on_crash=crash, plant_params=plant, resume=res)
+        else:
+            res = batch_svmpc.simulate(state, dyn_dist, hi - lo, warm_up=warm_up, goal=model.target, goal_radius=1.0, stop_on_crash=crash,
+                                       plant_params=plant, resume=res)
         n = res.n_run.numpy()
         for b in np.nonzero(n > 0)[0]:
             state[b] = res.states[n[b] - 1, b]

@@ -854,6 +854,50 @@ int dust_svmpc_dual_batch_episode(dust_svmpc_batch *batch, dust_mpf_batch *mpf, 
                                   int n_periods, int n_steps, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds,
                                   const float *plant_params, int flags, const unsigned char *active,
                                   float *states_out, float *actions_out, float *pw_out, float *bw_out, float *a_seq);
+/* dust_svmpc_dual_batch_optimize = one WARM-UP period of the DuSt-MPC loop (simulations.py:104-117 while step < warm_up) for B
+ * environments: dust_svmpc_dual_batch_tick WITHOUT forward() - the filters' update for (actions_prev[b], states[b]) (skipped when
+ * actions_prev is NULL), then ONE launch of svmpc_prior_batch_kernel (or the navigation instance) with do_forward = 0.  No roll, no prior
+ * refresh, no a_seq and no weights; the Philox position and the optimiser count move as dust_svmpc_batch_optimize moves them.  The
+ * controller batch is left, bit for bit, where dust_svmpc_batch_optimize fed params_out would leave it; the filters where
+ * dust_mpf_batch_optimize leaves them.  Refusals, staging order, the filter side's launch count and the commit of the filters' host rows
+ * are the dual tick's. */
+int dust_svmpc_dual_batch_optimize(dust_svmpc_batch *batch, dust_mpf_batch *mpf, const float *states, const float *actions_prev, int n_steps,
+                                   const void *eps, int flags, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds,
+                                   const unsigned char *active, float *params_out, float *bw_used);
+/* dust_svmpc_dual_batch_simulate = dust_svmpc_dual_batch_episode under the reference's episode rules (dust_episode_rules, as
+ * dust_svmpc_batch_simulate reads them): the loop of run_pendulum_simulation(mpf=...) (simulations.py:104-138) with its warm-up and its
+ * cost, and the Particle loop's crash and goal, for B environments in one call.  Period t of the call is period g = t0 + t of the
+ * episode.  For an environment that is still running:
+ *   filter    when the period has an action (t >= 1, or actions_prev), Silverman's rule (mpf_bw <= 0) and the filters' update, reading
+ *             the per-environment rows in device memory - ALSO while the episode warms up;
+ *   period    ONE launch of svmpc_dual_sim_period_kernel (Pendulum, Particle; counted under DUST_K_SVMPC_BATCH): the PRIOR tick under
+ *             the key row prior_seeds + t B, with forward() only when g >= warm_up - below, the plant gets the zero action, no pw_out
+ *             row is written and the particles do not roll;
+ *   cost      the plant steps under the true row; the family's instantaneous cost of the new state goes to costs_out[t][b] and is added
+ *             in fp32 to loss[b];
+ *   stops     crash (status 2, loss = +inf; wins) and goal (status 1), the predicates of dust_svmpc_batch_simulate;
+ *   next      the filter's row is conditioned for period t + 1 unless this is the call's last period or the environment has just
+ *             stopped: a stop leaves (a_{n-1}, x_n) pending, exactly as the last period of a call does.
+ * A stopping environment clears its byte of a device-resident run mask (staged once as active[b] && status[b] == 0) with the launch's
+ * last store; every later launch of the call takes that mask, so a stopped environment takes no further filter update and no tick.  The
+ * host queues T period launches whatever stops and waits once.
+ * THE CONTRACT: afterwards environment b is, on both sides, where n_run[b] per-period calls would have left it -
+ * dust_svmpc_dual_batch_optimize while warming up and dust_svmpc_dual_batch_tick afterwards, with the environment inactive from its
+ * stop on: getters, counters and noise streams; the filters' particles, prior bandwidths, optimiser slots and step counts; the filters'
+ * host rows (observation, past observation, past action, step count), committed per environment from n_run[b] and not from T.
+ * Rows t >= n_run[b] of states_out / actions_out / pw_out / bw_out / costs_out are NOT written, nor anything of an inactive environment;
+ * bw_out[t][b] is 0 where no update ran; a_seq receives an environment's row only when one of its periods ran forward().  An environment
+ * entering with status != 0 does nothing: only n_run[b] = 0 is written.  With warm_up = 0, no goal and no crash rule the call computes,
+ * bit for bit, what dust_svmpc_dual_batch_episode computes.  The filters' particles are not recorded per period: read them after the call.
+ * Refused before anything is staged or launched, both batches and the in-out arrays unchanged.  DUST_ERR_INVALID: what
+ * dust_svmpc_dual_batch_episode refuses; NULL rules, loss, status, n_run or costs_out; t0 < 0 or warm_up < 0; a goal or radius that is
+ * not finite; an entry status outside 0 .. 2.  DUST_ERR_UNSUPPORTED: stop_on_crash without a Particle with_obstacle map; a skid-steer or
+ * cart-pole pair; per-environment hyper rows; any flag. */
+int dust_svmpc_dual_batch_simulate(dust_svmpc_batch *batch, dust_mpf_batch *mpf, const float *states, const float *actions_prev,
+                                   int n_periods, int n_steps, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds /* [T][B] */,
+                                   const float *plant_params, const dust_episode_rules *rules, int flags, const unsigned char *active,
+                                   float *states_out, float *actions_out, float *pw_out, float *bw_out, float *costs_out /* [T][B] */,
+                                   float *loss /* [B] in-out */, int *status /* [B] in-out */, int *n_run /* [B] out */, float *a_seq);
 
 #ifdef __cplusplus
 }
