@@ -5,6 +5,6 @@
 Nothing here falls back to the CPU: the HIP library must be built (`__graft_entry__.build()`) and a GPU present.
 """
 from . import _lib  # noqa: F401
-from .backend import AmppiBatch, Context, MpfBatch, MpfContext, SvmpcBatch, make_config  # noqa: F401
+from .backend import AmppiBatch, Context, DiscoBatch, MpfBatch, MpfContext, SvmpcBatch, make_config  # noqa: F401
 
-__all__ = ["AmppiBatch", "Context", "MpfBatch", "MpfContext", "SvmpcBatch", "make_config"]
+__all__ = ["AmppiBatch", "Context", "DiscoBatch", "MpfBatch", "MpfContext", "SvmpcBatch", "make_config"]

@@ -27,6 +27,8 @@ K_ROLLOUT, K_PRIOR_SCORE, K_STEIN, K_UPDATE, K_FORWARD, K_BANDWIDTH, K_MPF, K_RO
 K_SVMPC_BATCH, K_ALL = 9, 10  # appended behind ABI 3's first list (K_COUNT is that list's length); every id is < K_ALL
 (SVB_THETA, SVB_PRIOR_MEANS, SVB_PRIOR_MIX, SVB_A_MAT, SVB_COSTS, SVB_SCORE, SVB_PHI, SVB_LOG_L, SVB_LOG_P, SVB_A_MIX,
  SVB_ACTIONS) = range(11)
+DCB_A_MAT, DCB_A_SEQ, DCB_A_MIX, DCB_COSTS, DCB_OMEGA, DCB_ACTIONS = range(6)  # dust_disco_batch_quantity
+DISCO_PARAMS_ONCE = 128  # dust_disco_batch_episode: params [B][M][P] serves every period
 
 
 class DustError(RuntimeError):
@@ -173,6 +175,17 @@ SYMBOLS = {
     "dust_svmpc_batch_get_hyper": (C.c_int, [VP, C.POINTER(SvmpcHyper)]),
     "dust_svmpc_batch_simulate": (C.c_int, [VP, FP, C.c_int, C.c_int, FP, FP, C.POINTER(EpisodeRules), C.c_int, C.POINTER(C.c_ubyte), FP, FP, FP,
                                             FP, FP, C.POINTER(C.c_int), C.POINTER(C.c_int), FP]),
+    "dust_disco_batch_create": (C.c_int, [VP, C.c_int, C.POINTER(C.c_uint64), C.POINTER(VP)]),
+    "dust_disco_batch_destroy": (None, [VP]),
+    "dust_disco_batch_clone": (C.c_int, [VP, C.POINTER(VP)]),
+    "dust_disco_batch_ctx": (C.c_int, [VP, C.POINTER(VP)]),
+    "dust_disco_batch_set": (C.c_int, [VP, C.c_int, FP]),
+    "dust_disco_batch_get": (C.c_int, [VP, C.c_int, FP]),
+    "dust_disco_batch_forward": (C.c_int, [VP, FP, FP, FP, C.c_int, C.POINTER(C.c_ubyte)]),
+    "dust_disco_batch_step": (C.c_int, [VP, C.c_int, C.c_int, FP, C.POINTER(C.c_ubyte), FP]),
+    "dust_disco_batch_tick": (C.c_int, [VP, FP, FP, FP, C.c_int, C.POINTER(C.c_ubyte), C.c_int, C.c_int, FP, FP]),
+    "dust_disco_batch_episode": (C.c_int, [VP, FP, C.c_int, FP, FP, C.c_int, C.POINTER(EpisodeRules), C.c_int, C.POINTER(C.c_ubyte), FP, FP, FP,
+                                           FP, C.POINTER(C.c_int), C.POINTER(C.c_int), FP]),
     "dust_mpf_batch_create": (C.c_int, [VP, C.c_int, C.POINTER(VP)]),
     "dust_mpf_batch_destroy": (None, [VP]),
     "dust_mpf_batch_clone": (C.c_int, [VP, C.POINTER(VP)]),

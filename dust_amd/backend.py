@@ -599,6 +599,12 @@ class Context:
         runs the navigation instance on its one map (set_grid; without a map: ERR_STATE)."""
         return SvmpcBatch(self, n_envs, seeds)
 
+    def disco_batch(self, n_envs, seeds=None):
+        """`n_envs` independent MultiDISCO controllers of this context's configuration - a_mat, a_seq, a_mix and noise stream each -, one
+        kernel launch per forward / step / tick and per closed-loop episode (dust_disco_batch_create): the batch keeps its own copy of
+        the context.  seeds [n_envs] (None: this context's seed + b).  Sigma-point weights (set_param_weights) make it the "DISCO" case."""
+        return DiscoBatch(self, n_envs, seeds)
+
     def get_costs(self):
         return self._get(L.load().dust_get_costs, (self.S, self.N))
 
@@ -1172,6 +1178,139 @@ class SvmpcBatch(_BatchHandle):
                                                         _p(xs), _p(acts), _p(pw), _p(bw), _p(costs), _p(loss), status.ctypes.data_as(IP),
                                                         n_run.ctypes.data_as(IP), _p(a_seq)))
         return xs, acts, pw, bw, costs, loss, status, n_run, a_seq
+
+
+_STEP_IDS = {"argmax": L.STEP_ARGMAX, "average": L.STEP_AVERAGE, "external": L.STEP_EXTERNAL}
+
+
+class DiscoBatch(_BatchHandle):
+    """B independent MultiDISCO controllers in one launch (dust_disco_batch_*): per environment a state, a_mat, a_seq, a_mix, a noise
+    stream and parameter rows; everything else is the prototype context's.  `ctx` is the batch's inner context (borrowed) for sync() and
+    profile() / profile_get()."""
+
+    _destroy, _clone = "dust_disco_batch_destroy", "dust_disco_batch_clone"
+
+    def __init__(self, proto=None, n_envs=1, seeds=None, _handle=None):
+        self._h = None
+        lib = L.load()
+        if _handle is None:
+            sd, sp = _seeds(seeds, int(n_envs))
+            h = L.VP()
+            L.check(lib.dust_disco_batch_create(proto._h, int(n_envs), sp, C.byref(h)))
+            _handle = h
+        self._h = _handle
+        self.B = int(n_envs)
+        inner = L.VP()
+        L.check(lib.dust_disco_batch_ctx(self._h, C.byref(inner)))
+        self.ctx = Context(_handle=inner)
+        self.ctx._borrowed = True
+        c = self.ctx
+        self.N, self.S, self.H, self.da, self.ds, self.P, self.M = c.N, c.S, c.H, c.da, c.ds, c.P, c.M
+        B, N, S, H, da = self.B, self.N, self.S, self.H, self.da
+        self._shapes = {L.DCB_A_MAT: (B, N, H, da), L.DCB_A_SEQ: (B, H, da), L.DCB_A_MIX: (B, N), L.DCB_COSTS: (B, S, N),
+                        L.DCB_OMEGA: (B, S, N), L.DCB_ACTIONS: (B, S, N, H, da)}
+
+    def set(self, what, value):
+        """A_MAT [B, N, H, da], A_SEQ [B, H, da] (`what`: _lib.DCB_*)"""
+        L.check(L.load().dust_disco_batch_set(self._h, int(what), _p(_f(value, self._shapes[int(what)]))))
+
+    def get(self, what):
+        """any of _lib.DCB_*: a settable quantity, a_mix, or a record of the last forward"""
+        out = np.empty(self._shapes[int(what)], np.float32)
+        L.check(L.load().dust_disco_batch_get(self._h, int(what), _p(out)))
+        return out
+
+    def _forward_inputs(self, states, actions, params, around_a_mat, keep_actions):
+        B = self.B
+        st = None if states is None else _f(states, (B, self.ds))  # (None: the library refuses)
+        act = None if actions is None else _f(actions, (B, self.S, self.N, self.H, self.da))
+        pr = None
+        if params is not None:
+            pr = _f(params)
+            want = (B, self.M, max(self.P, 1))
+            if pr.shape != want:
+                raise ValueError("params has shape %s, the call reads %s" % (pr.shape, want))
+        return st, act, pr, (L.EPS_AROUND_A_MAT if around_a_mat else 0) | (L.SVMPC_BATCH_KEEP_ACTIONS if keep_actions else 0)
+
+    def _step_inputs(self, strategy, steps, ext_actions):
+        sid = _STEP_IDS.get(strategy, -1) if isinstance(strategy, str) else int(strategy)
+        ext = None if ext_actions is None else _f(ext_actions, (self.B, self.H, self.da))
+        rows = min(max(int(steps), 0), self.H)  # (steps outside [1, H]: the library refuses before it writes anything)
+        return sid, ext, np.full((self.B, rows, self.da), np.nan, np.float32)
+
+    def forward(self, states, actions=None, params=None, active=None, around_a_mat=False, keep_actions=False, flags=0):
+        """MultiDISCO.forward of every active environment in one launch (dust_disco_batch_forward).  states [B, ds]; actions
+        [B, S, N, H, da] recorded, or None (drawn on the device); params [B, M, P] (the sigma points under sigma weights) or None (no
+        uncertain parameters).  Nothing is read back: the call does not wait for the device."""
+        st, act, pr, fl = self._forward_inputs(states, actions, params, around_a_mat, keep_actions)
+        _, mp = _mask(active, self.B)
+        L.check(L.load().dust_disco_batch_forward(self._h, _p(st), _p(act), _p(pr), fl | int(flags), mp))
+
+    def step(self, strategy="argmax", steps=1, ext_actions=None, active=None):
+        """MultiDISCO.step of every active environment in one launch -> next_actions [B, steps, da]; inactive rows are NaN."""
+        sid, ext, nxt = self._step_inputs(strategy, steps, ext_actions)
+        _, mp = _mask(active, self.B)
+        L.check(L.load().dust_disco_batch_step(self._h, sid, int(steps), _p(ext), mp, _p(nxt)))
+        return nxt
+
+    def tick(self, states, strategy="argmax", steps=1, actions=None, params=None, ext_actions=None, active=None, around_a_mat=False,
+             keep_actions=False, flags=0):
+        """forward + step in ONE launch (dust_disco_batch_tick) -> next_actions as step()."""
+        st, act, pr, fl = self._forward_inputs(states, actions, params, around_a_mat, keep_actions)
+        sid, ext, nxt = self._step_inputs(strategy, steps, ext_actions)
+        _, mp = _mask(active, self.B)
+        L.check(L.load().dust_disco_batch_tick(self._h, _p(st), _p(act), _p(pr), fl | int(flags), mp, sid, int(steps), _p(ext), _p(nxt)))
+        return nxt
+
+    def episode(self, states, n_periods, strategy="average", params=None, plant_params=None, params_once=False, rules=None, loss=None,
+                status=None, active=None, flags=0):
+        """n_periods closed-loop periods of every active environment in ONE launch (dust_disco_batch_episode): per period forward (noise
+        drawn on the device), step(strategy, 1), the plant's step under the environment's true parameters.  params [T, B, M, P], or
+        [B, M, P] with params_once; plant_params [B, P] or None (nominal plants).  rules: None, or a dict with any of t0, goal [ds],
+        goal_radius, stop_on_crash (and warm_up, which must be 0) - the reference's episode rules as SvmpcBatch.simulate applies them;
+        loss / status [B]: where a previous call left them.  -> (states [T, B, ds], actions [T, B, da], a_seq [B, H, da]) without
+        rules, (states, actions, costs [T, B], loss [B], status [B], n_run [B], a_seq) with them; rows the call did not write are NaN
+        (n_run: -1)."""
+        B, T = self.B, int(n_periods)
+        st = None if states is None else _f(states, (B, self.ds))  # (None: the library refuses)
+        pr = pl = None
+        if params is not None:
+            pr = _f(params)
+            want = (B, self.M, max(self.P, 1)) if params_once else (T, B, self.M, max(self.P, 1))
+            if pr.shape != want:
+                raise ValueError("params has shape %s, the call reads %s" % (pr.shape, want))
+        if plant_params is not None:
+            pl = _f(plant_params)
+            if pl.shape != (B, max(self.P, 1)):
+                raise ValueError("plant_params has shape %s, the call reads %s" % (pl.shape, (B, max(self.P, 1))))
+        sid = _STEP_IDS.get(strategy, -1) if isinstance(strategy, str) else int(strategy)
+        _, mp = _mask(active, B)
+        rows = max(T, 0)  # (n_periods < 1: the library refuses before it writes anything)
+        xs, acts, a_seq = (np.full(sh, np.nan, np.float32) for sh in ((rows, B, self.ds), (rows, B, self.da), (B, self.H, self.da)))
+        fl = int(flags) | (L.DISCO_PARAMS_ONCE if params_once else 0)
+        IP = C.POINTER(C.c_int)
+        if rules is None:
+            L.check(L.load().dust_disco_batch_episode(self._h, _p(st), T, _p(pr), _p(pl), sid, None, fl, mp, _p(xs), _p(acts), None, None,
+                                                      None, None, _p(a_seq)))
+            return xs, acts, a_seq
+        unknown = set(rules) - {"t0", "warm_up", "goal", "goal_radius", "stop_on_crash"}
+        if unknown:
+            raise ValueError("rules has the unknown keys %s" % sorted(unknown))
+        ru = L.EpisodeRules()
+        ru.t0, ru.warm_up, ru.stop_on_crash = int(rules.get("t0", 0)), int(rules.get("warm_up", 0)), int(bool(rules.get("stop_on_crash", False)))
+        ru.goal_radius = 0.0 if rules.get("goal_radius") is None else float(rules["goal_radius"])
+        if rules.get("goal") is not None:
+            g = np.asarray(rules["goal"], np.float32).reshape(-1)
+            if g.shape != (self.ds,):
+                raise ValueError("goal has %d entries, a state has %d" % (g.size, self.ds))
+            ru.goal[:self.ds] = [float(v) for v in g]
+        costs = np.full((rows, B), np.nan, np.float32)
+        loss = np.zeros(B, np.float32) if loss is None else np.array(_f(loss, (B,)))
+        status = np.zeros(B, np.int32) if status is None else np.ascontiguousarray(np.array(status, np.int32).reshape(B))
+        n_run = np.full(B, -1, np.int32)
+        L.check(L.load().dust_disco_batch_episode(self._h, _p(st), T, _p(pr), _p(pl), sid, C.byref(ru), fl, mp, _p(xs), _p(acts), _p(costs),
+                                                  _p(loss), status.ctypes.data_as(IP), n_run.ctypes.data_as(IP), _p(a_seq)))
+        return xs, acts, costs, loss, status, n_run, a_seq
 
 
 class MpfBatch(_BatchHandle):

@@ -4,6 +4,7 @@
 The controller OWNS the device context (one dust_ctx): rollouts, costs, weights and - when an SVMPC is attached - the Stein
 particles and prior live there.  `copy.deepcopy(controller)` clones the context (dust_clone), as the simulation loops
 require (simulations.py:62, particle_example.py:166-175)."""
+import collections
 import copy
 
 import numpy as np
@@ -248,3 +249,248 @@ class MultiDISCO:
             return torch.from_numpy(self._ctx.disco_step(strategy, steps, ext))
         except L.DustError as e:
             raise ValueError(str(e))
+
+
+class DiscoSimResult(collections.namedtuple("DiscoSimResult", "states actions costs loss status n_run a_seq")):
+    """What BatchDISCO.simulate returns; `t0`: the periods the episode has run so far (simulate(resume=) goes on from there)"""
+
+
+class BatchDISCO(MultiDISCO):
+    """`n_envs` independent `MultiDISCO` controllers of one configuration - the deep copies the reference makes per episode
+    (simulations.py:62, 78) - whose forward / step / tick are ONE kernel launch each, and whose closed-loop episodes are one launch per
+    call (csrc/disco_batch.hpp).  Every environment has its own state, a_mat, a_seq, a_mix, noise stream (`seeds`, default seed + b) and
+    parameter rows.  The constructor takes MultiDISCO's arguments behind `n_envs` and refuses what lies outside the kernel's box
+    (N <= 64, S <= 1024, M <= 64, H d_a <= 128, a diagonal a_cov) before any device is touched.  `params_sampling=None` is the MPPI
+    baseline of the reference's demo/pendulum_example.py, `params_sampling=MerweScaledUTF(...)` its DISCO case."""
+
+    def __init__(self, n_envs, observation_space, action_space, hz_len, n_policies, action_samples, seeds=None, **kwargs):
+        if not 1 <= int(n_envs) <= 65535:
+            raise ValueError("n_envs = %d outside [1, 65535]" % int(n_envs))
+        self.n_envs = int(n_envs)
+        if seeds is not None and len(seeds) != self.n_envs:
+            raise ValueError("seeds has %d entries for %d environments" % (len(seeds), self.n_envs))
+        self._seeds = None if seeds is None else [int(v) for v in seeds]
+        super().__init__(observation_space, action_space, hz_len, n_policies, action_samples, **kwargs)
+        a_cov = self.a_dist.covariance_matrix
+        if not torch.equal(a_cov, torch.diag(torch.diag(a_cov))):
+            raise NotImplementedError("a batched MultiDISCO has a diagonal a_cov only (a full a_cov: lone MultiDISCO objects)")
+        M = self._tf.pts if self._tf is not None else self.n_params
+        for name, v, hi in (("n_policies", self.n_pol, 64), ("action_samples", self.n_actions, 1024),
+                            ("sigma points" if self._tf is not None else "params_samples", M, 9 if self._tf is not None else 64),
+                            ("hz_len * dim_a", self.hz_len * self.dim_a, 128)):
+            if not 1 <= int(v) <= hi:
+                raise ValueError("%s = %d outside [1, %d] for a batched MultiDISCO" % (name, int(v), hi))
+        B = self.n_envs
+        self._a_mat = self._a_mat[None].repeat(B, 1, 1, 1)
+        self._a_seq = self._a_seq[None].repeat(B, 1, 1)
+        self._a_mix = self._a_mix[None].repeat(B, 1)
+        self._batch = None
+        self._key = None
+
+    # ------------------------------------------------------------------ device plumbing
+    def _ensure_batch(self, model, params_dist=None):
+        if self._tf is not None and model.family == "particle":
+            raise NotImplementedError("a batched MultiDISCO has no sigma-point rollouts for Particle")
+        pd0 = params_dist[0] if isinstance(params_dist, (list, tuple)) else params_dist
+        cfg = self._config(model, pd0)
+        key = repr(sorted((k, np.asarray(v).tolist() if not isinstance(v, (str, bool, int, float, tuple)) else v) for k, v in cfg.items()))
+        if self._batch is not None and key == self._key:
+            return self._batch
+        carry = (self._a_mat.numpy(), self._a_seq.numpy())
+        if self._batch is not None:  # configuration changed: carry every environment's plan over
+            carry = (self._batch.get(L.DCB_A_MAT), self._batch.get(L.DCB_A_SEQ))
+            self._batch.close()
+            self._batch = None
+        own_a_mat, own_a_seq = self._a_mat, self._a_seq
+        self._a_mat, self._a_seq = own_a_mat[0], own_a_seq[0]  # (the prototype is a lone controller's context)
+        try:
+            proto = self._ensure_ctx(model, pd0)
+        finally:
+            self._a_mat, self._a_seq = own_a_mat, own_a_seq
+        try:
+            self._batch, self._key = proto.disco_batch(self.n_envs, self._seeds), key
+        finally:
+            proto.close()  # (the batch keeps its own copy)
+            self._ctx = self._ctx_key = None
+        self._batch.set(L.DCB_A_MAT, carry[0])
+        self._batch.set(L.DCB_A_SEQ, carry[1])
+        return self._batch
+
+    def __deepcopy__(self, memo):
+        new = copy.copy(self)
+        memo[id(self)] = new
+        for k, v in self.__dict__.items():
+            if k == "_batch":
+                new._batch = None if v is None else v.clone()
+            elif k in ("inst_cost_fn", "term_cost_fn", "_ctx"):
+                setattr(new, k, v)
+            else:
+                setattr(new, k, copy.deepcopy(v, memo))
+        return new
+
+    # ------------------------------------------------------------------ the plans, [B, ...]
+    @property
+    def a_mat(self):
+        return torch.from_numpy(self._batch.get(L.DCB_A_MAT)) if self._batch is not None else self._a_mat
+
+    @a_mat.setter
+    def a_mat(self, v):
+        self._a_mat = torch.as_tensor(v, dtype=torch.float).detach().clone().reshape(self.n_envs, self.n_pol, self.hz_len, self.dim_a)
+        if self._batch is not None:
+            self._batch.set(L.DCB_A_MAT, self._a_mat.numpy())
+
+    @property
+    def a_mix(self):
+        return torch.from_numpy(self._batch.get(L.DCB_A_MIX)) if self._batch is not None else self._a_mix
+
+    @property
+    def a_seq(self):
+        return torch.from_numpy(self._batch.get(L.DCB_A_SEQ)) if self._batch is not None else self._a_seq
+
+    @a_seq.setter
+    def a_seq(self, v):
+        self._a_seq = torch.as_tensor(v, dtype=torch.float).detach().clone().reshape(self.n_envs, self.hz_len, self.dim_a)
+        if self._batch is not None:
+            self._batch.set(L.DCB_A_SEQ, self._a_seq.numpy())
+
+    # ------------------------------------------------------------------ inputs
+    def _states(self, states):
+        return torch.as_tensor(states, dtype=torch.float).reshape(self.n_envs, -1).numpy()
+
+    def _active(self, active):
+        if active is None:
+            return np.ones(self.n_envs, bool)
+        on = np.asarray(torch.as_tensor(active).numpy() if isinstance(active, torch.Tensor) else active).reshape(-1) != 0
+        if on.shape != (self.n_envs,):
+            raise ValueError("active has %d entries for %d environments" % (on.size, self.n_envs))
+        return on
+
+    def _rows(self, params_dist, on, params=None):
+        """[B, M, P]: the caller's rows, or what MultiDISCO.forward makes of `params_dist` (one distribution, or one per environment) -
+        its sigma points, or one draw per active environment in environment order"""
+        if params is not None:
+            return np.asarray(torch.as_tensor(params, dtype=torch.float).numpy(), np.float32)
+        if not self._sampling:
+            return None
+        pds = list(params_dist) if isinstance(params_dist, (list, tuple)) else [params_dist] * self.n_envs
+        if len(pds) != self.n_envs:
+            raise ValueError("%d parameter distributions for %d environments" % (len(pds), self.n_envs))
+        rows = [np.asarray(self._sample_params(pds[b])[0][0], np.float32) if on[b] else None for b in range(self.n_envs)]
+        shape = next(r for r in rows if r is not None).shape if on.any() else (self.n_params, 1)
+        return np.stack([np.zeros(shape, np.float32) if r is None else r for r in rows])
+
+    @staticmethod
+    def _strategy(strategy, ext_actions, allow_external=True):
+        if strategy not in ("argmax", "average", "external") or (strategy == "external" and (ext_actions is None or not allow_external)):
+            raise ValueError("Invalid value for strategy.")
+
+    def _steps(self, steps):
+        if not 1 <= int(steps) <= self.hz_len:
+            raise ValueError("steps = %d outside [1, hz_len = %d]" % (int(steps), self.hz_len))
+
+    # ------------------------------------------------------------------ disco.py:348-417 for every environment
+    def forward(self, states, model, params_dist=None, ext_actions=None, active=None, params=None):
+        """states [B, ds]; ext_actions [B, S, N, H, da] or None (drawn on the device) -> (costs [B, S, N], omega [B, S, N])"""
+        on = self._active(active)
+        batch = self._ensure_batch(model, params_dist)
+        acts = None if ext_actions is None else torch.as_tensor(ext_actions, dtype=torch.float).numpy()
+        batch.forward(self._states(states), acts, self._rows(params_dist, on, params), None if active is None else on)
+        return torch.from_numpy(batch.get(L.DCB_COSTS)), torch.from_numpy(batch.get(L.DCB_OMEGA))
+
+    def step(self, strategy="argmax", steps=1, ext_actions=None, active=None):
+        """-> next_actions [B, steps, da]; ext_actions [B, H, da] with "external"; the rows of inactive environments are NaN"""
+        self._strategy(strategy, ext_actions)
+        self._steps(steps)
+        on = self._active(active)
+        if self._batch is None:
+            raise RuntimeError("step() before the first forward(): no rollouts have been evaluated yet")
+        ext = None if ext_actions is None else torch.as_tensor(ext_actions, dtype=torch.float).numpy()
+        return torch.from_numpy(self._batch.step(strategy, int(steps), ext, None if active is None else on))
+
+    def tick(self, states, model, params_dist=None, strategy="argmax", steps=1, ext_actions=None, actions=None, active=None, params=None):
+        """forward + step of every active environment in ONE launch -> next_actions [B, steps, da].  actions: recorded
+        [B, S, N, H, da] (forward's ext_actions); ext_actions: step's rows [B, H, da]"""
+        self._strategy(strategy, ext_actions)
+        self._steps(steps)
+        on = self._active(active)
+        batch = self._ensure_batch(model, params_dist)
+        acts = None if actions is None else torch.as_tensor(actions, dtype=torch.float).numpy()
+        ext = None if ext_actions is None else torch.as_tensor(ext_actions, dtype=torch.float).numpy()
+        return torch.from_numpy(batch.tick(self._states(states), strategy, int(steps), acts, self._rows(params_dist, on, params), ext,
+                                           None if active is None else on))
+
+    # ------------------------------------------------------------------ simulations.py:104-130, 217-260, the use_svmpc=False branch
+    def _episode_inputs(self, model, params_dist, n_periods, strategy, plant_params, active, params):
+        self._strategy(strategy, None, allow_external=False)
+        T = int(n_periods)
+        if not 1 <= T <= 4096:
+            raise ValueError("n_periods = %d outside [1, 4096]: one launch runs one episode piece, split a longer one" % T)
+        on = self._active(active)
+        P = len(model.uncertain_params or ()) if self._sampling else 0
+        if plant_params is not None:
+            plant_params = np.asarray(torch.as_tensor(plant_params, dtype=torch.float).numpy(), np.float32)
+            if P == 0 or plant_params.shape != (self.n_envs, P):
+                raise ValueError("plant_params has shape %s, the plants read %s" % (plant_params.shape, (self.n_envs, P) if P else "none"))
+        once = False
+        if params is not None:
+            rows = np.asarray(torch.as_tensor(params, dtype=torch.float).numpy(), np.float32)
+            once = rows.ndim == 3
+        elif not self._sampling:
+            rows = None
+        elif self._tf is not None:  # the sigma points of a fixed prior serve every period
+            rows, once = self._rows(params_dist, on), True
+        else:  # T successive draws of forward(), in period order
+            rows = None
+        return T, on, plant_params, rows, once
+
+    def run_episodes(self, states, model, params_dist=None, n_periods=1, strategy="average", plant_params=None, active=None, params=None):
+        """`n_periods` closed-loop periods - forward, step(strategy), the plant's step with that action under the environment's TRUE
+        parameters `plant_params` [B, P] (None: the nominal model), without process noise - of every active environment in ONE launch.
+        Dynamics rows: `params` [T, B, M, P] (or [B, M, P] for every period), else the sigma points of `params_dist`, else T successive
+        draws as T calls of forward() make them.  -> (states [T, B, ds] after every step, actions [T, B, da], a_seq [B, H, da]); the
+        rows of inactive environments are NaN."""
+        T, on, plant_params, rows, once = self._episode_inputs(model, params_dist, n_periods, strategy, plant_params, active, params)
+        batch = self._ensure_batch(model, params_dist)
+        if rows is None and self._sampling:
+            rows = np.stack([self._rows(params_dist, on) for _ in range(T)])
+        xs, acts, a_seq = batch.episode(self._states(states), T, strategy, rows, plant_params, once, active=None if active is None else on)
+        return torch.from_numpy(xs), torch.from_numpy(acts), torch.from_numpy(a_seq)
+
+    def simulate(self, states, model, params_dist=None, n_periods=1, strategy="average", goal=None, goal_radius=None, stop_on_crash=False,
+                 plant_params=None, active=None, params=None, resume=None, warm_up=0):
+        """run_episodes() under the reference's episode rules, still ONE launch: the controller's instantaneous cost of every new state
+        is recorded and summed in fp32 into `loss`; `stop_on_crash`: a new position on an occupied cell ends the environment with loss =
+        inf, status 2; `goal` [ds] with `goal_radius` > 0: an environment within the radius ends with status 1.  This branch of the
+        reference has no warm-up: `warm_up` must be 0.  `resume`: the result of a previous call - the episode goes on from its loss,
+        status and period index.  -> DiscoSimResult(states, actions, costs [T, B], loss [B], status [B], n_run [B], a_seq) with the
+        attribute t0; rows the call did not write are NaN (n_run: -1)."""
+        if int(warm_up) != 0:
+            raise ValueError("warm_up = %d: the MultiDISCO branch of the reference's loops has no warm-up" % int(warm_up))
+        T, on, plant_params, rows, once = self._episode_inputs(model, params_dist, n_periods, strategy, plant_params, active, params)
+        if (goal is None) != (goal_radius is None):
+            raise ValueError("goal and goal_radius come together")
+        rules = dict(stop_on_crash=bool(stop_on_crash))
+        if goal is not None:
+            goal = np.asarray(torch.as_tensor(goal, dtype=torch.float).numpy(), np.float32).reshape(-1)
+            if goal.shape != (self.dim_s,) or not np.isfinite(goal).all():
+                raise ValueError("goal has shape %s: [%d] finite entries" % (goal.shape, self.dim_s))
+            if not (np.isfinite(float(goal_radius)) and float(goal_radius) > 0):
+                raise ValueError("goal_radius must be finite and > 0")
+            rules.update(goal=goal, goal_radius=float(goal_radius))
+        if stop_on_crash:
+            has_map = (model.family == "particle" and bool(model.with_obstacle)) or cost_grid_key(self.inst_cost_fn) is not None
+            if not has_map:
+                raise ValueError("stop_on_crash needs an occupancy map: Particle(with_obstacle=True) or a NavigationCost")
+        loss = status = None
+        if resume is not None:
+            rules["t0"], loss, status = int(resume.t0), resume.loss.numpy(), resume.status.numpy()
+            if loss.shape != (self.n_envs,) or status.shape != (self.n_envs,):
+                raise ValueError("resume carries %d environments, the batch has %d" % (loss.size, self.n_envs))
+        batch = self._ensure_batch(model, params_dist)
+        if rows is None and self._sampling:
+            rows = np.stack([self._rows(params_dist, on) for _ in range(T)])
+        out = batch.episode(self._states(states), T, strategy, rows, plant_params, once, rules=rules, loss=loss, status=status,
+                            active=None if active is None else on)
+        res = DiscoSimResult(*(torch.from_numpy(np.ascontiguousarray(v)) for v in out))
+        res.t0 = rules.get("t0", 0) + T
+        return res

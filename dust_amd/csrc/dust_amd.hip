@@ -42,6 +42,7 @@
 #include "amppi.hpp"
 #include "svmpc_batch.hpp"
 #include "svmpc_episode.hpp"
+#include "disco_batch.hpp"
 #include "amppi_episode.hpp"
 #include "particle_general.hpp"
 #include "rollout.hpp"
@@ -6138,6 +6139,457 @@ extern "C" int dust_svmpc_batch_simulate(dust_svmpc_batch *b, const float *state
   if (!rules) return fail(DUST_ERR_INVALID, "null rules");
   return svb_episode_call(b, states, n_periods, n_steps, params, plant_params, rules, flags, active, states_out, actions_out, pw_out, costs_out,
                           loss, status, n_run, a_seq);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// MultiDISCO over a batch of plants: forward, step or both of B controllers in one launch, and closed-loop episodes (disco_batch.hpp).
+// The batch owns a private clone of the prototype context - model, cost, map, sigma weights, stream, profile counters - and every
+// environment's device rows; per-call inputs travel as the other controller batches' do (BatchInputs).
+struct dust_disco_batch {
+  dust_ctx *c;
+  int B;
+  DevBuf<float> a_mat;            // [B][N][D]
+  DevBuf<float> a_seq, ext;       // [B][D]
+  DevBuf<float> a_mix, eta;       // [B][N]
+  DevBuf<float> costs, wts, omg;  // [B][S][N]
+  DevBuf<float> acts;             // [B][S][N][D]
+  DevBuf<float> next;             // [B][H][da]
+  DevBuf<int> alias;              // [B] (svb_begin reads it)
+  DevBuf<uint32_t> ctr;           // [B][4]
+  DevBuf<uint64_t> seeds;         // [B]
+  DevBuf<float> rec_acts, params; // staged inputs of a call
+  DevBuf<float> plant, rec;       // dust_disco_batch_episode: [B][P] true parameter rows; the records
+  BatchInputs in;
+  bool have_forward, acts_kept;
+};
+
+// the box of disco_batch.hpp: svb_check's without its a_reg = 0 and Stein-kernel conditions, plus the sigma-point corner
+static int dcb_check(const dust_ctx *c) {
+  const dust_config &g = c->cfg;
+  if (c->N < 1 || c->N > SVB_MAX_N) return fail(DUST_ERR_UNSUPPORTED, "n_policies = %d outside [1, %d]: a batched MultiDISCO keeps an environment in one workgroup", c->N, SVB_MAX_N);
+  if (c->S < 1 || c->S > SVB_MAX_S) return fail(DUST_ERR_UNSUPPORTED, "n_samples = %d outside [1, %d] for a batched MultiDISCO", c->S, SVB_MAX_S);
+  if (c->M < 1 || c->M > SVB_MAX_M) return fail(DUST_ERR_UNSUPPORTED, "n_params = %d outside [1, %d] for a batched MultiDISCO", c->M, SVB_MAX_M);
+  if (c->D > 128) return fail(DUST_ERR_UNSUPPORTED, "H*da = %d > 128 not supported by the kernels", c->D);
+  if (g.dim_p > 4) return fail(DUST_ERR_UNSUPPORTED, "dim_p = %d > 4 uncertain parameters", g.dim_p);
+  if (g.full_cov) return fail(DUST_ERR_UNSUPPORTED, "a batched MultiDISCO has a diagonal a_cov only");
+  if (particle_general(c)) return fail(DUST_ERR_UNSUPPORTED, "a batched MultiDISCO runs Particle with acceleration control and no control-channel noise");
+  if (c->nloc != c->N || comm_active(c)) return fail(DUST_ERR_UNSUPPORTED, "a batched MultiDISCO is not sharded over GPUs");
+  if (c->serve_on) return fail(DUST_ERR_UNSUPPORTED, "the context is serving (dust_svmpc_serve_stop first)");
+  if (c->mw_dev) {  // sigma-point rollouts: Pendulum, skid-steer, cart-pole, as the lone path
+    if (g.model == DUST_MODEL_PARTICLE) return fail(DUST_ERR_UNSUPPORTED, "sigma-point weights are not implemented for Particle rollouts in a batch");
+    if (c->M > 9) return fail(DUST_ERR_UNSUPPORTED, "%d sigma points > 9 (dim_p <= 4: 2 P + 1 points) for a batched MultiDISCO", c->M);
+    if (g.dim_p < 1) return fail(DUST_ERR_UNSUPPORTED, "sigma-point weights without uncertain parameters");
+    if (g.model == DUST_MODEL_SKID_STEER || g.model == DUST_MODEL_CARTPOLE) {  // launch_rollout's two refusals
+      const bool skid = g.model == DUST_MODEL_SKID_STEER;
+      const char *family = skid ? "skid-steer" : "cart-pole";
+      const bool ctrl = skid ? (c->skid.w_ctrl[0] != 0.f || c->skid.w_ctrl[1] != 0.f) : c->cart.w_ctrl[0] != 0.f;
+      if (ctrl) return fail(DUST_ERR_UNSUPPORTED, "sigma-point weights with a non-zero control weight (%s family): the reference raises (disco.py:306-309)", family);
+      if (g.a_reg != 0.0f) return fail(DUST_ERR_UNSUPPORTED, "sigma-point weights with a_reg != 0 (%s family): the reference's control cost reads actions[0] (disco.py:338-340)", family);
+    }
+  }
+  if (g.model == DUST_MODEL_PARTICLE && g.with_obstacle && !c->grid_bits)
+    return fail(DUST_ERR_STATE, "with_obstacle is set but no occupancy grid was supplied (dust_set_grid)");
+  if (skid_nav_on(c)) {  // the navigation cost family needs its map (skid_nav_args' refusal, ahead of any launch)
+    SkidNav nv;
+    TRY(skid_nav_args(c, nv));
+  }
+  return DUST_OK;
+}
+
+static void dcb_free(dust_disco_batch *b) {
+  if (!b) return;
+  if (b->c) {
+    (void)hipSetDevice(b->c->cfg.device);
+    (void)hipStreamSynchronize(b->c->stream);
+  }
+  dust_ctx *inner = b->c;
+  delete b;  // the batch's own rows first, then the context they were allocated beside
+  if (inner) dust_destroy(inner);
+}
+
+// the batch around an inner context it takes over: buffers allocated, nothing filled yet
+static int dcb_alloc(dust_ctx *inner, int n_env, dust_disco_batch **out) {
+  dust_disco_batch *b = new dust_disco_batch();
+  b->c = inner;
+  b->B = n_env;
+  *out = b;
+  const size_t B = (size_t)n_env, N = (size_t)inner->N, S = (size_t)inner->S, D = (size_t)inner->D;
+  HIP_TRY(hipSetDevice(inner->cfg.device));
+  TRY(b->a_mat.alloc(B * N * D));
+  DevBuf<float> *bd[] = {&b->a_seq, &b->ext, &b->next};
+  for (auto p : bd) TRY(p->alloc(B * D));
+  DevBuf<float> *nn[] = {&b->a_mix, &b->eta};
+  for (auto p : nn) TRY(p->alloc(B * N));
+  DevBuf<float> *sn[] = {&b->costs, &b->wts, &b->omg};
+  for (auto p : sn) TRY(p->alloc(B * S * N));
+  TRY(b->acts.alloc(B * S * N * D));
+  TRY(b->alias.alloc(B));
+  TRY(b->ctr.alloc(B * 4));
+  TRY(b->seeds.alloc(B));
+  HIP_TRY(hipMemsetAsync(b->alias, 0, B * sizeof(int), inner->stream));
+  HIP_TRY(hipMemsetAsync(b->eta, 0, B * N * sizeof(float), inner->stream));
+  return b->in.alloc(n_env);
+}
+
+extern "C" int dust_disco_batch_create(const dust_ctx *proto, int n_env, const uint64_t *seeds, dust_disco_batch **out) {
+  if (!proto || !out) return fail(DUST_ERR_INVALID, "null argument");
+  *out = nullptr;
+  TRY(dcb_check(proto));
+  TRY(batch_n_env_check(n_env, "one workgroup per environment"));
+  dust_ctx *inner = nullptr;
+  TRY(dust_clone(proto, &inner));  // (settles and waits for the prototype's stream)
+  dust_disco_batch *b = nullptr;
+  int st = dcb_alloc(inner, n_env, &b);
+  if (st == DUST_OK) {
+    const size_t B = (size_t)n_env, N = (size_t)inner->N, D = (size_t)inner->D;
+    st = spread(inner, B, b->a_mat, inner->a_mat, N * D * sizeof(float));
+    if (st == DUST_OK) st = spread(inner, B, b->a_seq, inner->a_seq, D * sizeof(float));
+    if (st == DUST_OK) st = spread(inner, B, b->a_mix, inner->a_mix, N * sizeof(float));  // (ones until a forward: disco.py:108)
+    if (st == DUST_OK) st = spread(inner, B, b->ctr, inner->ctr_dev, 4 * sizeof(uint32_t));
+    if (st == DUST_OK) st = batch_seeds_set(inner, B, seeds, b->seeds);
+  }
+  if (st != DUST_OK) {
+    dcb_free(b);
+    return st;
+  }
+  *out = b;
+  return DUST_OK;
+}
+
+extern "C" void dust_disco_batch_destroy(dust_disco_batch *b) { dcb_free(b); }
+
+extern "C" int dust_disco_batch_clone(const dust_disco_batch *src, dust_disco_batch **out) {
+  if (!src || !out) return fail(DUST_ERR_INVALID, "null argument");
+  *out = nullptr;
+  dust_ctx *inner = nullptr;
+  TRY(dust_clone(src->c, &inner));  // (waits for the source's stream)
+  dust_disco_batch *b = nullptr;
+  int st = dcb_alloc(inner, src->B, &b);
+  const size_t B = (size_t)src->B, N = (size_t)inner->N, S = (size_t)inner->S, D = (size_t)inner->D, f = sizeof(float);
+  struct {
+    void *dst;
+    const void *s;
+    size_t bytes;
+  } cp[] = {{b->a_mat, src->a_mat, B * N * D * f}, {b->a_seq, src->a_seq, B * D * f},   {b->a_mix, src->a_mix, B * N * f},
+            {b->eta, src->eta, B * N * f},         {b->costs, src->costs, B * S * N * f}, {b->omg, src->omg, B * S * N * f},
+            {b->wts, src->wts, B * S * N * f},     {b->ctr, src->ctr, B * 4 * sizeof(uint32_t)}, {b->seeds, src->seeds, B * sizeof(uint64_t)}};
+  for (auto &e : cp)
+    if (st == DUST_OK) st = d2d(inner, e.dst, e.s, e.bytes);
+  if (st == DUST_OK && src->acts_kept) st = d2d(inner, b->acts, src->acts, B * S * N * D * f);
+  if (st == DUST_OK) {
+    b->have_forward = src->have_forward;
+    b->acts_kept = src->acts_kept;
+  }
+  if (st == DUST_OK && hipStreamSynchronize(inner->stream) != hipSuccess) st = fail(DUST_ERR_HIP, "hipStreamSynchronize failed");
+  if (st != DUST_OK) {
+    dcb_free(b);
+    return st;
+  }
+  *out = b;
+  return DUST_OK;
+}
+
+extern "C" int dust_disco_batch_ctx(dust_disco_batch *b, dust_ctx **out) {
+  if (!b || !out) return fail(DUST_ERR_INVALID, "null argument");
+  *out = b->c;
+  return DUST_OK;
+}
+
+extern "C" int dust_disco_batch_set(dust_disco_batch *b, int what, const float *in) {
+  if (!b || !in) return fail(DUST_ERR_INVALID, "null argument");
+  dust_ctx *c = b->c;
+  const size_t B = (size_t)b->B, D = (size_t)c->D, ND = (size_t)c->N * D;
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  switch (what) {
+    case DUST_DCB_A_MAT: return h2d(c, b->a_mat, in, B * ND * sizeof(float));
+    case DUST_DCB_A_SEQ: return h2d(c, b->a_seq, in, B * D * sizeof(float));
+    default: return fail(DUST_ERR_INVALID, "dust_disco_batch_set: %d is not a settable quantity", what);
+  }
+}
+
+extern "C" int dust_disco_batch_get(dust_disco_batch *b, int what, float *out) {
+  if (!b || !out) return fail(DUST_ERR_INVALID, "null argument");
+  dust_ctx *c = b->c;
+  const size_t B = (size_t)b->B, N = (size_t)c->N, S = (size_t)c->S, D = (size_t)c->D, f = sizeof(float);
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  if ((what == DUST_DCB_COSTS || what == DUST_DCB_OMEGA || what == DUST_DCB_ACTIONS) && !b->have_forward)
+    return fail(DUST_ERR_STATE, "no forward of the batch has run yet: there is no such record");
+  switch (what) {
+    case DUST_DCB_A_MAT: return d2h(c, out, b->a_mat, B * N * D * f);
+    case DUST_DCB_A_SEQ: return d2h(c, out, b->a_seq, B * D * f);
+    case DUST_DCB_A_MIX: return d2h(c, out, b->a_mix, B * N * f);
+    case DUST_DCB_COSTS: return d2h(c, out, b->costs, B * S * N * f);
+    case DUST_DCB_OMEGA: return d2h(c, out, b->omg, B * S * N * f);
+    case DUST_DCB_ACTIONS:
+      if (!b->acts_kept) return fail(DUST_ERR_STATE, "the last forward did not keep its actions (DUST_SVMPC_BATCH_KEEP_ACTIONS)");
+      return d2h(c, out, b->acts, B * S * N * D * f);
+    default: return fail(DUST_ERR_INVALID, "dust_disco_batch_get: %d is not a quantity of the batch", what);
+  }
+}
+
+// What a call of the batch refuses, ahead of any copy or launch
+static int dcb_call_check(const dust_disco_batch *b, bool forward, const float *states, const float *params, int flags, int allowed_flags, bool step,
+                          int strategy, int steps, const float *ext, const float *next, bool episode) {
+  if (!b) return fail(DUST_ERR_INVALID, "null batch");
+  const dust_ctx *c = b->c;
+  if (forward) {
+    if (!states) return fail(DUST_ERR_INVALID, "null argument");
+    if (flags & ~allowed_flags) return fail(DUST_ERR_UNSUPPORTED, "flags = %d: a flag this call of the batched MultiDISCO does not have", flags);
+    if (c->cfg.dim_p > 0 && !params) return fail(DUST_ERR_INVALID, "params_sampling is on: pass the parameter rows");
+    if (c->cfg.dim_p == 0 && params) return fail(DUST_ERR_INVALID, "parameter rows without uncertain parameters (dim_p = 0)");
+  }
+  if (step) {
+    if (!episode && !next) return fail(DUST_ERR_INVALID, "null argument");
+    if (strategy < 0 || strategy > 2 || (strategy == DUST_STEP_EXTERNAL && (!ext || episode))) return fail(DUST_ERR_INVALID, "Invalid value for strategy.");
+    if (steps < 1 || steps > c->H) return fail(DUST_ERR_INVALID, "steps = %d outside [1, H = %d]", steps, c->H);
+  }
+  return dcb_check(c);
+}
+
+// the kernel's arguments for the inputs a call has staged
+static void dcb_args(const dust_disco_batch *b, const float *acts_dev, const float *params_dev, const unsigned char *active, int flags, bool forward,
+                     bool step, int strategy, int steps, bool ext, DiscoBatchArgs &d) {
+  const dust_ctx *c = b->c;
+  memset(&d, 0, sizeof d);
+  SvmpcBatchArgs &k = d.k;
+  k.dm = make_dev_model(c);
+  k.sk = c->skid;
+  k.cp = c->cart;
+  k.N = c->N;
+  k.S = c->S;
+  k.M = c->M;
+  k.H = c->H;
+  k.da = c->da;
+  k.D = c->D;
+  k.P = c->cfg.dim_p;
+  k.n_steps = 1;
+  k.philox = acts_dev ? 0 : 1;
+  k.G = c->mw_dev ? 1 : svb_groups(c->N * c->S, c->M);
+  k.Q = c->N * c->D >= SVB_THREADS ? 1 : std::max(1, std::min(SVB_THREADS / (c->N * c->D), c->S));
+  k.dt = (float)c->cfg.dt;
+  k.temp = c->cfg.temperature;
+  for (int e = 0; e < 2; ++e) {
+    const int dd = e < c->da ? e : 0;  // (dim_a = 1: entry 1 repeats entry 0, no kernel reads it)
+    k.chol_a[e] = c->cfg.chol_a[dd];
+    d.a_pre[e] = c->cfg.a_pre[dd];
+    d.min_a[e] = c->cfg.min_a[dd];
+    d.max_a[e] = c->cfg.max_a[dd];
+  }
+  k.states = b->in.states_dev();
+  k.seeds = b->seeds;
+  k.active = b->in.mask_dev(active);
+  k.eps = acts_dev;
+  k.params = params_dev;
+  k.a_mat = b->a_mat;
+  k.alias = b->alias;
+  k.ctr = b->ctr;
+  k.acts = b->acts;
+  k.costs = b->costs;
+  k.wts = b->wts;
+  k.omg = b->omg;
+  k.eta = b->eta;
+  k.a_mix = b->a_mix;
+  d.a_reg = c->cfg.a_reg;
+  d.do_forward = forward ? 1 : 0;
+  d.do_step = step ? 1 : 0;
+  d.around_a_mat = (flags & DUST_EPS_AROUND_A_MAT) ? 1 : 0;
+  d.strategy = strategy;
+  d.steps = steps;
+  d.a_seq = b->a_seq;
+  d.ext = ext ? b->ext.get() : nullptr;
+  d.mw = c->mw_dev;
+  d.next = b->next;
+}
+
+// States and mask through the next pinned slot and the ONE launch; nothing waits for the device.  ep: the launch runs ep->ep.T periods
+// (ep->d is filled here)
+static int dcb_go(dust_disco_batch *b, const float *states, const unsigned char *active, const DiscoBatchArgs &d, DiscoEpisodeArgs *ep) {
+  dust_ctx *c = b->c;
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  TRY(b->in.stage(c, states, active));
+  const bool nav = skid_nav_on(c), sigma = c->mw_dev != nullptr;
+  SkidNav nv;
+  memset(&nv, 0, sizeof nv);
+  if (nav) TRY(skid_nav_args(c, nv));
+  const size_t lds = svmpc_batch_lds_bytes(c->N, c->D, c->M) + (size_t)nv.grid_words * sizeof(uint32_t);  // the map behind the tick's own LDS
+  Prof pr(c, DUST_K_ROLLOUT);
+  auto go = [&](auto kernel, const auto &args) -> int {
+    HIP_TRY(launch_on(c->stream, false, kernel, b->B, SVB_THREADS, lds, args));  // (the batches are never captured)
+    return DUST_OK;
+  };
+  // the sigma-point instances exist for Pendulum, skid-steer and cart-pole (dcb_check has refused Particle)
+  auto by_sigma_model = [&](auto f) -> int {
+    if (!sigma) return by_model(c, [&](auto M) { return f(M, std::false_type()); });
+    return pick_int<DUST_MODEL_PENDULUM, DUST_MODEL_SKID_STEER, DUST_MODEL_CARTPOLE>(c->cfg.model, [&](auto M) { return f(M, std::true_type()); });
+  };
+  if (ep) {
+    ep->d = d;
+    if (nav) {
+      DiscoNavEpisodeArgs kn;
+      kn.e = *ep;
+      kn.nav = nv;
+      TRY(pick_bool(sigma, [&](auto sg) { return go(&disco_skid_nav_episode_kernel<decltype(sg)::value>, kn); }));
+    } else {
+      TRY(by_sigma_model([&](auto M, auto sg) { return go(&disco_episode_kernel<decltype(M)::value, decltype(sg)::value>, *ep); }));
+    }
+  } else if (nav) {
+    DiscoNavBatchArgs kn;
+    kn.d = d;
+    kn.nav = nv;
+    TRY(pick_bool(sigma, [&](auto sg) { return go(&disco_skid_nav_batch_kernel<decltype(sg)::value>, kn); }));
+  } else {
+    TRY(by_sigma_model([&](auto M, auto sg) { return go(&disco_batch_kernel<decltype(M)::value, decltype(sg)::value>, d); }));
+  }
+  return DUST_OK;
+}
+
+// forward (states .. flags), step (strategy .. next) or both: every check, the staging of the inputs, the ONE launch, the outputs
+static int dcb_launch(dust_disco_batch *b, bool forward, const float *states, const float *actions, const float *params, int flags, bool step,
+                      int strategy, int steps, const float *ext, const unsigned char *active, float *next) {
+  TRY(dcb_call_check(b, forward, states, params, flags, DUST_EPS_AROUND_A_MAT | DUST_SVMPC_BATCH_KEEP_ACTIONS, step, strategy, steps, ext, next, false));
+  dust_ctx *c = b->c;
+  const size_t B = (size_t)b->B, N = (size_t)c->N, S = (size_t)c->S, D = (size_t)c->D, M = (size_t)c->M, P = (size_t)c->cfg.dim_p;
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  const bool use_ext = step && strategy == DUST_STEP_EXTERNAL;
+  if (forward && actions) {
+    TRY(b->rec_acts.ensure(B * S * N * D));
+    TRY(h2d(c, b->rec_acts, actions, B * S * N * D * sizeof(float)));
+  }
+  if (forward && params) {
+    TRY(b->params.ensure(B * M * P));
+    TRY(h2d(c, b->params, params, B * M * P * sizeof(float)));
+  }
+  if (use_ext) TRY(h2d(c, b->ext, ext, B * D * sizeof(float)));
+  DiscoBatchArgs d;
+  dcb_args(b, (forward && actions) ? b->rec_acts.get() : nullptr, (forward && params) ? b->params.get() : nullptr, active, flags, forward, step, strategy,
+           steps, use_ext, d);
+  TRY(dcb_go(b, forward ? states : nullptr, active, d, nullptr));
+  if (forward) {
+    b->have_forward = true;
+    b->acts_kept = (flags & DUST_SVMPC_BATCH_KEEP_ACTIONS) != 0;
+  }
+  if (step) {
+    TRY(rows_d2h(b->B, c->stream, next, b->next, (size_t)steps * c->da, active));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  return DUST_OK;
+}
+
+extern "C" int dust_disco_batch_forward(dust_disco_batch *b, const float *states, const float *actions, const float *params, int flags,
+                                        const unsigned char *active) {
+  return dcb_launch(b, true, states, actions, params, flags, false, 0, 1, nullptr, active, nullptr);
+}
+
+extern "C" int dust_disco_batch_step(dust_disco_batch *b, int strategy, int steps, const float *ext, const unsigned char *active, float *next) {
+  return dcb_launch(b, false, nullptr, nullptr, nullptr, 0, true, strategy, steps, ext, active, next);
+}
+
+extern "C" int dust_disco_batch_tick(dust_disco_batch *b, const float *states, const float *actions, const float *params, int flags,
+                                     const unsigned char *active, int strategy, int steps, const float *ext, float *next) {
+  return dcb_launch(b, true, states, actions, params, flags, true, strategy, steps, ext, active, next);
+}
+
+// T closed-loop periods (forward, step(strategy, 1), plant step, records) of every active environment in ONE launch; rules: the
+// reference's episode rules (disco_episode_body), or NULL (every environment runs its T periods)
+extern "C" int dust_disco_batch_episode(dust_disco_batch *b, const float *states, int n_periods, const float *params, const float *plant_params,
+                                        int strategy, const dust_episode_rules *rules, int flags, const unsigned char *active, float *states_out,
+                                        float *actions_out, float *costs_out, float *loss, int *status, int *n_run, float *a_seq) {
+  if (!b) return fail(DUST_ERR_INVALID, "null batch");
+  if (!states || !states_out || !actions_out) return fail(DUST_ERR_INVALID, "null argument");
+  if (n_periods < 1 || n_periods > 4096)
+    return fail(DUST_ERR_INVALID, "n_periods = %d outside [1, 4096] (one launch stays short on a shared device: split a longer episode)", n_periods);
+  dust_ctx *c = b->c;
+  TRY(dcb_call_check(b, true, states, params, flags, DUST_DISCO_PARAMS_ONCE, true, strategy, 1, nullptr, nullptr, true));
+  if (c->cfg.dim_p == 0 && plant_params) return fail(DUST_ERR_INVALID, "plant parameter rows without uncertain parameters (dim_p = 0)");
+  const size_t T = (size_t)n_periods, B = (size_t)b->B, M = (size_t)c->M, P = (size_t)c->cfg.dim_p;
+  const size_t ds = (size_t)c->ds, da = (size_t)c->da, D = (size_t)c->D;
+  const bool once = (flags & DUST_DISCO_PARAMS_ONCE) != 0;
+  if (rules) {
+    if (!costs_out || !loss || !status || !n_run) return fail(DUST_ERR_INVALID, "null argument");
+    if (rules->warm_up != 0) return fail(DUST_ERR_INVALID, "warm_up = %d: the MultiDISCO branch of the reference's loops has no warm-up", rules->warm_up);
+    if (rules->t0 < 0) return fail(DUST_ERR_INVALID, "t0 = %d: >= 0", rules->t0);
+    if (rules->t0 > 0x7fffffff - 4096) return fail(DUST_ERR_INVALID, "t0 = %d: the episode's period index does not fit", rules->t0);
+    bool finite = std::isfinite(rules->goal_radius);
+    for (size_t k = 0; k < ds; ++k) finite = finite && std::isfinite(rules->goal[k]);
+    if (!finite) return fail(DUST_ERR_INVALID, "the goal and its radius must be finite");
+    for (size_t e = 0; e < B; ++e)
+      if ((!active || active[e]) && (status[e] < 0 || status[e] > 2))
+        return fail(DUST_ERR_INVALID, "status[%zu] = %d: 0 (running), 1 (goal) or 2 (crash)", e, status[e]);
+    const bool have_map = (c->cfg.model == DUST_MODEL_PARTICLE && c->cfg.with_obstacle && c->grid_bits) || skid_nav_on(c);
+    if (rules->stop_on_crash && !have_map)
+      return fail(DUST_ERR_UNSUPPORTED, "stop_on_crash needs an occupancy map: Particle with_obstacle, or the skid-steer navigation cost");
+  }
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  if (params) {
+    const size_t n = (once ? 1 : T) * B * M * P;
+    TRY(b->params.ensure(n));
+    TRY(h2d(c, b->params, params, n * sizeof(float)));
+  }
+  if (plant_params) {
+    TRY(b->plant.ensure(B * P));
+    TRY(h2d(c, b->plant, plant_params, B * P * sizeof(float)));
+  }
+  // the records, then (rules) the cost rows and the words [B] loss, [B] status, [B] n_run
+  const size_t n_cost = rules ? T * B : 0, words = T * B * (ds + da) + n_cost, n_rec = words + (rules ? 3 * B : 0);
+  TRY(b->rec.ensure(n_rec));
+  DiscoEpisodeArgs ke;
+  memset(&ke, 0, sizeof ke);
+  ke.ep.T = n_periods;
+  ke.ep.plant = plant_params ? b->plant.get() : nullptr;
+  ke.ep.states_out = b->rec;
+  ke.ep.actions_out = ke.ep.states_out + T * B * ds;
+  ke.ep.pw_out = nullptr;
+  ke.has_rules = rules ? 1 : 0;
+  ke.params_once = once ? 1 : 0;
+  if (rules) {
+    SvbRules &ru = ke.ru;
+    // (t0 and warm_up stay 0 in SvbRules: disco_episode_body reads neither - without a warm-up no period depends on its index)
+    ru.stop_on_crash = rules->stop_on_crash ? 1 : 0;
+    ru.goal_on = rules->goal_radius > 0.f ? 1 : 0;
+    ru.r2 = (float)((double)rules->goal_radius * (double)rules->goal_radius);
+    for (int k = 0; k < 8; ++k) ru.goal[k] = (size_t)k < ds ? rules->goal[k] : 0.f;
+    ru.costs_out = ke.ep.actions_out + T * B * da;
+    ru.loss = b->rec + words;
+    ru.status = reinterpret_cast<int *>(ru.loss + B);
+    ru.n_run = ru.status + B;
+    std::vector<float> in(3 * B, 0.f);  // (n_run starts at 0: an environment that enters stopped has run no period)
+    memcpy(in.data(), loss, B * sizeof(float));
+    memcpy(in.data() + B, status, B * sizeof(int));
+    TRY(h2d(c, ru.loss, in.data(), 3 * B * sizeof(float)));
+  }
+  DiscoBatchArgs d;
+  dcb_args(b, nullptr, params ? b->params.get() : nullptr, active, 0, true, true, strategy, 1, false, d);
+  d.next = nullptr;
+  TRY(dcb_go(b, states, active, d, &ke));
+  b->have_forward = true;
+  b->acts_kept = false;
+  // the records come back once; the rows of inactive environments stay out of the caller's arrays
+  std::vector<float> host(n_rec), seq(a_seq ? B * D : 0);
+  HIP_TRY(hipMemcpyAsync(host.data(), b->rec, n_rec * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (a_seq) HIP_TRY(hipMemcpyAsync(seq.data(), b->a_seq, B * D * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const int *ran = rules ? reinterpret_cast<const int *>(host.data() + words + 2 * B) : nullptr;
+  // rows [0, n_run[e]) of an active environment's record (no rules: all T of them)
+  auto rows = [&](float *dst, const float *src, size_t row) {
+    for (size_t e = 0; e < B; ++e) {
+      if (active && !active[e]) continue;
+      for (size_t t = 0; t < (ran ? (size_t)ran[e] : T); ++t) memcpy(dst + (t * B + e) * row, src + (t * B + e) * row, row * sizeof(float));
+    }
+  };
+  rows(states_out, host.data(), ds);
+  rows(actions_out, host.data() + T * B * ds, da);
+  if (rules) rows(costs_out, host.data() + T * B * (ds + da), 1);
+  for (size_t e = 0; e < B; ++e) {
+    if (active && !active[e]) continue;
+    if (rules) {
+      n_run[e] = ran[e];
+      if (ran[e] == 0) continue;  // (entered with status != 0: nothing of it was written)
+      memcpy(loss + e, host.data() + words + e, sizeof(float));
+      memcpy(status + e, host.data() + words + B + e, sizeof(int));
+    }
+    if (a_seq) memcpy(a_seq + e * D, seq.data() + e * D, D * sizeof(float));
+  }
+  return DUST_OK;
 }
 
 #include "mpf.hpp"

@@ -145,7 +145,8 @@ def run_particle_episode(init_state, model, dyn_dist, controller, use_svmpc=True
 
 
 def run_pendulum_simulations(init_state, init_policies, model_kwargs, experiment_params, controller, svmpc_kwargs, lik_kwargs, mpf, mpf_bw=None,
-                             mpf_steps=20, episodes=3, steps=200, warm_up=1, seed=0, init_particles=None, frame=False):
+                             mpf_steps=20, episodes=3, steps=200, warm_up=1, seed=0, init_particles=None, frame=False, *, use_svmpc=True,
+                             dyn_dist=None, use_exact_model=False):
     """The batched twin of `run_pendulum_simulation(use_svmpc=True, mpf=...)`: the `episodes` become the B environments of one
     `BatchSVMPC` plus `BatchDualSVMPC`, environment i's plant runs under `experiment_params[i]`, and the whole loop - warm-up periods
     that only optimize and apply a zero action while the filters keep updating, the cost of every new state - runs on the device, one
@@ -163,9 +164,20 @@ def run_pendulum_simulations(init_state, init_policies, model_kwargs, experiment
     `Timestep`, `Iteration`, `DynBandwidths`, `Weights` [B, steps, N] (NaN while warming up), `ExpParams` [B, steps, P], `AvgCumCost`,
     and - the episode is not interrupted to read them - `DynParticles` [B, Mp, P] and `PolParticles` [B, N]: the FINAL filter particles
     (the last pair folded in) and the final particles' first actions, not one row per period.  frame=True: the reference's pandas
-    frame of the per-period columns, when pandas imports (it is optional here); otherwise the dict."""
+    frame of the per-period columns, when pandas imports (it is optional here); otherwise the dict.
+
+    use_svmpc=False (keyword only): the `use_svmpc=False` branch of the lone driver (simulations.py:124-126) - the MPPI-baseline and DISCO
+    cases of demo/pendulum_example.py - as one `BatchDISCO.simulate` per piece: `controller` is a `BatchDISCO` of `episodes` environments
+    (params_sampling=None: the baseline; a MerweScaledUTF: DISCO, whose sigma points are `dyn_dist`'s, fixed over the episode), every
+    period forward + step("average"); `svmpc_kwargs`, `lik_kwargs` and `mpf` are not read and may be None, and there is no warm-up.
+    use_exact_model=True (the demo's baseline): every environment's rollouts run under ITS true row - the controller then has
+    params_sampling=True with params_samples=1, and the row it "samples" is the truth.  The
+    dict then has no `DynParticles` / `DynBandwidths` / `Weights`, and `PolParticles` are the final plans' first actions."""
     import numpy as np
 
+    if not use_svmpc:
+        return _run_pendulum_baselines(init_state, init_policies, model_kwargs, experiment_params, controller, dyn_dist, int(episodes), int(steps), frame,
+                                       bool(use_exact_model))
     from ..controllers.dual import BatchDualSVMPC
     from ..inference.svmpc import BatchSVMPC
 
@@ -209,6 +221,86 @@ def run_pendulum_simulations(init_state, init_policies, model_kwargs, experiment
     return data
 
 
+def _run_pendulum_baselines(init_state, init_policies, model_kwargs, experiment_params, controller, dyn_dist, B, steps, frame, exact):
+    """run_pendulum_simulations(use_svmpc=False): the episodes as the environments of a `BatchDISCO`"""
+    import numpy as np
+
+    from ..controllers.disco import BatchDISCO
+
+    if not isinstance(controller, BatchDISCO) or controller.n_envs != B:
+        raise ValueError("use_svmpc=False runs the episodes as the environments of one BatchDISCO: pass one of %d environments" % B)
+    if len(experiment_params) < B:
+        raise ValueError("experiment_params has %d entries for %d episodes" % (len(experiment_params), B))
+    model = PendulumModel(**model_kwargs)
+    sampled = bool(controller._sampling)
+    names = tuple(model.uncertain_params or ()) if sampled else ()
+    sim_ctrl = deepcopy(controller)
+    init = torch.as_tensor(init_policies, dtype=torch.float).detach().clone()
+    sim_ctrl.a_mat = init if init.ndim == 4 else init[None].repeat(B, 1, 1, 1)
+    true = torch.tensor([[float(experiment_params[i].get(k, model.params_dict[k])) for k in names] for i in range(B)], dtype=torch.float).reshape(B, len(names))
+    rows = None if not names else (true.log() if bool(sim_ctrl._params_log_space) else true)
+    known = None
+    if exact:
+        if rows is None or sim_ctrl._tf is not None or sim_ctrl.n_params != 1:
+            raise ValueError("use_exact_model=True hands every environment its true row: a BatchDISCO with params_sampling=True, "
+                             "params_samples=1 over a model with uncertain_params")
+        known = rows[:, None, :]  # [B, 1, P]: serves every period
+    state = torch.as_tensor(init_state, dtype=torch.float).reshape(1, -1).repeat(B, 1)
+    out, res = [], None
+    for lo in range(0, steps, 4096):
+        res = sim_ctrl.simulate(state, model, dyn_dist, min(4096, steps - lo), "average", plant_params=rows, resume=res, params=known)
+        out.append(res)
+        state = res.states[-1]
+    cat = lambda k: torch.cat([getattr(r, k) for r in out]).transpose(0, 1).numpy()  # [B, steps, ...]
+    xs, cost = cat("states"), cat("costs")
+    t = np.broadcast_to(np.arange(steps), (B, steps))
+    data = {"Cost": cost, "Position": xs[..., 0], "Speed": xs[..., 1], "Actions": cat("actions")[..., 0], "Timestep": t.copy(),
+            "Iteration": np.broadcast_to(np.arange(B)[:, None], (B, steps)).copy(), "PolParticles": sim_ctrl.a_mat[:, :, 0, 0].numpy(),
+            "ExpParams": np.broadcast_to(true.numpy()[:, None], (B, steps, len(names))).copy(),
+            "AvgCumCost": np.round(np.cumsum(cost.astype(np.float64), 1) / (t + 1), 2)}
+    if frame:
+        try:
+            import pandas as pd
+        except ImportError:
+            return data
+        per = ("Cost", "Position", "Speed", "Actions", "Timestep", "Iteration", "AvgCumCost")
+        cols = {k: data[k].reshape(-1) for k in per}
+        cols["ExpParams"] = data["ExpParams"].reshape(B * steps, -1).tolist()
+        return pd.DataFrame(index=list(t.reshape(-1)), data=cols)
+    return data
+
+
+def _run_particle_baselines(init_states, model, dyn_dist, ctrl, load, steps, plant_params):
+    """run_particle_episodes with a `BatchDISCO`: run_particle_episode's use_svmpc=False branch, step("argmax"), no warm-up"""
+    import numpy as np
+
+    B = ctrl.n_envs
+    state = torch.as_tensor(init_states, dtype=torch.float).reshape(B, -1).clone()
+    rows = None if plant_params is None else torch.as_tensor(plant_params, dtype=torch.float).reshape(B, -1).clone()
+    loaded = rows
+    if load != 0:
+        names = tuple(model.uncertain_params or ()) if ctrl._sampling else ()
+        if "mass" not in names:
+            raise ValueError("load != 0 changes the plants' mass: 'mass' must be one of the model's uncertain parameters")
+        log_space = bool(ctrl._params_log_space)
+        if rows is None:
+            nominal = torch.tensor([float(model.params_dict[k]) for k in names])
+            rows = (nominal.log() if log_space else nominal).repeat(B, 1)
+        j = names.index("mass")
+        loaded = rows.clone()
+        loaded[:, j] = (rows[:, j].exp() + load).log() if log_space else rows[:, j] + load
+    cuts = sorted({0, steps} | ({min(steps // 4, steps)} if load != 0 else set()) | set(range(0, steps, 4096)))
+    res = None
+    for lo, hi in zip(cuts[:-1], cuts[1:]):
+        plant = loaded if (load != 0 and lo >= steps // 4) else rows
+        res = ctrl.simulate(state, model, dyn_dist, hi - lo, "argmax", goal=model.target, goal_radius=1.0, stop_on_crash=bool(model.with_obstacle),
+                            plant_params=plant, resume=res)
+        n = res.n_run.numpy()
+        for b in np.nonzero(n > 0)[0]:
+            state[b] = res.states[n[b] - 1, b]
+    return res.loss if res is not None else torch.zeros(B)
+
+
 def run_particle_episodes(init_states, model, dyn_dist, batch_svmpc, warm_up=30, load=0, steps=400, plant_params=None, mpf=None, mpf_bw=None,
                           mpf_steps=20):
     """The batched twin of `run_particle_episode`: environment b of `batch_svmpc` (a `BatchSVMPC` over `model`) runs that episode from
@@ -219,9 +311,17 @@ def run_particle_episodes(init_states, model, dyn_dist, batch_svmpc, warm_up=30,
     `mpf` (a filter prototype, as run_particle_episode's): the episode is the DuSt-MPC loop - every environment a copy of the filter,
     updated after every plant step, the warm-up periods included, and stopped with its environment - on `BatchDualSVMPC.simulate`;
     the dynamics samples then come from the filters (`dyn_dist` is not read).  The `load` split stays two calls.
+    `batch_svmpc` may be a `BatchDISCO` instead: the episode is run_particle_episode's `use_svmpc=False` branch - every period forward +
+    step("argmax"), no warm-up (`warm_up` is not read), no filter (`mpf` must be None) - on `BatchDISCO.simulate`.
     -> losses [B]: the cumulated cost of every environment, inf after a crash."""
     import numpy as np
 
+    from ..controllers.disco import BatchDISCO
+
+    if isinstance(batch_svmpc, BatchDISCO):
+        if mpf is not None:
+            raise ValueError("a BatchDISCO episode has no dynamics filter: mpf must be None")
+        return _run_particle_baselines(init_states, model, dyn_dist, batch_svmpc, load, int(steps), plant_params)
     ctrl = batch_svmpc.likelihood.controller
     B = batch_svmpc.n_envs
     state = torch.as_tensor(init_states, dtype=torch.float).reshape(B, -1).clone()

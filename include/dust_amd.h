@@ -564,6 +564,69 @@ int dust_svmpc_batch_simulate(dust_svmpc_batch *batch, const float *states, int 
                               float *states_out, float *actions_out, float *pw_out, float *costs_out /* [T][B] */,
                               float *loss /* [B] in-out */, int *status /* [B] in-out */, int *n_run /* [B] out */, float *a_seq);
 
+/* ---- MultiDISCO over a batch of plants (ABI 3): B independent controllers - the MPPI baseline of the reference's demo/pendulum_example.py,
+ * disco.py:139-417 - whose forward(), step() or both are ONE kernel launch (csrc/disco_batch.hpp), counted under DUST_K_ROLLOUT, the slot
+ * of the lone dust_disco_forward's launch.  Per environment: a state, a_mat [N][H][da], a_seq [H][da], a_mix [N] (ones until a forward),
+ * a Philox stream (key seeds[b]; NULL: the prototype's seed + b) and parameter rows; model, cost, map, N, S, M, H, temperature,
+ * ctrl_penalty and a_cov are the prototype's.  Environment b's device-drawn actions are, bit for bit, those of a lone context created
+ * with seed seeds[b] after the same calls, and an environment computes the same bits alone, in any slot of any batch and beside
+ * inactive neighbours.
+ * The box (dust_disco_batch_create: DUST_ERR_UNSUPPORTED before anything is allocated): dust_svmpc_batch_create's without its a_reg = 0 and
+ * Stein-kernel conditions - N <= 64, S <= 1024, M <= 64, H da <= 128, dim_p <= 4, a diagonal a_cov, Particle with acceleration control
+ * and no control-channel noise, one GPU.  Sigma-point rollouts (a prototype with dust_set_param_weights: the "DISCO" case) run on Pendulum,
+ * skid-steer - with and without the navigation cost - and cart-pole, as dust_disco_forward runs them: the M rows of `params` are then the
+ * pts = M <= 9 sigma points and a rollout's cost is the weighted sum of disco.py:312-323, not the mean.  Refused under sigma weights:
+ * Particle, more than 9 points, no uncertain parameter, and - skid-steer and cart-pole - a non-zero control weight or a_reg != 0
+ * (ctrl_penalty != 1), the two cases dust_disco_forward refuses.
+ *   forward   states [B][ds]; actions [B][S][N][H][da] recorded (host) or NULL (drawn: a_mat + chol_a z); params [B][M][P] - every
+ *             environment's sampled rows, or its sigma points [B][pts][P] under sigma weights -, or NULL exactly when the prototype has no
+ *             uncertain parameters; flags: DUST_EPS_AROUND_A_MAT (recorded actions: eps = a - a_mat[n],
+ *             not a - a_seq, as dust_disco_forward reads it) and DUST_SVMPC_BATCH_KEEP_ACTIONS (the ACTIONS getter serves this call's
+ *             actions); every other flag DUST_ERR_UNSUPPORTED.  Updates a_mat, a_mix and the records COSTS / OMEGA.
+ *   step      strategy: dust_step_strategy (DUST_STEP_EXTERNAL reads ext_actions [B][H][da]); steps in [1, H]; next_actions
+ *             [B][steps][da] receives the rows of active environments.  "argmax" is the FIRST maximum of a_mix and clamps that row of
+ *             a_mat in place, as dust_disco_step does.
+ *   tick      forward then step in ONE launch.
+ *   episode   n_periods (1 .. 4096) closed-loop periods in ONE launch: forward (drawn noise), step(strategy, 1), the plant's step under
+ *             plant_params [B][P] (NULL: the nominal model), the records states_out [T][B][ds], actions_out [T][B][da].  params
+ *             [T][B][M][P], or [B][M][P] serving every period with DUST_DISCO_PARAMS_ONCE (the only flag).  rules NULL: every active
+ *             environment runs its T periods, costs_out / loss / status / n_run are not touched (may be NULL).  Otherwise the rules of
+ *             dust_svmpc_batch_simulate - cost, fp32 running loss, crash, goal, chaining through t0 and the in-out loss / status, rows past
+ *             n_run[b] not written - with warm_up = 0: this branch of the reference has no warm-up (anything else DUST_ERR_INVALID).
+ *             t0 is checked as dust_svmpc_batch_simulate checks it and otherwise unused: without a warm-up no period depends on its
+ *             index, and two calls chain through loss and status alone.
+ *             DUST_STEP_EXTERNAL is refused.  a_seq [B][H][da] (may be NULL): every environment's sequence after its last period.
+ * `active` [B] (NULL: everybody): an inactive environment runs nothing, none of its rows or output rows is written.
+ * Refused before anything is staged or launched, in-out arrays untouched - DUST_ERR_INVALID: NULL arguments, a strategy outside 0 .. 2 or
+ * "external" without rows, steps outside [1, H], params given without uncertain parameters or missing with them, what
+ * dust_svmpc_batch_simulate refuses of rules; DUST_ERR_UNSUPPORTED: a flag not named above, stop_on_crash without a map; DUST_ERR_STATE: the
+ * navigation cost family without its map. */
+typedef struct dust_disco_batch dust_disco_batch;
+enum dust_disco_batch_quantity {
+  DUST_DCB_A_MAT = 0,  /* [B][N][H][da] set / get */
+  DUST_DCB_A_SEQ = 1,  /* [B][H][da] set / get */
+  DUST_DCB_A_MIX = 2,  /* [B][N] */
+  DUST_DCB_COSTS = 3,  /* [B][S][N], of the last forward */
+  DUST_DCB_OMEGA = 4,  /* [B][S][N] */
+  DUST_DCB_ACTIONS = 5 /* [B][S][N][H][da], kept only when the call carried DUST_SVMPC_BATCH_KEEP_ACTIONS */
+};
+enum { DUST_DISCO_PARAMS_ONCE = 128 }; /* dust_disco_batch_episode: params is [B][M][P] and serves every period */
+int dust_disco_batch_create(const dust_ctx *proto, int n_env, const uint64_t *seeds, dust_disco_batch **out);
+void dust_disco_batch_destroy(dust_disco_batch *batch);
+int dust_disco_batch_clone(const dust_disco_batch *batch, dust_disco_batch **out);
+int dust_disco_batch_ctx(dust_disco_batch *batch, dust_ctx **ctx); /* borrowed: sync, profile counters */
+int dust_disco_batch_set(dust_disco_batch *batch, int what, const float *in);
+int dust_disco_batch_get(dust_disco_batch *batch, int what, float *out);
+int dust_disco_batch_forward(dust_disco_batch *batch, const float *states, const float *actions, const float *params, int flags,
+                             const unsigned char *active);
+int dust_disco_batch_step(dust_disco_batch *batch, int strategy, int steps, const float *ext_actions, const unsigned char *active,
+                          float *next_actions);
+int dust_disco_batch_tick(dust_disco_batch *batch, const float *states, const float *actions, const float *params, int flags,
+                          const unsigned char *active, int strategy, int steps, const float *ext_actions, float *next_actions);
+int dust_disco_batch_episode(dust_disco_batch *batch, const float *states, int n_periods, const float *params, const float *plant_params,
+                             int strategy, const dust_episode_rules *rules, int flags, const unsigned char *active, float *states_out,
+                             float *actions_out, float *costs_out, float *loss, int *status, int *n_run, float *a_seq);
+
 /* stage outputs of the last call, for parity tests ([S][N] / [N][H][da] / [N]) */
 int dust_get_costs(dust_ctx *ctx, float *costs);
 int dust_get_actions(dust_ctx *ctx, float *actions);
