@@ -694,6 +694,44 @@ def _seeds(seeds, B):
     return sd, sd.ctypes.data_as(C.POINTER(C.c_uint64))
 
 
+def _period_seeds(seeds, rows, B):
+    """an episode's Philox keys [rows, B], period by period (None: the library refuses) -> as _seeds"""
+    if seeds is not None and np.shape(seeds) != (rows, B):
+        raise ValueError("seeds has shape %s, the call reads %s" % (np.shape(seeds), (rows, B)))
+    return _seeds(seeds, rows * B)
+
+
+def _plant_rows(pl, B, P):
+    """the plants' true parameter rows as [B, P] float32 (None: nominal plants)"""
+    if pl is None:
+        return None
+    pl = _f(pl)
+    if pl.shape != (B, max(P, 1)):
+        raise ValueError("plant_params has shape %s, the call reads %s" % (pl.shape, (B, max(P, 1))))
+    return pl
+
+
+def _episode_rules(ds, t0, warm_up, goal, goal_radius, stop_on_crash):
+    """the reference's episode rules as the library reads them (goal [ds] or None, goal_radius None: no goal)"""
+    ru = L.EpisodeRules()
+    ru.t0, ru.warm_up, ru.stop_on_crash = int(t0), int(warm_up), int(bool(stop_on_crash))
+    ru.goal_radius = 0.0 if goal_radius is None else float(goal_radius)
+    if goal is not None:
+        g = np.asarray(goal, np.float32).reshape(-1)
+        if g.shape != (ds,):
+            raise ValueError("goal has %d entries, a state has %d" % (g.size, ds))
+        ru.goal[:ds] = [float(v) for v in g]
+    return ru
+
+
+def _rules_state(B, loss, status):
+    """what an episode under rules carries from call to call: loss / status [B] where a previous call left them (None: 0), and n_run
+    [B] = -1 for the call to write -> (loss, status, n_run, the pointer type of the two int arrays)"""
+    loss = np.zeros(B, np.float32) if loss is None else np.array(_f(loss, (B,)))
+    status = np.zeros(B, np.int32) if status is None else np.ascontiguousarray(np.array(status, np.int32).reshape(B))
+    return loss, status, np.full(B, -1, np.int32), C.POINTER(C.c_int)
+
+
 class _BatchHandle:
     """The lifetime of a batch's C handle `_h`; a class names its library symbols in `_destroy` and `_clone`.  A controller batch's
     borrowed inner context `ctx` is closed ahead of the handle."""
@@ -825,16 +863,13 @@ class AmppiBatch(_BatchHandle):
         the last period before its roll); the rows of inactive environments are NaN."""
         B, T, S = self.B, int(n_periods), self.S
         st = None if states is None else _f(states, (B, self.ds))  # (None: the library refuses)
-        pr = pl = None
+        pr = None
         if params is not None:
             pr = _f(params)
             want = (T, B, self.M if self.M > 1 else (1 if shared_params else S), max(self.P, 1))
             if pr.shape != want:
                 raise ValueError("params has shape %s, the call reads %s" % (pr.shape, want))
-        if plant_params is not None:
-            pl = _f(plant_params)
-            if pl.shape != (B, max(self.P, 1)):
-                raise ValueError("plant_params has shape %s, the call reads %s" % (pl.shape, (B, max(self.P, 1))))
+        pl = _plant_rows(plant_params, B, self.P)
         _, mp = _mask(active, B)
         rows = max(T, 0)  # (n_periods < 1: the library refuses before it writes anything)
         xs, acts, a_seq = (np.full(sh, np.nan, np.float32) for sh in ((rows, B, self.ds), (rows, B, self.da), (B, self.H, self.da)))
@@ -857,14 +892,8 @@ class AmppiBatch(_BatchHandle):
         st = None if states is None else _f(states, (B, self.ds))  # (None: the library refuses)
         ap = None if actions_prev is None else _f(actions_prev, (B, self.da))
         rows = max(T, 0)  # (n_periods < 1: the library refuses before it reads or writes anything)
-        if seeds is not None and np.shape(seeds) != (rows, B):
-            raise ValueError("seeds has shape %s, the call reads %s" % (np.shape(seeds), (rows, B)))
-        sd, sp = _seeds(seeds, rows * B)
-        pl = None
-        if plant_params is not None:
-            pl = _f(plant_params)
-            if pl.shape != (B, max(self.P, 1)):
-                raise ValueError("plant_params has shape %s, the call reads %s" % (pl.shape, (B, max(self.P, 1))))
+        sd, sp = _period_seeds(seeds, rows, B)
+        pl = _plant_rows(plant_params, B, self.P)
         _, mp = _mask(active, B)
         xs, acts, bw, a_seq = (np.full(sh, np.nan, np.float32) for sh in ((rows, B, self.ds), (rows, B, self.da), (rows, B), (B, self.H, self.da)))
         costs, omega = ((np.full((rows, B, S), np.nan, np.float32) for _ in range(2)) if want_costs else (None, None))
@@ -1010,16 +1039,13 @@ class SvmpcBatch(_BatchHandle):
         refuses any)."""
         B, T = self.B, int(n_periods)
         st = None if states is None else _f(states, (B, self.ds))  # (None: the library refuses)
-        pr = pl = None
+        pr = None
         if params is not None:
             pr = _f(params)
             want = (T, B, int(n_steps), self.M, max(self.P, 1))
             if pr.shape != want:
                 raise ValueError("params has shape %s, the call reads %s" % (pr.shape, want))
-        if plant_params is not None:
-            pl = _f(plant_params)
-            if pl.shape != (B, max(self.P, 1)):
-                raise ValueError("plant_params has shape %s, the call reads %s" % (pl.shape, (B, max(self.P, 1))))
+        pl = _plant_rows(plant_params, B, self.P)
         _, mp = _mask(active, B)
         rows = max(T, 0)  # (n_periods < 1: the library refuses before it writes anything)
         xs, acts, a_seq = (np.full(sh, np.nan, np.float32) for sh in ((rows, B, self.ds), (rows, B, self.da), (B, self.H, self.da)))
@@ -1038,32 +1064,19 @@ class SvmpcBatch(_BatchHandle):
         warm-up rows of p_weights, inactive environments - are NaN (n_run: -1)."""
         B, T = self.B, int(n_periods)
         st = None if states is None else _f(states, (B, self.ds))  # (None: the library refuses)
-        pr = pl = None
+        pr = None
         if params is not None:
             pr = _f(params)
             want = (T, B, int(n_steps), self.M, max(self.P, 1))
             if pr.shape != want:
                 raise ValueError("params has shape %s, the call reads %s" % (pr.shape, want))
-        if plant_params is not None:
-            pl = _f(plant_params)
-            if pl.shape != (B, max(self.P, 1)):
-                raise ValueError("plant_params has shape %s, the call reads %s" % (pl.shape, (B, max(self.P, 1))))
-        ru = L.EpisodeRules()
-        ru.t0, ru.warm_up, ru.stop_on_crash = int(t0), int(warm_up), int(bool(stop_on_crash))
-        ru.goal_radius = 0.0 if goal_radius is None else float(goal_radius)
-        if goal is not None:
-            g = np.asarray(goal, np.float32).reshape(-1)
-            if g.shape != (self.ds,):
-                raise ValueError("goal has %d entries, a state has %d" % (g.size, self.ds))
-            ru.goal[:self.ds] = [float(v) for v in g]
+        pl = _plant_rows(plant_params, B, self.P)
+        ru = _episode_rules(self.ds, t0, warm_up, goal, goal_radius, stop_on_crash)
         _, mp = _mask(active, B)
         rows = max(T, 0)  # (n_periods < 1: the library refuses before it writes anything)
         xs, acts, costs, a_seq = (np.full(sh, np.nan, np.float32) for sh in ((rows, B, self.ds), (rows, B, self.da), (rows, B), (B, self.H, self.da)))
         pw = np.full((rows, B, self.N), np.nan, np.float32) if want_pw else None
-        loss = np.zeros(B, np.float32) if loss is None else np.array(_f(loss, (B,)))
-        status = np.zeros(B, np.int32) if status is None else np.ascontiguousarray(np.array(status, np.int32).reshape(B))
-        n_run = np.full(B, -1, np.int32)
-        IP = C.POINTER(C.c_int)
+        loss, status, n_run, IP = _rules_state(B, loss, status)
         L.check(L.load().dust_svmpc_batch_simulate(self._h, _p(st), T, int(n_steps), _p(pr), _p(pl), C.byref(ru), int(flags), mp, _p(xs), _p(acts),
                                                    _p(pw), _p(costs), _p(loss), status.ctypes.data_as(IP), n_run.ctypes.data_as(IP), _p(a_seq)))
         return xs, acts, pw, costs, loss, status, n_run, a_seq
@@ -1103,14 +1116,8 @@ class SvmpcBatch(_BatchHandle):
         st = None if states is None else _f(states, (B, self.ds))  # (None: the library refuses)
         ap = None if actions_prev is None else _f(actions_prev, (B, self.da))
         rows = max(T, 0)  # (n_periods < 1: the library refuses before it reads or writes anything)
-        if seeds is not None and np.shape(seeds) != (rows, B):
-            raise ValueError("seeds has shape %s, the call reads %s" % (np.shape(seeds), (rows, B)))
-        sd, sp = _seeds(seeds, rows * B)
-        pl = None
-        if plant_params is not None:
-            pl = _f(plant_params)
-            if pl.shape != (B, max(self.P, 1)):
-                raise ValueError("plant_params has shape %s, the call reads %s" % (pl.shape, (B, max(self.P, 1))))
+        sd, sp = _period_seeds(seeds, rows, B)
+        pl = _plant_rows(plant_params, B, self.P)
         _, mp = _mask(active, B)
         xs, acts, bw, a_seq = (np.full(sh, np.nan, np.float32) for sh in ((rows, B, self.ds), (rows, B, self.da), (rows, B), (B, self.H, self.da)))
         pw = np.full((rows, B, self.N), np.nan, np.float32) if want_pw else None
@@ -1149,30 +1156,14 @@ class SvmpcBatch(_BatchHandle):
         st = None if states is None else _f(states, (B, self.ds))  # (None: the library refuses)
         ap = None if actions_prev is None else _f(actions_prev, (B, self.da))
         rows = max(T, 0)  # (n_periods < 1: the library refuses before it reads or writes anything)
-        if seeds is not None and np.shape(seeds) != (rows, B):
-            raise ValueError("seeds has shape %s, the call reads %s" % (np.shape(seeds), (rows, B)))
-        sd, sp = _seeds(seeds, rows * B)
-        pl = None
-        if plant_params is not None:
-            pl = _f(plant_params)
-            if pl.shape != (B, max(self.P, 1)):
-                raise ValueError("plant_params has shape %s, the call reads %s" % (pl.shape, (B, max(self.P, 1))))
-        ru = L.EpisodeRules()
-        ru.t0, ru.warm_up, ru.stop_on_crash = int(t0), int(warm_up), int(bool(stop_on_crash))
-        ru.goal_radius = 0.0 if goal_radius is None else float(goal_radius)
-        if goal is not None:
-            g = np.asarray(goal, np.float32).reshape(-1)
-            if g.shape != (self.ds,):
-                raise ValueError("goal has %d entries, a state has %d" % (g.size, self.ds))
-            ru.goal[:self.ds] = [float(v) for v in g]
+        sd, sp = _period_seeds(seeds, rows, B)
+        pl = _plant_rows(plant_params, B, self.P)
+        ru = _episode_rules(self.ds, t0, warm_up, goal, goal_radius, stop_on_crash)
         _, mp = _mask(active, B)
         xs, acts, bw, costs, a_seq = (np.full(sh, np.nan, np.float32)
                                       for sh in ((rows, B, self.ds), (rows, B, self.da), (rows, B), (rows, B), (B, self.H, self.da)))
         pw = np.full((rows, B, self.N), np.nan, np.float32) if want_pw else None
-        loss = np.zeros(B, np.float32) if loss is None else np.array(_f(loss, (B,)))
-        status = np.zeros(B, np.int32) if status is None else np.ascontiguousarray(np.array(status, np.int32).reshape(B))
-        n_run = np.full(B, -1, np.int32)
-        IP = C.POINTER(C.c_int)
+        loss, status, n_run, IP = _rules_state(B, loss, status)
         L.check(L.load().dust_svmpc_dual_batch_simulate(self._h, mpf._h, _p(st), _p(ap), T, int(n_steps), int(mpf_steps),
                                                         float(-1.0 if mpf_bw is None else mpf_bw), sp, _p(pl), C.byref(ru), int(flags), mp,
                                                         _p(xs), _p(acts), _p(pw), _p(bw), _p(costs), _p(loss), status.ctypes.data_as(IP),
@@ -1273,22 +1264,18 @@ class DiscoBatch(_BatchHandle):
         (n_run: -1)."""
         B, T = self.B, int(n_periods)
         st = None if states is None else _f(states, (B, self.ds))  # (None: the library refuses)
-        pr = pl = None
+        pr = None
         if params is not None:
             pr = _f(params)
             want = (B, self.M, max(self.P, 1)) if params_once else (T, B, self.M, max(self.P, 1))
             if pr.shape != want:
                 raise ValueError("params has shape %s, the call reads %s" % (pr.shape, want))
-        if plant_params is not None:
-            pl = _f(plant_params)
-            if pl.shape != (B, max(self.P, 1)):
-                raise ValueError("plant_params has shape %s, the call reads %s" % (pl.shape, (B, max(self.P, 1))))
+        pl = _plant_rows(plant_params, B, self.P)
         sid = _STEP_IDS.get(strategy, -1) if isinstance(strategy, str) else int(strategy)
         _, mp = _mask(active, B)
         rows = max(T, 0)  # (n_periods < 1: the library refuses before it writes anything)
         xs, acts, a_seq = (np.full(sh, np.nan, np.float32) for sh in ((rows, B, self.ds), (rows, B, self.da), (B, self.H, self.da)))
         fl = int(flags) | (L.DISCO_PARAMS_ONCE if params_once else 0)
-        IP = C.POINTER(C.c_int)
         if rules is None:
             L.check(L.load().dust_disco_batch_episode(self._h, _p(st), T, _p(pr), _p(pl), sid, None, fl, mp, _p(xs), _p(acts), None, None,
                                                       None, None, _p(a_seq)))
@@ -1296,18 +1283,10 @@ class DiscoBatch(_BatchHandle):
         unknown = set(rules) - {"t0", "warm_up", "goal", "goal_radius", "stop_on_crash"}
         if unknown:
             raise ValueError("rules has the unknown keys %s" % sorted(unknown))
-        ru = L.EpisodeRules()
-        ru.t0, ru.warm_up, ru.stop_on_crash = int(rules.get("t0", 0)), int(rules.get("warm_up", 0)), int(bool(rules.get("stop_on_crash", False)))
-        ru.goal_radius = 0.0 if rules.get("goal_radius") is None else float(rules["goal_radius"])
-        if rules.get("goal") is not None:
-            g = np.asarray(rules["goal"], np.float32).reshape(-1)
-            if g.shape != (self.ds,):
-                raise ValueError("goal has %d entries, a state has %d" % (g.size, self.ds))
-            ru.goal[:self.ds] = [float(v) for v in g]
+        ru = _episode_rules(self.ds, rules.get("t0", 0), rules.get("warm_up", 0), rules.get("goal"), rules.get("goal_radius"),
+                            rules.get("stop_on_crash", False))
         costs = np.full((rows, B), np.nan, np.float32)
-        loss = np.zeros(B, np.float32) if loss is None else np.array(_f(loss, (B,)))
-        status = np.zeros(B, np.int32) if status is None else np.ascontiguousarray(np.array(status, np.int32).reshape(B))
-        n_run = np.full(B, -1, np.int32)
+        loss, status, n_run, IP = _rules_state(B, loss, status)
         L.check(L.load().dust_disco_batch_episode(self._h, _p(st), T, _p(pr), _p(pl), sid, C.byref(ru), fl, mp, _p(xs), _p(acts), _p(costs),
                                                   _p(loss), status.ctypes.data_as(IP), n_run.ctypes.data_as(IP), _p(a_seq)))
         return xs, acts, costs, loss, status, n_run, a_seq

@@ -27,6 +27,7 @@
 #include "bandwidth.hpp"
 #include "common.hpp"
 #include "devbuf.hpp"
+#include "episode_host.hpp"
 #include "forward.hpp"
 #include "fused.hpp"
 #include "pairwise_big.hpp"
@@ -1629,26 +1630,20 @@ static int batch_seeds_set(dust_ctx *c, size_t B, const uint64_t *seeds, uint64_
   return h2d(c, dev, sd.data(), B * sizeof(uint64_t));
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// AMPPI over a batch of plants: B independent ticks in one launch (amppi.hpp amppi_batch_kernel).  The batch owns a private clone of
-// the prototype context - model, cost, map, sigma weights, stream, profile counters - and the per-environment device rows.
-struct dust_amppi_batch {
-  dust_ctx *c;
-  int B;
-  DevBuf<float> a_seq;           // [B][D]
-  DevBuf<float> acts;            // [B][S][D]
-  DevBuf<float> costs, omega;    // [B][S]
-  DevBuf<float> params;          // [B][rows][P]
-  DevBuf<uint32_t> ctr;          // [B][4]: every environment's Philox stream position {tick, iter, .., ..}
-  DevBuf<uint64_t> seeds;        // [B]
-  DevBuf<unsigned int> ticket;   // [B]
-  DevBuf<float> plant, rec;      // dust_amppi_batch_episode: [B][P] true parameter rows; the records [T][B][ds], [T][B][da], [T][B][S] x 2, [B][D]
-  BatchInputs in;         // per-call inputs
-  std::vector<unsigned char> last_active;  // the mask of the last tick (dust_amppi_batch_get_actions writes the rows of that tick's environments)
-  bool acts_valid;
+// What the three controller batch handles (dust_amppi_batch, dust_svmpc_batch, dust_disco_batch) are made of.  A batch owns a private
+// clone of the prototype context - model, cost, map, sigma weights, stream, profile counters - and every environment's device rows
+struct BatchCore {
+  dust_ctx *c = nullptr;
+  int B = 0;
+  DevBuf<uint32_t> ctr;      // [B][4]: every environment's Philox stream position {tick, iter, .., ..}
+  DevBuf<uint64_t> seeds;    // [B]
+  DevBuf<float> params;      // the parameter rows a call has staged
+  DevBuf<float> plant, rec;  // the episodes: [B][P] true parameter rows; the records (episode_host.hpp)
+  BatchInputs in;            // per-call inputs
 };
 
-static void batch_free(dust_amppi_batch *b) {
+template <class T>
+static void batch_free(T *b) {
   if (!b) return;
   if (b->c) {
     (void)hipSetDevice(b->c->cfg.device);
@@ -1659,78 +1654,168 @@ static void batch_free(dust_amppi_batch *b) {
   if (inner) dust_destroy(inner);
 }
 
-// the batch around an inner context it takes over: buffers allocated, nothing filled yet
-static int batch_alloc(dust_ctx *inner, int n_env, dust_amppi_batch **out) {
-  dust_amppi_batch *b = new dust_amppi_batch();
+template <class T>
+static int batch_ctx(T *b, dust_ctx **out) {
+  if (!b || !out) return fail(DUST_ERR_INVALID, "null argument");
+  *out = b->c;
+  return DUST_OK;
+}
+
+// the batch around an inner context it takes over: `rows` allocates the type's buffers, nothing is filled yet
+template <class T, class Rows>
+static int batch_alloc(dust_ctx *inner, int n_env, T **out, Rows rows) {
+  T *b = new T();
   b->c = inner;
   b->B = n_env;
   *out = b;
-  const size_t B = (size_t)n_env, S = (size_t)inner->S, D = (size_t)inner->D;
   HIP_TRY(hipSetDevice(inner->cfg.device));
+  TRY(rows(b));
+  return b->in.alloc(n_env);
+}
+
+// the end of a create or clone: the batch goes to the caller, or away
+template <class T>
+static int batch_hand_over(T *b, int st, T **out) {
+  if (st != DUST_OK) {
+    batch_free(b);
+    return st;
+  }
+  *out = b;
+  return DUST_OK;
+}
+
+// create: the type's check and `unit` (what a launch spends per environment), a clone of the prototype, `rows`, then `fill` - every
+// environment starts from the prototype's rows
+template <class T, class Rows, class Fill>
+static int batch_create(const dust_ctx *proto, int n_env, T **out, int (*check)(const dust_ctx *), const char *unit, Rows rows, Fill fill) {
+  if (!proto || !out) return fail(DUST_ERR_INVALID, "null argument");
+  *out = nullptr;
+  TRY(check(proto));
+  TRY(batch_n_env_check(n_env, unit));
+  dust_ctx *inner = nullptr;
+  TRY(dust_clone(proto, &inner));  // (settles and waits for the prototype's stream)
+  T *b = nullptr;
+  int st = batch_alloc(inner, n_env, &b, rows);
+  if (st == DUST_OK) st = fill(b);
+  return batch_hand_over(b, st, out);
+}
+
+// clone: a clone of the source's context, `rows`, then `copy` - the source's rows and flags - and the wait for the copies
+template <class T, class Rows, class Copy>
+static int batch_clone(const T *src, T **out, Rows rows, Copy copy) {
+  if (!src || !out) return fail(DUST_ERR_INVALID, "null argument");
+  *out = nullptr;
+  dust_ctx *inner = nullptr;
+  TRY(dust_clone(src->c, &inner));  // (waits for the source's stream)
+  T *b = nullptr;
+  int st = batch_alloc(inner, src->B, &b, rows);
+  if (st == DUST_OK) st = copy(b);
+  if (st == DUST_OK && hipStreamSynchronize(inner->stream) != hipSuccess) st = fail(DUST_ERR_HIP, "hipStreamSynchronize failed");
+  return batch_hand_over(b, st, out);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// What the episode entries refuse alike, ahead of any copy or launch.  `why`: the entry's own words on what a long call costs
+static int episode_periods_check(int n_periods, const char *why) {
+  if (n_periods < 1 || n_periods > 4096) return fail(DUST_ERR_INVALID, "n_periods = %d outside [1, 4096] (%s)", n_periods, why);
+  return DUST_OK;
+}
+static int episode_plant_check(const dust_ctx *c, const float *plant_params) {
+  if (c->cfg.dim_p == 0 && plant_params) return fail(DUST_ERR_INVALID, "plant parameter rows without uncertain parameters (dim_p = 0)");
+  return DUST_OK;
+}
+// dust_episode_rules against the batch's context and the caller's status words.  no_warm_up: the MultiDISCO loop has none; particle_map:
+// the dual loop stops on the Particle map alone (the plain ticks also know the skid-steer navigation cost's)
+static int rules_check(const dust_ctx *c, const dust_episode_rules *r, size_t B, const unsigned char *active, const int *status, bool no_warm_up,
+                       bool particle_map) {
+  if (no_warm_up) {
+    if (r->warm_up != 0) return fail(DUST_ERR_INVALID, "warm_up = %d: the MultiDISCO branch of the reference's loops has no warm-up", r->warm_up);
+    if (r->t0 < 0) return fail(DUST_ERR_INVALID, "t0 = %d: >= 0", r->t0);
+  } else if (r->t0 < 0 || r->warm_up < 0) {
+    return fail(DUST_ERR_INVALID, "t0 = %d, warm_up = %d: both are >= 0", r->t0, r->warm_up);
+  }
+  if (r->t0 > 0x7fffffff - 4096) return fail(DUST_ERR_INVALID, "t0 = %d: the episode's period index does not fit", r->t0);
+  bool finite = std::isfinite(r->goal_radius);
+  for (int k = 0; k < c->ds && k < 8; ++k) finite = finite && std::isfinite(r->goal[k]);
+  if (!finite) return fail(DUST_ERR_INVALID, "the goal and its radius must be finite");
+  for (size_t e = 0; e < B; ++e)
+    if ((!active || active[e]) && (status[e] < 0 || status[e] > 2))
+      return fail(DUST_ERR_INVALID, "status[%zu] = %d: 0 (running), 1 (goal) or 2 (crash)", e, status[e]);
+  const bool map = c->cfg.model == DUST_MODEL_PARTICLE && c->cfg.with_obstacle && c->grid_bits;
+  if (r->stop_on_crash && !(map || (!particle_map && skid_nav_on(c))))
+    return fail(DUST_ERR_UNSUPPORTED, particle_map ? "stop_on_crash needs an occupancy map: Particle with_obstacle"
+                                                   : "stop_on_crash needs an occupancy map: Particle with_obstacle, or the skid-steer navigation cost");
+  return DUST_OK;
+}
+// the rules as a kernel reads them (SvbRules, SvbDualSim): the stops, and the words behind the records (`words`: device memory)
+template <class R>
+static void rules_fill(R &ru, const dust_episode_rules *r, int ds, float *costs_out, float *words, size_t B) {
+  ru.stop_on_crash = r->stop_on_crash ? 1 : 0;
+  ru.goal_on = r->goal_radius > 0.f ? 1 : 0;
+  ru.r2 = (float)((double)r->goal_radius * (double)r->goal_radius);
+  for (int k = 0; k < 8; ++k) ru.goal[k] = k < ds ? r->goal[k] : 0.f;
+  ru.costs_out = costs_out;
+  ru.loss = words;
+  ru.status = reinterpret_cast<int *>(words + B);
+  ru.n_run = ru.status + B;
+}
+// periods of the call without forward(): no particle weights, and no sequence while it lasts
+static size_t rules_warm(const dust_episode_rules *r) { return r ? (size_t)std::max(0, r->warm_up - r->t0) : 0; }
+
+// ---------------------------------------------------------------------------------------------------------------
+// AMPPI over a batch of plants: B independent ticks in one launch (amppi.hpp amppi_batch_kernel).
+struct dust_amppi_batch : BatchCore {
+  DevBuf<float> a_seq;           // [B][D]
+  DevBuf<float> acts;            // [B][S][D]
+  DevBuf<float> costs, omega;    // [B][S]
+  DevBuf<unsigned int> ticket;   // [B]
+  // (params: [B][rows][P]; rec: [T][B][ds], [T][B][da], [T][B][S] x 2, [B][D])
+  std::vector<unsigned char> last_active;  // the mask of the last tick (dust_amppi_batch_get_actions writes the rows of that tick's environments)
+  bool acts_valid = false;
+};
+
+static int amppi_batch_rows(dust_amppi_batch *b) {
+  const size_t B = (size_t)b->B, S = (size_t)b->c->S, D = (size_t)b->c->D;
   TRY(b->a_seq.alloc(B * D));
   TRY(b->acts.alloc(B * S * D));
   TRY(b->costs.alloc(B * S));
   TRY(b->omega.alloc(B * S));
   TRY(b->ctr.alloc(B * 4));
   TRY(b->seeds.alloc(B));
-  TRY(b->ticket.alloc(B));
-  return b->in.alloc(n_env);
+  return b->ticket.alloc(B);
 }
 
 static int batch_null(const dust_amppi_batch *b) { return b ? DUST_OK : fail(DUST_ERR_INVALID, "null batch"); }
 
 extern "C" int dust_amppi_batch_create(const dust_ctx *proto, int n_env, const uint64_t *seeds, dust_amppi_batch **out) {
-  if (!proto || !out) return fail(DUST_ERR_INVALID, "null argument");
-  *out = nullptr;
-  TRY(amppi_check(proto));
-  TRY(batch_n_env_check(n_env, "one grid row per environment"));
-  dust_ctx *inner = nullptr;
-  TRY(dust_clone(proto, &inner));
-  dust_amppi_batch *b = nullptr;
-  int st = batch_alloc(inner, n_env, &b);
-  if (st == DUST_OK) st = spread(inner, (size_t)n_env, b->a_seq, inner->a_seq, (size_t)inner->D * sizeof(float));
-  if (st == DUST_OK) st = spread(inner, (size_t)n_env, b->ctr, inner->ctr_dev, 4 * sizeof(uint32_t));
-  if (st == DUST_OK) st = batch_seeds_set(inner, (size_t)n_env, seeds, b->seeds);
-  if (st != DUST_OK) {
-    batch_free(b);
-    return st;
-  }
-  *out = b;
-  return DUST_OK;
+  return batch_create(proto, n_env, out, amppi_check, "one grid row per environment", amppi_batch_rows, [&](dust_amppi_batch *b) -> int {
+    dust_ctx *inner = b->c;
+    TRY(spread(inner, (size_t)n_env, b->a_seq, inner->a_seq, (size_t)inner->D * sizeof(float)));
+    TRY(spread(inner, (size_t)n_env, b->ctr, inner->ctr_dev, 4 * sizeof(uint32_t)));
+    return batch_seeds_set(inner, (size_t)n_env, seeds, b->seeds);
+  });
 }
 
 extern "C" void dust_amppi_batch_destroy(dust_amppi_batch *b) { batch_free(b); }
 
 extern "C" int dust_amppi_batch_clone(const dust_amppi_batch *src, dust_amppi_batch **out) {
-  if (!src || !out) return fail(DUST_ERR_INVALID, "null argument");
-  *out = nullptr;
-  dust_ctx *inner = nullptr;
-  TRY(dust_clone(src->c, &inner));  // (waits for the source's stream)
-  dust_amppi_batch *b = nullptr;
-  int st = batch_alloc(inner, src->B, &b);
-  const size_t B = (size_t)src->B, S = (size_t)inner->S, D = (size_t)inner->D;
-  if (st == DUST_OK) st = d2d(inner, b->a_seq, src->a_seq, B * D * sizeof(float));
-  if (st == DUST_OK) st = d2d(inner, b->ctr, src->ctr, B * 4 * sizeof(uint32_t));
-  if (st == DUST_OK) st = d2d(inner, b->seeds, src->seeds, B * sizeof(uint64_t));
-  if (st == DUST_OK && src->acts_valid) {  // (dust_amppi_batch_get_actions of the copy gives what the source's would)
-    st = d2d(inner, b->acts, src->acts, B * S * D * sizeof(float));
-    b->acts_valid = true;
-    b->last_active = src->last_active;
-  }
-  if (st == DUST_OK && hipStreamSynchronize(inner->stream) != hipSuccess) st = fail(DUST_ERR_HIP, "hipStreamSynchronize failed");
-  if (st != DUST_OK) {
-    batch_free(b);
-    return st;
-  }
-  *out = b;
-  return DUST_OK;
+  return batch_clone(src, out, amppi_batch_rows, [&](dust_amppi_batch *b) -> int {
+    dust_ctx *inner = b->c;
+    const size_t B = (size_t)src->B, S = (size_t)inner->S, D = (size_t)inner->D;
+    TRY(d2d(inner, b->a_seq, src->a_seq, B * D * sizeof(float)));
+    TRY(d2d(inner, b->ctr, src->ctr, B * 4 * sizeof(uint32_t)));
+    TRY(d2d(inner, b->seeds, src->seeds, B * sizeof(uint64_t)));
+    if (src->acts_valid) {  // (dust_amppi_batch_get_actions of the copy gives what the source's would)
+      const int st = d2d(inner, b->acts, src->acts, B * S * D * sizeof(float));
+      b->acts_valid = true;
+      b->last_active = src->last_active;
+      return st;
+    }
+    return DUST_OK;
+  });
 }
 
-extern "C" int dust_amppi_batch_ctx(dust_amppi_batch *b, dust_ctx **out) {
-  if (!b || !out) return fail(DUST_ERR_INVALID, "null argument");
-  *out = b->c;
-  return DUST_OK;
-}
+extern "C" int dust_amppi_batch_ctx(dust_amppi_batch *b, dust_ctx **out) { return batch_ctx(b, out); }
 
 extern "C" int dust_amppi_batch_set_a_seq(dust_amppi_batch *b, const float *a_seq) {
   if (!b || !a_seq) return fail(DUST_ERR_INVALID, "null argument");
@@ -1847,13 +1932,44 @@ extern "C" int dust_amppi_batch_get_actions(dust_amppi_batch *b, float *actions)
 // staged once and period t reads its slice; the call waits once, for the records.
 // DUST_AMPPI_EPISODE_MAX_FLOATS bounds the staged rows and the records (each at most 2^28 floats, 1 GiB): a longer episode is split.
 static constexpr size_t DUST_AMPPI_EPISODE_MAX_FLOATS = (size_t)1 << 28;
+// The records of an AMPPI episode, plain or dual (the plain one has no bandwidths): states | actions | costs | omega | bw, then the final a_seq
+struct AmppiRecords {
+  RecSection s, a, co, om, bw, q;
+  size_t n_rec;
+  AmppiRecords(const dust_ctx *c, size_t T, size_t B, bool costs, bool omega, bool bw_dev, bool a_seq) {
+    EpisodeRecords lay(T, B);
+    s = lay.add((size_t)c->ds);
+    a = lay.add((size_t)c->da);
+    co = lay.add((size_t)c->S, costs);
+    om = lay.add((size_t)c->S, omega);
+    bw = lay.add(1, bw_dev);
+    q = lay.per_call((size_t)c->D, a_seq);
+    n_rec = lay.total();
+  }
+  // where period t writes: its rows of the sections, and the final sequence in the last period (AmppiEpisode's bw_out is the dual entry's)
+  template <class Ep>
+  void period(Ep &ep, float *rec, size_t t) const {
+    ep.states_out = s.at(rec, t);
+    ep.actions_out = a.at(rec, t);
+    ep.costs_out = co.at(rec, t);
+    ep.omega_out = om.at(rec, t);
+    ep.a_seq_out = t + 1 == s.n ? q.at(rec, 0) : nullptr;
+  }
+  // what of the block read back goes to the caller: the rows of the call's environments
+  void out(const float *host, const unsigned char *active, float *states_out, float *actions_out, float *costs_out, float *omega_out, float *bw_out,
+           float *a_seq) const {
+    const RecSection *sec[] = {&s, &a, &co, &om, &bw, &q};
+    float *dst[] = {states_out, actions_out, costs_out, omega_out, bw_out, a_seq};
+    for (int k = 0; k < 6; ++k)
+      if (sec[k]->present) records_scatter(dst[k], host, *sec[k], active, nullptr);
+  }
+};
 extern "C" int dust_amppi_batch_episode(dust_amppi_batch *b, const float *states, int n_periods, const float *params, int flags, int roll_steps,
                                         const float *plant_params, const unsigned char *active, float *states_out, float *actions_out,
                                         float *costs_out, float *omega_out, float *a_seq) {
   TRY(batch_null(b));
   if (!states || !states_out || !actions_out) return fail(DUST_ERR_INVALID, "null argument");
-  if (n_periods < 1 || n_periods > 4096)
-    return fail(DUST_ERR_INVALID, "n_periods = %d outside [1, 4096] (the queue of one call stays short on a shared device: split a longer episode)", n_periods);
+  TRY(episode_periods_check(n_periods, "the queue of one call stays short on a shared device: split a longer episode"));
   if (roll_steps < 1) return fail(DUST_ERR_INVALID, "roll(steps = %d): steps >= 1", roll_steps);
   if (flags & ~DUST_AMPPI_PARAMS_SHARED)
     return fail(DUST_ERR_UNSUPPORTED,
@@ -1861,14 +1977,14 @@ extern "C" int dust_amppi_batch_episode(dust_amppi_batch *b, const float *states
                 "flags may hold DUST_AMPPI_PARAMS_SHARED alone (got %d)", flags);
   dust_ctx *c = b->c;
   TRY(amppi_check(c));
-  if (c->cfg.dim_p == 0 && plant_params) return fail(DUST_ERR_INVALID, "plant parameter rows without uncertain parameters (dim_p = 0)");
+  TRY(episode_plant_check(c, plant_params));
   int mode = AMPPI_PARAMS_NONE, pts = 1;
   size_t prows = 0;
   TRY(amppi_params_mode(c, params != nullptr, flags, nullptr, &mode, &pts, &prows));
-  const size_t T = (size_t)n_periods, B = (size_t)b->B, S = (size_t)c->S, D = (size_t)c->D, P = (size_t)c->cfg.dim_p;
-  const size_t ds = (size_t)c->ds, da = (size_t)c->da;
+  const size_t T = (size_t)n_periods, B = (size_t)b->B, S = (size_t)c->S, P = (size_t)c->cfg.dim_p;
   const size_t per = B * prows * P;  // parameter values of one period
-  const size_t n_rec = T * B * (ds + da + (costs_out ? S : 0) + (omega_out ? S : 0)) + (a_seq ? B * D : 0);
+  const AmppiRecords lay(c, T, B, costs_out != nullptr, omega_out != nullptr, false, a_seq != nullptr);
+  const size_t n_rec = lay.n_rec;
   if (T * per > DUST_AMPPI_EPISODE_MAX_FLOATS)
     return fail(DUST_ERR_UNSUPPORTED, "%zu parameter values to stage for %d periods exceed %zu: split the episode into shorter calls", T * per, n_periods,
                 DUST_AMPPI_EPISODE_MAX_FLOATS);
@@ -1892,8 +2008,6 @@ extern "C" int dust_amppi_batch_episode(dust_amppi_batch *b, const float *states
   AmppiPeriodArgs kp;
   memset(&kp.ep, 0, sizeof kp.ep);  // (no filters: the dual episode's fields stay NULL)
   batch_tick_args(b, mode, pts, prows, true, active, kp.k);
-  float *rec_s = b->rec, *rec_a = rec_s + T * B * ds, *rec_c = rec_a + T * B * da, *rec_o = rec_c + (costs_out ? T * B * S : 0);
-  float *rec_q = rec_o + (omega_out ? T * B * S : 0);
   const long shift = (long)roll_steps * c->da;
   kp.ep.plant = plant_params ? b->plant.get() : nullptr;
   kp.ep.state = const_cast<float *>(b->in.states_dev());
@@ -1907,11 +2021,7 @@ extern "C" int dust_amppi_batch_episode(dust_amppi_batch *b, const float *states
   else b->last_active.clear();
   for (size_t t = 0; t < T; ++t) {
     kp.k.a.params = prows ? b->params.get() + t * per : nullptr;
-    kp.ep.states_out = rec_s + t * B * ds;
-    kp.ep.actions_out = rec_a + t * B * da;
-    kp.ep.costs_out = costs_out ? rec_c + t * B * S : nullptr;
-    kp.ep.omega_out = omega_out ? rec_o + t * B * S : nullptr;
-    kp.ep.a_seq_out = a_seq && t + 1 == T ? rec_q : nullptr;
+    lay.period(kp.ep, b->rec, t);
     Prof pr(c, DUST_K_AMPPI);
     if (nav) HIP_TRY(launch_on(c->stream, false, &amppi_skid_nav_period_kernel, grid, AMPPI_THREADS, map_lds, AmppiNavPeriodArgs{kp.k, nv, kp.ep}));
     else HIP_TRY(by_model(c, [&](auto M) { return launch_on(c->stream, false, &amppi_period_kernel<M()>, grid, AMPPI_THREADS, 0, kp); }));
@@ -1920,16 +2030,7 @@ extern "C" int dust_amppi_batch_episode(dust_amppi_batch *b, const float *states
   std::vector<float> host(n_rec);
   HIP_TRY(hipMemcpyAsync(host.data(), b->rec, n_rec * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  auto rows = [&](float *dst, const float *src, size_t n, size_t row) {
-    for (size_t t = 0; t < n; ++t)
-      for (size_t e = 0; e < B; ++e)
-        if (!active || active[e]) memcpy(dst + (t * B + e) * row, src + (t * B + e) * row, row * sizeof(float));
-  };
-  rows(states_out, host.data() + (rec_s - b->rec.get()), T, ds);
-  rows(actions_out, host.data() + (rec_a - b->rec.get()), T, da);
-  if (costs_out) rows(costs_out, host.data() + (rec_c - b->rec.get()), T, S);
-  if (omega_out) rows(omega_out, host.data() + (rec_o - b->rec.get()), T, S);
-  if (a_seq) rows(a_seq, host.data() + (rec_q - b->rec.get()), 1, D);
+  lay.out(host.data(), active, states_out, actions_out, costs_out, omega_out, nullptr, a_seq);
   return DUST_OK;
 }
 
@@ -5451,26 +5552,19 @@ extern "C" int dust_debug_stamps(dust_ctx *c, int kernel_id, unsigned long long 
 #endif
 
 // ---------------------------------------------------------------------------------------------------------------
-// SVMPC over a batch of plants: B independent ticks in one launch (svmpc_batch.hpp svmpc_batch_kernel).  The batch owns a private clone
-// of the prototype context - model, cost, map, stream, profile counters - and every environment's device rows.
-struct dust_svmpc_batch {
-  dust_ctx *c;
-  int B;
+// SVMPC over a batch of plants: B independent ticks in one launch (svmpc_batch.hpp svmpc_batch_kernel).
+struct dust_svmpc_batch : BatchCore {
   DevBuf<float> theta, mu, a_mat;  // [B][N][D]
   DevBuf<float> mixw, logmix;      // [B][N]
   DevBuf<int> alias;               // [B]
-  DevBuf<uint32_t> ctr;            // [B][4]
-  DevBuf<uint64_t> seeds;          // [B]
   DevBuf<float> opt_s[3];          // [B][N][D] or empty
   DevBuf<float> acts;              // [B][S][N][D]
   DevBuf<float> costs, wts, omg;   // [B][S][N]
   DevBuf<float> score, phi;        // [B][N][D]
   DevBuf<float> logl, logp, eta, a_mix, pw;  // [B][N]
   DevBuf<float> a_seq_out;         // [B][D]
-  DevBuf<float> eps, params;       // staged inputs of a call
-  DevBuf<float> plant, rec;        // dust_svmpc_batch_episode: [B][P] true parameter rows; the records [T][B][ds], [T][B][da], [T][B][N]
-  BatchInputs in;             // per-call inputs
-  bool have_costs, have_forward, acts_kept;
+  DevBuf<float> eps;               // the noise a call has staged (rec: [T][B][ds], [T][B][da], [T][B][N], the rules' costs and words)
+  bool have_costs = false, have_forward = false, acts_kept = false;
   std::vector<dust_svmpc_hyper> hyper;  // dust_svmpc_batch_set_hyper: the caller's rows [B], or empty (every environment: the prototype's)
   DevBuf<SvbHyper> hyper_dev;           // ... what the sweep instances read of them
 };
@@ -5538,25 +5632,9 @@ static int svb_check(const dust_ctx *c) {
   return DUST_OK;
 }
 
-static void svb_free(dust_svmpc_batch *b) {
-  if (!b) return;
-  if (b->c) {
-    (void)hipSetDevice(b->c->cfg.device);
-    (void)hipStreamSynchronize(b->c->stream);
-  }
+static int svb_rows(dust_svmpc_batch *b) {
   dust_ctx *inner = b->c;
-  delete b;  // the batch's own rows first, then the context they were allocated beside
-  if (inner) dust_destroy(inner);
-}
-
-// the batch around an inner context it takes over: buffers allocated, nothing filled yet
-static int svb_alloc(dust_ctx *inner, int n_env, dust_svmpc_batch **out) {
-  dust_svmpc_batch *b = new dust_svmpc_batch();
-  b->c = inner;
-  b->B = n_env;
-  *out = b;
-  const size_t B = (size_t)n_env, N = (size_t)inner->N, S = (size_t)inner->S, D = (size_t)inner->D;
-  HIP_TRY(hipSetDevice(inner->cfg.device));
+  const size_t B = (size_t)b->B, N = (size_t)inner->N, S = (size_t)inner->S, D = (size_t)inner->D;
   DevBuf<float> *nd[] = {&b->theta, &b->mu, &b->a_mat, &b->score, &b->phi};
   for (auto p : nd) TRY(p->alloc(B * N * D));
   DevBuf<float> *nn[] = {&b->mixw, &b->logmix, &b->logl, &b->logp, &b->eta, &b->a_mix, &b->pw};
@@ -5570,88 +5648,63 @@ static int svb_alloc(dust_ctx *inner, int n_env, dust_svmpc_batch **out) {
   TRY(b->seeds.alloc(B));
   TRY(optim_slots_alloc(inner->opt, b->opt_s, B * N * D));
   HIP_TRY(hipMemsetAsync(b->a_mix, 0, B * N * sizeof(float), inner->stream));
-  return b->in.alloc(n_env);
+  return DUST_OK;
 }
 
 extern "C" int dust_svmpc_batch_create(const dust_ctx *proto, int n_env, const uint64_t *seeds, dust_svmpc_batch **out) {
-  if (!proto || !out) return fail(DUST_ERR_INVALID, "null argument");
-  *out = nullptr;
-  TRY(svb_check(proto));
-  TRY(batch_n_env_check(n_env, "one workgroup per environment"));
-  dust_ctx *inner = nullptr;
-  TRY(dust_clone(proto, &inner));  // (settles and waits for the prototype's stream)
-  dust_svmpc_batch *b = nullptr;
-  int st = svb_alloc(inner, n_env, &b);
-  if (st == DUST_OK) {
+  return batch_create(proto, n_env, out, svb_check, "one workgroup per environment", svb_rows, [&](dust_svmpc_batch *b) -> int {
+    dust_ctx *inner = b->c;
     const size_t B = (size_t)n_env, N = (size_t)inner->N, ND = N * (size_t)inner->D;
-    st = spread(inner, B, b->theta, inner->theta, ND * sizeof(float));
-    if (st == DUST_OK) st = spread(inner, B, b->mu, inner->mu_aliased ? inner->theta : inner->mu, ND * sizeof(float));
-    if (st == DUST_OK) st = spread(inner, B, b->a_mat, inner->a_mat, ND * sizeof(float));
-    if (st == DUST_OK) st = spread(inner, B, b->mixw, inner->mixw, N * sizeof(float));
-    if (st == DUST_OK) st = spread(inner, B, b->logmix, inner->logmix, N * sizeof(float));
-    if (st == DUST_OK) st = spread(inner, B, b->ctr, inner->ctr_dev, 4 * sizeof(uint32_t));
-    for (int k = 0; k < 3 && st == DUST_OK; ++k)
-      if (b->opt_s[k] && inner->opt_s[k]) st = spread(inner, B, b->opt_s[k], inner->opt_s[k], ND * sizeof(float));
+    TRY(spread(inner, B, b->theta, inner->theta, ND * sizeof(float)));
+    TRY(spread(inner, B, b->mu, inner->mu_aliased ? inner->theta : inner->mu, ND * sizeof(float)));
+    TRY(spread(inner, B, b->a_mat, inner->a_mat, ND * sizeof(float)));
+    TRY(spread(inner, B, b->mixw, inner->mixw, N * sizeof(float)));
+    TRY(spread(inner, B, b->logmix, inner->logmix, N * sizeof(float)));
+    TRY(spread(inner, B, b->ctr, inner->ctr_dev, 4 * sizeof(uint32_t)));
+    for (int k = 0; k < 3; ++k)
+      if (b->opt_s[k] && inner->opt_s[k]) TRY(spread(inner, B, b->opt_s[k], inner->opt_s[k], ND * sizeof(float)));
     std::vector<int> al(B, inner->mu_aliased ? 1 : 0);
-    if (st == DUST_OK) st = h2d(inner, b->alias, al.data(), B * sizeof(int));
-    if (st == DUST_OK) st = batch_seeds_set(inner, B, seeds, b->seeds);
-  }
-  if (st != DUST_OK) {
-    svb_free(b);
-    return st;
-  }
-  *out = b;
-  return DUST_OK;
+    TRY(h2d(inner, b->alias, al.data(), B * sizeof(int)));
+    return batch_seeds_set(inner, B, seeds, b->seeds);
+  });
 }
 
-extern "C" void dust_svmpc_batch_destroy(dust_svmpc_batch *b) { svb_free(b); }
+extern "C" void dust_svmpc_batch_destroy(dust_svmpc_batch *b) { batch_free(b); }
+
+// what a clone copies of its source's rows: one device-to-device copy per entry that both sides hold
+struct BatchCopy {
+  void *dst;
+  const void *src;
+  size_t bytes;
+};
 
 extern "C" int dust_svmpc_batch_clone(const dust_svmpc_batch *src, dust_svmpc_batch **out) {
-  if (!src || !out) return fail(DUST_ERR_INVALID, "null argument");
-  *out = nullptr;
-  dust_ctx *inner = nullptr;
-  TRY(dust_clone(src->c, &inner));  // (waits for the source's stream)
-  dust_svmpc_batch *b = nullptr;
-  int st = svb_alloc(inner, src->B, &b);
-  const size_t B = (size_t)src->B, N = (size_t)inner->N, S = (size_t)inner->S, D = (size_t)inner->D, f = sizeof(float);
-  struct {
-    void *dst;
-    const void *s;
-    size_t bytes;
-  } cp[] = {{b->theta, src->theta, B * N * D * f}, {b->mu, src->mu, B * N * D * f}, {b->a_mat, src->a_mat, B * N * D * f},
-            {b->score, src->score, B * N * D * f}, {b->phi, src->phi, B * N * D * f}, {b->mixw, src->mixw, B * N * f},
-            {b->logmix, src->logmix, B * N * f}, {b->logl, src->logl, B * N * f}, {b->logp, src->logp, B * N * f},
-            {b->eta, src->eta, B * N * f}, {b->a_mix, src->a_mix, B * N * f}, {b->pw, src->pw, B * N * f},
-            {b->costs, src->costs, B * S * N * f}, {b->a_seq_out, src->a_seq_out, B * D * f}, {b->alias, src->alias, B * sizeof(int)},
-            {b->ctr, src->ctr, B * 4 * sizeof(uint32_t)}, {b->seeds, src->seeds, B * sizeof(uint64_t)},
-            {b->opt_s[0], src->opt_s[0], B * N * D * f}, {b->opt_s[1], src->opt_s[1], B * N * D * f}, {b->opt_s[2], src->opt_s[2], B * N * D * f}};
-  for (auto &e : cp)
-    if (st == DUST_OK && e.dst && e.s) st = d2d(inner, e.dst, e.s, e.bytes);
-  if (st == DUST_OK && src->acts_kept) st = d2d(inner, b->acts, src->acts, B * S * N * D * f);
-  if (st == DUST_OK && !src->hyper.empty()) {  // the per-environment rows travel with the batch
-    st = b->hyper_dev.alloc(B);
-    if (st == DUST_OK) st = d2d(inner, b->hyper_dev, src->hyper_dev, B * sizeof(SvbHyper));
-    if (st == DUST_OK) b->hyper = src->hyper;
-  }
-  if (st == DUST_OK) {
+  return batch_clone(src, out, svb_rows, [&](dust_svmpc_batch *b) -> int {
+    dust_ctx *inner = b->c;
+    const size_t B = (size_t)src->B, N = (size_t)inner->N, S = (size_t)inner->S, D = (size_t)inner->D, f = sizeof(float);
+    const BatchCopy cp[] = {{b->theta, src->theta, B * N * D * f}, {b->mu, src->mu, B * N * D * f}, {b->a_mat, src->a_mat, B * N * D * f},
+                            {b->score, src->score, B * N * D * f}, {b->phi, src->phi, B * N * D * f}, {b->mixw, src->mixw, B * N * f},
+                            {b->logmix, src->logmix, B * N * f}, {b->logl, src->logl, B * N * f}, {b->logp, src->logp, B * N * f},
+                            {b->eta, src->eta, B * N * f}, {b->a_mix, src->a_mix, B * N * f}, {b->pw, src->pw, B * N * f},
+                            {b->costs, src->costs, B * S * N * f}, {b->a_seq_out, src->a_seq_out, B * D * f}, {b->alias, src->alias, B * sizeof(int)},
+                            {b->ctr, src->ctr, B * 4 * sizeof(uint32_t)}, {b->seeds, src->seeds, B * sizeof(uint64_t)},
+                            {b->opt_s[0], src->opt_s[0], B * N * D * f}, {b->opt_s[1], src->opt_s[1], B * N * D * f}, {b->opt_s[2], src->opt_s[2], B * N * D * f}};
+    for (auto &e : cp)
+      if (e.dst && e.src) TRY(d2d(inner, e.dst, e.src, e.bytes));
+    if (src->acts_kept) TRY(d2d(inner, b->acts, src->acts, B * S * N * D * f));
+    if (!src->hyper.empty()) {  // the per-environment rows travel with the batch
+      TRY(b->hyper_dev.alloc(B));
+      TRY(d2d(inner, b->hyper_dev, src->hyper_dev, B * sizeof(SvbHyper)));
+      b->hyper = src->hyper;
+    }
     b->have_costs = src->have_costs;
     b->have_forward = src->have_forward;
     b->acts_kept = src->acts_kept;
-  }
-  if (st == DUST_OK && hipStreamSynchronize(inner->stream) != hipSuccess) st = fail(DUST_ERR_HIP, "hipStreamSynchronize failed");
-  if (st != DUST_OK) {
-    svb_free(b);
-    return st;
-  }
-  *out = b;
-  return DUST_OK;
+    return DUST_OK;
+  });
 }
 
-extern "C" int dust_svmpc_batch_ctx(dust_svmpc_batch *b, dust_ctx **out) {
-  if (!b || !out) return fail(DUST_ERR_INVALID, "null argument");
-  *out = b->c;
-  return DUST_OK;
-}
+extern "C" int dust_svmpc_batch_ctx(dust_svmpc_batch *b, dust_ctx **out) { return batch_ctx(b, out); }
 
 extern "C" int dust_svmpc_batch_set(dust_svmpc_batch *b, int what, const float *in) {
   if (!b || !in) return fail(DUST_ERR_INVALID, "null argument");
@@ -6029,27 +6082,15 @@ static int svb_episode_call(dust_svmpc_batch *b, const float *states, int n_peri
   if (!b) return fail(DUST_ERR_INVALID, "null batch");
   if (!states || !states_out || !actions_out) return fail(DUST_ERR_INVALID, "null argument");
   if (n_steps < 1) return fail(DUST_ERR_INVALID, "a tick has n_steps >= 1 (got %d)", n_steps);
-  if (n_periods < 1 || n_periods > 4096)
-    return fail(DUST_ERR_INVALID, "n_periods = %d outside [1, 4096] (one launch stays short on a shared device: split a longer episode)", n_periods);
+  TRY(episode_periods_check(n_periods, "one launch stays short on a shared device: split a longer episode"));
   if (flags != 0) return fail(DUST_ERR_UNSUPPORTED, "an episode draws its noise on the device and keeps no actions: flags must be 0 (got %d)", flags);
   dust_ctx *c = b->c;
-  if (c->cfg.dim_p == 0 && plant_params) return fail(DUST_ERR_INVALID, "plant parameter rows without uncertain parameters (dim_p = 0)");
-  const size_t T = (size_t)n_periods, B = (size_t)b->B, N = (size_t)c->N, M = (size_t)c->M, P = (size_t)c->cfg.dim_p;
-  const size_t ds = (size_t)c->ds, da = (size_t)c->da, D = (size_t)c->D;
+  TRY(episode_plant_check(c, plant_params));
+  const size_t T = (size_t)n_periods, B = (size_t)b->B, N = (size_t)c->N, M = (size_t)c->M, P = (size_t)c->cfg.dim_p, D = (size_t)c->D;
   bool forward = true;  // some period of the call runs forward()
   if (rules) {
     if (!costs_out || !loss || !status || !n_run) return fail(DUST_ERR_INVALID, "null argument");
-    if (rules->t0 < 0 || rules->warm_up < 0) return fail(DUST_ERR_INVALID, "t0 = %d, warm_up = %d: both are >= 0", rules->t0, rules->warm_up);
-    if (rules->t0 > 0x7fffffff - 4096) return fail(DUST_ERR_INVALID, "t0 = %d: the episode's period index does not fit", rules->t0);
-    bool finite = std::isfinite(rules->goal_radius);
-    for (size_t k = 0; k < ds; ++k) finite = finite && std::isfinite(rules->goal[k]);
-    if (!finite) return fail(DUST_ERR_INVALID, "the goal and its radius must be finite");
-    for (size_t e = 0; e < B; ++e)
-      if ((!active || active[e]) && (status[e] < 0 || status[e] > 2))
-        return fail(DUST_ERR_INVALID, "status[%zu] = %d: 0 (running), 1 (goal) or 2 (crash)", e, status[e]);
-    const bool have_map = (c->cfg.model == DUST_MODEL_PARTICLE && c->cfg.with_obstacle && c->grid_bits) || skid_nav_on(c);
-    if (rules->stop_on_crash && !have_map)
-      return fail(DUST_ERR_UNSUPPORTED, "stop_on_crash needs an occupancy map: Particle with_obstacle, or the skid-steer navigation cost");
+    TRY(rules_check(c, rules, B, active, status, false, false));
     forward = rules->t0 + n_periods > rules->warm_up;
   }
   TRY(svb_call_check(b, states, n_steps, params, false, 0, forward));
@@ -6060,32 +6101,23 @@ static int svb_episode_call(dust_svmpc_batch *b, const float *states, int n_peri
     TRY(h2d(c, b->plant, plant_params, B * P * sizeof(float)));
   }
   // the records, then (rules) the cost rows and the words [B] loss, [B] status, [B] n_run
-  const size_t n_pw = pw_out ? T * B * N : 0, n_cost = rules ? T * B : 0, n_rec = T * B * (ds + da) + n_pw + n_cost + (rules ? 3 * B : 0);
+  EpisodeRecords lay(T, B);
+  const RecSection sec_s = lay.add((size_t)c->ds), sec_a = lay.add((size_t)c->da), sec_pw = lay.add(N, pw_out != nullptr), sec_c = lay.add(1, rules != nullptr);
+  const size_t words = lay.words(rules != nullptr), n_rec = lay.total();
   TRY(b->rec.ensure(n_rec));
   SvbEpisode ep;
   ep.T = n_periods;
   ep.plant = plant_params ? b->plant : nullptr;
-  ep.states_out = b->rec;
-  ep.actions_out = ep.states_out + T * B * ds;
-  ep.pw_out = pw_out ? ep.actions_out + T * B * da : nullptr;
+  ep.states_out = sec_s.at(b->rec, 0);
+  ep.actions_out = sec_a.at(b->rec, 0);
+  ep.pw_out = sec_pw.at(b->rec, 0);
   SvbRules ru;
   memset(&ru, 0, sizeof ru);
-  const size_t words = T * B * (ds + da) + n_pw + n_cost;  // where loss, status and n_run lie in the records
   if (rules) {
     ru.t0 = rules->t0;
     ru.warm_up = rules->warm_up;
-    ru.stop_on_crash = rules->stop_on_crash ? 1 : 0;
-    ru.goal_on = rules->goal_radius > 0.f ? 1 : 0;
-    ru.r2 = (float)((double)rules->goal_radius * (double)rules->goal_radius);
-    for (int k = 0; k < 8; ++k) ru.goal[k] = (size_t)k < ds ? rules->goal[k] : 0.f;
-    ru.costs_out = ep.actions_out + T * B * da + n_pw;
-    ru.loss = b->rec + words;
-    ru.status = reinterpret_cast<int *>(ru.loss + B);
-    ru.n_run = ru.status + B;
-    std::vector<float> in(3 * B, 0.f);  // (n_run starts at 0: an environment that enters stopped has run no period)
-    memcpy(in.data(), loss, B * sizeof(float));
-    memcpy(in.data() + B, status, B * sizeof(int));
-    TRY(h2d(c, ru.loss, in.data(), 3 * B * sizeof(float)));
+    rules_fill(ru, rules, c->ds, sec_c.at(b->rec, 0), b->rec + words, B);
+    TRY(h2d(c, ru.loss, rules_words_in(loss, status, B).data(), 3 * B * sizeof(float)));
   }
   TRY(svb_go(b, states, n_steps, nullptr, params ? b->params : nullptr, 0, active, forward, nullptr, &ep, rules ? &ru : nullptr));
   // the records come back once; the rows of inactive environments stay out of the caller's arrays
@@ -6094,32 +6126,16 @@ static int svb_episode_call(dust_svmpc_batch *b, const float *states, int n_peri
   if (a_seq && rules) HIP_TRY(hipMemcpyAsync(seq.data(), b->a_seq_out, B * D * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   else TRY(svb_outputs_copy(b, active, a_seq, nullptr));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  const int *ran = rules ? reinterpret_cast<const int *>(host.data() + words + 2 * B) : nullptr;
-  // rows [first, n_run[e]) of an active environment's record (no rules: all T of them)
-  auto rows = [&](float *dst, const float *src, size_t row, size_t first) {
-    if (!active && !ran) {
-      memcpy(dst, src, T * B * row * sizeof(float));
-      return;
-    }
-    for (size_t e = 0; e < B; ++e) {
-      if (active && !active[e]) continue;
-      for (size_t t = first; t < (ran ? (size_t)ran[e] : T); ++t) memcpy(dst + (t * B + e) * row, src + (t * B + e) * row, row * sizeof(float));
-    }
-  };
-  const size_t warm = rules ? (size_t)std::max(0, rules->warm_up - rules->t0) : 0;  // periods without forward(): no particle weights
-  rows(states_out, host.data(), ds, 0);
-  rows(actions_out, host.data() + T * B * ds, da, 0);
-  if (pw_out) rows(pw_out, host.data() + T * B * (ds + da), N, warm);
+  const std::vector<int> ran_v = rules ? rules_ran(host.data() + words, B) : std::vector<int>();
+  const int *ran = rules ? ran_v.data() : nullptr;
+  const size_t warm = rules_warm(rules);
+  records_scatter(states_out, host.data(), sec_s, active, ran);
+  records_scatter(actions_out, host.data(), sec_a, active, ran);
+  if (pw_out) records_scatter(pw_out, host.data(), sec_pw, active, ran, warm);
   if (rules) {
-    rows(costs_out, host.data() + T * B * (ds + da) + n_pw, 1, 0);
-    for (size_t e = 0; e < B; ++e) {
-      if (active && !active[e]) continue;
-      n_run[e] = ran[e];
-      if (ran[e] == 0) continue;  // (entered with status != 0: nothing of it was written)
-      memcpy(loss + e, host.data() + words + e, sizeof(float));
-      memcpy(status + e, host.data() + words + B + e, sizeof(int));
-      if (a_seq && (size_t)ran[e] > warm) memcpy(a_seq + e * D, seq.data() + e * D, D * sizeof(float));
-    }
+    records_scatter(costs_out, host.data(), sec_c, active, ran);
+    rules_words_out(host.data() + words, B, active, ran, loss, status, n_run);
+    if (a_seq) env_rows_out(a_seq, seq.data(), B, D, active, ran, warm);
   }
   return DUST_OK;
 }
@@ -6143,11 +6159,7 @@ extern "C" int dust_svmpc_batch_simulate(dust_svmpc_batch *b, const float *state
 
 // ---------------------------------------------------------------------------------------------------------------
 // MultiDISCO over a batch of plants: forward, step or both of B controllers in one launch, and closed-loop episodes (disco_batch.hpp).
-// The batch owns a private clone of the prototype context - model, cost, map, sigma weights, stream, profile counters - and every
-// environment's device rows; per-call inputs travel as the other controller batches' do (BatchInputs).
-struct dust_disco_batch {
-  dust_ctx *c;
-  int B;
+struct dust_disco_batch : BatchCore {
   DevBuf<float> a_mat;            // [B][N][D]
   DevBuf<float> a_seq, ext;       // [B][D]
   DevBuf<float> a_mix, eta;       // [B][N]
@@ -6155,12 +6167,8 @@ struct dust_disco_batch {
   DevBuf<float> acts;             // [B][S][N][D]
   DevBuf<float> next;             // [B][H][da]
   DevBuf<int> alias;              // [B] (svb_begin reads it)
-  DevBuf<uint32_t> ctr;           // [B][4]
-  DevBuf<uint64_t> seeds;         // [B]
-  DevBuf<float> rec_acts, params; // staged inputs of a call
-  DevBuf<float> plant, rec;       // dust_disco_batch_episode: [B][P] true parameter rows; the records
-  BatchInputs in;
-  bool have_forward, acts_kept;
+  DevBuf<float> rec_acts;         // the recorded actions a call has staged
+  bool have_forward = false, acts_kept = false;
 };
 
 // the box of disco_batch.hpp: svb_check's without its a_reg = 0 and Stein-kernel conditions, plus the sigma-point corner
@@ -6196,25 +6204,9 @@ static int dcb_check(const dust_ctx *c) {
   return DUST_OK;
 }
 
-static void dcb_free(dust_disco_batch *b) {
-  if (!b) return;
-  if (b->c) {
-    (void)hipSetDevice(b->c->cfg.device);
-    (void)hipStreamSynchronize(b->c->stream);
-  }
+static int dcb_rows(dust_disco_batch *b) {
   dust_ctx *inner = b->c;
-  delete b;  // the batch's own rows first, then the context they were allocated beside
-  if (inner) dust_destroy(inner);
-}
-
-// the batch around an inner context it takes over: buffers allocated, nothing filled yet
-static int dcb_alloc(dust_ctx *inner, int n_env, dust_disco_batch **out) {
-  dust_disco_batch *b = new dust_disco_batch();
-  b->c = inner;
-  b->B = n_env;
-  *out = b;
-  const size_t B = (size_t)n_env, N = (size_t)inner->N, S = (size_t)inner->S, D = (size_t)inner->D;
-  HIP_TRY(hipSetDevice(inner->cfg.device));
+  const size_t B = (size_t)b->B, N = (size_t)inner->N, S = (size_t)inner->S, D = (size_t)inner->D;
   TRY(b->a_mat.alloc(B * N * D));
   DevBuf<float> *bd[] = {&b->a_seq, &b->ext, &b->next};
   for (auto p : bd) TRY(p->alloc(B * D));
@@ -6228,72 +6220,39 @@ static int dcb_alloc(dust_ctx *inner, int n_env, dust_disco_batch **out) {
   TRY(b->seeds.alloc(B));
   HIP_TRY(hipMemsetAsync(b->alias, 0, B * sizeof(int), inner->stream));
   HIP_TRY(hipMemsetAsync(b->eta, 0, B * N * sizeof(float), inner->stream));
-  return b->in.alloc(n_env);
+  return DUST_OK;
 }
 
 extern "C" int dust_disco_batch_create(const dust_ctx *proto, int n_env, const uint64_t *seeds, dust_disco_batch **out) {
-  if (!proto || !out) return fail(DUST_ERR_INVALID, "null argument");
-  *out = nullptr;
-  TRY(dcb_check(proto));
-  TRY(batch_n_env_check(n_env, "one workgroup per environment"));
-  dust_ctx *inner = nullptr;
-  TRY(dust_clone(proto, &inner));  // (settles and waits for the prototype's stream)
-  dust_disco_batch *b = nullptr;
-  int st = dcb_alloc(inner, n_env, &b);
-  if (st == DUST_OK) {
+  return batch_create(proto, n_env, out, dcb_check, "one workgroup per environment", dcb_rows, [&](dust_disco_batch *b) -> int {
+    dust_ctx *inner = b->c;
     const size_t B = (size_t)n_env, N = (size_t)inner->N, D = (size_t)inner->D;
-    st = spread(inner, B, b->a_mat, inner->a_mat, N * D * sizeof(float));
-    if (st == DUST_OK) st = spread(inner, B, b->a_seq, inner->a_seq, D * sizeof(float));
-    if (st == DUST_OK) st = spread(inner, B, b->a_mix, inner->a_mix, N * sizeof(float));  // (ones until a forward: disco.py:108)
-    if (st == DUST_OK) st = spread(inner, B, b->ctr, inner->ctr_dev, 4 * sizeof(uint32_t));
-    if (st == DUST_OK) st = batch_seeds_set(inner, B, seeds, b->seeds);
-  }
-  if (st != DUST_OK) {
-    dcb_free(b);
-    return st;
-  }
-  *out = b;
-  return DUST_OK;
+    TRY(spread(inner, B, b->a_mat, inner->a_mat, N * D * sizeof(float)));
+    TRY(spread(inner, B, b->a_seq, inner->a_seq, D * sizeof(float)));
+    TRY(spread(inner, B, b->a_mix, inner->a_mix, N * sizeof(float)));  // (ones until a forward: disco.py:108)
+    TRY(spread(inner, B, b->ctr, inner->ctr_dev, 4 * sizeof(uint32_t)));
+    return batch_seeds_set(inner, B, seeds, b->seeds);
+  });
 }
 
-extern "C" void dust_disco_batch_destroy(dust_disco_batch *b) { dcb_free(b); }
+extern "C" void dust_disco_batch_destroy(dust_disco_batch *b) { batch_free(b); }
 
 extern "C" int dust_disco_batch_clone(const dust_disco_batch *src, dust_disco_batch **out) {
-  if (!src || !out) return fail(DUST_ERR_INVALID, "null argument");
-  *out = nullptr;
-  dust_ctx *inner = nullptr;
-  TRY(dust_clone(src->c, &inner));  // (waits for the source's stream)
-  dust_disco_batch *b = nullptr;
-  int st = dcb_alloc(inner, src->B, &b);
-  const size_t B = (size_t)src->B, N = (size_t)inner->N, S = (size_t)inner->S, D = (size_t)inner->D, f = sizeof(float);
-  struct {
-    void *dst;
-    const void *s;
-    size_t bytes;
-  } cp[] = {{b->a_mat, src->a_mat, B * N * D * f}, {b->a_seq, src->a_seq, B * D * f},   {b->a_mix, src->a_mix, B * N * f},
-            {b->eta, src->eta, B * N * f},         {b->costs, src->costs, B * S * N * f}, {b->omg, src->omg, B * S * N * f},
-            {b->wts, src->wts, B * S * N * f},     {b->ctr, src->ctr, B * 4 * sizeof(uint32_t)}, {b->seeds, src->seeds, B * sizeof(uint64_t)}};
-  for (auto &e : cp)
-    if (st == DUST_OK) st = d2d(inner, e.dst, e.s, e.bytes);
-  if (st == DUST_OK && src->acts_kept) st = d2d(inner, b->acts, src->acts, B * S * N * D * f);
-  if (st == DUST_OK) {
+  return batch_clone(src, out, dcb_rows, [&](dust_disco_batch *b) -> int {
+    dust_ctx *inner = b->c;
+    const size_t B = (size_t)src->B, N = (size_t)inner->N, S = (size_t)inner->S, D = (size_t)inner->D, f = sizeof(float);
+    const BatchCopy cp[] = {{b->a_mat, src->a_mat, B * N * D * f}, {b->a_seq, src->a_seq, B * D * f},   {b->a_mix, src->a_mix, B * N * f},
+                            {b->eta, src->eta, B * N * f},         {b->costs, src->costs, B * S * N * f}, {b->omg, src->omg, B * S * N * f},
+                            {b->wts, src->wts, B * S * N * f},     {b->ctr, src->ctr, B * 4 * sizeof(uint32_t)}, {b->seeds, src->seeds, B * sizeof(uint64_t)}};
+    for (auto &e : cp) TRY(d2d(inner, e.dst, e.src, e.bytes));
+    if (src->acts_kept) TRY(d2d(inner, b->acts, src->acts, B * S * N * D * f));
     b->have_forward = src->have_forward;
     b->acts_kept = src->acts_kept;
-  }
-  if (st == DUST_OK && hipStreamSynchronize(inner->stream) != hipSuccess) st = fail(DUST_ERR_HIP, "hipStreamSynchronize failed");
-  if (st != DUST_OK) {
-    dcb_free(b);
-    return st;
-  }
-  *out = b;
-  return DUST_OK;
+    return DUST_OK;
+  });
 }
 
-extern "C" int dust_disco_batch_ctx(dust_disco_batch *b, dust_ctx **out) {
-  if (!b || !out) return fail(DUST_ERR_INVALID, "null argument");
-  *out = b->c;
-  return DUST_OK;
-}
+extern "C" int dust_disco_batch_ctx(dust_disco_batch *b, dust_ctx **out) { return batch_ctx(b, out); }
 
 extern "C" int dust_disco_batch_set(dust_disco_batch *b, int what, const float *in) {
   if (!b || !in) return fail(DUST_ERR_INVALID, "null argument");
@@ -6496,28 +6455,15 @@ extern "C" int dust_disco_batch_episode(dust_disco_batch *b, const float *states
                                         float *actions_out, float *costs_out, float *loss, int *status, int *n_run, float *a_seq) {
   if (!b) return fail(DUST_ERR_INVALID, "null batch");
   if (!states || !states_out || !actions_out) return fail(DUST_ERR_INVALID, "null argument");
-  if (n_periods < 1 || n_periods > 4096)
-    return fail(DUST_ERR_INVALID, "n_periods = %d outside [1, 4096] (one launch stays short on a shared device: split a longer episode)", n_periods);
+  TRY(episode_periods_check(n_periods, "one launch stays short on a shared device: split a longer episode"));
   dust_ctx *c = b->c;
   TRY(dcb_call_check(b, true, states, params, flags, DUST_DISCO_PARAMS_ONCE, true, strategy, 1, nullptr, nullptr, true));
-  if (c->cfg.dim_p == 0 && plant_params) return fail(DUST_ERR_INVALID, "plant parameter rows without uncertain parameters (dim_p = 0)");
-  const size_t T = (size_t)n_periods, B = (size_t)b->B, M = (size_t)c->M, P = (size_t)c->cfg.dim_p;
-  const size_t ds = (size_t)c->ds, da = (size_t)c->da, D = (size_t)c->D;
+  TRY(episode_plant_check(c, plant_params));
+  const size_t T = (size_t)n_periods, B = (size_t)b->B, M = (size_t)c->M, P = (size_t)c->cfg.dim_p, D = (size_t)c->D;
   const bool once = (flags & DUST_DISCO_PARAMS_ONCE) != 0;
   if (rules) {
     if (!costs_out || !loss || !status || !n_run) return fail(DUST_ERR_INVALID, "null argument");
-    if (rules->warm_up != 0) return fail(DUST_ERR_INVALID, "warm_up = %d: the MultiDISCO branch of the reference's loops has no warm-up", rules->warm_up);
-    if (rules->t0 < 0) return fail(DUST_ERR_INVALID, "t0 = %d: >= 0", rules->t0);
-    if (rules->t0 > 0x7fffffff - 4096) return fail(DUST_ERR_INVALID, "t0 = %d: the episode's period index does not fit", rules->t0);
-    bool finite = std::isfinite(rules->goal_radius);
-    for (size_t k = 0; k < ds; ++k) finite = finite && std::isfinite(rules->goal[k]);
-    if (!finite) return fail(DUST_ERR_INVALID, "the goal and its radius must be finite");
-    for (size_t e = 0; e < B; ++e)
-      if ((!active || active[e]) && (status[e] < 0 || status[e] > 2))
-        return fail(DUST_ERR_INVALID, "status[%zu] = %d: 0 (running), 1 (goal) or 2 (crash)", e, status[e]);
-    const bool have_map = (c->cfg.model == DUST_MODEL_PARTICLE && c->cfg.with_obstacle && c->grid_bits) || skid_nav_on(c);
-    if (rules->stop_on_crash && !have_map)
-      return fail(DUST_ERR_UNSUPPORTED, "stop_on_crash needs an occupancy map: Particle with_obstacle, or the skid-steer navigation cost");
+    TRY(rules_check(c, rules, B, active, status, true, false));
   }
   HIP_TRY(hipSetDevice(c->cfg.device));
   if (params) {
@@ -6530,32 +6476,23 @@ extern "C" int dust_disco_batch_episode(dust_disco_batch *b, const float *states
     TRY(h2d(c, b->plant, plant_params, B * P * sizeof(float)));
   }
   // the records, then (rules) the cost rows and the words [B] loss, [B] status, [B] n_run
-  const size_t n_cost = rules ? T * B : 0, words = T * B * (ds + da) + n_cost, n_rec = words + (rules ? 3 * B : 0);
+  EpisodeRecords lay(T, B);
+  const RecSection sec_s = lay.add((size_t)c->ds), sec_a = lay.add((size_t)c->da), sec_c = lay.add(1, rules != nullptr);
+  const size_t words = lay.words(rules != nullptr), n_rec = lay.total();
   TRY(b->rec.ensure(n_rec));
   DiscoEpisodeArgs ke;
   memset(&ke, 0, sizeof ke);
   ke.ep.T = n_periods;
   ke.ep.plant = plant_params ? b->plant.get() : nullptr;
-  ke.ep.states_out = b->rec;
-  ke.ep.actions_out = ke.ep.states_out + T * B * ds;
+  ke.ep.states_out = sec_s.at(b->rec, 0);
+  ke.ep.actions_out = sec_a.at(b->rec, 0);
   ke.ep.pw_out = nullptr;
   ke.has_rules = rules ? 1 : 0;
   ke.params_once = once ? 1 : 0;
   if (rules) {
-    SvbRules &ru = ke.ru;
     // (t0 and warm_up stay 0 in SvbRules: disco_episode_body reads neither - without a warm-up no period depends on its index)
-    ru.stop_on_crash = rules->stop_on_crash ? 1 : 0;
-    ru.goal_on = rules->goal_radius > 0.f ? 1 : 0;
-    ru.r2 = (float)((double)rules->goal_radius * (double)rules->goal_radius);
-    for (int k = 0; k < 8; ++k) ru.goal[k] = (size_t)k < ds ? rules->goal[k] : 0.f;
-    ru.costs_out = ke.ep.actions_out + T * B * da;
-    ru.loss = b->rec + words;
-    ru.status = reinterpret_cast<int *>(ru.loss + B);
-    ru.n_run = ru.status + B;
-    std::vector<float> in(3 * B, 0.f);  // (n_run starts at 0: an environment that enters stopped has run no period)
-    memcpy(in.data(), loss, B * sizeof(float));
-    memcpy(in.data() + B, status, B * sizeof(int));
-    TRY(h2d(c, ru.loss, in.data(), 3 * B * sizeof(float)));
+    rules_fill(ke.ru, rules, c->ds, sec_c.at(b->rec, 0), b->rec + words, B);
+    TRY(h2d(c, ke.ru.loss, rules_words_in(loss, status, B).data(), 3 * B * sizeof(float)));
   }
   DiscoBatchArgs d;
   dcb_args(b, nullptr, params ? b->params.get() : nullptr, active, 0, true, true, strategy, 1, false, d);
@@ -6568,27 +6505,15 @@ extern "C" int dust_disco_batch_episode(dust_disco_batch *b, const float *states
   HIP_TRY(hipMemcpyAsync(host.data(), b->rec, n_rec * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   if (a_seq) HIP_TRY(hipMemcpyAsync(seq.data(), b->a_seq, B * D * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  const int *ran = rules ? reinterpret_cast<const int *>(host.data() + words + 2 * B) : nullptr;
-  // rows [0, n_run[e]) of an active environment's record (no rules: all T of them)
-  auto rows = [&](float *dst, const float *src, size_t row) {
-    for (size_t e = 0; e < B; ++e) {
-      if (active && !active[e]) continue;
-      for (size_t t = 0; t < (ran ? (size_t)ran[e] : T); ++t) memcpy(dst + (t * B + e) * row, src + (t * B + e) * row, row * sizeof(float));
-    }
-  };
-  rows(states_out, host.data(), ds);
-  rows(actions_out, host.data() + T * B * ds, da);
-  if (rules) rows(costs_out, host.data() + T * B * (ds + da), 1);
-  for (size_t e = 0; e < B; ++e) {
-    if (active && !active[e]) continue;
-    if (rules) {
-      n_run[e] = ran[e];
-      if (ran[e] == 0) continue;  // (entered with status != 0: nothing of it was written)
-      memcpy(loss + e, host.data() + words + e, sizeof(float));
-      memcpy(status + e, host.data() + words + B + e, sizeof(int));
-    }
-    if (a_seq) memcpy(a_seq + e * D, seq.data() + e * D, D * sizeof(float));
+  const std::vector<int> ran_v = rules ? rules_ran(host.data() + words, B) : std::vector<int>();
+  const int *ran = rules ? ran_v.data() : nullptr;
+  records_scatter(states_out, host.data(), sec_s, active, ran);
+  records_scatter(actions_out, host.data(), sec_a, active, ran);
+  if (rules) {
+    records_scatter(costs_out, host.data(), sec_c, active, ran);
+    rules_words_out(host.data() + words, B, active, ran, loss, status, n_run);
   }
+  if (a_seq) env_rows_out(a_seq, seq.data(), B, D, active, ran);
   return DUST_OK;
 }
 

@@ -2566,6 +2566,56 @@ static void dual_episode_commit(dust_mpf_batch *mb, MpfbRows &rows, const std::v
   mpfb_commit(mb, rows);
 }
 
+// What the two dual episodes stage for their filters, once per call, through the filter batch's pinned block: the MpfEnvIn rows as period
+// 0's update reads them (or, without one, as they stand), the seeds [T][B], the plant rows [B][P] - and what they read back of it
+struct DualEpisodeStage {
+  dust_mpf_batch *mb;
+  size_t T, B, off_seeds, off_plant, n_stage;
+  bool first;  // period 0 has an update
+  MpfbRows rows;
+  std::vector<dust::MpfEnvIn> in_host;
+  DualEpisodeStage(dust_mpf_batch *filters, size_t periods, size_t n_env, size_t P, bool has_first)
+      : mb(filters), T(periods), B(n_env), off_seeds(n_env * sizeof(dust::MpfEnvIn)), off_plant(off_seeds + periods * n_env * sizeof(uint64_t)),
+        n_stage(off_plant + n_env * P * sizeof(float)), first(has_first), in_host(n_env) {}
+  // room (reallocations free behind the device's queued work)
+  int room(int mpf_steps) {
+    TRY(mpfb_gn_room(mb, mpf_steps));
+    TRY(mb->ep.ensure(n_stage));
+    if (mb->ep_host.cap() < n_stage) TRY(mb->ep_host.alloc(n_stage, hipHostMallocDefault));
+    return DUST_OK;
+  }
+  // the rows of the environments of `on`, seeds and plants -> the device in one copy on the controller's stream, behind the filters' last work
+  int stage(const dust_ctx *c, const float *states, const float *actions_prev, int mpf_steps, const unsigned char *on, const uint64_t *prior_seeds,
+            const float *plant_params) {
+    unsigned char *hb = mb->ep_host;  // (free: every call that wrote it has waited for its stream)
+    mpfb_rows(mb, actions_prev, first ? states : nullptr, first ? mpf_steps : 0, on, hb, rows);
+    memcpy(hb + off_seeds, prior_seeds, off_plant - off_seeds);
+    if (plant_params) memcpy(hb + off_plant, plant_params, n_stage - off_plant);
+    HIP_TRY(hipStreamWaitEvent(c->stream, mb->ev_ext, 0));
+    HIP_TRY(hipMemcpyAsync(mb->ep, hb, plant_params ? n_stage : off_plant, hipMemcpyHostToDevice, c->stream));
+    return DUST_OK;
+  }
+  dust::MpfEnvIn *in_dev() const { return mpfb_in_view(mb->ep.get()); }
+  const uint64_t *seeds_dev(size_t t) const { return reinterpret_cast<const uint64_t *>(mb->ep.get() + off_seeds) + t * B; }
+  const float *plant_dev(const float *plant_params) const { return plant_params ? reinterpret_cast<const float *>(mb->ep.get() + off_plant) : nullptr; }
+  // behind the periods: the records and the advanced rows come back, ...
+  int read_back(const dust_ctx *c, std::vector<float> &host, const float *rec) {
+    HIP_TRY(hipMemcpyAsync(host.data(), rec, host.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(in_host.data(), in_dev(), B * sizeof(dust::MpfEnvIn), hipMemcpyDeviceToHost, c->stream));
+    return DUST_OK;
+  }
+  // ... the call waits once (the filters' own stream waits for ev_ext before it touches the rows again), ...
+  int wait(const dust_ctx *c) {
+    HIP_TRY(hipEventRecord(mb->ev_ext, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return DUST_OK;
+  }
+  // ... and the filters' host rows move to where the periods left them
+  void commit(float mpf_bw, const unsigned char *on, float *bw_out, const int *ran = nullptr) {
+    dual_episode_commit(mb, rows, in_host, T, first, !(mpf_bw > 0.f), mpf_bw, on, bw_out, ran);
+  }
+};
+
 // T control periods of the DuSt-MPC loop (simulations.py:104-138) for B environments in one call: T successive dust_svmpc_dual_batch_tick
 // calls with device-drawn noise, and between them the plant of dust_svmpc_batch_episode - x_{t+1} = step(x_t, a_t) under the true rows
 // plant_params - stepped on the device.  Everything is staged once (states and mask through the controller batch's pinned slot; the
@@ -2591,26 +2641,16 @@ static int svb_dual_episode_call(dust_svmpc_batch *b, dust_mpf_batch *mb, const 
   if (!b || !mb || !states || !states_out || !actions_out) return fail(DUST_ERR_INVALID, "null argument");
   if (rules && (!loss || !status || !n_run || !costs_out)) return fail(DUST_ERR_INVALID, "null argument: loss, status, n_run and costs_out are required");
   if (!prior_seeds) return fail(DUST_ERR_INVALID, "null argument: the draws from the filters' priors need prior_seeds [T][B]");
-  if (n_periods < 1 || n_periods > 4096)
-    return fail(DUST_ERR_INVALID, "n_periods = %d outside [1, 4096] (the queue of one call stays short on a shared device: chain a longer episode)", n_periods);
+  TRY(episode_periods_check(n_periods, "the queue of one call stays short on a shared device: chain a longer episode"));
   if (n_steps < 1 || mpf_steps < 0) return fail(DUST_ERR_INVALID, "bad step counts");
   if (flags != 0) return fail(DUST_ERR_UNSUPPORTED, "a dual episode draws its noise on the device and keeps no actions: flags must be 0 (got %d)", flags);
   dust_ctx *c = b->c;
   dust_mpf *m = mb->m;
-  if (c->cfg.dim_p == 0 && plant_params) return fail(DUST_ERR_INVALID, "plant parameter rows without uncertain parameters (dim_p = 0)");
-  const size_t T = (size_t)n_periods, B = (size_t)b->B, N = (size_t)c->N, P = (size_t)c->cfg.dim_p, ds = (size_t)c->ds, da = (size_t)c->da, D = (size_t)c->D;
+  TRY(episode_plant_check(c, plant_params));
+  const size_t T = (size_t)n_periods, B = (size_t)b->B, N = (size_t)c->N, P = (size_t)c->cfg.dim_p, D = (size_t)c->D;
   bool forward = true;  // some period of the call runs forward()
   if (rules) {
-    if (rules->t0 < 0 || rules->warm_up < 0) return fail(DUST_ERR_INVALID, "t0 = %d, warm_up = %d: both are >= 0", rules->t0, rules->warm_up);
-    if (rules->t0 > 0x7fffffff - 4096) return fail(DUST_ERR_INVALID, "t0 = %d: the episode's period index does not fit", rules->t0);
-    bool finite = std::isfinite(rules->goal_radius);
-    for (size_t k = 0; k < ds && k < 8; ++k) finite = finite && std::isfinite(rules->goal[k]);
-    if (!finite) return fail(DUST_ERR_INVALID, "the goal and its radius must be finite");
-    for (size_t e = 0; e < B; ++e)
-      if ((!active || active[e]) && (status[e] < 0 || status[e] > 2))
-        return fail(DUST_ERR_INVALID, "status[%zu] = %d: 0 (running), 1 (goal) or 2 (crash)", e, status[e]);
-    if (rules->stop_on_crash && !(c->cfg.model == DUST_MODEL_PARTICLE && c->cfg.with_obstacle && c->grid_bits))
-      return fail(DUST_ERR_UNSUPPORTED, "stop_on_crash needs an occupancy map: Particle with_obstacle");
+    TRY(rules_check(c, rules, B, active, status, false, true));
     forward = rules->t0 + n_periods > rules->warm_up;
   }
   TRY(svb_call_check(b, states, n_steps, nullptr, true, 0, forward));
@@ -2630,71 +2670,51 @@ static int svb_dual_episode_call(dust_svmpc_batch *b, dust_mpf_batch *mb, const 
   std::vector<unsigned char> run(rules ? B : 0);
   for (size_t e = 0; e < run.size(); ++e) run[e] = ((!active || active[e]) && status[e] == 0) ? 1 : 0;
   const unsigned char *on = rules ? run.data() : active;
-  // ---- room (reallocations free behind the device's queued work)
-  const bool silverman = !(mpf_bw > 0.f);
-  TRY(mpfb_gn_room(mb, mpf_steps));
-  const size_t off_seeds = B * sizeof(dust::MpfEnvIn), off_plant = off_seeds + T * B * sizeof(uint64_t), n_stage = off_plant + B * P * sizeof(float);
-  TRY(mb->ep.ensure(n_stage));
-  if (mb->ep_host.cap() < n_stage) TRY(mb->ep_host.alloc(n_stage, hipHostMallocDefault));
-  const bool bw_dev = bw_out && silverman;
+  // ---- room
+  const bool bw_dev = bw_out && !(mpf_bw > 0.f);  // Silverman's bandwidths are the device's to record
+  DualEpisodeStage st(mb, T, B, P, first);
+  TRY(st.room(mpf_steps));
   // the records [T][B]: states | actions | weights | bandwidths | (rules) costs, then (rules) the words [B] loss | status | n_run
-  const size_t words = T * B * (ds + da + (pw_out ? N : 0) + (bw_dev ? 1 : 0) + (rules ? 1 : 0)), n_rec = words + (rules ? 3 * B : 0);
+  EpisodeRecords lay(T, B);
+  const RecSection sec_s = lay.add((size_t)c->ds), sec_a = lay.add((size_t)c->da), sec_pw = lay.add(N, pw_out != nullptr), sec_bw = lay.add(1, bw_dev),
+                   sec_c = lay.add(1, rules != nullptr);
+  const size_t words = lay.words(rules != nullptr), n_rec = lay.total();
   TRY(b->rec.ensure(n_rec));
-  // ---- staged once: states and mask; the filters' rows as period 0's update reads them (or, without one, as they stand), seeds, plants
+  // ---- staged once: states and mask; the filters' rows, seeds, plants
   TRY(b->in.stage(c, states, on));
-  unsigned char *hb = mb->ep_host;  // (free: every call that wrote it has waited for its stream)
-  MpfbRows rows;
-  mpfb_rows(mb, actions_prev, first ? states : nullptr, first ? mpf_steps : 0, on, hb, rows);
-  memcpy(hb + off_seeds, prior_seeds, T * B * sizeof(uint64_t));
-  if (plant_params) memcpy(hb + off_plant, plant_params, B * P * sizeof(float));
-  HIP_TRY(hipStreamWaitEvent(c->stream, mb->ev_ext, 0));
-  HIP_TRY(hipMemcpyAsync(mb->ep, hb, plant_params ? n_stage : off_plant, hipMemcpyHostToDevice, c->stream));
-  float *rec_s = b->rec, *rec_a = rec_s + T * B * ds, *rec_pw = rec_a + T * B * da, *rec_bw = rec_pw + (pw_out ? T * B * N : 0),
-        *rec_c = rec_bw + (bw_dev ? T * B : 0), *rec_w = b->rec + words;
-  if (rules) {
-    std::vector<float> in(3 * B, 0.f);  // (n_run starts at 0: an environment that enters stopped has run no period)
-    memcpy(in.data(), loss, B * sizeof(float));
-    memcpy(in.data() + B, status, B * sizeof(int));
-    TRY(h2d(c, rec_w, in.data(), 3 * B * sizeof(float)));
-  }
+  TRY(st.stage(c, states, actions_prev, mpf_steps, on, prior_seeds, plant_params));
+  if (rules) TRY(h2d(c, b->rec + words, rules_words_in(loss, status, B).data(), 3 * B * sizeof(float)));
   if (first || n_periods > 1) serve_cancel_device(m->cfg.device);  // (as mpfb_enqueue, once for the call)
   // ---- the periods
-  dust::MpfEnvIn *in_dev = mpfb_in_view(mb->ep.get());
-  const uint64_t *seeds_dev = reinterpret_cast<const uint64_t *>(mb->ep.get() + off_seeds);
+  dust::MpfEnvIn *in_dev = st.in_dev();
   const unsigned char *mask = b->in.mask_dev(on);
   SvmpcDualSimPeriodArgs ka;  // (its first three members are the plain period's arguments)
   svb_args(b, n_steps, nullptr, nullptr, on, true, ka.k);
   dual_batch_prior(mb, nullptr, ka.pr);
   memset(&ka.ds, 0, sizeof ka.ds);
   if (rules) {
-    ka.ds.stop_on_crash = rules->stop_on_crash ? 1 : 0;
-    ka.ds.goal_on = rules->goal_radius > 0.f ? 1 : 0;
-    ka.ds.r2 = (float)((double)rules->goal_radius * (double)rules->goal_radius);
-    for (size_t k = 0; k < 8; ++k) ka.ds.goal[k] = k < ds ? rules->goal[k] : 0.f;
-    ka.ds.loss = rec_w;
-    ka.ds.status = reinterpret_cast<int *>(rec_w + B);
-    ka.ds.n_run = ka.ds.status + B;
+    rules_fill(ka.ds, rules, c->ds, nullptr, b->rec + words, B);
     ka.ds.run = const_cast<unsigned char *>(mask);
   }
   const size_t lds = svmpc_batch_lds_bytes(c->N, c->D, c->M);
-  const size_t warm = rules ? (size_t)std::max(0, rules->warm_up - rules->t0) : 0;  // periods of this call without forward()
+  const size_t warm = rules_warm(rules);
   for (size_t t = 0; t < T; ++t) {
     const bool update = t > 0 || first;
     if (update) TRY(mpfb_update_launch(mb, c->stream, in_dev, mask, mpf_bw, mpf_steps));
     mb->n_calls++;
     ka.k.do_forward = t >= warm ? 1 : 0;
-    ka.pr.seeds = seeds_dev + t * B;
-    ka.dp.plant = plant_params ? reinterpret_cast<const float *>(mb->ep.get() + off_plant) : nullptr;
+    ka.pr.seeds = st.seeds_dev(t);
+    ka.dp.plant = st.plant_dev(plant_params);
     ka.dp.state = const_cast<float *>(b->in.states_dev());
     ka.dp.in = in_dev;
-    ka.dp.states_out = rec_s + t * B * ds;
-    ka.dp.actions_out = rec_a + t * B * da;
-    ka.dp.pw_out = pw_out && t >= warm ? rec_pw + t * B * N : nullptr;
+    ka.dp.states_out = sec_s.at(b->rec, t);
+    ka.dp.actions_out = sec_a.at(b->rec, t);
+    ka.dp.pw_out = t >= warm ? sec_pw.at(b->rec, t) : nullptr;
     ka.dp.bw = bw_dev && update ? mb->bw.get() : nullptr;
-    ka.dp.bw_out = bw_dev ? rec_bw + t * B : nullptr;
+    ka.dp.bw_out = sec_bw.at(b->rec, t);
     ka.dp.t0_add = update ? mpf_steps : 0;
     ka.dp.condition = t + 1 < T ? 1 : 0;
-    ka.ds.costs_out = rec_c + t * B;
+    ka.ds.costs_out = b->rec + sec_c.off + t * B;
     Prof pr(c, DUST_K_SVMPC_BATCH);
     const hipError_t launched = by_model(c, [&](auto M) -> hipError_t {
       if constexpr (M() == DUST_MODEL_PENDULUM || M() == DUST_MODEL_PARTICLE) {
@@ -2713,40 +2733,23 @@ static int svb_dual_episode_call(dust_svmpc_batch *b, dust_mpf_batch *mb, const 
   if (forward) b->have_forward = true;
   // ---- the records, the words and the advanced rows come back once; the rows of inactive environments stay out of the caller's arrays
   std::vector<float> host(n_rec), seq(a_seq && rules ? B * D : 0);
-  std::vector<dust::MpfEnvIn> in_host(B);
-  HIP_TRY(hipMemcpyAsync(host.data(), b->rec, n_rec * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(in_host.data(), in_dev, B * sizeof(dust::MpfEnvIn), hipMemcpyDeviceToHost, c->stream));
+  TRY(st.read_back(c, host, b->rec));
   if (a_seq && rules) HIP_TRY(hipMemcpyAsync(seq.data(), b->a_seq_out, B * D * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   else TRY(svb_outputs_copy(b, active, a_seq, nullptr));
-  HIP_TRY(hipEventRecord(mb->ev_ext, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  std::vector<int> ran(rules ? B : 0);  // (rules) the periods every environment ran: nothing of it is written past row ran[e] - 1
-  if (rules) memcpy(ran.data(), host.data() + words + 2 * B, B * sizeof(int));
-  for (size_t e = 0; e < ran.size(); ++e)
-    if (!run[e]) ran[e] = 0;
-  // rows [from, the periods it ran) of a participating environment's record
-  auto out = [&](float *dst, const float *dev, size_t row, size_t from) {
-    const float *src = host.data() + (dev - b->rec.get());
-    for (size_t e = 0; e < B; ++e)
-      for (size_t t = from; (!on || on[e]) && t < (rules ? (size_t)ran[e] : T); ++t)
-        memcpy(dst + (t * B + e) * row, src + (t * B + e) * row, row * sizeof(float));
-  };
-  out(states_out, rec_s, ds, 0);
-  out(actions_out, rec_a, da, 0);
-  if (pw_out) out(pw_out, rec_pw, N, warm);
-  if (bw_dev) out(bw_out, rec_bw, 1, 0);
+  TRY(st.wait(c));
+  // (rules) the periods every environment ran - none where it did not take part: nothing of it is written past row ran[e] - 1
+  const std::vector<int> ran_v = rules ? rules_ran(host.data() + words, B, run.data()) : std::vector<int>();
+  const int *ran = rules ? ran_v.data() : nullptr;
+  records_scatter(states_out, host.data(), sec_s, on, ran);
+  records_scatter(actions_out, host.data(), sec_a, on, ran);
+  if (pw_out) records_scatter(pw_out, host.data(), sec_pw, on, ran, warm);
+  if (bw_dev) records_scatter(bw_out, host.data(), sec_bw, on, ran);
   if (rules) {
-    out(costs_out, rec_c, 1, 0);
-    for (size_t e = 0; e < B; ++e) {
-      if (active && !active[e]) continue;
-      n_run[e] = ran[e];
-      if (ran[e] == 0) continue;  // (entered with status != 0: nothing else of it is written)
-      memcpy(loss + e, host.data() + words + e, sizeof(float));
-      memcpy(status + e, host.data() + words + B + e, sizeof(int));
-      if (a_seq && (size_t)ran[e] > warm) memcpy(a_seq + e * D, seq.data() + e * D, D * sizeof(float));
-    }
+    records_scatter(costs_out, host.data(), sec_c, on, ran);
+    rules_words_out(host.data() + words, B, active, ran, loss, status, n_run);
+    if (a_seq) env_rows_out(a_seq, seq.data(), B, D, active, ran, warm);
   }
-  dual_episode_commit(mb, rows, in_host, T, first, silverman, mpf_bw, on, bw_out, rules ? ran.data() : nullptr);
+  st.commit(mpf_bw, on, bw_out, ran);
   return DUST_OK;
 }
 
@@ -2783,8 +2786,7 @@ extern "C" int dust_amppi_dual_batch_episode(dust_amppi_batch *b, dust_mpf_batch
                                              float *bw_out, float *a_seq) {
   if (!b || !mb || !states || !states_out || !actions_out) return fail(DUST_ERR_INVALID, "null argument");
   if (!prior_seeds) return fail(DUST_ERR_INVALID, "null argument: the draws from the filters' priors need prior_seeds [T][B]");
-  if (n_periods < 1 || n_periods > 4096)
-    return fail(DUST_ERR_INVALID, "n_periods = %d outside [1, 4096] (the queue of one call stays short on a shared device: chain a longer episode)", n_periods);
+  TRY(episode_periods_check(n_periods, "the queue of one call stays short on a shared device: chain a longer episode"));
   if (mpf_steps < 0) return fail(DUST_ERR_INVALID, "bad step counts");
   if (roll_steps < 1) return fail(DUST_ERR_INVALID, "roll(steps = %d): steps >= 1", roll_steps);
   if (flags & ~DUST_AMPPI_PARAMS_SHARED)
@@ -2793,7 +2795,7 @@ extern "C" int dust_amppi_dual_batch_episode(dust_amppi_batch *b, dust_mpf_batch
   dust_ctx *c = b->c;
   dust_mpf *m = mb->m;
   TRY(amppi_check(c));
-  if (c->cfg.dim_p == 0 && plant_params) return fail(DUST_ERR_INVALID, "plant parameter rows without uncertain parameters (dim_p = 0)");
+  TRY(episode_plant_check(c, plant_params));
   TRY(dual_batch_pair_check(c, "AMPPI", b->B, mb));
   bool sigma, shared;
   TRY(amppi_dual_check(c, m, flags, &sigma, &shared));
@@ -2812,45 +2814,34 @@ extern "C" int dust_amppi_dual_batch_episode(dust_amppi_batch *b, dust_mpf_batch
   TRY(mpfb_limits(m, mb->B));
   const bool first = actions_prev != nullptr;  // period 0 has an update
   if (first || n_periods > 1) TRY(mpfb_update_check(mb, first ? actions_prev : states, states, mpf_steps, active));
-  const size_t T = (size_t)n_periods, B = (size_t)b->B, S = (size_t)c->S, D = (size_t)c->D, P = (size_t)m->P, ds = (size_t)c->ds, da = (size_t)c->da;
-  const bool silverman = !(mpf_bw > 0.f);
-  const bool bw_dev = bw_out && silverman;
-  const size_t n_rec = T * B * (ds + da + (costs_out ? S : 0) + (omega_out ? S : 0) + (bw_dev ? 1 : 0)) + (a_seq ? B * D : 0);
+  const size_t T = (size_t)n_periods, B = (size_t)b->B, S = (size_t)c->S, P = (size_t)m->P;
+  const bool bw_dev = bw_out && !(mpf_bw > 0.f);  // Silverman's bandwidths are the device's to record
+  const AmppiRecords lay(c, T, B, costs_out != nullptr, omega_out != nullptr, bw_dev, a_seq != nullptr);
+  const size_t n_rec = lay.n_rec;
   if (n_rec > DUST_AMPPI_EPISODE_MAX_FLOATS)
     return fail(DUST_ERR_UNSUPPORTED, "%zu record values for %d periods exceed %zu: split the episode into shorter calls (or leave costs / omega out)", n_rec,
                 n_periods, DUST_AMPPI_EPISODE_MAX_FLOATS);
   HIP_TRY(hipSetDevice(c->cfg.device));
   TRY(settle_pending(c));
-  // ---- room (reallocations free behind the device's queued work)
-  TRY(mpfb_gn_room(mb, mpf_steps));
-  const size_t off_seeds = B * sizeof(dust::MpfEnvIn), off_plant = off_seeds + T * B * sizeof(uint64_t), n_stage = off_plant + B * P * sizeof(float);
-  TRY(mb->ep.ensure(n_stage));
-  if (mb->ep_host.cap() < n_stage) TRY(mb->ep_host.alloc(n_stage, hipHostMallocDefault));
+  // ---- room
+  DualEpisodeStage st(mb, T, B, P, first);
+  TRY(st.room(mpf_steps));
   if (staged) TRY(b->params.ensure(B * prows * P));
   TRY(b->rec.ensure(n_rec));
   // ---- staged once
   TRY(b->in.stage(c, states, active));
-  unsigned char *hb = mb->ep_host;  // (free: every call that wrote it has waited for its stream)
-  MpfbRows rows;
-  mpfb_rows(mb, actions_prev, first ? states : nullptr, first ? mpf_steps : 0, active, hb, rows);
-  memcpy(hb + off_seeds, prior_seeds, T * B * sizeof(uint64_t));
-  if (plant_params) memcpy(hb + off_plant, plant_params, B * P * sizeof(float));
-  HIP_TRY(hipStreamWaitEvent(c->stream, mb->ev_ext, 0));
-  HIP_TRY(hipMemcpyAsync(mb->ep, hb, plant_params ? n_stage : off_plant, hipMemcpyHostToDevice, c->stream));
+  TRY(st.stage(c, states, actions_prev, mpf_steps, active, prior_seeds, plant_params));
   HIP_TRY(hipMemsetAsync(b->ticket, 0, B * sizeof(unsigned int), c->stream));
   if (first || n_periods > 1) serve_cancel_device(m->cfg.device);  // (as mpfb_enqueue, once for the call)
   // ---- the periods
-  dust::MpfEnvIn *in_dev = mpfb_in_view(mb->ep.get());
-  const uint64_t *seeds_dev = reinterpret_cast<const uint64_t *>(mb->ep.get() + off_seeds);
+  dust::MpfEnvIn *in_dev = st.in_dev();
   const unsigned char *mask = b->in.mask_dev(active);
   AmppiPriorPeriodArgs ka;
   batch_tick_args(b, mode, pts, prows, true, active, ka.k);
   dual_batch_prior(mb, nullptr, ka.pr);
   memset(&ka.ep, 0, sizeof ka.ep);
-  float *rec_s = b->rec, *rec_a = rec_s + T * B * ds, *rec_c = rec_a + T * B * da, *rec_o = rec_c + (costs_out ? T * B * S : 0);
-  float *rec_bw = rec_o + (omega_out ? T * B * S : 0), *rec_q = rec_bw + (bw_dev ? T * B : 0);
   const long shift = (long)roll_steps * c->da;
-  ka.ep.plant = plant_params ? reinterpret_cast<const float *>(mb->ep.get() + off_plant) : nullptr;
+  ka.ep.plant = st.plant_dev(plant_params);
   ka.ep.state = const_cast<float *>(b->in.states_dev());
   ka.ep.shift = shift > c->D ? c->D : (int)shift;
   ka.ep.in = in_dev;
@@ -2864,18 +2855,14 @@ extern "C" int dust_amppi_dual_batch_episode(dust_amppi_batch *b, dust_mpf_batch
     mb->n_calls++;
     if (staged) {
       if (sigma) dust::mpf_sigma_points_batch_kernel<<<b->B, 256, 0, c->stream>>>(mb->x, m->Mp, m->P, mb->prior_bwv, c->sigma_scale, b->params, mask);
-      else dust::mpf_sample_batch_kernel<<<(b->B + 255) / 256, 256, 0, c->stream>>>(mb->x, m->Mp, m->P, mb->prior_bwv, seeds_dev + t * B, b->B, b->params, mask);
+      else dust::mpf_sample_batch_kernel<<<(b->B + 255) / 256, 256, 0, c->stream>>>(mb->x, m->Mp, m->P, mb->prior_bwv, st.seeds_dev(t), b->B, b->params, mask);
       HIP_TRY(hipGetLastError());
       mb->n_launch++;
     }
-    ka.pr.seeds = seeds_dev + t * B;
-    ka.ep.states_out = rec_s + t * B * ds;
-    ka.ep.actions_out = rec_a + t * B * da;
-    ka.ep.costs_out = costs_out ? rec_c + t * B * S : nullptr;
-    ka.ep.omega_out = omega_out ? rec_o + t * B * S : nullptr;
-    ka.ep.a_seq_out = a_seq && t + 1 == T ? rec_q : nullptr;
+    ka.pr.seeds = st.seeds_dev(t);
+    lay.period(ka.ep, b->rec, t);
     ka.ep.bw = bw_dev && update ? mb->bw.get() : nullptr;
-    ka.ep.bw_out = bw_dev ? rec_bw + t * B : nullptr;
+    ka.ep.bw_out = lay.bw.at(b->rec, t);
     ka.ep.t0_add = update ? mpf_steps : 0;
     ka.ep.condition = t + 1 < T ? 1 : 0;
     Prof pr(c, DUST_K_AMPPI);
@@ -2889,23 +2876,9 @@ extern "C" int dust_amppi_dual_batch_episode(dust_amppi_batch *b, dust_mpf_batch
   }
   // ---- the records and the advanced rows come back once; the rows of inactive environments stay out of the caller's arrays
   std::vector<float> host(n_rec);
-  std::vector<dust::MpfEnvIn> in_host(B);
-  HIP_TRY(hipMemcpyAsync(host.data(), b->rec, n_rec * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(in_host.data(), in_dev, B * sizeof(dust::MpfEnvIn), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipEventRecord(mb->ev_ext, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  auto out = [&](float *dst, const float *dev, size_t n, size_t row) {
-    const float *src = host.data() + (dev - b->rec.get());
-    for (size_t t = 0; t < n; ++t)
-      for (size_t e = 0; e < B; ++e)
-        if (!active || active[e]) memcpy(dst + (t * B + e) * row, src + (t * B + e) * row, row * sizeof(float));
-  };
-  out(states_out, rec_s, T, ds);
-  out(actions_out, rec_a, T, da);
-  if (costs_out) out(costs_out, rec_c, T, S);
-  if (omega_out) out(omega_out, rec_o, T, S);
-  if (bw_dev) out(bw_out, rec_bw, T, 1);
-  if (a_seq) out(a_seq, rec_q, 1, D);
-  dual_episode_commit(mb, rows, in_host, T, first, silverman, mpf_bw, active, bw_out);
+  TRY(st.read_back(c, host, b->rec));
+  TRY(st.wait(c));
+  lay.out(host.data(), active, states_out, actions_out, costs_out, omega_out, bw_out, a_seq);
+  st.commit(mpf_bw, active, bw_out);
   return DUST_OK;
 }
