@@ -99,6 +99,10 @@ class SvmpcHyper(C.Structure):  # dust_svmpc_hyper: one environment's row of dus
                 ("sigma_p", C.c_float * 2), ("weighted_prior", C.c_int)]
 
 
+class MpfHyper(C.Structure):  # dust_mpf_hyper: one environment's row of dust_mpf_batch_set_hyper
+    _fields_ = [("lr", C.c_double), ("obs_std", C.c_float), ("bw", C.c_float), ("bw_scale", C.c_float), ("reserved", C.c_float)]
+
+
 class EpisodeRules(C.Structure):  # dust_episode_rules: the reference's episode rules of dust_svmpc_batch_simulate
     _fields_ = [("t0", C.c_int), ("warm_up", C.c_int), ("stop_on_crash", C.c_int), ("goal_radius", C.c_float), ("goal", C.c_float * 8)]
 
@@ -195,6 +199,8 @@ SYMBOLS = {
     "dust_mpf_batch_get_prior_bw": (C.c_int, [VP, FP]),
     "dust_mpf_batch_stats": (C.c_int, [VP, C.POINTER(C.c_longlong)]),
     "dust_mpf_batch_optimize": (C.c_int, [VP, FP, FP, C.c_float, C.c_int, C.POINTER(C.c_ubyte), FP, FP]),
+    "dust_mpf_batch_set_hyper": (C.c_int, [VP, C.POINTER(MpfHyper)]),
+    "dust_mpf_batch_get_hyper": (C.c_int, [VP, C.POINTER(MpfHyper)]),
     "dust_amppi_dual_batch_tick": (C.c_int, [VP, VP, FP, FP, VP, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_ubyte),
                                              FP, FP, FP, FP, FP]),
     "dust_svmpc_dual_batch_tick": (C.c_int, [VP, VP, FP, FP, C.c_int, VP, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_uint64), C.POINTER(C.c_ubyte),

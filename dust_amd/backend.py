@@ -1309,6 +1309,12 @@ class MpfBatch(_BatchHandle):
             L.check(L.load().dust_mpf_batch_create(proto._h, self.B, C.byref(h)))
             _handle = h
         self._h = _handle
+        if isinstance(like, MpfBatch):  # (a clone: the source's prototype)
+            self._proto_hyper = dict(like._proto_hyper)
+        else:  # what a field left out of a row takes: the values of a batch without rows
+            row = (L.MpfHyper * self.B)()
+            L.check(L.load().dust_mpf_batch_get_hyper(self._h, row))
+            self._proto_hyper = {k: getattr(row[0], k) for k in self.HYPER_FIELDS}
 
     def set_particles(self, x):
         L.check(L.load().dust_mpf_batch_set_particles(self._h, _p(_f(x, (self.B, self.Mp, self.P)))))
@@ -1334,9 +1340,50 @@ class MpfBatch(_BatchHandle):
         L.check(L.load().dust_mpf_batch_stats(self._h, n))
         return {"launches": int(n[0]), "calls": int(n[1])}
 
+    HYPER_FIELDS = ("lr", "obs_std", "bw", "bw_scale")
+    HYPER_DTYPE = np.dtype([("lr", np.float64), ("obs_std", np.float32), ("bw", np.float32), ("bw_scale", np.float32)])
+
+    def set_hyper(self, rows):
+        """Per-environment filter hyper-parameters (dust_mpf_batch_set_hyper): `rows` is a list of B dicts or a structured array [B]
+        with any of lr, obs_std, bw, bw_scale - fields left out take the prototype's values (bw: 0, Silverman's rule) - or None: back to
+        the prototype's.  While rows are set environment b updates under row b: its bandwidth is bw when that is > 0, else Silverman's
+        rule on its particles times bw_scale, and the bw of optimize() / the mpf_bw of the dual calls must be None or <= 0.  Copies and
+        deep copies carry the rows; the library refuses invalid rows and skid-steer / cart-pole batches."""
+        if rows is None:
+            L.check(L.load().dust_mpf_batch_set_hyper(self._h, None))
+            return
+        B = self.B
+        if isinstance(rows, np.ndarray) and rows.dtype.names:
+            unknown = set(rows.dtype.names) - set(self.HYPER_FIELDS)
+            rows = [{k: r[k] for k in rows.dtype.names} for r in rows.reshape(-1)]
+        else:
+            rows = [dict(r) for r in rows]
+            unknown = set().union(*[set(r) for r in rows]) - set(self.HYPER_FIELDS) if rows else set()
+        if unknown:
+            raise ValueError("a filter hyper-parameter row has the fields %s (got %s)" % (list(self.HYPER_FIELDS), sorted(unknown)))
+        if len(rows) != B:
+            raise ValueError("%d rows for %d environments" % (len(rows), B))
+        arr = (L.MpfHyper * B)()
+        for b, r in enumerate(rows):
+            for k in self.HYPER_FIELDS:
+                setattr(arr[b], k, float(r[k]) if k in r else self._proto_hyper[k])
+        L.check(L.load().dust_mpf_batch_set_hyper(self._h, arr))
+
+    @property
+    def hyper(self):
+        """The rows in force as a structured array [B] (HYPER_DTYPE; dust_mpf_batch_get_hyper): the prototype's values, with bw = 0,
+        where none are set."""
+        arr = (L.MpfHyper * self.B)()
+        L.check(L.load().dust_mpf_batch_get_hyper(self._h, arr))
+        out = np.zeros(self.B, self.HYPER_DTYPE)
+        for b, r in enumerate(arr):
+            out[b] = (r.lr, r.obs_std, r.bw, r.bw_scale)
+        return out
+
     def optimize(self, actions, new_obs, bw, n_steps, active=None):
         """B x MpfContext.optimize in one launch (dust_mpf_batch_optimize).  actions [B, da], new_obs [B, ds]; bw None or <= 0:
-        Silverman's rule per environment on the device.  -> (grad_norms [B, n_steps], bw_used [B]); NaN rows for inactive environments."""
+        Silverman's rule per environment on the device (with rows set: row b's bandwidth).  -> (grad_norms [B, n_steps], bw_used [B]);
+        NaN rows for inactive environments."""
         a = None if actions is None else _f(actions, (self.B, self.da))
         o = None if new_obs is None else _f(new_obs, (self.B, self.ds))
         _, mp = _mask(active, self.B)

@@ -257,8 +257,37 @@ class _BatchDual:
                 raise ValueError("init_particles has shape %s, the batch takes %s" % (tuple(init_particles.shape), want))
         self._init_particles = init_particles
         self._mb = None
+        self._filter_hyper = None
         self.ticks = 0
         self.last_bw = None
+
+    def set_filter_hyper(self, rows):
+        """Per-environment filter hyper-parameters (MpfBatch.set_hyper): a list of B dicts or a structured array [B] with any of lr,
+        obs_std, bw, bw_scale, or None to clear.  Environment b's filter then updates under row b in every call of this object; the
+        rows carry the bandwidths, so an object made with a positive `mpf_bw` refuses (before any device call)."""
+        if rows is not None:
+            if self.mpf_bw is not None and float(self.mpf_bw) > 0:
+                raise ValueError("mpf_bw = %g was given to the constructor: with per-environment filter rows the rows carry the bandwidths - "
+                                 "put it in the rows (bw) and construct with mpf_bw=None" % float(self.mpf_bw))
+            if len(rows) != self.n_envs:
+                raise ValueError("%d rows for %d environments" % (len(rows), self.n_envs))
+            rows = rows.copy() if hasattr(rows, "dtype") else [dict(r) for r in rows]
+        if self._mb is not None:
+            self._mb.set_hyper(rows)
+        self._filter_hyper = rows  # (the filters of an object that has not run yet take them when they are made)
+
+    @property
+    def filter_hyper(self):
+        """The filter rows in force, a structured array [B] (MpfBatch.hyper): the prototype's values where none are set."""
+        if self._mb is not None:
+            return self._mb.hyper
+        mb = self.mpf._dev.batch(self.n_envs)  # (the filters are made by the first forward(): ask a batch of their kind)
+        try:
+            if self._filter_hyper is not None:
+                mb.set_hyper(self._filter_hyper)
+            return mb.hyper
+        finally:
+            mb.close()
 
     def prior_keys(self, t):
         """The Philox keys of period t = 1, 2, ...: seed + (b << 32) + t for environment b (modulo 2^64)."""
@@ -281,6 +310,8 @@ class _BatchDual:
                 mb.set_particles(self._init_particles.numpy())
             if states is not None:
                 mb.set_obs(states)
+            if self._filter_hyper is not None:
+                mb.set_hyper(self._filter_hyper)
             self._mb = mb
         return self._mb
 

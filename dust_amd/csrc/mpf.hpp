@@ -287,7 +287,8 @@ __global__ __launch_bounds__(1024) void mpf_optimize_kernel(const MpfArgs a) {
 // [B][Mp][P], the observations, the action, the steps taken so far (MpfEnvIn [B], staged by the host per call), the prior bandwidths
 // [B][4], the kernel bandwidth [B] (Silverman's, written by mpf_silverman_batch_kernel just ahead on the same stream; or the call's fixed
 // one), grad_norms [B][gn_stride], SkidLik / CartLik [B] - and runs the SAME body text on them: the arithmetic and its order are the lone
-// kernel's, per environment.  Model, grid bits, obs_std, the optimiser's options, Mp and P are shared.  Behind the body lane 0 does what
+// kernel's, per environment.  Model, grid bits, obs_std, the optimiser's options, Mp and P are shared (obs_std, the optimiser's lr and the
+// bandwidth per environment: mpf_optimize_rows_kernel below).  Behind the body lane 0 does what
 // the host does after a lone call: the prior bandwidths become the kernel bandwidth (update_prior(bw), mpf.py:85) and bw_used[b] records
 // it.  The workgroup of an environment whose `active` byte is 0 returns before it touches anything.  No workgroup talks to another one.
 // MODEL, LOG, ADAM: the shared model - with it the widths of state and action -, log_space and whether the optimiser is Adam (its step
@@ -366,6 +367,57 @@ __global__ __launch_bounds__(1024) void mpf_optimize_batch_kernel(const MpfBatch
   if (threadIdx.x == 0) {
     float *pb = k.prior_bwv + (size_t)env * 4;
     _Pragma("unroll") for (int p = 0; p < 4; ++p) pb[p] = a.bw;
+    k.bw[env] = a.bw;
+  }
+}
+
+// ---- the rows form (dust_mpf_batch_set_hyper): every environment under its own lr, obs_std and bandwidth - the B trials of a sweep over
+// the filter's settings in the launches of one update.  Instances of their own, as svmpc_sweep_kernel's are: the uniform instances above
+// keep their text, argument block and registers.  Workgroup b loads rows[b] once (the row is workgroup-uniform and no kernel writes it:
+// scalar loads); the view of its environment is mpf_env_view's with obs_std from the row and, for the optimiser, a copy of the shared
+// options whose lr is the row's (88 bytes read at compile-time offsets: scalar registers - only the WHOLE argument block, whose model
+// carries arrays, would go to scratch memory).  The bandwidth is always bw[env]: mpf_silverman_rows_kernel, just ahead on the same
+// stream, has written the row's fixed value or Silverman's there.  The body is the same text.  Pendulum and Particle only.
+struct MpfRowsArgs {
+  MpfBatchArgs k;              // bw_fixed is 0
+  const dust_mpf_hyper *rows;  // [B]
+};
+template <int P, int MODEL, bool LOG, bool ADAM>
+__global__ __launch_bounds__(1024) void mpf_optimize_rows_kernel(const MpfRowsArgs kr) {
+  const MpfBatchArgs &k = kr.k;
+  const int env = (int)blockIdx.x;
+  if (k.active && k.active[env] == 0) return;
+  constexpr bool CART = false;
+  __builtin_assume(k.a.dm.model == MODEL);
+  __builtin_assume(k.a.ds == (MODEL == DUST_MODEL_PENDULUM ? 2 : 4));
+  __builtin_assume(k.a.da == (MODEL == DUST_MODEL_PENDULUM ? 1 : 2));
+  __builtin_assume(k.a.dm.log_space == (LOG ? 1 : 0));
+  __builtin_assume(k.a.log_space == (LOG ? 1 : 0));
+  __builtin_assume(ADAM ? k.a.opt.kind == DUST_OPT_ADAM : k.a.opt.kind != DUST_OPT_ADAM);
+  const dust_mpf_hyper &row = kr.rows[env];
+  OptArgs opt = k.a.opt;
+  opt.lr = row.lr;
+  const MpfArgs &g = k.a;
+  const MpfEnvIn &in = k.in[env];
+  const float *pb = k.prior_bwv + (size_t)env * 4;
+  const size_t np = (size_t)env * (size_t)g.Mp * (size_t)g.P;
+  const MpfEnvArgs a{g.dm, g.Mp, g.P, g.ds, g.da, g.n_steps, g.log_space,
+                     {pb[0], pb[1], pb[2], pb[3]},
+                     k.bw[env], row.obs_std,
+                     {in.past_obs[0], in.past_obs[1], in.past_obs[2], in.past_obs[3]},
+                     {in.past_action[0], in.past_action[1]},
+                     {in.obs[0], in.obs[1], in.obs[2], in.obs[3]},
+                     nullptr, nullptr, nullptr,
+                     g.x + np, g.grad_norms + (size_t)env * (size_t)k.gn_stride, nullptr,
+                     opt, in.t0,
+                     g.opt_s0 ? g.opt_s0 + np : nullptr, g.opt_s1 ? g.opt_s1 + np : nullptr, g.opt_s2 ? g.opt_s2 + np : nullptr};
+#define MPF_UNIFORM(v) mpf_uniform(v)
+#include "mpf_body.inc"
+#undef MPF_UNIFORM
+  wg_sync();
+  if (threadIdx.x == 0) {
+    float *pbo = k.prior_bwv + (size_t)env * 4;
+    _Pragma("unroll") for (int p = 0; p < 4; ++p) pbo[p] = a.bw;
     k.bw[env] = a.bw;
   }
 }
@@ -1113,6 +1165,18 @@ __global__ __launch_bounds__(1024) void mpf_silverman_batch_kernel(const float *
   const int env = (int)blockIdx.x;
   if (active && active[env] == 0) return;
   mpf_silverman_body(x + (size_t)env * (size_t)n, n, bw_scale, bw + env);
+}
+// the rows form (dust_mpf_batch_set_hyper), launched ahead of every update while rows are set: workgroup b writes its row's fixed
+// bandwidth and skips the order statistics, or runs Silverman's rule under its row's bw_scale (the branch is workgroup-uniform)
+__global__ __launch_bounds__(1024) void mpf_silverman_rows_kernel(const float *x, const int n, const dust_mpf_hyper *rows, float *bw, const unsigned char *active) {
+  const int env = (int)blockIdx.x;
+  if (active && active[env] == 0) return;
+  const float fixed = rows[env].bw;
+  if (fixed > 0.f) {
+    if (threadIdx.x == 0) bw[env] = fixed;
+    return;
+  }
+  mpf_silverman_body(x + (size_t)env * (size_t)n, n, rows[env].bw_scale, bw + env);
 }
 
 }  // namespace dust
@@ -2003,6 +2067,8 @@ struct dust_mpf_batch {
   PinBuf<unsigned char> ep_host;
   hipEvent_t ev_ext;   // behind the last work a dual tick put on a controller batch's stream (AMPPI or SVMPC)
   long long n_launch, n_calls;
+  std::vector<dust_mpf_hyper> hyper;  // dust_mpf_batch_set_hyper: the caller's rows [B], or empty (every environment: the prototype's)
+  DevBuf<dust_mpf_hyper> hyper_dev;   // [B] while rows are set
 };
 
 static size_t mpfb_lik_bytes(const dust_mpf *m) {
@@ -2143,12 +2209,69 @@ extern "C" int dust_mpf_batch_clone(const dust_mpf_batch *src, dust_mpf_batch **
     mb->past_action = src->past_action;
     mb->have_past = src->have_past;
     mb->opt_t = src->opt_t;
+    if (st == DUST_OK && !src->hyper.empty()) {  // (the host rows are what the device holds: set_hyper uploads before it stores)
+      st = mb->hyper_dev.alloc(B);
+      if (st == DUST_OK && hipMemcpy(mb->hyper_dev, src->hyper.data(), B * sizeof(dust_mpf_hyper), hipMemcpyHostToDevice) != hipSuccess)
+        st = fail(DUST_ERR_HIP, "hipMemcpy failed");
+      if (st == DUST_OK) mb->hyper = src->hyper;
+    }
   }
   if (st != DUST_OK) {
     mpfb_free(mb);
     return st;
   }
   *out = mb;
+  return DUST_OK;
+}
+
+// Per-environment filter hyper-parameters: the B trials of a sweep over the filter's own settings as the environments of one batch.
+// The rows are checked whole before anything is stored; nothing else of the batch is touched.
+static dust_mpf_hyper mpfb_proto_hyper(const dust_mpf *m) {
+  dust_mpf_hyper h;
+  memset(&h, 0, sizeof h);
+  h.lr = m->opt.lr;
+  h.obs_std = m->cfg.obs_std;
+  h.bw = 0.f;  // (the prototype has no bandwidth of its own: each call names one)
+  h.bw_scale = m->cfg.bw_scale;
+  return h;
+}
+extern "C" int dust_mpf_batch_set_hyper(dust_mpf_batch *mb, const dust_mpf_hyper *rows) {
+  if (!mb) return fail(DUST_ERR_INVALID, "null batch");
+  if (!rows) {  // back to the prototype's: the uniform instances serve the next call
+    mb->hyper.clear();
+    return DUST_OK;
+  }
+  const int model = mb->m->cfg.model_cfg.model;
+  if (model != DUST_MODEL_PENDULUM && model != DUST_MODEL_PARTICLE)
+    return fail(DUST_ERR_UNSUPPORTED, "per-environment filter hyper-parameters are for Pendulum and Particle filters: no rows on a skid-steer or cart-pole filter batch");
+  const size_t B = (size_t)mb->B;
+  std::vector<dust_mpf_hyper> keep(rows, rows + B);
+  for (size_t e = 0; e < B; ++e) {
+    dust_mpf_hyper &h = keep[e];
+    h.reserved = 0.f;
+    auto pos = [](double v) { return std::isfinite(v) && v > 0.0; };
+    if (!(pos(h.lr) && pos((double)h.obs_std) && pos((double)h.bw_scale) && std::isfinite(h.bw)))
+      return fail(DUST_ERR_INVALID, "filter hyper-parameter row %zu: lr, obs_std and bw_scale must be finite and > 0, bw finite (<= 0: Silverman's rule)", e);
+  }
+  TRY(mpfb_settle(mb));
+  TRY(mb->hyper_dev.ensure(B));
+  // on the batch's stream, behind every launch that read the old rows
+  HIP_TRY(hipMemcpyAsync(mb->hyper_dev, keep.data(), B * sizeof(dust_mpf_hyper), hipMemcpyHostToDevice, mb->m->stream));
+  HIP_TRY(hipStreamSynchronize(mb->m->stream));
+  mb->hyper.swap(keep);
+  return DUST_OK;
+}
+extern "C" int dust_mpf_batch_get_hyper(dust_mpf_batch *mb, dust_mpf_hyper *rows) {
+  if (!mb || !rows) return fail(DUST_ERR_INVALID, "null argument");
+  if (!mb->hyper.empty()) std::copy(mb->hyper.begin(), mb->hyper.end(), rows);
+  else std::fill(rows, rows + (size_t)mb->B, mpfb_proto_hyper(mb->m));
+  return DUST_OK;
+}
+// while rows are set they carry the bandwidths: the call's own must be <= 0 (ahead of any staging or launch)
+static int mpfb_bw_check(const dust_mpf_batch *mb, float bw) {
+  if (!mb->hyper.empty() && bw > 0.f)
+    return fail(DUST_ERR_INVALID, "the filter batch has per-environment hyper-parameters: the rows carry the bandwidths (rows[b].bw), so the call's bandwidth "
+                "must be <= 0 (got %g)", (double)bw);
   return DUST_OK;
 }
 
@@ -2229,6 +2352,15 @@ static bool mpfb_launch(const dust_mpf *m, int B, hipStream_t stream, const MpfB
   });
 }
 
+// the rows form (dust_mpf_batch_set_hyper): mpf_optimize_rows_kernel of a Pendulum or Particle filter
+template <int MODEL, int... Ps>
+static bool mpfb_launch_rows(const dust_mpf *m, int B, hipStream_t stream, const MpfRowsArgs &k, int *st) {
+  return mpf_pick<Ps...>(m->P, m->cfg.log_space != 0, [&](auto p, auto lg) {
+    if (m->opt.kind == DUST_OPT_ADAM) *st = mpf_wg_launch(mpf_optimize_rows_kernel<p(), MODEL, lg(), true>, B, mpf_wg(m), stream, k);
+    else *st = mpf_wg_launch(mpf_optimize_rows_kernel<p(), MODEL, lg(), false>, B, mpf_wg(m), stream, k);
+  });
+}
+
 // GaussianLikelihood.condition of every active environment (likelihoods.py:51-64) on copies of the host rows (`w`; new_obs NULL: the
 // rows as they stand), and what the update of `n_steps` steps reads of them: MpfEnvIn [B] in front of the stage's bytes `hb`, and the
 // skid-steer / cart-pole likelihood rows behind the seeds
@@ -2283,7 +2415,13 @@ static int mpfb_update_launch(dust_mpf_batch *mb, hipStream_t stream, const dust
     mb->n_launch++;
   }
   const int n = m->Mp * m->P;
-  if (!(bw > 0.f)) {
+  const bool rows = !mb->hyper.empty();  // (Pendulum or Particle: dust_mpf_batch_set_hyper; bw <= 0: mpfb_bw_check)
+  if (rows) {
+    if (bw > 0.f) return fail(DUST_ERR_INVALID, "the rows carry the bandwidths");
+    dust::mpf_silverman_rows_kernel<<<B, 1024, (size_t)n * sizeof(float), stream>>>(mb->x, n, mb->hyper_dev, mb->bw, mask);
+    HIP_TRY(hipGetLastError());
+    mb->n_launch++;
+  } else if (!(bw > 0.f)) {
     dust::mpf_silverman_batch_kernel<<<B, 1024, (size_t)n * sizeof(float), stream>>>(mb->x, n, m->cfg.bw_scale, mb->bw, mask);
     HIP_TRY(hipGetLastError());
     mb->n_launch++;
@@ -2310,7 +2448,17 @@ static int mpfb_update_launch(dust_mpf_batch *mb, hipStream_t stream, const dust
   k.active = mask;
   // (P up to the model's parameter count: mpfb_limits has refused the rest)
   int st = DUST_OK;
-  if (cart) {
+  if (rows) {
+    MpfRowsArgs kr;
+    kr.k = k;
+    kr.rows = mb->hyper_dev;
+    if (model == DUST_MODEL_PARTICLE) {
+      if (!mpfb_launch_rows<DUST_MODEL_PARTICLE, 1>(m, B, stream, kr, &st))
+        return fail(DUST_ERR_UNSUPPORTED, "no batched filter kernel for a Particle filter over %d particle columns", m->P);
+    } else if (!mpfb_launch_rows<DUST_MODEL_PENDULUM, 1, 2, 3>(m, B, stream, kr, &st)) {
+      return fail(DUST_ERR_UNSUPPORTED, "no batched filter kernel for a Pendulum filter over %d particle columns", m->P);
+    }
+  } else if (cart) {
     mpfb_launch<DUST_MODEL_CARTPOLE, 1, 2, 3, 4>(m, B, stream, k, &st);
   } else if (model == DUST_MODEL_SKID_STEER) {
     if (!mpfb_launch<DUST_MODEL_SKID_STEER, 1, 2, 3>(m, B, stream, k, &st))
@@ -2353,6 +2501,7 @@ static int mpfb_gn_room(dust_mpf_batch *mb, int n_steps) { return mb->gn.ensure(
 extern "C" int dust_mpf_batch_optimize(dust_mpf_batch *mb, const float *actions, const float *new_obs, float bw, int n_steps, const unsigned char *active,
                                        float *bw_used, float *grad_norms) {
   if (!mb) return fail(DUST_ERR_INVALID, "null batch");
+  TRY(mpfb_bw_check(mb, bw));
   TRY(mpfb_update_check(mb, actions, new_obs, n_steps, active));
   TRY(mpfb_settle(mb));
   TRY(mpfb_gn_room(mb, n_steps));
@@ -2383,6 +2532,7 @@ template <class Stage>
 static int dual_batch_filters(dust_ctx *c, dust_mpf_batch *mb, const float *states, const float *actions_prev, int mpf_steps, float mpf_bw,
                               const uint64_t *prior_seeds, const unsigned char *active, MpfbRows &rows, Stage stage) {
   TRY(mpfb_limits(mb->m, mb->B));
+  TRY(mpfb_bw_check(mb, mpf_bw));
   if (actions_prev) TRY(mpfb_update_check(mb, actions_prev, states, mpf_steps, active));
   HIP_TRY(hipSetDevice(c->cfg.device));
   TRY(settle_pending(c));
@@ -2661,6 +2811,7 @@ static int svb_dual_episode_call(dust_svmpc_batch *b, dust_mpf_batch *mb, const 
                 "a dual episode conditions the filters on the device: Pendulum and Particle pairs (a skid-steer or cart-pole filter's likelihood rows "
                 "carry the host's sin / cos of the past heading: dust_svmpc_dual_batch_tick per period)");
   TRY(mpfb_limits(m, mb->B));
+  TRY(mpfb_bw_check(mb, mpf_bw));
   const bool first = actions_prev != nullptr;  // period 0 has an update
   // (the periods behind the first always have one; its refusals depend on whether its arguments are there, not on their values)
   if (first || n_periods > 1) TRY(mpfb_update_check(mb, first ? actions_prev : states, states, mpf_steps, active));
@@ -2812,6 +2963,7 @@ extern "C" int dust_amppi_dual_batch_episode(dust_amppi_batch *b, dust_mpf_batch
   one.P = m->P;
   TRY(amppi_params_mode(c, staged, flags, staged ? nullptr : &one, &mode, &pts, &prows));
   TRY(mpfb_limits(m, mb->B));
+  TRY(mpfb_bw_check(mb, mpf_bw));
   const bool first = actions_prev != nullptr;  // period 0 has an update
   if (first || n_periods > 1) TRY(mpfb_update_check(mb, first ? actions_prev : states, states, mpf_steps, active));
   const size_t T = (size_t)n_periods, B = (size_t)b->B, S = (size_t)c->S, P = (size_t)m->P;

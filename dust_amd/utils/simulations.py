@@ -146,13 +146,15 @@ def run_particle_episode(init_state, model, dyn_dist, controller, use_svmpc=True
 
 def run_pendulum_simulations(init_state, init_policies, model_kwargs, experiment_params, controller, svmpc_kwargs, lik_kwargs, mpf, mpf_bw=None,
                              mpf_steps=20, episodes=3, steps=200, warm_up=1, seed=0, init_particles=None, frame=False, *, use_svmpc=True,
-                             dyn_dist=None, use_exact_model=False):
+                             dyn_dist=None, use_exact_model=False, mpf_hyper=None):
     """The batched twin of `run_pendulum_simulation(use_svmpc=True, mpf=...)`: the `episodes` become the B environments of one
     `BatchSVMPC` plus `BatchDualSVMPC`, environment i's plant runs under `experiment_params[i]`, and the whole loop - warm-up periods
     that only optimize and apply a zero action while the filters keep updating, the cost of every new state - runs on the device, one
     `BatchDualSVMPC.simulate` call per piece of at most 4096 periods.  `svmpc_kwargs` are SVMPC's keywords (init_particles, prior, ...;
     `seeds` too), `lik_kwargs` ExponentiatedUtility's, `mpf` the filter prototype every environment copies (`init_particles`
-    [B, Mp, P]: its own start), `seed` the base of the filters' prior keys.
+    [B, Mp, P]: its own start), `seed` the base of the filters' prior keys.  `mpf_hyper` (keyword only): B filter rows - dicts or a
+    structured array with any of lr, obs_std, bw, bw_scale (`BatchDualSVMPC.set_filter_hyper`) - the trials of a sweep over the filter's
+    settings, one per environment; `mpf_bw` must then be None (the rows carry the bandwidths).
 
     The plants.  They step the CONTROLLER'S model - `PendulumModel(**model_kwargs)`, the model of all B environments - under the true
     rows: the columns of its `uncertain_params`, from `experiment_params[i]` (a name it lacks keeps the model's value), without noise and
@@ -193,6 +195,8 @@ def run_pendulum_simulations(init_state, init_policies, model_kwargs, experiment
     sim_ctrl.return_rollouts = False
     sv = BatchSVMPC(B, likelihood=ExponentiatedUtility(**lik_kwargs, controller=sim_ctrl, model=model), **svmpc_kwargs)
     dual = BatchDualSVMPC(sv, mpf, mpf_bw=mpf_bw, mpf_steps=mpf_steps, seed=seed, init_particles=init_particles, warm_up=warm_up)
+    if mpf_hyper is not None:
+        dual.set_filter_hyper(mpf_hyper)
     true = torch.tensor([[float(experiment_params[i].get(k, model.params_dict[k])) for k in names] for i in range(B)], dtype=torch.float)
     rows = true.log() if bool(sim_ctrl._params_log_space) else true
     state = torch.as_tensor(init_state, dtype=torch.float).reshape(1, -1).repeat(B, 1)
@@ -302,7 +306,7 @@ def _run_particle_baselines(init_states, model, dyn_dist, ctrl, load, steps, pla
 
 
 def run_particle_episodes(init_states, model, dyn_dist, batch_svmpc, warm_up=30, load=0, steps=400, plant_params=None, mpf=None, mpf_bw=None,
-                          mpf_steps=20):
+                          mpf_steps=20, mpf_hyper=None):
     """The batched twin of `run_particle_episode`: environment b of `batch_svmpc` (a `BatchSVMPC` over `model`) runs that episode from
     init_states[b] on the device (`BatchSVMPC.simulate`: warm-up, accumulated cost, crash - when the model has obstacles - and the goal
     `model.target` within 1.0), in pieces of at most 4096 periods.  The plants are deterministic and step under `plant_params` [B, P]
@@ -310,7 +314,8 @@ def run_particle_episodes(init_states, model, dyn_dist, batch_svmpc, warm_up=30,
     steps // 4 and the true mass grows by `load` from there on, which needs `mass` among the model's uncertain parameters.
     `mpf` (a filter prototype, as run_particle_episode's): the episode is the DuSt-MPC loop - every environment a copy of the filter,
     updated after every plant step, the warm-up periods included, and stopped with its environment - on `BatchDualSVMPC.simulate`;
-    the dynamics samples then come from the filters (`dyn_dist` is not read).  The `load` split stays two calls.
+    the dynamics samples then come from the filters (`dyn_dist` is not read).  The `load` split stays two calls.  `mpf_hyper`: B filter
+    rows (`BatchDualSVMPC.set_filter_hyper`), one per environment; needs `mpf`, and `mpf_bw` must then be None.
     `batch_svmpc` may be a `BatchDISCO` instead: the episode is run_particle_episode's `use_svmpc=False` branch - every period forward +
     step("argmax"), no warm-up (`warm_up` is not read), no filter (`mpf` must be None) - on `BatchDISCO.simulate`.
     -> losses [B]: the cumulated cost of every environment, inf after a crash."""
@@ -322,6 +327,8 @@ def run_particle_episodes(init_states, model, dyn_dist, batch_svmpc, warm_up=30,
         if mpf is not None:
             raise ValueError("a BatchDISCO episode has no dynamics filter: mpf must be None")
         return _run_particle_baselines(init_states, model, dyn_dist, batch_svmpc, load, int(steps), plant_params)
+    if mpf_hyper is not None and mpf is None:
+        raise ValueError("mpf_hyper are the rows of the filters: pass the filter prototype as mpf")
     ctrl = batch_svmpc.likelihood.controller
     B = batch_svmpc.n_envs
     state = torch.as_tensor(init_states, dtype=torch.float).reshape(B, -1).clone()
@@ -347,6 +354,8 @@ def run_particle_episodes(init_states, model, dyn_dist, batch_svmpc, warm_up=30,
         from ..controllers.dual import BatchDualSVMPC
 
         dual = BatchDualSVMPC(batch_svmpc, mpf, mpf_bw=mpf_bw, mpf_steps=mpf_steps, warm_up=warm_up)
+        if mpf_hyper is not None:
+            dual.set_filter_hyper(mpf_hyper)
     for lo, hi in zip(cuts[:-1], cuts[1:]):
         plant = loaded if (load != 0 and lo >= steps // 4) else rows
         if dual is not None:

@@ -843,6 +843,28 @@ int dust_mpf_batch_get_prior_bw(dust_mpf_batch *batch, float *bw);
 int dust_mpf_batch_stats(dust_mpf_batch *batch, long long out[2]);
 int dust_mpf_batch_optimize(dust_mpf_batch *batch, const float *actions, const float *new_obs, float bw, int n_steps, const unsigned char *active,
                             float *bw_used, float *grad_norms);
+/* Per-environment filter hyper-parameters: the B trials of a sweep over the filter's own settings (the reference's mpf_learning_rate,
+ * mpf_obs_std, mpf_bandwidth, mpf_bandwidth_scaling of demo/.._config.yaml) as the environments of one batch.  Pendulum and Particle filters; rows
+ * on a skid-steer or cart-pole batch are DUST_ERR_UNSUPPORTED.
+ * dust_mpf_batch_set_hyper: rows [B], host, copied (and uploaded on the batch's stream) before the call returns; NULL: back to the
+ *   prototype's values and the uniform kernels.  Particles, optimiser state, step counts, prior bandwidths and host rows are not touched.
+ *   A row with a value that is not finite, or with lr, obs_std or bw_scale <= 0, is DUST_ERR_INVALID and leaves the stored rows as they
+ *   were.  dust_mpf_batch_clone copies the rows.
+ * dust_mpf_batch_get_hyper: the rows as they were set, or B times the prototype's values where none are set - bw is then 0 (the
+ *   prototype has no bandwidth of its own: each call names one).
+ * While rows are set the rows carry the bandwidths: the bw of dust_mpf_batch_optimize and the mpf_bw of every dual entry must be <= 0
+ *   (> 0: DUST_ERR_INVALID ahead of any staging or launch).  Environment b updates under rows[b].bw when that is > 0, else under
+ *   Silverman's rule on its own particles times rows[b].bw_scale; bw_used / bw_out and the refreshed prior bandwidths report that value.
+ *   The launch count per update is the one of a call with bw <= 0 without rows, whatever B and the rows' values. */
+typedef struct dust_mpf_hyper { /* one environment's row */
+  double lr;      /* the optimiser's lr (dust_optim_config.lr) */
+  float obs_std;  /* GaussianLikelihood's sigma */
+  float bw;       /* > 0: this environment's fixed kernel bandwidth; <= 0: Silverman's rule on its particles */
+  float bw_scale; /* the factor on Silverman's rule (MPF(bw_scale=)) */
+  float reserved; /* 0 */
+} dust_mpf_hyper;
+int dust_mpf_batch_set_hyper(dust_mpf_batch *batch, const dust_mpf_hyper *rows /* [B], or NULL: back to the prototype's */);
+int dust_mpf_batch_get_hyper(dust_mpf_batch *batch, dust_mpf_hyper *rows /* [B]: the prototype's values where none are set */);
 /* One control period of the dual loop for B environments in one call = B x dust_amppi_dual_tick, on the AMPPI batch's stream in launch
  * order with no event, no synchronisation and no host round trip between the filters and the ticks; the number of kernel launches does
  * not depend on B.  states [B][ds]; actions_prev [B][da] or NULL (no filter update: the first period); actions [B][S][H][da] or NULL
