@@ -28,6 +28,8 @@ K_SVMPC_BATCH, K_ALL = 9, 10  # appended behind ABI 3's first list (K_COUNT is t
 (SVB_THETA, SVB_PRIOR_MEANS, SVB_PRIOR_MIX, SVB_A_MAT, SVB_COSTS, SVB_SCORE, SVB_PHI, SVB_LOG_L, SVB_LOG_P, SVB_A_MIX,
  SVB_ACTIONS) = range(11)
 DCB_A_MAT, DCB_A_SEQ, DCB_A_MIX, DCB_COSTS, DCB_OMEGA, DCB_ACTIONS = range(6)  # dust_disco_batch_quantity
+HIST_THETA, HIST_FILTER = 1, 2  # dust_svmpc_batch_set_history / _get_history
+SVMPC_HISTORY_MAX_FLOATS = 1 << 28
 DISCO_PARAMS_ONCE = 128  # dust_disco_batch_episode: params [B][M][P] serves every period
 
 
@@ -179,6 +181,8 @@ SYMBOLS = {
     "dust_svmpc_batch_get_hyper": (C.c_int, [VP, C.POINTER(SvmpcHyper)]),
     "dust_svmpc_batch_simulate": (C.c_int, [VP, FP, C.c_int, C.c_int, FP, FP, C.POINTER(EpisodeRules), C.c_int, C.POINTER(C.c_ubyte), FP, FP, FP,
                                             FP, FP, C.POINTER(C.c_int), C.POINTER(C.c_int), FP]),
+    "dust_svmpc_batch_set_history": (C.c_int, [VP, C.c_int]),
+    "dust_svmpc_batch_get_history": (C.c_int, [VP, C.c_int, C.POINTER(C.c_int), FP]),
     "dust_disco_batch_create": (C.c_int, [VP, C.c_int, C.POINTER(C.c_uint64), C.POINTER(VP)]),
     "dust_disco_batch_destroy": (None, [VP]),
     "dust_disco_batch_clone": (C.c_int, [VP, C.POINTER(VP)]),

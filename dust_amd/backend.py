@@ -927,6 +927,7 @@ class SvmpcBatch(_BatchHandle):
         c = self.ctx
         self.N, self.S, self.H, self.da, self.ds, self.P, self.M = c.N, c.S, c.H, c.da, c.ds, c.P, c.M
         B, N, S, H, da = self.B, self.N, self.S, self.H, self.da
+        self._hist_x_row = None  # (Mp, P) of the filters the last dual_simulate() ran with: a recorded filter row's shape
         self._shapes = {L.SVB_THETA: (B, N, H, da), L.SVB_PRIOR_MEANS: (B, N, H, da), L.SVB_PRIOR_MIX: (B, N), L.SVB_A_MAT: (B, N, H, da),
                         L.SVB_COSTS: (B, S, N), L.SVB_SCORE: (B, N, H, da), L.SVB_PHI: (B, N, H, da), L.SVB_LOG_L: (B, N),
                         L.SVB_LOG_P: (B, N), L.SVB_A_MIX: (B, N), L.SVB_ACTIONS: (B, S, N, H, da)}
@@ -985,6 +986,23 @@ class SvmpcBatch(_BatchHandle):
                "weighted_prior": np.array([r.weighted_prior for r in arr], np.int32)}
         for k in ("sigma_a", "chol_a", "sigma_p"):
             out[k] = np.array([list(getattr(r, k))[:self.da] for r in arr], np.float32).reshape(B, self.da)
+        return out
+
+    def set_history(self, theta=False, filter=False):
+        """What simulate() / dual_simulate() record from now on (dust_svmpc_batch_set_history): the particles after every period
+        (`theta`) and, in dual_simulate(), the filters' particles every period's tick drew from (`filter`) - written by the episodes' own
+        kernels, no launch added.  Both False: recording off, the buffers released.  Nothing else of the batch changes."""
+        L.check(L.load().dust_svmpc_batch_set_history(self._h, (L.HIST_THETA if theta else 0) | (L.HIST_FILTER if filter else 0)))
+
+    def history(self, which):
+        """The last recording of one kind (dust_svmpc_batch_get_history) as a NaN-filled array: which = _lib.HIST_THETA -> [T, B, N, H, da];
+        _lib.HIST_FILTER -> [T, B, Mp, P] (Mp, P: the filters of the dual_simulate() that recorded).  Rows (t, b) the recording call did
+        not run are NaN, as the reference's frame has them.  The library answers DUST_ERR_STATE while nothing of that kind is recorded."""
+        T = C.c_int(0)
+        L.check(L.load().dust_svmpc_batch_get_history(self._h, int(which), C.byref(T), None))
+        row = (self.N, self.H, self.da) if int(which) == L.HIST_THETA else self._hist_x_row
+        out = np.full((T.value, self.B) + row, np.nan, np.float32)
+        L.check(L.load().dust_svmpc_batch_get_history(self._h, int(which), None, _p(out)))
         return out
 
     def _inputs(self, states, n_steps, eps, params, eps_dev_ptr, keep_actions):
@@ -1168,6 +1186,7 @@ class SvmpcBatch(_BatchHandle):
                                                         float(-1.0 if mpf_bw is None else mpf_bw), sp, _p(pl), C.byref(ru), int(flags), mp,
                                                         _p(xs), _p(acts), _p(pw), _p(bw), _p(costs), _p(loss), status.ctypes.data_as(IP),
                                                         n_run.ctypes.data_as(IP), _p(a_seq)))
+        self._hist_x_row = (int(mpf.Mp), int(mpf.P))
         return xs, acts, pw, bw, costs, loss, status, n_run, a_seq
 
 

@@ -527,6 +527,32 @@ class BatchDualSVMPC(_BatchDual):
     def controller(self):
         return self.svmpc.likelihood.controller
 
+    # -- the posterior's history: the reference's PolParticles / DynParticles rows (simulations.py:122, 134-137) out of simulate()
+    def set_history(self, theta=True, filter=True):
+        """What simulate() records from now on (BatchSVMPC.set_history, dust_svmpc_batch_set_history): `theta` - the controllers'
+        particles after every period; `filter` - the filters' particles every period's tick drew its dynamics samples from.  Written by
+        the period's own kernel (svmpc_dual_sim_hist_period_kernel): no launch is added and nothing the episode computes changes.  Both
+        False: recording off.  simulate()'s signature and result do not change: read the rows from `history`.  Deep copies carry the
+        setting, not the rows."""
+        self.svmpc.set_history(theta, filter)
+
+    @property
+    def history(self):
+        """The rows of the last recording simulate(), the kinds that were asked for: 'theta' [T, B, N, H, da] - `theta` after period t -
+        and 'dyn_particles' [T, B, Mp, P] - the filters' particles after period t's update, before the pair (actions[t], states[t]) is
+        folded in (in a period 0 without a noted update: the particles at entry).  Rows an environment did not run are NaN."""
+        from .. import _lib as L
+
+        sv = self.svmpc
+        if sv._batch is None:
+            raise RuntimeError("nothing is recorded yet: set_history(), then simulate()")
+        out = {}
+        if sv._history[0]:
+            out["theta"] = torch.from_numpy(sv._batch.history(L.HIST_THETA))
+        if sv._history[1]:
+            out["dyn_particles"] = torch.from_numpy(sv._batch.history(L.HIST_FILTER))
+        return out
+
     def forward(self, states, eps=None, active=None):
         """eps [B, n_steps, S, N, H, da]: recorded noise in place of device-drawn noise; active [B]: the environments that tick"""
         from ..inference.svmpc import check_optimizer
@@ -627,13 +653,14 @@ class BatchDualSVMPC(_BatchDual):
         -> DualSimResult(states [T, B, ds], actions [T, B, da], p_weights [T, B, N], bw [T, B], costs [T, B], loss [B], status [B],
         n_run [B], a_seq [B, H, da]) with the attribute t0; rows the call did not write - past n_run[b], warm-up rows of p_weights,
         inactive environments - are NaN (n_run: -1).  Afterwards the noted update is, per environment, (actions[n_run - 1],
-        states[n_run - 1]), or the pair the environment came with when n_run <= 0.  The filters' particles are not recorded per
-        period: `dyn_particles` reads them after the call (and carries the noted update out first)."""
+        states[n_run - 1]), or the pair the environment came with when n_run <= 0.  The filters' particles are recorded per period
+        only after set_history() (read `history`); `dyn_particles` reads them after the call (and carries the noted update out first)."""
         from ..inference.svmpc import check_optimizer
         from ..models import CartPoleModel, SkidSteerRobot
 
         sv = self.svmpc
         self._no_rows(sv)
+        sv._history_refusals()
         ctrl, model = sv.likelihood.controller, sv.likelihood.model
         T = int(n_periods)
         if not 1 <= T <= 4096:

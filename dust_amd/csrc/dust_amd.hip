@@ -5567,6 +5567,13 @@ struct dust_svmpc_batch : BatchCore {
   bool have_costs = false, have_forward = false, acts_kept = false;
   std::vector<dust_svmpc_hyper> hyper;  // dust_svmpc_batch_set_hyper: the caller's rows [B], or empty (every environment: the prototype's)
   DevBuf<SvbHyper> hyper_dev;           // ... what the sweep instances read of them
+  // dust_svmpc_batch_set_history: what the rule-driven episodes record, and the last recording of either kind
+  int hist_what = 0;  // DUST_HIST_THETA | DUST_HIST_FILTER
+  struct Hist {
+    DevBuf<float> rows;    // [T][B][row]: only the rows (t, b) with t < ran[b] were written
+    size_t T = 0, row = 0;  // T = 0: nothing recorded
+    std::vector<int> ran;  // [B] the periods every environment ran in the recording call (0: it took no part)
+  } hist_theta, hist_x;
 };
 
 // What an environment without a row of its own runs under: the prototype's values of the fields a dust_svmpc_hyper row overrides
@@ -5700,6 +5707,7 @@ extern "C" int dust_svmpc_batch_clone(const dust_svmpc_batch *src, dust_svmpc_ba
     b->have_costs = src->have_costs;
     b->have_forward = src->have_forward;
     b->acts_kept = src->acts_kept;
+    b->hist_what = src->hist_what;  // (the setting, not the recorded rows)
     return DUST_OK;
   });
 }
@@ -5804,6 +5812,80 @@ extern "C" int dust_svmpc_batch_get_hyper(dust_svmpc_batch *b, dust_svmpc_hyper 
   if (!b->hyper.empty()) std::copy(b->hyper.begin(), b->hyper.end(), rows);
   else std::fill(rows, rows + B, svb_proto_hyper(b->c));
   return DUST_OK;
+}
+
+// The posterior's history (the reference's PolParticles / DynParticles rows, simulations.py:122, 134-137): what the rule-driven episodes
+// record through their recording instances (svmpc_episode.hpp svmpc_sim_hist_kernel / svmpc_dual_sim_hist_period_kernel)
+extern "C" int dust_svmpc_batch_set_history(dust_svmpc_batch *b, int what) {
+  if (!b) return fail(DUST_ERR_INVALID, "null batch");
+  if (what & ~(DUST_HIST_THETA | DUST_HIST_FILTER))
+    return fail(DUST_ERR_INVALID, "dust_svmpc_batch_set_history: what = %d has a bit beyond DUST_HIST_THETA | DUST_HIST_FILTER", what);
+  b->hist_what = what;
+  if (what == 0) {  // off: the recordings go with their buffers (hipFree waits for the device's queued work)
+    HIP_TRY(hipSetDevice(b->c->cfg.device));
+    for (auto h : {&b->hist_theta, &b->hist_x}) {
+      h->T = 0;
+      h->ran.clear();
+      if (h->rows.reset() != 0) return fail(DUST_ERR_HIP, "dust_svmpc_batch_set_history: releasing a history buffer failed");
+    }
+  }
+  return DUST_OK;
+}
+
+extern "C" int dust_svmpc_batch_get_history(dust_svmpc_batch *b, int which, int *n_periods, float *out) {
+  if (!b) return fail(DUST_ERR_INVALID, "null batch");
+  if (which != DUST_HIST_THETA && which != DUST_HIST_FILTER)
+    return fail(DUST_ERR_INVALID, "dust_svmpc_batch_get_history: which = %d is neither DUST_HIST_THETA nor DUST_HIST_FILTER", which);
+  const dust_svmpc_batch::Hist &h = which == DUST_HIST_THETA ? b->hist_theta : b->hist_x;
+  if (h.T == 0)
+    return fail(DUST_ERR_STATE, "no call has recorded %s (dust_svmpc_batch_set_history, then dust_svmpc_batch_simulate / dust_svmpc_dual_batch_simulate)",
+                which == DUST_HIST_THETA ? "the particles' history" : "the filters' history");
+  if (n_periods) *n_periods = (int)h.T;
+  if (!out) return DUST_OK;
+  dust_ctx *c = b->c;
+  const size_t B = (size_t)b->B, n = h.T * B * h.row;
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  std::vector<float> host(n);  // the block comes back once; only the rows the call wrote go on to the caller
+  TRY(d2h(c, host.data(), h.rows, n * sizeof(float)));
+  for (size_t e = 0; e < B; ++e) {
+    const size_t end = std::min(h.T, (size_t)std::max(h.ran[e], 0));
+    for (size_t t = 0; t < end; ++t) memcpy(out + (t * B + e) * h.row, host.data() + (t * B + e) * h.row, h.row * sizeof(float));
+  }
+  return DUST_OK;
+}
+
+// What a recording call refuses - from the setting and the sizes alone, ahead of any allocation, copy or launch.  rec: the kinds this call
+// would record; x_row: Mp P of the pair's filters (the dual call)
+static int svb_hist_check(const dust_svmpc_batch *b, int rec, size_t T, size_t x_row) {
+  if (!rec) return DUST_OK;
+  const dust_ctx *c = b->c;
+  if (!b->hyper.empty())
+    return fail(DUST_ERR_UNSUPPORTED, "per-environment hyper-parameters have no recording episode: dust_svmpc_batch_set_history(batch, 0) first "
+                "(or dust_svmpc_batch_set_hyper(batch, NULL))");
+  if (skid_nav_on(c))
+    return fail(DUST_ERR_UNSUPPORTED, "the navigation cost family has no recording episode: dust_svmpc_batch_set_history(batch, 0) first");
+  const size_t B = (size_t)b->B, n_theta = T * B * (size_t)c->N * (size_t)c->D, n_x = T * B * x_row;
+  if ((rec & DUST_HIST_THETA) && n_theta > DUST_SVMPC_HISTORY_MAX_FLOATS)
+    return fail(DUST_ERR_UNSUPPORTED, "%zu history values of the particles for %zu periods exceed %zu: split the episode into shorter calls", n_theta, T,
+                (size_t)DUST_SVMPC_HISTORY_MAX_FLOATS);
+  if ((rec & DUST_HIST_FILTER) && n_x > DUST_SVMPC_HISTORY_MAX_FLOATS)
+    return fail(DUST_ERR_UNSUPPORTED, "%zu history values of the filters for %zu periods exceed %zu: split the episode into shorter calls", n_x, T,
+                (size_t)DUST_SVMPC_HISTORY_MAX_FLOATS);
+  return DUST_OK;
+}
+// room for a recording of T periods; the recording is valid once the call has set T and ran
+static int svb_hist_room(dust_svmpc_batch *b, dust_svmpc_batch::Hist &h, size_t T, size_t row) {
+  h.T = 0;  // (a call that fails from here on leaves no recording of this kind)
+  h.ran.clear();
+  h.row = row;
+  return h.rows.ensure(T * (size_t)b->B * row);
+}
+// ... the periods every environment ran, nobody who took no part
+static void svb_hist_done(dust_svmpc_batch *b, dust_svmpc_batch::Hist &h, size_t T, const int *ran, const unsigned char *on) {
+  h.ran.assign(ran, ran + b->B);
+  for (int e = 0; e < b->B && on; ++e)
+    if (!on[e]) h.ran[e] = 0;
+  h.T = T;
 }
 
 // lane groups of phase C: the G that needs the fewest rounds of rollouts per lane (ties: the smaller), G N S partials in LDS
@@ -5934,10 +6016,10 @@ static void svb_args(const dust_svmpc_batch *b, int n_steps, const float *eps_de
 // States and mask through the next pinned slot, the kernel's arguments and the ONE launch; nothing waits for the device.  params_dev: the
 // staged parameter rows or NULL; prior: the filters the PRIOR instances draw their rows from, or NULL; episode: the launch runs
 // episode->T ticks, each followed by the plant's step (svmpc_episode.hpp), not one; rules (with episode): ... under the reference's
-// episode rules (svb_sim_body)
+// episode rules (svb_sim_body); hist (with rules; svb_hist_check has passed): ... through the recording instance
 static int svb_go(dust_svmpc_batch *b, const float *states, int n_steps, const float *eps_dev, const float *params_dev, int flags,
                   const unsigned char *active, bool do_forward, const dust::SvbPrior *prior, const dust::SvbEpisode *episode = nullptr,
-                  const dust::SvbRules *rules = nullptr) {
+                  const dust::SvbRules *rules = nullptr, const dust::SvbHist *hist = nullptr) {
   dust_ctx *c = b->c;
   HIP_TRY(hipSetDevice(c->cfg.device));
   TRY(b->in.stage(c, states, active));
@@ -5983,6 +6065,13 @@ static int svb_go(dust_svmpc_batch *b, const float *states, int n_steps, const f
         ke.ru = *rules;
         ke.nav = nv;
         TRY(go(&svmpc_skid_nav_sim_kernel, ke));
+      } else if (hist) {
+        SvmpcSimHistArgs ke;
+        ke.k = k;
+        ke.ep = *episode;
+        ke.ru = *rules;
+        ke.hs = *hist;
+        TRY(by_model(c, [&](auto M) { return go(&svmpc_sim_hist_kernel<M()>, ke); }));
       } else {
         SvmpcSimArgs ke;
         ke.k = k;
@@ -6093,8 +6182,11 @@ static int svb_episode_call(dust_svmpc_batch *b, const float *states, int n_peri
     TRY(rules_check(c, rules, B, active, status, false, false));
     forward = rules->t0 + n_periods > rules->warm_up;
   }
+  const bool record = rules && (b->hist_what & DUST_HIST_THETA);  // (the rule-driven episode alone records, and the particles alone)
+  TRY(svb_hist_check(b, record ? DUST_HIST_THETA : 0, T, 0));
   TRY(svb_call_check(b, states, n_steps, params, false, 0, forward));
   HIP_TRY(hipSetDevice(c->cfg.device));
+  if (record) TRY(svb_hist_room(b, b->hist_theta, T, N * D));
   if (params) TRY(svb_stage_params(b, params, T * B * (size_t)n_steps * M * P));
   if (plant_params) {
     TRY(b->plant.ensure(B * P));
@@ -6119,7 +6211,10 @@ static int svb_episode_call(dust_svmpc_batch *b, const float *states, int n_peri
     rules_fill(ru, rules, c->ds, sec_c.at(b->rec, 0), b->rec + words, B);
     TRY(h2d(c, ru.loss, rules_words_in(loss, status, B).data(), 3 * B * sizeof(float)));
   }
-  TRY(svb_go(b, states, n_steps, nullptr, params ? b->params : nullptr, 0, active, forward, nullptr, &ep, rules ? &ru : nullptr));
+  SvbHist hs;
+  hs.theta = record ? b->hist_theta.rows.get() : nullptr;
+  hs.x = nullptr;
+  TRY(svb_go(b, states, n_steps, nullptr, params ? b->params : nullptr, 0, active, forward, nullptr, &ep, rules ? &ru : nullptr, record ? &hs : nullptr));
   // the records come back once; the rows of inactive environments stay out of the caller's arrays
   std::vector<float> host(n_rec), seq(a_seq ? B * D : 0);
   HIP_TRY(hipMemcpyAsync(host.data(), b->rec, n_rec * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -6137,6 +6232,7 @@ static int svb_episode_call(dust_svmpc_batch *b, const float *states, int n_peri
     rules_words_out(host.data() + words, B, active, ran, loss, status, n_run);
     if (a_seq) env_rows_out(a_seq, seq.data(), B, D, active, ran, warm);
   }
+  if (record) svb_hist_done(b, b->hist_theta, T, ran, active);
   return DUST_OK;
 }
 

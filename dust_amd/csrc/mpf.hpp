@@ -2803,6 +2803,9 @@ static int svb_dual_episode_call(dust_svmpc_batch *b, dust_mpf_batch *mb, const 
     TRY(rules_check(c, rules, B, active, status, false, true));
     forward = rules->t0 + n_periods > rules->warm_up;
   }
+  const int record = rules ? b->hist_what : 0;  // (the rule-driven episode alone records: dust_svmpc_batch_set_history)
+  const size_t x_row = (size_t)m->Mp * (size_t)m->P;
+  TRY(svb_hist_check(b, record, T, x_row));
   TRY(svb_call_check(b, states, n_steps, nullptr, true, 0, forward));
   TRY(dual_batch_pair_check(c, "SVMPC", b->B, mb));
   auto host_lik = [](int model) { return model == DUST_MODEL_SKID_STEER || model == DUST_MODEL_CARTPOLE; };
@@ -2831,6 +2834,8 @@ static int svb_dual_episode_call(dust_svmpc_batch *b, dust_mpf_batch *mb, const 
                    sec_c = lay.add(1, rules != nullptr);
   const size_t words = lay.words(rules != nullptr), n_rec = lay.total();
   TRY(b->rec.ensure(n_rec));
+  if (record & DUST_HIST_THETA) TRY(svb_hist_room(b, b->hist_theta, T, N * D));
+  if (record & DUST_HIST_FILTER) TRY(svb_hist_room(b, b->hist_x, T, x_row));
   // ---- staged once: states and mask; the filters' rows, seeds, plants
   TRY(b->in.stage(c, states, on));
   TRY(st.stage(c, states, actions_prev, mpf_steps, on, prior_seeds, plant_params));
@@ -2869,6 +2874,16 @@ static int svb_dual_episode_call(dust_svmpc_batch *b, dust_mpf_batch *mb, const 
     Prof pr(c, DUST_K_SVMPC_BATCH);
     const hipError_t launched = by_model(c, [&](auto M) -> hipError_t {
       if constexpr (M() == DUST_MODEL_PENDULUM || M() == DUST_MODEL_PARTICLE) {
+        if (record) {  // the recording instance: the same period, plus this period's rows of the history
+          SvmpcDualSimHistPeriodArgs kh;
+          kh.k = ka.k;
+          kh.pr = ka.pr;
+          kh.dp = ka.dp;
+          kh.ds = ka.ds;
+          kh.hs.theta = (record & DUST_HIST_THETA) ? b->hist_theta.rows.get() + t * B * N * D : nullptr;
+          kh.hs.x = (record & DUST_HIST_FILTER) ? b->hist_x.rows.get() + t * B * x_row : nullptr;
+          return launch_on(c->stream, false, &svmpc_dual_sim_hist_period_kernel<M()>, b->B, SVB_THREADS, lds, kh);
+        }
         if (rules) return launch_on(c->stream, false, &svmpc_dual_sim_period_kernel<M()>, b->B, SVB_THREADS, lds, ka);
         SvmpcDualPeriodArgs kp;
         kp.k = ka.k;
@@ -2901,6 +2916,8 @@ static int svb_dual_episode_call(dust_svmpc_batch *b, dust_mpf_batch *mb, const 
     if (a_seq) env_rows_out(a_seq, seq.data(), B, D, active, ran, warm);
   }
   st.commit(mpf_bw, on, bw_out, ran);
+  if (record & DUST_HIST_THETA) svb_hist_done(b, b->hist_theta, T, ran, on);
+  if (record & DUST_HIST_FILTER) svb_hist_done(b, b->hist_x, T, ran, on);
   return DUST_OK;
 }
 

@@ -41,6 +41,14 @@
 // of periods are words in device memory that lane 0 of one launch writes and LATER launches read; a stopping environment clears its
 // byte of the call's run mask with its last store, and every later launch of the call - Silverman's rule, the filters' update, this
 // kernel - skips the environment.  A second body beside svb_dual_period_body: svmpc_dual_period_kernel keeps its text.
+//
+// svmpc_sim_hist_kernel / svmpc_dual_sim_hist_period_kernel (dust_svmpc_batch_set_history): the two rule-driven kernels above plus the
+// posterior's history - the reference's PolParticles / DynParticles rows (simulations.py:122, 134-137).  Behind the sync that closes a
+// period the workgroup copies the environment's particles theta [N][D] - as the period's closing operation left them: the optimiser
+// step while the episode warms up, forward()'s roll afterwards - into theta_hist[t][b], and the dual form also the filter's particles
+// [Mp][P] its tick drew from into x_hist[t][b]: all 512 lanes, strided, float4 where the rows are whole quads, ordinary vector stores.
+// A period that does not run writes nothing.  The copies sit behind `if constexpr (HIST)` in the shared bodies: the instances above
+// keep their code.  No launch is added: the copy rides the period's own.
 #pragma once
 #include "mpf_env.hpp"
 #include "svmpc_batch.hpp"
@@ -208,6 +216,24 @@ __global__ __launch_bounds__(SVB_THREADS) void svmpc_dual_period_kernel(const Sv
   svb_dual_period_body<MODEL>(ka.k, ka.pr, ka.dp);
 }
 
+// The posterior's history (dust_svmpc_batch_set_history): where the recording kernels put a period's rows.  svmpc_sim_hist_kernel: the
+// call's blocks [T][B][..]; svmpc_dual_sim_hist_period_kernel: this period's rows [B][..].  nullptr: that kind is not recorded
+struct SvbHist {
+  float *theta;  // [N][D] per (period, environment)
+  float *x;      // [Mp][P] per (period, environment): the dual form alone
+};
+// n floats src -> dst by every lane of the workgroup, behind a svb_sync() that made `src` visible.  Both rows start n floats times an
+// index behind a hipMalloc'ed base: with n a multiple of 4 they lie on 16-byte boundaries and move as float4
+__device__ __forceinline__ void svb_hist_copy(float *dst, const float *src, const int n) {
+  if ((n & 3) == 0) {
+    const float4 *s4 = reinterpret_cast<const float4 *>(src);
+    float4 *d4 = reinterpret_cast<float4 *>(dst);
+    for (int i = (int)threadIdx.x; i < (n >> 2); i += SVB_THREADS) d4[i] = s4[i];
+  } else {
+    for (int i = (int)threadIdx.x; i < n; i += SVB_THREADS) dst[i] = src[i];
+  }
+}
+
 // The reference's episode rules (run_particle_episode / run_pendulum_simulation, simulations.py:104-130, 217-260) for
 // dust_svmpc_batch_simulate: what svb_sim_body adds to svb_episode_body.  Period t of the call is period g = t0 + t of the episode.
 struct SvbRules {
@@ -277,8 +303,10 @@ __device__ __forceinline__ bool svb_crashed(const SvmpcBatchArgs &a, const float
 // svb_episode_body's loop under the rules.  Whether an environment leaves the loop is computed by EVERY lane from the carry in its
 // registers (cy.x0) and from read-only data (map, rules) - never from a word one lane stored earlier in the launch -, so the decision is
 // the same in all 512 lanes by construction; the loop is left at a period's end alone, behind its closing svb_sync(), and through svb_end.
-template <int MODEL, bool NAV>
-__device__ __forceinline__ void svb_sim_body(const SvmpcBatchArgs &a, const SvbEpisode &ep, const SvbRules &ru, const SkidNav *nav) {
+// HIST (svmpc_sim_hist_kernel): behind the period's closing sync the particles also go to hs->theta[t][env]
+template <int MODEL, bool NAV, bool HIST = false>
+__device__ __forceinline__ void svb_sim_body(const SvmpcBatchArgs &a, const SvbEpisode &ep, const SvbRules &ru, const SkidNav *nav,
+                                             const SvbHist *hs = nullptr) {
   constexpr int DS = SvbDims<MODEL>::DS;
   const int env = (int)blockIdx.x, B = (int)gridDim.x;
   if (a.active && a.active[env] == 0) return;
@@ -325,6 +353,10 @@ __device__ __forceinline__ void svb_sim_body(const SvmpcBatchArgs &a, const SvbE
     }
     n = t + 1;
     svb_sync();  // the roll has read the particles' LDS rows, the next period's phase 0 overwrites them
+    if constexpr (HIST) {  // (the rows every lane stored are visible; the next store to them lies behind phase 0's sync)
+      const int ND = a.N * a.D;
+      svb_hist_copy(hs->theta + row * ND, a.theta + (size_t)env * ND, ND);
+    }
     if (status != 0) break;
   }
   svb_end(a, cy);
@@ -359,8 +391,11 @@ struct SvmpcDualSimPeriodArgs {
 // period unless the environment has just stopped: (a_{n-1}, x_n) then stays pending, as behind a call's last period.  Whether it stops is
 // computed by every lane from the carry in its registers and read-only data; lane 0 stores all of it, and clears the environment's byte
 // of the run mask with its LAST store: the filter launches and period launches queued behind this one skip the environment.
-template <int MODEL>
-__device__ __forceinline__ void svb_dual_sim_period_body(const SvmpcBatchArgs &a, const SvbPrior &pri, const SvbDualPeriod &dp, const SvbDualSim &ru) {
+// HIST (svmpc_dual_sim_hist_period_kernel): behind a sync of its own the particles also go to hs->theta[env], and the filter's particles
+// the tick drew from - read-only in this launch - to hs->x[env]
+template <int MODEL, bool HIST = false>
+__device__ __forceinline__ void svb_dual_sim_period_body(const SvmpcBatchArgs &a, const SvbPrior &pri, const SvbDualPeriod &dp, const SvbDualSim &ru,
+                                                         const SvbHist *hs = nullptr) {
   static_assert(MODEL == DUST_MODEL_PENDULUM || MODEL == DUST_MODEL_PARTICLE, "the other families' likelihood rows are made on the host");
   constexpr int DS = SvbDims<MODEL>::DS;
   const int env = (int)blockIdx.x;
@@ -374,6 +409,12 @@ __device__ __forceinline__ void svb_dual_sim_period_body(const SvmpcBatchArgs &a
   float loss = ru.loss[env];
   float act[2] = {0.f, 0.f};  // (warm-up: no forward() writes it - the plant gets the zero action)
   svb_tick<MODEL, true, false, true>(a, &pri, nullptr, cy, map, w_obs, dp.pw_out ? dp.pw_out + (size_t)env * a.N : nullptr, act);
+  if constexpr (HIST) {
+    svb_sync();  // the roll's stores (the last iteration's, while the episode warms up) are visible to every lane
+    const int ND = a.N * a.D, KP = pri.K * pri.P;
+    if (hs->theta) svb_hist_copy(hs->theta + (size_t)env * ND, a.theta + (size_t)env * ND, ND);
+    if (hs->x) svb_hist_copy(hs->x + (size_t)env * KP, pri.means + (size_t)env * KP, KP);
+  }
   svb_plant_step<MODEL>(a, cf, cy.x0, act);
   const float cost = svb_state_cost<MODEL, false>(a, cy.x0, map, w_obs);
   loss += cost;
@@ -440,6 +481,30 @@ __global__ __launch_bounds__(SVB_THREADS) void svmpc_rows_sim_kernel(const Svmpc
   SvmpcBatchArgs a = ka.k;
   SVB_HYPER_APPLY(a, h);
   svb_sim_body<MODEL, false>(a, ka.ep, ka.ru, nullptr);
+}
+
+// The recording forms (dust_svmpc_batch_set_history): new kernels over new argument blocks, the bodies above with HIST set.  Plain cost,
+// launch-uniform hyper-parameters: the navigation and the per-environment instances have no recording form (the host refuses)
+struct SvmpcSimHistArgs {
+  SvmpcBatchArgs k;
+  SvbEpisode ep;
+  SvbRules ru;
+  SvbHist hs;  // theta: [T][B][N][D]
+};
+template <int MODEL>
+__global__ __launch_bounds__(SVB_THREADS) void svmpc_sim_hist_kernel(const SvmpcSimHistArgs ka) {
+  svb_sim_body<MODEL, false, true>(ka.k, ka.ep, ka.ru, nullptr, &ka.hs);
+}
+struct SvmpcDualSimHistPeriodArgs {
+  SvmpcBatchArgs k;
+  SvbPrior pr;
+  SvbDualPeriod dp;
+  SvbDualSim ds;
+  SvbHist hs;  // this period's rows: theta [B][N][D], x [B][Mp][P]; either may be nullptr
+};
+template <int MODEL>
+__global__ __launch_bounds__(SVB_THREADS) void svmpc_dual_sim_hist_period_kernel(const SvmpcDualSimHistPeriodArgs ka) {
+  svb_dual_sim_period_body<MODEL, true>(ka.k, ka.pr, ka.dp, ka.ds, &ka.hs);
 }
 
 }  // namespace dust

@@ -248,6 +248,7 @@ class BatchSVMPC:
         self._batch = None
         self._key = None
         self._hyper = None  # set_hyper(): per-environment rows (a dict of arrays), kept here until - and whenever - a batch is built
+        self._history = (False, False)  # set_history(): (theta, filter), kept here likewise
         self.optimizer = optimizer_class(params=[torch.zeros(1, requires_grad=True)], **opt_args)
         self._opt_group = group_options(self.optimizer)
 
@@ -281,6 +282,8 @@ class BatchSVMPC:
             self._batch.set(L.SVB_THETA, self._theta0.numpy())
         if self._hyper is not None:  # the per-environment rows belong to this object: a new or a rebuilt batch gets them again
             self._batch.set_hyper(self._hyper)
+        if any(self._history):
+            self._batch.set_history(*self._history)
         return self._batch
 
     # -- per-environment hyper-parameters: the trials of a tuning sweep as the environments of one batch
@@ -359,6 +362,38 @@ class BatchSVMPC:
         out = {k: np.array(v) for k, v in rows.items()}
         out["weighted_prior"] = np.asarray(out["weighted_prior"], np.int32)
         return out
+
+    # -- the posterior's history: the reference's PolParticles / DynParticles rows (simulations.py:122, 134-137) out of the device episodes
+    def set_history(self, theta=True, filter=False):
+        """What simulate() records from now on (dust_svmpc_batch_set_history): `theta` - the particles after every period, written by the
+        episode's own kernel (svmpc_sim_hist_kernel; no launch is added, nothing the episode computes changes); `filter` - the filters'
+        particles, which only the dual loop has (BatchDualSVMPC.set_history).  Both False: recording off.  simulate()'s signature and
+        result do not change: read the rows from `history`.  Deep copies carry the setting, not the rows."""
+        self._history = (bool(theta), bool(filter))
+        if self._batch is not None:
+            self._batch.set_history(*self._history)
+
+    @property
+    def history(self):
+        """{'theta': [T, B, N, H, da]} of the last recording simulate(): theta[t] is `theta` after period t (optimize() while the episode
+        warms up, tick() afterwards); rows an environment did not run are NaN.  The library raises (DUST_ERR_STATE) while nothing is
+        recorded."""
+        from .. import _lib as L
+
+        if self._batch is None:
+            raise RuntimeError("nothing is recorded yet: set_history(), then simulate()")
+        return {"theta": torch.from_numpy(self._batch.history(L.HIST_THETA))}
+
+    def _history_refusals(self):
+        """what a recording episode refuses, ahead of any device call: there is no recording instance for these two forms"""
+        if not any(self._history):
+            return
+        from ..costs import cost_grid_key
+
+        if self._hyper is not None:
+            raise NotImplementedError("a recording episode has no per-environment hyper-parameters: set_history(False, False) first (or set_hyper())")
+        if cost_grid_key(self.likelihood.controller.inst_cost_fn) is not None:
+            raise NotImplementedError("a recording episode has no navigation cost: set_history(False, False) first")
 
     def __deepcopy__(self, memo):
         import copy
@@ -486,6 +521,8 @@ class BatchSVMPC:
         [B, H, da]) with the attribute t0 (the periods the episode has run); rows the call did not write - past n_run[b], warm-up rows
         of p_weights, inactive environments - are NaN (n_run: -1)."""
         check_optimizer(self.optimizer, self._opt_group)
+        if self._history[0]:  # (with `filter` alone the plain episode records nothing)
+            self._history_refusals()
         ctrl, model = self.likelihood.controller, self.likelihood.model
         T, warm_up = int(n_periods), int(warm_up)
         if not 1 <= T <= 4096:

@@ -144,9 +144,45 @@ def run_particle_episode(init_state, model, dyn_dist, controller, use_svmpc=True
     return cum_cost
 
 
+_PIECE = 4096  # the periods one device episode call takes: a longer episode is a chain of pieces
+
+
+def posterior_history_columns(theta_pieces, x_pieces, final_x, warm_up, n_run=None):
+    """The reference frame's `PolParticles` / `DynParticles` columns (simulations.py:122, 134-137) from the rows the device episodes
+    record - a pure host function over arrays.  theta_pieces: the pieces' `theta` histories [T_i, B, N, H, da] in episode order;
+    x_pieces: their filter histories [T_i, B, Mp, P] - row t holds the filter period t's tick drew from, that is BEFORE the pair of
+    period t is folded in; final_x [B, Mp, P]: the filters with the episode's last pair folded in (`dual.dyn_particles`); warm_up: the
+    episode's warm-up periods; n_run [B]: the periods every environment ran (None: all of them).
+    -> (DynParticles [B, steps, Mp, P], PolParticles [B, steps, N]):
+       PolParticles[:, t] = theta[..., 0, 0] after period t, NaN while the episode warms up (the reference stores a row only behind a
+       forward());
+       DynParticles[:, t] = the filter after it folded in the pair of period t: row t + 1 of the recording - across a piece's end row 0
+       of the next piece, whose update runs from the noted pair - and, for an environment's last period, final_x.
+    Rows past n_run[b] are NaN."""
+    import numpy as np
+
+    theta = np.concatenate([np.asarray(v, np.float32) for v in theta_pieces])  # [steps, B, N, H, da]
+    x = np.concatenate([np.asarray(v, np.float32) for v in x_pieces])          # [steps, B, Mp, P]
+    final_x = np.asarray(final_x, np.float32)
+    steps, B = theta.shape[:2]
+    if x.shape[:2] != (steps, B) or final_x.shape != x.shape[1:]:
+        raise ValueError("histories of %s and %s rows, final particles %s" % (theta.shape[:2], x.shape[:2], final_x.shape))
+    n_run = np.full(B, steps, np.int64) if n_run is None else np.asarray(n_run, np.int64).reshape(B)
+    pol = theta[..., 0, 0].transpose(1, 0, 2).copy()  # [B, steps, N]
+    pol[:, :min(int(warm_up), steps)] = np.nan
+    dyn = np.full((B, steps) + x.shape[2:], np.nan, np.float32)
+    dyn[:, :steps - 1] = x[1:].transpose(1, 0, 2, 3)
+    for b in range(B):
+        n = int(min(max(n_run[b], 0), steps))
+        dyn[b, n:], pol[b, n:] = np.nan, np.nan
+        if n > 0:
+            dyn[b, n - 1] = final_x[b]
+    return dyn, pol
+
+
 def run_pendulum_simulations(init_state, init_policies, model_kwargs, experiment_params, controller, svmpc_kwargs, lik_kwargs, mpf, mpf_bw=None,
                              mpf_steps=20, episodes=3, steps=200, warm_up=1, seed=0, init_particles=None, frame=False, *, use_svmpc=True,
-                             dyn_dist=None, use_exact_model=False, mpf_hyper=None):
+                             dyn_dist=None, use_exact_model=False, mpf_hyper=None, history=False):
     """The batched twin of `run_pendulum_simulation(use_svmpc=True, mpf=...)`: the `episodes` become the B environments of one
     `BatchSVMPC` plus `BatchDualSVMPC`, environment i's plant runs under `experiment_params[i]`, and the whole loop - warm-up periods
     that only optimize and apply a zero action while the filters keep updating, the cost of every new state - runs on the device, one
@@ -165,7 +201,10 @@ def run_pendulum_simulations(init_state, init_policies, model_kwargs, experiment
     -> a dict of arrays under the reference frame's column names, [B, steps] unless stated: `Cost`, `Position`, `Speed`, `Actions`,
     `Timestep`, `Iteration`, `DynBandwidths`, `Weights` [B, steps, N] (NaN while warming up), `ExpParams` [B, steps, P], `AvgCumCost`,
     and - the episode is not interrupted to read them - `DynParticles` [B, Mp, P] and `PolParticles` [B, N]: the FINAL filter particles
-    (the last pair folded in) and the final particles' first actions, not one row per period.  frame=True: the reference's pandas
+    (the last pair folded in) and the final particles' first actions, not one row per period.  history=True (keyword only): one row
+    per period, as the reference's frame has them - `DynParticles` [B, steps, Mp, P], the filter after it folded in the pair of period
+    t, and `PolParticles` [B, steps, N], the particles' first actions after period t (NaN while warming up) - recorded by the episodes'
+    own kernels (`BatchDualSVMPC.set_history`): still no interruption, no launch more.  frame=True: the reference's pandas
     frame of the per-period columns, when pandas imports (it is optional here); otherwise the dict.
 
     use_svmpc=False (keyword only): the `use_svmpc=False` branch of the lone driver (simulations.py:124-126) - the MPPI-baseline and DISCO
@@ -197,13 +236,17 @@ def run_pendulum_simulations(init_state, init_policies, model_kwargs, experiment
     dual = BatchDualSVMPC(sv, mpf, mpf_bw=mpf_bw, mpf_steps=mpf_steps, seed=seed, init_particles=init_particles, warm_up=warm_up)
     if mpf_hyper is not None:
         dual.set_filter_hyper(mpf_hyper)
+    if history:
+        dual.set_history(theta=True, filter=True)
     true = torch.tensor([[float(experiment_params[i].get(k, model.params_dict[k])) for k in names] for i in range(B)], dtype=torch.float)
     rows = true.log() if bool(sim_ctrl._params_log_space) else true
     state = torch.as_tensor(init_state, dtype=torch.float).reshape(1, -1).repeat(B, 1)
-    out, res = [], None
-    for lo in range(0, steps, 4096):
-        res = dual.simulate(state, min(4096, steps - lo), plant_params=rows, resume=res)
+    out, res, hist = [], None, []
+    for lo in range(0, steps, _PIECE):
+        res = dual.simulate(state, min(_PIECE, steps - lo), plant_params=rows, resume=res)
         out.append(res)
+        if history:
+            hist.append(dual.history)
         state = res.states[-1]
     cat = lambda k: torch.cat([getattr(r, k) for r in out]).transpose(0, 1).numpy()  # [B, steps, ...]
     xs, cost = cat("states"), cat("costs")
@@ -213,6 +256,9 @@ def run_pendulum_simulations(init_state, init_policies, model_kwargs, experiment
             "DynBandwidths": cat("bw"), "PolParticles": dual.theta[:, :, 0, 0].numpy(), "Weights": cat("p_weights"),
             "ExpParams": np.broadcast_to(true.numpy()[:, None], (B, steps, len(names))).copy(),
             "AvgCumCost": np.round(np.cumsum(cost.astype(np.float64), 1) / (t + 1), 2)}
+    if history:
+        data["DynParticles"], data["PolParticles"] = posterior_history_columns(
+            [h["theta"].numpy() for h in hist], [h["dyn_particles"].numpy() for h in hist], data["DynParticles"], warm_up)
     if frame:
         try:
             import pandas as pd

@@ -32,8 +32,8 @@ from dust_amd.utils.simulations import run_pendulum_simulations  # noqa: E402
 TINY = dict(episodes=3, steps=5, warm_up=2, horizon=4, n_particles=2, action_samples=8, params_samples=2, mpf_n_particles=8, mpf_steps=2)
 
 
-def run(episodes=8, steps=200, warm_up=10, seed=0, quiet=False, **over):
-    """-> (the dict of run_pendulum_simulations, the true (length, mass) [B, 2])"""
+def run(episodes=8, steps=200, warm_up=10, seed=0, quiet=False, history=False, **over):
+    """-> (the dict of run_pendulum_simulations, the true (length, mass) [B, 2]); history: one DynParticles / PolParticles row per period"""
     e = dict(DEFAULTS["exp_params"], **over)
     torch.manual_seed(seed)
     N, H, S, M, alpha = e["n_particles"], e["horizon"], e["action_samples"], e["params_samples"], e["alpha"]
@@ -57,9 +57,9 @@ def run(episodes=8, steps=200, warm_up=10, seed=0, quiet=False, **over):
     data = run_pendulum_simulations(init_state, init_policies, dict(g=10.0, uncertain_params=("length", "mass")),
                                     [dict(length=float(v[0]), mass=float(v[1])) for v in true], controller, svmpc_kwargs,
                                     dict(alpha=alpha, n_samples=S), mpf, mpf_bw=e["mpf_bandwidth"], mpf_steps=e["mpf_steps"], episodes=episodes,
-                                    steps=steps, warm_up=warm_up, seed=seed, init_particles=mpf_init)
+                                    steps=steps, warm_up=warm_up, seed=seed, init_particles=mpf_init, history=history)
     if not quiet:
-        est = data["DynParticles"].mean(1)
+        est = (data["DynParticles"][:, -1] if history else data["DynParticles"]).mean(1)
         print("%d periods of %d pendulums, %d of them warm-up: final mean |angle| %.2f rad"
               % (steps, episodes, min(warm_up, steps), float(abs(data["Position"][:, -1]).mean())))
         for b in range(episodes):

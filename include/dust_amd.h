@@ -563,6 +563,34 @@ int dust_svmpc_batch_simulate(dust_svmpc_batch *batch, const float *states, int 
                               const float *plant_params, const dust_episode_rules *rules, int flags, const unsigned char *active,
                               float *states_out, float *actions_out, float *pw_out, float *costs_out /* [T][B] */,
                               float *loss /* [B] in-out */, int *status /* [B] in-out */, int *n_run /* [B] out */, float *a_seq);
+/* The posterior's history: the reference's per-period PolParticles / DynParticles rows (run_pendulum_simulation, simulations.py:122 and
+ * 134-137; what plot_stein_particles and plot_dist_ridgeplot draw) out of the device episodes, written by the episodes' own kernels -
+ * recording forms of the two rule-driven kernels (svmpc_episode.hpp svmpc_sim_hist_kernel / svmpc_dual_sim_hist_period_kernel) whose
+ * workgroups copy their rows behind a period's closing sync.  No launch, copy or host round trip is added to a call, and nothing a call
+ * computes changes.
+ * dust_svmpc_batch_set_history(batch, what): what later calls record, a mask of DUST_HIST_THETA | DUST_HIST_FILTER; 0: nothing, and the
+ *   buffers are released.  Nothing else of the batch changes.  DUST_ERR_INVALID for any other bit.
+ *   While a bit is set dust_svmpc_batch_simulate records theta (DUST_HIST_THETA; with DUST_HIST_FILTER alone it records nothing) and
+ *   dust_svmpc_dual_batch_simulate records theta (DUST_HIST_THETA) and the filters' particles (DUST_HIST_FILTER), into device buffers the
+ *   batch owns, grown on demand.  Every other entry ignores the setting: it records nothing and the last recording stays.
+ *   theta_hist[t] is what dust_svmpc_batch_get(DUST_SVB_THETA) returns after the t-th per-period call - dust_svmpc_batch_optimize /
+ *   dust_svmpc_dual_batch_optimize while the episode warms up, the tick afterwards.  x_hist[t] is what dust_mpf_batch_get_particles returns
+ *   after the t-th per-period dual call: the particles period t's dynamics samples were drawn from - in a period 0 without actions_prev
+ *   the particles at entry.
+ *   Refused by a recording call before anything is allocated, staged or launched, the batch and the in-out arrays unchanged, with
+ *   DUST_ERR_UNSUPPORTED: more than DUST_SVMPC_HISTORY_MAX_FLOATS values of one kind (T B N H da, or T B Mp P: split the episode into
+ *   shorter calls); a batch with per-environment controller rows (dust_svmpc_batch_set_hyper) or with the navigation cost - neither has a
+ *   recording instance: dust_svmpc_batch_set_history(batch, 0) first.  Per-environment FILTER rows (dust_mpf_batch_set_hyper) touch the
+ *   filters' kernels alone and keep working.  dust_svmpc_batch_clone copies the setting, not the recorded rows.
+ * dust_svmpc_batch_get_history(batch, which, n_periods, out): the last recording of ONE kind (DUST_HIST_THETA or DUST_HIST_FILTER; anything
+ *   else DUST_ERR_INVALID); DUST_ERR_STATE when no call has recorded that kind (or since set_history(batch, 0)).  *n_periods (may be
+ *   NULL) receives T of the recording call; out (host; may be NULL to ask for T alone) is [T][B][N][H][da], or [T][B][Mp][P], copied
+ *   once.  Rows (t, b) the call did not run - t >= n_run[b], inactive environments, environments that entered stopped - are NOT written:
+ *   the caller's fill stays (the reference fills with NaN). */
+enum { DUST_HIST_THETA = 1, DUST_HIST_FILTER = 2 };
+#define DUST_SVMPC_HISTORY_MAX_FLOATS ((size_t)1 << 28) /* per kind and call: 1 GiB */
+int dust_svmpc_batch_set_history(dust_svmpc_batch *batch, int what);
+int dust_svmpc_batch_get_history(dust_svmpc_batch *batch, int which, int *n_periods, float *out);
 
 /* ---- MultiDISCO over a batch of plants (ABI 3): B independent controllers - the MPPI baseline of the reference's demo/pendulum_example.py,
  * disco.py:139-417 - whose forward(), step() or both are ONE kernel launch (csrc/disco_batch.hpp), counted under DUST_K_ROLLOUT, the slot
@@ -973,7 +1001,8 @@ int dust_svmpc_dual_batch_optimize(dust_svmpc_batch *batch, dust_mpf_batch *mpf,
  * Rows t >= n_run[b] of states_out / actions_out / pw_out / bw_out / costs_out are NOT written, nor anything of an inactive environment;
  * bw_out[t][b] is 0 where no update ran; a_seq receives an environment's row only when one of its periods ran forward().  An environment
  * entering with status != 0 does nothing: only n_run[b] = 0 is written.  With warm_up = 0, no goal and no crash rule the call computes,
- * bit for bit, what dust_svmpc_dual_batch_episode computes.  The filters' particles are not recorded per period: read them after the call.
+ * bit for bit, what dust_svmpc_dual_batch_episode computes.  The filters' particles are recorded per period only while
+ * dust_svmpc_batch_set_history(DUST_HIST_FILTER) is on; otherwise read them after the call.
  * Refused before anything is staged or launched, both batches and the in-out arrays unchanged.  DUST_ERR_INVALID: what
  * dust_svmpc_dual_batch_episode refuses; NULL rules, loss, status, n_run or costs_out; t0 < 0 or warm_up < 0; a goal or radius that is
  * not finite; an entry status outside 0 .. 2.  DUST_ERR_UNSUPPORTED: stop_on_crash without a Particle with_obstacle map; a skid-steer or
