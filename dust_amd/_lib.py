@@ -218,6 +218,11 @@ SYMBOLS = {
     "dust_svmpc_dual_batch_simulate": (C.c_int, [VP, VP, FP, FP, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_uint64), FP,
                                                  C.POINTER(EpisodeRules), C.c_int, C.POINTER(C.c_ubyte), FP, FP, FP, FP, FP, FP, C.POINTER(C.c_int),
                                                  C.POINTER(C.c_int), FP]),
+    "dust_amppi_batch_simulate": (C.c_int, [VP, FP, C.c_int, FP, C.c_int, C.c_int, FP, C.POINTER(EpisodeRules), C.POINTER(C.c_ubyte), FP, FP, FP, FP,
+                                            FP, FP, C.POINTER(C.c_int), C.POINTER(C.c_int), FP]),
+    "dust_amppi_dual_batch_simulate": (C.c_int, [VP, VP, FP, FP, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_uint64), C.c_int, FP,
+                                                 C.POINTER(EpisodeRules), C.POINTER(C.c_ubyte), FP, FP, FP, FP, FP, FP, FP, C.POINTER(C.c_int),
+                                                 C.POINTER(C.c_int), FP]),
     "dust_get_costs": (C.c_int, [VP, FP]),
     "dust_get_actions": (C.c_int, [VP, FP]),
     "dust_get_states_rows": (C.c_int, [VP, C.POINTER(C.c_longlong), C.c_int, VP]),

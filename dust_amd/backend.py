@@ -902,6 +902,65 @@ class AmppiBatch(_BatchHandle):
                                                        _p(xs), _p(acts), _p(costs), _p(omega), _p(bw), _p(a_seq)))
         return xs, acts, costs, omega, bw, a_seq
 
+    def simulate(self, states, n_periods, params=None, shared_params=False, plant_params=None, t0=0, goal=None, goal_radius=None,
+                 stop_on_crash=False, loss=None, status=None, active=None, roll_steps=1, want_costs=True, flags=0, warm_up=0):
+        """episode() under the reference's episode rules (dust_amppi_batch_simulate), still one launch per period and no host between two
+        periods.  Period t is period t0 + t of the episode; this branch of the reference has no warm-up (warm_up != 0: the library
+        refuses).  The family's instantaneous cost of every new state goes to `inst_costs` and, as an fp32 running sum, to `loss`; with
+        stop_on_crash a new position on an occupied cell ends the environment with loss = inf, status 2; with goal [ds] and
+        goal_radius > 0, |goal - x|^2 <= radius^2 ends it with status 1.  loss / status [B]: where a previous call left them (None: 0).
+        -> (states [T, B, ds], actions [T, B, da], costs [T, B, S] or None, omega [T, B, S] or None, inst_costs [T, B], loss [B],
+        status [B] int32, n_run [B] int32, a_seq [B, H, da] of every environment's last period before its roll); rows the call did not
+        write - past n_run[b], inactive environments - are NaN (n_run: -1)."""
+        B, T, S = self.B, int(n_periods), self.S
+        st = None if states is None else _f(states, (B, self.ds))  # (None: the library refuses)
+        pr = None
+        if params is not None:
+            pr = _f(params)
+            want = (T, B, self.M if self.M > 1 else (1 if shared_params else S), max(self.P, 1))
+            if pr.shape != want:
+                raise ValueError("params has shape %s, the call reads %s" % (pr.shape, want))
+        pl = _plant_rows(plant_params, B, self.P)
+        ru = _episode_rules(self.ds, t0, warm_up, goal, goal_radius, stop_on_crash)
+        _, mp = _mask(active, B)
+        rows = max(T, 0)  # (n_periods < 1: the library refuses before it writes anything)
+        xs, acts, ic, a_seq = (np.full(sh, np.nan, np.float32) for sh in ((rows, B, self.ds), (rows, B, self.da), (rows, B), (B, self.H, self.da)))
+        costs, omega = ((np.full((rows, B, S), np.nan, np.float32) for _ in range(2)) if want_costs else (None, None))
+        loss, status, n_run, IP = _rules_state(B, loss, status)
+        fl = int(flags) | (L.AMPPI_PARAMS_SHARED if shared_params else 0)
+        L.check(L.load().dust_amppi_batch_simulate(self._h, _p(st), T, _p(pr), fl, int(roll_steps), _p(pl), C.byref(ru), mp, _p(xs), _p(acts),
+                                                   _p(costs), _p(omega), _p(ic), _p(loss), status.ctypes.data_as(IP), n_run.ctypes.data_as(IP),
+                                                   _p(a_seq)))
+        return xs, acts, costs, omega, ic, loss, status, n_run, a_seq
+
+    def dual_simulate(self, mpf, states, n_periods, actions_prev=None, shared_params=False, mpf_steps=20, mpf_bw=None, seeds=None, roll_steps=1,
+                      plant_params=None, t0=0, goal=None, goal_radius=None, stop_on_crash=False, loss=None, status=None, active=None,
+                      want_costs=True, flags=0, warm_up=0):
+        """dual_episode() under the reference's episode rules, in one C call (dust_amppi_dual_batch_simulate): the cost of every new state
+        goes to `inst_costs` and, as an fp32 running sum, to `loss`; crash (status 2, loss inf) and goal (status 1) stop an environment
+        on both sides - no further filter update, no tick -, and its pair (a_{n-1}, x_n) stays pending.  No warm-up.  loss / status [B]:
+        where a previous call left them.  -> (states [T, B, ds], actions [T, B, da], costs [T, B, S] or None, omega [T, B, S] or None,
+        bw [T, B], inst_costs [T, B], loss [B], status [B] int32, n_run [B] int32, a_seq [B, H, da]); rows the call did not write - past
+        n_run[b], inactive environments - are NaN (n_run: -1)."""
+        B, T, S = self.B, int(n_periods), self.S
+        st = None if states is None else _f(states, (B, self.ds))  # (None: the library refuses)
+        ap = None if actions_prev is None else _f(actions_prev, (B, self.da))
+        rows = max(T, 0)  # (n_periods < 1: the library refuses before it reads or writes anything)
+        sd, sp = _period_seeds(seeds, rows, B)
+        pl = _plant_rows(plant_params, B, self.P)
+        ru = _episode_rules(self.ds, t0, warm_up, goal, goal_radius, stop_on_crash)
+        _, mp = _mask(active, B)
+        xs, acts, bw, ic, a_seq = (np.full(sh, np.nan, np.float32)
+                                   for sh in ((rows, B, self.ds), (rows, B, self.da), (rows, B), (rows, B), (B, self.H, self.da)))
+        costs, omega = ((np.full((rows, B, S), np.nan, np.float32) for _ in range(2)) if want_costs else (None, None))
+        loss, status, n_run, IP = _rules_state(B, loss, status)
+        fl = int(flags) | (L.AMPPI_PARAMS_SHARED if shared_params else 0)
+        L.check(L.load().dust_amppi_dual_batch_simulate(self._h, mpf._h, _p(st), _p(ap), T, fl, int(mpf_steps),
+                                                        float(-1.0 if mpf_bw is None else mpf_bw), sp, int(roll_steps), _p(pl), C.byref(ru), mp,
+                                                        _p(xs), _p(acts), _p(costs), _p(omega), _p(bw), _p(ic), _p(loss),
+                                                        status.ctypes.data_as(IP), n_run.ctypes.data_as(IP), _p(a_seq)))
+        return xs, acts, costs, omega, bw, ic, loss, status, n_run, a_seq
+
 
 class SvmpcBatch(_BatchHandle):
     """B independent SVMPC ticks in one launch (dust_svmpc_batch_*): per environment a state, particles, a prior, a_mat, optimiser

@@ -6,6 +6,7 @@ The controller owns one device context; `a_seq` lives there.  Parameter draws co
 (n = 1 or n_samples rows of a handful of columns: base.py:149-171), sigma points from `model.params_dist` through
 `dust_amd.utils.utf.MerweScaledUTF`; everything else of the tick - noise, rollouts, costs, weights, the update - runs on the device.
 `copy.deepcopy(controller)` clones the context."""
+import collections
 import copy
 
 import numpy as np
@@ -342,3 +343,98 @@ class BatchAMPPI(AMPPI):
                                                   plant_params=plant_params, active=None if active is None else on, roll_steps=roll_steps)
         t = torch.from_numpy
         return t(xs), t(acts), t(costs), t(omega)
+
+    # -- run_particle_episode's use_svmpc=False branch / run_pendulum_simulation's AMPPI loop (simulations.py:217-260, 124-160) for every
+    # environment: the episode under the reference's rules - the accumulated cost, crash and goal; this branch has no warm-up
+    def simulate(self, model, states, n_periods, goal=None, goal_radius=None, stop_on_crash=False, plant_params=None, active=None, roll_steps=1,
+                 resume=None, params=None):
+        """run_episodes() under the reference's episode rules (dust_amppi_batch_simulate), still one launch per period and no host between
+        two periods: the controller's instantaneous cost of every new state is recorded and summed in fp32 into `loss`; `stop_on_crash`: a
+        new position on an occupied cell of the model's (or the navigation cost's) map ends the environment with loss = inf, status 2;
+        `goal` [ds] with `goal_radius` > 0: an environment within the radius ends with status 1.  `resume`: the result of a previous call
+        - the episode goes on from its loss, status and period index (a changed plant, such as the reference's load at steps // 4, is two
+        calls).  The parameter rows are drawn as run_episodes() draws them - under one torch.manual_seed the call consumes the torch
+        stream as `n_periods` calls of update_actions with the same `active` do - unless `params` [T, B, rows, P] overrides them.
+        -> AmppiSimResult(states [T, B, ds], actions [T, B, da], costs [T, B, S], omega [T, B, S], inst_costs [T, B], loss [B], status
+        [B], n_run [B], a_seq [B, H, da] of every environment's last period before its roll) with the attribute t0 (the periods the
+        episode has run); rows the call did not write - past n_run[b], inactive environments - are NaN (n_run: -1)."""
+        T, B = int(n_periods), self.n_envs
+        if not 1 <= T <= 4096:
+            raise ValueError("n_periods = %d outside [1, 4096]: one call runs one episode piece, split a longer one" % T)
+        if roll_steps < 1:
+            raise ValueError("roll(steps=%d): steps >= 1" % roll_steps)
+        on = self._active(active)
+        sampled = self._tf is not None or bool(self._sample_shape)
+        P = len(getattr(model, "uncertain_params", None) or ()) if sampled else 0
+        if plant_params is not None:
+            plant_params = np.asarray(torch.as_tensor(plant_params, dtype=torch.float).numpy(), np.float32)
+            if P == 0 or plant_params.shape != (B, P):
+                raise ValueError("plant_params has shape %s, the plants read %s" % (plant_params.shape, (B, P) if P else "none"))
+        goal, goal_radius = _sim_goal(goal, goal_radius, self.dim_s)
+        if stop_on_crash:
+            has_map = (getattr(model, "family", None) == "particle" and bool(model.with_obstacle)) or cost_grid_key(self.inst_cost_fn) is not None
+            if not has_map:
+                raise ValueError("stop_on_crash needs an occupancy map: Particle(with_obstacle=True) or a NavigationCost")
+        t0, loss, status = _sim_resume(resume, B)
+        states = torch.as_tensor(states, dtype=torch.float).reshape(B, -1)
+        batch = self._ensure_batch(model)
+        if params is not None:
+            params = np.asarray(torch.as_tensor(params, dtype=torch.float).numpy(), np.float32)
+        elif self._tf is not None and on.any():
+            params = np.stack([np.repeat(self._sigma_points(model)[None], B, 0) for _ in range(T)])
+        elif self._sample_shape and on.any():
+            per = []
+            for _ in range(T):  # (update_actions' draws: once per active environment, in environment order)
+                rows = [model.dict_to_params(model.sample_params(self._sample_shape)).numpy() if on[b] else None for b in range(B)]
+                shape = next(r.shape for r in rows if r is not None)
+                per.append(np.stack([r if r is not None else np.zeros(shape, np.float32) for r in rows]))
+            params = np.stack(per)
+        if params is None and sampled:  # nobody ticks: nothing to launch
+            nan = lambda *sh: torch.full(sh, float("nan"))
+            S = self.n_samples
+            res = AmppiSimResult(nan(T, B, states.shape[1]), nan(T, B, self.dim_a), nan(T, B, S), nan(T, B, S), nan(T, B),
+                                 torch.zeros(B) if loss is None else torch.from_numpy(np.array(loss, np.float32)),
+                                 torch.zeros(B, dtype=torch.int32) if status is None else torch.from_numpy(np.array(status, np.int32)),
+                                 torch.full((B,), -1, dtype=torch.int32), nan(B, self.hz_len, self.dim_a))
+            res.t0 = t0 + T
+            return res
+        out = batch.simulate(states.numpy(), T, params, shared_params=self._params_sampling == "single" and params is not None,
+                             plant_params=plant_params, t0=t0, goal=goal, goal_radius=goal_radius, stop_on_crash=stop_on_crash, loss=loss,
+                             status=status, active=None if active is None else on, roll_steps=roll_steps)
+        res = AmppiSimResult(*(torch.from_numpy(np.ascontiguousarray(v)) for v in out))
+        res.t0 = t0 + T
+        return res
+
+
+def _sim_goal(goal, goal_radius, ds):
+    """the goal rule's arguments as the library reads them (both None: no goal rule); refused on the host what needs no device"""
+    if (goal is None) != (goal_radius is None):
+        raise ValueError("goal and goal_radius come together")
+    if goal is None:
+        return None, None
+    goal = np.asarray(torch.as_tensor(goal, dtype=torch.float).numpy(), np.float32).reshape(-1)
+    if goal.shape != (ds,) or not np.isfinite(goal).all():
+        raise ValueError("goal has shape %s: [%d] finite entries" % (goal.shape, ds))
+    if not (np.isfinite(float(goal_radius)) and float(goal_radius) > 0):
+        raise ValueError("goal_radius must be finite and > 0")
+    return goal, float(goal_radius)
+
+
+def _sim_resume(resume, B):
+    """(t0, loss, status) a call goes on from: the result of a previous simulate(), or the episode's start"""
+    if resume is None:
+        return 0, None, None
+    loss, status = resume.loss.numpy(), resume.status.numpy()
+    if loss.shape != (B,) or status.shape != (B,):
+        raise ValueError("resume carries %d environments, the batch has %d" % (loss.size, B))
+    return int(resume.t0), loss, status
+
+
+class AmppiSimResult(collections.namedtuple("AmppiSimResult", "states actions costs omega inst_costs loss status n_run a_seq")):
+    """What BatchAMPPI.simulate returns; `t0`: the periods the episode has run so far (simulate(resume=) goes on from there)"""
+    t0 = 0
+
+
+class DualAmppiSimResult(collections.namedtuple("DualAmppiSimResult", "states actions costs omega bw inst_costs loss status n_run a_seq")):
+    """What BatchDualAMPPI.simulate returns; `t0` as AmppiSimResult's"""
+    t0 = 0

@@ -467,6 +467,78 @@ class BatchDualAMPPI(_BatchDual):
         self.ticks += T
         return torch.from_numpy(xs), torch.from_numpy(acts), torch.from_numpy(costs), torch.from_numpy(omega)
 
+    # -- run_pendulum_simulation(mpf=...)'s AMPPI loop / the Particle loop's crash and goal (simulations.py:124-160, 217-260) for every
+    # environment: the episode under the reference's rules; this branch has no warm-up
+    def simulate(self, states, n_periods, goal=None, goal_radius=None, stop_on_crash=False, plant_params=None, active=None, resume=None):
+        """run_episodes() under the reference's episode rules, in one C call (dust_amppi_dual_batch_simulate): the controller's
+        instantaneous cost of every new state is recorded and summed in fp32 into `loss`; `stop_on_crash` (Particle with_obstacle): a new
+        position on an occupied cell ends the environment with loss = inf, status 2; `goal` [ds] with `goal_radius` > 0: an environment
+        within the radius ends with status 1.  A stopped environment takes no further filter update and no tick; environments with
+        `resume.status != 0` are passed as inactive.  Period t draws under `prior_keys(_t + 1 + t)`; the roll is the constructor's
+        `roll`, which must be >= 1 here.
+        -> DualAmppiSimResult(states [T, B, ds], actions [T, B, da], costs [T, B, S], omega [T, B, S], bw [T, B], inst_costs [T, B], loss
+        [B], status [B], n_run [B], a_seq [B, H, da]) with the attribute t0; rows the call did not write - past n_run[b], inactive
+        environments - are NaN (n_run: -1).  Afterwards the noted update is, per environment, (actions[n_run - 1], states[n_run - 1]),
+        or the pair the environment came with when n_run <= 0."""
+        from ..inference.svmpc import _active
+        from ..models import CartPoleModel, SkidSteerRobot
+        from .amppi import DualAmppiSimResult, _sim_goal, _sim_resume
+
+        ctrl = self.controller
+        T, B = int(n_periods), self.n_envs
+        if not 1 <= T <= 4096:
+            raise ValueError("n_periods = %d outside [1, 4096]: one call runs one episode piece, chain a longer one" % T)
+        if self.roll < 1:
+            raise ValueError("simulate rolls every period: roll=%d, roll >= 1" % self.roll)
+        for model in (self.model, getattr(self.mpf.likelihood, "model", None)):
+            if isinstance(model, (SkidSteerRobot, CartPoleModel)):
+                raise NotImplementedError("simulate conditions the filters on the device: Pendulum and Particle (a %s pair runs tick())"
+                                          % type(model).__name__)
+        on = np.ones(B, bool) if active is None else np.array(_active(active, B), bool)
+        P = self.mpf._dev.P
+        if plant_params is not None:
+            plant_params = np.asarray(torch.as_tensor(plant_params, dtype=torch.float).numpy(), np.float32)
+            if plant_params.shape != (B, P):
+                raise ValueError("plant_params has shape %s, the plants read %s" % (plant_params.shape, (B, P)))
+        goal, goal_radius = _sim_goal(goal, goal_radius, ctrl.dim_s)
+        if stop_on_crash and not (getattr(self.model, "family", None) == "particle" and bool(self.model.with_obstacle)):
+            raise ValueError("stop_on_crash needs an occupancy map: Particle(with_obstacle=True)")
+        t0, loss, status = _sim_resume(resume, B)
+        if status is not None:
+            on = on & (status == 0)
+        self.model.params_dist = self.mpf.prior  # (what the context's configuration reads)
+        batch = ctrl._ensure_batch(self.model)
+        if ctrl._tf is not None:
+            batch.ctx.set_sigma_scale(ctrl._tf.scale)
+        st = torch.as_tensor(states, dtype=torch.float).reshape(B, -1).numpy()
+        mb = self._filters(st)
+        pend = self._pending
+        keys = np.array([self.prior_keys(self._t + 1 + t) for t in range(T)], np.uint64)
+        masked = active is not None or resume is not None
+        out = batch.dual_simulate(mb, st, T, None if pend is None else pend[0], shared_params=ctrl.params_sampling == "single",
+                                  mpf_steps=self.mpf_steps, mpf_bw=self.mpf_bw, seeds=keys, roll_steps=self.roll, plant_params=plant_params,
+                                  t0=t0, goal=goal, goal_radius=goal_radius, stop_on_crash=stop_on_crash, loss=loss, status=status,
+                                  active=on if masked else None)
+        # (a refused call consumes neither the keys nor the noted update)
+        xs, acts, costs, omega, bw, ic, loss, status, n_run, a_seq = out
+        a_last = np.zeros((B, acts.shape[2]), np.float32) if pend is None else pend[0].copy()
+        x_last = np.array(st, np.float32).reshape(B, -1).copy()
+        for e in range(B):
+            n = int(n_run[e])
+            if n > 0:  # (n <= 0: the environment keeps the pair it came with)
+                a_last[e], x_last[e] = acts[n - 1, e], xs[n - 1, e]
+        have = pend is not None or bool((n_run > 0).any())
+        self._t, self._pending = self._t + T, ((a_last, x_last) if have else None)
+        full = n_run == T
+        if (pend is not None or T > 1) and bool(full.any()):
+            self.last_bw = torch.from_numpy(bw[-1].copy())
+        if bool(full.any()):
+            self.last_costs = torch.from_numpy(costs[-1].copy())
+        self.ticks += T
+        res = DualAmppiSimResult(*(torch.from_numpy(np.ascontiguousarray(v)) for v in (xs, acts, costs, omega, bw, ic, loss, status, n_run, a_seq)))
+        res.t0 = t0 + T
+        return res
+
 
 class BatchDualSVMPC(_BatchDual):
     """The DuSt-MPC loop over `B = svmpc.n_envs` plants at once: a `BatchSVMPC` and B copies of one `MPF` - the deep copies of controller

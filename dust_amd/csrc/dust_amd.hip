@@ -1724,12 +1724,12 @@ static int episode_plant_check(const dust_ctx *c, const float *plant_params) {
   if (c->cfg.dim_p == 0 && plant_params) return fail(DUST_ERR_INVALID, "plant parameter rows without uncertain parameters (dim_p = 0)");
   return DUST_OK;
 }
-// dust_episode_rules against the batch's context and the caller's status words.  no_warm_up: the MultiDISCO loop has none; particle_map:
+// dust_episode_rules against the batch's context and the caller's status words.  no_warm_up: the MultiDISCO and AMPPI loops have none; particle_map:
 // the dual loop stops on the Particle map alone (the plain ticks also know the skid-steer navigation cost's)
 static int rules_check(const dust_ctx *c, const dust_episode_rules *r, size_t B, const unsigned char *active, const int *status, bool no_warm_up,
                        bool particle_map) {
   if (no_warm_up) {
-    if (r->warm_up != 0) return fail(DUST_ERR_INVALID, "warm_up = %d: the MultiDISCO branch of the reference's loops has no warm-up", r->warm_up);
+    if (r->warm_up != 0) return fail(DUST_ERR_INVALID, "warm_up = %d: the MultiDISCO / AMPPI branch of the reference's loops has no warm-up", r->warm_up);
     if (r->t0 < 0) return fail(DUST_ERR_INVALID, "t0 = %d: >= 0", r->t0);
   } else if (r->t0 < 0 || r->warm_up < 0) {
     return fail(DUST_ERR_INVALID, "t0 = %d, warm_up = %d: both are >= 0", r->t0, r->warm_up);
@@ -1934,41 +1934,56 @@ extern "C" int dust_amppi_batch_get_actions(dust_amppi_batch *b, float *actions)
 static constexpr size_t DUST_AMPPI_EPISODE_MAX_FLOATS = (size_t)1 << 28;
 // The records of an AMPPI episode, plain or dual (the plain one has no bandwidths): states | actions | costs | omega | bw, then the final a_seq
 struct AmppiRecords {
-  RecSection s, a, co, om, bw, q;
-  size_t n_rec;
-  AmppiRecords(const dust_ctx *c, size_t T, size_t B, bool costs, bool omega, bool bw_dev, bool a_seq) {
+  RecSection s, a, co, om, bw, ic, q;
+  size_t n_rec, words;  // words: where the rules' [B] loss | status | n_run lie
+  AmppiRecords(const dust_ctx *c, size_t T, size_t B, bool costs, bool omega, bool bw_dev, bool a_seq, bool rules = false) {
     EpisodeRecords lay(T, B);
     s = lay.add((size_t)c->ds);
     a = lay.add((size_t)c->da);
     co = lay.add((size_t)c->S, costs);
     om = lay.add((size_t)c->S, omega);
     bw = lay.add(1, bw_dev);
+    ic = lay.add(1, rules);  // the instantaneous costs [T][B]
     q = lay.per_call((size_t)c->D, a_seq);
+    words = lay.words(rules);
     n_rec = lay.total();
   }
-  // where period t writes: its rows of the sections, and the final sequence in the last period (AmppiEpisode's bw_out is the dual entry's)
+  // where period t writes: its rows of the sections, and the final sequence in the last period - under the rules (every_seq) in EVERY
+  // period: an environment's row ends as its last period's (AmppiEpisode's bw_out is the dual entry's)
   template <class Ep>
-  void period(Ep &ep, float *rec, size_t t) const {
+  void period(Ep &ep, float *rec, size_t t, bool every_seq = false) const {
     ep.states_out = s.at(rec, t);
     ep.actions_out = a.at(rec, t);
     ep.costs_out = co.at(rec, t);
     ep.omega_out = om.at(rec, t);
-    ep.a_seq_out = t + 1 == s.n ? q.at(rec, 0) : nullptr;
+    ep.a_seq_out = every_seq || t + 1 == s.n ? q.at(rec, 0) : nullptr;
   }
-  // what of the block read back goes to the caller: the rows of the call's environments
-  void out(const float *host, const unsigned char *active, float *states_out, float *actions_out, float *costs_out, float *omega_out, float *bw_out,
-           float *a_seq) const {
-    const RecSection *sec[] = {&s, &a, &co, &om, &bw, &q};
-    float *dst[] = {states_out, actions_out, costs_out, omega_out, bw_out, a_seq};
+  // what of the block read back goes to the caller: the rows of the call's environments (ran: the periods each ran, or NULL - all T)
+  void out(const float *host, const unsigned char *active, const int *ran, float *states_out, float *actions_out, float *costs_out, float *omega_out,
+           float *bw_out, float *inst_costs_out, float *a_seq) const {
+    const RecSection *sec[] = {&s, &a, &co, &om, &bw, &ic};
+    float *dst[] = {states_out, actions_out, costs_out, omega_out, bw_out, inst_costs_out};
     for (int k = 0; k < 6; ++k)
-      if (sec[k]->present) records_scatter(dst[k], host, *sec[k], active, nullptr);
+      if (sec[k]->present) records_scatter(dst[k], host, *sec[k], active, ran);
+    if (q.present) {
+      if (ran) env_rows_out(a_seq, host + q.off, q.B, q.row, active, ran);
+      else records_scatter(a_seq, host, q, active, nullptr);
+    }
   }
 };
-extern "C" int dust_amppi_batch_episode(dust_amppi_batch *b, const float *states, int n_periods, const float *params, int flags, int roll_steps,
-                                        const float *plant_params, const unsigned char *active, float *states_out, float *actions_out,
-                                        float *costs_out, float *omega_out, float *a_seq) {
+// rules (dust_amppi_batch_simulate; NULL: dust_amppi_batch_episode): the episode under the reference's rules - the non-SVMPC branch of
+// run_particle_episode / run_pendulum_simulation (simulations.py:217-260, 124-160), which has no warm-up.  The mask that is staged - always,
+// so that it is never NULL - is then the RUN MASK active[b] && status[b] == 0; the period kernels are the amppi_*_sim_period_kernel
+// instances, whose reducer clears an environment's byte in the period that stops it, so the later launches skip the environment.  The
+// rules' words [B] loss | status | n_run lie behind the records; the host queues T period launches whatever stops.
+static int amppi_episode_call(dust_amppi_batch *b, const float *states, int n_periods, const float *params, int flags, int roll_steps,
+                              const float *plant_params, const dust_episode_rules *rules, const unsigned char *active, float *states_out,
+                              float *actions_out, float *costs_out, float *omega_out, float *inst_costs_out, float *loss, int *status, int *n_run,
+                              float *a_seq) {
   TRY(batch_null(b));
   if (!states || !states_out || !actions_out) return fail(DUST_ERR_INVALID, "null argument");
+  if (rules && (!loss || !status || !n_run || !inst_costs_out))
+    return fail(DUST_ERR_INVALID, "null argument: loss, status, n_run and inst_costs_out are required");
   TRY(episode_periods_check(n_periods, "the queue of one call stays short on a shared device: split a longer episode"));
   if (roll_steps < 1) return fail(DUST_ERR_INVALID, "roll(steps = %d): steps >= 1", roll_steps);
   if (flags & ~DUST_AMPPI_PARAMS_SHARED)
@@ -1981,9 +1996,10 @@ extern "C" int dust_amppi_batch_episode(dust_amppi_batch *b, const float *states
   int mode = AMPPI_PARAMS_NONE, pts = 1;
   size_t prows = 0;
   TRY(amppi_params_mode(c, params != nullptr, flags, nullptr, &mode, &pts, &prows));
-  const size_t T = (size_t)n_periods, B = (size_t)b->B, S = (size_t)c->S, P = (size_t)c->cfg.dim_p;
+  const size_t T = (size_t)n_periods, B = (size_t)b->B, S = (size_t)c->S, P = (size_t)c->cfg.dim_p, D = (size_t)c->D;
+  if (rules) TRY(rules_check(c, rules, B, active, status, true, false));
   const size_t per = B * prows * P;  // parameter values of one period
-  const AmppiRecords lay(c, T, B, costs_out != nullptr, omega_out != nullptr, false, a_seq != nullptr);
+  AmppiRecords lay(c, T, B, costs_out != nullptr, omega_out != nullptr, false, a_seq != nullptr, rules != nullptr);
   const size_t n_rec = lay.n_rec;
   if (T * per > DUST_AMPPI_EPISODE_MAX_FLOATS)
     return fail(DUST_ERR_UNSUPPORTED, "%zu parameter values to stage for %d periods exceed %zu: split the episode into shorter calls", T * per, n_periods,
@@ -1996,18 +2012,28 @@ extern "C" int dust_amppi_batch_episode(dust_amppi_batch *b, const float *states
   memset(&nv, 0, sizeof nv);
   if (nav) TRY(skid_nav_args(c, nv));
   HIP_TRY(hipSetDevice(c->cfg.device));
+  // ---- who takes part: the caller's mask, or (rules) the run mask
+  std::vector<unsigned char> run(rules ? B : 0);
+  for (size_t e = 0; e < run.size(); ++e) run[e] = ((!active || active[e]) && status[e] == 0) ? 1 : 0;
+  const unsigned char *on = rules ? run.data() : active;
   // ---- room, then everything staged once
   if (prows) TRY(b->params.ensure(T * per));
   if (plant_params) TRY(b->plant.ensure(B * P));
   TRY(b->rec.ensure(n_rec));
   if (prows) TRY(h2d(c, b->params, params, T * per * sizeof(float)));
   if (plant_params) TRY(h2d(c, b->plant, plant_params, B * P * sizeof(float)));
-  TRY(b->in.stage(c, states, active));
+  TRY(b->in.stage(c, states, on));
+  if (rules) TRY(h2d(c, b->rec + lay.words, rules_words_in(loss, status, B).data(), 3 * B * sizeof(float)));
   HIP_TRY(hipMemsetAsync(b->ticket, 0, B * sizeof(unsigned int), c->stream));
   // ---- the periods
-  AmppiPeriodArgs kp;
+  AmppiSimPeriodArgs kp;  // (its first two members are the plain period's arguments)
   memset(&kp.ep, 0, sizeof kp.ep);  // (no filters: the dual episode's fields stay NULL)
-  batch_tick_args(b, mode, pts, prows, true, active, kp.k);
+  memset(&kp.ru, 0, sizeof kp.ru);
+  batch_tick_args(b, mode, pts, prows, true, on, kp.k);
+  if (rules) {
+    rules_fill(kp.ru, rules, c->ds, nullptr, b->rec + lay.words, B);
+    kp.ru.run = const_cast<unsigned char *>(kp.k.active);
+  }
   const long shift = (long)roll_steps * c->da;
   kp.ep.plant = plant_params ? b->plant.get() : nullptr;
   kp.ep.state = const_cast<float *>(b->in.states_dev());
@@ -2017,21 +2043,52 @@ extern "C" int dust_amppi_batch_episode(dust_amppi_batch *b, const float *states
   // (ahead of the chain: should a launch in its middle fail, the periods before it have run - sequences, stream positions and the device
   // state rows have advanced, no record comes back - and dust_amppi_batch_get_actions speaks of this call's environments)
   b->acts_valid = true;
-  if (active) b->last_active.assign(active, active + B);
+  if (on) b->last_active.assign(on, on + B);
   else b->last_active.clear();
   for (size_t t = 0; t < T; ++t) {
     kp.k.a.params = prows ? b->params.get() + t * per : nullptr;
-    lay.period(kp.ep, b->rec, t);
+    lay.period(kp.ep, b->rec, t, rules != nullptr);
+    kp.ru.costs_out = lay.ic.at(b->rec, t);
     Prof pr(c, DUST_K_AMPPI);
-    if (nav) HIP_TRY(launch_on(c->stream, false, &amppi_skid_nav_period_kernel, grid, AMPPI_THREADS, map_lds, AmppiNavPeriodArgs{kp.k, nv, kp.ep}));
-    else HIP_TRY(by_model(c, [&](auto M) { return launch_on(c->stream, false, &amppi_period_kernel<M()>, grid, AMPPI_THREADS, 0, kp); }));
+    if (rules) {
+      if (nav) HIP_TRY(launch_on(c->stream, false, &amppi_skid_nav_sim_period_kernel, grid, AMPPI_THREADS, map_lds, AmppiNavSimPeriodArgs{kp.k, nv, kp.ep, kp.ru}));
+      else HIP_TRY(by_model(c, [&](auto M) { return launch_on(c->stream, false, &amppi_sim_period_kernel<M()>, grid, AMPPI_THREADS, 0, kp); }));
+    } else if (nav) {
+      HIP_TRY(launch_on(c->stream, false, &amppi_skid_nav_period_kernel, grid, AMPPI_THREADS, map_lds, AmppiNavPeriodArgs{kp.k, nv, kp.ep}));
+    } else {
+      HIP_TRY(by_model(c, [&](auto M) { return launch_on(c->stream, false, &amppi_period_kernel<M()>, grid, AMPPI_THREADS, 0, AmppiPeriodArgs{kp.k, kp.ep}); }));
+    }
   }
-  // ---- the records come back once; the rows of inactive environments stay out of the caller's arrays
+  // ---- the records (and the words) come back once; the rows of inactive environments stay out of the caller's arrays
   std::vector<float> host(n_rec);
   HIP_TRY(hipMemcpyAsync(host.data(), b->rec, n_rec * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  lay.out(host.data(), active, states_out, actions_out, costs_out, omega_out, nullptr, a_seq);
+  if (!rules) {
+    lay.out(host.data(), active, nullptr, states_out, actions_out, costs_out, omega_out, nullptr, nullptr, a_seq);
+    return DUST_OK;
+  }
+  // the periods every environment ran - none where it did not take part: nothing of it is written past row ran[e] - 1
+  const std::vector<int> ran = rules_ran(host.data() + lay.words, B, run.data());
+  lay.out(host.data(), on, ran.data(), states_out, actions_out, costs_out, omega_out, nullptr, inst_costs_out, a_seq);
+  rules_words_out(host.data() + lay.words, B, active, ran.data(), loss, status, n_run);
   return DUST_OK;
+}
+
+extern "C" int dust_amppi_batch_episode(dust_amppi_batch *b, const float *states, int n_periods, const float *params, int flags, int roll_steps,
+                                        const float *plant_params, const unsigned char *active, float *states_out, float *actions_out,
+                                        float *costs_out, float *omega_out, float *a_seq) {
+  return amppi_episode_call(b, states, n_periods, params, flags, roll_steps, plant_params, nullptr, active, states_out, actions_out, costs_out,
+                            omega_out, nullptr, nullptr, nullptr, nullptr, a_seq);
+}
+
+// ... under the reference's episode rules: the cost, crash and goal
+extern "C" int dust_amppi_batch_simulate(dust_amppi_batch *b, const float *states, int n_periods, const float *params, int flags, int roll_steps,
+                                         const float *plant_params, const dust_episode_rules *rules, const unsigned char *active, float *states_out,
+                                         float *actions_out, float *costs_out, float *omega_out, float *inst_costs_out, float *loss, int *status,
+                                         int *n_run, float *a_seq) {
+  if (!rules) return fail(DUST_ERR_INVALID, "null rules");
+  return amppi_episode_call(b, states, n_periods, params, flags, roll_steps, plant_params, rules, active, states_out, actions_out, costs_out,
+                            omega_out, inst_costs_out, loss, status, n_run, a_seq);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

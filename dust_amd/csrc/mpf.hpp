@@ -2948,11 +2948,20 @@ extern "C" int dust_svmpc_dual_batch_simulate(dust_svmpc_batch *b, dust_mpf_batc
 // amppi_prior_period_kernel in the "extended" mode, amppi_period_kernel on b->params otherwise), whose reducer also conditions the
 // environment's MpfEnvIn row for period t + 1.  No host wait, event or copy lies between two periods; the call waits once, reads the
 // rows back and commits them as the SVMPC episode does (dual_episode_commit): the pair (a_{T-1}, x_T) is NOT folded in.
-extern "C" int dust_amppi_dual_batch_episode(dust_amppi_batch *b, dust_mpf_batch *mb, const float *states, const float *actions_prev, int n_periods,
-                                             int flags, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds, int roll_steps, const float *plant_params,
-                                             const unsigned char *active, float *states_out, float *actions_out, float *costs_out, float *omega_out,
-                                             float *bw_out, float *a_seq) {
+//
+// rules (dust_amppi_dual_batch_simulate; NULL: dust_amppi_dual_batch_episode): the loop under the reference's rules, as
+// svb_dual_episode_call runs the SVMPC pair under them - the run mask active[b] && status[b] == 0 is what every launch of the call takes
+// (Silverman's rule, the filters' update, the parameter staging of the single / sigma modes, the period kernel), the reducer of
+// amppi_sim_period_kernel / amppi_prior_sim_period_kernel clears an environment's byte in the period that stops it and leaves its pair
+// pending, and the filters' host rows are committed from n_run[b].  This branch of the reference has no warm-up.
+static int amppi_dual_episode_call(dust_amppi_batch *b, dust_mpf_batch *mb, const float *states, const float *actions_prev, int n_periods, int flags,
+                                   int mpf_steps, float mpf_bw, const uint64_t *prior_seeds, int roll_steps, const float *plant_params,
+                                   const dust_episode_rules *rules, const unsigned char *active, float *states_out, float *actions_out,
+                                   float *costs_out, float *omega_out, float *bw_out, float *inst_costs_out, float *loss, int *status, int *n_run,
+                                   float *a_seq) {
   if (!b || !mb || !states || !states_out || !actions_out) return fail(DUST_ERR_INVALID, "null argument");
+  if (rules && (!loss || !status || !n_run || !inst_costs_out))
+    return fail(DUST_ERR_INVALID, "null argument: loss, status, n_run and inst_costs_out are required");
   if (!prior_seeds) return fail(DUST_ERR_INVALID, "null argument: the draws from the filters' priors need prior_seeds [T][B]");
   TRY(episode_periods_check(n_periods, "the queue of one call stays short on a shared device: chain a longer episode"));
   if (mpf_steps < 0) return fail(DUST_ERR_INVALID, "bad step counts");
@@ -2964,6 +2973,7 @@ extern "C" int dust_amppi_dual_batch_episode(dust_amppi_batch *b, dust_mpf_batch
   dust_mpf *m = mb->m;
   TRY(amppi_check(c));
   TRY(episode_plant_check(c, plant_params));
+  if (rules) TRY(rules_check(c, rules, (size_t)b->B, active, status, true, true));
   TRY(dual_batch_pair_check(c, "AMPPI", b->B, mb));
   bool sigma, shared;
   TRY(amppi_dual_check(c, m, flags, &sigma, &shared));
@@ -2982,10 +2992,14 @@ extern "C" int dust_amppi_dual_batch_episode(dust_amppi_batch *b, dust_mpf_batch
   TRY(mpfb_limits(m, mb->B));
   TRY(mpfb_bw_check(mb, mpf_bw));
   const bool first = actions_prev != nullptr;  // period 0 has an update
-  if (first || n_periods > 1) TRY(mpfb_update_check(mb, first ? actions_prev : states, states, mpf_steps, active));
   const size_t T = (size_t)n_periods, B = (size_t)b->B, S = (size_t)c->S, P = (size_t)m->P;
+  // who takes part: the caller's mask, or (rules) the run mask - an environment that enters stopped does nothing, and is not checked
+  std::vector<unsigned char> run(rules ? B : 0);
+  for (size_t e = 0; e < run.size(); ++e) run[e] = ((!active || active[e]) && status[e] == 0) ? 1 : 0;
+  const unsigned char *on = rules ? run.data() : active;
+  if (first || n_periods > 1) TRY(mpfb_update_check(mb, first ? actions_prev : states, states, mpf_steps, on));
   const bool bw_dev = bw_out && !(mpf_bw > 0.f);  // Silverman's bandwidths are the device's to record
-  const AmppiRecords lay(c, T, B, costs_out != nullptr, omega_out != nullptr, bw_dev, a_seq != nullptr);
+  const AmppiRecords lay(c, T, B, costs_out != nullptr, omega_out != nullptr, bw_dev, a_seq != nullptr, rules != nullptr);
   const size_t n_rec = lay.n_rec;
   if (n_rec > DUST_AMPPI_EPISODE_MAX_FLOATS)
     return fail(DUST_ERR_UNSUPPORTED, "%zu record values for %d periods exceed %zu: split the episode into shorter calls (or leave costs / omega out)", n_rec,
@@ -2998,17 +3012,23 @@ extern "C" int dust_amppi_dual_batch_episode(dust_amppi_batch *b, dust_mpf_batch
   if (staged) TRY(b->params.ensure(B * prows * P));
   TRY(b->rec.ensure(n_rec));
   // ---- staged once
-  TRY(b->in.stage(c, states, active));
-  TRY(st.stage(c, states, actions_prev, mpf_steps, active, prior_seeds, plant_params));
+  TRY(b->in.stage(c, states, on));
+  TRY(st.stage(c, states, actions_prev, mpf_steps, on, prior_seeds, plant_params));
+  if (rules) TRY(h2d(c, b->rec + lay.words, rules_words_in(loss, status, B).data(), 3 * B * sizeof(float)));
   HIP_TRY(hipMemsetAsync(b->ticket, 0, B * sizeof(unsigned int), c->stream));
   if (first || n_periods > 1) serve_cancel_device(m->cfg.device);  // (as mpfb_enqueue, once for the call)
   // ---- the periods
   dust::MpfEnvIn *in_dev = st.in_dev();
-  const unsigned char *mask = b->in.mask_dev(active);
-  AmppiPriorPeriodArgs ka;
-  batch_tick_args(b, mode, pts, prows, true, active, ka.k);
+  const unsigned char *mask = b->in.mask_dev(on);
+  AmppiPriorSimPeriodArgs ka;  // (its first three members are the plain period's arguments)
+  batch_tick_args(b, mode, pts, prows, true, on, ka.k);
   dual_batch_prior(mb, nullptr, ka.pr);
   memset(&ka.ep, 0, sizeof ka.ep);
+  memset(&ka.ru, 0, sizeof ka.ru);
+  if (rules) {
+    rules_fill(ka.ru, rules, c->ds, nullptr, b->rec + lay.words, B);
+    ka.ru.run = const_cast<unsigned char *>(mask);
+  }
   const long shift = (long)roll_steps * c->da;
   ka.ep.plant = st.plant_dev(plant_params);
   ka.ep.state = const_cast<float *>(b->in.states_dev());
@@ -3016,7 +3036,7 @@ extern "C" int dust_amppi_dual_batch_episode(dust_amppi_batch *b, dust_mpf_batch
   ka.ep.in = in_dev;
   const dim3 grid((unsigned)((S + AMPPI_THREADS - 1) / AMPPI_THREADS), (unsigned)B);
   b->acts_valid = true;  // (ahead of the chain, as in dust_amppi_batch_episode)
-  if (active) b->last_active.assign(active, active + B);
+  if (on) b->last_active.assign(on, on + B);
   else b->last_active.clear();
   for (size_t t = 0; t < T; ++t) {
     const bool update = t > 0 || first;
@@ -3029,7 +3049,8 @@ extern "C" int dust_amppi_dual_batch_episode(dust_amppi_batch *b, dust_mpf_batch
       mb->n_launch++;
     }
     ka.pr.seeds = st.seeds_dev(t);
-    lay.period(ka.ep, b->rec, t);
+    lay.period(ka.ep, b->rec, t, rules != nullptr);
+    ka.ru.costs_out = lay.ic.at(b->rec, t);
     ka.ep.bw = bw_dev && update ? mb->bw.get() : nullptr;
     ka.ep.bw_out = lay.bw.at(b->rec, t);
     ka.ep.t0_add = update ? mpf_steps : 0;
@@ -3037,8 +3058,12 @@ extern "C" int dust_amppi_dual_batch_episode(dust_amppi_batch *b, dust_mpf_batch
     Prof pr(c, DUST_K_AMPPI);
     const hipError_t launched = by_model(c, [&](auto M) -> hipError_t {
       if constexpr (M() == DUST_MODEL_PENDULUM || M() == DUST_MODEL_PARTICLE) {
+        if (rules) {
+          if (staged) return launch_on(c->stream, false, &amppi_sim_period_kernel<M()>, grid, AMPPI_THREADS, 0, AmppiSimPeriodArgs{ka.k, ka.ep, ka.ru});
+          return launch_on(c->stream, false, &amppi_prior_sim_period_kernel<M()>, grid, AMPPI_THREADS, 0, ka);
+        }
         if (staged) return launch_on(c->stream, false, &amppi_period_kernel<M()>, grid, AMPPI_THREADS, 0, AmppiPeriodArgs{ka.k, ka.ep});
-        return launch_on(c->stream, false, &amppi_prior_period_kernel<M()>, grid, AMPPI_THREADS, 0, ka);
+        return launch_on(c->stream, false, &amppi_prior_period_kernel<M()>, grid, AMPPI_THREADS, 0, AmppiPriorPeriodArgs{ka.k, ka.pr, ka.ep});
       } else return hipErrorInvalidValue;  // (refused above)
     });
     HIP_TRY(launched);
@@ -3047,7 +3072,30 @@ extern "C" int dust_amppi_dual_batch_episode(dust_amppi_batch *b, dust_mpf_batch
   std::vector<float> host(n_rec);
   TRY(st.read_back(c, host, b->rec));
   TRY(st.wait(c));
-  lay.out(host.data(), active, states_out, actions_out, costs_out, omega_out, bw_out, a_seq);
-  st.commit(mpf_bw, active, bw_out);
+  // (rules) the periods every environment ran - none where it did not take part: nothing of it is written past row ran[e] - 1
+  const std::vector<int> ran_v = rules ? rules_ran(host.data() + lay.words, B, run.data()) : std::vector<int>();
+  const int *ran = rules ? ran_v.data() : nullptr;
+  lay.out(host.data(), on, ran, states_out, actions_out, costs_out, omega_out, bw_out, inst_costs_out, a_seq);
+  if (rules) rules_words_out(host.data() + lay.words, B, active, ran, loss, status, n_run);
+  st.commit(mpf_bw, on, bw_out, ran);
   return DUST_OK;
+}
+
+extern "C" int dust_amppi_dual_batch_episode(dust_amppi_batch *b, dust_mpf_batch *mb, const float *states, const float *actions_prev, int n_periods,
+                                             int flags, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds, int roll_steps, const float *plant_params,
+                                             const unsigned char *active, float *states_out, float *actions_out, float *costs_out, float *omega_out,
+                                             float *bw_out, float *a_seq) {
+  return amppi_dual_episode_call(b, mb, states, actions_prev, n_periods, flags, mpf_steps, mpf_bw, prior_seeds, roll_steps, plant_params, nullptr, active,
+                                 states_out, actions_out, costs_out, omega_out, bw_out, nullptr, nullptr, nullptr, nullptr, a_seq);
+}
+
+// ... under the reference's episode rules: the cost, crash and goal
+extern "C" int dust_amppi_dual_batch_simulate(dust_amppi_batch *b, dust_mpf_batch *mb, const float *states, const float *actions_prev, int n_periods,
+                                              int flags, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds, int roll_steps,
+                                              const float *plant_params, const dust_episode_rules *rules, const unsigned char *active, float *states_out,
+                                              float *actions_out, float *costs_out, float *omega_out, float *bw_out, float *inst_costs_out, float *loss,
+                                              int *status, int *n_run, float *a_seq) {
+  if (!rules) return fail(DUST_ERR_INVALID, "null rules");
+  return amppi_dual_episode_call(b, mb, states, actions_prev, n_periods, flags, mpf_steps, mpf_bw, prior_seeds, roll_steps, plant_params, rules, active,
+                                 states_out, actions_out, costs_out, omega_out, bw_out, inst_costs_out, loss, status, n_run, a_seq);
 }

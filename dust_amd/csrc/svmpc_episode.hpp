@@ -267,8 +267,9 @@ struct SvmpcRowsSimArgs {
 
 // controller.inst_cost_fn(state) of the plant's new state: the family's own instantaneous cost, the one the rollouts of phase C call, with
 // a zero action (Particle: w_obs collision() included; skid-steer / cart-pole: the quadratic state cost of svb_traj, NAV: plus the map term)
-template <int MODEL, bool NAV>
-__device__ __forceinline__ float svb_state_cost(const SvmpcBatchArgs &a, const float *x, const DevModel &map, const float w_obs) {
+// ARGS: as svb_coef's (the AMPPI periods under the rules, amppi_episode.hpp, hand it their environment's view)
+template <int MODEL, bool NAV, class ARGS>
+__device__ __forceinline__ float svb_state_cost(const ARGS &a, const float *x, const DevModel &map, const float w_obs) {
   if constexpr (MODEL == DUST_MODEL_PENDULUM || MODEL == DUST_MODEL_PARTICLE) {
     const float zero[2] = {0.f, 0.f};
     return inst_cost<MODEL>(a.dm, x, zero);
@@ -293,8 +294,8 @@ __device__ __forceinline__ float svb_state_cost(const SvmpcBatchArgs &a, const f
 }
 
 // obst_map.get_collisions(state[:2]) of the new position: Particle on its own map, the skid-steer navigation instance on its own
-template <int MODEL, bool NAV>
-__device__ __forceinline__ bool svb_crashed(const SvmpcBatchArgs &a, const float *x, const DevModel &map) {
+template <int MODEL, bool NAV, class ARGS>
+__device__ __forceinline__ bool svb_crashed(const ARGS &a, const float *x, const DevModel &map) {
   if constexpr (MODEL == DUST_MODEL_PARTICLE) return collision(a.dm, x[0], x[1]) != 0.f;
   else if constexpr (NAV) return collision(map, x[0], x[1]) != 0.f;
   else return false;  // (the host refuses the rule for every other family)

@@ -320,25 +320,60 @@ def _run_pendulum_baselines(init_state, init_policies, model_kwargs, experiment_
     return data
 
 
-def _run_particle_baselines(init_states, model, dyn_dist, ctrl, load, steps, plant_params):
-    """run_particle_episodes with a `BatchDISCO`: run_particle_episode's use_svmpc=False branch, step("argmax"), no warm-up"""
-    import numpy as np
-
-    B = ctrl.n_envs
-    state = torch.as_tensor(init_states, dtype=torch.float).reshape(B, -1).clone()
+def _particle_plants(model, sampling, log_space, plant_params, load, B):
+    """(rows, loaded rows) [B, P] of run_particle_episodes' plants: the true rows (None: nominal) and, with `load` != 0, the rows from
+    steps // 4 on - the mass grown by `load`"""
     rows = None if plant_params is None else torch.as_tensor(plant_params, dtype=torch.float).reshape(B, -1).clone()
     loaded = rows
     if load != 0:
-        names = tuple(model.uncertain_params or ()) if ctrl._sampling else ()
+        names = tuple(model.uncertain_params or ()) if sampling else ()
         if "mass" not in names:
             raise ValueError("load != 0 changes the plants' mass: 'mass' must be one of the model's uncertain parameters")
-        log_space = bool(ctrl._params_log_space)
         if rows is None:
             nominal = torch.tensor([float(model.params_dict[k]) for k in names])
             rows = (nominal.log() if log_space else nominal).repeat(B, 1)
         j = names.index("mass")
         loaded = rows.clone()
         loaded[:, j] = (rows[:, j].exp() + load).log() if log_space else rows[:, j] + load
+    return rows, loaded
+
+
+def _run_particle_amppi(init_states, model, ctrl, load, steps, plant_params, mpf, mpf_bw, mpf_steps, details):
+    """run_particle_episodes with a `BatchAMPPI`: run_particle_episode's use_svmpc=False branch under AMPPI - update_actions, the plant's
+    step, roll(1) per period, no warm-up - on `BatchAMPPI.simulate`, or with `mpf` the dual loop on `BatchDualAMPPI.simulate`"""
+    import numpy as np
+
+    B = ctrl.n_envs
+    state = torch.as_tensor(init_states, dtype=torch.float).reshape(B, -1).clone()
+    sampling = ctrl._tf is not None or bool(ctrl._sample_shape)
+    rows, loaded = _particle_plants(model, sampling, False, plant_params, load, B)
+    dual = None
+    if mpf is not None:
+        from ..controllers.dual import BatchDualAMPPI
+
+        dual = BatchDualAMPPI(ctrl, model, mpf, mpf_bw=mpf_bw, mpf_steps=mpf_steps)
+    cuts = sorted({0, steps} | ({min(steps // 4, steps)} if load != 0 else set()) | set(range(0, steps, 4096)))
+    crash = bool(model.with_obstacle)
+    res, ran = None, torch.zeros(B, dtype=torch.int32)
+    for lo, hi in zip(cuts[:-1], cuts[1:]):
+        plant = loaded if (load != 0 and lo >= steps // 4) else rows
+        kw = dict(goal=model.target, goal_radius=1.0, stop_on_crash=crash, plant_params=plant, resume=res)
+        res = dual.simulate(state, hi - lo, **kw) if dual is not None else ctrl.simulate(model, state, hi - lo, **kw)
+        n = res.n_run.numpy()
+        for b in np.nonzero(n > 0)[0]:
+            state[b] = res.states[n[b] - 1, b]
+        ran += res.n_run.clamp(min=0)
+    loss = res.loss if res is not None else torch.zeros(B)
+    return (loss, res.status if res is not None else torch.zeros(B, dtype=torch.int32), ran) if details else loss
+
+
+def _run_particle_baselines(init_states, model, dyn_dist, ctrl, load, steps, plant_params):
+    """run_particle_episodes with a `BatchDISCO`: run_particle_episode's use_svmpc=False branch, step("argmax"), no warm-up"""
+    import numpy as np
+
+    B = ctrl.n_envs
+    state = torch.as_tensor(init_states, dtype=torch.float).reshape(B, -1).clone()
+    rows, loaded = _particle_plants(model, ctrl._sampling, bool(ctrl._params_log_space), plant_params, load, B)
     cuts = sorted({0, steps} | ({min(steps // 4, steps)} if load != 0 else set()) | set(range(0, steps, 4096)))
     res = None
     for lo, hi in zip(cuts[:-1], cuts[1:]):
@@ -352,7 +387,7 @@ def _run_particle_baselines(init_states, model, dyn_dist, ctrl, load, steps, pla
 
 
 def run_particle_episodes(init_states, model, dyn_dist, batch_svmpc, warm_up=30, load=0, steps=400, plant_params=None, mpf=None, mpf_bw=None,
-                          mpf_steps=20, mpf_hyper=None):
+                          mpf_steps=20, mpf_hyper=None, *, details=False):
     """The batched twin of `run_particle_episode`: environment b of `batch_svmpc` (a `BatchSVMPC` over `model`) runs that episode from
     init_states[b] on the device (`BatchSVMPC.simulate`: warm-up, accumulated cost, crash - when the model has obstacles - and the goal
     `model.target` within 1.0), in pieces of at most 4096 periods.  The plants are deterministic and step under `plant_params` [B, P]
@@ -364,34 +399,32 @@ def run_particle_episodes(init_states, model, dyn_dist, batch_svmpc, warm_up=30,
     rows (`BatchDualSVMPC.set_filter_hyper`), one per environment; needs `mpf`, and `mpf_bw` must then be None.
     `batch_svmpc` may be a `BatchDISCO` instead: the episode is run_particle_episode's `use_svmpc=False` branch - every period forward +
     step("argmax"), no warm-up (`warm_up` is not read), no filter (`mpf` must be None) - on `BatchDISCO.simulate`.
+    Or a `BatchAMPPI`: that branch under AMPPI - update_actions, the plant's step, roll(1); `warm_up` and `dyn_dist` are not read (the
+    controller draws from `model.params_dist`) - on `BatchAMPPI.simulate`, and with `mpf` the dual loop on `BatchDualAMPPI.simulate`.
+    details=True (keyword only, a `BatchAMPPI`): -> (losses [B], statuses [B]: 0 running, 1 goal, 2 crash; periods run [B]).
     -> losses [B]: the cumulated cost of every environment, inf after a crash."""
     import numpy as np
 
+    from ..controllers.amppi import BatchAMPPI
     from ..controllers.disco import BatchDISCO
 
     if isinstance(batch_svmpc, BatchDISCO):
         if mpf is not None:
             raise ValueError("a BatchDISCO episode has no dynamics filter: mpf must be None")
         return _run_particle_baselines(init_states, model, dyn_dist, batch_svmpc, load, int(steps), plant_params)
+    if isinstance(batch_svmpc, BatchAMPPI):
+        if mpf_hyper is not None:
+            raise ValueError("per-environment filter rows are the DuSt-MPC loop's: mpf_hyper must be None under a BatchAMPPI")
+        return _run_particle_amppi(init_states, model, batch_svmpc, load, int(steps), plant_params, mpf, mpf_bw, mpf_steps, bool(details))
+    if details:
+        raise ValueError("details=True reports the statuses and periods of a BatchAMPPI episode")
     if mpf_hyper is not None and mpf is None:
         raise ValueError("mpf_hyper are the rows of the filters: pass the filter prototype as mpf")
     ctrl = batch_svmpc.likelihood.controller
     B = batch_svmpc.n_envs
     state = torch.as_tensor(init_states, dtype=torch.float).reshape(B, -1).clone()
     steps = int(steps)
-    rows = None if plant_params is None else torch.as_tensor(plant_params, dtype=torch.float).reshape(B, -1).clone()
-    loaded = rows
-    if load != 0:
-        names = tuple(model.uncertain_params or ()) if ctrl._sampling else ()
-        if "mass" not in names:
-            raise ValueError("load != 0 changes the plants' mass: 'mass' must be one of the model's uncertain parameters")
-        log_space = bool(ctrl._params_log_space)
-        if rows is None:
-            nominal = torch.tensor([float(model.params_dict[k]) for k in names])
-            rows = (nominal.log() if log_space else nominal).repeat(B, 1)
-        j = names.index("mass")
-        loaded = rows.clone()
-        loaded[:, j] = (rows[:, j].exp() + load).log() if log_space else rows[:, j] + load
+    rows, loaded = _particle_plants(model, ctrl._sampling, bool(ctrl._params_log_space), plant_params, load, B)
     cuts = sorted({0, steps} | ({min(steps // 4, steps)} if load != 0 else set()) | set(range(0, steps, 4096)))
     crash = bool(model.with_obstacle)
     res = None

@@ -1013,6 +1013,53 @@ int dust_svmpc_dual_batch_simulate(dust_svmpc_batch *batch, dust_mpf_batch *mpf,
                                    float *states_out, float *actions_out, float *pw_out, float *bw_out, float *costs_out /* [T][B] */,
                                    float *loss /* [B] in-out */, int *status /* [B] in-out */, int *n_run /* [B] out */, float *a_seq);
 
+/* ---- AMPPI episodes under the reference's episode rules (ABI 3, additive) ----
+ * dust_amppi_batch_simulate = dust_amppi_batch_episode under dust_episode_rules: the use_svmpc=False branch of run_particle_episode
+ * (simulations.py:217-260; particle_example.py:191-242) and the AMPPI loop of run_pendulum_simulation (simulations.py:124-160) for B
+ * environments in one call - what the per-period host loop (dust_amppi_batch_update, read back, a host plant, host cost and predicates,
+ * dust_amppi_batch_roll) does, without the host between two periods.  This branch of the reference has no warm-up: warm_up must be 0.
+ * Period t is ONE launch of amppi_sim_period_kernel / amppi_skid_nav_sim_period_kernel (amppi_episode.hpp, counted under DUST_K_AMPPI):
+ * the period of dust_amppi_batch_episode, and in the reducer workgroup of a running environment
+ *   cost     the family's own instantaneous cost (dust_svmpc_batch_simulate's) of the state AFTER the step, with a zero action:
+ *            inst_costs_out[t][b], and loss[b] += cost as an fp32 running sum in period order;
+ *   crash    stop_on_crash: the new position lies on an occupied cell of Particle's map or of the navigation cost's -> loss[b] = +inf,
+ *            status[b] = 2, stop;
+ *   goal     goal_radius > 0: the fp32 predicate of dust_svmpc_batch_simulate -> status[b] = 1, stop.  The crash rule wins.
+ * A stopping environment still rolls; it then clears its byte of a device-resident run mask (staged once as active[b] && status[b] == 0),
+ * which every later launch of the call takes.  The host queues T launches whatever stops and waits once.
+ * THE CONTRACT: afterwards environment b is where n_run[b] x (dust_amppi_batch_update on the recorded states, dust_amppi_batch_roll)
+ * would have left it, bit for bit, with the environment inactive from its stop on: sequences, stream positions, and the last period's
+ * actions through dust_amppi_batch_get_actions for every environment that ran a period.  Rows t >= n_run[b] of every record are NOT
+ * written, nor anything of an inactive environment; a_seq [B][H][da] (may be NULL) receives the sequence of the environment's LAST period,
+ * before its roll.  An environment entering with status != 0 does nothing: only n_run[b] = 0 is written.  loss / status are read at entry
+ * and rules->t0 is accepted, so calls chain (a mid-episode change of the true parameters is two chained calls).  With no goal and no crash
+ * rule the call computes, bit for bit, what dust_amppi_batch_episode computes.
+ * Refused before anything is staged or launched, the batch and the in-out arrays unchanged.  DUST_ERR_INVALID: what
+ * dust_amppi_batch_episode refuses; NULL rules, loss, status, n_run or inst_costs_out; warm_up != 0; t0 < 0; a goal or radius that is not
+ * finite; an entry status outside 0 .. 2.  DUST_ERR_UNSUPPORTED: stop_on_crash without an occupancy map (Particle's with_obstacle map, or
+ * the navigation cost's); every flag but DUST_AMPPI_PARAMS_SHARED.  The staging and record caps are dust_amppi_batch_episode's. */
+int dust_amppi_batch_simulate(dust_amppi_batch *batch, const float *states, int n_periods, const float *params, int flags, int roll_steps,
+                              const float *plant_params, const dust_episode_rules *rules, const unsigned char *active, float *states_out,
+                              float *actions_out, float *costs_out, float *omega_out, float *inst_costs_out /* [T][B] */,
+                              float *loss /* [B] in-out */, int *status /* [B] in-out */, int *n_run /* [B] out */, float *a_seq);
+/* dust_amppi_dual_batch_simulate = dust_amppi_dual_batch_episode under the same rules: the AMPPI loop of
+ * run_pendulum_simulation(mpf=...) (simulations.py:124-160) with its cost, and the Particle loop's crash and goal (217-260).  The run mask
+ * is taken by every launch of the call - Silverman's rule, the filters' update, the parameter staging of the single / sigma modes, the
+ * period kernels amppi_sim_period_kernel / amppi_prior_sim_period_kernel -, so a stopped environment takes no further update and no tick,
+ * and the filter-side launch count depends neither on B nor on the stops.  A stopping environment does not condition its filter row:
+ * (a_{n-1}, x_n) stays pending, exactly as behind a call's last period.
+ * THE CONTRACT: afterwards environment b is, on both sides, where n_run[b] dust_amppi_dual_batch_tick calls would have left it, with the
+ * environment inactive from its stop on: what dust_amppi_batch_simulate lists, and the filters' particles, prior bandwidths, optimiser
+ * slots, step counts, dust_mpf_batch_stats and host rows (committed per environment from n_run[b]).  bw_out[t][b] is 0 where no update
+ * ran.  Everything else - records, chaining, rules off - as dust_amppi_batch_simulate, against dust_amppi_dual_batch_episode.
+ * Refused as there, and what dust_amppi_dual_batch_episode refuses.  DUST_ERR_UNSUPPORTED: stop_on_crash without a Particle with_obstacle
+ * map; a skid-steer or cart-pole pair; every flag but DUST_AMPPI_PARAMS_SHARED. */
+int dust_amppi_dual_batch_simulate(dust_amppi_batch *batch, dust_mpf_batch *mpf, const float *states, const float *actions_prev, int n_periods,
+                                   int flags, int mpf_steps, float mpf_bw, const uint64_t *prior_seeds /* [T][B] */, int roll_steps,
+                                   const float *plant_params, const dust_episode_rules *rules, const unsigned char *active, float *states_out,
+                                   float *actions_out, float *costs_out, float *omega_out, float *bw_out, float *inst_costs_out /* [T][B] */,
+                                   float *loss /* [B] in-out */, int *status /* [B] in-out */, int *n_run /* [B] out */, float *a_seq);
+
 #ifdef __cplusplus
 }
 #endif
